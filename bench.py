@@ -2,7 +2,7 @@
 """Headline benchmark: short-axis FCN inference, batch = 64 synthetic 192x208
 slices per GPU, fp32 (BASELINE.json configs[1]).
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -10,6 +10,9 @@ A "step" = one forward of the hot path over one batch of 64 slices already
 resident in HBM, label map (int32) left in HBM.  One process per GPU, batch
 split only, no data-path collective (weak scaling); the process group is used
 for the barrier and the max-over-ranks time only.  Rank 0 prints ONE JSON line.
+A plain run sets up, warms up, times the K steps and prints that line; --full
+adds the side measurements (roofline, f32x3, other configs, cohort, CPU
+baseline, sustained loop).  --dump-outputs writes the last step's label map.
 """
 import argparse
 import json
@@ -22,6 +25,7 @@ sys.path.insert(0, ROOT)
 
 PEAK_FP32_MFMA_TFLOPS = 157.3      # MI355X_MICROARCH.md: 256 CU x 4 SIMD x 64 FLOP/clk x 2.4 GHz
 BATCH, H, W = 64, 192, 208
+DUMP_BYTES = 60 << 20              # --dump-outputs cap: under 64 MB, binary or decimal, header included
 
 
 def kernel_source_sha():
@@ -613,6 +617,13 @@ def main():
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--batch', type=int, default=BATCH)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last step returned to its caller, rank 0\'s label map [N,H,W] as '
+                         'float32, to DIR/pred.npy (at most %d MB: a larger batch is sampled by slice, default_rng(0))' % (DUMP_BYTES >> 20))
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline also take every side measurement: per-kernel survey and roofline, f32x3, other configs, '
+                         'cohort, CPU baseline, sustained loop (--no-*, --pmc-traffic, --cohort-subjects, --inflight-probe and '
+                         '--sustained-seconds shape those and matter only with --full). Without it a run times the headline steps only')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-f32x3-probe', action='store_true', help='skip the extra K steps in UKBB_PREC_F32X3 mode reported as out["f32x3"]')
     ap.add_argument('--pmc-traffic', default=None,
@@ -638,6 +649,16 @@ def main():
     args = ap.parse_args()
     if args.cpu_leg:
         return cpu_leg(args.cpu_leg)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    if not args.full:
+        # the plain run is what gets repeated for every change: set up, warm up, time the steps, print the line
+        asked = ['--' + o.replace('_', '-') for o in ('pmc_traffic', 'cohort_subjects', 'inflight_probe', 'sustained_seconds')
+                 if getattr(args, o) and getattr(args, o) != ap.get_default(o)]
+        if asked and os.environ.get('RANK', '0') == '0':
+            print('bench.py: %s ignored without --full (plain run: headline only)' % ', '.join(asked), file=sys.stderr, flush=True)
+        args.no_kernel_events = args.no_f32x3_probe = args.no_other_configs = args.no_cpu_baseline = True
+        args.cohort_subjects, args.sustained_seconds, args.inflight_probe = 0, 0.0, False
 
     import numpy as np
     import torch
@@ -740,6 +761,15 @@ def main():
         if world > 1:
             dist.destroy_process_group()
         sys.exit(3)
+
+    if args.dump_outputs and rank == 0:
+        # the int32 labels (0..n_class-1) are exact in float32; slices are sampled only when --batch pushes past the cap
+        labels = pred.cpu().numpy()
+        if labels.nbytes > DUMP_BYTES:
+            keep = np.sort(np.random.default_rng(0).choice(n, DUMP_BYTES // (labels[0].size * 4), replace=False))
+            labels = labels[keep]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, 'pred.npy'), labels.astype(np.float32))
 
     m3, m1 = fcn_macs_per_slice(arch, H, W)
     roofline = None

@@ -182,7 +182,7 @@ def test_bench_two_rank_launch_rehearsal():
     import json
     port = 29600 + os.getpid() % 300
     cmd = ['-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1', '--master-port', str(port),
-              os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '2', '--no-cpu-baseline', '--cohort-subjects', '24']
+              os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '2', '--full', '--no-cpu-baseline', '--cohort-subjects', '24']
     import torch
     one_gpu = torch.cuda.device_count() < 2
     r = _run(cmd + (['--rehearsal'] if one_gpu else []))

@@ -230,6 +230,14 @@ from ukbb_cardiac_amd import deploy_network as DN
 rank = int(os.environ['UKBB_SHARD_INDEX'])
 F, _ = DN.define_flags().parse(['--data_dir', sys.argv[1]])
 assert (F.num_shards, F.shard_index, F.work_stealing) == (2, rank, True)
+# both workers up before either takes a subject: on a loaded host worker 0 can start so late that worker 1 has already
+# stolen its whole share, and then it never reaches the forward it is meant to die in.  The rerun ('ok') finds the ready
+# files of the first launch and does not wait: harmless, it is only checked to be a no-op
+here = os.path.dirname(os.path.abspath(__file__))
+open(os.path.join(here, 'ready%d' % rank), 'w').close()
+t0 = time.time()
+while not all(os.path.exists(os.path.join(here, 'ready%d' % r)) for r in range(2)) and time.time() - t0 < 60:
+    time.sleep(0.01)
 calls = [0]
 def forward(batch):
     calls[0] += 1

@@ -5,7 +5,7 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 for r in 1 2 3; do
   for L in "$@"; do
     echo -n "$L: "
-    UKBB_FCN_LIB=$ROOT/$L python3 "$ROOT/bench.py" --no-cpu-baseline --no-other-configs --no-f32x3-probe --sustained-seconds 0 2>/dev/null | python3 -c "
+    UKBB_FCN_LIB=$ROOT/$L python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-other-configs --no-f32x3-probe --sustained-seconds 0 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=d['roofline_detail']['per_kernel_us']
