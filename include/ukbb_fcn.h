@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define UKBB_FCN_ABI_VERSION 7
+#define UKBB_FCN_ABI_VERSION 8
 #define UKBB_FCN_MAX_LEVEL 8
 
 #define UKBB_OK 0
@@ -58,6 +58,14 @@ extern "C" {
                                kind with an all-zero backward gate kernel + bias and the output kernel [W; 0]: exact
                                (that cell's hidden maps are 0 at every step), detected at create, its time steps are
                                skipped (round 6; weights.embed_unidirectional_lstm does the embedding). */
+#define UKBB_KIND_TEMPORAL_UNET 3 /* common/network_ao.py:67-114 Temporal_UNet: the UNet with every 3x3 unit a 3x3x3 conv3d
+                               (time stride 1, spatial strides (1,2,2) where the UNet has 2; TF 'SAME' zero padding at the
+                               WINDOW edges along time); fc = window length T (9); same_dim unused.
+                               weights [TF-recall]: per layer of the UNet order (encoder convs; per decoder level the transposed
+                               conv then its convs; conv_out) the kernel -- conv3d DHWIO [3,3,3,Cin,Cout], conv3d_transpose
+                               [3,3,3,Cout,Cin], conv_out [1,1,1,16,n_class] -- then gamma, beta, moving_mean, moving_variance
+                               (BN epsilon 1e-3), or the bias for conv_out.  fp32 only (set_precision(BF16) -> UKBB_EARCH).
+                               Use forward_seq / forward_cine. */
 
 /* Hyper-parameters of build_FCN / UNet as bound in common/train_network.py:174-195
  * and common/train_network_ao.py:268,275-284. */
@@ -140,6 +148,8 @@ int ukbb_fcn_forward(ukbb_fcn_handle *h, const float *image, int n, int height, 
 int ukbb_fcn_forward_host(ukbb_fcn_handle *h, const float *image, int n, int height, int width,
                           float *logits, float *prob, int32_t *pred);
 
+/* ---- UNet-LSTM (kind 2) and Temporal-UNet (kind 3): the windowed aortic models of demo_pipeline.py:116-117 ---------
+ * Both kinds take forward_seq / forward_cine below; forward / forward_host refuse them with UKBB_EINVAL. */
 /* ---- UNet-LSTM (kind 2): the default aortic model of demo_pipeline.py:116-117 -------------------
  * Reference call (common/deploy_network_ao.py:171-172):
  *   prob_idx = sess.run('prob:0', {'image:0': image_idx [N,T,X,Y,1], 'training:0': False})  -> [N,T,X,Y,C]
@@ -165,7 +175,14 @@ int ukbb_fcn_forward_seq(ukbb_fcn_handle *h, const float *image, int n_seq, int 
  *   every step's hidden maps 2*T*Wn*HW*16*e  +  hoisted gate pre-activations 2*F*HW*64*e  +  first-step hidden maps 2*F*HW*16*e
  *   +  cell state (2*F + Wn)*HW*16*4.
  * F = Wn = 100 frames of 256x256: 7.5 + 3.4 + 0.8 + 1.3 = 13.0 GB in fp32, 7.2 GB in bf16 -- several handles per GPU, or cines of
- * hundreds of frames, reach UKBB_ENOMEM on that, not on the U-Net (0.9 GB). */
+ * hundreds of frames, reach UKBB_ENOMEM on that, not on the U-Net (0.9 GB).
+ * Temporal-UNet (kind 3): the same call, bit for bit the same tiling arithmetic and corner cases, but each window runs the whole 3-D
+ * network on its T frames (its first layer reads them from `image` through a window -> frame table).  Windows run in chunks of Wc,
+ * in ascending order (results do not depend on Wc); device scratch the handle keeps, with HW = H*W, C = n_class and the standard
+ * filters 16..256 (the activations of every layer, 152*HW floats per frame):
+ *   Wc*T*(152 + C)*HW*4 bytes  +  tables (Wn*T + F*T)*4 + (T + F)*8 bytes,
+ * Wc = the largest number of windows that keeps the first term within 4e9 bytes (at least 1; UKBB_TEMPORAL_CHUNK_WINDOWS=n sets it):
+ * 256x256, T = 9, C = 3: Wc = 10, 3.66 GB, whatever the number of frames. */
 int ukbb_fcn_forward_cine(ukbb_fcn_handle *h, const float *image, int n_frames, int height, int width,
                           int weight_R, double weight_r, int time_step, float *prob, int32_t *pred, void *stream);
 
@@ -290,7 +307,8 @@ int ukbb_fcn_set_timing_kernel(ukbb_fcn_handle *h, int kernel);
 int ukbb_fcn_kernel_times(ukbb_fcn_handle *h, double *sum_ms, int64_t *count, int n, int reset);
 
 /* Copy an intermediate activation of the LAST forward to host (tests only).
- * Names: "conv0".."conv4" (level outputs), "g1".."g4" (FCN: out0's level-l slice applied to
+ * Names: the layer names of the plan ("conv0_0".."conv4_1", "up3_t".."up0_1": every conv's output map, NHWC;
+ * a Temporal-UNet's are per frame of the batch, [N*T][H][W][C]), "conv0".."conv4" (level outputs), "g1".."g4" (FCN: out0's level-l slice applied to
  * the squeezed map at low resolution, 64 channels),
  * "up3".."up0" (UNet decoder outputs).  Returns the number of floats, or a
  * negative error; with dst == NULL only the size is returned. */

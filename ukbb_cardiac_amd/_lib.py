@@ -12,7 +12,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('UKBB_FCN_LIB') or os.path.join(_HERE, 'libukbb_fcn.so')   # override: A/B builds of the kernels
-ABI_VERSION = 7
+ABI_VERSION = 8
 MAX_LEVEL = 8
 
 # every symbol include/ukbb_fcn.h declares

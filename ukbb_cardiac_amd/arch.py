@@ -9,22 +9,26 @@ hyper-parameters are hard-wired here.
 from dataclasses import dataclass, field
 from typing import List, Tuple
 
+import numpy as np
+
 KIND_FCN = 0    # common/network.py:170-230  build_FCN
 KIND_UNET = 1   # common/network_ao.py:18-64 UNet
 KIND_UNET_LSTM = 2   # common/network_ao.py:322-399 UNet_LSTM_Model with BiConv_LSTM (:255-319)
+KIND_TEMPORAL_UNET = 3   # common/network_ao.py:67-114 Temporal_UNet (conv3d 3x3x3 units, network.py:37-52)
 
 
 @dataclass(frozen=True)
 class LayerSpec:
     name: str
-    kernel_shape: Tuple[int, int, int, int]   # HWIO, or [kh,kw,Cout,Cin] for transposed
+    kernel_shape: Tuple[int, ...]             # HWIO, or [kh,kw,Cout,Cin] for transposed; kd > 1: DHWIO / [kd,kh,kw,Cout,Cin]
     has_bn: bool                              # conv+BN+ReLU unit (network.py:19-34)
     has_bias: bool                            # only the logits layer (network.py:229)
     transposed: bool = False
+    kd: int = 1                               # time taps (3: the Temporal-UNet's conv3d units, network.py:37-52)
 
     def n_floats(self) -> int:
-        kh, kw, a, b = self.kernel_shape
-        n = kh * kw * a * b
+        a, b = self.kernel_shape[-2:]
+        n = int(np.prod(self.kernel_shape))
         cout = a if self.transposed else b
         if self.has_bn:
             n += 4 * cout
@@ -42,7 +46,7 @@ class ModelArch:
     n_filter: Tuple[int, ...] = (16, 32, 64, 128, 256)
     n_block: Tuple[int, ...] = (2, 2, 3, 3, 3)
     same_dim: int = 32                    # KIND_UNET_LSTM: number of ConvLSTM hidden channels (n_hidden)
-    fc: int = 64                          # KIND_UNET_LSTM: number of unrolled time steps (n_step)
+    fc: int = 64                          # KIND_UNET_LSTM: number of unrolled time steps (n_step); KIND_TEMPORAL_UNET: window length T
 
     @property
     def n_hidden(self) -> int:
@@ -58,6 +62,21 @@ class ModelArch:
         L = []
         nf = self.n_filter
         cin = 1
+        if self.kind == KIND_TEMPORAL_UNET:
+            # network_ao.py:67-114: conv3d DHWIO [3,3,3,Cin,Cout], conv3d_transpose [3,3,3,Cout,Cin], conv_out [1,1,1,C,n_class]
+            # with bias [TF-recall]; same layer names and order as the UNet
+            for l in range(self.n_level):
+                for i in range(self.n_block[l]):
+                    L.append(LayerSpec('conv%d_%d' % (l, i), (3, 3, 3, cin, nf[l]), True, False, kd=3))
+                    cin = nf[l]
+            for l in range(self.n_level - 2, -1, -1):
+                L.append(LayerSpec('up%d_t' % l, (3, 3, 3, nf[l], nf[l + 1]), True, False, transposed=True, kd=3))
+                c = 2 * nf[l]
+                for i in range(self.n_block[l]):
+                    L.append(LayerSpec('up%d_%d' % (l, i), (3, 3, 3, c, nf[l]), True, False, kd=3))
+                    c = nf[l]
+            L.append(LayerSpec('logits', (1, 1, 1, nf[0], self.n_class), False, True, kd=1))
+            return L
         for l in range(self.n_level):
             for i in range(self.n_block[l]):
                 L.append(LayerSpec('conv%d_%d' % (l, i), (3, 3, cin, nf[l]), True, False))
@@ -91,12 +110,12 @@ class ModelArch:
         return sum(s.n_floats() for s in self.layer_specs())
 
     def macs_per_pixel_table(self):
-        """(name, kernel area, stride-accumulated downscale, Cin, Cout) rows used
+        """(name, kernel taps (kd*kh*kw), Cin, Cout, transposed) rows used
         by bench.py to compute the algorithmic FLOPs."""
         rows = []
         for s in self.layer_specs():
-            kh, kw, a, b = s.kernel_shape
-            rows.append((s.name, kh * kw, a, b, s.transposed))
+            a, b = s.kernel_shape[-2:]
+            rows.append((s.name, int(np.prod(s.kernel_shape[:-2])), a, b, s.transposed))
         return rows
 
 
@@ -111,12 +130,15 @@ MODELS = {
     'UNet_ao': ModelArch('UNet_ao', KIND_UNET, 3, n_block=(2, 2, 2, 2, 2)),
     # train_network_ao.py:292-298 with the demo model's name (...tw9_h16_bidir...): 9 steps, 16 hidden channels
     'UNet-LSTM_ao': ModelArch('UNet-LSTM_ao', KIND_UNET_LSTM, 3, n_block=(2, 2, 2, 2, 2), same_dim=16, fc=9),
+    # train_network_ao.py:39-42,268,275-284,307-312: num_filter 16, 5 levels, two units per level, window 2 * weight_R - 1 = 9
+    'Temporal-UNet_ao': ModelArch('Temporal-UNet_ao', KIND_TEMPORAL_UNET, 3, n_block=(2, 2, 2, 2, 2), fc=9),
 }
 
 
 def fcn_macs_per_slice(arch: ModelArch, H: int, W: int):
     """Algorithmic MACs per HxW slice, split (conv3x3, conv1x1); bilinear
-    upsample counted as 0."""
+    upsample counted as 0.  Temporal-UNet: per frame, the 3x3 part
+    counted with its three time taps (the window-edge taps TF multiplies with its zero padding included)."""
     m3 = m1 = 0
     h, w = H, W
     nf = arch.n_filter
@@ -144,4 +166,6 @@ def fcn_macs_per_slice(arch: ModelArch, H: int, W: int):
                 m3 += h * w * 9 * c * nf[l]
                 c = nf[l]
         m1 += H * W * nf[0] * arch.n_class
+    if arch.kind == KIND_TEMPORAL_UNET:
+        m3 *= 3
     return m3, m1

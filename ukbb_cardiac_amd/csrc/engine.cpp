@@ -62,8 +62,9 @@ constexpr float BN_EPS = 1e-3f;   // tf.layers.batch_normalization default
 struct HostLayer {            // one conv(+BN) unit with BN folded (fp32, same op order as
     std::string name;         // ukbb_cardiac_amd/weights.py fold_bn)
     int ks = 0, cin = 0, cout = 0;
+    int kd = 1;               // time taps (3: a conv3d / conv3d_transpose of the Temporal-UNet)
     bool transposed = false, relu = true;
-    std::vector<float> w;     // [ks][ks][cin][cout], scale folded in
+    std::vector<float> w;     // [kd][ks][ks][cin][cout], scale folded in
     std::vector<float> b;     // [cout]
 };
 
@@ -85,7 +86,8 @@ struct DevBuf {
     }
 };
 
-enum OpKind { OP_FIRST, OP_CONV, OP_HEAD, OP_TCONV, OP_LOGITS, OP_SQG, OP_SQG_MULTI, OP_TAIL, OP_STEM };
+enum OpKind { OP_FIRST, OP_CONV, OP_HEAD, OP_TCONV, OP_LOGITS, OP_SQG, OP_SQG_MULTI, OP_TAIL, OP_STEM,
+              OP_FIRST3D, OP_CONV3D, OP_TCONV3D };   // ..._3D: the Temporal-UNet's 3-D convolutions (kernels_conv3d.hip)
 
 struct Op {                    // one kernel launch of the plan
     OpKind kind;
@@ -104,6 +106,7 @@ struct Op {                    // one kernel launch of the plan
     double mfma_macs_per_image = -1; // issued to the matrix pipe; -1 = same as algorithmic
     double padded_macs_per_image = -1;   // ... including the slots of partly filled tiles / Winograd regions; -1 = same as mfma_macs_per_image
     const float *wpk = nullptr, *bias = nullptr;
+    const float *wph[4] = {nullptr, nullptr, nullptr, nullptr};   // OP_TCONV3D: packed weights of the 4 sub-pixel phases
 };
 
 }  // namespace
@@ -146,6 +149,11 @@ struct ukbb_fcn_handle {
     // lstm_gx / lstm_c1 / lstm_h1: per direction and FRAME (the x pass); lstm_c: per window; lstm_hall: per direction, step and window
     DevBuf lstm_gx, lstm_c1, lstm_h1, lstm_c, lstm_hall, lstm_probw, lstm_aux;   // lstm_aux: int maps / orders / double weights (raw bytes)
     long long lstm_aux_key = -1;              // which tables lstm_aux holds (shape-keyed, uploaded once per shape)
+
+    // Temporal-UNet (kind 3)
+    const int *t3d_map = nullptr;             // first layer: batch image n reads frame t3d_map[n] (NULL: frame n); set around run_plan
+    DevBuf t3d_aux, t3d_probw;                // forward_cine tables (window -> frame map, per-frame order, weights); softmax of a chunk's window frames
+    long long t3d_aux_key = -1;
 
     // image-slice streams (experiment UKBB_SPLIT, run_plan): consecutive conv ops run as S independent image ranges on S streams
     // side stream for kernels that only feed the head (sqg_l): fork after level l, join before the head
@@ -190,7 +198,7 @@ int upload(ukbb_fcn_handle *h, const std::string &key, const std::vector<float> 
 }
 
 // ---- architecture walk ---------------------------------------------------------
-struct Spec { std::string name; int ks, cin, cout; bool bn, bias, transposed; };
+struct Spec { std::string name; int ks, cin, cout; bool bn, bias, transposed; int kd = 1; };
 
 bool arch_specs(const ukbb_fcn_arch &a, std::vector<Spec> &out) {
     out.clear();
@@ -213,6 +221,21 @@ bool arch_specs(const ukbb_fcn_arch &a, std::vector<Spec> &out) {
         out.push_back({"out0", 1, a.same_dim * a.n_level, a.fc, true, false, false});
         out.push_back({"out1", 1, a.fc, a.fc, true, false, false});
         out.push_back({"logits", 1, a.fc, a.n_class, false, true, false});
+    } else if (a.kind == UKBB_KIND_TEMPORAL_UNET) {
+        // network_ao.py:67-114: every 3x3 unit of the U-Net as a 3x3x3 conv3d (DHWIO) / conv3d_transpose ([3,3,3,Cout,Cin])
+        // [TF-recall]; conv_out a 1x1x1 conv3d with bias
+        for (auto &s : out) s.kd = 3;
+        for (int l = a.n_level - 2; l >= 0; --l) {
+            snprintf(nm, sizeof nm, "up%d_t", l);
+            out.push_back({nm, 3, a.n_filter[l + 1], a.n_filter[l], true, false, true, 3});
+            int c = 2 * a.n_filter[l];
+            for (int i = 0; i < a.n_block[l]; ++i) {
+                snprintf(nm, sizeof nm, "up%d_%d", l, i);
+                out.push_back({nm, 3, c, a.n_filter[l], true, false, false, 3});
+                c = a.n_filter[l];
+            }
+        }
+        out.push_back({"logits", 1, a.n_filter[0], a.n_class, false, true, false, 1});
     } else if (a.kind == UKBB_KIND_UNET || a.kind == UKBB_KIND_UNET_LSTM) {
         for (int l = a.n_level - 2; l >= 0; --l) {
             snprintf(nm, sizeof nm, "up%d_t", l);
@@ -239,7 +262,7 @@ bool arch_specs(const ukbb_fcn_arch &a, std::vector<Spec> &out) {
 }
 
 size_t spec_floats(const Spec &s) {
-    size_t n = (size_t)s.ks * s.ks * s.cin * s.cout;
+    size_t n = (size_t)s.kd * s.ks * s.ks * s.cin * s.cout;
     if (s.bn) n += 4 * (size_t)s.cout;
     if (s.bias) n += s.cout;
     return n;
@@ -255,6 +278,9 @@ bool supported(const ukbb_fcn_arch &a, std::string &why) {
         if (a.n_class < 2 || a.n_class > 6) { why = "n_class must be in 2..6"; return false; }
     } else {
         if (a.n_class < 2 || a.n_class > 4) { why = "UNet n_class must be in 2..4"; return false; }
+        if (a.kind == UKBB_KIND_TEMPORAL_UNET) {
+            if (a.fc < 1 || a.fc > 31 || !(a.fc & 1)) { why = "the time window must be odd and < 32 frames"; return false; }
+        }
         if (a.kind == UKBB_KIND_UNET_LSTM) {
             if (a.same_dim != 16) { why = "ConvLSTM kernels are built for 16 hidden channels"; return false; }
             if (a.fc < 1 || a.fc > 31 || !(a.fc & 1)) { why = "the time window must be odd and < 32 steps"; return false; }
@@ -688,10 +714,124 @@ int add_tconv(ukbb_fcn_handle *h, const std::string &lname, int in0, int H, int 
     return UKBB_OK;
 }
 
+// ---- Temporal-UNet (kind 3): network_ao.py:67-114 on kernels_conv3d.hip -------------------------------------------
+// Weights of conv3d (kernel order (kt, ky, kx)) or of one sub-pixel phase (py, px) of conv3d_transpose (kt reversed: the
+// transposed conv reads in[t + 1 - kt], kernels_conv3d.hip), packed for conv3d_kernel; key "<layer>/pk3d<phase>".
+const float *ensure_packed3d(ukbb_fcn_handle *h, const HostLayer &L, int py, int px, int ny, int nx) {
+    char key[128];
+    snprintf(key, sizeof key, "%s/pk3d%d%d", L.name.c_str(), py, px);
+    if (const float *p = dev_ptr(h, key)) return p;
+    const int ntap = 3 * ny * nx, cpad = round_up(L.cout, 32);
+    std::vector<float> w((size_t)ntap * L.cin * L.cout), pk((size_t)ntap * L.cin * cpad);
+    for (int dti = 0; dti < 3; ++dti)
+        for (int jy = 0; jy < ny; ++jy)
+            for (int jx = 0; jx < nx; ++jx) {
+                const int kt = L.transposed ? 2 - dti : dti;
+                const int ky = L.transposed ? py + 2 * jy : jy, kx = L.transposed ? px + 2 * jx : jx;
+                const size_t src = (((size_t)kt * 3 + ky) * 3 + kx) * L.cin * L.cout, dst = (((size_t)dti * ny + jy) * nx + jx) * L.cin * L.cout;
+                std::copy(L.w.begin() + src, L.w.begin() + src + (size_t)L.cin * L.cout, w.begin() + dst);
+            }
+    pack_conv3d_weights(w.data(), ntap, L.cin, L.cout, cpad, pk.data());
+    if (upload(h, key, pk)) return nullptr;
+    return dev_ptr(h, key);
+}
+
+int add_conv3d(ukbb_fcn_handle *h, const std::string &lname, int in0, int in1, int H, int W, int stride, int *out_buf) {
+    const int li = h->layer_index.at(lname);
+    const HostLayer &L = h->layers[li];
+    Op op;
+    op.kind = L.cin == 1 ? OP_FIRST3D : OP_CONV3D; op.name = lname; op.layer = li; op.in0 = in0; op.in1 = in1;
+    op.H = H; op.W = W; op.stride = stride;
+    op.Ho = (H + stride - 1) / stride; op.Wo = (W + stride - 1) / stride;
+    op.pad_y = std::max((op.Ho - 1) * stride + 3 - H, 0) / 2;          // TF 'SAME' pad_before
+    op.pad_x = std::max((op.Wo - 1) * stride + 3 - W, 0) / 2;
+    if (op.kind == OP_FIRST3D && (stride != 1 || L.cout != 16)) { set_err("%s: the first 3-D layer must be 1 -> 16 channels, stride 1", lname.c_str()); return UKBB_EARCH; }
+    if (op.kind == OP_CONV3D && !(op.wpk = ensure_packed3d(h, L, 0, 0, 3, 3))) return UKBB_EDEVICE;
+    op.bias = dev_ptr(h, lname + "/bias");
+    op.out = new_act(h, lname, (size_t)op.Ho * op.Wo * L.cout, L.cout);
+    op.macs_per_image = (double)op.Ho * op.Wo * 27 * L.cin * L.cout;
+    // issued: the window's first and last frame skip one time tap (3T - 2 of 3T); the first layer runs on the vector ALU
+    const double tfrac = (3.0 * h->arch.fc - 2) / (3.0 * h->arch.fc);
+    op.mfma_macs_per_image = op.kind == OP_FIRST3D ? 0.0 : op.macs_per_image * tfrac;
+    if (op.kind == OP_CONV3D)                                          // ... in 32-pixel tiles x 32-row channel blocks
+        op.padded_macs_per_image = (double)((op.Ho * op.Wo + 31) / 32) * 32 * 27 * L.cin * round_up(L.cout, 32) * tfrac;
+    h->ops.push_back(op);
+    *out_buf = op.out;
+    return UKBB_OK;
+}
+
+int add_tconv3d(ukbb_fcn_handle *h, const std::string &lname, int in0, int H, int W, int *out_buf) {
+    const int li = h->layer_index.at(lname);
+    const HostLayer &L = h->layers[li];
+    Op op;
+    op.kind = OP_TCONV3D; op.name = lname; op.layer = li; op.in0 = in0;
+    op.H = H; op.W = W; op.Ho = 2 * H; op.Wo = 2 * W; op.stride = 1;
+    for (int ph = 0; ph < 4; ++ph) {
+        const int py = ph >> 1, px = ph & 1;
+        if (!(op.wph[ph] = ensure_packed3d(h, L, py, px, py ? 1 : 2, px ? 1 : 2))) return UKBB_EDEVICE;
+    }
+    op.bias = dev_ptr(h, lname + "/bias");
+    op.out = new_act(h, lname, (size_t)op.Ho * op.Wo * L.cout, L.cout);
+    op.macs_per_image = (double)H * W * 27 * L.cin * L.cout;           // 27 taps per INPUT pixel
+    const double tfrac = (3.0 * h->arch.fc - 2) / (3.0 * h->arch.fc);  // window-edge frames skip one time tap
+    op.mfma_macs_per_image = op.macs_per_image * tfrac;
+    op.padded_macs_per_image = (double)((H * W + 31) / 32) * 32 * 27 * L.cin * round_up(L.cout, 32) * tfrac;
+    h->ops.push_back(op);
+    *out_buf = op.out;
+    return UKBB_OK;
+}
+
+// the Temporal-UNet plan: encoder, decoder (transposed conv, concat([skip, up]), convs), conv_out + softmax / argmax (network_ao.py:67-114)
+int build_plan_t3d(ukbb_fcn_handle *h, int H, int W, int n_hint) {
+    const ukbb_fcn_arch &a = h->arch;
+    char nm[64];
+    int cur = -1, hh = H, ww = W;
+    std::vector<int> level_out(a.n_level), lh(a.n_level), lw(a.n_level);
+    for (int l = 0; l < a.n_level; ++l) {
+        for (int i = 0; i < a.n_block[l]; ++i) {
+            snprintf(nm, sizeof nm, "conv%d_%d", l, i);
+            const int stride = (l > 0 && i == 0) ? 2 : 1;
+            int rc = add_conv3d(h, nm, cur, -1, hh, ww, stride, &cur);
+            if (rc) return rc;
+            hh = (hh + stride - 1) / stride; ww = (ww + stride - 1) / stride;
+        }
+        level_out[l] = cur; lh[l] = hh; lw[l] = ww;
+    }
+    for (int l = a.n_level - 2; l >= 0; --l) {
+        snprintf(nm, sizeof nm, "up%d_t", l);
+        int up = -1;
+        int rc = add_tconv3d(h, nm, cur, lh[l + 1], lw[l + 1], &up);
+        if (rc) return rc;
+        cur = up;
+        for (int i = 0; i < a.n_block[l]; ++i) {
+            snprintf(nm, sizeof nm, "up%d_%d", l, i);
+            rc = i == 0 ? add_conv3d(h, nm, level_out[l], up, lh[l], lw[l], 1, &cur)    // concat([skip, up]) (network_ao.py:51 order)
+                        : add_conv3d(h, nm, cur, -1, lh[l], lw[l], 1, &cur);
+            if (rc) return rc;
+        }
+    }
+    Op lg;
+    lg.kind = OP_LOGITS; lg.name = "logits"; lg.layer = h->layer_index.at("logits"); lg.in0 = cur; lg.H = H; lg.W = W;
+    lg.macs_per_image = (double)H * W * a.n_filter[0] * a.n_class;
+    lg.mfma_macs_per_image = 0.0;
+    h->ops.push_back(lg);
+    h->plan_h = H; h->plan_w = W; h->plan_small = n_hint <= SMALL_BATCH; h->plan_n = n_hint;
+    h->plan_bfio = false;
+    h->split_first = -1; h->split_last = -2;
+    h->debug_first_op = 0; h->debug_last_op = 1 << 30;
+    for (auto e : h->ev) (void)hipEventDestroy(e);
+    h->ev.clear();
+    h->t_sum.assign(h->ops.size(), 0.0);
+    h->t_cnt.assign(h->ops.size(), 0);
+    h->ev_pending = false;
+    return UKBB_OK;
+}
+
 int build_plan(ukbb_fcn_handle *h, int H, int W, int n_hint) {
     h->ops.clear();
     h->act.clear(); h->act_per_image.clear(); h->act_name.clear(); h->act_ch.clear();
     h->cap_n = 0;
+    if (h->arch.kind == UKBB_KIND_TEMPORAL_UNET) return build_plan_t3d(h, H, W, n_hint);
     const ukbb_fcn_arch &a = h->arch;
     char nm[64];
     // encoder (network.py:179-189 / network_ao.py:31-41)
@@ -1154,6 +1294,36 @@ int run_plan(ukbb_fcn_handle *h, const float *image, int n, float *logits, float
                 e = launch_logits(la, s);
                 break;
             }
+            case OP_FIRST3D: {
+                Conv3dFirstArgs fa{image, h->t3d_map, dev_ptr(h, "conv0_0/w"), op.bias, actp(op.out), n, a.fc, op.H, op.W};
+                e = launch_conv3d_first(fa, s);
+                break;
+            }
+            case OP_CONV3D:
+            case OP_TCONV3D: {
+                const HostLayer &L = h->layers[op.layer];
+                Conv3dArgs ca{};
+                ca.in0 = actp(op.in0);
+                ca.in1 = op.in1 >= 0 ? actp(op.in1) : nullptr;
+                ca.C1 = op.in1 >= 0 ? h->act_ch[op.in1] : 0;
+                ca.C0 = L.cin - ca.C1;
+                ca.bias = op.bias; ca.out = actp(op.out);
+                ca.N = n; ca.T = a.fc; ca.Hi = op.H; ca.Wi = op.W;
+                ca.Ho = op.Ho; ca.Wo = op.Wo; ca.Cout = L.cout; ca.Cout_pad = round_up(L.cout, 32);
+                ca.relu = L.relu ? 1 : 0;
+                if (op.kind == OP_CONV3D) {
+                    ca.Hg = op.Ho; ca.Wg = op.Wo; ca.stride = op.stride; ca.up = 1;
+                    ca.oy = -op.pad_y; ca.ox = -op.pad_x; ca.jstep = 1;
+                    ca.nph = 1; ca.ph[0] = Conv3dPhase{op.wpk, 0, 0, 3, 3};
+                } else {
+                    ca.Hg = op.H; ca.Wg = op.W; ca.stride = 1; ca.up = 2;
+                    ca.oy = 0; ca.ox = 0; ca.jstep = -1;
+                    ca.nph = 4;
+                    for (int ph = 0; ph < 4; ++ph) ca.ph[ph] = Conv3dPhase{op.wph[ph], ph >> 1, ph & 1, (ph >> 1) ? 1 : 2, (ph & 1) ? 1 : 2};
+                }
+                e = launch_conv3d(ca, s);
+                break;
+            }
             default:
                 set_err("op kind %d not implemented", (int)op.kind);
                 return UKBB_EARCH;
@@ -1293,9 +1463,9 @@ ukbb_fcn_handle *ukbb_fcn_create(const ukbb_fcn_arch *arch, const float *weights
     const float *p = weights;
     for (auto &s : specs) {
         HostLayer L;
-        L.name = s.name; L.ks = s.ks; L.cin = s.cin; L.cout = s.cout; L.transposed = s.transposed;
+        L.name = s.name; L.ks = s.ks; L.kd = s.kd; L.cin = s.cin; L.cout = s.cout; L.transposed = s.transposed;
         L.relu = s.bn;
-        const size_t nk = (size_t)s.ks * s.ks * s.cin * s.cout;
+        const size_t nk = (size_t)s.kd * s.ks * s.ks * s.cin * s.cout;
         const float *k = p; p += nk;
         std::vector<float> scale(s.cout, 1.f);
         L.b.assign(s.cout, 0.f);
@@ -1314,8 +1484,8 @@ ukbb_fcn_handle *ukbb_fcn_create(const ukbb_fcn_arch *arch, const float *weights
         if (!s.transposed) {
             for (size_t i = 0; i < nk; ++i) L.w[i] = k[i] * scale[i % s.cout];
         } else {
-            // TF transposed filter [kh][kw][Cout][Cin] -> [kh][kw][Cin][Cout]
-            for (int t = 0; t < s.ks * s.ks; ++t)
+            // TF transposed filter [kd][kh][kw][Cout][Cin] -> [kd][kh][kw][Cin][Cout]
+            for (int t = 0; t < s.kd * s.ks * s.ks; ++t)
                 for (int co = 0; co < s.cout; ++co)
                     for (int ci = 0; ci < s.cin; ++ci)
                         L.w[((size_t)t * s.cin + ci) * s.cout + co] = k[((size_t)t * s.cout + co) * s.cin + ci] * scale[co];
@@ -1362,7 +1532,7 @@ ukbb_fcn_handle *ukbb_fcn_create(const ukbb_fcn_arch *arch, const float *weights
             v.assign(2 * 4 * 64 * 4, 0.f);       pack_rowmap_32x64(o0.w.data() + (size_t)32 * l * 64, 64, v.data());
             if (upload(h.get(), "sqg" + std::to_string(l) + "/w_g", v)) return nullptr;
         }
-    } else if (arch->kind == UKBB_KIND_UNET) {
+    } else if (arch->kind == UKBB_KIND_UNET || arch->kind == UKBB_KIND_TEMPORAL_UNET) {
         const HostLayer &lg = h->layers[h->layer_index.at("logits")];
         if (upload(h.get(), "logits/w", lg.w)) return nullptr;
     }
@@ -1385,6 +1555,7 @@ int ukbb_fcn_forward(ukbb_fcn_handle *h, const float *image, int n, int height, 
                      float *logits, float *prob, int32_t *pred, void *stream) {
     if (!h || !image) { set_err("forward: NULL argument"); return UKBB_EINVAL; }
     if (h->arch.kind == UKBB_KIND_UNET_LSTM) { set_err("forward: UNet-LSTM models take sequences: use ukbb_fcn_forward_seq / ukbb_fcn_forward_cine"); return UKBB_EINVAL; }
+    if (h->arch.kind == UKBB_KIND_TEMPORAL_UNET) { set_err("forward: Temporal-UNet models take sequences: use ukbb_fcn_forward_seq / ukbb_fcn_forward_cine"); return UKBB_EINVAL; }
     int rc = prepare(h, n, height, width);
     if (rc) return rc;
     return run_plan(h, image, n, logits, prob, pred, static_cast<hipStream_t>(stream));
@@ -1394,6 +1565,7 @@ int ukbb_fcn_forward_host(ukbb_fcn_handle *h, const float *image, int n, int hei
                           float *logits, float *prob, int32_t *pred) {
     if (!h || !image) { set_err("forward_host: NULL argument"); return UKBB_EINVAL; }
     if (h->arch.kind == UKBB_KIND_UNET_LSTM) { set_err("forward_host: UNet-LSTM models take sequences: use ukbb_fcn_forward_seq / ukbb_fcn_forward_cine"); return UKBB_EINVAL; }
+    if (h->arch.kind == UKBB_KIND_TEMPORAL_UNET) { set_err("forward_host: Temporal-UNet models take sequences: use ukbb_fcn_forward_seq / ukbb_fcn_forward_cine"); return UKBB_EINVAL; }
     int rc = prepare(h, n, height, width);
     if (rc) return rc;
     const size_t npix = (size_t)n * height * width, ncls = h->arch.n_class;
@@ -1495,6 +1667,126 @@ int run_bilstm(ukbb_fcn_handle *h, const float *feat, int NF, const int *d_map, 
     return UKBB_OK;
 }
 
+// host-side tables of the windowed deploy loop (deploy_network_ao.py:129-183) for F frames, windows of T = 2 * weight_R - 1 frames
+// centred on range(0, F, time_step): map[k * Wn + w] = frame of position k of window w (circular, :147-158), wk = the window
+// weights (:134-144), order[f * T ..] = the (w * T + k) terms frame f receives in the reference's order (-1 ends), wsum[f] their weights
+void cine_tables(int F, int T, int time_step, int weight_R, double weight_r, std::vector<int> &map, std::vector<int> &order,
+                 std::vector<double> &wk, std::vector<double> &wsum) {
+    const int rad = (T - 1) / 2, Wn = (F + time_step - 1) / time_step;
+    map.assign((size_t)T * Wn, 0); order.assign((size_t)F * T, -1);
+    wk.assign(T, 0.0); wsum.assign(F, 0.0);
+    for (int k = 0; k < T; ++k) {
+        const int d = k > rad ? k - rad : rad - k;
+        wk[k] = d <= weight_R ? pow(1.0 - (double)d / weight_R, weight_r) : 0.0;
+        for (int w = 0; w < Wn; ++w) {
+            int i = w * time_step - rad + k;
+            if (i < 0) i += F; else if (i >= F) i -= F;
+            map[(size_t)k * Wn + w] = i;
+        }
+    }
+    // `prob[..., idx] += p * w` with fancy indexing (:179-180) is prob[idx] = prob[idx] + p*w: when a frame occurs
+    // more than once in a window's idx (only if F < T) the LAST occurrence wins instead of accumulating
+    // (SURVEY.md App. C.7); same for `weight[..., idx] += w`.  So per window a frame receives at most one term.
+    std::vector<int> cnt(F, 0), last(F);
+    for (int w = 0; w < Wn; ++w) {                                          // the reference's loop over window centres
+        std::fill(last.begin(), last.end(), -1);
+        for (int k = 0; k < T; ++k) last[map[(size_t)k * Wn + w]] = k;
+        for (int k = 0; k < T; ++k) {                                       // frames in idx order; the order across frames is irrelevant
+            const int f = map[(size_t)k * Wn + w];
+            if (last[f] != k) continue;
+            order[(size_t)f * T + cnt[f]++] = w * T + k;
+            wsum[f] += wk[k];
+        }
+    }
+}
+
+// ---- Temporal-UNet (kind 3) --------------------------------------------------------------------------
+// n_seq windows of T frames through the 3-D plan: image n = window * T + t, outputs in the same [N][T] order
+int t3d_forward_seq(ukbb_fcn_handle *h, const float *image, int n_seq, int height, int width,
+                    float *logits, float *prob, int32_t *pred, hipStream_t s) {
+    if (n_seq < 1) { set_err("forward_seq: n_seq must be positive"); return UKBB_EINVAL; }
+    int rc = prepare(h, n_seq * h->arch.fc, height, width);
+    if (rc) return rc;
+    h->t3d_map = nullptr;
+    return run_plan(h, image, n_seq * h->arch.fc, logits, prob, pred, s);
+}
+
+// Windows per chunk of forward_cine: UKBB_TEMPORAL_CHUNK_WINDOWS=n (tests force small chunks with it), else as many as fit
+// T3D_CHUNK_BYTES of activations + window probabilities (at least one)
+constexpr double T3D_CHUNK_BYTES = 4.0e9;
+
+int t3d_chunk_windows(const ukbb_fcn_handle *h, int Wn, size_t HW) {
+    if (const char *e = getenv("UKBB_TEMPORAL_CHUNK_WINDOWS")) { const int v = atoi(e); if (v >= 1) return std::min(v, Wn); }
+    size_t per_frame = HW * h->arch.n_class;
+    for (size_t i = 0; i < h->act.size(); ++i) per_frame += h->act_per_image[i];
+    const double per_window = (double)per_frame * sizeof(float) * h->arch.fc;
+    return std::max(1, std::min(Wn, (int)(T3D_CHUNK_BYTES / per_window)));
+}
+
+// The windowed deploy loop (deploy_network_ao.py:129-183) for one slice position: every window runs the whole 3-D network
+// on its T frames (gathered from the cine by the first layer through the window -> frame table); windows go in chunks, in
+// ascending order, and each chunk's softmax maps are added into prob by t3d_tile_kernel in the reference's order -- the
+// result does not depend on the chunk size.
+int t3d_forward_cine(ukbb_fcn_handle *h, const float *image, int F, int height, int width,
+                     int weight_R, double weight_r, int time_step, float *prob, int32_t *pred, hipStream_t s) {
+    const int T = h->arch.fc, C = h->arch.n_class;
+    if (!prob) { set_err("forward_cine: prob must not be NULL"); return UKBB_EINVAL; }
+    if (2 * weight_R - 1 != T) { set_err("forward_cine: time window 2*weight_R-1 = %d, the model is built for %d frames", 2 * weight_R - 1, T); return UKBB_EINVAL; }
+    if (time_step < 1) { set_err("forward_cine: time_step must be >= 1 (got %d)", time_step); return UKBB_EINVAL; }
+    const int rad = (T - 1) / 2;
+    if (F < rad || F < 1) { set_err("forward_cine: %d frames, the circular window of radius %d needs at least %d (the reference raises IndexError)", F, rad, rad > 1 ? rad : 1); return UKBB_EINVAL; }
+    int rc = prepare(h, T, height, width);                                 // the plan (its per-frame workspace sizes the chunks)
+    if (rc) return rc;
+    const size_t HW = (size_t)height * width;
+    const int Wn = (F + time_step - 1) / time_step;
+    const int cw = t3d_chunk_windows(h, Wn, HW);
+    rc = prepare(h, cw * T, height, width);
+    if (rc) return rc;
+    std::vector<int> map, order;
+    std::vector<double> wk, wsum;
+    cine_tables(F, T, time_step, weight_R, weight_r, map, order, wk, wsum);
+    std::vector<int> fmap((size_t)Wn * T);                                  // window-major: batch image (w - w0) * T + k reads frame fmap[w * T + k]
+    for (int w = 0; w < Wn; ++w)
+        for (int k = 0; k < T; ++k) fmap[(size_t)w * T + k] = map[(size_t)k * Wn + w];
+    const size_t b_map = fmap.size() * sizeof(int), b_ord = order.size() * sizeof(int);
+    const size_t off_ord = (b_map + 7) / 8 * 8, off_wk = (off_ord + b_ord + 7) / 8 * 8, off_ws = off_wk + T * sizeof(double);
+    const size_t total = off_ws + F * sizeof(double);
+    long long wr_bits;
+    memcpy(&wr_bits, &weight_r, sizeof wr_bits);
+    const long long key = (((((long long)F << 8) | T) * 1000003ll + time_step) * 1000003ll) ^ wr_bits;
+    if (h->t3d_aux_key != key) {                                             // first call for this shape: upload (blocking)
+        HIP_TRY(hipStreamSynchronize(s), UKBB_EDEVICE);
+        HIP_TRY(h->t3d_aux.ensure((total + 3) / 4), UKBB_ENOMEM);
+        char *aux0 = reinterpret_cast<char *>(h->t3d_aux.p);
+        HIP_TRY(hipMemcpy(aux0, fmap.data(), b_map, hipMemcpyHostToDevice), UKBB_EDEVICE);
+        HIP_TRY(hipMemcpy(aux0 + off_ord, order.data(), b_ord, hipMemcpyHostToDevice), UKBB_EDEVICE);
+        HIP_TRY(hipMemcpy(aux0 + off_wk, wk.data(), T * sizeof(double), hipMemcpyHostToDevice), UKBB_EDEVICE);
+        HIP_TRY(hipMemcpy(aux0 + off_ws, wsum.data(), F * sizeof(double), hipMemcpyHostToDevice), UKBB_EDEVICE);
+        h->t3d_aux_key = key;
+    }
+    if (h->t3d_probw.n < (size_t)cw * T * HW * C) HIP_TRY(hipStreamSynchronize(s), UKBB_EDEVICE);   // the old buffer may still be read
+    HIP_TRY(h->t3d_probw.ensure((size_t)cw * T * HW * C), UKBB_ENOMEM);
+    const char *aux = reinterpret_cast<const char *>(h->t3d_aux.p);
+    const int *d_fmap = reinterpret_cast<const int *>(aux);
+    for (int w0 = 0; w0 < Wn; w0 += cw) {
+        const int nw = std::min(cw, Wn - w0);
+        h->t3d_map = d_fmap + (size_t)w0 * T;
+        rc = run_plan(h, image, nw * T, nullptr, h->t3d_probw.p, nullptr, s);
+        h->t3d_map = nullptr;
+        if (rc) return rc;
+        T3dTileArgs ta{};
+        ta.probw = h->t3d_probw.p;
+        ta.order = reinterpret_cast<const int *>(aux + off_ord);
+        ta.wk = reinterpret_cast<const double *>(aux + off_wk); ta.wsum = reinterpret_cast<const double *>(aux + off_ws);
+        ta.prob = prob; ta.pred = pred;
+        ta.F = F; ta.K = T; ta.HW = (int)HW; ta.C = C; ta.w0 = w0; ta.w1 = w0 + nw;
+        ta.first = w0 == 0; ta.last = w0 + nw == Wn;
+        hipError_t e = launch_t3d_tile(ta, s);
+        if (e != hipSuccess) { set_err("tiling kernel launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
+    }
+    return UKBB_OK;
+}
+
 int lstm_common_checks(ukbb_fcn_handle *h, const float *image, const char *what) {
     if (!h || !image) { set_err("%s: NULL argument", what); return UKBB_EINVAL; }
     if (h->arch.kind != UKBB_KIND_UNET_LSTM) { set_err("%s: the model is not a UNet-LSTM", what); return UKBB_EINVAL; }
@@ -1505,6 +1797,8 @@ int lstm_common_checks(ukbb_fcn_handle *h, const float *image, const char *what)
 
 int ukbb_fcn_forward_seq(ukbb_fcn_handle *h, const float *image, int n_seq, int height, int width,
                          float *logits, float *prob, int32_t *pred, void *stream) {
+    if (h && image && h->arch.kind == UKBB_KIND_TEMPORAL_UNET)
+        return t3d_forward_seq(h, image, n_seq, height, width, logits, prob, pred, static_cast<hipStream_t>(stream));
     int rc = lstm_common_checks(h, image, "forward_seq");
     if (rc) return rc;
     const int T = h->arch.fc, C = h->arch.n_class;
@@ -1558,6 +1852,8 @@ int ukbb_fcn_forward_seq(ukbb_fcn_handle *h, const float *image, int n_seq, int 
 
 int ukbb_fcn_forward_cine(ukbb_fcn_handle *h, const float *image, int n_frames, int height, int width,
                           int weight_R, double weight_r, int time_step, float *prob, int32_t *pred, void *stream) {
+    if (h && image && h->arch.kind == UKBB_KIND_TEMPORAL_UNET)
+        return t3d_forward_cine(h, image, n_frames, height, width, weight_R, weight_r, time_step, prob, pred, static_cast<hipStream_t>(stream));
     int rc = lstm_common_checks(h, image, "forward_cine");
     if (rc) return rc;
     const int T = h->arch.fc, C = h->arch.n_class, F = n_frames;
@@ -1575,32 +1871,9 @@ int ukbb_fcn_forward_cine(ukbb_fcn_handle *h, const float *image, int n_frames, 
     if (rc) return rc;
     const size_t HW = (size_t)height * width;
     const int Wn = (F + time_step - 1) / time_step;                         // window centres range(0, F, time_step) (:147)
-    // host-side tables: window maps (deploy_network_ao.py:147-158), weights (:134-144), per-frame order + weight sums
-    std::vector<int> map((size_t)T * Wn), order((size_t)F * T, -1);
-    std::vector<double> wk(T), wsum(F, 0.0);
-    for (int k = 0; k < T; ++k) {
-        const int d = k > rad ? k - rad : rad - k;
-        wk[k] = d <= weight_R ? pow(1.0 - (double)d / weight_R, weight_r) : 0.0;
-        for (int w = 0; w < Wn; ++w) {
-            int i = w * time_step - rad + k;
-            if (i < 0) i += F; else if (i >= F) i -= F;
-            map[(size_t)k * Wn + w] = i;
-        }
-    }
-    // `prob[..., idx] += p * w` with fancy indexing (:179-180) is prob[idx] = prob[idx] + p*w: when a frame occurs
-    // more than once in a window's idx (only if F < T) the LAST occurrence wins instead of accumulating
-    // (SURVEY.md App. C.7); same for `weight[..., idx] += w`.  So per window a frame receives at most one term.
-    std::vector<int> cnt(F, 0), last(F);
-    for (int w = 0; w < Wn; ++w) {                                          // the reference's loop over window centres
-        std::fill(last.begin(), last.end(), -1);
-        for (int k = 0; k < T; ++k) last[map[(size_t)k * Wn + w]] = k;
-        for (int k = 0; k < T; ++k) {                                       // frames in idx order; the order across frames is irrelevant
-            const int f = map[(size_t)k * Wn + w];
-            if (last[f] != k) continue;
-            order[(size_t)f * T + cnt[f]++] = w * T + k;
-            wsum[f] += wk[k];
-        }
-    }
+    std::vector<int> map, order;
+    std::vector<double> wk, wsum;
+    cine_tables(F, T, time_step, weight_R, weight_r, map, order, wk, wsum);
     const size_t b_map = map.size() * sizeof(int), b_ord = order.size() * sizeof(int);
     const size_t off_ord = (b_map + 7) / 8 * 8, off_wk = (off_ord + b_ord + 7) / 8 * 8, off_ws = off_wk + T * sizeof(double);
     const size_t total = off_ws + F * sizeof(double);
@@ -1668,6 +1941,10 @@ double ukbb_fcn_kernel_mfma_macs_issued(const ukbb_fcn_handle *h, int i) {
 
 int ukbb_fcn_set_precision(ukbb_fcn_handle *h, int precision) {
     if (!h || (precision != UKBB_PREC_FP32 && precision != UKBB_PREC_BF16 && precision != UKBB_PREC_F32X3)) { set_err("set_precision: bad argument"); return UKBB_EINVAL; }
+    if (h->arch.kind == UKBB_KIND_TEMPORAL_UNET && precision == UKBB_PREC_BF16) {
+        set_err("set_precision: the Temporal-UNet's 3-D convolutions are built for fp32 only (no bf16 plan)");
+        return UKBB_EARCH;
+    }
     if (precision != h->precision) {
         if (hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { set_err("set_precision: device sync failed"); return UKBB_EDEVICE; }
         h->precision = precision;

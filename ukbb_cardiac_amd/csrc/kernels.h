@@ -334,4 +334,49 @@ struct LstmTileArgs {       // per-(window, step) outputs + the weighted tiling 
 };
 hipError_t launch_lstm_tile(const LstmTileArgs &a, hipStream_t s);
 
+// ---- 3-D convolutions of the aortic Temporal-UNet (network_ao.py:67-114), kernels_conv3d.hip ----
+struct Conv3dPhase {        // one sub-pixel phase of a transposed conv (the whole conv: one phase at (0, 0))
+    const float *wpk;       // packed A fragments (pack_conv3d_weights) of the taps this phase reads
+    int py, px;             // output pixel = (up * gy + py, up * gx + px)
+    int ny, nx;             // spatial taps along y / x
+};
+struct Conv3dArgs {         // 3x3x3 conv (+ folded BN + ReLU) over windows of T frames: image n = window * T + t
+    const float *in0, *in1; // NHWC sources [N][Hi][Wi][C0] and (skip concat second source, or NULL) [N][Hi][Wi][C1]
+    int C0, C1;             // multiples of 8
+    const float *bias;      // [Cout]
+    float *out;             // [N][Ho][Wo][Cout]
+    int N, T, Hi, Wi;
+    int Hg, Wg;             // output grid the launch iterates (per phase)
+    int Ho, Wo, Cout, Cout_pad;   // stored map; Cout_pad = Cout rounded up to the MFMA's 32 rows
+    int stride, up;         // input row = gy * stride + oy + j * jstep; output row = gy * up + py
+    int oy, ox, jstep;      // conv: -pad_before, -pad_before, +1; transposed conv: 0, 0, -1
+    int relu;
+    int nph;                // phases (blockIdx.y): 1 or 4
+    Conv3dPhase ph[4];
+};
+hipError_t launch_conv3d(const Conv3dArgs &a, hipStream_t s);
+void pack_conv3d_weights(const float *w /*[ntap][cin][cout]*/, int ntap, int cin, int cout, int cout_pad, float *dst);
+
+struct Conv3dFirstArgs {    // first layer, C_in = 1 -> 16, 3x3x3, stride 1 (+ folded BN + ReLU)
+    const float *image;     // frames [.][H][W]
+    const int *map;         // image n of the batch reads frame map[n] (NULL: frame n)
+    const float *w;         // [27][16] folded, taps in (kt, ky, kx) order
+    const float *bias;      // [16]
+    float *out;             // [N][H][W][16]
+    int N, T, H, W;
+};
+hipError_t launch_conv3d_first(const Conv3dFirstArgs &a, hipStream_t s);
+
+struct T3dTileArgs {        // weighted circular tiling (deploy_network_ao.py:176-183) of the windows [w0, w1) of a cine
+    const float *probw;     // [(w1 - w0) * K][HW][C]: softmax of each window frame
+    const int *order;       // [F][K]: contributing (window w, position k) pairs, packed w*K + k, ascending w, -1 ends the list
+    const double *wk;       // [K] window weights
+    const double *wsum;     // [F] accumulated weight per frame
+    float *prob;            // [F][HW][C]: the accumulator between chunks, the result after the last
+    int32_t *pred;          // [F][HW] (last chunk)
+    int F, K, HW, C, w0, w1;
+    int first, last;        // first chunk: start from 0; last chunk: prob /= weight, argmax
+};
+hipError_t launch_t3d_tile(const T3dTileArgs &a, hipStream_t s);
+
 }  // namespace ukbb

@@ -4,10 +4,10 @@ segmentation) on the MI355X HIP engine.
 
 Command line as in ``demo_pipeline.py:116-117``.  Implemented: ``--model UNet``
 (frame-wise 2-D U-Net, ``deploy_network_ao.py:111-128``) in sequence and ED/ES
-mode, and the reference's default ``--model UNet-LSTM`` (U-Net features +
+mode, the reference's default ``--model UNet-LSTM`` (U-Net features +
 bidirectional ConvLSTM over circular 9-frame windows with weighted tiling,
-``:129-183``) in sequence mode, any ``--time_step``.  ``Temporal-UNet`` is not
-built and is refused with a clear message rather than silently replaced.
+``:129-183``) and ``--model Temporal-UNet`` (3-D convolutions over the same
+windows, ``network_ao.py:67-114``; fp32 only) in sequence mode, any ``--time_step``.
 
 Output: ``seg_ao.nii.gz`` int32 with the input's affine and pixdim (``:189-196``).
 """
@@ -81,11 +81,13 @@ def _pp(central_pp, data, log=print):
 
 
 def run(FLAGS, forward, log=print, cine_forward=None, engine=None):
-    """``forward`` stands for the frame-wise sess.run ('UNet'); ``cine_forward`` for the windowed one ('UNet-LSTM').
-    With ``engine`` (and --device_preproc, --z_score) float32 UNet-LSTM sequences take device_pipeline.aortic_lstm_sequence_device."""
-    if FLAGS.model == 'Temporal-UNet':
-        raise NotImplementedError("--model Temporal-UNet (common/network_ao.py:67-114, 3-D convolutions) is not built")
-    if FLAGS.model == 'UNet-LSTM':
+    """``forward`` stands for the frame-wise sess.run ('UNet'); ``cine_forward`` for the windowed one ('UNet-LSTM', 'Temporal-UNet').
+    With ``engine`` (and --device_preproc, --z_score) float32 windowed sequences take device_pipeline.aortic_lstm_sequence_device."""
+    windowed = FLAGS.model in ('UNet-LSTM', 'Temporal-UNet')
+    if FLAGS.model == 'Temporal-UNet' and cine_forward is None:
+        # NotImplementedError (not ValueError): a Temporal-UNet needs the windowed forward, frame-wise calls cannot serve it
+        raise NotImplementedError('--model Temporal-UNet needs a Temporal-UNet model (cine_forward)')
+    if windowed:
         if cine_forward is None:
             raise ValueError('--model UNet-LSTM needs a UNet-LSTM model (cine_forward)')
         if FLAGS.time_step < 1:
@@ -160,7 +162,7 @@ def run(FLAGS, forward, log=print, cine_forward=None, engine=None):
                 from ukbb_cardiac_amd.device_pipeline import device_zscore_matches_numpy
                 on_device = device_zscore_matches_numpy(engine, warn=log)
             counts = None
-            if on_device and FLAGS.model == 'UNet-LSTM':
+            if on_device and windowed:
                 from ukbb_cardiac_amd.device_pipeline import aortic_lstm_sequence_device
                 pred, aux = aortic_lstm_sequence_device(image, engine, True, FLAGS.weight_R, FLAGS.weight_r, FLAGS.time_step,
                                                         return_aux='counts')
@@ -170,7 +172,7 @@ def run(FLAGS, forward, log=print, cine_forward=None, engine=None):
                 pred, aux = aortic_unet_sequence_device(image, engine, FLAGS.batch_slices, return_aux=True)
                 counts = aux['counts']
             else:
-                if FLAGS.model == 'UNet-LSTM':
+                if windowed:
                     prob = pipeline.aortic_lstm_prob_sequence(image, cine_forward, FLAGS.z_score, FLAGS.weight_R, FLAGS.weight_r,
                                                               time_step=FLAGS.time_step)
                 else:
@@ -186,8 +188,8 @@ def run(FLAGS, forward, log=print, cine_forward=None, engine=None):
                     counts = measures.counts_from_labels(pred, 3)
                 csv_rows[data] = _qc_row(counts, nim.header['pixdim'], _pp(central_pp, data, log))
         else:
-            if FLAGS.model == 'UNet-LSTM':                             # reference: deploy_network_ao.py:202-205
-                log('UNet-LSTM does not support frame-wise segmentation. Please use the -process_seq flag.')
+            if windowed:                                               # reference: deploy_network_ao.py:202-205
+                log('{0} does not support frame-wise segmentation. Please use the -process_seq flag.'.format(FLAGS.model))
                 return processed
             names = {fr: '{0}/{1}_{2}.nii.gz'.format(data_dir, seq, fr) for fr in ('ED', 'ES')}
             if not all(os.path.exists(p) for p in names.values()):
@@ -245,16 +247,17 @@ def main(argv=None):
         sys.exit('FATAL Flags parsing error: %s\n%s' % (e, fs.usage()))
     if 'CUDA_VISIBLE_DEVICES' in os.environ and 'HIP_VISIBLE_DEVICES' not in os.environ:
         os.environ['HIP_VISIBLE_DEVICES'] = os.environ['CUDA_VISIBLE_DEVICES']
-    if FLAGS.model == 'Temporal-UNet':
-        sys.exit("Error: --model Temporal-UNet is not available on the HIP engine (see DESIGN.md section 7).")
+    if FLAGS.model == 'Temporal-UNet' and FLAGS.precision != 'fp32':
+        sys.exit('Error: --model Temporal-UNet runs in fp32 only (no bf16 plan for its 3-D convolutions).')
     from ukbb_cardiac_amd.shard import apply_cpu_set_from_env
     apply_cpu_set_from_env()                             # shard.launch's per-worker CPU set, before the first GPU call starts threads
-    from ukbb_cardiac_amd.arch import KIND_UNET_LSTM
+    from ukbb_cardiac_amd.arch import KIND_TEMPORAL_UNET, KIND_UNET_LSTM
     from ukbb_cardiac_amd.engine import Session
     nifti.set_label_gzip(FLAGS.label_gzip)
     with Session(FLAGS.model_path, device=FLAGS.device) as sess:
-        is_lstm = sess.engine.arch.kind == KIND_UNET_LSTM
-        if is_lstm != (FLAGS.model == 'UNet-LSTM'):
+        want = {'UNet-LSTM': KIND_UNET_LSTM, 'Temporal-UNet': KIND_TEMPORAL_UNET}.get(FLAGS.model)     # 'UNet': any frame-wise model
+        have = sess.engine.arch.kind
+        if (want is not None or have in (KIND_UNET_LSTM, KIND_TEMPORAL_UNET)) and have != want:
             sys.exit('Error: --model %s but %s holds a %s model.' % (FLAGS.model, FLAGS.model_path, sess.engine.arch.name))
         if FLAGS.precision != 'fp32':
             sess.engine.set_precision(FLAGS.precision)

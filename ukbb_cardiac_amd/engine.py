@@ -8,7 +8,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from .arch import ModelArch, MODELS
+from .arch import KIND_TEMPORAL_UNET, ModelArch, MODELS
 from .weights import Params, load_blob, pack_flat, synthetic_params
 
 MODEL_EXT = '.ukbbw'
@@ -90,9 +90,9 @@ class Engine:
                                        C.c_void_p(pred_ptr or None), C.c_void_p(stream or None))
         _lib.check(rc, 'ukbb_fcn_forward')
 
-    # -- UNet-LSTM (aortic default model) ---------------------------------------------
+    # -- UNet-LSTM (aortic default model) and Temporal-UNet -------------------------------
     def run_seq(self, image: np.ndarray, want_logits=False, want_prob=True, want_pred=True):
-        """The reference's ``sess.run('prob:0', {'image:0': image_idx})`` for the UNet-LSTM graph
+        """The reference's ``sess.run('prob:0', {'image:0': image_idx})`` for the UNet-LSTM or Temporal-UNet graph
         (common/deploy_network_ao.py:171-172): image float32 [N,T,H,W,1] (or [N,T,H,W]) with T = arch.n_step
         -> 'prob' [N,T,H,W,C], 'pred' [N,T,H,W], optionally 'logits'.  Host arrays; staged through torch tensors."""
         import torch
@@ -124,9 +124,10 @@ class Engine:
         return out
 
     def run_cine(self, frames: np.ndarray, weight_R: int = 5, weight_r: float = 0.1, time_step: int = 1):
-        """One slice position of the 'UNet-LSTM' branch of common/deploy_network_ao.py:129-183,189: frames float32
-        [F,H,W] (normalised, padded) -> (prob [F,H,W,C] float32, pred [F,H,W] int32), circular windows centred
-        on frames range(0, F, time_step) tiled on the device; the U-Net features of each frame are computed once."""
+        """One slice position of the 'UNet-LSTM' / 'Temporal-UNet' branch of common/deploy_network_ao.py:129-183,189: frames
+        float32 [F,H,W] (normalised, padded) -> (prob [F,H,W,C] float32, pred [F,H,W] int32), circular windows centred
+        on frames range(0, F, time_step) tiled on the device (UNet-LSTM: the U-Net features of each frame are computed once;
+        Temporal-UNet: every window runs the 3-D network, in chunks of windows)."""
         import torch
         x = np.ascontiguousarray(frames, dtype=np.float32)
         if x.ndim != 3:
@@ -266,7 +267,10 @@ class Session:
             raise KeyError("feed_dict lacks 'image:0'")
         if feed_dict.get('training:0', False):
             raise ValueError("'training:0' must be False: only the inference graph (BN moving statistics) exists")
-        out = self.engine.run(feed_dict['image:0'], want_logits='logits:0' in names,
-                              want_prob='prob:0' in names, want_pred='pred:0' in names)
+        run = self.engine.run
+        if self.engine.arch.kind == KIND_TEMPORAL_UNET:   # image:0 is NTXYC: softmax / argmax of every frame of every window (network_ao.py:159-160)
+            run = self.engine.run_seq
+        out = run(feed_dict['image:0'], want_logits='logits:0' in names,
+                  want_prob='prob:0' in names, want_pred='pred:0' in names)
         res = [out[f.split(':')[0]] for f in names]
         return res[0] if single else res

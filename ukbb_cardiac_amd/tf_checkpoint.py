@@ -25,7 +25,8 @@ scope variables, so ``tf.layers`` numbers them in creation order: ``conv2d/kerne
 ``conv2d_1/kernel``, ..., ``batch_normalization[_k]/{gamma,beta,moving_mean,moving_variance}``, and
 the last ``conv2d_K/{kernel,bias}``.  ``UNet`` (common/network_ao.py:18-64) uses
 ``tf.variable_scope('UNet')`` / ``conv{l}`` / ``conv{l}_up`` / ``conv_out``, and the numbering restarts
-in every scope **[TF-recall]**.  Optimizer slots (``.../Adam``, ``.../Adam_1``, ``beta1_power``, ...)
+in every scope **[TF-recall]**.  ``Temporal_UNet`` (common/network_ao.py:67-114) has the same scopes under
+``Temporal_UNet/`` with ``conv3d[_k]`` / ``conv3d_transpose`` layers (common/network.py:37-52) **[TF-recall]**.  Optimizer slots (``.../Adam``, ``.../Adam_1``, ``beta1_power``, ...)
 and ``global_step`` are ignored.
 """
 import os
@@ -36,7 +37,7 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from .arch import KIND_FCN, KIND_UNET, KIND_UNET_LSTM, MODELS, ModelArch
+from .arch import KIND_FCN, KIND_TEMPORAL_UNET, KIND_UNET, KIND_UNET_LSTM, MODELS, ModelArch
 
 TABLE_MAGIC = 0xdb4775248b80fb57
 FOOTER_LEN = 48
@@ -368,13 +369,14 @@ def variable_names(arch: ModelArch, available=None) -> "OrderedDict[str, Dict[st
         if s.name == 'lstm_out':
             out[s.name] = {'kernel': 'LSTM/output/conv2d/kernel', 'bias': 'LSTM/output/conv2d/bias'}   # :298-309
             continue
+        root, conv = ('Temporal_UNet', 'conv3d') if arch.kind == KIND_TEMPORAL_UNET else ('UNet', 'conv2d')
         if s.name == 'logits':
-            scope = 'UNet/conv_out'
+            scope = root + '/conv_out'
         elif s.name.startswith('conv'):
-            scope = 'UNet/conv%s' % s.name[4:].split('_')[0]
+            scope = root + '/conv%s' % s.name[4:].split('_')[0]
         else:                                               # up{l}_t, up{l}_{i}
-            scope = 'UNet/conv%s_up' % s.name[2:].split('_')[0]
-        layer = take(scope, 'conv2d_transpose' if s.transposed else 'conv2d')
+            scope = root + '/conv%s_up' % s.name[2:].split('_')[0]
+        layer = take(scope, conv + '_transpose' if s.transposed else conv)
         d = {'kernel': layer + '/kernel'}
         if s.has_bias:
             d['bias'] = layer + '/bias'
@@ -407,7 +409,23 @@ def infer_arch(reader: CheckpointReader) -> ModelArch:
     """Hyper-parameters from the kernel shapes (the .meta graph is not parsed)."""
     names = set(reader.names())
     unet = any(n.startswith('UNet/') for n in names)
-    if unet:
+    if any(n.startswith('Temporal_UNet/') for n in names):
+        # network_ao.py:67-114: the UNet's scopes with conv3d layers; the window length is not recoverable from the variables:
+        # train_network_ao.py:307-312 trains it on 2 * weight_R - 1 = 9 frames
+        n_filter, n_block = [], []
+        l = 0
+        while 'Temporal_UNet/conv%d/conv3d/kernel' % l in names:
+            k = 0
+            while 'Temporal_UNet/conv%d/%s/kernel' % (l, _numbered('conv3d', k)) in names:
+                k += 1
+            n_filter.append(reader.shape('Temporal_UNet/conv%d/conv3d/kernel' % l)[4])
+            n_block.append(k)
+            l += 1
+        if not n_filter or 'Temporal_UNet/conv_out/conv3d/kernel' not in names:
+            raise CheckpointError('Temporal_UNet checkpoint without the expected Temporal_UNet/conv{l}/conv3d variables')
+        cand = ModelArch('Temporal-UNet_custom', KIND_TEMPORAL_UNET, reader.shape('Temporal_UNet/conv_out/conv3d/kernel')[4],
+                         n_level=len(n_filter), n_filter=tuple(n_filter), n_block=tuple(n_block), fc=9)
+    elif unet:
         n_filter, n_block = [], []
         l = 0
         while 'UNet/conv%d/conv2d/kernel' % l in names:

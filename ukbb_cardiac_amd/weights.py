@@ -40,11 +40,11 @@ def synthetic_params(arch: ModelArch, seed: int = 1234) -> Params:
     rng = np.random.default_rng(seed)
     params: Params = {}
     for s in arch.layer_specs():
-        kh, kw, a, b = s.kernel_shape
+        a, b = s.kernel_shape[-2:]
         cin, cout = (b, a) if s.transposed else (a, b)
-        fan_in = kh * kw * cin
+        fan_in = int(np.prod(s.kernel_shape[:-2])) * cin          # taps (kd x kh x kw) x C_in
         if s.transposed:
-            # stride-2 transposed conv: each output sees ~ (k/s)^2 taps
+            # spatial stride-2 transposed conv: each output sees ~ (k/s)^2 of the spatial taps
             fan_in = max(1, fan_in // 4)
         p = {'kernel': rng.normal(0.0, np.sqrt(2.0 / fan_in), size=s.kernel_shape).astype(np.float32)}
         if s.has_bn:
@@ -148,9 +148,9 @@ def unpack_flat(arch: ModelArch, flat: np.ndarray) -> Params:
     params: Params = {}
     off = 0
     for s in arch.layer_specs():
-        kh, kw, a, b = s.kernel_shape
+        a, b = s.kernel_shape[-2:]
         cout = a if s.transposed else b
-        n = kh * kw * a * b
+        n = int(np.prod(s.kernel_shape))
         p = {'kernel': flat[off:off + n].reshape(s.kernel_shape).copy()}
         off += n
         if s.has_bn:
