@@ -350,7 +350,11 @@ bool cfg_valid(const ConvConfig &c, int ks, int stride, int c0, int c1, int cout
                int bf16 = 0, int fuse = 0) {
     if (c.ks != ks || c.stride != stride) return false;
     if (c.fuse != fuse) return false;
-    if ((c.pc == 2) != fused_first) return false;
+    if ((c.pc == 2 || c.pc == 7) != fused_first) return false;
+    if (c.pc == 7) {                                  // fused first layer + Winograd conv0_1: the 16 -> 16 stem of the fp32 FCN plans only
+        static const bool off = getenv("UKBB_NO_WINOGRAD_FIRST") != nullptr;    // A/B knob: the direct fused kernel (130-133)
+        if (off || ks != 3 || stride != 1 || c0 != 16 || c1 != 0 || cout != 16) return false;
+    }
     if ((c.pc == 3) != (bf16 == 1) || (c.pc == 5 || c.pc == 6) != (bf16 == 2)) return false;
     if (c.pc == 5 || c.pc == 6) cout = round_up(cout, 32);         // 16-channel layers run zero-padded on the 32-row MFMA
     if (c.pc == 6) {                                  // weight-stationary: the Cout group's whole packed filter + the waves' rings in LDS
@@ -379,7 +383,7 @@ bool cfg_valid(const ConvConfig &c, int ks, int stride, int c0, int c1, int cout
         }
         return !off && !fused_first && ks == 3 && stride == 1 && cout % (16 * c.wm) == 0 && c0 % 16 == 0 && c1 % 16 == 0;
     }
-    if (c.pc == 2 && cout != c.mb * c.cb * c.wm) return false;   // fused kernel stages its weights once: one Cout group
+    if ((c.pc == 2 || c.pc == 7) && cout != c.mb * c.cb * c.wm) return false;   // fused kernel stages its weights once: one Cout group
     if (c.lds_bytes > 160 * 1024) return false;      // LDS per CU on gfx950
     const int group = c.mb * c.cb * c.wm;
     return !(cout % group || c0 % c.kc || c1 % c.kc);
@@ -394,7 +398,7 @@ int wino_orient(int id, int Ho, int Wo) {
 }
 
 int choose_cfg_raw(const std::string &layer, int ks, int stride, int c0, int c1, int cout, int Ho, int Wo, int N,
-                   bool fused_first, int want_bf16);
+                   bool fused_first, int want_bf16, bool wino_first);
 int find_cfg(int id, ConvConfig &out);
 
 // Small batches (N <= SMALL_BATCH, e.g. the reference's own sess.run of one frame's 10 slices, deploy_network.py:103-111): the
@@ -440,9 +444,10 @@ int pick_wino24(int id, int ks, int stride, int c0, int c1, int cout, int Ho, in
     return best;
 }
 
+// wino_first: the plan may run a fused first layer's conv0_1 as Winograd (tiling 134; add_conv: fp32 FCN plans only)
 int choose_cfg(const std::string &layer, int ks, int stride, int c0, int c1, int cout, int Ho, int Wo, int N,
-               bool fused_first = false, int want_bf16 = 0) {
-    const int id = choose_cfg_raw(layer, ks, stride, c0, c1, cout, Ho, Wo, N, fused_first, want_bf16);
+               bool fused_first = false, int want_bf16 = 0, bool wino_first = false) {
+    const int id = choose_cfg_raw(layer, ks, stride, c0, c1, cout, Ho, Wo, N, fused_first, want_bf16, wino_first);
     if (override_cfg(layer) >= 0) return id;
     return finer_sibling(wino_orient(pick_wino24(id, ks, stride, c0, c1, cout, Ho, Wo, N), Ho, Wo), ks, stride, c0, c1, cout, Ho, Wo, N);
 }
@@ -462,7 +467,7 @@ const Tuned g_tuned_bfio[] = {
 };
 
 int choose_cfg_raw(const std::string &layer, int ks, int stride, int c0, int c1, int cout, int Ho, int Wo, int N,
-                   bool fused_first, int want_bf16) {
+                   bool fused_first, int want_bf16, bool wino_first) {
     if (want_bf16 == 2 && !fused_first && override_cfg(layer) < 0) {
         for (const Tuned &t : g_tuned_bfio) {
             if (t.ks != ks || t.stride != stride || t.cin != c0 + c1 || t.cout != cout) continue;
@@ -496,6 +501,12 @@ int choose_cfg_raw(const std::string &layer, int ks, int stride, int c0, int c1,
             if (conv_config(i).id == forced && cfg_valid(conv_config(i), ks, stride, c0, c1, cout, fused_first)) return forced;
     }
     (void)fc;
+    if (fused_first && wino_first && want_bf16 == 0) {
+        // conv0_1 as Winograd F(2x2) behind the fused first layer (kernels_conv.hip, conv_pc_kernel WINO): 64 MFMAs per consumer wave and
+        // 16 x 16 tile instead of the direct form's 144, so even at 60-70 % tile fill it issues less than any direct tiling at 100 %
+        ConvConfig cw;
+        if (find_cfg(134, cw) == 0 && cfg_valid(cw, ks, stride, c0, c1, cout, true)) return 134;
+    }
     if (!fused_first && c1 == 0) {
         const bool small = small_batch_tilings() && N <= SMALL_BATCH;
         const Tuned *tab = small ? g_tuned_small : g_tuned_large;
@@ -529,7 +540,7 @@ int choose_cfg_raw(const std::string &layer, int ks, int stride, int c0, int c1,
     int best_id = -1;
     for (int i = 0; i < num_conv_configs(); ++i) {
         const ConvConfig &c = conv_config(i);
-        if (c.id == 306 || !cfg_valid(c, ks, stride, c0, c1, cout, fused_first)) continue;
+        if (c.id == 306 || c.pc == 7 || !cfg_valid(c, ks, stride, c0, c1, cout, fused_first)) continue;
         const int group = c.mb * c.cb * c.wm;
         const int tiles = ((Ho + c.th - 1) / c.th) * ((Wo + c.tw - 1) / c.tw);
         const int npb = (c.th * c.tw + c.mb - 1) / c.mb;
@@ -571,10 +582,15 @@ int ensure_packed(ukbb_fcn_handle *h, int layer, const ConvConfig &c, const floa
     const bool bfpk = c.pc == 3 || c.pc == 5 || c.pc == 6;
     const int coutp = (c.pc == 5 || c.pc == 6) ? round_up(L.cout, 32) : L.cout;
     const bool w24 = is_wino24(c);
-    snprintf(key, sizeof key, "%s/pk%s_mb%d_kc%d_g%d", L.name.c_str(), bfpk ? "bf16" : w24 ? "wino24" : c.pc == 4 ? "wino" : "", c.mb, c.kc, c.wm * c.cb);
+    snprintf(key, sizeof key, "%s/pk%s_mb%d_kc%d_g%d", L.name.c_str(), bfpk ? "bf16" : w24 ? "wino24" : c.pc == 4 ? "wino" : c.pc == 7 ? "winofirst" : "",
+             c.mb, c.kc, c.wm * c.cb);
     if (!dev_ptr(h, key)) {
-        std::vector<float> pk(w24 ? (size_t)24 * L.cin * L.cout : c.pc == 4 ? (size_t)16 * L.cin * L.cout : (size_t)L.ks * L.ks * L.cin * coutp);
-        if (w24) pack_wino24_weights(L.w.data(), L.cin, L.cout, c.wm, pk.data());
+        std::vector<float> pk(w24 ? (size_t)24 * L.cin * L.cout : (c.pc == 4 || c.pc == 7) ? (size_t)16 * L.cin * L.cout : (size_t)L.ks * L.ks * L.cin * coutp);
+        if (c.pc == 7) {
+            if (L.ks != 3 || L.cin != 16 || L.cout != 16) { set_err("layer %s: the Winograd first-layer tiling needs a 16 -> 16 3x3 conv", L.name.c_str()); return UKBB_EARCH; }
+            pack_wino_first_weights(L.w.data(), pk.data());
+        }
+        else if (w24) pack_wino24_weights(L.w.data(), L.cin, L.cout, c.wm, pk.data());
         else if (c.pc == 4) pack_wino_weights(L.w.data(), L.cin, L.cout, c.wm, pk.data());
         else if (bfpk && coutp != L.cout) {           // zero rows up to the MFMA's 32
             std::vector<float> wp((size_t)L.ks * L.ks * L.cin * coutp, 0.f);
@@ -631,9 +647,12 @@ int add_conv(ukbb_fcn_handle *h, const std::string &lname, int in0, int in1, int
     const int c0 = L.cin - c1;
     op.fused_first = fused_first;
     const int fuse_bf = bf16_mode(h) != 2 ? 0 : fused_first ? 1 : fused_logits ? 2 : 0;
+    // the Winograd form of the fused first layer (134) was measured on, and is taken by, the fp32 FCN plans only (UKBB_PREC_F32X3 included:
+    // its convs are fp32); the U-Net / UNet-LSTM plans and the bf16-operand FCN plans keep the direct fused kernel (130-133)
+    const bool wino_first = fused_first && h->arch.kind == UKBB_KIND_FCN && bf16_mode(h) == 0;
     if (fuse_bf) op.cfg = pick_fused_bf_cfg(lname, L.ks, stride, c0, c1, L.cout, op.Ho, op.Wo, fuse_bf);
     else
-    op.cfg = choose_cfg(lname, L.ks, stride, c0, c1, L.cout, op.Ho, op.Wo, n_hint, fused_first, bf16_mode(h));
+    op.cfg = choose_cfg(lname, L.ks, stride, c0, c1, L.cout, op.Ho, op.Wo, n_hint, fused_first, bf16_mode(h), wino_first);
     op.fused_logits = fuse_bf == 2;
     if (op.cfg < 0) { set_err("no conv tiling for layer %s (ks %d stride %d cin %d+%d cout %d)", lname.c_str(), L.ks, stride, c0, c1, L.cout); return UKBB_EARCH; }
     ConvConfig c;
@@ -656,6 +675,14 @@ int add_conv(ukbb_fcn_handle *h, const std::string &lname, int in0, int in1, int
         double slots = 0;
         for (int ry = 0; ry < regs_y; ++ry) slots += (double)regs_x * ((c.wm == 4 && ry * 2 * trY + trY >= op.Ho) ? 16 : 32);
         op.padded_macs_per_image = slots * 16.0 * L.cin * L.cout;
+    } else if (c.pc == 7) {
+        // what the kernel issues: conv0_1 as F(2x2) (16 products per 4 outputs) + conv0_0 on the producers' MFMAs (K = 9 taps of 12
+        // issued: three 16x16x4 per 16 halo pixels of every 18 x 18 halo tile)
+        const double tiles = (double)((op.Ho + c.th - 1) / c.th) * ((op.Wo + c.tw - 1) / c.tw);
+        const double halo_blocks = (double)(((c.th + 2) * (c.tw + 2) + 15) / 16);
+        const double first_macs = (double)op.Ho * op.Wo * 9 * L.cin;   // conv0_0: 1 -> L.cin channels
+        op.mfma_macs_per_image = op.macs_per_image * (16.0 / 36.0) + first_macs;
+        op.padded_macs_per_image = tiles * ((c.th / 2) * (c.tw / 2) * 16.0 * L.cin * L.cout + halo_blocks * 16 * 12 * L.cin);
     } else if (c.pc <= 2) {                            // direct tilings: tiles x pixel blocks of the MFMA's N width
         const int npb = (c.th * c.tw + c.mb - 1) / c.mb;
         const double tiles = (double)((op.Ho + c.th - 1) / c.th) * ((op.Wo + c.tw - 1) / c.tw);

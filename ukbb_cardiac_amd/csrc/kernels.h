@@ -135,6 +135,8 @@ struct ConvConfig {
                         //    (r04: in plain NHWC a wave's 16-byte pieces of one chunk lay 2 C bytes apart, every piece pulled a whole
                         //    128-byte line out of L2 for 16-32 useful bytes); for C = 16 the two layouts coincide
                         // 6: bf16 storage as 5, weight-stationary persistent kernel of independent waves (kernels_ws.hip)
+                        // 7: as 2 (fused first layer, fp32), the 16 -> 16 conv as Winograd F(2x2,3x3) in the consumers (id 134; weights
+                        //    from pack_wino_first_weights)
     const char *name;
     int fuse;           // pc == 5 only: 1 = the C_in = 1 first layer evaluated in this conv's staging (ConvArgs::first_w / first_b,
                         // in0 = the fp32 image), 2 = the logits conv + softmax / argmax in its epilogue (ConvArgs::lg_*); else 0
@@ -171,6 +173,7 @@ void set_error(const char *fmt, ...);
 hipError_t launch_wino(const ConvArgs &a, int ncb /*16-channel blocks per item: 4 or 2*/, int tile_rows /*4: 8x16-pixel regions, 8: 16x8*/,
                        hipStream_t s);
 size_t pack_wino_weights(const float *w /*[3][3][cin][cout] folded*/, int cin, int cout, int ncb, float *dst /*16*cin*cout*/);
+size_t pack_wino_first_weights(const float *w /*[3][3][16][16] folded*/, float *dst /*16*16*16*/);
 int wino_lds_bytes();
 // Winograd F(2x4,3x3) (kernels_wino24.hip): 64-channel output groups, 8 x 32- or 8 x 16-pixel regions, ConvConfig::pc == 4, ids 304 / 305 / 306 / 307 (306: 8 x 16 over image pairs; 307: 32-channel items)
 inline bool is_wino24(const ConvConfig &c) { return c.pc == 4 && c.id >= 304; }

@@ -538,8 +538,15 @@ __global__ __launch_bounds__(256, conv_min_waves(KS, STRIDE, MB, TH, TW, KC, WM,
 // pixel directly from the 1-channel image (9 taps x KC channels on the vector ALU, same fma
 // order as conv_first_kernel) and write the KC-channel tile to LDS, so that layer's output
 // never exists in HBM.  Halo pixels outside the image are this conv's zero padding.
-template <int KS, int STRIDE, int MB, int TH, int TW, int KC, int WM, int WN, int CB, bool FIRST = false, bool DI = false>
-__global__ __launch_bounds__(512, 2) void conv_pc_kernel(const ConvArgs a) {
+//
+// WINO = true (with FIRST; ConvConfig::pc == 7): conv0_1 as Winograd F(2x2, 3x3) instead of the direct 3x3.  The producers are the
+// FIRST producers above, unchanged (raw tile -> conv0_0 -> the 18 x 18 x 16 halo tile xs); the consumers transform their B operands in
+// registers -- no VS stage, no extra barrier -- and the 16 x 16-point pre-transformed weights U (pack_wino_first_weights) are staged
+// once into LDS beside the two halo buffers.  See the consumer branch below.  Its consumers hold 64 accumulators + 32 transformed operands:
+// left to the (512, 2) budget hipcc spent 160 VGPRs on them (prefetching the second half's patch), one workgroup per CU where the
+// launcher counts on two, so this instance asks for 4 waves per SIMD (<= 128 VGPRs; no scratch, checked with kernel-resource-usage).
+template <int KS, int STRIDE, int MB, int TH, int TW, int KC, int WM, int WN, int CB, bool FIRST = false, bool DI = false, bool WINO = false>
+__global__ __launch_bounds__(512, WINO ? 4 : 2) void conv_pc_kernel(const ConvArgs a) {
     using M = Mfma<MB>;
     using Acc = typename M::Acc;
     constexpr int KK = M::KK, KSTEPS = KC / KK, PB = MB;
@@ -549,9 +556,12 @@ __global__ __launch_bounds__(512, 2) void conv_pc_kernel(const ConvArgs a) {
     constexpr int NCBL = WM * CB, SLAB = KS2 * 64 * KSTEPS;
     constexpr int NIT = (HP * C4 + 255) / 256, WF4 = NCBL * SLAB / 4, NWT = (WF4 + 255) / 256;
     constexpr int PSTEP = 256 / C4;
-    constexpr int BUF = HP * XS + NCBL * SLAB;
+    constexpr int WUF = 2 * 16 * 64 * 2;                 // WINO: floats of U in LDS, [half][point][lane][2]
+    constexpr int BUF = HP * XS + (WINO ? 0 : NCBL * SLAB);
     constexpr int RH = IH + 2, RW = IW + 2, RP = RH * RW, NRAW = (RP + 255) / 256;   // FIRST: raw image tile
     static_assert(WM * WN == 4, "4 consumer waves");
+    static_assert(!WINO || (FIRST && KS == 3 && STRIDE == 1 && MB == 16 && TH == 16 && TW == 16 && KC == 16 && WM == 1 && WN == 4 && CB == 1),
+                  "Winograd consumers: the 16 x 16 fused-first tiling only");
     // r06: stride-2 halo rows are staged DE-INTERLEAVED -- even halo columns first (TW + 1 of them), then the odd ones -- so that the
     // consumers' B fragment of tap (kh, kw), whose 32 lanes are consecutive OUTPUT pixels, reads consecutive LDS slots (80 bytes
     // apart: the eight lanes of a ds_read_b128 group cover all 32 banks) instead of every second one (160 bytes apart: four bank
@@ -594,7 +604,7 @@ __global__ __launch_bounds__(512, 2) void conv_pc_kernel(const ConvArgs a) {
             // waves): ReLU as one v_max_i32, per-thread LDS / global offsets computed once, raw pixels outside
             // the image as out-of-range buffer loads, and the halo-validity select only in tiles that touch the
             // image border.
-            float *raw = lds + 2 * BUF;                        // [2][RP]
+            float *raw = lds + 2 * BUF + (WINO ? WUF : 0);      // [2][RP]
             // conv0_0 is a [16 x 9] x [9 x pixels] product: three v_mfma_f32_16x16x4_f32 per 16 halo pixels (taps 9..11 carry
             // zero weights), bias as the C operand; the D layout (lane = pixel, 4 consecutive channels per lane) is exactly
             // the float4 the halo tile stores.  30 instead of ~200 vector-ALU instructions per thread and tile.
@@ -693,7 +703,13 @@ __global__ __launch_bounds__(512, 2) void conv_pc_kernel(const ConvArgs a) {
             }
             // single Cout group (enforced by the launcher): this conv's weights are the same for every
             // item, so they are staged ONCE into both buffers instead of once per stage
-            {
+            if constexpr (WINO) {                              // U: once, after the two halo buffers (never rewritten)
+#pragma unroll
+                for (int it = 0; it < WUF / 4 / 256; ++it) {
+                    const int i4 = it * 256 + tid;
+                    *reinterpret_cast<f32x4 *>(lds + 2 * BUF + 4 * i4) = *reinterpret_cast<const f32x4 *>(a.wpk + 4 * i4);
+                }
+            } else {
                 const float *wp = a.wpk + (size_t)(item / per_group) * nchunk * (NCBL * SLAB);
 #pragma unroll
                 for (int it = 0; it < NWT; ++it) {
@@ -1003,6 +1019,98 @@ __global__ __launch_bounds__(512, 2) void conv_pc_kernel(const ConvArgs a) {
                 o[8] = __builtin_amdgcn_s_memtime() - st_p0; o[9] = st_pbar; o[10] = st_pstore; o[11] = straight ? 1 : 0;
             }
 #endif
+        }
+    } else if constexpr (WINO) {
+        // ============ Winograd F(2x2, 3x3) consumers: xs -> B^T d B in registers -> MFMA -> A^T M A -> global ============
+        // The 16 x 16 output tile is 8 x 8 Winograd tiles; wave w owns tile rows 2w, 2w + 1 (16 tiles = one MFMA N block) and all
+        // 16 output channels (M).  Lane (g, t) takes tile t and, for the k-steps of half h, channels 4g + 2h, 4g + 2h + 1 (K = the
+        // 16 channels of the one chunk in the permuted order pack_wino_first_weights packs U in): it reads its 4 x 4 patch of those two
+        // channels (16 ds_read_b64), forms the 16 points of B^T d B with packed fp32 adds and feeds them straight into 16 x 2 MFMAs whose
+        // A operands (U, one ds_read_b64 per point) come from LDS.  Per wave and item 64 MFMAs instead of the direct form's 144.
+        const int tid = role_tid, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid) >> 6;
+        const int g = lane >> 4, t = lane & 15;
+        const int wty = 2 * wave + (t >> 3), wtx = t & 7;               // this lane's Winograd tile (row, column) in the 8 x 8 grid
+        const float *const xs_l = lds + ((2 * wty) * IW + 2 * wtx) * XS + 4 * g;
+        const float *const u_l = lds + 2 * BUF + 2 * lane;
+        const f32x4 bias = *reinterpret_cast<const f32x4 *>(a.bias + 4 * g);
+        // output offsets of this lane's 2 x 2 pixels (4 channels each) from the item's first output pixel
+        const int oty = 2 * wty, otx = 2 * wtx;
+        const int ooff = (oty * a.Wo + otx) * a.Cout + 4 * g;
+        int s = 0;
+        __syncthreads();                                // matches the producers' raw-tile barrier
+        for (int item = blockIdx.x; item < nitems; item += gridDim.x) {
+            __syncthreads();                            // barrier #s: buffer s&1 holds this item's halo tile
+            const float *xs = xs_l + (s & 1) * BUF;
+            f32x4 acc[16];
+            unroll_taps<2>([&](auto hc) {
+                constexpr int H = decltype(hc)::value;
+                f32x2 d[4][4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) d[i][j] = *reinterpret_cast<const f32x2 *>(xs + (i * IW + j) * XS + 2 * H);
+                // rows: w = B^T d  (B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1])
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const f32x2 r0 = d[0][j] - d[2][j], r1 = d[1][j] + d[2][j], r2 = d[2][j] - d[1][j], r3 = d[1][j] - d[3][j];
+                    d[0][j] = r0; d[1][j] = r1; d[2][j] = r2; d[3][j] = r3;
+                }
+                // columns: V = w B, point k = 4 * row + column
+                f32x2 v[16];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    v[4 * i + 0] = d[i][0] - d[i][2];
+                    v[4 * i + 1] = d[i][1] + d[i][2];
+                    v[4 * i + 2] = d[i][2] - d[i][1];
+                    v[4 * i + 3] = d[i][1] - d[i][3];
+                }
+#pragma unroll
+                for (int k = 0; k < 16; ++k) {
+                    const f32x2 u = *reinterpret_cast<const f32x2 *>(u_l + (H * 16 + k) * 128);
+                    if constexpr (H == 0) {
+                        // the folded-BN bias rides in as point (1,1)'s C operand: A^T M A adds M[1][1] to all four outputs of the tile
+                        const f32x4 c0 = k == 5 ? bias : f32x4{0.f, 0.f, 0.f, 0.f};
+                        acc[k] = __builtin_amdgcn_mfma_f32_16x16x4f32(u[0], v[k][0], c0, 0, 0, 0);
+                    } else {
+                        acc[k] = __builtin_amdgcn_mfma_f32_16x16x4f32(u[0], v[k][0], acc[k], 0, 0, 0);
+                    }
+                    acc[k] = __builtin_amdgcn_mfma_f32_16x16x4f32(u[1], v[k][1], acc[k], 0, 0, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);      // the second half's patch reads reuse this half's operand registers
+            });
+            ++s;
+            // ---- output transform Y = A^T M A (A^T = [1 1 1 0; 0 1 -1 -1]), ReLU, NHWC stores ----
+            f32x4 t0[4], t1[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                t0[j] = acc[0 + j] + acc[4 + j] + acc[8 + j];
+                t1[j] = acc[4 + j] - acc[8 + j] - acc[12 + j];
+            }
+            f32x4 y[2][2];
+            y[0][0] = t0[0] + t0[1] + t0[2];
+            y[0][1] = t0[1] - t0[2] - t0[3];
+            y[1][0] = t1[0] + t1[1] + t1[2];
+            y[1][1] = t1[1] - t1[2] - t1[3];
+            const int rest = item - (item / per_group) * per_group;
+            const int n = rest / tiles, tt = rest - n * tiles;
+            const int ty = tt / a.tiles_x, tx = tt - ty * a.tiles_x;
+            const int oy0 = ty * TH, ox0 = tx * TW;
+            float *const o = a.out + ((size_t)(n * a.Ho + oy0) * a.Wo + ox0) * a.Cout + ooff;
+            // the engine only plans maps whose sides are multiples of 16 (ukbb_fcn_forward*), so every tile is whole; the masked path
+            // keeps the kernel correct for any map all the same
+            const bool whole = oy0 + TH <= a.Ho && ox0 + TW <= a.Wo;
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    f32x4 v = y[i][j];
+                    if (a.relu) {
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) v[c] = relu_bits(v[c]);
+                    }
+                    if (whole || (oy0 + oty + i < a.Ho && ox0 + otx + j < a.Wo))
+                        *reinterpret_cast<f32x4 *>(o + (i * a.Wo + j) * a.Cout) = v;
+                }
         }
     } else {
         // ===================== consumers: LDS -> MFMA -> global =====================
@@ -1372,7 +1480,9 @@ static const ConvConfig g_cfgs[] = {UKBB_CONV_CONFIGS(UKBB_CFG_ENTRY) UKBB_PC_CO
                                     {304, 3, 1, 16, 8, 32, 16, 4, 1, 1, 152960, 4, "winogradF2x4_3x3_t8x32_kc16_cout64"},
                                     {305, 3, 1, 16, 8, 16, 16, 4, 1, 1, 87808, 4, "winogradF2x4_3x3_t8x16_kc16_cout64"},
                                     {306, 3, 1, 16, 8, 16, 16, 4, 1, 1, 95488, 4, "winogradF2x4_3x3_t8x16pair_kc16_cout64"},
-                                    {307, 3, 1, 16, 8, 32, 16, 2, 1, 1, 152960, 4, "winogradF2x4_3x3_t8x32_kc16_cout32"}};
+                                    {307, 3, 1, 16, 8, 32, 16, 2, 1, 1, 152960, 4, "winogradF2x4_3x3_t8x32_kc16_cout32"},
+                                    // fused first layer + Winograd F(2x2,3x3) conv0_1 (conv_pc_kernel WINO): two 18x18x20 halo buffers, U, two raw tiles
+                                    {134, 3, 1, 16, 16, 16, 16, 1, 4, 1, (2 * 324 * 20 + 2 * 16 * 64 * 2 + 2 * 400) * 4, 7, "winogradF2x2_first+3x3s1_t16x16_kc16_cout16"}};
 
 static constexpr int N_BASE_CFGS = (int)(sizeof(g_cfgs) / sizeof(g_cfgs[0]));
 int num_conv_configs() { return N_BASE_CFGS + num_pk16_configs() + num_ws_configs(); }
@@ -1438,7 +1548,7 @@ hipError_t launch_conv(int cfg_id, const ConvArgs &a_in, hipStream_t s) {
     const int group = c->mb * c->cb * c->wm;
     if (c->pc == 4) return is_wino24(*c) ? launch_wino24(a, c->tw, c->id == 306, c->wm, s) : launch_wino(a, c->wm, c->th / 2, s);
     if (a.in0_map) return hipErrorInvalidValue;       // image remapping exists in the Winograd kernel only
-    if (c->pc == 2) {
+    if (c->pc == 2 || c->pc == 7) {
         if (!a.first_w || !a.first_b || a.Cout != group) return hipErrorInvalidValue;
     } else if (a.Cout % group || (a.C0 + a.C1) % c->kc || a.C0 % c->kc) {
         return hipErrorInvalidValue;
@@ -1475,21 +1585,25 @@ hipError_t launch_conv(int cfg_id, const ConvArgs &a_in, hipStream_t s) {
         break;                                                                                  \
     }
         UKBB_PC_CONFIGS(UKBB_PC_CASE)
-#define UKBB_PCF_CASE(ID, KS, S, MB, TH, TW, KC, WM, WN, CB)                                    \
+// WINO: the Winograd consumers (tiling 134), whose output tile is the halo tile's centre: 3x3 stride 1 'SAME' only
+#define UKBB_PCF_CASE_W(ID, WINO, KS, S, MB, TH, TW, KC, WM, WN, CB)                             \
     case ID: {                                                                                  \
-        auto k = conv_pc_kernel<KS, S, MB, TH, TW, KC, WM, WN, CB, true>;                       \
+        auto k = conv_pc_kernel<KS, S, MB, TH, TW, KC, WM, WN, CB, true, false, WINO>;          \
         static OncePerDevice lds_ok;                                                            \
         {                                                                                       \
             hipError_t e = allow_dynamic_lds(lds_ok, reinterpret_cast<const void *>(k), c->lds_bytes); \
             if (e != hipSuccess) return e;                                                      \
         }                                                                                       \
+        if ((WINO) && (a.pad_y != 1 || a.pad_x != 1 || a.Ho != a.H || a.Wo != a.W)) return hipErrorInvalidValue; \
         const int per_cu = c->lds_bytes * 2 <= 160 * 1024 ? 2 : 1;                              \
         const long long cap = (long long)n_cu * per_cu;                                         \
         dim3 pgrid((unsigned)(nitems < cap ? nitems : cap), 1, 1);                              \
         hipLaunchKernelGGL(k, pgrid, dim3(512), c->lds_bytes, s, a);                            \
         break;                                                                                  \
     }
+#define UKBB_PCF_CASE(ID, ...) UKBB_PCF_CASE_W(ID, false, __VA_ARGS__)
         UKBB_PCF_CONFIGS(UKBB_PCF_CASE)
+        UKBB_PCF_CASE_W(134, true, 3, 1, 16, 16, 16, 16, 1, 4, 1)
 #define UKBB_BF_CASE(ID, KS, S, TH, TW, WM, WN, CB)                                             \
     case ID: {                                                                                  \
         auto k = conv_mfma_kernel<KS, S, 32, TH, TW, 16, WM, WN, CB, true>;                     \
@@ -1551,6 +1665,27 @@ size_t pack_conv_weights(const float *w, int ks, int cin, int cout, int mb, int 
                             dst[o++] = w[((size_t)tap * cin + ci) * cout + co];
                         }
                     }
+    return o;
+}
+
+size_t pack_wino_first_weights(const float *w, float *dst) {
+    // w: folded [3][3][16][16] of a 16 -> 16 3x3 conv.  U = G g G^T per (ci, co), G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]] (the +-1/2
+    // factors stay in the weights, as in pack_wino_weights).  dst[h][k = 4*xi + nu][lane][s]: the A fragment of k-step s of half h of the
+    // Winograd consumers of conv_pc_kernel<..., WINO>: lane = (g << 4) | m, co = m, ci = 4*g + 2*h + s.
+    static const float G[4][3] = {{1.f, 0.f, 0.f}, {.5f, .5f, .5f}, {.5f, -.5f, .5f}, {0.f, 0.f, 1.f}};
+    size_t o = 0;
+    for (int h = 0; h < 2; ++h)
+        for (int k = 0; k < 16; ++k)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int s = 0; s < 2; ++s) {
+                    const int m = lane & 15, g = lane >> 4, ci = 4 * g + 2 * h + s, co = m;
+                    const int xi = k >> 2, nu = k & 3;
+                    double u = 0.0;                         // exact products of small dyadic factors; one rounding
+                    for (int i = 0; i < 3; ++i)
+                        for (int j = 0; j < 3; ++j)
+                            u += (double)G[xi][i] * (double)w[((size_t)(i * 3 + j) * 16 + ci) * 16 + co] * (double)G[nu][j];
+                    dst[o++] = (float)u;
+                }
     return o;
 }
 
