@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define UKBB_FCN_ABI_VERSION 8
+#define UKBB_FCN_ABI_VERSION 9
 #define UKBB_FCN_MAX_LEVEL 8
 
 #define UKBB_OK 0
@@ -233,6 +233,50 @@ int ukbb_fcn_pairwise_sum(const float *d_a, uint64_t n, int squared_dev, float m
  * division), zero padding around it.  Replaces image_utils.py:67 + deploy_network_ao.py:105-108,147-150. */
 int ukbb_fcn_zscore_pack(const float *d_vol, int X, int Y, int Z, int T, int64_t sx, int64_t sy, int64_t sz, int64_t st,
                          float mu, float den, int X2, int Y2, int x_pre, int y_pre, float *d_batch, void *stream);
+
+/* -- integer volumes (ABI 9): the same pre-processing for the uint8 / int16 / uint16 files MR converters write ---------
+ * What nib.load(...).get_data() returns for them (common/deploy_network.py:80-81, deploy_network_ao.py:82-85) goes through
+ * image_utils.py with numpy's integer arithmetic, which the calls below reproduce bit for bit:
+ *   - np.percentile takes float64 quantiles (scalar or tuple q alike) and interpolates in float64 between two integer order
+ *     statistics (numpy's lerp subtracts them in the integer type first; the caller does that interpolation);
+ *   - the in-place clip stores the float64 bound TRUNCATED toward zero into the integer array, the comparisons and the
+ *     rescale use the untruncated float64 bounds;
+ *   - np.mean / np.std of image[roi] reduce in float64 (the plain sum of 8/16-bit values is exact in any order, the sum of
+ *     squared deviations is not: numpy's pairwise tree again), and the z-score is float64 rounded once to float32.
+ * nifti_datatype: the NIfTI codes ukbb_fcn_gzip_labels uses -- 2 (uint8), 4 (int16), 512 (uint16); any other code, float32
+ * (16) included, returns UKBB_EINVAL (float32 volumes take the untyped calls above).  Device pointers; asynchronous on
+ * `stream` unless stated. */
+
+/* ukbb_fcn_select_kth for integer voxels: out_host[i] = the ranks[i]-th smallest value (exact, as a double).  d_data 16-byte
+ * aligned.  1 radix pass for uint8, 2 for the 16-bit types (int16 with its sign bit flipped).  Synchronous.
+ * Replaces the sort inside np.percentile(image, ...), common/image_utils.py:62,72. */
+int ukbb_fcn_select_kth_t(const void *d_data, int nifti_datatype, size_t n, const uint64_t *ranks, int nranks, double *out_host,
+                          void *stream);
+
+/* ukbb_fcn_rescale_pack for an integer volume: clip_lo / clip_hi = the float64 percentiles lo / hi truncated toward zero (what
+ * image[image < lo] = lo stores; they must fit the voxel type), v compared with lo / hi in float64, then (v - lo) / (hi - lo)
+ * in float64 rounded to float32, centred zero padding, batch index b = t*Z + z.  Replaces common/image_utils.py:73-76 and
+ * common/deploy_network.py:97-107 for integer data. */
+int ukbb_fcn_rescale_pack_t(const void *d_vol, int nifti_datatype, int X, int Y, int Z, int T, int64_t sx, int64_t sy, int64_t sz,
+                            int64_t st, int64_t clip_lo, int64_t clip_hi, double lo, double hi, int X2, int Y2, int x_pre, int y_pre,
+                            float *d_batch, void *stream);
+
+/* ukbb_fcn_roi_compact for an integer volume: d_out (voxel type, up to X*Y*Z*T elements) = the elements with
+ * float64(v) >= thr in numpy's row-major index order -- image[image >= val_l], image_utils.py:63-64.  Synchronous. */
+int ukbb_fcn_roi_compact_t(const void *d_vol, int nifti_datatype, int X, int Y, int Z, int T, int64_t sx, int64_t sy, int64_t sz,
+                           int64_t st, double thr, void *d_out, uint64_t *n_host, void *stream);
+
+/* ukbb_fcn_pairwise_sum over n contiguous integer values converted to float64: the sum (squared_dev = 0; exact, what np.mean of
+ * integer data divides) or the sum of (v - mean)^2 evaluated in float64 (squared_dev = 1, the inner sum of np.var) along
+ * numpy's pairwise tree, float64 leaves and float64 additions up the tree.  Synchronous.  Replaces the reductions of
+ * image_utils.py:65. */
+int ukbb_fcn_pairwise_sum_t(const void *d_a, int nifti_datatype, uint64_t n, int squared_dev, double mean, double *sum_host,
+                            void *stream);
+
+/* ukbb_fcn_zscore_pack for an integer volume: d_batch[t*Z+z][X2][Y2] = (float64(v) - mu) / den in float64 (IEEE division),
+ * rounded once to float32, zero padding around it.  Replaces image_utils.py:67 + deploy_network_ao.py:105-108,147-150. */
+int ukbb_fcn_zscore_pack_t(const void *d_vol, int nifti_datatype, int X, int Y, int Z, int T, int64_t sx, int64_t sy, int64_t sz,
+                           int64_t st, double mu, double den, int X2, int Y2, int x_pre, int y_pre, float *d_batch, void *stream);
 
 /* ---- label-volume files (host only: no device, no stream) ---------------------------------------
  * What the reference does with the result: nib.save of np.zeros(image.shape) filled with the labels

@@ -9,6 +9,11 @@
 //
 // All three are HBM-bound byte/float shuffles: coalesced 16-byte loads, 32x32 LDS tile transposes between
 // the volume's x-fastest order and the network's y-fastest order, no arithmetic to speak of.
+//
+// Every pre-processing kernel is a template on the voxel type: float32, or the uint8 / int16 / uint16 volumes MR
+// converters write (the *_t entry points, NIfTI datatype 2 / 4 / 512).  The arithmetic is numpy's for that dtype: a
+// 1- or 2-pass radix select on 8/16-bit keys, the clip stored truncated toward zero into the integer array, float64
+// thresholds, float64 z-score sums and arithmetic (see the header).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -42,24 +47,48 @@ __device__ __host__ inline float fkey_inv(unsigned k) {
     return f;
 }
 
+// Radix keys per voxel type: an order-preserving unsigned key of BITS bits (int16: sign bit flipped) and, for the
+// integer types, the voxel value of a key.  The select runs BITS / 8 byte passes, the first at shift BITS - 8.
+template <typename T> struct Key;
+template <> struct Key<float> {
+    static constexpr int BITS = 32;
+    __device__ static unsigned of(float x) { return fkey(x); }
+};
+template <> struct Key<int16_t> {
+    static constexpr int BITS = 16;
+    __device__ static unsigned of(int16_t x) { return (unsigned)(uint16_t)x ^ 0x8000u; }
+    static double value(unsigned k) { return (double)(int16_t)(uint16_t)(k ^ 0x8000u); }
+};
+template <> struct Key<uint16_t> {
+    static constexpr int BITS = 16;
+    __device__ static unsigned of(uint16_t x) { return x; }
+    static double value(unsigned k) { return (double)k; }
+};
+template <> struct Key<uint8_t> {
+    static constexpr int BITS = 8;
+    __device__ static unsigned of(uint8_t x) { return x; }
+    static double value(unsigned k) { return (double)k; }
+};
+
 // One radix pass: histogram of byte `shift/8` over the elements whose higher bytes equal prefix[r].
 // LDS-privatised; runs of equal bins (MR intensities share their top byte) are counted in a register and
-// flushed once, which removes the same-address atomic contention of the first pass.
-template <int NR>
-__global__ __launch_bounds__(256) void sel_hist_kernel(const float *__restrict__ data, size_t n, SelState *st, int shift) {
+// flushed once, which removes the same-address atomic contention of the first pass.  16-byte loads: 4 float32,
+// 8 int16 / uint16 or 16 uint8 keys each.
+template <int NR, typename T>
+__global__ __launch_bounds__(256) void sel_hist_kernel(const T *__restrict__ data, size_t n, SelState *st, int shift) {
     __shared__ unsigned h[NR][256];
     for (int i = threadIdx.x; i < NR * 256; i += 256) (&h[0][0])[i] = 0;
     unsigned prefix[NR];
 #pragma unroll
     for (int r = 0; r < NR; ++r) prefix[r] = st->prefix[r];
-    const unsigned himask = shift == 24 ? 0u : 0xFFFFFFFFu << (shift + 8);
+    const unsigned himask = shift == Key<T>::BITS - 8 ? 0u : 0xFFFFFFFFu << (shift + 8);
     __syncthreads();
     int last_bin[NR];
     unsigned run[NR];
 #pragma unroll
     for (int r = 0; r < NR; ++r) { last_bin[r] = 0; run[r] = 0; }
-    auto feed = [&](float x) {
-        const unsigned k = fkey(x);
+    auto feed = [&](T x) {
+        const unsigned k = Key<T>::of(x);
         const int bin = (k >> shift) & 255;
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
@@ -69,13 +98,17 @@ __global__ __launch_bounds__(256) void sel_hist_kernel(const float *__restrict__
             }
         }
     };
-    const size_t n4 = n / 4;
-    const float4 *d4 = reinterpret_cast<const float4 *>(data);
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-        const float4 v = d4[i];
-        feed(v.x); feed(v.y); feed(v.z); feed(v.w);
+    constexpr int V = 16 / sizeof(T);
+    const size_t nv = n / V;
+    const uint4 *dv = reinterpret_cast<const uint4 *>(data);
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nv; i += (size_t)gridDim.x * 256) {
+        const uint4 w = dv[i];
+        T v[V];
+        memcpy(v, &w, 16);
+#pragma unroll
+        for (int j = 0; j < V; ++j) feed(v[j]);
     }
-    for (size_t i = n4 * 4 + (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) feed(data[i]);
+    for (size_t i = nv * V + (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) feed(data[i]);
 #pragma unroll
     for (int r = 0; r < NR; ++r)
         if (run[r]) atomicAdd(&h[r][last_bin[r]], run[r]);
@@ -104,10 +137,12 @@ __global__ void sel_pick_kernel(SelState *st, int nr, int shift) {
 
 // ---- rescale + pad + transpose ----------------------------------------------------------------------------
 // One workgroup: a 32x32 (x, y) tile of one (z, t) slice.  Reads run along the volume's fastest axis when
-// sx == 1 (NIfTI order), writes run along y2 (the network's fastest axis).
-__global__ __launch_bounds__(256) void rescale_pack_kernel(const float *__restrict__ vol, int X, int Y, int Z, int T,
+// sx == 1 (NIfTI order), writes run along y2 (the network's fastest axis).  T = float, int16_t, uint16_t or uint8_t:
+// every value of these types is exact in float32 and float64.
+template <typename T>
+__global__ __launch_bounds__(256) void rescale_pack_kernel(const T *__restrict__ vol, int X, int Y, int Z, int T_,
                                                            long long sx, long long sy, long long sz, long long st,
-                                                           double lo, double hi, int X2, int Y2, int x_pre, int y_pre,
+                                                           T clo, T chi, double lo, double hi, int X2, int Y2, int x_pre, int y_pre,
                                                            float *__restrict__ out) {
     __shared__ float tile[32][33];
     const int tiles_x = (X2 + 31) / 32;
@@ -115,7 +150,6 @@ __global__ __launch_bounds__(256) void rescale_pack_kernel(const float *__restri
     const int b = blockIdx.y;                           // b = t * Z + z
     const int t = b / Z, z = b - t * Z;
     const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5;
-    const float flo = (float)lo, fhi = (float)hi;       // what the in-place clip stores into the float32 array
     const double inv_den = hi - lo;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -123,9 +157,11 @@ __global__ __launch_bounds__(256) void rescale_pack_kernel(const float *__restri
         const int x = x2 - x_pre, y = y2 - y_pre;
         float r = 0.f;                                  // np.pad(..., 'constant') after the rescale
         if (x >= 0 && x < X && y >= 0 && y < Y) {
-            float v = vol[x * sx + y * sy + z * sz + t * st];
-            if ((double)v < lo) v = flo;                // image[image < val_l] = val_l   (image_utils.py:73)
-            if ((double)v > hi) v = fhi;                // image[image > val_h] = val_h   (:74)
+            // clo / chi: what the in-place clip stores into the caller's array -- the bound rounded to float32, or for an
+            // integer array truncated toward zero -- while the comparisons and the rescale use the float64 bounds
+            T v = vol[x * sx + y * sy + z * sz + t * st];
+            if ((double)v < lo) v = clo;                // image[image < val_l] = val_l   (image_utils.py:73)
+            if ((double)v > hi) v = chi;                // image[image > val_h] = val_h   (:74)
             r = (float)(((double)v - lo) / inv_den);    // (:75-76), float64 arithmetic, float32 at deploy_network.py:105
         }
         tile[ly + 8 * j][lx] = r;
@@ -180,21 +216,26 @@ __global__ __launch_bounds__(256) void unpack_labels_kernel(const int *__restric
 // leaf sums up the tree in the same order, one tree per 8192-element buffer of numpy's reduction iterator, buffers in sequence.  No FMA contraction (-ffp-contract=off), IEEE division.
 constexpr int CCH = 1024;                            // row-major indices per workgroup of the compaction kernels
 
-__device__ __forceinline__ float roi_elem(const float *vol, long long i, int Y, int Z, int T, long long sx, long long sy, long long sz, long long st) {
-    const int t = (int)(i % T); long long r = i / T;
+// Integer volumes (numpy, for int16 / uint16 / uint8 data): the percentile threshold is float64 and so is `image >= val_l`;
+// the compacted ROI keeps the voxel type, and the two sums run in float64 (pairwise_leaf_kernel<T, double>).  TH = the type
+// of the comparison: float for float32 volumes, double for integer ones.
+template <typename T>
+__device__ __forceinline__ T roi_elem(const T *vol, long long i, int Y, int Z, int T_, long long sx, long long sy, long long sz, long long st) {
+    const int t = (int)(i % T_); long long r = i / T_;
     const int z = (int)(r % Z); r /= Z;
     const int y = (int)(r % Y); const long long x = r / Y;
     return vol[x * sx + y * sy + z * sz + t * st];
 }
 
-__global__ __launch_bounds__(256) void roi_count_kernel(const float *__restrict__ vol, long long n, int Y, int Z, int T, long long sx, long long sy,
-                                                        long long sz, long long st, float thr, unsigned *__restrict__ counts) {
+template <typename T, typename TH>
+__global__ __launch_bounds__(256) void roi_count_kernel(const T *__restrict__ vol, long long n, int Y, int Z, int T_, long long sx, long long sy,
+                                                        long long sz, long long st, TH thr, unsigned *__restrict__ counts) {
     __shared__ unsigned wsum[4];
     const long long i0 = (long long)blockIdx.x * CCH + threadIdx.x * 4;
     unsigned c = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k)
-        if (i0 + k < n && roi_elem(vol, i0 + k, Y, Z, T, sx, sy, sz, st) >= thr) ++c;
+        if (i0 + k < n && (TH)roi_elem(vol, i0 + k, Y, Z, T_, sx, sy, sz, st) >= thr) ++c;
     for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
     __syncthreads();
@@ -219,18 +260,19 @@ __global__ __launch_bounds__(1024) void roi_scan_kernel(const unsigned *__restri
     for (int b = b0; b < b1; ++b) { offs[b] = run; run += counts[b]; }
 }
 
-__global__ __launch_bounds__(256) void roi_write_kernel(const float *__restrict__ vol, long long n, int Y, int Z, int T, long long sx, long long sy,
-                                                        long long sz, long long st, float thr, const unsigned long long *__restrict__ offs,
-                                                        float *__restrict__ out) {
+template <typename T, typename TH>
+__global__ __launch_bounds__(256) void roi_write_kernel(const T *__restrict__ vol, long long n, int Y, int Z, int T_, long long sx, long long sy,
+                                                        long long sz, long long st, TH thr, const unsigned long long *__restrict__ offs,
+                                                        T *__restrict__ out) {
     __shared__ unsigned wpre[4];
     const long long i0 = (long long)blockIdx.x * CCH + threadIdx.x * 4;
-    float v[4];
+    T v[4];
     bool keep[4];
     unsigned c = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         keep[k] = false;
-        if (i0 + k < n) { v[k] = roi_elem(vol, i0 + k, Y, Z, T, sx, sy, sz, st); keep[k] = v[k] >= thr; }
+        if (i0 + k < n) { v[k] = roi_elem(vol, i0 + k, Y, Z, T_, sx, sy, sz, st); keep[k] = (TH)v[k] >= thr; }
         c += keep[k];
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -246,21 +288,24 @@ __global__ __launch_bounds__(256) void roi_write_kernel(const float *__restrict_
         if (keep[k]) out[pos++] = v[k];
 }
 
-// one thread = one leaf of numpy's pairwise summation tree (loops_utils.h.src, pairwise_sum with PW_BLOCKSIZE = 128)
-__global__ __launch_bounds__(128) void pairwise_leaf_kernel(const float *__restrict__ a, const unsigned long long *__restrict__ leaf_off,
-                                                            const unsigned *__restrict__ leaf_len, int nleaf, int sq, float mean,
-                                                            float *__restrict__ leaf_sum) {
+// one thread = one leaf of numpy's pairwise summation tree (loops_utils.h.src, pairwise_sum with PW_BLOCKSIZE = 128).
+// A = the type numpy accumulates in: float for a float32 ROI, double for an integer one (np.mean / np.var of integer data
+// reduce with dtype float64; every value is exact in it, and so is every partial sum of the plain sum: < 2^53).
+template <typename T, typename A>
+__global__ __launch_bounds__(128) void pairwise_leaf_kernel(const T *__restrict__ a, const unsigned long long *__restrict__ leaf_off,
+                                                            const unsigned *__restrict__ leaf_len, int nleaf, int sq, A mean,
+                                                            A *__restrict__ leaf_sum) {
     const int l = blockIdx.x * 128 + threadIdx.x;
     if (l >= nleaf) return;
-    const float *p = a + leaf_off[l];
+    const T *p = a + leaf_off[l];
     const int n = (int)leaf_len[l];
-    auto val = [&](int i) { float v = p[i]; if (sq) { const float d = v - mean; v = d * d; } return v; };
-    float res;
+    auto val = [&](int i) { A v = (A)p[i]; if (sq) { const A d = v - mean; v = d * d; } return v; };
+    A res;
     if (n < 8) {
-        res = 0.f;
+        res = 0;
         for (int i = 0; i < n; ++i) res += val(i);
     } else {
-        float r0 = val(0), r1 = val(1), r2 = val(2), r3 = val(3), r4 = val(4), r5 = val(5), r6 = val(6), r7 = val(7);
+        A r0 = val(0), r1 = val(1), r2 = val(2), r3 = val(3), r4 = val(4), r5 = val(5), r6 = val(6), r7 = val(7);
         int i = 8;
         for (; i < n - (n % 8); i += 8) {
             r0 += val(i); r1 += val(i + 1); r2 += val(i + 2); r3 += val(i + 3);
@@ -272,10 +317,15 @@ __global__ __launch_bounds__(128) void pairwise_leaf_kernel(const float *__restr
     leaf_sum[l] = res;
 }
 
-// (v - mu) / den in float32, centred zero padding, (X,Y,Z,T) -> [T*Z][X2][Y2]: rescale_pack_kernel with the z-score arithmetic
-__global__ __launch_bounds__(256) void zscore_pack_kernel(const float *__restrict__ vol, int X, int Y, int Z, int T,
+__device__ __forceinline__ float div_rn(float a, float b) { return __fdiv_rn(a, b); }
+__device__ __forceinline__ double div_rn(double a, double b) { return a / b; }      // IEEE: no fast-math in this build
+
+// (v - mu) / den in A, rounded to float32, centred zero padding, (X,Y,Z,T) -> [T*Z][X2][Y2]: rescale_pack_kernel with the z-score
+// arithmetic.  A = float for a float32 volume (numpy keeps float32 there), double for an integer one (mu, sigma are float64).
+template <typename T, typename A>
+__global__ __launch_bounds__(256) void zscore_pack_kernel(const T *__restrict__ vol, int X, int Y, int Z, int T_,
                                                           long long sx, long long sy, long long sz, long long st,
-                                                          float mu, float den, int X2, int Y2, int x_pre, int y_pre, float *__restrict__ out) {
+                                                          A mu, A den, int X2, int Y2, int x_pre, int y_pre, float *__restrict__ out) {
     __shared__ float tile[32][33];
     const int tiles_x = (X2 + 31) / 32;
     const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
@@ -287,7 +337,7 @@ __global__ __launch_bounds__(256) void zscore_pack_kernel(const float *__restric
         const int x2 = tx * 32 + lx, y2 = ty * 32 + ly + 8 * j;
         const int x = x2 - x_pre, y = y2 - y_pre;
         float r = 0.f;                                  // np.pad(..., 'constant') after the normalisation (deploy_network_ao.py:105-108)
-        if (x >= 0 && x < X && y >= 0 && y < Y) r = __fdiv_rn(vol[x * sx + y * sy + z * sz + t * st] - mu, den);
+        if (x >= 0 && x < X && y >= 0 && y < Y) r = (float)div_rn((A)vol[x * sx + y * sy + z * sz + t * st] - mu, den);
         tile[ly + 8 * j][lx] = r;
     }
     __syncthreads();
@@ -327,13 +377,92 @@ void pairwise_leaves(unsigned long long off, unsigned long long n, std::vector<u
     pairwise_leaves(off, n2, offs, lens);
     pairwise_leaves(off + n2, n - n2, offs, lens);
 }
-float pairwise_combine(const float *leaf, size_t &idx, unsigned long long n) {
+template <typename A>
+A pairwise_combine(const A *leaf, size_t &idx, unsigned long long n) {
     if (n <= 128) return leaf[idx++];
     unsigned long long n2 = n / 2;
     n2 -= n2 % 8;
-    const volatile float l = pairwise_combine(leaf, idx, n2);
-    const volatile float r = pairwise_combine(leaf, idx, n - n2);
+    const volatile A l = pairwise_combine(leaf, idx, n2);
+    const volatile A r = pairwise_combine(leaf, idx, n - n2);
     return l + r;
+}
+
+// np.add.reduce of n values of type T at d_a (or of their squared deviations from `mean`) accumulated in A, numpy's tree
+template <typename T, typename A>
+int pairwise_sum_impl(const T *d_a, uint64_t n, int squared_dev, A mean, A *sum_host, hipStream_t s) {
+    if (n == 0) { *sum_host = 0; return UKBB_OK; }
+    std::vector<unsigned long long> offs;
+    std::vector<unsigned> lens;
+    offs.reserve((size_t)(n / 64) + 2); lens.reserve((size_t)(n / 64) + 2);
+    for (uint64_t c = 0; c < n; c += NPY_BUFSIZE) pairwise_leaves(c, n - c < NPY_BUFSIZE ? n - c : NPY_BUFSIZE, offs, lens);
+    const size_t nl = offs.size();
+    const size_t sum_at = nl * 8 + ((nl * 4 + 7) / 8) * 8;  // offsets, lengths, leaf sums (8-byte aligned)
+    Scratch *sc = prep_scratch(1);
+    char *buf = sc ? static_cast<char *>(sc->get(sum_at + nl * sizeof(A))) : nullptr;
+    if (!buf) { set_error("pairwise_sum: scratch allocation failed"); return UKBB_ENOMEM; }
+    unsigned long long *d_off = reinterpret_cast<unsigned long long *>(buf);
+    unsigned *d_len = reinterpret_cast<unsigned *>(buf + nl * 8);
+    A *d_sum = reinterpret_cast<A *>(buf + sum_at);
+    std::vector<A> leaf(nl);
+    if (hipMemcpyAsync(d_off, offs.data(), nl * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(d_len, lens.data(), nl * 4, hipMemcpyHostToDevice, s) != hipSuccess) { set_error("pairwise_sum: H2D failed"); return UKBB_EDEVICE; }
+    hipLaunchKernelGGL((pairwise_leaf_kernel<T, A>), dim3((unsigned)((nl + 127) / 128)), dim3(128), 0, s, d_a, d_off, d_len, (int)nl, squared_dev, mean, d_sum);
+    if (hipMemcpyAsync(leaf.data(), d_sum, nl * sizeof(A), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+        set_error("pairwise_sum: device error: %s", hipGetErrorString(hipGetLastError()));
+        return UKBB_EDEVICE;
+    }
+    size_t idx = 0;
+    volatile A acc = 0;                                 // add.reduce starts from the identity and adds one pairwise sum per buffer
+    for (uint64_t c = 0; c < n; c += NPY_BUFSIZE) {
+        const volatile A tree = pairwise_combine(leaf.data(), idx, n - c < NPY_BUFSIZE ? n - c : NPY_BUFSIZE);
+        acc = acc + tree;
+    }
+    *sum_host = acc;
+    return UKBB_OK;
+}
+
+// compaction of the elements >= thr in row-major index order (see roi_count_kernel); TH = the comparison type
+template <typename T, typename TH>
+int roi_compact_impl(const T *d_vol, int X, int Y, int Z, int T_, int64_t sx, int64_t sy, int64_t sz, int64_t st, TH thr,
+                     T *d_out, uint64_t *n_host, hipStream_t s) {
+    const long long n = (long long)X * Y * Z * T_;
+    const int nb = (int)((n + CCH - 1) / CCH);
+    Scratch *sc = prep_scratch(0);
+    void *buf = sc ? sc->get((size_t)nb * 4 + 8 + ((size_t)nb + 1) * 8) : nullptr;
+    if (!buf) { set_error("roi_compact: scratch allocation failed"); return UKBB_ENOMEM; }
+    unsigned *counts = static_cast<unsigned *>(buf);
+    unsigned long long *offs = reinterpret_cast<unsigned long long *>(static_cast<char *>(buf) + (((size_t)nb * 4 + 7) / 8) * 8);
+    hipLaunchKernelGGL((roi_count_kernel<T, TH>), dim3(nb), dim3(256), 0, s, d_vol, n, Y, Z, T_, (long long)sx, (long long)sy, (long long)sz,
+                       (long long)st, thr, counts);
+    hipLaunchKernelGGL(roi_scan_kernel, dim3(1), dim3(1024), 0, s, counts, nb, offs);
+    hipLaunchKernelGGL((roi_write_kernel<T, TH>), dim3(nb), dim3(256), 0, s, d_vol, n, Y, Z, T_, (long long)sx, (long long)sy, (long long)sz,
+                       (long long)st, thr, offs, d_out);
+    unsigned long long total = 0;
+    if (hipMemcpyAsync(&total, offs + nb, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+        set_error("roi_compact: device error: %s", hipGetErrorString(hipGetLastError()));
+        return UKBB_EDEVICE;
+    }
+    *n_host = total;
+    return UKBB_OK;
+}
+
+bool shape_ok(int X, int Y, int Z, int T, int X2, int Y2, int x_pre, int y_pre) {
+    return X >= 1 && Y >= 1 && Z >= 1 && T >= 1 && x_pre >= 0 && y_pre >= 0 && X2 >= X + x_pre && Y2 >= Y + y_pre && (long long)Z * T <= 65535;
+}
+
+// the NIfTI datatype codes of the integer volumes (those of ukbb_fcn_gzip_labels): f(tag) with decltype(tag)::type the voxel type
+template <typename U> struct Tag { using type = U; };
+template <typename F>
+int dispatch_int(int nifti_datatype, const char *who, F &&f) {
+    switch (nifti_datatype) {
+    case 2: return f(Tag<uint8_t>());
+    case 4: return f(Tag<int16_t>());
+    case 512: return f(Tag<uint16_t>());
+    default:
+        set_error("%s: NIfTI datatype %d is not supported (2 uint8, 4 int16, 512 uint16; float32 volumes take the untyped entry point)",
+                  who, nifti_datatype);
+        return UKBB_EINVAL;
+    }
 }
 
 // ---- synthetic subjects generated on the device ("generated on device from seed = subject id") ----
@@ -370,6 +499,60 @@ SelState *sel_scratch() {
     return p[d];
 }
 
+// exact order statistics of n values of type T (Key<T>::BITS / 8 radix passes); keys[r] = the key of the ranks[r]-th smallest
+template <typename T>
+int select_kth_impl(const T *d_data, size_t n, const uint64_t *ranks, int nranks, unsigned *keys, hipStream_t s) {
+    if (!d_data || !ranks || !keys || n == 0 || nranks < 1 || nranks > MAXR) {
+        set_error("select_kth: bad argument (1..8 ranks, n > 0)");
+        return UKBB_EINVAL;
+    }
+    for (int r = 0; r < nranks; ++r)
+        if (ranks[r] >= n) { set_error("select_kth: rank outside [0, n)"); return UKBB_EINVAL; }
+    SelState *st = sel_scratch();
+    if (!st) { set_error("select_kth: no HIP device / scratch allocation failed (there is no CPU fallback)"); return UKBB_EDEVICE; }
+    SelState init;
+    memset(&init, 0, sizeof init);
+    for (int r = 0; r < MAXR; ++r) init.rank[r] = ranks[r < nranks ? r : nranks - 1];
+    if (hipMemcpyAsync(st, &init, sizeof init, hipMemcpyHostToDevice, s) != hipSuccess) { set_error("select_kth: H2D failed"); return UKBB_EDEVICE; }
+    constexpr size_t V = 16 / sizeof(T);
+    size_t blocks = (n / V + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    if (blocks < 1) blocks = 1;
+    for (int shift = Key<T>::BITS - 8; shift >= 0; shift -= 8) {
+        if (nranks <= 2) hipLaunchKernelGGL((sel_hist_kernel<2, T>), dim3((unsigned)blocks), dim3(256), 0, s, d_data, n, st, shift);
+        else if (nranks <= 4) hipLaunchKernelGGL((sel_hist_kernel<4, T>), dim3((unsigned)blocks), dim3(256), 0, s, d_data, n, st, shift);
+        else hipLaunchKernelGGL((sel_hist_kernel<8, T>), dim3((unsigned)blocks), dim3(256), 0, s, d_data, n, st, shift);
+        hipLaunchKernelGGL(sel_pick_kernel, dim3(1), dim3(64), 0, s, st, MAXR, shift);
+    }
+    if (hipMemcpyAsync(keys, st->prefix, sizeof(unsigned) * MAXR, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+        set_error("select_kth: device error: %s", hipGetErrorString(hipGetLastError()));
+        return UKBB_EDEVICE;
+    }
+    return UKBB_OK;
+}
+
+template <typename T>
+int rescale_pack_impl(const T *d_vol, int X, int Y, int Z, int T_, int64_t sx, int64_t sy, int64_t sz, int64_t st, T clo, T chi,
+                      double lo, double hi, int X2, int Y2, int x_pre, int y_pre, float *d_batch, hipStream_t s) {
+    dim3 grid((unsigned)(((X2 + 31) / 32) * ((Y2 + 31) / 32)), (unsigned)(Z * T_));
+    hipLaunchKernelGGL((rescale_pack_kernel<T>), grid, dim3(256), 0, s, d_vol, X, Y, Z, T_, (long long)sx, (long long)sy,
+                       (long long)sz, (long long)st, clo, chi, lo, hi, X2, Y2, x_pre, y_pre, d_batch);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("rescale_pack: launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
+    return UKBB_OK;
+}
+
+template <typename T, typename A>
+int zscore_pack_impl(const T *d_vol, int X, int Y, int Z, int T_, int64_t sx, int64_t sy, int64_t sz, int64_t st, A mu, A den,
+                     int X2, int Y2, int x_pre, int y_pre, float *d_batch, hipStream_t s) {
+    dim3 grid((unsigned)(((X2 + 31) / 32) * ((Y2 + 31) / 32)), (unsigned)(Z * T_));
+    hipLaunchKernelGGL((zscore_pack_kernel<T, A>), grid, dim3(256), 0, s, d_vol, X, Y, Z, T_, (long long)sx, (long long)sy,
+                       (long long)sz, (long long)st, mu, den, X2, Y2, x_pre, y_pre, d_batch);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("zscore_pack: launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
+    return UKBB_OK;
+}
+
 }  // namespace
 }  // namespace ukbb
 
@@ -378,50 +561,55 @@ using namespace ukbb;
 extern "C" {
 
 int ukbb_fcn_select_kth(const float *d_data, size_t n, const uint64_t *ranks, int nranks, float *out_host, void *stream) {
-    if (!d_data || !ranks || !out_host || n == 0 || nranks < 1 || nranks > MAXR) {
-        set_error("select_kth: bad argument (1..8 ranks, n > 0)");
-        return UKBB_EINVAL;
-    }
-    for (int r = 0; r < nranks; ++r)
-        if (ranks[r] >= n) { set_error("select_kth: rank outside [0, n)"); return UKBB_EINVAL; }
-    SelState *st = sel_scratch();
-    if (!st) { set_error("select_kth: no HIP device / scratch allocation failed (there is no CPU fallback)"); return UKBB_EDEVICE; }
-    hipStream_t s = (hipStream_t)stream;
-    SelState init;
-    memset(&init, 0, sizeof init);
-    for (int r = 0; r < MAXR; ++r) init.rank[r] = ranks[r < nranks ? r : nranks - 1];
-    if (hipMemcpyAsync(st, &init, sizeof init, hipMemcpyHostToDevice, s) != hipSuccess) { set_error("select_kth: H2D failed"); return UKBB_EDEVICE; }
-    size_t blocks = (n / 4 + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    if (blocks < 1) blocks = 1;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        if (nranks <= 2) hipLaunchKernelGGL(sel_hist_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, s, d_data, n, st, shift);
-        else if (nranks <= 4) hipLaunchKernelGGL(sel_hist_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, s, d_data, n, st, shift);
-        else hipLaunchKernelGGL(sel_hist_kernel<8>, dim3((unsigned)blocks), dim3(256), 0, s, d_data, n, st, shift);
-        hipLaunchKernelGGL(sel_pick_kernel, dim3(1), dim3(64), 0, s, st, MAXR, shift);
-    }
+    if (!out_host) { set_error("select_kth: bad argument (1..8 ranks, n > 0)"); return UKBB_EINVAL; }
     unsigned keys[MAXR];
-    if (hipMemcpyAsync(keys, st->prefix, sizeof keys, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-        set_error("select_kth: device error: %s", hipGetErrorString(hipGetLastError()));
-        return UKBB_EDEVICE;
-    }
+    const int rc = select_kth_impl(d_data, n, ranks, nranks, keys, (hipStream_t)stream);
+    if (rc != UKBB_OK) return rc;
     for (int r = 0; r < nranks; ++r) out_host[r] = fkey_inv(keys[r]);
     return UKBB_OK;
 }
 
+int ukbb_fcn_select_kth_t(const void *d_data, int nifti_datatype, size_t n, const uint64_t *ranks, int nranks, double *out_host, void *stream) {
+    return dispatch_int(nifti_datatype, "select_kth_t", [&](auto tag) {
+        using V = typename decltype(tag)::type;
+        if (!out_host || (reinterpret_cast<uintptr_t>(d_data) & 15)) {
+            set_error("select_kth_t: bad argument (NULL result, or data not 16-byte aligned)");
+            return UKBB_EINVAL;
+        }
+        unsigned keys[MAXR];
+        const int rc = select_kth_impl(static_cast<const V *>(d_data), n, ranks, nranks, keys, (hipStream_t)stream);
+        if (rc != UKBB_OK) return rc;
+        for (int r = 0; r < nranks; ++r) out_host[r] = Key<V>::value(keys[r]);
+        return UKBB_OK;
+    });
+}
+
 int ukbb_fcn_rescale_pack(const float *d_vol, int X, int Y, int Z, int T, int64_t sx, int64_t sy, int64_t sz, int64_t st,
                           double lo, double hi, int X2, int Y2, int x_pre, int y_pre, float *d_batch, void *stream) {
-    if (!d_vol || !d_batch || X < 1 || Y < 1 || Z < 1 || T < 1 || x_pre < 0 || y_pre < 0 || X2 < X + x_pre || Y2 < Y + y_pre ||
-        (long long)Z * T > 65535) {
+    if (!d_vol || !d_batch || !shape_ok(X, Y, Z, T, X2, Y2, x_pre, y_pre)) {
         set_error("rescale_pack: bad shape X=%d Y=%d Z=%d T=%d X2=%d Y2=%d pre=(%d,%d) (Z*T <= 65535)", X, Y, Z, T, X2, Y2, x_pre, y_pre);
         return UKBB_EINVAL;
     }
-    dim3 grid((unsigned)(((X2 + 31) / 32) * ((Y2 + 31) / 32)), (unsigned)(Z * T));
-    hipLaunchKernelGGL(rescale_pack_kernel, grid, dim3(256), 0, (hipStream_t)stream, d_vol, X, Y, Z, T, (long long)sx, (long long)sy,
-                       (long long)sz, (long long)st, lo, hi, X2, Y2, x_pre, y_pre, d_batch);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("rescale_pack: launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
-    return UKBB_OK;
+    // what the in-place clip stores into the float32 array: the bounds rounded to float32
+    return rescale_pack_impl(d_vol, X, Y, Z, T, sx, sy, sz, st, (float)lo, (float)hi, lo, hi, X2, Y2, x_pre, y_pre, d_batch, (hipStream_t)stream);
+}
+
+int ukbb_fcn_rescale_pack_t(const void *d_vol, int nifti_datatype, int X, int Y, int Z, int T, int64_t sx, int64_t sy, int64_t sz, int64_t st,
+                            int64_t clip_lo, int64_t clip_hi, double lo, double hi, int X2, int Y2, int x_pre, int y_pre, float *d_batch,
+                            void *stream) {
+    return dispatch_int(nifti_datatype, "rescale_pack_t", [&](auto tag) {
+        using V = typename decltype(tag)::type;
+        if (!d_vol || !d_batch || !shape_ok(X, Y, Z, T, X2, Y2, x_pre, y_pre)) {
+            set_error("rescale_pack_t: bad shape X=%d Y=%d Z=%d T=%d X2=%d Y2=%d pre=(%d,%d) (Z*T <= 65535)", X, Y, Z, T, X2, Y2, x_pre, y_pre);
+            return UKBB_EINVAL;
+        }
+        if (clip_lo != (int64_t)(V)clip_lo || clip_hi != (int64_t)(V)clip_hi) {
+            set_error("rescale_pack_t: clip bounds %lld, %lld outside the voxel type", (long long)clip_lo, (long long)clip_hi);
+            return UKBB_EINVAL;
+        }
+        return rescale_pack_impl(static_cast<const V *>(d_vol), X, Y, Z, T, sx, sy, sz, st, (V)clip_lo, (V)clip_hi, lo, hi, X2, Y2, x_pre,
+                                 y_pre, d_batch, (hipStream_t)stream);
+    });
 }
 
 int ukbb_fcn_unpack_labels(const int32_t *d_pred, int X, int Y, int Z, int T, int X2, int Y2, int x_pre, int y_pre, int n_class,
@@ -444,57 +632,30 @@ int ukbb_fcn_unpack_labels(const int32_t *d_pred, int X, int Y, int Z, int T, in
 int ukbb_fcn_roi_compact(const float *d_vol, int X, int Y, int Z, int T, int64_t sx, int64_t sy, int64_t sz, int64_t st, float thr,
                          float *d_out, uint64_t *n_host, void *stream) {
     if (!d_vol || !d_out || !n_host || X < 1 || Y < 1 || Z < 1 || T < 1) { set_error("roi_compact: bad argument"); return UKBB_EINVAL; }
-    const long long n = (long long)X * Y * Z * T;
-    const int nb = (int)((n + CCH - 1) / CCH);
-    Scratch *sc = prep_scratch(0);
-    void *buf = sc ? sc->get((size_t)nb * 4 + 8 + ((size_t)nb + 1) * 8) : nullptr;
-    if (!buf) { set_error("roi_compact: scratch allocation failed"); return UKBB_ENOMEM; }
-    unsigned *counts = static_cast<unsigned *>(buf);
-    unsigned long long *offs = reinterpret_cast<unsigned long long *>(static_cast<char *>(buf) + (((size_t)nb * 4 + 7) / 8) * 8);
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(roi_count_kernel, dim3(nb), dim3(256), 0, s, d_vol, n, Y, Z, T, (long long)sx, (long long)sy, (long long)sz, (long long)st, thr, counts);
-    hipLaunchKernelGGL(roi_scan_kernel, dim3(1), dim3(1024), 0, s, counts, nb, offs);
-    hipLaunchKernelGGL(roi_write_kernel, dim3(nb), dim3(256), 0, s, d_vol, n, Y, Z, T, (long long)sx, (long long)sy, (long long)sz, (long long)st, thr, offs, d_out);
-    unsigned long long total = 0;
-    if (hipMemcpyAsync(&total, offs + nb, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-        set_error("roi_compact: device error: %s", hipGetErrorString(hipGetLastError()));
-        return UKBB_EDEVICE;
-    }
-    *n_host = total;
-    return UKBB_OK;
+    return roi_compact_impl(d_vol, X, Y, Z, T, sx, sy, sz, st, thr, d_out, n_host, (hipStream_t)stream);
+}
+
+int ukbb_fcn_roi_compact_t(const void *d_vol, int nifti_datatype, int X, int Y, int Z, int T, int64_t sx, int64_t sy, int64_t sz, int64_t st,
+                           double thr, void *d_out, uint64_t *n_host, void *stream) {
+    return dispatch_int(nifti_datatype, "roi_compact_t", [&](auto tag) {
+        using V = typename decltype(tag)::type;
+        if (!d_vol || !d_out || !n_host || X < 1 || Y < 1 || Z < 1 || T < 1) { set_error("roi_compact_t: bad argument"); return UKBB_EINVAL; }
+        return roi_compact_impl(static_cast<const V *>(d_vol), X, Y, Z, T, sx, sy, sz, st, thr, static_cast<V *>(d_out), n_host,
+                                (hipStream_t)stream);
+    });
 }
 
 int ukbb_fcn_pairwise_sum(const float *d_a, uint64_t n, int squared_dev, float mean, float *sum_host, void *stream) {
     if (!d_a || !sum_host) { set_error("pairwise_sum: NULL argument"); return UKBB_EINVAL; }
-    if (n == 0) { *sum_host = 0.f; return UKBB_OK; }
-    std::vector<unsigned long long> offs;
-    std::vector<unsigned> lens;
-    offs.reserve((size_t)(n / 64) + 2); lens.reserve((size_t)(n / 64) + 2);
-    for (uint64_t c = 0; c < n; c += NPY_BUFSIZE) pairwise_leaves(c, n - c < NPY_BUFSIZE ? n - c : NPY_BUFSIZE, offs, lens);
-    const size_t nl = offs.size();
-    Scratch *sc = prep_scratch(1);
-    char *buf = sc ? static_cast<char *>(sc->get(nl * 16)) : nullptr;
-    if (!buf) { set_error("pairwise_sum: scratch allocation failed"); return UKBB_ENOMEM; }
-    unsigned long long *d_off = reinterpret_cast<unsigned long long *>(buf);
-    unsigned *d_len = reinterpret_cast<unsigned *>(buf + nl * 8);
-    float *d_sum = reinterpret_cast<float *>(buf + nl * 12);
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<float> leaf(nl);
-    if (hipMemcpyAsync(d_off, offs.data(), nl * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(d_len, lens.data(), nl * 4, hipMemcpyHostToDevice, s) != hipSuccess) { set_error("pairwise_sum: H2D failed"); return UKBB_EDEVICE; }
-    hipLaunchKernelGGL(pairwise_leaf_kernel, dim3((unsigned)((nl + 127) / 128)), dim3(128), 0, s, d_a, d_off, d_len, (int)nl, squared_dev, mean, d_sum);
-    if (hipMemcpyAsync(leaf.data(), d_sum, nl * 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-        set_error("pairwise_sum: device error: %s", hipGetErrorString(hipGetLastError()));
-        return UKBB_EDEVICE;
-    }
-    size_t idx = 0;
-    volatile float acc = 0.f;                           // add.reduce starts from the identity and adds one pairwise sum per buffer
-    for (uint64_t c = 0; c < n; c += NPY_BUFSIZE) {
-        const volatile float tree = pairwise_combine(leaf.data(), idx, n - c < NPY_BUFSIZE ? n - c : NPY_BUFSIZE);
-        acc = acc + tree;
-    }
-    *sum_host = acc;
-    return UKBB_OK;
+    return pairwise_sum_impl(d_a, n, squared_dev, mean, sum_host, (hipStream_t)stream);
+}
+
+int ukbb_fcn_pairwise_sum_t(const void *d_a, int nifti_datatype, uint64_t n, int squared_dev, double mean, double *sum_host, void *stream) {
+    return dispatch_int(nifti_datatype, "pairwise_sum_t", [&](auto tag) {
+        using V = typename decltype(tag)::type;
+        if (!d_a || !sum_host) { set_error("pairwise_sum_t: NULL argument"); return UKBB_EINVAL; }
+        return pairwise_sum_impl(static_cast<const V *>(d_a), n, squared_dev, mean, sum_host, (hipStream_t)stream);
+    });
 }
 
 // ---- shader clock under load (measurement only) ----
@@ -526,17 +687,24 @@ int ukbb_fcn_clock_probe(int device, void *stream, int spin_us, double *mhz) {
 
 int ukbb_fcn_zscore_pack(const float *d_vol, int X, int Y, int Z, int T, int64_t sx, int64_t sy, int64_t sz, int64_t st,
                          float mu, float den, int X2, int Y2, int x_pre, int y_pre, float *d_batch, void *stream) {
-    if (!d_vol || !d_batch || X < 1 || Y < 1 || Z < 1 || T < 1 || x_pre < 0 || y_pre < 0 || X2 < X + x_pre || Y2 < Y + y_pre ||
-        (long long)Z * T > 65535) {
+    if (!d_vol || !d_batch || !shape_ok(X, Y, Z, T, X2, Y2, x_pre, y_pre)) {
         set_error("zscore_pack: bad shape X=%d Y=%d Z=%d T=%d X2=%d Y2=%d pre=(%d,%d) (Z*T <= 65535)", X, Y, Z, T, X2, Y2, x_pre, y_pre);
         return UKBB_EINVAL;
     }
-    dim3 grid((unsigned)(((X2 + 31) / 32) * ((Y2 + 31) / 32)), (unsigned)(Z * T));
-    hipLaunchKernelGGL(zscore_pack_kernel, grid, dim3(256), 0, (hipStream_t)stream, d_vol, X, Y, Z, T, (long long)sx, (long long)sy,
-                       (long long)sz, (long long)st, mu, den, X2, Y2, x_pre, y_pre, d_batch);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("zscore_pack: launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
-    return UKBB_OK;
+    return zscore_pack_impl(d_vol, X, Y, Z, T, sx, sy, sz, st, mu, den, X2, Y2, x_pre, y_pre, d_batch, (hipStream_t)stream);
+}
+
+int ukbb_fcn_zscore_pack_t(const void *d_vol, int nifti_datatype, int X, int Y, int Z, int T, int64_t sx, int64_t sy, int64_t sz, int64_t st,
+                           double mu, double den, int X2, int Y2, int x_pre, int y_pre, float *d_batch, void *stream) {
+    return dispatch_int(nifti_datatype, "zscore_pack_t", [&](auto tag) {
+        using V = typename decltype(tag)::type;
+        if (!d_vol || !d_batch || !shape_ok(X, Y, Z, T, X2, Y2, x_pre, y_pre)) {
+            set_error("zscore_pack_t: bad shape X=%d Y=%d Z=%d T=%d X2=%d Y2=%d pre=(%d,%d) (Z*T <= 65535)", X, Y, Z, T, X2, Y2, x_pre, y_pre);
+            return UKBB_EINVAL;
+        }
+        return zscore_pack_impl(static_cast<const V *>(d_vol), X, Y, Z, T, sx, sy, sz, st, mu, den, X2, Y2, x_pre, y_pre, d_batch,
+                                (hipStream_t)stream);
+    });
 }
 
 // ---- debugging aid (r06): fill every CU's LDS with a bit pattern.  LDS is not cleared between workgroups; a kernel that reads LDS it never wrote

@@ -46,7 +46,7 @@ def define_flags():
                       'LOCAL_RANK under torch.distributed.run.')
     fs.DEFINE_integer('batch_slices', 128, 'Slices per forward call.')
     fs.DEFINE_boolean('device_preproc', True, 'Percentile rescale, padding, transposes and label counting on the GPU '
-                      '(float32 sequences; results identical to the host path).')
+                      '(float32, uint8, int16 and uint16 sequences; results identical to the host path).')
     fs.DEFINE_boolean('numpy1_casting', False, 'Rescale intensities with the float32 arithmetic numpy 1.x used when the reference '
                       'was written (1 ulp from numpy 2; host pre-processing only; INTEGRATION.md section 5).')
     fs.DEFINE_integer('io_threads', int(os.environ.get('UKBB_IO_THREADS', 8)), 'Reader threads (gzip NIfTI -> pinned staging) and writer threads (float64 label volume, gzip) '
@@ -80,6 +80,23 @@ def save_sequence_outputs(data_dir, pre, seq, affine, pixdim, pred, frames):
     # file nifti.save writes -- appears under its name only when complete (tmp file + os.replace): a worker killed
     # anywhere in here leaves a subject that the rerun segments again, never a half-written one that it skips.
     nifti.save(pred, '{0}/{1}_{2}.nii.gz'.format(data_dir, pre, seq), affine, pixdim, as_dtype=np.float64)
+
+
+def pipelined_on_device(image):
+    """run_pipelined: does this subject go through the subject pipeline (else: drain, then the sequential path)?  4-D
+    float32, uint8, int16 or uint16 volumes; float64 (every file with a non-trivial scl_slope) and the other integer types
+    stay on the host."""
+    from ukbb_cardiac_amd import device_pipeline
+    return image.ndim == 4 and device_pipeline.device_dtype_ok(image.dtype)
+
+
+def sequence_on_device(FLAGS, engine, image):
+    """_sequence_subject: device pre-processing (device_pipeline.segment_sequence_device) for this subject?  Needs an engine,
+    --device_preproc, not --numpy1_casting (its float32 arithmetic is host only), and a dtype the device reproduces."""
+    if engine is None or not getattr(FLAGS, 'device_preproc', False) or getattr(FLAGS, 'numpy1_casting', False):
+        return False
+    from ukbb_cardiac_amd import device_pipeline
+    return device_pipeline.device_dtype_ok(image.dtype)
 
 
 def run_pipelined(FLAGS, engine, data_list, log=print, csv_rows=None, queue=None):
@@ -127,7 +144,7 @@ def run_pipelined(FLAGS, engine, data_list, log=print, csv_rows=None, queue=None
     mk = threading.Lock()
 
     def alloc(shape, dt):
-        if len(shape) == 4 and dt == np.float32:
+        if len(shape) == 4 and device_pipeline.device_dtype_ok(dt):
             with mk:
                 if state['pipe'] is None:                  # sized by the first volume; bigger ones fall back below
                     state['pipe'] = SubjectPipeline(engine, shape, FLAGS.batch_slices, depth=depth, extra_inputs=window)
@@ -208,7 +225,7 @@ def run_pipelined(FLAGS, engine, data_list, log=print, csv_rows=None, queue=None
             nim, _ = fut.result()
             image = nim.get_data()
             pipe = state['pipe']
-            if image.ndim != 4 or image.dtype != np.float32 or pipe is None or image.size > pipe._in_cap:
+            if not pipelined_on_device(image) or pipe is None or image.size > pipe._in_cap:
                 while inflight:                             # odd subject: drain, then take the sequential path
                     finish(*inflight.pop(0))
                 log(item[0])
@@ -246,7 +263,7 @@ def _sequence_subject(FLAGS, item, nim, forward, engine, log, processed, table_t
     log('  Segmenting full sequence ...')
     t0 = time.time()
     np1 = bool(getattr(FLAGS, 'numpy1_casting', False))
-    on_device = engine is not None and getattr(FLAGS, 'device_preproc', False) and image.dtype == np.float32 and not np1
+    on_device = sequence_on_device(FLAGS, engine, image)
     if on_device:
         from ukbb_cardiac_amd import device_pipeline
         pred, aux = device_pipeline.segment_sequence_device(image, engine, FLAGS.batch_slices, return_aux=True)

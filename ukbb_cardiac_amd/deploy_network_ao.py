@@ -46,7 +46,7 @@ def define_flags():
     fs.DEFINE_integer('io_threads', min(2, int(os.environ.get('UKBB_IO_THREADS', 2))), 'Sequence mode: threads that read (inflate) the next cines ahead of the GPU and threads that '
                       'write finished segmentations behind it; 0 = strictly sequential subjects as in the reference.')
     fs.DEFINE_boolean('device_preproc', True, 'Sequences: z-score, padding, transposes and the argmax on the GPU '
-                      '(bit-identical to the host path; --nodevice_preproc restores it).')
+                      '(float32, uint8, int16 and uint16 cines; bit-identical to the host path; --nodevice_preproc restores it).')
     fs.DEFINE_enum('precision', 'fp32', ['fp32', 'bf16'], 'Arithmetic of the U-Net convolutions: fp32 MFMA (default) or bf16 MFMA operands with fp32 '
                    'accumulation (UKBB_PREC_BF16, include/ukbb_fcn.h; --model UNet: bf16 activations in HBM too, 2.8x the fp32 rate, '
                    'Dice 0.99 against fp32; BASELINE config 5.  Default UNet-LSTM model: the same U-Net plan, ConvLSTM on the bf16 matrix '
@@ -78,6 +78,18 @@ def _pp(central_pp, data, log=print):
         # the reference's central_pp.loc[int(data)] raises KeyError here and the whole evaluation stops; this script keeps the areas
         log('  Warning: subject {0} is not in the pressure spreadsheet: distensibility left empty.'.format(data))
     return central_pp.get(key, float('nan'))
+
+
+def sequence_on_device(FLAGS, engine, image, log=print):
+    """Does this cine take the device pre-processing?  Needs an engine, --device_preproc, --z_score, a 4-D float32, uint8,
+    int16 or uint16 volume, and the once-per-dtype check that the device z-score reproduces this numpy (it mirrors numpy
+    internals; a mismatch keeps the host path and is logged)."""
+    if engine is None or not getattr(FLAGS, 'device_preproc', False) or not FLAGS.z_score or image.ndim != 4:
+        return False
+    from ukbb_cardiac_amd import device_pipeline
+    if not device_pipeline.device_dtype_ok(image.dtype):
+        return False
+    return device_pipeline.device_zscore_matches_numpy(engine, warn=log, dtype=image.dtype)
 
 
 def run(FLAGS, forward, log=print, cine_forward=None, engine=None):
@@ -156,11 +168,7 @@ def run(FLAGS, forward, log=print, cine_forward=None, engine=None):
             image = nim.get_data()
             log('  Segmenting full sequence ...')
             t0 = time.time()
-            on_device = (engine is not None and getattr(FLAGS, 'device_preproc', False)
-                         and FLAGS.z_score and image.ndim == 4 and image.dtype == np.float32)
-            if on_device:                                         # the device z-score mirrors numpy internals: verify once
-                from ukbb_cardiac_amd.device_pipeline import device_zscore_matches_numpy
-                on_device = device_zscore_matches_numpy(engine, warn=log)
+            on_device = sequence_on_device(FLAGS, engine, image, log)
             counts = None
             if on_device and windowed:
                 from ukbb_cardiac_amd.device_pipeline import aortic_lstm_sequence_device

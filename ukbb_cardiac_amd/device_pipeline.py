@@ -11,6 +11,10 @@ label transposes plus the per-frame class counts of the ES pick (:125-130) anoth
 numpy's ``percentile(..., method='linear')`` is reproduced bit for bit: the device returns the two
 neighbouring order statistics of each percentile, and the interpolation between them is done here
 by numpy itself (``np.quantile`` on the two-element array with the same fractional index).
+
+Volumes may be float32 or one of the integer types MR converters write (uint8, int16, uint16:
+``NIFTI_DATATYPE``); integer volumes follow numpy's integer arithmetic (``*_int`` helpers below,
+the ``*_t`` entry points of include/ukbb_fcn.h).  Any other dtype raises ``TypeError``.
 """
 import ctypes as C
 import math
@@ -19,6 +23,29 @@ import numpy as np
 
 from . import _lib
 from .pipeline import pad_amounts, pad_amounts_fixed
+
+# integer voxel types the device pre-processing takes, with their NIfTI datatype codes (those of ukbb_fcn_gzip_labels)
+NIFTI_DATATYPE = {np.dtype(np.uint8): 2, np.dtype(np.int16): 4, np.dtype(np.uint16): 512}
+
+
+def device_dtype_ok(dtype):
+    """Is a volume of this dtype pre-processed on the device (float32 or one of NIFTI_DATATYPE)?"""
+    return np.dtype(dtype) == np.float32 or np.dtype(dtype) in NIFTI_DATATYPE
+
+
+def _check_dtype(image, host_alternative):
+    if not device_dtype_ok(image.dtype):
+        raise TypeError('device pre-processing is exact for float32, uint8, int16 and uint16 volumes only (got %s); use %s'
+                        % (image.dtype, host_alternative))
+
+
+def _to_device(image, dev):
+    """Dense device copy of a host volume, strides preserved (a uint16 volume travels as int16: same bytes, a dtype torch has)."""
+    import torch
+    src = image if (image.flags.f_contiguous or image.flags.c_contiguous) else np.asfortranarray(image)
+    if src.dtype == np.uint16:
+        src = src.view(np.int16)
+    return torch.from_numpy(src).to(dev)
 
 
 def percentile_ranks(n, q):
@@ -39,44 +66,102 @@ def lerp_like_numpy(a_k, a_k1, gamma):
     return np.quantile(np.array([a_k, a_k1], dtype=np.float32), np.array([gamma], dtype=np.float64))[0]
 
 
-def device_percentiles(vol_t, qs, stream=0):
-    """Exact np.percentile(volume, qs) of a dense float32 torch tensor on the GPU."""
-    n = vol_t.numel()
+def percentile_ranks_int(n, q):
+    """percentile_ranks for an INTEGER array: numpy divides q by the Python int 100 there (only float arrays get a divisor of
+    their own dtype), so a scalar q and a tuple q both take float64 quantiles and a float64 virtual index (n - 1) * quantile --
+    the float32 route of ``scalar_percentile_ranks`` does not exist for integer data.  Returns (k, k1, gamma) as numpy's
+    _get_indexes / _get_gamma form them, including the top end: a virtual index >= n - 1 takes the last element (k = k1 =
+    n - 1; gamma is then irrelevant, the two neighbours are equal)."""
+    quantile = np.true_divide(q, 100)
+    virtual = (n - 1) * quantile
+    if virtual >= n - 1:
+        return n - 1, n - 1, np.float64(0.0)
+    k = int(math.floor(virtual))
+    return k, k + 1, np.float64(virtual - k)
+
+
+def lerp_like_numpy_int(a_k, a_k1, gamma, dtype):
+    """np.percentile's interpolation between the neighbouring order statistics a[k] <= a[k+1] of an integer array: a float64
+    result.  numpy's _lerp takes their difference IN THE INTEGER TYPE first (int16 neighbours more than 32767 apart wrap
+    around), which numpy itself reproduces on the two-element array of that dtype with the same fractional index."""
+    pair = np.array([a_k, a_k1], dtype=dtype)
+    return np.quantile(pair, np.array([gamma], dtype=np.float64))[0]
+
+
+def clip_bounds_int(lo, hi, dtype):
+    """What image[image < lo] = lo / image[image > hi] = hi store into an integer array: the float64 bounds truncated toward
+    zero (numpy's unsafe cast)."""
+    b = np.array([lo, hi], dtype=np.float64).astype(dtype)
+    return int(b[0]), int(b[1])
+
+
+def _select(vol_t, dtype, ranks, stream, n=None):
+    """The ranks-th smallest values of the first n (default: all) elements of a device tensor, in the volume's dtype
+    (exact radix select)."""
+    n = vol_t.numel() if n is None else n
+    r = (C.c_uint64 * len(ranks))(*ranks)
+    if np.dtype(dtype) == np.float32:
+        out = np.empty(len(ranks), np.float32)
+        _lib.check(_lib.lib.ukbb_fcn_select_kth(vol_t.data_ptr(), n, r, len(ranks), _lib.f32ptr(out), stream), 'ukbb_fcn_select_kth')
+        return out
+    out = np.empty(len(ranks), np.float64)
+    _lib.check(_lib.lib.ukbb_fcn_select_kth_t(vol_t.data_ptr(), NIFTI_DATATYPE[np.dtype(dtype)], n, r, len(ranks),
+                                              out.ctypes.data_as(C.POINTER(C.c_double)), stream), 'ukbb_fcn_select_kth_t')
+    return out.astype(dtype)
+
+
+def device_percentiles(vol_t, qs, stream=0, dtype=np.float32, n=None):
+    """Exact np.percentile(volume, qs) of a dense torch tensor on the GPU; ``dtype``: the host volume's dtype (float32, or
+    an integer type of NIFTI_DATATYPE -- a uint16 volume is an int16 tensor on the device); ``n``: the number of voxels when
+    the volume fills only the start of the tensor (a staging buffer, whatever its torch dtype)."""
+    n = vol_t.numel() if n is None else n
+    integer = np.dtype(dtype) != np.float32
     ranks, gammas = [], []
     for q in qs:
-        k, k1, g = percentile_ranks(n, q)
+        k, k1, g = percentile_ranks_int(n, q) if integer else percentile_ranks(n, q)
         ranks += [k, k1]
         gammas.append(g)
-    r = (C.c_uint64 * len(ranks))(*ranks)
-    out = np.empty(len(ranks), np.float32)
-    _lib.check(_lib.lib.ukbb_fcn_select_kth(vol_t.data_ptr(), n, r, len(ranks), _lib.f32ptr(out), stream), 'ukbb_fcn_select_kth')
+    out = _select(vol_t, dtype, ranks, stream, n)
+    if integer:
+        return [lerp_like_numpy_int(out[2 * i], out[2 * i + 1], gammas[i], dtype) for i in range(len(qs))]
     return [lerp_like_numpy(out[2 * i], out[2 * i + 1], gammas[i]) for i in range(len(qs))]
 
 
+def pack_rescaled(vol_ptr, dtype, shape, strides, lo, hi, pad, batch_ptr, stream):
+    """Clip + rescale + pad + transpose of a device (X,Y,Z,T) volume (element strides) into the network batch [T*Z][X2][Y2]:
+    ukbb_fcn_rescale_pack, or for an integer volume ukbb_fcn_rescale_pack_t with the truncated clip bounds.
+    pad = (X2, Y2, x_pre, y_pre)."""
+    if np.dtype(dtype) == np.float32:
+        _lib.check(_lib.lib.ukbb_fcn_rescale_pack(vol_ptr, *shape, *strides, float(lo), float(hi), *pad, batch_ptr, stream),
+                   'ukbb_fcn_rescale_pack')
+        return
+    clo, chi = clip_bounds_int(lo, hi, dtype)
+    _lib.check(_lib.lib.ukbb_fcn_rescale_pack_t(vol_ptr, NIFTI_DATATYPE[np.dtype(dtype)], *shape, *strides, clo, chi, float(lo), float(hi),
+                                                *pad, batch_ptr, stream), 'ukbb_fcn_rescale_pack_t')
+
+
 def segment_sequence_device(image, engine, batch_slices=128, thres=(1, 99), return_aux=False):
-    """(X,Y,Z,T) float32 volume -> float64 label volume of the same shape, like pipeline.segment_sequence.
+    """(X,Y,Z,T) float32 / uint8 / int16 / uint16 volume -> float64 label volume of the same shape, like
+    pipeline.segment_sequence.
 
     ``image`` is NOT modified (the reference clips it in place); callers that
-    save image frames afterwards clip them with the returned bounds (``aux['clip']``).
+    save image frames afterwards clip them with the returned bounds (``aux['clip']``: the float64
+    percentiles; clip_like_reference stores them into an integer frame truncated, as numpy does).
     ``aux['counts'][t, c]`` = voxels of class c in frame t (input of the ES pick)."""
     import torch
     if image.ndim != 4:
         raise ValueError('expected a 4-D (X,Y,Z,T) sequence, got shape %s' % (image.shape,))
-    if image.dtype != np.float32:
-        raise TypeError('device pre-processing is exact for float32 volumes only (got %s); use pipeline.segment_sequence'
-                        % image.dtype)
+    _check_dtype(image, 'pipeline.segment_sequence')
     X, Y, Z, T = image.shape
     dev = torch.device('cuda', engine.device)
     stream = torch.cuda.current_stream(dev).cuda_stream
-    src = image if (image.flags.f_contiguous or image.flags.c_contiguous) else np.asfortranarray(image)
-    vol = torch.from_numpy(src).to(dev)                          # dense copy, strides preserved
-    lo, hi = device_percentiles(vol, thres, stream)
+    vol = _to_device(image, dev)                                 # dense copy, strides preserved
+    lo, hi = device_percentiles(vol, thres, stream, image.dtype)
     X2, Y2, x_pre, _, y_pre, _ = pad_amounts(X, Y)
     n = T * Z
     batch = torch.empty((n, X2, Y2), dtype=torch.float32, device=dev)
     sx, sy, sz, st = vol.stride()
-    _lib.check(_lib.lib.ukbb_fcn_rescale_pack(vol.data_ptr(), X, Y, Z, T, sx, sy, sz, st, float(lo), float(hi),
-                                              X2, Y2, x_pre, y_pre, batch.data_ptr(), stream), 'ukbb_fcn_rescale_pack')
+    pack_rescaled(vol.data_ptr(), image.dtype, (X, Y, Z, T), (sx, sy, sz, st), lo, hi, (X2, Y2, x_pre, y_pre), batch.data_ptr(), stream)
     pred = torch.empty((n, X2, Y2), dtype=torch.int32, device=dev)
     engine.reserve(min(batch_slices, n), X2, Y2)
     for i in range(0, n, batch_slices):
@@ -138,11 +223,15 @@ def device_scalar_percentile(vol_t, q, stream=0):
     return np.quantile(out, g)
 
 
-def device_zscore_stats(vol_t, thres_roi=10.0, stream=0):
-    """(mu, sigma + eps, n_roi, val_l) of image_utils.normalise_intensity for a dense float32 (X,Y,Z,T) torch tensor on the
+def device_zscore_stats(vol_t, thres_roi=10.0, stream=0, dtype=np.float32):
+    """(mu, sigma + eps, n_roi, val_l) of image_utils.normalise_intensity for a dense (X,Y,Z,T) torch tensor on the
     GPU, bit-identical to numpy: the ROI is compacted in numpy's element order and summed along numpy's pairwise tree
-    (``ukbb_fcn_roi_compact`` / ``ukbb_fcn_pairwise_sum``); the few scalar operations around the sums are numpy's own."""
+    (``ukbb_fcn_roi_compact`` / ``ukbb_fcn_pairwise_sum``); the few scalar operations around the sums are numpy's own.
+    ``dtype``: the host volume's dtype.  float32: float32 sums and results, as numpy.  An integer type of NIFTI_DATATYPE:
+    float64 threshold, float64 sums (the plain one exact), float64 mu and sigma + eps (the ``*_t`` entry points)."""
     import torch
+    if np.dtype(dtype) != np.float32:
+        return _device_zscore_stats_int(vol_t, thres_roi, stream, np.dtype(dtype))
     X, Y, Z, T = vol_t.shape
     val_l = device_scalar_percentile(vol_t, thres_roi, stream)
     roi = torch.empty(vol_t.numel(), dtype=torch.float32, device=vol_t.device)
@@ -161,33 +250,89 @@ def device_zscore_stats(vol_t, thres_roi=10.0, stream=0):
     return mu, sigma + 1e-6, int(n), val_l                   # float32 + Python float stays float32 (image_utils.py:66-67)
 
 
+def _device_zscore_stats_int(vol_t, thres_roi, stream, dtype):
+    """device_zscore_stats of an integer volume.  numpy there: val_l = float64 percentile (float64 quantile whether q is a
+    scalar or not), roi = image >= val_l compared in float64, np.mean / np.std reduce with dtype float64 -- the plain sum of
+    8/16-bit values is exact in any order (every partial sum an integer below 2^53), the sum of (x - mu)^2 follows numpy's
+    pairwise tree -- and divide by the intp count: everything float64."""
+    import torch
+    X, Y, Z, T = vol_t.shape
+    code = NIFTI_DATATYPE[dtype]
+    n_all = vol_t.numel()
+    k, k1, g = percentile_ranks_int(n_all, thres_roi)
+    a = _select(vol_t, dtype, [k, k1], stream)
+    val_l = lerp_like_numpy_int(a[0], a[1], g, dtype)
+    roi = torch.empty(n_all, dtype=vol_t.dtype, device=vol_t.device)
+    sx, sy, sz, st = vol_t.stride()
+    n_roi = C.c_uint64(0)
+    _lib.check(_lib.lib.ukbb_fcn_roi_compact_t(vol_t.data_ptr(), code, X, Y, Z, T, sx, sy, sz, st, float(val_l), roi.data_ptr(),
+                                               C.byref(n_roi), stream), 'ukbb_fcn_roi_compact_t')
+    n = np.intp(n_roi.value)
+    s = C.c_double(0)
+    _lib.check(_lib.lib.ukbb_fcn_pairwise_sum_t(roi.data_ptr(), code, int(n), 0, 0.0, C.byref(s), stream), 'ukbb_fcn_pairwise_sum_t')
+    with np.errstate(all='ignore'):
+        mu = np.float64(np.float64(s.value) / n)              # np.mean: float64 sum / intp count
+        _lib.check(_lib.lib.ukbb_fcn_pairwise_sum_t(roi.data_ptr(), code, int(n), 1, float(mu), C.byref(s), stream),
+                   'ukbb_fcn_pairwise_sum_t')
+        var = np.float64(np.float64(s.value) / n)             # np.var: float64 sum of squared deviations / intp count
+        sigma = np.sqrt(var)
+    return mu, sigma + 1e-6, int(n), val_l
+
+
+def zscore_pack(vol_ptr, dtype, shape, strides, mu, den, pad, batch_ptr, stream):
+    """(v - mu) / den + pad + transpose of a device (X,Y,Z,T) volume into [T*Z][X2][Y2]: ukbb_fcn_zscore_pack (float32
+    arithmetic) or, for an integer volume, ukbb_fcn_zscore_pack_t (float64 arithmetic).  pad = (X2, Y2, x_pre, y_pre)."""
+    if np.dtype(dtype) == np.float32:
+        _lib.check(_lib.lib.ukbb_fcn_zscore_pack(vol_ptr, *shape, *strides, float(mu), float(den), *pad, batch_ptr, stream),
+                   'ukbb_fcn_zscore_pack')
+        return
+    _lib.check(_lib.lib.ukbb_fcn_zscore_pack_t(vol_ptr, NIFTI_DATATYPE[np.dtype(dtype)], *shape, *strides, float(mu), float(den),
+                                               *pad, batch_ptr, stream), 'ukbb_fcn_zscore_pack_t')
+
+
 _ZSCORE_OK = {}
 
 
-def device_zscore_matches_numpy(engine, warn=None):
-    """Once per process and device: does the device z-score reproduce THIS numpy?  ``device_zscore_stats`` mirrors numpy
+def _zscore_probe(dtype):
+    """A 26 k-voxel probe volume of the dtype: more than three reduction buffers, ROI not a multiple of anything, ties."""
+    rng = np.random.default_rng(20261003)
+    probe = 1000.0 * rng.gamma(2.0, 1.0, size=(37, 29, 1, 25))
+    if dtype == np.float32:
+        return probe.astype(np.float32)
+    info = np.iinfo(dtype)
+    scale = 1.0 if info.max > 10000 else 0.05                   # uint8: squeeze into 0..255 (many ties)
+    if dtype == np.int16:
+        probe -= 300.0                                          # negative intensities too
+    return np.clip(np.round(probe * scale), info.min, info.max).astype(dtype)
+
+
+def device_zscore_matches_numpy(engine, warn=None, dtype=np.float32):
+    """Once per process, device and dtype: does the device z-score reproduce THIS numpy?  ``device_zscore_stats`` mirrors numpy
     internals -- the 8192-element buffering and the 128-element / 8-accumulator pairwise leaves of ``np.add.reduce``, the float32
-    handling of a scalar percentile -- that ``np.setbufsize`` or another numpy release can change without notice.  A
-    26 k-voxel probe (more than three reduction buffers, ROI not a multiple of anything) is pushed through both; on any
-    difference in (val_l, mu, sigma + eps) the callers keep the host path (deploy_network_ao.py) and say so."""
-    key = engine.device
+    handling of a scalar percentile, the float64 reductions of integer data -- that ``np.setbufsize`` or another numpy release
+    can change without notice.  A 26 k-voxel probe of the dtype is pushed through both; on any difference in
+    (val_l, mu, sigma + eps) the callers keep the host path (deploy_network_ao.py) and say so."""
+    dtype = np.dtype(dtype)
+    key = (engine.device, dtype)
     if key not in _ZSCORE_OK:
         import torch
         ok, why = True, ''
-        if np.getbufsize() != 8192:
+        if not device_dtype_ok(dtype):
+            ok, why = False, 'no device z-score for %s volumes' % dtype
+        elif np.getbufsize() != 8192:
             ok, why = False, 'np.getbufsize() = %d, the device reproduces the 8192-element default' % np.getbufsize()
         else:
-            rng = np.random.default_rng(20261003)
-            probe = (1000.0 * rng.gamma(2.0, 1.0, size=(37, 29, 1, 25))).astype(np.float32)
+            probe = _zscore_probe(dtype)
             val_l = np.percentile(probe, 10.0)
             roi = probe[probe >= val_l]
             want = (val_l, np.mean(roi), np.std(roi) + 1e-6)
             dev = torch.device('cuda', engine.device)
-            vol = torch.from_numpy(np.asfortranarray(probe)).to(dev)
-            mu, den, _, got_l = device_zscore_stats(vol, 10.0, torch.cuda.current_stream(dev).cuda_stream)
+            vol = _to_device(np.asfortranarray(probe), dev)
+            mu, den, _, got_l = device_zscore_stats(vol, 10.0, torch.cuda.current_stream(dev).cuda_stream, dtype)
             got = (got_l, mu, den)
-            if not all(np.float32(a) == np.float32(b) for a, b in zip(want, got)):
-                ok, why = False, 'probe statistics differ: numpy %r, device %r (numpy %s)' % (want, got, np.__version__)
+            rt = np.float32 if dtype == np.float32 else np.float64
+            if not all(rt(a) == rt(b) for a, b in zip(want, got)):
+                ok, why = False, 'probe statistics differ for %s: numpy %r, device %r (numpy %s)' % (dtype, want, got, np.__version__)
         _ZSCORE_OK[key] = (ok, why)
         if not ok and warn is not None:
             warn('  device z-score disabled, host pre-processing used instead: ' + why)
@@ -196,27 +341,25 @@ def device_zscore_matches_numpy(engine, warn=None):
 
 def aortic_lstm_sequence_device(image, engine, z_score=True, weight_R=5, weight_r=0.1, time_step=1, return_aux=False):
     """pipeline.aortic_lstm_prob_sequence + the argmax of deploy_network_ao.py:189 with the array work on the GPU:
-    (X,Y,Z,T) float32 aortic cine -> int32 label volume (X,Y,Z,T).  Only the raw volume goes in and uint8 labels come
+    (X,Y,Z,T) float32 / uint8 / int16 / uint16 aortic cine -> int32 label volume (X,Y,Z,T).  Only the raw volume goes in and uint8 labels come
     back (the host path moves the padded float32 cine in and 3 float32 probability maps per voxel out, and spends more
     time in np.percentile / np.argmax than the network takes).  ``aux['prob']`` (X,Y,Z,T,C) on request; ``aux['counts']``
     = pixels of each class per frame (what eval_aortic_area.py:60-78 turns into areas)."""
     import torch
-    if image.ndim != 4 or image.dtype != np.float32:
-        raise TypeError('expected a 4-D float32 (X,Y,Z,T) cine; use pipeline.aortic_lstm_prob_sequence otherwise')
+    if image.ndim != 4:
+        raise TypeError('expected a 4-D (X,Y,Z,T) cine; use pipeline.aortic_lstm_prob_sequence otherwise')
+    _check_dtype(image, 'pipeline.aortic_lstm_prob_sequence')
     if not z_score:
         raise ValueError('the device path implements the default --z_score pre-processing')
     X, Y, Z, T = image.shape
     dev = torch.device('cuda', engine.device)
     stream = torch.cuda.current_stream(dev).cuda_stream
-    src = image if (image.flags.f_contiguous or image.flags.c_contiguous) else np.asfortranarray(image)
-    vol = torch.from_numpy(src).to(dev)
-    mu, den, n_roi, val_l = device_zscore_stats(vol, 10.0, stream)
+    vol = _to_device(image, dev)
+    mu, den, n_roi, val_l = device_zscore_stats(vol, 10.0, stream, image.dtype)
     X2, Y2, x_pre, _, y_pre, _ = pad_amounts_fixed(X, Y)
     n_class = engine.arch.n_class
     batch = torch.empty((T, Z, X2, Y2), dtype=torch.float32, device=dev)
-    sx, sy, sz, st = vol.stride()
-    _lib.check(_lib.lib.ukbb_fcn_zscore_pack(vol.data_ptr(), X, Y, Z, T, sx, sy, sz, st, float(mu), float(den), X2, Y2, x_pre, y_pre,
-                                             batch.data_ptr(), stream), 'ukbb_fcn_zscore_pack')
+    zscore_pack(vol.data_ptr(), image.dtype, (X, Y, Z, T), vol.stride(), mu, den, (X2, Y2, x_pre, y_pre), batch.data_ptr(), stream)
     prob = torch.empty((T, Z, X2, Y2, n_class), dtype=torch.float32, device=dev)
     pred = torch.empty((T, Z, X2, Y2), dtype=torch.int32, device=dev)
     for z in range(Z):                                       # slice positions are independent cines (usually Z = 1)
@@ -245,22 +388,20 @@ def aortic_unet_sequence_device(image, engine, batch_slices=128, return_aux=Fals
     """pipeline.aortic_prob_sequence + the argmax of deploy_network_ao.py:189 for the frame-wise 'UNet' model with the array work
     on the GPU: device z-score, pack, batched forward (the engine's label map IS the lowest-index argmax of the float32
     probabilities it would return: ``softmax_argmax``, csrc/kernels.h), labels back as uint8.
-    (X,Y,Z,T) float32 -> int32 labels (X,Y,Z,T)."""
+    (X,Y,Z,T) float32 / uint8 / int16 / uint16 -> int32 labels (X,Y,Z,T)."""
     import torch
-    if image.ndim != 4 or image.dtype != np.float32:
-        raise TypeError('expected a 4-D float32 (X,Y,Z,T) cine; use pipeline.aortic_prob_sequence otherwise')
+    if image.ndim != 4:
+        raise TypeError('expected a 4-D (X,Y,Z,T) cine; use pipeline.aortic_prob_sequence otherwise')
+    _check_dtype(image, 'pipeline.aortic_prob_sequence')
     X, Y, Z, T = image.shape
     dev = torch.device('cuda', engine.device)
     stream = torch.cuda.current_stream(dev).cuda_stream
-    src = image if (image.flags.f_contiguous or image.flags.c_contiguous) else np.asfortranarray(image)
-    vol = torch.from_numpy(src).to(dev)
-    mu, den, n_roi, val_l = device_zscore_stats(vol, 10.0, stream)
+    vol = _to_device(image, dev)
+    mu, den, n_roi, val_l = device_zscore_stats(vol, 10.0, stream, image.dtype)
     X2, Y2, x_pre, _, y_pre, _ = pad_amounts_fixed(X, Y)
     n = T * Z
     batch = torch.empty((n, X2, Y2), dtype=torch.float32, device=dev)
-    sx, sy, sz, st = vol.stride()
-    _lib.check(_lib.lib.ukbb_fcn_zscore_pack(vol.data_ptr(), X, Y, Z, T, sx, sy, sz, st, float(mu), float(den), X2, Y2, x_pre, y_pre,
-                                             batch.data_ptr(), stream), 'ukbb_fcn_zscore_pack')
+    zscore_pack(vol.data_ptr(), image.dtype, (X, Y, Z, T), vol.stride(), mu, den, (X2, Y2, x_pre, y_pre), batch.data_ptr(), stream)
     pred = torch.empty((n, X2, Y2), dtype=torch.int32, device=dev)
     engine.reserve(min(batch_slices, n), X2, Y2)
     for i in range(0, n, batch_slices):

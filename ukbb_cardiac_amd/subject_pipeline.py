@@ -22,7 +22,7 @@ import queue
 import numpy as np
 
 from . import _lib
-from .device_pipeline import lerp_like_numpy, percentile_ranks
+from .device_pipeline import device_dtype_ok, device_percentiles, pack_rescaled
 from .pipeline import pad_amounts
 
 
@@ -31,7 +31,8 @@ class _Slot:
 
 
 class Staged:
-    """A pinned input buffer on loan from the pipeline: ``array`` is its (X,Y,Z,T) Fortran-ordered float32 view."""
+    """A pinned input buffer on loan from the pipeline: ``array`` is its (X,Y,Z,T) Fortran-ordered view (float32, uint8,
+    int16 or uint16)."""
 
     def __init__(self, array, buf):
         self.array, self.buf = array, buf
@@ -88,15 +89,18 @@ class SubjectPipeline:
 
     def stage(self, shape, dtype=np.float32, timeout=None):
         """Borrow a pinned input buffer (thread-safe; blocks while all are in use): ``Staged.array`` is a Fortran-ordered
-        float32 (X,Y,Z,T) view to fill -- e.g. ``nifti.load(path, alloc=lambda sh, dt: pipe.stage(sh, dt).array)`` makes
-        the file decompress straight into pinned memory.  Pass the Staged object (or its array) to ``submit``."""
-        if np.dtype(dtype) != np.float32:
-            raise TypeError('the device pipeline is exact for float32 volumes only')
+        (X,Y,Z,T) view of the dtype to fill -- e.g. ``nifti.load(path, alloc=lambda sh, dt: pipe.stage(sh, dt).array)`` makes
+        the file decompress straight into pinned memory.  Pass the Staged object (or its array) to ``submit``.
+        dtype: float32, uint8, int16 or uint16 (the pool's buffers viewed as bytes: an int16 volume fills, and copies to the
+        device, half the bytes of a float32 one)."""
+        dtype = np.dtype(dtype)
+        if not device_dtype_ok(dtype):
+            raise TypeError('the device pipeline is exact for float32, uint8, int16 and uint16 volumes only (got %s)' % dtype)
         n = int(np.prod(shape))
         if len(shape) != 4 or n > self._in_cap:
             raise ValueError('volume %s does not fit the staging buffers sized for %d voxels' % (shape, self._in_cap))
         buf = self._in_free.get(timeout=timeout)            # returned by Result.done()
-        st = Staged(buf.numpy()[:n].reshape(shape, order='F'), buf)
+        st = Staged(buf.numpy().view(np.uint8)[:n * dtype.itemsize].view(dtype).reshape(shape, order='F'), buf)
         with self._lock:
             self._staged[id(st.array)] = st
         return st
@@ -122,10 +126,10 @@ class SubjectPipeline:
 
     # ---- submit / collect -----------------------------------------------------------------------------
     def submit(self, image):
-        """Enqueue one (X,Y,Z,T) float32 volume: a ``Staged`` object / the array ``stage()`` handed out (used in place),
-        or any other array (copied into a pinned buffer first: one host memcpy).  Returns once the exact percentiles
-        of the volume are known (the copy-in stream is waited for, the compute stream is not)."""
-        torch = self.torch
+        """Enqueue one (X,Y,Z,T) float32 / uint8 / int16 / uint16 volume: a ``Staged`` object / the array ``stage()`` handed
+        out (used in place), or any other array (copied into a pinned buffer first: one host memcpy).  Returns once the exact
+        percentiles of the volume are known (the copy-in stream is waited for, the compute stream is not).  Subjects of
+        different dtypes may follow each other: the select and pack kernels are chosen per subject."""
         if isinstance(image, Staged):
             st = image
             with self._lock:
@@ -134,9 +138,9 @@ class SubjectPipeline:
             with self._lock:
                 st = self._staged.pop(id(image), None)
             if st is None:
-                if image.ndim != 4 or image.dtype != np.float32:
-                    raise TypeError('expected a 4-D float32 (X,Y,Z,T) volume')
-                st = self.stage(image.shape)
+                if image.ndim != 4 or not device_dtype_ok(image.dtype):
+                    raise TypeError('expected a 4-D float32, uint8, int16 or uint16 (X,Y,Z,T) volume')
+                st = self.stage(image.shape, image.dtype)
                 with self._lock:
                     self._staged.pop(id(st.array), None)
                 st.array[...] = image
@@ -163,33 +167,25 @@ class SubjectPipeline:
         n_class = self.engine.arch.n_class
         X2, Y2, x_pre, _, y_pre, _ = pad_amounts(X, Y)
         nsl = T * Z
+        dtype = np.dtype(np.float32) if st is None else st.array.dtype
         with torch.cuda.stream(self.s_in):
             if st is not None:
-                slot.d_vol[:n].copy_(st.buf[:n], non_blocking=True)
+                nb = n * dtype.itemsize                     # an int16 volume copies half the bytes of a float32 one
+                slot.d_vol.view(torch.uint8)[:nb].copy_(st.buf.view(torch.uint8)[:nb], non_blocking=True)
             else:
                 # the slot's previous subject was collected (its pack kernel, the last reader of d_vol, has finished long ago)
                 fill(slot.d_vol.data_ptr(), n, self.s_in.cuda_stream)
             # exact np.percentile(volume, (1, 99)): two neighbouring order statistics per percentile from the device
-            # (4-pass radix select; synchronises the copy-in stream only), numpy's own interpolation on the host
-            ranks, gammas = [], []
-            for q in self.thres:
-                k, k1, g = percentile_ranks(n, q)
-                ranks += [k, k1]
-                gammas.append(g)
-            import ctypes as C
-            r = (C.c_uint64 * len(ranks))(*ranks)
-            out = np.empty(len(ranks), np.float32)
-            _lib.check(_lib.lib.ukbb_fcn_select_kth(slot.d_vol.data_ptr(), n, r, len(ranks), _lib.f32ptr(out), self.s_in.cuda_stream),
-                       'ukbb_fcn_select_kth')
-            lo, hi = (lerp_like_numpy(out[2 * i], out[2 * i + 1], gammas[i]) for i in range(2))
+            # (radix select on the voxel type; synchronises the copy-in stream only), numpy's own interpolation on the host
+            lo, hi = device_percentiles(slot.d_vol, self.thres, self.s_in.cuda_stream, dtype, n=n)
             slot.ev_in.record(self.s_in)
         slot.clip = (lo, hi)
         with torch.cuda.stream(self.s_cmp):
             self.s_cmp.wait_event(slot.ev_in)
             cs = self.s_cmp.cuda_stream
             # element strides of the Fortran-ordered (X,Y,Z,T) volume
-            _lib.check(_lib.lib.ukbb_fcn_rescale_pack(slot.d_vol.data_ptr(), X, Y, Z, T, 1, X, X * Y, X * Y * Z, float(lo), float(hi),
-                                                      X2, Y2, x_pre, y_pre, slot.d_batch.data_ptr(), cs), 'ukbb_fcn_rescale_pack')
+            pack_rescaled(slot.d_vol.data_ptr(), dtype, (X, Y, Z, T), (1, X, X * Y, X * Y * Z), lo, hi, (X2, Y2, x_pre, y_pre),
+                          slot.d_batch.data_ptr(), cs)
             self.engine.reserve(min(self.batch_slices, nsl), X2, Y2)
             px = X2 * Y2
             for i in range(0, nsl, self.batch_slices):
