@@ -506,6 +506,9 @@ __device__ unsigned long long g_hstamps[8];
 //   waves 0-3 "consumers": same_dim0 (8 MFMA) -> out0 level-0 slice accumulated ONTO the handed
 //       tile (32 MFMA) -> ReLU -> out1 (64 MFMA) -> ReLU -> logits / softmax / argmax.
 // A stage = one block per consumer wave (2 stages per tile); one barrier per stage.
+// r08: the producers evaluate the bilinear taps separably with channels on the lanes (x once per window row, y per output row with
+// compile-time weights), so a stage is eight contiguous tile rows and consumer wave w takes block 4 * (stage & 1) + w; the
+// r02-r07 direct 2-D gather (one pixel per lane, blocks 2 w + (stage & 1)) is the DG instance (UKBB_HEAD_DIRECT_GATHER=1).
 // r01 measurements behind this split: in the single-role kernel the gather (VALU+LDS), the G
 // staging and the MFMA chains simply added up (ablation: 76 + 63 + 40%..) because every wave
 // ran them back to back and at most 3 waves fit per SIMD.
@@ -581,7 +584,23 @@ __device__ __forceinline__ f32x16 mfma_b16(const u32x4 &a, const u32x4 &b, const
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(hbf16x8, a), __builtin_bit_cast(hbf16x8, b), c, 0, 0, 0);
 }
 
-template <int NCLS, bool X3 = false>
+// ---- separable gather (r08): which x-interpolated window rows a run of four output rows reads ---------------------------------
+// Tile origins are multiples of 16 >= f, so for tile row r the level-l taps sit in window rows (r + pb) >> l (weight
+// (f - 1 - jy) / f, zero when jy = f - 1) and that + 1 (weight (jy + 1) / f), jy = (r + pb) & (f - 1): compile-time per run.
+__host__ __device__ constexpr int sep_pb(int l) { return ((1 << l) - 1) >> 1; }
+__host__ __device__ constexpr int sep_row0(int r0, int l) { return (r0 + sep_pb(l)) >> l; }   // window row of h[0]
+__host__ __device__ constexpr bool sep_row_used(int r0, int l, int k) {   // does output row r0..r0+3 read window row row0 + k?
+    const int f = 1 << l, i = sep_row0(r0, l) + k;
+    bool used = false;
+    for (int t = 0; t < 4; ++t) {
+        const int y = r0 + t + sep_pb(l);
+        if ((y >> l) + 1 == i || ((y >> l) == i && (y & (f - 1)) != f - 1)) used = true;
+    }
+    return used;
+}
+
+// DG: the r02-r07 direct 2-D gather (UKBB_HEAD_DIRECT_GATHER=1, A/B); otherwise the separable one
+template <int NCLS, bool X3 = false, bool DG = false>
 __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     using LM = HeadLds<X3>;
@@ -690,7 +709,7 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
         int tap0[2][4];
         float tw[2][4][4];
 #pragma unroll
-        for (int par = 0; par < 2; ++par) {
+        for (int par = 0; par < (DG ? 2 : 0); ++par) {
             const int blk = pw * 2 + par;
             const int yl = 2 * blk + (p >> 4), xl = p & 15;
 #pragma unroll
@@ -707,7 +726,73 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
                 tw[par][l - 1][2] = wy1 * wx0; tw[par][l - 1][3] = wy1 * wx1;
             }
         }
-        f32x16 P;
+        // Separable gather constants.  Channels on the lanes: producer wave 4 + 4 rg + cb owns channels 16 cb .. 16 cb + 15 of tile rows
+        // 8 PAR + 4 rg .. + 3 (a run of four rows, consumer waves 2 rg and 2 rg + 1); a lane holds the float4 of channels 4 k4 .. 4 k4 + 3
+        // (k4 = 4 cb + cg) of column lane & 15.  cg is the lane's ds_read_b128 lane group ({0-3,12-15,20-27}, {4-11,16-19,28-31}, and
+        // the same + 32), so the 16 lanes the LDS serves together read one channel group of 16 different columns: at most 9 window
+        // pixels, on distinct bank quads (stride 68 floats).  The hand-over stores (8 consecutive lanes per LDS cycle) then write 8
+        // different columns.  Per level: the LDS offset of the lane's x0 tap in window row 0, and its two x weights (the y weights are
+        // compile-time, sep_row_used).
+        const int l5 = lane & 31, col = lane & 15;
+        const int cb = (tid >> 6) & 3, k4 = 4 * cb + 2 * (lane >> 5) + ((((l5 + 4) >> 3) ^ (l5 >> 4)) & 1);
+        int xoff[4];
+        float wx0[4], wx1[4];
+#pragma unroll
+        for (int l = 1; l <= (DG ? 0 : 4); ++l) {
+            const int f = 1 << l, txx = col + sep_pb(l), jx = txx & (f - 1);
+            const float inv = 1.0f / (float)f;
+            xoff[l - 1] = (win_base(l) + (txx >> l)) * GSTRIDE + 4 * k4;
+            wx1[l - 1] = (float)(jx + 1) * inv;
+            wx0[l - 1] = (float)(f - 1 - jx) * inv;
+        }
+        f32x16 P;                                       // DG: 16 channels of one pixel; else register 4 t + i = channel 4 k4 + i of run row t
+        auto gather_sep = [&](auto parc, auto bufc, auto rgc) {
+            constexpr int BUF = decltype(bufc)::value, R0 = 8 * decltype(parc)::value + 4 * decltype(rgc)::value;
+            const f32x4 b = lds4(lds + L_BO0 + 4 * k4);
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) P[4 * t + i] = b[i];
+#ifdef UKBB_DIAG
+            if (a.diag & 1) return;                 // ablation: no gather (hand over the bias tile only)
+#endif
+            unroll_n<4>([&](auto lc) {
+                constexpr int l = decltype(lc)::value + 1, f = 1 << l, wn_ = win_n(l), I0 = sep_row0(R0, l);
+                static_assert(sep_row0(R0 + 3, l) + 1 - I0 < 3, "a run of four rows reads at most three window rows");
+                const float *src = gw + BUF * GPIX * GSTRIDE + xoff[l - 1] + I0 * wn_ * GSTRIDE;
+                const float u0 = wx0[l - 1], u1 = wx1[l - 1];
+                f32x4 h[3];                             // window rows I0 .. I0 + 2, interpolated in x at the lane's column
+                unroll_n<3>([&](auto kc) {
+                    constexpr int k = decltype(kc)::value;
+                    if constexpr (sep_row_used(R0, l, k)) {
+                        const f32x4 a0 = lds4(src + k * wn_ * GSTRIDE), a1 = lds4(src + k * wn_ * GSTRIDE + GSTRIDE);
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) h[k][i] = fmaf(u0, a0[i], u1 * a1[i]);
+                    }
+                });
+                unroll_n<4>([&](auto tc) {
+                    constexpr int t = decltype(tc)::value, y = R0 + t + sep_pb(l), i1 = (y >> l) - I0, jy = y & (f - 1);
+                    constexpr float wy1 = (float)(jy + 1) / (float)f, wy0 = (float)(f - 1 - jy) / (float)f;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) P[4 * t + i] = fmaf(wy1, h[i1 + 1][i], P[4 * t + i]);
+                    if constexpr (jy != f - 1) {        // a zero y weight: the tap is dropped, not multiplied
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) P[4 * t + i] = fmaf(wy0, h[i1][i], P[4 * t + i]);
+                    }
+                });
+            });
+        };
+        auto hand_over_sep = [&](auto rgc) {            // run row t = pixel 16 (t & 1) + col of consumer wave 2 RG + (t >> 1)
+            constexpr int RG = decltype(rgc)::value;
+            float *dst = px + (4 * (k4 >> 3) + ((k4 >> 1) & 3)) * 256 + (col + 32 * (k4 & 1)) * 4;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                f32x4 v;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) v[i] = P[4 * t + i];
+                *reinterpret_cast<f32x4 *>(dst + (2 * RG + (t >> 1)) * PX_WAVE + 16 * (t & 1) * 4) = v;
+            }
+        };
         auto gather = [&](auto parc, auto bufc) {       // block 2*pw + PAR of the tile staged in window buffer BUF -> P (32 channels)
             constexpr int PAR = decltype(parc)::value, BUF = decltype(bufc)::value;
             P = bias_tile_lds(lds + L_BO0 + 32 * half, g);
@@ -743,10 +828,15 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
         if (my_tiles > 0) { g_load(0); g_store(0); }
         if (my_tiles > 1) { g_load(1); g_store(1); }
         __syncthreads();                                // barrier X: weights, GW[0], GW[1] visible
-        auto stage = [&](auto parc, auto bufc, int s) {
+        auto stage = [&](auto parc, auto bufc, auto rgc, int s) {
             constexpr int PAR = decltype(parc)::value, BUF = decltype(bufc)::value;
-            gather(parc, bufc);                         // LDS windows -> registers (consumers still busy with s-1)
-            hand_over();                                // px was released at barrier B of stage s-1
+            if constexpr (DG) {
+                gather(parc, bufc);                     // LDS windows -> registers (consumers still busy with s-1)
+                hand_over();                            // px was released at barrier B of stage s-1
+            } else {
+                gather_sep(parc, bufc, rgc);
+                hand_over_sep(rgc);
+            }
             __syncthreads();                            // barrier A_s: px ready
             __syncthreads();                            // barrier B_s: px consumed
             if constexpr (PAR == 1) {                   // tile k = s>>1 fully gathered: its window buffer is free
@@ -759,12 +849,17 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
         };
         constexpr std::integral_constant<int, 0> I0{};
         constexpr std::integral_constant<int, 1> I1{};
+        auto run = [&](auto rgc) {                      // separable gather: one copy of the loop per run of rows (rg is wave-uniform)
 #pragma unroll 1
-        for (int s = 0; s < nstages; s += 4) {          // nstages is even
-            stage(I0, I0, s);
-            stage(I1, I0, s + 1);
-            if (s + 2 < nstages) { stage(I0, I1, s + 2); stage(I1, I1, s + 3); }
-        }
+            for (int s = 0; s < nstages; s += 4) {      // nstages is even
+                stage(I0, I0, rgc, s);
+                stage(I1, I0, rgc, s + 1);
+                if (s + 2 < nstages) { stage(I0, I1, rgc, s + 2); stage(I1, I1, rgc, s + 3); }
+            }
+        };
+        if constexpr (DG) run(I0);
+        else if (__builtin_amdgcn_readfirstlane(tid) < 256) run(I0);
+        else run(I1);
     } else {
         const int wave = threadIdx.x >> 6;
         const float *w_s0 = lds + L_WS0, *w_o0 = lds + L_WO0, *w_o1 = lds + L_WO1, *w_lg = lds + L_WLG;
@@ -773,7 +868,7 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
             const int tx = bid % tiles_x; bid /= tiles_x;
             const int ty = bid % tiles_y;
             const int n = bid / tiles_y;
-            const int blk = wave * 2 + (s & 1);
+            const int blk = DG ? wave * 2 + (s & 1) : 4 * (s & 1) + wave;   // separable gather: stage s & 1 = tile rows 8 (s & 1) .. + 7
             const int y = ty * HT + 2 * blk + (p >> 4), x = tx * HT + (p & 15);
             return ((size_t)n * a.H + y) * a.W + x;
         };
@@ -961,11 +1056,12 @@ static hipError_t launch_head_pc(const HeadArgs &a, hipStream_t s) {
     const int ntiles = a.N * (a.H / HT) * (a.W / HT);
     dim3 grid((unsigned)(ntiles < n_cu ? ntiles : n_cu)), block(768);
     static const bool x3_env = [] { const char *e = getenv("UKBB_HEAD_X3"); return e && atoi(e) != 0; }();   // A/B knob
+    static const bool dg = [] { const char *e = getenv("UKBB_HEAD_DIRECT_GATHER"); return e && atoi(e) != 0; }();   // A/B knob (r08)
     if ((a.x3 || x3_env) && a.w_o1x3 && a.w_o0x3) {     // UKBB_PREC_F32X3
         const size_t ldsx = HEADPC_X3_LDS_FLOATS * sizeof(float);
 #define UKBB_HEADX3_CASE(NC)                                                                          \
     case NC: {                                                                                       \
-        auto k = fcn_head_pc_kernel<NC, true>;                                                       \
+        auto k = dg ? fcn_head_pc_kernel<NC, true, true> : fcn_head_pc_kernel<NC, true, false>;      \
         static OncePerDevice lds_ok;                                                                 \
         {                                                                                            \
             hipError_t e = allow_dynamic_lds(lds_ok, reinterpret_cast<const void *>(k), (int)ldsx);    \
@@ -983,7 +1079,7 @@ static hipError_t launch_head_pc(const HeadArgs &a, hipStream_t s) {
     const size_t lds = HEADPC_LDS_FLOATS * sizeof(float);
 #define UKBB_HEADPC_CASE(NC)                                                                          \
     case NC: {                                                                                       \
-        auto k = fcn_head_pc_kernel<NC>;                                                             \
+        auto k = dg ? fcn_head_pc_kernel<NC, false, true> : fcn_head_pc_kernel<NC, false, false>;    \
         static OncePerDevice lds_ok;                                                                 \
         {                                                                                            \
             hipError_t e = allow_dynamic_lds(lds_ok, reinterpret_cast<const void *>(k), (int)lds);    \
