@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define UKBB_FCN_ABI_VERSION 9
+#define UKBB_FCN_ABI_VERSION 10
 #define UKBB_FCN_MAX_LEVEL 8
 
 #define UKBB_OK 0
@@ -277,6 +277,34 @@ int ukbb_fcn_pairwise_sum_t(const void *d_a, int nifti_datatype, uint64_t n, int
  * rounded once to float32, zero padding around it.  Replaces image_utils.py:67 + deploy_network_ao.py:105-108,147-150. */
 int ukbb_fcn_zscore_pack_t(const void *d_vol, int nifti_datatype, int X, int Y, int Z, int T, int64_t sx, int64_t sy, int64_t sz,
                            int64_t st, double mu, double den, int X2, int Y2, int x_pre, int y_pre, float *d_batch, void *stream);
+
+/* -- the aortic quality control (ABI 10): the label-map and image statistics of cardiac_utils.aorta_pass_quality_control ---
+ * (reference common/cardiac_utils.py:1739-1796, applied by aortic/eval_aortic_area.py:68-69) on the cine and the uint8 label
+ * volume (NIfTI order, what ukbb_fcn_unpack_labels writes) the aortic device path already holds.  nifti_datatype of the voxels:
+ * 16 (float32), 2 (uint8), 4 (int16), 512 (uint16).  ukbb_cardiac_amd/aorta_qc.py shows the sequence and the host arithmetic. */
+
+/* d_n_large[t][k] (int32, T x n_class) = the number of connected components of the mask lab[:, :, :, t] == k with MORE than
+ * min_size voxels, k = 1 .. n_class - 1 (column 0 stays 0); connectivity 2 of skimage in 3-D (18-neighbourhood: neighbours
+ * differ in at most two coordinates), no connectivity across frames.  Replaces skimage.measure.label(seg_t == l,
+ * connectivity=2) and the size filter of cardiac_utils.py:1766-1780.  d_work: 2*X*Y*Z*T int32 the caller allocates (the
+ * union-find's parents and component sizes).  Union-find with integer atomics: the counts do not depend on arrival order.
+ * Asynchronous.  n_class <= 16, Z*T <= 65535, 2*X*Y*Z*T < 2^31. */
+int ukbb_fcn_label_components(const uint8_t *d_lab, int X, int Y, int Z, int T, int n_class, int min_size, int32_t *d_work,
+                              int32_t *d_n_large, void *stream);
+
+/* d_max[t][k] (float64, T x n_class) = np.max(image[:, :, :, t][lab[:, :, :, t] == k]) of the (X,Y,Z,T) volume with element
+ * strides (sx,sy,sz,st): exact for every voxel type, NaN when a NaN lies under the mask (as np.max), -inf for an empty mask.
+ * Integer maxima of order-preserving keys: no float atomics, no dependence on arrival order.  Replaces the np.max of
+ * cardiac_utils.py:1757-1761.  Asynchronous.  n_class <= 16, T <= 65535. */
+int ukbb_fcn_label_max(const void *d_vol, int nifti_datatype, int X, int Y, int Z, int T, int64_t sx, int64_t sy, int64_t sz, int64_t st,
+                       const uint8_t *d_lab, int n_class, double *d_max, void *stream);
+
+/* d_out[i] = the i-th element of frame 0 of the volume (element strides sx,sy,sz) whose label lab[x + X*(y + Y*z)] is `label`,
+ * in row-major INDEX order of the (X,Y,Z) frame (z fastest): numpy's image_ED[seg_ED == l], cardiac_utils.py:1753-1755.  d_out
+ * (voxel type) holds up to X*Y*Z elements; *n_host receives the count.  ukbb_fcn_pairwise_sum (float32) or
+ * ukbb_fcn_pairwise_sum_t (integer types) over it then give numpy's .mean() sum bit for bit.  Synchronous. */
+int ukbb_fcn_label_compact(const void *d_vol, int nifti_datatype, int X, int Y, int Z, int64_t sx, int64_t sy, int64_t sz, const uint8_t *d_lab,
+                           int label, void *d_out, uint64_t *n_host, void *stream);
 
 /* ---- label-volume files (host only: no device, no stream) ---------------------------------------
  * What the reference does with the result: nib.save of np.zeros(image.shape) filled with the labels

@@ -1,6 +1,8 @@
 """Aortic cohort through the drop-in script (deploy_network_ao.py, default UNet-LSTM model), gzip NIfTI files included:
 subjects/s for --io_threads 0 (the reference's strictly sequential loop) and with read-ahead / write-behind threads.
-GPU box only.   python tools/bench_aortic_cohort.py [--cohort 24] [--io_threads 2,4,8]"""
+--aortic_qc_full: every configuration runs twice with --output_csv, without and with --aortic_qc_full (the full quality control
+of aorta_qc.py), and the ratio of the two rates is printed.
+GPU box only.   python tools/bench_aortic_cohort.py [--cohort 24] [--io_threads 2,4,8] [--aortic_qc_full]"""
 import argparse
 import os
 import shutil
@@ -17,6 +19,7 @@ if __name__ == '__main__':
     ap.add_argument('--cohort', type=int, default=24)
     ap.add_argument('--io_threads', default='2,4,8')
     ap.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'])
+    ap.add_argument('--aortic_qc_full', action='store_true', help='time --output_csv without and with --aortic_qc_full')
     args = ap.parse_args()
     from ukbb_cardiac_amd import deploy_network_ao, nifti
     from ukbb_cardiac_amd.arch import MODELS
@@ -43,16 +46,26 @@ if __name__ == '__main__':
         print('aortic cohort (%s): %d subjects of %dx%dx1x%d float32, ao.nii.gz %.1f MB each' %
               (args.precision, args.cohort, X, Y, T, os.path.getsize(os.path.join(src, 's000', 'ao.nii.gz')) / 1e6), flush=True)
         cine = lambda f, R, r, ts=1: eng.run_cine(f, R, r, ts)[0]
+        variants = [[], ['--aortic_qc_full']] if args.aortic_qc_full else [None]
         for thr in [0] + [int(v) for v in args.io_threads.split(',')]:
-            work = os.path.join(root, 'run%d' % thr)
-            shutil.copytree(src, work)
-            flags = deploy_network_ao.define_flags().parse(['--data_dir', work, '--model_path', mp, '--io_threads', str(thr)])[0]
-            t0 = time.perf_counter()
-            deploy_network_ao.run(flags, None, log=lambda *_: None, cine_forward=cine, engine=eng)
-            dt = time.perf_counter() - t0
-            print('   deploy_network_ao.py --io_threads %-2d: %6.2f s = %5.2f subjects/s (%5.0f frames/s), files included' %
-                  (thr, dt, args.cohort / dt, args.cohort * T / dt), flush=True)
-            shutil.rmtree(work)
+            rate = {}
+            for extra in variants:
+                work = os.path.join(root, 'run%d' % thr)
+                shutil.copytree(src, work)
+                argv = ['--data_dir', work, '--model_path', mp, '--io_threads', str(thr)]
+                if extra is not None:
+                    argv += ['--output_csv', os.path.join(root, 'ao.csv')] + extra
+                flags = deploy_network_ao.define_flags().parse(argv)[0]
+                t0 = time.perf_counter()
+                deploy_network_ao.run(flags, None, log=lambda *_: None, cine_forward=cine, engine=eng)
+                dt = time.perf_counter() - t0
+                rate[bool(extra)] = args.cohort / dt
+                print('   deploy_network_ao.py --io_threads %-2d%s: %6.2f s = %5.2f subjects/s (%5.0f frames/s), files included' %
+                      (thr, '' if extra is None else ' --output_csv' + ''.join(' ' + e for e in extra), dt, args.cohort / dt,
+                       args.cohort * T / dt), flush=True)
+                shutil.rmtree(work)
+            if args.aortic_qc_full:
+                print('   --io_threads %-2d: with --aortic_qc_full %.3fx the rate without' % (thr, rate[True] / rate[False]), flush=True)
     finally:
         shutil.rmtree(root, ignore_errors=True)
     eng.close()

@@ -12,7 +12,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('UKBB_FCN_LIB') or os.path.join(_HERE, 'libukbb_fcn.so')   # override: A/B builds of the kernels
-ABI_VERSION = 9
+ABI_VERSION = 10
 MAX_LEVEL = 8
 
 # every symbol include/ukbb_fcn.h declares
@@ -28,6 +28,7 @@ EXPORTS = [
     'ukbb_fcn_forward_seq', 'ukbb_fcn_forward_cine', 'ukbb_fcn_clock_probe', 'ukbb_fcn_kernel_mfma_macs_issued',
     'ukbb_fcn_synth_volume',
     'ukbb_fcn_select_kth_t', 'ukbb_fcn_rescale_pack_t', 'ukbb_fcn_roi_compact_t', 'ukbb_fcn_pairwise_sum_t', 'ukbb_fcn_zscore_pack_t',
+    'ukbb_fcn_label_components', 'ukbb_fcn_label_max', 'ukbb_fcn_label_compact',
 ]
 
 
@@ -109,6 +110,10 @@ def _load():
     lib.ukbb_fcn_pairwise_sum_t.argtypes = [vp, C.c_int, C.c_uint64, C.c_int, C.c_double, C.POINTER(C.c_double), vp]
     lib.ukbb_fcn_zscore_pack_t.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i64, i64, i64, i64,
                                            C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
+    lib.ukbb_fcn_label_components.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    lib.ukbb_fcn_label_max.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i64, i64, i64, i64, vp, C.c_int, vp, vp]
+    lib.ukbb_fcn_label_compact.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, i64, i64, i64, vp, C.c_int, vp,
+                                           C.POINTER(C.c_uint64), vp]
     lib.ukbb_fcn_gzip_labels_bound.restype = C.c_uint64
     lib.ukbb_fcn_gzip_labels_bound.argtypes = [C.c_uint64, C.c_int, C.c_uint64]
     lib.ukbb_fcn_gzip_labels.restype = C.c_int64

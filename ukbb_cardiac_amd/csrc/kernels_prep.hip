@@ -446,6 +446,86 @@ int roi_compact_impl(const T *d_vol, int X, int Y, int Z, int T_, int64_t sx, in
     return UKBB_OK;
 }
 
+// ---- the label-masked compaction of the aortic quality control: image_ED[seg_ED == l] (cardiac_utils.py:1753-1755) ---------
+// The frame (t = 0) of the volume, the elements whose label is k, in row-major index order of the (X,Y,Z) frame (z fastest);
+// the labels are dense in NIfTI order (x fastest).  The scan and the write are those of roi_compact_impl with this predicate.
+template <typename T>
+__device__ __forceinline__ bool lab_elem(const T *vol, const unsigned char *lab, long long i, int X, int Y, int Z, long long sx, long long sy,
+                                         long long sz, int k, T &v) {
+    const int z = (int)(i % Z); const long long r = i / Z;
+    const int y = (int)(r % Y); const int x = (int)(r / Y);
+    if (lab[x + (long long)X * (y + (long long)Y * z)] != k) return false;
+    v = vol[x * sx + y * sy + z * sz];
+    return true;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void lab_count_kernel(const T *__restrict__ vol, const unsigned char *__restrict__ lab, long long n, int X, int Y,
+                                                        int Z, long long sx, long long sy, long long sz, int k, unsigned *__restrict__ counts) {
+    __shared__ unsigned wsum[4];
+    const long long i0 = (long long)blockIdx.x * CCH + threadIdx.x * 4;
+    unsigned c = 0;
+    T v;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (i0 + j < n && lab_elem(vol, lab, i0 + j, X, Y, Z, sx, sy, sz, k, v)) ++c;
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void lab_write_kernel(const T *__restrict__ vol, const unsigned char *__restrict__ lab, long long n, int X, int Y,
+                                                        int Z, long long sx, long long sy, long long sz, int k,
+                                                        const unsigned long long *__restrict__ offs, T *__restrict__ out) {
+    __shared__ unsigned wpre[4];
+    const long long i0 = (long long)blockIdx.x * CCH + threadIdx.x * 4;
+    T v[4];
+    bool keep[4];
+    unsigned c = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        keep[j] = i0 + j < n && lab_elem(vol, lab, i0 + j, X, Y, Z, sx, sy, sz, k, v[j]);
+        c += keep[j];
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned incl = c;
+    for (int o = 1; o < 64; o <<= 1) { const unsigned u = __shfl_up(incl, o); if (lane >= o) incl += u; }
+    if (lane == 63) wpre[wave] = incl;
+    __syncthreads();
+    unsigned base = 0;
+    for (int w = 0; w < wave; ++w) base += wpre[w];
+    unsigned long long pos = offs[blockIdx.x] + base + (incl - c);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (keep[j]) out[pos++] = v[j];
+}
+
+template <typename T>
+int label_compact_impl(const T *d_vol, int X, int Y, int Z, int64_t sx, int64_t sy, int64_t sz, const uint8_t *d_lab, int k, T *d_out,
+                       uint64_t *n_host, hipStream_t s) {
+    const long long n = (long long)X * Y * Z;
+    const int nb = (int)((n + CCH - 1) / CCH);
+    Scratch *sc = prep_scratch(0);
+    void *buf = sc ? sc->get((size_t)nb * 4 + 8 + ((size_t)nb + 1) * 8) : nullptr;
+    if (!buf) { set_error("label_compact: scratch allocation failed"); return UKBB_ENOMEM; }
+    unsigned *counts = static_cast<unsigned *>(buf);
+    unsigned long long *offs = reinterpret_cast<unsigned long long *>(static_cast<char *>(buf) + (((size_t)nb * 4 + 7) / 8) * 8);
+    hipLaunchKernelGGL((lab_count_kernel<T>), dim3(nb), dim3(256), 0, s, d_vol, d_lab, n, X, Y, Z, (long long)sx, (long long)sy, (long long)sz, k,
+                       counts);
+    hipLaunchKernelGGL(roi_scan_kernel, dim3(1), dim3(1024), 0, s, counts, nb, offs);
+    hipLaunchKernelGGL((lab_write_kernel<T>), dim3(nb), dim3(256), 0, s, d_vol, d_lab, n, X, Y, Z, (long long)sx, (long long)sy, (long long)sz, k,
+                       offs, d_out);
+    unsigned long long total = 0;
+    if (hipMemcpyAsync(&total, offs + nb, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+        set_error("label_compact: device error: %s", hipGetErrorString(hipGetLastError()));
+        return UKBB_EDEVICE;
+    }
+    *n_host = total;
+    return UKBB_OK;
+}
+
 bool shape_ok(int X, int Y, int Z, int T, int X2, int Y2, int x_pre, int y_pre) {
     return X >= 1 && Y >= 1 && Z >= 1 && T >= 1 && x_pre >= 0 && y_pre >= 0 && X2 >= X + x_pre && Y2 >= Y + y_pre && (long long)Z * T <= 65535;
 }
@@ -642,6 +722,22 @@ int ukbb_fcn_roi_compact_t(const void *d_vol, int nifti_datatype, int X, int Y, 
         if (!d_vol || !d_out || !n_host || X < 1 || Y < 1 || Z < 1 || T < 1) { set_error("roi_compact_t: bad argument"); return UKBB_EINVAL; }
         return roi_compact_impl(static_cast<const V *>(d_vol), X, Y, Z, T, sx, sy, sz, st, thr, static_cast<V *>(d_out), n_host,
                                 (hipStream_t)stream);
+    });
+}
+
+int ukbb_fcn_label_compact(const void *d_vol, int nifti_datatype, int X, int Y, int Z, int64_t sx, int64_t sy, int64_t sz, const uint8_t *d_lab,
+                           int label, void *d_out, uint64_t *n_host, void *stream) {
+    if (!d_vol || !d_lab || !d_out || !n_host || X < 1 || Y < 1 || Z < 1 || label < 0 || label > 255) {
+        set_error("label_compact: bad argument");
+        return UKBB_EINVAL;
+    }
+    if (nifti_datatype == 16)
+        return label_compact_impl(static_cast<const float *>(d_vol), X, Y, Z, sx, sy, sz, d_lab, label, static_cast<float *>(d_out), n_host,
+                                  (hipStream_t)stream);
+    return dispatch_int(nifti_datatype, "label_compact", [&](auto tag) {
+        using V = typename decltype(tag)::type;
+        return label_compact_impl(static_cast<const V *>(d_vol), X, Y, Z, sx, sy, sz, d_lab, label, static_cast<V *>(d_out), n_host,
+                                  (hipStream_t)stream);
     });
 }
 

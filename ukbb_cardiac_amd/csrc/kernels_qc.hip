@@ -1,0 +1,333 @@
+// The label-map and image statistics of the aortic quality control (cardiac_utils.aorta_pass_quality_control, reference
+// common/cardiac_utils.py:1739-1796, as eval_aortic_area.py:68-69 calls it), on the volumes the aortic device path already
+// holds in HBM:
+//
+//   ukbb_fcn_label_components  per (frame, class): components of seg_t == k with more than min_size voxels
+//                              -- skimage.measure.label(seg_t == l, connectivity=2) + the size filter of :1766-1780
+//   ukbb_fcn_label_max         per (frame, class): np.max(image_t[seg_t == k]) as float64, NaN propagated -- :1757-1764
+//
+// (the third statistic, the float32 / float64 mean of image_ED[seg_ED == l] of :1753-1755, is ukbb_fcn_label_compact in
+// kernels_prep.hip followed by the pairwise sums there.)
+//
+// Connected components: a union-find on an int32 parent array over the whole (X,Y,Z,T) label volume, every non-zero class at
+// once (a voxel unites only with neighbours of its own label, which gives exactly the components of each seg_t == k mask).
+// Neighbourhood: connectivity 2 of skimage in 3-D = 18: the 8 in-plane neighbours and, across z, the voxel itself and its 4
+// edge neighbours (3-D corners do not connect); never across frames.  Four launches:
+//   1. ccl_local_kernel   a 32x32 tile of one (z, t) plane per workgroup: union-find in LDS, then every voxel's global parent
+//                         = its tile-local root (the smallest index of its tile component) and that root's voxel count
+//   2. ccl_border_kernel  the neighbour pairs that cross a tile edge or a z plane: union in the global array (agent-scope atomics)
+//   3. ccl_size_kernel    every tile-local root adds its count to its global root (one integer atomic per tile component)
+//   4. ccl_count_kernel   every global root with more than min_size voxels adds 1 to n_large[t][k]
+// Roots are the smallest voxel index of their component: parent[i] <= i always, so every find terminates and the result does
+// not depend on the order in which unions arrive; the counts are integer sums, order-independent too.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+
+#include "../../include/ukbb_fcn.h"
+#include "kernels.h"
+
+namespace ukbb {
+
+namespace {
+
+constexpr int TILE = 32;                                // tile edge of ccl_local_kernel (1024 voxels, 4 per thread)
+constexpr int MAXC = 16;                                // classes per call (as ukbb_fcn_unpack_labels)
+
+// ---- union-find in LDS (one workgroup, workgroup-scope atomics) ---------------------------------------------------------
+__device__ __forceinline__ int lds_find(int *p, int i) {
+    for (;;) {
+        const int q = __hip_atomic_load(&p[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (q == i) return i;
+        i = q;
+    }
+}
+__device__ __forceinline__ void lds_union(int *p, int a, int b) {
+    for (;;) {                                          // hang the larger root under the smaller one
+        a = lds_find(p, a);
+        b = lds_find(p, b);
+        if (a == b) return;
+        if (a > b) { const int s = a; a = b; b = s; }
+        const int old = __hip_atomic_fetch_min(&p[b], a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (old == b) return;                           // b was still a root: linked
+        b = old;                                        // b was linked meanwhile: its (smaller) parent now takes a
+    }
+}
+
+// ---- union-find in HBM (all workgroups, agent-scope atomics) -----------------------------------------------------------
+// Workgroups on other XCDs rewrite parents while this one reads them.  The links are agent-scope atomic minima: they execute
+// at the memory side and return the parent as it is.  The loads are agent-scope atomic loads (sc1: past this CU's L1), but
+// this XCD's L2 may still hold an older copy of the line.  Stale loads are harmless: parents only ever decrease and always
+// stay inside the component, so a stale value is an older, larger ancestor; find then stops at a former root, the atomic
+// minimum on it returns its newer parent, and union carries on from there.  Every failed link replaces the larger of the two
+// roots by a smaller index, so union terminates.
+__device__ __forceinline__ int hbm_find(int *p, int i) {
+    for (;;) {
+        const int q = __hip_atomic_load(&p[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (q == i) return i;
+        i = q;
+    }
+}
+__device__ __forceinline__ void hbm_union(int *p, int a, int b) {
+    for (;;) {
+        a = hbm_find(p, a);
+        b = hbm_find(p, b);
+        if (a == b) return;
+        if (a > b) { const int s = a; a = b; b = s; }
+        const int old = __hip_atomic_fetch_min(&p[b], a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (old == b) return;
+        b = old;
+    }
+}
+
+// grid (tiles_x * tiles_y, Z * T), 256 threads; voxel gi = x + X*(y + Y*(z + Z*t)) (NIfTI order)
+__global__ __launch_bounds__(256) void ccl_local_kernel(const unsigned char *__restrict__ lab, int X, int Y, int *__restrict__ parent,
+                                                        int *__restrict__ size) {
+    __shared__ int lp[TILE * TILE];
+    __shared__ int cnt[TILE * TILE];
+    __shared__ unsigned char ll[TILE * TILE];
+    const int tiles_x = (X + TILE - 1) / TILE;
+    const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
+    const long long base = (long long)X * Y * blockIdx.y;
+    unsigned char v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int li = threadIdx.x + 256 * j, x = tx * TILE + (li & (TILE - 1)), y = ty * TILE + li / TILE;
+        v[j] = (x < X && y < Y) ? lab[base + x + (long long)X * y] : 0;
+        ll[li] = v[j];
+        lp[li] = li;
+        cnt[li] = 0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {                       // the in-plane half neighbourhood inside the tile: (-1,0) (-1,-1) (0,-1) (+1,-1)
+        if (!v[j]) continue;
+        const int li = threadIdx.x + 256 * j, lx = li & (TILE - 1), ly = li / TILE;
+        if (lx > 0 && ll[li - 1] == v[j]) lds_union(lp, li, li - 1);
+        if (ly > 0) {
+            if (lx > 0 && ll[li - TILE - 1] == v[j]) lds_union(lp, li, li - TILE - 1);
+            if (ll[li - TILE] == v[j]) lds_union(lp, li, li - TILE);
+            if (lx < TILE - 1 && ll[li - TILE + 1] == v[j]) lds_union(lp, li, li - TILE + 1);
+        }
+    }
+    __syncthreads();
+    int root[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        root[j] = -1;
+        if (!v[j]) continue;
+        root[j] = lds_find(lp, threadIdx.x + 256 * j);
+        atomicAdd(&cnt[root[j]], 1);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int li = threadIdx.x + 256 * j, x = tx * TILE + (li & (TILE - 1)), y = ty * TILE + li / TILE;
+        if (x >= X || y >= Y) continue;
+        const long long gi = base + x + (long long)X * y;
+        const int r = root[j];
+        // background: its own root of size 0 (never counted, never a neighbour: the labels differ)
+        parent[gi] = r < 0 ? (int)gi : (int)(base + tx * TILE + (r & (TILE - 1)) + (long long)X * (ty * TILE + r / TILE));
+        size[gi] = r == li ? cnt[li] : 0;
+    }
+}
+
+// one thread per voxel; only voxels with a half-neighbourhood neighbour outside their tile or in the plane below do any work
+__global__ __launch_bounds__(256) void ccl_border_kernel(const unsigned char *__restrict__ lab, int X, int Y, int Z, long long n,
+                                                         int *parent) {
+    const long long gi = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gi >= n) return;
+    const int x = (int)(gi % X);
+    long long r = gi / X;
+    const int y = (int)(r % Y);
+    r /= Y;
+    const int z = (int)(r % Z);
+    const int ex = x & (TILE - 1);
+    if (!(ex == 0 || ex == TILE - 1 || (y & (TILE - 1)) == 0 || z > 0)) return;
+    const unsigned char v = lab[gi];
+    if (!v) return;
+    const int txo = x / TILE, tyo = y / TILE;
+    auto link = [&](int dx, int dy, long long off) {    // neighbour (x+dx, y+dy) of this plane, if it lies in another tile
+        const int xn = x + dx, yn = y + dy;
+        if (xn < 0 || xn >= X || yn < 0) return;
+        if (xn / TILE == txo && yn / TILE == tyo) return;   // inside the tile: done by ccl_local_kernel
+        if (lab[gi + off] == v) hbm_union(parent, (int)gi, (int)(gi + off));
+    };
+    link(-1, 0, -1);
+    link(-1, -1, -1LL - X);
+    link(0, -1, -(long long)X);
+    link(1, -1, 1LL - X);
+    if (z > 0) {                                        // the plane below: the voxel itself and its 4 edge neighbours (18-connectivity)
+        const long long dz = -(long long)X * Y;
+        auto down = [&](int dx, int dy) {
+            const int xn = x + dx, yn = y + dy;
+            if (xn < 0 || xn >= X || yn < 0 || yn >= Y) return;
+            const long long o = gi + dz + dx + (long long)X * dy;
+            if (lab[o] == v) hbm_union(parent, (int)gi, (int)o);
+        };
+        down(0, 0);
+        down(-1, 0);
+        down(1, 0);
+        down(0, -1);
+        down(0, 1);
+    }
+}
+
+// every tile-local root (size > 0 after ccl_local_kernel) that is no longer a global root hands its count to its global root.
+// parent is read-only in this launch; size[i] of a tile-local root i changes only if i is a global root, which adds nothing.
+__global__ __launch_bounds__(256) void ccl_size_kernel(const unsigned char *__restrict__ lab, long long n, const int *__restrict__ parent,
+                                                       int *size) {
+    const long long gi = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gi >= n || !lab[gi]) return;
+    const int s = __hip_atomic_load(&size[gi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (s == 0) return;
+    int i = (int)gi;
+    for (int q = parent[i]; q != i; q = parent[i]) i = q;
+    if (i != (int)gi) __hip_atomic_fetch_add(&size[i], s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ __launch_bounds__(256) void ccl_count_kernel(const unsigned char *__restrict__ lab, long long n, long long frame, int n_class,
+                                                        int min_size, const int *__restrict__ parent, const int *__restrict__ size,
+                                                        int *n_large) {
+    const long long gi = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gi >= n) return;
+    const int k = lab[gi];
+    if (k == 0 || k >= n_class || parent[gi] != (int)gi || size[gi] <= min_size) return;
+    atomicAdd(&n_large[(gi / frame) * n_class + k], 1);
+}
+
+// ---- masked maximum ----------------------------------------------------------------------------------------------------
+// The maximum as an unsigned key whose integer order is numpy's: NaN above everything (np.max propagates it), then the value
+// order; 0 = no voxel (the key of every value is >= 1).  Integer maxima are order-independent, so the result does not depend
+// on which workgroup comes first; the keys live in the 8-byte output cells until label_max_final_kernel decodes them in place.
+__device__ __forceinline__ unsigned long long max_key(float v) {
+    if (v != v) return 0x100000000ull;
+    const unsigned u = __float_as_uint(v);
+    return (unsigned long long)((u & 0x80000000u) ? ~u : (u | 0x80000000u)) + 1;   // -0 < +0; every key >= 0x7FFFFF + 1
+}
+__device__ __forceinline__ unsigned long long max_key(uint8_t v) { return (unsigned long long)v + 1; }
+__device__ __forceinline__ unsigned long long max_key(uint16_t v) { return (unsigned long long)v + 1; }
+__device__ __forceinline__ unsigned long long max_key(int16_t v) { return (unsigned long long)(v + 32768) + 1; }
+
+template <typename T> __device__ double key_value(unsigned long long k);
+template <> __device__ double key_value<float>(unsigned long long k) {
+    if (k == 0x100000000ull) return __longlong_as_double(0x7FF8000000000000ll);
+    const unsigned u = (unsigned)(k - 1);
+    return (double)__uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u);
+}
+template <> __device__ double key_value<uint8_t>(unsigned long long k) { return (double)(k - 1); }
+template <> __device__ double key_value<uint16_t>(unsigned long long k) { return (double)(k - 1); }
+template <> __device__ double key_value<int16_t>(unsigned long long k) { return (double)((long long)k - 1 - 32768); }
+
+constexpr int MAX_CHUNK = 4096;                         // voxels of one frame per workgroup (16 per thread)
+
+// grid (chunks of a frame, T), 256 threads; keys [T][n_class] as uint64 in the output cells (zeroed by the caller)
+template <typename T>
+__global__ __launch_bounds__(256) void label_max_kernel(const T *__restrict__ vol, const unsigned char *__restrict__ lab, int X, int Y,
+                                                        long long frame, long long sx, long long sy, long long sz, long long st, int n_class,
+                                                        unsigned long long *keys) {
+    const int t = blockIdx.y;
+    unsigned long long best[MAXC];
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) best[c] = 0;
+    const long long i0 = (long long)blockIdx.x * MAX_CHUNK;
+    const long long i1 = i0 + MAX_CHUNK < frame ? i0 + MAX_CHUNK : frame;
+    for (long long i = i0 + threadIdx.x; i < i1; i += 256) {    // x fastest across the lanes: coalesced for F-ordered volumes
+        const int k = lab[frame * t + i];
+        if (k >= n_class) continue;
+        const int x = (int)(i % X);
+        const long long r = i / X;
+        const int y = (int)(r % Y), z = (int)(r / Y);
+        const unsigned long long key = max_key(vol[x * sx + y * sy + z * sz + t * st]);
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c)                  // unrolled selects keep best[] in registers
+            if (c == k && key > best[c]) best[c] = key;
+    }
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) {
+        if (c >= n_class) continue;                     // uniform: no divergence, and the loop stays unrolled
+        unsigned long long b = best[c];
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long u = __shfl_xor(b, o);
+            b = u > b ? u : b;
+        }
+        if ((threadIdx.x & 63) == 0 && b) atomicMax(&keys[(size_t)t * n_class + c], b);
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void label_max_final_kernel(unsigned long long *keys, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long k = keys[i];
+    reinterpret_cast<double *>(keys)[i] = k ? key_value<T>(k) : -INFINITY;      // an empty mask: the identity of max
+}
+
+template <typename T>
+int label_max_impl(const T *d_vol, int X, int Y, int Z, int T_, int64_t sx, int64_t sy, int64_t sz, int64_t st, const uint8_t *d_lab,
+                   int n_class, double *d_max, hipStream_t s) {
+    const long long frame = (long long)X * Y * Z;
+    const int n = T_ * n_class;
+    if (hipMemsetAsync(d_max, 0, sizeof(double) * (size_t)n, s) != hipSuccess) { set_error("label_max: memset failed"); return UKBB_EDEVICE; }
+    unsigned long long *keys = reinterpret_cast<unsigned long long *>(d_max);
+    hipLaunchKernelGGL((label_max_kernel<T>), dim3((unsigned)((frame + MAX_CHUNK - 1) / MAX_CHUNK), (unsigned)T_), dim3(256), 0, s,
+                       d_vol, d_lab, X, Y, frame, (long long)sx, (long long)sy, (long long)sz, (long long)st, n_class, keys);
+    hipLaunchKernelGGL((label_max_final_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, keys, n);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("label_max: launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
+    return UKBB_OK;
+}
+
+}  // namespace
+}  // namespace ukbb
+
+using namespace ukbb;
+
+extern "C" {
+
+int ukbb_fcn_label_components(const uint8_t *d_lab, int X, int Y, int Z, int T, int n_class, int min_size, int32_t *d_work,
+                              int32_t *d_n_large, void *stream) {
+    const long long n = (long long)X * Y * Z * T;
+    if (!d_lab || !d_work || !d_n_large || X < 1 || Y < 1 || Z < 1 || T < 1 || n_class < 1 || n_class > MAXC ||
+        (long long)Z * T > 65535 || 2 * n > 0x7FFFFFFFll) {
+        set_error("label_components: bad argument (n_class 1..16, Z*T <= 65535, 2*X*Y*Z*T < 2^31)");
+        return UKBB_EINVAL;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    int *parent = d_work, *size = d_work + n;
+    if (hipMemsetAsync(d_n_large, 0, sizeof(int32_t) * (size_t)T * n_class, s) != hipSuccess) {
+        set_error("label_components: memset failed");
+        return UKBB_EDEVICE;
+    }
+    const unsigned tiles = (unsigned)(((X + TILE - 1) / TILE) * ((Y + TILE - 1) / TILE));
+    const unsigned nb = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(ccl_local_kernel, dim3(tiles, (unsigned)(Z * T)), dim3(256), 0, s, d_lab, X, Y, parent, size);
+    hipLaunchKernelGGL(ccl_border_kernel, dim3(nb), dim3(256), 0, s, d_lab, X, Y, Z, n, parent);
+    hipLaunchKernelGGL(ccl_size_kernel, dim3(nb), dim3(256), 0, s, d_lab, n, (const int *)parent, size);
+    hipLaunchKernelGGL(ccl_count_kernel, dim3(nb), dim3(256), 0, s, d_lab, n, (long long)X * Y * Z, n_class, min_size,
+                       (const int *)parent, (const int *)size, d_n_large);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("label_components: launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
+    return UKBB_OK;
+}
+
+int ukbb_fcn_label_max(const void *d_vol, int nifti_datatype, int X, int Y, int Z, int T, int64_t sx, int64_t sy, int64_t sz, int64_t st,
+                       const uint8_t *d_lab, int n_class, double *d_max, void *stream) {
+    if (!d_vol || !d_lab || !d_max || X < 1 || Y < 1 || Z < 1 || T < 1 || T > 65535 || n_class < 1 || n_class > MAXC) {
+        set_error("label_max: bad argument (n_class 1..16, T <= 65535)");
+        return UKBB_EINVAL;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    switch (nifti_datatype) {
+    case 16: return label_max_impl(static_cast<const float *>(d_vol), X, Y, Z, T, sx, sy, sz, st, d_lab, n_class, d_max, s);
+    case 2: return label_max_impl(static_cast<const uint8_t *>(d_vol), X, Y, Z, T, sx, sy, sz, st, d_lab, n_class, d_max, s);
+    case 4: return label_max_impl(static_cast<const int16_t *>(d_vol), X, Y, Z, T, sx, sy, sz, st, d_lab, n_class, d_max, s);
+    case 512: return label_max_impl(static_cast<const uint16_t *>(d_vol), X, Y, Z, T, sx, sy, sz, st, d_lab, n_class, d_max, s);
+    default:
+        set_error("label_max: NIfTI datatype %d is not supported (16 float32, 2 uint8, 4 int16, 512 uint16)", nifti_datatype);
+        return UKBB_EINVAL;
+    }
+}
+
+}  // extern "C"

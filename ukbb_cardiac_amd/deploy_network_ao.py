@@ -20,7 +20,7 @@ import numpy as np
 if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from ukbb_cardiac_amd import measures, nifti, pipeline             # noqa: E402
+from ukbb_cardiac_amd import aorta_qc, measures, nifti, pipeline   # noqa: E402
 from ukbb_cardiac_amd.flags import FlagError, FlagSet              # noqa: E402
 from ukbb_cardiac_amd.shard import default_device, shard_from_env, subjects_for_shard   # noqa: E402
 
@@ -57,8 +57,12 @@ def define_flags():
                      'the per-frame class counts the GPU leaves behind.  Of the evaluation script\'s quality control '
                      '(cardiac_utils.aorta_pass_quality_control, eval_aortic_area.py:68-69) the criteria that need only the areas are applied '
                      '(1: zero area in a frame, 4: abrupt change between adjacent frames, 5: max / min >= 2) and a failing subject is dropped with '
-                     'the script\'s message; criteria 2 (image noise) and 3 (connected components) are NOT applied.')
+                     'the script\'s message; criteria 2 (image noise) and 3 (connected components) are applied only with --aortic_qc_full.')
     fs.DEFINE_boolean('aortic_qc', True, 'With --output_csv: apply the count-only quality-control criteria above (false: every segmented subject gets a row).')
+    fs.DEFINE_boolean('aortic_qc_full', False, 'With --output_csv and --aortic_qc: apply all five criteria of aorta_pass_quality_control in the script\'s '
+                      'order, adding 2 (max intensity of a frame / mean ED intensity under the label >= 3) and 3 (two or more '
+                      '18-connected components of more than 10 pixels in a frame); computed on the GPU next to the labels on the device '
+                      'path (aorta_qc.py).')
     fs.DEFINE_string('pressure_csv', '', 'With --output_csv: the blood-pressure spreadsheet of eval_aortic_area.py:41-46 for the distensibility columns '
                      '(left empty without it).')
     fs.DEFINE_integer('num_shards', env_cnt, 'Number of workers sharing data_dir.')
@@ -110,16 +114,18 @@ def run(FLAGS, forward, log=print, cine_forward=None, engine=None):
     processed = []
     seq = FLAGS.seq_name
     csv_rows = None
+    qc_full = bool(getattr(FLAGS, 'output_csv', '') and getattr(FLAGS, 'aortic_qc', True) and getattr(FLAGS, 'aortic_qc_full', False))
     if getattr(FLAGS, 'output_csv', ''):
         if not FLAGS.process_seq:
             raise ValueError('--output_csv writes the table of aortic/eval_aortic_area.py: it needs sequence mode')
         csv_rows = {}
         central_pp = measures.read_central_pp(FLAGS.pressure_csv) if getattr(FLAGS, 'pressure_csv', '') else {}
 
-        def _qc_row(counts, pixdim, pp):
-            """The subject's table line, or None when the count-only quality control drops it (the script's own message is printed)."""
+        def _qc_row(counts, pixdim, pp, stats=None):
+            """The subject's table line, or None when the quality control drops it (the script's own message is printed);
+            ``stats``: the aorta_qc statistics, needed with --aortic_qc_full."""
             if getattr(FLAGS, 'aortic_qc', True):
-                ok, why = measures.aorta_qc_from_counts(counts)
+                ok, why = aorta_qc.aorta_qc_full(counts, stats) if qc_full else measures.aorta_qc_from_counts(counts)
                 if not ok:
                     log(why)
                     return None
@@ -169,23 +175,29 @@ def run(FLAGS, forward, log=print, cine_forward=None, engine=None):
             log('  Segmenting full sequence ...')
             t0 = time.time()
             on_device = sequence_on_device(FLAGS, engine, image, log)
-            counts = None
+            counts = qc_stats = None
             if on_device and windowed:
                 from ukbb_cardiac_amd.device_pipeline import aortic_lstm_sequence_device
                 pred, aux = aortic_lstm_sequence_device(image, engine, True, FLAGS.weight_R, FLAGS.weight_r, FLAGS.time_step,
-                                                        return_aux='counts')
-                counts = aux['counts']
+                                                        return_aux='counts', qc=qc_full)
+                counts, qc_stats = aux['counts'], aux.get('qc')
             elif on_device:
                 from ukbb_cardiac_amd.device_pipeline import aortic_unet_sequence_device
-                pred, aux = aortic_unet_sequence_device(image, engine, FLAGS.batch_slices, return_aux=True)
-                counts = aux['counts']
+                pred, aux = aortic_unet_sequence_device(image, engine, FLAGS.batch_slices, return_aux=True, qc=qc_full)
+                counts, qc_stats = aux['counts'], aux.get('qc')
             else:
+                if qc_full and not FLAGS.z_score:
+                    image_qc = image.copy()                 # rescale_intensity clips `image` in place; the script reads the file
+                else:
+                    image_qc = image
                 if windowed:
                     prob = pipeline.aortic_lstm_prob_sequence(image, cine_forward, FLAGS.z_score, FLAGS.weight_R, FLAGS.weight_r,
                                                               time_step=FLAGS.time_step)
                 else:
                     prob = pipeline.aortic_prob_sequence(image, forward, FLAGS.z_score, FLAGS.batch_slices)
                 pred = np.argmax(prob, axis=-1).astype(np.int32)      # host argmax, as :189
+                if qc_full:
+                    qc_stats = aorta_qc.stats_host(image_qc, pred)
             if FLAGS.save_seg:
                 log('  Saving segmentation ...')
                 save(pred, '{0}/seg_{1}.nii.gz'.format(data_dir, seq), nim.affine, nim.header['pixdim'])
@@ -194,7 +206,7 @@ def run(FLAGS, forward, log=print, cine_forward=None, engine=None):
             if csv_rows is not None:
                 if counts is None:
                     counts = measures.counts_from_labels(pred, 3)
-                csv_rows[data] = _qc_row(counts, nim.header['pixdim'], _pp(central_pp, data, log))
+                csv_rows[data] = _qc_row(counts, nim.header['pixdim'], _pp(central_pp, data, log), qc_stats)
         else:
             if windowed:                                               # reference: deploy_network_ao.py:202-205
                 log('{0} does not support frame-wise segmentation. Please use the -process_seq flag.'.format(FLAGS.model))
@@ -232,7 +244,9 @@ def run(FLAGS, forward, log=print, cine_forward=None, engine=None):
             elif os.path.exists(image_name) and os.path.exists(seg_name):
                 log(data)
                 seg = nifti.load(seg_name).get_data()
-                row = _qc_row(measures.counts_from_labels(seg, 3), nifti.load_header(image_name)['pixdim'], _pp(central_pp, data, log))
+                stats = aorta_qc.stats_host(nifti.load(image_name).get_data(), seg) if qc_full else None
+                row = _qc_row(measures.counts_from_labels(seg, 3), nifti.load_header(image_name)['pixdim'], _pp(central_pp, data, log),
+                              stats)
             else:
                 continue
             if row is not None:                                 # None: dropped by the quality control, as eval_aortic_area.py:68-69

@@ -339,13 +339,55 @@ def device_zscore_matches_numpy(engine, warn=None, dtype=np.float32):
     return _ZSCORE_OK[key][0]
 
 
-def aortic_lstm_sequence_device(image, engine, z_score=True, weight_R=5, weight_r=0.1, time_step=1, return_aux=False):
+def device_qc_stats(vol_t, lab_t, dtype, n_class, stream=0, min_size=None):
+    """The three statistics of aorta_qc (``n_large``, ``max``, ``mean_ed``: see that module) of the dense (X,Y,Z,T) torch
+    cine ``vol_t`` (``dtype``: the host volume's dtype; a uint16 cine is an int16 tensor) and the uint8 labels ``lab_t`` in NIfTI
+    order that ukbb_fcn_unpack_labels left on the device, equal to aorta_qc.stats_host of the same arrays.  Components and
+    maxima: ukbb_fcn_label_components / ukbb_fcn_label_max; the mean: ukbb_fcn_label_compact + numpy's pairwise tree
+    (ukbb_fcn_pairwise_sum / _t) and numpy's division, as device_zscore_stats."""
+    import torch
+    from .aorta_qc import PIXEL_THRES
+    min_size = PIXEL_THRES if min_size is None else min_size
+    X, Y, Z, T = vol_t.shape
+    dtype = np.dtype(dtype)
+    code = 16 if dtype == np.float32 else NIFTI_DATATYPE[dtype]
+    sx, sy, sz, st = vol_t.stride()
+    work = torch.empty(2 * X * Y * Z * T, dtype=torch.int32, device=vol_t.device)
+    n_large = torch.empty((T, n_class), dtype=torch.int32, device=vol_t.device)
+    _lib.check(_lib.lib.ukbb_fcn_label_components(lab_t.data_ptr(), X, Y, Z, T, n_class, min_size, work.data_ptr(), n_large.data_ptr(),
+                                                  stream), 'ukbb_fcn_label_components')
+    mx = torch.empty((T, n_class), dtype=torch.float64, device=vol_t.device)
+    _lib.check(_lib.lib.ukbb_fcn_label_max(vol_t.data_ptr(), code, X, Y, Z, T, sx, sy, sz, st, lab_t.data_ptr(), n_class, mx.data_ptr(),
+                                           stream), 'ukbb_fcn_label_max')
+    comp = torch.empty(X * Y * Z, dtype=vol_t.dtype, device=vol_t.device)
+    rt = np.float32 if dtype == np.float32 else np.float64        # numpy's .mean() result type (float64 for integer data)
+    means = [rt(np.nan)]
+    for k in range(1, n_class):
+        n_k = C.c_uint64(0)
+        _lib.check(_lib.lib.ukbb_fcn_label_compact(vol_t.data_ptr(), code, X, Y, Z, sx, sy, sz, lab_t.data_ptr(), k, comp.data_ptr(),
+                                                   C.byref(n_k), stream), 'ukbb_fcn_label_compact')
+        n = np.intp(n_k.value)                                     # _count_reduce_items: an intp count
+        if dtype == np.float32:
+            s = C.c_float(0)
+            _lib.check(_lib.lib.ukbb_fcn_pairwise_sum(comp.data_ptr(), int(n), 0, 0.0, C.byref(s), stream), 'ukbb_fcn_pairwise_sum')
+        else:
+            s = C.c_double(0)
+            _lib.check(_lib.lib.ukbb_fcn_pairwise_sum_t(comp.data_ptr(), code, int(n), 0, 0.0, C.byref(s), stream), 'ukbb_fcn_pairwise_sum_t')
+        with np.errstate(all='ignore'):
+            means.append(rt(rt(s.value) / n))                      # np.mean: ret.dtype.type(ret / rcount); empty: 0 / 0 = NaN
+    return {'n_large': n_large.cpu().numpy(), 'max': mx.cpu().numpy(), 'mean_ed': np.array(means, dtype=rt)}
+
+
+def aortic_lstm_sequence_device(image, engine, z_score=True, weight_R=5, weight_r=0.1, time_step=1, return_aux=False, qc=False):
     """pipeline.aortic_lstm_prob_sequence + the argmax of deploy_network_ao.py:189 with the array work on the GPU:
     (X,Y,Z,T) float32 / uint8 / int16 / uint16 aortic cine -> int32 label volume (X,Y,Z,T).  Only the raw volume goes in and uint8 labels come
     back (the host path moves the padded float32 cine in and 3 float32 probability maps per voxel out, and spends more
     time in np.percentile / np.argmax than the network takes).  ``aux['prob']`` (X,Y,Z,T,C) on request; ``aux['counts']``
-    = pixels of each class per frame (what eval_aortic_area.py:60-78 turns into areas)."""
+    = pixels of each class per frame (what eval_aortic_area.py:60-78 turns into areas); with ``qc`` (needs ``return_aux``),
+    ``aux['qc']`` = device_qc_stats of the cine and the labels, the input of aorta_qc.aorta_qc_full."""
     import torch
+    if qc and not return_aux:
+        raise ValueError('qc=True returns its statistics in aux: pass return_aux')
     if image.ndim != 4:
         raise TypeError('expected a 4-D (X,Y,Z,T) cine; use pipeline.aortic_lstm_prob_sequence otherwise')
     _check_dtype(image, 'pipeline.aortic_lstm_prob_sequence')
@@ -378,18 +420,23 @@ def aortic_lstm_sequence_device(image, engine, z_score=True, weight_R=5, weight_
     if not return_aux:
         return out
     aux = {'mu': mu, 'den': den, 'n_roi': n_roi, 'val_l': val_l, 'counts': counts.cpu().numpy()}
+    if qc:
+        aux['qc'] = device_qc_stats(vol, lab, image.dtype, n_class, stream)
     if return_aux != 'counts':                                 # 'counts': skip the 78 MB of probabilities
         p = prob[:, :, x_pre:x_pre + X, y_pre:y_pre + Y].permute(2, 3, 1, 0, 4)
         aux['prob'] = p.cpu().numpy()
     return out, aux
 
 
-def aortic_unet_sequence_device(image, engine, batch_slices=128, return_aux=False):
+def aortic_unet_sequence_device(image, engine, batch_slices=128, return_aux=False, qc=False):
     """pipeline.aortic_prob_sequence + the argmax of deploy_network_ao.py:189 for the frame-wise 'UNet' model with the array work
     on the GPU: device z-score, pack, batched forward (the engine's label map IS the lowest-index argmax of the float32
     probabilities it would return: ``softmax_argmax``, csrc/kernels.h), labels back as uint8.
-    (X,Y,Z,T) float32 / uint8 / int16 / uint16 -> int32 labels (X,Y,Z,T)."""
+    (X,Y,Z,T) float32 / uint8 / int16 / uint16 -> int32 labels (X,Y,Z,T).  With ``qc`` (needs ``return_aux``), ``aux['qc']`` =
+    device_qc_stats of the cine and the labels, as aortic_lstm_sequence_device."""
     import torch
+    if qc and not return_aux:
+        raise ValueError('qc=True returns its statistics in aux: pass return_aux')
     if image.ndim != 4:
         raise TypeError('expected a 4-D (X,Y,Z,T) cine; use pipeline.aortic_prob_sequence otherwise')
     _check_dtype(image, 'pipeline.aortic_prob_sequence')
@@ -414,5 +461,8 @@ def aortic_unet_sequence_device(image, engine, batch_slices=128, return_aux=Fals
                                                lab.data_ptr(), counts.data_ptr(), stream), 'ukbb_fcn_unpack_labels')
     out = lab.cpu().numpy().reshape((X, Y, Z, T), order='F').astype(np.int32)
     if return_aux:
-        return out, {'mu': mu, 'den': den, 'n_roi': n_roi, 'val_l': val_l, 'counts': counts.cpu().numpy()}
+        aux = {'mu': mu, 'den': den, 'n_roi': n_roi, 'val_l': val_l, 'counts': counts.cpu().numpy()}
+        if qc:
+            aux['qc'] = device_qc_stats(vol, lab, image.dtype, n_class, stream)
+        return out, aux
     return out
