@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define UKBB_FCN_ABI_VERSION 10
+#define UKBB_FCN_ABI_VERSION 11
 #define UKBB_FCN_MAX_LEVEL 8
 
 #define UKBB_OK 0
@@ -175,16 +175,49 @@ int ukbb_fcn_forward_seq(ukbb_fcn_handle *h, const float *image, int n_seq, int 
  *   every step's hidden maps 2*T*Wn*HW*16*e  +  hoisted gate pre-activations 2*F*HW*64*e  +  first-step hidden maps 2*F*HW*16*e
  *   +  cell state (2*F + Wn)*HW*16*4.
  * F = Wn = 100 frames of 256x256: 7.5 + 3.4 + 0.8 + 1.3 = 13.0 GB in fp32, 7.2 GB in bf16 -- several handles per GPU, or cines of
- * hundreds of frames, reach UKBB_ENOMEM on that, not on the U-Net (0.9 GB).
+ * hundreds of frames, reach UKBB_ENOMEM on that unless a scratch budget is set (below).  Exactly (what ukbb_fcn_cine_scratch_bytes
+ * returns): the gate pre-activations and the cell state live in the kernels' tile layouts, so HW in those two terms is the map padded to
+ * whole tiles (fp32: 8 rows x 32 or 16 columns, the region shape of the plan; bf16: 2 rows x 32 columns); the U-Net workspace is
+ * F * (every activation map of the plan) * 4 bytes in either precision; the tables take (T*Wn + F*T)*4 + (T + F)*8 bytes.
+ * With a scratch budget (ABI 11, ukbb_fcn_set_scratch_budget) the windows run in ascending chunks of Wc, each on the circular run of
+ * R = min(F, (Wc - 1)*time_step + T) frames it touches: the formula above with Wn -> Wc in the first and last term and F -> R everywhere
+ * else (U-Net workspace included), plus R*HW*4 bytes for the contiguous copy of the run's input frames and the same tables -- no term
+ * grows with F but the tables.  Frames shared by neighbouring chunks (T - time_step of them) are recomputed: U-Net features, gate
+ * pre-activations and first steps are per-frame quantities, so every chunk size gives the bits of the unchunked call.  Wc = the largest that
+ * fits; a budget at or above the unchunked size runs unchunked.
  * Temporal-UNet (kind 3): the same call, bit for bit the same tiling arithmetic and corner cases, but each window runs the whole 3-D
  * network on its T frames (its first layer reads them from `image` through a window -> frame table).  Windows run in chunks of Wc,
  * in ascending order (results do not depend on Wc); device scratch the handle keeps, with HW = H*W, C = n_class and the standard
  * filters 16..256 (the activations of every layer, 152*HW floats per frame):
  *   Wc*T*(152 + C)*HW*4 bytes  +  tables (Wn*T + F*T)*4 + (T + F)*8 bytes,
- * Wc = the largest number of windows that keeps the first term within 4e9 bytes (at least 1; UKBB_TEMPORAL_CHUNK_WINDOWS=n sets it):
+ * Wc = the largest number of windows that keeps the first term within 4e9 bytes (at least 1), or, with a scratch budget, the whole sum
+ * within the budget; UKBB_TEMPORAL_CHUNK_WINDOWS=n overrides both (a test knob):
  * 256x256, T = 9, C = 3: Wc = 10, 3.66 GB, whatever the number of frames. */
 int ukbb_fcn_forward_cine(ukbb_fcn_handle *h, const float *image, int n_frames, int height, int width,
                           int weight_R, double weight_r, int time_step, float *prob, int32_t *pred, void *stream);
+
+/* -- scratch budget of forward_cine (ABI 11) ------------------------------------------------------------------------
+ * bytes = 0 (the default): no budget -- forward_cine runs as described above (UNet-LSTM: one chunk; Temporal-UNet: the 4e9-byte rule).
+ * bytes > 0: the device memory forward_cine may hold for its per-cine scratch (everything in the formulas above, the U-Net / 3-D network
+ * activation workspace included; weights excluded).  A budget below what one window needs makes forward_cine return UKBB_EINVAL with the
+ * minimum for that shape in the message; the handle stays usable.  Setting a new non-zero budget releases the handle's activation and
+ * cine buffers (after a device synchronise), and under a budget a forward_cine with another shape or chunk plan than the previous one
+ * releases them before it allocates -- so after every budgeted call ukbb_fcn_scratch_bytes() equals ukbb_fcn_cine_scratch_bytes() of that
+ * call and is <= the budget.  (Without a budget buffers only grow.)  The UNet-LSTM A/B forms UKBB_LSTM_BF16_WINOGRAD /
+ * UKBB_LSTM_BF16_UNHOIST run unchunked only.  FCN / UNet handles accept the call and ignore it. */
+int ukbb_fcn_set_scratch_budget(ukbb_fcn_handle *h, uint64_t bytes);
+/* Bytes of device memory the handle holds right now in its activation, staging and cine buffers (weights and packed filters excluded). */
+uint64_t ukbb_fcn_scratch_bytes(const ukbb_fcn_handle *h);
+/* What forward_cine allocates for this call under `budget` (0 = none) on a fresh handle: host arithmetic only, no device needed (like
+ * ukbb_fcn_weight_count).  precision: UKBB_PREC_FP32 | UKBB_PREC_BF16.  0 for a malformed request (kinds 0 / 1, shape not a multiple of 16,
+ * fewer frames than the window radius, time_step < 1, bf16 Temporal-UNet) and for a budget below the minimum.  The engine plans its chunks
+ * with the same function.  The fp32 region shape is chosen for the MI355X's 256 compute units and cines of n_frames frames. */
+uint64_t ukbb_fcn_cine_scratch_bytes(const ukbb_fcn_arch *arch, int precision, int n_frames, int height, int width, int time_step,
+                                     uint64_t budget);
+/* The smallest non-zero budget forward_cine accepts for this call (0: malformed request), and the windows per chunk Wc it runs with
+ * under `budget` (0: malformed or below the minimum; the number of windows ceil(n_frames / time_step) when unchunked). */
+uint64_t ukbb_fcn_cine_min_scratch_bytes(const ukbb_fcn_arch *arch, int precision, int n_frames, int height, int width, int time_step);
+int ukbb_fcn_cine_chunk_windows(const ukbb_fcn_arch *arch, int precision, int n_frames, int height, int width, int time_step, uint64_t budget);
 
 /* ---- device-side pre/post-processing of the deploy loop ----------------
  * Stateless; device pointers; asynchronous on `stream` unless stated.  They take the host numpy work

@@ -12,7 +12,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('UKBB_FCN_LIB') or os.path.join(_HERE, 'libukbb_fcn.so')   # override: A/B builds of the kernels
-ABI_VERSION = 10
+ABI_VERSION = 11
 MAX_LEVEL = 8
 
 # every symbol include/ukbb_fcn.h declares
@@ -29,6 +29,8 @@ EXPORTS = [
     'ukbb_fcn_synth_volume',
     'ukbb_fcn_select_kth_t', 'ukbb_fcn_rescale_pack_t', 'ukbb_fcn_roi_compact_t', 'ukbb_fcn_pairwise_sum_t', 'ukbb_fcn_zscore_pack_t',
     'ukbb_fcn_label_components', 'ukbb_fcn_label_max', 'ukbb_fcn_label_compact',
+    'ukbb_fcn_set_scratch_budget', 'ukbb_fcn_scratch_bytes', 'ukbb_fcn_cine_scratch_bytes',
+    'ukbb_fcn_cine_min_scratch_bytes', 'ukbb_fcn_cine_chunk_windows',
 ]
 
 
@@ -114,6 +116,16 @@ def _load():
     lib.ukbb_fcn_label_max.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i64, i64, i64, i64, vp, C.c_int, vp, vp]
     lib.ukbb_fcn_label_compact.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, i64, i64, i64, vp, C.c_int, vp,
                                            C.POINTER(C.c_uint64), vp]
+    lib.ukbb_fcn_set_scratch_budget.argtypes = [vp, C.c_uint64]
+    lib.ukbb_fcn_scratch_bytes.restype = C.c_uint64
+    lib.ukbb_fcn_scratch_bytes.argtypes = [vp]
+    cine_q = [C.POINTER(ArchStruct), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.ukbb_fcn_cine_scratch_bytes.restype = C.c_uint64
+    lib.ukbb_fcn_cine_scratch_bytes.argtypes = cine_q + [C.c_uint64]
+    lib.ukbb_fcn_cine_min_scratch_bytes.restype = C.c_uint64
+    lib.ukbb_fcn_cine_min_scratch_bytes.argtypes = cine_q
+    lib.ukbb_fcn_cine_chunk_windows.restype = C.c_int
+    lib.ukbb_fcn_cine_chunk_windows.argtypes = cine_q + [C.c_uint64]
     lib.ukbb_fcn_gzip_labels_bound.restype = C.c_uint64
     lib.ukbb_fcn_gzip_labels_bound.argtypes = [C.c_uint64, C.c_int, C.c_uint64]
     lib.ukbb_fcn_gzip_labels.restype = C.c_int64

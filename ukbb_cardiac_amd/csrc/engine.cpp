@@ -149,6 +149,11 @@ struct ukbb_fcn_handle {
     // lstm_gx / lstm_c1 / lstm_h1: per direction and FRAME (the x pass); lstm_c: per window; lstm_hall: per direction, step and window
     DevBuf lstm_gx, lstm_c1, lstm_h1, lstm_c, lstm_hall, lstm_probw, lstm_aux;   // lstm_aux: int maps / orders / double weights (raw bytes)
     long long lstm_aux_key = -1;              // which tables lstm_aux holds (shape-keyed, uploaded once per shape)
+    DevBuf lstm_img;                          // forward_cine in chunks: the chunk's frame run, contiguous (a run may wrap from frame F-1 to 0)
+
+    // forward_cine scratch budget (ukbb_fcn_set_scratch_budget; 0 = none)
+    uint64_t scratch_budget = 0;
+    long long budget_key = -1;                // the (shape, chunk plan) the buffers were allocated for under the budget
 
     // Temporal-UNet (kind 3)
     const int *t3d_map = nullptr;             // first layer: batch image n reads frame t3d_map[n] (NULL: frame n); set around run_plan
@@ -426,9 +431,9 @@ int finer_sibling(int id, int ks, int stride, int c0, int c1, int cout, int Ho, 
 // Winograd F(2x4,3x3) comes with 8 x 32-pixel regions (304) and 8 x 16 (305); both compute every tile with the same arithmetic (same tile
 // grid, same transforms, same K order), so the choice is a matter of filling the CUs: the region shape whose item count wastes less of
 // the last round wins, 304 on a tie (fewer, longer items: FCN level 2 60 us against 65); small batches take the finer one.
-int pick_wino24(int id, int ks, int stride, int c0, int c1, int cout, int Ho, int Wo, int N) {
+int pick_wino24(int id, int ks, int stride, int c0, int c1, int cout, int Ho, int Wo, int N, int cus = -1) {      // cus < 0: the current device's
     if (id != 304 && id != 305) return id;
-    const int cus = device_cu_count();
+    if (cus < 0) cus = device_cu_count();
     int best = id; double best_eff = -1.0;
     for (int cand : {304, 305}) {
         ConvConfig c;
@@ -631,6 +636,19 @@ int pick_fused_bf_cfg(const std::string &lname, int ks, int stride, int c0, int 
             (cand == forced || tile_fit_ok(cc, Ho, Wo))) return cand;
     }
     return -1;
+}
+
+int bf16_mode(int kind, int precision) { return precision != 1 ? 0 : kind != UKBB_KIND_FCN ? 2 : 1; }
+
+// Region width (32 | 16 columns) of the fused ConvLSTM gate-conv / cell kernel (kernels_wino24.hip) for a plan built for batches of N
+// on a device of `cus` compute units; 0 when the F(2x4) kernel does not apply.  Both shapes give identical bits; the choice sizes the
+// tile-padded gx / cell-state buffers, so build_plan and the host-only cine planner (cine_units) share it.
+int lstm_region_cols(const ukbb_fcn_arch &a, int H, int W, int N, int cus) {
+    int cfg = choose_cfg_raw("lstm_fw", 3, 1, a.n_filter[0], a.same_dim, 4 * a.same_dim, H, W, N, false, 0, false);
+    if (override_cfg("lstm_fw") < 0) cfg = pick_wino24(cfg, 3, 1, a.n_filter[0], a.same_dim, 4 * a.same_dim, H, W, N, cus);
+    ConvConfig c;
+    const bool have24 = cfg >= 0 && !find_cfg(cfg, c) && is_wino24(c) && c.wm == 4 && (c.tw == 32 || c.tw == 16);
+    return have24 ? c.tw : 0;
 }
 
 int add_conv(ukbb_fcn_handle *h, const std::string &lname, int in0, int in1, int c1, int H, int W, int stride,
@@ -1032,16 +1050,15 @@ int build_plan(ukbb_fcn_handle *h, int H, int W, int n_hint) {
             // 354.8 -> 372.1 us, x pass 754 -> 636 us, cine 8.17 -> 8.31 ms: the step is not bound by its bytes alone -- the second chunk's staging and MFMAs
             // cost more issue time than the gx loads they replace.  The hoisted form (r05) stays.
             h->lstm_bf_hoist = getenv("UKBB_LSTM_BF16_UNHOIST") == nullptr;
-            const int cfg = choose_cfg("lstm_fw", 3, 1, a.n_filter[0], a.same_dim, 4 * a.same_dim, H, W, n_hint, false, false);
-            ConvConfig c;
-            const bool have24 = cfg >= 0 && !find_cfg(cfg, c) && is_wino24(c) && c.wm == 4 && (c.tw == 32 || c.tw == 16);
+            const int cols24 = lstm_region_cols(a, H, W, n_hint, device_cu_count());
+            const bool have24 = cols24 != 0;
             // the bf16 plan's time steps run on launch_lstm_ws (kernels_ws.hip) and never touch the F(2x4) kernel: only the fp32 plan and the
             // bf16-storage Winograd A/B form need that tiling
             if (!have24 && (bf16_mode(h) != 2 || h->lstm_bf_wino)) {
                 set_err("the ConvLSTM needs the Winograd F(2x4) kernel (unset UKBB_NO_WINOGRAD / UKBB_NO_WINOGRAD24 / UKBB_CONV_CFG overrides)");
                 return UKBB_EARCH;
             }
-            h->lstm_tile_cols = have24 ? c.tw : 32;
+            h->lstm_tile_cols = have24 ? cols24 : 32;
             if (const char *e = getenv("UKBB_LSTM_TILE_COLS")) { const int v = atoi(e); if (v == 16 || v == 32) h->lstm_tile_cols = v; }   // A/B knob (identical bits)
             {
                 const HostLayer &B = h->layers[h->layer_index.at("lstm_bw")];
@@ -1147,7 +1164,8 @@ int check_shape(int n, int H, int W) {
     return UKBB_OK;
 }
 
-int prepare(ukbb_fcn_handle *h, int n, int H, int W) {
+// n: the batch the plan is chosen for; cap (>= 0): the batch the workspace is sized for when that is smaller (forward_cine in chunks; 0: plan only)
+int prepare(ukbb_fcn_handle *h, int n, int H, int W, int cap = -1) {
     int rc = check_shape(n, H, W);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(h->device), UKBB_EDEVICE);
@@ -1159,6 +1177,7 @@ int prepare(ukbb_fcn_handle *h, int n, int H, int W) {
         rc = build_plan(h, H, W, h->max_n);
         if (rc) { h->plan_h = h->plan_w = 0; return rc; }
     }
+    if (cap >= 0 && cap < n) n = cap;
     if (n > h->cap_n) {
         HIP_TRY(hipDeviceSynchronize(), UKBB_EDEVICE);
         rc = ensure_capacity(h, n);
@@ -1611,6 +1630,221 @@ int ukbb_fcn_forward_host(ukbb_fcn_handle *h, const float *image, int n, int hei
     return UKBB_OK;
 }
 
+// ---- forward_cine scratch planner (host only) -----------------------------------------------------------
+namespace {
+
+// Device bytes forward_cine holds per frame / per window of a cine at one (arch, precision, H, W).  DevBufs count floats; bf16 maps take half.
+struct CineUnits {
+    int kind = 0, T = 0, n_class = 0;
+    size_t HW = 0;
+    size_t act_frame = 0;        // the plan's activation workspace, floats per frame (U-Net: allocated as floats in either precision)
+    size_t esz = 4;              // UNet-LSTM: bytes per stored gx / hidden element
+    size_t gx_frame = 0;         // UNet-LSTM: gx elements per frame and direction (tile-padded: wino24_lstm_gx_floats / lstm_ws_gx_elems)
+    size_t c_item = 0;           // UNet-LSTM: cell-state floats per frame (c1, per direction) or window (c) (tile-padded likewise)
+    size_t h_item = 0;           // UNet-LSTM: hidden elements per frame or window, direction and step (HW * 16)
+};
+
+struct CinePlan {
+    int Wn = 0, Wc = 0, chunks = 0;
+    int run = 0;                 // frames of the longest chunk's run (F when unchunked)
+    uint64_t bytes = 0;          // what forward_cine holds for this call
+    uint64_t min_bytes = 0;      // the smallest budget that runs this call
+};
+
+size_t bytes_of(size_t elems, size_t esz) { return (elems * esz + 3) / 4 * 4; }      // a DevBuf of `elems` elements of esz bytes
+
+uint64_t cine_table_bytes(int F, int T, int Wn) {        // lstm_aux / t3d_aux: window -> frame map, per-frame order, window weights, per-frame weight sums
+    const size_t b_map = (size_t)T * Wn * sizeof(int), b_ord = (size_t)F * T * sizeof(int);
+    const size_t off_ord = (b_map + 7) / 8 * 8, off_wk = (off_ord + b_ord + 7) / 8 * 8, off_ws = off_wk + T * sizeof(double);
+    return (off_ws + F * sizeof(double) + 3) / 4 * 4;
+}
+
+// UNet-LSTM: bytes held with chunks of Wc windows whose longest run has R frames; stage = the contiguous copy of the run's input frames
+uint64_t lstm_cine_bytes(const CineUnits &u, int F, int Wn, int R, int Wc, bool stage) {
+    uint64_t b = (uint64_t)u.act_frame * R * 4;                                      // U-Net activations of R frames
+    if (stage) b += (uint64_t)u.HW * R * 4;                                          // lstm_img
+    b += bytes_of(2 * (size_t)R * u.gx_frame, u.esz);                                // lstm_gx
+    b += (uint64_t)2 * R * u.c_item * 4;                                             // lstm_c1
+    b += bytes_of(2 * (size_t)R * u.h_item, u.esz);                                  // lstm_h1
+    b += (uint64_t)Wc * u.c_item * 4;                                                // lstm_c
+    b += bytes_of(2 * (size_t)u.T * Wc * u.h_item, u.esz);                           // lstm_hall
+    return b + cine_table_bytes(F, u.T, Wn);
+}
+
+constexpr double T3D_CHUNK_BYTES = 4.0e9;      // Temporal-UNet without a budget: the chunk's activations + window probabilities stay within this
+
+// THE chunk plan of forward_cine, shared by the engine (units from its plan) and ukbb_fcn_cine_scratch_bytes (units from cine_units).
+// budget 0: UNet-LSTM one chunk, Temporal-UNet the T3D_CHUNK_BYTES rule.  false: the budget is below plan.min_bytes.
+bool plan_cine(const CineUnits &u, int F, int time_step, uint64_t budget, CinePlan &pl) {
+    const int T = u.T, Wn = (F + time_step - 1) / time_step;
+    pl = CinePlan();
+    pl.Wn = Wn;
+    if (u.kind == UKBB_KIND_TEMPORAL_UNET) {
+        const uint64_t per_window = (uint64_t)(u.act_frame + u.HW * u.n_class) * 4 * T, tables = cine_table_bytes(F, T, Wn);
+        pl.min_bytes = per_window + tables;
+        int Wc;
+        if (!budget) Wc = std::max(1, (int)std::min<double>(Wn, T3D_CHUNK_BYTES / (double)per_window));
+        else if (budget < pl.min_bytes) return false;
+        else Wc = (int)std::min<uint64_t>(Wn, (budget - tables) / per_window);
+        pl.Wc = Wc; pl.chunks = (Wn + Wc - 1) / Wc; pl.run = Wc * T;
+        pl.bytes = (uint64_t)Wc * per_window + tables;
+        return true;
+    }
+    // a chunk of n windows touches one circular run of (n - 1) * time_step + T frames (all F when that exceeds F)
+    auto run_of = [&](int n) { return (int)std::min<long long>(F, (long long)(n - 1) * time_step + T); };
+    const uint64_t whole = lstm_cine_bytes(u, F, Wn, F, Wn, false);
+    pl.min_bytes = Wn > 1 ? std::min(whole, lstm_cine_bytes(u, F, Wn, run_of(1), 1, true)) : whole;
+    if (!budget || budget >= whole) { pl.Wc = Wn; pl.chunks = 1; pl.run = F; pl.bytes = whole; return true; }
+    if (budget < pl.min_bytes) return false;
+    int lo = 1, hi = Wn - 1;                     // lstm_cine_bytes grows with Wc: the largest Wc < Wn that fits (Wc = 1 does, and Wn > 1 here)
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) / 2;
+        if (lstm_cine_bytes(u, F, Wn, run_of(mid), mid, true) <= budget) lo = mid; else hi = mid - 1;
+    }
+    pl.Wc = lo; pl.chunks = (Wn + lo - 1) / lo; pl.run = run_of(lo);
+    pl.bytes = lstm_cine_bytes(u, F, Wn, pl.run, lo, true);
+    return true;
+}
+
+// The units of a FRESH handle's plan for cines of F frames on an MI355X (256 compute units), without a device: the activation maps
+// build_plan / build_plan_t3d create and the ConvLSTM buffers run_bilstm sizes.  (The A/B environment knobs that add or drop a map,
+// or a handle whose plan was built for another frame count, can differ; the engine always plans with the units of its own plan.)
+bool cine_units(const ukbb_fcn_arch &a, int precision, int F, int H, int W, CineUnits &u) {
+    if (a.kind != UKBB_KIND_UNET_LSTM && a.kind != UKBB_KIND_TEMPORAL_UNET) return false;
+    if (precision != UKBB_PREC_FP32 && precision != UKBB_PREC_BF16) return false;
+    if (a.kind == UKBB_KIND_TEMPORAL_UNET && precision != UKBB_PREC_FP32) return false;
+    if (a.n_level < 1 || a.n_level > UKBB_FCN_MAX_LEVEL || a.fc < 1) return false;
+    const int bfm = bf16_mode(a.kind, precision);
+    u = CineUnits();
+    u.kind = a.kind; u.T = a.fc; u.n_class = a.n_class; u.HW = (size_t)H * W;
+    std::vector<int> lh(a.n_level), lw(a.n_level);
+    int hh = H, ww = W;
+    for (int l = 0; l < a.n_level; ++l) {
+        if (l > 0) { hh = (hh + 1) / 2; ww = (ww + 1) / 2; }
+        lh[l] = hh; lw[l] = ww;
+        int maps = a.n_block[l];
+        if (l == 0 && a.kind == UKBB_KIND_UNET_LSTM) {        // conv0_0 evaluated inside conv0_1's launch: no map of its own (build_plan: stem / can_fuse)
+            const bool std0 = a.n_block[0] >= 2 && a.n_filter[0] == 16;
+            const bool stem = bfm == 2 && getenv("UKBB_NO_FUSE_STEM") == nullptr && std0 && override_cfg("conv0_1") < 0;
+            const bool can_fuse = getenv("UKBB_NO_FUSE_FIRST") == nullptr && std0 && (bfm != 2 || pick_fused_bf_cfg("conv0_1", 3, 1, 16, 0, 16, H, W, 1) >= 0);
+            if (stem || can_fuse) --maps;
+        }
+        u.act_frame += (size_t)maps * hh * ww * a.n_filter[l];
+    }
+    for (int l = a.n_level - 2; l >= 0; --l)                  // transposed conv (2 x the level below), then the level's convs
+        u.act_frame += (size_t)4 * lh[l + 1] * lw[l + 1] * a.n_filter[l] + (size_t)a.n_block[l] * lh[l] * lw[l] * a.n_filter[l];
+    if (a.kind == UKBB_KIND_UNET_LSTM) {
+        if (a.same_dim != 16 || a.n_filter[0] != 16) return false;
+        u.esz = bfm == 2 ? 2 : 4;
+        u.h_item = u.HW * a.same_dim;
+        if (bfm == 2) { u.gx_frame = lstm_ws_gx_elems(H, W); u.c_item = lstm_ws_c_floats(H, W); }
+        else {
+            int tc = lstm_region_cols(a, H, W, F, 256);
+            if (!tc) return false;
+            if (const char *e = getenv("UKBB_LSTM_TILE_COLS")) { const int v = atoi(e); if (v == 16 || v == 32) tc = v; }
+            u.gx_frame = wino24_lstm_gx_floats(H, W, tc); u.c_item = wino24_lstm_c_floats(H, W, tc);
+        }
+    }
+    return true;
+}
+
+// the same from a handle's built plan
+void cine_units_of(const ukbb_fcn_handle *h, int H, int W, CineUnits &u) {
+    const ukbb_fcn_arch &a = h->arch;
+    u = CineUnits();
+    u.kind = a.kind; u.T = a.fc; u.n_class = a.n_class; u.HW = (size_t)H * W;
+    for (size_t i = 0; i < h->act.size(); ++i) u.act_frame += h->act_per_image[i];
+    if (a.kind != UKBB_KIND_UNET_LSTM) return;
+    const bool wsf = h->plan_bfio && !h->lstm_bf_wino;
+    u.esz = h->plan_bfio ? 2 : 4;
+    u.h_item = u.HW * a.same_dim;
+    u.gx_frame = wsf ? lstm_ws_gx_elems(H, W) : wino24_lstm_gx_floats(H, W, h->lstm_tile_cols);
+    u.c_item = wsf ? lstm_ws_c_floats(H, W) : wino24_lstm_c_floats(H, W, h->lstm_tile_cols);
+}
+
+bool cine_request_ok(int T, int F, int H, int W, int time_step) {
+    if (F < 1 || H < 16 || W < 16 || (H % 16) || (W % 16) || time_step < 1 || T < 1 || !(T & 1)) return false;
+    if ((long long)F * H * W > (1ll << 31) - 1) return false;
+    return F >= (T - 1) / 2;
+}
+
+void scratch_bufs(ukbb_fcn_handle *h, std::vector<DevBuf *> &v) {
+    v = {&h->io_image, &h->io_logits, &h->io_prob, &h->io_pred, &h->lstm_gx, &h->lstm_c1, &h->lstm_h1, &h->lstm_c, &h->lstm_hall,
+         &h->lstm_probw, &h->lstm_aux, &h->lstm_img, &h->t3d_aux, &h->t3d_probw};
+    for (auto &b : h->act) v.push_back(b.get());
+}
+
+// frees every activation and cine buffer (the plan stays); nothing of the handle may be in flight afterwards
+int release_scratch(ukbb_fcn_handle *h) {
+    HIP_TRY(hipSetDevice(h->device), UKBB_EDEVICE);
+    HIP_TRY(hipDeviceSynchronize(), UKBB_EDEVICE);
+    std::vector<DevBuf *> bufs;
+    scratch_bufs(h, bufs);
+    for (DevBuf *b : bufs) {
+        if (b->p) (void)hipFree(b->p);
+        b->p = nullptr; b->n = 0;
+    }
+    h->cap_n = 0;
+    h->lstm_aux_key = h->t3d_aux_key = h->budget_key = -1;
+    return UKBB_OK;
+}
+
+// Under a budget the buffers hold exactly what the chunk plan of the LAST call needs: a call with another shape or plan releases them
+// first (buffers only grow otherwise, and two shapes' maxima together could exceed the budget).
+int budget_enter(ukbb_fcn_handle *h, int F, int H, int W, int time_step, const CinePlan &pl) {
+    if (!h->scratch_budget) return UKBB_OK;
+    const long long key = ((((((long long)F * 4099 + H) * 4099 + W) * 4099 + time_step) * 4099 + pl.Wc) * 4 + h->precision) ^ (long long)(h->scratch_budget * 0x9E3779B97F4A7C15ull >> 1);
+    if (h->budget_key == key) return UKBB_OK;
+    int rc = release_scratch(h);
+    if (rc) return rc;
+    h->budget_key = key;
+    return UKBB_OK;
+}
+
+}  // namespace
+
+uint64_t ukbb_fcn_cine_scratch_bytes(const ukbb_fcn_arch *arch, int precision, int n_frames, int height, int width, int time_step, uint64_t budget) {
+    if (!arch || !ukbb_fcn_weight_count(arch)) return 0;
+    CineUnits u;
+    CinePlan pl;
+    if (!cine_request_ok(arch->fc, n_frames, height, width, time_step) || !cine_units(*arch, precision, n_frames, height, width, u)) return 0;
+    return plan_cine(u, n_frames, time_step, budget, pl) ? pl.bytes : 0;
+}
+
+uint64_t ukbb_fcn_cine_min_scratch_bytes(const ukbb_fcn_arch *arch, int precision, int n_frames, int height, int width, int time_step) {
+    if (!arch || !ukbb_fcn_weight_count(arch)) return 0;
+    CineUnits u;
+    CinePlan pl;
+    if (!cine_request_ok(arch->fc, n_frames, height, width, time_step) || !cine_units(*arch, precision, n_frames, height, width, u)) return 0;
+    plan_cine(u, n_frames, time_step, 0, pl);
+    return pl.min_bytes;
+}
+
+int ukbb_fcn_cine_chunk_windows(const ukbb_fcn_arch *arch, int precision, int n_frames, int height, int width, int time_step, uint64_t budget) {
+    if (!arch || !ukbb_fcn_weight_count(arch)) return 0;
+    CineUnits u;
+    CinePlan pl;
+    if (!cine_request_ok(arch->fc, n_frames, height, width, time_step) || !cine_units(*arch, precision, n_frames, height, width, u)) return 0;
+    return plan_cine(u, n_frames, time_step, budget, pl) ? pl.Wc : 0;
+}
+
+int ukbb_fcn_set_scratch_budget(ukbb_fcn_handle *h, uint64_t bytes) {
+    if (!h) { set_err("set_scratch_budget: NULL handle"); return UKBB_EINVAL; }
+    if (h->arch.kind != UKBB_KIND_UNET_LSTM && h->arch.kind != UKBB_KIND_TEMPORAL_UNET) return UKBB_OK;      // no cine scratch: accepted, ignored
+    if (bytes == h->scratch_budget) return UKBB_OK;
+    h->scratch_budget = bytes;
+    return bytes ? release_scratch(h) : UKBB_OK;      // a new budget starts from empty buffers, so that what the handle holds is what the plan predicts
+}
+
+uint64_t ukbb_fcn_scratch_bytes(const ukbb_fcn_handle *h) {
+    if (!h) return 0;
+    uint64_t n = 0;
+    std::vector<DevBuf *> bufs;
+    scratch_bufs(const_cast<ukbb_fcn_handle *>(h), bufs);
+    for (DevBuf *b : bufs) n += b->n;
+    return n * sizeof(float);
+}
+
 // ---- UNet-LSTM --------------------------------------------------------------------------------------
 namespace {
 
@@ -1738,17 +1972,6 @@ int t3d_forward_seq(ukbb_fcn_handle *h, const float *image, int n_seq, int heigh
     return run_plan(h, image, n_seq * h->arch.fc, logits, prob, pred, s);
 }
 
-// Windows per chunk of forward_cine: UKBB_TEMPORAL_CHUNK_WINDOWS=n (tests force small chunks with it), else as many as fit
-// T3D_CHUNK_BYTES of activations + window probabilities (at least one)
-constexpr double T3D_CHUNK_BYTES = 4.0e9;
-
-int t3d_chunk_windows(const ukbb_fcn_handle *h, int Wn, size_t HW) {
-    if (const char *e = getenv("UKBB_TEMPORAL_CHUNK_WINDOWS")) { const int v = atoi(e); if (v >= 1) return std::min(v, Wn); }
-    size_t per_frame = HW * h->arch.n_class;
-    for (size_t i = 0; i < h->act.size(); ++i) per_frame += h->act_per_image[i];
-    const double per_window = (double)per_frame * sizeof(float) * h->arch.fc;
-    return std::max(1, std::min(Wn, (int)(T3D_CHUNK_BYTES / per_window)));
-}
 
 // The windowed deploy loop (deploy_network_ao.py:129-183) for one slice position: every window runs the whole 3-D network
 // on its T frames (gathered from the cine by the first layer through the window -> frame table); windows go in chunks, in
@@ -1762,11 +1985,24 @@ int t3d_forward_cine(ukbb_fcn_handle *h, const float *image, int F, int height, 
     if (time_step < 1) { set_err("forward_cine: time_step must be >= 1 (got %d)", time_step); return UKBB_EINVAL; }
     const int rad = (T - 1) / 2;
     if (F < rad || F < 1) { set_err("forward_cine: %d frames, the circular window of radius %d needs at least %d (the reference raises IndexError)", F, rad, rad > 1 ? rad : 1); return UKBB_EINVAL; }
-    int rc = prepare(h, T, height, width);                                 // the plan (its per-frame workspace sizes the chunks)
+    int rc = prepare(h, T, height, width, h->scratch_budget ? 0 : -1);     // the plan (its per-frame workspace sizes the chunks)
     if (rc) return rc;
     const size_t HW = (size_t)height * width;
     const int Wn = (F + time_step - 1) / time_step;
-    const int cw = t3d_chunk_windows(h, Wn, HW);
+    // Windows per chunk: as many as fit the scratch budget (without one: T3D_CHUNK_BYTES of activations + window probabilities, at least one
+    // window); UKBB_TEMPORAL_CHUNK_WINDOWS=n overrides either (tests force small chunks with it)
+    CineUnits un;
+    CinePlan pl;
+    cine_units_of(h, height, width, un);
+    if (!plan_cine(un, F, time_step, h->scratch_budget, pl)) {
+        set_err("forward_cine: the scratch budget of %llu bytes is below the %llu bytes one window of %d frames of %dx%d needs", (unsigned long long)h->scratch_budget,
+                (unsigned long long)pl.min_bytes, T, height, width);
+        return UKBB_EINVAL;
+    }
+    if (const char *e = getenv("UKBB_TEMPORAL_CHUNK_WINDOWS")) { const int v = atoi(e); if (v >= 1) pl.Wc = std::min(v, Wn); }
+    const int cw = pl.Wc;
+    rc = budget_enter(h, F, height, width, time_step, pl);
+    if (rc) return rc;
     rc = prepare(h, cw * T, height, width);
     if (rc) return rc;
     std::vector<int> map, order;
@@ -1830,6 +2066,7 @@ int ukbb_fcn_forward_seq(ukbb_fcn_handle *h, const float *image, int n_seq, int 
     if (rc) return rc;
     const int T = h->arch.fc, C = h->arch.n_class;
     if (n_seq < 1) { set_err("forward_seq: n_seq must be positive"); return UKBB_EINVAL; }
+    h->budget_key = -1;                                                      // the scratch budget bounds forward_cine only: its next call starts from empty buffers again
     rc = prepare(h, n_seq * T, height, width);
     if (rc) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1891,24 +2128,58 @@ int ukbb_fcn_forward_cine(ukbb_fcn_handle *h, const float *image, int n_frames, 
     // the reference wraps a window index once only (i < 0: i + T; i >= T: i - T, deploy_network_ao.py:151-157):
     // with fewer than rad frames the wrapped index is still out of range and numpy raises IndexError
     if (F < rad || F < 1) { set_err("forward_cine: %d frames, the circular window of radius %d needs at least %d (the reference raises IndexError)", F, rad, rad > 1 ? rad : 1); return UKBB_EINVAL; }
-    rc = prepare(h, F, height, width);
-    if (rc) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    rc = run_plan(h, image, F, nullptr, nullptr, nullptr, s);               // each frame's U-Net features, once
-    if (rc) return rc;
     const size_t HW = (size_t)height * width;
     const int Wn = (F + time_step - 1) / time_step;                         // window centres range(0, F, time_step) (:147)
+    // The plan is chosen for the whole cine (its tilings and the ConvLSTM region shape must not depend on the chunk size); under a scratch
+    // budget the workspace is sized for a chunk's frame run only.
+    rc = prepare(h, F, height, width, h->scratch_budget ? 0 : -1);
+    if (rc) return rc;
+    CineUnits un;
+    CinePlan pl;
+    cine_units_of(h, height, width, un);
+    if (!plan_cine(un, F, time_step, h->scratch_budget, pl)) {
+        set_err("forward_cine: the scratch budget of %llu bytes is below the minimum of %llu bytes for %d frames of %dx%d at time_step %d", (unsigned long long)h->scratch_budget,
+                (unsigned long long)pl.min_bytes, F, height, width, time_step);
+        return UKBB_EINVAL;
+    }
+    const int Wc = pl.Wc;
+    if (pl.chunks > 1 && h->plan_bfio && (h->lstm_bf_wino || !h->lstm_bf_hoist)) {
+        set_err("forward_cine: the A/B forms UKBB_LSTM_BF16_WINOGRAD / UKBB_LSTM_BF16_UNHOIST run unchunked only (unset them or the scratch budget)");
+        return UKBB_EINVAL;
+    }
+    rc = budget_enter(h, F, height, width, time_step, pl);
+    if (rc) return rc;
+    rc = prepare(h, F, height, width, pl.run);
+    if (rc) return rc;
     std::vector<int> map, order;
     std::vector<double> wk, wsum;
     cine_tables(F, T, time_step, weight_R, weight_r, map, order, wk, wsum);
+    // Chunk c = windows [w0, w0 + nw) reads the circular frame run starting at frame r0 = w0 * time_step - rad; its table (at map offset
+    // T * w0, step-major [k * nw + (w - w0)]) holds run-local frames.  One chunk: r0 = 0, the run is the cine and the table is `map` itself.
+    auto run_start = [&](int w0) { const int r = (w0 * time_step - rad) % F; return r < 0 ? r + F : r; };
+    if (pl.chunks > 1) {
+        std::vector<int> cmap(map.size());
+        for (int w0 = 0; w0 < Wn; w0 += Wc) {
+            const int nw = std::min(Wc, Wn - w0), r0 = run_start(w0);
+            for (int k = 0; k < T; ++k)
+                for (int w = w0; w < w0 + nw; ++w) {
+                    const int loc = map[(size_t)k * Wn + w] - r0;
+                    cmap[(size_t)T * w0 + (size_t)k * nw + (w - w0)] = loc < 0 ? loc + F : loc;
+                }
+        }
+        map.swap(cmap);
+    }
     const size_t b_map = map.size() * sizeof(int), b_ord = order.size() * sizeof(int);
     const size_t off_ord = (b_map + 7) / 8 * 8, off_wk = (off_ord + b_ord + 7) / 8 * 8, off_ws = off_wk + T * sizeof(double);
     const size_t total = off_ws + F * sizeof(double);
     long long wr_bits;
     memcpy(&wr_bits, &weight_r, sizeof wr_bits);
-    const long long key = (((((long long)F << 8) | T) * 1000003ll + time_step) * 1000003ll) ^ wr_bits ^ (1ll << 62);   // cine tables: (F, T, time_step, weight_r)
+    // cine tables: (F, T, time_step, weight_r) and the chunk plan
+    const long long key = (((((long long)F << 8) | T) * 1000003ll + time_step) * 1000003ll) ^ wr_bits ^ (1ll << 62) ^ (pl.chunks > 1 ? (long long)Wc << 40 : 0);
     if (h->lstm_aux_key != key) {                                            // first call for this shape: upload (blocking)
         HIP_TRY(hipStreamSynchronize(s), UKBB_EDEVICE);
+        h->lstm_aux_key = -1;                                                // until every table is up
         HIP_TRY(h->lstm_aux.ensure((total + 3) / 4), UKBB_ENOMEM);
         char *aux0 = reinterpret_cast<char *>(h->lstm_aux.p);
         HIP_TRY(hipMemcpy(aux0, map.data(), b_map, hipMemcpyHostToDevice), UKBB_EDEVICE);
@@ -1918,26 +2189,40 @@ int ukbb_fcn_forward_cine(ukbb_fcn_handle *h, const float *image, int n_frames, 
         h->lstm_aux_key = key;
     }
     char *aux = reinterpret_cast<char *>(h->lstm_aux.p);
-    const int *d_map = reinterpret_cast<const int *>(aux);
-    rc = run_bilstm(h, h->act[h->feat_buf]->p, F, d_map, Wn, height, width, s);
-    if (rc) return rc;
     const int NHID = h->arch.same_dim;
-    LstmTileArgs ta{};
-    ta.k_stride = (long long)Wn * HW * NHID;
-    {
-        const size_t esz = h->plan_bfio ? 2 : 4;
-        auto at = [esz](const float *p, size_t elems) { return reinterpret_cast<const float *>(reinterpret_cast<const char *>(p) + elems * esz); };
+    const size_t esz = h->plan_bfio ? 2 : 4;
+    auto at = [esz](const float *p, size_t elems) { return reinterpret_cast<const float *>(reinterpret_cast<const char *>(p) + elems * esz); };
+    if (pl.chunks > 1) HIP_TRY(h->lstm_img.ensure((size_t)pl.run * HW), UKBB_ENOMEM);
+    for (int w0 = 0; w0 < Wn; w0 += Wc) {
+        const int nw = std::min(Wc, Wn - w0);
+        const int R = pl.chunks > 1 ? (int)std::min<long long>(F, (long long)(nw - 1) * time_step + T) : F;   // frames of this chunk's run
+        const float *frames = image;
+        if (pl.chunks > 1) {                                                 // the run, contiguous: frames [r0, F) then [0, ...) when it wraps
+            const int r0 = run_start(w0), n0 = std::min(R, F - r0);
+            HIP_TRY(hipMemcpyAsync(h->lstm_img.p, image + (size_t)r0 * HW, (size_t)n0 * HW * sizeof(float), hipMemcpyDeviceToDevice, s), UKBB_EDEVICE);
+            if (R > n0) HIP_TRY(hipMemcpyAsync(h->lstm_img.p + (size_t)n0 * HW, image, (size_t)(R - n0) * HW * sizeof(float), hipMemcpyDeviceToDevice, s), UKBB_EDEVICE);
+            frames = h->lstm_img.p;
+        }
+        rc = run_plan(h, frames, R, nullptr, nullptr, nullptr, s);          // each frame's U-Net features, once per chunk that reads it
+        if (rc) return rc;
+        const int *d_map = reinterpret_cast<const int *>(aux) + (size_t)T * w0;
+        rc = run_bilstm(h, h->act[h->feat_buf]->p, R, d_map, nw, height, width, s);
+        if (rc) return rc;
+        LstmTileChunkArgs ca{};
+        LstmTileArgs &ta = ca.t;
+        ta.k_stride = (long long)nw * HW * NHID;
         ta.h_bf16 = h->plan_bfio ? 1 : 0;
         ta.hf = h->lstm_hall.p; ta.hb = at(h->lstm_hall.p, (size_t)T * ta.k_stride);
-        ta.h1f = h->lstm_h1.p; ta.h1b = at(h->lstm_h1.p, (size_t)F * HW * NHID);
+        ta.h1f = h->lstm_h1.p; ta.h1b = at(h->lstm_h1.p, (size_t)R * HW * NHID);
+        ta.map_first = d_map; ta.map_last = d_map + (size_t)(T - 1) * nw;
+        ta.w_out = dev_ptr(h, "lstm_out/w"); ta.b_out = dev_ptr(h, "lstm_out/bias");
+        ta.order = reinterpret_cast<const int *>(aux + off_ord);
+        ta.wk = reinterpret_cast<const double *>(aux + off_wk); ta.wsum = reinterpret_cast<const double *>(aux + off_ws);
+        ta.prob = prob; ta.pred = pred; ta.F = F; ta.K = T; ta.Wn = nw; ta.HW = (int)HW; ta.C = C;
+        ca.w0 = w0; ca.w1 = w0 + nw; ca.first = w0 == 0; ca.last = w0 + nw == Wn;
+        hipError_t e = pl.chunks > 1 ? launch_lstm_tile_chunk(ca, s) : launch_lstm_tile(ta, s);
+        if (e != hipSuccess) { set_err("tiling kernel launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
     }
-    ta.map_first = d_map; ta.map_last = d_map + (size_t)(T - 1) * Wn;
-    ta.w_out = dev_ptr(h, "lstm_out/w"); ta.b_out = dev_ptr(h, "lstm_out/bias");
-    ta.order = reinterpret_cast<const int *>(aux + off_ord);
-    ta.wk = reinterpret_cast<const double *>(aux + off_wk); ta.wsum = reinterpret_cast<const double *>(aux + off_ws);
-    ta.prob = prob; ta.pred = pred; ta.F = F; ta.K = T; ta.Wn = Wn; ta.HW = (int)HW; ta.C = C;
-    hipError_t e = launch_lstm_tile(ta, s);
-    if (e != hipSuccess) { set_err("tiling kernel launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
     return UKBB_OK;
 }
 

@@ -337,6 +337,14 @@ struct LstmTileArgs {       // per-(window, step) outputs + the weighted tiling 
 };
 hipError_t launch_lstm_tile(const LstmTileArgs &a, hipStream_t s);
 
+struct LstmTileChunkArgs {  // the same for the windows [w0, w1) of a cine that runs in chunks (forward_cine under a scratch budget)
+    LstmTileArgs t;         // hf / hb / map_first / map_last hold the CHUNK's windows (index w - w0, t.Wn = w1 - w0, t.k_stride = (w1 - w0) * HW * NH),
+                            // h1f / h1b the chunk's frame run (map_first / map_last give run-local frames); order / wk / wsum / prob / pred / F: the whole cine
+    int w0, w1;
+    int first, last;        // first chunk: start from 0; between chunks prob is the float32 accumulator; last chunk: prob /= weight, argmax
+};
+hipError_t launch_lstm_tile_chunk(const LstmTileChunkArgs &a, hipStream_t s);
+
 // ---- 3-D convolutions of the aortic Temporal-UNet (network_ao.py:67-114), kernels_conv3d.hip ----
 struct Conv3dPhase {        // one sub-pixel phase of a transposed conv (the whole conv: one phase at (0, 0))
     const float *wpk;       // packed A fragments (pack_conv3d_weights) of the taps this phase reads

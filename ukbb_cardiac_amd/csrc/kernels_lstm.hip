@@ -141,6 +141,62 @@ __global__ __launch_bounds__(256) void lstm_tile_kernel(const LstmTileArgs a) {
     }
 }
 
+// lstm_tile_kernel for a cine whose windows run in chunks: this launch adds the terms of the windows [w0, w1) only.  A frame's terms come in
+// ascending window order (order[]), chunks run in ascending order, and the one-pass kernel rounds its accumulator to float32 after every
+// term -- so carrying that float32 in prob between chunks performs the same sequence of float64-widened adds.  Every (frame, pixel) belongs
+// to one lane per launch (no atomics).  A frame the chunk does not reach is not touched, except by the first chunk (zero) and the last
+// (divide by wsum, argmax).
+template <int NCLS, bool BF>
+__global__ __launch_bounds__(256) void lstm_tile_chunk_kernel(const LstmTileChunkArgs ca) {
+    const LstmTileArgs &a = ca.t;
+    float w[2 * NH][NCLS], b[NCLS];
+    load_out_weights<NCLS>(a.w_out, a.b_out, w, b);
+    const long long total = (long long)a.F * a.HW;
+    for (long long id = (long long)blockIdx.x * 256 + threadIdx.x; id < total; id += (long long)gridDim.x * 256) {
+        const int f = (int)(id / a.HW);
+        const long long pix = id - (long long)f * a.HW;
+        // the frame's terms of this chunk: entries [j0, j1) of its list
+        int j0 = 0, j1;
+        for (; j0 < a.K; ++j0) {
+            const int wk_ = a.order[f * a.K + j0];
+            if (wk_ < 0 || wk_ / a.K >= ca.w0) break;
+        }
+        for (j1 = j0; j1 < a.K; ++j1) {
+            const int wk_ = a.order[f * a.K + j1];
+            if (wk_ < 0 || wk_ / a.K >= ca.w1) break;
+        }
+        if (j0 == j1 && !ca.first && !ca.last) continue;
+        float acc[NCLS];
+        float *o = a.prob + id * NCLS;
+#pragma unroll
+        for (int k = 0; k < NCLS; ++k) acc[k] = ca.first ? 0.f : o[k];
+        for (int j = j0; j < j1; ++j) {
+            const int wk_ = a.order[f * a.K + j];
+            const int wi = wk_ / a.K, k = wk_ - wi * a.K, wl = wi - ca.w0;
+            const long long mf = k == 0 ? a.map_first[wl] : wl, mb = k == a.K - 1 ? a.map_last[wl] : wl;
+            float lg[NCLS], p[NCLS], vf[NH], vb[NH];
+            load_h16<BF>(k == 0 ? a.h1f : a.hf, (k == 0 ? 0 : (long long)k * a.k_stride) + (mf * a.HW + pix) * NH, vf);
+            load_h16<BF>(k == a.K - 1 ? a.h1b : a.hb, (k == a.K - 1 ? 0 : (long long)k * a.k_stride) + (mb * a.HW + pix) * NH, vb);
+            out_conv<NCLS>(vf, vb, w, b, lg);
+            (void)softmax_argmax<NCLS>(lg, p);
+            const double wt = a.wk[k];
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c) acc[c] = (float)((double)acc[c] + (double)p[c] * wt);
+        }
+        if (ca.last) {
+            const double ws = a.wsum[f];
+            int best = 0;
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c) acc[c] = (float)((double)acc[c] / ws);
+#pragma unroll
+            for (int c = 1; c < NCLS; ++c) if (acc[c] > acc[best]) best = c;
+            if (a.pred) a.pred[id] = best;
+        }
+#pragma unroll
+        for (int c = 0; c < NCLS; ++c) o[c] = acc[c];
+    }
+}
+
 }  // namespace
 
 hipError_t launch_lstm_out(const LstmOutArgs &a, hipStream_t s) {
@@ -172,6 +228,24 @@ hipError_t launch_lstm_tile(const LstmTileArgs &a, hipStream_t s) {
         case 7: hipLaunchKernelGGL((lstm_tile_kernel<3, true>), g, t, 0, s, a); break;
         case 8: hipLaunchKernelGGL((lstm_tile_kernel<4, false>), g, t, 0, s, a); break;
         case 9: hipLaunchKernelGGL((lstm_tile_kernel<4, true>), g, t, 0, s, a); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_lstm_tile_chunk(const LstmTileChunkArgs &a, hipStream_t s) {
+    if (a.w0 < 0 || a.w1 <= a.w0 || a.t.Wn != a.w1 - a.w0) return hipErrorInvalidValue;
+    const long long total = (long long)a.t.F * a.t.HW;
+    long long blocks = (total + 255) / 256;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    const dim3 g((unsigned)blocks), t(256);
+    switch (a.t.C * 2 + (a.t.h_bf16 ? 1 : 0)) {
+        case 4: hipLaunchKernelGGL((lstm_tile_chunk_kernel<2, false>), g, t, 0, s, a); break;
+        case 5: hipLaunchKernelGGL((lstm_tile_chunk_kernel<2, true>), g, t, 0, s, a); break;
+        case 6: hipLaunchKernelGGL((lstm_tile_chunk_kernel<3, false>), g, t, 0, s, a); break;
+        case 7: hipLaunchKernelGGL((lstm_tile_chunk_kernel<3, true>), g, t, 0, s, a); break;
+        case 8: hipLaunchKernelGGL((lstm_tile_chunk_kernel<4, false>), g, t, 0, s, a); break;
+        case 9: hipLaunchKernelGGL((lstm_tile_chunk_kernel<4, true>), g, t, 0, s, a); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

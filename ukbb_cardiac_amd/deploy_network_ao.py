@@ -51,6 +51,13 @@ def define_flags():
                    'accumulation (UKBB_PREC_BF16, include/ukbb_fcn.h; --model UNet: bf16 activations in HBM too, 2.8x the fp32 rate, '
                    'Dice 0.99 against fp32; BASELINE config 5.  Default UNet-LSTM model: the same U-Net plan, ConvLSTM on the bf16 matrix '
                    'instruction with bf16 hidden maps and fp32 cell state, 2.3x the fp32 rate, Dice >= 0.98 against fp32).')
+    fs.DEFINE_float('cine_scratch_gb', 0.0, 'UNet-LSTM and Temporal-UNet: device memory (GB, 1e9 bytes) the engine may hold for the per-cine scratch of the '
+                    'windowed forward (hidden maps, gate pre-activations, cell state, network activations).  The windows of a cine then run in '
+                    'chunks that fit, with the same bits as the unchunked run; a cine of any length fits a few GB, at the price of recomputing '
+                    'the frames neighbouring chunks share.  0 (default): no budget (UNet-LSTM: the whole cine at once, 16.6 GB fp32 / 10.7 GB '
+                    'bf16 for 100 frames of 256x256; Temporal-UNet: 4 GB chunks).  Several workers per GPU (shard.py --shards_per_gpu) should set '
+                    'it to their share of the HBM.  A value below what one window needs stops at the first cine with the minimum in the message.',
+                    lower_bound=0.0)
     fs.DEFINE_enum('label_gzip', 'small', list(nifti.LABEL_GZIP_MODES), 'Deflate of the label volumes: small = run-length tokens + dynamic Huffman '
                    '(typically below the size of zlib level 1; never above it on segmentation-like volumes), fast = fixed Huffman (larger files), zlib = as nibabel.  Same inflated bytes.')
     fs.DEFINE_string('output_csv', '', 'Sequence mode: also write the spreadsheet of aortic/eval_aortic_area.py (same columns and arithmetic) from '
@@ -283,6 +290,11 @@ def main(argv=None):
             sys.exit('Error: --model %s but %s holds a %s model.' % (FLAGS.model, FLAGS.model_path, sess.engine.arch.name))
         if FLAGS.precision != 'fp32':
             sess.engine.set_precision(FLAGS.precision)
+        if FLAGS.cine_scratch_gb > 0:
+            if want is None:
+                print('--cine_scratch_gb is ignored with --model UNet (frame-wise batches hold no per-cine scratch; see --batch_slices).')
+            else:
+                sess.engine.set_scratch_budget(int(FLAGS.cine_scratch_gb * 1e9))
         print('Start evaluating on the test set ...')
 
         def forward(batch):

@@ -156,6 +156,17 @@ class Engine:
         code = {'fp32': 0, 'bf16': 1, 'f32x3': 2}[precision]
         _lib.check(_lib.lib.ukbb_fcn_set_precision(self._h, code), 'ukbb_fcn_set_precision')
 
+    def set_scratch_budget(self, nbytes: int):
+        """Bound the device memory ``run_cine`` / ``run_cine_device`` may hold for their per-cine scratch (0 = no budget, the default):
+        the windows then run in chunks, bit-identical to the unchunked call (include/ukbb_fcn.h, ukbb_fcn_set_scratch_budget)."""
+        if nbytes < 0:
+            raise ValueError('scratch budget must be >= 0 bytes, got %r' % (nbytes,))
+        _lib.check(_lib.lib.ukbb_fcn_set_scratch_budget(self._h, int(nbytes)), 'ukbb_fcn_set_scratch_budget')
+
+    def scratch_bytes(self) -> int:
+        """Bytes of device memory the handle holds right now in its activation and cine buffers (weights excluded)."""
+        return int(_lib.lib.ukbb_fcn_scratch_bytes(self._h))
+
     # -- measurement -----------------------------------------------------------
     def kernel_names(self):
         n = _lib.lib.ukbb_fcn_num_kernels(self._h)
@@ -200,6 +211,28 @@ class Engine:
         _lib.check(int(_lib.lib.ukbb_fcn_get_activation(self._h, name.encode(), _lib.f32ptr(buf), n)),
                    'ukbb_fcn_get_activation')
         return buf
+
+
+_PREC = {'fp32': 0, 'bf16': 1}
+
+
+def cine_scratch_bytes(arch: ModelArch, precision: str, n_frames: int, height: int, width: int, time_step: int = 1, budget: int = 0) -> int:
+    """Device bytes ``Engine.run_cine`` allocates for this call under ``budget`` (0 = none) on a fresh engine; 0 for a malformed
+    request or a budget below the minimum.  Host arithmetic only (ukbb_fcn_cine_scratch_bytes): the engine plans with the same function."""
+    a = _lib.arch_struct(arch)
+    return int(_lib.lib.ukbb_fcn_cine_scratch_bytes(C.byref(a), _PREC[precision], int(n_frames), int(height), int(width), int(time_step), int(budget)))
+
+
+def cine_min_scratch_bytes(arch: ModelArch, precision: str, n_frames: int, height: int, width: int, time_step: int = 1) -> int:
+    """The smallest non-zero scratch budget ``run_cine`` accepts for this call (0: malformed request)."""
+    a = _lib.arch_struct(arch)
+    return int(_lib.lib.ukbb_fcn_cine_min_scratch_bytes(C.byref(a), _PREC[precision], int(n_frames), int(height), int(width), int(time_step)))
+
+
+def cine_chunk_windows(arch: ModelArch, precision: str, n_frames: int, height: int, width: int, time_step: int = 1, budget: int = 0) -> int:
+    """Windows per chunk ``run_cine`` uses under ``budget`` (all of them when unchunked; 0: malformed or below the minimum)."""
+    a = _lib.arch_struct(arch)
+    return int(_lib.lib.ukbb_fcn_cine_chunk_windows(C.byref(a), _PREC[precision], int(n_frames), int(height), int(width), int(time_step), int(budget)))
 
 
 def load_model(model_path: str):

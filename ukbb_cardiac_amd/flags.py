@@ -19,6 +19,7 @@ class FlagError(ValueError):
 class FlagSet:
     def __init__(self):
         self._defs = {}
+        self._lower = {}           # name -> smallest accepted value (absl's lower_bound)
 
     def DEFINE_string(self, name, default, help=''):
         self._defs[name] = ('string', default, None, help)
@@ -26,8 +27,10 @@ class FlagSet:
     def DEFINE_integer(self, name, default, help=''):
         self._defs[name] = ('integer', default, None, help)
 
-    def DEFINE_float(self, name, default, help=''):
+    def DEFINE_float(self, name, default, help='', lower_bound=None):
         self._defs[name] = ('float', default, None, help)
+        if lower_bound is not None:
+            self._lower[name] = lower_bound
 
     def DEFINE_boolean(self, name, default, help=''):
         self._defs[name] = ('boolean', default, None, help)
@@ -41,7 +44,12 @@ class FlagSet:
             if kind == 'integer':
                 return int(text)
             if kind == 'float':
-                return float(text)
+                v = float(text)
+                if name in self._lower and not v >= self._lower[name]:
+                    raise FlagError('flag --%s=%s: must be >= %s' % (name, text, self._lower[name]))
+                return v
+        except FlagError:
+            raise
         except ValueError:
             raise FlagError('flag --%s=%s: not a valid %s' % (name, text, kind))
         if kind == 'boolean':

@@ -276,7 +276,10 @@ def _flag_value(argv, name):
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    usage = 'usage: python -m ukbb_cardiac_amd.shard --gpus N [--shards_per_gpu M] -- script.py [flags...]'
+    usage = ('usage: python -m ukbb_cardiac_amd.shard --gpus N [--shards_per_gpu M] -- script.py [flags...]\n'
+             '  The worker flags are passed on unchanged.  With M > 1 workers of deploy_network_ao.py on one GPU, give them\n'
+             '  --cine_scratch_gb G (their share of the HBM): without it every worker holds a whole cine\'s scratch\n'
+             '  (16.6 GB fp32 / 10.7 GB bf16 per 100 frames of 256x256); the launcher adds no such flag by itself.')
     if '--' not in argv or len(argv) < 3 or argv[0] != '--gpus':
         sys.exit(usage)
     head, rest = argv[:argv.index('--')], argv[argv.index('--') + 1:]
