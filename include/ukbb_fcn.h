@@ -401,6 +401,12 @@ double ukbb_fcn_kernel_mfma_macs_issued(const ukbb_fcn_handle *h, int i);
 int ukbb_fcn_kernel_config(const ukbb_fcn_handle *h, int i);
 const char *ukbb_fcn_conv_config_name(int id);
 
+/* Which form of the logits tail the most recent producer/consumer head launch of this process ran: 0 deferred into the next
+ * block's MFMA stream (the fp32 separable instance's default), 1 inside the block's own stage (UKBB_HEAD_INLINE_TAIL=1, and always
+ * the f32x3 and direct-gather instances), -1 before the first such launch.  For A/B tests of the knob, which is latched per
+ * process (tests/test_head_tail_gpu.py).  Added without an ABI bump: nothing that existed changed. */
+int ukbb_fcn_head_tail_form(void);
+
 /* When enabled, every launch of forward() is bracketed by hipEvents recorded
  * on the forward's own stream; ukbb_fcn_kernel_times() then synchronises and
  * returns, per kernel, the summed duration in ms and the number of timed

@@ -2270,6 +2270,8 @@ int ukbb_fcn_kernel_config(const ukbb_fcn_handle *h, int i) {
     return h->ops[i].cfg;
 }
 
+int ukbb_fcn_head_tail_form(void) { return head_tail_form(); }
+
 const char *ukbb_fcn_conv_config_name(int id) {
     for (int i = 0; i < num_conv_configs(); ++i)
         if (conv_config(i).id == id) return conv_config(i).name;

@@ -253,6 +253,7 @@ struct HeadArgs {
     int diag;                // diagnostic builds only (-DUKBB_DIAG, env UKBB_HEAD_DIAG): ablation bits of fcn_head_pc_kernel
 };
 hipError_t launch_head(const HeadArgs &a, hipStream_t s);
+int head_tail_form();      // ukbb_fcn_head_tail_form()
 void pack_sq(const float *w /*[cin][32] folded*/, int cin, float *dst /*cin*32*/);
 void pack_rowmap_32x64(const float *w /*32 rows x 64 cols*/, int ld, float *dst /*2*4*64*4*/);
 void pack_head_lg(const float *w /*[64][n_class]*/, int n_class, float *dst /*2*n_class*32*/);

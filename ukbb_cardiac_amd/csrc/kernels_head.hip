@@ -25,6 +25,7 @@
 // lanes 32-63, and the weights are packed on the host in that k order.
 #include "kernels.h"
 
+#include <atomic>
 #include <cstdio>
 
 #include <cstdlib>
@@ -494,7 +495,7 @@ __global__ __launch_bounds__(256, OCC) void fcn_head_kernel(const HeadArgs a) {
 }
 
 #ifdef UKBB_DIAG
-__device__ unsigned long long g_hstamps[8];
+__device__ unsigned long long g_hstamps[16];
 #endif
 // ---------------------------------------------------------------------------
 // Producer/consumer head (768 threads, persistent over 16x16 tiles, one workgroup per CU):
@@ -534,6 +535,12 @@ constexpr int HEADPC_X3_LDS_FLOATS = HeadLds<true>::FLOATS;
 static_assert(HEADPC_X3_LDS_FLOATS * 4 <= 160 * 1024, "head kernel LDS");
 
 __device__ __forceinline__ f32x4 lds4(const float *p) { return *reinterpret_cast<const f32x4 *>(p); }
+// An LDS pointer the optimiser cannot see through: reads at compile-time distances from it become one base register plus the
+// instruction's immediate offset, instead of one loop-invariant address register per distance (r11: 16 of them in the consumer loop)
+typedef const __attribute__((address_space(3))) float lds_cf;
+typedef const __attribute__((address_space(3))) f32x4 lds_cf4;
+__device__ __forceinline__ lds_cf *lds_opaque(const float *p) { lds_cf *q = (lds_cf *)p; asm volatile("" : "+v"(q)); return q; }
+__device__ __forceinline__ f32x4 lds4(lds_cf *p) { return *(lds_cf4 *)p; }
 
 template <int N, int I = 0, class F>
 __device__ __forceinline__ void unroll_n(F &&f) {
@@ -599,8 +606,254 @@ __host__ __device__ constexpr bool sep_row_used(int r0, int l, int k) {   // doe
     return used;
 }
 
+// ---- deferred tail (r11): behind which MFMA of the next block's same_dim0 (slots 0..7) and out0 (8..39) step k = 0..6 of finishing
+// a block's logits issues.  One step per three or four MFMAs: a step's LDS reads are used by the next one, two to four MFMAs later,
+// and step 2 falls behind same_dim0's last MFMA, whose result the wave has to wait for anyway.
+__host__ __device__ constexpr int fin_slot(int k) { return k < 3 ? 1 + 3 * k : 7 + 4 * (k - 2); }
+__host__ __device__ constexpr int fin_step_at(int m) {
+    for (int k = 0; k < 7; ++k) if (fin_slot(k) == m) return k;
+    return -1;
+}
+static_assert(fin_slot(2) == 7 && fin_slot(6) == 23, "tail steps end well inside out0's 32 MFMAs");
+
+#ifdef UKBB_DIAG
+#define UKBB_HS(var, prev) { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); var += t_ - prev; prev = t_; __builtin_amdgcn_sched_barrier(0); }
+#else
+#define UKBB_HS(var, prev)
+#endif
+
+// The consumer waves (0-3) of the fp32 separable instance of fcn_head_pc_kernel; same barriers, hand-over tile and block order as the
+// in-stage loop in the kernel (barrier X, then A_s and B_s per stage).
+template <int NCLS>
+__device__ __forceinline__ void head_consumer_deferred(const HeadArgs &a, float *lds, int nstages, int tiles_x, int tiles_y) {
+    using LM = HeadLds<false>;
+    constexpr int L_WS0 = LM::WS0, L_WO0 = LM::WO0, L_WO1 = LM::WO1, L_BS0 = LM::BS0, L_BO1 = LM::BO1, L_WLG = LM::WLG, L_BLG = LM::BLG;
+    const float *px = lds + L_PX;
+    const int lane = threadIdx.x & 63, p = lane & 31, g = lane >> 5, wave = threadIdx.x >> 6;
+    auto pixel_of = [&](int s) -> size_t {
+        int bid = blockIdx.x + (s >> 1) * gridDim.x;
+        const int tx = bid % tiles_x; bid /= tiles_x;
+        const int ty = bid % tiles_y;
+        const int n = bid / tiles_y;
+        const int blk = 4 * (s & 1) + wave;             // stage s & 1 = tile rows 8 (s & 1) .. + 7
+        const int y = ty * HT + 2 * blk + (p >> 4), x = tx * HT + (p & 15);
+        return ((size_t)n * a.H + y) * a.W + x;
+    };
+    f32x4 xv0 = {0.f, 0.f, 0.f, 0.f}, xv1 = xv0;          // conv0 features of the NEXT block, prefetched
+    size_t qnext = 0;                                   // and its pixel index: pixel_of runs once per stage
+    if (nstages > 0) {
+        qnext = pixel_of(0);
+        xv0 = ldg4(a.conv0 + qnext * 16 + 4 * g);
+        xv1 = ldg4(a.conv0 + qnext * 16 + 8 + 4 * g);
+    }
+    __syncthreads();                                    // barrier X
+#ifdef UKBB_DIAG
+    // stamps as in the kernel's in-stage loop; the segments here: same_dim0 with three steps of the previous block's tail | out0 with
+    // four steps, the store and relu16(P0) | out1 with relu16(P1) and this block's first logits half | (empty)
+    unsigned long long hs_a = 0, hs_r = 0, hs_b = 0, hs_j[4] = {0, 0, 0, 0}, hs_t0 = __builtin_amdgcn_s_memtime();
+#endif
+    // ---- deferred tail (r11) ---------------------------------------------------------------------------------------------
+    // A block's logits need out1's last MFMA, and every step after it (ReLU, a chain of dependent FMAs per class fed from LDS,
+    // the exchange between the lane halves, the compare chain, the store) waits on the one before while the SIMD's matrix pipe
+    // has nothing to issue.  So out1 runs as two dependent runs, Q0's 32 MFMAs and then Q1's: Q0's ReLU and its half of the
+    // logits FMAs issue between Q1's MFMAs, and Q1 (before its ReLU), the NCLS partial sums and the pixel index are carried
+    // over the back-edge and finished between the MFMAs of the next block's same_dim0 and out0 (fin_slot); the store fills the
+    // wait at the end of out0.  Every accumulator and every class sum adds its terms in the order of the in-stage form, so no bit moves
+    // (tests/test_head_tail_gpu.py).  sched_barrier pins each step behind its MFMA for the machine scheduler (left alone it sinks the
+    // step to its first use); Q1's MFMAs, whose result nothing reads inside the stage, are tied to their steps by an empty asm as well.
+    lds_cf *const wbase = lds_opaque(lds + L_WS0 + lane * 4);          // weight fragments: [fragment][lane] float4
+    lds_cf *const bbase = lds_opaque(lds + L_BS0 + 4 * g);             // bias tiles: register 4 j + i = bias[8 j + 4 g + i]
+    lds_cf *const lbase = lds_opaque(lds + L_WLG + g * NCLS * 32);     // logits weights of the lane's half
+    auto bias_tile_at = [&](int off) {
+        f32x16 acc;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const f32x4 b = lds4(bbase + off + 8 * j);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[4 * j + i] = b[i];
+        }
+        return acc;
+    };
+    f32x16 Qd;                                      // out1 rows 32..63 of the deferred block, before ReLU
+#pragma unroll
+    for (int r = 0; r < 16; ++r) Qd[r] = 0.f;
+    f32x2 accd[NCLS];                               // its class sums over rows 0..31
+    f32x4 wl[NCLS];                                 // logits weights in flight
+    float hsum[NCLS], hoth[NCLS], hbias[NCLS], lgd[NCLS];
+#pragma unroll
+    for (int c = 0; c < NCLS; ++c) accd[c] = f32x2{0.f, 0.f};
+    size_t qd = 0;
+    auto relu_n = [&](f32x16 &Q, auto r0c, auto nc) {
+#pragma unroll
+        for (int r = 0; r < decltype(nc)::value; ++r) Q[decltype(r0c)::value + r] = relu1(Q[decltype(r0c)::value + r]);
+    };
+    auto lg_load = [&](int j, int half) {           // weights of channels 32 half + rowmap(4 j .. 4 j + 3, g), every class
+#pragma unroll
+        for (int c = 0; c < NCLS; ++c) wl[c] = lds4(lbase + c * 32 + 16 * half + 4 * j);
+    };
+    // step k of one half (16 registers Q) of the logits product: 0, 1 ReLU (and the first weights), 2..5 the FMAs of registers
+    // 4 (k - 2) .. + 3, classes interleaved (per class the additions keep the order of the in-stage form), weights one step ahead
+    auto half_step = [&](auto kc, auto halfc, f32x16 &Q, f32x2 (&acc)[NCLS]) {
+        constexpr int k = decltype(kc)::value, half = decltype(halfc)::value;
+        if constexpr (k == 0) { lg_load(0, half); relu_n(Q, std::integral_constant<int, 0>{}, std::integral_constant<int, 8>{}); }
+        else if constexpr (k == 1) relu_n(Q, std::integral_constant<int, 8>{}, std::integral_constant<int, 8>{});
+        else if constexpr (k <= 5) {
+            constexpr int j = k - 2;
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c) acc[c] = pk_fma(f32x2{wl[c][0], wl[c][1]}, f32x2{Q[4 * j], Q[4 * j + 1]}, acc[c]);
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c) acc[c] = pk_fma(f32x2{wl[c][2], wl[c][3]}, f32x2{Q[4 * j + 2], Q[4 * j + 3]}, acc[c]);
+            if constexpr (j < 3) lg_load(j + 1, half);
+        }
+    };
+    auto fin = [&](auto kc) {                       // step k = 0..7 of finishing the deferred block: Qd's half, then the reduction
+        constexpr int k = decltype(kc)::value;
+        if constexpr (k <= 5) half_step(kc, std::integral_constant<int, 1>{}, Qd, accd);
+        else if constexpr (k == 6) {
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c) { hsum[c] = accd[c][0] + accd[c][1]; hbias[c] = lds[L_BLG + c]; }
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c) hoth[c] = __shfl_xor(hsum[c], 32);
+        } else {
+            // both halves form (lower + upper) in the SAME order -> identical bits
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c) lgd[c] = (g == 0 ? hsum[c] + hoth[c] : hoth[c] + hsum[c]) + hbias[c];
+        }
+    };
+    auto store_tail = [&](size_t qq) {
+        if (g == 0) {
+            if (a.logits) {
+#pragma unroll
+                for (int c = 0; c < NCLS; ++c) a.logits[qq * NCLS + c] = lgd[c];
+            }
+            float pr[NCLS];
+            const int best = softmax_argmax_opt<NCLS>(lgd, a.prob != nullptr, pr);
+            if (a.pred) a.pred[qq] = best;
+            if (a.prob) {
+#pragma unroll
+                for (int c = 0; c < NCLS; ++c) a.prob[qq * NCLS + c] = pr[c];
+            }
+        }
+    };
+#pragma unroll 1
+    for (int s = 0; s < nstages; ++s) {
+        const size_t q = qnext;
+        const f32x4 x0 = xv0, x1 = xv1;
+#ifdef UKBB_DIAG
+        unsigned long long hs_p = __builtin_amdgcn_s_memtime();
+#endif
+        __syncthreads();                                // barrier A_s: px[wave] ready
+        UKBB_HS(hs_a, hs_p)
+        f32x16 P0, P1;
+        {
+            const float *src = px + wave * PX_WAVE + lane * 4;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const f32x4 v0 = lds4(src + j * 256);
+                const f32x4 v1 = lds4(src + (4 + j) * 256);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { P0[4 * j + i] = v0[i]; P1[4 * j + i] = v1[i]; }
+            }
+        }
+        UKBB_HS(hs_r, hs_p)
+        __syncthreads();                                // barrier B_s: px may be overwritten
+        UKBB_HS(hs_b, hs_p)
+        if (s + 1 < nstages) {                          // features of the next block: a whole stage to arrive
+            qnext = pixel_of(s + 1);
+            xv0 = ldg4(a.conv0 + qnext * 16 + 4 * g);
+            xv1 = ldg4(a.conv0 + qnext * 16 + 8 + 4 * g);
+        }
+        // ---- same_dim0 and out0 (slots 0..39), with the seven steps of the tail of block s - 1 spread between their MFMAs
+        // (at s = 0 that tail is all zeros and is not stored) ----
+        f32x16 S = bias_tile_at(0);
+        auto at_slot = [&](auto mc, auto &&mfma) {  // the MFMA of slot m and, pinned behind it, the tail step that belongs there
+            constexpr int k = fin_step_at(decltype(mc)::value);
+            if constexpr (k >= 0) __builtin_amdgcn_sched_barrier(0);
+            mfma();
+            if constexpr (k >= 0) { fin(std::integral_constant<int, k>{}); __builtin_amdgcn_sched_barrier(0); }
+        };
+        constexpr int WO0 = L_WO0 - L_WS0, WO1 = L_WO1 - L_WS0;
+        f32x4 oa = lds4(wbase + WO0), ob = lds4(wbase + WO0 + 4 * 256);     // out0's first fragments
+        {
+            const f32x4 wv0 = lds4(wbase), wv1 = lds4(wbase + 256);
+            unroll_n<8>([&](auto mc) {
+                constexpr int m = decltype(mc)::value;
+                at_slot(mc, [&] { S = MFMA32(m < 4 ? wv0[m & 3] : wv1[m & 3], m < 4 ? x0[m & 3] : x1[m & 3], S); });
+            });
+        }
+        relu16(S);
+        UKBB_HS(hs_j[0], hs_p)
+        unroll_n<4>([&](auto qc) {
+            constexpr int q4 = decltype(qc)::value;
+            f32x4 na = oa, nb = ob;
+            if constexpr (q4 < 3) { na = lds4(wbase + WO0 + (q4 + 1) * 256); nb = lds4(wbase + WO0 + (4 + q4 + 1) * 256); }
+            unroll_n<4>([&](auto ic) {
+                constexpr int i = decltype(ic)::value, m = 8 + 8 * q4 + 2 * i;
+                at_slot(std::integral_constant<int, m>{}, [&] { P0 = MFMA32(oa[i], S[4 * q4 + i], P0); });
+                at_slot(std::integral_constant<int, m + 1>{}, [&] { P1 = MFMA32(ob[i], S[4 * q4 + i], P1); });
+            });
+            oa = na; ob = nb;
+        });
+        f32x16 Q0 = bias_tile_at(L_BO1 - L_BS0), Q1;
+        auto wf = [&](int G) {                   // out1 fragment G = 8 cb + k: rows 32 cb .. + 31 of the output, k steps 4 k .. 4 k + 3 of P0 (k < 4) / P1
+            return lds4(wbase + WO1 + (((G & 4) ? 2 * 4 * 64 : 0) + ((G >> 3) * 4 + (G & 3)) * 64) * 4);
+        };
+        f32x4 wq = wf(0);
+        fin(std::integral_constant<int, 7>{});
+        if (s > 0) store_tail(qd);              // the last step and the stores, in the wait for out0's last MFMAs
+        relu16(P0);
+        UKBB_HS(hs_j[1], hs_p)
+        // ---- out1 (slots 0..63): Q0's 32 MFMAs, then Q1's.  relu16(P1) sits behind the first MFMAs on P0; Q0's ReLU and its
+        // half of the logits behind every fourth of Q1's ----
+        f32x2 acc[NCLS];
+#pragma unroll
+        for (int c = 0; c < NCLS; ++c) acc[c] = f32x2{0.f, 0.f};
+        unroll_n<16>([&](auto Gc) {
+            constexpr int G = decltype(Gc)::value, k = G & 7;
+            f32x4 wn = wq;
+            if constexpr (G < 15) wn = wf(G + 1);
+            if constexpr (G == 6) Q1 = bias_tile_at(L_BO1 - L_BS0 + 32);
+            unroll_n<4>([&](auto ic) {
+                constexpr int i = decltype(ic)::value, slot = 4 * G + i;
+                constexpr bool relu_p1 = slot >= 1 && slot <= 4, head = slot >= 33 && slot <= 53 && (slot - 33) % 4 == 0;
+                const float xb = k < 4 ? P0[4 * (k & 3) + i] : P1[4 * (k & 3) + i];
+                if constexpr (relu_p1 || head) __builtin_amdgcn_sched_barrier(0);
+                if constexpr (G < 8) Q0 = MFMA32(wq[i], xb, Q0);
+                else Q1 = MFMA32(wq[i], xb, Q1);
+                // sched_barrier binds the machine scheduler only: before it, an MFMA whose result nothing reads until the loop's end
+                // floats below every barrier (all of Q1's run came out behind the last head step).  An empty volatile asm that
+                // "rewrites" Q1 keeps this MFMA above the step and the next one below it.
+                if constexpr (head) asm volatile("" : "+v"(Q1));
+                if constexpr (relu_p1) relu_n(P1, std::integral_constant<int, 4 * (slot - 1)>{}, std::integral_constant<int, 4>{});
+                if constexpr (head) half_step(std::integral_constant<int, (slot - 33) / 4>{}, std::integral_constant<int, 0>{}, Q0, acc);
+                if constexpr (relu_p1 || head) __builtin_amdgcn_sched_barrier(0);
+            });
+            wq = wn;
+        });
+        UKBB_HS(hs_j[2], hs_p)
+        Qd = Q1;
+#pragma unroll
+        for (int c = 0; c < NCLS; ++c) accd[c] = acc[c];
+        qd = q;
+    }
+    if (nstages > 0) {                                  // the last block's tail
+        unroll_n<8>([&](auto kc) { fin(kc); });
+        store_tail(qd);
+    }
+#ifdef UKBB_DIAG
+    if (lane == 0 && (a.diag & 64)) {
+        atomicAdd(g_hstamps + 0, hs_a); atomicAdd(g_hstamps + 1, hs_r); atomicAdd(g_hstamps + 2, hs_b);
+        atomicAdd(g_hstamps + 3, __builtin_amdgcn_s_memtime() - hs_t0); atomicAdd(g_hstamps + 4, (unsigned long long)nstages);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) atomicAdd(g_hstamps + 5 + j, hs_j[j]);
+    }
+#endif
+}
+
 // DG: the r02-r07 direct 2-D gather (UKBB_HEAD_DIRECT_GATHER=1, A/B); otherwise the separable one
-template <int NCLS, bool X3 = false, bool DG = false>
+// IT: the consumers finish a block's logits inside its own stage (r01-r08; UKBB_HEAD_INLINE_TAIL=1, A/B).  The fp32 separable instance
+// defers them instead (r11, DESIGN.md section 4 "Deferred tail"); the X3 and DG instances exist with IT = true only.
+template <int NCLS, bool X3 = false, bool DG = false, bool IT = true>
 __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     using LM = HeadLds<X3>;
@@ -860,6 +1113,8 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
         if constexpr (DG) run(I0);
         else if (__builtin_amdgcn_readfirstlane(tid) < 256) run(I0);
         else run(I1);
+    } else if constexpr (!X3 && !DG && !IT) {
+        head_consumer_deferred<NCLS>(a, lds, nstages, tiles_x, tiles_y);
     } else {
         const int wave = threadIdx.x >> 6;
         const float *w_s0 = lds + L_WS0, *w_o0 = lds + L_WO0, *w_o1 = lds + L_WO1, *w_lg = lds + L_WLG;
@@ -881,11 +1136,9 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
         __syncthreads();                                // barrier X
 #ifdef UKBB_DIAG
         // diagnostic build, UKBB_HEAD_STAMPS=1: where an MFMA wave's stage goes -- wait at barrier A (the producers' hand-off), the LDS
-        // read of the handed tile, wait at barrier B, everything else (MFMA chain + own vector work)
-        unsigned long long hs_a = 0, hs_r = 0, hs_b = 0, hs_t0 = __builtin_amdgcn_s_memtime();
-#define UKBB_HS(var, prev) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); var += t_ - prev; prev = t_; }
-#else
-#define UKBB_HS(var, prev)
+        // read of the handed tile, wait at barrier B, and the rest split at the joints of the chain (hs_j): same_dim0 with its ReLU,
+        // out0 with its ReLU, out1 with its ReLU, logits up to the store (head_consumer_deferred: what its three segments hold).
+        unsigned long long hs_a = 0, hs_r = 0, hs_b = 0, hs_j[4] = {0, 0, 0, 0}, hs_t0 = __builtin_amdgcn_s_memtime();
 #endif
 #pragma unroll 1
         for (int s = 0; s < nstages; ++s) {
@@ -925,6 +1178,7 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
                 for (int i = 0; i < 4; ++i) S = MFMA32(wv1[i], x1[i], S);
             }
             relu16(S);
+            UKBB_HS(hs_j[0], hs_p)
 #ifdef UKBB_DIAG
             if (a.diag & 2) { relu16(P0); relu16(P1); if (a.pred) a.pred[q] = (int)P0[0]; continue; }   // ablation: no out0/out1/logits
 #endif
@@ -956,6 +1210,7 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
             }
             relu16(P0);
             relu16(P1);
+            UKBB_HS(hs_j[1], hs_p)
             // ---- out1 ----
             f32x16 Q0 = bias_tile_lds(lds + L_BO1, g), Q1 = bias_tile_lds(lds + L_BO1 + 32, g);
             if constexpr (X3) {
@@ -1001,6 +1256,7 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
             }
             relu16(Q0);
             relu16(Q1);
+            UKBB_HS(hs_j[2], hs_p)
 #ifdef UKBB_DIAG
             if (a.diag & 4) { if (a.pred) a.pred[q] = (int)(Q0[0] + Q1[0]); continue; }   // ablation: no logits / softmax VALU
 #endif
@@ -1041,58 +1297,64 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
                     for (int c = 0; c < NCLS; ++c) a.prob[q * NCLS + c] = pr[c];
                 }
             }
+            UKBB_HS(hs_j[3], hs_p)
         }
 #ifdef UKBB_DIAG
         if (lane == 0 && (a.diag & 64)) {
             atomicAdd(g_hstamps + 0, hs_a); atomicAdd(g_hstamps + 1, hs_r); atomicAdd(g_hstamps + 2, hs_b);
             atomicAdd(g_hstamps + 3, __builtin_amdgcn_s_memtime() - hs_t0); atomicAdd(g_hstamps + 4, (unsigned long long)nstages);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) atomicAdd(g_hstamps + 5 + j, hs_j[j]);
         }
 #endif
     }
 }
 
+// One function per kernel instantiation, so that each owns the static that records its dynamic-LDS grant (kernels.h, allow_dynamic_lds)
+template <int NC, bool X3, bool DG, bool IT>
+static hipError_t launch_head_pc_inst(const HeadArgs &a, dim3 grid, size_t lds_bytes, hipStream_t s) {
+    static OncePerDevice lds_ok;
+    const hipError_t e = allow_dynamic_lds(lds_ok, reinterpret_cast<const void *>(fcn_head_pc_kernel<NC, X3, DG, IT>), (int)lds_bytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((fcn_head_pc_kernel<NC, X3, DG, IT>), grid, dim3(768), lds_bytes, s, a);
+    return hipGetLastError();
+}
+
+static std::atomic<int> g_head_tail_form{-1};
+int head_tail_form() { return g_head_tail_form.load(std::memory_order_relaxed); }
+
+template <int NC>
+static hipError_t launch_head_pc_nc(const HeadArgs &a, dim3 grid, hipStream_t s) {
+    static const bool x3_env = [] { const char *e = getenv("UKBB_HEAD_X3"); return e && atoi(e) != 0; }();   // A/B knob
+    static const bool dg = [] { const char *e = getenv("UKBB_HEAD_DIRECT_GATHER"); return e && atoi(e) != 0; }();   // A/B knob (r08)
+    static const bool inline_tail = [] { const char *e = getenv("UKBB_HEAD_INLINE_TAIL"); return e && atoi(e) != 0; }();   // A/B knob (r11)
+    if ((a.x3 || x3_env) && a.w_o1x3 && a.w_o0x3) {     // UKBB_PREC_F32X3; its tail stays in the stage (profiles/r11_notes.md)
+        const size_t ldsx = HEADPC_X3_LDS_FLOATS * sizeof(float);
+        g_head_tail_form.store(1, std::memory_order_relaxed);
+        return dg ? launch_head_pc_inst<NC, true, true, true>(a, grid, ldsx, s) : launch_head_pc_inst<NC, true, false, true>(a, grid, ldsx, s);
+    }
+    const size_t lds = HEADPC_LDS_FLOATS * sizeof(float);
+    bool it = inline_tail;
+#ifdef UKBB_DIAG
+    if (a.diag & 6) it = true;                          // ablation bits 2 and 4 exist in the in-stage loop only
+#endif
+    g_head_tail_form.store(dg || it ? 1 : 0, std::memory_order_relaxed);
+    if (dg) return launch_head_pc_inst<NC, false, true, true>(a, grid, lds, s);
+    return it ? launch_head_pc_inst<NC, false, false, true>(a, grid, lds, s) : launch_head_pc_inst<NC, false, false, false>(a, grid, lds, s);
+}
+
 static hipError_t launch_head_pc(const HeadArgs &a, hipStream_t s) {
     const int n_cu = device_cu_count();
     const int ntiles = a.N * (a.H / HT) * (a.W / HT);
-    dim3 grid((unsigned)(ntiles < n_cu ? ntiles : n_cu)), block(768);
-    static const bool x3_env = [] { const char *e = getenv("UKBB_HEAD_X3"); return e && atoi(e) != 0; }();   // A/B knob
-    static const bool dg = [] { const char *e = getenv("UKBB_HEAD_DIRECT_GATHER"); return e && atoi(e) != 0; }();   // A/B knob (r08)
-    if ((a.x3 || x3_env) && a.w_o1x3 && a.w_o0x3) {     // UKBB_PREC_F32X3
-        const size_t ldsx = HEADPC_X3_LDS_FLOATS * sizeof(float);
-#define UKBB_HEADX3_CASE(NC)                                                                          \
-    case NC: {                                                                                       \
-        auto k = dg ? fcn_head_pc_kernel<NC, true, true> : fcn_head_pc_kernel<NC, true, false>;      \
-        static OncePerDevice lds_ok;                                                                 \
-        {                                                                                            \
-            hipError_t e = allow_dynamic_lds(lds_ok, reinterpret_cast<const void *>(k), (int)ldsx);    \
-            if (e != hipSuccess) return e;                                                           \
-        }                                                                                            \
-        hipLaunchKernelGGL(k, grid, block, ldsx, s, a);                                              \
-        break;                                                                                       \
-    }
-        switch (a.n_class) {
-            UKBB_HEADX3_CASE(2) UKBB_HEADX3_CASE(3) UKBB_HEADX3_CASE(4) UKBB_HEADX3_CASE(5) UKBB_HEADX3_CASE(6)
-            default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    const size_t lds = HEADPC_LDS_FLOATS * sizeof(float);
-#define UKBB_HEADPC_CASE(NC)                                                                          \
-    case NC: {                                                                                       \
-        auto k = dg ? fcn_head_pc_kernel<NC, false, true> : fcn_head_pc_kernel<NC, false, false>;    \
-        static OncePerDevice lds_ok;                                                                 \
-        {                                                                                            \
-            hipError_t e = allow_dynamic_lds(lds_ok, reinterpret_cast<const void *>(k), (int)lds);    \
-            if (e != hipSuccess) return e;                                                           \
-        }                                                                                            \
-        hipLaunchKernelGGL(k, grid, block, lds, s, a);                                               \
-        break;                                                                                       \
-    }
+    dim3 grid((unsigned)(ntiles < n_cu ? ntiles : n_cu));
     switch (a.n_class) {
-        UKBB_HEADPC_CASE(2) UKBB_HEADPC_CASE(3) UKBB_HEADPC_CASE(4) UKBB_HEADPC_CASE(5) UKBB_HEADPC_CASE(6)
+        case 2: return launch_head_pc_nc<2>(a, grid, s);
+        case 3: return launch_head_pc_nc<3>(a, grid, s);
+        case 4: return launch_head_pc_nc<4>(a, grid, s);
+        case 5: return launch_head_pc_nc<5>(a, grid, s);
+        case 6: return launch_head_pc_nc<6>(a, grid, s);
         default: return hipErrorInvalidValue;
     }
-    return hipGetLastError();
 }
 
 template <int OCC>
@@ -1120,17 +1382,22 @@ hipError_t launch_head(const HeadArgs &a_in, hipStream_t s) {
 #ifdef UKBB_DIAG
     if (use_pc && getenv("UKBB_HEAD_STAMPS")) {        // the 6th stamped launch reports the MFMA waves' stage budget
         static int shots = 0;
-        unsigned long long z[8] = {0};
+        unsigned long long z[16] = {0};
         a.diag |= 64;
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_hstamps), z, 64);
+        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_hstamps), z, sizeof(z));
         const hipError_t e = launch_head_pc(a, s);
         (void)hipStreamSynchronize(s);
         if (++shots == 6) {
-            unsigned long long h[8];
-            (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_hstamps), 64);
+            unsigned long long h[16];
+            (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_hstamps), sizeof(h));
             const double st = (double)h[4];
             if (st > 0) fprintf(stderr, "[head stamps] per MFMA wave and stage (32-pixel block): wait at barrier A (hand-off) %.0f, read of the handed tile %.0f, wait at barrier B %.0f, "
                                         "MFMA chain + own vector work %.0f; total %.0f cycles\n", h[0] / st, h[1] / st, h[2] / st, (h[3] - h[0] - h[1] - h[2]) / st, h[3] / st);
+            // in-stage tail: the four joints of the chain.  Deferred tail (the default of the fp32 separable instance): the first two hold the
+            // previous block's logits and store, the third this block's first logits half, the fourth is empty
+            if (st > 0) fprintf(stderr, "[head stamps] of it: same_dim0 + ReLU %.0f, out0 + ReLU %.0f, out1 + ReLU %.0f, logits to store %.0f; outside the stamps "
+                                        "(prologue, prefetch issue, flush) %.0f\n", h[5] / st, h[6] / st, h[7] / st, h[8] / st,
+                                (h[3] - h[0] - h[1] - h[2] - h[5] - h[6] - h[7] - h[8]) / st);
         }
         return e;
     }
