@@ -1,7 +1,7 @@
 """Measure every compiled conv tiling on every conv layer of a model at a given
 batch shape (GPU box):  python tools/tune_convs.py [model] [N H W]
 Prints, per layer, the tilings sorted by measured time; the winners are baked
-into engine.cpp's preference table by hand."""
+into plan.cpp's preference table by hand."""
 import os
 import sys
 

@@ -1,10 +1,12 @@
 // Engine behind include/ukbb_fcn.h: owns device weights (BN folded, packed in
-// MFMA fragment order), the activation workspace in HBM and the launch plan.
+// MFMA fragment order) and the activation workspace in HBM; materialises the launch
+// plan the host-only planner lays out (plan.h: layout_plan) and runs it.
 //
 // Reference counterpart: the TensorFlow session + restored graph of
 // common/deploy_network.py:44-49 and the sess.run call at :110-111.
 #include "../../include/ukbb_fcn.h"
 #include "kernels.h"
+#include "plan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -86,29 +88,6 @@ struct DevBuf {
     }
 };
 
-enum OpKind { OP_FIRST, OP_CONV, OP_HEAD, OP_TCONV, OP_LOGITS, OP_SQG, OP_SQG_MULTI, OP_TAIL, OP_STEM,
-              OP_FIRST3D, OP_CONV3D, OP_TCONV3D };   // ..._3D: the Temporal-UNet's 3-D convolutions (kernels_conv3d.hip)
-
-struct Op {                    // one kernel launch of the plan
-    OpKind kind;
-    std::string name;
-    int layer = -1;            // index into host layers (OP_FIRST/OP_CONV/OP_TCONV/OP_LOGITS)
-    int cfg = -1;              // conv config id
-    int in0 = -1, in1 = -1;    // activation buffer ids (-1: network input / none)
-    int out = -1;
-    int sq[4] = {-1, -1, -1, -1};   // OP_HEAD: squeezed maps of levels 1..4
-    int mlayer[4] = {-1, -1, -1, -1}, min_[4] = {-1, -1, -1, -1}, mout[4] = {-1, -1, -1, -1}, mh[4] = {0, 0, 0, 0}, mw[4] = {0, 0, 0, 0};   // OP_SQG_MULTI: levels 1..4
-    bool fused_first = false;       // OP_CONV: conv0_0 (C_in = 1) evaluated by this kernel's producers
-    bool fused_logits = false;      // OP_CONV (bf16 storage): the 1x1 logits conv + softmax / argmax evaluated in this kernel's epilogue
-    bool on_side = false;           // launched on the handle's side stream (fork/join by events)
-    int H = 0, W = 0, Ho = 0, Wo = 0, stride = 1, pad_y = 0, pad_x = 0;
-    double macs_per_image = 0; // algorithmic
-    double mfma_macs_per_image = -1; // issued to the matrix pipe; -1 = same as algorithmic
-    double padded_macs_per_image = -1;   // ... including the slots of partly filled tiles / Winograd regions; -1 = same as mfma_macs_per_image
-    const float *wpk = nullptr, *bias = nullptr;
-    const float *wph[4] = {nullptr, nullptr, nullptr, nullptr};   // OP_TCONV3D: packed weights of the 4 sub-pixel phases
-};
-
 }  // namespace
 
 struct ukbb_fcn_handle {
@@ -137,6 +116,7 @@ struct ukbb_fcn_handle {
                                               // not flip the plan (a rebuild re-allocates the workspace) back and forth
     bool plan_bfio = false;                   // plan stores every activation between layers as bf16 (UKBB_PREC_BF16, U-Net)
     std::vector<Op> ops;
+    CineUnits cine;                           // what forward_cine holds per frame / window of this plan (plan.h)
     int last_n = 0;
 
     // UNet-LSTM (kind 2)
@@ -167,7 +147,6 @@ struct ukbb_fcn_handle {
     int debug_first_op = 0, debug_last_op = 1 << 30;   // UKBB_DEBUG_OPS="first,last" at plan build: run_plan launches only these ops
     int split_first = -1, split_last = -2;      // op range run as two half-batch chains (UKBB_SPLIT_FROM at plan build)
     std::vector<hipEvent_t> ev_fork, ev_join;
-    bool use_side = false;
 
     // timing
     bool timing = false;
@@ -202,385 +181,7 @@ int upload(ukbb_fcn_handle *h, const std::string &key, const std::vector<float> 
     return UKBB_OK;
 }
 
-// ---- architecture walk ---------------------------------------------------------
-struct Spec { std::string name; int ks, cin, cout; bool bn, bias, transposed; int kd = 1; };
-
-bool arch_specs(const ukbb_fcn_arch &a, std::vector<Spec> &out) {
-    out.clear();
-    if (a.n_level < 1 || a.n_level > UKBB_FCN_MAX_LEVEL || a.n_class < 1) return false;
-    int cin = 1;
-    char nm[64];
-    for (int l = 0; l < a.n_level; ++l) {
-        if (a.n_block[l] < 1 || a.n_filter[l] < 1) return false;
-        for (int i = 0; i < a.n_block[l]; ++i) {
-            snprintf(nm, sizeof nm, "conv%d_%d", l, i);
-            out.push_back({nm, 3, cin, a.n_filter[l], true, false, false});
-            cin = a.n_filter[l];
-        }
-    }
-    if (a.kind == UKBB_KIND_FCN) {
-        for (int l = 0; l < a.n_level; ++l) {
-            snprintf(nm, sizeof nm, "same_dim%d", l);
-            out.push_back({nm, 1, a.n_filter[l], a.same_dim, true, false, false});
-        }
-        out.push_back({"out0", 1, a.same_dim * a.n_level, a.fc, true, false, false});
-        out.push_back({"out1", 1, a.fc, a.fc, true, false, false});
-        out.push_back({"logits", 1, a.fc, a.n_class, false, true, false});
-    } else if (a.kind == UKBB_KIND_TEMPORAL_UNET) {
-        // network_ao.py:67-114: every 3x3 unit of the U-Net as a 3x3x3 conv3d (DHWIO) / conv3d_transpose ([3,3,3,Cout,Cin])
-        // [TF-recall]; conv_out a 1x1x1 conv3d with bias
-        for (auto &s : out) s.kd = 3;
-        for (int l = a.n_level - 2; l >= 0; --l) {
-            snprintf(nm, sizeof nm, "up%d_t", l);
-            out.push_back({nm, 3, a.n_filter[l + 1], a.n_filter[l], true, false, true, 3});
-            int c = 2 * a.n_filter[l];
-            for (int i = 0; i < a.n_block[l]; ++i) {
-                snprintf(nm, sizeof nm, "up%d_%d", l, i);
-                out.push_back({nm, 3, c, a.n_filter[l], true, false, false, 3});
-                c = a.n_filter[l];
-            }
-        }
-        out.push_back({"logits", 1, a.n_filter[0], a.n_class, false, true, false, 1});
-    } else if (a.kind == UKBB_KIND_UNET || a.kind == UKBB_KIND_UNET_LSTM) {
-        for (int l = a.n_level - 2; l >= 0; --l) {
-            snprintf(nm, sizeof nm, "up%d_t", l);
-            out.push_back({nm, 3, a.n_filter[l + 1], a.n_filter[l], true, false, true});
-            int c = 2 * a.n_filter[l];
-            for (int i = 0; i < a.n_block[l]; ++i) {
-                snprintf(nm, sizeof nm, "up%d_%d", l, i);
-                out.push_back({nm, 3, c, a.n_filter[l], true, false, false});
-                c = a.n_filter[l];
-            }
-        }
-        if (a.kind == UKBB_KIND_UNET) {
-            out.push_back({"logits", 1, a.n_filter[0], a.n_class, false, true, false});
-        } else {                                  // BiConv_LSTM, network_ao.py:255-319 (same_dim = hidden channels)
-            if (a.same_dim < 1 || a.fc < 1) return false;
-            out.push_back({"lstm_fw", 3, a.n_filter[0] + a.same_dim, 4 * a.same_dim, false, true, false});
-            out.push_back({"lstm_bw", 3, a.n_filter[0] + a.same_dim, 4 * a.same_dim, false, true, false});
-            out.push_back({"lstm_out", 1, 2 * a.same_dim, a.n_class, false, true, false});
-        }
-    } else {
-        return false;
-    }
-    return true;
-}
-
-size_t spec_floats(const Spec &s) {
-    size_t n = (size_t)s.kd * s.ks * s.ks * s.cin * s.cout;
-    if (s.bn) n += 4 * (size_t)s.cout;
-    if (s.bias) n += s.cout;
-    return n;
-}
-
-bool supported(const ukbb_fcn_arch &a, std::string &why) {
-    if (a.n_level != 5) { why = "n_level must be 5"; return false; }
-    if (a.n_filter[0] != 16) { why = "n_filter[0] must be 16"; return false; }
-    for (int l = 1; l < a.n_level; ++l)
-        if (a.n_filter[l] % 32) { why = "n_filter[l>0] must be multiples of 32"; return false; }
-    if (a.kind == UKBB_KIND_FCN) {
-        if (a.same_dim != 32 || a.fc != 64) { why = "FCN head kernel is built for same_dim=32, fc=64"; return false; }
-        if (a.n_class < 2 || a.n_class > 6) { why = "n_class must be in 2..6"; return false; }
-    } else {
-        if (a.n_class < 2 || a.n_class > 4) { why = "UNet n_class must be in 2..4"; return false; }
-        if (a.kind == UKBB_KIND_TEMPORAL_UNET) {
-            if (a.fc < 1 || a.fc > 31 || !(a.fc & 1)) { why = "the time window must be odd and < 32 frames"; return false; }
-        }
-        if (a.kind == UKBB_KIND_UNET_LSTM) {
-            if (a.same_dim != 16) { why = "ConvLSTM kernels are built for 16 hidden channels"; return false; }
-            if (a.fc < 1 || a.fc > 31 || !(a.fc & 1)) { why = "the time window must be odd and < 32 steps"; return false; }
-        }
-    }
-    return true;
-}
-
-// ---- conv tiling choice --------------------------------------------------------
-int override_cfg(const std::string &layer) {
-    const char *env = getenv("UKBB_CONV_CFG");     // e.g. "conv0_1:7,conv4_1:6"
-    if (!env) return -1;
-    std::string s(env);
-    size_t pos = 0;
-    while (pos < s.size()) {
-        size_t e = s.find(',', pos);
-        if (e == std::string::npos) e = s.size();
-        std::string item = s.substr(pos, e - pos);
-        size_t c = item.find(':');
-        if (c != std::string::npos && item.substr(0, c) == layer) return atoi(item.c_str() + c + 1);
-        pos = e + 1;
-    }
-    return -1;
-}
-
-// Tilings measured best on MI355X (tools/tune_convs.py, profiles/r01_tune_convs*.txt): {ks, stride, cin, cout, cfg}
-// per layer type, for large batches (tuned at N = 64, 192x208) and for small ones (tuned at N = 10, the
-// reference's own per-frame call, deploy_network.py:103-111: there the persistent kernels have fewer work
-// items than CUs, and tilings with smaller channel groups / tiles win).  Other image sizes of the same layer
-// type reuse the entry (e.g. the long-axis models at 176x208).
-struct Tuned { int ks, stride, cin, cout, cfg, alt, alt2, alt3 = -1; };   // alt.. (or -1): the first of the four whose tiles divide the map wins
-const Tuned g_tuned_large[] = {
-    {3, 1, 16, 16, 11, -1, -1}, {3, 2, 16, 32, 120, 123, -1},  {3, 1, 32, 32, 307, 301, -1},
-    {3, 2, 32, 64, 124, 123, 142, 145},  {3, 1, 64, 64, 304, 300, -1},  {3, 2, 64, 128, 124, 123, 142, 145},
-    {3, 1, 128, 128, 304, 300, -1},  {3, 2, 128, 256, 124, 123, 142, 145}, {3, 1, 256, 256, 304, 305, 300},
-};      // r03: 13x16 tiles (145) divide the 208x256 pyramid (52x64, 26x32, 13x16: conv2_0 112 -> 86 us, conv3_0 / conv4_0 -6 / -7 at N = 64);
-        // r02: the stride-2 layers moved to the producer/consumer kernel once its loads ran two stages ahead (profiles/r02_notes.md);
-        // its straight-line producer needs tiles that divide the map: 12x13 tiles for the 192x208 pyramid, 8x16 (123) for the
-        // power-of-two maps of the aortic U-Net (256x256: 148 / 143 / 133 / 136 us instead of 184 / 208 / 159 / 156 at N = 100),
-        // 11x13 (142) for the long-axis models' 176x208 pyramid (88x104, 44x52, 22x26, 11x13)
-const Tuned g_tuned_small[] = {
-    {3, 1, 16, 16, 11, -1, -1}, {3, 2, 16, 32, 29, -1, -1},  {3, 1, 32, 32, 301, -1, -1},
-    {3, 2, 32, 64, 20, -1, -1},  {3, 1, 64, 64, 300, -1, -1},  {3, 2, 64, 128, 123, -1, -1},
-    {3, 1, 128, 128, 301, -1, -1},  {3, 2, 128, 256, 26, -1, -1}, {3, 1, 256, 256, 301, -1, -1},
-};
-constexpr int SMALL_BATCH = 16;
-// The small-batch table is opt-in (UKBB_SMALL_BATCH_TILINGS=1; +30 % at N = 10): with it the tiling, and so
-// the fp32 summation order, would depend on the batch size, and by default the engine guarantees bit-identical
-// results for a slice whatever batch it is part of (tests: batch independence).
-bool small_batch_tilings() { static const bool on = getenv("UKBB_SMALL_BATCH_TILINGS") != nullptr; return on; }
-
-// A tuned tiling is reused for another image size only if its tiles still fit that size well.
-bool tile_fit_ok(const ConvConfig &c, int Ho, int Wo) {
-    const int th = c.th, tw = c.tw;
-    const double covered = (double)((Ho + th - 1) / th * th) * ((Wo + tw - 1) / tw * tw);
-    // Winograd kept its lead over the direct tilings down to 61 % region fill (12x13 maps, r01 sweep)
-    // F(2x4) regions: at 61 % fill (12 x 13 maps) the F(2x2) kernel with its half regions (81 %) is as fast, at 74 % (44 x 52, 22 x 26) F(2x4) still wins by 2 %
-    return (double)Ho * Wo >= (is_wino24(c) ? 0.7 : c.pc == 4 ? 0.5 : 0.8) * covered;
-}
-// Fallback preference (small tiles / high occupancy won everywhere in the sweep).
-const int g_pref[] = {4, 5, 18, 3, 11, 7, 31, 23, 22, 29, 27, 26};
-
-int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
-// bf16: 0 = fp32 tilings, 1 = bf16 operands / fp32 storage (pc 3), 2 = bf16 operands and storage (pc 5)
-bool cfg_valid(const ConvConfig &c, int ks, int stride, int c0, int c1, int cout, bool fused_first = false,
-               int bf16 = 0, int fuse = 0) {
-    if (c.ks != ks || c.stride != stride) return false;
-    if (c.fuse != fuse) return false;
-    if ((c.pc == 2 || c.pc == 7) != fused_first) return false;
-    if (c.pc == 7) {                                  // fused first layer + Winograd conv0_1: the 16 -> 16 stem of the fp32 FCN plans only
-        static const bool off = getenv("UKBB_NO_WINOGRAD_FIRST") != nullptr;    // A/B knob: the direct fused kernel (130-133)
-        if (off || ks != 3 || stride != 1 || c0 != 16 || c1 != 0 || cout != 16) return false;
-    }
-    if ((c.pc == 3) != (bf16 == 1) || (c.pc == 5 || c.pc == 6) != (bf16 == 2)) return false;
-    if (c.pc == 5 || c.pc == 6) cout = round_up(cout, 32);         // 16-channel layers run zero-padded on the 32-row MFMA
-    if (c.pc == 6) {                                  // weight-stationary: the Cout group's whole packed filter + the waves' rings in LDS
-        const int nch = (c0 + c1) / 16;
-        if (stride != 1 || (c0 + c1) % 16) return false;
-        if (ks == 2) {                                // transposed conv as 2x2 sub-pixel conv: cout = 4 x real channels (16, or multiples of 32)
-            const int real = cout / 4;
-            if (c1 || cout % 64 || (real != 16 && real % 32) || (real == 16 ? nch != 2 : (nch != 4 && nch != 8))) return false;
-        } else if (c.kc == 32) {                      // weights through a ring: any even number of chunks, source switch at an even chunk
-            if (ks != 3 || nch < 2 || (nch & 1) || (c1 && (c0 / 16) % 2)) return false;
-        } else if (ks != 3 || (c1 && c1 != c0) || (nch != 1 && nch != 2 && nch != 4 && nch != 8) || (c1 && nch < 2)) return false;
-        if (cout % (32 * c.cb)) return false;
-        return ws_lds_bytes_for(c, c0 + c1) <= 160 * 1024;
-    }
-    if (c.pc == 4) {                                  // Winograd: 3x3 s1, 64-channel output groups, single source ok
-        static const bool off = getenv("UKBB_NO_WINOGRAD") != nullptr;
-        if (c.id == 306) {                            // image pairs with seam regions (maps with Ho % 8 == 4): only where UKBB_CONV_CFG names it -- at N = 64 its 384
-            const char *e = getenv("UKBB_CONV_CFG");   // items leave half the CUs idle in the second round, and the plan must not depend on the batch (r04_notes.md)
-            if (!e || !strstr(e, ":306")) return false;
-        }
-        if (is_wino24(c)) {                           // F(2x4,3x3), kernels_wino24.hip: 64-channel groups, K >= 64 (the MFMA-bound layers; no frame map)
-            static const bool off24 = getenv("UKBB_NO_WINOGRAD24") != nullptr;
-            if (off24) return false;
-            if (c.wm == 2) { if (cout != 32) return false; }   // 32-channel items (307): the layers with exactly 32 output channels
-            else if (cout % 64 || c0 + c1 < 32) return false;   // K = 32: the ConvLSTM gate convs (16 + 16 -> 64)
-        }
-        return !off && !fused_first && ks == 3 && stride == 1 && cout % (16 * c.wm) == 0 && c0 % 16 == 0 && c1 % 16 == 0;
-    }
-    if ((c.pc == 2 || c.pc == 7) && cout != c.mb * c.cb * c.wm) return false;   // fused kernel stages its weights once: one Cout group
-    if (c.lds_bytes > 160 * 1024) return false;      // LDS per CU on gfx950
-    const int group = c.mb * c.cb * c.wm;
-    return !(cout % group || c0 % c.kc || c1 % c.kc);
-}
-
-// Winograd regions are 8x16 (ids 300/301) or 16x8 pixels (302/303): take the orientation with fewer regions.
-int wino_orient(int id, int Ho, int Wo) {
-    if (id < 300 || id > 303) return id;
-    const int base = 300 + (id & 1);
-    const long long r_8x16 = (long long)((Ho + 7) / 8) * ((Wo + 15) / 16), r_16x8 = (long long)((Ho + 15) / 16) * ((Wo + 7) / 8);
-    return r_16x8 < r_8x16 ? base + 2 : base;
-}
-
-int choose_cfg_raw(const std::string &layer, int ks, int stride, int c0, int c1, int cout, int Ho, int Wo, int N,
-                   bool fused_first, int want_bf16, bool wino_first);
-int find_cfg(int id, ConvConfig &out);
-
-// Small batches (N <= SMALL_BATCH, e.g. the reference's own sess.run of one frame's 10 slices, deploy_network.py:103-111): the
-// deep levels have fewer work items than the chip has CUs, and a CU streaming an item's weights alone pulls only ~25-50 GB/s
-// from L2, so those layers are bound by the number of CUs at work.  Swap the tiling for a FINER SIBLING THAT COMPUTES EVERY
-// OUTPUT WITH THE SAME ARITHMETIC -- same algorithm, MFMA shape, channels per stage and tile, only fewer output channels per
-// work item -- so results stay bit-identical whatever batch a slice is part of (tests: batch independence, slices of the
-// bench batch against single-slice runs).  The r01 small-batch table (other tiles / KC) stays opt-in for that reason.
-int finer_sibling(int id, int ks, int stride, int c0, int c1, int cout, int Ho, int Wo, int N) {
-    static const bool off = getenv("UKBB_NO_SMALL_BATCH_SIBLINGS") != nullptr;    // A/B knob
-    if (off || N > SMALL_BATCH) return id;
-    static const int sib[][2] = {{300, 301}, {302, 303},     // Winograd: 64 -> 32 output channels per item
-                                 {124, 141}};                // stride-2 producer/consumer, mb16 12x13 kc8: Cout blocks per wave 2 -> 1
-    ConvConfig c, f;
-    if (find_cfg(id, c)) return id;
-    for (const auto &p : sib) {
-        if (p[0] != id || find_cfg(p[1], f) || !cfg_valid(f, ks, stride, c0, c1, cout)) continue;
-        const long long tiles = (long long)((Ho + c.th - 1) / c.th) * ((Wo + c.tw - 1) / c.tw) * N;
-        const long long items = tiles * (cout / (c.pc == 4 ? 16 * c.wm : c.mb * c.cb * c.wm));
-        if (items <= device_cu_count() / 2) return p[1];      // at most half the CUs (of the current device) at work: halve the item (r03 on 256 CUs: 160-210 items were faster left alone)
-    }
-    return id;
-}
-
-// Winograd F(2x4,3x3) comes with 8 x 32-pixel regions (304) and 8 x 16 (305); both compute every tile with the same arithmetic (same tile
-// grid, same transforms, same K order), so the choice is a matter of filling the CUs: the region shape whose item count wastes less of
-// the last round wins, 304 on a tie (fewer, longer items: FCN level 2 60 us against 65); small batches take the finer one.
-int pick_wino24(int id, int ks, int stride, int c0, int c1, int cout, int Ho, int Wo, int N, int cus = -1) {      // cus < 0: the current device's
-    if (id != 304 && id != 305) return id;
-    if (cus < 0) cus = device_cu_count();
-    int best = id; double best_eff = -1.0;
-    for (int cand : {304, 305}) {
-        ConvConfig c;
-        if (find_cfg(cand, c) || !cfg_valid(c, ks, stride, c0, c1, cout) || !tile_fit_ok(c, Ho, Wo)) continue;
-        const long long items = (long long)N * ((Ho + c.th - 1) / c.th) * ((Wo + c.tw - 1) / c.tw) * (cout / 64);
-        const long long rounds = (items + cus - 1) / cus;
-        // makespan in units of an 8 x 16 region's work (an 8 x 32 item is two): the shorter wins -- that counts the padding columns of the
-        // wider regions as well as the idle CUs of the last round
-        double eff = 1.0 / (double)(rounds * (c.tw / 16));
-        if (N <= SMALL_BATCH) eff = cand == 305 ? 2.0 : 1.0;          // fewer items than CUs either way: more of them
-        if (eff > best_eff + 1e-12) { best_eff = eff; best = cand; }
-    }
-    return best;
-}
-
-// wino_first: the plan may run a fused first layer's conv0_1 as Winograd (tiling 134; add_conv: fp32 FCN plans only)
-int choose_cfg(const std::string &layer, int ks, int stride, int c0, int c1, int cout, int Ho, int Wo, int N,
-               bool fused_first = false, int want_bf16 = 0, bool wino_first = false) {
-    const int id = choose_cfg_raw(layer, ks, stride, c0, c1, cout, Ho, Wo, N, fused_first, want_bf16, wino_first);
-    if (override_cfg(layer) >= 0) return id;
-    return finer_sibling(wino_orient(pick_wino24(id, ks, stride, c0, c1, cout, Ho, Wo, N), Ho, Wo), ks, stride, c0, c1, cout, Ho, Wo, N);
-}
-
-// bf16-storage tilings measured best per layer type of the aortic U-Net at N = 100 x 256 x 256 (tools/sweep_convs.py with
-// PREC=bf16, profiles/r03_sweep_bf16.txt): {ks, stride, cin (both sources), cout (4 x cout for the 2x2 form of a transposed conv), cfg}.
-// Levels 2-4 sit on a 35-50 us floor per launch whatever the tiling (launch + first-load latency + tail at 100-400 tiles);
-// the table mostly avoids the bad cases (conv3_0 108 -> 47 us, up2_0 104 -> 80, conv2_0 61 -> 45).
-// r04: the weight-stationary persistent tilings (400-403, kernels_ws.hip) where a Cout group's whole filter fits LDS (K <= 1152); up3_0
-// (K = 2304) on the ring-streamed form 422 (72 vs 78 us; one barrier per chunk keeps it from the ws rate, r04_notes.md)
-const Tuned g_tuned_bfio[] = {
-    {3, 1, 16, 16, 236, 232, -1},   {3, 1, 32, 32, 401, 232, -1},   {3, 1, 64, 64, 402, 235, 232},    {3, 1, 128, 128, 400, 235, 232},
-    {3, 1, 256, 256, 239, 232, -1}, {3, 1, 256, 128, 422, 239, 232}, {3, 1, 128, 64, 400, 239, 232},  {3, 1, 64, 32, 401, 232, -1},
-    {3, 1, 32, 16, 401, 236, 232},
-    {3, 2, 16, 32, 241, -1, -1},    {3, 2, 32, 64, 242, 241, -1},   {3, 2, 64, 128, 244, 241, -1},  {3, 2, 128, 256, 244, 241, -1},
-    {2, 1, 256, 512, 253, 251, -1}, {2, 1, 128, 256, 411, 253, 251}, {2, 1, 64, 128, 411, 253, 251},  {2, 1, 32, 64, 410, 258, 253},
-};
-
-int choose_cfg_raw(const std::string &layer, int ks, int stride, int c0, int c1, int cout, int Ho, int Wo, int N,
-                   bool fused_first, int want_bf16, bool wino_first) {
-    if (want_bf16 == 2 && !fused_first && override_cfg(layer) < 0) {
-        for (const Tuned &t : g_tuned_bfio) {
-            if (t.ks != ks || t.stride != stride || t.cin != c0 + c1 || t.cout != cout) continue;
-            for (int cand : {t.cfg, t.alt, t.alt2}) {
-                ConvConfig cc;
-                if (cand >= 0 && find_cfg(cand, cc) == 0 && cfg_valid(cc, ks, stride, c0, c1, cout, false, 2) && tile_fit_ok(cc, Ho, Wo)) return cand;
-            }
-        }
-    }
-    if (want_bf16 && !fused_first) {          // bf16 tilings first; fall back to fp32 where none fits (e.g. Cout = 16 with fp32 storage)
-        const int forced_bf = override_cfg(layer);
-        double best = 1e300; int best_id = -1;
-        for (int i = 0; i < num_conv_configs(); ++i) {
-            const ConvConfig &c = conv_config(i);
-            if (!cfg_valid(c, ks, stride, c0, c1, cout, false, want_bf16)) continue;
-            if (c.id == forced_bf) return c.id;
-            const int group = c.mb * c.cb * c.wm;
-            const int coutp = want_bf16 == 2 ? round_up(cout, 32) : cout;
-            const int tiles = ((Ho + c.th - 1) / c.th) * ((Wo + c.tw - 1) / c.tw);
-            const int npb = (c.th * c.tw + c.mb - 1) / c.mb, pbw = (npb + c.wn - 1) / c.wn;
-            const double cost = (double)tiles * (coutp / group) * pbw * c.cb;
-            if (cost < best) { best = cost; best_id = c.id; }
-        }
-        if (best_id >= 0) return best_id;
-        if (want_bf16 == 2) return -1;        // bf16 storage has no fp32 fallback
-    }
-    const int forced = override_cfg(layer);
-    ConvConfig fc;
-    if (forced >= 0) {
-        for (int i = 0; i < num_conv_configs(); ++i)
-            if (conv_config(i).id == forced && cfg_valid(conv_config(i), ks, stride, c0, c1, cout, fused_first)) return forced;
-    }
-    (void)fc;
-    if (fused_first && wino_first && want_bf16 == 0) {
-        // conv0_1 as Winograd F(2x2) behind the fused first layer (kernels_conv.hip, conv_pc_kernel WINO): 64 MFMAs per consumer wave and
-        // 16 x 16 tile instead of the direct form's 144, so even at 60-70 % tile fill it issues less than any direct tiling at 100 %
-        ConvConfig cw;
-        if (find_cfg(134, cw) == 0 && cfg_valid(cw, ks, stride, c0, c1, cout, true)) return 134;
-    }
-    if (!fused_first && c1 == 0) {
-        const bool small = small_batch_tilings() && N <= SMALL_BATCH;
-        const Tuned *tab = small ? g_tuned_small : g_tuned_large;
-        const size_t ntab = small ? sizeof(g_tuned_small) / sizeof(Tuned) : sizeof(g_tuned_large) / sizeof(Tuned);
-        for (size_t j = 0; j < ntab; ++j) {
-            const Tuned &t = tab[j];
-            if (t.ks == ks && t.stride == stride && t.cin == c0 && t.cout == cout) {
-                const int cand[4] = {t.cfg, t.alt, t.alt2, t.alt3};
-                int first_ok = -1;
-                for (int k = 0; k < 4; ++k) {
-                    ConvConfig cc;
-                    if (cand[k] < 0 || find_cfg(cand[k], cc) || !cfg_valid(cc, ks, stride, c0, c1, cout) || !tile_fit_ok(cc, Ho, Wo)) continue;
-                    // F(2x4) on 32-channel layers pays only where its 8 x 32 regions fill the map (U-Net 128 x 128: 177 -> 150 us; FCN 96 x 104: 81 %
-                    // fill against 100 % of the 16 x 8 F(2x2) regions, no gain)
-                    if (cand[k] == 307 && (Ho % 8 || Wo % 32)) continue;
-                    if (Ho % cc.th == 0 && Wo % cc.tw == 0) return cand[k];      // tiles divide the map: straight-line producer applies
-                    if (first_ok < 0) first_ok = cand[k];
-                }
-                if (first_ok >= 0) return first_ok;
-            }
-        }
-    }
-    if (!fused_first && c1 > 0 && ks == 3 && stride == 1 && cout == 32) {
-        // skip-concat conv of the U-Net's level 1 (network_ao.py:51-53, 32 + 32 -> 32): the two-source Winograd kernel in its
-        // 32-channel form (r02 sweep at 256x256, N = 100: 345 us against 544 for the best direct tiling)
-        ConvConfig cw;
-        if (Ho % 8 == 0 && Wo % 32 == 0 && find_cfg(307, cw) == 0 && cfg_valid(cw, ks, stride, c0, c1, cout)) return 307;   // F(2x4): 321 -> 252 us (r04)
-        if (find_cfg(301, cw) == 0 && cfg_valid(cw, ks, stride, c0, c1, cout) && tile_fit_ok(cw, Ho, Wo)) return 301;
-    }
-    double best = 1e300;
-    int best_id = -1;
-    for (int i = 0; i < num_conv_configs(); ++i) {
-        const ConvConfig &c = conv_config(i);
-        if (c.id == 306 || c.pc == 7 || !cfg_valid(c, ks, stride, c0, c1, cout, fused_first)) continue;
-        const int group = c.mb * c.cb * c.wm;
-        const int tiles = ((Ho + c.th - 1) / c.th) * ((Wo + c.tw - 1) / c.tw);
-        const int npb = (c.th * c.tw + c.mb - 1) / c.mb;
-        const int pbw = (npb + c.wn - 1) / c.wn;
-        // matrix-pipe cycles per wave x workgroups = padded work (tile overhang + block rounding)
-        const double cyc = (double)pbw * c.cb * (ks * ks * (c0 + c1) / (c.mb == 32 ? 2 : 4)) * (c.mb == 32 ? 64 : 32);
-        double cost = (double)tiles * (cout / group) * cyc;
-        // Winograd: one stage (16 input channels of one 8x16 region, 64 output channels) costs ~5.2k cycles
-        // per CU measured; 5800 puts it on the scale of the direct estimate above (which ignores the direct
-        // kernels' ~70 % matrix-pipe efficiency), calibrated on the three tuned shapes.
-        if (c.pc == 4) cost = (double)tiles * (cout / (16 * c.wm)) * ((c0 + c1) / 16) * (is_wino24(c) ? (c.tw == 32 ? 9300.0 : 4700.0) : c.wm == 4 ? 5800.0 : 3500.0);   // F(2x4): 256 / 128 pixels per stage
-        int rank = 12;
-        for (int r = 0; r < (int)(sizeof(g_pref) / sizeof(g_pref[0])); ++r)
-            if (g_pref[r] == c.id) { rank = r % 6; break; }
-        cost *= 1.0 + 0.04 * rank;
-        if (cost < best) { best = cost; best_id = c.id; }
-    }
-    return best_id;
-}
-
-int find_cfg(int id, ConvConfig &out) {
-    for (int i = 0; i < num_conv_configs(); ++i)
-        if (conv_config(i).id == id) { out = conv_config(i); return 0; }
-    return -1;
-}
-
-// ---- plan ------------------------------------------------------------------------
-int new_act(ukbb_fcn_handle *h, const std::string &name, size_t per_image, int channels = 0) {
-    h->act.emplace_back(new DevBuf);
-    h->act_per_image.push_back(per_image);
-    h->act_name.push_back(name);
-    h->act_ch.push_back(channels);
-    return (int)h->act.size() - 1;
-}
-
+// ---- plan: materialise a PlanLayout (plan.h) on the device -------------------------------------------------------------
 int ensure_packed(ukbb_fcn_handle *h, int layer, const ConvConfig &c, const float **wpk) {
     const HostLayer &L = h->layers[layer];
     char key[128];
@@ -618,116 +219,14 @@ int ensure_packed(ukbb_fcn_handle *h, int layer, const ConvConfig &c, const floa
     return UKBB_OK;
 }
 
-// UKBB_PREC_BF16 on the aortic U-Net: bf16 operands AND bf16 activations in HBM between all layers (r03);
-// on the other graphs: bf16 operands, fp32 storage (r01).
-// r05: the U-Net of a UNet-LSTM handle takes the same bf16-storage plan (its last map, net['conv0_up'], feeds the ConvLSTM as bf16; the
-// LSTM then keeps gx and the hidden maps in bf16 as well, cell state and arithmetic fp32: run_bilstm)
-int bf16_mode(const ukbb_fcn_handle *h) { return h->precision != 1 ? 0 : h->arch.kind != UKBB_KIND_FCN ? 2 : 1; }
-
-// bf16 storage: the fused variants of the level-0 tilings (ConvConfig::fuse: 1 = first layer in the staging, 2 = logits in the
-// epilogue), first fit in measured order; -1 if none fits (the plan then keeps that layer as a launch of its own).
-int pick_fused_bf_cfg(const std::string &lname, int ks, int stride, int c0, int c1, int cout, int Ho, int Wo, int fuse_bf) {
-    const int forced = override_cfg(lname);
-    // fused logits: the persistent kernel first (kernels_bf16.hip: 104-110 vs 124 us), then the tile-per-workgroup tilings in
-    // measured order; fused first layer: tile-per-workgroup only (its persistent form was no faster, r03_notes.md)
-    for (int cand : {forced, fuse_bf == 1 ? 296 : 404, fuse_bf == 1 ? 294 : 325, fuse_bf == 1 ? 295 : 324, fuse_bf == 1 ? -1 : 298, fuse_bf == 1 ? -1 : 297, fuse_bf == 1 ? -1 : 299}) {
-        ConvConfig cc;
-        if (cand >= 0 && find_cfg(cand, cc) == 0 && cfg_valid(cc, ks, stride, c0, c1, cout, false, 2, fuse_bf) &&
-            (cand == forced || tile_fit_ok(cc, Ho, Wo))) return cand;
-    }
-    return -1;
-}
-
-int bf16_mode(int kind, int precision) { return precision != 1 ? 0 : kind != UKBB_KIND_FCN ? 2 : 1; }
-
-// Region width (32 | 16 columns) of the fused ConvLSTM gate-conv / cell kernel (kernels_wino24.hip) for a plan built for batches of N
-// on a device of `cus` compute units; 0 when the F(2x4) kernel does not apply.  Both shapes give identical bits; the choice sizes the
-// tile-padded gx / cell-state buffers, so build_plan and the host-only cine planner (cine_units) share it.
-int lstm_region_cols(const ukbb_fcn_arch &a, int H, int W, int N, int cus) {
-    int cfg = choose_cfg_raw("lstm_fw", 3, 1, a.n_filter[0], a.same_dim, 4 * a.same_dim, H, W, N, false, 0, false);
-    if (override_cfg("lstm_fw") < 0) cfg = pick_wino24(cfg, 3, 1, a.n_filter[0], a.same_dim, 4 * a.same_dim, H, W, N, cus);
-    ConvConfig c;
-    const bool have24 = cfg >= 0 && !find_cfg(cfg, c) && is_wino24(c) && c.wm == 4 && (c.tw == 32 || c.tw == 16);
-    return have24 ? c.tw : 0;
-}
-
-int add_conv(ukbb_fcn_handle *h, const std::string &lname, int in0, int in1, int c1, int H, int W, int stride,
-             int n_hint, int *out_buf, bool fused_first = false, bool fused_logits = false) {
-    const int li = h->layer_index.at(lname);
-    const HostLayer &L = h->layers[li];
-    Op op;
-    op.kind = OP_CONV; op.name = lname; op.layer = li; op.in0 = in0; op.in1 = in1;
-    op.H = H; op.W = W; op.stride = stride;
-    op.Ho = (H + stride - 1) / stride; op.Wo = (W + stride - 1) / stride;
-    // TF 'SAME' pad_before
-    op.pad_y = std::max((op.Ho - 1) * stride + L.ks - H, 0) / 2;
-    op.pad_x = std::max((op.Wo - 1) * stride + L.ks - W, 0) / 2;
-    const int c0 = L.cin - c1;
-    op.fused_first = fused_first;
-    const int fuse_bf = bf16_mode(h) != 2 ? 0 : fused_first ? 1 : fused_logits ? 2 : 0;
-    // the Winograd form of the fused first layer (134) was measured on, and is taken by, the fp32 FCN plans only (UKBB_PREC_F32X3 included:
-    // its convs are fp32); the U-Net / UNet-LSTM plans and the bf16-operand FCN plans keep the direct fused kernel (130-133)
-    const bool wino_first = fused_first && h->arch.kind == UKBB_KIND_FCN && bf16_mode(h) == 0;
-    if (fuse_bf) op.cfg = pick_fused_bf_cfg(lname, L.ks, stride, c0, c1, L.cout, op.Ho, op.Wo, fuse_bf);
-    else
-    op.cfg = choose_cfg(lname, L.ks, stride, c0, c1, L.cout, op.Ho, op.Wo, n_hint, fused_first, bf16_mode(h), wino_first);
-    op.fused_logits = fuse_bf == 2;
-    if (op.cfg < 0) { set_err("no conv tiling for layer %s (ks %d stride %d cin %d+%d cout %d)", lname.c_str(), L.ks, stride, c0, c1, L.cout); return UKBB_EARCH; }
-    ConvConfig c;
-    find_cfg(op.cfg, c);
-    int rc = ensure_packed(h, li, c, &op.wpk);
-    if (rc) return rc;
-    op.bias = ((c.pc == 5 || c.pc == 6) && L.cout % 32) ? dev_ptr(h, lname + "/bias_pad") : dev_ptr(h, lname + "/bias");
-    op.out = new_act(h, lname, (size_t)op.Ho * op.Wo * L.cout, L.cout);
-    op.macs_per_image = (double)op.Ho * op.Wo * L.ks * L.ks * L.cin * L.cout;
-    if (is_wino24(c)) {
-        op.mfma_macs_per_image = op.macs_per_image * (24.0 / 72.0);   // F(2x4,3x3): 24 products per 8 outputs
-        const double regs = (double)((op.Ho + 7) / 8) * ((op.Wo + c.tw - 1) / c.tw);      // every region issues all its tile slots (c.tw / 4 x 4)
-        op.padded_macs_per_image = regs * c.tw * 24.0 * L.cin * L.cout;
-    } else if (c.pc == 4) {
-        op.mfma_macs_per_image = op.macs_per_image * (16.0 / 36.0);   // F(2x2,3x3): 16 products per 4 outputs
-        // what the kernel ISSUES: every region runs two MFMA column blocks of 16 tile slots (one for a region whose lower half lies below
-        // the map in the 64-channel form, kernels_wino.hip `half`), whatever part of its 4 x 8 (8 x 4) tiles the map fills
-        const int trY = c.th / 2, trX = 32 / trY;        // tiles per region along y / x
-        const int regs_y = (op.Ho + 2 * trY - 1) / (2 * trY), regs_x = (op.Wo + 2 * trX - 1) / (2 * trX);
-        double slots = 0;
-        for (int ry = 0; ry < regs_y; ++ry) slots += (double)regs_x * ((c.wm == 4 && ry * 2 * trY + trY >= op.Ho) ? 16 : 32);
-        op.padded_macs_per_image = slots * 16.0 * L.cin * L.cout;
-    } else if (c.pc == 7) {
-        // what the kernel issues: conv0_1 as F(2x2) (16 products per 4 outputs) + conv0_0 on the producers' MFMAs (K = 9 taps of 12
-        // issued: three 16x16x4 per 16 halo pixels of every 18 x 18 halo tile)
-        const double tiles = (double)((op.Ho + c.th - 1) / c.th) * ((op.Wo + c.tw - 1) / c.tw);
-        const double halo_blocks = (double)(((c.th + 2) * (c.tw + 2) + 15) / 16);
-        const double first_macs = (double)op.Ho * op.Wo * 9 * L.cin;   // conv0_0: 1 -> L.cin channels
-        op.mfma_macs_per_image = op.macs_per_image * (16.0 / 36.0) + first_macs;
-        op.padded_macs_per_image = tiles * ((c.th / 2) * (c.tw / 2) * 16.0 * L.cin * L.cout + halo_blocks * 16 * 12 * L.cin);
-    } else if (c.pc <= 2) {                            // direct tilings: tiles x pixel blocks of the MFMA's N width
-        const int npb = (c.th * c.tw + c.mb - 1) / c.mb;
-        const double tiles = (double)((op.Ho + c.th - 1) / c.th) * ((op.Wo + c.tw - 1) / c.tw);
-        op.padded_macs_per_image = tiles * npb * c.mb * L.ks * L.ks * (double)L.cin * L.cout;
-    }
-    else if (fused_first) op.mfma_macs_per_image = op.macs_per_image;              // conv0_0 itself runs on the vector ALU
-    h->ops.push_back(op);
-    *out_buf = op.out;
-    return UKBB_OK;
-}
-
-// conv2d_transpose 3x3 s2 + BN + ReLU as a 2x2 sub-pixel conv (kernels.h, tconv_as_conv2x2)
-int add_tconv(ukbb_fcn_handle *h, const std::string &lname, int in0, int H, int W, int n_hint, int *out_buf) {
-    const int li = h->layer_index.at(lname);
-    const HostLayer &L = h->layers[li];
-    Op op;
-    op.kind = OP_TCONV; op.name = lname; op.layer = li; op.in0 = in0;
-    op.H = H; op.W = W; op.Ho = H; op.Wo = W; op.stride = 1; op.pad_y = 1; op.pad_x = 1;
-    op.cfg = choose_cfg(lname, 2, 1, L.cin, 0, 4 * L.cout, H, W, n_hint, false, bf16_mode(h));
-    if (op.cfg < 0) { set_err("no tiling for transposed conv %s", lname.c_str()); return UKBB_EARCH; }
-    ConvConfig c;
-    find_cfg(op.cfg, c);
+// conv2d_transpose 3x3 s2 + BN + ReLU as a 2x2 sub-pixel conv (kernels.h, tconv_as_conv2x2): packed weights and the bias of the 4 phases
+int ensure_packed_tconv(ukbb_fcn_handle *h, int layer, const ConvConfig &c, const float **wpk, const float **bias) {
+    const HostLayer &L = h->layers[layer];
     char key[128];
     const bool bfpk = c.pc == 3 || c.pc == 5 || c.pc == 6;
     const bool paired = c.pc == 6;                    // weight-stationary tilings: virtual channels in the paired block order (wst_pack_order)
     snprintf(key, sizeof key, "%s/pk2x2%s%s_mb%d_kc%d_g%d", L.name.c_str(), bfpk ? "bf16" : "", paired ? "ws" : "", c.mb, c.kc, c.wm * c.cb);
-    const std::string bkey = lname + (paired ? "/bias4ws" : "/bias4");
+    const std::string bkey = L.name + (paired ? "/bias4ws" : "/bias4");
     if (!dev_ptr(h, key)) {
         const int vc = 4 * L.cout;
         std::vector<float> w2((size_t)4 * L.cin * vc), pk(w2.size());
@@ -750,16 +249,12 @@ int add_tconv(ukbb_fcn_handle *h, const std::string &lname, int in0, int H, int 
         rc = upload(h, bkey, b4);
         if (rc) return rc;
     }
-    op.wpk = dev_ptr(h, key);
-    op.bias = dev_ptr(h, bkey);
-    op.out = new_act(h, lname, (size_t)4 * H * W * L.cout, L.cout);
-    op.macs_per_image = (double)H * W * 9 * L.cin * L.cout;
-    h->ops.push_back(op);
-    *out_buf = op.out;
+    *wpk = dev_ptr(h, key);
+    *bias = dev_ptr(h, bkey);
     return UKBB_OK;
 }
 
-// ---- Temporal-UNet (kind 3): network_ao.py:67-114 on kernels_conv3d.hip -------------------------------------------
+// Temporal-UNet (kind 3), kernels_conv3d.hip:
 // Weights of conv3d (kernel order (kt, ky, kx)) or of one sub-pixel phase (py, px) of conv3d_transpose (kt reversed: the
 // transposed conv reads in[t + 1 - kt], kernels_conv3d.hip), packed for conv3d_kernel; key "<layer>/pk3d<phase>".
 const float *ensure_packed3d(ukbb_fcn_handle *h, const HostLayer &L, int py, int px, int ny, int nx) {
@@ -781,89 +276,129 @@ const float *ensure_packed3d(ukbb_fcn_handle *h, const HostLayer &L, int py, int
     return dev_ptr(h, key);
 }
 
-int add_conv3d(ukbb_fcn_handle *h, const std::string &lname, int in0, int in1, int H, int W, int stride, int *out_buf) {
-    const int li = h->layer_index.at(lname);
-    const HostLayer &L = h->layers[li];
-    Op op;
-    op.kind = L.cin == 1 ? OP_FIRST3D : OP_CONV3D; op.name = lname; op.layer = li; op.in0 = in0; op.in1 = in1;
-    op.H = H; op.W = W; op.stride = stride;
-    op.Ho = (H + stride - 1) / stride; op.Wo = (W + stride - 1) / stride;
-    op.pad_y = std::max((op.Ho - 1) * stride + 3 - H, 0) / 2;          // TF 'SAME' pad_before
-    op.pad_x = std::max((op.Wo - 1) * stride + 3 - W, 0) / 2;
-    if (op.kind == OP_FIRST3D && (stride != 1 || L.cout != 16)) { set_err("%s: the first 3-D layer must be 1 -> 16 channels, stride 1", lname.c_str()); return UKBB_EARCH; }
-    if (op.kind == OP_CONV3D && !(op.wpk = ensure_packed3d(h, L, 0, 0, 3, 3))) return UKBB_EDEVICE;
-    op.bias = dev_ptr(h, lname + "/bias");
-    op.out = new_act(h, lname, (size_t)op.Ho * op.Wo * L.cout, L.cout);
-    op.macs_per_image = (double)op.Ho * op.Wo * 27 * L.cin * L.cout;
-    // issued: the window's first and last frame skip one time tap (3T - 2 of 3T); the first layer runs on the vector ALU
-    const double tfrac = (3.0 * h->arch.fc - 2) / (3.0 * h->arch.fc);
-    op.mfma_macs_per_image = op.kind == OP_FIRST3D ? 0.0 : op.macs_per_image * tfrac;
-    if (op.kind == OP_CONV3D)                                          // ... in 32-pixel tiles x 32-row channel blocks
-        op.padded_macs_per_image = (double)((op.Ho * op.Wo + 31) / 32) * 32 * 27 * L.cin * round_up(L.cout, 32) * tfrac;
-    h->ops.push_back(op);
-    *out_buf = op.out;
-    return UKBB_OK;
+// bf16 storage: the 1 -> 16 -> 16 stem as one launch (kernels_stem.hip)
+int ensure_packed_stem(ukbb_fcn_handle *h) {
+    if (dev_ptr(h, "stem/wA0")) return UKBB_OK;
+    const HostLayer &L0 = h->layers[h->layer_index.at("conv0_0")], &L1 = h->layers[h->layer_index.at("conv0_1")];
+    std::vector<float> p0((size_t)64 * 4), dummy((size_t)9 * 64 * 4), p1((size_t)5 * 64 * 4), w0z((size_t)9 * 32 * 16, 0.f);
+    pack_stem_weights(L0.w.data(), p0.data());
+    pack_tail_weights(w0z.data(), L1.w.data(), dummy.data(), p1.data());
+    int rc = upload(h, "stem/wA0", p0);
+    if (rc) return rc;
+    return upload(h, "stem/wA1", p1);
 }
 
-int add_tconv3d(ukbb_fcn_handle *h, const std::string &lname, int in0, int H, int W, int *out_buf) {
-    const int li = h->layer_index.at(lname);
-    const HostLayer &L = h->layers[li];
-    Op op;
-    op.kind = OP_TCONV3D; op.name = lname; op.layer = li; op.in0 = in0;
-    op.H = H; op.W = W; op.Ho = 2 * H; op.Wo = 2 * W; op.stride = 1;
-    for (int ph = 0; ph < 4; ++ph) {
-        const int py = ph >> 1, px = ph & 1;
-        if (!(op.wph[ph] = ensure_packed3d(h, L, py, px, py ? 1 : 2, px ? 1 : 2))) return UKBB_EDEVICE;
-    }
-    op.bias = dev_ptr(h, lname + "/bias");
-    op.out = new_act(h, lname, (size_t)op.Ho * op.Wo * L.cout, L.cout);
-    op.macs_per_image = (double)H * W * 27 * L.cin * L.cout;           // 27 taps per INPUT pixel
-    const double tfrac = (3.0 * h->arch.fc - 2) / (3.0 * h->arch.fc);  // window-edge frames skip one time tap
-    op.mfma_macs_per_image = op.macs_per_image * tfrac;
-    op.padded_macs_per_image = (double)((H * W + 31) / 32) * 32 * 27 * L.cin * round_up(L.cout, 32) * tfrac;
-    h->ops.push_back(op);
-    *out_buf = op.out;
-    return UKBB_OK;
+// bf16 storage: up0_0, up0_1 and the logits as one launch (kernels_tail.hip)
+int ensure_packed_tail(ukbb_fcn_handle *h) {
+    if (dev_ptr(h, "tail/wA0")) return UKBB_OK;
+    const HostLayer &L0 = h->layers[h->layer_index.at("up0_0")], &L1 = h->layers[h->layer_index.at("up0_1")];
+    std::vector<float> p0((size_t)9 * 64 * 4), p1((size_t)5 * 64 * 4);
+    pack_tail_weights(L0.w.data(), L1.w.data(), p0.data(), p1.data());
+    int rc = upload(h, "tail/wA0", p0);
+    if (rc) return rc;
+    return upload(h, "tail/wA1", p1);
 }
 
-// the Temporal-UNet plan: encoder, decoder (transposed conv, concat([skip, up]), convs), conv_out + softmax / argmax (network_ao.py:67-114)
-int build_plan_t3d(ukbb_fcn_handle *h, int H, int W, int n_hint) {
+// ConvLSTM packed filters: the x rows of both directions as ONE 128-channel conv (groups = directions), the h rows per direction
+int ensure_packed_lstm(ukbb_fcn_handle *h) {
+    if (dev_ptr(h, "lstm/wx")) return UKBB_OK;
     const ukbb_fcn_arch &a = h->arch;
-    char nm[64];
-    int cur = -1, hh = H, ww = W;
-    std::vector<int> level_out(a.n_level), lh(a.n_level), lw(a.n_level);
-    for (int l = 0; l < a.n_level; ++l) {
-        for (int i = 0; i < a.n_block[l]; ++i) {
-            snprintf(nm, sizeof nm, "conv%d_%d", l, i);
-            const int stride = (l > 0 && i == 0) ? 2 : 1;
-            int rc = add_conv3d(h, nm, cur, -1, hh, ww, stride, &cur);
-            if (rc) return rc;
-            hh = (hh + stride - 1) / stride; ww = (ww + stride - 1) / stride;
-        }
-        level_out[l] = cur; lh[l] = hh; lw[l] = ww;
-    }
-    for (int l = a.n_level - 2; l >= 0; --l) {
-        snprintf(nm, sizeof nm, "up%d_t", l);
-        int up = -1;
-        int rc = add_tconv3d(h, nm, cur, lh[l + 1], lw[l + 1], &up);
+    const size_t per = (size_t)24 * 16 * 64;
+    std::vector<float> wx(2 * per), bx(2 * 64), wh(per);
+    int d = 0;
+    for (const char *nm2 : {"lstm_fw", "lstm_bw"}) {
+        const HostLayer &L = h->layers[h->layer_index.at(nm2)];
+        if (L.cin != 32 || L.cout != 64 || L.ks != 3) { set_err("ConvLSTM gate kernel must be 3x3x(16+16)x64"); return UKBB_EARCH; }
+        pack_lstm_gate_weights(L.w.data(), L.cin, 0, L.b.data(), wx.data() + d * per, bx.data() + d * 64);
+        pack_lstm_gate_weights(L.w.data(), L.cin, a.n_filter[0], nullptr, wh.data(), nullptr);
+        int rc = upload(h, std::string(nm2) + "/wh", wh);
         if (rc) return rc;
-        cur = up;
-        for (int i = 0; i < a.n_block[l]; ++i) {
-            snprintf(nm, sizeof nm, "up%d_%d", l, i);
-            rc = i == 0 ? add_conv3d(h, nm, level_out[l], up, lh[l], lw[l], 1, &cur)    // concat([skip, up]) (network_ao.py:51 order)
-                        : add_conv3d(h, nm, cur, -1, lh[l], lw[l], 1, &cur);
-            if (rc) return rc;
-        }
+        ++d;
     }
-    Op lg;
-    lg.kind = OP_LOGITS; lg.name = "logits"; lg.layer = h->layer_index.at("logits"); lg.in0 = cur; lg.H = H; lg.W = W;
-    lg.macs_per_image = (double)H * W * a.n_filter[0] * a.n_class;
-    lg.mfma_macs_per_image = 0.0;
-    h->ops.push_back(lg);
-    h->plan_h = H; h->plan_w = W; h->plan_small = n_hint <= SMALL_BATCH; h->plan_n = n_hint;
-    h->plan_bfio = false;
-    h->split_first = -1; h->split_last = -2;
-    h->debug_first_op = 0; h->debug_last_op = 1 << 30;
+    int rc = upload(h, "lstm/wx", wx);
+    if (rc) return rc;
+    rc = upload(h, "lstm/bx", bx);
+    if (rc) return rc;
+    // bf16 form (kernels_ws.hip, ws_main LS): direct 3x3 conv on the bf16 matrix instruction, its own channel order
+    const size_t perb = (size_t)9 * 16 * 64 / 2;          // dwords
+    std::vector<float> wxb(2 * perb), bxb(2 * 64), whb(perb);
+    d = 0;
+    for (const char *nm2 : {"lstm_fw", "lstm_bw"}) {
+        const HostLayer &L = h->layers[h->layer_index.at(nm2)];
+        pack_lstm_gate_weights_bf16(L.w.data(), L.cin, 0, L.b.data(), wxb.data() + d * perb, bxb.data() + d * 64);
+        pack_lstm_gate_weights_bf16(L.w.data(), L.cin, a.n_filter[0], nullptr, whb.data(), nullptr);
+        rc = upload(h, std::string(nm2) + "/wh_bf16", whb);
+        if (rc) return rc;
+        std::vector<float> wxhb(2 * perb);               // r06: both halves as one two-chunk filter (un-hoisted time steps, ls_mode 3)
+        pack_lstm_gate_weights_bf16_xh(L.w.data(), nullptr, wxhb.data(), nullptr);
+        rc = upload(h, std::string(nm2) + "/wxh_bf16", wxhb);
+        if (rc) return rc;
+        ++d;
+    }
+    rc = upload(h, "lstm/wx_bf16", wxb);
+    if (rc) return rc;
+    return upload(h, "lstm/bx_bf16", bxb);
+}
+
+// Takes the layout's ops and activation maps into the handle: packs and uploads what each op's kind and tiling need, resolves the
+// ops' device pointers, and resets the run-time state (events, timing sums) of the previous plan.
+int materialize_plan(ukbb_fcn_handle *h, PlanLayout &L) {
+    h->ops.clear();
+    h->act.clear(); h->act_per_image.clear(); h->act_name.clear(); h->act_ch.clear();
+    h->cap_n = 0;
+    for (const ActSpec &s : L.acts) {
+        h->act.emplace_back(new DevBuf);
+        h->act_per_image.push_back(s.per_image);
+        h->act_name.push_back(s.name);
+        h->act_ch.push_back(s.channels);
+    }
+    for (Op &op : L.ops) {
+        int rc = UKBB_OK;
+        ConvConfig c;
+        const std::string lname = op.layer >= 0 ? h->layers[op.layer].name : std::string();
+        switch (op.kind) {
+            case OP_CONV:
+                find_cfg(op.cfg, c);
+                rc = ensure_packed(h, op.layer, c, &op.wpk);
+                op.bias = ((c.pc == 5 || c.pc == 6) && h->layers[op.layer].cout % 32) ? dev_ptr(h, lname + "/bias_pad") : dev_ptr(h, lname + "/bias");
+                break;
+            case OP_TCONV:
+                find_cfg(op.cfg, c);
+                rc = ensure_packed_tconv(h, op.layer, c, &op.wpk, &op.bias);
+                break;
+            case OP_STEM: rc = ensure_packed_stem(h); break;
+            case OP_TAIL: rc = ensure_packed_tail(h); break;
+            case OP_CONV3D:
+                if (!(op.wpk = ensure_packed3d(h, h->layers[op.layer], 0, 0, 3, 3))) rc = UKBB_EDEVICE;
+                op.bias = dev_ptr(h, lname + "/bias");
+                break;
+            case OP_TCONV3D:
+                for (int ph = 0; ph < 4 && !rc; ++ph) {
+                    const int py = ph >> 1, px = ph & 1;
+                    if (!(op.wph[ph] = ensure_packed3d(h, h->layers[op.layer], py, px, py ? 1 : 2, px ? 1 : 2))) rc = UKBB_EDEVICE;
+                }
+                op.bias = dev_ptr(h, lname + "/bias");
+                break;
+            case OP_FIRST3D: op.bias = dev_ptr(h, lname + "/bias"); break;
+            default: break;                            // OP_FIRST / OP_SQG* / OP_HEAD / OP_LOGITS: what ukbb_fcn_create uploaded
+        }
+        if (rc) return rc;
+    }
+    if (L.needs_lstm) {
+        const HostLayer &B = h->layers[h->layer_index.at("lstm_bw")];
+        bool z = getenv("UKBB_LSTM_RUN_ZERO_CELL") == nullptr;      // knob: run the zero cell anyway (tests compare both ways)
+        for (size_t i = 0; z && i < B.w.size(); ++i) z = B.w[i] == 0.f;
+        for (size_t i = 0; z && i < B.b.size(); ++i) z = B.b[i] == 0.f;
+        h->lstm_bw_zero = z;
+        int rc = ensure_packed_lstm(h);
+        if (rc) return rc;
+        h->lstm_bf_wino = L.lstm_bf_wino; h->lstm_bf_hoist = L.lstm_bf_hoist; h->lstm_tile_cols = L.lstm_tile_cols;
+    }
+    h->ops = std::move(L.ops);
+    h->feat_buf = L.feat_buf;
+    h->plan_bfio = L.bfio;
+    h->split_first = L.split_first; h->split_last = L.split_last;
+    h->debug_first_op = L.debug_first_op; h->debug_last_op = L.debug_last_op;
     for (auto e : h->ev) (void)hipEventDestroy(e);
     h->ev.clear();
     h->t_sum.assign(h->ops.size(), 0.0);
@@ -873,276 +408,13 @@ int build_plan_t3d(ukbb_fcn_handle *h, int H, int W, int n_hint) {
 }
 
 int build_plan(ukbb_fcn_handle *h, int H, int W, int n_hint) {
-    h->ops.clear();
-    h->act.clear(); h->act_per_image.clear(); h->act_name.clear(); h->act_ch.clear();
-    h->cap_n = 0;
-    if (h->arch.kind == UKBB_KIND_TEMPORAL_UNET) return build_plan_t3d(h, H, W, n_hint);
-    const ukbb_fcn_arch &a = h->arch;
-    char nm[64];
-    // encoder (network.py:179-189 / network_ao.py:31-41)
-    int cur = -1, ch = 1, cw = 1;
-    std::vector<int> level_out(a.n_level), lh(a.n_level), lw(a.n_level), sqg_out(a.n_level, -1);
-    Op multi;
-    multi.kind = OP_FIRST;                         // becomes OP_SQG_MULTI when the first merged level arrives
-    int hh = H, ww = W;
-    for (int l = 0; l < a.n_level; ++l) {
-        for (int i = 0; i < a.n_block[l]; ++i) {
-            snprintf(nm, sizeof nm, "conv%d_%d", l, i);
-            const int stride = (l > 0 && i == 0) ? 2 : 1;
-            static const bool no_fuse = getenv("UKBB_NO_FUSE_FIRST") != nullptr;    // A/B knob
-            // bf16 storage: only if a fused tiling fits conv0_1 at this size (otherwise conv0_0 runs as its own launch, bf16 out)
-            const bool can_fuse = !no_fuse && a.n_block[0] >= 2 && a.n_filter[0] == 16 &&
-                                  (bf16_mode(h) != 2 || pick_fused_bf_cfg("conv0_1", 3, 1, 16, 0, 16, H, W, 1) >= 0);
-            // bf16 storage with the standard 1 -> 16 -> 16 stem: conv0_0 and conv0_1 as ONE launch of kernels_stem.hip
-            // (UKBB_NO_FUSE_STEM=1: the r03 form, conv0_0 evaluated in conv0_1's staging)
-            const bool stem = a.kind != UKBB_KIND_FCN && bf16_mode(h) == 2 && getenv("UKBB_NO_FUSE_STEM") == nullptr && a.n_block[0] >= 2 &&
-                              a.n_filter[0] == 16 && override_cfg("conv0_1") < 0;
-            if (l == 0 && i == 0 && stem) continue;
-            if (l == 0 && i == 1 && stem) {
-                const int l0 = h->layer_index.at("conv0_0"), l1 = h->layer_index.at("conv0_1");
-                const HostLayer &L0 = h->layers[l0], &L1 = h->layers[l1];
-                if (!dev_ptr(h, "stem/wA0")) {
-                    std::vector<float> p0((size_t)64 * 4), dummy((size_t)9 * 64 * 4), p1((size_t)5 * 64 * 4), w0z((size_t)9 * 32 * 16, 0.f);
-                    pack_stem_weights(L0.w.data(), p0.data());
-                    pack_tail_weights(w0z.data(), L1.w.data(), dummy.data(), p1.data());
-                    int rc = upload(h, "stem/wA0", p0);
-                    if (rc) return rc;
-                    rc = upload(h, "stem/wA1", p1);
-                    if (rc) return rc;
-                }
-                Op op; op.kind = OP_STEM; op.name = "conv0_0+conv0_1"; op.layer = l1;
-                op.H = op.Ho = H; op.W = op.Wo = W;
-                op.out = new_act(h, "conv0_1", (size_t)H * W * L1.cout, L1.cout);
-                op.macs_per_image = (double)H * W * 9 * (L0.cin * L0.cout + L1.cin * L1.cout);
-                h->ops.push_back(op);
-                cur = op.out;
-                continue;
-            }
-            if (l == 0 && i == 0) {
-                if (can_fuse) continue;              // evaluated inside conv0_1's producers
-                Op op; op.kind = OP_FIRST; op.name = nm; op.layer = h->layer_index.at(nm);
-                op.H = op.Ho = H; op.W = op.Wo = W;
-                op.out = new_act(h, nm, (size_t)H * W * a.n_filter[0], a.n_filter[0]);
-                op.macs_per_image = (double)H * W * 9 * a.n_filter[0];
-                op.mfma_macs_per_image = 0;          // vector ALU kernel
-                h->ops.push_back(op);
-                cur = op.out;
-            } else {
-                int out;
-                const bool fused = (l == 0 && i == 1 && can_fuse);
-                int rc = add_conv(h, nm, cur, -1, 0, hh, ww, stride, n_hint, &out, fused);
-                if (rc) return rc;
-                if (fused) {
-                    h->ops.back().name = "conv0_0+conv0_1";
-                    h->ops.back().macs_per_image += (double)H * W * 9 * a.n_filter[0];
-                }
-                cur = out;
-                if (stride == 2) { hh = (hh + 1) / 2; ww = (ww + 1) / 2; }
-            }
-        }
-        level_out[l] = cur; lh[l] = hh; lw[l] = ww;
-        h->act_name[cur] = std::string("conv") + std::to_string(l);
-        if (a.kind == UKBB_KIND_FCN && l >= 1) {
-            // same_dim_l + out0's level-l slice at low resolution (same_dim0 lives inside the head kernel).
-            // Emitted right after its level and run on the side stream: it only feeds the head, is
-            // memory-bound, and overlaps with the MFMA-bound convs of the deeper levels.
-            snprintf(nm, sizeof nm, "same_dim%d", l);
-            Op op; op.kind = OP_SQG; op.name = std::string("sqg") + std::to_string(l);
-            op.layer = h->layer_index.at(nm); op.in0 = level_out[l];
-            op.H = op.Ho = lh[l]; op.W = op.Wo = lw[l]; op.stride = l;
-            op.on_side = h->use_side;
-            op.out = new_act(h, std::string("g") + std::to_string(l), (size_t)lh[l] * lw[l] * a.fc);
-            // algorithmic MACs: the squeeze; the 32->64 projection is out0's work moved to low
-            // resolution and is accounted to the head (so the per-layer sums equal Appendix A)
-            op.macs_per_image = (double)lh[l] * lw[l] * a.n_filter[l] * a.same_dim;
-            op.mfma_macs_per_image = (double)lh[l] * lw[l] * (a.n_filter[l] * a.same_dim + a.same_dim * a.fc);
-            sqg_out[l] = op.out;
-            // levels 1-4 of the standard filter pyramid go out as ONE launch after level 4 (sqg_multi_kernel)
-            static const bool split1 = getenv("UKBB_SQG1_SEPARATE") != nullptr;    // A/B knob: level 1 as a launch of its own
-            const bool merge = !h->use_side && a.n_level == 5 && a.n_filter[1] == 32 && a.n_filter[2] == 64 && a.n_filter[3] == 128 && a.n_filter[4] == 256;
-            if (merge && l >= 1 && !(split1 && l == 1)) {
-                if (multi.kind != OP_SQG_MULTI) { multi = Op(); multi.kind = OP_SQG_MULTI; multi.name = split1 ? "sqg2-4" : "sqg1-4"; multi.macs_per_image = 0; multi.mfma_macs_per_image = 0; }
-                multi.mlayer[l - 1] = op.layer; multi.min_[l - 1] = op.in0; multi.mout[l - 1] = op.out;
-                multi.mh[l - 1] = lh[l]; multi.mw[l - 1] = lw[l];
-                multi.macs_per_image += op.macs_per_image; multi.mfma_macs_per_image += op.mfma_macs_per_image;
-                if (l == 4) h->ops.push_back(multi);
-            } else {
-                h->ops.push_back(op);
-            }
-        }
-    }
-    (void)ch; (void)cw;
-    if (a.kind == UKBB_KIND_FCN) {
-        std::vector<int> &sq = sqg_out;
-        Op op; op.kind = OP_HEAD; op.name = "head"; op.in0 = level_out[0];
-        op.H = op.Ho = H; op.W = op.Wo = W;
-        op.macs_per_image = (double)H * W * (a.n_filter[0] * a.same_dim + a.same_dim * a.n_level * a.fc +
-                                             a.fc * a.fc + a.fc * a.n_class);
-        // matrix pipe: same_dim0, the level-0 slice of out0, out1 (the logits run on the vector ALU)
-        op.mfma_macs_per_image = (double)H * W * (a.n_filter[0] * a.same_dim + a.same_dim * a.fc + a.fc * a.fc);
-        for (int l = 1; l < 5; ++l) op.sq[l - 1] = sq[l];
-        h->ops.push_back(op);
-    } else {
-        // decoder (network_ao.py:44-55): transposed conv, concat [skip, up] (two-source conv), convs
-        int up = level_out[a.n_level - 1];
-        for (int l = a.n_level - 2; l >= 0; --l) {
-            snprintf(nm, sizeof nm, "up%d_t", l);
-            int t;
-            int rc = add_tconv(h, nm, up, lh[l + 1], lw[l + 1], n_hint, &t);
-            if (rc) return rc;
-            int x = -1;
-            // bf16 storage, level 0 with the standard two 16-channel convs: up0_0, up0_1, logits and softmax / argmax as ONE launch
-            // (kernels_tail.hip); UKBB_NO_FUSE_TAIL=1 keeps the separate launches (A/B knob)
-            const bool no_tail = getenv("UKBB_NO_FUSE_TAIL") != nullptr;      // read at every plan build (tools/check_tail.py switches it inside one process)
-            if (l == 0 && a.kind == UKBB_KIND_UNET && bf16_mode(h) == 2 && !no_tail && a.n_block[0] == 2 && a.n_filter[0] == 16 &&
-                a.n_class >= 2 && a.n_class <= 4 && override_cfg("up0_0") < 0 && override_cfg("up0_1") < 0) {
-                const int l0 = h->layer_index.at("up0_0"), l1 = h->layer_index.at("up0_1");
-                const HostLayer &L0 = h->layers[l0], &L1 = h->layers[l1];
-                if (!dev_ptr(h, "tail/wA0")) {
-                    std::vector<float> p0((size_t)9 * 64 * 4), p1((size_t)5 * 64 * 4);
-                    pack_tail_weights(L0.w.data(), L1.w.data(), p0.data(), p1.data());
-                    int rc = upload(h, "tail/wA0", p0);
-                    if (rc) return rc;
-                    rc = upload(h, "tail/wA1", p1);
-                    if (rc) return rc;
-                }
-                Op op; op.kind = OP_TAIL; op.name = "up0_0+up0_1+logits"; op.layer = l0; op.in0 = level_out[0]; op.in1 = t;
-                op.H = op.Ho = lh[0]; op.W = op.Wo = lw[0];
-                op.macs_per_image = (double)lh[0] * lw[0] * (9.0 * L0.cin * L0.cout + 9.0 * L1.cin * L1.cout + (double)a.n_filter[0] * a.n_class);
-                h->ops.push_back(op);
-                h->feat_buf = -1;
-                up = -1;
-                continue;
-            }
-            for (int i = 0; i < a.n_block[l]; ++i) {
-                snprintf(nm, sizeof nm, "up%d_%d", l, i);
-                static const bool no_fuse_lg = getenv("UKBB_NO_FUSE_LOGITS") != nullptr;    // A/B knob
-                // bf16 storage: logits + softmax / argmax ride in the epilogue of the very last conv (its output is never stored)
-                const bool flg = a.kind == UKBB_KIND_UNET && bf16_mode(h) == 2 && !no_fuse_lg && l == 0 && i == a.n_block[0] - 1 &&
-                                 i > 0 && a.n_filter[0] == 16 && pick_fused_bf_cfg(nm, 3, 1, 16, 0, 16, lh[0], lw[0], 2) >= 0;
-                rc = (i == 0) ? add_conv(h, nm, level_out[l], t, a.n_filter[l], lh[l], lw[l], 1, n_hint, &x)
-                              : add_conv(h, nm, x, -1, 0, lh[l], lw[l], 1, n_hint, &x, false, flg);
-                if (rc) return rc;
-            }
-            up = x;
-            h->act_name[up] = std::string("up") + std::to_string(l);
-        }
-        h->feat_buf = up;                              // net['conv0_up']: what UNet_LSTM_Model feeds the LSTM (:343-347)
-        if (a.kind == UKBB_KIND_UNET && h->ops.back().kind == OP_TAIL) {
-            // logits, softmax / argmax are part of the fused tail launch
-        } else if (a.kind == UKBB_KIND_UNET && h->ops.back().kind == OP_CONV && h->ops.back().fused_logits) {
-            Op &last = h->ops.back();
-            last.name += "+logits";
-            last.macs_per_image += (double)H * W * a.n_filter[0] * a.n_class;
-            h->act_name[up] = "";                      // net['conv0_up'] does not exist in HBM in this plan
-        } else if (a.kind == UKBB_KIND_UNET) {
-            Op op; op.kind = OP_LOGITS; op.name = "logits"; op.layer = h->layer_index.at("logits"); op.in0 = up;
-            op.H = op.Ho = H; op.W = op.Wo = W;
-            op.macs_per_image = (double)H * W * a.n_filter[0] * a.n_class;
-            h->ops.push_back(op);
-        } else {
-            // ConvLSTM: region shape of the fused gate-conv / cell kernel, chosen once per plan (both shapes give identical bits);
-            // packed filters: the x rows of both directions as ONE 128-channel conv (groups = directions), the h rows per direction
-            // (read per plan build, like UKBB_NO_FUSE_TAIL: the A/B knob can be toggled inside one process by re-planning)
-            h->lstm_bf_wino = getenv("UKBB_LSTM_BF16_WINOGRAD") != nullptr;
-            // r06 experiment, measured and NOT the default: UKBB_LSTM_BF16_UNHOIST=1 makes the bf16 time steps re-multiply x instead of reading the hoisted gx
-            // (320 -> 224 bytes per pixel and step).  100-frame 256x256 cine, three alternating rounds + rocprofv3 (profiles/r06_ab_lstm_unhoist.txt): step
-            // 354.8 -> 372.1 us, x pass 754 -> 636 us, cine 8.17 -> 8.31 ms: the step is not bound by its bytes alone -- the second chunk's staging and MFMAs
-            // cost more issue time than the gx loads they replace.  The hoisted form (r05) stays.
-            h->lstm_bf_hoist = getenv("UKBB_LSTM_BF16_UNHOIST") == nullptr;
-            const int cols24 = lstm_region_cols(a, H, W, n_hint, device_cu_count());
-            const bool have24 = cols24 != 0;
-            // the bf16 plan's time steps run on launch_lstm_ws (kernels_ws.hip) and never touch the F(2x4) kernel: only the fp32 plan and the
-            // bf16-storage Winograd A/B form need that tiling
-            if (!have24 && (bf16_mode(h) != 2 || h->lstm_bf_wino)) {
-                set_err("the ConvLSTM needs the Winograd F(2x4) kernel (unset UKBB_NO_WINOGRAD / UKBB_NO_WINOGRAD24 / UKBB_CONV_CFG overrides)");
-                return UKBB_EARCH;
-            }
-            h->lstm_tile_cols = have24 ? cols24 : 32;
-            if (const char *e = getenv("UKBB_LSTM_TILE_COLS")) { const int v = atoi(e); if (v == 16 || v == 32) h->lstm_tile_cols = v; }   // A/B knob (identical bits)
-            {
-                const HostLayer &B = h->layers[h->layer_index.at("lstm_bw")];
-                bool z = getenv("UKBB_LSTM_RUN_ZERO_CELL") == nullptr;      // knob: run the zero cell anyway (tests compare both ways)
-                for (size_t i = 0; z && i < B.w.size(); ++i) z = B.w[i] == 0.f;
-                for (size_t i = 0; z && i < B.b.size(); ++i) z = B.b[i] == 0.f;
-                h->lstm_bw_zero = z;
-            }
-            if (!dev_ptr(h, "lstm/wx")) {
-                const size_t per = (size_t)24 * 16 * 64;
-                std::vector<float> wx(2 * per), bx(2 * 64), wh(per);
-                int d = 0;
-                for (const char *nm2 : {"lstm_fw", "lstm_bw"}) {
-                    const HostLayer &L = h->layers[h->layer_index.at(nm2)];
-                    if (L.cin != 32 || L.cout != 64 || L.ks != 3) { set_err("ConvLSTM gate kernel must be 3x3x(16+16)x64"); return UKBB_EARCH; }
-                    pack_lstm_gate_weights(L.w.data(), L.cin, 0, L.b.data(), wx.data() + d * per, bx.data() + d * 64);
-                    pack_lstm_gate_weights(L.w.data(), L.cin, a.n_filter[0], nullptr, wh.data(), nullptr);
-                    int rc = upload(h, std::string(nm2) + "/wh", wh);
-                    if (rc) return rc;
-                    ++d;
-                }
-                int rc = upload(h, "lstm/wx", wx);
-                if (rc) return rc;
-                rc = upload(h, "lstm/bx", bx);
-                if (rc) return rc;
-                // bf16 form (kernels_ws.hip, ws_main LS): direct 3x3 conv on the bf16 matrix instruction, its own channel order
-                const size_t perb = (size_t)9 * 16 * 64 / 2;          // dwords
-                std::vector<float> wxb(2 * perb), bxb(2 * 64), whb(perb);
-                d = 0;
-                for (const char *nm2 : {"lstm_fw", "lstm_bw"}) {
-                    const HostLayer &L = h->layers[h->layer_index.at(nm2)];
-                    pack_lstm_gate_weights_bf16(L.w.data(), L.cin, 0, L.b.data(), wxb.data() + d * perb, bxb.data() + d * 64);
-                    pack_lstm_gate_weights_bf16(L.w.data(), L.cin, a.n_filter[0], nullptr, whb.data(), nullptr);
-                    rc = upload(h, std::string(nm2) + "/wh_bf16", whb);
-                    if (rc) return rc;
-                    std::vector<float> wxhb(2 * perb);               // r06: both halves as one two-chunk filter (un-hoisted time steps, ls_mode 3)
-                    pack_lstm_gate_weights_bf16_xh(L.w.data(), nullptr, wxhb.data(), nullptr);
-                    rc = upload(h, std::string(nm2) + "/wxh_bf16", wxhb);
-                    if (rc) return rc;
-                    ++d;
-                }
-                rc = upload(h, "lstm/wx_bf16", wxb);
-                if (rc) return rc;
-                rc = upload(h, "lstm/bx_bf16", bxb);
-                if (rc) return rc;
-            }
-        }
-    }
+    PlanLayout L;
+    int rc = layout_plan(h->arch, h->precision, H, W, n_hint, device_cu_count(), L);
+    if (rc) return rc;
+    h->cine = cine_units_from(L, h->arch, H, W);
+    rc = materialize_plan(h, L);
+    if (rc) return rc;
     h->plan_h = H; h->plan_w = W; h->plan_small = n_hint <= SMALL_BATCH; h->plan_n = n_hint;
-    h->plan_bfio = bf16_mode(h) == 2;
-    // r06: the levels >= k of a plan (U-Net: conv{k}_0 .. up{k}_1) run as two half-batch chains on two streams (run_plan), so that one half's
-    // fill / drain / serial chains hide under the other half's body.  Measured at N = 100 x 256x256 (profiles/r06_split_levels.txt and
-    // r06_split_after_fix.txt), labels bit-identical to the unsplit plan in every run: fp32 U-Net 4.02 -> 3.86 ms per forward with k = 1
-    // (+4 %; k = 2: 3.88, k = 3: 3.92, k = 4: no change), bf16-storage U-Net 1.042 -> 1.042 (nothing to hide once the walkers fill the chip),
-    // FCN 0.5-1 % slower.  So: ON from level 1 for a UKBB_KIND_UNET plan in fp32, off everywhere else; UKBB_SPLIT_FROM=k overrides (0 = off).
-    // (While this was first tried the 300-case bf16 sweep met sporadic wrong tiles with it; that was the wide-store hazard of kernels_ws.hip,
-    // store_b128_sofs there and profiles/r06_notes.md section 10 -- fixed, and the sweep is clean with the split forced on.)
-    h->split_first = -1; h->split_last = -2;
-    {
-        const char *e = getenv("UKBB_SPLIT_FROM");
-        const int k = e ? atoi(e) : (a.kind == UKBB_KIND_UNET && bf16_mode(h) == 0) ? 1 : 0;
-        if (k >= 1 && k < a.n_level) {
-            // U-Net: conv{k}_0 .. up{k}_1; FCN (no decoder): conv{k}_0 .. the last encoder conv (the squeeze launches and the head follow unsplit)
-            const std::string c0 = "conv" + std::to_string(k) + "_0";
-            const std::string u0 = a.kind == UKBB_KIND_FCN ? "conv" + std::to_string(a.n_level - 1) + "_" : "up" + std::to_string(k) + "_";
-            for (size_t i = 0; i < h->ops.size(); ++i) {
-                if (h->split_first < 0 && h->ops[i].name.compare(0, c0.size(), c0) == 0) h->split_first = (int)i;
-                if (h->ops[i].name.compare(0, u0.size(), u0) == 0 && h->ops[i].kind != OP_TAIL) h->split_last = (int)i;
-            }
-            if (h->split_first < 0 || h->split_last < h->split_first) { h->split_first = -1; h->split_last = -2; }
-        }
-        h->debug_first_op = 0; h->debug_last_op = 1 << 30;
-        if (const char *o = getenv("UKBB_DEBUG_OPS")) { int f = 0, l = 1 << 30; if (sscanf(o, "%d,%d", &f, &l) >= 1) { h->debug_first_op = f; h->debug_last_op = l; } }
-        if (const char *o = getenv("UKBB_SPLIT_OP")) {     // debugging: ONLY op i runs as two half-batch launches on two streams
-            const int i = atoi(o);
-            if (i >= 0 && i < (int)h->ops.size()) { h->split_first = i; h->split_last = i; }
-        }
-    }
-    // events
-    for (auto e : h->ev) (void)hipEventDestroy(e);
-    h->ev.clear();
-    h->t_sum.assign(h->ops.size(), 0.0);
-    h->t_cnt.assign(h->ops.size(), 0);
-    h->ev_pending = false;
     return UKBB_OK;
 }
 
@@ -1462,6 +734,38 @@ int ukbb_fcn_debug_set_ops(ukbb_fcn_handle *h, int first, int last) {
     return UKBB_OK;
 }
 
+// debugging / testing aid, not in the public header: the plan layout_plan makes for batches of n images of H x W on a device of `cus`
+// compute units, as text -- host arithmetic only, no device needed.  One line per op, one per activation map, then the plan's fields.
+// Returns the text's length (it is truncated when cap is smaller), or the negative code create / set_precision / reserve would give.
+int ukbb_fcn_debug_plan_layout(const ukbb_fcn_arch *arch, int precision, int n, int H, int W, int cus, char *buf, size_t cap) {
+    static const char *const kinds[] = {"first", "conv", "head", "tconv", "logits", "sqg", "sqg_multi", "tail", "stem", "first3d", "conv3d", "tconv3d"};
+    if (!arch || (!buf && cap) || cus < 1) { set_err("debug_plan_layout: bad argument"); return UKBB_EINVAL; }
+    if (precision != UKBB_PREC_FP32 && precision != UKBB_PREC_BF16 && precision != UKBB_PREC_F32X3) { set_err("debug_plan_layout: bad precision"); return UKBB_EINVAL; }
+    int rc = check_shape(n, H, W);
+    if (rc) return rc;
+    if (arch->kind == UKBB_KIND_TEMPORAL_UNET && precision == UKBB_PREC_BF16) { set_err("the Temporal-UNet's 3-D convolutions are built for fp32 only (no bf16 plan)"); return UKBB_EARCH; }
+    PlanLayout L;
+    rc = layout_plan(*arch, precision, H, W, n, cus, L);
+    if (rc) return rc;
+    std::string out;
+    char line[512];
+    for (size_t i = 0; i < L.ops.size(); ++i) {
+        const Op &op = L.ops[i];
+        snprintf(line, sizeof line, "op %zu %s %s %d %d %d %d %d %d %d %d %d %.17g %.17g %.17g\n", i, op.name.c_str(), kinds[op.kind], op.cfg, op.H, op.W, op.Ho, op.Wo,
+                 op.stride, op.in0, op.in1, op.out, op.macs_per_image, op.mfma_macs_per_image, op.padded_macs_per_image);
+        out += line;
+    }
+    for (const ActSpec &s : L.acts) {
+        snprintf(line, sizeof line, "act %s %zu %d\n", s.name.empty() ? "-" : s.name.c_str(), s.per_image, s.channels);
+        out += line;
+    }
+    snprintf(line, sizeof line, "plan split %d %d bfio %d feat_buf %d lstm %d %d %d %d\n", L.split_first, L.split_last, (int)L.bfio, L.feat_buf,
+             (int)L.needs_lstm, L.lstm_tile_cols, (int)L.lstm_bf_wino, (int)L.lstm_bf_hoist);
+    out += line;
+    if (cap) { const size_t m = std::min(out.size(), cap - 1); memcpy(buf, out.data(), m); buf[m] = 0; }
+    return (int)out.size();
+}
+
 const char *ukbb_fcn_last_error(void) { return g_err.c_str(); }
 
 size_t ukbb_fcn_weight_count(const ukbb_fcn_arch *arch) {
@@ -1500,10 +804,6 @@ ukbb_fcn_handle *ukbb_fcn_create(const ukbb_fcn_arch *arch, const float *weights
     std::unique_ptr<ukbb_fcn_handle> h(new ukbb_fcn_handle);
     h->arch = *arch;
     h->device = device;
-    // r01 measurement: running sqg_l concurrently with the deeper convs made the step 9 % SLOWER
-    // (1.88 vs 1.72 ms: the sqg waves take SIMD slots and L2 bandwidth from the MFMA-bound persistent
-    // conv kernels), so the fork/join path is off unless UKBB_SIDE_STREAM is set.
-    h->use_side = getenv("UKBB_SIDE_STREAM") != nullptr;
 
     // ---- fold BN (fp32; same op order as weights.py fold_bn) --------------------------
     const float *p = weights;
@@ -1630,142 +930,21 @@ int ukbb_fcn_forward_host(ukbb_fcn_handle *h, const float *image, int n, int hei
     return UKBB_OK;
 }
 
-// ---- forward_cine scratch planner (host only) -----------------------------------------------------------
+// ---- forward_cine scratch planner: the host-only queries (the arithmetic is plan.cpp's) ---------------------------------------
 namespace {
 
-// Device bytes forward_cine holds per frame / per window of a cine at one (arch, precision, H, W).  DevBufs count floats; bf16 maps take half.
-struct CineUnits {
-    int kind = 0, T = 0, n_class = 0;
-    size_t HW = 0;
-    size_t act_frame = 0;        // the plan's activation workspace, floats per frame (U-Net: allocated as floats in either precision)
-    size_t esz = 4;              // UNet-LSTM: bytes per stored gx / hidden element
-    size_t gx_frame = 0;         // UNet-LSTM: gx elements per frame and direction (tile-padded: wino24_lstm_gx_floats / lstm_ws_gx_elems)
-    size_t c_item = 0;           // UNet-LSTM: cell-state floats per frame (c1, per direction) or window (c) (tile-padded likewise)
-    size_t h_item = 0;           // UNet-LSTM: hidden elements per frame or window, direction and step (HW * 16)
-};
-
-struct CinePlan {
-    int Wn = 0, Wc = 0, chunks = 0;
-    int run = 0;                 // frames of the longest chunk's run (F when unchunked)
-    uint64_t bytes = 0;          // what forward_cine holds for this call
-    uint64_t min_bytes = 0;      // the smallest budget that runs this call
-};
-
-size_t bytes_of(size_t elems, size_t esz) { return (elems * esz + 3) / 4 * 4; }      // a DevBuf of `elems` elements of esz bytes
-
-uint64_t cine_table_bytes(int F, int T, int Wn) {        // lstm_aux / t3d_aux: window -> frame map, per-frame order, window weights, per-frame weight sums
-    const size_t b_map = (size_t)T * Wn * sizeof(int), b_ord = (size_t)F * T * sizeof(int);
-    const size_t off_ord = (b_map + 7) / 8 * 8, off_wk = (off_ord + b_ord + 7) / 8 * 8, off_ws = off_wk + T * sizeof(double);
-    return (off_ws + F * sizeof(double) + 3) / 4 * 4;
-}
-
-// UNet-LSTM: bytes held with chunks of Wc windows whose longest run has R frames; stage = the contiguous copy of the run's input frames
-uint64_t lstm_cine_bytes(const CineUnits &u, int F, int Wn, int R, int Wc, bool stage) {
-    uint64_t b = (uint64_t)u.act_frame * R * 4;                                      // U-Net activations of R frames
-    if (stage) b += (uint64_t)u.HW * R * 4;                                          // lstm_img
-    b += bytes_of(2 * (size_t)R * u.gx_frame, u.esz);                                // lstm_gx
-    b += (uint64_t)2 * R * u.c_item * 4;                                             // lstm_c1
-    b += bytes_of(2 * (size_t)R * u.h_item, u.esz);                                  // lstm_h1
-    b += (uint64_t)Wc * u.c_item * 4;                                                // lstm_c
-    b += bytes_of(2 * (size_t)u.T * Wc * u.h_item, u.esz);                           // lstm_hall
-    return b + cine_table_bytes(F, u.T, Wn);
-}
-
-constexpr double T3D_CHUNK_BYTES = 4.0e9;      // Temporal-UNet without a budget: the chunk's activations + window probabilities stay within this
-
-// THE chunk plan of forward_cine, shared by the engine (units from its plan) and ukbb_fcn_cine_scratch_bytes (units from cine_units).
-// budget 0: UNet-LSTM one chunk, Temporal-UNet the T3D_CHUNK_BYTES rule.  false: the budget is below plan.min_bytes.
-bool plan_cine(const CineUnits &u, int F, int time_step, uint64_t budget, CinePlan &pl) {
-    const int T = u.T, Wn = (F + time_step - 1) / time_step;
-    pl = CinePlan();
-    pl.Wn = Wn;
-    if (u.kind == UKBB_KIND_TEMPORAL_UNET) {
-        const uint64_t per_window = (uint64_t)(u.act_frame + u.HW * u.n_class) * 4 * T, tables = cine_table_bytes(F, T, Wn);
-        pl.min_bytes = per_window + tables;
-        int Wc;
-        if (!budget) Wc = std::max(1, (int)std::min<double>(Wn, T3D_CHUNK_BYTES / (double)per_window));
-        else if (budget < pl.min_bytes) return false;
-        else Wc = (int)std::min<uint64_t>(Wn, (budget - tables) / per_window);
-        pl.Wc = Wc; pl.chunks = (Wn + Wc - 1) / Wc; pl.run = Wc * T;
-        pl.bytes = (uint64_t)Wc * per_window + tables;
-        return true;
-    }
-    // a chunk of n windows touches one circular run of (n - 1) * time_step + T frames (all F when that exceeds F)
-    auto run_of = [&](int n) { return (int)std::min<long long>(F, (long long)(n - 1) * time_step + T); };
-    const uint64_t whole = lstm_cine_bytes(u, F, Wn, F, Wn, false);
-    pl.min_bytes = Wn > 1 ? std::min(whole, lstm_cine_bytes(u, F, Wn, run_of(1), 1, true)) : whole;
-    if (!budget || budget >= whole) { pl.Wc = Wn; pl.chunks = 1; pl.run = F; pl.bytes = whole; return true; }
-    if (budget < pl.min_bytes) return false;
-    int lo = 1, hi = Wn - 1;                     // lstm_cine_bytes grows with Wc: the largest Wc < Wn that fits (Wc = 1 does, and Wn > 1 here)
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) / 2;
-        if (lstm_cine_bytes(u, F, Wn, run_of(mid), mid, true) <= budget) lo = mid; else hi = mid - 1;
-    }
-    pl.Wc = lo; pl.chunks = (Wn + lo - 1) / lo; pl.run = run_of(lo);
-    pl.bytes = lstm_cine_bytes(u, F, Wn, pl.run, lo, true);
-    return true;
-}
-
-// The units of a FRESH handle's plan for cines of F frames on an MI355X (256 compute units), without a device: the activation maps
-// build_plan / build_plan_t3d create and the ConvLSTM buffers run_bilstm sizes.  (The A/B environment knobs that add or drop a map,
-// or a handle whose plan was built for another frame count, can differ; the engine always plans with the units of its own plan.)
-bool cine_units(const ukbb_fcn_arch &a, int precision, int F, int H, int W, CineUnits &u) {
-    if (a.kind != UKBB_KIND_UNET_LSTM && a.kind != UKBB_KIND_TEMPORAL_UNET) return false;
+// The units of a FRESH handle's plan for cines of F frames on an MI355X (256 compute units), without a device: the layout the engine
+// itself would build, so the A/B knobs that add or drop a map count here as they do there.  false: a request forward_cine would refuse.
+bool cine_query_units(const ukbb_fcn_arch *arch, int precision, int F, int H, int W, int time_step, CineUnits &u) {
+    if (!arch || !ukbb_fcn_weight_count(arch)) return false;
+    if (arch->kind != UKBB_KIND_UNET_LSTM && arch->kind != UKBB_KIND_TEMPORAL_UNET) return false;
     if (precision != UKBB_PREC_FP32 && precision != UKBB_PREC_BF16) return false;
-    if (a.kind == UKBB_KIND_TEMPORAL_UNET && precision != UKBB_PREC_FP32) return false;
-    if (a.n_level < 1 || a.n_level > UKBB_FCN_MAX_LEVEL || a.fc < 1) return false;
-    const int bfm = bf16_mode(a.kind, precision);
-    u = CineUnits();
-    u.kind = a.kind; u.T = a.fc; u.n_class = a.n_class; u.HW = (size_t)H * W;
-    std::vector<int> lh(a.n_level), lw(a.n_level);
-    int hh = H, ww = W;
-    for (int l = 0; l < a.n_level; ++l) {
-        if (l > 0) { hh = (hh + 1) / 2; ww = (ww + 1) / 2; }
-        lh[l] = hh; lw[l] = ww;
-        int maps = a.n_block[l];
-        if (l == 0 && a.kind == UKBB_KIND_UNET_LSTM) {        // conv0_0 evaluated inside conv0_1's launch: no map of its own (build_plan: stem / can_fuse)
-            const bool std0 = a.n_block[0] >= 2 && a.n_filter[0] == 16;
-            const bool stem = bfm == 2 && getenv("UKBB_NO_FUSE_STEM") == nullptr && std0 && override_cfg("conv0_1") < 0;
-            const bool can_fuse = getenv("UKBB_NO_FUSE_FIRST") == nullptr && std0 && (bfm != 2 || pick_fused_bf_cfg("conv0_1", 3, 1, 16, 0, 16, H, W, 1) >= 0);
-            if (stem || can_fuse) --maps;
-        }
-        u.act_frame += (size_t)maps * hh * ww * a.n_filter[l];
-    }
-    for (int l = a.n_level - 2; l >= 0; --l)                  // transposed conv (2 x the level below), then the level's convs
-        u.act_frame += (size_t)4 * lh[l + 1] * lw[l + 1] * a.n_filter[l] + (size_t)a.n_block[l] * lh[l] * lw[l] * a.n_filter[l];
-    if (a.kind == UKBB_KIND_UNET_LSTM) {
-        if (a.same_dim != 16 || a.n_filter[0] != 16) return false;
-        u.esz = bfm == 2 ? 2 : 4;
-        u.h_item = u.HW * a.same_dim;
-        if (bfm == 2) { u.gx_frame = lstm_ws_gx_elems(H, W); u.c_item = lstm_ws_c_floats(H, W); }
-        else {
-            int tc = lstm_region_cols(a, H, W, F, 256);
-            if (!tc) return false;
-            if (const char *e = getenv("UKBB_LSTM_TILE_COLS")) { const int v = atoi(e); if (v == 16 || v == 32) tc = v; }
-            u.gx_frame = wino24_lstm_gx_floats(H, W, tc); u.c_item = wino24_lstm_c_floats(H, W, tc);
-        }
-    }
+    if (arch->kind == UKBB_KIND_TEMPORAL_UNET && precision != UKBB_PREC_FP32) return false;
+    if (!cine_request_ok(arch->fc, F, H, W, time_step)) return false;
+    PlanLayout L;
+    if (layout_plan(*arch, precision, H, W, F, 256, L)) return false;
+    u = cine_units_from(L, *arch, H, W);
     return true;
-}
-
-// the same from a handle's built plan
-void cine_units_of(const ukbb_fcn_handle *h, int H, int W, CineUnits &u) {
-    const ukbb_fcn_arch &a = h->arch;
-    u = CineUnits();
-    u.kind = a.kind; u.T = a.fc; u.n_class = a.n_class; u.HW = (size_t)H * W;
-    for (size_t i = 0; i < h->act.size(); ++i) u.act_frame += h->act_per_image[i];
-    if (a.kind != UKBB_KIND_UNET_LSTM) return;
-    const bool wsf = h->plan_bfio && !h->lstm_bf_wino;
-    u.esz = h->plan_bfio ? 2 : 4;
-    u.h_item = u.HW * a.same_dim;
-    u.gx_frame = wsf ? lstm_ws_gx_elems(H, W) : wino24_lstm_gx_floats(H, W, h->lstm_tile_cols);
-    u.c_item = wsf ? lstm_ws_c_floats(H, W) : wino24_lstm_c_floats(H, W, h->lstm_tile_cols);
-}
-
-bool cine_request_ok(int T, int F, int H, int W, int time_step) {
-    if (F < 1 || H < 16 || W < 16 || (H % 16) || (W % 16) || time_step < 1 || T < 1 || !(T & 1)) return false;
-    if ((long long)F * H * W > (1ll << 31) - 1) return false;
-    return F >= (T - 1) / 2;
 }
 
 void scratch_bufs(ukbb_fcn_handle *h, std::vector<DevBuf *> &v) {
@@ -1804,27 +983,24 @@ int budget_enter(ukbb_fcn_handle *h, int F, int H, int W, int time_step, const C
 }  // namespace
 
 uint64_t ukbb_fcn_cine_scratch_bytes(const ukbb_fcn_arch *arch, int precision, int n_frames, int height, int width, int time_step, uint64_t budget) {
-    if (!arch || !ukbb_fcn_weight_count(arch)) return 0;
     CineUnits u;
     CinePlan pl;
-    if (!cine_request_ok(arch->fc, n_frames, height, width, time_step) || !cine_units(*arch, precision, n_frames, height, width, u)) return 0;
+    if (!cine_query_units(arch, precision, n_frames, height, width, time_step, u)) return 0;
     return plan_cine(u, n_frames, time_step, budget, pl) ? pl.bytes : 0;
 }
 
 uint64_t ukbb_fcn_cine_min_scratch_bytes(const ukbb_fcn_arch *arch, int precision, int n_frames, int height, int width, int time_step) {
-    if (!arch || !ukbb_fcn_weight_count(arch)) return 0;
     CineUnits u;
     CinePlan pl;
-    if (!cine_request_ok(arch->fc, n_frames, height, width, time_step) || !cine_units(*arch, precision, n_frames, height, width, u)) return 0;
+    if (!cine_query_units(arch, precision, n_frames, height, width, time_step, u)) return 0;
     plan_cine(u, n_frames, time_step, 0, pl);
     return pl.min_bytes;
 }
 
 int ukbb_fcn_cine_chunk_windows(const ukbb_fcn_arch *arch, int precision, int n_frames, int height, int width, int time_step, uint64_t budget) {
-    if (!arch || !ukbb_fcn_weight_count(arch)) return 0;
     CineUnits u;
     CinePlan pl;
-    if (!cine_request_ok(arch->fc, n_frames, height, width, time_step) || !cine_units(*arch, precision, n_frames, height, width, u)) return 0;
+    if (!cine_query_units(arch, precision, n_frames, height, width, time_step, u)) return 0;
     return plan_cine(u, n_frames, time_step, budget, pl) ? pl.Wc : 0;
 }
 
@@ -1859,7 +1035,7 @@ int run_bilstm(ukbb_fcn_handle *h, const float *feat, int NF, const int *d_map, 
     // bf16 plan: the direct-conv bf16 form (kernels_ws.hip) unless UKBB_LSTM_BF16_WINOGRAD=1 asks for the fp32 Winograd arithmetic on bf16 storage (A/B)
     const bool wsf = h->plan_bfio && !h->lstm_bf_wino;
     // r06 experiment (UKBB_LSTM_BF16_UNHOIST=1): the direct-conv bf16 steps read the feature frame (32 bytes per pixel) and multiply it again
-    // instead of reading gx (128 bytes per pixel); no gx buffer exists in that form.  Slower by 5 % per step (see build_plan), so not the default.
+    // instead of reading gx (128 bytes per pixel); no gx buffer exists in that form.  Slower by 5 % per step (plan.cpp, read_knobs), so not the default.
     const bool unhoist = wsf && !h->lstm_bf_hoist;
     const size_t gxf = wsf ? lstm_ws_gx_elems(H, W) : wino24_lstm_gx_floats(H, W, tc), cf = wsf ? lstm_ws_c_floats(H, W) : wino24_lstm_c_floats(H, W, tc);
     const bool bf = h->plan_bfio;                        // bf16 plan: features, gx and hidden maps are bf16 in HBM
@@ -1991,9 +1167,8 @@ int t3d_forward_cine(ukbb_fcn_handle *h, const float *image, int F, int height, 
     const int Wn = (F + time_step - 1) / time_step;
     // Windows per chunk: as many as fit the scratch budget (without one: T3D_CHUNK_BYTES of activations + window probabilities, at least one
     // window); UKBB_TEMPORAL_CHUNK_WINDOWS=n overrides either (tests force small chunks with it)
-    CineUnits un;
+    const CineUnits &un = h->cine;
     CinePlan pl;
-    cine_units_of(h, height, width, un);
     if (!plan_cine(un, F, time_step, h->scratch_budget, pl)) {
         set_err("forward_cine: the scratch budget of %llu bytes is below the %llu bytes one window of %d frames of %dx%d needs", (unsigned long long)h->scratch_budget,
                 (unsigned long long)pl.min_bytes, T, height, width);
@@ -2135,9 +1310,8 @@ int ukbb_fcn_forward_cine(ukbb_fcn_handle *h, const float *image, int n_frames, 
     // budget the workspace is sized for a chunk's frame run only.
     rc = prepare(h, F, height, width, h->scratch_budget ? 0 : -1);
     if (rc) return rc;
-    CineUnits un;
+    const CineUnits &un = h->cine;
     CinePlan pl;
-    cine_units_of(h, height, width, un);
     if (!plan_cine(un, F, time_step, h->scratch_budget, pl)) {
         set_err("forward_cine: the scratch budget of %llu bytes is below the minimum of %llu bytes for %d frames of %dx%d at time_step %d", (unsigned long long)h->scratch_budget,
                 (unsigned long long)pl.min_bytes, F, height, width, time_step);

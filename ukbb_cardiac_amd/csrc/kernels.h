@@ -1,4 +1,4 @@
-// Internal interface between the engine (engine.cpp) and the gfx950 kernels.
+// Internal interface between the engine (plan.cpp: which kernels and tilings; engine.cpp: packing and launches) and the gfx950 kernels.
 // Not part of the public ABI (that is include/ukbb_fcn.h).
 #pragma once
 #include <hip/hip_runtime.h>

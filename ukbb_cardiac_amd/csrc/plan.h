@@ -1,0 +1,92 @@
+// Host-only planner of the engine: which launches a forward consists of, the tiling each conv gets, the activation maps and their
+// sizes, the MAC accounting and the chunk plan of forward_cine.  Pure arithmetic over (architecture, precision, H, W, batch, CU count,
+// environment knobs): no HIP call, no handle, no weights.  engine.cpp materialises a PlanLayout on the device and runs it.
+#pragma once
+#include "../../include/ukbb_fcn.h"
+#include "kernels.h"
+
+#include <string>
+#include <vector>
+
+namespace ukbb {
+
+// ---- architecture walk ---------------------------------------------------------
+struct Spec { std::string name; int ks, cin, cout; bool bn, bias, transposed; int kd = 1; };
+
+bool arch_specs(const ukbb_fcn_arch &a, std::vector<Spec> &out);     // the layers in the order of the flat weight array
+size_t spec_floats(const Spec &s);
+bool supported(const ukbb_fcn_arch &a, std::string &why);
+
+// ---- the plan --------------------------------------------------------------------
+enum OpKind { OP_FIRST, OP_CONV, OP_HEAD, OP_TCONV, OP_LOGITS, OP_SQG, OP_SQG_MULTI, OP_TAIL, OP_STEM,
+              OP_FIRST3D, OP_CONV3D, OP_TCONV3D };   // ..._3D: the Temporal-UNet's 3-D convolutions (kernels_conv3d.hip)
+
+struct Op {                    // one kernel launch of the plan
+    OpKind kind;
+    std::string name;
+    int layer = -1;            // index into arch_specs / the handle's host layers (OP_FIRST/OP_CONV/OP_TCONV/OP_LOGITS)
+    int cfg = -1;              // conv config id
+    int in0 = -1, in1 = -1;    // activation buffer ids (-1: network input / none)
+    int out = -1;
+    int sq[4] = {-1, -1, -1, -1};   // OP_HEAD: squeezed maps of levels 1..4
+    int mlayer[4] = {-1, -1, -1, -1}, min_[4] = {-1, -1, -1, -1}, mout[4] = {-1, -1, -1, -1}, mh[4] = {0, 0, 0, 0}, mw[4] = {0, 0, 0, 0};   // OP_SQG_MULTI: levels 1..4
+    bool fused_first = false;       // OP_CONV: conv0_0 (C_in = 1) evaluated by this kernel's producers
+    bool fused_logits = false;      // OP_CONV (bf16 storage): the 1x1 logits conv + softmax / argmax evaluated in this kernel's epilogue
+    bool on_side = false;           // launched on the handle's side stream (fork/join by events)
+    int H = 0, W = 0, Ho = 0, Wo = 0, stride = 1, pad_y = 0, pad_x = 0;
+    double macs_per_image = 0; // algorithmic
+    double mfma_macs_per_image = -1; // issued to the matrix pipe; -1 = same as algorithmic
+    double padded_macs_per_image = -1;   // ... including the slots of partly filled tiles / Winograd regions; -1 = same as mfma_macs_per_image
+    // resolved by engine.cpp's materialize_plan (null in a PlanLayout)
+    const float *wpk = nullptr, *bias = nullptr;
+    const float *wph[4] = {nullptr, nullptr, nullptr, nullptr};   // OP_TCONV3D: packed weights of the 4 sub-pixel phases
+};
+
+struct ActSpec { std::string name; size_t per_image; int channels; };   // per_image: elements per image; channels 0: not a channel map
+
+struct PlanLayout {
+    std::vector<Op> ops;
+    std::vector<ActSpec> acts;
+    int feat_buf = -1;                        // UNet-LSTM: activation index of net['conv0_up']
+    bool bfio = false;                        // every activation between layers is stored as bf16
+    int lstm_tile_cols = 0;                   // region shape of the fused gate-conv / cell kernel (kernels_wino24.hip): 32 | 16
+    bool lstm_bf_wino = false;                // UKBB_LSTM_BF16_WINOGRAD: fp32 Winograd arithmetic on bf16 storage (A/B form)
+    bool lstm_bf_hoist = true;                // false (UKBB_LSTM_BF16_UNHOIST): the bf16 time steps re-multiply x (r06 experiment)
+    bool needs_lstm = false;                  // the plan is followed by the ConvLSTM (its packed gate filters must exist)
+    int split_first = -1, split_last = -2;    // op range run as two half-batch chains
+    int debug_first_op = 0, debug_last_op = 1 << 30;   // UKBB_DEBUG_OPS
+};
+
+constexpr int SMALL_BATCH = 16;
+inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+int find_cfg(int id, ConvConfig &out);        // 0: found
+
+// The plan for batches of up to n_hint images of H x W on a device of `cus` compute units.  UKBB_OK, or UKBB_EARCH with the error text set.
+int layout_plan(const ukbb_fcn_arch &a, int precision, int H, int W, int n_hint, int cus, PlanLayout &L);
+
+// ---- forward_cine scratch planner ---------------------------------------------------
+// Device bytes forward_cine holds per frame / per window of a cine at one (arch, precision, H, W).  DevBufs count floats; bf16 maps take half.
+struct CineUnits {
+    int kind = 0, T = 0, n_class = 0;
+    size_t HW = 0;
+    size_t act_frame = 0;        // the plan's activation workspace, floats per frame (U-Net: allocated as floats in either precision)
+    size_t esz = 4;              // UNet-LSTM: bytes per stored gx / hidden element
+    size_t gx_frame = 0;         // UNet-LSTM: gx elements per frame and direction (tile-padded: wino24_lstm_gx_floats / lstm_ws_gx_elems)
+    size_t c_item = 0;           // UNet-LSTM: cell-state floats per frame (c1, per direction) or window (c) (tile-padded likewise)
+    size_t h_item = 0;           // UNet-LSTM: hidden elements per frame or window, direction and step (HW * 16)
+};
+
+struct CinePlan {
+    int Wn = 0, Wc = 0, chunks = 0;
+    int run = 0;                 // frames of the longest chunk's run (F when unchunked)
+    uint64_t bytes = 0;          // what forward_cine holds for this call
+    uint64_t min_bytes = 0;      // the smallest budget that runs this call
+};
+
+// THE units of a plan: what the engine allocates for it and what ukbb_fcn_cine_scratch_bytes predicts (from a layout for 256 compute units)
+CineUnits cine_units_from(const PlanLayout &L, const ukbb_fcn_arch &a, int H, int W);
+// THE chunk plan of forward_cine.  budget 0: UNet-LSTM one chunk, Temporal-UNet the 4e9-byte rule.  false: the budget is below pl.min_bytes.
+bool plan_cine(const CineUnits &u, int F, int time_step, uint64_t budget, CinePlan &pl);
+bool cine_request_ok(int T, int F, int H, int W, int time_step);
+
+}  // namespace ukbb

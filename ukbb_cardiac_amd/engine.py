@@ -235,6 +235,42 @@ def cine_chunk_windows(arch: ModelArch, precision: str, n_frames: int, height: i
     return int(_lib.lib.ukbb_fcn_cine_chunk_windows(C.byref(a), _PREC[precision], int(n_frames), int(height), int(width), int(time_step), int(budget)))
 
 
+_PLAN_PREC = {'fp32': 0, 'bf16': 1, 'f32x3': 2}
+_OP_FIELDS = ('cfg', 'H', 'W', 'Ho', 'Wo', 'stride', 'in0', 'in1', 'out')
+
+
+def plan_layout(arch: ModelArch, precision: str, n: int, h: int, w: int, cus: int = 256) -> dict:
+    """The launch plan the engine builds for batches of ``n`` images of ``h`` x ``w`` on a device of ``cus`` compute units, from
+    the host-only planner (no GPU needed): ``{'ops': [dict], 'acts': [dict], 'split': (first, last), 'bfio', 'feat_buf', 'lstm'}``.
+    An op's ``macs`` / ``mfma_macs`` / ``issued_macs`` are per image, as ``Engine.kernel_macs()`` etc. report them per batch.
+    Raises UkbbFcnError where ``Engine`` would refuse the combination."""
+    fn = _lib.lib.ukbb_fcn_debug_plan_layout                     # debugging aid: not part of the public header
+    fn.argtypes = [C.POINTER(_lib.ArchStruct)] + [C.c_int] * 5 + [C.c_char_p, C.c_size_t]
+    a = _lib.arch_struct(arch)
+    buf = C.create_string_buffer(1 << 16)
+    got = _lib.check(fn(C.byref(a), _PLAN_PREC[precision], int(n), int(h), int(w), int(cus), buf, len(buf)), 'ukbb_fcn_debug_plan_layout')
+    if got >= len(buf):
+        buf = C.create_string_buffer(got + 1)
+        _lib.check(fn(C.byref(a), _PLAN_PREC[precision], int(n), int(h), int(w), int(cus), buf, len(buf)), 'ukbb_fcn_debug_plan_layout')
+    out = {'ops': [], 'acts': []}
+    for line in buf.value.decode().splitlines():
+        f = line.split(' ')
+        if f[0] == 'op':
+            op = {'name': f[2], 'kind': f[3]}
+            op.update(zip(_OP_FIELDS, map(int, f[4:13])))
+            macs, mfma, issued = map(float, f[13:16])
+            mfma = macs if mfma < 0 else mfma                    # -1: same as the figure before it
+            op.update(macs=macs, mfma_macs=mfma, issued_macs=mfma if issued < 0 else issued)
+            out['ops'].append(op)
+        elif f[0] == 'act':
+            out['acts'].append({'name': '' if f[1] == '-' else f[1], 'per_image': int(f[2]), 'channels': int(f[3])})
+        elif f[0] == 'plan':
+            v = list(map(int, f[2:4] + f[5:6] + f[7:8] + f[9:13]))
+            out.update(split=(v[0], v[1]), bfio=bool(v[2]), feat_buf=v[3],
+                       lstm={'needed': bool(v[4]), 'tile_cols': v[5], 'bf_wino': bool(v[6]), 'bf_hoist': bool(v[7])})
+    return out
+
+
 def load_model(model_path: str):
     """Resolve the reference's ``--model_path`` (a TF checkpoint prefix,
     ``demo_pipeline.py:63``): this repo's weight blob ``<model_path>.ukbbw`` if present, else the
