@@ -16,10 +16,22 @@ inline int device_cu_count() {
     const int d = current_device();
     return cu.get(d, [d] { hipDeviceProp_t p; return d >= 0 && hipGetDeviceProperties(&p, d) == hipSuccess ? p.multiProcessorCount : 0; }, 256);
 }
-// grant `kernel` `bytes` of dynamic LDS on the CURRENT device, once per device (`once`: one static per kernel instantiation)
+// grant `kernel` `bytes` of dynamic LDS on the CURRENT device, once per device.  The internal step of launch_lds(): nothing else calls it
 inline hipError_t allow_dynamic_lds(OncePerDevice &once, const void *kernel, int bytes) {
     return (hipError_t)once.run(current_device(), [&] {
         return (int)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); });
+}
+// Launch `Kernel` with `lds_bytes` of dynamic LDS.  A kernel that uses more than 64 KB must be granted it on every device it runs on;
+// the static that records the grant lives in this template, so every kernel instantiation owns its own by construction.  Every launch
+// with dynamic LDS goes through here, and no launcher declares a OncePerDevice of its own.
+// GRANT: the bytes to grant where one kernel is launched with several sizes (its largest, the same at every site); 0 = lds_bytes.
+template <auto Kernel, int GRANT = 0, class... Args>
+hipError_t launch_lds(dim3 grid, dim3 block, int lds_bytes, hipStream_t s, const Args &...args) {
+    static OncePerDevice granted;
+    const hipError_t e = allow_dynamic_lds(granted, reinterpret_cast<const void *>(Kernel), GRANT ? GRANT : lds_bytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, s, args...);
+    return hipGetLastError();
 }
 
 // prob / pred of train_network.py:198-199 (network_ao.py:159-160): prob = softmax(logits), pred = argmax(prob) -- the argmax
@@ -241,7 +253,7 @@ struct HeadArgs {
     const float *b_o0;       // [64]
     const float *w_o1;       // pack_rowmap_32x64(out1 rows 0..31) ++ pack_rowmap_32x64(out1 rows 32..63)
     const float *b_o1;       // [64]
-    const float *w_o0x3;     // optional (experiment UKBB_HEAD_X3): pack_head_x3(out0 rows 0..31, 32) -- three bf16 pieces per weight; may be null
+    const float *w_o0x3;     // optional (UKBB_PREC_F32X3): pack_head_x3(out0 rows 0..31, 32) -- three bf16 pieces per weight; may be null
     const float *w_o1x3;     // optional: pack_head_x3(out1, 64)
     const float *w_lg;       // pack_head_lg: [2][n_class][32]
     const float *b_lg;       // [n_class]

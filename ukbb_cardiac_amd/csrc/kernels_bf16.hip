@@ -231,21 +231,10 @@ hipError_t launch_conv16_pk(int cfg_id, const ConvArgs &a, hipStream_t s) {
     const long long cap = (long long)device_cu_count() * (per_cu < 1 ? 1 : per_cu);
     dim3 grid((unsigned)(ntiles < cap ? ntiles : cap));
     switch (cfg_id) {
-#define UKBB_PK16_CASE(ID, TH, TW)                                                              \
-    case ID: {                                                                                  \
-        auto k = conv16_logits_pk_kernel<TH, TW>;                                               \
-        static OncePerDevice lds_ok;                                                            \
-        {                                                                                       \
-            hipError_t e = allow_dynamic_lds(lds_ok, reinterpret_cast<const void *>(k), c->lds_bytes); \
-            if (e != hipSuccess) return e;                                                      \
-        }                                                                                       \
-        hipLaunchKernelGGL(k, grid, dim3(256), c->lds_bytes, s, a);                             \
-        break;                                                                                  \
-    }
+#define UKBB_PK16_CASE(ID, TH, TW) case ID: return launch_lds<conv16_logits_pk_kernel<TH, TW>>(grid, dim3(256), c->lds_bytes, s, a);
         UKBB_PK16_CONFIGS(UKBB_PK16_CASE)
         default: return hipErrorInvalidValue;
     }
-    return hipGetLastError();
 }
 
 }  // namespace ukbb

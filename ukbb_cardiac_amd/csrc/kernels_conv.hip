@@ -565,7 +565,7 @@ __global__ __launch_bounds__(512, WINO ? 4 : 2) void conv_pc_kernel(const ConvAr
     // r06: stride-2 halo rows are staged DE-INTERLEAVED -- even halo columns first (TW + 1 of them), then the odd ones -- so that the
     // consumers' B fragment of tap (kh, kw), whose 32 lanes are consecutive OUTPUT pixels, reads consecutive LDS slots (80 bytes
     // apart: the eight lanes of a ds_read_b128 group cover all 32 banks) instead of every second one (160 bytes apart: four bank
-    // quads, a 2-way conflict on every fragment read; profiles/r02_notes.md section 2).  UKBB_CONV_S2_INTERLEAVED=1 (environment, read per launch) keeps the old layout (A/B).
+    // quads, a 2-way conflict on every fragment read; profiles/r02_notes.md section 2).
     // Measured at N = 64 (r06, tools/ab_libs.sh, three alternating rounds on one box): conv2_0 66.7 -> 65.0 us, conv3_0 62.8 -> 61.1, conv4_0
     // 59.3 -> 58.0, but conv1_0 (ONE 16-channel chunk per item: the producers' LDS writes, which now alternate between the two halves
     // of a row, are its critical path, not the consumers' reads) 69.3 -> 71.0: the launcher picks DI for layers of more than one chunk.
@@ -1496,7 +1496,6 @@ hipError_t launch_conv(int cfg_id, const ConvArgs &a_in, hipStream_t s) {
     for (int i = 0; i < num_ws_configs(); ++i)
         if (ws_config(i).id == cfg_id) return launch_conv_ws(cfg_id, a_in, s);
     ConvArgs a = a_in;
-    const bool s2_interleaved = getenv("UKBB_CONV_S2_INTERLEAVED") != nullptr;     // A/B knob of the stride-2 halo layout (conv_pc_kernel DI)
 #ifdef UKBB_DIAG
     { const char *e = getenv("UKBB_CONV_DIAG"); a.diag = e ? atoi(e) : 0; }
     static unsigned long long *d_stamps = nullptr;
@@ -1556,94 +1555,42 @@ hipError_t launch_conv(int cfg_id, const ConvArgs &a_in, hipStream_t s) {
     dim3 grid((unsigned)(a.N * a.tiles_y * a.tiles_x), (unsigned)(a.Cout / group), 1);
     const long long nitems = (long long)a.N * a.tiles_y * a.tiles_x * (a.Cout / group);
     const int n_cu = device_cu_count();
+    // persistent grids of the producer/consumer kernels: one or two workgroups per CU as the LDS allows, never more than there are items
+    const int per_cu = c->lds_bytes * 2 <= 160 * 1024 ? 2 : 1;
+    const long long cap = (long long)n_cu * per_cu;
+    const dim3 pgrid((unsigned)(nitems < cap ? nitems : cap), 1, 1);
     switch (cfg_id) {
 #define UKBB_CFG_CASE(ID, KS, S, MB, TH, TW, KC, WM, WN, CB)                                    \
-    case ID: {                                                                                  \
-        auto k = conv_mfma_kernel<KS, S, MB, TH, TW, KC, WM, WN, CB>;                           \
-        static OncePerDevice lds_ok;                                                            \
-        {                                                                                       \
-            hipError_t e = allow_dynamic_lds(lds_ok, reinterpret_cast<const void *>(k), c->lds_bytes); \
-            if (e != hipSuccess) return e;                                                      \
-        }                                                                                       \
-        hipLaunchKernelGGL(k, grid, dim3(256), c->lds_bytes, s, a);                             \
-        break;                                                                                  \
-    }
+    case ID: return launch_lds<conv_mfma_kernel<KS, S, MB, TH, TW, KC, WM, WN, CB>>(grid, dim3(256), c->lds_bytes, s, a);
         UKBB_CONV_CONFIGS(UKBB_CFG_CASE)
+// stride-2 3x3 layers with more than one K chunk take the de-interleaved halo (conv_pc_kernel DI); a layer with Cin == KC the plain form
 #define UKBB_PC_CASE(ID, KS, S, MB, TH, TW, KC, WM, WN, CB)                                     \
-    case ID: {                                                                                  \
-        auto k = conv_pc_kernel<KS, S, MB, TH, TW, KC, WM, WN, CB>;                             \
-        if (S == 2 && KS == 3 && a.C0 + a.C1 > KC && !s2_interleaved) k = conv_pc_kernel<KS, S, MB, TH, TW, KC, WM, WN, CB, false, true>;   \
-        static OncePerDevice lds_ok;                                                            \
-        {                                                                                       \
-            hipError_t e = allow_dynamic_lds(lds_ok, reinterpret_cast<const void *>(k), c->lds_bytes); \
-            if (e != hipSuccess) return e;                                                      \
-        }                                                                                       \
-        const int per_cu = c->lds_bytes * 2 <= 160 * 1024 ? 2 : 1;                              \
-        const long long cap = (long long)n_cu * per_cu;                                         \
-        dim3 pgrid((unsigned)(nitems < cap ? nitems : cap), 1, 1);                              \
-        hipLaunchKernelGGL(k, pgrid, dim3(512), c->lds_bytes, s, a);                            \
-        break;                                                                                  \
-    }
+    case ID:                                                                                    \
+        if (S == 2 && KS == 3 && a.C0 + a.C1 > KC)                                              \
+            return launch_lds<conv_pc_kernel<KS, S, MB, TH, TW, KC, WM, WN, CB, false, true>>(pgrid, dim3(512), c->lds_bytes, s, a); \
+        return launch_lds<conv_pc_kernel<KS, S, MB, TH, TW, KC, WM, WN, CB>>(pgrid, dim3(512), c->lds_bytes, s, a);
         UKBB_PC_CONFIGS(UKBB_PC_CASE)
 // WINO: the Winograd consumers (tiling 134), whose output tile is the halo tile's centre: 3x3 stride 1 'SAME' only
 #define UKBB_PCF_CASE_W(ID, WINO, KS, S, MB, TH, TW, KC, WM, WN, CB)                             \
-    case ID: {                                                                                  \
-        auto k = conv_pc_kernel<KS, S, MB, TH, TW, KC, WM, WN, CB, true, false, WINO>;          \
-        static OncePerDevice lds_ok;                                                            \
-        {                                                                                       \
-            hipError_t e = allow_dynamic_lds(lds_ok, reinterpret_cast<const void *>(k), c->lds_bytes); \
-            if (e != hipSuccess) return e;                                                      \
-        }                                                                                       \
+    case ID:                                                                                    \
         if ((WINO) && (a.pad_y != 1 || a.pad_x != 1 || a.Ho != a.H || a.Wo != a.W)) return hipErrorInvalidValue; \
-        const int per_cu = c->lds_bytes * 2 <= 160 * 1024 ? 2 : 1;                              \
-        const long long cap = (long long)n_cu * per_cu;                                         \
-        dim3 pgrid((unsigned)(nitems < cap ? nitems : cap), 1, 1);                              \
-        hipLaunchKernelGGL(k, pgrid, dim3(512), c->lds_bytes, s, a);                            \
-        break;                                                                                  \
-    }
+        return launch_lds<conv_pc_kernel<KS, S, MB, TH, TW, KC, WM, WN, CB, true, false, WINO>>(pgrid, dim3(512), c->lds_bytes, s, a);
 #define UKBB_PCF_CASE(ID, ...) UKBB_PCF_CASE_W(ID, false, __VA_ARGS__)
         UKBB_PCF_CONFIGS(UKBB_PCF_CASE)
         UKBB_PCF_CASE_W(134, true, 3, 1, 16, 16, 16, 16, 1, 4, 1)
 #define UKBB_BF_CASE(ID, KS, S, TH, TW, WM, WN, CB)                                             \
-    case ID: {                                                                                  \
-        auto k = conv_mfma_kernel<KS, S, 32, TH, TW, 16, WM, WN, CB, true>;                     \
-        static OncePerDevice lds_ok;                                                            \
-        {                                                                                       \
-            hipError_t e = allow_dynamic_lds(lds_ok, reinterpret_cast<const void *>(k), c->lds_bytes); \
-            if (e != hipSuccess) return e;                                                      \
-        }                                                                                       \
-        hipLaunchKernelGGL(k, grid, dim3(256), c->lds_bytes, s, a);                             \
-        break;                                                                                  \
-    }
+    case ID: return launch_lds<conv_mfma_kernel<KS, S, 32, TH, TW, 16, WM, WN, CB, true>>(grid, dim3(256), c->lds_bytes, s, a);
         UKBB_BF_CONFIGS(UKBB_BF_CASE)
 #define UKBB_BFIO_CASE(ID, KS, S, TH, TW, WM, WN, CB)                                           \
-    case ID: {                                                                                  \
-        auto k = conv_mfma_kernel<KS, S, 32, TH, TW, 16, WM, WN, CB, true, true>;               \
-        static OncePerDevice lds_ok;                                                            \
-        {                                                                                       \
-            hipError_t e = allow_dynamic_lds(lds_ok, reinterpret_cast<const void *>(k), c->lds_bytes); \
-            if (e != hipSuccess) return e;                                                      \
-        }                                                                                       \
-        hipLaunchKernelGGL(k, grid, dim3(256), c->lds_bytes, s, a);                             \
-        break;                                                                                  \
-    }
+    case ID: return launch_lds<conv_mfma_kernel<KS, S, 32, TH, TW, 16, WM, WN, CB, true, true>>(grid, dim3(256), c->lds_bytes, s, a);
         UKBB_BFIO_CONFIGS(UKBB_BFIO_CASE)
 #define UKBB_BFIOF_CASE(ID, TH, TW, FUSE)                                                       \
-    case ID: {                                                                                  \
+    case ID:                                                                                    \
         if ((FUSE) == 1 ? (!a.first_w || !a.first_b) : (!a.lg_w || !a.lg_b || a.lg_ncls < 2 || a.lg_ncls > 4)) return hipErrorInvalidValue; \
-        auto k = conv_mfma_kernel<3, 1, 32, TH, TW, 16, 1, 4, 1, true, true, FUSE>;             \
-        static OncePerDevice lds_ok;                                                            \
-        {                                                                                       \
-            hipError_t e = allow_dynamic_lds(lds_ok, reinterpret_cast<const void *>(k), c->lds_bytes); \
-            if (e != hipSuccess) return e;                                                      \
-        }                                                                                       \
-        hipLaunchKernelGGL(k, grid, dim3(256), c->lds_bytes, s, a);                             \
-        break;                                                                                  \
-    }
+        return launch_lds<conv_mfma_kernel<3, 1, 32, TH, TW, 16, 1, 4, 1, true, true, FUSE>>(grid, dim3(256), c->lds_bytes, s, a);
         UKBB_BFIOF_CONFIGS(UKBB_BFIOF_CASE)
         default: return hipErrorInvalidValue;
     }
-    return hipGetLastError();
 }
 
 size_t pack_conv_weights(const float *w, int ks, int cin, int cout, int mb, int kc, int ncbl, float *dst) {

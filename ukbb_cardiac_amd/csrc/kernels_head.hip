@@ -44,16 +44,9 @@ __host__ __device__ __forceinline__ constexpr int rowmap(int r, int g) {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-#ifdef UKBB_NO_PACKED_F32
-// A/B form (r06): pairs of scalar v_fma_f32 instead of v_pk_fma_f32 (build with -fno-slp-vectorize as well, or
-// hipcc packs the gather's scalar FMAs again); tools/ab_packed.sh
-__device__ __forceinline__ float s_fma(float a, float b, float c) { float r; asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-__device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) { return f32x2{s_fma(a[0], b[0], c[0]), s_fma(a[1], b[1], c[1])}; }
-#else
 __device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) {
     f32x2 r; asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r;
 }
-#endif
 #define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 
 __device__ __forceinline__ f32x4 ldg4(const float *p) { return *reinterpret_cast<const f32x4 *>(p); }
@@ -318,11 +311,7 @@ hipError_t launch_sqg_multi(const SqgArgs lv[4], hipStream_t s) {
         m.nb[i] = (int)wg;
         total += m.nb[i];
     }
-    static const bool tr = [] { const char *e = getenv("UKBB_SQG_TR"); return e ? atoi(e) != 0 : true; }();
-    static const bool lt = [] { const char *e = getenv("UKBB_SQG_LT"); return e ? atoi(e) != 0 : true; }();
-    if (tr && lt) hipLaunchKernelGGL((sqg_multi_kernel<true, true>), dim3((unsigned)total), dim3(256), 0, s, m);
-    else if (tr) hipLaunchKernelGGL((sqg_multi_kernel<true, false>), dim3((unsigned)total), dim3(256), 0, s, m);
-    else hipLaunchKernelGGL((sqg_multi_kernel<false, false>), dim3((unsigned)total), dim3(256), 0, s, m);
+    hipLaunchKernelGGL((sqg_multi_kernel<true, true>), dim3((unsigned)total), dim3(256), 0, s, m);
     return hipGetLastError();
 }
 
@@ -342,10 +331,9 @@ hipError_t launch_sqg(const SqgArgs &a, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------
-// fcn_head_kernel: one workgroup = one 16x16 pixel tile (H, W are multiples of 16) =
-// 8 blocks of 32 pixels (two tile rows each), two blocks per wave.
+// The head works on 16x16 pixel tiles (H, W are multiples of 16) = 8 blocks of 32 pixels (two tile rows each).
 //
-// LDS holds the low-resolution windows of G_1..G_4 this tile's bilinear taps touch:
+// LDS holds the low-resolution windows of G_1..G_4 a tile's bilinear taps touch:
 // for level l (factor f = 2^l, pb = (f-1)/2) output row y reads source rows
 // i1 = (y+pb)>>l and i1-1, so a 16-row tile origin y0 needs rows (y0>>l)-1 .. (y0>>l)+((15+pb)>>l):
 // 9, 6, 4, 3 rows (and columns) for l = 1..4, i.e. 81+36+16+9 = 142 source pixels x 64 ch.
@@ -358,141 +346,6 @@ constexpr int GSTRIDE = 68;                            // floats per staged sour
 __host__ __device__ constexpr int win_n(int l) { return l == 1 ? 9 : l == 2 ? 6 : l == 3 ? 4 : 3; }
 __host__ __device__ constexpr int win_base(int l) { return l == 1 ? 0 : l == 2 ? 81 : l == 3 ? 117 : 133; }
 constexpr int GPIX = 142;
-constexpr int HEAD_LDS_FLOATS = GPIX * GSTRIDE;
-
-template <int NCLS, int OCC>
-__global__ __launch_bounds__(256, OCC) void fcn_head_kernel(const HeadArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float gl[];   // [GPIX][GSTRIDE]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int p = lane & 31, g = lane >> 5;
-    const int tiles_x = a.W / HT, tiles_y = a.H / HT;
-    int bid = blockIdx.x;
-    const int tx = bid % tiles_x; bid /= tiles_x;
-    const int ty = bid % tiles_y;
-    const int n = bid / tiles_y;
-    const int y0 = ty * HT, x0 = tx * HT;
-
-    // ---- stage the G windows (global NHWC -> LDS), 16 float4 per source pixel ---------
-    {
-        constexpr int NF4 = GPIX * 16, NIT = (NF4 + 255) / 256;
-        f32x4 v[NIT];
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int idx = it * 256 + tid;
-            const int sp = idx >> 4, c4 = idx & 15;
-            f32x4 t = {0.f, 0.f, 0.f, 0.f};
-            if (sp < GPIX) {
-                const int l = sp < 81 ? 1 : sp < 117 ? 2 : sp < 133 ? 3 : 4;
-                const int wn_ = win_n(l), rel = sp - win_base(l);
-                const int ry = rel / wn_, rx = rel - ry * wn_;
-                const int hl = a.H >> l, wl = a.W >> l;
-                const int sy = (y0 >> l) - 1 + ry, sx = (x0 >> l) - 1 + rx;
-                if ((unsigned)sy < (unsigned)hl && (unsigned)sx < (unsigned)wl)
-                    t = ldg4(a.G[l - 1] + (((size_t)n * hl + sy) * wl + sx) * 64 + 4 * c4);
-            }
-            v[it] = t;
-        }
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int idx = it * 256 + tid;
-            const int sp = idx >> 4, c4 = idx & 15;
-            if (sp < GPIX) *reinterpret_cast<f32x4 *>(gl + sp * GSTRIDE + 4 * c4) = v[it];
-        }
-    }
-    __syncthreads();
-
-#pragma unroll 1
-    for (int bb = 0; bb < 2; ++bb) {
-        const int blk = wave * 2 + bb;                        // tile rows 2*blk, 2*blk+1
-        const int yl = 2 * blk + (p >> 4), xl = p & 15;
-        const int y = y0 + yl, x = x0 + xl;
-        const size_t q = ((size_t)n * a.H + y) * a.W + x;
-
-        // ---- out0 = bias + sum_l up_l(G_l) [<= 2x2 taps per level, from LDS] + W0_0[64][32] * S -------
-        f32x16 P0 = bias_tile(a.b_o0, g), P1 = bias_tile(a.b_o0 + 32, g);
-#pragma unroll
-        for (int l = 1; l <= 4; ++l) {
-            const int f = 1 << l, pb = (f - 1) >> 1;
-            const float inv = 1.0f / (float)f;
-            const int tyy = yl + pb, txx = xl + pb;           // tile-relative: (y0 >> l) cancels
-            const int ry1 = (tyy >> l) + 1, rx1 = (txx >> l) + 1;   // window index (row 0 = source row (y0>>l)-1)
-            const int jy = tyy & (f - 1), jx = txx & (f - 1);
-            const float wy1 = (float)(jy + 1) * inv, wy0 = (float)(f - 1 - jy) * inv;
-            const float wx1 = (float)(jx + 1) * inv, wx0 = (float)(f - 1 - jx) * inv;
-            const int wn_ = win_n(l);
-            const float *b11 = gl + (win_base(l) + ry1 * wn_ + rx1) * GSTRIDE + 4 * g;
-            const float *b10 = b11 - GSTRIDE, *b01 = b11 - wn_ * GSTRIDE, *b00 = b01 - GSTRIDE;
-            const float w00 = wy0 * wx0, w01 = wy0 * wx1, w10 = wy1 * wx0, w11 = wy1 * wx1;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const f32x4 a00 = *reinterpret_cast<const f32x4 *>(b00 + 8 * j), a01 = *reinterpret_cast<const f32x4 *>(b01 + 8 * j);
-                const f32x4 a10 = *reinterpret_cast<const f32x4 *>(b10 + 8 * j), a11 = *reinterpret_cast<const f32x4 *>(b11 + 8 * j);
-                const f32x4 c00 = *reinterpret_cast<const f32x4 *>(b00 + 32 + 8 * j), c01 = *reinterpret_cast<const f32x4 *>(b01 + 32 + 8 * j);
-                const f32x4 c10 = *reinterpret_cast<const f32x4 *>(b10 + 32 + 8 * j), c11 = *reinterpret_cast<const f32x4 *>(b11 + 32 + 8 * j);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    P0[4 * j + i] = fmaf(w00, a00[i], fmaf(w01, a01[i], fmaf(w10, a10[i], fmaf(w11, a11[i], P0[4 * j + i]))));
-                    P1[4 * j + i] = fmaf(w00, c00[i], fmaf(w01, c01[i], fmaf(w10, c10[i], fmaf(w11, c11[i], P1[4 * j + i]))));
-                }
-            }
-        }
-        // ---- same_dim0: S[32][px] = Ws0[32][16] * conv0[16][px] -----------------------------
-        f32x16 S = bias_tile(a.b_s0, g);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const f32x4 xv = ldg4(a.conv0 + q * 16 + 8 * j + 4 * g);
-            const f32x4 wv = ldg4(a.w_s0 + (j * 64 + lane) * 4);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) S = MFMA32(wv[i], xv[i], S);
-        }
-        relu16(S);
-        chain_32to64(a.w_o0, lane, S, P0, P1);
-        relu16(P0);
-        relu16(P1);
-        // ---- out1: Q[64][px] = b1 + W1[64][64] * X[64][px] ------------------------------------------------
-        f32x16 Q0 = bias_tile(a.b_o1, g), Q1 = bias_tile(a.b_o1 + 32, g);
-        chain_32to64(a.w_o1, lane, P0, Q0, Q1);               // k rows 0..31
-        chain_32to64(a.w_o1 + 2 * 4 * 64 * 4, lane, P1, Q0, Q1);   // k rows 32..63
-        relu16(Q0);
-        relu16(Q1);
-        // ---- logits on the vector ALU: each lane holds 32 of the 64 channels --------------------------
-        // w_lg layout: [g][c][32] with index cb*16 + r  <->  channel cb*32 + rowmap(r, g)
-        float lg[NCLS];
-#pragma unroll
-        for (int c = 0; c < NCLS; ++c) {
-            const float *wp = a.w_lg + (g * NCLS + c) * 32;
-            float s = 0.f;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const f32x4 w = ldg4(wp + 4 * j);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) s = fmaf(w[i], Q0[4 * j + i], s);
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const f32x4 w = ldg4(wp + 16 + 4 * j);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) s = fmaf(w[i], Q1[4 * j + i], s);
-            }
-            // both halves form (lower + upper) in the SAME order -> identical bits
-            const float other = __shfl_xor(s, 32);
-            lg[c] = (g == 0 ? s + other : other + s) + a.b_lg[c];
-        }
-        if (g == 0) {
-            if (a.logits) {
-#pragma unroll
-                for (int c = 0; c < NCLS; ++c) a.logits[q * NCLS + c] = lg[c];
-            }
-            float pr[NCLS];
-            const int best = softmax_argmax_opt<NCLS>(lg, a.prob != nullptr, pr);
-            if (a.pred) a.pred[q] = best;
-            if (a.prob) {
-#pragma unroll
-                for (int c = 0; c < NCLS; ++c) a.prob[q * NCLS + c] = pr[c];
-            }
-        }
-    }
-}
 
 #ifdef UKBB_DIAG
 __device__ unsigned long long g_hstamps[16];
@@ -510,9 +363,9 @@ __device__ unsigned long long g_hstamps[16];
 // r08: the producers evaluate the bilinear taps separably with channels on the lanes (x once per window row, y per output row with
 // compile-time weights), so a stage is eight contiguous tile rows and consumer wave w takes block 4 * (stage & 1) + w; the
 // r02-r07 direct 2-D gather (one pixel per lane, blocks 2 w + (stage & 1)) is the DG instance (UKBB_HEAD_DIRECT_GATHER=1).
-// r01 measurements behind this split: in the single-role kernel the gather (VALU+LDS), the G
-// staging and the MFMA chains simply added up (ablation: 76 + 63 + 40%..) because every wave
-// ran them back to back and at most 3 waves fit per SIMD.
+// r01 measurements behind this split: in the single-role kernel (one workgroup per tile, every wave both roles; since removed,
+// its numbers are in profiles/r01_notes.md) the gather (VALU+LDS), the G staging and the MFMA chains simply added up (ablation:
+// 76 + 63 + 40%..) because every wave ran them back to back and at most 3 waves fit per SIMD.
 // ---------------------------------------------------------------------------
 constexpr int PX_WAVE = 8 * 64 * 4;                    // floats of one handed-over tile (64 ch x 32 px)
 // LDS map of fcn_head_pc_kernel (floats)
@@ -896,15 +749,12 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
         // window coordinates and byte offsets are computed once, validity is one and/compare against a
         // per-tile row|column mask, and taps outside the map are buffer loads with an out-of-range
         // offset (the hardware returns 0, border taps are dropped).
-#ifndef UKBB_HEAD_RECOMPUTE_WINDOW_CONSTS
-#define UKBB_HEAD_RECOMPUTE_WINDOW_CONSTS 0
-#endif
-        // r05 experiment (-DUKBB_HEAD_RECOMPUTE_WINDOW_CONSTS=1): the 14 per-thread window constants recomputed inside g_load (once per
-        // tile) instead of living in registers across the stage loop -- removes the 2 spilled VGPRs of the 168-register budget
+        // The 14 per-thread window constants, evaluated once and kept in registers across the stage loop (recomputing them per tile freed the
+        // 2 spilled VGPRs and cost 10 % of the head: profiles/r05_notes.md).  A lambda with its own sp32: written in line, hipcc orders two
+        // instruction pairs of the fp32 instances differently from the code that was measured.
         unsigned tbit[NIT], goff[NIT];
         auto window_consts = [&]() {
-        int sp32 = tid >> 4;                            // shadows the outer one: opaque to the optimiser in the recompute form, so that it is not hoisted back
-        if (UKBB_HEAD_RECOMPUTE_WINDOW_CONSTS) asm volatile("" : "+v"(sp32));
+        int sp32 = tid >> 4;
         unroll_n<NIT>([&](auto ic) {
             constexpr int it = decltype(ic)::value;
             constexpr int l = it < 3 ? 1 : it < 5 ? 2 : it < 6 ? 3 : 4;
@@ -916,9 +766,8 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
             goff[it] = (unsigned)((ry * (a.W >> l) + rx) * 64 + 4 * c4) * 4u;
         });
         };
-        if (!UKBB_HEAD_RECOMPUTE_WINDOW_CONSTS) window_consts();
+        window_consts();
         auto g_load = [&](int k) {                      // G windows of this workgroup's k-th tile -> registers
-            if (UKBB_HEAD_RECOMPUTE_WINDOW_CONSTS) window_consts();
             int bid = blockIdx.x + k * gridDim.x;
             const int tx = bid % tiles_x; bid /= tiles_x;
             const int ty = bid % tiles_y;
@@ -1310,37 +1159,28 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
     }
 }
 
-// One function per kernel instantiation, so that each owns the static that records its dynamic-LDS grant (kernels.h, allow_dynamic_lds)
-template <int NC, bool X3, bool DG, bool IT>
-static hipError_t launch_head_pc_inst(const HeadArgs &a, dim3 grid, size_t lds_bytes, hipStream_t s) {
-    static OncePerDevice lds_ok;
-    const hipError_t e = allow_dynamic_lds(lds_ok, reinterpret_cast<const void *>(fcn_head_pc_kernel<NC, X3, DG, IT>), (int)lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((fcn_head_pc_kernel<NC, X3, DG, IT>), grid, dim3(768), lds_bytes, s, a);
-    return hipGetLastError();
-}
-
 static std::atomic<int> g_head_tail_form{-1};
 int head_tail_form() { return g_head_tail_form.load(std::memory_order_relaxed); }
 
 template <int NC>
 static hipError_t launch_head_pc_nc(const HeadArgs &a, dim3 grid, hipStream_t s) {
-    static const bool x3_env = [] { const char *e = getenv("UKBB_HEAD_X3"); return e && atoi(e) != 0; }();   // A/B knob
     static const bool dg = [] { const char *e = getenv("UKBB_HEAD_DIRECT_GATHER"); return e && atoi(e) != 0; }();   // A/B knob (r08)
     static const bool inline_tail = [] { const char *e = getenv("UKBB_HEAD_INLINE_TAIL"); return e && atoi(e) != 0; }();   // A/B knob (r11)
-    if ((a.x3 || x3_env) && a.w_o1x3 && a.w_o0x3) {     // UKBB_PREC_F32X3; its tail stays in the stage (profiles/r11_notes.md)
-        const size_t ldsx = HEADPC_X3_LDS_FLOATS * sizeof(float);
+#define UKBB_HEAD_GO(X3, DG, IT, BYTES) launch_lds<fcn_head_pc_kernel<NC, X3, DG, IT>>(grid, dim3(768), BYTES, s, a)
+    if (a.x3 && a.w_o1x3 && a.w_o0x3) {                 // UKBB_PREC_F32X3; its tail stays in the stage (profiles/r11_notes.md)
+        constexpr int ldsx = HEADPC_X3_LDS_FLOATS * 4;
         g_head_tail_form.store(1, std::memory_order_relaxed);
-        return dg ? launch_head_pc_inst<NC, true, true, true>(a, grid, ldsx, s) : launch_head_pc_inst<NC, true, false, true>(a, grid, ldsx, s);
+        return dg ? UKBB_HEAD_GO(true, true, true, ldsx) : UKBB_HEAD_GO(true, false, true, ldsx);
     }
-    const size_t lds = HEADPC_LDS_FLOATS * sizeof(float);
+    constexpr int lds = HEADPC_LDS_FLOATS * 4;
     bool it = inline_tail;
 #ifdef UKBB_DIAG
     if (a.diag & 6) it = true;                          // ablation bits 2 and 4 exist in the in-stage loop only
 #endif
     g_head_tail_form.store(dg || it ? 1 : 0, std::memory_order_relaxed);
-    if (dg) return launch_head_pc_inst<NC, false, true, true>(a, grid, lds, s);
-    return it ? launch_head_pc_inst<NC, false, false, true>(a, grid, lds, s) : launch_head_pc_inst<NC, false, false, false>(a, grid, lds, s);
+    if (dg) return UKBB_HEAD_GO(false, true, true, lds);
+    return it ? UKBB_HEAD_GO(false, false, true, lds) : UKBB_HEAD_GO(false, false, false, lds);
+#undef UKBB_HEAD_GO
 }
 
 static hipError_t launch_head_pc(const HeadArgs &a, hipStream_t s) {
@@ -1357,30 +1197,14 @@ static hipError_t launch_head_pc(const HeadArgs &a, hipStream_t s) {
     }
 }
 
-template <int OCC>
-static hipError_t launch_head_occ(const HeadArgs &a, hipStream_t s) {
-    dim3 grid((unsigned)(a.N * (a.H / HT) * (a.W / HT))), block(256);
-    const size_t lds = HEAD_LDS_FLOATS * sizeof(float);
-    switch (a.n_class) {
-        case 2: hipLaunchKernelGGL((fcn_head_kernel<2, OCC>), grid, block, lds, s, a); break;
-        case 3: hipLaunchKernelGGL((fcn_head_kernel<3, OCC>), grid, block, lds, s, a); break;
-        case 4: hipLaunchKernelGGL((fcn_head_kernel<4, OCC>), grid, block, lds, s, a); break;
-        case 5: hipLaunchKernelGGL((fcn_head_kernel<5, OCC>), grid, block, lds, s, a); break;
-        case 6: hipLaunchKernelGGL((fcn_head_kernel<6, OCC>), grid, block, lds, s, a); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
 hipError_t launch_head(const HeadArgs &a_in, hipStream_t s) {
     HeadArgs a = a_in;
 #ifdef UKBB_DIAG
     { const char *e = getenv("UKBB_HEAD_DIAG"); a.diag = e ? atoi(e) : 0; }
 #endif
     if ((a.H % HT) || (a.W % HT)) return hipErrorInvalidValue;
-    static const int use_pc = [] { const char *e = getenv("UKBB_HEAD_PC"); return e ? atoi(e) : 1; }();   // A/B knob
 #ifdef UKBB_DIAG
-    if (use_pc && getenv("UKBB_HEAD_STAMPS")) {        // the 6th stamped launch reports the MFMA waves' stage budget
+    if (getenv("UKBB_HEAD_STAMPS")) {        // the 6th stamped launch reports the MFMA waves' stage budget
         static int shots = 0;
         unsigned long long z[16] = {0};
         a.diag |= 64;
@@ -1402,12 +1226,7 @@ hipError_t launch_head(const HeadArgs &a_in, hipStream_t s) {
         return e;
     }
 #endif
-    if (use_pc) return launch_head_pc(a, s);
-    const HeadArgs &b = a;
-    static const int occ = [] { const char *e = getenv("UKBB_HEAD_OCC"); return e ? atoi(e) : 3; }();   // tuning knob
-    if (occ == 2) return launch_head_occ<2>(b, s);
-    if (occ == 4) return launch_head_occ<4>(b, s);
-    return launch_head_occ<3>(b, s);
+    return launch_head_pc(a, s);
 }
 
 // ---- host-side weight packers (k order documented at the top) ---------------

@@ -811,13 +811,12 @@ static __global__ __launch_bounds__(256) void poison_lds_kernel(unsigned pattern
     __syncthreads();
     if (sink && pl_lds[(threadIdx.x * 97) % dwords] != pattern) sink[0] = 1;     // keeps the stores alive
 }
+constexpr int POISON_MAX_BYTES = 160 * 1024;      // granted whichever of the two entry points launches first
 int ukbb_fcn_debug_poison_lds(uint32_t pattern, void *stream) {
-    constexpr int bytes = 160 * 1024;
-    static OncePerDevice ok;
-    if (allow_dynamic_lds(ok, reinterpret_cast<const void *>(poison_lds_kernel), bytes) != hipSuccess) { set_error("poison_lds: cannot get 160 KB of LDS"); return UKBB_EDEVICE; }
-    hipLaunchKernelGGL(poison_lds_kernel, dim3((unsigned)(device_cu_count() * 4)), dim3(256), bytes, (hipStream_t)stream, pattern, bytes / 4, (unsigned *)nullptr);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("poison_lds: launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
+    constexpr int bytes = POISON_MAX_BYTES;
+    const hipError_t e = launch_lds<poison_lds_kernel, POISON_MAX_BYTES>(dim3((unsigned)(device_cu_count() * 4)), dim3(256), bytes, (hipStream_t)stream,
+                                                                         pattern, bytes / 4, (unsigned *)nullptr);
+    if (e != hipSuccess) { set_error("poison_lds: 160 KB of LDS not granted, or the launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
     return UKBB_OK;
 }
 
@@ -835,11 +834,9 @@ int ukbb_fcn_debug_fence_kernel(void *stream) {
 
 // the same with a chosen LDS footprint per block (co-resident with other kernels' workgroups: a kernel that uses LDS beyond what it asked for reads this)
 int ukbb_fcn_debug_poison_lds_sized(uint32_t pattern, int bytes, int blocks, void *stream) {
-    if (bytes < 1024 || bytes > 160 * 1024 || blocks < 1) return UKBB_EINVAL;
-    static OncePerDevice ok;
-    if (allow_dynamic_lds(ok, reinterpret_cast<const void *>(poison_lds_kernel), 160 * 1024) != hipSuccess) return UKBB_EDEVICE;
-    hipLaunchKernelGGL(poison_lds_kernel, dim3((unsigned)blocks), dim3(256), bytes, (hipStream_t)stream, pattern, bytes / 4, (unsigned *)nullptr);
-    return hipGetLastError() == hipSuccess ? UKBB_OK : UKBB_EDEVICE;
+    if (bytes < 1024 || bytes > POISON_MAX_BYTES || blocks < 1) return UKBB_EINVAL;
+    return launch_lds<poison_lds_kernel, POISON_MAX_BYTES>(dim3((unsigned)blocks), dim3(256), bytes, (hipStream_t)stream, pattern, bytes / 4, (unsigned *)nullptr) == hipSuccess
+               ? UKBB_OK : UKBB_EDEVICE;
 }
 
 int ukbb_fcn_synth_volume(uint64_t seed, size_t n, float *d_out, void *stream) {

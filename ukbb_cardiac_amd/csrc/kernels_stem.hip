@@ -288,17 +288,11 @@ hipError_t launch_unet_stem(const StemArgs &a, hipStream_t s) {
     const int cus = device_cu_count();
     const long long want = (ntiles + NW - 1) / NW;
     // two workgroups per CU (240 registers, 57 KB of LDS each): two waves per SIMD cover each other's non-MFMA phases (101 -> 78 us at N = 100; r04)
-    static const int per_cu = getenv("UKBB_STEM_WGS_PER_CU") ? atoi(getenv("UKBB_STEM_WGS_PER_CU")) : 2;   // A/B knob
-    const long long cap = (long long)cus * (per_cu > 0 ? per_cu : 1);
+    const long long cap = (long long)cus * 2;
     const int grid = (int)(want < cap ? want : cap);
     constexpr int bytes = NW * st_wave_bytes(R);
     static_assert(bytes <= 160 * 1024, "LDS");
-    auto k = unet_stem_kernel<R, NW>;
-    static OncePerDevice lds_ok;
-    hipError_t e = allow_dynamic_lds(lds_ok, reinterpret_cast<const void *>(k), bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(NW * 64), bytes, s, a);
-    return hipGetLastError();
+    return launch_lds<unet_stem_kernel<R, NW>>(dim3((unsigned)grid), dim3(NW * 64), bytes, s, a);
 }
 
 }  // namespace ukbb

@@ -510,19 +510,12 @@ hipError_t launch_unet_tail(const TailArgs &a_in, hipStream_t s) {
         }
     } dump{stamp, s, d_st, grid * NW > 4096 ? 4096 : grid * NW};
 #endif
-    auto go = [&](auto k, OncePerDevice &lds_ok) -> hipError_t {
-        hipError_t e = allow_dynamic_lds(lds_ok, reinterpret_cast<const void *>(k), bytes);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(NW * 64), bytes, s, a);
-        return hipGetLastError();
-    };
+    const dim3 g((unsigned)grid), b(NW * 64);
+#define UKBB_TAIL_GO(NC, FULL, STRIPS) launch_lds<unet_tail_kernel<R, NW, NB, NC, FULL, STRIPS>>(g, b, bytes, s, a)
 #define UKBB_TAIL_CASE(NC)                                                                         \
-    case NC: {                                                                                     \
-        static OncePerDevice ok_full, ok_pred;                                                     \
-        static OncePerDevice ok_full_s, ok_pred_s;                                                 \
-        if (strips) return full ? go(unet_tail_kernel<R, NW, NB, NC, true, true>, ok_full_s) : go(unet_tail_kernel<R, NW, NB, NC, false, true>, ok_pred_s); \
-        return full ? go(unet_tail_kernel<R, NW, NB, NC, true>, ok_full) : go(unet_tail_kernel<R, NW, NB, NC, false>, ok_pred); \
-    }
+    case NC:                                                                                       \
+        if (strips) return full ? UKBB_TAIL_GO(NC, true, true) : UKBB_TAIL_GO(NC, false, true);    \
+        return full ? UKBB_TAIL_GO(NC, true, false) : UKBB_TAIL_GO(NC, false, false);
     switch (a.ncls) {
         UKBB_TAIL_CASE(2)
         UKBB_TAIL_CASE(3)

@@ -92,21 +92,10 @@ __device__ __forceinline__ void st1_s(float *p, float v) {
 }
 __device__ __forceinline__ void st4(float *p, const f32x4 &v) { *reinterpret_cast<f32x4 *>(p) = v; }
 
-#ifdef UKBB_NO_PACKED_F32
-// A/B form (r06): the same arithmetic as pairs of scalar VALU instructions -- the guide prices a packed f32 op
-// beside MFMAs above two scalar ones; tools/ab_packed.sh measures it next to the fp32 MFMA streams of these kernels.
-__device__ __forceinline__ float s_add(float a, float b) { float r; asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ float s_sub(float a, float b) { float r; asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ float s_fma(float a, float b, float c) { float r; asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-__device__ __forceinline__ f32x2 pk_add(f32x2 a, f32x2 b) { return f32x2{s_add(a[0], b[0]), s_add(a[1], b[1])}; }
-__device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) { return f32x2{s_sub(a[0], b[0]), s_sub(a[1], b[1])}; }
-__device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 s, f32x2 b) { return f32x2{s_fma(a[0], s[0], b[0]), s_fma(a[1], s[1], b[1])}; }
-#else
 __device__ __forceinline__ f32x2 pk_add(f32x2 a, f32x2 b) { f32x2 r; asm("v_pk_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) { f32x2 r; asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b)); return r; }
 // a * s + b with a scalar factor in both halves (v_pk_fma_f32; the factor is splat into a register pair by the caller)
 __device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 s, f32x2 b) { f32x2 r; asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(s), "v"(b)); return r; }
-#endif
 
 struct V4 { f32x2 lo, hi; };                           // four channels as two packed pairs
 __device__ __forceinline__ V4 operator+(const V4 &a, const V4 &b) { return V4{pk_add(a.lo, b.lo), pk_add(a.hi, b.hi)}; }
@@ -687,9 +676,6 @@ template <int TBW, bool PAIR, int NCB>
 static hipError_t launch_wino24_t(const ConvArgs &a, hipStream_t s) {
     using G = W24<TBW, PAIR>;
     const int n_cu = device_cu_count();
-    static OncePerDevice lds_ok;
-    hipError_t e = allow_dynamic_lds(lds_ok, reinterpret_cast<const void *>(wino24_pc_kernel<TBW, PAIR, NCB>), G::LDS_FLOATS * 4);
-    if (e != hipSuccess) return e;
     const int regs_x = (a.Wo + 4 * G::TRX - 1) / (4 * G::TRX);
     const long long per_image_or_pair = PAIR ? (long long)(2 * (a.Ho / 8) + 1) * ((a.N + 1) / 2) : (long long)((a.Ho + 2 * TRY - 1) / (2 * TRY)) * a.N;
     const long long nitems = per_image_or_pair * regs_x * (a.Cout / (16 * NCB));
@@ -699,7 +685,7 @@ static hipError_t launch_wino24_t(const ConvArgs &a, hipStream_t s) {
     unsigned long long z[8] = {0};
     if (on) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_w24stamps), z, 64);
 #endif
-    hipLaunchKernelGGL((wino24_pc_kernel<TBW, PAIR, NCB>), grid, dim3(512), G::LDS_FLOATS * 4, s, a);
+    const hipError_t e = launch_lds<wino24_pc_kernel<TBW, PAIR, NCB>>(grid, dim3(512), G::LDS_FLOATS * 4, s, a);
 #ifdef UKBB_WINO_STAMPS
     if (on) {
         unsigned long long h[8];
@@ -710,7 +696,7 @@ static hipError_t launch_wino24_t(const ConvArgs &a, hipStream_t s) {
                 h[4] / st, h[5] / st, h[6] / st, st / grid.x);
     }
 #endif
-    return hipGetLastError();
+    return e;
 }
 
 // tile_cols: 32 | 16 (regions of 8 x 32 / 8 x 16 pixels); pair: images in pairs with seam regions (16 only, Ho % 8 == 4); ncb: 4 | 2 (2: tile_cols 32)
@@ -726,9 +712,6 @@ template <int TBW, int LS, bool BF>
 static hipError_t launch_wino24_lstm_t(const ConvArgs &a, hipStream_t s) {
     using G = W24<TBW, false>;
     const int n_cu = device_cu_count();
-    static OncePerDevice lds_ok;
-    hipError_t e = allow_dynamic_lds(lds_ok, reinterpret_cast<const void *>(wino24_pc_kernel<TBW, false, 4, LS, BF>), G::LDS_FLOATS * 4);
-    if (e != hipSuccess) return e;
     const int regs_x = (a.Wo + 4 * G::TRX - 1) / (4 * G::TRX);
     const long long nitems = (long long)((a.Ho + 2 * TRY - 1) / (2 * TRY)) * a.N * regs_x * (a.Cout / 64);
     dim3 grid((unsigned)(nitems < n_cu ? nitems : n_cu));
@@ -737,7 +720,7 @@ static hipError_t launch_wino24_lstm_t(const ConvArgs &a, hipStream_t s) {
     unsigned long long z[16] = {0};
     if (on) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_w24stamps), z, 128);
 #endif
-    hipLaunchKernelGGL((wino24_pc_kernel<TBW, false, 4, LS, BF>), grid, dim3(512), G::LDS_FLOATS * 4, s, a);
+    const hipError_t e = launch_lds<wino24_pc_kernel<TBW, false, 4, LS, BF>>(grid, dim3(512), G::LDS_FLOATS * 4, s, a);
 #ifdef UKBB_WINO_STAMPS
     if (on) {
         unsigned long long h[16];
@@ -748,7 +731,7 @@ static hipError_t launch_wino24_lstm_t(const ConvArgs &a, hipStream_t s) {
                 h[4] / st, h[5] / st, h[6] / st, h[8] / st, h[9] / st, h[10] / st, (h[6] - h[8] - h[9] - h[10]) / st, st / grid.x);
     }
 #endif
-    return hipGetLastError();
+    return e;
 }
 
 hipError_t launch_wino24_lstm(const ConvArgs &a, int tile_cols, hipStream_t s) {

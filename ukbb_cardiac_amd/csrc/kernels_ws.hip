@@ -976,21 +976,11 @@ int ws_lds_bytes_for(const ConvConfig &c, int cin) {
 }
 
 namespace {
-template <class K>
-hipError_t launch_ws_kernel(K k, int bytes, int threads, const ConvArgs &a, int grid, hipStream_t s, OncePerDevice &lds_ok) {
-    hipError_t e = allow_dynamic_lds(lds_ok, reinterpret_cast<const void *>(k), bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(threads), bytes, s, a);
-    return hipGetLastError();
-}
 template <int R, int CB, int NW, int NCH, bool TWO>
 hipError_t launch_ws_one(const ConvArgs &a, int grid, hipStream_t s) {
     constexpr int bytes = ws_lds_bytes(0, R, CB, NW, NCH);
     if constexpr (bytes > 160 * 1024) { return hipErrorInvalidValue; }
-    else {
-        static OncePerDevice lds_ok;
-        return launch_ws_kernel(conv_ws_kernel<R, CB, NW, NCH, TWO>, bytes, NW * 64, a, grid, s, lds_ok);
-    }
+    else return launch_lds<conv_ws_kernel<R, CB, NW, NCH, TWO>>(dim3((unsigned)grid), dim3(NW * 64), bytes, s, a);
 }
 template <int R, int CB, int NW>
 hipError_t launch_ws_cfg(const ConvArgs &a, int grid, hipStream_t s) {
@@ -1010,24 +1000,19 @@ hipError_t launch_wr_cfg(const ConvArgs &a, int grid, hipStream_t s) {
     if (nch < 2 || (nch & 1) || (a.C1 && (a.C0 / 16) % 2)) return hipErrorInvalidValue;   // two chunks per loop body; a source switch at an even chunk
     constexpr int bytes = 2 * CB * 9 * 1024 + NW * 2 * ws_stage_bytes(0, R);
     static_assert(bytes <= 160 * 1024, "LDS");
-    static OncePerDevice lds_ok;
-    return launch_ws_kernel(conv_wr_kernel<R, CB, NW>, bytes, NW * 64, a, grid, s, lds_ok);
+    return launch_lds<conv_wr_kernel<R, CB, NW>>(dim3((unsigned)grid), dim3(NW * 64), bytes, s, a);
 }
 template <int R, int NW>
 hipError_t launch_wsl_cfg(const ConvArgs &a, int grid, hipStream_t s) {
     if (a.C0 != 16 || a.C1 || a.Cout != 32 || a.cout_store != 16 || !a.lg_w || !a.lg_b || a.lg_ncls < 2 || a.lg_ncls > 4) return hipErrorInvalidValue;
     constexpr int bytes = ws_lds_bytes(0, R, 1, NW, 1);
-    static OncePerDevice lds_ok;
-    return launch_ws_kernel(conv_ws_kernel<R, 1, NW, 1, false, true>, bytes, NW * 64, a, grid, s, lds_ok);
+    return launch_lds<conv_ws_kernel<R, 1, NW, 1, false, true>>(dim3((unsigned)grid), dim3(NW * 64), bytes, s, a);
 }
 template <int R, int NW, int NCH, bool C16>
 hipError_t launch_wst_one(const ConvArgs &a, int grid, hipStream_t s) {
     constexpr int bytes = ws_lds_bytes(1, R, 2, NW, NCH);
     if constexpr (bytes > 160 * 1024) { return hipErrorInvalidValue; }
-    else {
-        static OncePerDevice lds_ok;
-        return launch_ws_kernel(tconv_ws_kernel<R, NW, NCH, C16>, bytes, NW * 64, a, grid, s, lds_ok);
-    }
+    else return launch_lds<tconv_ws_kernel<R, NW, NCH, C16>>(dim3((unsigned)grid), dim3(NW * 64), bytes, s, a);
 }
 template <int R, int NW>
 hipError_t launch_wst_cfg(const ConvArgs &a, int grid, hipStream_t s) {
@@ -1071,10 +1056,10 @@ hipError_t launch_lstm_ws(const ConvArgs &a_in, hipStream_t s) {
     if (want < grid) grid = (int)((want + nG - 1) / nG * nG);
     constexpr int bytes = ws_lds_bytes(0, LSW_R, 2, LSW_NW, 1), bytes3 = ws_lds_bytes(0, LSW_R, 2, LSW_NW, 2);
     static_assert(bytes <= 160 * 1024 && 2 * bytes3 <= 160 * 1024, "LDS (two workgroups per CU)");
-    static OncePerDevice ok1, ok2, ok3;
-    if (a.ls_mode == 1) return launch_ws_kernel(lstm_ws_kernel<LSW_R, LSW_NW, 1>, bytes, LSW_NW * 64, a, grid, s, ok1);
-    if (a.ls_mode == 3) return launch_ws_kernel(lstm_ws_kernel<LSW_R, LSW_NW, 3>, bytes3, LSW_NW * 64, a, grid, s, ok3);
-    return launch_ws_kernel(lstm_ws_kernel<LSW_R, LSW_NW, 2>, bytes, LSW_NW * 64, a, grid, s, ok2);
+    const dim3 g((unsigned)grid), b(LSW_NW * 64);
+    if (a.ls_mode == 1) return launch_lds<lstm_ws_kernel<LSW_R, LSW_NW, 1>>(g, b, bytes, s, a);
+    if (a.ls_mode == 3) return launch_lds<lstm_ws_kernel<LSW_R, LSW_NW, 3>>(g, b, bytes3, s, a);
+    return launch_lds<lstm_ws_kernel<LSW_R, LSW_NW, 2>>(g, b, bytes, s, a);
 }
 
 size_t pack_lstm_gate_weights_bf16_xh(const float *w, const float *bias, float *dst, float *bias_perm) {
@@ -1131,8 +1116,7 @@ hipError_t launch_conv_ws(int cfg_id, const ConvArgs &a_in, hipStream_t s) {
     const int nG = a.Cout / (32 * c->cb);
     const long long ntiles = (long long)a.N * a.tiles_y * a.tiles_x;
     // one workgroup per CU; a multiple of 8 nG where the chip allows it (XCD-aware walker mapping), never more walkers than tiles need
-    int cus = device_cu_count();
-    { static const int per_cu = getenv("UKBB_WS_WGS_PER_CU") ? atoi(getenv("UKBB_WS_WGS_PER_CU")) : 1; if (per_cu > 1) cus *= per_cu; }   // A/B knob
+    const int cus = device_cu_count();
     long long want = ((ntiles + c->wn - 1) / c->wn) * nG;           // workgroups that would give every wave one tile
     int grid = cus >= 8 * nG ? cus / (8 * nG) * (8 * nG) : cus / nG * nG;
     if (grid < nG) grid = nG;
