@@ -1,0 +1,438 @@
+"""Does every launch touch only the device memory it owns, and does it write all of what it owns?
+
+The engine's buffers only grow (DevBuf::ensure, csrc/engine.cpp): a handle runs a small shape inside buffers a larger shape filled, a tail
+batch inside a batch-64 buffer, and what lies behind and beside the current map is finite data of the previous run.  A kernel that loads it
+and masks it gives the bits of a correct kernel; a kernel that leaves part of a map unwritten passes whenever the previous call left the
+right values there; a ragged tile that stores a row too far lands in hipMalloc slack or in a neighbouring allocation.  No parity test sees
+any of that.  Here handles created under UKBB_DEBUG_GUARD=<hex pattern> allocate every buffer as guard | payload | guard (1 MiB guards),
+fill a payload with the pattern when it is allocated, and ``Engine.poison(p)`` refills everything the engine rewrites per call:
+
+  a. first use of fresh memory: a guarded and a plain handle in one process, every model and precision, ragged shapes -> identical bits;
+  b. small after large on one handle, a tail batch in a kept plan, each pattern -> the bits of a fresh plain handle that ran only that case;
+  c. precision switches on one handle;
+  d. cines (UNet-LSTM whole and in chunks under the minimum scratch budget, Temporal-UNet in chunks of one window and unchunked);
+  e. the instrument itself: the poison is read back, a damaged guard is reported with buffer and offset;
+  f. caller-owned outputs of the device-pointer forward and of the pre- / post-processing entries, carved from the middle of larger
+     tensors filled with a sentinel: nothing beside an output changes, everything the entry's contract covers is written.
+
+No tolerance anywhere: bits, and guard bytes."""
+import ctypes as C
+import functools
+import os
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+PATTERNS = ('7FC07FC0', 'FFFFFFFF', '7F800000')                   # bf16 NaN pairs, all ones, fp32 +inf (as tests/test_concurrency_gpu.py)
+FRAME_MODELS = ['FCN_sa', 'FCN_la_2ch', 'FCN_la_4ch', 'FCN_la_4ch_seg4', 'UNet_ao']
+PRECISIONS = {m: ('fp32', 'bf16', 'f32x3') for m in FRAME_MODELS + ['UNet-LSTM_ao']}
+PRECISIONS['Temporal-UNet_ao'] = ('fp32', 'f32x3')                # its 3-D convolutions have no bf16 plan
+# ascending in pixels, so that the staging buffers of a handle are re-allocated (fresh, poisoned) by every case; 16 and 17 images of
+# 64 x 96 lie on either side of the planner's small-batch threshold (plan.h, SMALL_BATCH = 16), and 16 comes first: a handle leaves the
+# small-batch plans for good with the first larger batch it sees
+FRAME_SHAPES = [(1, 16, 16), (3, 80, 112), (2, 48, 400), (16, 64, 96), (17, 64, 96), (2, 272, 304)]
+SEQ_SHAPES = [(1, 9, 32, 48), (2, 9, 48, 80)]
+LARGE = (17, 272, 304)
+
+
+@functools.lru_cache(maxsize=None)
+def _params(model):
+    from ukbb_cardiac_amd.arch import MODELS
+    from ukbb_cardiac_amd.weights import synthetic_params
+    return synthetic_params(MODELS[model], 1234)
+
+
+def _engine(model, guard=None):
+    """A fresh engine: guarded and poisoned with the hex pattern ``guard``, or plain (None).  The variable is read in ukbb_fcn_create only."""
+    from ukbb_cardiac_amd.arch import MODELS
+    from ukbb_cardiac_amd.engine import Engine
+    old = os.environ.pop('UKBB_DEBUG_GUARD', None)
+    try:
+        if guard is not None:
+            os.environ['UKBB_DEBUG_GUARD'] = guard
+        return Engine(MODELS[model], _params(model))
+    finally:
+        os.environ.pop('UKBB_DEBUG_GUARD', None)
+        if old is not None:
+            os.environ['UKBB_DEBUG_GUARD'] = old
+
+
+@pytest.fixture(scope='module')
+def guarded():
+    """One guarded engine per model for the whole module (created on first use)."""
+    made = {}
+
+    def get(model):
+        if model not in made:
+            made[model] = _engine(model, PATTERNS[0])
+        return made[model]
+    yield get
+    for eng in made.values():
+        eng.close()
+
+
+@functools.lru_cache(maxsize=None)
+def _image(shape):
+    rng = np.random.default_rng(sum(shape) + 7 * len(shape))
+    return rng.standard_normal(shape).astype(np.float32)
+
+
+def _run(eng, shape):
+    img = _image(shape)
+    return eng.run_seq(img, want_logits=True) if len(shape) == 4 else eng.run(img, want_logits=True)
+
+
+def _same_bits(got, want, what):
+    for k in ('logits', 'prob', 'pred'):
+        assert got[k].shape == want[k].shape and got[k].tobytes() == want[k].tobytes(), what + (k,)
+
+
+def _guards_intact(eng, what):
+    bad, report = eng.check_guards()
+    assert bad == 0, (what, report)
+
+
+_REF = {}
+
+
+def _fresh_plain(model, prec, shape):
+    """What a fresh plain handle that ran only this case returns (computed once, shared, never modified)."""
+    key = (model, prec, shape)
+    if key not in _REF:
+        with _engine(model) as eng:
+            eng.set_precision(prec)
+            out = _run(eng, shape)
+        for v in out.values():
+            v.setflags(write=False)
+        _REF[key] = out
+    return _REF[key]
+
+
+# ---- a. first use of fresh memory ----------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize('model,prec', [(m, p) for m in FRAME_MODELS + ['UNet-LSTM_ao', 'Temporal-UNet_ao'] for p in PRECISIONS[m]])
+def test_first_use_of_fresh_memory(model, prec):
+    """Every payload of the guarded handle holds NaN pairs when a launch first sees it; the plain handle beside it runs the same calls.
+    Fresh handles (not the module's): the small-batch plans exist only on a handle that never saw more than 16 images."""
+    shapes = FRAME_SHAPES if model in FRAME_MODELS else SEQ_SHAPES
+    with _engine(model, PATTERNS[0]) as g, _engine(model) as p:
+        with pytest.raises(Exception, match='UKBB_DEBUG_GUARD'):
+            p.check_guards()                                       # the plain handle really is plain
+        for eng in (g, p):
+            eng.set_precision(prec)
+        for shape in shapes:
+            got, want = _run(g, shape), _run(p, shape)
+            _same_bits(got, want, (model, prec, shape))
+            _guards_intact(g, (model, prec, shape))
+            assert g.kernel_configs() == p.kernel_configs()
+            assert g.scratch_bytes() == p.scratch_bytes()          # the guards are not part of the documented footprint
+            assert np.isfinite(got['logits']).all() and got['logits'].std() > 0
+        nb, payload, guards = g.guard_info()
+        print('%s %s: %d guarded buffers, %d payload bytes, %d guard bytes' % (model, prec, nb, payload, guards))
+        assert nb > 20 and guards == nb * 2 * (1 << 20) and payload > g.scratch_bytes() > 0     # weights are guarded too
+        assert p.guard_info()[0] == 0
+
+
+# ---- b. small after large, on one handle -----------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize('pattern', PATTERNS)
+@pytest.mark.parametrize('prec', ['fp32', 'bf16'])
+@pytest.mark.parametrize('model', FRAME_MODELS)
+def test_small_after_large_on_one_handle(guarded, model, prec, pattern):
+    """17 images of 272 x 304, then -- a poison in front of each -- a tail batch in the kept plan, a small ragged shape, a smaller batch of
+    it (plan kept: the tail of every map is stale), the smallest shape.  Each equals a fresh plain handle that ran only that case."""
+    eng = guarded(model)
+    eng.set_precision(prec)
+    for i, shape in enumerate([LARGE, (5,) + LARGE[1:], (3, 80, 112), (2, 80, 112), (1, 16, 16)]):
+        if i:
+            assert eng.poison(pattern) > 10
+        got = _run(eng, shape)
+        _same_bits(got, _fresh_plain(model, prec, shape), (model, prec, pattern, shape))
+        _guards_intact(eng, (model, prec, pattern, shape))
+
+
+# ---- c. precision switches --------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize('model,other,shape', [('UNet_ao', 'bf16', (3, 80, 112)), ('UNet-LSTM_ao', 'bf16', (2, 9, 48, 80)), ('FCN_sa', 'f32x3', (3, 80, 112))])
+def test_precision_switches_on_one_handle(guarded, model, other, shape):
+    eng = guarded(model)
+    outs = []
+    for i, prec in enumerate(('fp32', other, 'fp32')):
+        if i:
+            eng.poison(PATTERNS[i])
+        eng.set_precision(prec)
+        outs.append(_run(eng, shape))
+        _guards_intact(eng, (model, prec, i))
+    _same_bits(outs[2], outs[0], (model, 'fp32 again'))
+    with _engine(model, PATTERNS[0]) as fresh:
+        fresh.set_precision(other)
+        want = _run(fresh, shape)
+        _guards_intact(fresh, (model, other, 'fresh'))
+    _same_bits(outs[1], want, (model, other))
+    if other == 'bf16':
+        assert outs[1]['logits'].tobytes() != outs[0]['logits'].tobytes()  # the other precision really ran
+
+
+# ---- d. cines ------------------------------------------------------------------------------------------------------------------------
+
+def _same_cine(got, want, what):
+    assert np.array_equal(got[0], want[0], equal_nan=True), what + ('prob',)     # NaNs of frames no window covers compare equal
+    assert np.array_equal(got[1], want[1]), what + ('pred',)
+
+
+def _lstm_cines(eng, prec, pattern=None):
+    """13 frames of 48 x 64 at time_step 1 and 2, and 5 < 9 frames: whole, then under the minimum scratch budget the host query reports
+    (chunks: lstm_tile_chunk_kernel and lstm_img), there twice -- the first call allocates the released buffers, the second finds
+    them poisoned with ``pattern``."""
+    from ukbb_cardiac_amd import engine
+    out = []
+    eng.set_precision(prec)
+    for F, ts in ((13, 1), (13, 2), (5, 1)):
+        frames = _image((F, 48, 64))
+        low = engine.cine_min_scratch_bytes(eng.arch, prec, F, 48, 64, ts)
+        assert low > 0
+        if F == 13:
+            assert engine.cine_chunk_windows(eng.arch, prec, F, 48, 64, ts, low) < -(-F // ts)       # really chunked
+        for budget, calls in ((0, 1), (low, 2)):
+            eng.set_scratch_budget(budget)
+            for _ in range(calls):
+                if pattern:
+                    eng.poison(pattern)
+                out.append(eng.run_cine(frames, time_step=ts))
+                if pattern:
+                    _guards_intact(eng, (prec, F, ts, budget))
+        eng.set_scratch_budget(0)
+    return out
+
+
+_CINE_REF = {}
+
+
+@pytest.mark.parametrize('pattern', PATTERNS)
+@pytest.mark.parametrize('prec', ['fp32', 'bf16'])
+def test_unet_lstm_cines(guarded, prec, pattern):
+    if prec not in _CINE_REF:
+        with _engine('UNet-LSTM_ao') as plain:
+            _CINE_REF[prec] = _lstm_cines(plain, prec)
+    got = _lstm_cines(guarded('UNet-LSTM_ao'), prec, pattern)
+    assert len(got) == len(_CINE_REF[prec]) == 9
+    for i, (g, w) in enumerate(zip(got, _CINE_REF[prec])):
+        _same_cine(g, w, (prec, pattern, i))
+        assert np.isfinite(g[0]).all() and g[0].std() > 0
+
+
+@pytest.mark.parametrize('pattern', PATTERNS)
+def test_temporal_unet_cines(guarded, pattern, monkeypatch):
+    frames = _image((13, 32, 48))
+    eng = guarded('Temporal-UNet_ao')
+    eng.set_precision('fp32')
+    with _engine('Temporal-UNet_ao') as plain:
+        for chunk in ('1', None):
+            if chunk is None:
+                monkeypatch.delenv('UKBB_TEMPORAL_CHUNK_WINDOWS', raising=False)
+            else:
+                monkeypatch.setenv('UKBB_TEMPORAL_CHUNK_WINDOWS', chunk)
+            want = plain.run_cine(frames)
+            eng.poison(pattern)
+            got = eng.run_cine(frames)
+            _same_cine(got, want, (pattern, chunk))
+            _guards_intact(eng, (pattern, chunk))
+            assert np.isfinite(got[0]).all() and got[0].std() > 0
+
+
+# ---- e. the instrument works ----------------------------------------------------------------------------------------------------------
+
+def test_poison_is_read_back_and_a_damaged_guard_is_reported():
+    G = 1 << 20
+    with _engine('FCN_sa', PATTERNS[0]) as eng:                       # a throw-away handle: its guards end up damaged
+        eng.run(_image((2, 32, 48)))
+        _guards_intact(eng, 'before')
+        for pat in PATTERNS:
+            eng.poison(pat)
+            conv0 = eng.activation('conv0')                            # before any forward: what the poison left
+            assert conv0.size == 2 * 32 * 48 * 16
+            assert np.all(conv0.view(np.uint32) == int(pat, 16)), pat
+        nbytes = conv0.size * 4
+        with pytest.raises(Exception, match='no guard'):
+            eng.damage_guard('act0:conv0', 0)                           # the payload is not a guard
+        with pytest.raises(Exception, match='no buffer'):
+            eng.damage_guard('act0:nonsense', -1)
+        eng.damage_guard('act0:conv0', nbytes + 7)
+        bad, report = eng.check_guards()
+        assert bad == 1 and report.splitlines() == ['act0:conv0 back %d %d' % (nbytes + 7, nbytes + 7)], report
+        from ukbb_cardiac_amd import _lib
+        assert 'act0:conv0 back' in _lib.last_error()
+        eng.damage_guard('act0:conv0', nbytes + G - 1)                 # the guard's last byte
+        eng.damage_guard('dev:conv0_0/bias', -G)                       # a weight buffer, the front guard's first byte
+        eng.damage_guard('io_prob', -1)
+        bad, report = eng.check_guards()
+        assert bad == 3, report
+        assert sorted(report.splitlines()) == sorted(['act0:conv0 back %d %d' % (nbytes + 7, nbytes + G - 1), 'dev:conv0_0/bias front %d %d' % (-G, -G),
+                                                      'io_prob front -1 -1']), report
+        out = eng.run(_image((2, 32, 48)))                              # a damaged guard harms nothing: the handle still runs
+        assert np.isfinite(out['prob']).all() and out['prob'].std() > 0
+
+
+# ---- f. caller-owned outputs ----------------------------------------------------------------------------------------------------------
+
+MARGIN = 1 << 16                                                     # bytes on either side of a carved region
+SENTINELS = (0xCD, 0x32)                                             # every case runs with both: a byte an entry leaves unwritten cannot equal the reference twice
+
+
+class Carved:
+    """``nbytes`` of device memory in the middle of a larger torch tensor: MARGIN bytes before it, MARGIN (+ up to 15) behind it,
+    all filled with the byte ``fill`` (or float32 NaN for ``fill='nan'``); the region itself holds ``payload`` if given."""
+
+    def __init__(self, nbytes, fill, payload=None):
+        import torch
+        self.nbytes = int(nbytes)
+        host = np.empty(2 * MARGIN + -(-self.nbytes // 16) * 16, np.uint8)
+        if fill == 'nan':
+            host.view(np.float32)[:] = np.nan
+        else:
+            host[:] = fill
+        if payload is not None:
+            raw = np.ascontiguousarray(payload.ravel(order='K')).view(np.uint8)     # memory order of a C- or F-contiguous array
+            assert raw.size == self.nbytes
+            host[MARGIN:MARGIN + self.nbytes] = raw
+        self.before = host.copy()
+        self.t = torch.from_numpy(host).cuda()
+        self.ptr = self.t.data_ptr() + MARGIN
+
+    def read(self, what):
+        """The region's bytes now; everything around it must be as it was."""
+        import torch
+        torch.cuda.synchronize()
+        now = self.t.cpu().numpy()
+        end = MARGIN + self.nbytes
+        assert np.array_equal(now[:MARGIN], self.before[:MARGIN]), (what, 'bytes in front of the region changed', np.flatnonzero(now[:MARGIN] != self.before[:MARGIN])[[0, -1]] - MARGIN)
+        assert np.array_equal(now[end:], self.before[end:]), (what, 'bytes behind the region changed', np.flatnonzero(now[end:] != self.before[end:])[[0, -1]])
+        return now[MARGIN:end]
+
+    def untouched(self, what):
+        assert np.array_equal(self.read(what), self.before[MARGIN:MARGIN + self.nbytes]), (what, 'an input was written')
+
+
+def _volume(shape, dtype, seed, order):
+    """MR-like magnitudes with background ties, in the dtype's range (int16: negative values too; uint16: above 32767), as the
+    volumes of tests/test_device_pipeline.py and tests/test_integer_volumes_gpu.py."""
+    rng = np.random.default_rng(seed)
+    v = rng.gamma(1.5, 1.0, size=shape)
+    v[rng.random(shape) < 0.08] = 0.0
+    if dtype == np.float32:
+        return np.asarray(np.round(v * 120.0), dtype=np.float32, order=order)
+    v = v * 40.0 if dtype == np.uint8 else v * 3000.0 - 2000.0 if dtype == np.int16 else v * 12000.0
+    info = np.iinfo(dtype)
+    return np.asarray(np.clip(np.round(v), info.min, info.max).astype(dtype), order=order)
+
+
+def _strides(a):
+    return tuple(s // a.itemsize for s in a.strides)
+
+
+def _bytes(a):
+    return np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+
+
+@pytest.mark.parametrize('dtype', [np.float32, np.uint8, np.int16, np.uint16])
+@pytest.mark.parametrize('order', ['F', 'C'])
+@pytest.mark.parametrize('shape', [(37, 29, 1, 7), (65, 33, 2, 3)])
+def test_prep_entries_write_their_outputs_and_nothing_else(shape, order, dtype):
+    """rescale_pack(_t), zscore_pack(_t), unpack_labels, roi_compact(_t), label_max and label_compact on carved device pointers,
+    against the host references the existing tests use (image_utils, the numpy mirror of the deploy loop, aorta_qc.stats_host)."""
+    from ukbb_cardiac_amd import _lib, aorta_qc, device_pipeline as dp
+    from ukbb_cardiac_amd.image_utils import normalise_intensity, rescale_intensity
+    from ukbb_cardiac_amd.pipeline import pad_amounts, pad_amounts_fixed
+    X, Y, Z, T = shape
+    dtype = np.dtype(dtype)
+    code = 16 if dtype == np.float32 else dp.NIFTI_DATATYPE[dtype]
+    vol = _volume(shape, dtype, X + Y + dtype.itemsize, order)
+    assert vol.flags.f_contiguous if order == 'F' else vol.flags.c_contiguous
+    n_class = 3
+    rng = np.random.default_rng(X * Y)
+    # references (host)
+    lo, hi = np.percentile(vol, (1, 99))
+    X2, Y2, x_pre, x_post, y_pre, y_post = pad_amounts(X, Y)
+    scaled = rescale_intensity(vol.copy(order='K'), (1, 99))
+    want_rescale = np.transpose(np.pad(scaled, ((x_pre, x_post), (y_pre, y_post), (0, 0), (0, 0)), 'constant'), (3, 2, 0, 1)).reshape(T * Z, X2, Y2).astype(np.float32)
+    val_l = np.percentile(vol, 10.0)
+    roi = vol >= val_l
+    mu, den = np.mean(vol[roi]), np.std(vol[roi]) + 1e-6
+    F2, G2, fx_pre, fx_post, fy_pre, fy_post = pad_amounts_fixed(X, Y)
+    norm = normalise_intensity(vol, 10.0)
+    want_zscore = np.transpose(np.pad(norm, ((fx_pre, fx_post), (fy_pre, fy_post), (0, 0), (0, 0)), 'constant'), (3, 2, 0, 1)).reshape(T * Z, F2, G2).astype(np.float32)
+    lab = rng.integers(0, n_class, size=(T * Z, X2, Y2)).astype(np.int32)
+    want_vol = np.asfortranarray(lab.reshape(T, Z, X2, Y2).transpose(2, 3, 1, 0)[x_pre:x_pre + X, y_pre:y_pre + Y].astype(np.uint8))
+    want_counts = np.stack([[np.sum(want_vol[..., t] == c) for c in range(n_class)] for t in range(T)]).astype(np.uint64)
+    want_roi = vol[roi]
+    seg = np.asfortranarray(rng.integers(0, n_class, size=shape).astype(np.uint8))            # NIfTI order, what unpack_labels writes
+    seg[..., T - 1][seg[..., T - 1] == 2] = 0                                                    # an empty mask: -inf
+    stats = aorta_qc.stats_host(vol, seg, n_class)
+    for s in SENTINELS:
+        src = Carved(vol.nbytes, 'nan' if dtype == np.float32 else 0x7F, vol)
+        st = _strides(vol)
+        # rescale_pack / rescale_pack_t
+        out = Carved(want_rescale.nbytes, s)
+        dp.pack_rescaled(src.ptr, dtype, shape, st, lo, hi, (X2, Y2, x_pre, y_pre), out.ptr, 0)
+        assert np.array_equal(out.read('rescale_pack'), _bytes(want_rescale)), 'rescale_pack'
+        # zscore_pack / zscore_pack_t
+        out = Carved(want_zscore.nbytes, s)
+        dp.zscore_pack(src.ptr, dtype, shape, st, mu, den, (F2, G2, fx_pre, fy_pre), out.ptr, 0)
+        assert np.array_equal(out.read('zscore_pack'), _bytes(want_zscore)), 'zscore_pack'
+        # roi_compact / roi_compact_t: the first n elements are the entry's to write
+        out = Carved(vol.nbytes, s)
+        n = C.c_uint64(0)
+        if dtype == np.float32:
+            _lib.check(_lib.lib.ukbb_fcn_roi_compact(src.ptr, X, Y, Z, T, *st, float(val_l), out.ptr, C.byref(n), 0), 'roi_compact')
+        else:
+            _lib.check(_lib.lib.ukbb_fcn_roi_compact_t(src.ptr, code, X, Y, Z, T, *st, float(val_l), out.ptr, C.byref(n), 0), 'roi_compact_t')
+        assert n.value == want_roi.size and 0 < n.value < vol.size
+        assert np.array_equal(out.read('roi_compact')[:want_roi.nbytes], _bytes(want_roi)), 'roi_compact'
+        # unpack_labels
+        pred = Carved(lab.nbytes, 0x7F, lab)
+        out, cnt = Carved(want_vol.nbytes, s), Carved(want_counts.nbytes, s)
+        _lib.check(_lib.lib.ukbb_fcn_unpack_labels(pred.ptr, X, Y, Z, T, X2, Y2, x_pre, y_pre, n_class, out.ptr, cnt.ptr, 0), 'unpack_labels')
+        assert np.array_equal(out.read('unpack_labels volume'), want_vol.ravel(order='F')), 'unpack_labels volume'
+        assert np.array_equal(cnt.read('unpack_labels counts'), _bytes(want_counts)), 'unpack_labels counts'
+        pred.untouched('unpack_labels pred')
+        # label_max, label_compact
+        labels = Carved(seg.nbytes, 0x01, seg)                                                  # a label read from beside the volume would count
+        mx = Carved(T * n_class * 8, s)
+        _lib.check(_lib.lib.ukbb_fcn_label_max(src.ptr, code, X, Y, Z, T, *st, labels.ptr, n_class, mx.ptr, 0), 'label_max')
+        got_max = mx.read('label_max').view(np.float64).reshape(T, n_class)
+        assert np.array_equal(got_max, stats['max'], equal_nan=True) and np.isneginf(got_max[T - 1, 2]), 'label_max'
+        for k in range(1, n_class):
+            want_k = vol[..., 0][seg[..., 0] == k]
+            out = Carved(X * Y * Z * dtype.itemsize, s)
+            _lib.check(_lib.lib.ukbb_fcn_label_compact(src.ptr, code, X, Y, Z, *st[:3], labels.ptr, k, out.ptr, C.byref(n), 0), 'label_compact')
+            assert n.value == want_k.size > 0
+            assert np.array_equal(out.read('label_compact')[:want_k.nbytes], _bytes(want_k)), 'label_compact'
+            with np.errstate(all='ignore'):
+                assert want_k.mean() == stats['mean_ed'][k]                                      # the reference the compacted voxels feed
+        src.untouched('the volume')
+        labels.untouched('the labels')
+
+
+@pytest.mark.parametrize('model,prec', [('FCN_sa', 'fp32'), ('FCN_sa', 'bf16'), ('FCN_sa', 'f32x3'), ('FCN_la_4ch_seg4', 'fp32'), ('UNet_ao', 'fp32'), ('UNet_ao', 'bf16')])
+def test_device_pointer_forward_writes_only_the_callers_outputs(guarded, model, prec):
+    """ukbb_fcn_forward with the image between NaNs and logits / prob / pred each between sentinels: the bits of the host-array call."""
+    eng = guarded(model)
+    eng.set_precision(prec)
+    ncls = eng.arch.n_class
+    for shape in [(3, 80, 112), (1, 16, 16), (2, 48, 400)]:
+        n, h, w = shape
+        img = _image(shape)
+        want = eng.run(img, want_logits=True)
+        for s in SENTINELS:
+            eng.poison(PATTERNS[0])
+            x = Carved(img.nbytes, 'nan', img)
+            lg, pr, pd = Carved(img.nbytes * ncls, s), Carved(img.nbytes * ncls, s), Carved(img.nbytes, s)
+            eng.run_device(x.ptr, n, h, w, logits_ptr=lg.ptr, prob_ptr=pr.ptr, pred_ptr=pd.ptr, stream=0)
+            what = (model, prec, shape, s)
+            assert np.array_equal(lg.read(what + ('logits',)), _bytes(want['logits'])), what
+            assert np.array_equal(pr.read(what + ('prob',)), _bytes(want['prob'])), what
+            assert np.array_equal(pd.read(what + ('pred',)), _bytes(want['pred'])), what
+            x.untouched(what + ('image',))
+            _guards_intact(eng, what)

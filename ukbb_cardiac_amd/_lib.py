@@ -142,6 +142,11 @@ def _load():
     lib.ukbb_fcn_get_activation.argtypes = [vp, C.c_char_p, f32p, C.c_int64]
     lib.ukbb_fcn_synth_volume.argtypes = [C.c_uint64, C.c_size_t, vp, vp]
     lib.ukbb_fcn_clock_probe.argtypes = [C.c_int, vp, C.c_int, C.POINTER(C.c_double)]
+    # debugging aids, not in the public header (engine.cpp: handles created under UKBB_DEBUG_GUARD)
+    lib.ukbb_fcn_debug_check_guards.argtypes = [vp, C.c_char_p, C.c_size_t]
+    lib.ukbb_fcn_debug_guard_info.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.ukbb_fcn_debug_poison.argtypes = [vp, C.c_uint32]
+    lib.ukbb_fcn_debug_damage_guard.argtypes = [vp, C.c_char_p, C.c_longlong]
     if lib.ukbb_fcn_abi_version() != ABI_VERSION:
         raise ImportError('libukbb_fcn.so ABI %d != binding ABI %d: rebuild' % (lib.ukbb_fcn_abi_version(), ABI_VERSION))
     return lib

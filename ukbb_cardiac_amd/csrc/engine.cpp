@@ -70,16 +70,51 @@ struct HostLayer {            // one conv(+BN) unit with BN folded (fp32, same o
     std::vector<float> b;     // [cout]
 };
 
+// Debugging aid (UKBB_DEBUG_GUARD=<hex pattern> at ukbb_fcn_create, kept per handle): every DevBuf of the handle is allocated as
+// guard | payload | guard.  The guards hold GUARD_BYTE; a payload is filled with the pattern when it is allocated, before anything is
+// uploaded into it or cleared.  ukbb_fcn_debug_check_guards reads the guards back, ukbb_fcn_debug_poison refills the payloads the
+// engine rewrites on every call.  GUARD_BYTES is a power of two, so the payload keeps the alignment hipMalloc gave.
+constexpr size_t GUARD_BYTES = (size_t)1 << 20;
+constexpr unsigned char GUARD_BYTE = 0xA5;
+
+struct GuardMode {
+    bool on = false;
+    uint32_t pattern = 0;
+};
+
 struct DevBuf {
     float *p = nullptr;
     size_t n = 0;
-    ~DevBuf() { if (p) (void)hipFree(p); }
+    const GuardMode *guard = nullptr;       // the owning handle's mode (NULL / off: plain allocations)
+    ~DevBuf() { release(); }
+    bool guarded() const { return guard && guard->on; }
+    void release() {
+        if (p) (void)hipFree(guarded() ? reinterpret_cast<char *>(p) - GUARD_BYTES : reinterpret_cast<char *>(p));
+        p = nullptr; n = 0;
+    }
     hipError_t ensure(size_t want) {
         if (want <= n) return hipSuccess;
-        if (p) { (void)hipFree(p); p = nullptr; n = 0; }
+        release();
+        if (guarded()) return ensure_guarded(want);
         hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), want * sizeof(float));
         if (e == hipSuccess) n = want;
         return e;
+    }
+    hipError_t ensure_guarded(size_t want) {
+        char *base = nullptr;
+        const size_t bytes = want * sizeof(float);
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(&base), bytes + 2 * GUARD_BYTES);
+        if (e != hipSuccess) return e;
+        // the fills are ordered against every stream of the process: a debugging mode pays for two device-wide waits per allocation
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e == hipSuccess) e = hipMemset(base, GUARD_BYTE, GUARD_BYTES);
+        if (e == hipSuccess) e = hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(base + GUARD_BYTES), (int)guard->pattern, want);
+        if (e == hipSuccess) e = hipMemset(base + GUARD_BYTES + bytes, GUARD_BYTE, GUARD_BYTES);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) { (void)hipFree(base); return e; }
+        p = reinterpret_cast<float *>(base + GUARD_BYTES);
+        n = want;
+        return hipSuccess;
     }
     hipError_t upload(const std::vector<float> &v) {
         hipError_t e = ensure(v.size());
@@ -93,6 +128,7 @@ struct DevBuf {
 struct ukbb_fcn_handle {
     ukbb_fcn_arch arch{};
     int device = 0;
+    GuardMode guard;                          // UKBB_DEBUG_GUARD at create (debugging aid): every DevBuf below points at it
     std::vector<HostLayer> layers;
     std::map<std::string, int> layer_index;
 
@@ -156,6 +192,13 @@ struct ukbb_fcn_handle {
     std::vector<int64_t> t_cnt;
     bool ev_pending = false;
 
+    // the handle's own buffers by name (weights and activation maps are listed by guard_bufs)
+    std::vector<std::pair<const char *, DevBuf *>> named_bufs() {
+        return {{"io_image", &io_image}, {"io_logits", &io_logits}, {"io_prob", &io_prob}, {"io_pred", &io_pred}, {"lstm_gx", &lstm_gx}, {"lstm_c1", &lstm_c1},
+                {"lstm_h1", &lstm_h1}, {"lstm_c", &lstm_c}, {"lstm_hall", &lstm_hall}, {"lstm_probw", &lstm_probw}, {"lstm_aux", &lstm_aux}, {"lstm_img", &lstm_img},
+                {"t3d_aux", &t3d_aux}, {"t3d_probw", &t3d_probw}};
+    }
+    ukbb_fcn_handle() { for (auto &kv : named_bufs()) kv.second->guard = &guard; }
     ~ukbb_fcn_handle() {
         for (auto e : ev) (void)hipEventDestroy(e);
         if (ev_split_fork) (void)hipEventDestroy(ev_split_fork);
@@ -176,7 +219,7 @@ const float *dev_ptr(ukbb_fcn_handle *h, const std::string &key) {
 
 int upload(ukbb_fcn_handle *h, const std::string &key, const std::vector<float> &v) {
     auto &slot = h->dev[key];
-    if (!slot) slot.reset(new DevBuf);
+    if (!slot) { slot.reset(new DevBuf); slot->guard = &h->guard; }
     HIP_TRY(slot->upload(v), UKBB_EDEVICE);
     return UKBB_OK;
 }
@@ -348,6 +391,7 @@ int materialize_plan(ukbb_fcn_handle *h, PlanLayout &L) {
     h->cap_n = 0;
     for (const ActSpec &s : L.acts) {
         h->act.emplace_back(new DevBuf);
+        h->act.back()->guard = &h->guard;
         h->act_per_image.push_back(s.per_image);
         h->act_name.push_back(s.name);
         h->act_ch.push_back(s.channels);
@@ -720,6 +764,24 @@ int run_plan(ukbb_fcn_handle *h, const float *image, int n, float *logits, float
     return UKBB_OK;
 }
 
+// every DevBuf of the handle by name: the handle's own ("io_prob", "lstm_hall", ...), the activation maps ("act<index>:<name>") and the
+// device-side parameters ("dev:<layer>/<what>")
+void guard_bufs(ukbb_fcn_handle *h, std::vector<std::pair<std::string, DevBuf *>> &v) {
+    v.clear();
+    for (auto &kv : h->named_bufs()) v.emplace_back(kv.first, kv.second);
+    for (size_t i = 0; i < h->act.size(); ++i)
+        v.emplace_back("act" + std::to_string(i) + (h->act_name[i].empty() ? std::string() : ":" + h->act_name[i]), h->act[i].get());
+    for (auto &kv : h->dev) v.emplace_back("dev:" + kv.first, kv.second.get());
+}
+
+int guard_checks(ukbb_fcn_handle *h, const char *what) {
+    if (!h) { set_err("%s: NULL handle", what); return UKBB_EINVAL; }
+    if (!h->guard.on) { set_err("%s: the handle was not created under UKBB_DEBUG_GUARD", what); return UKBB_EINVAL; }
+    HIP_TRY(hipSetDevice(h->device), UKBB_EDEVICE);
+    HIP_TRY(hipDeviceSynchronize(), UKBB_EDEVICE);
+    return UKBB_OK;
+}
+
 }  // namespace
 
 // =============================== C ABI ===========================================
@@ -732,6 +794,101 @@ int ukbb_fcn_debug_set_ops(ukbb_fcn_handle *h, int first, int last) {
     if (!h) return UKBB_EINVAL;
     h->debug_first_op = first; h->debug_last_op = last;
     return UKBB_OK;
+}
+
+// ---- guarded, poisonable buffers (debugging aids, not in the public header; handles created under UKBB_DEBUG_GUARD only) ----------
+// Waits for the device, then reads every guard back.  Returns the number of buffers with a damaged guard (or a negative code); one line
+// per damaged guard goes to report (truncated at cap) and to ukbb_fcn_last_error: "<buffer> <front|back> <first> <last>", the first and
+// last damaged byte as offsets from the payload's start (front guard: negative; back guard: >= the payload's bytes).
+int ukbb_fcn_debug_check_guards(ukbb_fcn_handle *h, char *report, size_t cap) {
+    int rc = guard_checks(h, "debug_check_guards");
+    if (rc) return rc;
+    std::vector<std::pair<std::string, DevBuf *>> bufs;
+    guard_bufs(h, bufs);
+    std::vector<unsigned char> host(GUARD_BYTES);
+    std::string out;
+    int bad = 0;
+    for (auto &kv : bufs) {
+        const DevBuf *b = kv.second;
+        if (!b->p) continue;
+        const long long bytes = (long long)(b->n * sizeof(float));
+        bool hit = false;
+        for (int side = 0; side < 2; ++side) {
+            const long long off = side ? bytes : -(long long)GUARD_BYTES;
+            HIP_TRY(hipMemcpy(host.data(), reinterpret_cast<const char *>(b->p) + off, GUARD_BYTES, hipMemcpyDeviceToHost), UKBB_EDEVICE);
+            long long first = -1, last = -1;
+            for (size_t i = 0; i < GUARD_BYTES; ++i)
+                if (host[i] != GUARD_BYTE) { if (first < 0) first = (long long)i; last = (long long)i; }
+            if (first < 0) continue;
+            char line[256];
+            snprintf(line, sizeof line, "%s %s %lld %lld\n", kv.first.c_str(), side ? "back" : "front", off + first, off + last);
+            out += line;
+            hit = true;
+        }
+        bad += hit;
+    }
+    if (report && cap) { const size_t m = std::min(out.size(), cap - 1); memcpy(report, out.data(), m); report[m] = 0; }
+    set_err("%s", out.c_str());
+    return bad;
+}
+
+// The number of guarded buffers the handle holds right now; their payload bytes and the bytes of their guards.
+int ukbb_fcn_debug_guard_info(ukbb_fcn_handle *h, uint64_t *payload_bytes, uint64_t *guard_bytes) {
+    if (!h) { set_err("debug_guard_info: NULL handle"); return UKBB_EINVAL; }
+    std::vector<std::pair<std::string, DevBuf *>> bufs;
+    guard_bufs(h, bufs);
+    int nb = 0;
+    uint64_t pay = 0;
+    for (auto &kv : bufs)
+        if (kv.second->p && kv.second->guarded()) { ++nb; pay += kv.second->n * sizeof(float); }
+    if (payload_bytes) *payload_bytes = pay;
+    if (guard_bytes) *guard_bytes = (uint64_t)nb * 2 * GUARD_BYTES;
+    return nb;
+}
+
+// Refills the payloads of the buffers a call rewrites before it reads them -- the activation maps, the ConvLSTM and cine working buffers
+// and the host-call staging of the outputs -- with `pattern`.  Weights, the staged input (io_image) and the tables uploaded once per
+// shape (lstm_aux, t3d_aux) keep their contents.  Returns the number of buffers refilled.
+int ukbb_fcn_debug_poison(ukbb_fcn_handle *h, uint32_t pattern) {
+    int rc = guard_checks(h, "debug_poison");
+    if (rc) return rc;
+    std::vector<DevBuf *> bufs = {&h->io_logits, &h->io_prob, &h->io_pred, &h->lstm_gx, &h->lstm_c1, &h->lstm_h1, &h->lstm_c, &h->lstm_hall,
+                                  &h->lstm_probw, &h->lstm_img, &h->t3d_probw};
+    for (auto &b : h->act) bufs.push_back(b.get());
+    int nb = 0;
+    for (DevBuf *b : bufs) {
+        if (!b->p) continue;
+        HIP_TRY(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(b->p), (int)pattern, b->n), UKBB_EDEVICE);
+        ++nb;
+    }
+    HIP_TRY(hipDeviceSynchronize(), UKBB_EDEVICE);
+    return nb;
+}
+
+// Writes one byte that differs from the guard's into a guard of `buffer` (a name as debug_check_guards reports it), `offset` bytes from the
+// payload's start: inside the front guard (-GUARD_BYTES .. -1) or the back guard (payload bytes .. + GUARD_BYTES - 1), i.e. inside the
+// buffer's own allocation.  So that a test can show the checker sees damage.
+int ukbb_fcn_debug_damage_guard(ukbb_fcn_handle *h, const char *buffer, long long offset) {
+    int rc = guard_checks(h, "debug_damage_guard");
+    if (rc) return rc;
+    if (!buffer) { set_err("debug_damage_guard: NULL buffer name"); return UKBB_EINVAL; }
+    std::vector<std::pair<std::string, DevBuf *>> bufs;
+    guard_bufs(h, bufs);
+    for (auto &kv : bufs) {
+        if (kv.first != buffer) continue;
+        const DevBuf *b = kv.second;
+        const long long bytes = (long long)(b->n * sizeof(float)), G = (long long)GUARD_BYTES;
+        if (!b->p) { set_err("debug_damage_guard: buffer '%s' is not allocated", buffer); return UKBB_EINVAL; }
+        if (!((offset >= -G && offset < 0) || (offset >= bytes && offset < bytes + G))) {
+            set_err("debug_damage_guard: offset %lld is in no guard of '%s' (payload %lld bytes, guards %lld)", offset, buffer, bytes, G);
+            return UKBB_EINVAL;
+        }
+        const unsigned char v = (unsigned char)~GUARD_BYTE;
+        HIP_TRY(hipMemcpy(reinterpret_cast<char *>(b->p) + offset, &v, 1, hipMemcpyHostToDevice), UKBB_EDEVICE);
+        return UKBB_OK;
+    }
+    set_err("debug_damage_guard: no buffer named '%s'", buffer);
+    return UKBB_EINVAL;
 }
 
 // debugging / testing aid, not in the public header: the plan layout_plan makes for batches of n images of H x W on a device of `cus`
@@ -804,6 +961,10 @@ ukbb_fcn_handle *ukbb_fcn_create(const ukbb_fcn_arch *arch, const float *weights
     std::unique_ptr<ukbb_fcn_handle> h(new ukbb_fcn_handle);
     h->arch = *arch;
     h->device = device;
+    if (const char *g = getenv("UKBB_DEBUG_GUARD")) {   // debugging aid, read here only: guarded, poisoned buffers for this handle
+        h->guard.on = true;
+        h->guard.pattern = (uint32_t)strtoul(g, nullptr, 16);
+    }
 
     // ---- fold BN (fp32; same op order as weights.py fold_bn) --------------------------
     const float *p = weights;
@@ -959,10 +1120,7 @@ int release_scratch(ukbb_fcn_handle *h) {
     HIP_TRY(hipDeviceSynchronize(), UKBB_EDEVICE);
     std::vector<DevBuf *> bufs;
     scratch_bufs(h, bufs);
-    for (DevBuf *b : bufs) {
-        if (b->p) (void)hipFree(b->p);
-        b->p = nullptr; b->n = 0;
-    }
+    for (DevBuf *b : bufs) b->release();
     h->cap_n = 0;
     h->lstm_aux_key = h->t3d_aux_key = h->budget_key = -1;
     return UKBB_OK;

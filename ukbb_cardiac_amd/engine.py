@@ -167,6 +167,32 @@ class Engine:
         """Bytes of device memory the handle holds right now in its activation and cine buffers (weights excluded)."""
         return int(_lib.lib.ukbb_fcn_scratch_bytes(self._h))
 
+    # -- guarded, poisonable buffers (debugging aid: engines created with UKBB_DEBUG_GUARD=<hex pattern> in the environment) ----------
+    def check_guards(self):
+        """Waits for the device and reads the guards on either side of every device buffer of the handle.  Returns
+        ``(damaged, report)``: the number of buffers with a damaged guard and one line ``<buffer> <front|back> <first> <last>`` per
+        damaged guard (byte offsets from the payload's start)."""
+        buf = C.create_string_buffer(1 << 14)
+        bad = _lib.check(_lib.lib.ukbb_fcn_debug_check_guards(self._h, buf, len(buf)), 'ukbb_fcn_debug_check_guards')
+        return bad, buf.value.decode()
+
+    def guard_info(self):
+        """``(buffers, payload_bytes, guard_bytes)`` of the guarded buffers the handle holds right now."""
+        pay, gb = C.c_uint64(0), C.c_uint64(0)
+        nb = _lib.check(_lib.lib.ukbb_fcn_debug_guard_info(self._h, C.byref(pay), C.byref(gb)), 'ukbb_fcn_debug_guard_info')
+        return nb, int(pay.value), int(gb.value)
+
+    def poison(self, pattern) -> int:
+        """Fill every buffer the engine rewrites on each call (activation maps, ConvLSTM / cine working buffers, output staging) with
+        the 32-bit ``pattern`` (int or hex string); returns how many were filled."""
+        pat = int(pattern, 16) if isinstance(pattern, str) else int(pattern)
+        return _lib.check(_lib.lib.ukbb_fcn_debug_poison(self._h, pat & 0xFFFFFFFF), 'ukbb_fcn_debug_poison')
+
+    def damage_guard(self, buffer: str, offset: int):
+        """Write one byte into a guard of ``buffer`` (a name as ``check_guards`` reports it) at ``offset`` bytes from its payload's
+        start -- inside the buffer's own allocation; shows that ``check_guards`` sees damage."""
+        _lib.check(_lib.lib.ukbb_fcn_debug_damage_guard(self._h, buffer.encode(), int(offset)), 'ukbb_fcn_debug_damage_guard')
+
     # -- measurement -----------------------------------------------------------
     def kernel_names(self):
         n = _lib.lib.ukbb_fcn_num_kernels(self._h)
