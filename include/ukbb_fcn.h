@@ -339,6 +339,25 @@ int ukbb_fcn_label_max(const void *d_vol, int nifti_datatype, int X, int Y, int 
 int ukbb_fcn_label_compact(const void *d_vol, int nifti_datatype, int X, int Y, int Z, int64_t sx, int64_t sy, int64_t sz, const uint8_t *d_lab,
                            int label, void *d_out, uint64_t *n_host, void *stream);
 
+/* -- the short- and long-axis quality-control gates (additive to ABI 11): component statistics of P label planes of X*Y uint8
+ * voxels (x fastest: the planes ukbb_fcn_unpack_labels leaves behind).  Planes never connect; inside a plane connectivity is 8,
+ * skimage.measure.label's default for a 2-D array.  All outputs int32 and exact:
+ *   d_count[p][k], d_largest[p][k], d_kept[p][k] (P x n_class, column 0 stays 0): the voxels of class k on plane p, the size
+ *     of the largest component of plane == k (0 if absent), the sum of the sizes of its components with AT LEAST keep_min voxels
+ *     (remove_small_cc deletes area < thres);
+ *   d_union_largest[p]: the size of the largest component of (largest component of class a) | (components of class b with at
+ *     least keep_min voxels) -- `epi`.  Of two class-a components of equal largest size the one whose smallest x*Y + y is
+ *     smaller joins the union: get_largest_cc takes the first label of the strictly greatest area, and labels are numbered in
+ *     a C-order scan of the [x][y] array.
+ * Replaces get_largest_cc / remove_small_cc (reference common/image_utils.py:227-249) as sa_pass_quality_control
+ * (common/cardiac_utils.py:119-135, a = 1, b = 2, keep_min = 10) and la_pass_quality_control (:157-168) apply them, and the
+ * np.sum(seg == l) of :86-105 and :149-155.  Labels >= n_class are ignored.  d_work: 8-byte aligned,
+ * 2*P*n_class + 3*X*Y*P + (X*Y*P + 3)/4 int32 the caller allocates (keys, parents, sizes, first indices, the derived mask).
+ * Integer atomic add / min / max only: nothing depends on arrival order.  Asynchronous.
+ * n_class <= 16, 1 <= a != b < n_class, P <= 65535, 4*X*Y*P < 2^31. */
+int ukbb_fcn_plane_components(const uint8_t *d_planes, int X, int Y, int P, int n_class, int a, int b, int keep_min, int32_t *d_work,
+                              int32_t *d_count, int32_t *d_largest, int32_t *d_kept, int32_t *d_union_largest, void *stream);
+
 /* ---- label-volume files (host only: no device, no stream) ---------------------------------------
  * What the reference does with the result: nib.save of np.zeros(image.shape) filled with the labels
  * (common/deploy_network.py:92,116,136-138; deploy_network_ao.py:189-196) -- for a short-axis subject

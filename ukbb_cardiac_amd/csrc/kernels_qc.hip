@@ -6,6 +6,11 @@
 //                              -- skimage.measure.label(seg_t == l, connectivity=2) + the size filter of :1766-1780
 //   ukbb_fcn_label_max         per (frame, class): np.max(image_t[seg_t == k]) as float64, NaN propagated -- :1757-1764
 //
+//   ukbb_fcn_plane_components per (plane, class) of P label planes: voxels, the largest 8-connected component, the voxels in
+//                              components of at least keep_min voxels; per plane: the largest component of (largest of class a |
+//                              kept of class b) -- get_largest_cc / remove_small_cc of sa_pass_quality_control (:77-136) and
+//                              la_pass_quality_control (:139-169)
+//
 // (the third statistic, the float32 / float64 mean of image_ED[seg_ED == l] of :1753-1755, is ukbb_fcn_label_compact in
 // kernels_prep.hip followed by the pairwise sums there.)
 //
@@ -197,6 +202,92 @@ __global__ __launch_bounds__(256) void ccl_count_kernel(const unsigned char *__r
     atomicAdd(&n_large[(gi / frame) * n_class + k], 1);
 }
 
+// ---- plane-wise component statistics (ukbb_fcn_plane_components) -------------------------------------------------------
+// The planes are labelled by the three ccl_* kernels above with Z = 1 (a plane is a frame: 8-connectivity, nothing across
+// planes).  What the short- and long-axis gates need on top is each component's size and, for the tie rule of get_largest_cc
+// (the first label of the strictly greatest area, labels numbered by the first voxel of a C-order scan of the [x][y] array),
+// the smallest x*Y + y of each component.  A voxel whose (x-1, y-1), (x-1, y), (x-1, y+1) or (x, y-1) neighbour carries its
+// label cannot be that minimum -- the neighbour is in its component and comes earlier in the scan -- so only the few voxels
+// without such a neighbour offer their index to their root (integer atomic minimum).  Every root then offers the key
+// (size << 32) | (0xFFFFFFFF - first) to an integer atomic maximum per (plane, class): the largest component, the earliest
+// in scan order among equals, whatever the arrival order.
+
+// first[] = INT_MAX, the keys and the three accumulated outputs = 0
+__global__ __launch_bounds__(256) void plane_init_kernel(long long n, int cells, int planes, int *__restrict__ first,
+                                                         unsigned long long *__restrict__ keys, int *__restrict__ count,
+                                                         int *__restrict__ kept, int *__restrict__ union_largest) {
+    const long long gi = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gi < n) first[gi] = 0x7FFFFFFF;
+    if (gi < cells) {
+        keys[gi] = 0;
+        count[gi] = 0;
+        kept[gi] = 0;
+    }
+    if (gi < planes) union_largest[gi] = 0;
+}
+
+__device__ __forceinline__ int root_of(const int *__restrict__ parent, int i) {     // parent is read-only in the launches that call this
+    for (int q = parent[i]; q != i; q = parent[i]) i = q;
+    return i;
+}
+
+__global__ __launch_bounds__(256) void plane_first_kernel(const unsigned char *__restrict__ lab, int X, int Y, long long n,
+                                                          const int *__restrict__ parent, int *first) {
+    const long long gi = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gi >= n) return;
+    const unsigned char v = lab[gi];
+    if (!v) return;
+    const int x = (int)(gi % X), y = (int)((gi / X) % Y);
+    if (y > 0 && lab[gi - X] == v) return;                                  // (x, y-1)
+    if (x > 0 && (lab[gi - 1] == v || (y > 0 && lab[gi - 1 - X] == v) || (y < Y - 1 && lab[gi - 1 + X] == v))) return;
+    __hip_atomic_fetch_min(&first[root_of(parent, (int)gi)], x * Y + y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// every root of a class below n_class: its size to count (and to kept, if it has at least keep_min voxels), its key to the maximum
+__global__ __launch_bounds__(256) void plane_root_kernel(const unsigned char *__restrict__ lab, long long n, long long plane, int n_class,
+                                                         int keep_min, const int *__restrict__ parent, const int *__restrict__ size,
+                                                         const int *__restrict__ first, unsigned long long *keys, int *count, int *kept) {
+    const long long gi = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gi >= n) return;
+    const int k = lab[gi];
+    if (k == 0 || k >= n_class || parent[gi] != (int)gi) return;
+    const int s = size[gi];
+    const size_t cell = (size_t)(gi / plane) * n_class + k;
+    atomicAdd(&count[cell], s);
+    if (s >= keep_min) atomicAdd(&kept[cell], s);
+    atomicMax(&keys[cell], ((unsigned long long)(unsigned)s << 32) | (0xFFFFFFFFu - (unsigned)first[gi]));
+}
+
+__global__ __launch_bounds__(256) void plane_largest_kernel(const unsigned long long *__restrict__ keys, int cells, int *__restrict__ largest) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < cells) largest[i] = (int)(keys[i] >> 32);
+}
+
+// mask = (the largest component of class a) | (the components of class b with at least keep_min voxels)
+__global__ __launch_bounds__(256) void plane_mask_kernel(const unsigned char *__restrict__ lab, long long n, long long plane, int n_class, int a,
+                                                         int b, int keep_min, const int *__restrict__ parent, const int *__restrict__ size,
+                                                         const int *__restrict__ first, const unsigned long long *__restrict__ keys,
+                                                         unsigned char *__restrict__ mask) {
+    const long long gi = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gi >= n) return;
+    const int k = lab[gi];
+    unsigned char m = 0;
+    if (k == a) {
+        const unsigned long long key = keys[(size_t)(gi / plane) * n_class + a];   // non-zero: the class has a voxel, so a component
+        m = (unsigned)first[root_of(parent, (int)gi)] == 0xFFFFFFFFu - (unsigned)key;
+    } else if (k == b) {
+        m = size[root_of(parent, (int)gi)] >= keep_min;
+    }
+    mask[gi] = m;
+}
+
+__global__ __launch_bounds__(256) void plane_union_kernel(const unsigned char *__restrict__ mask, long long n, long long plane,
+                                                          const int *__restrict__ parent, const int *__restrict__ size, int *union_largest) {
+    const long long gi = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gi >= n || !mask[gi] || parent[gi] != (int)gi) return;
+    atomicMax(&union_largest[gi / plane], size[gi]);
+}
+
 // ---- masked maximum ----------------------------------------------------------------------------------------------------
 // The maximum as an unsigned key whose integer order is numpy's: NaN above everything (np.max propagates it), then the value
 // order; 0 = no voxel (the key of every value is >= 1).  Integer maxima are order-independent, so the result does not depend
@@ -309,6 +400,47 @@ int ukbb_fcn_label_components(const uint8_t *d_lab, int X, int Y, int Z, int T, 
                        (const int *)parent, (const int *)size, d_n_large);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("label_components: launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
+    return UKBB_OK;
+}
+
+int ukbb_fcn_plane_components(const uint8_t *d_planes, int X, int Y, int P, int n_class, int a, int b, int keep_min, int32_t *d_work,
+                              int32_t *d_count, int32_t *d_largest, int32_t *d_kept, int32_t *d_union_largest, void *stream) {
+    // X*Y < 2^62 for any two ints, and once it is known to be below 2^29 the product with P <= 65535 cannot overflow either
+    const long long plane = X >= 1 && Y >= 1 ? (long long)X * Y : 0;
+    const long long n = plane >= 1 && plane <= 0x1FFFFFFFll && P >= 1 && P <= 65535 ? plane * P : 0;
+    if (!d_planes || !d_work || !d_count || !d_largest || !d_kept || !d_union_largest || n < 1 || 4 * n > 0x7FFFFFFFll ||
+        n_class < 1 || n_class > MAXC || a < 1 || a >= n_class || b < 1 || b >= n_class || a == b || ((uintptr_t)d_work & 7)) {
+        set_error("plane_components: bad argument (n_class 1..16, 1 <= a != b < n_class, P <= 65535, 4*X*Y*P < 2^31, d_work 8-byte aligned)");
+        return UKBB_EINVAL;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int cells = P * n_class;
+    // d_work: keys [P*n_class] uint64 | parent [n] | size [n] | first [n] int32 | mask [n] uint8
+    unsigned long long *keys = reinterpret_cast<unsigned long long *>(d_work);
+    int *parent = d_work + 2 * (size_t)cells, *size = parent + n, *first = size + n;
+    unsigned char *mask = reinterpret_cast<unsigned char *>(first + n);
+    const unsigned tiles = (unsigned)(((X + TILE - 1) / TILE) * ((Y + TILE - 1) / TILE));
+    const unsigned nb = (unsigned)((n + 255) / 256);
+    const unsigned nb_init = (unsigned)(((n > cells ? n : (long long)cells) + 255) / 256);
+    hipLaunchKernelGGL(plane_init_kernel, dim3(nb_init), dim3(256), 0, s, n, cells, P, first, keys, d_count, d_kept, d_union_largest);
+    hipLaunchKernelGGL(ccl_local_kernel, dim3(tiles, (unsigned)P), dim3(256), 0, s, d_planes, X, Y, parent, size);
+    hipLaunchKernelGGL(ccl_border_kernel, dim3(nb), dim3(256), 0, s, d_planes, X, Y, 1, n, parent);
+    hipLaunchKernelGGL(ccl_size_kernel, dim3(nb), dim3(256), 0, s, d_planes, n, (const int *)parent, size);
+    hipLaunchKernelGGL(plane_first_kernel, dim3(nb), dim3(256), 0, s, d_planes, X, Y, n, (const int *)parent, first);
+    hipLaunchKernelGGL(plane_root_kernel, dim3(nb), dim3(256), 0, s, d_planes, n, plane, n_class, keep_min, (const int *)parent,
+                       (const int *)size, (const int *)first, keys, d_count, d_kept);
+    hipLaunchKernelGGL(plane_largest_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, (const unsigned long long *)keys, cells,
+                       d_largest);
+    hipLaunchKernelGGL(plane_mask_kernel, dim3(nb), dim3(256), 0, s, d_planes, n, plane, n_class, a, b, keep_min, (const int *)parent,
+                       (const int *)size, (const int *)first, (const unsigned long long *)keys, mask);
+    // the same labeller on the derived mask; only the largest size is asked for, so the key is the size itself
+    hipLaunchKernelGGL(ccl_local_kernel, dim3(tiles, (unsigned)P), dim3(256), 0, s, (const unsigned char *)mask, X, Y, parent, size);
+    hipLaunchKernelGGL(ccl_border_kernel, dim3(nb), dim3(256), 0, s, (const unsigned char *)mask, X, Y, 1, n, parent);
+    hipLaunchKernelGGL(ccl_size_kernel, dim3(nb), dim3(256), 0, s, (const unsigned char *)mask, n, (const int *)parent, size);
+    hipLaunchKernelGGL(plane_union_kernel, dim3(nb), dim3(256), 0, s, (const unsigned char *)mask, n, plane, (const int *)parent,
+                       (const int *)size, d_union_largest);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("plane_components: launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
     return UKBB_OK;
 }
 

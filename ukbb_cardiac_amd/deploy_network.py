@@ -15,7 +15,7 @@ and writes the same files (``deploy_network.py:136-151,207-216``):
 ``--model_path`` names ``<model_path>.ukbbw``.
 
 Extra flags (not in the reference): ``--device``, ``--batch_slices``,
-``--num_shards`` / ``--shard_index`` (multi-GPU batch split).
+``--num_shards`` / ``--shard_index`` (multi-GPU batch split), ``--output_csv``, ``--qc_csv``.
 """
 import os
 import sys
@@ -26,7 +26,7 @@ import numpy as np
 if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from ukbb_cardiac_amd import measures, nifti, pipeline             # noqa: E402
+from ukbb_cardiac_amd import measures, nifti, pipeline, qc_gates   # noqa: E402
 from ukbb_cardiac_amd.flags import FlagError, FlagSet              # noqa: E402
 from ukbb_cardiac_amd.shard import ClaimQueue, apply_cpu_set_from_env, default_device, shard_from_env   # noqa: E402
 
@@ -58,6 +58,11 @@ def define_flags():
     fs.DEFINE_string('output_csv', '', '--seq_name sa, sequence mode: also write the spreadsheet of short_axis/eval_ventricular_volume.py '
                      '(same columns, same arithmetic) from the per-frame class counts the GPU leaves behind -- no second pass over '
                      'seg_sa.nii.gz.  Subjects already segmented by an earlier run are measured from their files.')
+    fs.DEFINE_string('qc_csv', '', 'Sequence mode: also write the verdict of the quality-control gate the reference applies to this '
+                     'segmentation before its strain / wall-thickness / atrial-volume stages (sa: sa_pass_quality_control on the ED frame; '
+                     'la_4ch --seg4: la_pass_quality_control; la_2ch, la_4ch: atrium_pass_quality_control), from component statistics of '
+                     'the labels while they are on the GPU: columns gate, passed, message.  Subjects already segmented by an earlier '
+                     'run are gated from their files.')
     fs.DEFINE_integer('num_shards', env_cnt, 'Number of workers sharing data_dir.')
     fs.DEFINE_integer('shard_index', env_idx, 'This worker: subjects i with i % num_shards == shard_index.')
     fs.DEFINE_boolean('work_stealing', True, 'With num_shards > 1: after its own share a worker takes subjects of the other shards that '
@@ -99,7 +104,7 @@ def sequence_on_device(FLAGS, engine, image):
     return device_pipeline.device_dtype_ok(image.dtype)
 
 
-def run_pipelined(FLAGS, engine, data_list, log=print, csv_rows=None, queue=None):
+def run_pipelined(FLAGS, engine, data_list, log=print, csv_rows=None, queue=None, qc_rows=None):
     """Sequence mode with subjects overlapped: reader threads decompress the next files into pinned staging buffers,
     the GPU thread (this one) keeps up to two subjects in flight on three streams (subject_pipeline.SubjectPipeline),
     writer threads expand the uint8 labels to the reference's float64 volume, gzip and save.  Same files, byte for byte,
@@ -147,7 +152,8 @@ def run_pipelined(FLAGS, engine, data_list, log=print, csv_rows=None, queue=None
         if len(shape) == 4 and device_pipeline.device_dtype_ok(dt):
             with mk:
                 if state['pipe'] is None:                  # sized by the first volume; bigger ones fall back below
-                    state['pipe'] = SubjectPipeline(engine, shape, FLAGS.batch_slices, depth=depth, extra_inputs=window)
+                    state['pipe'] = SubjectPipeline(engine, shape, FLAGS.batch_slices, depth=depth, extra_inputs=window,
+                                                    qc=None if qc_rows is None else (seq, FLAGS.seg4))
             try:
                 return state['pipe'].stage(shape, dt).array, SubjectPipeline.HEADROOM
             except ValueError:
@@ -191,6 +197,8 @@ def run_pipelined(FLAGS, engine, data_list, log=print, csv_rows=None, queue=None
         processed.append(data)
         if csv_rows is not None:
             csv_rows[data] = measures.sa_row(res.counts, nim.header['pixdim'])
+        if qc_rows is not None:
+            record_gate(FLAGS, qc_rows, data, data_dir, res.qc, log)
         if FLAGS.save_seg:
             log('  Saving segmentation ...')
             # the saved frames are the CLIPPED intensities (alias quirk)
@@ -230,7 +238,7 @@ def run_pipelined(FLAGS, engine, data_list, log=print, csv_rows=None, queue=None
                     finish(*inflight.pop(0))
                 log(item[0])
                 try:
-                    _sequence_subject(FLAGS, item, nim, None, engine, log, processed, table_time, csv_rows)
+                    _sequence_subject(FLAGS, item, nim, None, engine, log, processed, table_time, csv_rows, qc_rows)
                 finally:
                     release(item[0])
                 top_up()
@@ -252,7 +260,16 @@ def run_pipelined(FLAGS, engine, data_list, log=print, csv_rows=None, queue=None
     return processed, table_time, start_time
 
 
-def _sequence_subject(FLAGS, item, nim, forward, engine, log, processed, table_time, csv_rows=None):
+def record_gate(FLAGS, qc_rows, data, data_dir, stats, log):
+    """--qc_csv: the verdict of this sequence's gate from its statistics (qc_gates.stats_host / device_pipeline.device_gate_stats) into
+    qc_rows; the message of a failing subject is logged the way the reference prints it."""
+    name = '{0}/{1}'.format(data_dir, qc_gates.seg_file_name(FLAGS.seq_name, FLAGS.seg4))
+    qc_rows[data] = passed, message = qc_gates.gate_from_stats(stats, FLAGS.seq_name, FLAGS.seg4, name)
+    if not passed:
+        log(message)
+
+
+def _sequence_subject(FLAGS, item, nim, forward, engine, log, processed, table_time, csv_rows=None, qc_rows=None):
     """One subject of sequence mode, start to finish on this thread (deploy_network.py:80-151)."""
     data, data_dir, image_name = item
     seq, pre = FLAGS.seq_name, seg_prefix(FLAGS)
@@ -266,7 +283,8 @@ def _sequence_subject(FLAGS, item, nim, forward, engine, log, processed, table_t
     on_device = sequence_on_device(FLAGS, engine, image)
     if on_device:
         from ukbb_cardiac_amd import device_pipeline
-        pred, aux = device_pipeline.segment_sequence_device(image, engine, FLAGS.batch_slices, return_aux=True)
+        pred, aux = device_pipeline.segment_sequence_device(image, engine, FLAGS.batch_slices, return_aux=True,
+                                                            qc=None if qc_rows is None else (seq, FLAGS.seg4))
     else:
         if forward is None:
             forward = lambda b: {'pred': engine.run(b, want_prob=False)['pred']}
@@ -284,6 +302,9 @@ def _sequence_subject(FLAGS, item, nim, forward, engine, log, processed, table_t
         n_class = 4 if engine is None else engine.arch.n_class
         counts = aux['counts'] if on_device else measures.counts_from_labels(pred, n_class)
         csv_rows[data] = measures.sa_row(counts, nim.header['pixdim'])
+    if qc_rows is not None:
+        n_class = None if engine is None else engine.arch.n_class
+        record_gate(FLAGS, qc_rows, data, data_dir, aux['qc'] if on_device else qc_gates.stats_host(pred, seq, FLAGS.seg4, n_class), log)
     if FLAGS.save_seg:
         log('  Saving segmentation ...')
         frames = {}
@@ -314,6 +335,25 @@ def write_measures_csv(FLAGS, subjects, csv_rows, log=print):
     log('Clinical measures of {0} subjects written to {1}'.format(len(rows), path))
 
 
+def write_qc_csv(FLAGS, subjects, qc_rows, log=print):
+    """--qc_csv for this worker's subjects, sorted: verdicts of this run from qc_rows; a subject segmented by an earlier run
+    (skipped above) is gated from its label file on the host.  Same sharing between workers as write_measures_csv."""
+    seq, pre = FLAGS.seq_name, seg_prefix(FLAGS)
+    rows = []
+    for data in sorted(set(subjects) | set(qc_rows)):
+        data_dir = os.path.join(FLAGS.data_dir, data)
+        seg_name = '{0}/{1}_{2}.nii.gz'.format(data_dir, pre, seq)
+        if data not in qc_rows and os.path.isdir(data_dir) and os.path.exists(seg_name):
+            seg = nifti.load(seg_name).get_data()
+            if seg.ndim == 4:
+                record_gate(FLAGS, qc_rows, data, data_dir, qc_gates.stats_host(seg, seq, FLAGS.seg4), log)
+        if data in qc_rows:
+            rows.append((data, qc_rows[data]))
+    path = measures.shard_csv_name(FLAGS.qc_csv, FLAGS.shard_index, FLAGS.num_shards)
+    qc_gates.write_csv(path, seq, FLAGS.seg4, rows)
+    log('Quality-control verdicts of {0} subjects written to {1}'.format(len(rows), path))
+
+
 def run(FLAGS, forward, log=print, engine=None):
     """The subject loop of deploy_network.py:52-225 with ``forward`` standing for sess.run.
     With ``engine`` (and --device_preproc) float32 sequences take the device pipeline."""
@@ -329,10 +369,18 @@ def run(FLAGS, forward, log=print, engine=None):
         if seq != 'sa' or not FLAGS.process_seq:
             raise ValueError('--output_csv writes the table of short_axis/eval_ventricular_volume.py: it needs --seq_name sa in sequence mode')
         csv_rows = {}
+    qc_rows = None
+    if getattr(FLAGS, 'qc_csv', ''):
+        if not FLAGS.process_seq:
+            raise ValueError('--qc_csv gates the segmentation of a whole sequence: it needs sequence mode (--process_seq)')
+        if engine is not None and engine.arch.n_class < qc_gates.min_classes(seq, FLAGS.seg4):
+            raise ValueError('--qc_csv: the gate of --seq_name {0}{1} reads {2} classes, the model has {3}'.format(
+                seq, ' --seg4' if FLAGS.seg4 else '', qc_gates.min_classes(seq, FLAGS.seg4), engine.arch.n_class))
+        qc_rows = {}
     shard_subjects = list(queue.static)                 # whose earlier-run results this worker measures for --output_csv
     if (FLAGS.process_seq and engine is not None and getattr(FLAGS, 'device_preproc', False) and getattr(FLAGS, 'io_threads', 0) > 0
             and not getattr(FLAGS, 'numpy1_casting', False)):
-        processed, table_time, _ = run_pipelined(FLAGS, engine, data_list, log, csv_rows, queue)
+        processed, table_time, _ = run_pipelined(FLAGS, engine, data_list, log, csv_rows, queue, qc_rows)
         data_list = []
     def one_subject(data, second):
         """One entry of the walk; ``second``: a subject another worker held when this one first came by (--work_stealing)."""
@@ -357,7 +405,7 @@ def run(FLAGS, forward, log=print, engine=None):
                     log(data)
                 log('  Reading {} ...'.format(image_name))
                 nim = nifti.load(image_name)
-                _sequence_subject(FLAGS, (data, data_dir, image_name), nim, forward, engine, log, processed, table_time, csv_rows)
+                _sequence_subject(FLAGS, (data, data_dir, image_name), nim, forward, engine, log, processed, table_time, csv_rows, qc_rows)
             finally:
                 queue.done(data)
         else:
@@ -387,6 +435,8 @@ def run(FLAGS, forward, log=print, engine=None):
         one_subject(data, True)
     if csv_rows is not None:
         write_measures_csv(FLAGS, shard_subjects, csv_rows, log)
+    if qc_rows is not None:
+        write_qc_csv(FLAGS, shard_subjects, qc_rows, log)
     if table_time:
         log('Average segmentation time = {:.3f}s per {}'.format(float(np.mean(table_time)),
                                                                'sequence' if FLAGS.process_seq else 'frame'))

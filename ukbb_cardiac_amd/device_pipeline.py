@@ -140,15 +140,19 @@ def pack_rescaled(vol_ptr, dtype, shape, strides, lo, hi, pad, batch_ptr, stream
                                                 *pad, batch_ptr, stream), 'ukbb_fcn_rescale_pack_t')
 
 
-def segment_sequence_device(image, engine, batch_slices=128, thres=(1, 99), return_aux=False):
+def segment_sequence_device(image, engine, batch_slices=128, thres=(1, 99), return_aux=False, qc=None):
     """(X,Y,Z,T) float32 / uint8 / int16 / uint16 volume -> float64 label volume of the same shape, like
     pipeline.segment_sequence.
 
     ``image`` is NOT modified (the reference clips it in place); callers that
     save image frames afterwards clip them with the returned bounds (``aux['clip']``: the float64
     percentiles; clip_like_reference stores them into an integer frame truncated, as numpy does).
-    ``aux['counts'][t, c]`` = voxels of class c in frame t (input of the ES pick)."""
+    ``aux['counts'][t, c]`` = voxels of class c in frame t (input of the ES pick).  ``qc = (seq_name, seg4)`` (needs
+    ``return_aux``): ``aux['qc']`` = the statistics of that sequence's quality-control gate (device_gate_stats; the input of
+    qc_gates.gate_from_stats) from the labels while they are still on the device."""
     import torch
+    if qc is not None and not return_aux:
+        raise ValueError('qc returns its statistics in aux: pass return_aux')
     if image.ndim != 4:
         raise ValueError('expected a 4-D (X,Y,Z,T) sequence, got shape %s' % (image.shape,))
     _check_dtype(image, 'pipeline.segment_sequence')
@@ -176,7 +180,10 @@ def segment_sequence_device(image, engine, batch_slices=128, thres=(1, 99), retu
     out = np.zeros(image.shape)                                 # float64, as deploy_network.py:92
     out[...] = lab_h
     if return_aux:
-        return out, {'clip': (lo, hi), 'counts': counts.cpu().numpy()}
+        aux = {'clip': (lo, hi), 'counts': counts.cpu().numpy()}
+        if qc is not None:
+            aux['qc'] = device_gate_stats(lab, (X, Y, Z, T), qc[0], qc[1], n_class, stream, aux['counts'])
+        return out, aux
     return out
 
 
@@ -376,6 +383,92 @@ def device_qc_stats(vol_t, lab_t, dtype, n_class, stream=0, min_size=None):
         with np.errstate(all='ignore'):
             means.append(rt(rt(s.value) / n))                      # np.mean: ret.dtype.type(ret / rcount); empty: 0 / 0 = NaN
     return {'n_large': n_large.cpu().numpy(), 'max': mx.cpu().numpy(), 'mean_ed': np.array(means, dtype=rt)}
+
+
+# ---- the short- and long-axis quality-control gates (qc_gates.py) on the labels ukbb_fcn_unpack_labels left in HBM ----------
+
+def gate_buffer_sizes(seq_name, seg4, shape, n_class):
+    """(work, out) int32 counts of the device buffers launch_gate_stats needs for an (X,Y,Z,T) label volume: the work buffer
+    of ukbb_fcn_plane_components (sa: the Z planes of frame 0; la_4ch --seg4: plane 0) or of ukbb_fcn_label_components (the
+    atrial gate: the whole sequence), and the statistics themselves."""
+    from .qc_gates import gate_kind
+    X, Y, Z, T = shape
+    kind = gate_kind(seq_name, seg4)
+    if kind == 'atrium':
+        return 2 * X * Y * Z * T, T * n_class
+    P = Z if kind == 'sa' else 1
+    return 2 * P * n_class + 3 * X * Y * P + (X * Y * P + 3) // 4, P * (3 * n_class + 1)
+
+
+def launch_gate_stats(seq_name, seg4, lab_ptr, shape, n_class, work_ptr, out_ptr, stream):
+    """Enqueue on ``stream`` the statistics of this sequence's gate from the uint8 labels at device address lab_ptr (NIfTI
+    order) into out_ptr; buffers as gate_buffer_sizes (the work buffer 8-byte aligned).  Asynchronous; decode_gate_stats
+    reads the result once it is on the host."""
+    from .qc_gates import PIXEL_THRES, gate_kind
+    X, Y, Z, T = shape
+    kind = gate_kind(seq_name, seg4)
+    if kind == 'atrium':
+        _lib.check(_lib.lib.ukbb_fcn_label_components(lab_ptr, X, Y, Z, T, n_class, PIXEL_THRES, work_ptr, out_ptr, stream),
+                   'ukbb_fcn_label_components')
+        return
+    P = Z if kind == 'sa' else 1                                  # frame 0 comes first in NIfTI order, plane 0 first in it
+    cells = 4 * P * n_class
+    _lib.check(_lib.lib.ukbb_fcn_plane_components(lab_ptr, X, Y, P, n_class, 1, 2, PIXEL_THRES, work_ptr, out_ptr, out_ptr + cells,
+                                                  out_ptr + 2 * cells, out_ptr + 3 * cells, stream), 'ukbb_fcn_plane_components')
+
+
+def decode_gate_stats(seq_name, seg4, out, shape, n_class, counts=None):
+    """The host copy ``out`` (int32) of what launch_gate_stats wrote -> the dict qc_gates.gate_from_stats reads.  The atrial
+    gate also takes the per-frame class counts of ukbb_fcn_unpack_labels."""
+    from .qc_gates import gate_kind
+    X, Y, Z, T = shape
+    kind = gate_kind(seq_name, seg4)
+    out = np.asarray(out, dtype=np.int32)
+    if kind == 'atrium':
+        return {'counts': np.asarray(counts), 'n_large': out[:T * n_class].reshape(T, n_class).copy()}
+    P = Z if kind == 'sa' else 1
+    c = P * n_class
+    return {'count': out[:c].reshape(P, n_class).copy(), 'largest': out[c:2 * c].reshape(P, n_class).copy(),
+            'kept': out[2 * c:3 * c].reshape(P, n_class).copy(), 'union_largest': out[3 * c:3 * c + P].copy()}
+
+
+def device_plane_stats(lab_t, X, Y, P, n_class, a=1, b=2, keep_min=10, stream=0):
+    """qc_gates.plane_stats_host of the first P planes of X*Y uint8 labels (x fastest) of a device tensor:
+    ukbb_fcn_plane_components."""
+    import torch
+    n_work, n_out = gate_buffer_sizes('sa', False, (X, Y, P, 1), n_class)
+    work = torch.empty(n_work, dtype=torch.int32, device=lab_t.device)
+    out = torch.empty(n_out, dtype=torch.int32, device=lab_t.device)
+    c = 4 * P * n_class
+    o = out.data_ptr()
+    _lib.check(_lib.lib.ukbb_fcn_plane_components(lab_t.data_ptr(), X, Y, P, n_class, a, b, keep_min, work.data_ptr(), o, o + c, o + 2 * c,
+                                                  o + 3 * c, stream), 'ukbb_fcn_plane_components')
+    return decode_gate_stats('sa', False, out.cpu().numpy(), (X, Y, P, 1), n_class)
+
+
+def device_gate_stats(lab_t, shape, seq_name, seg4, n_class, stream=0, counts=None):
+    """qc_gates.stats_host of the (X,Y,Z,T) uint8 label volume ``lab_t`` (NIfTI order) on the device.  ``counts``: the per-frame
+    class counts if the caller has them (ukbb_fcn_unpack_labels, as on every path of the deploy script); the atrial gate
+    otherwise takes them from one torch.bincount over the label tensor."""
+    import torch
+    from .qc_gates import gate_kind
+    X, Y, Z, T = shape
+    n_work, n_out = gate_buffer_sizes(seq_name, seg4, shape, n_class)
+    work = torch.empty(n_work, dtype=torch.int32, device=lab_t.device)
+    out = torch.empty(n_out, dtype=torch.int32, device=lab_t.device)
+    launch_gate_stats(seq_name, seg4, lab_t.data_ptr(), shape, n_class, work.data_ptr(), out.data_ptr(), stream)
+    if gate_kind(seq_name, seg4) == 'atrium' and counts is None:
+        # one histogram over (frame, label) keys; labels >= n_class fall into columns that are dropped
+        keys = lab_t[:X * Y * Z * T].view(T, -1).to(torch.int64) + 256 * torch.arange(T, device=lab_t.device)[:, None]
+        counts = torch.bincount(keys.reshape(-1), minlength=256 * T).view(T, 256)[:, :n_class].cpu().numpy()
+    return decode_gate_stats(seq_name, seg4, out.cpu().numpy(), shape, n_class, counts)
+
+
+def device_gate(lab_t, shape, seq_name, seg4, name, n_class, stream=0, counts=None):
+    """(passed, message) of the reference's gate for this sequence (qc_gates.gate_from_stats) from a uint8 label volume on the
+    device; only the few hundred bytes of statistics cross to the host."""
+    from .qc_gates import gate_from_stats
+    return gate_from_stats(device_gate_stats(lab_t, shape, seq_name, seg4, n_class, stream, counts), seq_name, seg4, name)
 
 
 def aortic_lstm_sequence_device(image, engine, z_score=True, weight_R=5, weight_r=0.1, time_step=1, return_aux=False, qc=False):

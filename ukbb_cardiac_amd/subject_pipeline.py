@@ -22,7 +22,8 @@ import queue
 import numpy as np
 
 from . import _lib
-from .device_pipeline import device_dtype_ok, device_percentiles, pack_rescaled
+from .device_pipeline import (decode_gate_stats, device_dtype_ok, device_percentiles, gate_buffer_sizes, launch_gate_stats,
+                              pack_rescaled)
 from .pipeline import pad_amounts
 
 
@@ -41,8 +42,10 @@ class Staged:
 class SubjectPipeline:
     HEADROOM = 4096                                         # bytes of writable pinned memory in front of every staged array
 
-    def __init__(self, engine, max_shape, batch_slices=128, depth=3, thres=(1, 99), extra_inputs=2, pinned_inputs=True):
+    def __init__(self, engine, max_shape, batch_slices=128, depth=3, thres=(1, 99), extra_inputs=2, pinned_inputs=True, qc=None):
         """max_shape: largest (X, Y, Z, T) expected (buffers are sized for it; larger volumes re-allocate).
+        qc = (seq_name, seg4): also compute the statistics of that sequence's quality-control gate (qc_gates.py) from the
+        labels on the compute stream, right behind the unpack; ``Result.qc`` then holds them (None otherwise).
         extra_inputs: pinned input buffers beyond ``depth`` (one per reader thread that may hold one).
         pinned_inputs=False: no pinned input pool at all -- for cohorts whose volumes are produced on the device
         (``submit_generated``; ``stage`` / ``submit`` of host arrays then block forever and must not be used)."""
@@ -51,6 +54,7 @@ class SubjectPipeline:
         self.engine = engine
         self.batch_slices = int(batch_slices)
         self.thres = tuple(thres)
+        self.qc = None if qc is None else (qc[0], bool(qc[1]))
         self.dev = torch.device('cuda', engine.device)
         self.s_in = torch.cuda.Stream(self.dev)
         self.s_cmp = torch.cuda.Stream(self.dev)
@@ -83,6 +87,11 @@ class SubjectPipeline:
         s.d_pred = torch.empty(s.cap_pix, dtype=torch.int32, device=self.dev)
         s.d_lab = torch.empty(s.cap_vox, dtype=torch.uint8, device=self.dev)
         s.d_cnt = torch.empty(T * 16, dtype=torch.int64, device=self.dev)
+        if self.qc is not None:
+            s.cap_qc = gate_buffer_sizes(self.qc[0], self.qc[1], shape, 16)     # n_class <= 16, as d_cnt
+            s.d_qc_work = torch.empty(s.cap_qc[0], dtype=torch.int32, device=self.dev)
+            s.d_qc = torch.empty(s.cap_qc[1], dtype=torch.int32, device=self.dev)
+            s.pin_qc = torch.empty(s.cap_qc[1], dtype=torch.int32, pin_memory=True)
         s.ev_in, s.ev_cmp, s.ev_out = torch.cuda.Event(), torch.cuda.Event(), torch.cuda.Event()
         s.busy = False
         return s
@@ -119,7 +128,11 @@ class SubjectPipeline:
         if slot.busy:
             raise RuntimeError('pipeline full: collect() a result before staging another subject (depth %d)' % self.depth)
         X, Y, Z, T = shape
-        if X * Y * Z * T > slot.cap_vox or pad_amounts(X, Y)[0] * pad_amounts(X, Y)[1] * Z * T > slot.cap_pix or T * 16 > slot.pin_cnt.numel():
+        too_small = X * Y * Z * T > slot.cap_vox or pad_amounts(X, Y)[0] * pad_amounts(X, Y)[1] * Z * T > slot.cap_pix or T * 16 > slot.pin_cnt.numel()
+        if not too_small and self.qc is not None:
+            need = gate_buffer_sizes(self.qc[0], self.qc[1], shape, 16)
+            too_small = need[0] > slot.cap_qc[0] or need[1] > slot.cap_qc[1]
+        if too_small:
             self.torch.cuda.synchronize(self.dev)
             self.slots[self._next] = slot = self._make_slot(shape)
         return slot
@@ -193,11 +206,17 @@ class SubjectPipeline:
                 self.engine.run_device(slot.d_batch.data_ptr() + 4 * i * px, m, X2, Y2, pred_ptr=slot.d_pred.data_ptr() + 4 * i * px, stream=cs)
             _lib.check(_lib.lib.ukbb_fcn_unpack_labels(slot.d_pred.data_ptr(), X, Y, Z, T, X2, Y2, x_pre, y_pre, n_class,
                                                        slot.d_lab.data_ptr(), slot.d_cnt.data_ptr(), cs), 'ukbb_fcn_unpack_labels')
+            if self.qc is not None:
+                launch_gate_stats(self.qc[0], self.qc[1], slot.d_lab.data_ptr(), shape, n_class, slot.d_qc_work.data_ptr(),
+                                  slot.d_qc.data_ptr(), cs)
             slot.ev_cmp.record(self.s_cmp)
         with torch.cuda.stream(self.s_out):
             self.s_out.wait_event(slot.ev_cmp)
             slot.pin_lab[:n].copy_(slot.d_lab[:n], non_blocking=True)
             slot.pin_cnt[:T * n_class].copy_(slot.d_cnt[:T * n_class], non_blocking=True)
+            if self.qc is not None:
+                n_qc = gate_buffer_sizes(self.qc[0], self.qc[1], shape, n_class)[1]
+                slot.pin_qc[:n_qc].copy_(slot.d_qc[:n_qc], non_blocking=True)
             slot.ev_out.record(self.s_out)
         self._inflight.append(slot)
 
@@ -218,9 +237,13 @@ class SubjectPipeline:
         if copy:
             lab = lab.copy(order='F')
         cnt = slot.pin_cnt.numpy()[:T * n_class].reshape(T, n_class).copy()
+        qc = None
+        if self.qc is not None:
+            n_qc = gate_buffer_sizes(self.qc[0], self.qc[1], slot.shape, n_class)[1]
+            qc = decode_gate_stats(self.qc[0], self.qc[1], slot.pin_qc.numpy()[:n_qc], slot.shape, n_class, cnt)
         st, slot.staged = slot.staged, None
         slot.busy = False
-        return Result(self, lab, cnt, slot.clip, st)
+        return Result(self, lab, cnt, slot.clip, st, qc)
 
     def run(self, volumes):
         """Generator: segment an iterable of volumes with up to depth-1 subjects in flight; yields Results in order
@@ -243,8 +266,9 @@ class SubjectPipeline:
 
 
 class Result:
-    def __init__(self, pipe, labels, counts, clip, staged):
+    def __init__(self, pipe, labels, counts, clip, staged, qc=None):
         self._pipe, self.labels, self.counts, self.clip, self._staged = pipe, labels, counts, clip, staged
+        self.qc = qc                                          # the gate statistics (SubjectPipeline(qc=...)), or None
 
     @property
     def image(self):
