@@ -9,7 +9,7 @@ tests/test_fp32_launch_coverage.py shows on the CPU that CASES reaches all of th
 One forward per case.  Each stored map is recomputed in numpy float64 (oracle/fcn_oracle.py conv2d_same / conv2d_transpose_same, the float32 BN fold of
 engine.cpp create()) from the map or maps the engine stored in front of it, so a launch's deviation is its kernel's own; the fused first layer
 (conv0_0 + conv0_1) is graded as a unit from the image, the skip-concat convs from concatenate([skip, upL_t]), the logits from the stored up0 with bias
-and no ReLU.  The FCN squeeze and head launches are graded in tests/test_head_gather_gpu.py.
+and no ReLU.  The FCN squeeze and head launches are graded in tests/test_head_launches_gpu.py.
 Bound, as in tests/test_fp32_layers_gpu.py: max |engine - float64| <= 1e-5 x the layer's largest activation, for every launch.
 
 A batch is made of copies of at most three distinct images, img[i] = distinct[i % 3]: a phantom slice, a uniform-noise slice and a standard-normal
