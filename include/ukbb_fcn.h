@@ -358,6 +358,24 @@ int ukbb_fcn_label_compact(const void *d_vol, int nifti_datatype, int X, int Y, 
 int ukbb_fcn_plane_components(const uint8_t *d_planes, int X, int Y, int P, int n_class, int a, int b, int keep_min, int32_t *d_work,
                               int32_t *d_count, int32_t *d_largest, int32_t *d_kept, int32_t *d_union_largest, void *stream);
 
+/* -- atrial area and length (additive to ABI 11): cardiac_utils.evaluate_atrial_area_length (reference
+ * common/cardiac_utils.py:1655-1736) for every (plane, class) cell of P label planes of X*Y uint8 voxels (x fastest), by the
+ * rules ukbb_cardiac_amd/atrial.py states (frame_stats_host is the specification).  d_out[p][k][8] (int32, all P*n_class*8
+ * written; the cells of class 0 are zero) = size, status, x0, y0, x1, y1, n_hits, 0:
+ *   size    voxels of the largest 8-connected component C of plane == k (ties as ukbb_fcn_plane_components)
+ *   status  0 the class is absent, 1 measured, 2 the major axis is NaN (fewer than 3 voxels, or the centres of the bottom and the
+ *           top third coincide), 3 the axis line misses C
+ *   (x0, y0), (x1, y1)  the pixels of the rasterised axis line inside C that come first and last in the order (d, x*Y + y),
+ *           n_hits their number; d(x, y) = (w0*l0 + w1*l1) + w2*l2, w_i = (a_i0*x + a_i1*y) + a_i3 in float64, one rounding per
+ *           operation.  affine: rows 0..2 of the voxel-to-world matrix, row-major; long_axis: l.  Both finite.
+ * The thirds come from an exact radix select on (order-preserving key of d, x*Y + y), their centres from integer sums, the two
+ * hits from integer minima and maxima: no float atomics, nothing depends on arrival order.  The line is the 8-connected line of
+ * OpenCV (clipLine + LineIterator, left to right) as atrial.line_pixels restates it.  Labels >= n_class are ignored.
+ * d_work: 8-byte aligned, 2*P*n_class + 3*X*Y*P + (X*Y*P + 3)/4 int32 the caller allocates (keys, parents, sizes, first
+ * indices, the map of the winning components).  Asynchronous.  n_class <= 16, P <= 65535, 4*X*Y*P < 2^31. */
+int ukbb_fcn_atrial_area_length(const uint8_t *d_planes, int X, int Y, int P, int n_class, const double affine[12], const double long_axis[3],
+                                int32_t *d_work, int32_t *d_out, void *stream);
+
 /* ---- label-volume files (host only: no device, no stream) ---------------------------------------
  * What the reference does with the result: nib.save of np.zeros(image.shape) filled with the labels
  * (common/deploy_network.py:92,116,136-138; deploy_network_ao.py:189-196) -- for a short-axis subject

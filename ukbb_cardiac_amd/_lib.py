@@ -32,7 +32,7 @@ EXPORTS = [
     'ukbb_fcn_label_components', 'ukbb_fcn_label_max', 'ukbb_fcn_label_compact',
     'ukbb_fcn_set_scratch_budget', 'ukbb_fcn_scratch_bytes', 'ukbb_fcn_cine_scratch_bytes',
     'ukbb_fcn_cine_min_scratch_bytes', 'ukbb_fcn_cine_chunk_windows',
-    'ukbb_fcn_plane_components',
+    'ukbb_fcn_plane_components', 'ukbb_fcn_atrial_area_length',
 ]
 
 
@@ -119,6 +119,7 @@ def _load():
     lib.ukbb_fcn_label_compact.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, i64, i64, i64, vp, C.c_int, vp,
                                            C.POINTER(C.c_uint64), vp]
     lib.ukbb_fcn_plane_components.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
+    lib.ukbb_fcn_atrial_area_length.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, vp, vp]
     lib.ukbb_fcn_set_scratch_budget.argtypes = [vp, C.c_uint64]
     lib.ukbb_fcn_scratch_bytes.restype = C.c_uint64
     lib.ukbb_fcn_scratch_bytes.argtypes = [vp]

@@ -288,6 +288,265 @@ __global__ __launch_bounds__(256) void plane_union_kernel(const unsigned char *_
     atomicMax(&union_largest[gi / plane], size[gi]);
 }
 
+// ---- atrial area and length (ukbb_fcn_atrial_area_length) -------------------------------------------------------------------
+// cardiac_utils.evaluate_atrial_area_length (reference common/cardiac_utils.py:1655-1736) per (plane, class) cell, by the rules
+// of ukbb_cardiac_amd/atrial.py (frame_stats_host is the specification; the numbers below are its).  The planes are labelled
+// as for ukbb_fcn_plane_components; atrial_member_kernel then marks the voxels of every class's winning component, and one
+// workgroup per cell works on that map alone.  Float64 throughout, every operation rounded once (-ffp-contract=off), in the
+// order atrial.projection states; the order of the voxels is the integer order of (key of d, x*Y + y), so the thirds, the sums
+// (integers) and the two extreme hits (integer minima / maxima) do not depend on which lane or wave comes first.
+struct AtrialGeom {
+    double a[12];                                       // rows 0..2 of the affine
+    double l[3];                                        // the long axis
+};
+
+// member[gi] = k if voxel gi belongs to the largest component of its plane's class k (the earliest in scan order among equals)
+__global__ __launch_bounds__(256) void atrial_member_kernel(const unsigned char *__restrict__ lab, long long n, long long plane, int n_class,
+                                                            const int *__restrict__ parent, const int *__restrict__ first,
+                                                            const unsigned long long *__restrict__ keys, unsigned char *__restrict__ member) {
+    const long long gi = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gi >= n) return;
+    const int k = lab[gi];
+    unsigned char m = 0;
+    if (k != 0 && k < n_class) {
+        const unsigned long long key = keys[(size_t)(gi / plane) * n_class + k];   // non-zero: the class has a voxel here
+        if ((unsigned)first[root_of(parent, (int)gi)] == 0xFFFFFFFFu - (unsigned)key) m = (unsigned char)k;
+    }
+    member[gi] = m;
+}
+
+// the order-preserving key of d(x, y); -0.0 counts as 0.0 (d + 0.0)
+__device__ __forceinline__ unsigned long long atrial_key(const AtrialGeom &g, int x, int y) {
+    const double fx = (double)x, fy = (double)y;
+    const double w0 = (g.a[0] * fx + g.a[1] * fy) + g.a[3];
+    const double w1 = (g.a[4] * fx + g.a[5] * fy) + g.a[7];
+    const double w2 = (g.a[8] * fx + g.a[9] * fy) + g.a[11];
+    const double d = ((w0 * g.l[0] + w1 * g.l[1]) + w2 * g.l[2]) + 0.0;
+    const unsigned long long u = (unsigned long long)__double_as_longlong(d);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+
+// cv::clipLine on [0, W-1] x [0, H-1] (atrial._clip_line); false: the line is rejected
+__device__ bool atrial_clip(long long W, long long H, long long &x1, long long &y1, long long &x2, long long &y2) {
+    const long long right = W - 1, bottom = H - 1;
+    int c1 = (x1 < 0) + (x1 > right) * 2 + (y1 < 0) * 4 + (y1 > bottom) * 8;
+    int c2 = (x2 < 0) + (x2 > right) * 2 + (y2 < 0) * 4 + (y2 > bottom) * 8;
+    if ((c1 & c2) == 0 && (c1 | c2) != 0) {
+        if (c1 & 12) {
+            const long long a = c1 < 8 ? 0 : bottom;
+            x1 += (long long)((double)(a - y1) * (double)(x2 - x1) / (double)(y2 - y1));
+            y1 = a;
+            c1 = (x1 < 0) + (x1 > right) * 2;
+        }
+        if (c2 & 12) {
+            const long long a = c2 < 8 ? 0 : bottom;
+            x2 += (long long)((double)(a - y2) * (double)(x2 - x1) / (double)(y2 - y1));
+            y2 = a;
+            c2 = (x2 < 0) + (x2 > right) * 2;
+        }
+        if ((c1 & c2) == 0 && (c1 | c2) != 0) {
+            if (c1) {
+                const long long a = c1 == 1 ? 0 : right;
+                y1 += (long long)((double)(a - x1) * (double)(y2 - y1) / (double)(x2 - x1));
+                x1 = a;
+                c1 = 0;
+            }
+            if (c2) {
+                const long long a = c2 == 1 ? 0 : right;
+                y2 += (long long)((double)(a - x2) * (double)(y2 - y1) / (double)(x2 - x1));
+                x2 = a;
+                c2 = 0;
+            }
+        }
+    }
+    return (c1 | c2) == 0;
+}
+
+// grid (P * n_class), 256 threads: cell = plane * n_class + class; out[cell][8] = size, status, x0, y0, x1, y1, n_hits, 0
+__global__ __launch_bounds__(256) void atrial_cell_kernel(const unsigned char *__restrict__ member, int X, int Y, int n_class,
+                                                          const unsigned long long *__restrict__ keys, AtrialGeom g, int *__restrict__ out) {
+    __shared__ int hist[2][256];
+    __shared__ int scan[2][256];
+    __shared__ int box[4];                              // x min, x max, y min, y max of the component
+    __shared__ int sel_digit[2], sel_rank[2];
+    __shared__ unsigned long long sums[4];              // sum x, sum y of the bottom third; of the top third
+    __shared__ long long line[8];                       // status, start x, y (cv), major dx, dy, minor dx, dy, count
+    __shared__ long long line_d[2];                     // dmaj, dmin
+    __shared__ unsigned long long hit_key[2];           // the smallest and the largest key among the hits
+    __shared__ unsigned hit_idx[2];
+    __shared__ int n_hits;
+    const int tid = threadIdx.x, cell = blockIdx.x, k = cell % n_class;
+    int *o = out + (size_t)cell * 8;
+    const unsigned long long win = k ? keys[cell] : 0;
+    if (win == 0) {                                     // class 0, or no voxel of the class on this plane (uniform: all lanes leave)
+        if (tid < 8) o[tid] = 0;
+        return;
+    }
+    const int size = (int)(win >> 32);
+    const unsigned char *pl = member + (size_t)(cell / n_class) * X * Y;
+    const int plane = X * Y;                            // < 2^29
+    if (tid == 0) {
+        box[0] = X; box[1] = -1; box[2] = Y; box[3] = -1;
+        sums[0] = sums[1] = sums[2] = sums[3] = 0;
+        hit_key[0] = ~0ull; hit_key[1] = 0;
+        hit_idx[0] = 0xFFFFFFFFu; hit_idx[1] = 0;
+        n_hits = 0;
+    }
+    __syncthreads();
+    {
+        int x0 = X, x1 = -1, y0 = Y, y1 = -1;
+        for (int gi = tid; gi < plane; gi += 256) {
+            if (pl[gi] != k) continue;
+            const int x = gi % X, y = gi / X;
+            x0 = x < x0 ? x : x0; x1 = x > x1 ? x : x1;
+            y0 = y < y0 ? y : y0; y1 = y > y1 ? y : y1;
+        }
+        if (x1 >= 0) {
+            atomicMin(&box[0], x0); atomicMax(&box[1], x1);
+            atomicMin(&box[2], y0); atomicMax(&box[3], y1);
+        }
+    }
+    __syncthreads();
+    const int bx0 = box[0], by0 = box[2], bw = box[1] - box[0] + 1, bh = box[3] - box[2] + 1;
+    const long long bn = (long long)bw * bh;            // >= 1: the component has a voxel
+
+    // the elements of ranks k1 and k2 in the order (key, x*Y + y): a most-significant-digit-first radix select over the 12 bytes
+    unsigned long long sel_k[2] = {0, 0};
+    unsigned sel_i[2] = {0, 0};
+    int rank[2] = {(int)(size / 3), (int)(2 * (long long)size / 3)};
+    for (int p = 0; p < 12; ++p) {
+        hist[0][tid] = 0;
+        hist[1][tid] = 0;
+        __syncthreads();
+        for (long long i = tid; i < bn; i += 256) {
+            const int x = bx0 + (int)(i % bw), y = by0 + (int)(i / bw);
+            if (pl[x + (size_t)X * y] != k) continue;
+            const unsigned long long key = atrial_key(g, x, y);
+            const unsigned idx = (unsigned)(x * Y + y);
+            const int digit = p < 8 ? (int)((key >> (56 - 8 * p)) & 255) : (int)((idx >> (24 - 8 * (p - 8))) & 255);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                bool match;
+                if (p == 0) match = true;
+                else if (p <= 8) match = (key >> (64 - 8 * p)) == (sel_k[j] >> (64 - 8 * p));
+                else match = key == sel_k[j] && (idx >> (32 - 8 * (p - 8))) == (sel_i[j] >> (32 - 8 * (p - 8)));
+                if (match) atomicAdd(&hist[j][digit], 1);
+            }
+        }
+        __syncthreads();
+        const int h0 = hist[0][tid], h1 = hist[1][tid];
+        scan[0][tid] = h0;
+        scan[1][tid] = h1;
+        __syncthreads();
+        for (int off = 1; off < 256; off <<= 1) {       // inclusive prefix sums of the two histograms
+            const int v0 = tid >= off ? scan[0][tid - off] : 0, v1 = tid >= off ? scan[1][tid - off] : 0;
+            __syncthreads();
+            scan[0][tid] += v0;
+            scan[1][tid] += v1;
+            __syncthreads();
+        }
+        const int e0 = scan[0][tid] - h0, e1 = scan[1][tid] - h1;
+        if (e0 <= rank[0] && rank[0] < e0 + h0) { sel_digit[0] = tid; sel_rank[0] = rank[0] - e0; }     // one bin holds the rank
+        if (e1 <= rank[1] && rank[1] < e1 + h1) { sel_digit[1] = tid; sel_rank[1] = rank[1] - e1; }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            if (p < 8) sel_k[j] |= (unsigned long long)sel_digit[j] << (56 - 8 * p);
+            else sel_i[j] |= (unsigned)sel_digit[j] << (24 - 8 * (p - 8));
+            rank[j] = sel_rank[j];
+        }
+        __syncthreads();                                // sel_digit is rewritten in the next pass
+    }
+
+    // coordinate sums of the bottom third (below the element of rank k1) and of the top third (from the element of rank k2 on)
+    {
+        unsigned long long s[4] = {0, 0, 0, 0};
+        for (long long i = tid; i < bn; i += 256) {
+            const int x = bx0 + (int)(i % bw), y = by0 + (int)(i / bw);
+            if (pl[x + (size_t)X * y] != k) continue;
+            const unsigned long long key = atrial_key(g, x, y);
+            const unsigned idx = (unsigned)(x * Y + y);
+            if (key < sel_k[0] || (key == sel_k[0] && idx < sel_i[0])) { s[0] += x; s[1] += y; }
+            if (key > sel_k[1] || (key == sel_k[1] && idx >= sel_i[1])) { s[2] += x; s[3] += y; }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            for (int off = 32; off > 0; off >>= 1) s[j] += __shfl_xor(s[j], off);
+            if ((tid & 63) == 0 && s[j]) atomicAdd(&sums[j], s[j]);
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {                                     // the major axis, its end points, the clipped line
+        const int k1 = size / 3, k2 = (int)(2 * (long long)size / 3);
+        const double bx = (double)sums[0] / (double)k1, by = (double)sums[1] / (double)k1;       // k1 = 0: 0 / 0 = NaN
+        const double cx = (double)sums[2] / (double)(size - k2), cy = (double)sums[3] / (double)(size - k2);
+        double m0 = cx - bx, m1 = cy - by;
+        const double norm = sqrt(m0 * m0 + m1 * m1);
+        m0 = m0 / norm;
+        m1 = m1 / norm;
+        const double px = cx + 100.0 * m0, py = cy + 100.0 * m1, qx = cx - 100.0 * m0, qy = cy - 100.0 * m1;
+        long long st = 2;
+        if (px == px && py == py && qx == qx && qy == qy) {
+            // cv points are (y, x): width Y, height X
+            long long x1 = (long long)qy, y1 = (long long)qx, x2 = (long long)py, y2 = (long long)px;
+            st = 3;
+            if (atrial_clip(Y, X, x1, y1, x2, y2)) {
+                long long dx = x2 - x1, dy = y2 - y1, sy = 1;
+                if (dx < 0) { dx = -dx; dy = -dy; x1 = x2; y1 = y2; }
+                if (dy < 0) { dy = -dy; sy = -1; }
+                st = 1;
+                line[1] = x1; line[2] = y1;
+                if (dy > dx) {
+                    line[3] = 0; line[4] = sy; line[5] = 1; line[6] = 0; line[7] = dy + 1;
+                    line_d[0] = dy; line_d[1] = dx;
+                } else {
+                    line[3] = 1; line[4] = 0; line[5] = 0; line[6] = sy; line[7] = dx + 1;
+                    line_d[0] = dx; line_d[1] = dy;
+                }
+            }
+        }
+        line[0] = st;
+    }
+    __syncthreads();
+    int status = (int)line[0];
+    if (status == 1) {
+        // pixel i of the line in closed form: i major steps and ceil((2 dmin i - dmaj) / (2 dmaj)) minor steps (atrial.minor_steps)
+        const long long count = line[7], dmaj = line_d[0], dmin = line_d[1];
+        for (int pass = 0; pass < 2; ++pass) {
+            for (long long i = tid; i < count; i += 256) {
+                const long long mi = dmaj == 0 ? 0 : (2 * dmin * i + dmaj - 1) / (2 * dmaj);
+                const long long cvx = line[1] + i * line[3] + mi * line[5], cvy = line[2] + i * line[4] + mi * line[6];
+                if (cvx < 0 || cvx >= Y || cvy < 0 || cvy >= X) continue;           // never after the clip; a guard all the same
+                const int x = (int)cvy, y = (int)cvx;
+                if (pl[x + (size_t)X * y] != k) continue;
+                const unsigned long long key = atrial_key(g, x, y);
+                const unsigned idx = (unsigned)(x * Y + y);
+                if (pass == 0) {
+                    atomicMin(&hit_key[0], key);
+                    atomicMax(&hit_key[1], key);
+                    atomicAdd(&n_hits, 1);
+                } else {
+                    if (key == hit_key[0]) atomicMin(&hit_idx[0], idx);
+                    if (key == hit_key[1]) atomicMax(&hit_idx[1], idx);
+                }
+            }
+            __syncthreads();
+        }
+        if (n_hits == 0) status = 3;
+    }
+    if (tid == 0) {
+        const bool ok = status == 1;
+        o[0] = size;
+        o[1] = status;
+        o[2] = ok ? (int)(hit_idx[0] / (unsigned)Y) : 0;
+        o[3] = ok ? (int)(hit_idx[0] % (unsigned)Y) : 0;
+        o[4] = ok ? (int)(hit_idx[1] / (unsigned)Y) : 0;
+        o[5] = ok ? (int)(hit_idx[1] % (unsigned)Y) : 0;
+        o[6] = ok ? n_hits : 0;
+        o[7] = 0;
+    }
+}
+
 // ---- masked maximum ----------------------------------------------------------------------------------------------------
 // The maximum as an unsigned key whose integer order is numpy's: NaN above everything (np.max propagates it), then the value
 // order; 0 = no voxel (the key of every value is >= 1).  Integer maxima are order-independent, so the result does not depend
@@ -441,6 +700,49 @@ int ukbb_fcn_plane_components(const uint8_t *d_planes, int X, int Y, int P, int 
                        (const int *)size, d_union_largest);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("plane_components: launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
+    return UKBB_OK;
+}
+
+int ukbb_fcn_atrial_area_length(const uint8_t *d_planes, int X, int Y, int P, int n_class, const double affine[12], const double long_axis[3],
+                                int32_t *d_work, int32_t *d_out, void *stream) {
+    const long long plane = X >= 1 && Y >= 1 ? (long long)X * Y : 0;
+    const long long n = plane >= 1 && plane <= 0x1FFFFFFFll && P >= 1 && P <= 65535 ? plane * P : 0;
+    bool finite = affine && long_axis;
+    for (int i = 0; finite && i < 12; ++i) finite = std::isfinite(affine[i]);
+    for (int i = 0; finite && i < 3; ++i) finite = std::isfinite(long_axis[i]);
+    if (!d_planes || !d_work || !d_out || !finite || n < 1 || 4 * n > 0x7FFFFFFFll || n_class < 1 || n_class > MAXC ||
+        ((uintptr_t)d_work & 7)) {
+        set_error("atrial_area_length: bad argument (n_class 1..16, P <= 65535, 4*X*Y*P < 2^31, finite affine and long axis, d_work 8-byte aligned)");
+        return UKBB_EINVAL;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int cells = P * n_class;
+    // d_work: keys [P*n_class] uint64 | parent [n] | size [n] | first [n] int32 | member [n] uint8
+    unsigned long long *keys = reinterpret_cast<unsigned long long *>(d_work);
+    int *parent = d_work + 2 * (size_t)cells, *size = parent + n, *first = size + n;
+    unsigned char *member = reinterpret_cast<unsigned char *>(first + n);
+    // the class totals plane_init_kernel / plane_root_kernel also keep are not asked for here: they go to the first 2*cells + P
+    // of the 8*cells output cells, every one of which atrial_cell_kernel writes afterwards
+    int *count = d_out, *kept = d_out + cells, *unused = d_out + 2 * (size_t)cells;
+    AtrialGeom g;
+    for (int i = 0; i < 12; ++i) g.a[i] = affine[i];
+    for (int i = 0; i < 3; ++i) g.l[i] = long_axis[i];
+    const unsigned tiles = (unsigned)(((X + TILE - 1) / TILE) * ((Y + TILE - 1) / TILE));
+    const unsigned nb = (unsigned)((n + 255) / 256);
+    const unsigned nb_init = (unsigned)(((n > cells ? n : (long long)cells) + 255) / 256);
+    hipLaunchKernelGGL(plane_init_kernel, dim3(nb_init), dim3(256), 0, s, n, cells, P, first, keys, count, kept, unused);
+    hipLaunchKernelGGL(ccl_local_kernel, dim3(tiles, (unsigned)P), dim3(256), 0, s, d_planes, X, Y, parent, size);
+    hipLaunchKernelGGL(ccl_border_kernel, dim3(nb), dim3(256), 0, s, d_planes, X, Y, 1, n, parent);
+    hipLaunchKernelGGL(ccl_size_kernel, dim3(nb), dim3(256), 0, s, d_planes, n, (const int *)parent, size);
+    hipLaunchKernelGGL(plane_first_kernel, dim3(nb), dim3(256), 0, s, d_planes, X, Y, n, (const int *)parent, first);
+    hipLaunchKernelGGL(plane_root_kernel, dim3(nb), dim3(256), 0, s, d_planes, n, plane, n_class, 1, (const int *)parent, (const int *)size,
+                       (const int *)first, keys, count, kept);
+    hipLaunchKernelGGL(atrial_member_kernel, dim3(nb), dim3(256), 0, s, d_planes, n, plane, n_class, (const int *)parent, (const int *)first,
+                       (const unsigned long long *)keys, member);
+    hipLaunchKernelGGL(atrial_cell_kernel, dim3((unsigned)cells), dim3(256), 0, s, (const unsigned char *)member, X, Y, n_class,
+                       (const unsigned long long *)keys, g, d_out);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("atrial_area_length: launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
     return UKBB_OK;
 }
 

@@ -15,7 +15,8 @@ and writes the same files (``deploy_network.py:136-151,207-216``):
 ``--model_path`` names ``<model_path>.ukbbw``.
 
 Extra flags (not in the reference): ``--device``, ``--batch_slices``,
-``--num_shards`` / ``--shard_index`` (multi-GPU batch split), ``--output_csv``, ``--qc_csv``.
+``--num_shards`` / ``--shard_index`` (multi-GPU batch split), ``--output_csv``, ``--qc_csv``,
+``--atrial_csv``.
 """
 import os
 import sys
@@ -26,7 +27,7 @@ import numpy as np
 if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from ukbb_cardiac_amd import measures, nifti, pipeline, qc_gates   # noqa: E402
+from ukbb_cardiac_amd import atrial, measures, nifti, pipeline, qc_gates   # noqa: E402
 from ukbb_cardiac_amd.flags import FlagError, FlagSet              # noqa: E402
 from ukbb_cardiac_amd.shard import ClaimQueue, apply_cpu_set_from_env, default_device, shard_from_env   # noqa: E402
 
@@ -63,6 +64,12 @@ def define_flags():
                      'la_4ch --seg4: la_pass_quality_control; la_2ch, la_4ch: atrium_pass_quality_control), from component statistics of '
                      'the labels while they are on the GPU: columns gate, passed, message.  Subjects already segmented by an earlier '
                      'run are gated from their files.')
+    fs.DEFINE_string('atrial_csv', '', '--seq_name la_2ch or la_4ch (without --seg4), sequence mode: also write what '
+                     'cardiac_utils.evaluate_atrial_area_length measures on every frame -- one row per (subject, frame, label): the component '
+                     'size, the status, the two end pixels of the long-axis intersection, area (cm2), length (cm), the two landmarks in world '
+                     'coordinates and the verdict of the atrial gate -- from the labels while they are on the GPU.  The long axis comes from '
+                     '<subject>/sa.nii.gz; a subject without it gets no rows.  eval_atrial_volume.py --frames_2ch / --frames_4ch turns two '
+                     'such files into the table of long_axis/eval_atrial_volume.py.')
     fs.DEFINE_integer('num_shards', env_cnt, 'Number of workers sharing data_dir.')
     fs.DEFINE_integer('shard_index', env_idx, 'This worker: subjects i with i % num_shards == shard_index.')
     fs.DEFINE_boolean('work_stealing', True, 'With num_shards > 1: after its own share a worker takes subjects of the other shards that '
@@ -104,7 +111,7 @@ def sequence_on_device(FLAGS, engine, image):
     return device_pipeline.device_dtype_ok(image.dtype)
 
 
-def run_pipelined(FLAGS, engine, data_list, log=print, csv_rows=None, queue=None, qc_rows=None):
+def run_pipelined(FLAGS, engine, data_list, log=print, csv_rows=None, queue=None, qc_rows=None, atrial_rows=None):
     """Sequence mode with subjects overlapped: reader threads decompress the next files into pinned staging buffers,
     the GPU thread (this one) keeps up to two subjects in flight on three streams (subject_pipeline.SubjectPipeline),
     writer threads expand the uint8 labels to the reference's float64 volume, gzip and save.  Same files, byte for byte,
@@ -153,7 +160,7 @@ def run_pipelined(FLAGS, engine, data_list, log=print, csv_rows=None, queue=None
             with mk:
                 if state['pipe'] is None:                  # sized by the first volume; bigger ones fall back below
                     state['pipe'] = SubjectPipeline(engine, shape, FLAGS.batch_slices, depth=depth, extra_inputs=window,
-                                                    qc=None if qc_rows is None else (seq, FLAGS.seg4))
+                                                    qc=None if qc_rows is None else (seq, FLAGS.seg4), atrial=atrial_rows is not None)
             try:
                 return state['pipe'].stage(shape, dt).array, SubjectPipeline.HEADROOM
             except ValueError:
@@ -183,7 +190,7 @@ def run_pipelined(FLAGS, engine, data_list, log=print, csv_rows=None, queue=None
     futures = {}
     inflight = []                                       # (item, nim, t_submit)
 
-    def finish(item, nim, t0):
+    def finish(item, nim, t0, geom=None):
         data, data_dir, image_name = item
         res = state['pipe'].collect()
         seg_time = time.time() - t0
@@ -199,6 +206,8 @@ def run_pipelined(FLAGS, engine, data_list, log=print, csv_rows=None, queue=None
             csv_rows[data] = measures.sa_row(res.counts, nim.header['pixdim'])
         if qc_rows is not None:
             record_gate(FLAGS, qc_rows, data, data_dir, res.qc, log)
+        if geom is not None:
+            record_atrial(atrial_rows, data, res.atrial, nim, qc_rows[data][0])
         if FLAGS.save_seg:
             log('  Saving segmentation ...')
             # the saved frames are the CLIPPED intensities (alias quirk)
@@ -238,15 +247,16 @@ def run_pipelined(FLAGS, engine, data_list, log=print, csv_rows=None, queue=None
                     finish(*inflight.pop(0))
                 log(item[0])
                 try:
-                    _sequence_subject(FLAGS, item, nim, None, engine, log, processed, table_time, csv_rows, qc_rows)
+                    _sequence_subject(FLAGS, item, nim, None, engine, log, processed, table_time, csv_rows, qc_rows, atrial_rows)
                 finally:
                     release(item[0])
                 top_up()
                 continue
             if len(inflight) >= depth - 1:
                 finish(*inflight.pop(0))
-            pipe.submit(image)
-            inflight.append((item, nim, time.time()))
+            geom = None if atrial_rows is None else atrial_geometry(item[1], nim, log)
+            pipe.submit(image, atrial=geom)
+            inflight.append((item, nim, time.time(), geom))
             top_up()
         while inflight:
             finish(*inflight.pop(0))
@@ -269,7 +279,26 @@ def record_gate(FLAGS, qc_rows, data, data_dir, stats, log):
         log(message)
 
 
-def _sequence_subject(FLAGS, item, nim, forward, engine, log, processed, table_time, csv_rows=None, qc_rows=None):
+def atrial_geometry(data_dir, nim, log):
+    """--atrial_csv: (affine of the long-axis image, long axis) for this subject, the long axis from the short-axis header as
+    eval_atrial_volume.py:45-48 -- or None, logged, for a subject without sa.nii.gz (the reference skips it) or with more than one
+    slice."""
+    sa_name = '{0}/sa.nii.gz'.format(data_dir)
+    if not os.path.exists(sa_name):
+        log('  Directory {0} does not contain sa.nii.gz: no long axis, no atrial measures.'.format(data_dir))
+        return None
+    if nim.shape[2] != 1:
+        log('  {0} slices: the atrial measures read a single-slice long-axis sequence. Skip.'.format(nim.shape[2]))
+        return None
+    return nim.affine, atrial.long_axis_from_sa(nifti.load_header(sa_name)['affine'])
+
+
+def record_atrial(atrial_rows, data, stats, nim, gate_passed):
+    """--atrial_csv: the rows of this subject from its statistics (atrial.frame_stats_host / device_pipeline.device_atrial_stats)."""
+    atrial_rows[data] = atrial.frame_rows(stats, nim.affine, nim.header['pixdim'], gate_passed)
+
+
+def _sequence_subject(FLAGS, item, nim, forward, engine, log, processed, table_time, csv_rows=None, qc_rows=None, atrial_rows=None):
     """One subject of sequence mode, start to finish on this thread (deploy_network.py:80-151)."""
     data, data_dir, image_name = item
     seq, pre = FLAGS.seq_name, seg_prefix(FLAGS)
@@ -281,10 +310,11 @@ def _sequence_subject(FLAGS, item, nim, forward, engine, log, processed, table_t
     t0 = time.time()
     np1 = bool(getattr(FLAGS, 'numpy1_casting', False))
     on_device = sequence_on_device(FLAGS, engine, image)
+    geom = None if atrial_rows is None else atrial_geometry(data_dir, nim, log)
     if on_device:
         from ukbb_cardiac_amd import device_pipeline
         pred, aux = device_pipeline.segment_sequence_device(image, engine, FLAGS.batch_slices, return_aux=True,
-                                                            qc=None if qc_rows is None else (seq, FLAGS.seg4))
+                                                            qc=None if qc_rows is None else (seq, FLAGS.seg4), atrial=geom)
     else:
         if forward is None:
             forward = lambda b: {'pred': engine.run(b, want_prob=False)['pred']}
@@ -305,6 +335,10 @@ def _sequence_subject(FLAGS, item, nim, forward, engine, log, processed, table_t
     if qc_rows is not None:
         n_class = None if engine is None else engine.arch.n_class
         record_gate(FLAGS, qc_rows, data, data_dir, aux['qc'] if on_device else qc_gates.stats_host(pred, seq, FLAGS.seg4, n_class), log)
+    if geom is not None:
+        n_class = qc_gates.min_classes(seq) if engine is None else engine.arch.n_class
+        record_atrial(atrial_rows, data, aux['atrial'] if on_device else atrial.frame_stats_host(pred[:, :, 0, :], n_class, *geom), nim,
+                      qc_rows[data][0])
     if FLAGS.save_seg:
         log('  Saving segmentation ...')
         frames = {}
@@ -354,6 +388,29 @@ def write_qc_csv(FLAGS, subjects, qc_rows, log=print):
     log('Quality-control verdicts of {0} subjects written to {1}'.format(len(rows), path))
 
 
+def write_atrial_csv(FLAGS, subjects, atrial_rows, qc_rows, n_class, log=print):
+    """--atrial_csv for this worker's subjects, sorted: rows of this run from atrial_rows; a subject segmented by an earlier run
+    (skipped above) is measured from its label file on the host (atrial.frame_stats_host) if it has an sa.nii.gz.  Same sharing
+    between workers as write_measures_csv."""
+    seq = FLAGS.seq_name
+    rows = []
+    for data in sorted(set(subjects) | set(atrial_rows)):
+        data_dir = os.path.join(FLAGS.data_dir, data)
+        seg_name = '{0}/seg_{1}.nii.gz'.format(data_dir, seq)
+        if data not in atrial_rows and os.path.isdir(data_dir) and os.path.exists(seg_name) and os.path.exists('{0}/sa.nii.gz'.format(data_dir)):
+            nim = nifti.load(seg_name)
+            seg = nim.get_data()
+            geom = atrial_geometry(data_dir, nim, log) if seg.ndim == 4 else None
+            if geom is not None:
+                if data not in qc_rows:
+                    record_gate(FLAGS, qc_rows, data, data_dir, qc_gates.stats_host(seg, seq, False), log)
+                record_atrial(atrial_rows, data, atrial.frame_stats_host(seg[:, :, 0, :], n_class, *geom), nim, qc_rows[data][0])
+        rows += [(data, r) for r in atrial_rows.get(data, [])]
+    path = measures.shard_csv_name(FLAGS.atrial_csv, FLAGS.shard_index, FLAGS.num_shards)
+    atrial.write_frames_csv(path, rows)
+    log('Atrial measures of {0} frames and labels written to {1}'.format(len(rows), path))
+
+
 def run(FLAGS, forward, log=print, engine=None):
     """The subject loop of deploy_network.py:52-225 with ``forward`` standing for sess.run.
     With ``engine`` (and --device_preproc) float32 sequences take the device pipeline."""
@@ -377,10 +434,21 @@ def run(FLAGS, forward, log=print, engine=None):
             raise ValueError('--qc_csv: the gate of --seq_name {0}{1} reads {2} classes, the model has {3}'.format(
                 seq, ' --seg4' if FLAGS.seg4 else '', qc_gates.min_classes(seq, FLAGS.seg4), engine.arch.n_class))
         qc_rows = {}
+    atrial_rows = None
+    if getattr(FLAGS, 'atrial_csv', ''):
+        if seq not in ('la_2ch', 'la_4ch') or FLAGS.seg4 or not FLAGS.process_seq:
+            raise ValueError('--atrial_csv measures the atria of long_axis/eval_atrial_volume.py: it needs --seq_name la_2ch or la_4ch '
+                             'without --seg4, in sequence mode')
+        if engine is not None and engine.arch.n_class < qc_gates.min_classes(seq):
+            raise ValueError('--atrial_csv: --seq_name {0} has {1} classes, the model has {2}'.format(seq, qc_gates.min_classes(seq),
+                                                                                                   engine.arch.n_class))
+        atrial_rows = {}
+        if qc_rows is None:
+            qc_rows = {}                                # the rows carry the gate's verdict: gated, though no --qc_csv is written
     shard_subjects = list(queue.static)                 # whose earlier-run results this worker measures for --output_csv
     if (FLAGS.process_seq and engine is not None and getattr(FLAGS, 'device_preproc', False) and getattr(FLAGS, 'io_threads', 0) > 0
             and not getattr(FLAGS, 'numpy1_casting', False)):
-        processed, table_time, _ = run_pipelined(FLAGS, engine, data_list, log, csv_rows, queue, qc_rows)
+        processed, table_time, _ = run_pipelined(FLAGS, engine, data_list, log, csv_rows, queue, qc_rows, atrial_rows)
         data_list = []
     def one_subject(data, second):
         """One entry of the walk; ``second``: a subject another worker held when this one first came by (--work_stealing)."""
@@ -405,7 +473,8 @@ def run(FLAGS, forward, log=print, engine=None):
                     log(data)
                 log('  Reading {} ...'.format(image_name))
                 nim = nifti.load(image_name)
-                _sequence_subject(FLAGS, (data, data_dir, image_name), nim, forward, engine, log, processed, table_time, csv_rows, qc_rows)
+                _sequence_subject(FLAGS, (data, data_dir, image_name), nim, forward, engine, log, processed, table_time, csv_rows, qc_rows,
+                                  atrial_rows)
             finally:
                 queue.done(data)
         else:
@@ -435,7 +504,9 @@ def run(FLAGS, forward, log=print, engine=None):
         one_subject(data, True)
     if csv_rows is not None:
         write_measures_csv(FLAGS, shard_subjects, csv_rows, log)
-    if qc_rows is not None:
+    if atrial_rows is not None:
+        write_atrial_csv(FLAGS, shard_subjects, atrial_rows, qc_rows, qc_gates.min_classes(seq) if engine is None else engine.arch.n_class, log)
+    if getattr(FLAGS, 'qc_csv', ''):
         write_qc_csv(FLAGS, shard_subjects, qc_rows, log)
     if table_time:
         log('Average segmentation time = {:.3f}s per {}'.format(float(np.mean(table_time)),

@@ -140,7 +140,7 @@ def pack_rescaled(vol_ptr, dtype, shape, strides, lo, hi, pad, batch_ptr, stream
                                                 *pad, batch_ptr, stream), 'ukbb_fcn_rescale_pack_t')
 
 
-def segment_sequence_device(image, engine, batch_slices=128, thres=(1, 99), return_aux=False, qc=None):
+def segment_sequence_device(image, engine, batch_slices=128, thres=(1, 99), return_aux=False, qc=None, atrial=None):
     """(X,Y,Z,T) float32 / uint8 / int16 / uint16 volume -> float64 label volume of the same shape, like
     pipeline.segment_sequence.
 
@@ -149,10 +149,13 @@ def segment_sequence_device(image, engine, batch_slices=128, thres=(1, 99), retu
     percentiles; clip_like_reference stores them into an integer frame truncated, as numpy does).
     ``aux['counts'][t, c]`` = voxels of class c in frame t (input of the ES pick).  ``qc = (seq_name, seg4)`` (needs
     ``return_aux``): ``aux['qc']`` = the statistics of that sequence's quality-control gate (device_gate_stats; the input of
-    qc_gates.gate_from_stats) from the labels while they are still on the device."""
+    qc_gates.gate_from_stats) from the labels while they are still on the device.  ``atrial = (affine, long_axis)`` (needs
+    ``return_aux``, Z = 1): ``aux['atrial']`` = device_atrial_stats of the labels, [T, n_class, 8]."""
     import torch
     if qc is not None and not return_aux:
         raise ValueError('qc returns its statistics in aux: pass return_aux')
+    if atrial is not None and not return_aux:
+        raise ValueError('atrial returns its statistics in aux: pass return_aux')
     if image.ndim != 4:
         raise ValueError('expected a 4-D (X,Y,Z,T) sequence, got shape %s' % (image.shape,))
     _check_dtype(image, 'pipeline.segment_sequence')
@@ -183,6 +186,8 @@ def segment_sequence_device(image, engine, batch_slices=128, thres=(1, 99), retu
         aux = {'clip': (lo, hi), 'counts': counts.cpu().numpy()}
         if qc is not None:
             aux['qc'] = device_gate_stats(lab, (X, Y, Z, T), qc[0], qc[1], n_class, stream, aux['counts'])
+        if atrial is not None:
+            aux['atrial'] = device_atrial_stats(lab, (X, Y, Z, T), n_class, atrial[0], atrial[1], stream)
         return out, aux
     return out
 
@@ -469,6 +474,45 @@ def device_gate(lab_t, shape, seq_name, seg4, name, n_class, stream=0, counts=No
     device; only the few hundred bytes of statistics cross to the host."""
     from .qc_gates import gate_from_stats
     return gate_from_stats(device_gate_stats(lab_t, shape, seq_name, seg4, n_class, stream, counts), seq_name, seg4, name)
+
+
+# ---- atrial area and length (atrial.py) on the labels ukbb_fcn_unpack_labels left in HBM --------------------------------------
+
+def atrial_buffer_sizes(shape, n_class):
+    """(work, out) int32 counts of the device buffers launch_atrial_stats needs for an (X,Y,1,T) label volume: the work buffer
+    of ukbb_fcn_atrial_area_length (the T frames are its planes) and the T*n_class*8 statistics."""
+    X, Y, Z, T = shape
+    return 2 * T * n_class + 3 * X * Y * T + (X * Y * T + 3) // 4, T * n_class * 8
+
+
+def launch_atrial_stats(lab_ptr, shape, n_class, affine, long_axis, work_ptr, out_ptr, stream):
+    """Enqueue on ``stream`` the atrial statistics (atrial.frame_stats_host) of the uint8 labels at device address lab_ptr
+    (NIfTI order, one slice: every frame a plane) into out_ptr; buffers as atrial_buffer_sizes (the work buffer 8-byte aligned).
+    affine: the voxel-to-world matrix of the long-axis image; long_axis: atrial.long_axis_from_sa.  Asynchronous;
+    decode_atrial_stats reads the result once it is on the host."""
+    X, Y, Z, T = shape
+    if Z != 1:
+        raise ValueError('the atrial measures read a single-slice long-axis sequence, got Z = %d' % Z)
+    a = (C.c_double * 12)(*[float(v) for v in np.asarray(affine, np.float64)[:3, :4].ravel()])
+    l = (C.c_double * 3)(*[float(v) for v in np.asarray(long_axis, np.float64).ravel()[:3]])
+    _lib.check(_lib.lib.ukbb_fcn_atrial_area_length(lab_ptr, X, Y, T, n_class, a, l, work_ptr, out_ptr, stream), 'ukbb_fcn_atrial_area_length')
+
+
+def decode_atrial_stats(out, shape, n_class):
+    """The host copy ``out`` (int32) of what launch_atrial_stats wrote -> [T, n_class, 8]."""
+    T = shape[3]
+    return np.asarray(out, dtype=np.int32)[:T * n_class * 8].reshape(T, n_class, 8).copy()
+
+
+def device_atrial_stats(lab_t, shape, n_class, affine, long_axis, stream=0):
+    """atrial.frame_stats_host of the (X,Y,1,T) uint8 label volume ``lab_t`` (NIfTI order) on the device; only the T*n_class*32
+    bytes of statistics cross to the host."""
+    import torch
+    n_work, n_out = atrial_buffer_sizes(shape, n_class)
+    work = torch.empty(n_work, dtype=torch.int32, device=lab_t.device)
+    out = torch.empty(n_out, dtype=torch.int32, device=lab_t.device)
+    launch_atrial_stats(lab_t.data_ptr(), shape, n_class, affine, long_axis, work.data_ptr(), out.data_ptr(), stream)
+    return decode_atrial_stats(out.cpu().numpy(), shape, n_class)
 
 
 def aortic_lstm_sequence_device(image, engine, z_score=True, weight_R=5, weight_r=0.1, time_step=1, return_aux=False, qc=False):

@@ -129,9 +129,11 @@ def shard_csv_name(path, shard_index, num_shards):
     return path if num_shards <= 1 else '%s.shard%d-of-%d' % (path, shard_index, num_shards)
 
 
-def merge_shard_csv(path, num_shards, remove=True):
+def merge_shard_csv(path, num_shards, remove=True, key_columns=1):
     """Concatenate the per-worker parts into ``path`` with the subjects in sorted order (the reference's loop order,
-    eval_ventricular_volume.py:28).  Missing parts (a worker with no subjects writes none) are skipped."""
+    eval_ventricular_volume.py:28).  Missing parts (a worker with no subjects writes none) are skipped.  key_columns > 1: a
+    table with several rows per subject (atrial.FRAME_COLUMNS); the columns after the subject that complete the row's key are
+    integers."""
     import csv
     import os
     header, rows, parts = None, [], []
@@ -147,10 +149,11 @@ def merge_shard_csv(path, num_shards, remove=True):
             rows += rd[1:]
     if header is None:
         return False
-    rows.sort(key=lambda r: r[0])
+    key = lambda r: (r[0],) + tuple(int(v) for v in r[1:key_columns])
+    rows.sort(key=key)
     # one row per subject: with work stealing the worker that segmented a subject and the static owner of its index may both
     # have measured it (same counts, same text); the first one stays
-    rows = [r for i, r in enumerate(rows) if i == 0 or r[0] != rows[i - 1][0]]
+    rows = [r for i, r in enumerate(rows) if i == 0 or key(r) != key(rows[i - 1])]
     tmp = '%s.tmp.%d' % (path, os.getpid())
     with open(tmp, 'w', newline='') as f:
         wr = csv.writer(f, lineterminator='\n')

@@ -22,8 +22,8 @@ import queue
 import numpy as np
 
 from . import _lib
-from .device_pipeline import (decode_gate_stats, device_dtype_ok, device_percentiles, gate_buffer_sizes, launch_gate_stats,
-                              pack_rescaled)
+from .device_pipeline import (atrial_buffer_sizes, decode_atrial_stats, decode_gate_stats, device_dtype_ok, device_percentiles,
+                              gate_buffer_sizes, launch_atrial_stats, launch_gate_stats, pack_rescaled)
 from .pipeline import pad_amounts
 
 
@@ -42,10 +42,12 @@ class Staged:
 class SubjectPipeline:
     HEADROOM = 4096                                         # bytes of writable pinned memory in front of every staged array
 
-    def __init__(self, engine, max_shape, batch_slices=128, depth=3, thres=(1, 99), extra_inputs=2, pinned_inputs=True, qc=None):
+    def __init__(self, engine, max_shape, batch_slices=128, depth=3, thres=(1, 99), extra_inputs=2, pinned_inputs=True, qc=None, atrial=False):
         """max_shape: largest (X, Y, Z, T) expected (buffers are sized for it; larger volumes re-allocate).
         qc = (seq_name, seg4): also compute the statistics of that sequence's quality-control gate (qc_gates.py) from the
         labels on the compute stream, right behind the unpack; ``Result.qc`` then holds them (None otherwise).
+        atrial: reserve the buffers of the atrial statistics (atrial.py); a subject submitted with ``atrial=(affine, long_axis)``
+        then gets them computed behind the unpack as well, into ``Result.atrial`` [T, n_class, 8].
         extra_inputs: pinned input buffers beyond ``depth`` (one per reader thread that may hold one).
         pinned_inputs=False: no pinned input pool at all -- for cohorts whose volumes are produced on the device
         (``submit_generated``; ``stage`` / ``submit`` of host arrays then block forever and must not be used)."""
@@ -55,6 +57,7 @@ class SubjectPipeline:
         self.batch_slices = int(batch_slices)
         self.thres = tuple(thres)
         self.qc = None if qc is None else (qc[0], bool(qc[1]))
+        self.atrial = bool(atrial)
         self.dev = torch.device('cuda', engine.device)
         self.s_in = torch.cuda.Stream(self.dev)
         self.s_cmp = torch.cuda.Stream(self.dev)
@@ -92,6 +95,11 @@ class SubjectPipeline:
             s.d_qc_work = torch.empty(s.cap_qc[0], dtype=torch.int32, device=self.dev)
             s.d_qc = torch.empty(s.cap_qc[1], dtype=torch.int32, device=self.dev)
             s.pin_qc = torch.empty(s.cap_qc[1], dtype=torch.int32, pin_memory=True)
+        if self.atrial:
+            s.cap_at = atrial_buffer_sizes(shape, 16)
+            s.d_at_work = torch.empty(s.cap_at[0], dtype=torch.int32, device=self.dev)
+            s.d_at = torch.empty(s.cap_at[1], dtype=torch.int32, device=self.dev)
+            s.pin_at = torch.empty(s.cap_at[1], dtype=torch.int32, pin_memory=True)
         s.ev_in, s.ev_cmp, s.ev_out = torch.cuda.Event(), torch.cuda.Event(), torch.cuda.Event()
         s.busy = False
         return s
@@ -132,17 +140,23 @@ class SubjectPipeline:
         if not too_small and self.qc is not None:
             need = gate_buffer_sizes(self.qc[0], self.qc[1], shape, 16)
             too_small = need[0] > slot.cap_qc[0] or need[1] > slot.cap_qc[1]
+        if not too_small and self.atrial:
+            need = atrial_buffer_sizes(shape, 16)
+            too_small = need[0] > slot.cap_at[0] or need[1] > slot.cap_at[1]
         if too_small:
             self.torch.cuda.synchronize(self.dev)
             self.slots[self._next] = slot = self._make_slot(shape)
         return slot
 
     # ---- submit / collect -----------------------------------------------------------------------------
-    def submit(self, image):
+    def submit(self, image, atrial=None):
         """Enqueue one (X,Y,Z,T) float32 / uint8 / int16 / uint16 volume: a ``Staged`` object / the array ``stage()`` handed
         out (used in place), or any other array (copied into a pinned buffer first: one host memcpy).  Returns once the exact
         percentiles of the volume are known (the copy-in stream is waited for, the compute stream is not).  Subjects of
-        different dtypes may follow each other: the select and pack kernels are chosen per subject."""
+        different dtypes may follow each other: the select and pack kernels are chosen per subject.
+        atrial = (affine, long_axis) (a pipeline made with ``atrial=True``, Z = 1): also the atrial statistics of this subject."""
+        if atrial is not None and not self.atrial:
+            raise ValueError('this pipeline was made without the atrial buffers')
         if isinstance(image, Staged):
             st = image
             with self._lock:
@@ -157,7 +171,7 @@ class SubjectPipeline:
                 with self._lock:
                     self._staged.pop(id(st.array), None)
                 st.array[...] = image
-        self._enqueue(st.array.shape, st, None)
+        self._enqueue(st.array.shape, st, None, atrial)
 
     def submit_generated(self, shape, fill):
         """Enqueue one (X,Y,Z,T) float32 volume that is PRODUCED ON THE DEVICE: ``fill(d_ptr, n, stream)`` enqueues, on the copy-in
@@ -168,7 +182,7 @@ class SubjectPipeline:
             raise ValueError('expected an (X,Y,Z,T) shape, got %s' % (shape,))
         self._enqueue(tuple(int(v) for v in shape), None, fill)
 
-    def _enqueue(self, shape, st, fill):
+    def _enqueue(self, shape, st, fill, atrial=None):
         torch = self.torch
         X, Y, Z, T = shape
         slot = self._acquire(shape)
@@ -176,6 +190,7 @@ class SubjectPipeline:
         slot.busy = True
         slot.shape = shape
         slot.staged = st
+        slot.atrial = atrial is not None
         self._next = (self._next + 1) % self.depth
         n_class = self.engine.arch.n_class
         X2, Y2, x_pre, _, y_pre, _ = pad_amounts(X, Y)
@@ -209,6 +224,9 @@ class SubjectPipeline:
             if self.qc is not None:
                 launch_gate_stats(self.qc[0], self.qc[1], slot.d_lab.data_ptr(), shape, n_class, slot.d_qc_work.data_ptr(),
                                   slot.d_qc.data_ptr(), cs)
+            if atrial is not None:
+                launch_atrial_stats(slot.d_lab.data_ptr(), shape, n_class, atrial[0], atrial[1], slot.d_at_work.data_ptr(),
+                                    slot.d_at.data_ptr(), cs)
             slot.ev_cmp.record(self.s_cmp)
         with torch.cuda.stream(self.s_out):
             self.s_out.wait_event(slot.ev_cmp)
@@ -217,6 +235,9 @@ class SubjectPipeline:
             if self.qc is not None:
                 n_qc = gate_buffer_sizes(self.qc[0], self.qc[1], shape, n_class)[1]
                 slot.pin_qc[:n_qc].copy_(slot.d_qc[:n_qc], non_blocking=True)
+            if atrial is not None:
+                n_at = atrial_buffer_sizes(shape, n_class)[1]
+                slot.pin_at[:n_at].copy_(slot.d_at[:n_at], non_blocking=True)
             slot.ev_out.record(self.s_out)
         self._inflight.append(slot)
 
@@ -241,9 +262,12 @@ class SubjectPipeline:
         if self.qc is not None:
             n_qc = gate_buffer_sizes(self.qc[0], self.qc[1], slot.shape, n_class)[1]
             qc = decode_gate_stats(self.qc[0], self.qc[1], slot.pin_qc.numpy()[:n_qc], slot.shape, n_class, cnt)
+        at = None
+        if slot.atrial:
+            at = decode_atrial_stats(slot.pin_at.numpy()[:atrial_buffer_sizes(slot.shape, n_class)[1]], slot.shape, n_class)
         st, slot.staged = slot.staged, None
         slot.busy = False
-        return Result(self, lab, cnt, slot.clip, st, qc)
+        return Result(self, lab, cnt, slot.clip, st, qc, at)
 
     def run(self, volumes):
         """Generator: segment an iterable of volumes with up to depth-1 subjects in flight; yields Results in order
@@ -266,9 +290,10 @@ class SubjectPipeline:
 
 
 class Result:
-    def __init__(self, pipe, labels, counts, clip, staged, qc=None):
+    def __init__(self, pipe, labels, counts, clip, staged, qc=None, atrial=None):
         self._pipe, self.labels, self.counts, self.clip, self._staged = pipe, labels, counts, clip, staged
         self.qc = qc                                          # the gate statistics (SubjectPipeline(qc=...)), or None
+        self.atrial = atrial                                  # the atrial statistics (submit(..., atrial=...)), or None
 
     @property
     def image(self):
