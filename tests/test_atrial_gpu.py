@@ -165,7 +165,7 @@ def test_carved_buffers():
     affine, long_axis = TA.geometry(1)
     want = atrial.frame_stats_host(seg, n_class, affine, long_axis)
     n = X * Y * P
-    n_work, n_out = dp.atrial_buffer_sizes((X, Y, 1, P), n_class)
+    n_work, n_out = dp.AtrialStats().sizes((X, Y, 1, P), n_class)
     assert n_work == 2 * P * n_class + 3 * n + (n + 3) // 4 and n_out == P * n_class * 8
     results = []
     for s in SENTINELS:
@@ -185,12 +185,12 @@ def test_repeat_run_gives_identical_bits():
     seg = _atria((57, 33, 5), 3, 4)
     affine, long_axis = TA.geometry(2)
     lab = _lab_tensor(seg)
-    n_work, n_out = dp.atrial_buffer_sizes((57, 33, 1, 5), 3)
+    n_work, n_out = dp.AtrialStats().sizes((57, 33, 1, 5), 3)
     work = torch.empty(n_work, dtype=torch.int32, device='cuda')
     outs = [torch.empty(n_out, dtype=torch.int32, device='cuda') for _ in range(2)]
     stream = torch.cuda.current_stream().cuda_stream
     for o in outs:                                     # the same work buffer, dirty from the first call
-        dp.launch_atrial_stats(lab.data_ptr(), (57, 33, 1, 5), 3, affine, long_axis, work.data_ptr(), o.data_ptr(), stream)
+        dp.AtrialStats().launch(lab.data_ptr(), (57, 33, 1, 5), 3, work.data_ptr(), o.data_ptr(), stream, (affine, long_axis))
     a, b = (o.cpu().numpy() for o in outs)
     assert np.array_equal(a, b) and np.array_equal(a.reshape(5, 3, 8), atrial.frame_stats_host(seg, 3, affine, long_axis))
 

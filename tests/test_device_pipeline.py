@@ -189,6 +189,54 @@ def test_subject_pipeline_equals_sequential_device_path():
     eng.close()
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize('model,seq,with_atrial,sized_for,subjects', [
+    # same voxel count, twice the frames: the counts and both result buffers of the slot are too small
+    ('FCN_la_4ch', 'la_4ch', True, (48, 64, 1, 3), [((48, 64, 1, 3), True), ((32, 48, 1, 6), True), ((48, 64, 1, 3), False)]),
+    # same voxel count, fewer frames, three times the X*Y*Z planes: only the gate's buffers are too small
+    ('FCN_sa', 'sa', False, (32, 48, 2, 6), [((32, 48, 2, 6), False), ((48, 64, 3, 2), False)])])
+def test_subject_pipeline_statistics_follow_the_shape(model, seq, with_atrial, sized_for, subjects):
+    """The slot logic of SubjectPipeline(stats=...): a later subject with no more voxels than the pipeline was sized for, yet larger
+    statistic buffers, gets a slot of its own size (re-made, not overrun), and a subject without the argument of a statistic goes
+    without it.  Labels, counts and clip equal segment_sequence_device exactly, the statistics equal their host twins exactly."""
+    import test_atrial as TA
+    from ukbb_cardiac_amd import atrial, qc_gates
+    from ukbb_cardiac_amd.phantom import cine_phantom
+    from ukbb_cardiac_amd.subject_pipeline import SubjectPipeline, labels_as_float64
+    eng = _engine(model)
+    n_class = eng.arch.n_class
+    stats = (dp.GateStats(seq, False),) + ((dp.AtrialStats(),) if with_atrial else ())
+    pipe = SubjectPipeline(eng, sized_for, batch_slices=5, depth=3, extra_inputs=1, stats=stats)
+    made = list(pipe.slots)
+    jobs = []
+    for i, ((X, Y, Z, T), has_arg) in enumerate(subjects):
+        assert X * Y * Z * T <= pipe._in_cap
+        v = cine_phantom(Z * T, X, Y, seed=60 + i)[..., 0].reshape(T, Z, X, Y).transpose(2, 3, 1, 0) * 1000.0
+        v = np.asfortranarray(v.astype(np.float32))
+        args = {'atrial': TA.geometry(i % 3)} if has_arg else None
+        pipe.submit(v, args)
+        jobs.append((v, args, pipe.collect()))
+    # the first subject fits the slot made for it; every other one needed larger statistic buffers: a new slot
+    assert [pipe.slots[i] is made[i] for i in range(len(subjects))] == [True] + [shape == sized_for for shape, _ in subjects[1:]]
+    for v, args, res in jobs:
+        res.done()
+        w_pred, w_aux = dp.segment_sequence_device(v, eng, batch_slices=5, return_aux=True)
+        np.testing.assert_array_equal(labels_as_float64(res.labels), w_pred)
+        np.testing.assert_array_equal(res.counts, w_aux['counts'])
+        assert res.clip == w_aux['clip'] and len(np.unique(res.labels)) >= 2
+        want = {'qc': qc_gates.stats_host(res.labels, seq, False, n_class)}
+        if args:
+            want['atrial'] = atrial.frame_stats_host(res.labels[:, :, 0, :], n_class, *args['atrial'])
+        assert set(res.stats) == set(want)
+        for k, st in want['qc'].items():
+            assert np.array_equal(res.stats['qc'][k], st) and np.any(st), k
+        if args:
+            assert np.array_equal(res.stats['atrial'], want['atrial']) and np.any(want['atrial'])
+    with pytest.raises(ValueError):
+        pipe.submit(jobs[0][0], {'no_such_statistic': 1})
+    eng.close()
+
+
 # ---- aortic z-score on the device (common/image_utils.py:60-67) -------------------------------------------------------
 
 @pytest.mark.parametrize('n', [1, 2, 3, 7, 100, 1001, 240 * 196 * 50])

@@ -1,4 +1,4 @@
-"""What the atrial measures cost: ukbb_fcn_atrial_area_length (device_pipeline.launch_atrial_stats) on labels already in HBM, timed
+"""What the atrial measures cost: ukbb_fcn_atrial_area_length (device_pipeline.AtrialStats) on labels already in HBM, timed
 with HIP events after warm-up, for T = 50 frames of 208x176 phantom atria (both labels of la_4ch), beside atrial.frame_stats_host
 and the literal atrial.area_length_reference on the same labels; then the per-subject wall time of the pipelined la_4ch deploy
 loop (synthetic weights, --nosave_seg) with and without --atrial_csv.
@@ -47,20 +47,21 @@ if __name__ == '__main__':
     seg = phantom_cine(X, Y, T, 3)
     shape = (X, Y, 1, T)
     lab = torch.from_numpy(np.ascontiguousarray(seg.reshape(-1, order='F'))).to(dev)
-    n_work, n_out = dp.atrial_buffer_sizes(shape, n_class)
+    stat = dp.AtrialStats()
+    n_work, n_out = stat.sizes(shape, n_class)
     work = torch.empty(n_work, dtype=torch.int32, device=dev)
     out = torch.empty(n_out, dtype=torch.int32, device=dev)
     for _ in range(5):
-        dp.launch_atrial_stats(lab.data_ptr(), shape, n_class, affine, long_axis, work.data_ptr(), out.data_ptr(), stream)
+        stat.launch(lab.data_ptr(), shape, n_class, work.data_ptr(), out.data_ptr(), stream, (affine, long_axis))
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     for _ in range(args.reps):
-        dp.launch_atrial_stats(lab.data_ptr(), shape, n_class, affine, long_axis, work.data_ptr(), out.data_ptr(), stream)
+        stat.launch(lab.data_ptr(), shape, n_class, work.data_ptr(), out.data_ptr(), stream, (affine, long_axis))
     e1.record()
     torch.cuda.synchronize()
     dev_ms = e0.elapsed_time(e1) / args.reps
-    got = dp.decode_atrial_stats(out.cpu().numpy(), shape, n_class)
+    got = stat.decode(out.cpu().numpy(), shape, n_class)
     t0 = time.perf_counter()
     want = atrial.frame_stats_host(seg, n_class, affine, long_axis)
     host_ms = (time.perf_counter() - t0) * 1e3

@@ -1,5 +1,5 @@
 """What deploy_network.py --qc_csv adds to a subject on the device path: the statistics of the quality-control gates
-(device_pipeline.launch_gate_stats: ukbb_fcn_plane_components for sa and la_4ch --seg4, ukbb_fcn_label_components for the atrial
+(device_pipeline.GateStats: ukbb_fcn_plane_components for sa and la_4ch --seg4, ukbb_fcn_label_components for the atrial
 gate) on labels already in HBM, timed with HIP events after warm-up, for one full-size short-axis subject (192x208x10x50: the
 10 planes of the ED frame) and one la_4ch cine (208x187x1x50), beside qc_gates.stats_host on the same labels, and the device-path
 time of the whole short-axis subject (device_pipeline.segment_sequence_device, synthetic weights) with and without the gate.
@@ -51,21 +51,22 @@ if __name__ == '__main__':
                                             ('la_4ch cine', 'la_4ch', False, (208, 187, 1, 50), 3)):
         seg = heart_like(shape, n_class, 1)
         lab = torch.from_numpy(np.ascontiguousarray(seg.reshape(-1, order='F'))).to(dev)
-        n_work, n_out = dp.gate_buffer_sizes(seq, seg4, shape, n_class)
+        gate = dp.GateStats(seq, seg4)
+        n_work, n_out = gate.sizes(shape, n_class)
         work = torch.empty(n_work, dtype=torch.int32, device=dev)
         out = torch.empty(n_out, dtype=torch.int32, device=dev)
         counts = np.stack([[int((seg[..., t] == k).sum()) for k in range(n_class)] for t in range(shape[3])])
         for _ in range(5):
-            dp.launch_gate_stats(seq, seg4, lab.data_ptr(), shape, n_class, work.data_ptr(), out.data_ptr(), stream)
+            gate.launch(lab.data_ptr(), shape, n_class, work.data_ptr(), out.data_ptr(), stream)
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(args.reps):
-            dp.launch_gate_stats(seq, seg4, lab.data_ptr(), shape, n_class, work.data_ptr(), out.data_ptr(), stream)
+            gate.launch(lab.data_ptr(), shape, n_class, work.data_ptr(), out.data_ptr(), stream)
         e1.record()
         torch.cuda.synchronize()
         dev_ms = e0.elapsed_time(e1) / args.reps
-        got = dp.decode_gate_stats(seq, seg4, out.cpu().numpy(), shape, n_class, counts)
+        got = gate.decode(out.cpu().numpy(), shape, n_class, counts)
         t0 = time.perf_counter()
         want = qc_gates.stats_host(seg, seq, seg4, n_class)
         host_ms = (time.perf_counter() - t0) * 1e3
@@ -83,7 +84,7 @@ if __name__ == '__main__':
                 if i == 1:
                     torch.cuda.synchronize()
                     t0 = time.perf_counter()
-                dp.segment_sequence_device(image, eng, 128, return_aux=True, qc=qc)
+                dp.segment_sequence_device(image, eng, 128, return_aux=True, stats=[dp.GateStats(*qc)] if qc else ())
             torch.cuda.synchronize()
             print('segment_sequence_device 192x208x10x50 %-16s %.2f ms per subject (wall clock, 3 subjects after 1 warm-up)' %
                   ('with the sa gate' if qc else 'without a gate', (time.perf_counter() - t0) * 1e3 / 3), flush=True)

@@ -27,8 +27,9 @@ import numpy as np
 if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from ukbb_cardiac_amd import atrial, measures, nifti, pipeline, qc_gates   # noqa: E402
+from ukbb_cardiac_amd import nifti, pipeline                      # noqa: E402
 from ukbb_cardiac_amd.flags import FlagError, FlagSet              # noqa: E402
+from ukbb_cardiac_amd.label_tables import LabelTables              # noqa: E402
 from ukbb_cardiac_amd.shard import ClaimQueue, apply_cpu_set_from_env, default_device, shard_from_env   # noqa: E402
 
 
@@ -111,17 +112,19 @@ def sequence_on_device(FLAGS, engine, image):
     return device_pipeline.device_dtype_ok(image.dtype)
 
 
-def run_pipelined(FLAGS, engine, data_list, log=print, csv_rows=None, queue=None, qc_rows=None, atrial_rows=None):
+def run_pipelined(FLAGS, engine, data_list, log=print, tables=None, queue=None):
     """Sequence mode with subjects overlapped: reader threads decompress the next files into pinned staging buffers,
     the GPU thread (this one) keeps up to two subjects in flight on three streams (subject_pipeline.SubjectPipeline),
     writer threads expand the uint8 labels to the reference's float64 volume, gzip and save.  Same files, byte for byte,
-    as the sequential loop; log lines of a subject are emitted together when its result arrives."""
+    as the sequential loop; log lines of a subject are emitted together when its result arrives.  ``tables``: the run's
+    LabelTables (default: made from FLAGS)."""
     import threading
     from concurrent.futures import ThreadPoolExecutor
     from ukbb_cardiac_amd import device_pipeline
     from ukbb_cardiac_amd.subject_pipeline import SubjectPipeline
     start_time = time.time()
     seq, pre = FLAGS.seq_name, seg_prefix(FLAGS)
+    tables = tables or LabelTables(FLAGS, engine)
     def candidates(names, second=False):
         """(data, data_dir, image_name) of the subjects still to segment, in walk order, each claimed right before its read is
         scheduled (with --work_stealing a worker so holds at most window + depth claims; the rest of the list stays open)."""
@@ -159,8 +162,7 @@ def run_pipelined(FLAGS, engine, data_list, log=print, csv_rows=None, queue=None
         if len(shape) == 4 and device_pipeline.device_dtype_ok(dt):
             with mk:
                 if state['pipe'] is None:                  # sized by the first volume; bigger ones fall back below
-                    state['pipe'] = SubjectPipeline(engine, shape, FLAGS.batch_slices, depth=depth, extra_inputs=window,
-                                                    qc=None if qc_rows is None else (seq, FLAGS.seg4), atrial=atrial_rows is not None)
+                    state['pipe'] = SubjectPipeline(engine, shape, FLAGS.batch_slices, depth=depth, extra_inputs=window, stats=tables.statistics())
             try:
                 return state['pipe'].stage(shape, dt).array, SubjectPipeline.HEADROOM
             except ValueError:
@@ -190,7 +192,7 @@ def run_pipelined(FLAGS, engine, data_list, log=print, csv_rows=None, queue=None
     futures = {}
     inflight = []                                       # (item, nim, t_submit)
 
-    def finish(item, nim, t0, geom=None):
+    def finish(item, nim, t0):
         data, data_dir, image_name = item
         res = state['pipe'].collect()
         seg_time = time.time() - t0
@@ -202,12 +204,7 @@ def run_pipelined(FLAGS, engine, data_list, log=print, csv_rows=None, queue=None
         log('  ED frame = {:d}, ES frame = {:d}'.format(k_ed, k_es))
         table_time.append(seg_time)
         processed.append(data)
-        if csv_rows is not None:
-            csv_rows[data] = measures.sa_row(res.counts, nim.header['pixdim'])
-        if qc_rows is not None:
-            record_gate(FLAGS, qc_rows, data, data_dir, res.qc, log)
-        if geom is not None:
-            record_atrial(atrial_rows, data, res.atrial, nim, qc_rows[data][0])
+        tables.record(data, data_dir, nim, res.counts, res.stats, log)
         if FLAGS.save_seg:
             log('  Saving segmentation ...')
             # the saved frames are the CLIPPED intensities (alias quirk)
@@ -247,16 +244,15 @@ def run_pipelined(FLAGS, engine, data_list, log=print, csv_rows=None, queue=None
                     finish(*inflight.pop(0))
                 log(item[0])
                 try:
-                    _sequence_subject(FLAGS, item, nim, None, engine, log, processed, table_time, csv_rows, qc_rows, atrial_rows)
+                    _sequence_subject(FLAGS, item, nim, None, engine, log, processed, table_time, tables)
                 finally:
                     release(item[0])
                 top_up()
                 continue
             if len(inflight) >= depth - 1:
                 finish(*inflight.pop(0))
-            geom = None if atrial_rows is None else atrial_geometry(item[1], nim, log)
-            pipe.submit(image, atrial=geom)
-            inflight.append((item, nim, time.time(), geom))
+            pipe.submit(image, tables.subject_args(item[1], nim, log))
+            inflight.append((item, nim, time.time()))
             top_up()
         while inflight:
             finish(*inflight.pop(0))
@@ -270,35 +266,7 @@ def run_pipelined(FLAGS, engine, data_list, log=print, csv_rows=None, queue=None
     return processed, table_time, start_time
 
 
-def record_gate(FLAGS, qc_rows, data, data_dir, stats, log):
-    """--qc_csv: the verdict of this sequence's gate from its statistics (qc_gates.stats_host / device_pipeline.device_gate_stats) into
-    qc_rows; the message of a failing subject is logged the way the reference prints it."""
-    name = '{0}/{1}'.format(data_dir, qc_gates.seg_file_name(FLAGS.seq_name, FLAGS.seg4))
-    qc_rows[data] = passed, message = qc_gates.gate_from_stats(stats, FLAGS.seq_name, FLAGS.seg4, name)
-    if not passed:
-        log(message)
-
-
-def atrial_geometry(data_dir, nim, log):
-    """--atrial_csv: (affine of the long-axis image, long axis) for this subject, the long axis from the short-axis header as
-    eval_atrial_volume.py:45-48 -- or None, logged, for a subject without sa.nii.gz (the reference skips it) or with more than one
-    slice."""
-    sa_name = '{0}/sa.nii.gz'.format(data_dir)
-    if not os.path.exists(sa_name):
-        log('  Directory {0} does not contain sa.nii.gz: no long axis, no atrial measures.'.format(data_dir))
-        return None
-    if nim.shape[2] != 1:
-        log('  {0} slices: the atrial measures read a single-slice long-axis sequence. Skip.'.format(nim.shape[2]))
-        return None
-    return nim.affine, atrial.long_axis_from_sa(nifti.load_header(sa_name)['affine'])
-
-
-def record_atrial(atrial_rows, data, stats, nim, gate_passed):
-    """--atrial_csv: the rows of this subject from its statistics (atrial.frame_stats_host / device_pipeline.device_atrial_stats)."""
-    atrial_rows[data] = atrial.frame_rows(stats, nim.affine, nim.header['pixdim'], gate_passed)
-
-
-def _sequence_subject(FLAGS, item, nim, forward, engine, log, processed, table_time, csv_rows=None, qc_rows=None, atrial_rows=None):
+def _sequence_subject(FLAGS, item, nim, forward, engine, log, processed, table_time, tables):
     """One subject of sequence mode, start to finish on this thread (deploy_network.py:80-151)."""
     data, data_dir, image_name = item
     seq, pre = FLAGS.seq_name, seg_prefix(FLAGS)
@@ -310,11 +278,11 @@ def _sequence_subject(FLAGS, item, nim, forward, engine, log, processed, table_t
     t0 = time.time()
     np1 = bool(getattr(FLAGS, 'numpy1_casting', False))
     on_device = sequence_on_device(FLAGS, engine, image)
-    geom = None if atrial_rows is None else atrial_geometry(data_dir, nim, log)
+    args = tables.subject_args(data_dir, nim, log)
     if on_device:
         from ukbb_cardiac_amd import device_pipeline
-        pred, aux = device_pipeline.segment_sequence_device(image, engine, FLAGS.batch_slices, return_aux=True,
-                                                            qc=None if qc_rows is None else (seq, FLAGS.seg4), atrial=geom)
+        pred, aux = device_pipeline.segment_sequence_device(image, engine, FLAGS.batch_slices, return_aux=True, stats=tables.statistics(),
+                                                            stat_args=args)
     else:
         if forward is None:
             forward = lambda b: {'pred': engine.run(b, want_prob=False)['pred']}
@@ -328,17 +296,8 @@ def _sequence_subject(FLAGS, item, nim, forward, engine, log, processed, table_t
     else:
         k_ed, k_es = pipeline.pick_ed_es(pred, seq, FLAGS.seg4)
     log('  ED frame = {:d}, ES frame = {:d}'.format(k_ed, k_es))
-    if csv_rows is not None:
-        n_class = 4 if engine is None else engine.arch.n_class
-        counts = aux['counts'] if on_device else measures.counts_from_labels(pred, n_class)
-        csv_rows[data] = measures.sa_row(counts, nim.header['pixdim'])
-    if qc_rows is not None:
-        n_class = None if engine is None else engine.arch.n_class
-        record_gate(FLAGS, qc_rows, data, data_dir, aux['qc'] if on_device else qc_gates.stats_host(pred, seq, FLAGS.seg4, n_class), log)
-    if geom is not None:
-        n_class = qc_gates.min_classes(seq) if engine is None else engine.arch.n_class
-        record_atrial(atrial_rows, data, aux['atrial'] if on_device else atrial.frame_stats_host(pred[:, :, 0, :], n_class, *geom), nim,
-                      qc_rows[data][0])
+    counts, stats = (aux['counts'], aux['stats']) if on_device else tables.from_labels(pred, args, tables.n_class)
+    tables.record(data, data_dir, nim, counts, stats, log)
     if FLAGS.save_seg:
         log('  Saving segmentation ...')
         frames = {}
@@ -347,68 +306,6 @@ def _sequence_subject(FLAGS, item, nim, forward, engine, log, processed, table_t
             frame = device_pipeline.clip_like_reference(image[:, :, :, k], aux['clip']) if on_device else image[:, :, :, k]
             frames[fr] = (frame, pred[:, :, :, k])
         save_sequence_outputs(data_dir, pre, seq, nim.affine, nim.header['pixdim'], pred, frames)
-
-
-def write_measures_csv(FLAGS, subjects, csv_rows, log=print):
-    """The spreadsheet of short_axis/eval_ventricular_volume.py:28-79 for this worker's subjects: rows measured during this run
-    come from the device counts; a subject segmented by an earlier run (skipped above) is measured from its files the way the
-    evaluation script does.  Same inclusion rule (:35: image and segmentation both exist), same order (sorted directory names)."""
-    rows = []
-    # with --work_stealing this worker may also have segmented subjects of other shards (their rows are in csv_rows), and another
-    # worker may have taken some of this one's: both then hold a row for it -- identical text -- and the merge keeps one
-    for data in sorted(set(subjects) | set(csv_rows)):
-        data_dir = os.path.join(FLAGS.data_dir, data)
-        image_name, seg_name = '{0}/sa.nii.gz'.format(data_dir), '{0}/seg_sa.nii.gz'.format(data_dir)
-        if data in csv_rows:
-            rows.append((data, csv_rows[data]))
-        elif os.path.exists(image_name) and os.path.exists(seg_name):
-            seg = nifti.load(seg_name).get_data()
-            rows.append((data, measures.sa_row(measures.counts_from_labels(seg, 4), nifti.load_header(image_name)['pixdim'])))
-    path = measures.shard_csv_name(FLAGS.output_csv, FLAGS.shard_index, FLAGS.num_shards)
-    measures.write_csv(path, measures.SA_COLUMNS, rows)
-    log('Clinical measures of {0} subjects written to {1}'.format(len(rows), path))
-
-
-def write_qc_csv(FLAGS, subjects, qc_rows, log=print):
-    """--qc_csv for this worker's subjects, sorted: verdicts of this run from qc_rows; a subject segmented by an earlier run
-    (skipped above) is gated from its label file on the host.  Same sharing between workers as write_measures_csv."""
-    seq, pre = FLAGS.seq_name, seg_prefix(FLAGS)
-    rows = []
-    for data in sorted(set(subjects) | set(qc_rows)):
-        data_dir = os.path.join(FLAGS.data_dir, data)
-        seg_name = '{0}/{1}_{2}.nii.gz'.format(data_dir, pre, seq)
-        if data not in qc_rows and os.path.isdir(data_dir) and os.path.exists(seg_name):
-            seg = nifti.load(seg_name).get_data()
-            if seg.ndim == 4:
-                record_gate(FLAGS, qc_rows, data, data_dir, qc_gates.stats_host(seg, seq, FLAGS.seg4), log)
-        if data in qc_rows:
-            rows.append((data, qc_rows[data]))
-    path = measures.shard_csv_name(FLAGS.qc_csv, FLAGS.shard_index, FLAGS.num_shards)
-    qc_gates.write_csv(path, seq, FLAGS.seg4, rows)
-    log('Quality-control verdicts of {0} subjects written to {1}'.format(len(rows), path))
-
-
-def write_atrial_csv(FLAGS, subjects, atrial_rows, qc_rows, n_class, log=print):
-    """--atrial_csv for this worker's subjects, sorted: rows of this run from atrial_rows; a subject segmented by an earlier run
-    (skipped above) is measured from its label file on the host (atrial.frame_stats_host) if it has an sa.nii.gz.  Same sharing
-    between workers as write_measures_csv."""
-    seq = FLAGS.seq_name
-    rows = []
-    for data in sorted(set(subjects) | set(atrial_rows)):
-        data_dir = os.path.join(FLAGS.data_dir, data)
-        seg_name = '{0}/seg_{1}.nii.gz'.format(data_dir, seq)
-        if data not in atrial_rows and os.path.isdir(data_dir) and os.path.exists(seg_name) and os.path.exists('{0}/sa.nii.gz'.format(data_dir)):
-            nim = nifti.load(seg_name)
-            seg = nim.get_data()
-            geom = atrial_geometry(data_dir, nim, log) if seg.ndim == 4 else None
-            if geom is not None:
-                if data not in qc_rows:
-                    record_gate(FLAGS, qc_rows, data, data_dir, qc_gates.stats_host(seg, seq, False), log)
-                record_atrial(atrial_rows, data, atrial.frame_stats_host(seg[:, :, 0, :], n_class, *geom), nim, qc_rows[data][0])
-        rows += [(data, r) for r in atrial_rows.get(data, [])]
-    path = measures.shard_csv_name(FLAGS.atrial_csv, FLAGS.shard_index, FLAGS.num_shards)
-    atrial.write_frames_csv(path, rows)
-    log('Atrial measures of {0} frames and labels written to {1}'.format(len(rows), path))
 
 
 def run(FLAGS, forward, log=print, engine=None):
@@ -421,34 +318,11 @@ def run(FLAGS, forward, log=print, engine=None):
                        stealing=bool(getattr(FLAGS, 'work_stealing', False)) and FLAGS.process_seq)
     data_list = list(queue)
     processed, table_time = [], []
-    csv_rows = None
-    if getattr(FLAGS, 'output_csv', ''):
-        if seq != 'sa' or not FLAGS.process_seq:
-            raise ValueError('--output_csv writes the table of short_axis/eval_ventricular_volume.py: it needs --seq_name sa in sequence mode')
-        csv_rows = {}
-    qc_rows = None
-    if getattr(FLAGS, 'qc_csv', ''):
-        if not FLAGS.process_seq:
-            raise ValueError('--qc_csv gates the segmentation of a whole sequence: it needs sequence mode (--process_seq)')
-        if engine is not None and engine.arch.n_class < qc_gates.min_classes(seq, FLAGS.seg4):
-            raise ValueError('--qc_csv: the gate of --seq_name {0}{1} reads {2} classes, the model has {3}'.format(
-                seq, ' --seg4' if FLAGS.seg4 else '', qc_gates.min_classes(seq, FLAGS.seg4), engine.arch.n_class))
-        qc_rows = {}
-    atrial_rows = None
-    if getattr(FLAGS, 'atrial_csv', ''):
-        if seq not in ('la_2ch', 'la_4ch') or FLAGS.seg4 or not FLAGS.process_seq:
-            raise ValueError('--atrial_csv measures the atria of long_axis/eval_atrial_volume.py: it needs --seq_name la_2ch or la_4ch '
-                             'without --seg4, in sequence mode')
-        if engine is not None and engine.arch.n_class < qc_gates.min_classes(seq):
-            raise ValueError('--atrial_csv: --seq_name {0} has {1} classes, the model has {2}'.format(seq, qc_gates.min_classes(seq),
-                                                                                                   engine.arch.n_class))
-        atrial_rows = {}
-        if qc_rows is None:
-            qc_rows = {}                                # the rows carry the gate's verdict: gated, though no --qc_csv is written
-    shard_subjects = list(queue.static)                 # whose earlier-run results this worker measures for --output_csv
+    tables = LabelTables(FLAGS, engine)                 # --output_csv, --qc_csv, --atrial_csv: flag checks first
+    shard_subjects = list(queue.static)                 # whose earlier-run results this worker measures for the tables
     if (FLAGS.process_seq and engine is not None and getattr(FLAGS, 'device_preproc', False) and getattr(FLAGS, 'io_threads', 0) > 0
             and not getattr(FLAGS, 'numpy1_casting', False)):
-        processed, table_time, _ = run_pipelined(FLAGS, engine, data_list, log, csv_rows, queue, qc_rows, atrial_rows)
+        processed, table_time, _ = run_pipelined(FLAGS, engine, data_list, log, tables, queue)
         data_list = []
     def one_subject(data, second):
         """One entry of the walk; ``second``: a subject another worker held when this one first came by (--work_stealing)."""
@@ -473,8 +347,7 @@ def run(FLAGS, forward, log=print, engine=None):
                     log(data)
                 log('  Reading {} ...'.format(image_name))
                 nim = nifti.load(image_name)
-                _sequence_subject(FLAGS, (data, data_dir, image_name), nim, forward, engine, log, processed, table_time, csv_rows, qc_rows,
-                                  atrial_rows)
+                _sequence_subject(FLAGS, (data, data_dir, image_name), nim, forward, engine, log, processed, table_time, tables)
             finally:
                 queue.done(data)
         else:
@@ -502,12 +375,7 @@ def run(FLAGS, forward, log=print, engine=None):
         one_subject(data, False)
     for data in queue.second_chance():                  # finished by its owner meanwhile (skip-if-exists), or orphaned (stale claim)
         one_subject(data, True)
-    if csv_rows is not None:
-        write_measures_csv(FLAGS, shard_subjects, csv_rows, log)
-    if atrial_rows is not None:
-        write_atrial_csv(FLAGS, shard_subjects, atrial_rows, qc_rows, qc_gates.min_classes(seq) if engine is None else engine.arch.n_class, log)
-    if getattr(FLAGS, 'qc_csv', ''):
-        write_qc_csv(FLAGS, shard_subjects, qc_rows, log)
+    tables.write(shard_subjects, log)
     if table_time:
         log('Average segmentation time = {:.3f}s per {}'.format(float(np.mean(table_time)),
                                                                'sequence' if FLAGS.process_seq else 'frame'))

@@ -140,22 +140,34 @@ def pack_rescaled(vol_ptr, dtype, shape, strides, lo, hi, pad, batch_ptr, stream
                                                 *pad, batch_ptr, stream), 'ukbb_fcn_rescale_pack_t')
 
 
-def segment_sequence_device(image, engine, batch_slices=128, thres=(1, 99), return_aux=False, qc=None, atrial=None):
+def forward_and_unpack(engine, batch_ptr, pred_ptr, shape, pad, batch_slices, lab_ptr, counts_ptr, stream):
+    """The tail every frame-wise sequence path shares, enqueued on ``stream``: the network over the packed batch [T*Z][X2][Y2] at
+    batch_ptr in chunks of batch_slices (int32 label maps to pred_ptr), then ukbb_fcn_unpack_labels: the uint8 (X,Y,Z,T) label
+    volume in NIfTI order to lab_ptr and the per-frame class counts (int64 [T, n_class]) to counts_ptr.  pad = (X2, Y2, x_pre, y_pre)."""
+    X, Y, Z, T = shape
+    X2, Y2, x_pre, y_pre = pad
+    n, px = T * Z, X2 * Y2
+    engine.reserve(min(batch_slices, n), X2, Y2)
+    for i in range(0, n, batch_slices):
+        m = min(batch_slices, n - i)
+        engine.run_device(batch_ptr + 4 * i * px, m, X2, Y2, pred_ptr=pred_ptr + 4 * i * px, stream=stream)
+    _lib.check(_lib.lib.ukbb_fcn_unpack_labels(pred_ptr, X, Y, Z, T, X2, Y2, x_pre, y_pre, engine.arch.n_class, lab_ptr, counts_ptr, stream),
+               'ukbb_fcn_unpack_labels')
+
+
+def segment_sequence_device(image, engine, batch_slices=128, thres=(1, 99), return_aux=False, stats=(), stat_args=None):
     """(X,Y,Z,T) float32 / uint8 / int16 / uint16 volume -> float64 label volume of the same shape, like
     pipeline.segment_sequence.
 
     ``image`` is NOT modified (the reference clips it in place); callers that
     save image frames afterwards clip them with the returned bounds (``aux['clip']``: the float64
     percentiles; clip_like_reference stores them into an integer frame truncated, as numpy does).
-    ``aux['counts'][t, c]`` = voxels of class c in frame t (input of the ES pick).  ``qc = (seq_name, seg4)`` (needs
-    ``return_aux``): ``aux['qc']`` = the statistics of that sequence's quality-control gate (device_gate_stats; the input of
-    qc_gates.gate_from_stats) from the labels while they are still on the device.  ``atrial = (affine, long_axis)`` (needs
-    ``return_aux``, Z = 1): ``aux['atrial']`` = device_atrial_stats of the labels, [T, n_class, 8]."""
+    ``aux['counts'][t, c]`` = voxels of class c in frame t (input of the ES pick).  ``stats`` (needs ``return_aux``): label
+    statistics (GateStats, AtrialStats) to compute from the labels while they are still on the device, ``stat_args`` their
+    per-subject arguments {key: arg}: ``aux['stats']`` = {key: decoded statistic} (label_statistics)."""
     import torch
-    if qc is not None and not return_aux:
-        raise ValueError('qc returns its statistics in aux: pass return_aux')
-    if atrial is not None and not return_aux:
-        raise ValueError('atrial returns its statistics in aux: pass return_aux')
+    if stats and not return_aux:
+        raise ValueError('stats are returned in aux: pass return_aux')
     if image.ndim != 4:
         raise ValueError('expected a 4-D (X,Y,Z,T) sequence, got shape %s' % (image.shape,))
     _check_dtype(image, 'pipeline.segment_sequence')
@@ -170,24 +182,17 @@ def segment_sequence_device(image, engine, batch_slices=128, thres=(1, 99), retu
     sx, sy, sz, st = vol.stride()
     pack_rescaled(vol.data_ptr(), image.dtype, (X, Y, Z, T), (sx, sy, sz, st), lo, hi, (X2, Y2, x_pre, y_pre), batch.data_ptr(), stream)
     pred = torch.empty((n, X2, Y2), dtype=torch.int32, device=dev)
-    engine.reserve(min(batch_slices, n), X2, Y2)
-    for i in range(0, n, batch_slices):
-        m = min(batch_slices, n - i)
-        engine.run_device(batch[i].data_ptr(), m, X2, Y2, pred_ptr=pred[i].data_ptr(), stream=stream)
     n_class = engine.arch.n_class
     lab = torch.empty(X * Y * Z * T, dtype=torch.uint8, device=dev)
     counts = torch.empty((T, n_class), dtype=torch.int64, device=dev)
-    _lib.check(_lib.lib.ukbb_fcn_unpack_labels(pred.data_ptr(), X, Y, Z, T, X2, Y2, x_pre, y_pre, n_class,
-                                               lab.data_ptr(), counts.data_ptr(), stream), 'ukbb_fcn_unpack_labels')
+    forward_and_unpack(engine, batch.data_ptr(), pred.data_ptr(), (X, Y, Z, T), (X2, Y2, x_pre, y_pre), batch_slices, lab.data_ptr(),
+                       counts.data_ptr(), stream)
     lab_h = lab.cpu().numpy().reshape((X, Y, Z, T), order='F')
     out = np.zeros(image.shape)                                 # float64, as deploy_network.py:92
     out[...] = lab_h
     if return_aux:
         aux = {'clip': (lo, hi), 'counts': counts.cpu().numpy()}
-        if qc is not None:
-            aux['qc'] = device_gate_stats(lab, (X, Y, Z, T), qc[0], qc[1], n_class, stream, aux['counts'])
-        if atrial is not None:
-            aux['atrial'] = device_atrial_stats(lab, (X, Y, Z, T), n_class, atrial[0], atrial[1], stream)
+        aux['stats'] = label_statistics(lab, (X, Y, Z, T), n_class, stats, stat_args, stream, aux['counts'])
         return out, aux
     return out
 
@@ -390,65 +395,105 @@ def device_qc_stats(vol_t, lab_t, dtype, n_class, stream=0, min_size=None):
     return {'n_large': n_large.cpu().numpy(), 'max': mx.cpu().numpy(), 'mean_ed': np.array(means, dtype=rt)}
 
 
-# ---- the short- and long-axis quality-control gates (qc_gates.py) on the labels ukbb_fcn_unpack_labels left in HBM ----------
+# ---- statistics of the label volume ukbb_fcn_unpack_labels left in HBM: the gates (qc_gates.py), the atria (atrial.py) ------------
+# A statistic has a ``key``, says whether it takes a per-subject argument (``needs_arg``), and knows the (work, out) int32 counts
+# of its device buffers (``sizes``), how to enqueue itself on a stream (``launch``; the work buffer 8-byte aligned; asynchronous)
+# and how to read the host copy of what it wrote (``decode``).  SubjectPipeline keeps such buffers per slot; label_statistics
+# allocates them per call.
 
-def gate_buffer_sizes(seq_name, seg4, shape, n_class):
-    """(work, out) int32 counts of the device buffers launch_gate_stats needs for an (X,Y,Z,T) label volume: the work buffer
-    of ukbb_fcn_plane_components (sa: the Z planes of frame 0; la_4ch --seg4: plane 0) or of ukbb_fcn_label_components (the
-    atrial gate: the whole sequence), and the statistics themselves."""
-    from .qc_gates import gate_kind
-    X, Y, Z, T = shape
-    kind = gate_kind(seq_name, seg4)
-    if kind == 'atrium':
-        return 2 * X * Y * Z * T, T * n_class
-    P = Z if kind == 'sa' else 1
-    return 2 * P * n_class + 3 * X * Y * P + (X * Y * P + 3) // 4, P * (3 * n_class + 1)
+class GateStats:
+    """qc_gates.stats_host -- what the gate of this sequence reads (the input of qc_gates.gate_from_stats) -- of an (X,Y,Z,T) label
+    volume: ukbb_fcn_plane_components for sa (the Z planes of frame 0) and la_4ch --seg4 (plane 0), ukbb_fcn_label_components for
+    the atrial gate (the whole sequence).  plane_args = (a, b, keep_min) of the plane statistics (qc_gates.plane_stats_host)."""
+    key, needs_arg = 'qc', False
+
+    def __init__(self, seq_name, seg4, plane_args=None):
+        from .qc_gates import PIXEL_THRES, gate_kind
+        self.kind = gate_kind(seq_name, seg4)
+        self.plane_args = (1, 2, PIXEL_THRES) if plane_args is None else plane_args
+        self.min_size = PIXEL_THRES
+
+    def sizes(self, shape, n_class):
+        X, Y, Z, T = shape
+        if self.kind == 'atrium':
+            return 2 * X * Y * Z * T, T * n_class
+        P = Z if self.kind == 'sa' else 1
+        return 2 * P * n_class + 3 * X * Y * P + (X * Y * P + 3) // 4, P * (3 * n_class + 1)
+
+    def launch(self, lab_ptr, shape, n_class, work_ptr, out_ptr, stream, arg=None):
+        X, Y, Z, T = shape
+        if self.kind == 'atrium':
+            _lib.check(_lib.lib.ukbb_fcn_label_components(lab_ptr, X, Y, Z, T, n_class, self.min_size, work_ptr, out_ptr, stream),
+                       'ukbb_fcn_label_components')
+            return
+        P = Z if self.kind == 'sa' else 1                             # frame 0 comes first in NIfTI order, plane 0 first in it
+        cells = 4 * P * n_class
+        _lib.check(_lib.lib.ukbb_fcn_plane_components(lab_ptr, X, Y, P, n_class, *self.plane_args, work_ptr, out_ptr, out_ptr + cells,
+                                                      out_ptr + 2 * cells, out_ptr + 3 * cells, stream), 'ukbb_fcn_plane_components')
+
+    def decode(self, out, shape, n_class, counts=None):
+        """The atrial gate also takes the per-frame class counts of ukbb_fcn_unpack_labels."""
+        X, Y, Z, T = shape
+        out = np.asarray(out, dtype=np.int32)
+        if self.kind == 'atrium':
+            return {'counts': np.asarray(counts), 'n_large': out[:T * n_class].reshape(T, n_class).copy()}
+        P = Z if self.kind == 'sa' else 1
+        c = P * n_class
+        return {'count': out[:c].reshape(P, n_class).copy(), 'largest': out[c:2 * c].reshape(P, n_class).copy(),
+                'kept': out[2 * c:3 * c].reshape(P, n_class).copy(), 'union_largest': out[3 * c:3 * c + P].copy()}
 
 
-def launch_gate_stats(seq_name, seg4, lab_ptr, shape, n_class, work_ptr, out_ptr, stream):
-    """Enqueue on ``stream`` the statistics of this sequence's gate from the uint8 labels at device address lab_ptr (NIfTI
-    order) into out_ptr; buffers as gate_buffer_sizes (the work buffer 8-byte aligned).  Asynchronous; decode_gate_stats
-    reads the result once it is on the host."""
-    from .qc_gates import PIXEL_THRES, gate_kind
-    X, Y, Z, T = shape
-    kind = gate_kind(seq_name, seg4)
-    if kind == 'atrium':
-        _lib.check(_lib.lib.ukbb_fcn_label_components(lab_ptr, X, Y, Z, T, n_class, PIXEL_THRES, work_ptr, out_ptr, stream),
-                   'ukbb_fcn_label_components')
-        return
-    P = Z if kind == 'sa' else 1                                  # frame 0 comes first in NIfTI order, plane 0 first in it
-    cells = 4 * P * n_class
-    _lib.check(_lib.lib.ukbb_fcn_plane_components(lab_ptr, X, Y, P, n_class, 1, 2, PIXEL_THRES, work_ptr, out_ptr, out_ptr + cells,
-                                                  out_ptr + 2 * cells, out_ptr + 3 * cells, stream), 'ukbb_fcn_plane_components')
+class AtrialStats:
+    """atrial.frame_stats_host, [T, n_class, 8], of an (X,Y,1,T) label volume (one slice: every frame a plane of
+    ukbb_fcn_atrial_area_length).  Per-subject argument: (affine, long_axis) -- the voxel-to-world matrix of the long-axis image and
+    atrial.long_axis_from_sa; only the T*n_class*32 bytes of statistics cross to the host."""
+    key, needs_arg = 'atrial', True
+
+    def sizes(self, shape, n_class):
+        X, Y, Z, T = shape
+        return 2 * T * n_class + 3 * X * Y * T + (X * Y * T + 3) // 4, T * n_class * 8
+
+    def launch(self, lab_ptr, shape, n_class, work_ptr, out_ptr, stream, arg):
+        X, Y, Z, T = shape
+        if Z != 1:
+            raise ValueError('the atrial measures read a single-slice long-axis sequence, got Z = %d' % Z)
+        affine, long_axis = arg
+        a = (C.c_double * 12)(*[float(v) for v in np.asarray(affine, np.float64)[:3, :4].ravel()])
+        l = (C.c_double * 3)(*[float(v) for v in np.asarray(long_axis, np.float64).ravel()[:3]])
+        _lib.check(_lib.lib.ukbb_fcn_atrial_area_length(lab_ptr, X, Y, T, n_class, a, l, work_ptr, out_ptr, stream), 'ukbb_fcn_atrial_area_length')
+
+    def decode(self, out, shape, n_class, counts=None):
+        T = shape[3]
+        return np.asarray(out, dtype=np.int32)[:T * n_class * 8].reshape(T, n_class, 8).copy()
 
 
-def decode_gate_stats(seq_name, seg4, out, shape, n_class, counts=None):
-    """The host copy ``out`` (int32) of what launch_gate_stats wrote -> the dict qc_gates.gate_from_stats reads.  The atrial
-    gate also takes the per-frame class counts of ukbb_fcn_unpack_labels."""
-    from .qc_gates import gate_kind
-    X, Y, Z, T = shape
-    kind = gate_kind(seq_name, seg4)
-    out = np.asarray(out, dtype=np.int32)
-    if kind == 'atrium':
-        return {'counts': np.asarray(counts), 'n_large': out[:T * n_class].reshape(T, n_class).copy()}
-    P = Z if kind == 'sa' else 1
-    c = P * n_class
-    return {'count': out[:c].reshape(P, n_class).copy(), 'largest': out[c:2 * c].reshape(P, n_class).copy(),
-            'kept': out[2 * c:3 * c].reshape(P, n_class).copy(), 'union_largest': out[3 * c:3 * c + P].copy()}
+def stat_skipped(stat, stat_args):
+    """A statistic that takes a per-subject argument and has none for this subject (a long-axis subject without sa.nii.gz) is not
+    computed for it."""
+    return stat.needs_arg and (stat_args or {}).get(stat.key) is None
+
+
+def label_statistics(lab_t, shape, n_class, stats, stat_args=None, stream=0, counts=None):
+    """{key: decoded statistic} of the (X,Y,Z,T) uint8 label volume ``lab_t`` (a device tensor, NIfTI order) for a sequence of
+    statistics: buffers, launch, copy to the host and decode, one statistic after the other.  stat_args: {key: per-subject argument};
+    counts: the per-frame class counts of ukbb_fcn_unpack_labels, for the decodes that read them."""
+    import torch
+    got = {}
+    for stat in stats:
+        if stat_skipped(stat, stat_args):
+            continue
+        n_work, n_out = stat.sizes(shape, n_class)
+        work = torch.empty(n_work, dtype=torch.int32, device=lab_t.device)
+        out = torch.empty(n_out, dtype=torch.int32, device=lab_t.device)
+        stat.launch(lab_t.data_ptr(), shape, n_class, work.data_ptr(), out.data_ptr(), stream, (stat_args or {}).get(stat.key))
+        got[stat.key] = stat.decode(out.cpu().numpy(), shape, n_class, counts)
+    return got
 
 
 def device_plane_stats(lab_t, X, Y, P, n_class, a=1, b=2, keep_min=10, stream=0):
     """qc_gates.plane_stats_host of the first P planes of X*Y uint8 labels (x fastest) of a device tensor:
     ukbb_fcn_plane_components."""
-    import torch
-    n_work, n_out = gate_buffer_sizes('sa', False, (X, Y, P, 1), n_class)
-    work = torch.empty(n_work, dtype=torch.int32, device=lab_t.device)
-    out = torch.empty(n_out, dtype=torch.int32, device=lab_t.device)
-    c = 4 * P * n_class
-    o = out.data_ptr()
-    _lib.check(_lib.lib.ukbb_fcn_plane_components(lab_t.data_ptr(), X, Y, P, n_class, a, b, keep_min, work.data_ptr(), o, o + c, o + 2 * c,
-                                                  o + 3 * c, stream), 'ukbb_fcn_plane_components')
-    return decode_gate_stats('sa', False, out.cpu().numpy(), (X, Y, P, 1), n_class)
+    return label_statistics(lab_t, (X, Y, P, 1), n_class, [GateStats('sa', False, (a, b, keep_min))], stream=stream)['qc']
 
 
 def device_gate_stats(lab_t, shape, seq_name, seg4, n_class, stream=0, counts=None):
@@ -456,17 +501,13 @@ def device_gate_stats(lab_t, shape, seq_name, seg4, n_class, stream=0, counts=No
     class counts if the caller has them (ukbb_fcn_unpack_labels, as on every path of the deploy script); the atrial gate
     otherwise takes them from one torch.bincount over the label tensor."""
     import torch
-    from .qc_gates import gate_kind
     X, Y, Z, T = shape
-    n_work, n_out = gate_buffer_sizes(seq_name, seg4, shape, n_class)
-    work = torch.empty(n_work, dtype=torch.int32, device=lab_t.device)
-    out = torch.empty(n_out, dtype=torch.int32, device=lab_t.device)
-    launch_gate_stats(seq_name, seg4, lab_t.data_ptr(), shape, n_class, work.data_ptr(), out.data_ptr(), stream)
-    if gate_kind(seq_name, seg4) == 'atrium' and counts is None:
+    gate = GateStats(seq_name, seg4)
+    if gate.kind == 'atrium' and counts is None:
         # one histogram over (frame, label) keys; labels >= n_class fall into columns that are dropped
         keys = lab_t[:X * Y * Z * T].view(T, -1).to(torch.int64) + 256 * torch.arange(T, device=lab_t.device)[:, None]
         counts = torch.bincount(keys.reshape(-1), minlength=256 * T).view(T, 256)[:, :n_class].cpu().numpy()
-    return decode_gate_stats(seq_name, seg4, out.cpu().numpy(), shape, n_class, counts)
+    return label_statistics(lab_t, shape, n_class, [gate], stream=stream, counts=counts)['qc']
 
 
 def device_gate(lab_t, shape, seq_name, seg4, name, n_class, stream=0, counts=None):
@@ -476,43 +517,9 @@ def device_gate(lab_t, shape, seq_name, seg4, name, n_class, stream=0, counts=No
     return gate_from_stats(device_gate_stats(lab_t, shape, seq_name, seg4, n_class, stream, counts), seq_name, seg4, name)
 
 
-# ---- atrial area and length (atrial.py) on the labels ukbb_fcn_unpack_labels left in HBM --------------------------------------
-
-def atrial_buffer_sizes(shape, n_class):
-    """(work, out) int32 counts of the device buffers launch_atrial_stats needs for an (X,Y,1,T) label volume: the work buffer
-    of ukbb_fcn_atrial_area_length (the T frames are its planes) and the T*n_class*8 statistics."""
-    X, Y, Z, T = shape
-    return 2 * T * n_class + 3 * X * Y * T + (X * Y * T + 3) // 4, T * n_class * 8
-
-
-def launch_atrial_stats(lab_ptr, shape, n_class, affine, long_axis, work_ptr, out_ptr, stream):
-    """Enqueue on ``stream`` the atrial statistics (atrial.frame_stats_host) of the uint8 labels at device address lab_ptr
-    (NIfTI order, one slice: every frame a plane) into out_ptr; buffers as atrial_buffer_sizes (the work buffer 8-byte aligned).
-    affine: the voxel-to-world matrix of the long-axis image; long_axis: atrial.long_axis_from_sa.  Asynchronous;
-    decode_atrial_stats reads the result once it is on the host."""
-    X, Y, Z, T = shape
-    if Z != 1:
-        raise ValueError('the atrial measures read a single-slice long-axis sequence, got Z = %d' % Z)
-    a = (C.c_double * 12)(*[float(v) for v in np.asarray(affine, np.float64)[:3, :4].ravel()])
-    l = (C.c_double * 3)(*[float(v) for v in np.asarray(long_axis, np.float64).ravel()[:3]])
-    _lib.check(_lib.lib.ukbb_fcn_atrial_area_length(lab_ptr, X, Y, T, n_class, a, l, work_ptr, out_ptr, stream), 'ukbb_fcn_atrial_area_length')
-
-
-def decode_atrial_stats(out, shape, n_class):
-    """The host copy ``out`` (int32) of what launch_atrial_stats wrote -> [T, n_class, 8]."""
-    T = shape[3]
-    return np.asarray(out, dtype=np.int32)[:T * n_class * 8].reshape(T, n_class, 8).copy()
-
-
 def device_atrial_stats(lab_t, shape, n_class, affine, long_axis, stream=0):
-    """atrial.frame_stats_host of the (X,Y,1,T) uint8 label volume ``lab_t`` (NIfTI order) on the device; only the T*n_class*32
-    bytes of statistics cross to the host."""
-    import torch
-    n_work, n_out = atrial_buffer_sizes(shape, n_class)
-    work = torch.empty(n_work, dtype=torch.int32, device=lab_t.device)
-    out = torch.empty(n_out, dtype=torch.int32, device=lab_t.device)
-    launch_atrial_stats(lab_t.data_ptr(), shape, n_class, affine, long_axis, work.data_ptr(), out.data_ptr(), stream)
-    return decode_atrial_stats(out.cpu().numpy(), shape, n_class)
+    """atrial.frame_stats_host of the (X,Y,1,T) uint8 label volume ``lab_t`` (NIfTI order) on the device."""
+    return label_statistics(lab_t, shape, n_class, [AtrialStats()], {'atrial': (affine, long_axis)}, stream)['atrial']
 
 
 def aortic_lstm_sequence_device(image, engine, z_score=True, weight_R=5, weight_r=0.1, time_step=1, return_aux=False, qc=False):
@@ -587,15 +594,11 @@ def aortic_unet_sequence_device(image, engine, batch_slices=128, return_aux=Fals
     batch = torch.empty((n, X2, Y2), dtype=torch.float32, device=dev)
     zscore_pack(vol.data_ptr(), image.dtype, (X, Y, Z, T), vol.stride(), mu, den, (X2, Y2, x_pre, y_pre), batch.data_ptr(), stream)
     pred = torch.empty((n, X2, Y2), dtype=torch.int32, device=dev)
-    engine.reserve(min(batch_slices, n), X2, Y2)
-    for i in range(0, n, batch_slices):
-        m = min(batch_slices, n - i)
-        engine.run_device(batch[i].data_ptr(), m, X2, Y2, pred_ptr=pred[i].data_ptr(), stream=stream)
     n_class = engine.arch.n_class
     lab = torch.empty(X * Y * Z * T, dtype=torch.uint8, device=dev)
     counts = torch.empty((T, n_class), dtype=torch.int64, device=dev)
-    _lib.check(_lib.lib.ukbb_fcn_unpack_labels(pred.data_ptr(), X, Y, Z, T, X2, Y2, x_pre, y_pre, n_class,
-                                               lab.data_ptr(), counts.data_ptr(), stream), 'ukbb_fcn_unpack_labels')
+    forward_and_unpack(engine, batch.data_ptr(), pred.data_ptr(), (X, Y, Z, T), (X2, Y2, x_pre, y_pre), batch_slices, lab.data_ptr(),
+                       counts.data_ptr(), stream)
     out = lab.cpu().numpy().reshape((X, Y, Z, T), order='F').astype(np.int32)
     if return_aux:
         aux = {'mu': mu, 'den': den, 'n_roi': n_roi, 'val_l': val_l, 'counts': counts.cpu().numpy()}

@@ -1,0 +1,131 @@
+"""The tables deploy_network.py derives from a label map while it segments: ``--output_csv`` (ventricular volumes, measures.py),
+``--qc_csv`` (the sa / la / atrium gate, qc_gates.py) and ``--atrial_csv`` (atrial areas and lengths per frame, atrial.py).
+
+One ``LabelTables`` is made per run from the flags.  It checks the flags, names the device statistics the run needs of every
+label volume (``statistics``), gives the per-subject arguments of those statistics (``subject_args``), turns one subject's class
+counts and statistics into rows (``record``) and at the end writes the tables, measuring the subjects an earlier run segmented
+from their files (``write``).  Statistics arrive as ``{key: value}`` -- 'qc': qc_gates.stats_host or device_pipeline.GateStats,
+'atrial': atrial.frame_stats_host or device_pipeline.AtrialStats -- from the device (SubjectPipeline, segment_sequence_device) or
+from the host twins (``from_labels``)."""
+import os
+
+from . import atrial, measures, nifti, qc_gates
+
+
+class LabelTables:
+    def __init__(self, FLAGS, engine=None):
+        self.FLAGS = FLAGS
+        self.seq, self.seg4 = seq, seg4 = FLAGS.seq_name, FLAGS.seg4
+        self.n_class = n_class = None if engine is None else engine.arch.n_class
+        self.output_csv, self.qc_csv, self.atrial_csv = (getattr(FLAGS, f, '') for f in ('output_csv', 'qc_csv', 'atrial_csv'))
+        if self.output_csv and (seq != 'sa' or not FLAGS.process_seq):
+            raise ValueError('--output_csv writes the table of short_axis/eval_ventricular_volume.py: it needs --seq_name sa in sequence mode')
+        if self.qc_csv:
+            if not FLAGS.process_seq:
+                raise ValueError('--qc_csv gates the segmentation of a whole sequence: it needs sequence mode (--process_seq)')
+            if n_class is not None and n_class < qc_gates.min_classes(seq, seg4):
+                raise ValueError('--qc_csv: the gate of --seq_name {0}{1} reads {2} classes, the model has {3}'.format(
+                    seq, ' --seg4' if seg4 else '', qc_gates.min_classes(seq, seg4), n_class))
+        if self.atrial_csv:
+            if seq not in ('la_2ch', 'la_4ch') or seg4 or not FLAGS.process_seq:
+                raise ValueError('--atrial_csv measures the atria of long_axis/eval_atrial_volume.py: it needs --seq_name la_2ch or la_4ch '
+                                 'without --seg4, in sequence mode')
+            if n_class is not None and n_class < qc_gates.min_classes(seq):
+                raise ValueError('--atrial_csv: --seq_name {0} has {1} classes, the model has {2}'.format(seq, qc_gates.min_classes(seq), n_class))
+        # subject -> row(s).  The atrial rows carry the gate's verdict: gated, though no --qc_csv is written
+        self.volumes = {} if self.output_csv else None
+        self.gate = {} if self.qc_csv or self.atrial_csv else None
+        self.atrial = {} if self.atrial_csv else None
+
+    def statistics(self):
+        """The device statistics this run needs of every label volume.  Device paths only: device_pipeline loads the HIP library."""
+        from . import device_pipeline
+        return ([device_pipeline.GateStats(self.seq, self.seg4)] if self.gate is not None else []) + \
+            ([device_pipeline.AtrialStats()] if self.atrial is not None else [])
+
+    def subject_args(self, data_dir, nim, log):
+        """{key: argument} of the statistics that take one per subject.  --atrial_csv: (affine of the long-axis image, long axis), the
+        long axis from the short-axis header as eval_atrial_volume.py:45-48 -- absent, and logged, for a subject without sa.nii.gz (the
+        reference skips it) or with more than one slice."""
+        if self.atrial is None:
+            return {}
+        sa_name = '{0}/sa.nii.gz'.format(data_dir)
+        if not os.path.exists(sa_name):
+            log('  Directory {0} does not contain sa.nii.gz: no long axis, no atrial measures.'.format(data_dir))
+            return {}
+        if nim.shape[2] != 1:
+            log('  {0} slices: the atrial measures read a single-slice long-axis sequence. Skip.'.format(nim.shape[2]))
+            return {}
+        return {'atrial': (nim.affine, atrial.long_axis_from_sa(nifti.load_header(sa_name)['affine']))}
+
+    def from_labels(self, seg, args, n_class):
+        """(counts, statistics) of an (X,Y,Z,T) label volume for ``record`` from the host twins, each only if its table is on.  n_class:
+        the model's, or None for a label file."""
+        counts = None if self.volumes is None else measures.counts_from_labels(seg, n_class or 4)
+        stats = {}
+        if self.gate is not None:
+            stats['qc'] = qc_gates.stats_host(seg, self.seq, self.seg4, n_class)
+        if 'atrial' in args:
+            stats['atrial'] = atrial.frame_stats_host(seg[:, :, 0, :], self.n_class or qc_gates.min_classes(self.seq), *args['atrial'])
+        return counts, stats
+
+    def record(self, data, data_dir, nim, counts, stats, log):
+        """The rows of one subject from its per-frame class counts and statistics; nim: its image (affine and voxel size).  The gate comes
+        first -- the atrial rows carry its verdict -- and the message of a failing subject is logged the way the reference prints it."""
+        if self.volumes is not None and counts is not None:
+            self.volumes[data] = measures.sa_row(counts, nim.header['pixdim'])
+        if 'qc' in stats:
+            name = '{0}/{1}'.format(data_dir, qc_gates.seg_file_name(self.seq, self.seg4))
+            self.gate[data] = passed, message = qc_gates.gate_from_stats(stats['qc'], self.seq, self.seg4, name)
+            if not passed:
+                log(message)
+        if 'atrial' in stats:
+            self.atrial[data] = atrial.frame_rows(stats['atrial'], nim.affine, nim.header['pixdim'], self.gate[data][0])
+
+    def _back_fill(self, rows, data, log):
+        """A subject segmented by an earlier run (skipped by this one) into ``rows`` from its label file, the way the evaluation scripts
+        read it: the volumes need image and segmentation (eval_ventricular_volume.py:35), the atria an sa.nii.gz for the long axis."""
+        data_dir = os.path.join(self.FLAGS.data_dir, data)
+        seg_name = '{0}/{1}_{2}.nii.gz'.format(data_dir, 'seg4' if self.seq == 'la_4ch' and self.seg4 else 'seg', self.seq)
+        sa_name = '{0}/sa.nii.gz'.format(data_dir)
+        if not os.path.exists(seg_name) or (rows is not self.gate and not os.path.exists(sa_name)):
+            return
+        nim = nifti.load(seg_name)
+        seg = nim.get_data()
+        if rows is self.volumes:
+            head = nifti.load_header(sa_name)               # the voxel size is the image's (:40-47)
+            self.record(data, data_dir, nifti.NiftiImage(None, head['affine'], head['pixdim']), measures.counts_from_labels(seg, 4), {}, log)
+        elif seg.ndim == 4:
+            args = self.subject_args(data_dir, nim, log) if rows is self.atrial else {}
+            if args or rows is self.gate:
+                stats = self.from_labels(seg, args, None)[1]
+                if data in self.gate:
+                    del stats['qc']
+                self.record(data, data_dir, nim, None, stats, log)
+
+    def write(self, shard_subjects, log):
+        """The tables of this worker's subjects, sorted (the order of the evaluation scripts): volumes, atria, gate -- verdicts the
+        atrial table had to produce land in the gate table, logged once.  The gate table is written only with --qc_csv."""
+        F = self.FLAGS
+        for rows, csv in ((self.volumes, self.output_csv), (self.atrial, self.atrial_csv), (self.gate, self.qc_csv)):
+            if not csv:
+                continue
+            # with --work_stealing this worker may also have segmented subjects of other shards (their rows are in ``rows``), and
+            # another worker may have taken some of this one's: both then hold a row for it -- identical text -- and the merge keeps one
+            subjects = sorted(set(shard_subjects) | set(rows))
+            for data in subjects:
+                if data not in rows:
+                    self._back_fill(rows, data, log)
+            path = measures.shard_csv_name(csv, F.shard_index, F.num_shards)
+            if rows is self.atrial:
+                out = [(data, r) for data in subjects for r in rows.get(data, [])]
+                atrial.write_frames_csv(path, out)
+                log('Atrial measures of {0} frames and labels written to {1}'.format(len(out), path))
+                continue
+            out = [(data, rows[data]) for data in subjects if data in rows]
+            if rows is self.volumes:
+                measures.write_csv(path, measures.SA_COLUMNS, out)
+                log('Clinical measures of {0} subjects written to {1}'.format(len(out), path))
+            else:
+                qc_gates.write_csv(path, self.seq, self.seg4, out)
+                log('Quality-control verdicts of {0} subjects written to {1}'.format(len(out), path))

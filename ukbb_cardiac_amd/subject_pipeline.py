@@ -21,9 +21,7 @@ import queue
 
 import numpy as np
 
-from . import _lib
-from .device_pipeline import (atrial_buffer_sizes, decode_atrial_stats, decode_gate_stats, device_dtype_ok, device_percentiles,
-                              gate_buffer_sizes, launch_atrial_stats, launch_gate_stats, pack_rescaled)
+from .device_pipeline import device_dtype_ok, device_percentiles, forward_and_unpack, pack_rescaled, stat_skipped
 from .pipeline import pad_amounts
 
 
@@ -42,12 +40,11 @@ class Staged:
 class SubjectPipeline:
     HEADROOM = 4096                                         # bytes of writable pinned memory in front of every staged array
 
-    def __init__(self, engine, max_shape, batch_slices=128, depth=3, thres=(1, 99), extra_inputs=2, pinned_inputs=True, qc=None, atrial=False):
+    def __init__(self, engine, max_shape, batch_slices=128, depth=3, thres=(1, 99), extra_inputs=2, pinned_inputs=True, stats=()):
         """max_shape: largest (X, Y, Z, T) expected (buffers are sized for it; larger volumes re-allocate).
-        qc = (seq_name, seg4): also compute the statistics of that sequence's quality-control gate (qc_gates.py) from the
-        labels on the compute stream, right behind the unpack; ``Result.qc`` then holds them (None otherwise).
-        atrial: reserve the buffers of the atrial statistics (atrial.py); a subject submitted with ``atrial=(affine, long_axis)``
-        then gets them computed behind the unpack as well, into ``Result.atrial`` [T, n_class, 8].
+        stats: label statistics (the classes of device_pipeline with sizes / launch / decode) to compute from every subject's labels on the compute
+        stream, right behind the unpack; ``Result.stats`` holds them by key.  One that takes a per-subject argument is computed for
+        the subjects submitted with it (``submit(image, {key: arg})``).
         extra_inputs: pinned input buffers beyond ``depth`` (one per reader thread that may hold one).
         pinned_inputs=False: no pinned input pool at all -- for cohorts whose volumes are produced on the device
         (``submit_generated``; ``stage`` / ``submit`` of host arrays then block forever and must not be used)."""
@@ -56,8 +53,7 @@ class SubjectPipeline:
         self.engine = engine
         self.batch_slices = int(batch_slices)
         self.thres = tuple(thres)
-        self.qc = None if qc is None else (qc[0], bool(qc[1]))
-        self.atrial = bool(atrial)
+        self.stats = tuple(stats)
         self.dev = torch.device('cuda', engine.device)
         self.s_in = torch.cuda.Stream(self.dev)
         self.s_cmp = torch.cuda.Stream(self.dev)
@@ -90,16 +86,11 @@ class SubjectPipeline:
         s.d_pred = torch.empty(s.cap_pix, dtype=torch.int32, device=self.dev)
         s.d_lab = torch.empty(s.cap_vox, dtype=torch.uint8, device=self.dev)
         s.d_cnt = torch.empty(T * 16, dtype=torch.int64, device=self.dev)
-        if self.qc is not None:
-            s.cap_qc = gate_buffer_sizes(self.qc[0], self.qc[1], shape, 16)     # n_class <= 16, as d_cnt
-            s.d_qc_work = torch.empty(s.cap_qc[0], dtype=torch.int32, device=self.dev)
-            s.d_qc = torch.empty(s.cap_qc[1], dtype=torch.int32, device=self.dev)
-            s.pin_qc = torch.empty(s.cap_qc[1], dtype=torch.int32, pin_memory=True)
-        if self.atrial:
-            s.cap_at = atrial_buffer_sizes(shape, 16)
-            s.d_at_work = torch.empty(s.cap_at[0], dtype=torch.int32, device=self.dev)
-            s.d_at = torch.empty(s.cap_at[1], dtype=torch.int32, device=self.dev)
-            s.pin_at = torch.empty(s.cap_at[1], dtype=torch.int32, pin_memory=True)
+        s.stats = []                                          # (statistic, d_work, d_out, pin_out, capacity)
+        for stat in self.stats:
+            cap = stat.sizes(shape, 16)                       # n_class <= 16, as d_cnt
+            s.stats.append((stat, torch.empty(cap[0], dtype=torch.int32, device=self.dev), torch.empty(cap[1], dtype=torch.int32, device=self.dev),
+                            torch.empty(cap[1], dtype=torch.int32, pin_memory=True), cap))
         s.ev_in, s.ev_cmp, s.ev_out = torch.cuda.Event(), torch.cuda.Event(), torch.cuda.Event()
         s.busy = False
         return s
@@ -131,32 +122,33 @@ class SubjectPipeline:
             return True
         return False
 
+    @staticmethod
+    def _fits(slot, shape):
+        """Do the slot's buffers -- volume, batch, counts and every statistic's -- hold a subject of this shape?"""
+        X, Y, Z, T = shape
+        X2, Y2 = pad_amounts(X, Y)[:2]
+        return (X * Y * Z * T <= slot.cap_vox and X2 * Y2 * Z * T <= slot.cap_pix and T * 16 <= slot.pin_cnt.numel()
+                and all(need <= have for stat, _, _, _, cap in slot.stats for need, have in zip(stat.sizes(shape, 16), cap)))
+
     def _acquire(self, shape):
         slot = self.slots[self._next]
         if slot.busy:
             raise RuntimeError('pipeline full: collect() a result before staging another subject (depth %d)' % self.depth)
-        X, Y, Z, T = shape
-        too_small = X * Y * Z * T > slot.cap_vox or pad_amounts(X, Y)[0] * pad_amounts(X, Y)[1] * Z * T > slot.cap_pix or T * 16 > slot.pin_cnt.numel()
-        if not too_small and self.qc is not None:
-            need = gate_buffer_sizes(self.qc[0], self.qc[1], shape, 16)
-            too_small = need[0] > slot.cap_qc[0] or need[1] > slot.cap_qc[1]
-        if not too_small and self.atrial:
-            need = atrial_buffer_sizes(shape, 16)
-            too_small = need[0] > slot.cap_at[0] or need[1] > slot.cap_at[1]
-        if too_small:
+        if not self._fits(slot, shape):
             self.torch.cuda.synchronize(self.dev)
             self.slots[self._next] = slot = self._make_slot(shape)
         return slot
 
     # ---- submit / collect -----------------------------------------------------------------------------
-    def submit(self, image, atrial=None):
+    def submit(self, image, stat_args=None):
         """Enqueue one (X,Y,Z,T) float32 / uint8 / int16 / uint16 volume: a ``Staged`` object / the array ``stage()`` handed
         out (used in place), or any other array (copied into a pinned buffer first: one host memcpy).  Returns once the exact
         percentiles of the volume are known (the copy-in stream is waited for, the compute stream is not).  Subjects of
         different dtypes may follow each other: the select and pack kernels are chosen per subject.
-        atrial = (affine, long_axis) (a pipeline made with ``atrial=True``, Z = 1): also the atrial statistics of this subject."""
-        if atrial is not None and not self.atrial:
-            raise ValueError('this pipeline was made without the atrial buffers')
+        stat_args = {key: arg}: this subject's arguments of the statistics that take one."""
+        unknown = set(stat_args or ()) - {stat.key for stat in self.stats}
+        if unknown:
+            raise ValueError('this pipeline was made without the statistics %s' % sorted(unknown))
         if isinstance(image, Staged):
             st = image
             with self._lock:
@@ -171,7 +163,7 @@ class SubjectPipeline:
                 with self._lock:
                     self._staged.pop(id(st.array), None)
                 st.array[...] = image
-        self._enqueue(st.array.shape, st, None, atrial)
+        self._enqueue(st.array.shape, st, None, stat_args)
 
     def submit_generated(self, shape, fill):
         """Enqueue one (X,Y,Z,T) float32 volume that is PRODUCED ON THE DEVICE: ``fill(d_ptr, n, stream)`` enqueues, on the copy-in
@@ -182,7 +174,7 @@ class SubjectPipeline:
             raise ValueError('expected an (X,Y,Z,T) shape, got %s' % (shape,))
         self._enqueue(tuple(int(v) for v in shape), None, fill)
 
-    def _enqueue(self, shape, st, fill, atrial=None):
+    def _enqueue(self, shape, st, fill, stat_args=None):
         torch = self.torch
         X, Y, Z, T = shape
         slot = self._acquire(shape)
@@ -190,11 +182,10 @@ class SubjectPipeline:
         slot.busy = True
         slot.shape = shape
         slot.staged = st
-        slot.atrial = atrial is not None
+        slot.live = [entry for entry in slot.stats if not stat_skipped(entry[0], stat_args)]
         self._next = (self._next + 1) % self.depth
         n_class = self.engine.arch.n_class
         X2, Y2, x_pre, _, y_pre, _ = pad_amounts(X, Y)
-        nsl = T * Z
         dtype = np.dtype(np.float32) if st is None else st.array.dtype
         with torch.cuda.stream(self.s_in):
             if st is not None:
@@ -214,30 +205,18 @@ class SubjectPipeline:
             # element strides of the Fortran-ordered (X,Y,Z,T) volume
             pack_rescaled(slot.d_vol.data_ptr(), dtype, (X, Y, Z, T), (1, X, X * Y, X * Y * Z), lo, hi, (X2, Y2, x_pre, y_pre),
                           slot.d_batch.data_ptr(), cs)
-            self.engine.reserve(min(self.batch_slices, nsl), X2, Y2)
-            px = X2 * Y2
-            for i in range(0, nsl, self.batch_slices):
-                m = min(self.batch_slices, nsl - i)
-                self.engine.run_device(slot.d_batch.data_ptr() + 4 * i * px, m, X2, Y2, pred_ptr=slot.d_pred.data_ptr() + 4 * i * px, stream=cs)
-            _lib.check(_lib.lib.ukbb_fcn_unpack_labels(slot.d_pred.data_ptr(), X, Y, Z, T, X2, Y2, x_pre, y_pre, n_class,
-                                                       slot.d_lab.data_ptr(), slot.d_cnt.data_ptr(), cs), 'ukbb_fcn_unpack_labels')
-            if self.qc is not None:
-                launch_gate_stats(self.qc[0], self.qc[1], slot.d_lab.data_ptr(), shape, n_class, slot.d_qc_work.data_ptr(),
-                                  slot.d_qc.data_ptr(), cs)
-            if atrial is not None:
-                launch_atrial_stats(slot.d_lab.data_ptr(), shape, n_class, atrial[0], atrial[1], slot.d_at_work.data_ptr(),
-                                    slot.d_at.data_ptr(), cs)
+            forward_and_unpack(self.engine, slot.d_batch.data_ptr(), slot.d_pred.data_ptr(), shape, (X2, Y2, x_pre, y_pre), self.batch_slices,
+                               slot.d_lab.data_ptr(), slot.d_cnt.data_ptr(), cs)
+            for stat, d_work, d_out, _, _ in slot.live:
+                stat.launch(slot.d_lab.data_ptr(), shape, n_class, d_work.data_ptr(), d_out.data_ptr(), cs, (stat_args or {}).get(stat.key))
             slot.ev_cmp.record(self.s_cmp)
         with torch.cuda.stream(self.s_out):
             self.s_out.wait_event(slot.ev_cmp)
             slot.pin_lab[:n].copy_(slot.d_lab[:n], non_blocking=True)
             slot.pin_cnt[:T * n_class].copy_(slot.d_cnt[:T * n_class], non_blocking=True)
-            if self.qc is not None:
-                n_qc = gate_buffer_sizes(self.qc[0], self.qc[1], shape, n_class)[1]
-                slot.pin_qc[:n_qc].copy_(slot.d_qc[:n_qc], non_blocking=True)
-            if atrial is not None:
-                n_at = atrial_buffer_sizes(shape, n_class)[1]
-                slot.pin_at[:n_at].copy_(slot.d_at[:n_at], non_blocking=True)
+            for stat, _, d_out, pin_out, _ in slot.live:
+                n_out = stat.sizes(shape, n_class)[1]         # this shape's own count, not the slot's capacity
+                pin_out[:n_out].copy_(d_out[:n_out], non_blocking=True)
             slot.ev_out.record(self.s_out)
         self._inflight.append(slot)
 
@@ -245,8 +224,8 @@ class SubjectPipeline:
         return len(self._inflight)
 
     def collect(self, copy=True):
-        """Oldest submitted subject -> Result (labels uint8 (X,Y,Z,T), counts int64 [T, n_class], clip (lo, hi), image =
-        the staged input volume).  Call ``Result.done()`` when the image is no longer needed.
+        """Oldest submitted subject -> Result (labels uint8 (X,Y,Z,T), counts int64 [T, n_class], clip (lo, hi), stats = {key: the
+        decoded statistic}, image = the staged input volume).  Call ``Result.done()`` when the image is no longer needed.
         copy=False: ``labels`` is a view of the slot's pinned buffer, valid only until ``depth`` more subjects have been submitted
         (for callers that consume or drop it at once)."""
         slot = self._inflight.pop(0)
@@ -258,16 +237,11 @@ class SubjectPipeline:
         if copy:
             lab = lab.copy(order='F')
         cnt = slot.pin_cnt.numpy()[:T * n_class].reshape(T, n_class).copy()
-        qc = None
-        if self.qc is not None:
-            n_qc = gate_buffer_sizes(self.qc[0], self.qc[1], slot.shape, n_class)[1]
-            qc = decode_gate_stats(self.qc[0], self.qc[1], slot.pin_qc.numpy()[:n_qc], slot.shape, n_class, cnt)
-        at = None
-        if slot.atrial:
-            at = decode_atrial_stats(slot.pin_at.numpy()[:atrial_buffer_sizes(slot.shape, n_class)[1]], slot.shape, n_class)
+        stats = {stat.key: stat.decode(pin_out.numpy()[:stat.sizes(slot.shape, n_class)[1]], slot.shape, n_class, cnt)
+                 for stat, _, _, pin_out, _ in slot.live}
         st, slot.staged = slot.staged, None
         slot.busy = False
-        return Result(self, lab, cnt, slot.clip, st, qc, at)
+        return Result(self, lab, cnt, slot.clip, st, stats)
 
     def run(self, volumes):
         """Generator: segment an iterable of volumes with up to depth-1 subjects in flight; yields Results in order
@@ -290,10 +264,8 @@ class SubjectPipeline:
 
 
 class Result:
-    def __init__(self, pipe, labels, counts, clip, staged, qc=None, atrial=None):
-        self._pipe, self.labels, self.counts, self.clip, self._staged = pipe, labels, counts, clip, staged
-        self.qc = qc                                          # the gate statistics (SubjectPipeline(qc=...)), or None
-        self.atrial = atrial                                  # the atrial statistics (submit(..., atrial=...)), or None
+    def __init__(self, pipe, labels, counts, clip, staged, stats):
+        self._pipe, self.labels, self.counts, self.clip, self._staged, self.stats = pipe, labels, counts, clip, staged, stats
 
     @property
     def image(self):
