@@ -146,6 +146,25 @@ def test_mean_of_large_masks_follows_numpys_buffers():
         _assert_equal(_image(seg.shape, dtype, 9), seg)
 
 
+# ---- aux['qc'] and aux['counts'] of the sequence function: both forwards --------------------------------------------------
+@pytest.mark.parametrize('name', ['UNet_ao', 'UNet-LSTM_ao'])
+def test_sequence_device_qc_and_counts_equal_host(name):
+    from test_integer_volumes_gpu import _engine, _mr_like
+    eng = _engine(name)
+    try:
+        vol = _mr_like((64, 48, 2, 11), np.int16, 5)
+        pred, aux = dp.aortic_sequence_device(vol, eng, window=None if name == 'UNet_ao' else (5, 0.1, 1), return_aux=True, qc=True)
+    finally:
+        eng.close()
+    got, want = aux['qc'], aorta_qc.stats_host(vol, pred)
+    assert got['n_large'].tolist() == want['n_large'].tolist()
+    assert np.array_equal(got['max'], want['max'], equal_nan=True)
+    assert got['mean_ed'].dtype == want['mean_ed'].dtype and got['mean_ed'].tobytes() == want['mean_ed'].tobytes()
+    counts = np.stack([[np.sum(pred[..., t] == c) for c in range(3)] for t in range(vol.shape[3])])
+    np.testing.assert_array_equal(aux['counts'], counts)
+    assert len(np.unique(pred)) > 1
+
+
 # ---- deploy_network_ao.py --aortic_qc_full: device path == host path --------------------------------------------------
 QC_LINE = re.compile(r'^(The area of|The image becomes|The segmentation has|There is)')
 

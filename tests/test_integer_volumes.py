@@ -112,7 +112,7 @@ def test_device_functions_still_refuse_other_dtypes():
     """float64 (any file with a non-trivial scl_slope), int32, int8: TypeError before anything touches a device."""
     for t in (np.float64, np.int32, np.int8, np.uint32):
         img = np.zeros((8, 8, 1, 2), t)
-        for f in (lambda: dp.segment_sequence_device(img, _FakeEngine()), lambda: dp.aortic_unet_sequence_device(img, _FakeEngine()),
-                  lambda: dp.aortic_lstm_sequence_device(img, _FakeEngine())):
+        for f in (lambda: dp.segment_sequence_device(img, _FakeEngine()), lambda: dp.aortic_sequence_device(img, _FakeEngine()),
+                  lambda: dp.aortic_sequence_device(img, _FakeEngine(), window=(5, 0.1, 1))):
             with pytest.raises(TypeError):
                 f()

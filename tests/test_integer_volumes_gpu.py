@@ -193,7 +193,7 @@ def test_aortic_unet_sequence_device_integer_equals_host_path(dtype):
         vol = _mr_like(shape, dtype, 11)
         prob = pipeline.aortic_prob_sequence(vol.copy(), lambda b: eng.run(b), batch_slices=64)
         want = np.argmax(prob, axis=-1).astype(np.int32)
-        got, aux = dp.aortic_unet_sequence_device(vol, eng, batch_slices=64, return_aux=True)
+        got, aux = dp.aortic_sequence_device(vol, eng, batch_slices=64, return_aux=True)
         np.testing.assert_array_equal(got, want)
         counts = np.stack([[np.sum(want[..., t] == c) for c in range(3)] for t in range(shape[3])])
         np.testing.assert_array_equal(aux['counts'], counts)
@@ -212,7 +212,7 @@ def test_aortic_lstm_sequence_device_integer_equals_host_path(model, time_step):
             vol = _mr_like(shape, dtype, 20 + i + time_step)
             prob = pipeline.aortic_lstm_prob_sequence(vol.copy(), lambda f, R, r, ts=1: eng.run_cine(f, R, r, ts)[0], time_step=time_step)
             want = np.argmax(prob, axis=-1).astype(np.int32)
-            got, aux = dp.aortic_lstm_sequence_device(vol, eng, time_step=time_step, return_aux=True)
+            got, aux = dp.aortic_sequence_device(vol, eng, window=(5, 0.1, time_step), return_aux=True, prob=True)
             np.testing.assert_array_equal(aux['prob'], prob)
             np.testing.assert_array_equal(got, want)
     finally:

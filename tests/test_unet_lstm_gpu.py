@@ -166,15 +166,15 @@ def test_drop_in_aortic_script_with_the_default_model(tmp_path, model):
 
 @pytest.mark.parametrize('shape,time_step', [((70, 90, 1, 11), 1), ((240, 196, 1, 25), 1), ((64, 48, 2, 13), 2)])
 def test_aortic_device_pipeline_equals_host_pipeline(model, shape, time_step):
-    """z-score, pad, transposes, windows, argmax on the GPU (device_pipeline.aortic_lstm_sequence_device) against the numpy
+    """z-score, pad, transposes, windows, argmax on the GPU (device_pipeline.aortic_sequence_device) against the numpy
     mirror of deploy_network_ao.py:92-108,129-189 driven by the same engine: same probabilities bit for bit, same labels."""
     from ukbb_cardiac_amd import pipeline
-    from ukbb_cardiac_amd.device_pipeline import aortic_lstm_sequence_device
+    from ukbb_cardiac_amd.device_pipeline import aortic_sequence_device
     arch, params, eng = model
     rng = np.random.default_rng(shape[0] + time_step)
     vol = np.asfortranarray(np.round(100 * rng.gamma(2.0, 1.0, size=shape)).astype(np.float32))
     keep = vol.copy()
-    pred, aux = aortic_lstm_sequence_device(vol, eng, time_step=time_step, return_aux=True)
+    pred, aux = aortic_sequence_device(vol, eng, window=(5, 0.1, time_step), return_aux=True, prob=True)
     assert np.array_equal(vol, keep)                                       # input untouched
     prob = pipeline.aortic_lstm_prob_sequence(vol, lambda f, R, r, ts=1: eng.run_cine(f, R, r, ts)[0], time_step=time_step)
     np.testing.assert_array_equal(aux['prob'], prob)

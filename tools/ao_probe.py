@@ -1,5 +1,5 @@
 """Per-subject split of the aortic UNet-LSTM sequence path (deploy_network_ao.py:92-189) on one GPU: host pre/post-processing
-around Engine.run_cine against device_pipeline.aortic_lstm_sequence_device.  Prints milliseconds per 100-frame cine."""
+around Engine.run_cine against device_pipeline.aortic_sequence_device.  Prints milliseconds per 100-frame cine."""
 import os
 import sys
 import time
@@ -9,7 +9,7 @@ import numpy as np
 
 from ukbb_cardiac_amd import pipeline
 from ukbb_cardiac_amd.arch import MODELS
-from ukbb_cardiac_amd.device_pipeline import aortic_lstm_sequence_device
+from ukbb_cardiac_amd.device_pipeline import aortic_sequence_device
 from ukbb_cardiac_amd.engine import Engine
 from ukbb_cardiac_amd.image_utils import normalise_intensity
 from ukbb_cardiac_amd.weights import synthetic_params
@@ -41,8 +41,8 @@ def main():
     frames = np.zeros((100, 256, 256), np.float32)
     tc, _ = timed(lambda: eng.run_cine(frames), 3)
     print('run_cine alone (incl. H2D 26 MB + D2H 78 MB prob + pred): %.1f ms' % tc)
-    td, pred_d = timed(lambda: aortic_lstm_sequence_device(vol, eng), 5)
-    print('DEVICE PATH per subject (aortic_lstm_sequence_device): %.1f ms, identical labels: %s' % (td, np.array_equal(pred, pred_d)))
+    td, pred_d = timed(lambda: aortic_sequence_device(vol, eng, window=(5, 0.1, 1)), 5)
+    print('DEVICE PATH per subject (aortic_sequence_device): %.1f ms, identical labels: %s' % (td, np.array_equal(pred, pred_d)))
     import torch
     from ukbb_cardiac_amd.device_pipeline import device_zscore_stats
     v = torch.from_numpy(vol).cuda()

@@ -54,7 +54,7 @@ if __name__ == '__main__':
             vol = volume(shape, True)
             eng = engs['UNet_ao']
             prob = pipeline.aortic_prob_sequence(vol, lambda b: eng.run(b), batch_slices=5)
-            got = dp.aortic_unet_sequence_device(vol, eng, batch_slices=int(rng.integers(1, 9)))
+            got = dp.aortic_sequence_device(vol, eng, batch_slices=int(rng.integers(1, 9)))
             ok = np.array_equal(got, np.argmax(prob, -1).astype(np.int32))
         else:
             T = int(rng.integers(4, 16))
@@ -65,7 +65,7 @@ if __name__ == '__main__':
             prob = pipeline.aortic_lstm_prob_sequence(vol, lambda f, R, r, t_=1: eng.run_cine(f, R, r, t_)[0], time_step=ts)
             with np.errstate(invalid='ignore'):
                 want = np.argmax(prob, -1).astype(np.int32)
-            got, aux = dp.aortic_lstm_sequence_device(vol, eng, time_step=ts, return_aux=True)
+            got, aux = dp.aortic_sequence_device(vol, eng, window=(5, 0.1, ts), return_aux=True, prob=True)
             ok = np.array_equal(got, want) and np.array_equal(aux['prob'], prob, equal_nan=True)
         bad += not ok
         print('%-8s %-22s %s' % (which, shape, 'ok' if ok else 'MISMATCH'), flush=True)

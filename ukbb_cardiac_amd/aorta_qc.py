@@ -8,9 +8,9 @@ aortic/eval_aortic_area.py:68-69), from three statistics of the cine and its lab
   ``mean_ed [n_class]``     ``image_ED[seg_ED == k].mean()`` in numpy's result dtype (float32 for a float32 image, float64 for
                             an integer one; NaN for an empty mask; column 0 is not computed and holds NaN)
 
-``device_pipeline.device_qc_stats`` computes them on the GPU from the cine and the labels already there (``qc=True`` of the
-aortic device paths); ``stats_host`` computes the same numbers in numpy for the host path.  ``aorta_qc_full`` turns them and
-the per-frame class counts into the script's verdict and message."""
+``device_pipeline.device_qc_stats`` computes them on the GPU from the cine and the labels already there (``qc=True`` of
+``device_pipeline.aortic_sequence_device``); ``stats_host`` computes the same numbers in numpy for the host path.
+``aorta_qc_full`` turns them and the per-frame class counts into the script's verdict and message."""
 import warnings
 
 import numpy as np

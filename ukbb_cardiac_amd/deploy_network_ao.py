@@ -11,6 +11,7 @@ windows, ``network_ao.py:67-114``; fp32 only) in sequence mode, any ``--time_ste
 
 Output: ``seg_ao.nii.gz`` int32 with the input's affine and pixdim (``:189-196``).
 """
+import collections
 import os
 import sys
 import time
@@ -20,8 +21,9 @@ import numpy as np
 if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from ukbb_cardiac_amd import aorta_qc, measures, nifti, pipeline   # noqa: E402
+from ukbb_cardiac_amd import nifti, pipeline                      # noqa: E402
 from ukbb_cardiac_amd.flags import FlagError, FlagSet              # noqa: E402
+from ukbb_cardiac_amd.label_tables import AorticTable             # noqa: E402
 from ukbb_cardiac_amd.shard import default_device, shard_from_env, subjects_for_shard   # noqa: E402
 
 
@@ -77,20 +79,6 @@ def define_flags():
     return fs
 
 
-def _pp(central_pp, data, log=print):
-    """central_pp.loc[int(data)] of eval_aortic_area.py:80; None (no distensibility) when no spreadsheet was given."""
-    if not central_pp:
-        return None
-    try:
-        key = str(int(data))
-    except ValueError:
-        key = str(data)
-    if key not in central_pp:
-        # the reference's central_pp.loc[int(data)] raises KeyError here and the whole evaluation stops; this script keeps the areas
-        log('  Warning: subject {0} is not in the pressure spreadsheet: distensibility left empty.'.format(data))
-    return central_pp.get(key, float('nan'))
-
-
 def sequence_on_device(FLAGS, engine, image, log=print):
     """Does this cine take the device pre-processing?  Needs an engine, --device_preproc, --z_score, a 4-D float32, uint8,
     int16 or uint16 volume, and the once-per-dtype check that the device z-score reproduces this numpy (it mirrors numpy
@@ -103,9 +91,75 @@ def sequence_on_device(FLAGS, engine, image, log=print):
     return device_pipeline.device_zscore_matches_numpy(engine, warn=log, dtype=image.dtype)
 
 
+class _ReadAhead:
+    """nifti.load of the cines of a subject list on reader threads: asking for subject idx first schedules every read up to
+    subject idx + threads; names[i] is None for a subject without a cine."""
+    def __init__(self, names, threads):
+        from concurrent.futures import ThreadPoolExecutor
+        self.names, self.threads, self.pool = names, threads, ThreadPoolExecutor(threads)
+        self.pending, self.ahead = collections.deque(), 0           # (index, future) in ascending order; reads scheduled so far
+
+    def load(self, idx, name):
+        upto = min(idx + 1 + self.threads, len(self.names))
+        for i in range(self.ahead, upto):
+            if self.names[i] is not None:
+                self.pending.append((i, self.pool.submit(nifti.load, self.names[i])))
+        self.ahead = upto
+        while self.pending and self.pending[0][0] < idx:
+            self.pending.popleft()                                     # a cine that vanished between the listing and its turn
+        return self.pending.popleft()[1].result() if self.pending and self.pending[0][0] == idx else nifti.load(name)
+
+
+def _sequence_subject(FLAGS, data, data_dir, nim, forward, cine_forward, engine, log, table, save):
+    """One cine of sequence mode (deploy_network_ao.py:92-196): device function or host function, file, table line."""
+    window = (FLAGS.weight_R, FLAGS.weight_r, FLAGS.time_step) if FLAGS.model in ('UNet-LSTM', 'Temporal-UNet') else None
+    image = nim.get_data()
+    log('  Segmenting full sequence ...')
+    t0 = time.time()
+    if sequence_on_device(FLAGS, engine, image, log):
+        from ukbb_cardiac_amd.device_pipeline import aortic_sequence_device
+        pred, aux = aortic_sequence_device(image, engine, FLAGS.batch_slices, window, return_aux=True, qc=table.qc_full)
+        counts, qc_stats = aux['counts'], aux.get('qc')
+    else:
+        # rescale_intensity clips `image` in place; the script's quality control reads the file
+        image_qc = image.copy() if table.qc_full and not FLAGS.z_score else image
+        if window is not None:
+            prob = pipeline.aortic_lstm_prob_sequence(image, cine_forward, FLAGS.z_score, FLAGS.weight_R, FLAGS.weight_r,
+                                                      time_step=FLAGS.time_step)
+        else:
+            prob = pipeline.aortic_prob_sequence(image, forward, FLAGS.z_score, FLAGS.batch_slices)
+        pred = np.argmax(prob, axis=-1).astype(np.int32)      # host argmax, as :189
+        counts, qc_stats = table.from_labels(image_qc, pred)
+    if FLAGS.save_seg:
+        log('  Saving segmentation ...')
+        save(pred, '{0}/seg_{1}.nii.gz'.format(data_dir, FLAGS.seq_name), nim.affine, nim.header['pixdim'])
+    log('  Segmentation time = {:3f}s'.format(time.time() - t0))
+    table.record(data, nim.header['pixdim'], counts, qc_stats, log)
+
+
+def _frames_subject(FLAGS, data_dir, forward, log):
+    """The ED and ES frames of one subject (ED/ES mode, deploy_network_ao.py:206-258); False: a frame is missing, skipped."""
+    seq = FLAGS.seq_name
+    names = {fr: '{0}/{1}_{2}.nii.gz'.format(data_dir, seq, fr) for fr in ('ED', 'ES')}
+    if not all(os.path.exists(p) for p in names.values()):
+        log('  Directory {0} does not contain an image with file name {1} or {2}. Skip.'.format(
+            data_dir, os.path.basename(names['ED']), os.path.basename(names['ES'])))
+        return False
+    for fr in ('ED', 'ES'):
+        log('  Reading {} ...'.format(names[fr]))
+        nim = nifti.load(names[fr])
+        t0 = time.time()
+        pred = pipeline.aortic_segment_frame(nim.get_data(), forward, FLAGS.z_score, FLAGS.batch_slices)
+        log('  Segmentation time = {:3f}s'.format(time.time() - t0))
+        if FLAGS.save_seg:
+            log('  Saving segmentation ...')
+            nifti.save(pred, '{0}/seg_{1}_{2}.nii.gz'.format(data_dir, seq, fr), nim.affine, nim.header['pixdim'])
+    return True
+
+
 def run(FLAGS, forward, log=print, cine_forward=None, engine=None):
     """``forward`` stands for the frame-wise sess.run ('UNet'); ``cine_forward`` for the windowed one ('UNet-LSTM', 'Temporal-UNet').
-    With ``engine`` (and --device_preproc, --z_score) float32 windowed sequences take device_pipeline.aortic_lstm_sequence_device."""
+    With ``engine`` (and --device_preproc, --z_score) sequences take device_pipeline.aortic_sequence_device."""
     windowed = FLAGS.model in ('UNet-LSTM', 'Temporal-UNet')
     if FLAGS.model == 'Temporal-UNet' and cine_forward is None:
         # NotImplementedError (not ValueError): a Temporal-UNet needs the windowed forward, frame-wise calls cannot serve it
@@ -119,41 +173,17 @@ def run(FLAGS, forward, log=print, cine_forward=None, engine=None):
     start_time = time.time()
     data_list = subjects_for_shard(sorted(os.listdir(FLAGS.data_dir)), FLAGS.shard_index, FLAGS.num_shards)
     processed = []
-    seq = FLAGS.seq_name
-    csv_rows = None
-    qc_full = bool(getattr(FLAGS, 'output_csv', '') and getattr(FLAGS, 'aortic_qc', True) and getattr(FLAGS, 'aortic_qc_full', False))
-    if getattr(FLAGS, 'output_csv', ''):
-        if not FLAGS.process_seq:
-            raise ValueError('--output_csv writes the table of aortic/eval_aortic_area.py: it needs sequence mode')
-        csv_rows = {}
-        central_pp = measures.read_central_pp(FLAGS.pressure_csv) if getattr(FLAGS, 'pressure_csv', '') else {}
-
-        def _qc_row(counts, pixdim, pp, stats=None):
-            """The subject's table line, or None when the quality control drops it (the script's own message is printed);
-            ``stats``: the aorta_qc statistics, needed with --aortic_qc_full."""
-            if getattr(FLAGS, 'aortic_qc', True):
-                ok, why = aorta_qc.aorta_qc_full(counts, stats) if qc_full else measures.aorta_qc_from_counts(counts)
-                if not ok:
-                    log(why)
-                    return None
-            return measures.ao_row(counts, pixdim, pp)
+    table = AorticTable(FLAGS)                                  # --output_csv: flag checks first
     # Sequence mode with --io_threads > 0: the next cines are read (inflated) by reader threads while the GPU works on this one,
     # and the segmentation files are written behind it; order of subjects, log lines and files are those of the sequential loop.
     nthr = int(getattr(FLAGS, 'io_threads', 0)) if FLAGS.process_seq else 0
-    readers = writers = None
-    reads, writes = {}, []
+    reader = writers = None
+    writes = []
     if nthr > 0:
         from concurrent.futures import ThreadPoolExecutor
-        readers, writers = ThreadPoolExecutor(nthr), ThreadPoolExecutor(nthr)
-        names = ['{0}/{1}.nii.gz'.format(os.path.join(FLAGS.data_dir, d), seq) for d in data_list]
-        names = [n if os.path.isdir(os.path.dirname(n)) and os.path.exists(n) else None for n in names]
-        ahead = [0]
-
-        def prefetch(upto):
-            while ahead[0] < min(upto, len(names)):
-                if names[ahead[0]] is not None:
-                    reads[ahead[0]] = readers.submit(nifti.load, names[ahead[0]])
-                ahead[0] += 1
+        names = ['{0}/{1}.nii.gz'.format(os.path.join(FLAGS.data_dir, d), FLAGS.seq_name) for d in data_list]
+        reader = _ReadAhead([n if os.path.isdir(os.path.dirname(n)) and os.path.exists(n) else None for n in names], nthr)
+        writers = ThreadPoolExecutor(nthr)
 
     def save(*args):
         if writers is not None:
@@ -161,106 +191,35 @@ def run(FLAGS, forward, log=print, cine_forward=None, engine=None):
         else:
             nifti.save(*args)
 
-    for idx, data in enumerate(data_list):
-        log(data)
-        data_dir = os.path.join(FLAGS.data_dir, data)
-        if not os.path.isdir(data_dir):
-            continue
-        if FLAGS.process_seq:
-            image_name = '{0}/{1}.nii.gz'.format(data_dir, seq)
+    try:
+        for idx, data in enumerate(data_list):
+            log(data)
+            data_dir = os.path.join(FLAGS.data_dir, data)
+            if not os.path.isdir(data_dir):
+                continue
+            if not FLAGS.process_seq:
+                if windowed:                                           # reference: deploy_network_ao.py:202-205
+                    log('{0} does not support frame-wise segmentation. Please use the -process_seq flag.'.format(FLAGS.model))
+                    return processed
+                if _frames_subject(FLAGS, data_dir, forward, log):
+                    processed.append(data)
+                continue
+            image_name = '{0}/{1}.nii.gz'.format(data_dir, FLAGS.seq_name)
             if not os.path.exists(image_name):
                 log('  Directory {0} does not contain an image with file name {1}. Skip.'.format(
                     data_dir, os.path.basename(image_name)))
                 continue
             log('  Reading {} ...'.format(image_name))
-            if readers is not None:
-                prefetch(idx + 1 + nthr)
-                nim = reads.pop(idx).result() if idx in reads else nifti.load(image_name)
-            else:
-                nim = nifti.load(image_name)
-            image = nim.get_data()
-            log('  Segmenting full sequence ...')
-            t0 = time.time()
-            on_device = sequence_on_device(FLAGS, engine, image, log)
-            counts = qc_stats = None
-            if on_device and windowed:
-                from ukbb_cardiac_amd.device_pipeline import aortic_lstm_sequence_device
-                pred, aux = aortic_lstm_sequence_device(image, engine, True, FLAGS.weight_R, FLAGS.weight_r, FLAGS.time_step,
-                                                        return_aux='counts', qc=qc_full)
-                counts, qc_stats = aux['counts'], aux.get('qc')
-            elif on_device:
-                from ukbb_cardiac_amd.device_pipeline import aortic_unet_sequence_device
-                pred, aux = aortic_unet_sequence_device(image, engine, FLAGS.batch_slices, return_aux=True, qc=qc_full)
-                counts, qc_stats = aux['counts'], aux.get('qc')
-            else:
-                if qc_full and not FLAGS.z_score:
-                    image_qc = image.copy()                 # rescale_intensity clips `image` in place; the script reads the file
-                else:
-                    image_qc = image
-                if windowed:
-                    prob = pipeline.aortic_lstm_prob_sequence(image, cine_forward, FLAGS.z_score, FLAGS.weight_R, FLAGS.weight_r,
-                                                              time_step=FLAGS.time_step)
-                else:
-                    prob = pipeline.aortic_prob_sequence(image, forward, FLAGS.z_score, FLAGS.batch_slices)
-                pred = np.argmax(prob, axis=-1).astype(np.int32)      # host argmax, as :189
-                if qc_full:
-                    qc_stats = aorta_qc.stats_host(image_qc, pred)
-            if FLAGS.save_seg:
-                log('  Saving segmentation ...')
-                save(pred, '{0}/seg_{1}.nii.gz'.format(data_dir, seq), nim.affine, nim.header['pixdim'])
-            log('  Segmentation time = {:3f}s'.format(time.time() - t0))
+            nim = reader.load(idx, image_name) if reader is not None else nifti.load(image_name)
+            _sequence_subject(FLAGS, data, data_dir, nim, forward, cine_forward, engine, log, table, save)
             processed.append(data)
-            if csv_rows is not None:
-                if counts is None:
-                    counts = measures.counts_from_labels(pred, 3)
-                csv_rows[data] = _qc_row(counts, nim.header['pixdim'], _pp(central_pp, data, log), qc_stats)
-        else:
-            if windowed:                                               # reference: deploy_network_ao.py:202-205
-                log('{0} does not support frame-wise segmentation. Please use the -process_seq flag.'.format(FLAGS.model))
-                return processed
-            names = {fr: '{0}/{1}_{2}.nii.gz'.format(data_dir, seq, fr) for fr in ('ED', 'ES')}
-            if not all(os.path.exists(p) for p in names.values()):
-                log('  Directory {0} does not contain an image with file name {1} or {2}. Skip.'.format(
-                    data_dir, os.path.basename(names['ED']), os.path.basename(names['ES'])))
-                continue
-            for fr in ('ED', 'ES'):
-                log('  Reading {} ...'.format(names[fr]))
-                nim = nifti.load(names[fr])
-                t0 = time.time()
-                pred = pipeline.aortic_segment_frame(nim.get_data(), forward, FLAGS.z_score, FLAGS.batch_slices)
-                log('  Segmentation time = {:3f}s'.format(time.time() - t0))
-                if FLAGS.save_seg:
-                    log('  Saving segmentation ...')
-                    nifti.save(pred, '{0}/seg_{1}_{2}.nii.gz'.format(data_dir, seq, fr), nim.affine,
-                               nim.header['pixdim'])
-            processed.append(data)
-    if readers is not None:
-        try:
-            for w in writes:
-                w.result()
-        finally:
-            readers.shutdown(wait=True)
+        for w in writes:
+            w.result()
+    finally:
+        if reader is not None:
+            reader.pool.shutdown(wait=True)
             writers.shutdown(wait=True)
-    if csv_rows is not None:
-        rows = []
-        for data in data_list:                                  # eval_aortic_area.py:50-58: image and segmentation both exist
-            data_dir = os.path.join(FLAGS.data_dir, data)
-            image_name, seg_name = os.path.join(data_dir, 'ao.nii.gz'), os.path.join(data_dir, 'seg_ao.nii.gz')
-            if data in csv_rows:
-                row = csv_rows[data]
-            elif os.path.exists(image_name) and os.path.exists(seg_name):
-                log(data)
-                seg = nifti.load(seg_name).get_data()
-                stats = aorta_qc.stats_host(nifti.load(image_name).get_data(), seg) if qc_full else None
-                row = _qc_row(measures.counts_from_labels(seg, 3), nifti.load_header(image_name)['pixdim'], _pp(central_pp, data, log),
-                              stats)
-            else:
-                continue
-            if row is not None:                                 # None: dropped by the quality control, as eval_aortic_area.py:68-69
-                rows.append((data, row))
-        path = measures.shard_csv_name(FLAGS.output_csv, FLAGS.shard_index, FLAGS.num_shards)
-        measures.write_csv(path, measures.AO_COLUMNS, rows)
-        log('Aortic areas of {0} subjects written to {1}'.format(len(rows), path))
+    table.write(data_list, log)
     process_time = time.time() - start_time
     if processed:
         log('Including image I/O and device resource allocation, it took {:.3f}s for processing {:d} subjects '

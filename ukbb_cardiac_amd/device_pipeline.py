@@ -140,17 +140,22 @@ def pack_rescaled(vol_ptr, dtype, shape, strides, lo, hi, pad, batch_ptr, stream
                                                 *pad, batch_ptr, stream), 'ukbb_fcn_rescale_pack_t')
 
 
+def forward_chunks(engine, batch_ptr, pred_ptr, n, X2, Y2, batch_slices, stream):
+    """The frame-wise network over the packed batch [n][X2][Y2] at batch_ptr in chunks of batch_slices, enqueued on ``stream``: int32
+    label maps to pred_ptr."""
+    engine.reserve(min(batch_slices, n), X2, Y2)
+    for i in range(0, n, batch_slices):
+        m = min(batch_slices, n - i)
+        engine.run_device(batch_ptr + 4 * i * X2 * Y2, m, X2, Y2, pred_ptr=pred_ptr + 4 * i * X2 * Y2, stream=stream)
+
+
 def forward_and_unpack(engine, batch_ptr, pred_ptr, shape, pad, batch_slices, lab_ptr, counts_ptr, stream):
     """The tail every frame-wise sequence path shares, enqueued on ``stream``: the network over the packed batch [T*Z][X2][Y2] at
     batch_ptr in chunks of batch_slices (int32 label maps to pred_ptr), then ukbb_fcn_unpack_labels: the uint8 (X,Y,Z,T) label
     volume in NIfTI order to lab_ptr and the per-frame class counts (int64 [T, n_class]) to counts_ptr.  pad = (X2, Y2, x_pre, y_pre)."""
     X, Y, Z, T = shape
     X2, Y2, x_pre, y_pre = pad
-    n, px = T * Z, X2 * Y2
-    engine.reserve(min(batch_slices, n), X2, Y2)
-    for i in range(0, n, batch_slices):
-        m = min(batch_slices, n - i)
-        engine.run_device(batch_ptr + 4 * i * px, m, X2, Y2, pred_ptr=pred_ptr + 4 * i * px, stream=stream)
+    forward_chunks(engine, batch_ptr, pred_ptr, T * Z, X2, Y2, batch_slices, stream)
     _lib.check(_lib.lib.ukbb_fcn_unpack_labels(pred_ptr, X, Y, Z, T, X2, Y2, x_pre, y_pre, engine.arch.n_class, lab_ptr, counts_ptr, stream),
                'ukbb_fcn_unpack_labels')
 
@@ -522,21 +527,26 @@ def device_atrial_stats(lab_t, shape, n_class, affine, long_axis, stream=0):
     return label_statistics(lab_t, shape, n_class, [AtrialStats()], {'atrial': (affine, long_axis)}, stream)['atrial']
 
 
-def aortic_lstm_sequence_device(image, engine, z_score=True, weight_R=5, weight_r=0.1, time_step=1, return_aux=False, qc=False):
-    """pipeline.aortic_lstm_prob_sequence + the argmax of deploy_network_ao.py:189 with the array work on the GPU:
-    (X,Y,Z,T) float32 / uint8 / int16 / uint16 aortic cine -> int32 label volume (X,Y,Z,T).  Only the raw volume goes in and uint8 labels come
-    back (the host path moves the padded float32 cine in and 3 float32 probability maps per voxel out, and spends more
-    time in np.percentile / np.argmax than the network takes).  ``aux['prob']`` (X,Y,Z,T,C) on request; ``aux['counts']``
-    = pixels of each class per frame (what eval_aortic_area.py:60-78 turns into areas); with ``qc`` (needs ``return_aux``),
-    ``aux['qc']`` = device_qc_stats of the cine and the labels, the input of aorta_qc.aorta_qc_full."""
+def aortic_sequence_device(image, engine, batch_slices=128, window=None, return_aux=False, qc=False, prob=False):
+    """pipeline.aortic_prob_sequence (``window`` None: the frame-wise 'UNet' model in chunks of ``batch_slices``) or
+    pipeline.aortic_lstm_prob_sequence (``window`` = (weight_R, weight_r, time_step): the windowed models, one cine per slice
+    position) + the argmax of deploy_network_ao.py:189 with the array work on the GPU: (X,Y,Z,T) float32 / uint8 / int16 / uint16
+    aortic cine -> int32 label volume (X,Y,Z,T), the default --z_score pre-processing.  Only the raw volume goes in and uint8
+    labels come back (the host path moves the padded float32 cine in and 3 float32 probability maps per voxel out, and spends more
+    time in np.percentile / np.argmax than the network takes); the frame-wise engine's label map IS the lowest-index argmax of the
+    float32 probabilities it would return (``softmax_argmax``, csrc/kernels.h).  With ``return_aux``: the z-score statistics and
+    ``aux['counts']`` = pixels of each class per frame (what eval_aortic_area.py:60-78 turns into areas); with ``qc``,
+    ``aux['qc']`` = device_qc_stats of the cine and the labels, the input of aorta_qc.aorta_qc_full; with ``prob`` (windowed
+    forward only: 78 MB for 100 frames), ``aux['prob']`` (X,Y,Z,T,C)."""
     import torch
-    if qc and not return_aux:
-        raise ValueError('qc=True returns its statistics in aux: pass return_aux')
+    host = 'pipeline.aortic_prob_sequence' if window is None else 'pipeline.aortic_lstm_prob_sequence'
+    if (qc or prob) and not return_aux:
+        raise ValueError('qc=True and prob=True return their results in aux: pass return_aux')
+    if prob and window is None:
+        raise ValueError('prob=True: only the windowed forward leaves probabilities')
     if image.ndim != 4:
-        raise TypeError('expected a 4-D (X,Y,Z,T) cine; use pipeline.aortic_lstm_prob_sequence otherwise')
-    _check_dtype(image, 'pipeline.aortic_lstm_prob_sequence')
-    if not z_score:
-        raise ValueError('the device path implements the default --z_score pre-processing')
+        raise TypeError('expected a 4-D (X,Y,Z,T) cine; use %s otherwise' % host)
+    _check_dtype(image, host)
     X, Y, Z, T = image.shape
     dev = torch.device('cuda', engine.device)
     stream = torch.cuda.current_stream(dev).cuda_stream
@@ -546,16 +556,20 @@ def aortic_lstm_sequence_device(image, engine, z_score=True, weight_R=5, weight_
     n_class = engine.arch.n_class
     batch = torch.empty((T, Z, X2, Y2), dtype=torch.float32, device=dev)
     zscore_pack(vol.data_ptr(), image.dtype, (X, Y, Z, T), vol.stride(), mu, den, (X2, Y2, x_pre, y_pre), batch.data_ptr(), stream)
-    prob = torch.empty((T, Z, X2, Y2, n_class), dtype=torch.float32, device=dev)
+    if window is not None:
+        probs = torch.empty((T, Z, X2, Y2, n_class), dtype=torch.float32, device=dev)
     pred = torch.empty((T, Z, X2, Y2), dtype=torch.int32, device=dev)
-    for z in range(Z):                                       # slice positions are independent cines (usually Z = 1)
-        fr = batch[:, z] if Z == 1 else batch[:, z].contiguous()
-        pr = prob[:, z] if Z == 1 else torch.empty((T, X2, Y2, n_class), dtype=torch.float32, device=dev)
-        pd = pred[:, z] if Z == 1 else torch.empty((T, X2, Y2), dtype=torch.int32, device=dev)
-        engine.run_cine_device(fr.data_ptr(), T, X2, Y2, pr.data_ptr(), pd.data_ptr(), weight_R, weight_r, time_step, stream)
-        if Z > 1:
-            prob[:, z].copy_(pr)
-            pred[:, z].copy_(pd)
+    if window is None:
+        forward_chunks(engine, batch.data_ptr(), pred.data_ptr(), T * Z, X2, Y2, batch_slices, stream)
+    else:
+        for z in range(Z):                                   # slice positions are independent cines (usually Z = 1)
+            fr = batch[:, z] if Z == 1 else batch[:, z].contiguous()
+            pr = probs[:, z] if Z == 1 else torch.empty((T, X2, Y2, n_class), dtype=torch.float32, device=dev)
+            pd = pred[:, z] if Z == 1 else torch.empty((T, X2, Y2), dtype=torch.int32, device=dev)
+            engine.run_cine_device(fr.data_ptr(), T, X2, Y2, pr.data_ptr(), pd.data_ptr(), *window, stream)
+            if Z > 1:
+                probs[:, z].copy_(pr)
+                pred[:, z].copy_(pd)
     lab = torch.empty(X * Y * Z * T, dtype=torch.uint8, device=dev)
     counts = torch.empty((T, n_class), dtype=torch.int64, device=dev)
     _lib.check(_lib.lib.ukbb_fcn_unpack_labels(pred.data_ptr(), X, Y, Z, T, X2, Y2, x_pre, y_pre, n_class,
@@ -566,43 +580,6 @@ def aortic_lstm_sequence_device(image, engine, z_score=True, weight_R=5, weight_
     aux = {'mu': mu, 'den': den, 'n_roi': n_roi, 'val_l': val_l, 'counts': counts.cpu().numpy()}
     if qc:
         aux['qc'] = device_qc_stats(vol, lab, image.dtype, n_class, stream)
-    if return_aux != 'counts':                                 # 'counts': skip the 78 MB of probabilities
-        p = prob[:, :, x_pre:x_pre + X, y_pre:y_pre + Y].permute(2, 3, 1, 0, 4)
-        aux['prob'] = p.cpu().numpy()
+    if prob:
+        aux['prob'] = probs[:, :, x_pre:x_pre + X, y_pre:y_pre + Y].permute(2, 3, 1, 0, 4).cpu().numpy()
     return out, aux
-
-
-def aortic_unet_sequence_device(image, engine, batch_slices=128, return_aux=False, qc=False):
-    """pipeline.aortic_prob_sequence + the argmax of deploy_network_ao.py:189 for the frame-wise 'UNet' model with the array work
-    on the GPU: device z-score, pack, batched forward (the engine's label map IS the lowest-index argmax of the float32
-    probabilities it would return: ``softmax_argmax``, csrc/kernels.h), labels back as uint8.
-    (X,Y,Z,T) float32 / uint8 / int16 / uint16 -> int32 labels (X,Y,Z,T).  With ``qc`` (needs ``return_aux``), ``aux['qc']`` =
-    device_qc_stats of the cine and the labels, as aortic_lstm_sequence_device."""
-    import torch
-    if qc and not return_aux:
-        raise ValueError('qc=True returns its statistics in aux: pass return_aux')
-    if image.ndim != 4:
-        raise TypeError('expected a 4-D (X,Y,Z,T) cine; use pipeline.aortic_prob_sequence otherwise')
-    _check_dtype(image, 'pipeline.aortic_prob_sequence')
-    X, Y, Z, T = image.shape
-    dev = torch.device('cuda', engine.device)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    vol = _to_device(image, dev)
-    mu, den, n_roi, val_l = device_zscore_stats(vol, 10.0, stream, image.dtype)
-    X2, Y2, x_pre, _, y_pre, _ = pad_amounts_fixed(X, Y)
-    n = T * Z
-    batch = torch.empty((n, X2, Y2), dtype=torch.float32, device=dev)
-    zscore_pack(vol.data_ptr(), image.dtype, (X, Y, Z, T), vol.stride(), mu, den, (X2, Y2, x_pre, y_pre), batch.data_ptr(), stream)
-    pred = torch.empty((n, X2, Y2), dtype=torch.int32, device=dev)
-    n_class = engine.arch.n_class
-    lab = torch.empty(X * Y * Z * T, dtype=torch.uint8, device=dev)
-    counts = torch.empty((T, n_class), dtype=torch.int64, device=dev)
-    forward_and_unpack(engine, batch.data_ptr(), pred.data_ptr(), (X, Y, Z, T), (X2, Y2, x_pre, y_pre), batch_slices, lab.data_ptr(),
-                       counts.data_ptr(), stream)
-    out = lab.cpu().numpy().reshape((X, Y, Z, T), order='F').astype(np.int32)
-    if return_aux:
-        aux = {'mu': mu, 'den': den, 'n_roi': n_roi, 'val_l': val_l, 'counts': counts.cpu().numpy()}
-        if qc:
-            aux['qc'] = device_qc_stats(vol, lab, image.dtype, n_class, stream)
-        return out, aux
-    return out

@@ -6,10 +6,14 @@ label volume (``statistics``), gives the per-subject arguments of those statisti
 counts and statistics into rows (``record``) and at the end writes the tables, measuring the subjects an earlier run segmented
 from their files (``write``).  Statistics arrive as ``{key: value}`` -- 'qc': qc_gates.stats_host or device_pipeline.GateStats,
 'atrial': atrial.frame_stats_host or device_pipeline.AtrialStats -- from the device (SubjectPipeline, segment_sequence_device) or
-from the host twins (``from_labels``)."""
+from the host twins (``from_labels``).
+
+``AorticTable`` is the same for deploy_network_ao.py --output_csv (aortic areas and distensibility, measures.py): it checks the
+flags, applies the quality control of --aortic_qc / --aortic_qc_full to the class counts and aorta_qc statistics of a subject
+(``record``; ``from_labels``: the host twins) and writes the table.  The aortic run never skips a segmented subject: no back-fill."""
 import os
 
-from . import atrial, measures, nifti, qc_gates
+from . import aorta_qc, atrial, measures, nifti, qc_gates
 
 
 class LabelTables:
@@ -129,3 +133,56 @@ class LabelTables:
             else:
                 qc_gates.write_csv(path, self.seq, self.seg4, out)
                 log('Quality-control verdicts of {0} subjects written to {1}'.format(len(out), path))
+
+
+class AorticTable:
+    def __init__(self, FLAGS):
+        self.FLAGS = FLAGS
+        self.rows = {} if getattr(FLAGS, 'output_csv', '') else None       # subject -> row; none for one the quality control drops
+        self.qc = getattr(FLAGS, 'aortic_qc', True)
+        self.qc_full = bool(self.rows is not None and self.qc and getattr(FLAGS, 'aortic_qc_full', False))   # needs the aorta_qc statistics
+        if self.rows is not None:
+            if not FLAGS.process_seq:
+                raise ValueError('--output_csv writes the table of aortic/eval_aortic_area.py: it needs sequence mode')
+            self.central_pp = measures.read_central_pp(FLAGS.pressure_csv) if getattr(FLAGS, 'pressure_csv', '') else {}
+
+    def _pp(self, data, log):
+        """central_pp.loc[int(data)] of eval_aortic_area.py:80; None (no distensibility) when no spreadsheet was given."""
+        if not self.central_pp:
+            return None
+        try:
+            key = str(int(data))
+        except ValueError:
+            key = str(data)
+        if key not in self.central_pp:
+            # the reference's central_pp.loc[int(data)] raises KeyError here and the whole evaluation stops; this script keeps the areas
+            log('  Warning: subject {0} is not in the pressure spreadsheet: distensibility left empty.'.format(data))
+        return self.central_pp.get(key, float('nan'))
+
+    def from_labels(self, image, pred):
+        """(counts, qc_stats) of a cine and its (X,Y,Z,T) label volume for ``record`` from the host twins, each only if needed."""
+        if self.rows is None:
+            return None, None
+        return measures.counts_from_labels(pred, 3), aorta_qc.stats_host(image, pred) if self.qc_full else None
+
+    def record(self, data, pixdim, counts, qc_stats, log):
+        """The subject's table line from its per-frame class counts, or none when the quality control drops it (the script's own
+        message is logged); qc_stats: the aorta_qc statistics, needed with --aortic_qc_full."""
+        if self.rows is None:
+            return
+        pp = self._pp(data, log)
+        if self.qc:
+            ok, why = aorta_qc.aorta_qc_full(counts, qc_stats) if self.qc_full else measures.aorta_qc_from_counts(counts)
+            if not ok:
+                log(why)
+                return
+        self.rows[data] = measures.ao_row(counts, pixdim, pp)
+
+    def write(self, data_list, log):
+        """The table of this worker's subjects in their order; a dropped subject has no line, as eval_aortic_area.py:68-69."""
+        if self.rows is None:
+            return
+        rows = [(data, self.rows[data]) for data in data_list if data in self.rows]
+        path = measures.shard_csv_name(self.FLAGS.output_csv, self.FLAGS.shard_index, self.FLAGS.num_shards)
+        measures.write_csv(path, measures.AO_COLUMNS, rows)
+        log('Aortic areas of {0} subjects written to {1}'.format(len(rows), path))
