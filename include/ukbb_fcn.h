@@ -108,7 +108,8 @@ void ukbb_fcn_destroy(ukbb_fcn_handle *h);
  * at N = 100 x 256x256 (round 4-5 builds).  On a UKBB_KIND_UNET_LSTM handle (round 5) the U-Net runs the same bf16-storage
  * plan and the ConvLSTM runs as direct 3x3 convs on the bf16 matrix instruction with its features, the
  * hoisted x half of the gate pre-activations and the hidden maps as bf16 in HBM (accumulation and cell
- * state fp32): 8-9 ms instead of 19 per 100-frame cine, per-class Dice >= 0.98 against the fp32 cine.  On FCN handles only the operands are bf16 (fp32 activations in
+ * state fp32; gate kernels rounded to bf16, fp32 bias; the x pass rounds the x half of the gates to bf16 as it stores it and takes each
+ * frame's FIRST step from those rounded values too, the ones every later step adds; each hidden map is rounded once, as stored): 8-9 ms instead of 19 per 100-frame cine, per-class Dice >= 0.98 against the fp32 cine.  On FCN handles only the operands are bf16 (fp32 activations in
  * HBM; layers without such a tiling stay fp32).  Not bit-compatible with the reference; meant to be
  * judged by Dice against the fp32 result (common/image_utils.py:171-175): 0.993 / 0.992 measured.
  * Concurrency (round 6): a handle of any kind and precision may run beside kernels of other streams of the process (one handle per stream,

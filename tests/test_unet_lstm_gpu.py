@@ -270,7 +270,9 @@ def test_bf16_cine_dice_vs_fp32(model):
 def test_every_step_of_the_fused_convlstm_matches_numpy():
     """r05 white box: the x pass's per-frame first step (h1, both directions) and every later step's hidden map of the fused gate-conv / cell
     kernel (csrc/kernels_wino24.hip, ConvArgs::ls_mode) against oracle conv_lstm_cell on the engine's own feature maps, step by step
-    (tools/debug_lstm.py reads the buffers through ukbb_fcn_get_activation('lstm:h1' / 'lstm:hall')); two map sizes, the second with ragged regions."""
+    (tools/debug_lstm.py reads the buffers through ukbb_fcn_get_activation('lstm:h1' / 'lstm:hall')); two map sizes, 32 x 48 and 48 x 80.  Both plan
+    16-column regions for the nine frames of one window and both divide by 16, so no region is ragged and no workgroup takes a second item here: the
+    32-column form, ragged regions and multi-item workgroups are graded per launch in tests/test_lstm_launches_gpu.py."""
     import os
     import subprocess
     import sys

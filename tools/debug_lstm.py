@@ -1,6 +1,8 @@
 """Stage-by-stage check of the fused ConvLSTM kernels (kernels_wino24.hip, ConvArgs::ls_mode) against numpy on one small window:
-the x pass's per-frame first step h1 (both directions), then every step's hidden map.  GPU box; test infrastructure (uses oracle/).
-    python tools/debug_lstm.py [H W]"""
+the x pass's per-frame first step h1 (both directions), then every step's hidden map, errors carried from step to step (absolute 1e-4).
+One nine-frame window: the planner picks 16-column regions for it at 32 x 48, 48 x 80 and 256 x 256 alike, and a map whose width divides by 16 has no
+ragged region; tests/test_lstm_launches_gpu.py grades every launch form on its own stored input.  GPU box; test infrastructure (uses oracle/).
+    python tools/debug_lstm.py [H W [fp32|bf16]]"""
 import os
 import sys
 
