@@ -417,6 +417,37 @@ int64_t ukbb_fcn_gzip_labels_mode(const uint8_t *labels, uint64_t n_voxels, int 
 int64_t ukbb_fcn_gunzip(const uint8_t *src, uint64_t src_len, uint8_t *dst, uint64_t dst_cap, int verify_crc);
 uint32_t ukbb_fcn_gzip_crc(uint32_t crc, const uint8_t *data, uint64_t n);
 
+/* ---- image files in, on the device ------------------------------------------------------------------
+ * The same inflate for many files at once: the compressed bytes go up (fewer than the raw volume), ONE wave decodes one stream,
+ * hundreds decode side by side in one launch (csrc/kernels_inflate.hip; the decoder is csrc/inflate_core.h, one text for the kernel
+ * and for ukbb_fcn_inflate_core_host).  No reference counterpart (it leaves gzip to nibabel).
+ *
+ * ukbb_fcn_inflate_device: stream i is the RAW deflate stream (after the gzip member header, before the 8-byte trailer)
+ * d_src[src_off, src_off + src_len); its output goes to d_dst[dst_off, dst_off + dst_cap) and nothing outside that region is written.
+ * d_written[i] = bytes written, or -1 out of input / -2 invalid stream / -3 does not fit dst_cap; an error ends that stream only (its
+ * region then holds a prefix of unspecified length).  d_crc (optional) [i] = CRC-32 of the d_written[i] bytes (zlib's crc32; 0 for a
+ * refused stream).  Output regions must not overlap; any alignment is accepted, a 16-byte aligned dst_off stores fastest.
+ * `streams` is HOST memory and is copied before the call returns (one upload); everything else is asynchronous on `stream`.
+ * The library keeps two copies of the table per device and takes them in turn: a call returns at once while the PREVIOUS call's
+ * launches still run, and waits on the host for the call before that one if it has not finished.
+ * Limits: 1 <= n_streams <= UKBB_INFLATE_MAX_STREAMS, src_len and dst_cap <= UKBB_INFLATE_MAX_BYTES each.  Strictness is that of
+ * ukbb_fcn_gunzip's decoder: over-subscribed or incomplete codes (but the single length-1 distance code), symbols 286 / 287 and
+ * distance symbols 30 / 31, a repeat with nothing to repeat, HLIT > 286, block type 3 and LEN != ~NLEN are refused, and so is a
+ * stream whose last block ends before byte src_len - 1 (in a gzip member the trailer follows the stream at once).
+ * LDS: 56 368 bytes static per workgroup of one wave (tables 15.0 KB, 36 KB ring of the last output, 4 KB input window): 2 workgroups
+ * per CU, 512 streams in flight on 256 CUs; more streams than that are taken in turn by the same grid.  The CRC kernel takes
+ * UKBB_INFLATE_CRC_CHUNK bytes per workgroup. */
+typedef struct { uint64_t src_off, src_len, dst_off, dst_cap; } ukbb_fcn_gz_stream;
+#define UKBB_INFLATE_MAX_STREAMS 65535
+#define UKBB_INFLATE_MAX_BYTES (1ull << 40)
+#define UKBB_INFLATE_CRC_CHUNK 65536
+int ukbb_fcn_inflate_device(const uint8_t *d_src, uint8_t *d_dst, const ukbb_fcn_gz_stream *streams, int n_streams, int64_t *d_written,
+                            uint32_t *d_crc, void *stream);
+/* The same decoder core compiled for the host (tests, sanitizer runs): returns the bytes written or -1 / -2 / -3 as above. */
+int64_t ukbb_fcn_inflate_core_host(const uint8_t *src, uint64_t src_len, uint8_t *dst, uint64_t dst_cap);
+/* CRC-32 of A || B from crc_a = crc32(A), crc_b = crc32(B) and len_b = |B| (zlib's crc32_combine).  Host. */
+uint32_t ukbb_fcn_gzip_crc_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+
 /* ---- measurement / introspection (bench.py, tests) ---------------------- */
 
 /* Kernel launches of one forward, in launch order. */

@@ -33,6 +33,7 @@ EXPORTS = [
     'ukbb_fcn_set_scratch_budget', 'ukbb_fcn_scratch_bytes', 'ukbb_fcn_cine_scratch_bytes',
     'ukbb_fcn_cine_min_scratch_bytes', 'ukbb_fcn_cine_chunk_windows',
     'ukbb_fcn_plane_components', 'ukbb_fcn_atrial_area_length',
+    'ukbb_fcn_inflate_device', 'ukbb_fcn_inflate_core_host', 'ukbb_fcn_gzip_crc_combine',
 ]
 
 
@@ -40,6 +41,10 @@ class ArchStruct(C.Structure):
     _fields_ = [('kind', C.c_int32), ('n_class', C.c_int32), ('n_level', C.c_int32),
                 ('n_filter', C.c_int32 * MAX_LEVEL), ('n_block', C.c_int32 * MAX_LEVEL),
                 ('same_dim', C.c_int32), ('fc', C.c_int32)]
+
+
+class GzStream(C.Structure):
+    _fields_ = [('src_off', C.c_uint64), ('src_len', C.c_uint64), ('dst_off', C.c_uint64), ('dst_cap', C.c_uint64)]
 
 
 def arch_struct(arch) -> ArchStruct:
@@ -140,6 +145,11 @@ def _load():
     lib.ukbb_fcn_gunzip.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.c_int]
     lib.ukbb_fcn_gzip_crc.restype = C.c_uint32
     lib.ukbb_fcn_gzip_crc.argtypes = [C.c_uint32, vp, C.c_uint64]
+    lib.ukbb_fcn_inflate_device.argtypes = [vp, vp, C.POINTER(GzStream), C.c_int, vp, vp, vp]
+    lib.ukbb_fcn_inflate_core_host.restype = C.c_int64
+    lib.ukbb_fcn_inflate_core_host.argtypes = [vp, C.c_uint64, vp, C.c_uint64]
+    lib.ukbb_fcn_gzip_crc_combine.restype = C.c_uint32
+    lib.ukbb_fcn_gzip_crc_combine.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]
     lib.ukbb_fcn_kernel_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int, C.c_int]
     lib.ukbb_fcn_get_activation.restype = C.c_int64
     lib.ukbb_fcn_get_activation.argtypes = [vp, C.c_char_p, f32p, C.c_int64]

@@ -16,7 +16,7 @@ and writes the same files (``deploy_network.py:136-151,207-216``):
 
 Extra flags (not in the reference): ``--device``, ``--batch_slices``,
 ``--num_shards`` / ``--shard_index`` (multi-GPU batch split), ``--output_csv``, ``--qc_csv``,
-``--atrial_csv``.
+``--atrial_csv``, ``--device_inflate`` (gzip inputs inflated on the GPU).
 """
 import os
 import sys
@@ -53,6 +53,10 @@ def define_flags():
                       'was written (1 ulp from numpy 2; host pre-processing only; INTEGRATION.md section 5).')
     fs.DEFINE_integer('io_threads', int(os.environ.get('UKBB_IO_THREADS', 8)), 'Reader threads (gzip NIfTI -> pinned staging) and writer threads (float64 label volume, gzip) '
                       'around the GPU in sequence mode; 0 = strictly sequential subjects as in the reference.')
+    fs.DEFINE_integer('device_inflate', 0, 'Sequence mode with --device_preproc: inflate the gzip NIfTI inputs on the GPU, up to this many subjects per '
+                      'launch (one wave per file; the readers only read).  0 = off: the reader threads inflate.  A file the device path declines '
+                      '(scaled / big-endian / float64 voxels, several gzip members, anything its strict decoder or the CRC-32 check refuses) '
+                      'takes the host reader as before.  Same output files.')
     fs.DEFINE_enum('precision', 'fp32', ['fp32', 'f32x3'], 'Arithmetic of the matrix products: fp32 MFMA (default) or fp32 results from three '
                    'bf16 pieces per operand (UKBB_PREC_F32X3, include/ukbb_fcn.h; same labels, faster head).')
     fs.DEFINE_enum('label_gzip', 'small', list(nifti.LABEL_GZIP_MODES), 'Deflate of the label volumes: small = run-length tokens + dynamic Huffman '
@@ -320,7 +324,13 @@ def run(FLAGS, forward, log=print, engine=None):
     processed, table_time = [], []
     tables = LabelTables(FLAGS, engine)                 # --output_csv, --qc_csv, --atrial_csv: flag checks first
     shard_subjects = list(queue.static)                 # whose earlier-run results this worker measures for the tables
-    if (FLAGS.process_seq and engine is not None and getattr(FLAGS, 'device_preproc', False) and getattr(FLAGS, 'io_threads', 0) > 0
+    if int(getattr(FLAGS, 'device_inflate', 0) or 0) > 0:
+        if not (FLAGS.process_seq and engine is not None and getattr(FLAGS, 'device_preproc', False)) or getattr(FLAGS, 'numpy1_casting', False):
+            raise ValueError('--device_inflate needs sequence mode (--process_seq) with --device_preproc and without --numpy1_casting')
+        from ukbb_cardiac_amd import device_inflate
+        processed, table_time, _ = device_inflate.run_rounds(FLAGS, engine, data_list, log, tables, queue)
+        data_list = []
+    elif (FLAGS.process_seq and engine is not None and getattr(FLAGS, 'device_preproc', False) and getattr(FLAGS, 'io_threads', 0) > 0
             and not getattr(FLAGS, 'numpy1_casting', False)):
         processed, table_time, _ = run_pipelined(FLAGS, engine, data_list, log, tables, queue)
         data_list = []

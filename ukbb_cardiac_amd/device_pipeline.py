@@ -176,16 +176,32 @@ def segment_sequence_device(image, engine, batch_slices=128, thres=(1, 99), retu
     if image.ndim != 4:
         raise ValueError('expected a 4-D (X,Y,Z,T) sequence, got shape %s' % (image.shape,))
     _check_dtype(image, 'pipeline.segment_sequence')
-    X, Y, Z, T = image.shape
+    dev = torch.device('cuda', engine.device)
+    vol = _to_device(image, dev)                                 # dense copy, strides preserved
+    return segment_sequence_tensor(vol, image.dtype, image.shape, engine, batch_slices, thres, return_aux, stats, stat_args)
+
+
+def segment_sequence_tensor(vol_t, dtype, shape, engine, batch_slices=128, thres=(1, 99), return_aux=False, stats=(), stat_args=None):
+    """segment_sequence_device for a volume that is on the device already (device_inflate.DeviceInflater: the voxels never were
+    on the host): ``vol_t`` a 4-D torch tensor of ``shape`` (X,Y,Z,T) on the engine's device, dense (a permutation of contiguous memory, in any stride order), holding voxels of the
+    numpy ``dtype`` (a uint16 volume is an int16 tensor).  Same results, same exceptions."""
+    import torch
+    if stats and not return_aux:
+        raise ValueError('stats are returned in aux: pass return_aux')
+    if len(shape) != 4 or tuple(vol_t.shape) != tuple(shape):
+        raise ValueError('expected a 4-D (X,Y,Z,T) sequence, got shape %s' % (tuple(shape),))
+    if not device_dtype_ok(dtype):
+        raise TypeError('device pre-processing is exact for float32, uint8, int16 and uint16 volumes only (got %s); use %s'
+                        % (np.dtype(dtype), 'pipeline.segment_sequence'))
+    X, Y, Z, T = (int(v) for v in shape)
     dev = torch.device('cuda', engine.device)
     stream = torch.cuda.current_stream(dev).cuda_stream
-    vol = _to_device(image, dev)                                 # dense copy, strides preserved
-    lo, hi = device_percentiles(vol, thres, stream, image.dtype)
+    lo, hi = device_percentiles(vol_t, thres, stream, dtype)
     X2, Y2, x_pre, _, y_pre, _ = pad_amounts(X, Y)
     n = T * Z
     batch = torch.empty((n, X2, Y2), dtype=torch.float32, device=dev)
-    sx, sy, sz, st = vol.stride()
-    pack_rescaled(vol.data_ptr(), image.dtype, (X, Y, Z, T), (sx, sy, sz, st), lo, hi, (X2, Y2, x_pre, y_pre), batch.data_ptr(), stream)
+    sx, sy, sz, st = vol_t.stride()
+    pack_rescaled(vol_t.data_ptr(), dtype, (X, Y, Z, T), (sx, sy, sz, st), lo, hi, (X2, Y2, x_pre, y_pre), batch.data_ptr(), stream)
     pred = torch.empty((n, X2, Y2), dtype=torch.int32, device=dev)
     n_class = engine.arch.n_class
     lab = torch.empty(X * Y * Z * T, dtype=torch.uint8, device=dev)
@@ -193,7 +209,7 @@ def segment_sequence_device(image, engine, batch_slices=128, thres=(1, 99), retu
     forward_and_unpack(engine, batch.data_ptr(), pred.data_ptr(), (X, Y, Z, T), (X2, Y2, x_pre, y_pre), batch_slices, lab.data_ptr(),
                        counts.data_ptr(), stream)
     lab_h = lab.cpu().numpy().reshape((X, Y, Z, T), order='F')
-    out = np.zeros(image.shape)                                 # float64, as deploy_network.py:92
+    out = np.zeros((X, Y, Z, T))                                # float64, as deploy_network.py:92
     out[...] = lab_h
     if return_aux:
         aux = {'clip': (lo, hi), 'counts': counts.cpu().numpy()}
