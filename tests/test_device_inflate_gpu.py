@@ -1,7 +1,8 @@
 """ukbb_fcn_inflate_device on the MI355X: the corpus of tests/test_device_inflate.py (what the host-compiled core has passed under
 the sanitizers) in batches of very different sizes, byte for byte against zlib with guard bytes between the output regions; the
 malformed list mixed into a batch of good streams; the CRC kernel around its chunk size; segment_sequence_tensor against
-segment_sequence_device; and deploy_network --device_inflate against the run without the flag, file by file."""
+segment_sequence_device; deploy_network --device_inflate against the run without the flag, file by file; and the host path, the
+sequential device path, the pipelined loop and the inflate rounds against each other: files, tables and log lines per subject."""
 import gzip
 import os
 import re
@@ -269,6 +270,73 @@ def test_deploy_with_device_inflate_writes_the_same_files(cohort, monkeypatch):
         for key in runs['off'][0]:
             assert runs[name][0][key] == runs['off'][0][key], (name, key)
         assert runs[name][1] == runs['off'][1] and runs[name][1].count('\n') >= 5
+
+
+FOUR_MODES = {'host': ['--io_threads', '0', '--nodevice_preproc'], 'sequential': ['--io_threads', '0'], 'pipelined': ['--io_threads', '2'],
+              'rounds': ['--io_threads', '2', '--device_inflate', '2']}
+
+
+def test_four_loops_write_the_same_files_tables_and_log_blocks(cohort):
+    """The cohort plus a directory without a cine and a subject an earlier run segmented, through deploy_network.run on the host
+    path, the sequential device path, the pipelined loop and the inflate rounds: 25 files and both tables byte for byte, and per
+    subject the same block of log lines (time figures masked) -- the declined subject's with its Reading line in every mode."""
+    from ukbb_cardiac_amd import deploy_network, nifti
+    root, model, src = cohort
+    full = root / 'src_four'
+    shutil.copytree(str(src), str(full))
+    (full / 'n_nocine').mkdir()
+    (full / 'e_earlier').mkdir()
+    shutil.copyfile(str(src / 's0' / 'sa.nii.gz'), str(full / 'e_earlier' / 'sa.nii.gz'))
+    earlier = np.zeros((100, 90, 3, 4))
+    earlier[30:60, 30:60] = 2
+    earlier[38:52, 38:52] = 1
+    earlier[20:28, 40:60] = 3
+    nifti.save(earlier, str(full / 'e_earlier' / 'seg_sa.nii.gz'), np.diag([1.8, 1.8, 10.0, 1.0]), pixdim=[1, 1.8, 1.8, 10, 0.03, 0, 0, 0])
+    names = sorted(os.listdir(str(full)))
+    eng = _engine()
+    forward = lambda b: {'pred': eng.run(b, want_prob=False)['pred']}
+    seen = {}
+    try:
+        for mode, extra in FOUR_MODES.items():
+            work = root / ('four_' + mode)
+            shutil.copytree(str(full), str(work))
+            lines = []
+
+            def log(*a):
+                line = ' '.join(str(x) for x in a).replace(str(work), 'DIR')
+                lines.append(re.sub(r'\d+\.\d+s', '#s', line) if ('time =' in line or 'it took' in line) else line)
+            FLAGS, _ = deploy_network.define_flags().parse(['--seq_name', 'sa', '--data_dir', str(work), '--model_path', model, '--output_csv',
+                                                            str(work) + '.csv', '--qc_csv', str(work) + '.qc.csv'] + extra)
+            processed = deploy_network.run(FLAGS, forward, log=log, engine=eng)
+            assert sorted(processed) == ['s0', 's1', 's2', 's3', 's4'], mode
+            tail = next(i for i, l in enumerate(lines) if l.startswith('Clinical measures of'))
+            blocks = {}
+            for line in lines[:tail]:
+                if line in names:
+                    assert line not in blocks, (mode, line)
+                    blocks[line] = current = []
+                current.append(line)
+            files = {(s, f): open(str(work / s / f), 'rb').read() for s in names if s != 'n_nocine' for f in FILES if s != 'e_earlier' or f == FILES[0]}
+            # a failing gate's message names the subject's file
+            seen[mode] = (files, open(str(work) + '.csv').read(), open(str(work) + '.qc.csv').read().replace(str(work), 'DIR'), blocks, lines[tail:])
+    finally:
+        eng.close()
+    files, csv, qc, blocks, tail = seen['host']
+    assert len(files) == 25 + 1 and csv.count('\n') == 7 and qc.count('\n') == 7
+    assert set(blocks) == set(names) and blocks['e_earlier'] == ['e_earlier'] and len(blocks['n_nocine']) == 2
+    assert blocks['s0'][:4] == ['s0', '  Reading DIR/s0/sa.nii.gz ...', '  Segmenting full sequence ...', '  Segmentation time = #s']
+    assert blocks['s0'][4].startswith('  ED frame = 0, ES frame = ') and blocks['s0'][-1] == '  Saving segmentation ...'
+    for mode in FOUR_MODES:
+        m_files, m_csv, m_qc, m_blocks, m_tail = seen[mode]
+        assert m_files.keys() == files.keys()
+        for key in files:
+            assert m_files[key] == files[key], (mode, key)
+        assert m_csv == csv and m_qc == qc, mode
+        assert m_blocks.keys() == blocks.keys(), mode
+        for name in blocks:
+            assert m_blocks[name] == blocks[name], (mode, name, m_blocks[name], blocks[name])
+        assert '  Reading DIR/s4/sa.nii.gz ...' in m_blocks['s4'], mode
+        assert m_tail == tail, mode
 
 
 def test_deploy_flag_needs_device_preproc(cohort):

@@ -3,8 +3,8 @@
 1. kernel alone: K = 1, 16, 64, 256 copies of one sa.nii.gz (int16 and float32, the subjects of tools/bench_integer_cohort.py) in one
    ukbb_fcn_inflate_device launch, without and with the CRC launch: HIP events, median of --reps launches after a warm-up;
 2. end to end: a cohort of --cohort subjects through deploy_network.run with --device_inflate 64 and 256 against --device_inflate 0
-   (run_pipelined, the host readers) on the same files, alternating, --runs times each;
-3. where a round's time goes (device_inflate.run_rounds.last_phases of the last run of each K).
+   (SequenceRun.pipelined, the host readers) on the same files, alternating, --runs times each;
+3. where a round's time goes (sequence_run.SequenceRun.last_phases of the last run of each K).
 
 GPU box only.   python tools/bench_device_inflate.py [--frames 50] [--cohort 256] [--io_threads 8] [--reps 5] [--runs 3] [--skip kernel|e2e] [--once]"""
 import argparse
@@ -75,7 +75,7 @@ if __name__ == '__main__':
     ap.add_argument('--skip', default='')
     ap.add_argument('--once', action='store_true', help='kernel alone: one launch of K = 1 and of K = 256 per dtype, no warm-up (a full-size launch takes 10-15 s)')
     args = ap.parse_args()
-    from ukbb_cardiac_amd import deploy_network, device_inflate, nifti
+    from ukbb_cardiac_amd import deploy_network, nifti, sequence_run
     from ukbb_cardiac_amd.arch import MODELS
     from ukbb_cardiac_amd.engine import Engine
     from ukbb_cardiac_amd.weights import save_blob, synthetic_params
@@ -128,7 +128,7 @@ if __name__ == '__main__':
                     assert len(done) == args.cohort, len(done)
                     rates.setdefault(K, []).append(args.cohort / dt)
                     if K:
-                        phases[K] = dict(device_inflate.run_rounds.last_phases, total=dt)
+                        phases[K] = dict(sequence_run.SequenceRun.last_phases, total=dt)
                     print('   run %d  --device_inflate %3d  %7.2f s = %6.2f subjects/s' % (run, K, dt, args.cohort / dt), flush=True)
                     shutil.rmtree(work)
             base = float(np.median(rates[0]))

@@ -30,6 +30,9 @@ if __package__ in (None, ''):
 from ukbb_cardiac_amd import nifti, pipeline                      # noqa: E402
 from ukbb_cardiac_amd.flags import FlagError, FlagSet              # noqa: E402
 from ukbb_cardiac_amd.label_tables import LabelTables              # noqa: E402
+# pipelined_on_device and sequence_on_device are not used here: they keep the names under which callers and tests ask this script
+# how it routes a subject
+from ukbb_cardiac_amd.sequence_run import SequenceRun, device_path, pipelined_on_device, seg_prefix, sequence_on_device   # noqa: E402,F401
 from ukbb_cardiac_amd.shard import ClaimQueue, apply_cpu_set_from_env, default_device, shard_from_env   # noqa: E402
 
 
@@ -83,238 +86,20 @@ def define_flags():
     return fs
 
 
-def seg_prefix(FLAGS):
-    return 'seg4' if (FLAGS.seq_name == 'la_4ch' and FLAGS.seg4) else 'seg'
+_sequence_subject = SequenceRun.on_this_thread           # one subject start to finish on this thread, under the name it has here
 
 
-def save_sequence_outputs(data_dir, pre, seq, affine, pixdim, pred, frames):
-    """The five files of deploy_network.py:136-151.  pred: (X,Y,Z,T) labels, stored as float64 (:92); frames: {'ED'|'ES':
-    (image frame, label frame)}."""
-    for fr, (img_fr, seg_fr) in frames.items():
-        nifti.save(img_fr, '{0}/{1}_{2}.nii.gz'.format(data_dir, seq, fr), affine)
-        nifti.save(seg_fr, '{0}/{1}_{2}_{3}.nii.gz'.format(data_dir, pre, seq, fr), affine)
-    # seg_{seq}.nii.gz doubles as the 'already segmented, skip' marker (:66-67), so it is written LAST and -- like every
-    # file nifti.save writes -- appears under its name only when complete (tmp file + os.replace): a worker killed
-    # anywhere in here leaves a subject that the rerun segments again, never a half-written one that it skips.
-    nifti.save(pred, '{0}/{1}_{2}.nii.gz'.format(data_dir, pre, seq), affine, pixdim, as_dtype=np.float64)
+class _SequenceRun(SequenceRun):
+    """The loops of this script reach the one-subject path through ``_sequence_subject``: whoever replaces that name -- a test that
+    proves that no subject leaves the pipeline -- sees every subject that takes it, from whichever loop."""
 
-
-def pipelined_on_device(image):
-    """run_pipelined: does this subject go through the subject pipeline (else: drain, then the sequential path)?  4-D
-    float32, uint8, int16 or uint16 volumes; float64 (every file with a non-trivial scl_slope) and the other integer types
-    stay on the host."""
-    from ukbb_cardiac_amd import device_pipeline
-    return image.ndim == 4 and device_pipeline.device_dtype_ok(image.dtype)
-
-
-def sequence_on_device(FLAGS, engine, image):
-    """_sequence_subject: device pre-processing (device_pipeline.segment_sequence_device) for this subject?  Needs an engine,
-    --device_preproc, not --numpy1_casting (its float32 arithmetic is host only), and a dtype the device reproduces."""
-    if engine is None or not getattr(FLAGS, 'device_preproc', False) or getattr(FLAGS, 'numpy1_casting', False):
-        return False
-    from ukbb_cardiac_amd import device_pipeline
-    return device_pipeline.device_dtype_ok(image.dtype)
-
-
-def run_pipelined(FLAGS, engine, data_list, log=print, tables=None, queue=None):
-    """Sequence mode with subjects overlapped: reader threads decompress the next files into pinned staging buffers,
-    the GPU thread (this one) keeps up to two subjects in flight on three streams (subject_pipeline.SubjectPipeline),
-    writer threads expand the uint8 labels to the reference's float64 volume, gzip and save.  Same files, byte for byte,
-    as the sequential loop; log lines of a subject are emitted together when its result arrives.  ``tables``: the run's
-    LabelTables (default: made from FLAGS)."""
-    import threading
-    from concurrent.futures import ThreadPoolExecutor
-    from ukbb_cardiac_amd import device_pipeline
-    from ukbb_cardiac_amd.subject_pipeline import SubjectPipeline
-    start_time = time.time()
-    seq, pre = FLAGS.seq_name, seg_prefix(FLAGS)
-    tables = tables or LabelTables(FLAGS, engine)
-    def candidates(names, second=False):
-        """(data, data_dir, image_name) of the subjects still to segment, in walk order, each claimed right before its read is
-        scheduled (with --work_stealing a worker so holds at most window + depth claims; the rest of the list stays open)."""
-        for data in names:
-            data_dir = os.path.join(FLAGS.data_dir, data)
-            if not os.path.isdir(data_dir) or os.path.exists('{0}/{1}_{2}.nii.gz'.format(data_dir, pre, seq)):
-                if not second:
-                    log(data)
-                continue
-            image_name = '{0}/{1}.nii.gz'.format(data_dir, seq)
-            if not os.path.exists(image_name):
-                if not second:
-                    log(data)
-                    log('  Directory {0} does not contain an image with file name {1}. Skip.'.format(data_dir, os.path.basename(image_name)))
-                continue
-            if queue is not None and not queue.take(data):
-                continue                                    # another worker is on it
-            yield (data, data_dir, image_name)
-
-    def todo_items():
-        yield from candidates(data_list)
-        if queue is not None:                               # subjects a live worker held when we passed: finished by now, or orphaned
-            yield from candidates(queue.second_chance(), second=True)
-
-    def release(data):
-        if queue is not None:
-            queue.done(data)
-    nthr = max(1, int(FLAGS.io_threads))
-    window = nthr + 1                                   # reads allowed to run ahead of the GPU thread
-    depth = 3
-    state = {'pipe': None}
-    mk = threading.Lock()
-
-    def alloc(shape, dt):
-        if len(shape) == 4 and device_pipeline.device_dtype_ok(dt):
-            with mk:
-                if state['pipe'] is None:                  # sized by the first volume; bigger ones fall back below
-                    state['pipe'] = SubjectPipeline(engine, shape, FLAGS.batch_slices, depth=depth, extra_inputs=window, stats=tables.statistics())
-            try:
-                return state['pipe'].stage(shape, dt).array, SubjectPipeline.HEADROOM
-            except ValueError:
-                pass
-        return np.empty(shape, dt, order='F'), 0
-
-    def read(item):
-        t0 = time.time()
-        handed = []
-
-        def alloc_tracked(shape, dt):
-            a, headroom = alloc(shape, dt)
-            handed.append(a)
-            return a, headroom
-        try:
-            nim = nifti.load(item[2], alloc=alloc_tracked)
-        except BaseException:
-            pipe = state['pipe']                            # a truncated / corrupt file: the pinned buffer goes back to the pool
-            for a in handed:
-                if pipe is not None:
-                    pipe.release(a)
-            raise
-        return nim, time.time() - t0
-
-    processed, table_time, writes = [], [], []
-    readers, writers = ThreadPoolExecutor(nthr), ThreadPoolExecutor(nthr)
-    futures = {}
-    inflight = []                                       # (item, nim, t_submit)
-
-    def finish(item, nim, t0):
-        data, data_dir, image_name = item
-        res = state['pipe'].collect()
-        seg_time = time.time() - t0
-        k_ed, k_es = device_pipeline.pick_ed_es_from_counts(res.counts, seq, FLAGS.seg4)
-        log(data)
-        log('  Reading {} ...'.format(image_name))
-        log('  Segmenting full sequence ...')
-        log('  Segmentation time = {:3f}s'.format(seg_time))
-        log('  ED frame = {:d}, ES frame = {:d}'.format(k_ed, k_es))
-        table_time.append(seg_time)
-        processed.append(data)
-        tables.record(data, data_dir, nim, res.counts, res.stats, log)
-        if FLAGS.save_seg:
-            log('  Saving segmentation ...')
-            # the saved frames are the CLIPPED intensities (alias quirk, SURVEY.md App. C.1)
-            frames = {fr: (device_pipeline.clip_like_reference(res.image[:, :, :, k], res.clip), res.labels[:, :, :, k].astype(np.float64))
-                      for fr, k in (('ED', k_ed), ('ES', k_es))}
-            labels, affine, pixdim = res.labels, nim.affine, nim.header['pixdim']
-
-            def write_then_release():
-                try:
-                    save_sequence_outputs(data_dir, pre, seq, affine, pixdim, labels, frames)
-                finally:
-                    release(data)                           # the claim outlives the subject's last file (seg_{seq}.nii.gz, written last)
-            writes.append(writers.submit(write_then_release))
-        else:
-            release(data)
-        res.done()
-
-    try:
-        from collections import deque
-        todo = todo_items()
-        ahead = deque()                                     # (item, future of its read), in walk order
-
-        def top_up():
-            while len(ahead) < window:
-                item = next(todo, None)
-                if item is None:
-                    return
-                ahead.append((item, readers.submit(read, item)))
-        top_up()
-        while ahead:
-            item, fut = ahead.popleft()
-            nim, _ = fut.result()
-            image = nim.get_data()
-            pipe = state['pipe']
-            if not pipelined_on_device(image) or pipe is None or image.size > pipe._in_cap:
-                while inflight:                             # odd subject: drain, then take the sequential path
-                    finish(*inflight.pop(0))
-                log(item[0])
-                try:
-                    _sequence_subject(FLAGS, item, nim, None, engine, log, processed, table_time, tables)
-                finally:
-                    release(item[0])
-                top_up()
-                continue
-            if len(inflight) >= depth - 1:
-                finish(*inflight.pop(0))
-            pipe.submit(image, tables.subject_args(item[1], nim, log))
-            inflight.append((item, nim, time.time()))
-            top_up()
-        while inflight:
-            finish(*inflight.pop(0))
-        for w in writes:
-            w.result()
-    finally:
-        readers.shutdown(wait=True)
-        writers.shutdown(wait=True)
-        if queue is not None:
-            queue.release_all()                             # an exception above must not leave live-looking claims behind
-    return processed, table_time, start_time
-
-
-def _sequence_subject(FLAGS, item, nim, forward, engine, log, processed, table_time, tables):
-    """One subject of sequence mode, start to finish on this thread (deploy_network.py:80-151)."""
-    data, data_dir, image_name = item
-    seq, pre = FLAGS.seq_name, seg_prefix(FLAGS)
-    image = nim.get_data()
-    if image.ndim != 4:
-        log('  {0}: expected a 4-D sequence, found shape {1}. Skip.'.format(image_name, image.shape))
-        return
-    log('  Segmenting full sequence ...')
-    t0 = time.time()
-    np1 = bool(getattr(FLAGS, 'numpy1_casting', False))
-    on_device = sequence_on_device(FLAGS, engine, image)
-    args = tables.subject_args(data_dir, nim, log)
-    if on_device:
-        from ukbb_cardiac_amd import device_pipeline
-        pred, aux = device_pipeline.segment_sequence_device(image, engine, FLAGS.batch_slices, return_aux=True, stats=tables.statistics(),
-                                                            stat_args=args)
-    else:
-        if forward is None:
-            forward = lambda b: {'pred': engine.run(b, want_prob=False)['pred']}
-        pred = pipeline.segment_sequence(image, forward, FLAGS.batch_slices, np1)   # clips `image` in place
-    seg_time = time.time() - t0
-    log('  Segmentation time = {:3f}s'.format(seg_time))
-    table_time.append(seg_time)
-    processed.append(data)
-    if on_device:
-        k_ed, k_es = device_pipeline.pick_ed_es_from_counts(aux['counts'], seq, FLAGS.seg4)
-    else:
-        k_ed, k_es = pipeline.pick_ed_es(pred, seq, FLAGS.seg4)
-    log('  ED frame = {:d}, ES frame = {:d}'.format(k_ed, k_es))
-    counts, stats = (aux['counts'], aux['stats']) if on_device else tables.from_labels(pred, args, tables.n_class)
-    tables.record(data, data_dir, nim, counts, stats, log)
-    if FLAGS.save_seg:
-        log('  Saving segmentation ...')
-        frames = {}
-        for fr, k in (('ED', k_ed), ('ES', k_es)):
-            # the saved frames are the CLIPPED intensities (alias quirk, SURVEY.md App. C.1)
-            frame = device_pipeline.clip_like_reference(image[:, :, :, k], aux['clip']) if on_device else image[:, :, :, k]
-            frames[fr] = (frame, pred[:, :, :, k])
-        save_sequence_outputs(data_dir, pre, seq, nim.affine, nim.header['pixdim'], pred, frames)
+    def on_this_thread(self, *args, **kwargs):
+        return _sequence_subject(self, *args, **kwargs)
 
 
 def run(FLAGS, forward, log=print, engine=None):
-    """The subject loop of deploy_network.py:52-225 with ``forward`` standing for sess.run.
-    With ``engine`` (and --device_preproc) float32 sequences take the device pipeline."""
+    """The subject loop of deploy_network.py:52-225 with ``forward`` standing for sess.run.  Sequence mode is a SequenceRun
+    (sequence_run.py): with ``engine`` and --device_preproc, float32 and integer sequences take one of its device loops."""
     start_time = time.time()
     seq, pre = FLAGS.seq_name, seg_prefix(FLAGS)
     # the static split (subject i -> shard i mod num_shards) and, on top of it, claim-file work stealing in sequence mode
@@ -324,67 +109,50 @@ def run(FLAGS, forward, log=print, engine=None):
     processed, table_time = [], []
     tables = LabelTables(FLAGS, engine)                 # --output_csv, --qc_csv, --atrial_csv: flag checks first
     shard_subjects = list(queue.static)                 # whose earlier-run results this worker measures for the tables
-    if int(getattr(FLAGS, 'device_inflate', 0) or 0) > 0:
-        if not (FLAGS.process_seq and engine is not None and getattr(FLAGS, 'device_preproc', False)) or getattr(FLAGS, 'numpy1_casting', False):
-            raise ValueError('--device_inflate needs sequence mode (--process_seq) with --device_preproc and without --numpy1_casting')
-        from ukbb_cardiac_amd import device_inflate
-        processed, table_time, _ = device_inflate.run_rounds(FLAGS, engine, data_list, log, tables, queue)
-        data_list = []
-    elif (FLAGS.process_seq and engine is not None and getattr(FLAGS, 'device_preproc', False) and getattr(FLAGS, 'io_threads', 0) > 0
-            and not getattr(FLAGS, 'numpy1_casting', False)):
-        processed, table_time, _ = run_pipelined(FLAGS, engine, data_list, log, tables, queue)
-        data_list = []
-    def one_subject(data, second):
-        """One entry of the walk; ``second``: a subject another worker held when this one first came by (--work_stealing)."""
+    on_device = device_path(FLAGS, engine)
+    inflate = int(getattr(FLAGS, 'device_inflate', 0) or 0) > 0
+    if inflate and not on_device:
+        raise ValueError('--device_inflate needs sequence mode (--process_seq) with --device_preproc and without --numpy1_casting')
+
+    def one_subject(data):
+        """One entry of the walk in ED / ES mode (deploy_network.py:153-216)."""
         data_dir = os.path.join(FLAGS.data_dir, data)
-        if not second:
-            log(data)
+        log(data)
         if not os.path.isdir(data_dir):
             return
         if os.path.exists('{0}/{1}_{2}.nii.gz'.format(data_dir, pre, seq)):
             return                                   # already segmented: idempotent / resumable (:62-67)
-        if FLAGS.process_seq:
-            image_name = '{0}/{1}.nii.gz'.format(data_dir, seq)
-            if not os.path.exists(image_name):
-                if not second:
-                    log('  Directory {0} does not contain an image with file name {1}. Skip.'.format(
-                        data_dir, os.path.basename(image_name)))
-                return
-            if not queue.take(data):
-                return                               # claimed by another worker (--work_stealing)
-            try:
-                if second:
-                    log(data)
-                log('  Reading {} ...'.format(image_name))
-                nim = nifti.load(image_name)
-                _sequence_subject(FLAGS, (data, data_dir, image_name), nim, forward, engine, log, processed, table_time, tables)
-            finally:
-                queue.done(data)
+        names = {fr: '{0}/{1}_{2}.nii.gz'.format(data_dir, seq, fr) for fr in ('ED', 'ES')}
+        if not all(os.path.exists(p) for p in names.values()):
+            log('  Directory {0} does not contain an image with file name {1} or {2}. Skip.'.format(
+                data_dir, os.path.basename(names['ED']), os.path.basename(names['ES'])))
+            return
+        for fr in ('ED', 'ES'):
+            log('  Reading {} ...'.format(names[fr]))
+            nim = nifti.load(names[fr])
+            image = nim.get_data()
+            log('  Segmenting {} frame ...'.format(fr))
+            t0 = time.time()
+            pred = pipeline.segment_frame(image, forward, FLAGS.batch_slices, bool(getattr(FLAGS, 'numpy1_casting', False)))
+            seg_time = time.time() - t0
+            log('  Segmentation time = {:3f}s'.format(seg_time))
+            table_time.append(seg_time)
+            processed.append(data)
+            if FLAGS.save_seg:
+                log('  Saving segmentation ...')
+                nifti.save(pred, '{0}/{1}_{2}_{3}.nii.gz'.format(data_dir, pre, seq, fr), nim.affine,
+                           nim.header['pixdim'])
+    if FLAGS.process_seq:
+        seq_run = _SequenceRun(FLAGS, engine, tables, queue, log, data_list)
+        if inflate:
+            processed, table_time = seq_run.run(seq_run.inflate_rounds)
+        elif on_device and getattr(FLAGS, 'io_threads', 0) > 0:
+            processed, table_time = seq_run.run(seq_run.pipelined)
         else:
-            names = {fr: '{0}/{1}_{2}.nii.gz'.format(data_dir, seq, fr) for fr in ('ED', 'ES')}
-            if not all(os.path.exists(p) for p in names.values()):
-                log('  Directory {0} does not contain an image with file name {1} or {2}. Skip.'.format(
-                    data_dir, os.path.basename(names['ED']), os.path.basename(names['ES'])))
-                return
-            for fr in ('ED', 'ES'):
-                log('  Reading {} ...'.format(names[fr]))
-                nim = nifti.load(names[fr])
-                image = nim.get_data()
-                log('  Segmenting {} frame ...'.format(fr))
-                t0 = time.time()
-                pred = pipeline.segment_frame(image, forward, FLAGS.batch_slices, bool(getattr(FLAGS, 'numpy1_casting', False)))
-                seg_time = time.time() - t0
-                log('  Segmentation time = {:3f}s'.format(seg_time))
-                table_time.append(seg_time)
-                processed.append(data)
-                if FLAGS.save_seg:
-                    log('  Saving segmentation ...')
-                    nifti.save(pred, '{0}/{1}_{2}_{3}.nii.gz'.format(data_dir, pre, seq, fr), nim.affine,
-                               nim.header['pixdim'])
-    for data in data_list:
-        one_subject(data, False)
-    for data in queue.second_chance():                  # finished by its owner meanwhile (skip-if-exists), or orphaned (stale claim)
-        one_subject(data, True)
+            processed, table_time = seq_run.run(seq_run.sequential, forward)
+    else:
+        for data in data_list:
+            one_subject(data)
     tables.write(shard_subjects, log)
     if table_time:
         log('Average segmentation time = {:.3f}s per {}'.format(float(np.mean(table_time)),

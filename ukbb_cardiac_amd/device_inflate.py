@@ -211,149 +211,3 @@ def frame_to_host(volume, k, dtype):
     """Frame k of a device volume as a host array of the file's dtype (a uint16 volume is an int16 tensor on the device)."""
     a = volume[:, :, :, k].cpu().numpy()
     return a.view(np.uint16) if np.dtype(dtype) == np.uint16 else a
-
-
-def run_rounds(FLAGS, engine, data_list, log=print, tables=None, queue=None):
-    """deploy_network.py --device_inflate K: sequence mode in rounds of up to K subjects.  The --io_threads readers read the files
-    of round r + 1 (a read(), no decoding) while the GPU works on round r: one copy of the compressed bytes, one inflate launch,
-    one CRC launch, then subject by subject segment_sequence_tensor, the label tables and the writers of the pipelined loop.
-    Same files, byte for byte.  A declined subject takes nifti.load and the sequential path, as an odd subject of run_pipelined."""
-    import os
-    import time
-    from concurrent.futures import ThreadPoolExecutor
-    from . import device_pipeline
-    from .deploy_network import _sequence_subject, save_sequence_outputs, seg_prefix
-    from .label_tables import LabelTables
-    start_time = time.time()
-    seq, pre = FLAGS.seq_name, seg_prefix(FLAGS)
-    tables = tables or LabelTables(FLAGS, engine)
-    K = int(FLAGS.device_inflate)
-
-    def candidates(names, second=False):
-        """(data, data_dir, image_name) of the subjects still to segment, in walk order, each claimed right before its read is scheduled"""
-        for data in names:
-            data_dir = os.path.join(FLAGS.data_dir, data)
-            if not os.path.isdir(data_dir) or os.path.exists('{0}/{1}_{2}.nii.gz'.format(data_dir, pre, seq)):
-                if not second:
-                    log(data)
-                continue
-            image_name = '{0}/{1}.nii.gz'.format(data_dir, seq)
-            if not os.path.exists(image_name):
-                if not second:
-                    log(data)
-                    log('  Directory {0} does not contain an image with file name {1}. Skip.'.format(data_dir, os.path.basename(image_name)))
-                continue
-            if queue is not None and not queue.take(data):
-                continue                                    # another worker is on it
-            yield (data, data_dir, image_name)
-
-    def todo_items():
-        yield from candidates(data_list)
-        if queue is not None:
-            yield from candidates(queue.second_chance(), second=True)
-
-    def release(data):
-        if queue is not None:
-            queue.done(data)
-
-    def read(item):
-        with open(item[2], 'rb') as f:
-            return f.read()
-
-    nthr = max(1, int(FLAGS.io_threads))
-    readers, writers = ThreadPoolExecutor(nthr), ThreadPoolExecutor(nthr)
-    inflater = DeviceInflater(engine, max_streams=K)
-    processed, table_time, writes = [], [], []
-    phases = {'read_wait': 0.0, 'pack': 0.0, 'h2d': 0.0, 'inflate_crc': 0.0, 'results_d2h': 0.0, 'segment': 0.0, 'frames_tables': 0.0,
-              'writer_wait': 0.0}
-    todo = todo_items()
-
-    def schedule():
-        items = []
-        for item in todo:
-            items.append((item, readers.submit(read, item)))
-            if len(items) >= K:
-                break
-        return items
-
-    def one(item, got):
-        data, data_dir, image_name = item
-        if isinstance(got, Declined):
-            log(data)
-            try:
-                nim = nifti.load(image_name)
-                _sequence_subject(FLAGS, item, nim, None, engine, log, processed, table_time, tables)
-            finally:
-                release(data)
-            return
-        plan, nim = got.plan, header_image(got.plan)
-        t0 = time.time()
-        args = tables.subject_args(data_dir, nim, log)
-        pred, aux = device_pipeline.segment_sequence_tensor(got.volume, plan.dtype, plan.shape, engine, FLAGS.batch_slices, return_aux=True,
-                                                            stats=tables.statistics(), stat_args=args)
-        seg_time = time.time() - t0
-        phases['segment'] += seg_time
-        t1 = time.time()
-        k_ed, k_es = device_pipeline.pick_ed_es_from_counts(aux['counts'], seq, FLAGS.seg4)
-        log(data)
-        log('  Reading {} ...'.format(image_name))
-        log('  Segmenting full sequence ...')
-        log('  Segmentation time = {:3f}s'.format(seg_time))
-        log('  ED frame = {:d}, ES frame = {:d}'.format(k_ed, k_es))
-        table_time.append(seg_time)
-        processed.append(data)
-        tables.record(data, data_dir, nim, aux['counts'], aux['stats'], log)
-        if FLAGS.save_seg:
-            log('  Saving segmentation ...')
-            # the saved frames are the CLIPPED intensities (alias quirk, SURVEY.md App. C.1), copied back from the device volume
-            frames = {fr: (device_pipeline.clip_like_reference(frame_to_host(got.volume, k, plan.dtype), aux['clip']), pred[:, :, :, k])
-                      for fr, k in (('ED', k_ed), ('ES', k_es))}
-
-            def write_then_release():
-                try:
-                    save_sequence_outputs(data_dir, pre, seq, nim.affine, nim.header['pixdim'], pred, frames)
-                finally:
-                    release(data)
-            writes.append(writers.submit(write_then_release))
-        else:
-            release(data)
-        phases['frames_tables'] += time.time() - t1
-
-    try:
-        nxt = schedule()
-        while nxt:
-            cur, nxt = nxt, None
-            t0 = time.time()
-            blobs = [fut.result() for _, fut in cur]
-            phases['read_wait'] += time.time() - t0
-            nxt = schedule()                                    # the readers fill the next round while the GPU works on this one
-            while cur:
-                results = inflater.inflate(blobs)
-                tm = inflater.timing
-                phases['pack'] += tm.get('pack', 0.0)
-                phases['h2d'] += tm.get('h2d', 0.0)
-                phases['inflate_crc'] += tm.get('inflate_crc', 0.0)
-                phases['results_d2h'] += tm.get('device', 0.0) - tm.get('h2d', 0.0) - tm.get('inflate_crc', 0.0)
-                inflater.timing = {}
-                # what found no room in this launch (max_streams, max_bytes) gets a launch of its own once the others are through;
-                # a single subject that no launch can hold is declined for good
-                rest = [k for k, got in enumerate(results) if isinstance(got, Declined) and got.reason == NO_ROOM]
-                if rest and rest[0] == 0:
-                    results[0] = Declined('larger than the output buffer')
-                    rest = rest[1:]
-                for k, ((item, _), got) in enumerate(zip(cur, results)):
-                    if k not in rest:
-                        one(item, got)
-                cur, blobs = [cur[k] for k in rest], [blobs[k] for k in rest]
-            blobs = None
-        t0 = time.time()
-        for w in writes:
-            w.result()
-        phases['writer_wait'] += time.time() - t0
-    finally:
-        readers.shutdown(wait=True)
-        writers.shutdown(wait=True)
-        if queue is not None:
-            queue.release_all()
-    run_rounds.last_phases = phases                           # for tools/bench_device_inflate.py: where the GPU thread's time went
-    return processed, table_time, start_time

@@ -113,6 +113,10 @@ class SubjectPipeline:
             self._staged[id(st.array)] = st
         return st
 
+    def fits(self, image):
+        """Does a volume fit the pinned staging buffers (``stage`` raises for one that does not)?"""
+        return image.size <= self._in_cap
+
     def release(self, array):
         """Give back a buffer ``stage()`` handed out that will not be submitted after all (its file failed to load)."""
         with self._lock:
