@@ -401,6 +401,36 @@ int64_t ukbb_fcn_gzip_labels(const uint8_t *labels, uint64_t n_voxels, int nifti
 int64_t ukbb_fcn_gzip_labels_mode(const uint8_t *labels, uint64_t n_voxels, int nifti_datatype, const uint8_t *prefix, uint64_t prefix_len,
                                   uint8_t *out, uint64_t out_cap, int mode);
 
+/* ---- label-volume files, deflated on the device ---------------------------------------------------------------
+ * The member ukbb_fcn_gzip_labels_mode writes, byte for byte, from a label volume that lies in device memory: the token stream is a pure
+ * function of the run list, so run detection, the token histogram, per-run bit counts, a prefix sum of bit offsets, emission and the
+ * CRC-32 (closed form per run, GF(2) combine) are data-parallel (csrc/kernels_labelgz.hip; the per-run arithmetic is
+ * csrc/label_gzip_core.h, one text with the host writer).  The inflated stream is never formed.  No reference counterpart.
+ *
+ * ukbb_fcn_gzip_labels_device: everything is enqueued on `stream`; nothing synchronises.  d_labels[n_voxels] uint8 in file order,
+ * d_prefix[prefix_len] the bytes in front of the voxels (the 352-byte NIfTI-1 header), both device memory; mode UKBB_GZIP_FIXED or
+ * UKBB_GZIP_DYNAMIC; datatypes 2, 4, 8, 16, 64 as on the host.  d_out[out_cap] (4-byte aligned) receives the member; no byte at or
+ * beyond out_cap is written.  d_scratch: ukbb_fcn_gzip_labels_device_scratch(n_voxels, max_runs) bytes (16-byte aligned) holding, among
+ * others, a run table of max_runs entries; nothing outside it is written.  *d_len (device int64) = the member's length, or
+ * UKBB_LABELGZ_NO_ROOM when it does not fit out_cap, or UKBB_LABELGZ_TOO_MANY_RUNS when the volume has more than max_runs runs; after
+ * a decline d_out holds nothing of use.  The return value carries argument and launch errors only.
+ * Limits: 1 <= n_voxels <= UKBB_LABELGZ_MAX_VOXELS, prefix_len <= UKBB_LABELGZ_MAX_PREFIX, 1 <= max_runs <= n_voxels is enough.
+ * ukbb_fcn_gzip_labels_device_geometry: geometry[0] = voxels per workgroup of the run scan, [1] = runs per workgroup of the
+ * histogram / bit-offset / emission launches, [2] = bits per LDS window of the emission, [3] = (258, E) tokens from which a run is
+ * filled by the whole workgroup (tests place run starts around these borders). */
+#define UKBB_LABELGZ_NO_ROOM (-4)
+#define UKBB_LABELGZ_TOO_MANY_RUNS (-5)
+#define UKBB_LABELGZ_MAX_VOXELS 0x7fff0000ull
+#define UKBB_LABELGZ_MAX_PREFIX 4096
+uint64_t ukbb_fcn_gzip_labels_device_scratch(uint64_t n_voxels, uint64_t max_runs);
+void ukbb_fcn_gzip_labels_device_geometry(uint32_t geometry[4]);
+int ukbb_fcn_gzip_labels_device(const uint8_t *d_labels, uint64_t n_voxels, int nifti_datatype, const uint8_t *d_prefix, uint64_t prefix_len,
+                                int mode, uint8_t *d_out, uint64_t out_cap, void *d_scratch, uint64_t max_runs, int64_t *d_len, void *stream);
+/* The same parallel formulation, run serially on the host over host pointers (tests, sanitizer program): returns the length,
+ * UKBB_LABELGZ_NO_ROOM / UKBB_LABELGZ_TOO_MANY_RUNS (nothing written), or UKBB_EINVAL. */
+int64_t ukbb_fcn_gzip_labels_parallel_host(const uint8_t *labels, uint64_t n_voxels, int nifti_datatype, const uint8_t *prefix,
+                                           uint64_t prefix_len, int mode, uint8_t *out, uint64_t out_cap, uint64_t max_runs);
+
 /* ---- image files in (host only) -------------------------------------------------------------------
  * What the reference does first with every subject: nib.load(image_name).get_data()
  * (common/deploy_network.py:80-83, deploy_network_ao.py:88-92) -- for a short-axis cine 40 MB of int16

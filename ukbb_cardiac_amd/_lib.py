@@ -34,6 +34,8 @@ EXPORTS = [
     'ukbb_fcn_cine_min_scratch_bytes', 'ukbb_fcn_cine_chunk_windows',
     'ukbb_fcn_plane_components', 'ukbb_fcn_atrial_area_length',
     'ukbb_fcn_inflate_device', 'ukbb_fcn_inflate_core_host', 'ukbb_fcn_gzip_crc_combine',
+    'ukbb_fcn_gzip_labels_device_scratch', 'ukbb_fcn_gzip_labels_device_geometry', 'ukbb_fcn_gzip_labels_device',
+    'ukbb_fcn_gzip_labels_parallel_host',
 ]
 
 
@@ -150,6 +152,13 @@ def _load():
     lib.ukbb_fcn_inflate_core_host.argtypes = [vp, C.c_uint64, vp, C.c_uint64]
     lib.ukbb_fcn_gzip_crc_combine.restype = C.c_uint32
     lib.ukbb_fcn_gzip_crc_combine.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]
+    lib.ukbb_fcn_gzip_labels_device_scratch.restype = C.c_uint64
+    lib.ukbb_fcn_gzip_labels_device_scratch.argtypes = [C.c_uint64, C.c_uint64]
+    lib.ukbb_fcn_gzip_labels_device_geometry.restype = None
+    lib.ukbb_fcn_gzip_labels_device_geometry.argtypes = [C.POINTER(C.c_uint32 * 4)]
+    lib.ukbb_fcn_gzip_labels_device.argtypes = [vp, C.c_uint64, C.c_int, vp, C.c_uint64, C.c_int, vp, C.c_uint64, vp, C.c_uint64, vp, vp]
+    lib.ukbb_fcn_gzip_labels_parallel_host.restype = C.c_int64
+    lib.ukbb_fcn_gzip_labels_parallel_host.argtypes = [vp, C.c_uint64, C.c_int, vp, C.c_uint64, C.c_int, vp, C.c_uint64, C.c_uint64]
     lib.ukbb_fcn_kernel_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int, C.c_int]
     lib.ukbb_fcn_get_activation.restype = C.c_int64
     lib.ukbb_fcn_get_activation.argtypes = [vp, C.c_char_p, f32p, C.c_int64]

@@ -14,19 +14,23 @@
 // histogram, from which a length-limited Huffman code is built -- the handful of byte values a label pattern consists of
 // and the one distance in use then cost 1-3 bits each, which brings the file to the size zlib level 1 reaches on the
 // same volume (r03: smaller on every volume tried) for one extra 20 MB read.
+// The per-run arithmetic -- element patterns, the split of a run into tokens, length symbols, the Huffman builder and block header, the
+// GF(2) helpers and the closed-form CRC of a run -- is label_gzip_core.h, one text with the device encoder (kernels_labelgz.hip).  This
+// file keeps the serial walk (table-driven CRC, packed tokens) and runs the parallel formulation serially for tests.
 #include "../../include/ukbb_fcn.h"
+#include "label_gzip_core.h"
 
 #include <cstdint>
 #include <cstring>
+#include <vector>
 
 namespace {
 
-constexpr uint32_t POLY = 0xEDB88320u;                 // CRC-32 (reflected)
+using ukbb_labelgz::POLY;
 
 struct Tables {
     uint32_t crc[8][256];                              // slicing-by-8
     uint32_t x2n[32];                                  // x^(2^k) mod P, reflected
-    uint16_t lit_bits[288]; uint8_t lit_len[288];     // fixed literal/length codes, bit-reversed for LSB-first output
     uint16_t len_sym[259]; uint8_t len_xbits[259]; uint16_t len_xval[259];
     Tables() {
         for (uint32_t i = 0; i < 256; ++i) {
@@ -36,43 +40,14 @@ struct Tables {
         }
         for (uint32_t i = 0; i < 256; ++i)
             for (int t = 1; t < 8; ++t) crc[t][i] = (crc[t - 1][i] >> 8) ^ crc[0][crc[t - 1][i] & 0xff];
-        x2n[0] = 1u << 30;                             // x^1
-        for (int k = 1; k < 32; ++k) x2n[k] = mult(x2n[k - 1], x2n[k - 1]);
-        auto rev = [](uint32_t v, int n) { uint32_t r = 0; for (int i = 0; i < n; ++i) { r = (r << 1) | (v & 1); v >>= 1; } return r; };
-        for (int s = 0; s < 288; ++s) {
-            uint32_t code; int len;
-            if (s < 144) { code = 0x30 + s; len = 8; }
-            else if (s < 256) { code = 0x190 + (s - 144); len = 9; }
-            else if (s < 280) { code = s - 256; len = 7; }
-            else { code = 0xC0 + (s - 280); len = 8; }
-            lit_bits[s] = (uint16_t)rev(code, len); lit_len[s] = (uint8_t)len;
-        }
-        static const int base[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
-        static const int xb[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
+        ukbb_labelgz::x2n_fill(x2n);
         for (int l = 3; l <= 258; ++l) {
-            int i = 28;
-            while (base[i] > l) --i;
-            if (l == 258) i = 28;
-            else if (i == 28) i = 27;                  // 227..257 belong to symbol 284
-            len_sym[l] = (uint16_t)(257 + i); len_xbits[l] = (uint8_t)xb[i]; len_xval[l] = (uint16_t)(l - base[i]);
+            int s, xb, xv;
+            ukbb_labelgz::length_code(l, s, xb, xv);
+            len_sym[l] = (uint16_t)s; len_xbits[l] = (uint8_t)xb; len_xval[l] = (uint16_t)xv;
         }
     }
-    static uint32_t mult(uint32_t a, uint32_t b) {     // a * b mod P (reflected polynomials, zlib's multmodp)
-        uint32_t m = 1u << 31, p = 0;
-        for (;;) {
-            if (a & m) { p ^= b; if ((a & (m - 1)) == 0) break; }
-            m >>= 1;
-            b = b & 1 ? (b >> 1) ^ POLY : b >> 1;
-        }
-        return p;
-    }
-    uint32_t shift_zero_bytes(uint32_t reg, uint64_t nbytes) const {   // CRC register after nbytes zero bytes: reg * x^(8 n)
-        uint32_t p = 1u << 31;                         // x^0
-        unsigned k = 3;
-        for (uint64_t n = nbytes; n; n >>= 1, ++k)
-            if (n & 1) p = mult(x2n[k & 31], p);
-        return mult(p, reg);
-    }
+    uint32_t shift_zero_bytes(uint32_t reg, uint64_t nbytes) const { return ukbb_labelgz::shift_zero_bytes(x2n, reg, nbytes); }
 };
 const Tables &tables() { static const Tables t; return t; }
 
@@ -108,82 +83,8 @@ inline uint32_t crc_bytes(const Tables &t, uint32_t reg, const uint8_t *b, size_
     return reg;
 }
 
-int element_pattern(int datatype, unsigned label, uint8_t out[8]) {   // little-endian bytes of `label` as NIfTI datatype; returns the size
-    switch (datatype) {
-        case 2:  out[0] = (uint8_t)label; return 1;                                         // uint8
-        case 4:  { const int16_t v = (int16_t)label; memcpy(out, &v, 2); return 2; }         // int16
-        case 8:  { const int32_t v = (int32_t)label; memcpy(out, &v, 4); return 4; }         // int32
-        case 16: { const float v = (float)label; memcpy(out, &v, 4); return 4; }             // float32
-        case 64: { const double v = (double)label; memcpy(out, &v, 8); return 8; }           // float64
-        default: return 0;
-    }
-}
-
-
-// ---- code sets ---------------------------------------------------------------------------------------------------------
-struct CodeSet {
-    uint16_t lit_bits[288]; uint8_t lit_len[288];     // literal/length codes, bit-reversed for LSB-first output
-    uint32_t dbits; int dlen;                          // the one distance in use (E), extra bit included
-};
-
-inline uint32_t rev_bits(uint32_t v, int n) { uint32_t r = 0; for (int i = 0; i < n; ++i) { r = (r << 1) | (v & 1); v >>= 1; } return r; }
-
-// Huffman code lengths for freq[0..n) limited to max_len bits; symbols with freq 0 get length 0.  At least two symbols
-// get a code (zlib's inflate rejects an incomplete literal/length or code-length code).
-void huffman_lengths(const uint64_t *freq, int n, int max_len, uint8_t *len) {
-    int sym[288 + 2], m = 0;
-    for (int i = 0; i < n; ++i) { len[i] = 0; if (freq[i]) sym[m++] = i; }
-    for (int i = 0; m < 2 && i < n; ++i) if (!freq[i]) sym[m++] = i;    // pad with unused symbols (weight 0 -> treated as 1)
-    // plain O(m^2) Huffman over <= 288 leaves: parent links, depth = code length
-    uint64_t w[2 * 290]; int parent[2 * 290]; bool alive[2 * 290];
-    int nn = m;
-    for (int i = 0; i < m; ++i) { w[i] = freq[sym[i]] ? freq[sym[i]] : 1; parent[i] = -1; alive[i] = true; }
-    for (int left = m; left > 1; --left) {
-        int a = -1, b = -1;
-        for (int i = 0; i < nn; ++i) if (alive[i]) {
-            if (a < 0 || w[i] < w[a]) { b = a; a = i; }
-            else if (b < 0 || w[i] < w[b]) b = i;
-        }
-        w[nn] = w[a] + w[b]; parent[nn] = -1; alive[nn] = true;
-        parent[a] = parent[b] = nn; alive[a] = alive[b] = false;
-        ++nn;
-    }
-    int L[290];
-    for (int i = 0; i < m; ++i) { int d = 0; for (int j = i; parent[j] >= 0; j = parent[j]) ++d; L[i] = d < 1 ? 1 : d; }
-    // limit: clamp, then repair the Kraft sum (unit 2^-max_len) to exactly 1
-    int64_t K = 0;
-    const int64_t full = (int64_t)1 << max_len;
-    for (int i = 0; i < m; ++i) { if (L[i] > max_len) L[i] = max_len; K += full >> L[i]; }
-    while (K > full) {                                 // lengthen the cheapest symbol that still can be (longest code < max_len, smallest weight)
-        int best = -1;
-        for (int i = 0; i < m; ++i) if (L[i] < max_len && (best < 0 || L[i] > L[best] || (L[i] == L[best] && w[i] < w[best]))) best = i;
-        K -= full >> (L[best] + 1); ++L[best];
-    }
-    while (K < full) {                                 // shorten: the heaviest symbol whose step fits the deficit
-        int best = -1;
-        for (int i = 0; i < m; ++i) if (L[i] > 1 && (full >> L[i]) <= full - K && (best < 0 || w[i] > w[best])) best = i;
-        K += full >> L[best]; --L[best];
-    }
-    for (int i = 0; i < m; ++i) len[sym[i]] = (uint8_t)L[i];
-}
-
-void canonical_codes(const uint8_t *len, int n, int max_len, uint16_t *bits) {   // RFC 1951 3.2.2, bit-reversed
-    int count[16] = {0}, next[16];
-    for (int i = 0; i < n; ++i) ++count[len[i]];
-    count[0] = 0;
-    int code = 0;
-    for (int b = 1; b <= max_len; ++b) { code = (code + count[b - 1]) << 1; next[b] = code; }
-    for (int i = 0; i < n; ++i) bits[i] = len[i] ? (uint16_t)rev_bits((uint32_t)next[len[i]]++, len[i]) : 0;
-}
-
-int dist_code_of(int E) { return E == 1 ? 0 : E == 2 ? 1 : E == 4 ? 3 : 5; }
-
-void fixed_codes(const Tables &t, int E, CodeSet &c) {
-    for (int s = 0; s < 288; ++s) { c.lit_bits[s] = t.lit_bits[s]; c.lit_len[s] = t.lit_len[s]; }
-    // distance code of E: 1 -> 0, 2 -> 1, 4 -> 3, 8 -> code 5 + extra bit 1 (distances 7-8); 5-bit codes go out MSB first
-    c.dbits = rev_bits((uint32_t)dist_code_of(E), 5); c.dlen = 5;
-    if (E == 8) { c.dbits |= 1u << 5; c.dlen = 6; }
-}
+using ukbb_labelgz::CodeSet;
+using ukbb_labelgz::element_pattern;
 
 // Walks the runs of equal labels: f(v, run_length) per run, in order.
 template <class F>
@@ -202,15 +103,6 @@ inline void for_each_run(const uint8_t *labels, uint64_t n_voxels, F &&f) {
         f(v, j - i);
         i = j;
     }
-}
-
-// The matches that follow the E opening literals of a run: R = (run - 1) * E bytes at distance E as n258 matches of
-// length 258 plus a tail: 0, a literal tail of 1-2 bytes (tail < 3), one match (3..258) or two (259, 260 -> tail - 3, 3).
-inline void split_run(uint64_t R, uint64_t &n258, unsigned &tail) {
-    n258 = 0;
-    if (R >= 261) { n258 = (R - 3) / 258; R -= 258 * n258; }
-    if (R == 258) { ++n258; R = 0; }
-    tail = (unsigned)R;
 }
 
 }  // namespace
@@ -243,80 +135,23 @@ int64_t ukbb_fcn_gzip_labels_mode(const uint8_t *labels, uint64_t n_voxels, int 
     w.put(1, 1);                                       // BFINAL
     if (mode == UKBB_GZIP_FIXED) {
         w.put(1, 2);                                   // BTYPE = 01, fixed Huffman
-        fixed_codes(t, E, cs);
+        ukbb_labelgz::fixed_codes(E, cs);
     } else {
-        // ---- pass 1: the exact histogram of the tokens pass 2 will write ----
+        // ---- pass 1: the exact histogram of the tokens pass 2 will write, then the codes and the block header ----
         uint64_t runs[256] = {0}, lit[288] = {0};
+        auto add = [&](int s, uint64_t c) { lit[s] += c; };
         for (uint64_t i = 0; i < prefix_len; ++i) ++lit[prefix[i]];
         for_each_run(labels, n_voxels, [&](uint8_t v, uint64_t run) {
             ++runs[v];
-            uint64_t n258; unsigned tail;
-            split_run((run - 1) * (uint64_t)E, n258, tail);
-            lit[285] += n258;
-            if (tail > 258) { ++lit[t.len_sym[tail - 3]]; ++lit[t.len_sym[3]]; }
-            else if (tail >= 3) ++lit[t.len_sym[tail]];
-            else for (unsigned b = 0; b < tail; ++b) ++lit[pat[v][b % E]];
+            ukbb_labelgz::run_tail_histogram(pat[v], E, run, add);
         });
         for (unsigned v = 0; v < 256; ++v)
-            if (runs[v]) for (int b = 0; b < E; ++b) lit[pat[v][b]] += runs[v];
+            if (runs[v]) ukbb_labelgz::run_open_histogram(pat[v], E, runs[v], add);
         lit[256] = 1;                                  // end of block
-        huffman_lengths(lit, 286, 15, cs.lit_len);
-        cs.lit_len[286] = cs.lit_len[287] = 0;
-        canonical_codes(cs.lit_len, 286, 15, cs.lit_bits);
-        // one distance code in use: a single 1-bit code (RFC 1951 3.2.7), then the extra bit of distances 7-8 for E = 8
-        const int dcode = dist_code_of(E);
-        cs.dbits = 0; cs.dlen = 1;
-        if (E == 8) { cs.dbits |= 1u << 1; cs.dlen = 2; }
-        // ---- block header: BTYPE 10, HLIT / HDIST / HCLEN, code-length code, run-length coded code lengths ----
-        int nlit = 286;
-        while (nlit > 257 && !cs.lit_len[nlit - 1]) --nlit;
-        const int ndist = dcode + 1;
-        uint8_t seq[286 + 30];
-        for (int i = 0; i < nlit; ++i) seq[i] = cs.lit_len[i];
-        for (int i = 0; i < ndist; ++i) seq[nlit + i] = (uint8_t)(i == dcode ? 1 : 0);
-        const int nseq = nlit + ndist;
-        struct Cl { uint8_t sym, xbits, xval; } cl[286 + 30];
-        int ncl = 0;
-        uint64_t clfreq[19] = {0};
-        for (int i = 0; i < nseq;) {
-            int j = i + 1;
-            while (j < nseq && seq[j] == seq[i]) ++j;
-            int rep = j - i;
-            if (seq[i] == 0) {
-                while (rep >= 11) { const int k = rep > 138 ? 138 : rep; cl[ncl++] = Cl{18, 7, (uint8_t)(k - 11)}; rep -= k; }
-                if (rep >= 3) { cl[ncl++] = Cl{17, 3, (uint8_t)(rep - 3)}; rep = 0; }
-                while (rep--) cl[ncl++] = Cl{0, 0, 0};
-            } else {
-                cl[ncl++] = Cl{seq[i], 0, 0}; --rep;
-                while (rep >= 3) { const int k = rep > 6 ? 6 : rep; cl[ncl++] = Cl{16, 2, (uint8_t)(k - 3)}; rep -= k; }
-                while (rep--) cl[ncl++] = Cl{seq[i], 0, 0};
-            }
-            i = j;
-        }
-        for (int i = 0; i < ncl; ++i) ++clfreq[cl[i].sym];
-        uint8_t cll[19]; uint16_t clb[19];
-        huffman_lengths(clfreq, 19, 7, cll);
-        canonical_codes(cll, 19, 7, clb);
-        static const int order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-        int hclen = 19;
-        while (hclen > 4 && !cll[order[hclen - 1]]) --hclen;
-        w.put(2, 2);                                   // BTYPE = 10, dynamic Huffman
-        w.put((uint32_t)(nlit - 257), 5);
-        w.put((uint32_t)(ndist - 1), 5);
-        w.put((uint32_t)(hclen - 4), 4);
-        for (int i = 0; i < hclen; ++i) w.put(cll[order[i]], 3);
-        for (int i = 0; i < ncl; ++i) {
-            w.put(clb[cl[i].sym], cll[cl[i].sym]);
-            if (cl[i].xbits) w.put(cl[i].xval, cl[i].xbits);
-        }
+        ukbb_labelgz::HeaderWork hw;
+        ukbb_labelgz::dynamic_codes(lit, E, cs, hw, w);
     }
     auto literal = [&](uint8_t b) { w.put(cs.lit_bits[b], cs.lit_len[b]); };
-    auto match = [&](int len) {                        // (length, distance E)
-        const int s = t.len_sym[len];
-        w.put(cs.lit_bits[s], cs.lit_len[s]);
-        if (t.len_xbits[len]) w.put(t.len_xval[len], t.len_xbits[len]);
-        w.put(cs.dbits, cs.dlen);
-    };
     // (258, E) tokens, several to a 32-bit piece
     const int tok258_len = cs.lit_len[285] + cs.dlen;
     const uint32_t tok258 = (uint32_t)cs.lit_bits[285] | (cs.dbits << cs.lit_len[285]);
@@ -325,6 +160,14 @@ int64_t ukbb_fcn_gzip_labels_mode(const uint8_t *labels, uint64_t n_voxels, int 
     uint32_t pack258 = 0;
     for (int k = 0; k < pack_n && pack_n * tok258_len <= 32; ++k) pack258 |= tok258 << (k * tok258_len);
     struct Chunk { uint32_t bits; int len; };
+    struct Sink {                                      // the core's emission into the bit writer; (258, E) tokens go out packed
+        BitWriter &w; int pack_n, tok258_len; uint32_t pack258;
+        void put(uint32_t v, int bits) { w.put(v, bits); }
+        void fill258(uint64_t n258, uint32_t tok258, int) {
+            for (; n258 >= (uint64_t)pack_n; n258 -= pack_n) w.put(pack258, pack_n * tok258_len);
+            for (; n258; --n258) w.put(tok258, tok258_len);
+        }
+    } sink{w, pack_n, tok258_len, pack258};
     Chunk first_tok[256][5];                           // the E literals that open a run of label v, packed into <= 32-bit pieces
     int first_n[256];
     bool have[256] = {false};
@@ -350,13 +193,7 @@ int64_t ukbb_fcn_gzip_labels_mode(const uint8_t *labels, uint64_t n_voxels, int 
         const uint8_t *P = pat[v];
         // ---- deflate tokens ----
         for (int c = 0; c < first_n[v]; ++c) w.put(first_tok[v][c].bits, first_tok[v][c].len);
-        uint64_t n258; unsigned tail;
-        split_run((run - 1) * (uint64_t)E, n258, tail);
-        for (; n258 >= (uint64_t)pack_n; n258 -= pack_n) w.put(pack258, pack_n * tok258_len);
-        for (; n258; --n258) w.put(tok258, tok258_len);
-        if (tail > 258) { match((int)tail - 3); match(3); }
-        else if (tail >= 3) match((int)tail);
-        else for (unsigned b = 0; b < tail; ++b) literal(P[b % E]);
+        ukbb_labelgz::emit_run_body(sink, cs, P, E, run);
         if (w.overflow) { overflow = true; return; }
         // ---- CRC-32 of the run ----
         bool zero = true;
@@ -389,6 +226,86 @@ int64_t ukbb_fcn_gzip_labels_mode(const uint8_t *labels, uint64_t n_voxels, int 
 int64_t ukbb_fcn_gzip_labels(const uint8_t *labels, uint64_t n_voxels, int nifti_datatype, const uint8_t *prefix, uint64_t prefix_len,
                              uint8_t *out, uint64_t out_cap) {
     return ukbb_fcn_gzip_labels_mode(labels, n_voxels, nifti_datatype, prefix, prefix_len, out, out_cap, UKBB_GZIP_DYNAMIC);
+}
+
+// The formulation the device encoder runs (kernels_labelgz.hip), step by step and serially: run table, histogram, codes and head,
+// per-run bit counts and their exclusive scan, capacity check, every run written at its own bit offset (in no particular order: OR
+// onto zeroed bytes), closed-form CRC pieces joined in order.  Nothing is written unless the whole member fits out_cap.
+int64_t ukbb_fcn_gzip_labels_parallel_host(const uint8_t *labels, uint64_t n_voxels, int nifti_datatype, const uint8_t *prefix,
+                                           uint64_t prefix_len, int mode, uint8_t *out, uint64_t out_cap, uint64_t max_runs) {
+    using namespace ukbb_labelgz;
+    uint8_t P[8];
+    const int E = element_pattern(nifti_datatype, 0, P);
+    if (!labels || !out || (!prefix && prefix_len) || !E || (mode != UKBB_GZIP_FIXED && mode != UKBB_GZIP_DYNAMIC) || n_voxels < 1 ||
+        n_voxels > UKBB_LABELGZ_MAX_VOXELS || prefix_len > UKBB_LABELGZ_MAX_PREFIX || max_runs < 1)
+        return UKBB_EINVAL;
+    // 1. runs: a voxel starts one when it differs from its predecessor
+    uint64_t n_runs = 0;
+    for (uint64_t i = 0; i < n_voxels; ++i) n_runs += i == 0 || labels[i] != labels[i - 1];
+    if (n_runs > max_runs) return UKBB_LABELGZ_TOO_MANY_RUNS;
+    std::vector<uint32_t> start((size_t)n_runs);
+    for (uint64_t i = 0, r = 0; i < n_voxels; ++i) if (i == 0 || labels[i] != labels[i - 1]) start[(size_t)r++] = (uint32_t)i;
+    auto run_len = [&](uint64_t r) { return (r + 1 < n_runs ? start[(size_t)r + 1] : n_voxels) - start[(size_t)r]; };
+    // 2. histogram
+    uint64_t lit[288] = {0};
+    auto add = [&](int s, uint64_t c) { lit[s] += c; };
+    if (mode == UKBB_GZIP_DYNAMIC) {
+        for (uint64_t r = 0; r < n_runs; ++r) {
+            element_pattern(nifti_datatype, labels[start[(size_t)r]], P);
+            run_open_histogram(P, E, 1, add);
+            run_tail_histogram(P, E, run_len(r), add);
+        }
+        for (uint64_t i = 0; i < prefix_len; ++i) ++lit[prefix[i]];
+        lit[256] = 1;
+    }
+    // 3. codes and head
+    std::vector<uint32_t> head_words((size_t)(head_bits_bound(prefix_len) / 32 + 2), 0u);
+    WordSink head{head_words.data(), 0};
+    CodeSet cs;
+    HeaderWork hw;
+    uint32_t x2n[32];
+    x2n_fill(x2n);
+    const uint32_t reg0 = emit_head(head, mode, lit, E, prefix, prefix_len, cs, hw);
+    // 4. bit offsets
+    std::vector<uint64_t> off((size_t)n_runs + 1);
+    off[0] = head.pos;
+    for (uint64_t r = 0; r < n_runs; ++r) {
+        element_pattern(nifti_datatype, labels[start[(size_t)r]], P);
+        off[(size_t)r + 1] = off[(size_t)r] + run_bits(cs, P, E, run_len(r));
+    }
+    // 5. capacity, then emission
+    const uint64_t total_bits = off[(size_t)n_runs] + cs.lit_len[256];
+    const uint64_t len = (total_bits + 7) / 8 + 8;
+    if (len > out_cap) return UKBB_LABELGZ_NO_ROOM;
+    memset(out, 0, (size_t)len);
+    memcpy(out, head_words.data(), (size_t)((head.pos + 7) / 8));
+    struct ByteSink {
+        uint8_t *out; uint64_t pos;
+        void put(uint32_t v, int bits) {
+            uint64_t x = (uint64_t)v << (pos & 7);
+            for (uint64_t i = pos >> 3; x; ++i, x >>= 8) out[i] |= (uint8_t)x;
+            pos += (uint64_t)bits;
+        }
+        void fill258(uint64_t n, uint32_t tok, int len) { for (; n; --n) put(tok, len); }
+    };
+    CrcPiece all = crc_identity();
+    for (uint64_t k = n_runs; k-- > 0;) {              // back to front: the order does not matter
+        element_pattern(nifti_datatype, labels[start[(size_t)k]], P);
+        ByteSink s{out, off[(size_t)k]};
+        emit_run(s, cs, P, E, run_len(k));
+        if (s.pos != off[(size_t)k + 1]) return UKBB_EINVAL;   // run_bits and emit_run disagree: cannot happen
+    }
+    for (uint64_t r = 0; r < n_runs; ++r) {
+        element_pattern(nifti_datatype, labels[start[(size_t)r]], P);
+        all = crc_join(all, crc_pattern_run(x2n, P, E, run_len(r)));
+    }
+    // 6. end of block, CRC-32 and ISIZE
+    ByteSink s{out, off[(size_t)n_runs]};
+    s.put(cs.lit_bits[256], cs.lit_len[256]);
+    const uint32_t crc = (mult(all.pw, reg0) ^ all.c) ^ 0xFFFFFFFFu;
+    const uint32_t isize = (uint32_t)((prefix_len + n_voxels * (uint64_t)E) & 0xFFFFFFFFull);
+    memcpy(out + len - 8, &crc, 4); memcpy(out + len - 4, &isize, 4);
+    return (int64_t)len;
 }
 
 }  // extern "C"

@@ -16,7 +16,8 @@ and writes the same files (``deploy_network.py:136-151,207-216``):
 
 Extra flags (not in the reference): ``--device``, ``--batch_slices``,
 ``--num_shards`` / ``--shard_index`` (multi-GPU batch split), ``--output_csv``, ``--qc_csv``,
-``--atrial_csv``, ``--device_inflate`` (gzip inputs inflated on the GPU).
+``--atrial_csv``, ``--device_inflate`` (gzip inputs inflated on the GPU), ``--device_label_gzip`` (label
+volumes deflated on the GPU).
 """
 import os
 import sys
@@ -32,7 +33,8 @@ from ukbb_cardiac_amd.flags import FlagError, FlagSet              # noqa: E402
 from ukbb_cardiac_amd.label_tables import LabelTables              # noqa: E402
 # pipelined_on_device and sequence_on_device are not used here: they keep the names under which callers and tests ask this script
 # how it routes a subject
-from ukbb_cardiac_amd.sequence_run import SequenceRun, device_path, pipelined_on_device, seg_prefix, sequence_on_device   # noqa: E402,F401
+from ukbb_cardiac_amd.sequence_run import (SequenceRun, device_label_gzip_mode, device_path, pipelined_on_device, seg_prefix,   # noqa: E402,F401
+                                            sequence_on_device)
 from ukbb_cardiac_amd.shard import ClaimQueue, apply_cpu_set_from_env, default_device, shard_from_env   # noqa: E402
 
 
@@ -64,6 +66,11 @@ def define_flags():
                    'bf16 pieces per operand (UKBB_PREC_F32X3, include/ukbb_fcn.h; same labels, faster head).')
     fs.DEFINE_enum('label_gzip', 'small', list(nifti.LABEL_GZIP_MODES), 'Deflate of the label volumes: small = run-length tokens + dynamic Huffman '
                    '(typically below the size of zlib level 1, ~20x less CPU), fast = fixed Huffman (2-4x larger files), zlib = as nibabel. Same inflated bytes.')
+    fs.DEFINE_boolean('device_label_gzip', False, 'Sequence mode, pipelined loop (--device_preproc with --io_threads > 0, without --device_inflate): '
+                      'deflate the float64 label volume seg_{seq}.nii.gz on the GPU, with the code set of --label_gzip small | fast, and copy back the '
+                      'gzip member instead of the labels.  Same output files, byte for byte.  A subject the device encoder declines (more runs or more '
+                      'output than its buffers hold, noise-like labels) takes the host writer.  Ignored with --label_gzip zlib; the sequential loop '
+                      '(--io_threads 0, host pre-processing) and the --device_inflate rounds keep the host writer.')
     fs.DEFINE_string('output_csv', '', '--seq_name sa, sequence mode: also write the spreadsheet of short_axis/eval_ventricular_volume.py '
                      '(same columns, same arithmetic) from the per-frame class counts the GPU leaves behind -- no second pass over '
                      'seg_sa.nii.gz.  Subjects already segmented by an earlier run are measured from their files.')
@@ -142,6 +149,12 @@ def run(FLAGS, forward, log=print, engine=None):
                 log('  Saving segmentation ...')
                 nifti.save(pred, '{0}/{1}_{2}_{3}.nii.gz'.format(data_dir, pre, seq, fr), nim.affine,
                            nim.header['pixdim'])
+    if getattr(FLAGS, 'device_label_gzip', False):
+        pipelined = FLAGS.process_seq and not inflate and on_device and getattr(FLAGS, 'io_threads', 0) > 0
+        reason = device_label_gzip_mode(FLAGS)[1] if pipelined else \
+            'it takes effect in the pipelined sequence loop only (--device_preproc, --io_threads > 0, no --device_inflate)'
+        if reason:
+            log('--device_label_gzip ignored: %s' % reason)
     if FLAGS.process_seq:
         seq_run = _SequenceRun(FLAGS, engine, tables, queue, log, data_list)
         if inflate:

@@ -427,6 +427,49 @@ def load(path, alloc=None) -> NiftiImage:
     return NiftiImage(data, affine, pixdim, hdr)
 
 
+def _header_bytes(shape, affine, pixdim, out_dtype):
+    """The 348 header bytes save() writes for a volume of this shape stored as out_dtype."""
+    out_dtype = np.dtype(out_dtype)
+    key = out_dtype.newbyteorder('<').str[1:]
+    if key not in _CODES:
+        raise ValueError('cannot store dtype %s in NIfTI-1' % out_dtype)
+    affine = np.asarray(affine, dtype=np.float64)
+    if affine.shape != (4, 4):
+        raise ValueError('affine must be 4x4')
+    ndim = len(shape)
+    if not 1 <= ndim <= 7:
+        raise ValueError('NIfTI-1 stores 1 to 7 dimensions')
+    dim = [ndim] + list(shape) + [1] * (7 - ndim)
+    pd = np.ones(8, np.float32)
+    pd[1:4] = np.sqrt((affine[:3, :3] ** 2).sum(axis=0))
+    if pixdim is not None:
+        pd = np.asarray(pixdim, dtype=np.float32).copy()
+    hdr = bytearray(348)
+    struct.pack_into('<i', hdr, 0, 348)
+    struct.pack_into('<8h', hdr, 40, *dim)
+    struct.pack_into('<2h', hdr, 70, _CODES[key], out_dtype.itemsize * 8)
+    struct.pack_into('<8f', hdr, 76, *[float(v) for v in pd])
+    struct.pack_into('<3f', hdr, 108, 352.0, 1.0, 0.0)
+    hdr[123] = 10 if ndim >= 4 else 2                 # mm (+ seconds): informative only
+    struct.pack_into('<2h', hdr, 252, 0, 2)
+    struct.pack_into('<12f', hdr, 280, *[float(v) for v in affine[:3].ravel()])
+    hdr[344:348] = b'n+1\x00'
+    return hdr
+
+
+def header_prefix(shape, affine, pixdim=None, dtype=np.float64):
+    """The 352 bytes in front of the voxels in the file ``save(data, path, affine, pixdim, as_dtype=dtype)`` writes for data of this
+    shape: the NIfTI-1 header and its four extension bytes -- the prefix of ukbb_fcn_gzip_labels_mode / ukbb_fcn_gzip_labels_device."""
+    return bytes(_header_bytes(tuple(int(v) for v in shape), affine, pixdim, dtype)) + b'\x00\x00\x00\x00'
+
+
+def save_gzip_blob(blob, path):
+    """A ready-made gzip member (bytes, memoryview or uint8 array: what the device label encoder leaves) under ``path``, with the
+    atomic-file rules of save(): it appears under its name only when complete."""
+    with _AtomicFile(path) as f:
+        f.write(memoryview(np.ascontiguousarray(blob)) if isinstance(blob, np.ndarray) else blob)
+
+
 def save(img_or_data, path, affine=None, pixdim=None, as_dtype=None):
     """save(NiftiImage, path) or save(ndarray, path, affine[, pixdim]).  Writes the
     array's own dtype (the reference relies on that: float64 label volumes in
@@ -448,26 +491,7 @@ def save(img_or_data, path, affine=None, pixdim=None, as_dtype=None):
     key = out_dtype.newbyteorder('<').str[1:]
     if key not in _CODES:
         raise ValueError('cannot store dtype %s in NIfTI-1' % data.dtype)
-    affine = np.asarray(affine, dtype=np.float64)
-    if affine.shape != (4, 4):
-        raise ValueError('affine must be 4x4')
-    if not 1 <= data.ndim <= 7:
-        raise ValueError('NIfTI-1 stores 1 to 7 dimensions')
-    dim = [data.ndim] + list(data.shape) + [1] * (7 - data.ndim)
-    pd = np.ones(8, np.float32)
-    pd[1:4] = np.sqrt((affine[:3, :3] ** 2).sum(axis=0))
-    if pixdim is not None:
-        pd = np.asarray(pixdim, dtype=np.float32).copy()
-    hdr = bytearray(348)
-    struct.pack_into('<i', hdr, 0, 348)
-    struct.pack_into('<8h', hdr, 40, *dim)
-    struct.pack_into('<2h', hdr, 70, _CODES[key], out_dtype.itemsize * 8)
-    struct.pack_into('<8f', hdr, 76, *[float(v) for v in pd])
-    struct.pack_into('<3f', hdr, 108, 352.0, 1.0, 0.0)
-    hdr[123] = 10 if data.ndim >= 4 else 2            # mm (+ seconds): informative only
-    struct.pack_into('<2h', hdr, 252, 0, 2)
-    struct.pack_into('<12f', hdr, 280, *[float(v) for v in affine[:3].ravel()])
-    hdr[344:348] = b'n+1\x00'
+    hdr = _header_bytes(data.shape, affine, pixdim, out_dtype)
     if str(path).endswith('.gz') and _CODES[key] in (2, 4, 8, 16, 64):
         lab = _as_label_volume(data)
         if lab is not None and _save_labels_gz(lab, _CODES[key], bytes(hdr) + b'\x00\x00\x00\x00', path):

@@ -25,16 +25,20 @@ def seg_prefix(FLAGS):
     return 'seg4' if (FLAGS.seq_name == 'la_4ch' and FLAGS.seg4) else 'seg'
 
 
-def save_sequence_outputs(data_dir, pre, seq, affine, pixdim, pred, frames):
+def save_sequence_outputs(data_dir, pre, seq, affine, pixdim, pred, frames, blob=None):
     """The five files of deploy_network.py:136-151.  pred: (X,Y,Z,T) labels, stored as float64 (:92); frames: {'ED'|'ES':
-    (image frame, label frame)}."""
+    (image frame, label frame)}.  blob: seg_{seq}.nii.gz ready-made (the member the device encoder wrote: the bytes nifti.save
+    gives for pred), written in pred's place."""
     for fr, (img_fr, seg_fr) in frames.items():
         nifti.save(img_fr, '{0}/{1}_{2}.nii.gz'.format(data_dir, seq, fr), affine)
         nifti.save(seg_fr, '{0}/{1}_{2}_{3}.nii.gz'.format(data_dir, pre, seq, fr), affine)
     # seg_{seq}.nii.gz doubles as the 'already segmented, skip' marker (:66-67), so it is written LAST and -- like every
     # file nifti.save writes -- appears under its name only when complete (tmp file + os.replace): a worker killed
     # anywhere in here leaves a subject that the rerun segments again, never a half-written one that it skips.
-    nifti.save(pred, '{0}/{1}_{2}.nii.gz'.format(data_dir, pre, seq), affine, pixdim, as_dtype=np.float64)
+    if blob is not None:
+        nifti.save_gzip_blob(blob, '{0}/{1}_{2}.nii.gz'.format(data_dir, pre, seq))
+    else:
+        nifti.save(pred, '{0}/{1}_{2}.nii.gz'.format(data_dir, pre, seq), affine, pixdim, as_dtype=np.float64)
 
 
 def device_path(FLAGS, engine):
@@ -60,6 +64,20 @@ def pipelined_on_device(image):
     return image.ndim == 4 and device_pipeline.device_dtype_ok(image.dtype)
 
 
+def device_label_gzip_mode(FLAGS):
+    """pipelined: the code set --device_label_gzip gives the device encoder, or why the flag has no effect there:
+    ('small' | 'fast', None) or (None, reason); (None, None) without the flag.  deploy_network logs the reason."""
+    if not getattr(FLAGS, 'device_label_gzip', False):
+        return None, None
+    if not FLAGS.save_seg:
+        return None, 'no label volume is saved (--save_seg off)'
+    if not nifti.LABEL_FAST_PATH:
+        return None, "the run-length writer is switched off (nifti.LABEL_FAST_PATH), zlib's output is not what the device encoder writes"
+    if nifti.LABEL_GZIP_MODE not in ('small', 'fast'):
+        return None, '--label_gzip %s keeps the host writer' % nifti.LABEL_GZIP_MODE
+    return nifti.LABEL_GZIP_MODE, None
+
+
 class SequenceRun:
     """What the sequence-mode run of one worker shares.  ``run(loop)`` takes one of the three loops below to the end."""
     last_phases = {}                                    # for tools/bench_device_inflate.py: ``phases`` of the last completed run
@@ -70,7 +88,8 @@ class SequenceRun:
         self.processed, self.table_time = [], []
         self.readers = self.writers = None              # start_threads(); without writers a subject's files are written inline
         self.writes = []                                # futures of the writers
-        self.phases = {}                                # seconds of this thread by phase (inflate_rounds; writer_wait: run)
+        self.phases = {}                                # seconds of this thread by phase (inflate_rounds; writer_wait: run); pipelined with
+        #                                                 --device_label_gzip: subjects by label_gzip_device / label_gzip_fallback
 
     def start_threads(self):
         """The reader and writer pools of the overlapped loops, --io_threads each."""
@@ -118,13 +137,16 @@ class SequenceRun:
         yield from candidates(self.data_list, True)
         yield from candidates(self.queue.second_chance(), False)
 
-    def finish(self, item, nim, seg_time, labels, counts, stats, clip, frame, done=None, ed_es=None, announce=True):
+    def finish(self, item, nim, seg_time, labels, counts, stats, clip, frame, done=None, ed_es=None, announce=True, gz_blob=None,
+               label_frames=None):
         """Everything behind a subject's labels, once (deploy_network.py:118-151).  nim: its header (affine, pixdim); labels:
         (X,Y,Z,T) uint8 or float64; counts, stats: as LabelTables.record takes them; frame(k): image frame k, to be clipped to
         ``clip`` (lo, hi) -- the saved frames are the CLIPPED intensities (alias quirk) -- or clipped already
         (clip None); done(): called once the ED and ES frames have been copied out (the staging buffer goes back).  ed_es: the
         two frames where no counts exist to pick them from; announce=False: the caller has logged the three lines in front of the
-        segmentation as it went.  The claim is released behind the subject's last file, by whoever writes it."""
+        segmentation as it went.  gz_blob, label_frames: a subject whose label file was deflated on the device (labels None):
+        seg_{seq}.nii.gz ready-made, and label_frames(k_ed, k_es) -> its two uint8 label frames.  The claim is released behind the
+        subject's last file, by whoever writes it."""
         data, data_dir, image_name = item
         FLAGS, log = self.FLAGS, self.log
         if ed_es is None:
@@ -142,7 +164,8 @@ class SequenceRun:
         self.tables.record(data, data_dir, nim, counts, stats, log)
         if FLAGS.save_seg:
             log('  Saving segmentation ...')
-            frames = {fr: (frame(k), np.asarray(labels[:, :, :, k], np.float64)) for fr, k in (('ED', k_ed), ('ES', k_es))}
+            seg_frames = label_frames(k_ed, k_es) if labels is None else (labels[:, :, :, k_ed], labels[:, :, :, k_es])
+            frames = {fr: (frame(k), np.asarray(seg_fr, np.float64)) for (fr, k), seg_fr in zip((('ED', k_ed), ('ES', k_es)), seg_frames)}
             if clip is not None:
                 from .device_pipeline import clip_like_reference
                 frames = {fr: (clip_like_reference(img_fr, clip), seg_fr) for fr, (img_fr, seg_fr) in frames.items()}
@@ -155,7 +178,7 @@ class SequenceRun:
 
         def write_then_release():                       # uint8 labels are expanded to the float64 volume here, by nifti.save
             try:
-                save_sequence_outputs(data_dir, self.pre, self.seq, affine, pixdim, labels, frames)
+                save_sequence_outputs(data_dir, self.pre, self.seq, affine, pixdim, labels, frames, gz_blob)
             finally:
                 self.queue.done(data)                   # the claim outlives the subject's last file (seg_{seq}.nii.gz, written last)
         if self.writers is None:
@@ -211,6 +234,11 @@ class SequenceRun:
         FLAGS, tables = self.FLAGS, self.tables
         window = self.start_threads() + 1               # reads allowed to run ahead of the GPU thread
         depth = 3
+        # --device_label_gzip: the code set of --label_gzip on the device; 'zlib', the fast path switched off or nothing to save keep the
+        # host writer (deploy_network has logged which)
+        gz_mode = device_label_gzip_mode(FLAGS)[0]
+        if gz_mode:
+            self.phases.update(label_gzip_device=0, label_gzip_fallback=0)
         pipes = []                                      # the SubjectPipeline, once the first volume has sized it
         mk = threading.Lock()
 
@@ -218,7 +246,8 @@ class SequenceRun:
             if len(shape) == 4 and device_pipeline.device_dtype_ok(dt):
                 with mk:
                     if not pipes:                       # sized by the first volume; bigger ones fall back below
-                        pipes.append(SubjectPipeline(self.engine, shape, FLAGS.batch_slices, depth=depth, extra_inputs=window, stats=tables.statistics()))
+                        pipes.append(SubjectPipeline(self.engine, shape, FLAGS.batch_slices, depth=depth, extra_inputs=window, stats=tables.statistics(),
+                                                     device_label_gzip=gz_mode))
                 try:
                     return pipes[0].stage(shape, dt).array, SubjectPipeline.HEADROOM
                 except ValueError:
@@ -254,7 +283,10 @@ class SequenceRun:
         def collect():
             item, nim, t0 = inflight.popleft()
             res = pipes[0].collect()
-            self.finish(item, nim, time.time() - t0, res.labels, res.counts, res.stats, res.clip, lambda k: res.image[:, :, :, k], done=res.done)
+            if gz_mode:
+                self.phases['label_gzip_device' if res.gz_blob is not None else 'label_gzip_fallback'] += 1
+            self.finish(item, nim, time.time() - t0, res.labels, res.counts, res.stats, res.clip, lambda k: res.image[:, :, :, k], done=res.done,
+                        gz_blob=res.gz_blob, label_frames=res.label_frames)
 
         top_up()
         while ahead:
@@ -268,7 +300,7 @@ class SequenceRun:
             else:
                 if len(inflight) >= depth - 1:
                     collect()
-                pipes[0].submit(image, tables.subject_args(item[1], nim, self.log))
+                pipes[0].submit(image, tables.subject_args(item[1], nim, self.log), (nim.affine, nim.header['pixdim']) if gz_mode else None)
                 inflight.append((item, nim, time.time()))
             top_up()
         while inflight:
