@@ -184,7 +184,7 @@ def _same_cine(got, want, what):
 
 def _lstm_cines(eng, prec, pattern=None):
     """13 frames of 48 x 64 at time_step 1 and 2, and 5 < 9 frames: whole, then under the minimum scratch budget the host query reports
-    (chunks: lstm_tile_chunk_kernel and lstm_img), there twice -- the first call allocates the released buffers, the second finds
+    (chunks: the CHUNKED lstm_tile_kernel and lstm_img), there twice -- the first call allocates the released buffers, the second finds
     them poisoned with ``pattern``."""
     from ukbb_cardiac_amd import engine
     out = []

@@ -1295,6 +1295,33 @@ void cine_tables(int F, int T, int time_step, int weight_R, double weight_r, std
     }
 }
 
+// The device copy of those tables: map | order | wk | wsum laid into ONE aux buffer of the handle (8-byte aligned pieces), keyed by what
+// they were built from and uploaded, blocking, on the first call for that key.  `map` is the window -> frame table in the caller's layout.
+struct CineAux { const int *map; CineTable tb; };
+int cine_aux(DevBuf &buf, long long &have, long long key, const std::vector<int> &map, const std::vector<int> &order,
+             const std::vector<double> &wk, const std::vector<double> &wsum, hipStream_t s, CineAux &out) {
+    const size_t T = wk.size(), F = wsum.size();
+    const size_t b_map = map.size() * sizeof(int), b_ord = order.size() * sizeof(int);
+    const size_t off_ord = (b_map + 7) / 8 * 8, off_wk = (off_ord + b_ord + 7) / 8 * 8, off_ws = off_wk + T * sizeof(double);
+    const size_t total = off_ws + F * sizeof(double);
+    if (have != key) {
+        HIP_TRY(hipStreamSynchronize(s), UKBB_EDEVICE);                      // nothing in flight may still read the old tables
+        have = -1;                                                           // until every table is up
+        HIP_TRY(buf.ensure((total + 3) / 4), UKBB_ENOMEM);
+        char *aux0 = reinterpret_cast<char *>(buf.p);
+        HIP_TRY(hipMemcpy(aux0, map.data(), b_map, hipMemcpyHostToDevice), UKBB_EDEVICE);
+        HIP_TRY(hipMemcpy(aux0 + off_ord, order.data(), b_ord, hipMemcpyHostToDevice), UKBB_EDEVICE);
+        HIP_TRY(hipMemcpy(aux0 + off_wk, wk.data(), T * sizeof(double), hipMemcpyHostToDevice), UKBB_EDEVICE);
+        HIP_TRY(hipMemcpy(aux0 + off_ws, wsum.data(), F * sizeof(double), hipMemcpyHostToDevice), UKBB_EDEVICE);
+        have = key;
+    }
+    const char *aux = reinterpret_cast<const char *>(buf.p);
+    out.map = reinterpret_cast<const int *>(aux);
+    out.tb = CineTable{reinterpret_cast<const int *>(aux + off_ord), reinterpret_cast<const double *>(aux + off_wk),
+                       reinterpret_cast<const double *>(aux + off_ws), (int)F, (int)T};
+    return UKBB_OK;
+}
+
 // ---- Temporal-UNet (kind 3) --------------------------------------------------------------------------
 // n_seq windows of T frames through the 3-D plan: image n = window * T + t, outputs in the same [N][T] order
 int t3d_forward_seq(ukbb_fcn_handle *h, const float *image, int n_seq, int height, int width,
@@ -1344,38 +1371,25 @@ int t3d_forward_cine(ukbb_fcn_handle *h, const float *image, int F, int height, 
     std::vector<int> fmap((size_t)Wn * T);                                  // window-major: batch image (w - w0) * T + k reads frame fmap[w * T + k]
     for (int w = 0; w < Wn; ++w)
         for (int k = 0; k < T; ++k) fmap[(size_t)w * T + k] = map[(size_t)k * Wn + w];
-    const size_t b_map = fmap.size() * sizeof(int), b_ord = order.size() * sizeof(int);
-    const size_t off_ord = (b_map + 7) / 8 * 8, off_wk = (off_ord + b_ord + 7) / 8 * 8, off_ws = off_wk + T * sizeof(double);
-    const size_t total = off_ws + F * sizeof(double);
     long long wr_bits;
     memcpy(&wr_bits, &weight_r, sizeof wr_bits);
     const long long key = (((((long long)F << 8) | T) * 1000003ll + time_step) * 1000003ll) ^ wr_bits;
-    if (h->t3d_aux_key != key) {                                             // first call for this shape: upload (blocking)
-        HIP_TRY(hipStreamSynchronize(s), UKBB_EDEVICE);
-        HIP_TRY(h->t3d_aux.ensure((total + 3) / 4), UKBB_ENOMEM);
-        char *aux0 = reinterpret_cast<char *>(h->t3d_aux.p);
-        HIP_TRY(hipMemcpy(aux0, fmap.data(), b_map, hipMemcpyHostToDevice), UKBB_EDEVICE);
-        HIP_TRY(hipMemcpy(aux0 + off_ord, order.data(), b_ord, hipMemcpyHostToDevice), UKBB_EDEVICE);
-        HIP_TRY(hipMemcpy(aux0 + off_wk, wk.data(), T * sizeof(double), hipMemcpyHostToDevice), UKBB_EDEVICE);
-        HIP_TRY(hipMemcpy(aux0 + off_ws, wsum.data(), F * sizeof(double), hipMemcpyHostToDevice), UKBB_EDEVICE);
-        h->t3d_aux_key = key;
-    }
+    CineAux aux;
+    rc = cine_aux(h->t3d_aux, h->t3d_aux_key, key, fmap, order, wk, wsum, s, aux);
+    if (rc) return rc;
     if (h->t3d_probw.n < (size_t)cw * T * HW * C) HIP_TRY(hipStreamSynchronize(s), UKBB_EDEVICE);   // the old buffer may still be read
     HIP_TRY(h->t3d_probw.ensure((size_t)cw * T * HW * C), UKBB_ENOMEM);
-    const char *aux = reinterpret_cast<const char *>(h->t3d_aux.p);
-    const int *d_fmap = reinterpret_cast<const int *>(aux);
     for (int w0 = 0; w0 < Wn; w0 += cw) {
         const int nw = std::min(cw, Wn - w0);
-        h->t3d_map = d_fmap + (size_t)w0 * T;
+        h->t3d_map = aux.map + (size_t)w0 * T;
         rc = run_plan(h, image, nw * T, nullptr, h->t3d_probw.p, nullptr, s);
         h->t3d_map = nullptr;
         if (rc) return rc;
         T3dTileArgs ta{};
         ta.probw = h->t3d_probw.p;
-        ta.order = reinterpret_cast<const int *>(aux + off_ord);
-        ta.wk = reinterpret_cast<const double *>(aux + off_wk); ta.wsum = reinterpret_cast<const double *>(aux + off_ws);
+        ta.tb = aux.tb;
         ta.prob = prob; ta.pred = pred;
-        ta.F = F; ta.K = T; ta.HW = (int)HW; ta.C = C; ta.w0 = w0; ta.w1 = w0 + nw;
+        ta.HW = (int)HW; ta.C = C; ta.w0 = w0; ta.w1 = w0 + nw;
         ta.first = w0 == 0; ta.last = w0 + nw == Wn;
         hipError_t e = launch_t3d_tile(ta, s);
         if (e != hipSuccess) { set_err("tiling kernel launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
@@ -1502,25 +1516,13 @@ int ukbb_fcn_forward_cine(ukbb_fcn_handle *h, const float *image, int n_frames, 
         }
         map.swap(cmap);
     }
-    const size_t b_map = map.size() * sizeof(int), b_ord = order.size() * sizeof(int);
-    const size_t off_ord = (b_map + 7) / 8 * 8, off_wk = (off_ord + b_ord + 7) / 8 * 8, off_ws = off_wk + T * sizeof(double);
-    const size_t total = off_ws + F * sizeof(double);
     long long wr_bits;
     memcpy(&wr_bits, &weight_r, sizeof wr_bits);
     // cine tables: (F, T, time_step, weight_r) and the chunk plan
     const long long key = (((((long long)F << 8) | T) * 1000003ll + time_step) * 1000003ll) ^ wr_bits ^ (1ll << 62) ^ (pl.chunks > 1 ? (long long)Wc << 40 : 0);
-    if (h->lstm_aux_key != key) {                                            // first call for this shape: upload (blocking)
-        HIP_TRY(hipStreamSynchronize(s), UKBB_EDEVICE);
-        h->lstm_aux_key = -1;                                                // until every table is up
-        HIP_TRY(h->lstm_aux.ensure((total + 3) / 4), UKBB_ENOMEM);
-        char *aux0 = reinterpret_cast<char *>(h->lstm_aux.p);
-        HIP_TRY(hipMemcpy(aux0, map.data(), b_map, hipMemcpyHostToDevice), UKBB_EDEVICE);
-        HIP_TRY(hipMemcpy(aux0 + off_ord, order.data(), b_ord, hipMemcpyHostToDevice), UKBB_EDEVICE);
-        HIP_TRY(hipMemcpy(aux0 + off_wk, wk.data(), T * sizeof(double), hipMemcpyHostToDevice), UKBB_EDEVICE);
-        HIP_TRY(hipMemcpy(aux0 + off_ws, wsum.data(), F * sizeof(double), hipMemcpyHostToDevice), UKBB_EDEVICE);
-        h->lstm_aux_key = key;
-    }
-    char *aux = reinterpret_cast<char *>(h->lstm_aux.p);
+    CineAux aux;
+    rc = cine_aux(h->lstm_aux, h->lstm_aux_key, key, map, order, wk, wsum, s, aux);
+    if (rc) return rc;
     const int NHID = h->arch.same_dim;
     const size_t esz = h->plan_bfio ? 2 : 4;
     auto at = [esz](const float *p, size_t elems) { return reinterpret_cast<const float *>(reinterpret_cast<const char *>(p) + elems * esz); };
@@ -1537,22 +1539,20 @@ int ukbb_fcn_forward_cine(ukbb_fcn_handle *h, const float *image, int n_frames, 
         }
         rc = run_plan(h, frames, R, nullptr, nullptr, nullptr, s);          // each frame's U-Net features, once per chunk that reads it
         if (rc) return rc;
-        const int *d_map = reinterpret_cast<const int *>(aux) + (size_t)T * w0;
+        const int *d_map = aux.map + (size_t)T * w0;
         rc = run_bilstm(h, h->act[h->feat_buf]->p, R, d_map, nw, height, width, s);
         if (rc) return rc;
-        LstmTileChunkArgs ca{};
-        LstmTileArgs &ta = ca.t;
+        LstmTileArgs ta{};
         ta.k_stride = (long long)nw * HW * NHID;
         ta.h_bf16 = h->plan_bfio ? 1 : 0;
         ta.hf = h->lstm_hall.p; ta.hb = at(h->lstm_hall.p, (size_t)T * ta.k_stride);
         ta.h1f = h->lstm_h1.p; ta.h1b = at(h->lstm_h1.p, (size_t)R * HW * NHID);
         ta.map_first = d_map; ta.map_last = d_map + (size_t)(T - 1) * nw;
         ta.w_out = dev_ptr(h, "lstm_out/w"); ta.b_out = dev_ptr(h, "lstm_out/bias");
-        ta.order = reinterpret_cast<const int *>(aux + off_ord);
-        ta.wk = reinterpret_cast<const double *>(aux + off_wk); ta.wsum = reinterpret_cast<const double *>(aux + off_ws);
-        ta.prob = prob; ta.pred = pred; ta.F = F; ta.K = T; ta.Wn = nw; ta.HW = (int)HW; ta.C = C;
-        ca.w0 = w0; ca.w1 = w0 + nw; ca.first = w0 == 0; ca.last = w0 + nw == Wn;
-        hipError_t e = pl.chunks > 1 ? launch_lstm_tile_chunk(ca, s) : launch_lstm_tile(ta, s);
+        ta.tb = aux.tb;
+        ta.prob = prob; ta.pred = pred; ta.Wn = nw; ta.HW = (int)HW; ta.C = C;
+        ta.w0 = w0; ta.w1 = w0 + nw; ta.first = w0 == 0; ta.last = w0 + nw == Wn;
+        hipError_t e = launch_lstm_tile(ta, s);
         if (e != hipSuccess) { set_err("tiling kernel launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
     }
     return UKBB_OK;

@@ -76,6 +76,68 @@ __device__ __forceinline__ int softmax_argmax_opt(const float (&lg)[NCLS], bool 
     return softmax_argmax<NCLS>(lg, nullptr);
 }
 
+// ---- the weighted circular tiling of deploy_network_ao.py:176-183, one body for the UNet-LSTM and the Temporal-UNet cines ----
+struct CineTable {          // the per-cine tables on the device (engine.cpp cine_aux)
+    const int *order;       // [F][K] for frame f: the <= K contributing (window w, position k) pairs packed w*K + k, ascending w (the way the
+                            //        reference's loop over t adds them), -1 ends the list
+    const double *wk;       // [K] window weights
+    const double *wsum;     // [F] accumulated weight per frame
+    int F, K;
+};
+// One (frame f, pixel) of prob / pred, element `id` of the [F][HW] maps:
+//   prob = (sum over the frame's terms, in list order, of p(window w, position k) * wk[k]) / wsum[f], pred = its lowest-index argmax.
+// term(w, k, p) supplies a term's NCLS probabilities.  Reference arithmetic: prob is float32, `prob[..., idx] += prob_idx * w` runs in
+// float64 and is cast back per addition; `prob /= weight` likewise.  A frame no window reaches (time_step > window) has wsum = 0:
+// 0/0 = NaN and argmax 0, as numpy gives the reference.
+// CHUNKED: this launch adds the terms of the windows [w0, w1) only.  A frame's terms come in ascending window order, chunks run in
+// ascending order, and the accumulator is rounded to float32 after every term -- so carrying that float32 in prob between chunks performs
+// the same sequence of float64-widened adds.  The first chunk starts from 0, the last divides and takes the argmax; a frame the chunk
+// does not reach is not touched otherwise.  Not CHUNKED: the whole list in one pass, prob is written only.
+template <int NCLS, bool CHUNKED, class Term>
+__device__ __forceinline__ void cine_tile_pixel(const CineTable &tb, int f, int w0, int w1, bool first, bool last,
+                                                float *prob, int32_t *pred, long long id, Term &&term) {
+    float acc[NCLS];
+    float *o = prob + id * NCLS;
+    bool open = !CHUNKED || first;                                       // acc holds the running sum (else it still lies in prob)
+    auto resume = [&] {
+        if (!open) {
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c) acc[c] = o[c];
+            open = true;
+        }
+    };
+#pragma unroll
+    for (int c = 0; c < NCLS; ++c) acc[c] = 0.f;
+    for (int j = 0; j < tb.K; ++j) {
+        const int wk_ = tb.order[f * tb.K + j];
+        if (wk_ < 0) break;                                              // fewer than K windows reach this frame (time_step > 1, F < K)
+        const int wi = wk_ / tb.K, k = wk_ - wi * tb.K;
+        if constexpr (CHUNKED) {
+            if (wi < w0) continue;                                       // an earlier chunk's window (already added)
+            if (wi >= w1) break;                                         // a later chunk's
+            resume();
+        }
+        float p[NCLS];
+        term(wi, k, p);
+        const double wt = tb.wk[k];
+#pragma unroll
+        for (int c = 0; c < NCLS; ++c) acc[c] = (float)((double)acc[c] + (double)p[c] * wt);
+    }
+    if (!CHUNKED || last) {
+        if constexpr (CHUNKED) resume();
+        const double ws = tb.wsum[f];
+        int best = 0;
+#pragma unroll
+        for (int c = 0; c < NCLS; ++c) acc[c] = (float)((double)acc[c] / ws);
+#pragma unroll
+        for (int c = 1; c < NCLS; ++c) if (acc[c] > acc[best]) best = c;
+        if (pred) pred[id] = best;
+    }
+    if (!open) return;
+#pragma unroll
+    for (int c = 0; c < NCLS; ++c) o[c] = acc[c];
+}
+
 // ---------------------------------------------------------------------------
 // Generic implicit-GEMM convolution (3x3 or 1x1, stride 1 or 2) + bias + ReLU
 // on the f32 MFMA pipes.  NHWC activations, weights pre-packed in MFMA
@@ -339,24 +401,18 @@ struct LstmTileArgs {       // per-(window, step) outputs + the weighted tiling 
     const int *map_first, *map_last;   // [Wn]: frame of window w at step 0 / at step K-1
     long long k_stride;     // floats between steps in hf / hb
     const float *w_out, *b_out;
-    const int *order;       // [F][K] for frame f: the <= K contributing (window w, position k) pairs packed w*K + k (-1 ends the list),
-                            //        sorted the way the reference's loop over t adds them
-    const double *wk;       // [K] window weights
-    const double *wsum;     // [F] accumulated weight per frame
+    CineTable tb;           // of the whole cine
     float *prob;            // [F][HW][C]
     int32_t *pred;          // [F][HW]
-    int F, K, Wn, HW, C;
+    int Wn, HW, C;
     int h_bf16;             // 1: hf / hb / h1f / h1b hold bf16 (k_stride still counts elements)
-};
-hipError_t launch_lstm_tile(const LstmTileArgs &a, hipStream_t s);
-
-struct LstmTileChunkArgs {  // the same for the windows [w0, w1) of a cine that runs in chunks (forward_cine under a scratch budget)
-    LstmTileArgs t;         // hf / hb / map_first / map_last hold the CHUNK's windows (index w - w0, t.Wn = w1 - w0, t.k_stride = (w1 - w0) * HW * NH),
-                            // h1f / h1b the chunk's frame run (map_first / map_last give run-local frames); order / wk / wsum / prob / pred / F: the whole cine
+    // The windows [w0, w1) of the cine, Wn = w1 - w0: all of them (first = last = 1), or one chunk of a cine that runs in chunks (forward_cine under a
+    // scratch budget).  hf / hb / map_first / map_last then hold the CHUNK's windows (index w - w0, k_stride = (w1 - w0) * HW * NH), h1f / h1b the chunk's
+    // frame run (map_first / map_last give run-local frames); tb / prob / pred: the whole cine
     int w0, w1;
     int first, last;        // first chunk: start from 0; between chunks prob is the float32 accumulator; last chunk: prob /= weight, argmax
 };
-hipError_t launch_lstm_tile_chunk(const LstmTileChunkArgs &a, hipStream_t s);
+hipError_t launch_lstm_tile(const LstmTileArgs &a, hipStream_t s);
 
 // ---- 3-D convolutions of the aortic Temporal-UNet (network_ao.py:67-114), kernels_conv3d.hip ----
 struct Conv3dPhase {        // one sub-pixel phase of a transposed conv (the whole conv: one phase at (0, 0))
@@ -393,12 +449,10 @@ hipError_t launch_conv3d_first(const Conv3dFirstArgs &a, hipStream_t s);
 
 struct T3dTileArgs {        // weighted circular tiling (deploy_network_ao.py:176-183) of the windows [w0, w1) of a cine
     const float *probw;     // [(w1 - w0) * K][HW][C]: softmax of each window frame
-    const int *order;       // [F][K]: contributing (window w, position k) pairs, packed w*K + k, ascending w, -1 ends the list
-    const double *wk;       // [K] window weights
-    const double *wsum;     // [F] accumulated weight per frame
+    CineTable tb;           // of the whole cine
     float *prob;            // [F][HW][C]: the accumulator between chunks, the result after the last
     int32_t *pred;          // [F][HW] (last chunk)
-    int F, K, HW, C, w0, w1;
+    int HW, C, w0, w1;
     int first, last;        // first chunk: start from 0; last chunk: prob /= weight, argmax
 };
 hipError_t launch_t3d_tile(const T3dTileArgs &a, hipStream_t s);

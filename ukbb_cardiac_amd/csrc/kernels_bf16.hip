@@ -13,28 +13,13 @@
 // Fragment layouts, packed weights (pack_conv_weights_bf16, one Cout block of 32 rows of which 16 are real), rounding and
 // the epilogue arithmetic are those of conv_mfma_kernel<..., BFIO, 2>: results are bit-identical to that kernel's.
 #include "kernels.h"
+#include "device_prims.h"
 
 #include <type_traits>
 
 namespace ukbb {
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ f32x16 mfma_bf16(const f32x4 &a, const f32x4 &b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
-    const __bf16 l = (__bf16)lo, h = (__bf16)hi;       // RNE; v_cvt_pk_bf16_f32
-    return (unsigned)__builtin_bit_cast(unsigned short, l) | ((unsigned)__builtin_bit_cast(unsigned short, h) << 16);
-}
-template <int N, int I = 0, class F>
-__device__ __forceinline__ void unroll_steps(F &&f) {
-    if constexpr (I < N) { f(std::integral_constant<int, I>{}); unroll_steps<N, I + 1>(f); }
-}
 
 constexpr int XS = 12;                                  // dwords per staged halo pixel: 16 bf16 channels + 4 pad
 constexpr int WSLAB = 9 * 64 * 4;                       // packed weights of the one Cout block: 9 taps x 64 lanes x 4 dwords
@@ -152,7 +137,7 @@ __global__ __launch_bounds__(256, 2) void conv16_logits_pk_kernel(const ConvArgs
                 for (int pb = 0; pb < PBW; ++pb) bv[set][pb] = *reinterpret_cast<const f32x4 *>(xs + lbase[pb] + (kh * IW + kw) * XS);
             };
             fetch(std::integral_constant<int, 0>{}, 0);
-            unroll_steps<9>([&](auto tc) {
+            unroll<9>([&](auto tc) {
                 constexpr int t = decltype(tc)::value;
                 if constexpr (t + 1 < 9) fetch(std::integral_constant<int, t + 1>{}, (t + 1) & 1);
                 __builtin_amdgcn_sched_barrier(0);

@@ -21,6 +21,7 @@
 // 4-8 MFMAs the matrix pipe is the only bound (r01 PMC: the earlier planar/ds_read_b32
 // layout spent 44 % of its LDS cycles in bank conflicts, profiles/r01_pmc_summary_head2.csv).
 #include "kernels.h"
+#include "device_prims.h"
 
 #include <cstdlib>
 #include <algorithm>
@@ -30,17 +31,6 @@
 #include <type_traits>
 
 namespace ukbb {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// ReLU as one v_max_i32 on the bit pattern (fmaxf on an MFMA result compiles to two v_max_f32).
-__device__ __forceinline__ float relu_bits(float x) {
-    const int b = __builtin_bit_cast(int, x);
-    return __builtin_bit_cast(float, b > 0 ? b : 0);
-}
 
 template <int MB> struct Mfma;
 template <> struct Mfma<32> {
@@ -59,20 +49,6 @@ template <> struct Mfma<16> {
         return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
     }
 };
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-// bf16 inputs, fp32 accumulate: one v_mfma_f32_32x32x16_bf16 covers a whole KC = 16 chunk of a tap.
-// Lane (m = lane & 31, h = lane >> 5) supplies A[m][k = 8h..8h+7] and B[k = 8h..8h+7][m] as 8 bf16
-// (4 dwords); the accumulator layout is the same as the f32 32x32 form.
-__device__ __forceinline__ f32x16 mfma_bf16(const f32x4 &a, const f32x4 &b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
-__device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
-    const __bf16 l = (__bf16)lo, h = (__bf16)hi;       // RNE; hipcc emits v_cvt_pk_bf16_f32
-    return (unsigned)__builtin_bit_cast(unsigned short, l) | ((unsigned)__builtin_bit_cast(unsigned short, h) << 16);
-}
 
 __host__ __device__ constexpr int xs_stride(int kc) {
     // floats per staged halo pixel: KC channels + 4 pad, so the 16-byte reads of the 16 lanes
@@ -109,15 +85,6 @@ template <> struct VecLoad<8> {
     static __device__ __forceinline__ void ld(const float *p, float *d) {
         VecLoad<4>::ld(p, d); VecLoad<4>::ld(p + 4, d + 4); }
 };
-
-// compile-time loop: f(integral_constant<int, 0>) ... f(integral_constant<int, N-1>)
-template <int N, int I = 0, class F>
-__device__ __forceinline__ void unroll_taps(F &&f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        unroll_taps<N, I + 1>(f);
-    }
-}
 
 // BF = true: bf16 operands (activations converted while staging, weights pre-converted on the host),
 // fp32 accumulation; requires MB = 32, KC = 16.  LDS then holds [halo px][8 dwords + 4 pad] and
@@ -340,7 +307,7 @@ __global__ __launch_bounds__(256, conv_min_waves(KS, STRIDE, MB, TH, TW, KC, WM,
                     VecLoad<KSTEPS>::ld(xs + lbase[pb] + (kh_ * IW + kw_) * XS, bv[SET][pb]);      \
             }
             UKBB_LOAD_TAP(0, 0)
-            unroll_taps<KS2>([&](auto tc) {
+            unroll<KS2>([&](auto tc) {
                 constexpr int t = decltype(tc)::value;
                 if constexpr (t + 1 < KS2) UKBB_LOAD_TAP(t + 1, (t + 1) & 1)
                 // Pin the software pipeline: without the barriers hipcc sinks the reads of tap
@@ -1042,7 +1009,7 @@ __global__ __launch_bounds__(512, WINO ? 4 : 2) void conv_pc_kernel(const ConvAr
             __syncthreads();                            // barrier #s: buffer s&1 holds this item's halo tile
             const float *xs = xs_l + (s & 1) * BUF;
             f32x4 acc[16];
-            unroll_taps<2>([&](auto hc) {
+            unroll<2>([&](auto hc) {
                 constexpr int H = decltype(hc)::value;
                 f32x2 d[4][4];
 #pragma unroll
@@ -1195,7 +1162,7 @@ __global__ __launch_bounds__(512, WINO ? 4 : 2) void conv_pc_kernel(const ConvAr
                 }
 #endif
                 UKBB_LOAD_TAP(0, 0)
-                unroll_taps<KS2>([&](auto tc) {
+                unroll<KS2>([&](auto tc) {
                     constexpr int t = decltype(tc)::value;
                     if constexpr (t + 1 < KS2) UKBB_LOAD_TAP(t + 1, (t + 1) & 1)
                     __builtin_amdgcn_sched_barrier(0);

@@ -24,11 +24,9 @@
 //                        reference's order and arithmetic (float32 accumulator updated through float64), as
 //                        kernels_lstm.hip lstm_tile_kernel does; prob /= weight and argmax behind the last chunk.
 #include "kernels.h"
+#include "device_prims.h"
 
 namespace ukbb {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -155,38 +153,18 @@ __global__ __launch_bounds__(256) void conv3d_first_kernel(const Conv3dFirstArgs
     }
 }
 
+// a term of the tiling (kernels.h cine_tile_pixel) is the stored softmax of a window frame
 template <int NCLS>
 __global__ __launch_bounds__(256) void t3d_tile_kernel(const T3dTileArgs a) {
-    const long long total = (long long)a.F * a.HW;
+    const long long total = (long long)a.tb.F * a.HW;
     for (long long id = (long long)blockIdx.x * 256 + threadIdx.x; id < total; id += (long long)gridDim.x * 256) {
         const int f = (int)(id / a.HW);
         const long long pix = id - (long long)f * a.HW;
-        float acc[NCLS];
-        float *o = a.prob + id * NCLS;
+        cine_tile_pixel<NCLS, true>(a.tb, f, a.w0, a.w1, a.first, a.last, a.prob, a.pred, id, [&](int wi, int k, float (&p)[NCLS]) {
+            const float *src = a.probw + (((long long)(wi - a.w0) * a.tb.K + k) * a.HW + pix) * NCLS;
 #pragma unroll
-        for (int c = 0; c < NCLS; ++c) acc[c] = a.first ? 0.f : o[c];
-        for (int j = 0; j < a.K; ++j) {
-            const int wk_ = a.order[f * a.K + j];
-            if (wk_ < 0) break;                                          // fewer than K windows reach this frame
-            const int wi = wk_ / a.K, k = wk_ - wi * a.K;
-            if (wi < a.w0) continue;                                     // an earlier chunk's window (already added)
-            if (wi >= a.w1) break;                                       // a later chunk's (the list ascends in window order)
-            const float *p = a.probw + (((long long)(wi - a.w0) * a.K + k) * a.HW + pix) * NCLS;
-            const double wt = a.wk[k];
-#pragma unroll
-            for (int c = 0; c < NCLS; ++c) acc[c] = (float)((double)acc[c] + (double)p[c] * wt);
-        }
-        if (a.last) {
-            const double ws = a.wsum[f];
-            int best = 0;
-#pragma unroll
-            for (int c = 0; c < NCLS; ++c) acc[c] = (float)((double)acc[c] / ws);
-#pragma unroll
-            for (int c = 1; c < NCLS; ++c) if (acc[c] > acc[best]) best = c;
-            if (a.pred) a.pred[id] = best;
-        }
-#pragma unroll
-        for (int c = 0; c < NCLS; ++c) o[c] = acc[c];
+            for (int c = 0; c < NCLS; ++c) p[c] = src[c];
+        });
     }
 }
 
@@ -214,17 +192,12 @@ hipError_t launch_conv3d_first(const Conv3dFirstArgs &a, hipStream_t s) {
 }
 
 hipError_t launch_t3d_tile(const T3dTileArgs &a, hipStream_t s) {
-    const long long total = (long long)a.F * a.HW;
+    const long long total = (long long)a.tb.F * a.HW;
     long long blocks = (total + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
     const dim3 g((unsigned)blocks), t(256);
-    switch (a.C) {
-        case 2: hipLaunchKernelGGL((t3d_tile_kernel<2>), g, t, 0, s, a); break;
-        case 3: hipLaunchKernelGGL((t3d_tile_kernel<3>), g, t, 0, s, a); break;
-        case 4: hipLaunchKernelGGL((t3d_tile_kernel<4>), g, t, 0, s, a); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    const bool ok = with_classes(a.C, [&](auto nc) { hipLaunchKernelGGL((t3d_tile_kernel<decltype(nc)::value>), g, t, 0, s, a); });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 // w: folded weights [3 dt][ny][nx][cin][cout] of ONE phase (dt = time tap - 1, taps already in kernel order);

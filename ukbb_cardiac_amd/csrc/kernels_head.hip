@@ -24,6 +24,7 @@
 // layer's B operand: k-step r supplies rows rowmap(r,0) on lanes 0-31 and rowmap(r,1) on
 // lanes 32-63, and the weights are packed on the host in that k order.
 #include "kernels.h"
+#include "device_prims.h"
 
 #include <atomic>
 #include <cstdio>
@@ -34,22 +35,12 @@
 
 namespace ukbb {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 __host__ __device__ __forceinline__ constexpr int rowmap(int r, int g) {
     // row of a 32x32 f32 MFMA result held in register r by lane half g
     return (r & 3) + 8 * (r >> 2) + 4 * g;
 }
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) {
-    f32x2 r; asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r;
-}
 #define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
-
-__device__ __forceinline__ f32x4 ldg4(const float *p) { return *reinterpret_cast<const f32x4 *>(p); }
 
 // Accumulator tile pre-loaded with the bias of its 16 rows: acc[4j+i] = bias[8j + 4g + i].
 // Used as the C operand of the first MFMA of a chain, so the bias add costs no VALU op.
@@ -57,25 +48,16 @@ __device__ __forceinline__ f32x16 bias_tile(const float *bias, int g) {
     f32x16 acc;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const f32x4 b = ldg4(bias + 8 * j + 4 * g);
+        const f32x4 b = ld4(bias + 8 * j + 4 * g);
 #pragma unroll
         for (int i = 0; i < 4; ++i) acc[4 * j + i] = b[i];
     }
     return acc;
 }
 
-// ReLU as one integer max: for IEEE floats max_i32(bits(x), 0) is x for x >= +0 and +0 for anything
-// with the sign bit set.  fmaxf() on an MFMA result compiles to two instructions (a canonicalising
-// max and the max), and on gfx950 every VALU instruction takes issue time away from the fp32 MFMA
-// stream (tools/mfma_coissue.hip).  Deliberately not inline asm: the compiler must see a VALU read of
-// the accumulator to insert the MFMA -> VALU wait states.
-__device__ __forceinline__ float relu1(float x) {
-    const int b = __builtin_bit_cast(int, x);
-    return __builtin_bit_cast(float, b > 0 ? b : 0);
-}
 __device__ __forceinline__ void relu16(f32x16 &acc) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = relu1(acc[r]);
+    for (int r = 0; r < 16; ++r) acc[r] = relu_bits(acc[r]);
 }
 
 // D0/D1 (two Cout blocks of 32) += W[64][32 rows of X] * X, X given as an accumulator tile.
@@ -83,8 +65,8 @@ __device__ __forceinline__ void relu16(f32x16 &acc) {
 __device__ __forceinline__ void chain_32to64(const float *wp, int lane, const f32x16 &X, f32x16 &D0, f32x16 &D1) {
 #pragma unroll
     for (int q4 = 0; q4 < 4; ++q4) {
-        const f32x4 wa = ldg4(wp + ((0 * 4 + q4) * 64 + lane) * 4);
-        const f32x4 wb = ldg4(wp + ((1 * 4 + q4) * 64 + lane) * 4);
+        const f32x4 wa = ld4(wp + ((0 * 4 + q4) * 64 + lane) * 4);
+        const f32x4 wb = ld4(wp + ((1 * 4 + q4) * 64 + lane) * 4);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             D0 = MFMA32(wa[i], X[4 * q4 + i], D0);
@@ -97,7 +79,7 @@ __device__ __forceinline__ void chain_32to64(const float *wp, int lane, const f3
 __device__ __forceinline__ void chain_32to32(const float *wp, int lane, const f32x16 &X, f32x16 &D) {
 #pragma unroll
     for (int q4 = 0; q4 < 4; ++q4) {
-        const f32x4 w = ldg4(wp + (q4 * 64 + lane) * 4);
+        const f32x4 w = ld4(wp + (q4 * 64 + lane) * 4);
 #pragma unroll
         for (int i = 0; i < 4; ++i) D = MFMA32(w[i], X[4 * q4 + i], D);
     }
@@ -127,10 +109,10 @@ __device__ __forceinline__ void sqg_body(const SqgArgs &a, int vblock, int vgrid
         for (int j0 = 0; j0 < CIN / 8; j0 += XG) {
             f32x4 xv[XG];
 #pragma unroll
-            for (int j = 0; j < XG; ++j) xv[j] = ldg4(xp + 8 * (j0 + j));
+            for (int j = 0; j < XG; ++j) xv[j] = ld4(xp + 8 * (j0 + j));
 #pragma unroll
             for (int j = 0; j < XG; ++j) {
-                const f32x4 wv = ldg4(a.w_s + ((j0 + j) * 64 + lane) * 4);
+                const f32x4 wv = ld4(a.w_s + ((j0 + j) * 64 + lane) * 4);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) S = MFMA32(wv[i], xv[j][i], S);
             }
@@ -178,11 +160,11 @@ __device__ __forceinline__ void sqg_stream_body(const SqgArgs &a, int vblock, in
     const long long step = (long long)vgrid * 4;
     f32x4 ws[NJ], wa[4], wb[4];
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) ws[j] = ldg4(a.w_s + (j * 64 + lane) * 4);
+    for (int j = 0; j < NJ; ++j) ws[j] = ld4(a.w_s + (j * 64 + lane) * 4);
 #pragma unroll
     for (int q4 = 0; q4 < 4; ++q4) {
-        wa[q4] = ldg4(a.w_g + ((0 * 4 + q4) * 64 + lane) * 4);
-        wb[q4] = ldg4(a.w_g + ((1 * 4 + q4) * 64 + lane) * 4);
+        wa[q4] = ld4(a.w_g + ((0 * 4 + q4) * 64 + lane) * 4);
+        wb[q4] = ld4(a.w_g + ((1 * 4 + q4) * 64 + lane) * 4);
     }
     const f32x16 bias = bias_tile(a.b_s, g);
     constexpr int RS = CIN + 4;                         // LDS row stride (floats): b128-aligned, the strided read is conflict-free
@@ -193,13 +175,13 @@ __device__ __forceinline__ void sqg_stream_body(const SqgArgs &a, int vblock, in
 #pragma unroll
             for (int t = 0; t < NJ; ++t) {
                 const long long f = blk * (32 * (CIN / 4)) + t * 64 + lane;
-                dst[t] = ldg4(a.x + 4 * (f < qlast ? f : qlast));
+                dst[t] = ld4(a.x + 4 * (f < qlast ? f : qlast));
             }
         } else {
             const long long q = blk * 32 + p;
             const float *xp = a.x + (q < a.npix ? q : a.npix - 1) * CIN + 4 * g;
 #pragma unroll
-            for (int j = 0; j < NJ; ++j) dst[j] = ldg4(xp + 8 * j);
+            for (int j = 0; j < NJ; ++j) dst[j] = ld4(xp + 8 * j);
         }
     };
     long long blk = (long long)vblock * 4 + (threadIdx.x >> 6);
@@ -387,7 +369,6 @@ constexpr int HEADPC_LDS_FLOATS = HeadLds<false>::FLOATS;
 constexpr int HEADPC_X3_LDS_FLOATS = HeadLds<true>::FLOATS;
 static_assert(HEADPC_X3_LDS_FLOATS * 4 <= 160 * 1024, "head kernel LDS");
 
-__device__ __forceinline__ f32x4 lds4(const float *p) { return *reinterpret_cast<const f32x4 *>(p); }
 // An LDS pointer the optimiser cannot see through: reads at compile-time distances from it become one base register plus the
 // instruction's immediate offset, instead of one loop-invariant address register per distance (r11: 16 of them in the consumer loop)
 typedef const __attribute__((address_space(3))) float lds_cf;
@@ -395,16 +376,11 @@ typedef const __attribute__((address_space(3))) f32x4 lds_cf4;
 __device__ __forceinline__ lds_cf *lds_opaque(const float *p) { lds_cf *q = (lds_cf *)p; asm volatile("" : "+v"(q)); return q; }
 __device__ __forceinline__ f32x4 lds4(lds_cf *p) { return *(lds_cf4 *)p; }
 
-template <int N, int I = 0, class F>
-__device__ __forceinline__ void unroll_n(F &&f) {
-    if constexpr (I < N) { f(std::integral_constant<int, I>{}); unroll_n<N, I + 1>(f); }
-}
-
 __device__ __forceinline__ f32x16 bias_tile_lds(const float *bias, int g) {
     f32x16 acc;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const f32x4 b = lds4(bias + 8 * j + 4 * g);
+        const f32x4 b = ld4(bias + 8 * j + 4 * g);
 #pragma unroll
         for (int i = 0; i < 4; ++i) acc[4 * j + i] = b[i];
     }
@@ -414,8 +390,8 @@ __device__ __forceinline__ f32x16 bias_tile_lds(const float *bias, int g) {
 __device__ __forceinline__ void chain_32to64_lds(const float *wp, int lane, const f32x16 &X, f32x16 &D0, f32x16 &D1) {
 #pragma unroll
     for (int q4 = 0; q4 < 4; ++q4) {
-        const f32x4 wa = lds4(wp + ((0 * 4 + q4) * 64 + lane) * 4);
-        const f32x4 wb = lds4(wp + ((1 * 4 + q4) * 64 + lane) * 4);
+        const f32x4 wa = ld4(wp + ((0 * 4 + q4) * 64 + lane) * 4);
+        const f32x4 wb = ld4(wp + ((1 * 4 + q4) * 64 + lane) * 4);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             D0 = MFMA32(wa[i], X[4 * q4 + i], D0);
@@ -428,20 +404,12 @@ __device__ __forceinline__ void chain_32to64_lds(const float *wp, int lane, cons
 // x = h + m + l with h = bf16(x), m = bf16(x - h), l = x - h - m (all exact in fp32); W likewise on the host.  The six partial
 // products that matter (hh, hm, mh, mm, hl, lh) run as v_mfma_f32_32x32x16_bf16 with fp32 accumulation; what is dropped is
 // below 2^-24 of |x||w| per product (profiles/r02_notes.md section 11).
-typedef __bf16 hbf16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ unsigned pk_bf16(float lo, float hi) {
-    const __bf16 l = (__bf16)lo, h = (__bf16)hi;       // RNE; v_cvt_pk_bf16_f32
-    return (unsigned)__builtin_bit_cast(unsigned short, l) | ((unsigned)__builtin_bit_cast(unsigned short, h) << 16);
-}
 __device__ __forceinline__ void split_pair(float x0, float x1, unsigned &h, unsigned &m, unsigned &l) {
-    h = pk_bf16(x0, x1);
+    h = pack_bf16x2(x0, x1);
     const float r0 = x0 - __builtin_bit_cast(float, h << 16), r1 = x1 - __builtin_bit_cast(float, h & 0xffff0000u);
-    m = pk_bf16(r0, r1);
+    m = pack_bf16x2(r0, r1);
     const float q0 = r0 - __builtin_bit_cast(float, m << 16), q1 = r1 - __builtin_bit_cast(float, m & 0xffff0000u);
-    l = pk_bf16(q0, q1);
-}
-__device__ __forceinline__ f32x16 mfma_b16(const u32x4 &a, const u32x4 &b, const f32x16 &c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(hbf16x8, a), __builtin_bit_cast(hbf16x8, b), c, 0, 0, 0);
+    l = pack_bf16x2(q0, q1);
 }
 
 // ---- separable gather (r08): which x-interpolated window rows a run of four output rows reads ---------------------------------
@@ -496,8 +464,8 @@ __device__ __forceinline__ void head_consumer_deferred(const HeadArgs &a, float 
     size_t qnext = 0;                                   // and its pixel index: pixel_of runs once per stage
     if (nstages > 0) {
         qnext = pixel_of(0);
-        xv0 = ldg4(a.conv0 + qnext * 16 + 4 * g);
-        xv1 = ldg4(a.conv0 + qnext * 16 + 8 + 4 * g);
+        xv0 = ld4(a.conv0 + qnext * 16 + 4 * g);
+        xv1 = ld4(a.conv0 + qnext * 16 + 8 + 4 * g);
     }
     __syncthreads();                                    // barrier X
 #ifdef UKBB_DIAG
@@ -538,7 +506,7 @@ __device__ __forceinline__ void head_consumer_deferred(const HeadArgs &a, float 
     size_t qd = 0;
     auto relu_n = [&](f32x16 &Q, auto r0c, auto nc) {
 #pragma unroll
-        for (int r = 0; r < decltype(nc)::value; ++r) Q[decltype(r0c)::value + r] = relu1(Q[decltype(r0c)::value + r]);
+        for (int r = 0; r < decltype(nc)::value; ++r) Q[decltype(r0c)::value + r] = relu_bits(Q[decltype(r0c)::value + r]);
     };
     auto lg_load = [&](int j, int half) {           // weights of channels 32 half + rowmap(4 j .. 4 j + 3, g), every class
 #pragma unroll
@@ -602,8 +570,8 @@ __device__ __forceinline__ void head_consumer_deferred(const HeadArgs &a, float 
             const float *src = px + wave * PX_WAVE + lane * 4;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const f32x4 v0 = lds4(src + j * 256);
-                const f32x4 v1 = lds4(src + (4 + j) * 256);
+                const f32x4 v0 = ld4(src + j * 256);
+                const f32x4 v1 = ld4(src + (4 + j) * 256);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) { P0[4 * j + i] = v0[i]; P1[4 * j + i] = v1[i]; }
             }
@@ -613,8 +581,8 @@ __device__ __forceinline__ void head_consumer_deferred(const HeadArgs &a, float 
         UKBB_HS(hs_b, hs_p)
         if (s + 1 < nstages) {                          // features of the next block: a whole stage to arrive
             qnext = pixel_of(s + 1);
-            xv0 = ldg4(a.conv0 + qnext * 16 + 4 * g);
-            xv1 = ldg4(a.conv0 + qnext * 16 + 8 + 4 * g);
+            xv0 = ld4(a.conv0 + qnext * 16 + 4 * g);
+            xv1 = ld4(a.conv0 + qnext * 16 + 8 + 4 * g);
         }
         // ---- same_dim0 and out0 (slots 0..39), with the seven steps of the tail of block s - 1 spread between their MFMAs
         // (at s = 0 that tail is all zeros and is not stored) ----
@@ -629,18 +597,18 @@ __device__ __forceinline__ void head_consumer_deferred(const HeadArgs &a, float 
         f32x4 oa = lds4(wbase + WO0), ob = lds4(wbase + WO0 + 4 * 256);     // out0's first fragments
         {
             const f32x4 wv0 = lds4(wbase), wv1 = lds4(wbase + 256);
-            unroll_n<8>([&](auto mc) {
+            unroll<8>([&](auto mc) {
                 constexpr int m = decltype(mc)::value;
                 at_slot(mc, [&] { S = MFMA32(m < 4 ? wv0[m & 3] : wv1[m & 3], m < 4 ? x0[m & 3] : x1[m & 3], S); });
             });
         }
         relu16(S);
         UKBB_HS(hs_j[0], hs_p)
-        unroll_n<4>([&](auto qc) {
+        unroll<4>([&](auto qc) {
             constexpr int q4 = decltype(qc)::value;
             f32x4 na = oa, nb = ob;
             if constexpr (q4 < 3) { na = lds4(wbase + WO0 + (q4 + 1) * 256); nb = lds4(wbase + WO0 + (4 + q4 + 1) * 256); }
-            unroll_n<4>([&](auto ic) {
+            unroll<4>([&](auto ic) {
                 constexpr int i = decltype(ic)::value, m = 8 + 8 * q4 + 2 * i;
                 at_slot(std::integral_constant<int, m>{}, [&] { P0 = MFMA32(oa[i], S[4 * q4 + i], P0); });
                 at_slot(std::integral_constant<int, m + 1>{}, [&] { P1 = MFMA32(ob[i], S[4 * q4 + i], P1); });
@@ -661,12 +629,12 @@ __device__ __forceinline__ void head_consumer_deferred(const HeadArgs &a, float 
         f32x2 acc[NCLS];
 #pragma unroll
         for (int c = 0; c < NCLS; ++c) acc[c] = f32x2{0.f, 0.f};
-        unroll_n<16>([&](auto Gc) {
+        unroll<16>([&](auto Gc) {
             constexpr int G = decltype(Gc)::value, k = G & 7;
             f32x4 wn = wq;
             if constexpr (G < 15) wn = wf(G + 1);
             if constexpr (G == 6) Q1 = bias_tile_at(L_BO1 - L_BS0 + 32);
-            unroll_n<4>([&](auto ic) {
+            unroll<4>([&](auto ic) {
                 constexpr int i = decltype(ic)::value, slot = 4 * G + i;
                 constexpr bool relu_p1 = slot >= 1 && slot <= 4, head = slot >= 33 && slot <= 53 && (slot - 33) % 4 == 0;
                 const float xb = k < 4 ? P0[4 * (k & 3) + i] : P1[4 * (k & 3) + i];
@@ -690,7 +658,7 @@ __device__ __forceinline__ void head_consumer_deferred(const HeadArgs &a, float 
         qd = q;
     }
     if (nstages > 0) {                                  // the last block's tail
-        unroll_n<8>([&](auto kc) { fin(kc); });
+        unroll<8>([&](auto kc) { fin(kc); });
         store_tail(qd);
     }
 #ifdef UKBB_DIAG
@@ -755,7 +723,7 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
         unsigned tbit[NIT], goff[NIT];
         auto window_consts = [&]() {
         int sp32 = tid >> 4;
-        unroll_n<NIT>([&](auto ic) {
+        unroll<NIT>([&](auto ic) {
             constexpr int it = decltype(ic)::value;
             constexpr int l = it < 3 ? 1 : it < 5 ? 2 : it < 6 ? 3 : 4;
             constexpr int it0 = l == 1 ? 0 : l == 2 ? 3 : l == 3 ? 5 : 6;
@@ -785,7 +753,7 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
                 const float *base = a.G[l - 1] + ((long long)(n * hl + sy0) * wl + sx0) * 64;   // may precede the map; masked lanes never use it
                 rs[l - 1] = __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, 0x7fffffff, 0x00020000);
             }
-            unroll_n<NIT>([&](auto ic) {
+            unroll<NIT>([&](auto ic) {
                 constexpr int it = decltype(ic)::value;
                 constexpr int l = it < 3 ? 1 : it < 5 ? 2 : it < 6 ? 3 : 4;
                 const unsigned vo = (cm[l - 1] & tbit[it]) == tbit[it] ? goff[it] : 0x80000000u;
@@ -795,7 +763,7 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
         float *const gdst = gw + sp32 * GSTRIDE + 4 * c4;
         auto g_store = [&](int b) {
             float *dst = gdst + b * GPIX * GSTRIDE;
-            unroll_n<NIT>([&](auto ic) {
+            unroll<NIT>([&](auto ic) {
                 constexpr int it = decltype(ic)::value;
                 constexpr int l = it < 3 ? 1 : it < 5 ? 2 : it < 6 ? 3 : 4;
                 constexpr int it0 = l == 1 ? 0 : l == 2 ? 3 : l == 3 ? 5 : 6;
@@ -850,7 +818,7 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
         f32x16 P;                                       // DG: 16 channels of one pixel; else register 4 t + i = channel 4 k4 + i of run row t
         auto gather_sep = [&](auto parc, auto bufc, auto rgc) {
             constexpr int BUF = decltype(bufc)::value, R0 = 8 * decltype(parc)::value + 4 * decltype(rgc)::value;
-            const f32x4 b = lds4(lds + L_BO0 + 4 * k4);
+            const f32x4 b = ld4(lds + L_BO0 + 4 * k4);
 #pragma unroll
             for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -858,21 +826,21 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
 #ifdef UKBB_DIAG
             if (a.diag & 1) return;                 // ablation: no gather (hand over the bias tile only)
 #endif
-            unroll_n<4>([&](auto lc) {
+            unroll<4>([&](auto lc) {
                 constexpr int l = decltype(lc)::value + 1, f = 1 << l, wn_ = win_n(l), I0 = sep_row0(R0, l);
                 static_assert(sep_row0(R0 + 3, l) + 1 - I0 < 3, "a run of four rows reads at most three window rows");
                 const float *src = gw + BUF * GPIX * GSTRIDE + xoff[l - 1] + I0 * wn_ * GSTRIDE;
                 const float u0 = wx0[l - 1], u1 = wx1[l - 1];
                 f32x4 h[3];                             // window rows I0 .. I0 + 2, interpolated in x at the lane's column
-                unroll_n<3>([&](auto kc) {
+                unroll<3>([&](auto kc) {
                     constexpr int k = decltype(kc)::value;
                     if constexpr (sep_row_used(R0, l, k)) {
-                        const f32x4 a0 = lds4(src + k * wn_ * GSTRIDE), a1 = lds4(src + k * wn_ * GSTRIDE + GSTRIDE);
+                        const f32x4 a0 = ld4(src + k * wn_ * GSTRIDE), a1 = ld4(src + k * wn_ * GSTRIDE + GSTRIDE);
 #pragma unroll
                         for (int i = 0; i < 4; ++i) h[k][i] = fmaf(u0, a0[i], u1 * a1[i]);
                     }
                 });
-                unroll_n<4>([&](auto tc) {
+                unroll<4>([&](auto tc) {
                     constexpr int t = decltype(tc)::value, y = R0 + t + sep_pb(l), i1 = (y >> l) - I0, jy = y & (f - 1);
                     constexpr float wy1 = (float)(jy + 1) / (float)f, wy0 = (float)(f - 1 - jy) / (float)f;
 #pragma unroll
@@ -909,7 +877,7 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
                 const float w00 = tw[PAR][l - 1][0], w01 = tw[PAR][l - 1][1], w10 = tw[PAR][l - 1][2], w11 = tw[PAR][l - 1][3];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const f32x4 a00 = lds4(b00 + 8 * j), a01 = lds4(b01 + 8 * j), a10 = lds4(b10 + 8 * j), a11 = lds4(b11 + 8 * j);
+                    const f32x4 a00 = ld4(b00 + 8 * j), a01 = ld4(b01 + 8 * j), a10 = ld4(b10 + 8 * j), a11 = ld4(b11 + 8 * j);
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
                         P[4 * j + i] = fmaf(w00, a00[i], fmaf(w01, a01[i], fmaf(w10, a10[i], fmaf(w11, a11[i], P[4 * j + i]))));
@@ -979,8 +947,8 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
         f32x4 xv0 = {0.f, 0.f, 0.f, 0.f}, xv1 = xv0;      // conv0 features of the NEXT block, prefetched
         if (nstages > 0) {
             const size_t q0 = pixel_of(0);
-            xv0 = ldg4(a.conv0 + q0 * 16 + 4 * g);
-            xv1 = ldg4(a.conv0 + q0 * 16 + 8 + 4 * g);
+            xv0 = ld4(a.conv0 + q0 * 16 + 4 * g);
+            xv1 = ld4(a.conv0 + q0 * 16 + 8 + 4 * g);
         }
         __syncthreads();                                // barrier X
 #ifdef UKBB_DIAG
@@ -1003,8 +971,8 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
                 const float *src = px + wave * PX_WAVE + lane * 4;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const f32x4 v0 = lds4(src + j * 256);
-                    const f32x4 v1 = lds4(src + (4 + j) * 256);
+                    const f32x4 v0 = ld4(src + j * 256);
+                    const f32x4 v1 = ld4(src + (4 + j) * 256);
 #pragma unroll
                     for (int i = 0; i < 4; ++i) { P0[4 * j + i] = v0[i]; P1[4 * j + i] = v1[i]; }
                 }
@@ -1014,13 +982,13 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
             UKBB_HS(hs_b, hs_p)
             if (s + 1 < nstages) {                      // features of the next block: a whole stage to arrive
                 const size_t qn = pixel_of(s + 1);
-                xv0 = ldg4(a.conv0 + qn * 16 + 4 * g);
-                xv1 = ldg4(a.conv0 + qn * 16 + 8 + 4 * g);
+                xv0 = ld4(a.conv0 + qn * 16 + 4 * g);
+                xv1 = ld4(a.conv0 + qn * 16 + 8 + 4 * g);
             }
             // ---- same_dim0 ----
             f32x16 S = bias_tile_lds(lds + L_BS0, g);
             {
-                const f32x4 wv0 = lds4(w_s0 + lane * 4), wv1 = lds4(w_s0 + (64 + lane) * 4);
+                const f32x4 wv0 = ld4(w_s0 + lane * 4), wv1 = ld4(w_s0 + (64 + lane) * 4);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) S = MFMA32(wv0[i], x0[i], S);
 #pragma unroll
@@ -1043,16 +1011,16 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
                         sh[kc][d] = th; sm[kc][d] = tm; sl[kc][d] = tl;
                     }
                 const float *wx0 = lds + L_WO0 + lane * 4;
-                auto A0 = [&](int t, int cb, int kc) { return __builtin_bit_cast(u32x4, lds4(wx0 + ((t * 2 + cb) * 2 + kc) * 256)); };
+                auto A0 = [&](int t, int cb, int kc) { return __builtin_bit_cast(u32x4, ld4(wx0 + ((t * 2 + cb) * 2 + kc) * 256)); };
 #pragma unroll
                 for (int kc = 0; kc < 2; ++kc) {
                     const u32x4 ah0 = A0(0, 0, kc), ah1 = A0(0, 1, kc), am0 = A0(1, 0, kc), am1 = A0(1, 1, kc), al0 = A0(2, 0, kc), al1 = A0(2, 1, kc);
-                    P0 = mfma_b16(al0, sh[kc], P0); P1 = mfma_b16(al1, sh[kc], P1);
-                    P0 = mfma_b16(ah0, sl[kc], P0); P1 = mfma_b16(ah1, sl[kc], P1);
-                    P0 = mfma_b16(am0, sm[kc], P0); P1 = mfma_b16(am1, sm[kc], P1);
-                    P0 = mfma_b16(am0, sh[kc], P0); P1 = mfma_b16(am1, sh[kc], P1);
-                    P0 = mfma_b16(ah0, sm[kc], P0); P1 = mfma_b16(ah1, sm[kc], P1);
-                    P0 = mfma_b16(ah0, sh[kc], P0); P1 = mfma_b16(ah1, sh[kc], P1);
+                    P0 = mfma_bf16(al0, sh[kc], P0); P1 = mfma_bf16(al1, sh[kc], P1);
+                    P0 = mfma_bf16(ah0, sl[kc], P0); P1 = mfma_bf16(ah1, sl[kc], P1);
+                    P0 = mfma_bf16(am0, sm[kc], P0); P1 = mfma_bf16(am1, sm[kc], P1);
+                    P0 = mfma_bf16(am0, sh[kc], P0); P1 = mfma_bf16(am1, sh[kc], P1);
+                    P0 = mfma_bf16(ah0, sm[kc], P0); P1 = mfma_bf16(ah1, sm[kc], P1);
+                    P0 = mfma_bf16(ah0, sh[kc], P0); P1 = mfma_bf16(ah1, sh[kc], P1);
                 }
             } else {
                 chain_32to64_lds(w_o0, lane, S, P0, P1);
@@ -1079,18 +1047,18 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
                     }
                 };
                 const float *wx = lds + L_WO1 + lane * 4;
-                auto A = [&](int t, int cb, int kc) { return __builtin_bit_cast(u32x4, lds4(wx + ((t * 2 + cb) * 4 + kc) * 256)); };
+                auto A = [&](int t, int cb, int kc) { return __builtin_bit_cast(u32x4, ld4(wx + ((t * 2 + cb) * 4 + kc) * 256)); };
                 split(std::integral_constant<int, 0>{});
-                unroll_n<4>([&](auto kcc) {
+                unroll<4>([&](auto kcc) {
                     constexpr int kc = decltype(kcc)::value;
                     const u32x4 ah0 = A(0, 0, kc), ah1 = A(0, 1, kc), am0 = A(1, 0, kc), am1 = A(1, 1, kc), al0 = A(2, 0, kc), al1 = A(2, 1, kc);
                     if constexpr (kc < 3) split(std::integral_constant<int, kc + 1>{});
-                    Q0 = mfma_b16(al0, bh[kc], Q0); Q1 = mfma_b16(al1, bh[kc], Q1);      // small terms first
-                    Q0 = mfma_b16(ah0, bl[kc], Q0); Q1 = mfma_b16(ah1, bl[kc], Q1);
-                    Q0 = mfma_b16(am0, bm[kc], Q0); Q1 = mfma_b16(am1, bm[kc], Q1);
-                    Q0 = mfma_b16(am0, bh[kc], Q0); Q1 = mfma_b16(am1, bh[kc], Q1);
-                    Q0 = mfma_b16(ah0, bm[kc], Q0); Q1 = mfma_b16(ah1, bm[kc], Q1);
-                    Q0 = mfma_b16(ah0, bh[kc], Q0); Q1 = mfma_b16(ah1, bh[kc], Q1);
+                    Q0 = mfma_bf16(al0, bh[kc], Q0); Q1 = mfma_bf16(al1, bh[kc], Q1);      // small terms first
+                    Q0 = mfma_bf16(ah0, bl[kc], Q0); Q1 = mfma_bf16(ah1, bl[kc], Q1);
+                    Q0 = mfma_bf16(am0, bm[kc], Q0); Q1 = mfma_bf16(am1, bm[kc], Q1);
+                    Q0 = mfma_bf16(am0, bh[kc], Q0); Q1 = mfma_bf16(am1, bh[kc], Q1);
+                    Q0 = mfma_bf16(ah0, bm[kc], Q0); Q1 = mfma_bf16(ah1, bm[kc], Q1);
+                    Q0 = mfma_bf16(ah0, bh[kc], Q0); Q1 = mfma_bf16(ah1, bh[kc], Q1);
                     if constexpr (kc < 3) {
 #pragma unroll
                         for (int i = 0; i < 12; ++i) {
@@ -1119,13 +1087,13 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
                 f32x2 acc2 = {0.f, 0.f};
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const f32x4 w = lds4(wp + 4 * j);
+                    const f32x4 w = ld4(wp + 4 * j);
                     acc2 = pk_fma(f32x2{w[0], w[1]}, f32x2{Q0[4 * j], Q0[4 * j + 1]}, acc2);
                     acc2 = pk_fma(f32x2{w[2], w[3]}, f32x2{Q0[4 * j + 2], Q0[4 * j + 3]}, acc2);
                 }
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const f32x4 w = lds4(wp + 16 + 4 * j);
+                    const f32x4 w = ld4(wp + 16 + 4 * j);
                     acc2 = pk_fma(f32x2{w[0], w[1]}, f32x2{Q1[4 * j], Q1[4 * j + 1]}, acc2);
                     acc2 = pk_fma(f32x2{w[2], w[3]}, f32x2{Q1[4 * j + 2], Q1[4 * j + 3]}, acc2);
                 }

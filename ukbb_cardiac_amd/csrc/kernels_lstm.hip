@@ -11,16 +11,13 @@
 //                     deploy_network_ao.py:176-183 in the reference's accumulation order and arithmetic (float32 accumulator
 //                     updated through float64) -- the per-window probabilities are never stored.
 #include "kernels.h"
+#include "device_prims.h"
 
 namespace ukbb {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
 constexpr int NH = 16;                       // hidden channels (train_network_ao.py num_hidden = 16)
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // 16 hidden channels of one pixel, fp32 or bf16 in memory
 template <bool BF>
@@ -97,103 +94,29 @@ __global__ __launch_bounds__(256) void lstm_out_kernel(const LstmOutArgs a) {
     }
 }
 
-// prob[f] = (sum over the <= K windows containing f, in the reference's order, of prob(window w, step k) * w_k) / wsum[f]
-//   prob(w, k) = softmax(out_conv(h_fw[k][w], h_bw[k][w])) exactly as lstm_out_kernel forms it (forward_seq of that window);
-//   a frame no window reaches (time_step > window) has wsum = 0: 0/0 = NaN and argmax 0, as numpy gives the reference
-//   reference arithmetic: prob is float32, `prob[..., idx] += prob_idx * w` runs in float64 and is cast back
-//   per addition; `prob /= weight` likewise (deploy_network_ao.py:176-183).
-template <int NCLS, bool BF>
+// prob / pred of a cine (kernels.h cine_tile_pixel): a term is
+//   prob(w, k) = softmax(out_conv(h_fw[k][w], h_bw[k][w])) exactly as lstm_out_kernel forms it (forward_seq of that window).
+// CHUNKED: the launch of one chunk of windows [w0, w1) of a cine that runs in chunks; every (frame, pixel) belongs to one lane per launch
+// (no atomics).  Not CHUNKED: the whole cine in one launch.
+template <int NCLS, bool BF, bool CHUNKED>
 __global__ __launch_bounds__(256) void lstm_tile_kernel(const LstmTileArgs a) {
     float w[2 * NH][NCLS], b[NCLS];
     load_out_weights<NCLS>(a.w_out, a.b_out, w, b);
-    const long long total = (long long)a.F * a.HW;
+    const int K = a.tb.K;
+    const long long total = (long long)a.tb.F * a.HW;
     for (long long id = (long long)blockIdx.x * 256 + threadIdx.x; id < total; id += (long long)gridDim.x * 256) {
         const int f = (int)(id / a.HW);
         const long long pix = id - (long long)f * a.HW;
-        float acc[NCLS];
-#pragma unroll
-        for (int k = 0; k < NCLS; ++k) acc[k] = 0.f;
-        for (int j = 0; j < a.K; ++j) {
-            const int wk_ = a.order[f * a.K + j];
-            if (wk_ < 0) break;                                             // fewer than K windows reach this frame (time_step > 1, F < K)
-            const int wi = wk_ / a.K, k = wk_ - wi * a.K;
+        cine_tile_pixel<NCLS, CHUNKED>(a.tb, f, a.w0, a.w1, a.first, a.last, a.prob, a.pred, id, [&](int wi, int k, float (&p)[NCLS]) {
+            const int wl = CHUNKED ? wi - a.w0 : wi;
             // the first step of a direction comes from the per-FRAME maps of the x pass, later steps from that direction's per-window maps
-            const long long mf = k == 0 ? a.map_first[wi] : wi, mb = k == a.K - 1 ? a.map_last[wi] : wi;
-            float lg[NCLS], p[NCLS], vf[NH], vb[NH];
+            const long long mf = k == 0 ? a.map_first[wl] : wl, mb = k == K - 1 ? a.map_last[wl] : wl;
+            float lg[NCLS], vf[NH], vb[NH];
             load_h16<BF>(k == 0 ? a.h1f : a.hf, (k == 0 ? 0 : (long long)k * a.k_stride) + (mf * a.HW + pix) * NH, vf);
-            load_h16<BF>(k == a.K - 1 ? a.h1b : a.hb, (k == a.K - 1 ? 0 : (long long)k * a.k_stride) + (mb * a.HW + pix) * NH, vb);
+            load_h16<BF>(k == K - 1 ? a.h1b : a.hb, (k == K - 1 ? 0 : (long long)k * a.k_stride) + (mb * a.HW + pix) * NH, vb);
             out_conv<NCLS>(vf, vb, w, b, lg);
             (void)softmax_argmax<NCLS>(lg, p);
-            const double wt = a.wk[k];
-#pragma unroll
-            for (int c = 0; c < NCLS; ++c) acc[c] = (float)((double)acc[c] + (double)p[c] * wt);
-        }
-        const double ws = a.wsum[f];
-        int best = 0;
-#pragma unroll
-        for (int c = 0; c < NCLS; ++c) acc[c] = (float)((double)acc[c] / ws);
-#pragma unroll
-        for (int c = 1; c < NCLS; ++c) if (acc[c] > acc[best]) best = c;
-        float *o = a.prob + id * NCLS;
-#pragma unroll
-        for (int c = 0; c < NCLS; ++c) o[c] = acc[c];
-        if (a.pred) a.pred[id] = best;
-    }
-}
-
-// lstm_tile_kernel for a cine whose windows run in chunks: this launch adds the terms of the windows [w0, w1) only.  A frame's terms come in
-// ascending window order (order[]), chunks run in ascending order, and the one-pass kernel rounds its accumulator to float32 after every
-// term -- so carrying that float32 in prob between chunks performs the same sequence of float64-widened adds.  Every (frame, pixel) belongs
-// to one lane per launch (no atomics).  A frame the chunk does not reach is not touched, except by the first chunk (zero) and the last
-// (divide by wsum, argmax).
-template <int NCLS, bool BF>
-__global__ __launch_bounds__(256) void lstm_tile_chunk_kernel(const LstmTileChunkArgs ca) {
-    const LstmTileArgs &a = ca.t;
-    float w[2 * NH][NCLS], b[NCLS];
-    load_out_weights<NCLS>(a.w_out, a.b_out, w, b);
-    const long long total = (long long)a.F * a.HW;
-    for (long long id = (long long)blockIdx.x * 256 + threadIdx.x; id < total; id += (long long)gridDim.x * 256) {
-        const int f = (int)(id / a.HW);
-        const long long pix = id - (long long)f * a.HW;
-        // the frame's terms of this chunk: entries [j0, j1) of its list
-        int j0 = 0, j1;
-        for (; j0 < a.K; ++j0) {
-            const int wk_ = a.order[f * a.K + j0];
-            if (wk_ < 0 || wk_ / a.K >= ca.w0) break;
-        }
-        for (j1 = j0; j1 < a.K; ++j1) {
-            const int wk_ = a.order[f * a.K + j1];
-            if (wk_ < 0 || wk_ / a.K >= ca.w1) break;
-        }
-        if (j0 == j1 && !ca.first && !ca.last) continue;
-        float acc[NCLS];
-        float *o = a.prob + id * NCLS;
-#pragma unroll
-        for (int k = 0; k < NCLS; ++k) acc[k] = ca.first ? 0.f : o[k];
-        for (int j = j0; j < j1; ++j) {
-            const int wk_ = a.order[f * a.K + j];
-            const int wi = wk_ / a.K, k = wk_ - wi * a.K, wl = wi - ca.w0;
-            const long long mf = k == 0 ? a.map_first[wl] : wl, mb = k == a.K - 1 ? a.map_last[wl] : wl;
-            float lg[NCLS], p[NCLS], vf[NH], vb[NH];
-            load_h16<BF>(k == 0 ? a.h1f : a.hf, (k == 0 ? 0 : (long long)k * a.k_stride) + (mf * a.HW + pix) * NH, vf);
-            load_h16<BF>(k == a.K - 1 ? a.h1b : a.hb, (k == a.K - 1 ? 0 : (long long)k * a.k_stride) + (mb * a.HW + pix) * NH, vb);
-            out_conv<NCLS>(vf, vb, w, b, lg);
-            (void)softmax_argmax<NCLS>(lg, p);
-            const double wt = a.wk[k];
-#pragma unroll
-            for (int c = 0; c < NCLS; ++c) acc[c] = (float)((double)acc[c] + (double)p[c] * wt);
-        }
-        if (ca.last) {
-            const double ws = a.wsum[f];
-            int best = 0;
-#pragma unroll
-            for (int c = 0; c < NCLS; ++c) acc[c] = (float)((double)acc[c] / ws);
-#pragma unroll
-            for (int c = 1; c < NCLS; ++c) if (acc[c] > acc[best]) best = c;
-            if (a.pred) a.pred[id] = best;
-        }
-#pragma unroll
-        for (int c = 0; c < NCLS; ++c) o[c] = acc[c];
+        });
     }
 }
 
@@ -204,51 +127,29 @@ hipError_t launch_lstm_out(const LstmOutArgs &a, hipStream_t s) {
     long long blocks = (total + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
     const dim3 g((unsigned)blocks), t(256);
-    switch (a.n_class * 2 + (a.h_bf16 ? 1 : 0)) {
-        case 4: hipLaunchKernelGGL((lstm_out_kernel<2, false>), g, t, 0, s, a); break;
-        case 5: hipLaunchKernelGGL((lstm_out_kernel<2, true>), g, t, 0, s, a); break;
-        case 6: hipLaunchKernelGGL((lstm_out_kernel<3, false>), g, t, 0, s, a); break;
-        case 7: hipLaunchKernelGGL((lstm_out_kernel<3, true>), g, t, 0, s, a); break;
-        case 8: hipLaunchKernelGGL((lstm_out_kernel<4, false>), g, t, 0, s, a); break;
-        case 9: hipLaunchKernelGGL((lstm_out_kernel<4, true>), g, t, 0, s, a); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    const bool ok = with_classes(a.n_class, [&](auto nc) {
+        constexpr int C = decltype(nc)::value;
+        if (a.h_bf16) hipLaunchKernelGGL((lstm_out_kernel<C, true>), g, t, 0, s, a);
+        else hipLaunchKernelGGL((lstm_out_kernel<C, false>), g, t, 0, s, a);
+    });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 hipError_t launch_lstm_tile(const LstmTileArgs &a, hipStream_t s) {
-    const long long total = (long long)a.F * a.HW;
+    if (a.w0 < 0 || a.w1 <= a.w0 || a.Wn != a.w1 - a.w0) return hipErrorInvalidValue;
+    const long long total = (long long)a.tb.F * a.HW;
     long long blocks = (total + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
     const dim3 g((unsigned)blocks), t(256);
-    switch (a.C * 2 + (a.h_bf16 ? 1 : 0)) {
-        case 4: hipLaunchKernelGGL((lstm_tile_kernel<2, false>), g, t, 0, s, a); break;
-        case 5: hipLaunchKernelGGL((lstm_tile_kernel<2, true>), g, t, 0, s, a); break;
-        case 6: hipLaunchKernelGGL((lstm_tile_kernel<3, false>), g, t, 0, s, a); break;
-        case 7: hipLaunchKernelGGL((lstm_tile_kernel<3, true>), g, t, 0, s, a); break;
-        case 8: hipLaunchKernelGGL((lstm_tile_kernel<4, false>), g, t, 0, s, a); break;
-        case 9: hipLaunchKernelGGL((lstm_tile_kernel<4, true>), g, t, 0, s, a); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_lstm_tile_chunk(const LstmTileChunkArgs &a, hipStream_t s) {
-    if (a.w0 < 0 || a.w1 <= a.w0 || a.t.Wn != a.w1 - a.w0) return hipErrorInvalidValue;
-    const long long total = (long long)a.t.F * a.t.HW;
-    long long blocks = (total + 255) / 256;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    const dim3 g((unsigned)blocks), t(256);
-    switch (a.t.C * 2 + (a.t.h_bf16 ? 1 : 0)) {
-        case 4: hipLaunchKernelGGL((lstm_tile_chunk_kernel<2, false>), g, t, 0, s, a); break;
-        case 5: hipLaunchKernelGGL((lstm_tile_chunk_kernel<2, true>), g, t, 0, s, a); break;
-        case 6: hipLaunchKernelGGL((lstm_tile_chunk_kernel<3, false>), g, t, 0, s, a); break;
-        case 7: hipLaunchKernelGGL((lstm_tile_chunk_kernel<3, true>), g, t, 0, s, a); break;
-        case 8: hipLaunchKernelGGL((lstm_tile_chunk_kernel<4, false>), g, t, 0, s, a); break;
-        case 9: hipLaunchKernelGGL((lstm_tile_chunk_kernel<4, true>), g, t, 0, s, a); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    const bool chunked = !(a.first && a.last);
+    const bool ok = with_classes(a.C, [&](auto nc) {
+        constexpr int C = decltype(nc)::value;
+        if (a.h_bf16 && chunked) hipLaunchKernelGGL((lstm_tile_kernel<C, true, true>), g, t, 0, s, a);
+        else if (a.h_bf16) hipLaunchKernelGGL((lstm_tile_kernel<C, true, false>), g, t, 0, s, a);
+        else if (chunked) hipLaunchKernelGGL((lstm_tile_kernel<C, false, true>), g, t, 0, s, a);
+        else hipLaunchKernelGGL((lstm_tile_kernel<C, false, false>), g, t, 0, s, a);
+    });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace ukbb

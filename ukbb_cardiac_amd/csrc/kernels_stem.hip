@@ -15,6 +15,7 @@
 //   store     bias, ReLU, bf16; lane (pixel, quarter kq) holds channels 4 kq .. 4 kq + 3: 8-byte stores, 512 contiguous bytes per
 //             instruction.
 #include "kernels.h"
+#include "device_prims.h"
 
 #include <cstring>
 #include <type_traits>
@@ -22,21 +23,6 @@
 namespace ukbb {
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ f32x4 mfma16(const u32x4 &a, const u32x4 &b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-template <int N, int I = 0, class F>
-__device__ __forceinline__ void unroll_steps(F &&f) {
-    if constexpr (I < N) { f(std::integral_constant<int, I>{}); unroll_steps<N, I + 1>(f); }
-}
 
 constexpr int ST_TW = 30, ST_MW = 32, ST_IW = 34;       // stored columns, stage-0 columns, image halo columns
 constexpr int ST_RP = 40;                                // bf16 elements per row of an image copy (34 + shift + window overhang, 8-byte rows)
@@ -163,8 +149,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void unet_stem_kernel(const StemAr
                 Wl[s % NB0] = *reinterpret_cast<const u32x2 *>(s0_lane + (r * ST_RP + 16 * blk) * 2);
                 Wh[s % NB0] = *reinterpret_cast<const u32x2 *>(s0_lane + ((r + 1) * ST_RP + 16 * blk) * 2);
             };
-            unroll_steps<PD0>([&](auto sc) { readW(sc); });
-            unroll_steps<S0>([&](auto sc) {
+            unroll<PD0>([&](auto sc) { readW(sc); });
+            unroll<S0>([&](auto sc) {
                 constexpr int s = decltype(sc)::value, r = s / 2, blk = s % 2;
                 if constexpr (s + PD0 < S0) readW(std::integral_constant<int, s + PD0>{});
                 __builtin_amdgcn_sched_barrier(0);
@@ -176,10 +162,10 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void unet_stem_kernel(const StemAr
         // ---- mid tile: ReLU, zero outside the image (only border tiles have such pixels), bf16 ----
         auto mid_store = [&](auto maskc) {
             constexpr bool MASK = decltype(maskc)::value;
-            unroll_steps<R1>([&](auto rc) {
+            unroll<R1>([&](auto rc) {
                 constexpr int r = decltype(rc)::value;
                 const bool rowok = (unsigned)(oy0 - 1 + r) < (unsigned)a.H;
-                unroll_steps<2>([&](auto bc) {
+                unroll<2>([&](auto bc) {
                     constexpr int blk = decltype(bc)::value;
                     const float e0 = acc1[r][blk][0], e1 = acc1[r][blk][1], e2 = acc1[r][blk][2], e3 = acc1[r][blk][3];
                     f32x2 lo2, hi2;
@@ -208,8 +194,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void unet_stem_kernel(const StemAr
                 constexpr int s = decltype(sc)::value, r = s / 10, blk = (s / 5) % 2, p = s % 5;
                 Bq[s % NB2] = *reinterpret_cast<const u32x4 *>(s2_lane[p] + (r * ST_MW + 16 * blk) * 16);
             };
-            unroll_steps<PD2>([&](auto sc) { readB(sc); });
-            unroll_steps<S2>([&](auto sc) {
+            unroll<PD2>([&](auto sc) { readB(sc); });
+            unroll<S2>([&](auto sc) {
                 constexpr int s = decltype(sc)::value, r = s / 10, blk = (s / 5) % 2, p = s % 5;
                 if constexpr (s + PD2 < S2) readB(std::integral_constant<int, s + PD2>{});
                 __builtin_amdgcn_sched_barrier(0);
@@ -220,11 +206,11 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void unet_stem_kernel(const StemAr
         }
         // ---- store: ReLU, bf16, 8 bytes per lane (channels 4 kq ..) of pixel (row r, column 16 blk + n16) ----
         unsigned char *const obase = outb + (size_t)n * out_img_bytes;
-        unroll_steps<R>([&](auto rc) {
+        unroll<R>([&](auto rc) {
             constexpr int r = decltype(rc)::value;
             const int oy = oy0 + r;
             const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc((void *)obase, 0, oy < a.H ? out_img_bytes : 0, 0x00020000);
-            unroll_steps<2>([&](auto bc) {
+            unroll<2>([&](auto bc) {
                 constexpr int blk = decltype(bc)::value;
                 const int c0 = 16 * blk + n16;
                 const bool own = c0 < ST_TW && ox0 + c0 < a.W;

@@ -22,6 +22,7 @@
 // rounding points (bf16 after up0_0 and after up0_1) are kept, so results agree with the unfused plan to a bf16 ulp of a few
 // intermediate values (tools/check_ws.py, tests/test_gpu_parity.py).
 #include "kernels.h"
+#include "device_prims.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -32,21 +33,6 @@
 namespace ukbb {
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ f32x4 mfma16(const u32x4 &a, const u32x4 &b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-template <int N, int I = 0, class F>
-__device__ __forceinline__ void unroll_steps(F &&f) {
-    if constexpr (I < N) { f(std::integral_constant<int, I>{}); unroll_steps<N, I + 1>(f); }
-}
 
 // NB = 16-pixel MFMA blocks per tile row: label columns per tile 16 NB - 2, stage-1 columns 16 NB, input halo columns 16 NB + 2.
 // NB = 2 (30-column tiles) needs 37 KB of LDS and 415 registers per wave: ONE wave per SIMD, and its non-MFMA phases (park, request,
@@ -287,12 +273,12 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void unet_tail_kernel(const TailAr
                 constexpr int s = decltype(sc)::value, blk = s / (3 * HR0), kw = (s / HR0) % 3, rp = s % HR0;
                 Bq[s % NB1] = *reinterpret_cast<const u32x4 *>(s1_lane + (rp * TL_IW + 16 * blk + kw) * 32);
             };
-            unroll_steps<PD1>([&](auto sc) { readB(sc); });
-            unroll_steps<S1>([&](auto sc) {
+            unroll<PD1>([&](auto sc) { readB(sc); });
+            unroll<S1>([&](auto sc) {
                 constexpr int s = decltype(sc)::value, blk = s / (3 * HR0), kw = (s / HR0) % 3, rp = s % HR0;
                 if constexpr (s + PD1 < S1) readB(std::integral_constant<int, s + PD1>{});
                 __builtin_amdgcn_sched_barrier(0);
-                unroll_steps<3>([&](auto khc) {
+                unroll<3>([&](auto khc) {
                     constexpr int kh = decltype(khc)::value, r = rp - kh;
                     if constexpr (r >= 0 && r < R1) {
                         if constexpr (kw == 0 && kh == 0) acc1[r][blk] = mfma16(A0[kh * 3 + kw], Bq[s % NB1], bias0);
@@ -306,10 +292,10 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void unet_tail_kernel(const TailAr
         // ---- mid tile: ReLU, zero outside the image (only border tiles have such pixels), bf16 ----
         auto mid_store = [&](auto maskc) {
             constexpr bool MASK = decltype(maskc)::value;
-            unroll_steps<R1>([&](auto rc) {
+            unroll<R1>([&](auto rc) {
                 constexpr int r = decltype(rc)::value;
                 const bool rowok = (unsigned)(oy0 - 1 + r) < (unsigned)a.H;
-                unroll_steps<NB>([&](auto bc) {
+                unroll<NB>([&](auto bc) {
                     constexpr int blk = decltype(bc)::value;
                     const float e0 = acc1[r][blk][0], e1 = acc1[r][blk][1], e2 = acc1[r][blk][2], e3 = acc1[r][blk][3];
                     f32x2 lo2, hi2;
@@ -339,8 +325,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void unet_tail_kernel(const TailAr
                 constexpr int s = decltype(sc)::value, r = s / (5 * NB), blk = (s / 5) % NB, p = s % 5;
                 Bq[s % NB2] = *reinterpret_cast<const u32x4 *>(s2_lane[p] + (r * TL_MW + 16 * blk) * 16);
             };
-            unroll_steps<PD2>([&](auto sc) { readB(sc); });
-            unroll_steps<S2>([&](auto sc) {
+            unroll<PD2>([&](auto sc) { readB(sc); });
+            unroll<S2>([&](auto sc) {
                 constexpr int s = decltype(sc)::value, r = s / (5 * NB), blk = (s / 5) % NB, p = s % 5;
                 if constexpr (s + PD2 < S2) readB(std::integral_constant<int, s + PD2>{});
                 __builtin_amdgcn_sched_barrier(0);
@@ -360,10 +346,10 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void unet_tail_kernel(const TailAr
         constexpr int GR = 4 / NB;                       // rows per group
         const int c0 = NB == 2 ? 16 * (kq & 1) + n16 : n16;     // this lane's column in the tile and ...
         const bool colok = c0 < TL_TW && ox0 + c0 < a.W;
-        unroll_steps<R / GR>([&](auto qc) {
+        unroll<R / GR>([&](auto qc) {
             constexpr int q = decltype(qc)::value;
             f32x4 lg = lgC;
-            unroll_steps<4>([&](auto uc) {
+            unroll<4>([&](auto uc) {
                 constexpr int u = decltype(uc)::value, r = NB == 2 ? 2 * q + (u >> 1) : 4 * q + u, blk = NB == 2 ? (u & 1) : 0;
                 const float e0 = acc2[r][blk][0], e1 = acc2[r][blk][1], e2 = acc2[r][blk][2], e3 = acc2[r][blk][3];
                 f32x2 lo2, hi2;

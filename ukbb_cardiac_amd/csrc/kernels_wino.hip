@@ -21,16 +21,13 @@
 //       output transform, bias, ReLU and the NHWC stores.
 // One barrier per stage.
 #include "kernels.h"
+#include "device_prims.h"
 
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
 namespace ukbb {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -49,23 +46,6 @@ constexpr int L_XS = 0;                               // [2][XSZ]
 constexpr int L_VS = L_XS + 2 * XSZ;            // [2][16][NT][WXS]
 constexpr int WINO_LDS_FLOATS = L_VS + 2 * 16 * NT * WXS;
 
-__device__ __forceinline__ f32x4 ld4(const float *p) { return *reinterpret_cast<const f32x4 *>(p); }
-__device__ __forceinline__ void st4(float *p, const f32x4 &v) { *reinterpret_cast<f32x4 *>(p) = v; }
-
-// Packed fp32 add / subtract on register pairs.  hipcc scalarises the subtractions of the input
-// transform into v_sub_f32 (+ moves) when left to itself; every VALU instruction of a producer wave
-// costs an MFMA slot, so the packed forms are spelled out.
-__device__ __forceinline__ f32x2 pk_add(f32x2 a, f32x2 b) {
-    f32x2 r; asm("v_pk_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r;
-}
-__device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) {
-    f32x2 r; asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b)); return r;
-}
-
-__device__ __forceinline__ float relu1(float x) {   // one v_max_i32 (fmaxf adds a canonicalising second instruction)
-    const int b = __builtin_bit_cast(int, x);
-    return __builtin_bit_cast(float, b > 0 ? b : 0);
-}
 __device__ __forceinline__ f32x4 add4(const f32x4 &a, const f32x4 &b) {
     const f32x2 lo = pk_add(f32x2{a[0], a[1]}, f32x2{b[0], b[1]}), hi = pk_add(f32x2{a[2], a[3]}, f32x2{b[2], b[3]});
     return f32x4{lo[0], lo[1], hi[0], hi[1]};
@@ -73,11 +53,6 @@ __device__ __forceinline__ f32x4 add4(const f32x4 &a, const f32x4 &b) {
 __device__ __forceinline__ f32x4 sub4(const f32x4 &a, const f32x4 &b) {
     const f32x2 lo = pk_sub(f32x2{a[0], a[1]}, f32x2{b[0], b[1]}), hi = pk_sub(f32x2{a[2], a[3]}, f32x2{b[2], b[3]});
     return f32x4{lo[0], lo[1], hi[0], hi[1]};
-}
-
-template <int N, int I = 0, class F>
-__device__ __forceinline__ void unroll_k(F &&f) {
-    if constexpr (I < N) { f(std::integral_constant<int, I>{}); unroll_k<N, I + 1>(f); }
 }
 
 }  // namespace
@@ -320,7 +295,7 @@ __global__ __launch_bounds__(512, 2) void wino_pc_kernel(const ConvArgs a) {
                     b0[i] = ld4(vs + i * NT * WXS);
                     if constexpr (TWO) b1[i] = ld4(vs + i * NT * WXS + 16 * WXS);
                 }
-                unroll_k<16>([&](auto kc) {
+                unroll<16>([&](auto kc) {
                     constexpr int k = decltype(kc)::value;
                     const f32x4 av = aq[k % AD];
                     if constexpr (k + AD < 16) aq[k % AD] = ld4(wp + (k + AD) * 64 * 4);
@@ -390,7 +365,7 @@ __global__ __launch_bounds__(512, 2) void wino_pc_kernel(const ConvArgs a) {
                         f32x4 v = y[i][j];
                         if (a.relu) {
 #pragma unroll
-                            for (int c = 0; c < 4; ++c) v[c] = relu1(v[c]);
+                            for (int c = 0; c < 4; ++c) v[c] = relu_bits(v[c]);
                         }
 #ifdef UKBB_WINO_STAMPS
                         if (a.diag & 32) continue;              // ablation: no output stores

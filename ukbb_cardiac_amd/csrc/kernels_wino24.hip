@@ -20,18 +20,13 @@
 // stages WITHOUT padding -- the 16-byte quad q of tile t sits at slot q ^ (3 * ((t >> 3) & 1)), which keeps the consumers' ds_read_b128
 // conflict-free at a pixel stride of 16 floats (slot = q ^ 3 for tiles 8-15 of each 16-tile block): 153 KB of the 160.
 #include "kernels.h"
+#include "device_prims.h"
 
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
 namespace ukbb {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -63,7 +58,6 @@ template <int TBW, bool PAIR = false> struct W24 {
     static_assert(LDS_FLOATS * 4 <= 160 * 1024, "LDS");
 };
 
-__device__ __forceinline__ f32x4 ld4(const float *p) { return *reinterpret_cast<const f32x4 *>(p); }
 #ifndef UKBB_LSTM_NT
 #define UKBB_LSTM_NT 1
 #endif
@@ -90,12 +84,6 @@ __device__ __forceinline__ void st1_s(float *p, float v) {
     *p = v;
 #endif
 }
-__device__ __forceinline__ void st4(float *p, const f32x4 &v) { *reinterpret_cast<f32x4 *>(p) = v; }
-
-__device__ __forceinline__ f32x2 pk_add(f32x2 a, f32x2 b) { f32x2 r; asm("v_pk_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) { f32x2 r; asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b)); return r; }
-// a * s + b with a scalar factor in both halves (v_pk_fma_f32; the factor is splat into a register pair by the caller)
-__device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 s, f32x2 b) { f32x2 r; asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(s), "v"(b)); return r; }
 
 struct V4 { f32x2 lo, hi; };                           // four channels as two packed pairs
 __device__ __forceinline__ V4 operator+(const V4 &a, const V4 &b) { return V4{pk_add(a.lo, b.lo), pk_add(a.hi, b.hi)}; }
@@ -103,13 +91,6 @@ __device__ __forceinline__ V4 operator-(const V4 &a, const V4 &b) { return V4{pk
 __device__ __forceinline__ V4 fma4(const V4 &a, const f32x2 &s, const V4 &b) { return V4{pk_fma(a.lo, s, b.lo), pk_fma(a.hi, s, b.hi)}; }
 __device__ __forceinline__ V4 to4(const f32x4 &v) { return V4{f32x2{v[0], v[1]}, f32x2{v[2], v[3]}}; }
 __device__ __forceinline__ f32x4 from4(const V4 &v) { return f32x4{v.lo[0], v.lo[1], v.hi[0], v.hi[1]}; }
-
-__device__ __forceinline__ float relu1(float x) { const int b = __builtin_bit_cast(int, x); return __builtin_bit_cast(float, b > 0 ? b : 0); }
-
-template <int N, int I = 0, class F>
-__device__ __forceinline__ void unroll_k(F &&f) {
-    if constexpr (I < N) { f(std::integral_constant<int, I>{}); unroll_k<N, I + 1>(f); }
-}
 
 // F(4,3) input transform of six values along a row (B_x^T d): 12 operations
 //   r0 = 4 d0 - 5 d2 + d4      r1 = (d4 - 4 d2) + (d3 - 4 d1)     r2 = (d4 - 4 d2) - (d3 - 4 d1)
@@ -452,7 +433,7 @@ __global__ __launch_bounds__(512) void wino24_pc_kernel(const ConvArgs a) {
                     f32x4 bp[BRG][2];
 #pragma unroll
                     for (int q = 0; q < BD; ++q) { bp[q][0] = ld4(vs + (2 * q) * NT * WKC + vofs0); bp[q][1] = ld4(vs + (2 * q + 1) * NT * WKC + vofs0); }
-                    unroll_k<NK / 2>([&](auto pc) {
+                    unroll<NK / 2>([&](auto pc) {
                         constexpr int p = decltype(pc)::value, k0 = 2 * p, k1 = 2 * p + 1;
                         const f32x4 av0 = aq[k0 % AD], av1 = aq[k1 % AD];
                         if constexpr (k0 + AD < NK) aq[k0 % AD] = ld4(wp + (k0 + AD) * 64 * 4);
@@ -480,7 +461,7 @@ __global__ __launch_bounds__(512) void wino24_pc_kernel(const ConvArgs a) {
                 }
                 f32x4 b0[2], b1[2];
                 if constexpr (CTB == 2) { b0[0] = ld4(vs + vofs0); b1[0] = ld4(vs + vofs1); }
-                if constexpr (CTB == 2) unroll_k<NK>([&](auto kc) {
+                if constexpr (CTB == 2) unroll<NK>([&](auto kc) {
                     constexpr int k = decltype(kc)::value;
                     const f32x4 av = aq[k % AD];
                     if constexpr (k + AD < NK) aq[k % AD] = ld4(wp + (k + AD) * 64 * 4);
@@ -655,7 +636,7 @@ __global__ __launch_bounds__(512) void wino24_pc_kernel(const ConvArgs a) {
                         f32x4 v = from4(y[j]);
                         if (a.relu) {
 #pragma unroll
-                            for (int c = 0; c < 4; ++c) v[c] = relu1(v[c]);
+                            for (int c = 0; c < 4; ++c) v[c] = relu_bits(v[c]);
                         }
                         if (oy + i < a.Ho && ox + j < a.Wo) st4(o00 + i * dy + j * dx, v);
                     }

@@ -34,6 +34,7 @@
 // same work -- {phase 00, phase 11} (4 + 1 taps) or {phase 01, phase 10} (2 + 2) of one 32-channel slice; for Cout = 16 the
 // blocks are {00 + 01} and {10 + 11} -- and the zero (tap, phase) pairs are skipped at COMPILE time (one specialisation per pairing).
 #include "kernels.h"
+#include "device_prims.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -45,17 +46,6 @@ namespace ukbb {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ f32x16 mfma_bf16(const u32x4 &a, const u32x4 &b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 // 16-byte buffer store whose soffset is an SGPR, followed by pinned wait states.
 // gfx950, found r06 (profiles/r06_notes.md section 10): the vector-memory unit reads the data registers of a store wider than 8 bytes over
 // several cycles AFTER issue, and a VALU write to one of them in the next issue slots changes what is stored.  hipcc pads this hazard only
@@ -81,15 +71,6 @@ __device__ __forceinline__ void store_b128_sofs(const u32x4 &v, __amdgpu_buffer_
     asm volatile("s_nop 3" ::: "memory");
 #endif
     __builtin_amdgcn_sched_barrier(0);
-}
-
-__device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
-    const __bf16 l = (__bf16)lo, h = (__bf16)hi;       // RNE; v_cvt_pk_bf16_f32
-    return (unsigned)__builtin_bit_cast(unsigned short, l) | ((unsigned)__builtin_bit_cast(unsigned short, h) << 16);
-}
-template <int N, int I = 0, class F>
-__device__ __forceinline__ void unroll_steps(F &&f) {
-    if constexpr (I < N) { f(std::integral_constant<int, I>{}); unroll_steps<N, I + 1>(f); }
 }
 
 constexpr int WS_TW = 32;                               // tile width = one 32-pixel MFMA block per image row
@@ -293,9 +274,9 @@ __device__ __forceinline__ void ws_main(const ConvArgs &a, const int grp, const 
     };
     auto readA = [&](auto gc) {                         // (chunk, kw | b) group GG of the body
         constexpr int GG = decltype(gc)::value, G = GG % (U * NGRP), CH = (G / NGRP) % NCH, kw = G % NGRP;
-        unroll_steps<CB>([&](auto cbc) {
+        unroll<CB>([&](auto cbc) {
             constexpr int cb = decltype(cbc)::value;
-            unroll_steps<NAF>([&](auto kc) {
+            unroll<NAF>([&](auto kc) {
                 constexpr int kh = decltype(kc)::value;     // KIND 1: kh = a, kw = b
                 constexpr int tap = KIND == 0 ? kh * 3 + kw : kh * 2 + kw;
                 if constexpr (KIND == 0 || wst_needed(TM, cb, kh, kw))
@@ -329,15 +310,15 @@ __device__ __forceinline__ void ws_main(const ConvArgs &a, const int grp, const 
     };
     auto compute = [&](auto qc) {                       // position Q of the body: chunk Q % NCH from ring stage Q & 1
         constexpr int Q = decltype(qc)::value, CH = Q % NCH;
-        unroll_steps<S>([&](auto sc) {
+        unroll<S>([&](auto sc) {
             constexpr int s = decltype(sc)::value, T = Q * S + s, kw = s / HR, rp = s % HR, G = Q * NGRP + kw;
             readB(std::integral_constant<int, T + PD>{});
             if constexpr (rp == 0) readA(std::integral_constant<int, G + 1>{});
             __builtin_amdgcn_sched_barrier(0);
-            unroll_steps<NAF>([&](auto khc) {
+            unroll<NAF>([&](auto khc) {
                 constexpr int kh = decltype(khc)::value, r = rp - kh;
                 if constexpr (r >= 0 && r < R) {
-                    unroll_steps<CB>([&](auto cbc) {
+                    unroll<CB>([&](auto cbc) {
                         constexpr int cb = decltype(cbc)::value;
                         // the folded-BN bias is the C operand of an accumulator's first MFMA of the tile (no zeroing, no bias adds)
                         if constexpr (KIND == 0) {
@@ -368,9 +349,9 @@ __device__ __forceinline__ void ws_main(const ConvArgs &a, const int grp, const 
     // partner's 8 bytes of it, upper lanes group jb + 1), so every lane then holds 8 consecutive channels = one 16-byte half of a pixel
     // of the channel-blocked map.  Half as many store instructions, each 1 KB of whole 16-byte pieces.
     unsigned svoff[CB][2];
-    unroll_steps<CB>([&](auto cbc) {
+    unroll<CB>([&](auto cbc) {
         constexpr int cb = decltype(cbc)::value;
-        unroll_steps<2>([&](auto pc) {
+        unroll<2>([&](auto pc) {
             constexpr int jb = 2 * decltype(pc)::value;
             if constexpr (KIND == 0) {
                 const int chn = (grp * CB + cb) * 32 + 8 * (jb + g);
@@ -425,7 +406,7 @@ __device__ __forceinline__ void ws_main(const ConvArgs &a, const int grp, const 
             const int himg_bytes = a.Ho * a.Wo * 32;
             const unsigned hvo = ox0 + pl < a.Wo ? (unsigned)(pl * 32 + g * 16) : OOB;
             const float fb = a.ls_forget_bias;
-            unroll_steps<R>([&](auto rc) {
+            unroll<R>([&](auto rc) {
                 constexpr int r = decltype(rc)::value;
                 const int oy = oy0 + r;
                 float hv[8], cn[8];
@@ -494,7 +475,7 @@ __device__ __forceinline__ void ws_main(const ConvArgs &a, const int grp, const 
             const __amdgpu_buffer_rsrc_t ro_pred = __builtin_amdgcn_make_buffer_rsrc((void *)(a.lg_pred + (size_t)n * npx), 0, a.lg_pred ? npx * 4 : 0, 0x00020000);
             const __amdgpu_buffer_rsrc_t ro_lg = __builtin_amdgcn_make_buffer_rsrc((void *)(a.lg_logits + (size_t)n * npx * a.lg_ncls), 0, a.lg_logits ? npx * a.lg_ncls * 4 : 0, 0x00020000);
             const __amdgpu_buffer_rsrc_t ro_pr = __builtin_amdgcn_make_buffer_rsrc((void *)(a.lg_prob + (size_t)n * npx * a.lg_ncls), 0, a.lg_prob ? npx * a.lg_ncls * 4 : 0, 0x00020000);
-            unroll_steps<R>([&](auto rc) {
+            unroll<R>([&](auto rc) {
                 constexpr int r = decltype(rc)::value;
                 const int oy = oy0 + r;
                 u32x4 bq;
@@ -549,13 +530,13 @@ __device__ __forceinline__ void ws_main(const ConvArgs &a, const int grp, const 
         for (int cb = 0; cb < CB; ++cb)
 #pragma unroll
             for (int q = 0; q < 2; ++q) vo[cb][q] = colok ? svoff[cb][q] : OOB;
-        unroll_steps<R>([&](auto rc) {
+        unroll<R>([&](auto rc) {
             constexpr int r = decltype(rc)::value;
             const int oy = oy0 + r;
             const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc((void *)obase, 0, (valid && oy < a.Ho) ? out_img_bytes : 0, 0x00020000);
-            unroll_steps<CB>([&](auto cbc) {
+            unroll<CB>([&](auto cbc) {
                 constexpr int cb = decltype(cbc)::value;
-                unroll_steps<2>([&](auto pc) {
+                unroll<2>([&](auto pc) {
                     constexpr int jb = 2 * decltype(pc)::value;
                     int srow;
                     if constexpr (KIND == 0) srow = (oy * a.Wo + ox0) * 32;
@@ -564,7 +545,7 @@ __device__ __forceinline__ void ws_main(const ConvArgs &a, const int grp, const 
                         srow = ((2 * oy + (ph >> 1)) * OW + 2 * ox0) * 32;
                     }
                     u32x2 pk[2];
-                    unroll_steps<2>([&](auto dc) {
+                    unroll<2>([&](auto dc) {
                         constexpr int j = jb + decltype(dc)::value;
                         // (elements copied to scalars first: __builtin_bit_cast applied to an ext_vector element expression reads element 0, hipcc 7.2)
                         const float e0 = acc[cb][r][4 * j + 0], e1 = acc[cb][r][4 * j + 1], e2 = acc[cb][r][4 * j + 2], e3 = acc[cb][r][4 * j + 3];
@@ -614,12 +595,12 @@ __device__ __forceinline__ void ws_main(const ConvArgs &a, const int grp, const 
     park(S0);
     request(S0, std::integral_constant<int, 2 % U>{});
     readA(std::integral_constant<int, 0>{});
-    unroll_steps<PD>([&](auto tc) { readB(tc); });
+    unroll<PD>([&](auto tc) { readB(tc); });
     UKBB_WS_STAMP(2)
 
     const int bodies = (my + TPB - 1) / TPB;
     auto body = [&](int bi) {
-        unroll_steps<U>([&](auto qc) {
+        unroll<U>([&](auto qc) {
             constexpr int Q = decltype(qc)::value;      // position modulo U of the compute cursor
             constexpr int SETN = (Q + 1) & 1;           // register set / stage of position Q + 1
             if constexpr (SETN == 0) { park(S0); request(S0, std::integral_constant<int, (Q + 3) % U>{}); }
@@ -775,14 +756,14 @@ __device__ __forceinline__ void wr_main(const ConvArgs &a, const int grp, const 
     };
     auto compute = [&](auto qc) {                       // chunk of parity Q: activation stage Q, weight stage Q
         constexpr int Q = decltype(qc)::value;
-        unroll_steps<S>([&](auto sc) {
+        unroll<S>([&](auto sc) {
             constexpr int s = decltype(sc)::value, T = Q * S + s, kw = s / HR, rp = s % HR, G = Q * NGRP + kw;
             // the reads of the NEXT chunk's first steps / first A group may only go out once its stages are visible: they are issued by
             // the caller behind the barrier (T + PD >= S of the last chunk before a barrier is handled by splitting the prefetch there)
             if constexpr (s + PD < S) readB(std::integral_constant<int, T + PD>{});
             if constexpr (rp == 0 && kw + 1 < NGRP) readA(std::integral_constant<int, G + 1>{});
             __builtin_amdgcn_sched_barrier(0);
-            unroll_steps<NAF>([&](auto khc) {
+            unroll<NAF>([&](auto khc) {
                 constexpr int kh = decltype(khc)::value, r = rp - kh;
                 if constexpr (r >= 0 && r < R) {
 #pragma unroll
@@ -795,7 +776,7 @@ __device__ __forceinline__ void wr_main(const ConvArgs &a, const int grp, const 
     auto prime = [&](auto qc) {                         // first reads of chunk parity Q (behind the barrier that made its stages visible)
         constexpr int Q = decltype(qc)::value;
         readA(std::integral_constant<int, Q * NGRP>{});
-        unroll_steps<PD>([&](auto tc) { readB(std::integral_constant<int, Q * S + decltype(tc)::value>{}); });
+        unroll<PD>([&](auto tc) { readB(std::integral_constant<int, Q * S + decltype(tc)::value>{}); });
     };
 
     // ---- epilogue (as ws_main KIND 0: 16-byte stores through v_permlane32_swap) ----
@@ -816,17 +797,17 @@ __device__ __forceinline__ void wr_main(const ConvArgs &a, const int grp, const 
         const bool valid = tile_coords(k, n, oy0, ox0);
         unsigned char *const obase = outb + (size_t)n * out_img_bytes;
         const bool colok = ox0 + pl < a.Wo;
-        unroll_steps<R>([&](auto rc) {
+        unroll<R>([&](auto rc) {
             constexpr int r = decltype(rc)::value;
             const int oy = oy0 + r;
             const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc((void *)obase, 0, (valid && oy < a.Ho) ? out_img_bytes : 0, 0x00020000);
             const int srow = (oy * a.Wo + ox0) * 32;
-            unroll_steps<CB>([&](auto cbc) {
+            unroll<CB>([&](auto cbc) {
                 constexpr int cb = decltype(cbc)::value;
-                unroll_steps<2>([&](auto pc) {
+                unroll<2>([&](auto pc) {
                     constexpr int jb = 2 * decltype(pc)::value;
                     u32x2 pk[2];
-                    unroll_steps<2>([&](auto dc) {
+                    unroll<2>([&](auto dc) {
                         constexpr int j = jb + decltype(dc)::value;
                         const float e0 = acc[cb][r][4 * j + 0], e1 = acc[cb][r][4 * j + 1], e2 = acc[cb][r][4 * j + 2], e3 = acc[cb][r][4 * j + 3];
                         f32x2 lo2, hi2;
