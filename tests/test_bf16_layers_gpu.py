@@ -15,7 +15,8 @@ ulp of one product, so those are graded at 4 ulps for every element and half an 
 
 This replaces comparing the r04 kernels with the kernels they replaced (tests/test_bf16_kernels_gpu.py: regression guards) as the parity statement of
 the bf16 kernels: kernels_ws.hip (conv / transposed conv walkers, the K = 2304 ring form), the bf16 tile-per-workgroup tilings, kernels_stem.hip and
-kernels_tail.hip are each checked against numpy, at the tuned 256 x 256 shape and at a shape where the small-map fall-backs run."""
+kernels_tail.hip are each checked against numpy, at the tuned 256 x 256 shape and at a shape where the small-map fall-backs run.
+tests/test_bf16_launches_gpu.py does the same for every (layer, tiling) combination of the default plans and at the batches where the walkers take several rounds."""
 import numpy as np
 import pytest
 
