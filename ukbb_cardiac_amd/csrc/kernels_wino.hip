@@ -57,13 +57,19 @@ __device__ __forceinline__ f32x4 sub4(const f32x4 &a, const f32x4 &b) {
 
 }  // namespace
 
-// Diagnostic only (-DUKBB_WINO_STAMPS + UKBB_STAMPS=1): s_memtime stamps around the phases of a stage.
+// Diagnostic only (-DUKBB_WINO_STAMPS + UKBB_STAMPS=1): two s_memtime reads per wave and stage, one on arrival at the stage barrier and
+// one on leaving it (the consumers add two per item around the epilogue).  The differences are summed in scalar registers and the
+// arithmetic of a stage is done at the next arrival, where the wave has nothing in flight that the counter read could hold up; every
+// wave writes its sums once, at the end, with ordinary vector stores.  Launch time within 5 % of the plain build (r13_notes.md).
 #ifdef UKBB_WINO_STAMPS
-#define STAMP(v) { asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory"); }
 #define STAMP_DO(...) __VA_ARGS__
-__device__ unsigned long long g_wstamps[8];
+// per workgroup and wave: work, wait, arrivals as the last wave, stages (each: [0] stages of full regions and every producer stage, [1]
+// the consumers' stages of half regions), epilogue, items, span
+constexpr int WST_WG = 256, WST_N = 11;
+__device__ unsigned g_wstamps[WST_WG * 8 * WST_N];
+// the low word is enough: a launch is far shorter than 2^32 cycles, and differences wrap correctly
+__device__ __forceinline__ unsigned st_now() { return (unsigned)__builtin_amdgcn_s_memtime(); }
 #else
-#define STAMP(v)
 #define STAMP_DO(...)
 #endif
 // NCB = blocks of 16 output channels per item.  NCB = 4: consumer wave w owns channel block w and both
@@ -71,9 +77,13 @@ __device__ unsigned long long g_wstamps[8];
 // wave w owns channel block w & 1 and tile half w >> 1 (64 MFMAs per stage).
 // TRY x (32 / TRY) tiles per region: 4 x 8 (8 x 16 pixels) or 8 x 4 (16 x 8 pixels) -- whichever wastes less of
 // the map (48 x 52: 24 regions of 8 x 16 at 81 % fill, or 21 of 16 x 8 at 93 %).
-template <int NCB, int TRY>
-__global__ __launch_bounds__(512, 2) void wino_pc_kernel(const ConvArgs a) {
+// R13 (NCB = 4 only; false = the stage loop as it was before r13, kept behind UKBB_WINO_STAGE_PARENT=1): the A queue is 8 k positions
+// deep instead of 4, and the producers share the transform of a half region's 16 tiles.  Neither changes an operand or the order of a
+// sum; what the stamps showed and what else was tried is in profiles/r13_notes.md.
+template <int NCB, int TRY, bool R13>
+__device__ __forceinline__ void wino_pc_body(const ConvArgs &a) {
     constexpr int WNCBL = NCB, TBW = NCB == 4 ? 2 : 1;
+    constexpr bool L4 = NCB == 4 && R13;
     constexpr int TRX = NT / TRY, WIH = 2 * TRY + 2, WIW = 2 * TRX + 2;
     static_assert(WIH * WIW == WHP && WIH + WIW < 31, "halo tile / mask layout");
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -174,8 +184,8 @@ __global__ __launch_bounds__(512, 2) void wino_pc_kernel(const ConvArgs a) {
         const int xt = tid & 127, x_tile = xt / C4, x_q = xt - x_tile * C4;
         const float *const xs_r = lds + L_XS + ((2 * (x_tile / TRX) + half) * RS + 2 * (x_tile % TRX)) * WXSX + 4 * x_q;
         float *const vs_w = lds + L_VS + half * 8 * NT * WXS + x_tile * WXS + 4 * x_q;
-        f32x2 e[3][4][2];
-        auto xform_read = [&](auto par) {               // issue the 12 patch reads of this thread
+        using Patch = f32x2[3][4][2];                   // a stage's own: declared where the stage is transformed, live nowhere else
+        auto xform_read = [&](auto par, Patch &e) {     // issue the 12 patch reads of this thread
             constexpr int B = decltype(par)::value;
             const float *xs = xs_r + B * XSZ;
 #pragma unroll
@@ -186,7 +196,7 @@ __global__ __launch_bounds__(512, 2) void wino_pc_kernel(const ConvArgs a) {
                     e[i][j][0] = f32x2{v[0], v[1]}; e[i][j][1] = f32x2{v[2], v[3]};
                 }
         };
-        auto xform_finish = [&](auto par) {             // row pass, column pass, 8 writes
+        auto xform_finish = [&](auto par, const Patch &e) {   // row pass, column pass, 8 writes
             constexpr int B = decltype(par)::value;
             float *vs = vs_w + B * 16 * NT * WXS;
             auto put = [&](int k, const f32x2 &lo, const f32x2 &hi) { st4(vs + k * NT * WXS, f32x4{lo[0], lo[1], hi[0], hi[1]}); };
@@ -212,6 +222,56 @@ __global__ __launch_bounds__(512, 2) void wino_pc_kernel(const ConvArgs a) {
             if (half == 0) rows(std::integral_constant<int, 0>{});
             else           rows(std::integral_constant<int, 1>{});
         };
+        // A half region (see the consumers) has real tiles in its first 16-tile block only, and its stages are the short ones: 64 MFMAs
+        // per consumer wave, less time than the transform above takes beside an MFMA stream.  There the two waves of a pair share the 16
+        // tiles: both form one of the pair's two rows of B^T d (8 reads, 8 packed adds) and its four columns (8 packed adds, 4 writes),
+        // the same operations on the same operands as above.  VS keeps whatever it held for tiles 16-31; no consumer reads them.
+        const int sub = (__builtin_amdgcn_readfirstlane(tid) >> 6) & 1;      // 0: the row `wa` above (k 0-3 / 8-11), 1: `wb` (k 4-7 / 12-15)
+        const int hl = tid & 63, h_tile = hl / C4, h_q = hl - h_tile * C4;
+        const int h_ra = (half ^ sub) ? 1 : 0, h_rb = half && !sub ? 0 : 2;   // wa: e0 - e2 | e1 - e0, wb: e1 + e2 | e0 - e2
+        const float *const xs_rh = lds + L_XS + ((2 * (h_tile / TRX) + half) * RS + 2 * (h_tile % TRX)) * WXSX + 4 * h_q;
+        const float *const xs_ha = xs_rh + h_ra * RS * WXSX, *const xs_hb = xs_rh + h_rb * RS * WXSX;
+        float *const vs_wh = lds + L_VS + (half * 8 + sub * 4) * NT * WXS + h_tile * WXS + 4 * h_q;
+        auto xform_read_h = [&](auto par, Patch &e) {
+            constexpr int B = decltype(par)::value;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const f32x4 va = ld4(xs_ha + B * XSZ + j * WXSX), vb = ld4(xs_hb + B * XSZ + j * WXSX);
+                e[0][j][0] = f32x2{va[0], va[1]}; e[0][j][1] = f32x2{va[2], va[3]};
+                e[1][j][0] = f32x2{vb[0], vb[1]}; e[1][j][1] = f32x2{vb[2], vb[3]};
+            }
+        };
+        auto xform_finish_h = [&](auto par, const Patch &e) {
+            constexpr int B = decltype(par)::value;
+            float *vs = vs_wh + B * 16 * NT * WXS;
+            auto put = [&](int k, const f32x2 &lo, const f32x2 &hi) { st4(vs + k * NT * WXS, f32x4{lo[0], lo[1], hi[0], hi[1]}); };
+            auto row = [&](auto addc) {                 // a real (uniform) branch, as above
+                f32x2 w[4][2];
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        if constexpr (decltype(addc)::value) w[j][h] = pk_add(e[0][j][h], e[1][j][h]);
+                        else                                 w[j][h] = pk_sub(e[0][j][h], e[1][j][h]);
+                    }
+                put(0, pk_sub(w[0][0], w[2][0]), pk_sub(w[0][1], w[2][1]));
+                put(1, pk_add(w[1][0], w[2][0]), pk_add(w[1][1], w[2][1]));
+                put(2, pk_sub(w[2][0], w[1][0]), pk_sub(w[2][1], w[1][1]));
+                put(3, pk_sub(w[1][0], w[3][0]), pk_sub(w[1][1], w[3][1]));
+            };
+            if (half == 0 && sub == 1) row(std::true_type{});
+            else                       row(std::false_type{});
+        };
+        // is the region of the next stage to transform a half one: the consumers' item walk, advanced once per stage on the scalar unit
+        int x_ch = 0, x_item = blockIdx.x, x_round = 0;
+        auto x_half = [&]() {
+            if (TBW != 2 || x_item >= nitems) return false;
+            int r = x_item % per_group % regions;
+            if (rotate) r = (r + x_round) % regions;
+            return (r / regs_x) * 2 * TRY + TRY >= a.Ho;
+        };
+        bool h_next = x_half();
+        auto x_advance = [&]() { if (++x_ch == nchunk) { x_ch = 0; x_item += gridDim.x; ++x_round; h_next = x_half(); } };
         constexpr std::integral_constant<int, 0> P0{};
         constexpr std::integral_constant<int, 1> P1{};
         // prologue: XS[0] <- stage 0, XS[1] <- stage 1, registers <- stage 2
@@ -219,31 +279,42 @@ __global__ __launch_bounds__(512, 2) void wino_pc_kernel(const ConvArgs a) {
         if (nstages > 1) { loadx(); storex(P1); }
         if (nstages > 2) loadx();
         __syncthreads();                                // barrier X: XS[0], XS[1] visible to every producer
-        if (nstages > 0) { xform_read(P0); xform_finish(P0); }
-        STAMP_DO(unsigned long long pw = 0, px_ = 0, pl = 0, t0, t1, t2, t3;)
+        if (nstages > 0) {
+            Patch e;
+            if (L4 && h_next) { xform_read_h(P0, e); xform_finish_h(P0, e); } else { xform_read(P0, e); xform_finish(P0, e); }
+            if constexpr (L4) x_advance();
+        }
+        STAMP_DO(const unsigned st_t0 = st_now(); unsigned st_work = 0, st_wait = 0, st_last = ~0u, st_ta = st_t0, st_tl = st_t0;)
         // One stage of the producer role.  The patch reads of the transform are issued first and their
         // latency is covered by parking stage s+2 in XS and requesting stage s+3 from global memory.
         auto stage = [&](auto par, auto npar, int s) {
-            STAMP(t0)
+            STAMP_DO({ const unsigned t = st_now();
+                       st_wait += st_tl - st_ta; st_last += st_tl - st_ta < 200 ? 1 : 0; st_work += t - st_tl; st_ta = t; })
             __syncthreads();                            // barrier #s: VS[s&1] ready / VS[(s+1)&1], XS[s&1] free
-            STAMP(t1)
+            STAMP_DO(st_tl = st_now();)
             const bool xf = s + 1 < nstages;
-            if (xf) xform_read(npar);
+            const bool hx = L4 && h_next;               // uniform
+            Patch e;                                    // a stage's own: nothing of it is live across the barrier
+            if (xf) { if (hx) xform_read_h(npar, e); else xform_read(npar, e); }
             __builtin_amdgcn_sched_barrier(0);
             if (s + 2 < nstages) storex(par);           // stage s+2 (requested an iteration ago) replaces stage s
             if (s + 3 < nstages) loadx();
             __builtin_amdgcn_sched_barrier(0);
-            STAMP(t2)
-            if (xf) xform_finish(npar);
-            STAMP(t3)
-            STAMP_DO(pw += t1 - t0; px_ += t2 - t1; pl += t3 - t2;)
+            if (xf) { if (hx) xform_finish_h(npar, e); else xform_finish(npar, e); }
+            if constexpr (L4) { if (xf) x_advance(); }
         };
 #pragma unroll 1
         for (int s = 0; s < nstages; s += 2) {
             stage(P0, P1, s);
             if (s + 1 < nstages) stage(P1, P0, s + 1);
         }
-        STAMP_DO(if (threadIdx.x == 256) { atomicAdd(g_wstamps + 0, pw); atomicAdd(g_wstamps + 1, px_); atomicAdd(g_wstamps + 2, pl); atomicAdd(g_wstamps + 3, (unsigned long long)nstages); })
+        STAMP_DO(if (a.diag & 64) {                     // UKBB_STAMPS=1.  The first arrival adds a wait of 0 and one `last`: st_last starts at -1
+            st_wait += st_tl - st_ta; st_last += st_tl - st_ta < 200 ? 1 : 0;
+            if ((threadIdx.x & 63) == 0 && blockIdx.x < WST_WG) {
+                unsigned *o = g_wstamps + (blockIdx.x * 8 + (threadIdx.x >> 6)) * WST_N;
+                o[0] = st_work; o[2] = st_wait; o[4] = st_last; o[6] = (unsigned)nstages; o[10] = st_now() - st_t0;
+            }
+        })
     } else {
         const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
         const int wave = NCB == 4 ? wid : (wid & 1);        // Cout block within the item
@@ -251,10 +322,18 @@ __global__ __launch_bounds__(512, 2) void wino_pc_kernel(const ConvArgs a) {
         const int t16 = lane & 15, g = lane >> 4;
         __syncthreads();                                // barrier X
         int s = 0;
-        constexpr int AD = TBW == 2 ? 4 : 8;             // A-fragment queue depth (k positions)
+        // A-fragment queue depth (k positions).  A half region's stage is 64 MFMAs, 128 cycles per k position: four positions ahead was
+        // less than the L2 latency, and the MFMA waves waited for their weights there (r13)
+        constexpr int AD = TBW == 2 && !L4 ? 4 : 8;
         constexpr int BA = TBW == 2 ? 1 : 2, BR = BA + 1; // B lookahead (k positions) and ring size
         f32x4 aq[AD];
-        STAMP_DO(unsigned long long cw = 0, cc = 0, ce = 0, c0, c1, c2, c3;)
+        STAMP_DO(const unsigned st_t0 = st_now();
+                 unsigned st_work[2] = {0, 0}, st_wait[2] = {0, 0}, st_last[2] = {0, 0}, st_n[2] = {0, 0}, st_epi = 0, st_items = 0, st_ta = st_t0, st_tl = st_t0;
+                 auto st_close = [&](bool h, unsigned t) {    // the stage whose barrier was reached at st_ta and left at st_tl ends at t
+                     const unsigned wt = st_tl - st_ta, wk = t - st_tl, l = wt < 200 ? 1 : 0;   // 200: a wave that waited less released the barrier
+                     if (h) { st_wait[1] += wt; st_work[1] += wk; st_last[1] += l; st_n[1] += 1; }
+                     else   { st_wait[0] += wt; st_work[0] += wk; st_last[0] += l; st_n[0] += 1; }
+                 };)
         int round = 0;
         for (int item = blockIdx.x; item < nitems; item += gridDim.x, ++round) {
             const int grp = item / per_group, rest = item - grp * per_group;
@@ -283,9 +362,11 @@ __global__ __launch_bounds__(512, 2) void wino_pc_kernel(const ConvArgs a) {
             auto chunk = [&](auto firstc, auto halfc, int ch) {
                 constexpr bool FIRST = decltype(firstc)::value;
                 constexpr bool TWO = TBW == 2 && !decltype(halfc)::value;   // second 16-tile block holds real tiles
-                STAMP(c0)
+                STAMP_DO({ const unsigned t = st_now();
+                           if constexpr (!FIRST) st_close(decltype(halfc)::value, t);   // an item's last stage is closed in front of the epilogue
+                           st_ta = t; })
                 __syncthreads();                        // barrier #s
-                STAMP(c1)
+                STAMP_DO(st_tl = st_now();)
                 const float *vs = lds + L_VS + (s & 1) * 16 * NT * WXS + (tb0 * 16 + t16) * WXS + 4 * g;
                 const float *wp = wbase + (size_t)ch * WNCBL * (16 * 64 * 4);
                 const float *wn = ch + 1 < nchunk ? wp + WNCBL * (16 * 64 * 4) : wnext;
@@ -319,8 +400,6 @@ __global__ __launch_bounds__(512, 2) void wino_pc_kernel(const ConvArgs a) {
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 });
-                STAMP(c2)
-                STAMP_DO(cw += c1 - c0; cc += c2 - c1;)
                 ++s;
             };
             // A region whose lower two tile rows lie entirely below the image (12-row maps: rows 8-11 of the second
@@ -335,7 +414,7 @@ __global__ __launch_bounds__(512, 2) void wino_pc_kernel(const ConvArgs a) {
 #pragma unroll 1
                 for (int ch = 1; ch < nchunk; ++ch) chunk(std::false_type{}, std::false_type{}, ch);
             }
-            STAMP(c2)
+            STAMP_DO(const unsigned st_te = st_now(); st_close(half, st_te);)
             // ---- output transform Y = A^T M A, bias, ReLU, NHWC stores -----------------------------
             // The packed adds below are inline asm, which the compiler's hazard recogniser does not treat as a
             // VALU read of MFMA results: cover the MFMA -> VALU wait states (11 for this 8-pass MFMA) by hand.
@@ -373,14 +452,54 @@ __global__ __launch_bounds__(512, 2) void wino_pc_kernel(const ConvArgs a) {
                         if (oy + i < a.Ho && ox + j < a.Wo) st4(o00 + i * dy + j * dx, v);
                     }
             }
-            STAMP(c3)
-            STAMP_DO(ce += c3 - c2;)
+            STAMP_DO(st_epi += st_now() - st_te; st_items += 1;)
         }
-        STAMP_DO(if (threadIdx.x == 0) { atomicAdd(g_wstamps + 4, cw); atomicAdd(g_wstamps + 5, cc); atomicAdd(g_wstamps + 6, ce); })
+        STAMP_DO(if ((a.diag & 64) && lane == 0 && blockIdx.x < WST_WG) {
+            unsigned *o = g_wstamps + (blockIdx.x * 8 + wid) * WST_N;
+            for (int h = 0; h < 2; ++h) { o[h] = st_work[h]; o[2 + h] = st_wait[h]; o[4 + h] = st_last[h]; o[6 + h] = st_n[h]; }
+            o[8] = st_epi; o[9] = st_items; o[10] = st_now() - st_t0;
+        })
     }
 }
 
+template <int NCB, int TRY>
+__global__ __launch_bounds__(512, 2) void wino_pc_kernel(const ConvArgs a) { wino_pc_body<NCB, TRY, true>(a); }
+// the stage loop from before r13, for A/B (UKBB_WINO_STAGE_PARENT=1; the NCB = 2 instances have one form only)
+template <int NCB, int TRY>
+__global__ __launch_bounds__(512, 2) void wino_pc_parent_kernel(const ConvArgs a) { wino_pc_body<NCB, TRY, false>(a); }
+
 int wino_lds_bytes() { return WINO_LDS_FLOATS * 4; }
+
+#ifdef UKBB_WINO_STAMPS
+static unsigned *stamps_ptr() { void *p = nullptr; (void)hipGetSymbolAddress(&p, HIP_SYMBOL(g_wstamps)); return (unsigned *)p; }
+// One line per role and region kind: cycles per stage as the mean over waves and workgroups, then the four waves' own means.
+static void report_stamps(const ConvArgs &a, int grid) {
+    static unsigned h[WST_WG * 8 * WST_N];
+    (void)hipMemcpy(h, stamps_ptr(), sizeof(h), hipMemcpyDeviceToHost);       // synchronises with the launch
+    const int nwg = grid < WST_WG ? grid : WST_WG;
+    fprintf(stderr, "WINOSTAMPS Cin %d Cout %d Ho %d Wo %d N %d grid %d\n", a.C0 + a.C1, a.Cout, a.Ho, a.Wo, a.N, grid);
+    for (int role = 0; role < 2; ++role)
+        for (int hk = 0; hk < (role ? 1 : 2); ++hk) {
+            double work[4] = {0}, wait[4] = {0}, last[4] = {0}, n[4] = {0}, spread = 0, epi = 0, items = 0, span = 0; int nsp = 0;
+            for (int g = 0; g < nwg; ++g) {
+                double lo = 1e30, hi = -1;
+                for (int w = 0; w < 4; ++w) {
+                    const unsigned *o = h + (g * 8 + role * 4 + w) * WST_N;
+                    work[w] += (double)o[hk]; wait[w] += (double)o[2 + hk]; last[w] += (double)o[4 + hk]; n[w] += (double)o[6 + hk];
+                    epi += (double)o[8]; items += (double)o[9]; span += (double)o[10];
+                    if (o[6 + hk]) { const double m = (double)o[2 + hk] / (double)o[6 + hk]; lo = m < lo ? m : lo; hi = m > hi ? m : hi; }
+                }
+                if (hi >= 0) { spread += hi - lo; ++nsp; }
+            }
+            if (n[0] + n[1] + n[2] + n[3] == 0) continue;
+            fprintf(stderr, "  %s %s: stages/wave %.1f | work %.0f %.0f %.0f %.0f | barrier wait %.0f %.0f %.0f %.0f | last to arrive %.2f %.2f %.2f %.2f | "
+                            "wait(max wave) - wait(min wave) per workgroup %.0f | epilogue/item %.0f | span %.0f\n",
+                    role ? "producers" : "consumers", role ? "all" : hk ? "half regions" : "full regions", n[0] / nwg,
+                    work[0] / n[0], work[1] / n[1], work[2] / n[2], work[3] / n[3], wait[0] / n[0], wait[1] / n[1], wait[2] / n[2], wait[3] / n[3],
+                    last[0] / n[0], last[1] / n[1], last[2] / n[2], last[3] / n[3], nsp ? spread / nsp : 0.0, items ? epi / items : 0.0, span / (4.0 * nwg));
+        }
+}
+#endif
 
 template <int NCB, int TRY>
 static hipError_t launch_wino_t(const ConvArgs &a, hipStream_t s) {
@@ -390,21 +509,16 @@ static hipError_t launch_wino_t(const ConvArgs &a, hipStream_t s) {
     const int regs_x = (a.Wo + 2 * TRX - 1) / (2 * TRX), regs_y = (a.Ho + 2 * TRY - 1) / (2 * TRY);
     const long long nitems = (long long)a.N * regs_x * regs_y * (a.Cout / (16 * NCB));
     dim3 grid((unsigned)(nitems < n_cu ? nitems : n_cu));
+    static const bool parent = [] { const char *e = getenv("UKBB_WINO_STAGE_PARENT"); return e && atoi(e) != 0; }();   // A/B knob (r13), latched
 #ifdef UKBB_WINO_STAMPS
-    const bool on = getenv("UKBB_STAMPS") != nullptr;
-    unsigned long long z[8] = {0};
-    if (on) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wstamps), z, 64);
+    const bool on = (a.diag & 64) != 0;
+    if (on) (void)hipMemset(stamps_ptr(), 0, sizeof(unsigned) * WST_WG * 8 * WST_N);
 #endif
-    const hipError_t e = launch_lds<wino_pc_kernel<NCB, TRY>>(grid, dim3(512), WINO_LDS_FLOATS * 4, s, a);
+    hipError_t e;
+    if (NCB == 4 && parent) e = launch_lds<wino_pc_parent_kernel<NCB, TRY>>(grid, dim3(512), WINO_LDS_FLOATS * 4, s, a);
+    else                     e = launch_lds<wino_pc_kernel<NCB, TRY>>(grid, dim3(512), WINO_LDS_FLOATS * 4, s, a);
 #ifdef UKBB_WINO_STAMPS
-    if (on) {
-        unsigned long long h[8];
-        (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_wstamps), 64);
-        const double st = (double)h[3];
-        fprintf(stderr, "WINOSTAMPS Cin %d Cout %d Ho %d: per stage: producer wait %.0f read+store+load %.0f transform %.0f | consumer wait %.0f "
-                        "mfma %.0f epilogue(avg/stage) %.0f (stages/WG %.0f)\n", a.C0 + a.C1, a.Cout, a.Ho, h[0] / st, h[1] / st, h[2] / st,
-                h[4] / st, h[5] / st, h[6] / st, st / grid.x);
-    }
+    if (on) report_stamps(a, (int)grid.x);
 #endif
     return e;
 }
@@ -412,7 +526,7 @@ static hipError_t launch_wino_t(const ConvArgs &a, hipStream_t s) {
 hipError_t launch_wino(const ConvArgs &a_in, int ncb, int tile_rows, hipStream_t s) {
     ConvArgs a = a_in;
 #ifdef UKBB_WINO_STAMPS
-    { const char *e = getenv("UKBB_CONV_DIAG"); a.diag = e ? atoi(e) : 0; }
+    { const char *e = getenv("UKBB_CONV_DIAG"); a.diag = (e ? atoi(e) & 32 : 0) | (getenv("UKBB_STAMPS") ? 64 : 0); }
 #endif
     if (ncb == 4) return tile_rows == 8 ? launch_wino_t<4, 8>(a, s) : launch_wino_t<4, 4>(a, s);
     if (ncb == 2) return tile_rows == 8 ? launch_wino_t<2, 8>(a, s) : launch_wino_t<2, 4>(a, s);
