@@ -377,6 +377,30 @@ int ukbb_fcn_plane_components(const uint8_t *d_planes, int X, int Y, int P, int 
 int ukbb_fcn_atrial_area_length(const uint8_t *d_planes, int X, int Y, int P, int n_class, const double affine[12], const double long_axis[3],
                                 int32_t *d_work, int32_t *d_out, void *stream);
 
+/* -- overlap and contour distances of two label volumes (additive to ABI 11): np_categorical_dice and distance_metric (reference
+ * common/image_utils.py:171-224) for every (plane, class) cell of P label planes of X*Y uint8 voxels (x fastest: d_pred as
+ * ukbb_fcn_unpack_labels leaves it, d_truth a second volume of the same layout), by the rules ukbb_cardiac_amd/seg_score.py states
+ * (stats_host is the specification).  With A = pred plane == k, B = truth plane == k:
+ *   d_cells[p][k][8] (int32, all P*n_class*8 written; the cells of class 0 are zero) = status, nA, nB, nAB, cA, cB, hA, hB
+ *     nA, nB, nAB   |A|, |B|, |A & B|
+ *     status        1 when nA > 0 and nB > 0 (the distances are defined), else 0 and the five fields below are zero
+ *     cA, cB        the contour pixels of A and of B: the pixels of the mask with a 4-neighbour off the image or in the outer
+ *                   background (the non-mask pixels 4-connected to the image frame) -- the set cv2.findContours(RETR_EXTERNAL,
+ *                   CHAIN_APPROX_NONE) visits
+ *     hA, hB        max over the contour of A of the smallest squared pixel distance to the contour of B, and the other way round
+ *   d_sums[p][k][2] (float64) = sA, sB: the sum over the contour of A (of B) of the square root of that smallest squared distance,
+ *                   the pixels taken in the order x*Y + y and added as np.add.reduce adds a contiguous float64 array (numpy's
+ *                   pairwise tree, one per 8192-element buffer).
+ * The outer background is flooded to a fixed point; the distances come from the exact two-phase squared Euclidean transform, at
+ * most X*Y + c*X steps per direction whatever the labels are: no capacity, no decline.  Integer minima, maxima and adds only, the
+ * float64 additions in a fixed order: nothing depends on arrival order.  Labels >= n_class are ignored.  d_work: 16-byte aligned,
+ * ukbb_fcn_score_planes_work(X, Y, P, n_class) bytes (0 for a shape the call refuses), at most 64 MB.  d_sums 8-byte aligned.
+ * Asynchronous.  n_class 2..16, P <= 65535; X, Y <= 1024 and ceil(X/32)*Y <= 8192 (the bit planes of one cell live in LDS:
+ * 512 x 512 fits): a larger plane returns UKBB_EINVAL with a message and the caller scores it on the host. */
+uint64_t ukbb_fcn_score_planes_work(int X, int Y, int P, int n_class);
+int ukbb_fcn_score_planes(const uint8_t *d_pred, const uint8_t *d_truth, int X, int Y, int P, int n_class, void *d_work, int32_t *d_cells,
+                          double *d_sums, void *stream);
+
 /* ---- label-volume files (host only: no device, no stream) ---------------------------------------
  * What the reference does with the result: nib.save of np.zeros(image.shape) filled with the labels
  * (common/deploy_network.py:92,116,136-138; deploy_network_ao.py:189-196) -- for a short-axis subject

@@ -418,14 +418,15 @@ def _cell(v):
     return measures._fmt(v)
 
 
-def write_frames_csv(path, rows):
+def write_frames_csv(path, rows, columns=None):
     """rows: [(subject, [FRAME_COLUMNS values])], one per (subject, frame, label).  Floats as measures.write_csv writes them
-    (repr: they read back exactly), written under a temporary name and renamed."""
+    (repr: they read back exactly), written under a temporary name and renamed.  columns: those of another table with several rows
+    per subject (seg_score.SCORE_COLUMNS)."""
     import csv
     import io
     buf = io.StringIO()
     wr = csv.writer(buf, lineterminator='\n')
-    wr.writerow([''] + FRAME_COLUMNS)
+    wr.writerow([''] + list(FRAME_COLUMNS if columns is None else columns))
     for subject, vals in rows:
         wr.writerow([subject] + [_cell(v) for v in vals])
     tmp = '%s.tmp.%d' % (path, os.getpid())

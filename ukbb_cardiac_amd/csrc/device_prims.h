@@ -62,6 +62,28 @@ __device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) { f32x2 r; asm("v_pk_a
 // a * b + c (v_pk_fma_f32; a scalar factor is splat into a register pair by the caller)
 __device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) { f32x2 r; asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
 
+// One leaf of numpy's pairwise summation tree (loops_utils.h.src, pairwise_sum with PW_BLOCKSIZE = 128): the sum of val(0) .. val(n - 1),
+// n <= 128, in numpy's order -- plain for n < 8, else 8 interleaved accumulators, their tree, then the remainder.  A = the type numpy
+// accumulates in.  The callers (kernels_prep.hip, kernels_score.hip) run one thread per leaf and combine the leaves up numpy's tree.
+template <class A, class V>
+__device__ __forceinline__ A pairwise_leaf(int n, V &&val) {
+    A res;
+    if (n < 8) {
+        res = 0;
+        for (int i = 0; i < n; ++i) res += val(i);
+    } else {
+        A r0 = val(0), r1 = val(1), r2 = val(2), r3 = val(3), r4 = val(4), r5 = val(5), r6 = val(6), r7 = val(7);
+        int i = 8;
+        for (; i < n - (n % 8); i += 8) {
+            r0 += val(i); r1 += val(i + 1); r2 += val(i + 2); r3 += val(i + 3);
+            r4 += val(i + 4); r5 += val(i + 5); r6 += val(i + 6); r7 += val(i + 7);
+        }
+        res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
+        for (; i < n; ++i) res += val(i);
+    }
+    return res;
+}
+
 // Host side of a kernel templated on the class count: f(integral_constant<int, C>{}) for the counts the launchers instantiate
 // (n_class 2, 3, 4: the reference's models); false, and no call, for any other.
 template <class F>

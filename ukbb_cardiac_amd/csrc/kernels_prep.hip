@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/ukbb_fcn.h"
+#include "device_prims.h"
 #include "kernels.h"
 
 namespace ukbb {
@@ -288,7 +289,7 @@ __global__ __launch_bounds__(256) void roi_write_kernel(const T *__restrict__ vo
         if (keep[k]) out[pos++] = v[k];
 }
 
-// one thread = one leaf of numpy's pairwise summation tree (loops_utils.h.src, pairwise_sum with PW_BLOCKSIZE = 128).
+// one thread = one leaf of numpy's pairwise summation tree (pairwise_leaf, device_prims.h).
 // A = the type numpy accumulates in: float for a float32 ROI, double for an integer one (np.mean / np.var of integer data
 // reduce with dtype float64; every value is exact in it, and so is every partial sum of the plain sum: < 2^53).
 template <typename T, typename A>
@@ -300,21 +301,7 @@ __global__ __launch_bounds__(128) void pairwise_leaf_kernel(const T *__restrict_
     const T *p = a + leaf_off[l];
     const int n = (int)leaf_len[l];
     auto val = [&](int i) { A v = (A)p[i]; if (sq) { const A d = v - mean; v = d * d; } return v; };
-    A res;
-    if (n < 8) {
-        res = 0;
-        for (int i = 0; i < n; ++i) res += val(i);
-    } else {
-        A r0 = val(0), r1 = val(1), r2 = val(2), r3 = val(3), r4 = val(4), r5 = val(5), r6 = val(6), r7 = val(7);
-        int i = 8;
-        for (; i < n - (n % 8); i += 8) {
-            r0 += val(i); r1 += val(i + 1); r2 += val(i + 2); r3 += val(i + 3);
-            r4 += val(i + 4); r5 += val(i + 5); r6 += val(i + 6); r7 += val(i + 7);
-        }
-        res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
-        for (; i < n; ++i) res += val(i);
-    }
-    leaf_sum[l] = res;
+    leaf_sum[l] = pairwise_leaf<A>(n, val);
 }
 
 __device__ __forceinline__ float div_rn(float a, float b) { return __fdiv_rn(a, b); }

@@ -16,7 +16,7 @@ and writes the same files (``deploy_network.py:136-151,207-216``):
 
 Extra flags (not in the reference): ``--device``, ``--batch_slices``,
 ``--num_shards`` / ``--shard_index`` (multi-GPU batch split), ``--output_csv``, ``--qc_csv``,
-``--atrial_csv``, ``--device_inflate`` (gzip inputs inflated on the GPU), ``--device_label_gzip`` (label
+``--atrial_csv``, ``--score_against`` / ``--score_csv`` (Dice and contour distances against a second segmentation), ``--device_inflate`` (gzip inputs inflated on the GPU), ``--device_label_gzip`` (label
 volumes deflated on the GPU).
 """
 import os
@@ -85,6 +85,14 @@ def define_flags():
                      'coordinates and the verdict of the atrial gate -- from the labels while they are on the GPU.  The long axis comes from '
                      '<subject>/sa.nii.gz; a subject without it gets no rows.  eval_atrial_volume.py --frames_2ch / --frames_4ch turns two '
                      'such files into the table of long_axis/eval_atrial_volume.py.')
+    fs.DEFINE_string('score_against', '', 'With --score_csv: the stem of the label file to score every segmentation against, '
+                     '<subject>/<STEM>.nii.gz (label_sa: the manual annotations in the layout of data/prepare_data_ukbb2964.py; seg_sa of another '
+                     'directory tree linked in: another tool\'s result).')
+    fs.DEFINE_string('score_csv', '', 'Sequence mode, with --score_against: also write one row per (subject, annotated frame, label) with the '
+                     'Dice overlap, the mean contour distance and the Hausdorff distance (mm) of common/image_utils.py np_categorical_dice and '
+                     'distance_metric, from the labels while they are on the GPU.  A subject without the file, or whose file has another '
+                     'shape or a label the model does not have, gets no rows; frames without a non-zero truth label give none.  Subjects '
+                     'already segmented by an earlier run are scored from their files.')
     fs.DEFINE_integer('num_shards', env_cnt, 'Number of workers sharing data_dir.')
     fs.DEFINE_integer('shard_index', env_idx, 'This worker: subjects i with i % num_shards == shard_index.')
     fs.DEFINE_boolean('work_stealing', True, 'With num_shards > 1: after its own share a worker takes subjects of the other shards that '
@@ -114,7 +122,7 @@ def run(FLAGS, forward, log=print, engine=None):
                        stealing=bool(getattr(FLAGS, 'work_stealing', False)) and FLAGS.process_seq)
     data_list = list(queue)
     processed, table_time = [], []
-    tables = LabelTables(FLAGS, engine)                 # --output_csv, --qc_csv, --atrial_csv: flag checks first
+    tables = LabelTables(FLAGS, engine)                 # --output_csv, --qc_csv, --atrial_csv, --score_csv: flag checks first
     shard_subjects = list(queue.static)                 # whose earlier-run results this worker measures for the tables
     on_device = device_path(FLAGS, engine)
     inflate = int(getattr(FLAGS, 'device_inflate', 0) or 0) > 0

@@ -168,7 +168,7 @@ def segment_sequence_device(image, engine, batch_slices=128, thres=(1, 99), retu
     save image frames afterwards clip them with the returned bounds (``aux['clip']``: the float64
     percentiles; clip_like_reference stores them into an integer frame truncated, as numpy does).
     ``aux['counts'][t, c]`` = voxels of class c in frame t (input of the ES pick).  ``stats`` (needs ``return_aux``): label
-    statistics (GateStats, AtrialStats) to compute from the labels while they are still on the device, ``stat_args`` their
+    statistics (GateStats, AtrialStats, ScoreStats) to compute from the labels while they are still on the device, ``stat_args`` their
     per-subject arguments {key: arg}: ``aux['stats']`` = {key: decoded statistic} (label_statistics)."""
     import torch
     if stats and not return_aux:
@@ -416,7 +416,8 @@ def device_qc_stats(vol_t, lab_t, dtype, n_class, stream=0, min_size=None):
     return {'n_large': n_large.cpu().numpy(), 'max': mx.cpu().numpy(), 'mean_ed': np.array(means, dtype=rt)}
 
 
-# ---- statistics of the label volume ukbb_fcn_unpack_labels left in HBM: the gates (qc_gates.py), the atria (atrial.py) ------------
+# ---- statistics of the label volume ukbb_fcn_unpack_labels left in HBM: the gates (qc_gates.py), the atria (atrial.py), the score against a
+# second segmentation (seg_score.py) -----------------------------------------------------------------------------------------------------
 # A statistic has a ``key``, says whether it takes a per-subject argument (``needs_arg``), and knows the (work, out) int32 counts
 # of its device buffers (``sizes``), how to enqueue itself on a stream (``launch``; the work buffer 8-byte aligned; asynchronous)
 # and how to read the host copy of what it wrote (``decode``).  SubjectPipeline keeps such buffers per slot; label_statistics
@@ -486,6 +487,49 @@ class AtrialStats:
     def decode(self, out, shape, n_class, counts=None):
         T = shape[3]
         return np.asarray(out, dtype=np.int32)[:T * n_class * 8].reshape(T, n_class, 8).copy()
+
+
+class ScoreStats:
+    """seg_score.stats_host -- overlap counts and contour distances per (plane, class) -- of an (X,Y,Z,T) label volume against a second
+    one (ukbb_fcn_score_planes).  Per-subject argument: the truth volume, a uint8 (X,Y,Z,T) array; it is uploaded once, on the
+    stream the statistic is enqueued on, and only the Z*T*n_class*48 bytes of results cross back.  A plane larger than the kernel's
+    bit planes hold (``fits``) is for seg_score.stats_host."""
+    key, needs_arg = 'score', True
+
+    def __init__(self, device=None):
+        self.device = device                                          # of the label volume; None: torch's current device
+
+    @staticmethod
+    def fits(shape, n_class):
+        X, Y, Z, T = shape
+        return Z * T <= 65535 and int(_lib.lib.ukbb_fcn_score_planes_work(X, Y, Z * T, max(2, n_class))) > 0
+
+    def sizes(self, shape, n_class):
+        X, Y, Z, T = shape
+        P = Z * T
+        return (int(_lib.lib.ukbb_fcn_score_planes_work(X, Y, P, max(2, n_class))) + 3) // 4, P * n_class * 12
+
+    def launch(self, lab_ptr, shape, n_class, work_ptr, out_ptr, stream, arg):
+        import contextlib
+        import torch
+        X, Y, Z, T = shape
+        truth = np.asarray(arg)
+        if truth.dtype != np.uint8 or truth.shape != tuple(shape):
+            raise ValueError('the truth volume is a uint8 array of the shape of the labels %s, got %s %s' % (tuple(shape), truth.dtype, truth.shape))
+        flat = np.asfortranarray(truth).reshape(-1, order='F')
+        # torch's allocator ties the block to the stream current at the allocation: freed behind the launch, it is handed out again
+        # only in stream order
+        with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=self.device)) if stream else contextlib.nullcontext():
+            d_truth = torch.from_numpy(flat).to(torch.device('cuda', torch.cuda.current_device() if self.device is None else self.device))
+            P = Z * T
+            _lib.check(_lib.lib.ukbb_fcn_score_planes(lab_ptr, d_truth.data_ptr(), X, Y, P, n_class, work_ptr, out_ptr, out_ptr + 32 * P * n_class,
+                                                      stream), 'ukbb_fcn_score_planes')
+
+    def decode(self, out, shape, n_class, counts=None):
+        P = shape[2] * shape[3]
+        out = np.ascontiguousarray(np.asarray(out, dtype=np.int32)[:P * n_class * 12])
+        return {'shape': tuple(int(v) for v in shape), 'cells': out[:P * n_class * 8].reshape(P, n_class, 8).copy(),
+                'sums': out[P * n_class * 8:].view(np.float64).reshape(P, n_class, 2).copy()}
 
 
 def stat_skipped(stat, stat_args):

@@ -1,19 +1,20 @@
 """The tables deploy_network.py derives from a label map while it segments: ``--output_csv`` (ventricular volumes, measures.py),
-``--qc_csv`` (the sa / la / atrium gate, qc_gates.py) and ``--atrial_csv`` (atrial areas and lengths per frame, atrial.py).
+``--qc_csv`` (the sa / la / atrium gate, qc_gates.py), ``--atrial_csv`` (atrial areas and lengths per frame, atrial.py) and
+``--score_csv`` (Dice and contour distances against the label file --score_against names, seg_score.py).
 
 One ``LabelTables`` is made per run from the flags.  It checks the flags, names the device statistics the run needs of every
 label volume (``statistics``), gives the per-subject arguments of those statistics (``subject_args``), turns one subject's class
 counts and statistics into rows (``record``) and at the end writes the tables, measuring the subjects an earlier run segmented
 from their files (``write``).  Statistics arrive as ``{key: value}`` -- 'qc': qc_gates.stats_host or device_pipeline.GateStats,
-'atrial': atrial.frame_stats_host or device_pipeline.AtrialStats -- from the device (SubjectPipeline, segment_sequence_device) or
-from the host twins (``from_labels``).
+'atrial': atrial.frame_stats_host or device_pipeline.AtrialStats, 'score': seg_score.stats_host or device_pipeline.ScoreStats -- from
+the device (SubjectPipeline, segment_sequence_device) or from the host twins (``from_labels``).
 
 ``AorticTable`` is the same for deploy_network_ao.py --output_csv (aortic areas and distensibility, measures.py): it checks the
 flags, applies the quality control of --aortic_qc / --aortic_qc_full to the class counts and aorta_qc statistics of a subject
 (``record``; ``from_labels``: the host twins) and writes the table.  The aortic run never skips a segmented subject: no back-fill."""
 import os
 
-from . import aorta_qc, atrial, measures, nifti, qc_gates
+from . import aorta_qc, atrial, measures, nifti, qc_gates, seg_score
 
 
 class LabelTables:
@@ -21,6 +22,7 @@ class LabelTables:
         self.FLAGS = FLAGS
         self.seq, self.seg4 = seq, seg4 = FLAGS.seq_name, FLAGS.seg4
         self.n_class = n_class = None if engine is None else engine.arch.n_class
+        self.device = None if engine is None else getattr(engine, 'device', None)
         self.output_csv, self.qc_csv, self.atrial_csv = (getattr(FLAGS, f, '') for f in ('output_csv', 'qc_csv', 'atrial_csv'))
         if self.output_csv and (seq != 'sa' or not FLAGS.process_seq):
             raise ValueError('--output_csv writes the table of short_axis/eval_ventricular_volume.py: it needs --seq_name sa in sequence mode')
@@ -36,21 +38,62 @@ class LabelTables:
                                  'without --seg4, in sequence mode')
             if n_class is not None and n_class < qc_gates.min_classes(seq):
                 raise ValueError('--atrial_csv: --seq_name {0} has {1} classes, the model has {2}'.format(seq, qc_gates.min_classes(seq), n_class))
+        self.score_against, self.score_csv = (getattr(FLAGS, f, '') for f in ('score_against', 'score_csv'))
+        if bool(self.score_against) != bool(self.score_csv):
+            raise ValueError('--score_against names the label file to score against and --score_csv the table to write: they need each other')
+        if self.score_csv and not FLAGS.process_seq:
+            raise ValueError('--score_csv scores the segmentation of a whole sequence: it needs sequence mode (--process_seq)')
         # subject -> row(s).  The atrial rows carry the gate's verdict: gated, though no --qc_csv is written
         self.volumes = {} if self.output_csv else None
         self.gate = {} if self.qc_csv or self.atrial_csv else None
         self.atrial = {} if self.atrial_csv else None
+        self.score = {} if self.score_csv else None
+        self._unscored = set()                          # data_dirs whose truth file is absent or refused: logged once, no back-fill
 
     def statistics(self):
         """The device statistics this run needs of every label volume.  Device paths only: device_pipeline loads the HIP library."""
         from . import device_pipeline
         return ([device_pipeline.GateStats(self.seq, self.seg4)] if self.gate is not None else []) + \
-            ([device_pipeline.AtrialStats()] if self.atrial is not None else [])
+            ([device_pipeline.AtrialStats()] if self.atrial is not None else []) + \
+            ([device_pipeline.ScoreStats(self.device)] if self.score is not None else [])
 
-    def subject_args(self, data_dir, nim, log):
+    def subject_args(self, data_dir, nim, log, truth=None):
         """{key: argument} of the statistics that take one per subject.  --atrial_csv: (affine of the long-axis image, long axis), the
         long axis from the short-axis header as eval_atrial_volume.py:45-48 -- absent, and logged, for a subject without sa.nii.gz (the
-        reference skips it) or with more than one slice."""
+        reference skips it) or with more than one slice.  --score_csv: the truth volume <subject>/<--score_against>.nii.gz as uint8 --
+        absent, and logged, for a subject without the file (the reference's loops ``continue``) or whose file has another shape
+        than the image, non-integral values or a label the model does not have.  A subject whose planes the device form does not
+        hold gets no argument either: it is scored from its label file when the tables are written.  truth: what ``read_truth`` gave
+        for this subject on a reader thread, where the loop has such threads."""
+        args = self._atrial_args(data_dir, nim, log)
+        if truth is None:
+            truth = self.read_truth(data_dir, nim.shape, log)
+        if truth is not None:
+            from . import device_pipeline
+            if device_pipeline.ScoreStats.fits(truth.shape, self.n_class or 2):
+                args['score'] = truth
+            else:
+                log('  {0} x {1} planes are larger than the device scores: scored on the host from the label file.'.format(*truth.shape[:2]))
+        return args
+
+    def read_truth(self, data_dir, shape, log):
+        """The truth volume of --score_against for a subject whose image has ``shape``, checked, as uint8; None, and logged once, for a
+        subject that has none or whose file is refused.  Reads and inflates a file: for the reader threads."""
+        if self.score is None or data_dir in self._unscored:
+            return None
+        name = '{0}/{1}.nii.gz'.format(data_dir, self.score_against)
+        if not os.path.exists(name):
+            log('  Directory {0} does not contain {1}.nii.gz: nothing to score against.'.format(data_dir, self.score_against))
+            self._unscored.add(data_dir)
+            return None
+        try:
+            return seg_score.check_truth(nifti.load(name).get_data(), shape, self.n_class or seg_score.MAX_CLASSES)
+        except Exception as e:                          # a shape or label check_truth refuses, a file nifti.load cannot read
+            log('  {0} cannot be scored against: {1}. Skip.'.format(name, e))
+            self._unscored.add(data_dir)
+            return None
+
+    def _atrial_args(self, data_dir, nim, log):
         if self.atrial is None:
             return {}
         sa_name = '{0}/sa.nii.gz'.format(data_dir)
@@ -71,6 +114,8 @@ class LabelTables:
             stats['qc'] = qc_gates.stats_host(seg, self.seq, self.seg4, n_class)
         if 'atrial' in args:
             stats['atrial'] = atrial.frame_stats_host(seg[:, :, 0, :], self.n_class or qc_gates.min_classes(self.seq), *args['atrial'])
+        if 'score' in args:
+            stats['score'] = seg_score.stats_host(seg, args['score'], self.n_class or max(2, int(max(seg.max(), args['score'].max())) + 1))
         return counts, stats
 
     def record(self, data, data_dir, nim, counts, stats, log):
@@ -85,6 +130,8 @@ class LabelTables:
                 log(message)
         if 'atrial' in stats:
             self.atrial[data] = atrial.frame_rows(stats['atrial'], nim.affine, nim.header['pixdim'], self.gate[data][0])
+        if 'score' in stats:
+            self.score[data] = seg_score.frame_rows(stats['score'], nim.header['pixdim'])
 
     def _back_fill(self, rows, data, log):
         """A subject segmented by an earlier run (skipped by this one) into ``rows`` from its label file, the way the evaluation scripts
@@ -92,15 +139,19 @@ class LabelTables:
         data_dir = os.path.join(self.FLAGS.data_dir, data)
         seg_name = '{0}/{1}_{2}.nii.gz'.format(data_dir, 'seg4' if self.seq == 'la_4ch' and self.seg4 else 'seg', self.seq)
         sa_name = '{0}/sa.nii.gz'.format(data_dir)
-        if not os.path.exists(seg_name) or (rows is not self.gate and not os.path.exists(sa_name)):
+        if not os.path.exists(seg_name) or (rows is not self.gate and rows is not self.score and not os.path.exists(sa_name)):
             return
         nim = nifti.load(seg_name)
         seg = nim.get_data()
         if rows is self.volumes:
             head = nifti.load_header(sa_name)               # the voxel size is the image's (:40-47)
             self.record(data, data_dir, nifti.NiftiImage(None, head['affine'], head['pixdim']), measures.counts_from_labels(seg, 4), {}, log)
+        elif rows is self.score:
+            truth = self.read_truth(data_dir, seg.shape, log) if seg.ndim == 4 else None
+            if truth is not None:
+                self.record(data, data_dir, nim, None, {'score': self.from_labels(seg, {'score': truth}, self.n_class)[1]['score']}, log)
         elif seg.ndim == 4:
-            args = self.subject_args(data_dir, nim, log) if rows is self.atrial else {}
+            args = self._atrial_args(data_dir, nim, log) if rows is self.atrial else {}
             if args or rows is self.gate:
                 stats = self.from_labels(seg, args, None)[1]
                 if data in self.gate:
@@ -108,10 +159,10 @@ class LabelTables:
                 self.record(data, data_dir, nim, None, stats, log)
 
     def write(self, shard_subjects, log):
-        """The tables of this worker's subjects, sorted (the order of the evaluation scripts): volumes, atria, gate -- verdicts the
+        """The tables of this worker's subjects, sorted (the order of the evaluation scripts): volumes, atria, scores, gate -- verdicts the
         atrial table had to produce land in the gate table, logged once.  The gate table is written only with --qc_csv."""
         F = self.FLAGS
-        for rows, csv in ((self.volumes, self.output_csv), (self.atrial, self.atrial_csv), (self.gate, self.qc_csv)):
+        for rows, csv in ((self.volumes, self.output_csv), (self.atrial, self.atrial_csv), (self.score, self.score_csv), (self.gate, self.qc_csv)):
             if not csv:
                 continue
             # with --work_stealing this worker may also have segmented subjects of other shards (their rows are in ``rows``), and
@@ -125,6 +176,11 @@ class LabelTables:
                 out = [(data, r) for data in subjects for r in rows.get(data, [])]
                 atrial.write_frames_csv(path, out)
                 log('Atrial measures of {0} frames and labels written to {1}'.format(len(out), path))
+                continue
+            if rows is self.score:
+                out = [(data, r) for data in subjects for r in rows.get(data, [])]
+                seg_score.write_csv(path, out)
+                log('Scores of {0} frames and labels against {1} written to {2}'.format(len(out), self.score_against, path))
                 continue
             out = [(data, rows[data]) for data in subjects if data in rows]
             if rows is self.volumes:

@@ -191,10 +191,10 @@ class SequenceRun:
         for item in self.walk():
             self.on_this_thread(item, forward)
 
-    def on_this_thread(self, item, forward=None, nim=None):
+    def on_this_thread(self, item, forward=None, nim=None, truth=None):
         """One subject start to finish on this thread (deploy_network.py:80-131): the host path -- pipeline.segment_sequence
         through ``forward`` (default: the engine) -- or, per sequence_on_device, device pre-processing of this one subject.
-        nim: its file where a reader thread has loaded it already."""
+        nim: its file where a reader thread has loaded it already; truth: what LabelTables.read_truth gave that thread."""
         data, data_dir, image_name = item
         FLAGS, log, tables = self.FLAGS, self.log, self.tables
         log(data)
@@ -208,7 +208,7 @@ class SequenceRun:
             return
         log('  Segmenting full sequence ...')
         t0 = time.time()
-        args = tables.subject_args(data_dir, nim, log)
+        args = tables.subject_args(data_dir, nim, log, truth)
         if sequence_on_device(FLAGS, self.engine, image):
             from . import device_pipeline
             pred, aux = device_pipeline.segment_sequence_device(image, self.engine, FLAGS.batch_slices, return_aux=True, stats=tables.statistics(),
@@ -240,6 +240,7 @@ class SequenceRun:
         if gz_mode:
             self.phases.update(label_gzip_device=0, label_gzip_fallback=0)
         pipes = []                                      # the SubjectPipeline, once the first volume has sized it
+        truths = {}                                     # subject -> what its reader got from LabelTables.read_truth
         mk = threading.Lock()
 
         def alloc(shape, dt):
@@ -262,7 +263,9 @@ class SequenceRun:
                 handed.append(a)
                 return a, headroom
             try:
-                return nifti.load(item[2], alloc=alloc_tracked)
+                nim = nifti.load(item[2], alloc=alloc_tracked)
+                truths[item[0]] = tables.read_truth(item[1], nim.shape, self.log)    # --score_csv: the second file of the subject, inflated here too
+                return nim
             except BaseException:
                 for a in handed:                        # a truncated / corrupt file: the pinned buffer goes back to the pool
                     if pipes:
@@ -296,11 +299,12 @@ class SequenceRun:
             if not pipelined_on_device(image) or not pipes or not pipes[0].fits(image):
                 while inflight:                         # odd subject: drain, then this thread alone
                     collect()
-                self.on_this_thread(item, nim=nim)
+                truth = truths.pop(item[0], None)
+                self.on_this_thread(item, nim=nim, **({} if truth is None else {'truth': truth}))
             else:
                 if len(inflight) >= depth - 1:
                     collect()
-                pipes[0].submit(image, tables.subject_args(item[1], nim, self.log), (nim.affine, nim.header['pixdim']) if gz_mode else None)
+                pipes[0].submit(image, tables.subject_args(item[1], nim, self.log, truths.pop(item[0], None)), (nim.affine, nim.header['pixdim']) if gz_mode else None)
                 inflight.append((item, nim, time.time()))
             top_up()
         while inflight:
