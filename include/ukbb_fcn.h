@@ -112,6 +112,7 @@ void ukbb_fcn_destroy(ukbb_fcn_handle *h);
  * frame's FIRST step from those rounded values too, the ones every later step adds; each hidden map is rounded once, as stored): 8-9 ms instead of 19 per 100-frame cine, per-class Dice >= 0.98 against the fp32 cine.  On FCN handles only the operands are bf16 (fp32 activations in
  * HBM; layers without such a tiling stay fp32).  Not bit-compatible with the reference; meant to be
  * judged by Dice against the fp32 result (common/image_utils.py:171-175): 0.993 / 0.992 measured.
+ * Each bf16-operand FCN launch is graded against float64 on the rounded operands in tests/test_bf16_operand_launches_gpu.py.
  * Concurrency (round 6): a handle of any kind and precision may run beside kernels of other streams of the process (one handle per stream,
  * one thread per handle; tests/test_concurrency_gpu.py runs two engines on two streams with batches in flight on both).  Until round 6 a
  * UKBB_KIND_UNET handle in UKBB_PREC_BF16 could not: 16-byte buffer stores of its weight-stationary kernels lacked a wait state that hipcc

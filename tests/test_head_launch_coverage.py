@@ -137,6 +137,26 @@ def test_cases_reach_every_situation_and_none_is_idle():
     assert all(HL.CASES[i][1] <= 3 and HL.CASES[i][2] * HL.CASES[i][3] <= 80 * 112 for i in HL.CHILD_CASES)
 
 
+def test_modes_and_the_plans_behind_them():
+    """Every case runs in the three precisions; in each the plan ends in the same sqg1-4 and head launches on the same maps (engine.cpp switches the
+    head's arithmetic for f32x3 only), and in bf16 every conv in front of them from conv1_0 on is a bf16-operand tiling storing fp32 maps, so the
+    squeeze and head of that mode are fp32 launches on maps another kernel family stored.  The knob children keep fp32 and f32x3."""
+    from ukbb_cardiac_amd import _lib, engine
+    from ukbb_cardiac_amd.arch import MODELS
+    assert HL.MODES == ('fp32', 'f32x3', 'bf16') and set(HL.CHILD_MODES) == {'fp32', 'f32x3'}
+    for model, n, H, W in HL.CASES:
+        tails = {}
+        for mode in HL.MODES:
+            p = engine.plan_layout(MODELS[model], mode, n, H, W)
+            assert not p['bfio'], (model, mode)                                         # fp32 maps in HBM in every mode
+            tails[mode] = [(o['name'], o['kind'], o['H'], o['W']) for o in p['ops'] if o['kind'] != 'conv']
+            acts = [(a['name'], a['per_image'], a['channels']) for a in p['acts']]
+            assert [t[0] for t in tails[mode]] == ['sqg1-4', 'head'] and {'conv%d' % l for l in range(5)} | {'g%d' % l for l in range(1, 5)} <= {a[0] for a in acts}
+            on_bf16 = [_lib.lib.ukbb_fcn_conv_config_name(o['cfg']).decode().startswith('convBF16_') for o in p['ops'] if o['kind'] == 'conv' and '+' not in o['name']]
+            assert len(on_bf16) == 11 and all(v == (mode == 'bf16') for v in on_bf16), (model, mode)
+        assert tails['fp32'] == tails['f32x3'] == tails['bf16']
+
+
 def test_window_arithmetic_against_the_taps_of_the_reference():
     """window() marks as inside exactly the source rows that the reference's taps of a tile's 16 output rows read with a non-zero weight or
     would read inside the map: rows (y + pb) >> l and one less, pb = (2^l - 1) // 2."""

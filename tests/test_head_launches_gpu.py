@@ -14,7 +14,10 @@ One forward per case and mode.  From what the engine stored (Engine.activation),
             is >= 4e-7 (the contract at softmax_argmax, kernels.h);  the pred-only call (want_logits=False, want_prob=False) gives the same map bit for
             bit;  against the float64 logits a label may differ only where the float64 top-two margin is <= 2e-5 of the logits' scale
 
-Every case runs in fp32 and in f32x3 on the same handle, with the same bounds (include/ukbb_fcn.h promises fp32-grade results for f32x3).  Inputs as in
+Every case runs in fp32, in f32x3 and in bf16 on the same handle, with the same bounds (include/ukbb_fcn.h promises fp32-grade results for f32x3).  In
+bf16 (UKBB_PREC_BF16 on an FCN handle: bf16-operand convs, fp32 maps in HBM; engine.cpp switches the head for f32x3 only) the squeeze and the head are
+the fp32 launches, fed by maps the bf16-operand convs stored (those are graded in tests/test_bf16_operand_launches_gpu.py); everything here is graded
+from the engine's own stored conv0..4 and g1..4, so the same bounds hold.  Inputs as in
 the fp32 launch test: a batch is made of copies of three rough images (phantom, uniform noise, scaled normal noise), slices 0-2 are graded in float64
 and every other slice of g1..g4, logits, prob and pred must be BIT-IDENTICAL to the graded copy of its image; weights from seeds 1234 and 7 in turn.
 Each case asserts that the plan it ran holds sqg1-4 and head.
@@ -52,8 +55,9 @@ wrong.
 Measured on an MI355X (profiles/head_launches.txt, one row per graded launch and mode, worst per launch kind, level and mode in its last block), worst
 over the 11 cases, fp32 / f32x3: g1 3.2e-7, g2 3.1e-7, g3 3.6e-7, g4 6.8e-7 of the map's scale (the squeeze is the same launch in both modes); logits
 5.7e-7 / 6.7e-7 of their scale; prob 1.6e-7 / 1.6e-7 absolute; no label differing from the float64 argmax, no copy differing, no defect found.  The
-three children measure the same or less on their cases.  The 11 cases take 3 s together (0.34 s of forwards and read-back, 1.6 s of float64; the
-largest 0.8 s), each child 3 s, most of it starting Python."""
+three children measure the same or less on their cases.  In bf16 (behind the bf16-operand encoder): g1 3.4e-7, g2 2.9e-7, g3 3.5e-7, g4 4.8e-7, logits
+5.6e-7, prob 1.6e-7, no label differing.  The 11 cases take 3 s together in fp32 and f32x3 (0.34 s of forwards and read-back, 1.6 s of float64; the
+largest 0.8 s) and 4.5 s with bf16 (the largest 1.3 s), each child 3 s, most of it starting Python."""
 import json
 import os
 import subprocess
@@ -72,7 +76,8 @@ PROB_ATOL = 1e-6                        # 16 x 2^-24 = 9.5e-7, see above
 NEAR_TIE_GAP = 4e-7                     # kernels.h softmax_argmax
 LABEL_MARGIN = 2e-5                     # of the float64 logits' scale: two fp32-grade evaluations, 1e-5 each
 SEEDS = (1234, 7)
-MODES = ('fp32', 'f32x3')
+MODES = ('fp32', 'f32x3', 'bf16')
+CHILD_MODES = ('fp32', 'f32x3')         # the knob children stay on the two modes whose head launches differ
 
 CASES = [
     ('FCN_sa', 1, 16, 16), ('FCN_sa', 1, 48, 16), ('FCN_sa', 1, 16, 144),
@@ -142,8 +147,8 @@ def rel_err(got, ex):
 
 
 # ---- one case, every mode, on one handle ---------------------------------------------------------------------------------------------------------------
-def grade_case(index, want_names=('sqg1-4', 'head'), tail_form=None):
-    """Runs case ``index`` in every mode, prints one line per graded launch and mode, asserts everything the module docstring lists.
+def grade_case(index, want_names=('sqg1-4', 'head'), tail_form=None, modes=MODES):
+    """Runs case ``index`` in every mode of ``modes``, prints one line per graded launch and mode, asserts everything the module docstring lists.
     Returns the rows [(mode, launch, figure, where)]."""
     from test_fp32_launches_gpu import batch_of_copies
     from ukbb_cardiac_amd import _lib, engine
@@ -159,11 +164,11 @@ def grade_case(index, want_names=('sqg1-4', 'head'), tail_form=None):
     t_gpu = t_ref = 0.0
     prev = None                                                          # (stored inputs, expected maps) of the mode before: same inputs, same reference
     with engine.Engine(arch, params) as eng:
-        for mode in MODES:
+        for mode in modes:
             t0 = time.perf_counter()
             eng.set_precision(mode)
             out = eng.run(img, want_logits=True, want_prob=True, want_pred=True)
-            names = eng.kernel_names()
+            names, cfgs = eng.kernel_names(), eng.kernel_configs()
             form = int(_lib.lib.ukbb_fcn_head_tail_form())
             conv = {l: eng.activation('conv%d' % l).reshape(n, H >> l, W >> l, -1) for l in range(5)}
             g = {l: eng.activation('g%d' % l).reshape(n, H >> l, W >> l, 64) for l in range(1, 5)}
@@ -171,6 +176,9 @@ def grade_case(index, want_names=('sqg1-4', 'head'), tail_form=None):
             t_gpu += time.perf_counter() - t0
             for nm in want_names:
                 assert nm in names, (mode, nm, names)
+            # bf16: the maps the squeeze and the head read were stored by bf16-operand convs, every one from conv1_0 on
+            on_bf16 = [_lib.lib.ukbb_fcn_conv_config_name(c).decode().startswith('convBF16_') for nm, c in zip(names, cfgs) if nm.startswith('conv') and '+' not in nm]
+            assert len(on_bf16) == 11 and all(v == (mode == 'bf16') for v in on_bf16), (mode, list(zip(names, cfgs)))
             if tail_form is not None and mode == 'fp32':                 # f32x3 keeps the in-stage tail in every form
                 assert form == tail_form, (form, tail_form)
             logits, prob, pred = out['logits'], out['prob'], out['pred']
@@ -234,7 +242,7 @@ def run_child(knob, path):
     form = 0 if knob == 'UKBB_SIDE_STREAM' else 1
     rows = []
     for index in CHILD_CASES:
-        rows += [(index,) + r[:3] for r in grade_case(index, want, form)]
+        rows += [(index,) + r[:3] for r in grade_case(index, want, form, CHILD_MODES)]
     with open(path, 'w') as f:
         json.dump(rows, f)
 
@@ -259,4 +267,4 @@ def test_non_default_launches_against_float64(knob, tmp_path):
     assert r.returncode == 0, r.stdout[-3000:]
     with open(path) as f:
         rows = json.load(f)
-    assert len(rows) == len(CHILD_CASES) * len(MODES) * 7 and {r[0] for r in rows} == set(CHILD_CASES)
+    assert len(rows) == len(CHILD_CASES) * len(CHILD_MODES) * 7 and {r[0] for r in rows} == set(CHILD_CASES)
