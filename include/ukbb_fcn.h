@@ -402,6 +402,23 @@ uint64_t ukbb_fcn_score_planes_work(int X, int Y, int P, int n_class);
 int ukbb_fcn_score_planes(const uint8_t *d_pred, const uint8_t *d_truth, int X, int Y, int P, int n_class, void *d_work, int32_t *d_cells,
                           double *d_sums, void *stream);
 
+/* -- how sure the network was (additive to ABI 11): per (frame, class) integer reductions of the softmax, by the rules
+ * ukbb_cardiac_amd/confidence.py states (cells_host is the specification).  d_prob [n][X2][Y2][n_class] float32 and d_pred [n][X2][Y2]
+ * int32 as ukbb_fcn_forward leaves them for n slices of the padded batch [T*Z][X2][Y2], the first of which is slice first_slice of
+ * that batch (slice b belongs to frame b / Z, as in ukbb_fcn_unpack_labels).  Only the image region counts: x2 in [x_pre, x_pre + X),
+ * y2 in [y_pre, y_pre + Y).  With q(p) = (int)(p * 65536.0f) (exact multiply, truncation; 0 for a denormal or a NaN) and, for a voxel
+ * labelled c = pred, q1 = q(p[c]), margin = q1 - max over c' != c of q(p[c']), the call ADDS into d_cells[t][c][20] (uint64):
+ *   0       the voxels of frame t with pred == c
+ *   1, 2    the sums of q1 and of margin over those voxels
+ *   3..18   the histogram of min(q1 >> 12, 15) over those voxels (16 bins of width 1/16; p == 1 lands in the last)
+ *   19      the sum of q(p[c]) over ALL voxels of the frame (the soft count)
+ * A voxel whose label lies outside 0 .. n_class - 1 counts in field 19 only.  The caller zeroes d_cells [T][n_class][20] once per
+ * subject and calls once per chunk of slices.  Integer adds only: nothing depends on arrival order or on the chunking.  Reads
+ * 4 * n_class + 4 bytes per image voxel and writes nothing else.  Asynchronous.  n_class 2..16, first_slice + n <= Z*T <= 65535,
+ * X*Y <= 2^30, d_prob 16-byte and d_cells 8-byte aligned. */
+int ukbb_fcn_confidence_cells(const float *d_prob, const int32_t *d_pred, int n, int X, int Y, int Z, int T, int X2, int Y2, int x_pre, int y_pre,
+                              int n_class, int first_slice, uint64_t *d_cells, void *stream);
+
 /* ---- label-volume files (host only: no device, no stream) ---------------------------------------
  * What the reference does with the result: nib.save of np.zeros(image.shape) filled with the labels
  * (common/deploy_network.py:92,116,136-138; deploy_network_ao.py:189-196) -- for a short-axis subject

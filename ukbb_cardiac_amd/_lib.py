@@ -33,6 +33,7 @@ EXPORTS = [
     'ukbb_fcn_set_scratch_budget', 'ukbb_fcn_scratch_bytes', 'ukbb_fcn_cine_scratch_bytes',
     'ukbb_fcn_cine_min_scratch_bytes', 'ukbb_fcn_cine_chunk_windows',
     'ukbb_fcn_plane_components', 'ukbb_fcn_atrial_area_length', 'ukbb_fcn_score_planes_work', 'ukbb_fcn_score_planes',
+    'ukbb_fcn_confidence_cells',
     'ukbb_fcn_inflate_device', 'ukbb_fcn_inflate_core_host', 'ukbb_fcn_gzip_crc_combine',
     'ukbb_fcn_gzip_labels_device_scratch', 'ukbb_fcn_gzip_labels_device_geometry', 'ukbb_fcn_gzip_labels_device',
     'ukbb_fcn_gzip_labels_parallel_host',
@@ -130,6 +131,7 @@ def _load():
     lib.ukbb_fcn_score_planes_work.restype = C.c_uint64
     lib.ukbb_fcn_score_planes_work.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     lib.ukbb_fcn_score_planes.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    lib.ukbb_fcn_confidence_cells.argtypes = [vp, vp] + [C.c_int] * 11 + [vp, vp]
     lib.ukbb_fcn_set_scratch_budget.argtypes = [vp, C.c_uint64]
     lib.ukbb_fcn_scratch_bytes.restype = C.c_uint64
     lib.ukbb_fcn_scratch_bytes.argtypes = [vp]

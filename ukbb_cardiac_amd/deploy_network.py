@@ -16,7 +16,7 @@ and writes the same files (``deploy_network.py:136-151,207-216``):
 
 Extra flags (not in the reference): ``--device``, ``--batch_slices``,
 ``--num_shards`` / ``--shard_index`` (multi-GPU batch split), ``--output_csv``, ``--qc_csv``,
-``--atrial_csv``, ``--score_against`` / ``--score_csv`` (Dice and contour distances against a second segmentation), ``--device_inflate`` (gzip inputs inflated on the GPU), ``--device_label_gzip`` (label
+``--atrial_csv``, ``--score_against`` / ``--score_csv`` (Dice and contour distances against a second segmentation), ``--confidence_csv`` (how sure the network was, per frame and class), ``--device_inflate`` (gzip inputs inflated on the GPU), ``--device_label_gzip`` (label
 volumes deflated on the GPU).
 """
 import os
@@ -93,6 +93,12 @@ def define_flags():
                      'distance_metric, from the labels while they are on the GPU.  A subject without the file, or whose file has another '
                      'shape or a label the model does not have, gets no rows; frames without a non-zero truth label give none.  Subjects '
                      'already segmented by an earlier run are scored from their files.')
+    fs.DEFINE_string('confidence_csv', '', 'Sequence mode: also write one row per (subject, frame, label), and one per (subject, label) over all frames, '
+                     'saying how sure the network was: the voxels of the label, their mean winning probability, their mean margin to the '
+                     'runner-up, the shares of them whose winning probability lies below 0.5 and below 0.75, and the soft volume (the sum of the '
+                     'label\'s probability over all voxels) -- integer reductions of the softmax while a chunk of slices is on the GPU '
+                     '(confidence.py).  The forward then stores its probabilities, one chunk at a time; off by default.  Subjects already '
+                     'segmented by an earlier run get no rows: their probabilities are gone.')
     fs.DEFINE_integer('num_shards', env_cnt, 'Number of workers sharing data_dir.')
     fs.DEFINE_integer('shard_index', env_idx, 'This worker: subjects i with i % num_shards == shard_index.')
     fs.DEFINE_boolean('work_stealing', True, 'With num_shards > 1: after its own share a worker takes subjects of the other shards that '
@@ -122,7 +128,7 @@ def run(FLAGS, forward, log=print, engine=None):
                        stealing=bool(getattr(FLAGS, 'work_stealing', False)) and FLAGS.process_seq)
     data_list = list(queue)
     processed, table_time = [], []
-    tables = LabelTables(FLAGS, engine)                 # --output_csv, --qc_csv, --atrial_csv, --score_csv: flag checks first
+    tables = LabelTables(FLAGS, engine)                 # --output_csv, --qc_csv, --atrial_csv, --score_csv, --confidence_csv: flag checks first
     shard_subjects = list(queue.static)                 # whose earlier-run results this worker measures for the tables
     on_device = device_path(FLAGS, engine)
     inflate = int(getattr(FLAGS, 'device_inflate', 0) or 0) > 0
@@ -202,6 +208,9 @@ def main(argv=None):
         print('Start deployment on the data set ...')
 
         def forward(batch):
+            if FLAGS.confidence_csv:                     # the host path forms the table from the probabilities of every chunk
+                prob, pred = sess.run(['prob:0', 'pred:0'], feed_dict={'image:0': batch, 'training:0': False})
+                return {'prob': prob, 'pred': pred}
             pred = sess.run('pred:0', feed_dict={'image:0': batch, 'training:0': False})
             return {'pred': pred}
         run(FLAGS, forward, engine=sess.engine)

@@ -74,6 +74,11 @@ def define_flags():
                       'path (aorta_qc.py).')
     fs.DEFINE_string('pressure_csv', '', 'With --output_csv: the blood-pressure spreadsheet of eval_aortic_area.py:41-46 for the distensibility columns '
                      '(left empty without it).')
+    fs.DEFINE_string('confidence_csv', '', 'Sequence mode, every model: also write one row per (subject, frame, label), and one per (subject, label) over '
+                     'all frames, saying how sure the network was: the pixels of the label, their mean winning probability, their mean margin to '
+                     'the runner-up, the shares of them whose winning probability lies below 0.5 and below 0.75, and the soft area (the sum of '
+                     'the label\'s probability over all pixels) -- integer reductions of the softmax (UNet) or of the averaged window '
+                     'probabilities (UNet-LSTM, Temporal-UNet) while they are on the GPU (confidence.py).  Off by default.')
     fs.DEFINE_integer('num_shards', env_cnt, 'Number of workers sharing data_dir.')
     fs.DEFINE_integer('shard_index', env_idx, 'This worker: subjects i with i % num_shards == shard_index.')
     return fs
@@ -118,8 +123,9 @@ def _sequence_subject(FLAGS, data, data_dir, nim, forward, cine_forward, engine,
     t0 = time.time()
     if sequence_on_device(FLAGS, engine, image, log):
         from ukbb_cardiac_amd.device_pipeline import aortic_sequence_device
-        pred, aux = aortic_sequence_device(image, engine, FLAGS.batch_slices, window, return_aux=True, qc=table.qc_full)
-        counts, qc_stats = aux['counts'], aux.get('qc')
+        pred, aux = aortic_sequence_device(image, engine, FLAGS.batch_slices, window, return_aux=True, qc=table.qc_full,
+                                           confidence=table.confidence is not None)
+        counts, qc_stats, cells = aux['counts'], aux.get('qc'), aux.get('confidence')
     else:
         # rescale_intensity clips `image` in place; the script's quality control reads the file
         image_qc = image.copy() if table.qc_full and not FLAGS.z_score else image
@@ -130,11 +136,16 @@ def _sequence_subject(FLAGS, data, data_dir, nim, forward, cine_forward, engine,
             prob = pipeline.aortic_prob_sequence(image, forward, FLAGS.z_score, FLAGS.batch_slices)
         pred = np.argmax(prob, axis=-1).astype(np.int32)      # host argmax, as :189
         counts, qc_stats = table.from_labels(image_qc, pred)
+        cells = None
+        if table.confidence is not None:
+            from ukbb_cardiac_amd import confidence
+            cells = confidence.cells_from_volume(prob, pred)
     if FLAGS.save_seg:
         log('  Saving segmentation ...')
         save(pred, '{0}/seg_{1}.nii.gz'.format(data_dir, FLAGS.seq_name), nim.affine, nim.header['pixdim'])
     log('  Segmentation time = {:3f}s'.format(time.time() - t0))
     table.record(data, nim.header['pixdim'], counts, qc_stats, log)
+    table.record_confidence(data, cells)
 
 
 def _frames_subject(FLAGS, data_dir, forward, log):
@@ -173,7 +184,7 @@ def run(FLAGS, forward, log=print, cine_forward=None, engine=None):
     start_time = time.time()
     data_list = subjects_for_shard(sorted(os.listdir(FLAGS.data_dir)), FLAGS.shard_index, FLAGS.num_shards)
     processed = []
-    table = AorticTable(FLAGS)                                  # --output_csv: flag checks first
+    table = AorticTable(FLAGS)                                  # --output_csv, --confidence_csv: flag checks first
     # Sequence mode with --io_threads > 0: the next cines are read (inflated) by reader threads while the GPU works on this one,
     # and the segmentation files are written behind it; order of subjects, log lines and files are those of the sequential loop.
     nthr = int(getattr(FLAGS, 'io_threads', 0)) if FLAGS.process_seq else 0

@@ -140,22 +140,29 @@ def pack_rescaled(vol_ptr, dtype, shape, strides, lo, hi, pad, batch_ptr, stream
                                                 *pad, batch_ptr, stream), 'ukbb_fcn_rescale_pack_t')
 
 
-def forward_chunks(engine, batch_ptr, pred_ptr, n, X2, Y2, batch_slices, stream):
+def forward_chunks(engine, batch_ptr, pred_ptr, n, X2, Y2, batch_slices, stream, chunk_stats=()):
     """The frame-wise network over the packed batch [n][X2][Y2] at batch_ptr in chunks of batch_slices, enqueued on ``stream``: int32
-    label maps to pred_ptr."""
+    label maps to pred_ptr.  chunk_stats: [(statistic, work_ptr, out_ptr, shape, pad)] of the statistics that read the probabilities
+    (``per_chunk``: ConfidenceStats).  With one, every chunk's forward also stores its probabilities -- into the statistic's work buffer,
+    one chunk large, written again by the next chunk -- and the statistic's launch is queued behind the chunk on the same stream."""
     engine.reserve(min(batch_slices, n), X2, Y2)
+    prob_ptr = chunk_stats[0][1] if chunk_stats else 0
     for i in range(0, n, batch_slices):
         m = min(batch_slices, n - i)
-        engine.run_device(batch_ptr + 4 * i * X2 * Y2, m, X2, Y2, pred_ptr=pred_ptr + 4 * i * X2 * Y2, stream=stream)
+        engine.run_device(batch_ptr + 4 * i * X2 * Y2, m, X2, Y2, prob_ptr=prob_ptr, pred_ptr=pred_ptr + 4 * i * X2 * Y2, stream=stream)
+        for stat, _, out_ptr, shape, pad in chunk_stats:
+            stat.launch_chunk(prob_ptr, pred_ptr + 4 * i * X2 * Y2, m, i, shape, pad, engine.arch.n_class, out_ptr, stream)
 
 
-def forward_and_unpack(engine, batch_ptr, pred_ptr, shape, pad, batch_slices, lab_ptr, counts_ptr, stream):
+def forward_and_unpack(engine, batch_ptr, pred_ptr, shape, pad, batch_slices, lab_ptr, counts_ptr, stream, chunk_stats=()):
     """The tail every frame-wise sequence path shares, enqueued on ``stream``: the network over the packed batch [T*Z][X2][Y2] at
     batch_ptr in chunks of batch_slices (int32 label maps to pred_ptr), then ukbb_fcn_unpack_labels: the uint8 (X,Y,Z,T) label
-    volume in NIfTI order to lab_ptr and the per-frame class counts (int64 [T, n_class]) to counts_ptr.  pad = (X2, Y2, x_pre, y_pre)."""
+    volume in NIfTI order to lab_ptr and the per-frame class counts (int64 [T, n_class]) to counts_ptr.  pad = (X2, Y2, x_pre, y_pre).
+    chunk_stats: [(statistic, work_ptr, out_ptr)] of the per-chunk statistics (forward_chunks), their outputs zeroed by the caller."""
     X, Y, Z, T = shape
     X2, Y2, x_pre, y_pre = pad
-    forward_chunks(engine, batch_ptr, pred_ptr, T * Z, X2, Y2, batch_slices, stream)
+    forward_chunks(engine, batch_ptr, pred_ptr, T * Z, X2, Y2, batch_slices, stream,
+                   [(stat, work_ptr, out_ptr, shape, pad) for stat, work_ptr, out_ptr in chunk_stats])
     _lib.check(_lib.lib.ukbb_fcn_unpack_labels(pred_ptr, X, Y, Z, T, X2, Y2, x_pre, y_pre, engine.arch.n_class, lab_ptr, counts_ptr, stream),
                'ukbb_fcn_unpack_labels')
 
@@ -168,7 +175,7 @@ def segment_sequence_device(image, engine, batch_slices=128, thres=(1, 99), retu
     save image frames afterwards clip them with the returned bounds (``aux['clip']``: the float64
     percentiles; clip_like_reference stores them into an integer frame truncated, as numpy does).
     ``aux['counts'][t, c]`` = voxels of class c in frame t (input of the ES pick).  ``stats`` (needs ``return_aux``): label
-    statistics (GateStats, AtrialStats, ScoreStats) to compute from the labels while they are still on the device, ``stat_args`` their
+    statistics (GateStats, AtrialStats, ScoreStats; ConfidenceStats: from the probabilities, chunk by chunk) to compute while the labels are still on the device, ``stat_args`` their
     per-subject arguments {key: arg}: ``aux['stats']`` = {key: decoded statistic} (label_statistics)."""
     import torch
     if stats and not return_aux:
@@ -206,14 +213,17 @@ def segment_sequence_tensor(vol_t, dtype, shape, engine, batch_slices=128, thres
     n_class = engine.arch.n_class
     lab = torch.empty(X * Y * Z * T, dtype=torch.uint8, device=dev)
     counts = torch.empty((T, n_class), dtype=torch.int64, device=dev)
+    per_chunk = chunk_statistics_buffers(stats, (X, Y, Z, T), n_class, dev)
     forward_and_unpack(engine, batch.data_ptr(), pred.data_ptr(), (X, Y, Z, T), (X2, Y2, x_pre, y_pre), batch_slices, lab.data_ptr(),
-                       counts.data_ptr(), stream)
+                       counts.data_ptr(), stream, [(stat, work.data_ptr(), out.data_ptr()) for stat, work, out in per_chunk])
     lab_h = lab.cpu().numpy().reshape((X, Y, Z, T), order='F')
     out = np.zeros((X, Y, Z, T))                                # float64, as deploy_network.py:92
     out[...] = lab_h
     if return_aux:
         aux = {'clip': (lo, hi), 'counts': counts.cpu().numpy()}
         aux['stats'] = label_statistics(lab, (X, Y, Z, T), n_class, stats, stat_args, stream, aux['counts'])
+        for stat, _, d_out in per_chunk:
+            aux['stats'][stat.key] = stat.decode(d_out.cpu().numpy(), (X, Y, Z, T), n_class, aux['counts'])
         return out, aux
     return out
 
@@ -427,7 +437,7 @@ class GateStats:
     """qc_gates.stats_host -- what the gate of this sequence reads (the input of qc_gates.gate_from_stats) -- of an (X,Y,Z,T) label
     volume: ukbb_fcn_plane_components for sa (the Z planes of frame 0) and la_4ch --seg4 (plane 0), ukbb_fcn_label_components for
     the atrial gate (the whole sequence).  plane_args = (a, b, keep_min) of the plane statistics (qc_gates.plane_stats_host)."""
-    key, needs_arg = 'qc', False
+    key, needs_arg, per_chunk = 'qc', False, False
 
     def __init__(self, seq_name, seg4, plane_args=None):
         from .qc_gates import PIXEL_THRES, gate_kind
@@ -469,7 +479,7 @@ class AtrialStats:
     """atrial.frame_stats_host, [T, n_class, 8], of an (X,Y,1,T) label volume (one slice: every frame a plane of
     ukbb_fcn_atrial_area_length).  Per-subject argument: (affine, long_axis) -- the voxel-to-world matrix of the long-axis image and
     atrial.long_axis_from_sa; only the T*n_class*32 bytes of statistics cross to the host."""
-    key, needs_arg = 'atrial', True
+    key, needs_arg, per_chunk = 'atrial', True, False
 
     def sizes(self, shape, n_class):
         X, Y, Z, T = shape
@@ -494,7 +504,7 @@ class ScoreStats:
     one (ukbb_fcn_score_planes).  Per-subject argument: the truth volume, a uint8 (X,Y,Z,T) array; it is uploaded once, on the
     stream the statistic is enqueued on, and only the Z*T*n_class*48 bytes of results cross back.  A plane larger than the kernel's
     bit planes hold (``fits``) is for seg_score.stats_host."""
-    key, needs_arg = 'score', True
+    key, needs_arg, per_chunk = 'score', True, False
 
     def __init__(self, device=None):
         self.device = device                                          # of the label volume; None: torch's current device
@@ -532,6 +542,48 @@ class ScoreStats:
                 'sums': out[P * n_class * 8:].view(np.float64).reshape(P, n_class, 2).copy()}
 
 
+class ConfidenceStats:
+    """confidence.cells_host -- [T, n_class, 20] uint64 reductions of the softmax per (frame, class) -- of a subject
+    (ukbb_fcn_confidence_cells).  It reads what the other statistics never see, the probabilities, and they exist for one chunk of slices
+    at a time: ``per_chunk``.  Its work buffer is that chunk's probabilities [batch_slices][X2][Y2][n_class] float32, which the forward
+    fills (forward_chunks); ``launch_chunk`` adds the chunk into the cells, which the caller has zeroed; only the T*n_class*160 bytes of
+    cells cross to the host.  pad(X, Y) -> (X2, Y2, x_pre, _, y_pre, _): how the path pads its batch; n_class: the model's, where the
+    caller sizes buffers for any model."""
+    key, needs_arg, per_chunk = 'confidence', False, True
+
+    def __init__(self, batch_slices, n_class=None, pad=pad_amounts):
+        self.batch_slices, self.n_class, self.pad = int(batch_slices), n_class, pad
+
+    def sizes(self, shape, n_class):
+        X, Y, Z, T = shape
+        X2, Y2 = self.pad(X, Y)[:2]
+        C = self.n_class or n_class
+        return min(self.batch_slices, Z * T) * X2 * Y2 * C, T * C * 40
+
+    def launch(self, lab_ptr, shape, n_class, work_ptr, out_ptr, stream, arg=None):
+        raise RuntimeError('ConfidenceStats reads the probabilities of a chunk of slices: launch_chunk, behind the chunk\'s forward')
+
+    def launch_chunk(self, prob_ptr, pred_ptr, n, first_slice, shape, pad, n_class, out_ptr, stream):
+        X, Y, Z, T = shape
+        _lib.check(_lib.lib.ukbb_fcn_confidence_cells(prob_ptr, pred_ptr, n, X, Y, Z, T, *pad, n_class, first_slice, out_ptr, stream),
+                   'ukbb_fcn_confidence_cells')
+
+    def decode(self, out, shape, n_class, counts=None):
+        T = shape[3]
+        return np.ascontiguousarray(np.asarray(out, dtype=np.int32)[:T * n_class * 40]).view(np.uint64).reshape(T, n_class, 20).copy()
+
+
+def chunk_statistics_buffers(stats, shape, n_class, device):
+    """[(statistic, work, out)] for the per-chunk statistics among ``stats``: fresh device tensors, the output zeroed on the current stream."""
+    import torch
+    got = []
+    for stat in stats:
+        if stat.per_chunk:
+            n_work, n_out = stat.sizes(shape, n_class)
+            got.append((stat, torch.empty(n_work, dtype=torch.float32, device=device), torch.zeros(n_out, dtype=torch.int32, device=device)))
+    return got
+
+
 def stat_skipped(stat, stat_args):
     """A statistic that takes a per-subject argument and has none for this subject (a long-axis subject without sa.nii.gz) is not
     computed for it."""
@@ -545,7 +597,7 @@ def label_statistics(lab_t, shape, n_class, stats, stat_args=None, stream=0, cou
     import torch
     got = {}
     for stat in stats:
-        if stat_skipped(stat, stat_args):
+        if stat.per_chunk or stat_skipped(stat, stat_args):       # per-chunk statistics ran with the forward (forward_chunks)
             continue
         n_work, n_out = stat.sizes(shape, n_class)
         work = torch.empty(n_work, dtype=torch.int32, device=lab_t.device)
@@ -587,7 +639,7 @@ def device_atrial_stats(lab_t, shape, n_class, affine, long_axis, stream=0):
     return label_statistics(lab_t, shape, n_class, [AtrialStats()], {'atrial': (affine, long_axis)}, stream)['atrial']
 
 
-def aortic_sequence_device(image, engine, batch_slices=128, window=None, return_aux=False, qc=False, prob=False):
+def aortic_sequence_device(image, engine, batch_slices=128, window=None, return_aux=False, qc=False, prob=False, confidence=False):
     """pipeline.aortic_prob_sequence (``window`` None: the frame-wise 'UNet' model in chunks of ``batch_slices``) or
     pipeline.aortic_lstm_prob_sequence (``window`` = (weight_R, weight_r, time_step): the windowed models, one cine per slice
     position) + the argmax of deploy_network_ao.py:189 with the array work on the GPU: (X,Y,Z,T) float32 / uint8 / int16 / uint16
@@ -597,11 +649,13 @@ def aortic_sequence_device(image, engine, batch_slices=128, window=None, return_
     float32 probabilities it would return (``softmax_argmax``, csrc/kernels.h).  With ``return_aux``: the z-score statistics and
     ``aux['counts']`` = pixels of each class per frame (what eval_aortic_area.py:60-78 turns into areas); with ``qc``,
     ``aux['qc']`` = device_qc_stats of the cine and the labels, the input of aorta_qc.aorta_qc_full; with ``prob`` (windowed
-    forward only: 78 MB for 100 frames), ``aux['prob']`` (X,Y,Z,T,C)."""
+    forward only: 78 MB for 100 frames), ``aux['prob']`` (X,Y,Z,T,C); with ``confidence``, ``aux['confidence']`` = confidence.cells_host of
+    the probabilities (ConfidenceStats: the windowed forward's averaged probabilities as they lie on the device, the frame-wise forward's
+    chunk by chunk)."""
     import torch
     host = 'pipeline.aortic_prob_sequence' if window is None else 'pipeline.aortic_lstm_prob_sequence'
-    if (qc or prob) and not return_aux:
-        raise ValueError('qc=True and prob=True return their results in aux: pass return_aux')
+    if (qc or prob or confidence) and not return_aux:
+        raise ValueError('qc=True, prob=True and confidence=True return their results in aux: pass return_aux')
     if prob and window is None:
         raise ValueError('prob=True: only the windowed forward leaves probabilities')
     if image.ndim != 4:
@@ -619,8 +673,12 @@ def aortic_sequence_device(image, engine, batch_slices=128, window=None, return_
     if window is not None:
         probs = torch.empty((T, Z, X2, Y2, n_class), dtype=torch.float32, device=dev)
     pred = torch.empty((T, Z, X2, Y2), dtype=torch.int32, device=dev)
+    conf = ConfidenceStats(batch_slices, n_class, pad_amounts_fixed) if confidence else None
+    per_chunk = chunk_statistics_buffers([conf] if conf else [], (X, Y, Z, T), n_class, dev) if window is None or conf is None else \
+        [(conf, probs, torch.zeros(conf.sizes((X, Y, Z, T), n_class)[1], dtype=torch.int32, device=dev))]
     if window is None:
-        forward_chunks(engine, batch.data_ptr(), pred.data_ptr(), T * Z, X2, Y2, batch_slices, stream)
+        forward_chunks(engine, batch.data_ptr(), pred.data_ptr(), T * Z, X2, Y2, batch_slices, stream,
+                       [(stat, work.data_ptr(), out.data_ptr(), (X, Y, Z, T), (X2, Y2, x_pre, y_pre)) for stat, work, out in per_chunk])
     else:
         for z in range(Z):                                   # slice positions are independent cines (usually Z = 1)
             fr = batch[:, z] if Z == 1 else batch[:, z].contiguous()
@@ -630,6 +688,9 @@ def aortic_sequence_device(image, engine, batch_slices=128, window=None, return_
             if Z > 1:
                 probs[:, z].copy_(pr)
                 pred[:, z].copy_(pd)
+        if conf is not None:                                 # the averaged probabilities of the whole cine lie on the device: one launch
+            conf.launch_chunk(probs.data_ptr(), pred.data_ptr(), T * Z, 0, (X, Y, Z, T), (X2, Y2, x_pre, y_pre), n_class,
+                              per_chunk[0][2].data_ptr(), stream)
     lab = torch.empty(X * Y * Z * T, dtype=torch.uint8, device=dev)
     counts = torch.empty((T, n_class), dtype=torch.int64, device=dev)
     _lib.check(_lib.lib.ukbb_fcn_unpack_labels(pred.data_ptr(), X, Y, Z, T, X2, Y2, x_pre, y_pre, n_class,
@@ -640,6 +701,8 @@ def aortic_sequence_device(image, engine, batch_slices=128, window=None, return_
     aux = {'mu': mu, 'den': den, 'n_roi': n_roi, 'val_l': val_l, 'counts': counts.cpu().numpy()}
     if qc:
         aux['qc'] = device_qc_stats(vol, lab, image.dtype, n_class, stream)
+    if conf is not None:
+        aux['confidence'] = conf.decode(per_chunk[0][2].cpu().numpy(), (X, Y, Z, T), n_class)
     if prob:
         aux['prob'] = probs[:, :, x_pre:x_pre + X, y_pre:y_pre + Y].permute(2, 3, 1, 0, 4).cpu().numpy()
     return out, aux

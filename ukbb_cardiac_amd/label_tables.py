@@ -1,12 +1,13 @@
 """The tables deploy_network.py derives from a label map while it segments: ``--output_csv`` (ventricular volumes, measures.py),
-``--qc_csv`` (the sa / la / atrium gate, qc_gates.py), ``--atrial_csv`` (atrial areas and lengths per frame, atrial.py) and
-``--score_csv`` (Dice and contour distances against the label file --score_against names, seg_score.py).
+``--qc_csv`` (the sa / la / atrium gate, qc_gates.py), ``--atrial_csv`` (atrial areas and lengths per frame, atrial.py),
+``--score_csv`` (Dice and contour distances against the label file --score_against names, seg_score.py) and ``--confidence_csv`` (how
+sure the network was, from the softmax behind the label map: confidence.py).
 
 One ``LabelTables`` is made per run from the flags.  It checks the flags, names the device statistics the run needs of every
 label volume (``statistics``), gives the per-subject arguments of those statistics (``subject_args``), turns one subject's class
 counts and statistics into rows (``record``) and at the end writes the tables, measuring the subjects an earlier run segmented
 from their files (``write``).  Statistics arrive as ``{key: value}`` -- 'qc': qc_gates.stats_host or device_pipeline.GateStats,
-'atrial': atrial.frame_stats_host or device_pipeline.AtrialStats, 'score': seg_score.stats_host or device_pipeline.ScoreStats -- from
+'atrial': atrial.frame_stats_host or device_pipeline.AtrialStats, 'score': seg_score.stats_host or device_pipeline.ScoreStats, 'confidence': confidence.cells_host or device_pipeline.ConfidenceStats -- from
 the device (SubjectPipeline, segment_sequence_device) or from the host twins (``from_labels``).
 
 ``AorticTable`` is the same for deploy_network_ao.py --output_csv (aortic areas and distensibility, measures.py): it checks the
@@ -14,7 +15,7 @@ flags, applies the quality control of --aortic_qc / --aortic_qc_full to the clas
 (``record``; ``from_labels``: the host twins) and writes the table.  The aortic run never skips a segmented subject: no back-fill."""
 import os
 
-from . import aorta_qc, atrial, measures, nifti, qc_gates, seg_score
+from . import aorta_qc, atrial, confidence, measures, nifti, qc_gates, seg_score
 
 
 class LabelTables:
@@ -43,19 +44,25 @@ class LabelTables:
             raise ValueError('--score_against names the label file to score against and --score_csv the table to write: they need each other')
         if self.score_csv and not FLAGS.process_seq:
             raise ValueError('--score_csv scores the segmentation of a whole sequence: it needs sequence mode (--process_seq)')
+        self.confidence_csv = getattr(FLAGS, 'confidence_csv', '')
+        if self.confidence_csv and not FLAGS.process_seq:
+            raise ValueError('--confidence_csv summarises the probabilities of a whole sequence: it needs sequence mode (--process_seq)')
         # subject -> row(s).  The atrial rows carry the gate's verdict: gated, though no --qc_csv is written
         self.volumes = {} if self.output_csv else None
         self.gate = {} if self.qc_csv or self.atrial_csv else None
         self.atrial = {} if self.atrial_csv else None
         self.score = {} if self.score_csv else None
+        self.confidence = {} if self.confidence_csv else None
         self._unscored = set()                          # data_dirs whose truth file is absent or refused: logged once, no back-fill
+        self._no_prob = set()                           # subjects an earlier run segmented: their probabilities are gone, logged once
 
     def statistics(self):
         """The device statistics this run needs of every label volume.  Device paths only: device_pipeline loads the HIP library."""
         from . import device_pipeline
         return ([device_pipeline.GateStats(self.seq, self.seg4)] if self.gate is not None else []) + \
             ([device_pipeline.AtrialStats()] if self.atrial is not None else []) + \
-            ([device_pipeline.ScoreStats(self.device)] if self.score is not None else [])
+            ([device_pipeline.ScoreStats(self.device)] if self.score is not None else []) + \
+            ([device_pipeline.ConfidenceStats(getattr(self.FLAGS, 'batch_slices', 128), self.n_class)] if self.confidence is not None else [])
 
     def subject_args(self, data_dir, nim, log, truth=None):
         """{key: argument} of the statistics that take one per subject.  --atrial_csv: (affine of the long-axis image, long axis), the
@@ -132,6 +139,8 @@ class LabelTables:
             self.atrial[data] = atrial.frame_rows(stats['atrial'], nim.affine, nim.header['pixdim'], self.gate[data][0])
         if 'score' in stats:
             self.score[data] = seg_score.frame_rows(stats['score'], nim.header['pixdim'])
+        if 'confidence' in stats:
+            self.confidence[data] = confidence.frame_rows(stats['confidence'])
 
     def _back_fill(self, rows, data, log):
         """A subject segmented by an earlier run (skipped by this one) into ``rows`` from its label file, the way the evaluation scripts
@@ -139,6 +148,11 @@ class LabelTables:
         data_dir = os.path.join(self.FLAGS.data_dir, data)
         seg_name = '{0}/{1}_{2}.nii.gz'.format(data_dir, 'seg4' if self.seq == 'la_4ch' and self.seg4 else 'seg', self.seq)
         sa_name = '{0}/sa.nii.gz'.format(data_dir)
+        if rows is self.confidence:                     # nothing to measure from: a label file holds no probabilities
+            if os.path.exists(seg_name) and data not in self._no_prob:
+                log('  {0} was segmented by an earlier run: its probabilities are gone, no confidence rows.'.format(data))
+                self._no_prob.add(data)
+            return
         if not os.path.exists(seg_name) or (rows is not self.gate and rows is not self.score and not os.path.exists(sa_name)):
             return
         nim = nifti.load(seg_name)
@@ -159,10 +173,11 @@ class LabelTables:
                 self.record(data, data_dir, nim, None, stats, log)
 
     def write(self, shard_subjects, log):
-        """The tables of this worker's subjects, sorted (the order of the evaluation scripts): volumes, atria, scores, gate -- verdicts the
+        """The tables of this worker's subjects, sorted (the order of the evaluation scripts): volumes, atria, scores, confidence, gate -- verdicts the
         atrial table had to produce land in the gate table, logged once.  The gate table is written only with --qc_csv."""
         F = self.FLAGS
-        for rows, csv in ((self.volumes, self.output_csv), (self.atrial, self.atrial_csv), (self.score, self.score_csv), (self.gate, self.qc_csv)):
+        for rows, csv in ((self.volumes, self.output_csv), (self.atrial, self.atrial_csv), (self.score, self.score_csv),
+                          (self.confidence, self.confidence_csv), (self.gate, self.qc_csv)):
             if not csv:
                 continue
             # with --work_stealing this worker may also have segmented subjects of other shards (their rows are in ``rows``), and
@@ -182,6 +197,11 @@ class LabelTables:
                 seg_score.write_csv(path, out)
                 log('Scores of {0} frames and labels against {1} written to {2}'.format(len(out), self.score_against, path))
                 continue
+            if rows is self.confidence:
+                out = [(data, r) for data in subjects for r in rows.get(data, [])]
+                confidence.write_csv(path, out)
+                log('Confidence of {0} frames and labels written to {1}'.format(len(out), path))
+                continue
             out = [(data, rows[data]) for data in subjects if data in rows]
             if rows is self.volumes:
                 measures.write_csv(path, measures.SA_COLUMNS, out)
@@ -197,6 +217,10 @@ class AorticTable:
         self.rows = {} if getattr(FLAGS, 'output_csv', '') else None       # subject -> row; none for one the quality control drops
         self.qc = getattr(FLAGS, 'aortic_qc', True)
         self.qc_full = bool(self.rows is not None and self.qc and getattr(FLAGS, 'aortic_qc_full', False))   # needs the aorta_qc statistics
+        self.confidence_csv = getattr(FLAGS, 'confidence_csv', '')
+        if self.confidence_csv and not FLAGS.process_seq:
+            raise ValueError('--confidence_csv summarises the probabilities of a whole sequence: it needs sequence mode (--process_seq)')
+        self.confidence = {} if self.confidence_csv else None           # subject -> confidence.frame_rows
         if self.rows is not None:
             if not FLAGS.process_seq:
                 raise ValueError('--output_csv writes the table of aortic/eval_aortic_area.py: it needs sequence mode')
@@ -234,8 +258,19 @@ class AorticTable:
                 return
         self.rows[data] = measures.ao_row(counts, pixdim, pp)
 
+    def record_confidence(self, data, cells):
+        """--confidence_csv: the subject's lines from its cells (confidence.cells_host or device_pipeline.ConfidenceStats)."""
+        if self.confidence is not None and cells is not None:
+            self.confidence[data] = confidence.frame_rows(cells)
+
     def write(self, data_list, log):
-        """The table of this worker's subjects in their order; a dropped subject has no line, as eval_aortic_area.py:68-69."""
+        """The table of this worker's subjects in their order; a dropped subject has no line, as eval_aortic_area.py:68-69.  The
+        confidence table likewise, whatever the quality control says of a subject."""
+        if self.confidence is not None:
+            out = [(data, r) for data in data_list for r in self.confidence.get(data, [])]
+            path = measures.shard_csv_name(self.confidence_csv, self.FLAGS.shard_index, self.FLAGS.num_shards)
+            confidence.write_csv(path, out)
+            log('Confidence of {0} frames and labels written to {1}'.format(len(out), path))
         if self.rows is None:
             return
         rows = [(data, self.rows[data]) for data in data_list if data in self.rows]

@@ -216,11 +216,29 @@ class SequenceRun:
             seg_time = time.time() - t0
             counts, stats, clip, ed_es = aux['counts'], aux['stats'], aux['clip'], None
         else:
+            want_prob = tables.confidence is not None       # --confidence_csv: the forward returns the probabilities too
             if forward is None:
-                forward = lambda b: {'pred': self.engine.run(b, want_prob=False)['pred']}
+                forward = lambda b: self.engine.run(b, want_prob=want_prob)
+            host_cells = None
+            if want_prob:                                   # confidence.cells_host of every chunk of slices, as the device adds them
+                from . import confidence
+                X2, Y2, x_pre, _, y_pre, _ = pipeline.pad_amounts(*image.shape[:2])
+                plain = forward
+
+                def forward(batch):
+                    nonlocal host_cells
+                    out = plain(batch)
+                    if 'prob' not in out:
+                        raise ValueError('--confidence_csv: the forward of the host path has to return prob next to pred')
+                    if host_cells is None:
+                        host_cells = confidence.HostCells(image.shape, (X2, Y2, x_pre, y_pre), out['prob'].shape[-1])
+                    host_cells.add(out['prob'], out['pred'])
+                    return out
             pred = pipeline.segment_sequence(image, forward, FLAGS.batch_slices, bool(getattr(FLAGS, 'numpy1_casting', False)))   # clips `image` in place
             seg_time = time.time() - t0
             (counts, stats), clip, ed_es = tables.from_labels(pred, args, tables.n_class), None, pipeline.pick_ed_es(pred, self.seq, FLAGS.seg4)
+            if host_cells is not None:
+                stats['confidence'] = host_cells.cells
         self.finish(item, nim, seg_time, pred, counts, stats, clip, lambda k: image[:, :, :, k], ed_es=ed_es, announce=False)
 
     def pipelined(self):

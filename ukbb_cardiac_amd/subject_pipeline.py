@@ -261,9 +261,16 @@ class SubjectPipeline:
             # element strides of the Fortran-ordered (X,Y,Z,T) volume
             pack_rescaled(slot.d_vol.data_ptr(), dtype, (X, Y, Z, T), (1, X, X * Y, X * Y * Z), lo, hi, (X2, Y2, x_pre, y_pre),
                           slot.d_batch.data_ptr(), cs)
+            # the statistics of the probabilities run chunk by chunk behind the forward, adding into outputs zeroed here
+            per_chunk = [entry for entry in slot.live if entry[0].per_chunk]
+            for stat, _, d_out, _, _ in per_chunk:
+                d_out[:stat.sizes(shape, n_class)[1]].zero_()
             forward_and_unpack(self.engine, slot.d_batch.data_ptr(), slot.d_pred.data_ptr(), shape, (X2, Y2, x_pre, y_pre), self.batch_slices,
-                               slot.d_lab.data_ptr(), slot.d_cnt.data_ptr(), cs)
+                               slot.d_lab.data_ptr(), slot.d_cnt.data_ptr(), cs,
+                               [(stat, d_work.data_ptr(), d_out.data_ptr()) for stat, d_work, d_out, _, _ in per_chunk])
             for stat, d_work, d_out, _, _ in slot.live:
+                if stat.per_chunk:
+                    continue
                 stat.launch(slot.d_lab.data_ptr(), shape, n_class, d_work.data_ptr(), d_out.data_ptr(), cs, (stat_args or {}).get(stat.key))
             if slot.gz:
                 from ._lib import check, lib
