@@ -128,6 +128,15 @@ void ukbb_fcn_destroy(ukbb_fcn_handle *h);
  * identical; it is a different instruction sequence from an fp32 MFMA, so it is offered as its own mode and reported
  * under its own name, never as the default.  Layers not converted yet run exactly as in UKBB_PREC_FP32. */
 #define UKBB_PREC_F32X3 2
+/* UKBB_PREC_BF16_STORE (UKBB_KIND_FCN only; additive to ABI 11): the FCN encoder on the bf16-storage kernels of the aortic U-Net.  Where it
+ * rounds: the folded 3x3 kernels are rounded to bf16 (RNE) once, when they are packed; the image is rounded to bf16 as the fused 1 -> 16 -> 16
+ * stem reads it and conv0_0's output as the stem hands it to conv0_1; every encoder map (conv0 .. conv4 and the maps between them) is rounded
+ * once, after bias + ReLU, as it is stored -- bf16, channel-blocked [N][C/16][H][W][16].  Accumulation is fp32 everywhere.  The squeeze launches
+ * and the head decode the stored bf16 values to fp32 on the way in (exact) and then run the very instruction sequence of UKBB_PREC_FP32 on
+ * them: the G_l maps, logits, prob and pred stay fp32 / int32.  UKBB_PREC_BF16 keeps its meaning on an FCN handle (operands only).  On every
+ * other kind set_precision returns UKBB_EARCH for this code: those kinds already store bf16 under UKBB_PREC_BF16.  Opt-in; each launch is graded
+ * in tests/test_fcn_bf16_store_launches_gpu.py. */
+#define UKBB_PREC_BF16_STORE 3
 int ukbb_fcn_set_precision(ukbb_fcn_handle *h, int precision);
 
 /* Pre-size the activation workspace for batches up to n x h x w (optional;

@@ -60,6 +60,7 @@ namespace {
     } while (0)
 
 constexpr float BN_EPS = 1e-3f;   // tf.layers.batch_normalization default
+const char *const BF16_STORE_FCN_ONLY = "UKBB_PREC_BF16_STORE is the FCN's bf16-storage mode; the U-Net kinds already store bf16 under UKBB_PREC_BF16";
 
 struct HostLayer {            // one conv(+BN) unit with BN folded (fp32, same op order as
     std::string name;         // ukbb_cardiac_amd/weights.py fold_bn)
@@ -137,20 +138,22 @@ struct ukbb_fcn_handle {
 
     // activation workspace
     std::vector<std::unique_ptr<DevBuf>> act;
-    std::vector<size_t> act_per_image;        // floats per image at the planned H,W
+    std::vector<size_t> act_per_image;        // elements per image at the planned H,W
+    std::vector<int> act_esz, act_alloc_esz;  // bytes of a stored element (2: bf16) / bytes the workspace holds per element (plan.h act_alloc_esz)
     std::vector<int> act_ch;                  // channels of the map (0: not a channel map); bf16 plans store maps with C > 16 channel-blocked
     std::vector<std::string> act_name;
     DevBuf io_image, io_logits, io_prob, io_pred;   // staging for forward_host
 
     // plan
-    int precision = 0;                        // 0: fp32; 1: bf16 operands for the MFMA convs (fp32 accumulate); 2: fp32 from bf16 pieces (head)
+    int precision = 0;                        // 0: fp32; 1: bf16 operands for the MFMA convs (fp32 accumulate); 2: fp32 from bf16 pieces (head);
+                                              // 3: FCN with bf16 encoder maps in HBM (UKBB_PREC_BF16_STORE)
     int plan_h = 0, plan_w = 0, cap_n = 0;
     bool plan_small = false;                  // plan built with the small-batch tilings
     int plan_n = 0;                           // ... for this largest batch
     int max_n = 0;                            // largest batch this handle was asked for (reserve / forward): the small-batch plan is
                                               // used only while that stays <= SMALL_BATCH, so a large-batch caller's tail batches do
                                               // not flip the plan (a rebuild re-allocates the workspace) back and forth
-    bool plan_bfio = false;                   // plan stores every activation between layers as bf16 (UKBB_PREC_BF16, U-Net)
+    bool plan_bfio = false;                   // plan stores every activation between layers as bf16 (UKBB_PREC_BF16, U-Net; UKBB_PREC_BF16_STORE, FCN encoder)
     std::vector<Op> ops;
     CineUnits cine;                           // what forward_cine holds per frame / window of this plan (plan.h)
     int last_n = 0;
@@ -387,7 +390,7 @@ int ensure_packed_lstm(ukbb_fcn_handle *h) {
 // ops' device pointers, and resets the run-time state (events, timing sums) of the previous plan.
 int materialize_plan(ukbb_fcn_handle *h, PlanLayout &L) {
     h->ops.clear();
-    h->act.clear(); h->act_per_image.clear(); h->act_name.clear(); h->act_ch.clear();
+    h->act.clear(); h->act_per_image.clear(); h->act_name.clear(); h->act_ch.clear(); h->act_esz.clear(); h->act_alloc_esz.clear();
     h->cap_n = 0;
     for (const ActSpec &s : L.acts) {
         h->act.emplace_back(new DevBuf);
@@ -395,6 +398,8 @@ int materialize_plan(ukbb_fcn_handle *h, PlanLayout &L) {
         h->act_per_image.push_back(s.per_image);
         h->act_name.push_back(s.name);
         h->act_ch.push_back(s.channels);
+        h->act_esz.push_back(s.esz);
+        h->act_alloc_esz.push_back((int)act_alloc_esz(h->arch, s));
     }
     for (Op &op : L.ops) {
         int rc = UKBB_OK;
@@ -465,7 +470,7 @@ int build_plan(ukbb_fcn_handle *h, int H, int W, int n_hint) {
 int ensure_capacity(ukbb_fcn_handle *h, int n) {
     if (n <= h->cap_n) return UKBB_OK;
     for (size_t i = 0; i < h->act.size(); ++i)
-        HIP_TRY(h->act[i]->ensure(h->act_per_image[i] * (size_t)n), UKBB_ENOMEM);
+        HIP_TRY(h->act[i]->ensure((h->act_per_image[i] * (size_t)n * h->act_alloc_esz[i] + 3) / 4), UKBB_ENOMEM);      // DevBufs count floats
     h->cap_n = n;
     return UKBB_OK;
 }
@@ -531,11 +536,10 @@ int run_plan(ukbb_fcn_handle *h, const float *image, int n, float *logits, float
     hipStream_t s_main = s;
     bool forked = false;
     // One launch of op i over images [n0, n0 + n) of the batch on stream s (the whole batch everywhere except inside a split range, below).
-    const size_t act_esz = h->plan_bfio ? 2 : 4;             // bytes per stored activation element
     auto launch_one = [&](size_t i, int n0, int n, hipStream_t s, hipError_t &e) -> int {
         const Op &op = h->ops[i];
         auto actp = [&](int id) -> float * {
-            return reinterpret_cast<float *>(reinterpret_cast<char *>(h->act[id]->p) + (size_t)n0 * h->act_per_image[id] * act_esz);
+            return reinterpret_cast<float *>(reinterpret_cast<char *>(h->act[id]->p) + (size_t)n0 * h->act_per_image[id] * h->act_esz[id]);
         };
         e = hipSuccess;
         switch (op.kind) {
@@ -578,6 +582,7 @@ int run_plan(ukbb_fcn_handle *h, const float *image, int n, float *logits, float
                 sa.w_g = dev_ptr(h, "sqg" + ls + "/w_g");
                 sa.out = actp(op.out);
                 sa.npix = (long long)n * op.H * op.W; sa.cin = L.cin;
+                sa.x_bf16 = h->plan_bfio ? 1 : 0; sa.hw = op.H * op.W;
                 e = launch_sqg(sa, s);
                 break;
             }
@@ -586,6 +591,7 @@ int run_plan(ukbb_fcn_handle *h, const float *image, int n, float *logits, float
                 for (int j = 0; j < 4; ++j) {
                     sa[j] = SqgArgs{};
                     sa[j].cin = 32 << j;
+                    sa[j].x_bf16 = h->plan_bfio ? 1 : 0;         // one input format per launch
                     if (op.mlayer[j] < 0) continue;              // level handled by a launch of its own: npix = 0 -> no blocks
                     const HostLayer &L = h->layers[op.mlayer[j]];
                     const std::string ls = std::to_string(j + 1);
@@ -594,6 +600,7 @@ int run_plan(ukbb_fcn_handle *h, const float *image, int n, float *logits, float
                     sa[j].w_g = dev_ptr(h, "sqg" + ls + "/w_g");
                     sa[j].out = actp(op.mout[j]);
                     sa[j].npix = (long long)n * op.mh[j] * op.mw[j]; sa[j].cin = L.cin;
+                    sa[j].hw = op.mh[j] * op.mw[j];
                 }
                 e = launch_sqg_multi(sa, s);
                 break;
@@ -610,6 +617,7 @@ int run_plan(ukbb_fcn_handle *h, const float *image, int n, float *logits, float
                 ha.logits = logits; ha.prob = prob; ha.pred = pred;
                 ha.N = n; ha.H = op.H; ha.W = op.W; ha.n_class = a.n_class;
                 ha.x3 = h->precision == UKBB_PREC_F32X3;
+                ha.conv0_bf16 = h->plan_bfio ? 1 : 0;
                 e = launch_head(ha, s);
                 break;
             }
@@ -897,10 +905,11 @@ int ukbb_fcn_debug_damage_guard(ukbb_fcn_handle *h, const char *buffer, long lon
 int ukbb_fcn_debug_plan_layout(const ukbb_fcn_arch *arch, int precision, int n, int H, int W, int cus, char *buf, size_t cap) {
     static const char *const kinds[] = {"first", "conv", "head", "tconv", "logits", "sqg", "sqg_multi", "tail", "stem", "first3d", "conv3d", "tconv3d"};
     if (!arch || (!buf && cap) || cus < 1) { set_err("debug_plan_layout: bad argument"); return UKBB_EINVAL; }
-    if (precision != UKBB_PREC_FP32 && precision != UKBB_PREC_BF16 && precision != UKBB_PREC_F32X3) { set_err("debug_plan_layout: bad precision"); return UKBB_EINVAL; }
+    if (precision != UKBB_PREC_FP32 && precision != UKBB_PREC_BF16 && precision != UKBB_PREC_F32X3 && precision != UKBB_PREC_BF16_STORE) { set_err("debug_plan_layout: bad precision"); return UKBB_EINVAL; }
     int rc = check_shape(n, H, W);
     if (rc) return rc;
     if (arch->kind == UKBB_KIND_TEMPORAL_UNET && precision == UKBB_PREC_BF16) { set_err("the Temporal-UNet's 3-D convolutions are built for fp32 only (no bf16 plan)"); return UKBB_EARCH; }
+    if (arch->kind != UKBB_KIND_FCN && precision == UKBB_PREC_BF16_STORE) { set_err("%s", BF16_STORE_FCN_ONLY); return UKBB_EARCH; }
     PlanLayout L;
     rc = layout_plan(*arch, precision, H, W, n, cus, L);
     if (rc) return rc;
@@ -913,7 +922,7 @@ int ukbb_fcn_debug_plan_layout(const ukbb_fcn_arch *arch, int precision, int n, 
         out += line;
     }
     for (const ActSpec &s : L.acts) {
-        snprintf(line, sizeof line, "act %s %zu %d\n", s.name.empty() ? "-" : s.name.c_str(), s.per_image, s.channels);
+        snprintf(line, sizeof line, "act %s %zu %d %zu\n", s.name.empty() ? "-" : s.name.c_str(), s.per_image, s.channels, act_alloc_esz(*arch, s));
         out += line;
     }
     snprintf(line, sizeof line, "plan split %d %d bfio %d feat_buf %d lstm %d %d %d %d\n", L.split_first, L.split_last, (int)L.bfio, L.feat_buf,
@@ -1584,7 +1593,8 @@ double ukbb_fcn_kernel_mfma_macs_issued(const ukbb_fcn_handle *h, int i) {
 }
 
 int ukbb_fcn_set_precision(ukbb_fcn_handle *h, int precision) {
-    if (!h || (precision != UKBB_PREC_FP32 && precision != UKBB_PREC_BF16 && precision != UKBB_PREC_F32X3)) { set_err("set_precision: bad argument"); return UKBB_EINVAL; }
+    if (!h || (precision != UKBB_PREC_FP32 && precision != UKBB_PREC_BF16 && precision != UKBB_PREC_F32X3 && precision != UKBB_PREC_BF16_STORE)) { set_err("set_precision: bad argument"); return UKBB_EINVAL; }
+    if (h->arch.kind != UKBB_KIND_FCN && precision == UKBB_PREC_BF16_STORE) { set_err("set_precision: %s", BF16_STORE_FCN_ONLY); return UKBB_EARCH; }
     if (h->arch.kind == UKBB_KIND_TEMPORAL_UNET && precision == UKBB_PREC_BF16) {
         set_err("set_precision: the Temporal-UNet's 3-D convolutions are built for fp32 only (no bf16 plan)");
         return UKBB_EARCH;
@@ -1649,7 +1659,7 @@ int64_t ukbb_fcn_get_activation(ukbb_fcn_handle *h, const char *name, float *dst
         const int64_t n = (int64_t)h->act_per_image[i] * h->last_n;
         if (!dst) return n;
         if (cap < n) { set_err("get_activation: buffer too small (%lld < %lld)", (long long)cap, (long long)n); return UKBB_EINVAL; }
-        if (h->plan_bfio) {                            // stored as bf16: widen on the host
+        if (h->act_esz[i] == 2) {                      // stored as bf16: widen on the host
             std::vector<uint16_t> tmp((size_t)n);
             if (hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
                 hipMemcpy(tmp.data(), h->act[i]->p, (size_t)n * 2, hipMemcpyDeviceToHost) != hipSuccess) {

@@ -301,6 +301,9 @@ struct SqgArgs {
     float *out;              // [npix][64]
     long long npix;
     int cin;
+    int x_bf16;              // input format.  0: x is fp32 [npix][cin].  1 (UKBB_PREC_BF16_STORE): x is bf16, channel-blocked [N][cin/16][hw][16]
+                             // (ConvConfig::pc == 5), decoded to fp32 on the way in (exact); everything behind the load is the fp32 launch
+    int hw;                  // x_bf16 only: pixels per image (npix = N * hw)
 };
 hipError_t launch_sqg(const SqgArgs &a, hipStream_t s);
 struct SqgMultiArgs { SqgArgs lv[4]; int nb[4]; };   // levels 1..4 (C_in 32, 64, 128, 256) and their virtual grid sizes
@@ -325,6 +328,8 @@ struct HeadArgs {
     int N, H, W, n_class;
     int x3;                  // UKBB_PREC_F32X3: out0's level-0 slice and out1 from bf16 pieces (needs w_o0x3 / w_o1x3)
     int diag;                // diagnostic builds only (-DUKBB_DIAG, env UKBB_HEAD_DIAG): ablation bits of fcn_head_pc_kernel
+    int conv0_bf16;          // input format of conv0.  0: fp32 [N,H,W,16].  1 (UKBB_PREC_BF16_STORE): bf16 [N][1][H][W][16], decoded to fp32 on the
+                             // way in (exact); not combined with x3
 };
 hipError_t launch_head(const HeadArgs &a, hipStream_t s);
 int head_tail_form();      // ukbb_fcn_head_tail_form()

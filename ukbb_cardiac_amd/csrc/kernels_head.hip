@@ -85,11 +85,34 @@ __device__ __forceinline__ void chain_32to32(const float *wp, int lane, const f3
     }
 }
 
+// ---- bf16 channel-blocked inputs (UKBB_PREC_BF16_STORE: SqgArgs::x_bf16, HeadArgs::conv0_bf16) ------------------------------------
+// A pixel's 16-channel block is 32 bytes, and the two lanes that hold a pixel (p, g = 0 | 1) fetch it as ONE unit: lane g loads the 16 bytes
+// of channels 8 g .. 8 g + 7, so a wave's 32 consecutive pixels are one contiguous 1-KB load.  The fp32 k order (pack_sq) wants channels
+// 4 g .. 4 g + 3 (k-group 2 c) and 8 + 4 g .. 8 + 4 g + 3 (k-group 2 c + 1) of chunk c on lane g, so the halves exchange one 8-byte piece
+// with v_permlane32_swap a, b (a's upper 32 lanes <-> b's lower 32 lanes) and widen: bf16 -> fp32 is a shift / a mask, exact.  What the
+// MFMAs behind it see is, value for value and in the same order, what the fp32 launch sees for a map that holds the same numbers.
+// Every lane of the wave must be active (the callers clamp the address of a pixel past the map instead of masking the lane).
+__device__ __forceinline__ void bf16_block_to_k(const u32x4 &d, f32x4 &x0, f32x4 &x1) {
+    const auto s0 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
+    const auto s1 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);
+    x0 = f32x4{__builtin_bit_cast(float, s0[0] << 16), __builtin_bit_cast(float, s0[0] & 0xffff0000u),
+               __builtin_bit_cast(float, s1[0] << 16), __builtin_bit_cast(float, s1[0] & 0xffff0000u)};
+    x1 = f32x4{__builtin_bit_cast(float, s0[1] << 16), __builtin_bit_cast(float, s0[1] & 0xffff0000u),
+               __builtin_bit_cast(float, s1[1] << 16), __builtin_bit_cast(float, s1[1] & 0xffff0000u)};
+}
+__device__ __forceinline__ u32x4 ld_block_half(const char *p) { return *reinterpret_cast<const u32x4 *>(p); }
+// lane (pixel q of the flattened [N * hw] map, half g): address of its half of chunk 0's block; chunk c lies c * hw * 32 bytes further
+__device__ __forceinline__ const char *bf16_block_addr(const SqgArgs &a, long long q, int nchunk, int g) {
+    const unsigned n = (unsigned)q / (unsigned)a.hw, pix = (unsigned)q - n * (unsigned)a.hw;      // q < 2^31 (engine.cpp check_shape)
+    return reinterpret_cast<const char *>(a.x) + ((size_t)n * nchunk * a.hw + pix) * 32 + 16 * g;
+}
+
 // ---------------------------------------------------------------------------
 // sqg_kernel: G[px][64] = W0_l (64x32) * relu(Ws (32xCIN) * x[px] + bs)   at low resolution.
 // One wave per 32 consecutive pixels of the flattened [N*H_l*W_l] map; no LDS.
+// BF: x is bf16, channel-blocked (SqgArgs::x_bf16).
 // ---------------------------------------------------------------------------
-template <int CIN>
+template <int CIN, bool BF = false>
 __device__ __forceinline__ void sqg_body(const SqgArgs &a, int vblock, int vgrid) {
     const int lane = threadIdx.x & 63;
     const int p = lane & 31, g = lane >> 5;
@@ -97,7 +120,6 @@ __device__ __forceinline__ void sqg_body(const SqgArgs &a, int vblock, int vgrid
     for (long long blk = (long long)vblock * 4 + (threadIdx.x >> 6); blk < nblk; blk += (long long)vgrid * 4) {
         const long long q = blk * 32 + p;
         const bool valid = q < a.npix;
-        const float *xp = a.x + (valid ? q : a.npix - 1) * CIN + 4 * g;
         f32x16 S = bias_tile(a.b_s, g);
         // k-step (j,i) pairs channels 8j+i (lanes 0-31) and 8j+4+i (lanes 32-63).
         // Levels 3-4 are small (1-2 blocks per wave): all of the block's feature loads are issued before
@@ -105,6 +127,28 @@ __device__ __forceinline__ void sqg_body(const SqgArgs &a, int vblock, int vgrid
         // (at most 128 channels at a time: inside sqg_multi_kernel this body must not push the register count past the
         // two-waves-per-SIMD limit, or level 1's bandwidth-bound stream loses half of its loads in flight)
         constexpr int XG = CIN / 8 < 16 ? CIN / 8 : 16;
+        if constexpr (BF) {                             // the same k-steps in the same order, two k-groups per 32-byte block
+            const char *xb = bf16_block_addr(a, valid ? q : a.npix - 1, CIN / 16, g);
+            const size_t cstride = (size_t)a.hw * 32;
+#pragma unroll
+            for (int j0 = 0; j0 < CIN / 8; j0 += XG) {
+                u32x4 xr[XG / 2];
+#pragma unroll
+                for (int c = 0; c < XG / 2; ++c) xr[c] = ld_block_half(xb + (j0 / 2 + c) * cstride);
+#pragma unroll
+                for (int c = 0; c < XG / 2; ++c) {
+                    f32x4 xk[2];
+                    bf16_block_to_k(xr[c], xk[0], xk[1]);
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const f32x4 wv = ld4(a.w_s + ((j0 + 2 * c + h) * 64 + lane) * 4);
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) S = MFMA32(wv[i], xk[h][i], S);
+                    }
+                }
+            }
+        } else {
+        const float *xp = a.x + (valid ? q : a.npix - 1) * CIN + 4 * g;
 #pragma unroll
         for (int j0 = 0; j0 < CIN / 8; j0 += XG) {
             f32x4 xv[XG];
@@ -116,6 +160,7 @@ __device__ __forceinline__ void sqg_body(const SqgArgs &a, int vblock, int vgrid
 #pragma unroll
                 for (int i = 0; i < 4; ++i) S = MFMA32(wv[i], xv[j][i], S);
             }
+        }
         }
         relu16(S);
         f32x16 G0, G1;
@@ -141,8 +186,8 @@ __device__ __forceinline__ void sqg_body(const SqgArgs &a, int vblock, int vgrid
 // matrices and the bias tile in registers and requests the features of the wave's next 32-pixel
 // block before it starts the MFMA chains of the current one: loads, MFMAs and stores of different
 // blocks overlap inside a wave instead of relying on occupancy alone.
-template <int CIN>
-__global__ __launch_bounds__(256) void sqg_kernel(const SqgArgs a) { sqg_body<CIN>(a, blockIdx.x, gridDim.x); }
+template <int CIN, bool BF = false>
+__global__ __launch_bounds__(256) void sqg_kernel(const SqgArgs a) { sqg_body<CIN, BF>(a, blockIdx.x, gridDim.x); }
 
 // TR: the last layer is computed transposed (G^T = S^T W0^T: the same registers with the MFMA operands swapped), which puts
 // the 32 output channels of a block on the lanes and the pixels on the registers: every store instruction then writes two
@@ -150,8 +195,10 @@ __global__ __launch_bounds__(256) void sqg_kernel(const SqgArgs a) { sqg_body<CI
 // LT: the features of a block (32 pixels x CIN floats, one contiguous chunk of the NHWC map) are fetched with fully contiguous
 // 1-KB wave loads and turned into the operand layout (pixel on the lane) through a wave-private LDS tile, instead of loads
 // that touch 32 rows with 32 bytes each.
+// BF: x is bf16, channel-blocked (SqgArgs::x_bf16).  A block's 32 pixels x one 16-channel chunk are 1 KB contiguous and each lane pair loads a
+// pixel's 32 bytes, so the loads are whole-line as they stand and LT is not used; a block in flight is NJ / 2 registers of 16 bytes.
 constexpr int SQG_LDS_WAVE = 32 * (64 + 4);
-template <int CIN, bool TR = false, bool LT = false>
+template <int CIN, bool TR = false, bool LT = false, bool BF = false>
 __device__ __forceinline__ void sqg_stream_body(const SqgArgs &a, int vblock, int vgrid, float *lds_x = nullptr) {
     constexpr int NJ = CIN / 8;
     const int lane = threadIdx.x & 63;
@@ -170,8 +217,16 @@ __device__ __forceinline__ void sqg_stream_body(const SqgArgs &a, int vblock, in
     constexpr int RS = CIN + 4;                         // LDS row stride (floats): b128-aligned, the strided read is conflict-free
     float *const xl = LT ? lds_x + (threadIdx.x >> 6) * SQG_LDS_WAVE : nullptr;
     const long long qlast = a.npix * (CIN / 4) - 1;     // last valid 16-byte quad of the map (rows past the end are never stored)
+    static_assert(!(LT && BF), "the LDS transpose serves the fp32 NHWC map only");
+    constexpr int NX = BF ? NJ / 2 : NJ;                // 16-byte registers of a block in flight
     auto fetch = [&](long long blk, f32x4 *dst) {
-        if constexpr (LT) {
+        if constexpr (BF) {
+            const long long q = blk * 32 + p;
+            const char *xb = bf16_block_addr(a, q < a.npix ? q : a.npix - 1, CIN / 16, g);
+            const size_t cstride = (size_t)a.hw * 32;
+#pragma unroll
+            for (int c = 0; c < NX; ++c) dst[c] = __builtin_bit_cast(f32x4, ld_block_half(xb + c * cstride));
+        } else if constexpr (LT) {
 #pragma unroll
             for (int t = 0; t < NJ; ++t) {
                 const long long f = blk * (32 * (CIN / 4)) + t * 64 + lane;
@@ -185,11 +240,14 @@ __device__ __forceinline__ void sqg_stream_body(const SqgArgs &a, int vblock, in
         }
     };
     long long blk = (long long)vblock * 4 + (threadIdx.x >> 6);
-    f32x4 xn[NJ];
+    f32x4 xn[NX];
     if (blk < nblk) fetch(blk, xn);
     for (; blk < nblk; blk += step) {
         f32x4 xv[NJ];
-        if constexpr (LT) {
+        if constexpr (BF) {
+#pragma unroll
+            for (int c = 0; c < NX; ++c) bf16_block_to_k(__builtin_bit_cast(u32x4, xn[c]), xv[2 * c], xv[2 * c + 1]);
+        } else if constexpr (LT) {
 #pragma unroll
             for (int t = 0; t < NJ; ++t) {
                 const int f = t * 64 + lane;
@@ -263,23 +321,23 @@ __device__ __forceinline__ void sqg_stream_body(const SqgArgs &a, int vblock, in
     }
 }
 
-template <int CIN>
-__global__ __launch_bounds__(256) void sqg_stream_kernel(const SqgArgs a) { sqg_stream_body<CIN>(a, blockIdx.x, gridDim.x); }
+template <int CIN, bool BF = false>
+__global__ __launch_bounds__(256) void sqg_stream_kernel(const SqgArgs a) { sqg_stream_body<CIN, false, false, BF>(a, blockIdx.x, gridDim.x); }
 
 // Levels 1-4 in ONE launch (C_in = 32, 64, 128, 256).  Levels 2-4 together are a tenth of level 1's work and as
 // launches of their own were dominated by launch ramp and tail (13-25 us each for 2-9 us of work); level 1 is a pure
 // HBM stream (82 MB in, 164 MB out at batch 64).  r02: every launch of this network costs ~10 us of fixed time
 // (dispatch + first-load latency + tail, measured as 2 t(N=64) - t(N=128) per kernel), so the four go out together after
 // level 4: the small levels' blocks come first and finish inside the first microseconds of level 1's stream.
-template <bool TR, bool LT>
+template <bool TR, bool LT, bool BF = false>
 __global__ __launch_bounds__(256, 2) void sqg_multi_kernel(const SqgMultiArgs m) {
     __shared__ __attribute__((aligned(16))) float lds_x[LT ? 4 * SQG_LDS_WAVE : 4];
     const int b = blockIdx.x;
     const int e1 = m.nb[1], e2 = e1 + m.nb[2], e3 = e2 + m.nb[3];
-    if (b < e1) sqg_stream_body<64, TR, LT>(m.lv[1], b, m.nb[1], lds_x);
-    else if (b < e2) sqg_body<128>(m.lv[2], b - e1, m.nb[2]);
-    else if (b < e3) sqg_body<256>(m.lv[3], b - e2, m.nb[3]);
-    else sqg_stream_body<32, TR, LT>(m.lv[0], b - e3, m.nb[0], lds_x);
+    if (b < e1) sqg_stream_body<64, TR, LT, BF>(m.lv[1], b, m.nb[1], lds_x);
+    else if (b < e2) sqg_body<128, BF>(m.lv[2], b - e1, m.nb[2]);
+    else if (b < e3) sqg_body<256, BF>(m.lv[3], b - e2, m.nb[3]);
+    else sqg_stream_body<32, TR, LT, BF>(m.lv[0], b - e3, m.nb[0], lds_x);
 }
 
 hipError_t launch_sqg_multi(const SqgArgs lv[4], hipStream_t s) {
@@ -293,7 +351,11 @@ hipError_t launch_sqg_multi(const SqgArgs lv[4], hipStream_t s) {
         m.nb[i] = (int)wg;
         total += m.nb[i];
     }
-    hipLaunchKernelGGL((sqg_multi_kernel<true, true>), dim3((unsigned)total), dim3(256), 0, s, m);
+    const int bf = lv[0].x_bf16;                        // one input format per launch: the four maps belong to one plan
+    for (int i = 1; i < 4; ++i) if (lv[i].x_bf16 != bf) return hipErrorInvalidValue;
+    for (int i = 0; i < 4; ++i) if (bf && lv[i].npix && (lv[i].hw < 1 || lv[i].npix % lv[i].hw)) return hipErrorInvalidValue;
+    if (bf) hipLaunchKernelGGL((sqg_multi_kernel<true, false, true>), dim3((unsigned)total), dim3(256), 0, s, m);
+    else hipLaunchKernelGGL((sqg_multi_kernel<true, true>), dim3((unsigned)total), dim3(256), 0, s, m);
     return hipGetLastError();
 }
 
@@ -302,6 +364,17 @@ hipError_t launch_sqg(const SqgArgs &a, hipStream_t s) {
     long long wg = (nblk + 3) / 4;
     if (wg > 256 * 8) wg = 256 * 8;
     dim3 grid((unsigned)wg), block(256);
+    if (a.x_bf16) {
+        if (a.hw < 1 || a.npix % a.hw) return hipErrorInvalidValue;
+        switch (a.cin) {
+            case 32: hipLaunchKernelGGL((sqg_stream_kernel<32, true>), grid, block, 0, s, a); break;
+            case 64: hipLaunchKernelGGL((sqg_stream_kernel<64, true>), grid, block, 0, s, a); break;
+            case 128: hipLaunchKernelGGL((sqg_kernel<128, true>), grid, block, 0, s, a); break;
+            case 256: hipLaunchKernelGGL((sqg_kernel<256, true>), grid, block, 0, s, a); break;
+            default: return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
+    }
     switch (a.cin) {
         case 32: hipLaunchKernelGGL(sqg_stream_kernel<32>, grid, block, 0, s, a); break;
         case 64: hipLaunchKernelGGL(sqg_stream_kernel<64>, grid, block, 0, s, a); break;
@@ -445,7 +518,8 @@ static_assert(fin_slot(2) == 7 && fin_slot(6) == 23, "tail steps end well inside
 
 // The consumer waves (0-3) of the fp32 separable instance of fcn_head_pc_kernel; same barriers, hand-over tile and block order as the
 // in-stage loop in the kernel (barrier X, then A_s and B_s per stage).
-template <int NCLS>
+// BF: conv0 is bf16 (HeadArgs::conv0_bf16); the prefetched block half rides in xv0 and is widened where the fp32 form first uses x0 / x1.
+template <int NCLS, bool BF>
 __device__ __forceinline__ void head_consumer_deferred(const HeadArgs &a, float *lds, int nstages, int tiles_x, int tiles_y) {
     using LM = HeadLds<false>;
     constexpr int L_WS0 = LM::WS0, L_WO0 = LM::WO0, L_WO1 = LM::WO1, L_BS0 = LM::BS0, L_BO1 = LM::BO1, L_WLG = LM::WLG, L_BLG = LM::BLG;
@@ -462,10 +536,13 @@ __device__ __forceinline__ void head_consumer_deferred(const HeadArgs &a, float 
     };
     f32x4 xv0 = {0.f, 0.f, 0.f, 0.f}, xv1 = xv0;          // conv0 features of the NEXT block, prefetched
     size_t qnext = 0;                                   // and its pixel index: pixel_of runs once per stage
+    auto fetch_conv0 = [&](size_t q) {
+        if constexpr (BF) xv0 = __builtin_bit_cast(f32x4, ld_block_half(reinterpret_cast<const char *>(a.conv0) + q * 32 + 16 * g));
+        else { xv0 = ld4(a.conv0 + q * 16 + 4 * g); xv1 = ld4(a.conv0 + q * 16 + 8 + 4 * g); }
+    };
     if (nstages > 0) {
         qnext = pixel_of(0);
-        xv0 = ld4(a.conv0 + qnext * 16 + 4 * g);
-        xv1 = ld4(a.conv0 + qnext * 16 + 8 + 4 * g);
+        fetch_conv0(qnext);
     }
     __syncthreads();                                    // barrier X
 #ifdef UKBB_DIAG
@@ -559,7 +636,7 @@ __device__ __forceinline__ void head_consumer_deferred(const HeadArgs &a, float 
 #pragma unroll 1
     for (int s = 0; s < nstages; ++s) {
         const size_t q = qnext;
-        const f32x4 x0 = xv0, x1 = xv1;
+        f32x4 x0 = xv0, x1 = xv1;
 #ifdef UKBB_DIAG
         unsigned long long hs_p = __builtin_amdgcn_s_memtime();
 #endif
@@ -579,10 +656,10 @@ __device__ __forceinline__ void head_consumer_deferred(const HeadArgs &a, float 
         UKBB_HS(hs_r, hs_p)
         __syncthreads();                                // barrier B_s: px may be overwritten
         UKBB_HS(hs_b, hs_p)
+        if constexpr (BF) bf16_block_to_k(__builtin_bit_cast(u32x4, xv0), x0, x1);
         if (s + 1 < nstages) {                          // features of the next block: a whole stage to arrive
             qnext = pixel_of(s + 1);
-            xv0 = ld4(a.conv0 + qnext * 16 + 4 * g);
-            xv1 = ld4(a.conv0 + qnext * 16 + 8 + 4 * g);
+            fetch_conv0(qnext);
         }
         // ---- same_dim0 and out0 (slots 0..39), with the seven steps of the tail of block s - 1 spread between their MFMAs
         // (at s = 0 that tail is all zeros and is not stored) ----
@@ -674,8 +751,10 @@ __device__ __forceinline__ void head_consumer_deferred(const HeadArgs &a, float 
 // DG: the r02-r07 direct 2-D gather (UKBB_HEAD_DIRECT_GATHER=1, A/B); otherwise the separable one
 // IT: the consumers finish a block's logits inside its own stage (r01-r08; UKBB_HEAD_INLINE_TAIL=1, A/B).  The fp32 separable instance
 // defers them instead (r11, DESIGN.md section 4 "Deferred tail"); the X3 and DG instances exist with IT = true only.
-template <int NCLS, bool X3 = false, bool DG = false, bool IT = true>
+// BF: conv0 is bf16 [N][1][H][W][16] (HeadArgs::conv0_bf16, UKBB_PREC_BF16_STORE), widened to fp32 on the way in; the fp32 instances only.
+template <int NCLS, bool X3 = false, bool DG = false, bool IT = true, bool BF = false>
 __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
+    static_assert(!(X3 && BF), "bf16 conv0 is not combined with the f32x3 head");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     using LM = HeadLds<X3>;
     constexpr int L_WS0 = LM::WS0, L_WO0 = LM::WO0, L_WO1 = LM::WO1, L_BS0 = LM::BS0, L_BO0 = LM::BO0, L_BO1 = LM::BO1, L_WLG = LM::WLG, L_BLG = LM::BLG;
@@ -931,7 +1010,7 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
         else if (__builtin_amdgcn_readfirstlane(tid) < 256) run(I0);
         else run(I1);
     } else if constexpr (!X3 && !DG && !IT) {
-        head_consumer_deferred<NCLS>(a, lds, nstages, tiles_x, tiles_y);
+        head_consumer_deferred<NCLS, BF>(a, lds, nstages, tiles_x, tiles_y);
     } else {
         const int wave = threadIdx.x >> 6;
         const float *w_s0 = lds + L_WS0, *w_o0 = lds + L_WO0, *w_o1 = lds + L_WO1, *w_lg = lds + L_WLG;
@@ -945,11 +1024,11 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
             return ((size_t)n * a.H + y) * a.W + x;
         };
         f32x4 xv0 = {0.f, 0.f, 0.f, 0.f}, xv1 = xv0;      // conv0 features of the NEXT block, prefetched
-        if (nstages > 0) {
-            const size_t q0 = pixel_of(0);
-            xv0 = ld4(a.conv0 + q0 * 16 + 4 * g);
-            xv1 = ld4(a.conv0 + q0 * 16 + 8 + 4 * g);
-        }
+        auto fetch_conv0 = [&](size_t q) {
+            if constexpr (BF) xv0 = __builtin_bit_cast(f32x4, ld_block_half(reinterpret_cast<const char *>(a.conv0) + q * 32 + 16 * g));
+            else { xv0 = ld4(a.conv0 + q * 16 + 4 * g); xv1 = ld4(a.conv0 + q * 16 + 8 + 4 * g); }
+        };
+        if (nstages > 0) fetch_conv0(pixel_of(0));
         __syncthreads();                                // barrier X
 #ifdef UKBB_DIAG
         // diagnostic build, UKBB_HEAD_STAMPS=1: where an MFMA wave's stage goes -- wait at barrier A (the producers' hand-off), the LDS
@@ -960,7 +1039,7 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
 #pragma unroll 1
         for (int s = 0; s < nstages; ++s) {
             const size_t q = pixel_of(s);
-            const f32x4 x0 = xv0, x1 = xv1;
+            f32x4 x0 = xv0, x1 = xv1;
 #ifdef UKBB_DIAG
             unsigned long long hs_p = __builtin_amdgcn_s_memtime();
 #endif
@@ -980,11 +1059,8 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
             UKBB_HS(hs_r, hs_p)
             __syncthreads();                            // barrier B_s: px may be overwritten
             UKBB_HS(hs_b, hs_p)
-            if (s + 1 < nstages) {                      // features of the next block: a whole stage to arrive
-                const size_t qn = pixel_of(s + 1);
-                xv0 = ld4(a.conv0 + qn * 16 + 4 * g);
-                xv1 = ld4(a.conv0 + qn * 16 + 8 + 4 * g);
-            }
+            if constexpr (BF) bf16_block_to_k(__builtin_bit_cast(u32x4, xv0), x0, x1);
+            if (s + 1 < nstages) fetch_conv0(pixel_of(s + 1));   // features of the next block: a whole stage to arrive
             // ---- same_dim0 ----
             f32x16 S = bias_tile_lds(lds + L_BS0, g);
             {
@@ -1135,6 +1211,8 @@ static hipError_t launch_head_pc_nc(const HeadArgs &a, dim3 grid, hipStream_t s)
     static const bool dg = [] { const char *e = getenv("UKBB_HEAD_DIRECT_GATHER"); return e && atoi(e) != 0; }();   // A/B knob (r08)
     static const bool inline_tail = [] { const char *e = getenv("UKBB_HEAD_INLINE_TAIL"); return e && atoi(e) != 0; }();   // A/B knob (r11)
 #define UKBB_HEAD_GO(X3, DG, IT, BYTES) launch_lds<fcn_head_pc_kernel<NC, X3, DG, IT>>(grid, dim3(768), BYTES, s, a)
+#define UKBB_HEAD_GO_BF(DG, IT, BYTES) launch_lds<fcn_head_pc_kernel<NC, false, DG, IT, true>>(grid, dim3(768), BYTES, s, a)
+    if (a.x3 && a.conv0_bf16) return hipErrorInvalidValue;      // no such instance (include/ukbb_fcn.h: the modes are not combined)
     if (a.x3 && a.w_o1x3 && a.w_o0x3) {                 // UKBB_PREC_F32X3; its tail stays in the stage (profiles/r11_notes.md)
         constexpr int ldsx = HEADPC_X3_LDS_FLOATS * 4;
         g_head_tail_form.store(1, std::memory_order_relaxed);
@@ -1146,9 +1224,14 @@ static hipError_t launch_head_pc_nc(const HeadArgs &a, dim3 grid, hipStream_t s)
     if (a.diag & 6) it = true;                          // ablation bits 2 and 4 exist in the in-stage loop only
 #endif
     g_head_tail_form.store(dg || it ? 1 : 0, std::memory_order_relaxed);
+    if (a.conv0_bf16) {                                 // UKBB_PREC_BF16_STORE: the same three forms behind a bf16 load
+        if (dg) return UKBB_HEAD_GO_BF(true, true, lds);
+        return it ? UKBB_HEAD_GO_BF(false, true, lds) : UKBB_HEAD_GO_BF(false, false, lds);
+    }
     if (dg) return UKBB_HEAD_GO(false, true, true, lds);
     return it ? UKBB_HEAD_GO(false, false, true, lds) : UKBB_HEAD_GO(false, false, false, lds);
 #undef UKBB_HEAD_GO
+#undef UKBB_HEAD_GO_BF
 }
 
 static hipError_t launch_head_pc(const HeadArgs &a, hipStream_t s) {

@@ -378,6 +378,10 @@ int choose_cfg_raw(const std::string &layer, int ks, int stride, int c0, int c1,
 // r05: the U-Net of a UNet-LSTM handle takes the same bf16-storage plan (its last map, net['conv0_up'], feeds the ConvLSTM as bf16; the
 // LSTM then keeps gx and the hidden maps in bf16 as well, cell state and arithmetic fp32: run_bilstm)
 int bf16_mode(int kind, int precision) { return precision != 1 ? 0 : kind != UKBB_KIND_FCN ? 2 : 1; }
+// ... and with UKBB_PREC_BF16_STORE (FCN handles only; the engine refuses the code elsewhere) the FCN encoder takes the same bf16-storage
+// kernels: mode 2.  Its squeeze launches and head read the bf16 maps (kernels_head.hip) and keep G_l, logits, prob and pred in fp32.  What
+// UKBB_PREC_BF16 means on an FCN handle (mode 1, above) is pinned by recorded plans and graders and does not move.
+int plan_bf16_mode(int kind, int precision) { return kind == UKBB_KIND_FCN && precision == UKBB_PREC_BF16_STORE ? 2 : bf16_mode(kind, precision); }
 
 // bf16 storage: the fused variants of the level-0 tilings (ConvConfig::fuse: 1 = first layer in the staging, 2 = logits in the
 // epilogue), first fit in measured order; -1 if none fits (the plan then keeps that layer as a launch of its own).
@@ -449,7 +453,7 @@ struct Planner {               // what the plan_* helpers below share
         return -1;
     }
     int new_act(const std::string &name, size_t per_image, int channels = 0) {
-        L.acts.push_back({name, per_image, channels});
+        L.acts.push_back({name, per_image, channels, bfm == 2 && channels > 0 ? 2 : 4});      // bf16 storage: the channel maps
         return (int)L.acts.size() - 1;
     }
 };
@@ -615,7 +619,7 @@ int layout_encoder(Planner &p, const Knobs &k, int H, int W, std::vector<int> &l
     // runs as its own launch, bf16 out)
     const bool can_fuse = !k.no_fuse_first && std0 && (p.bfm != 2 || pick_fused_bf_cfg("conv0_1", 3, 1, 16, 0, 16, H, W, 1) >= 0);
     // bf16 storage with the standard 1 -> 16 -> 16 stem: conv0_0 and conv0_1 as ONE launch of kernels_stem.hip
-    const bool stem = a.kind != UKBB_KIND_FCN && p.bfm == 2 && !k.no_fuse_stem && std0 && override_cfg("conv0_1") < 0;
+    const bool stem = p.bfm == 2 && !k.no_fuse_stem && std0 && override_cfg("conv0_1") < 0;
     // levels 1-4 of the standard filter pyramid go out as ONE launch after level 4 (sqg_multi_kernel)
     const bool merge = !k.side_stream && a.n_level == 5 && a.n_filter[1] == 32 && a.n_filter[2] == 64 && a.n_filter[3] == 128 && a.n_filter[4] == 256;
     int cur = -1, hh = H, ww = W;
@@ -782,7 +786,7 @@ void layout_split_range(const Planner &p, const Knobs &kn) {
 
 int layout_plan(const ukbb_fcn_arch &a, int precision, int H, int W, int n_hint, int cus, PlanLayout &L) {
     L = PlanLayout();
-    Planner p{a, bf16_mode(a.kind, precision), n_hint, cus, L, {}};
+    Planner p{a, plan_bf16_mode(a.kind, precision), n_hint, cus, L, {}};
     std::string why;
     if (!arch_specs(a, p.specs)) { set_error("malformed architecture descriptor"); return UKBB_EARCH; }
     if (!supported(a, why)) { set_error("unsupported architecture: %s", why.c_str()); return UKBB_EARCH; }

@@ -42,13 +42,17 @@ struct Op {                    // one kernel launch of the plan
     const float *wph[4] = {nullptr, nullptr, nullptr, nullptr};   // OP_TCONV3D: packed weights of the 4 sub-pixel phases
 };
 
-struct ActSpec { std::string name; size_t per_image; int channels; };   // per_image: elements per image; channels 0: not a channel map
+struct ActSpec { std::string name; size_t per_image; int channels; int esz = 4; };   // per_image: elements per image; channels 0: not a channel map;
+                                                                                       // esz: bytes of a stored element (2: bf16)
+// Bytes the workspace holds per element of a map.  The U-Net kinds allocate every map as floats in either precision (CineUnits::act_frame
+// and the recorded footprints count that); an FCN plan allocates what it stores.
+inline size_t act_alloc_esz(const ukbb_fcn_arch &a, const ActSpec &s) { return a.kind == UKBB_KIND_FCN ? (size_t)s.esz : 4; }
 
 struct PlanLayout {
     std::vector<Op> ops;
     std::vector<ActSpec> acts;
     int feat_buf = -1;                        // UNet-LSTM: activation index of net['conv0_up']
-    bool bfio = false;                        // every activation between layers is stored as bf16
+    bool bfio = false;                        // every activation between layers is stored as bf16 (an FCN plan: the encoder maps; G_l stays fp32)
     int lstm_tile_cols = 0;                   // region shape of the fused gate-conv / cell kernel (kernels_wino24.hip): 32 | 16
     bool lstm_bf_wino = false;                // UKBB_LSTM_BF16_WINOGRAD: fp32 Winograd arithmetic on bf16 storage (A/B form)
     bool lstm_bf_hoist = true;                // false (UKBB_LSTM_BF16_UNHOIST): the bf16 time steps re-multiply x (r06 experiment)

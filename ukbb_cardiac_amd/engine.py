@@ -151,9 +151,10 @@ class Engine:
         _lib.check(rc, 'ukbb_fcn_forward_cine')
 
     def set_precision(self, precision: str):
-        """'fp32' (default), 'bf16' (bf16 MFMA inputs, fp32 accumulate; BASELINE config 5) or 'f32x3' (fp32 results from three
-        bf16 pieces per operand on the dense matrix cores; FCN head so far; include/ukbb_fcn.h UKBB_PREC_F32X3)."""
-        code = {'fp32': 0, 'bf16': 1, 'f32x3': 2}[precision]
+        """'fp32' (default), 'bf16' (bf16 MFMA inputs, fp32 accumulate; BASELINE config 5), 'f32x3' (fp32 results from three
+        bf16 pieces per operand on the dense matrix cores; FCN head so far; include/ukbb_fcn.h UKBB_PREC_F32X3) or 'bf16_store'
+        (FCN models only: bf16 operands and bf16 encoder maps in HBM, squeeze and head in fp32; UKBB_PREC_BF16_STORE)."""
+        code = {'fp32': 0, 'bf16': 1, 'f32x3': 2, 'bf16_store': 3}[precision]
         _lib.check(_lib.lib.ukbb_fcn_set_precision(self._h, code), 'ukbb_fcn_set_precision')
 
     def set_scratch_budget(self, nbytes: int):
@@ -261,7 +262,7 @@ def cine_chunk_windows(arch: ModelArch, precision: str, n_frames: int, height: i
     return int(_lib.lib.ukbb_fcn_cine_chunk_windows(C.byref(a), _PREC[precision], int(n_frames), int(height), int(width), int(time_step), int(budget)))
 
 
-_PLAN_PREC = {'fp32': 0, 'bf16': 1, 'f32x3': 2}
+_PLAN_PREC = {'fp32': 0, 'bf16': 1, 'f32x3': 2, 'bf16_store': 3}
 _OP_FIELDS = ('cfg', 'H', 'W', 'Ho', 'Wo', 'stride', 'in0', 'in1', 'out')
 
 
@@ -269,6 +270,7 @@ def plan_layout(arch: ModelArch, precision: str, n: int, h: int, w: int, cus: in
     """The launch plan the engine builds for batches of ``n`` images of ``h`` x ``w`` on a device of ``cus`` compute units, from
     the host-only planner (no GPU needed): ``{'ops': [dict], 'acts': [dict], 'split': (first, last), 'bfio', 'feat_buf', 'lstm'}``.
     An op's ``macs`` / ``mfma_macs`` / ``issued_macs`` are per image, as ``Engine.kernel_macs()`` etc. report them per batch.
+    A map of the workspace takes ``per_image * bytes_per_element`` bytes per image.
     Raises UkbbFcnError where ``Engine`` would refuse the combination."""
     fn = _lib.lib.ukbb_fcn_debug_plan_layout                     # debugging aid: not part of the public header
     fn.argtypes = [C.POINTER(_lib.ArchStruct)] + [C.c_int] * 5 + [C.c_char_p, C.c_size_t]
@@ -289,7 +291,8 @@ def plan_layout(arch: ModelArch, precision: str, n: int, h: int, w: int, cus: in
             op.update(macs=macs, mfma_macs=mfma, issued_macs=mfma if issued < 0 else issued)
             out['ops'].append(op)
         elif f[0] == 'act':
-            out['acts'].append({'name': '' if f[1] == '-' else f[1], 'per_image': int(f[2]), 'channels': int(f[3])})
+            out['acts'].append({'name': '' if f[1] == '-' else f[1], 'per_image': int(f[2]), 'channels': int(f[3]),
+                                'bytes_per_element': int(f[4]) if len(f) > 4 else 4})       # (a library built before the field existed: floats)
         elif f[0] == 'plan':
             v = list(map(int, f[2:4] + f[5:6] + f[7:8] + f[9:13]))
             out.update(split=(v[0], v[1]), bfio=bool(v[2]), feat_buf=v[3],
