@@ -14,8 +14,9 @@ FCN_sa grades them.  No case is idle, none is the benchmark's batch, and the bat
 
 Tilings 203 and 212 are registered but taken by no recorded plan; the GPU file forces them in a child process (UKBB_CONV_CFG), and
 test_forced_tilings_are_planned_where_they_are_valid replays that plan here.  Tilings 220 and 221, the 2 x 2 (transposed-conv) kernels with bf16
-operands and fp32 storage, are UNREACHABLE: cfg_valid admits a pc-3 tiling only in bf16_mode 1, bf16_mode gives 1 to UKBB_KIND_FCN alone (every other
-kind takes 2, bf16 storage), and the FCN graph has no 2 x 2 layer; no record of any model, precision or knob holds them
+operands and fp32 storage, are UNREACHABLE: cfg_valid admits a ConvFamily::Bf16Operands tiling only in Bf16Mode::Operands, plan_mode gives that mode to
+UKBB_KIND_FCN alone (every other kind takes Bf16Mode::Storage), and the FCN graph has no 2 x 2 layer; forced on every layer (UKBB_CONV_CFG) of every
+model in every precision it accepts they enter no plan, and no record of any model, precision or knob holds them
 (test_tilings_220_and_221_are_unreachable).  They are left as they are.
 
 The bound tells a defect: on the three rough images at 32 x 48, the eleven layers conv1_0 .. conv4_2 each fed by the layer before, a float32 numpy
@@ -191,13 +192,30 @@ def test_forced_tilings_are_planned_where_they_are_valid(monkeypatch):
         assert max(-(-o['Ho'] // 16) * -(-o['Wo'] // 16) for o in conv_ops(n, H, W) if o['cfg'] == L.FORCED_S1) > 1      # more than one workgroup
 
 
-def test_tilings_220_and_221_are_unreachable():
-    from ukbb_cardiac_amd.arch import KIND_FCN, MODELS
-    with open(os.path.join(ROOT, 'ukbb_cardiac_amd', 'csrc', 'plan.cpp')) as f:
-        src = f.read()
-    # a pc-3 tiling only in bf16_mode 1; mode 1 only for FCN handles
-    assert 'if ((c.pc == 3) != (bf16 == 1) || (c.pc == 5 || c.pc == 6) != (bf16 == 2)) return false;' in src
-    assert 'int bf16_mode(int kind, int precision) { return precision != 1 ? 0 : kind != UKBB_KIND_FCN ? 2 : 1; }' in src
+def test_tilings_220_and_221_are_unreachable(monkeypatch):
+    from ukbb_cardiac_amd import _lib, engine
+    from ukbb_cardiac_amd.arch import KIND_FCN, KIND_TEMPORAL_UNET, MODELS
+    # a bf16-operand tiling only in a bf16-operand plan, and such a plan only for FCN handles: forced on every layer of every model in
+    # every precision the model accepts, neither tiling is planned anywhere
+    layers = ['up%d_t' % l for l in range(4)] + ['%s%d_%d' % (p, l, i) for p in ('conv', 'up') for l in range(5)
+                                                     for i in range(max(max(a.n_block) for a in MODELS.values()))]
+    n_plans, refused = 0, set()
+    for forced in (220, 221):
+        monkeypatch.setenv('UKBB_CONV_CFG', ','.join('%s:%d' % (k, forced) for k in layers))      # read at every plan build
+        for name, arch in MODELS.items():
+            for prec in ('fp32', 'bf16', 'f32x3', 'bf16_store'):
+                for n, H, W in ((1, 64, 96), (17, 48, 16)):
+                    try:
+                        ops = engine.plan_layout(arch, prec, n, H, W, L.CUS)['ops']
+                    except _lib.UkbbFcnError:
+                        refused.add((name, prec))
+                        continue
+                    assert forced not in [o['cfg'] for o in ops], (forced, name, prec, n, H, W)
+                    n_plans += 1
+    assert refused == ({(k, 'bf16') for k, a in MODELS.items() if a.kind == KIND_TEMPORAL_UNET} |
+                       {(k, 'bf16_store') for k, a in MODELS.items() if a.kind != KIND_FCN}), refused
+    assert n_plans == 96
+    monkeypatch.delenv('UKBB_CONV_CFG')
     assert L.config_name(220).startswith('convBF16_2x2s1_') and L.config_name(221).startswith('convBF16_2x2s1_')
     # the FCN graph has no 2 x 2 layer: no transposed conv among its launches, nor in any of its plans; the other kinds plan bf16 storage
     for name, arch in MODELS.items():

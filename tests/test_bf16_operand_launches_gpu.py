@@ -1,10 +1,10 @@
-"""Every bf16-operand conv launch of the FCN plans (--precision bf16 on an FCN handle: UKBB_PREC_BF16, plan.cpp bf16_mode == 1), one launch at a time,
+"""Every bf16-operand conv launch of the FCN plans (--precision bf16 on an FCN handle: UKBB_PREC_BF16, plan.cpp plan_mode: Bf16Mode::Operands), one launch at a time,
 against float64 on the engine's OWN stored input.
 
-On an FCN handle UKBB_PREC_BF16 keeps fp32 activations in HBM and takes ConvConfig::pc == 3, the tilings UKBB_BF_CONFIGS 200-221 of kernels_conv.hip:
+On an FCN handle UKBB_PREC_BF16 keeps fp32 activations in HBM and takes ConvFamily::Bf16Operands, the tilings UKBB_BF_CONFIGS 200-221 of kernels_conv.hip:
 the BF && !BFIO branch of conv_mfma_kernel, which exists nowhere else -- every staged float4 through pack_bf16x2 (RNE) into LDS at a halo pixel
 stride of KC / 2 + 4, weights rounded on the host by the bf16 weight packer, one bf16 MFMA per tap and chunk, fp32 NHWC stores.  The other graders
-stop in front of it (tests/test_fp32_launches_gpu.py: fp32 plans; tests/test_bf16_launches_gpu.py: the bf16-STORAGE U-Net, pc 5 / 6), and the tests
+stop in front of it (tests/test_fp32_launches_gpu.py: fp32 plans; tests/test_bf16_launches_gpu.py: the bf16-STORAGE U-Net, ConvFamily::Bf16Store / Bf16StoreWs), and the tests
 that run this mode compare it with itself.  A bf16 x bf16 product is exact in fp32, so one launch differs from float64 on the rounded operands only
 by its fp32 accumulation:
 
@@ -83,7 +83,7 @@ BF_PREFIX = 'convBF16_'
 CASES = [(1, 48, 16), (1, 32, 32), (1, 80, 16), (1, 16, 160), (1, 208, 16), (1, 192, 208), (17, 48, 16), (17, 32, 32), (17, 80, 16), (17, 16, 112), (17, 16, 160),
          (17, 192, 208)]
 
-# the registered pc-3 tilings no recorded plan reaches: forced in one child process
+# the registered ConvFamily::Bf16Operands tilings no recorded plan reaches: forced in one child process
 FORCED_CASES = [(1, 256, 256), (1, 80, 112)]
 FORCED_S1, FORCED_S2 = 203, 212
 

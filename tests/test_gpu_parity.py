@@ -358,7 +358,7 @@ def test_unet_bf16_dice_vs_fp32():
         eng.set_precision('bf16')
         b16 = eng.run(img, want_logits=True)
         names, cfgs = eng.kernel_names(), eng.kernel_configs()
-        # every conv / transposed conv on the bf16-storage tilings (ConvConfig::pc == 5, ids 230-299 and 320-325; pc == 6, the
+        # every conv / transposed conv on the bf16-storage tilings (ConvFamily::Bf16Store, ids 230-299 and 320-325; Bf16StoreWs, the
         # weight-stationary ids 400-), the stem and the tail as the fused launches of kernels_stem.hip / kernels_tail.hip (no tiling
         # id): nothing left in fp32.  20 launches: conv0_0 + conv0_1, 17 convs / transposed convs, up0_0 + up0_1 + logits
         assert names[0] == 'conv0_0+conv0_1' and names[-1] == 'up0_0+up0_1+logits' and cfgs[0] == -1 and cfgs[-1] == -1

@@ -28,15 +28,6 @@ namespace {
 
 thread_local std::string g_err;
 
-void set_err(const char *fmt, ...) {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-}
-
 }  // namespace
 
 void ukbb::set_error(const char *fmt, ...) {
@@ -54,13 +45,12 @@ namespace {
     do {                                                                               \
         hipError_t e_ = (expr);                                                        \
         if (e_ != hipSuccess) {                                                        \
-            set_err("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+            set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
             return code;                                                               \
         }                                                                              \
     } while (0)
 
 constexpr float BN_EPS = 1e-3f;   // tf.layers.batch_normalization default
-const char *const BF16_STORE_FCN_ONLY = "UKBB_PREC_BF16_STORE is the FCN's bf16-storage mode; the U-Net kinds already store bf16 under UKBB_PREC_BF16";
 
 struct HostLayer {            // one conv(+BN) unit with BN folded (fp32, same op order as
     std::string name;         // ukbb_cardiac_amd/weights.py fold_bn)
@@ -145,15 +135,14 @@ struct ukbb_fcn_handle {
     DevBuf io_image, io_logits, io_prob, io_pred;   // staging for forward_host
 
     // plan
-    int precision = 0;                        // 0: fp32; 1: bf16 operands for the MFMA convs (fp32 accumulate); 2: fp32 from bf16 pieces (head);
-                                              // 3: FCN with bf16 encoder maps in HBM (UKBB_PREC_BF16_STORE)
+    int precision = UKBB_PREC_FP32;           // the code the next plan is built for (ukbb_fcn_set_precision)
+    PlanMode mode;                            // what the CURRENT plan's code means for this architecture (plan.h plan_mode)
     int plan_h = 0, plan_w = 0, cap_n = 0;
     bool plan_small = false;                  // plan built with the small-batch tilings
     int plan_n = 0;                           // ... for this largest batch
     int max_n = 0;                            // largest batch this handle was asked for (reserve / forward): the small-batch plan is
                                               // used only while that stays <= SMALL_BATCH, so a large-batch caller's tail batches do
                                               // not flip the plan (a rebuild re-allocates the workspace) back and forth
-    bool plan_bfio = false;                   // plan stores every activation between layers as bf16 (UKBB_PREC_BF16, U-Net; UKBB_PREC_BF16_STORE, FCN encoder)
     std::vector<Op> ops;
     CineUnits cine;                           // what forward_cine holds per frame / window of this plan (plan.h)
     int last_n = 0;
@@ -231,27 +220,33 @@ int upload(ukbb_fcn_handle *h, const std::string &key, const std::vector<float> 
 int ensure_packed(ukbb_fcn_handle *h, int layer, const ConvConfig &c, const float **wpk) {
     const HostLayer &L = h->layers[layer];
     char key[128];
-    const bool bfpk = c.pc == 3 || c.pc == 5 || c.pc == 6;
-    const int coutp = (c.pc == 5 || c.pc == 6) ? round_up(L.cout, 32) : L.cout;
-    const bool w24 = is_wino24(c);
-    snprintf(key, sizeof key, "%s/pk%s_mb%d_kc%d_g%d", L.name.c_str(), bfpk ? "bf16" : w24 ? "wino24" : c.pc == 4 ? "wino" : c.pc == 7 ? "winofirst" : "",
-             c.mb, c.kc, c.wm * c.cb);
-    if (!dev_ptr(h, key)) {
-        std::vector<float> pk(w24 ? (size_t)24 * L.cin * L.cout : (c.pc == 4 || c.pc == 7) ? (size_t)16 * L.cin * L.cout : (size_t)L.ks * L.ks * L.cin * coutp);
-        if (c.pc == 7) {
-            if (L.ks != 3 || L.cin != 16 || L.cout != 16) { set_err("layer %s: the Winograd first-layer tiling needs a 16 -> 16 3x3 conv", L.name.c_str()); return UKBB_EARCH; }
-            pack_wino_first_weights(L.w.data(), pk.data());
-        }
-        else if (w24) pack_wino24_weights(L.w.data(), L.cin, L.cout, c.wm, pk.data());
-        else if (c.pc == 4) pack_wino_weights(L.w.data(), L.cin, L.cout, c.wm, pk.data());
-        else if (bfpk && coutp != L.cout) {           // zero rows up to the MFMA's 32
-            std::vector<float> wp((size_t)L.ks * L.ks * L.cin * coutp, 0.f);
-            for (size_t r = 0; r < (size_t)L.ks * L.ks * L.cin; ++r)
-                std::copy(L.w.begin() + r * L.cout, L.w.begin() + (r + 1) * L.cout, wp.begin() + r * coutp);
-            pack_conv_weights_bf16(wp.data(), L.ks, L.cin, coutp, c.wm * c.cb, pk.data());
-        }
-        else if (bfpk) pack_conv_weights_bf16(L.w.data(), L.ks, L.cin, L.cout, c.wm * c.cb, pk.data());
-        else pack_conv_weights(L.w.data(), L.ks, L.cin, L.cout, c.mb, c.kc, c.wm * c.cb, pk.data());
+    const int coutp = packed_cout(c, L.cout);
+    const size_t rows = (size_t)L.ks * L.ks * L.cin;
+    std::vector<float> pk;
+    auto fresh = [&](const char *suffix, size_t floats) {     // names the buffer of this packing; true, with pk sized, if it is not on the device yet
+        snprintf(key, sizeof key, "%s/pk%s_mb%d_kc%d_g%d", L.name.c_str(), suffix, c.mb, c.kc, c.wm * c.cb);
+        if (!dev_ptr(h, key)) pk.resize(floats);
+        return !pk.empty();
+    };
+    switch (c.family) {
+        case ConvFamily::Direct: case ConvFamily::ProdCons: case ConvFamily::ProdConsFirst:
+            if (fresh("", rows * coutp)) pack_conv_weights(L.w.data(), L.ks, L.cin, L.cout, c.mb, c.kc, c.wm * c.cb, pk.data());
+            break;
+        case ConvFamily::Bf16Operands: case ConvFamily::Bf16Store: case ConvFamily::Bf16StoreWs:
+            if (fresh("bf16", rows * coutp)) {
+                std::vector<float> wp(rows * coutp, 0.f);         // zero rows up to the MFMA's 32 where coutp > cout
+                for (size_t r = 0; r < rows; ++r) std::copy(L.w.begin() + r * L.cout, L.w.begin() + (r + 1) * L.cout, wp.begin() + r * coutp);
+                pack_conv_weights_bf16(wp.data(), L.ks, L.cin, coutp, c.wm * c.cb, pk.data());
+            }
+            break;
+        case ConvFamily::Wino22: if (fresh("wino", (size_t)16 * L.cin * L.cout)) pack_wino_weights(L.w.data(), L.cin, L.cout, c.wm, pk.data()); break;
+        case ConvFamily::Wino24: if (fresh("wino24", (size_t)24 * L.cin * L.cout)) pack_wino24_weights(L.w.data(), L.cin, L.cout, c.wm, pk.data()); break;
+        case ConvFamily::FirstWino22:
+            if (L.ks != 3 || L.cin != 16 || L.cout != 16) { set_error("layer %s: the Winograd first-layer tiling needs a 16 -> 16 3x3 conv", L.name.c_str()); return UKBB_EARCH; }
+            if (fresh("winofirst", (size_t)16 * L.cin * L.cout)) pack_wino_first_weights(L.w.data(), pk.data());
+            break;
+    }
+    if (!pk.empty()) {
         int rc = upload(h, key, pk);
         if (rc) return rc;
     }
@@ -269,8 +264,8 @@ int ensure_packed(ukbb_fcn_handle *h, int layer, const ConvConfig &c, const floa
 int ensure_packed_tconv(ukbb_fcn_handle *h, int layer, const ConvConfig &c, const float **wpk, const float **bias) {
     const HostLayer &L = h->layers[layer];
     char key[128];
-    const bool bfpk = c.pc == 3 || c.pc == 5 || c.pc == 6;
-    const bool paired = c.pc == 6;                    // weight-stationary tilings: virtual channels in the paired block order (wst_pack_order)
+    const bool bfpk = packs_bf16(c);
+    const bool paired = c.family == ConvFamily::Bf16StoreWs;   // weight-stationary tilings: virtual channels in the paired block order (wst_pack_order)
     snprintf(key, sizeof key, "%s/pk2x2%s%s_mb%d_kc%d_g%d", L.name.c_str(), bfpk ? "bf16" : "", paired ? "ws" : "", c.mb, c.kc, c.wm * c.cb);
     const std::string bkey = L.name + (paired ? "/bias4ws" : "/bias4");
     if (!dev_ptr(h, key)) {
@@ -354,7 +349,7 @@ int ensure_packed_lstm(ukbb_fcn_handle *h) {
     int d = 0;
     for (const char *nm2 : {"lstm_fw", "lstm_bw"}) {
         const HostLayer &L = h->layers[h->layer_index.at(nm2)];
-        if (L.cin != 32 || L.cout != 64 || L.ks != 3) { set_err("ConvLSTM gate kernel must be 3x3x(16+16)x64"); return UKBB_EARCH; }
+        if (L.cin != 32 || L.cout != 64 || L.ks != 3) { set_error("ConvLSTM gate kernel must be 3x3x(16+16)x64"); return UKBB_EARCH; }
         pack_lstm_gate_weights(L.w.data(), L.cin, 0, L.b.data(), wx.data() + d * per, bx.data() + d * 64);
         pack_lstm_gate_weights(L.w.data(), L.cin, a.n_filter[0], nullptr, wh.data(), nullptr);
         int rc = upload(h, std::string(nm2) + "/wh", wh);
@@ -409,7 +404,7 @@ int materialize_plan(ukbb_fcn_handle *h, PlanLayout &L) {
             case OP_CONV:
                 find_cfg(op.cfg, c);
                 rc = ensure_packed(h, op.layer, c, &op.wpk);
-                op.bias = ((c.pc == 5 || c.pc == 6) && h->layers[op.layer].cout % 32) ? dev_ptr(h, lname + "/bias_pad") : dev_ptr(h, lname + "/bias");
+                op.bias = dev_ptr(h, lname + (packed_cout(c, h->layers[op.layer].cout) != h->layers[op.layer].cout ? "/bias_pad" : "/bias"));
                 break;
             case OP_TCONV:
                 find_cfg(op.cfg, c);
@@ -445,7 +440,7 @@ int materialize_plan(ukbb_fcn_handle *h, PlanLayout &L) {
     }
     h->ops = std::move(L.ops);
     h->feat_buf = L.feat_buf;
-    h->plan_bfio = L.bfio;
+    h->mode = L.mode;
     h->split_first = L.split_first; h->split_last = L.split_last;
     h->debug_first_op = L.debug_first_op; h->debug_last_op = L.debug_last_op;
     for (auto e : h->ev) (void)hipEventDestroy(e);
@@ -477,11 +472,11 @@ int ensure_capacity(ukbb_fcn_handle *h, int n) {
 
 int check_shape(int n, int H, int W) {
     if (n < 1 || H < 16 || W < 16 || (H % 16) || (W % 16)) {
-        set_err("invalid batch shape n=%d h=%d w=%d: h and w must be positive multiples of 16 "
+        set_error("invalid batch shape n=%d h=%d w=%d: h and w must be positive multiples of 16 "
                 "(the reference pads to that, common/deploy_network.py:97)", n, H, W);
         return UKBB_EINVAL;
     }
-    if ((long long)n * H * W > (1ll << 31) - 1) { set_err("batch too large for 32-bit pixel indexing"); return UKBB_EINVAL; }
+    if ((long long)n * H * W > (1ll << 31) - 1) { set_error("batch too large for 32-bit pixel indexing"); return UKBB_EINVAL; }
     return UKBB_OK;
 }
 
@@ -546,7 +541,7 @@ int run_plan(ukbb_fcn_handle *h, const float *image, int n, float *logits, float
             case OP_FIRST: {
                 const HostLayer &L = h->layers[op.layer];
                 FirstArgs fa{image, dev_ptr(h, L.name + "/w"), dev_ptr(h, L.name + "/bias"), actp(op.out),
-                             n, op.H, op.W, L.cout, h->plan_bfio ? 1 : 0};
+                             n, op.H, op.W, L.cout, h->mode.bfio() ? 1 : 0};
                 e = launch_first(fa, s);
                 break;
             }
@@ -562,7 +557,7 @@ int run_plan(ukbb_fcn_handle *h, const float *image, int n, float *logits, float
                 ca.C0 = L.cin - ca.C1;
                 ca.wpk = op.wpk; ca.bias = op.bias; ca.out = actp(op.out);
                 ca.N = n; ca.H = op.H; ca.W = op.W; ca.Ho = op.Ho; ca.Wo = op.Wo; ca.Cout = L.cout;
-                if (c.pc == 5 || c.pc == 6) { ca.Cout = round_up(L.cout, 32); ca.cout_store = L.cout; }
+                if (stores_bf16(c)) { ca.Cout = packed_cout(c, L.cout); ca.cout_store = L.cout; }
                 if (op.fused_logits) {
                     ca.lg_w = dev_ptr(h, "logits/w"); ca.lg_b = dev_ptr(h, "logits/bias");
                     ca.lg_logits = logits; ca.lg_prob = prob; ca.lg_pred = pred; ca.lg_ncls = a.n_class;
@@ -582,7 +577,7 @@ int run_plan(ukbb_fcn_handle *h, const float *image, int n, float *logits, float
                 sa.w_g = dev_ptr(h, "sqg" + ls + "/w_g");
                 sa.out = actp(op.out);
                 sa.npix = (long long)n * op.H * op.W; sa.cin = L.cin;
-                sa.x_bf16 = h->plan_bfio ? 1 : 0; sa.hw = op.H * op.W;
+                sa.x_bf16 = h->mode.bfio() ? 1 : 0; sa.hw = op.H * op.W;
                 e = launch_sqg(sa, s);
                 break;
             }
@@ -591,7 +586,7 @@ int run_plan(ukbb_fcn_handle *h, const float *image, int n, float *logits, float
                 for (int j = 0; j < 4; ++j) {
                     sa[j] = SqgArgs{};
                     sa[j].cin = 32 << j;
-                    sa[j].x_bf16 = h->plan_bfio ? 1 : 0;         // one input format per launch
+                    sa[j].x_bf16 = h->mode.bfio() ? 1 : 0;         // one input format per launch
                     if (op.mlayer[j] < 0) continue;              // level handled by a launch of its own: npix = 0 -> no blocks
                     const HostLayer &L = h->layers[op.mlayer[j]];
                     const std::string ls = std::to_string(j + 1);
@@ -616,8 +611,8 @@ int run_plan(ukbb_fcn_handle *h, const float *image, int n, float *logits, float
                 ha.w_lg = dev_ptr(h, "head/w_lg"); ha.b_lg = dev_ptr(h, "logits/bias");
                 ha.logits = logits; ha.prob = prob; ha.pred = pred;
                 ha.N = n; ha.H = op.H; ha.W = op.W; ha.n_class = a.n_class;
-                ha.x3 = h->precision == UKBB_PREC_F32X3;
-                ha.conv0_bf16 = h->plan_bfio ? 1 : 0;
+                ha.x3 = h->mode.head_x3;
+                ha.conv0_bf16 = h->mode.bfio() ? 1 : 0;
                 e = launch_head(ha, s);
                 break;
             }
@@ -660,7 +655,7 @@ int run_plan(ukbb_fcn_handle *h, const float *image, int n, float *logits, float
                 la.in = actp(op.in0); la.w = dev_ptr(h, "logits/w"); la.bias = dev_ptr(h, "logits/bias");
                 la.logits = logits; la.prob = prob; la.pred = pred;
                 la.npix = (int64_t)n * op.H * op.W; la.C = L.cin; la.n_class = a.n_class;
-                la.in_bf16 = h->plan_bfio ? 1 : 0;
+                la.in_bf16 = h->mode.bfio() ? 1 : 0;
                 e = launch_logits(la, s);
                 break;
             }
@@ -695,7 +690,7 @@ int run_plan(ukbb_fcn_handle *h, const float *image, int n, float *logits, float
                 break;
             }
             default:
-                set_err("op kind %d not implemented", (int)op.kind);
+                set_error("op kind %d not implemented", (int)op.kind);
                 return UKBB_EARCH;
         }
         return UKBB_OK;
@@ -729,7 +724,7 @@ int run_plan(ukbb_fcn_handle *h, const float *image, int n, float *logits, float
                 if (rc) return rc;
                 if (e == hipSuccess) rc = launch_one(j, nA, n - nA, h->side2, e);
                 if (rc) return rc;
-                if (e != hipSuccess) { set_err("launch of %s (split) failed: %s", h->ops[j].name.c_str(), hipGetErrorString(e)); return UKBB_EDEVICE; }
+                if (e != hipSuccess) { set_error("launch of %s (split) failed: %s", h->ops[j].name.c_str(), hipGetErrorString(e)); return UKBB_EDEVICE; }
             }
             HIP_TRY(hipEventRecord(h->ev_split_join, h->side2), UKBB_EDEVICE);
             HIP_TRY(hipStreamWaitEvent(s_main, h->ev_split_join, 0), UKBB_EDEVICE);
@@ -761,7 +756,7 @@ int run_plan(ukbb_fcn_handle *h, const float *image, int n, float *logits, float
             const int rc = launch_one(i, 0, n, s, e);
             if (rc) return rc;
         }
-        if (e != hipSuccess) { set_err("launch of %s failed: %s", op.name.c_str(), hipGetErrorString(e)); return UKBB_EDEVICE; }
+        if (e != hipSuccess) { set_error("launch of %s failed: %s", op.name.c_str(), hipGetErrorString(e)); return UKBB_EDEVICE; }
         if (fence_on) (void)ukbb_fcn_debug_fence_kernel(s);                  // debugging aid: an explicit system-scope fence launch behind every op
         if (sync_on) (void)hipStreamSynchronize(s);                           // debugging aid: the host waits for every op before it enqueues the next
         if (timed) HIP_TRY(hipEventRecord(h->ev[2 * i + 1], s), UKBB_EDEVICE);
@@ -783,8 +778,8 @@ void guard_bufs(ukbb_fcn_handle *h, std::vector<std::pair<std::string, DevBuf *>
 }
 
 int guard_checks(ukbb_fcn_handle *h, const char *what) {
-    if (!h) { set_err("%s: NULL handle", what); return UKBB_EINVAL; }
-    if (!h->guard.on) { set_err("%s: the handle was not created under UKBB_DEBUG_GUARD", what); return UKBB_EINVAL; }
+    if (!h) { set_error("%s: NULL handle", what); return UKBB_EINVAL; }
+    if (!h->guard.on) { set_error("%s: the handle was not created under UKBB_DEBUG_GUARD", what); return UKBB_EINVAL; }
     HIP_TRY(hipSetDevice(h->device), UKBB_EDEVICE);
     HIP_TRY(hipDeviceSynchronize(), UKBB_EDEVICE);
     return UKBB_OK;
@@ -836,13 +831,13 @@ int ukbb_fcn_debug_check_guards(ukbb_fcn_handle *h, char *report, size_t cap) {
         bad += hit;
     }
     if (report && cap) { const size_t m = std::min(out.size(), cap - 1); memcpy(report, out.data(), m); report[m] = 0; }
-    set_err("%s", out.c_str());
+    set_error("%s", out.c_str());
     return bad;
 }
 
 // The number of guarded buffers the handle holds right now; their payload bytes and the bytes of their guards.
 int ukbb_fcn_debug_guard_info(ukbb_fcn_handle *h, uint64_t *payload_bytes, uint64_t *guard_bytes) {
-    if (!h) { set_err("debug_guard_info: NULL handle"); return UKBB_EINVAL; }
+    if (!h) { set_error("debug_guard_info: NULL handle"); return UKBB_EINVAL; }
     std::vector<std::pair<std::string, DevBuf *>> bufs;
     guard_bufs(h, bufs);
     int nb = 0;
@@ -879,23 +874,23 @@ int ukbb_fcn_debug_poison(ukbb_fcn_handle *h, uint32_t pattern) {
 int ukbb_fcn_debug_damage_guard(ukbb_fcn_handle *h, const char *buffer, long long offset) {
     int rc = guard_checks(h, "debug_damage_guard");
     if (rc) return rc;
-    if (!buffer) { set_err("debug_damage_guard: NULL buffer name"); return UKBB_EINVAL; }
+    if (!buffer) { set_error("debug_damage_guard: NULL buffer name"); return UKBB_EINVAL; }
     std::vector<std::pair<std::string, DevBuf *>> bufs;
     guard_bufs(h, bufs);
     for (auto &kv : bufs) {
         if (kv.first != buffer) continue;
         const DevBuf *b = kv.second;
         const long long bytes = (long long)(b->n * sizeof(float)), G = (long long)GUARD_BYTES;
-        if (!b->p) { set_err("debug_damage_guard: buffer '%s' is not allocated", buffer); return UKBB_EINVAL; }
+        if (!b->p) { set_error("debug_damage_guard: buffer '%s' is not allocated", buffer); return UKBB_EINVAL; }
         if (!((offset >= -G && offset < 0) || (offset >= bytes && offset < bytes + G))) {
-            set_err("debug_damage_guard: offset %lld is in no guard of '%s' (payload %lld bytes, guards %lld)", offset, buffer, bytes, G);
+            set_error("debug_damage_guard: offset %lld is in no guard of '%s' (payload %lld bytes, guards %lld)", offset, buffer, bytes, G);
             return UKBB_EINVAL;
         }
         const unsigned char v = (unsigned char)~GUARD_BYTE;
         HIP_TRY(hipMemcpy(reinterpret_cast<char *>(b->p) + offset, &v, 1, hipMemcpyHostToDevice), UKBB_EDEVICE);
         return UKBB_OK;
     }
-    set_err("debug_damage_guard: no buffer named '%s'", buffer);
+    set_error("debug_damage_guard: no buffer named '%s'", buffer);
     return UKBB_EINVAL;
 }
 
@@ -904,14 +899,13 @@ int ukbb_fcn_debug_damage_guard(ukbb_fcn_handle *h, const char *buffer, long lon
 // Returns the text's length (it is truncated when cap is smaller), or the negative code create / set_precision / reserve would give.
 int ukbb_fcn_debug_plan_layout(const ukbb_fcn_arch *arch, int precision, int n, int H, int W, int cus, char *buf, size_t cap) {
     static const char *const kinds[] = {"first", "conv", "head", "tconv", "logits", "sqg", "sqg_multi", "tail", "stem", "first3d", "conv3d", "tconv3d"};
-    if (!arch || (!buf && cap) || cus < 1) { set_err("debug_plan_layout: bad argument"); return UKBB_EINVAL; }
-    if (precision != UKBB_PREC_FP32 && precision != UKBB_PREC_BF16 && precision != UKBB_PREC_F32X3 && precision != UKBB_PREC_BF16_STORE) { set_err("debug_plan_layout: bad precision"); return UKBB_EINVAL; }
+    if (!arch || (!buf && cap) || cus < 1) { set_error("debug_plan_layout: bad argument"); return UKBB_EINVAL; }
+    PlanLayout L;
+    const char *why;
+    if (plan_mode(*arch, precision, L.mode, &why) == UKBB_EINVAL) { set_error("debug_plan_layout: bad precision"); return UKBB_EINVAL; }
     int rc = check_shape(n, H, W);
     if (rc) return rc;
-    if (arch->kind == UKBB_KIND_TEMPORAL_UNET && precision == UKBB_PREC_BF16) { set_err("the Temporal-UNet's 3-D convolutions are built for fp32 only (no bf16 plan)"); return UKBB_EARCH; }
-    if (arch->kind != UKBB_KIND_FCN && precision == UKBB_PREC_BF16_STORE) { set_err("%s", BF16_STORE_FCN_ONLY); return UKBB_EARCH; }
-    PlanLayout L;
-    rc = layout_plan(*arch, precision, H, W, n, cus, L);
+    rc = layout_plan(*arch, precision, H, W, n, cus, L);      // refuses the (kind, precision) pairs plan_mode refuses
     if (rc) return rc;
     std::string out;
     char line[512];
@@ -925,7 +919,7 @@ int ukbb_fcn_debug_plan_layout(const ukbb_fcn_arch *arch, int precision, int n, 
         snprintf(line, sizeof line, "act %s %zu %d %zu\n", s.name.empty() ? "-" : s.name.c_str(), s.per_image, s.channels, act_alloc_esz(*arch, s));
         out += line;
     }
-    snprintf(line, sizeof line, "plan split %d %d bfio %d feat_buf %d lstm %d %d %d %d\n", L.split_first, L.split_last, (int)L.bfio, L.feat_buf,
+    snprintf(line, sizeof line, "plan split %d %d bfio %d feat_buf %d lstm %d %d %d %d\n", L.split_first, L.split_last, (int)L.mode.bfio(), L.feat_buf,
              (int)L.needs_lstm, L.lstm_tile_cols, (int)L.lstm_bf_wino, (int)L.lstm_bf_hoist);
     out += line;
     if (cap) { const size_t m = std::min(out.size(), cap - 1); memcpy(buf, out.data(), m); buf[m] = 0; }
@@ -944,28 +938,28 @@ size_t ukbb_fcn_weight_count(const ukbb_fcn_arch *arch) {
 }
 
 ukbb_fcn_handle *ukbb_fcn_create(const ukbb_fcn_arch *arch, const float *weights, size_t n_floats, int device) {
-    if (!arch || !weights) { set_err("create: NULL argument"); return nullptr; }
+    if (!arch || !weights) { set_error("create: NULL argument"); return nullptr; }
     std::vector<Spec> specs;
-    if (!arch_specs(*arch, specs)) { set_err("create: malformed architecture descriptor"); return nullptr; }
+    if (!arch_specs(*arch, specs)) { set_error("create: malformed architecture descriptor"); return nullptr; }
     std::string why;
-    if (!supported(*arch, why)) { set_err("create: unsupported architecture: %s", why.c_str()); return nullptr; }
+    if (!supported(*arch, why)) { set_error("create: unsupported architecture: %s", why.c_str()); return nullptr; }
     size_t want = 0;
     for (auto &s : specs) want += spec_floats(s);
-    if (want != n_floats) { set_err("create: expected %zu weight floats, got %zu", want, n_floats); return nullptr; }
+    if (want != n_floats) { set_error("create: expected %zu weight floats, got %zu", want, n_floats); return nullptr; }
 
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-        set_err("create: no HIP device visible (this library has no CPU fallback)");
+        set_error("create: no HIP device visible (this library has no CPU fallback)");
         return nullptr;
     }
-    if (device < 0 || device >= ndev) { set_err("create: device %d out of range (0..%d)", device, ndev - 1); return nullptr; }
+    if (device < 0 || device >= ndev) { set_error("create: device %d out of range (0..%d)", device, ndev - 1); return nullptr; }
     hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) { set_err("create: hipGetDeviceProperties failed"); return nullptr; }
+    if (hipGetDeviceProperties(&prop, device) != hipSuccess) { set_error("create: hipGetDeviceProperties failed"); return nullptr; }
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-        set_err("create: device %d is %s; kernels are built for gfx950 (MI355X) only", device, prop.gcnArchName);
+        set_error("create: device %d is %s; kernels are built for gfx950 (MI355X) only", device, prop.gcnArchName);
         return nullptr;
     }
-    if (hipSetDevice(device) != hipSuccess) { set_err("create: hipSetDevice failed"); return nullptr; }
+    if (hipSetDevice(device) != hipSuccess) { set_error("create: hipSetDevice failed"); return nullptr; }
 
     std::unique_ptr<ukbb_fcn_handle> h(new ukbb_fcn_handle);
     h->arch = *arch;
@@ -1063,15 +1057,15 @@ void ukbb_fcn_destroy(ukbb_fcn_handle *h) {
 }
 
 int ukbb_fcn_reserve(ukbb_fcn_handle *h, int n, int height, int width) {
-    if (!h) { set_err("reserve: NULL handle"); return UKBB_EINVAL; }
+    if (!h) { set_error("reserve: NULL handle"); return UKBB_EINVAL; }
     return prepare(h, n, height, width);
 }
 
 int ukbb_fcn_forward(ukbb_fcn_handle *h, const float *image, int n, int height, int width,
                      float *logits, float *prob, int32_t *pred, void *stream) {
-    if (!h || !image) { set_err("forward: NULL argument"); return UKBB_EINVAL; }
-    if (h->arch.kind == UKBB_KIND_UNET_LSTM) { set_err("forward: UNet-LSTM models take sequences: use ukbb_fcn_forward_seq / ukbb_fcn_forward_cine"); return UKBB_EINVAL; }
-    if (h->arch.kind == UKBB_KIND_TEMPORAL_UNET) { set_err("forward: Temporal-UNet models take sequences: use ukbb_fcn_forward_seq / ukbb_fcn_forward_cine"); return UKBB_EINVAL; }
+    if (!h || !image) { set_error("forward: NULL argument"); return UKBB_EINVAL; }
+    if (h->arch.kind == UKBB_KIND_UNET_LSTM) { set_error("forward: UNet-LSTM models take sequences: use ukbb_fcn_forward_seq / ukbb_fcn_forward_cine"); return UKBB_EINVAL; }
+    if (h->arch.kind == UKBB_KIND_TEMPORAL_UNET) { set_error("forward: Temporal-UNet models take sequences: use ukbb_fcn_forward_seq / ukbb_fcn_forward_cine"); return UKBB_EINVAL; }
     int rc = prepare(h, n, height, width);
     if (rc) return rc;
     return run_plan(h, image, n, logits, prob, pred, static_cast<hipStream_t>(stream));
@@ -1079,9 +1073,9 @@ int ukbb_fcn_forward(ukbb_fcn_handle *h, const float *image, int n, int height, 
 
 int ukbb_fcn_forward_host(ukbb_fcn_handle *h, const float *image, int n, int height, int width,
                           float *logits, float *prob, int32_t *pred) {
-    if (!h || !image) { set_err("forward_host: NULL argument"); return UKBB_EINVAL; }
-    if (h->arch.kind == UKBB_KIND_UNET_LSTM) { set_err("forward_host: UNet-LSTM models take sequences: use ukbb_fcn_forward_seq / ukbb_fcn_forward_cine"); return UKBB_EINVAL; }
-    if (h->arch.kind == UKBB_KIND_TEMPORAL_UNET) { set_err("forward_host: Temporal-UNet models take sequences: use ukbb_fcn_forward_seq / ukbb_fcn_forward_cine"); return UKBB_EINVAL; }
+    if (!h || !image) { set_error("forward_host: NULL argument"); return UKBB_EINVAL; }
+    if (h->arch.kind == UKBB_KIND_UNET_LSTM) { set_error("forward_host: UNet-LSTM models take sequences: use ukbb_fcn_forward_seq / ukbb_fcn_forward_cine"); return UKBB_EINVAL; }
+    if (h->arch.kind == UKBB_KIND_TEMPORAL_UNET) { set_error("forward_host: Temporal-UNet models take sequences: use ukbb_fcn_forward_seq / ukbb_fcn_forward_cine"); return UKBB_EINVAL; }
     int rc = prepare(h, n, height, width);
     if (rc) return rc;
     const size_t npix = (size_t)n * height * width, ncls = h->arch.n_class;
@@ -1109,9 +1103,9 @@ bool cine_query_units(const ukbb_fcn_arch *arch, int precision, int F, int H, in
     if (!arch || !ukbb_fcn_weight_count(arch)) return false;
     if (arch->kind != UKBB_KIND_UNET_LSTM && arch->kind != UKBB_KIND_TEMPORAL_UNET) return false;
     if (precision != UKBB_PREC_FP32 && precision != UKBB_PREC_BF16) return false;
-    if (arch->kind == UKBB_KIND_TEMPORAL_UNET && precision != UKBB_PREC_FP32) return false;
-    if (!cine_request_ok(arch->fc, F, H, W, time_step)) return false;
     PlanLayout L;
+    const char *why;
+    if (plan_mode(*arch, precision, L.mode, &why) || !cine_request_ok(arch->fc, F, H, W, time_step)) return false;
     if (layout_plan(*arch, precision, H, W, F, 256, L)) return false;
     u = cine_units_from(L, *arch, H, W);
     return true;
@@ -1172,7 +1166,7 @@ int ukbb_fcn_cine_chunk_windows(const ukbb_fcn_arch *arch, int precision, int n_
 }
 
 int ukbb_fcn_set_scratch_budget(ukbb_fcn_handle *h, uint64_t bytes) {
-    if (!h) { set_err("set_scratch_budget: NULL handle"); return UKBB_EINVAL; }
+    if (!h) { set_error("set_scratch_budget: NULL handle"); return UKBB_EINVAL; }
     if (h->arch.kind != UKBB_KIND_UNET_LSTM && h->arch.kind != UKBB_KIND_TEMPORAL_UNET) return UKBB_OK;      // no cine scratch: accepted, ignored
     if (bytes == h->scratch_budget) return UKBB_OK;
     h->scratch_budget = bytes;
@@ -1200,12 +1194,12 @@ int run_bilstm(ukbb_fcn_handle *h, const float *feat, int NF, const int *d_map, 
     const int T = a.fc, NHID = a.same_dim, tc = h->lstm_tile_cols;
     const size_t HW = (size_t)H * W;
     // bf16 plan: the direct-conv bf16 form (kernels_ws.hip) unless UKBB_LSTM_BF16_WINOGRAD=1 asks for the fp32 Winograd arithmetic on bf16 storage (A/B)
-    const bool wsf = h->plan_bfio && !h->lstm_bf_wino;
+    const bool wsf = h->mode.bfio() && !h->lstm_bf_wino;
     // r06 experiment (UKBB_LSTM_BF16_UNHOIST=1): the direct-conv bf16 steps read the feature frame (32 bytes per pixel) and multiply it again
     // instead of reading gx (128 bytes per pixel); no gx buffer exists in that form.  Slower by 5 % per step (plan.cpp, read_knobs), so not the default.
     const bool unhoist = wsf && !h->lstm_bf_hoist;
     const size_t gxf = wsf ? lstm_ws_gx_elems(H, W) : wino24_lstm_gx_floats(H, W, tc), cf = wsf ? lstm_ws_c_floats(H, W) : wino24_lstm_c_floats(H, W, tc);
-    const bool bf = h->plan_bfio;                        // bf16 plan: features, gx and hidden maps are bf16 in HBM
+    const bool bf = h->mode.bfio();                        // bf16 plan: features, gx and hidden maps are bf16 in HBM
     const size_t esz = bf ? 2 : 4;
     // Scratch of one cine (include/ukbb_fcn.h, forward_cine): gx 2 NF gxf + h1 2 NF HW NHID + hall 2 T Wn HW NHID elements of esz bytes,
     // cell state (2 NF + Wn) cf floats.  DevBuf counts 4-byte units: the bf16 maps take half as many.
@@ -1231,7 +1225,7 @@ int run_bilstm(ukbb_fcn_handle *h, const float *feat, int NF, const int *d_map, 
         ca.ls_mode = 1; ca.ls_gx = unhoist ? nullptr : h->lstm_gx.p; ca.ls_c_out = h->lstm_c1.p; ca.out = h->lstm_h1.p;
         ca.ls_gx_dir = (long long)NF * gxf; ca.ls_c_dir = (long long)NF * cf; ca.ls_h_dir = (long long)NF * HW * NHID;
         hipError_t e = wsf ? launch_lstm_ws(ca, s) : launch_wino24_lstm(ca, tc, s);
-        if (e != hipSuccess) { set_err("ConvLSTM x-pass launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
+        if (e != hipSuccess) { set_error("ConvLSTM x-pass launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
     }
     const size_t kst = (size_t)Wn * HW * NHID;           // one step's hidden maps
     // A zero backward cell (the single-direction head served through the bidirectional layer set): from the zero state i = o = 1/2, j = tanh(0) = 0,
@@ -1265,7 +1259,7 @@ int run_bilstm(ukbb_fcn_handle *h, const float *feat, int NF, const int *d_map, 
             ca.ls_c_out = h->lstm_c.p;
             ca.out = at(hall, (size_t)k * kst);
             hipError_t e = wsf ? launch_lstm_ws(ca, s) : launch_wino24_lstm(ca, tc, s);
-            if (e != hipSuccess) { set_err("ConvLSTM step launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
+            if (e != hipSuccess) { set_error("ConvLSTM step launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
         }
     }
     return UKBB_OK;
@@ -1335,7 +1329,7 @@ int cine_aux(DevBuf &buf, long long &have, long long key, const std::vector<int>
 // n_seq windows of T frames through the 3-D plan: image n = window * T + t, outputs in the same [N][T] order
 int t3d_forward_seq(ukbb_fcn_handle *h, const float *image, int n_seq, int height, int width,
                     float *logits, float *prob, int32_t *pred, hipStream_t s) {
-    if (n_seq < 1) { set_err("forward_seq: n_seq must be positive"); return UKBB_EINVAL; }
+    if (n_seq < 1) { set_error("forward_seq: n_seq must be positive"); return UKBB_EINVAL; }
     int rc = prepare(h, n_seq * h->arch.fc, height, width);
     if (rc) return rc;
     h->t3d_map = nullptr;
@@ -1350,11 +1344,11 @@ int t3d_forward_seq(ukbb_fcn_handle *h, const float *image, int n_seq, int heigh
 int t3d_forward_cine(ukbb_fcn_handle *h, const float *image, int F, int height, int width,
                      int weight_R, double weight_r, int time_step, float *prob, int32_t *pred, hipStream_t s) {
     const int T = h->arch.fc, C = h->arch.n_class;
-    if (!prob) { set_err("forward_cine: prob must not be NULL"); return UKBB_EINVAL; }
-    if (2 * weight_R - 1 != T) { set_err("forward_cine: time window 2*weight_R-1 = %d, the model is built for %d frames", 2 * weight_R - 1, T); return UKBB_EINVAL; }
-    if (time_step < 1) { set_err("forward_cine: time_step must be >= 1 (got %d)", time_step); return UKBB_EINVAL; }
+    if (!prob) { set_error("forward_cine: prob must not be NULL"); return UKBB_EINVAL; }
+    if (2 * weight_R - 1 != T) { set_error("forward_cine: time window 2*weight_R-1 = %d, the model is built for %d frames", 2 * weight_R - 1, T); return UKBB_EINVAL; }
+    if (time_step < 1) { set_error("forward_cine: time_step must be >= 1 (got %d)", time_step); return UKBB_EINVAL; }
     const int rad = (T - 1) / 2;
-    if (F < rad || F < 1) { set_err("forward_cine: %d frames, the circular window of radius %d needs at least %d (the reference raises IndexError)", F, rad, rad > 1 ? rad : 1); return UKBB_EINVAL; }
+    if (F < rad || F < 1) { set_error("forward_cine: %d frames, the circular window of radius %d needs at least %d (the reference raises IndexError)", F, rad, rad > 1 ? rad : 1); return UKBB_EINVAL; }
     int rc = prepare(h, T, height, width, h->scratch_budget ? 0 : -1);     // the plan (its per-frame workspace sizes the chunks)
     if (rc) return rc;
     const size_t HW = (size_t)height * width;
@@ -1364,7 +1358,7 @@ int t3d_forward_cine(ukbb_fcn_handle *h, const float *image, int F, int height, 
     const CineUnits &un = h->cine;
     CinePlan pl;
     if (!plan_cine(un, F, time_step, h->scratch_budget, pl)) {
-        set_err("forward_cine: the scratch budget of %llu bytes is below the %llu bytes one window of %d frames of %dx%d needs", (unsigned long long)h->scratch_budget,
+        set_error("forward_cine: the scratch budget of %llu bytes is below the %llu bytes one window of %d frames of %dx%d needs", (unsigned long long)h->scratch_budget,
                 (unsigned long long)pl.min_bytes, T, height, width);
         return UKBB_EINVAL;
     }
@@ -1401,14 +1395,14 @@ int t3d_forward_cine(ukbb_fcn_handle *h, const float *image, int F, int height, 
         ta.HW = (int)HW; ta.C = C; ta.w0 = w0; ta.w1 = w0 + nw;
         ta.first = w0 == 0; ta.last = w0 + nw == Wn;
         hipError_t e = launch_t3d_tile(ta, s);
-        if (e != hipSuccess) { set_err("tiling kernel launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
+        if (e != hipSuccess) { set_error("tiling kernel launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
     }
     return UKBB_OK;
 }
 
 int lstm_common_checks(ukbb_fcn_handle *h, const float *image, const char *what) {
-    if (!h || !image) { set_err("%s: NULL argument", what); return UKBB_EINVAL; }
-    if (h->arch.kind != UKBB_KIND_UNET_LSTM) { set_err("%s: the model is not a UNet-LSTM", what); return UKBB_EINVAL; }
+    if (!h || !image) { set_error("%s: NULL argument", what); return UKBB_EINVAL; }
+    if (h->arch.kind != UKBB_KIND_UNET_LSTM) { set_error("%s: the model is not a UNet-LSTM", what); return UKBB_EINVAL; }
     return UKBB_OK;
 }
 
@@ -1421,7 +1415,7 @@ int ukbb_fcn_forward_seq(ukbb_fcn_handle *h, const float *image, int n_seq, int 
     int rc = lstm_common_checks(h, image, "forward_seq");
     if (rc) return rc;
     const int T = h->arch.fc, C = h->arch.n_class;
-    if (n_seq < 1) { set_err("forward_seq: n_seq must be positive"); return UKBB_EINVAL; }
+    if (n_seq < 1) { set_error("forward_seq: n_seq must be positive"); return UKBB_EINVAL; }
     h->budget_key = -1;                                                      // the scratch budget bounds forward_cine only: its next call starts from empty buffers again
     rc = prepare(h, n_seq * T, height, width);
     if (rc) return rc;
@@ -1452,9 +1446,9 @@ int ukbb_fcn_forward_seq(ukbb_fcn_handle *h, const float *image, int n_seq, int 
     const size_t kst = (size_t)n_seq * HW * NHID;
     for (int k = 0; k < T; ++k) {                                            // outputs straight into [N][T] order
         LstmOutArgs oa{};
-        const size_t esz = h->plan_bfio ? 2 : 4;
+        const size_t esz = h->mode.bfio() ? 2 : 4;
         auto at = [esz](const float *p, size_t elems) { return reinterpret_cast<const float *>(reinterpret_cast<const char *>(p) + elems * esz); };
-        oa.h_bf16 = h->plan_bfio ? 1 : 0;
+        oa.h_bf16 = h->mode.bfio() ? 1 : 0;
         oa.hf = k == 0 ? h->lstm_h1.p : at(h->lstm_hall.p, (size_t)k * kst);
         oa.mapf = k == 0 ? d_map : nullptr;
         oa.hb = k == T - 1 ? at(h->lstm_h1.p, (size_t)NF * HW * NHID) : at(h->lstm_hall.p, (size_t)T * kst + (size_t)k * kst);
@@ -1465,7 +1459,7 @@ int ukbb_fcn_forward_seq(ukbb_fcn_handle *h, const float *image, int n_seq, int 
         oa.pred = pred ? pred + (size_t)k * HW : nullptr;
         oa.m_stride = (long long)T * HW * C; oa.M = n_seq; oa.HW = (int)HW; oa.n_class = C;
         hipError_t e = launch_lstm_out(oa, s);
-        if (e != hipSuccess) { set_err("ConvLSTM output kernel launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
+        if (e != hipSuccess) { set_error("ConvLSTM output kernel launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
     }
     return UKBB_OK;
 }
@@ -1477,13 +1471,13 @@ int ukbb_fcn_forward_cine(ukbb_fcn_handle *h, const float *image, int n_frames, 
     int rc = lstm_common_checks(h, image, "forward_cine");
     if (rc) return rc;
     const int T = h->arch.fc, C = h->arch.n_class, F = n_frames;
-    if (!prob) { set_err("forward_cine: prob must not be NULL"); return UKBB_EINVAL; }
-    if (2 * weight_R - 1 != T) { set_err("forward_cine: time window 2*weight_R-1 = %d, the model is unrolled for %d steps", 2 * weight_R - 1, T); return UKBB_EINVAL; }
-    if (time_step < 1) { set_err("forward_cine: time_step must be >= 1 (got %d)", time_step); return UKBB_EINVAL; }
+    if (!prob) { set_error("forward_cine: prob must not be NULL"); return UKBB_EINVAL; }
+    if (2 * weight_R - 1 != T) { set_error("forward_cine: time window 2*weight_R-1 = %d, the model is unrolled for %d steps", 2 * weight_R - 1, T); return UKBB_EINVAL; }
+    if (time_step < 1) { set_error("forward_cine: time_step must be >= 1 (got %d)", time_step); return UKBB_EINVAL; }
     const int rad = (T - 1) / 2;
     // the reference wraps a window index once only (i < 0: i + T; i >= T: i - T, deploy_network_ao.py:151-157):
     // with fewer than rad frames the wrapped index is still out of range and numpy raises IndexError
-    if (F < rad || F < 1) { set_err("forward_cine: %d frames, the circular window of radius %d needs at least %d (the reference raises IndexError)", F, rad, rad > 1 ? rad : 1); return UKBB_EINVAL; }
+    if (F < rad || F < 1) { set_error("forward_cine: %d frames, the circular window of radius %d needs at least %d (the reference raises IndexError)", F, rad, rad > 1 ? rad : 1); return UKBB_EINVAL; }
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t HW = (size_t)height * width;
     const int Wn = (F + time_step - 1) / time_step;                         // window centres range(0, F, time_step) (:147)
@@ -1494,13 +1488,13 @@ int ukbb_fcn_forward_cine(ukbb_fcn_handle *h, const float *image, int n_frames, 
     const CineUnits &un = h->cine;
     CinePlan pl;
     if (!plan_cine(un, F, time_step, h->scratch_budget, pl)) {
-        set_err("forward_cine: the scratch budget of %llu bytes is below the minimum of %llu bytes for %d frames of %dx%d at time_step %d", (unsigned long long)h->scratch_budget,
+        set_error("forward_cine: the scratch budget of %llu bytes is below the minimum of %llu bytes for %d frames of %dx%d at time_step %d", (unsigned long long)h->scratch_budget,
                 (unsigned long long)pl.min_bytes, F, height, width, time_step);
         return UKBB_EINVAL;
     }
     const int Wc = pl.Wc;
-    if (pl.chunks > 1 && h->plan_bfio && (h->lstm_bf_wino || !h->lstm_bf_hoist)) {
-        set_err("forward_cine: the A/B forms UKBB_LSTM_BF16_WINOGRAD / UKBB_LSTM_BF16_UNHOIST run unchunked only (unset them or the scratch budget)");
+    if (pl.chunks > 1 && h->mode.bfio() && (h->lstm_bf_wino || !h->lstm_bf_hoist)) {
+        set_error("forward_cine: the A/B forms UKBB_LSTM_BF16_WINOGRAD / UKBB_LSTM_BF16_UNHOIST run unchunked only (unset them or the scratch budget)");
         return UKBB_EINVAL;
     }
     rc = budget_enter(h, F, height, width, time_step, pl);
@@ -1533,7 +1527,7 @@ int ukbb_fcn_forward_cine(ukbb_fcn_handle *h, const float *image, int n_frames, 
     rc = cine_aux(h->lstm_aux, h->lstm_aux_key, key, map, order, wk, wsum, s, aux);
     if (rc) return rc;
     const int NHID = h->arch.same_dim;
-    const size_t esz = h->plan_bfio ? 2 : 4;
+    const size_t esz = h->mode.bfio() ? 2 : 4;
     auto at = [esz](const float *p, size_t elems) { return reinterpret_cast<const float *>(reinterpret_cast<const char *>(p) + elems * esz); };
     if (pl.chunks > 1) HIP_TRY(h->lstm_img.ensure((size_t)pl.run * HW), UKBB_ENOMEM);
     for (int w0 = 0; w0 < Wn; w0 += Wc) {
@@ -1553,7 +1547,7 @@ int ukbb_fcn_forward_cine(ukbb_fcn_handle *h, const float *image, int n_frames, 
         if (rc) return rc;
         LstmTileArgs ta{};
         ta.k_stride = (long long)nw * HW * NHID;
-        ta.h_bf16 = h->plan_bfio ? 1 : 0;
+        ta.h_bf16 = h->mode.bfio() ? 1 : 0;
         ta.hf = h->lstm_hall.p; ta.hb = at(h->lstm_hall.p, (size_t)T * ta.k_stride);
         ta.h1f = h->lstm_h1.p; ta.h1b = at(h->lstm_h1.p, (size_t)R * HW * NHID);
         ta.map_first = d_map; ta.map_last = d_map + (size_t)(T - 1) * nw;
@@ -1562,7 +1556,7 @@ int ukbb_fcn_forward_cine(ukbb_fcn_handle *h, const float *image, int n_frames, 
         ta.prob = prob; ta.pred = pred; ta.Wn = nw; ta.HW = (int)HW; ta.C = C;
         ta.w0 = w0; ta.w1 = w0 + nw; ta.first = w0 == 0; ta.last = w0 + nw == Wn;
         hipError_t e = launch_lstm_tile(ta, s);
-        if (e != hipSuccess) { set_err("tiling kernel launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
+        if (e != hipSuccess) { set_error("tiling kernel launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
     }
     return UKBB_OK;
 }
@@ -1593,14 +1587,13 @@ double ukbb_fcn_kernel_mfma_macs_issued(const ukbb_fcn_handle *h, int i) {
 }
 
 int ukbb_fcn_set_precision(ukbb_fcn_handle *h, int precision) {
-    if (!h || (precision != UKBB_PREC_FP32 && precision != UKBB_PREC_BF16 && precision != UKBB_PREC_F32X3 && precision != UKBB_PREC_BF16_STORE)) { set_err("set_precision: bad argument"); return UKBB_EINVAL; }
-    if (h->arch.kind != UKBB_KIND_FCN && precision == UKBB_PREC_BF16_STORE) { set_err("set_precision: %s", BF16_STORE_FCN_ONLY); return UKBB_EARCH; }
-    if (h->arch.kind == UKBB_KIND_TEMPORAL_UNET && precision == UKBB_PREC_BF16) {
-        set_err("set_precision: the Temporal-UNet's 3-D convolutions are built for fp32 only (no bf16 plan)");
-        return UKBB_EARCH;
-    }
+    PlanMode m;
+    const char *why;
+    const int rc = h ? plan_mode(h->arch, precision, m, &why) : UKBB_EINVAL;
+    if (rc == UKBB_EINVAL) { set_error("set_precision: bad argument"); return rc; }
+    if (rc) { set_error("set_precision: %s", why); return rc; }
     if (precision != h->precision) {
-        if (hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { set_err("set_precision: device sync failed"); return UKBB_EDEVICE; }
+        if (hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { set_error("set_precision: device sync failed"); return UKBB_EDEVICE; }
         h->precision = precision;
         h->plan_h = h->plan_w = 0;               // re-plan (tilings and packed weights differ)
     }
@@ -1621,7 +1614,7 @@ const char *ukbb_fcn_conv_config_name(int id) {
 }
 
 int ukbb_fcn_set_timing(ukbb_fcn_handle *h, int enable) {
-    if (!h) { set_err("set_timing: NULL handle"); return UKBB_EINVAL; }
+    if (!h) { set_error("set_timing: NULL handle"); return UKBB_EINVAL; }
     int rc = collect_events(h);
     if (rc) return rc;
     h->timing = enable != 0;
@@ -1630,17 +1623,17 @@ int ukbb_fcn_set_timing(ukbb_fcn_handle *h, int enable) {
 }
 
 int ukbb_fcn_set_timing_kernel(ukbb_fcn_handle *h, int kernel) {
-    if (!h) { set_err("set_timing_kernel: NULL handle"); return UKBB_EINVAL; }
+    if (!h) { set_error("set_timing_kernel: NULL handle"); return UKBB_EINVAL; }
     int rc = collect_events(h);
     if (rc) return rc;
-    if (kernel >= (int)h->ops.size()) { set_err("set_timing_kernel: index out of range"); return UKBB_EINVAL; }
+    if (kernel >= (int)h->ops.size()) { set_error("set_timing_kernel: index out of range"); return UKBB_EINVAL; }
     h->timing = true;
     h->timing_only = kernel < 0 ? -1 : kernel;
     return UKBB_OK;
 }
 
 int ukbb_fcn_kernel_times(ukbb_fcn_handle *h, double *sum_ms, int64_t *count, int n, int reset) {
-    if (!h) { set_err("kernel_times: NULL handle"); return UKBB_EINVAL; }
+    if (!h) { set_error("kernel_times: NULL handle"); return UKBB_EINVAL; }
     int rc = collect_events(h);
     if (rc) return rc;
     const int m = std::min<int>(n, (int)h->ops.size());
@@ -1653,17 +1646,17 @@ int ukbb_fcn_kernel_times(ukbb_fcn_handle *h, double *sum_ms, int64_t *count, in
 }
 
 int64_t ukbb_fcn_get_activation(ukbb_fcn_handle *h, const char *name, float *dst, int64_t cap) {
-    if (!h || !name) { set_err("get_activation: NULL argument"); return UKBB_EINVAL; }
+    if (!h || !name) { set_error("get_activation: NULL argument"); return UKBB_EINVAL; }
     for (size_t i = 0; i < h->act.size(); ++i) {
         if (h->act_name[i] != name) continue;
         const int64_t n = (int64_t)h->act_per_image[i] * h->last_n;
         if (!dst) return n;
-        if (cap < n) { set_err("get_activation: buffer too small (%lld < %lld)", (long long)cap, (long long)n); return UKBB_EINVAL; }
+        if (cap < n) { set_error("get_activation: buffer too small (%lld < %lld)", (long long)cap, (long long)n); return UKBB_EINVAL; }
         if (h->act_esz[i] == 2) {                      // stored as bf16: widen on the host
             std::vector<uint16_t> tmp((size_t)n);
             if (hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
                 hipMemcpy(tmp.data(), h->act[i]->p, (size_t)n * 2, hipMemcpyDeviceToHost) != hipSuccess) {
-                set_err("get_activation: device copy failed");
+                set_error("get_activation: device copy failed");
                 return UKBB_EDEVICE;
             }
             // channel-blocked on the device ([N][C/16][H][W][16], kernels.h); handed out as NHWC like the fp32 plans' maps
@@ -1680,7 +1673,7 @@ int64_t ukbb_fcn_get_activation(ukbb_fcn_handle *h, const char *name, float *dst
         }
         if (hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
             hipMemcpy(dst, h->act[i]->p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
-            set_err("get_activation: device copy failed");
+            set_error("get_activation: device copy failed");
             return UKBB_EDEVICE;
         }
         return n;
@@ -1691,15 +1684,15 @@ int64_t ukbb_fcn_get_activation(ukbb_fcn_handle *h, const char *name, float *dst
         if (strcmp(kv.first, name)) continue;
         const int64_t n = (int64_t)kv.second->n;
         if (!dst) return n;
-        if (cap < n) { set_err("get_activation: buffer too small (%lld < %lld)", (long long)cap, (long long)n); return UKBB_EINVAL; }
+        if (cap < n) { set_error("get_activation: buffer too small (%lld < %lld)", (long long)cap, (long long)n); return UKBB_EINVAL; }
         if (hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
             hipMemcpy(dst, kv.second->p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
-            set_err("get_activation: device copy failed");
+            set_error("get_activation: device copy failed");
             return UKBB_EDEVICE;
         }
         return n;
     }
-    set_err("get_activation: no activation named '%s'", name);
+    set_error("get_activation: no activation named '%s'", name);
     return UKBB_EINVAL;
 }
 

@@ -162,14 +162,14 @@ struct ConvArgs {
     const int *in0_map; // optional (Winograd kernel only): image n of the batch reads in0 image in0_map[n]
                         // (ConvLSTM windows share cached U-Net feature frames); in1 / out are not remapped
     int diag;           // diagnostic builds only (-DUKBB_DIAG, env UKBB_CONV_DIAG): ablation bits of conv_pc_kernel
-    // bf16-storage tilings only (pc == 5): the 1x1 logits conv + softmax / argmax of network_ao.py:63,159-160 evaluated in the
+    // bf16-storage tilings only (ConvFamily::Bf16Store): the 1x1 logits conv + softmax / argmax of network_ao.py:63,159-160 evaluated in the
     // epilogue of the LAST 16-channel conv (out is then not written at all): lg_w [16][lg_ncls], lg_b [lg_ncls]
     const float *lg_w, *lg_b;
     float *lg_logits, *lg_prob;   // optional [N,Ho,Wo,lg_ncls]
     int32_t *lg_pred;             // optional [N,Ho,Wo]
     int lg_ncls;
     int xcd_local;      // kernels_ws.hip only: tile order (set by launch_conv_ws)
-    int cout_store;     // bf16-storage tilings (ConvConfig::pc == 5) only: real channel count of `out` when Cout is the zero-padded
+    int cout_store;     // bf16-storage tilings (stores_bf16) only: real channel count of `out` when Cout is the zero-padded
                         // count the weights were packed for (a 16-channel layer on the 32-row MFMA); 0 = Cout
     // ---- ConvLSTM cell in the epilogue of the F(2x4) Winograd kernel (kernels_wino24.hip, launch_wino24_lstm; network_ao.py:255-319) ----
     // ls_mode 1 ("x pass", once per call): in0 = the U-Net feature frames [N][H][W][16], Cout = 64 per direction (groups = directions),
@@ -191,6 +191,23 @@ struct ConvArgs {
                                 //    Strides (ls_*_dir) still count ELEMENTS; ls_gx_dir counts gx values (4 per lane-slot)
 };
 
+// The kernel family a tiling belongs to: which kernel runs it, in which number formats, from which packed weights.
+enum class ConvFamily {
+    Direct,         // single-role kernel
+    ProdCons,       // producer/consumer persistent kernel (512 threads)
+    ProdConsFirst,  // producer/consumer with the C_in = 1 first layer fused into the producers
+    Bf16Operands,   // single-role kernel with bf16 operands / fp32 accumulation (mb = 32, kc = 16)
+    Wino22,         // Winograd F(2x2,3x3) producer/consumer kernel (kernels_wino.hip): 8 x 16- or 16 x 8-pixel regions
+    Wino24,         // Winograd F(2x4,3x3) (kernels_wino24.hip): 8 x 32- or 8 x 16-pixel regions (id 306: 8 x 16 over image pairs; 307: 32-channel items)
+    Bf16Store,      // as Bf16Operands with bf16 activations in HBM on both sides (in0 / in1 / out point at bf16 data), CHANNEL-BLOCKED:
+                    // [N][C/16][H][W][16] -- a 16-channel K chunk of a row of pixels is one contiguous run of 32-byte pixels
+                    // (r04: in plain NHWC a wave's 16-byte pieces of one chunk lay 2 C bytes apart, every piece pulled a whole
+                    // 128-byte line out of L2 for 16-32 useful bytes); for C = 16 the two layouts coincide
+    Bf16StoreWs,    // bf16 storage as Bf16Store, weight-stationary persistent kernel of independent waves (kernels_ws.hip)
+    FirstWino22,    // as ProdConsFirst (fused first layer, fp32), the 16 -> 16 conv as Winograd F(2x2,3x3) in the consumers (id 134;
+                    // weights from pack_wino_first_weights)
+};
+
 // One compiled tiling of the conv kernel.
 struct ConvConfig {
     int id;
@@ -200,21 +217,22 @@ struct ConvConfig {
     int kc;             // input channels staged in LDS per pass
     int wm, wn, cb;     // waves along Cout / along pixels; Cout blocks per wave
     int lds_bytes;
-    int pc;             // 0: single-role kernel; 1: producer/consumer persistent kernel (512 threads);
-                        // 2: producer/consumer with the C_in = 1 first layer fused into the producers;
-                        // 3: single-role kernel with bf16 operands / fp32 accumulation (mb = 32, kc = 16);
-                        // 4: Winograd F(2x2,3x3) producer/consumer kernel (kernels_wino.hip)
-                        // 5: as 3 with bf16 activations in HBM on both sides (in0 / in1 / out point at bf16 data), CHANNEL-BLOCKED:
-                        //    [N][C/16][H][W][16] -- a 16-channel K chunk of a row of pixels is one contiguous run of 32-byte pixels
-                        //    (r04: in plain NHWC a wave's 16-byte pieces of one chunk lay 2 C bytes apart, every piece pulled a whole
-                        //    128-byte line out of L2 for 16-32 useful bytes); for C = 16 the two layouts coincide
-                        // 6: bf16 storage as 5, weight-stationary persistent kernel of independent waves (kernels_ws.hip)
-                        // 7: as 2 (fused first layer, fp32), the 16 -> 16 conv as Winograd F(2x2,3x3) in the consumers (id 134; weights
-                        //    from pack_wino_first_weights)
+    ConvFamily family;
     const char *name;
-    int fuse;           // pc == 5 only: 1 = the C_in = 1 first layer evaluated in this conv's staging (ConvArgs::first_w / first_b,
-                        // in0 = the fp32 image), 2 = the logits conv + softmax / argmax in its epilogue (ConvArgs::lg_*); else 0
+    int fuse;           // Bf16Store / Bf16StoreWs only: 1 = the C_in = 1 first layer evaluated in this conv's staging (ConvArgs::first_w /
+                        // first_b, in0 = the fp32 image), 2 = the logits conv + softmax / argmax in its epilogue (ConvArgs::lg_*); else 0
 };
+
+// What follows from a tiling's family, each fact stated once.
+inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+inline bool fuses_first(const ConvConfig &c) { return c.family == ConvFamily::ProdConsFirst || c.family == ConvFamily::FirstWino22; }
+inline bool stores_bf16(const ConvConfig &c) { return c.family == ConvFamily::Bf16Store || c.family == ConvFamily::Bf16StoreWs; }   // activations bf16 in HBM
+inline bool packs_bf16(const ConvConfig &c) { return c.family == ConvFamily::Bf16Operands || stores_bf16(c); }                      // weights packed as bf16
+inline bool is_wino24(const ConvConfig &c) { return c.family == ConvFamily::Wino24; }
+inline bool is_wino(const ConvConfig &c) { return c.family == ConvFamily::Wino22 || is_wino24(c); }
+inline int cout_per_item(const ConvConfig &c) { return is_wino(c) ? 16 * c.wm : c.mb * c.cb * c.wm; }    // output channels of one work item
+inline int packed_cout(const ConvConfig &c, int cout) { return stores_bf16(c) ? round_up(cout, 32) : cout; }   // 16-channel layers run zero-padded on the 32-row MFMA
+inline int map_tiles(const ConvConfig &c, int Ho, int Wo) { return ((Ho + c.th - 1) / c.th) * ((Wo + c.tw - 1) / c.tw); }   // tiles (regions) of one Ho x Wo map
 
 int num_conv_configs();
 const ConvConfig &conv_config(int id);
@@ -222,7 +240,7 @@ const ConvConfig &conv_config(int id);
 int num_pk16_configs();
 const ConvConfig &pk16_config(int i);
 hipError_t launch_conv16_pk(int cfg_id, const ConvArgs &a, hipStream_t s);
-// weight-stationary persistent 3x3 stride-1 tilings of the bf16 U-Net (ids 400-, ConvConfig::pc == 6: bf16 storage as pc 5; th = rows per
+// weight-stationary persistent 3x3 stride-1 tilings of the bf16 U-Net (ids 400-, ConvFamily::Bf16StoreWs: bf16 storage as Bf16Store; th = rows per
 // tile, tw = 32, wn = independent waves per workgroup, cb = 32-channel Cout blocks per workgroup) live in kernels_ws.hip; the three
 // functions above cover them.  LDS need depends on the layer's input channels (the whole packed filter of a Cout group is resident).
 int num_ws_configs();
@@ -236,11 +254,11 @@ hipError_t launch_conv(int cfg_id, const ConvArgs &a, hipStream_t s);
 // Host-side: pack folded weights W[ks][ks][Cin][Cout] into A-fragment order
 // for tiling (mb, kc) and workgroups of ncbl = wm*cb Cout blocks.  Returns floats written.
 size_t pack_conv_weights(const float *w, int ks, int cin, int cout, int mb, int kc, int ncbl, float *dst);
-// bf16 operand variant (ConvConfig::pc == 3): 8 bf16 per lane per tap, returns dwords written.
+// bf16 operand variant (packs_bf16): 8 bf16 per lane per tap, returns dwords written.
 size_t pack_conv_weights_bf16(const float *w, int ks, int cin, int cout, int ncbl, float *dst);
 
 // Winograd F(2x2,3x3) producer/consumer kernel (kernels_wino.hip): 3x3, stride 1, C_out % 64 == 0,
-// C_in % 16 == 0.  ConvConfig::pc == 4, id 300.  Same ConvArgs; wpk from pack_wino_weights().
+// C_in % 16 == 0.  ConvFamily::Wino22, ids 300-303.  Same ConvArgs; wpk from pack_wino_weights().
 // thread-local error string behind ukbb_fcn_last_error() (engine.cpp)
 void set_error(const char *fmt, ...);
 
@@ -249,8 +267,7 @@ hipError_t launch_wino(const ConvArgs &a, int ncb /*16-channel blocks per item: 
 size_t pack_wino_weights(const float *w /*[3][3][cin][cout] folded*/, int cin, int cout, int ncb, float *dst /*16*cin*cout*/);
 size_t pack_wino_first_weights(const float *w /*[3][3][16][16] folded*/, float *dst /*16*16*16*/);
 int wino_lds_bytes();
-// Winograd F(2x4,3x3) (kernels_wino24.hip): 64-channel output groups, 8 x 32- or 8 x 16-pixel regions, ConvConfig::pc == 4, ids 304 / 305 / 306 / 307 (306: 8 x 16 over image pairs; 307: 32-channel items)
-inline bool is_wino24(const ConvConfig &c) { return c.pc == 4 && c.id >= 304; }
+// Winograd F(2x4,3x3) (kernels_wino24.hip): 64-channel output groups, 8 x 32- or 8 x 16-pixel regions, ConvFamily::Wino24, ids 304 / 305 / 306 / 307 (306: 8 x 16 over image pairs; 307: 32-channel items)
 hipError_t launch_wino24(const ConvArgs &a, int tile_cols /*32 | 16*/, int pair /*id 306: image pairs with seam regions, Ho % 8 == 4*/, int ncb /*4 | 2 (id 307)*/,
                          hipStream_t s);
 size_t pack_wino24_weights(const float *w /*[3][3][cin][cout] folded*/, int cin, int cout, int ncb, float *dst /*24*cin*cout*/);
@@ -302,7 +319,7 @@ struct SqgArgs {
     long long npix;
     int cin;
     int x_bf16;              // input format.  0: x is fp32 [npix][cin].  1 (UKBB_PREC_BF16_STORE): x is bf16, channel-blocked [N][cin/16][hw][16]
-                             // (ConvConfig::pc == 5), decoded to fp32 on the way in (exact); everything behind the load is the fp32 launch
+                             // (ConvFamily::Bf16Store), decoded to fp32 on the way in (exact); everything behind the load is the fp32 launch
     int hw;                  // x_bf16 only: pixels per image (npix = N * hw)
 };
 hipError_t launch_sqg(const SqgArgs &a, hipStream_t s);

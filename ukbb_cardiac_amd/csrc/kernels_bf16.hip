@@ -192,13 +192,13 @@ __global__ __launch_bounds__(256, 2) void conv16_logits_pk_kernel(const ConvArgs
 
 }  // namespace
 
-// P(id, TH, TW); ConvConfig::pc == 5 (bf16 storage), fuse == 2, one 32-row Cout block, kc = 16
+// P(id, TH, TW); ConvFamily::Bf16Store, fuse == 2, one 32-row Cout block, kc = 16
 #define UKBB_PK16_CONFIGS(P)                   \
     P(324, 8, 32)                              \
     P(325, 16, 16)
 
 #define UKBB_PK16_ENTRY(ID, TH, TW)                                                                     \
-    {ID, 3, 1, 32, TH, TW, 16, 1, 4, 1, pk16_lds_bytes(TH, TW), 5, "convBF16pk_3x3s1+logits_t" #TH "x" #TW, 2},
+    {ID, 3, 1, 32, TH, TW, 16, 1, 4, 1, pk16_lds_bytes(TH, TW), ConvFamily::Bf16Store, "convBF16pk_3x3s1+logits_t" #TH "x" #TW, 2},
 static const ConvConfig g_pk16_cfgs[] = {UKBB_PK16_CONFIGS(UKBB_PK16_ENTRY)};
 
 int num_pk16_configs() { return (int)(sizeof(g_pk16_cfgs) / sizeof(g_pk16_cfgs[0])); }

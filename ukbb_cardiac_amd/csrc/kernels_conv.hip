@@ -506,7 +506,7 @@ __global__ __launch_bounds__(256, conv_min_waves(KS, STRIDE, MB, TH, TW, KC, WM,
 // order as conv_first_kernel) and write the KC-channel tile to LDS, so that layer's output
 // never exists in HBM.  Halo pixels outside the image are this conv's zero padding.
 //
-// WINO = true (with FIRST; ConvConfig::pc == 7): conv0_1 as Winograd F(2x2, 3x3) instead of the direct 3x3.  The producers are the
+// WINO = true (with FIRST; ConvFamily::FirstWino22): conv0_1 as Winograd F(2x2, 3x3) instead of the direct 3x3.  The producers are the
 // FIRST producers above, unchanged (raw tile -> conv0_0 -> the 18 x 18 x 16 halo tile xs); the consumers transform their B operands in
 // registers -- no VS stage, no extra barrier -- and the 16 x 16-point pre-transformed weights U (pack_wino_first_weights) are staged
 // once into LDS beside the two halo buffers.  See the consumer branch below.  Its consumers hold 64 accumulators + 32 transformed operands:
@@ -1321,11 +1321,11 @@ __global__ __launch_bounds__(512, WINO ? 4 : 2) void conv_pc_kernel(const ConvAr
 
 #define UKBB_CFG_ENTRY(ID, KS, S, MB, TH, TW, KC, WM, WN, CB)                                   \
     {ID, KS, S, MB, TH, TW, KC, WM, WN, CB,                                                     \
-     conv_lds_bytes(KS, S, MB, TH, TW, KC, WM, CB), 0,                                          \
+     conv_lds_bytes(KS, S, MB, TH, TW, KC, WM, CB), ConvFamily::Direct,                         \
      "conv" #KS "x" #KS "s" #S "_mb" #MB "_t" #TH "x" #TW "_kc" #KC "_w" #WM "x" #WN "_cb" #CB},
 #define UKBB_PC_ENTRY(ID, KS, S, MB, TH, TW, KC, WM, WN, CB)                                    \
     {ID, KS, S, MB, TH, TW, KC, WM, WN, CB,                                                     \
-     2 * conv_lds_bytes(KS, S, MB, TH, TW, KC, WM, CB), 1,                                      \
+     2 * conv_lds_bytes(KS, S, MB, TH, TW, KC, WM, CB), ConvFamily::ProdCons,                   \
      "convPC" #KS "x" #KS "s" #S "_mb" #MB "_t" #TH "x" #TW "_kc" #KC "_w" #WM "x" #WN "_cb" #CB},
 
 // Producer/consumer tilings.  Y(id, KS, STRIDE, MB, TH, TW, KC, WM, WN, CB)
@@ -1367,7 +1367,7 @@ __global__ __launch_bounds__(512, WINO ? 4 : 2) void conv_pc_kernel(const ConvAr
     B(220, 2, 1, 12, 13, 2, 2, 1)          \
     B(221, 2, 1, 16, 16, 2, 2, 1)
 
-// The same tilings with bf16 activations in HBM on both sides (ConvConfig::pc == 5).
+// The same tilings with bf16 activations in HBM on both sides (ConvFamily::Bf16Store).
 #define UKBB_BFIO_CONFIGS(B)               \
     B(230, 3, 1, 12, 13, 2, 2, 1)          \
     B(231, 3, 1, 12, 26, 2, 2, 1)          \
@@ -1411,18 +1411,18 @@ __global__ __launch_bounds__(512, WINO ? 4 : 2) void conv_pc_kernel(const ConvAr
 
 #define UKBB_PCF_ENTRY(ID, KS, S, MB, TH, TW, KC, WM, WN, CB)                                   \
     {ID, KS, S, MB, TH, TW, KC, WM, WN, CB,                                                     \
-     2 * conv_lds_bytes(KS, S, MB, TH, TW, KC, WM, CB) + 2 * 4 * (((TH - 1) * S + KS + 2) * ((TW - 1) * S + KS + 2)), 2, \
+     2 * conv_lds_bytes(KS, S, MB, TH, TW, KC, WM, CB) + 2 * 4 * (((TH - 1) * S + KS + 2) * ((TW - 1) * S + KS + 2)), ConvFamily::ProdConsFirst, \
      "convPCfirst" #KS "x" #KS "s" #S "_mb" #MB "_t" #TH "x" #TW "_kc" #KC "_w" #WM "x" #WN "_cb" #CB},
 
 __host__ __device__ constexpr int conv_bf_lds_bytes(int ks, int s, int th, int tw, int wm, int cb) {
     return ((16 / 2 + 4) * ((th - 1) * s + ks) * ((tw - 1) * s + ks) + wm * cb * ks * ks * 64 * 4) * 4;
 }
 #define UKBB_BF_ENTRY(ID, KS, S, TH, TW, WM, WN, CB)                                            \
-    {ID, KS, S, 32, TH, TW, 16, WM, WN, CB, conv_bf_lds_bytes(KS, S, TH, TW, WM, CB), 3,       \
+    {ID, KS, S, 32, TH, TW, 16, WM, WN, CB, conv_bf_lds_bytes(KS, S, TH, TW, WM, CB), ConvFamily::Bf16Operands, \
      "convBF16_" #KS "x" #KS "s" #S "_t" #TH "x" #TW "_w" #WM "x" #WN "_cb" #CB},
 
 #define UKBB_BFIO_ENTRY(ID, KS, S, TH, TW, WM, WN, CB)                                          \
-    {ID, KS, S, 32, TH, TW, 16, WM, WN, CB, conv_bf_lds_bytes(KS, S, TH, TW, WM, CB), 5,       \
+    {ID, KS, S, 32, TH, TW, 16, WM, WN, CB, conv_bf_lds_bytes(KS, S, TH, TW, WM, CB), ConvFamily::Bf16Store, \
      "convBF16io_" #KS "x" #KS "s" #S "_t" #TH "x" #TW "_w" #WM "x" #WN "_cb" #CB, 0},
 // F(id, TH, TW, WN-by-4 tiling, FUSE): 3x3 stride 1, one 32-row Cout block (the 16-channel layers of level 0)
 #define UKBB_BFIOF_CONFIGS(F)              \
@@ -1434,22 +1434,22 @@ __host__ __device__ constexpr int conv_bf_lds_bytes(int ks, int s, int th, int t
     F(299, 8, 32, 2)
 #define UKBB_BFIOF_ENTRY(ID, TH, TW, FUSE)                                                      \
     {ID, 3, 1, 32, TH, TW, 16, 1, 4, 1,                                                         \
-     conv_bf_lds_bytes(3, 1, TH, TW, 1, 1) + ((FUSE) == 1 ? 4 * ((TH) + 4) * ((TW) + 4) : 0), 5,   /* + raw tile of the fused first layer */ \
+     conv_bf_lds_bytes(3, 1, TH, TW, 1, 1) + ((FUSE) == 1 ? 4 * ((TH) + 4) * ((TW) + 4) : 0), ConvFamily::Bf16Store,   /* + raw tile of the fused first layer */ \
      (FUSE) == 1 ? "convBF16io_first+3x3s1_t" #TH "x" #TW "_w1x4_cb1" : "convBF16io_3x3s1+logits_t" #TH "x" #TW "_w1x4_cb1", FUSE},
 
 static const ConvConfig g_cfgs[] = {UKBB_CONV_CONFIGS(UKBB_CFG_ENTRY) UKBB_PC_CONFIGS(UKBB_PC_ENTRY)
                                     UKBB_PCF_CONFIGS(UKBB_PCF_ENTRY) UKBB_BF_CONFIGS(UKBB_BF_ENTRY) UKBB_BFIO_CONFIGS(UKBB_BFIO_ENTRY) UKBB_BFIOF_CONFIGS(UKBB_BFIOF_ENTRY)
                                     // Winograd F(2x2,3x3): region 4x8 tiles (8x16 px), 64 Cout per item, KC 16
-                                    {300, 3, 1, 16, 8, 16, 16, 4, 1, 1, 125184, 4, "winogradF2x2_3x3_t8x16_kc16_cout64"},
-                                    {301, 3, 1, 16, 8, 16, 16, 2, 1, 1, 125184, 4, "winogradF2x2_3x3_t8x16_kc16_cout32"},
-                                    {302, 3, 1, 16, 16, 8, 16, 4, 1, 1, 125184, 4, "winogradF2x2_3x3_t16x8_kc16_cout64"},
-                                    {303, 3, 1, 16, 16, 8, 16, 2, 1, 1, 125184, 4, "winogradF2x2_3x3_t16x8_kc16_cout32"},
-                                    {304, 3, 1, 16, 8, 32, 16, 4, 1, 1, 152960, 4, "winogradF2x4_3x3_t8x32_kc16_cout64"},
-                                    {305, 3, 1, 16, 8, 16, 16, 4, 1, 1, 87808, 4, "winogradF2x4_3x3_t8x16_kc16_cout64"},
-                                    {306, 3, 1, 16, 8, 16, 16, 4, 1, 1, 95488, 4, "winogradF2x4_3x3_t8x16pair_kc16_cout64"},
-                                    {307, 3, 1, 16, 8, 32, 16, 2, 1, 1, 152960, 4, "winogradF2x4_3x3_t8x32_kc16_cout32"},
+                                    {300, 3, 1, 16, 8, 16, 16, 4, 1, 1, 125184, ConvFamily::Wino22, "winogradF2x2_3x3_t8x16_kc16_cout64"},
+                                    {301, 3, 1, 16, 8, 16, 16, 2, 1, 1, 125184, ConvFamily::Wino22, "winogradF2x2_3x3_t8x16_kc16_cout32"},
+                                    {302, 3, 1, 16, 16, 8, 16, 4, 1, 1, 125184, ConvFamily::Wino22, "winogradF2x2_3x3_t16x8_kc16_cout64"},
+                                    {303, 3, 1, 16, 16, 8, 16, 2, 1, 1, 125184, ConvFamily::Wino22, "winogradF2x2_3x3_t16x8_kc16_cout32"},
+                                    {304, 3, 1, 16, 8, 32, 16, 4, 1, 1, 152960, ConvFamily::Wino24, "winogradF2x4_3x3_t8x32_kc16_cout64"},
+                                    {305, 3, 1, 16, 8, 16, 16, 4, 1, 1, 87808, ConvFamily::Wino24, "winogradF2x4_3x3_t8x16_kc16_cout64"},
+                                    {306, 3, 1, 16, 8, 16, 16, 4, 1, 1, 95488, ConvFamily::Wino24, "winogradF2x4_3x3_t8x16pair_kc16_cout64"},
+                                    {307, 3, 1, 16, 8, 32, 16, 2, 1, 1, 152960, ConvFamily::Wino24, "winogradF2x4_3x3_t8x32_kc16_cout32"},
                                     // fused first layer + Winograd F(2x2,3x3) conv0_1 (conv_pc_kernel WINO): two 18x18x20 halo buffers, U, two raw tiles
-                                    {134, 3, 1, 16, 16, 16, 16, 1, 4, 1, (2 * 324 * 20 + 2 * 16 * 64 * 2 + 2 * 400) * 4, 7, "winogradF2x2_first+3x3s1_t16x16_kc16_cout16"}};
+                                    {134, 3, 1, 16, 16, 16, 16, 1, 4, 1, (2 * 324 * 20 + 2 * 16 * 64 * 2 + 2 * 400) * 4, ConvFamily::FirstWino22, "winogradF2x2_first+3x3s1_t16x16_kc16_cout16"}};
 
 static constexpr int N_BASE_CFGS = (int)(sizeof(g_cfgs) / sizeof(g_cfgs[0]));
 int num_conv_configs() { return N_BASE_CFGS + num_pk16_configs() + num_ws_configs(); }
@@ -1511,10 +1511,10 @@ hipError_t launch_conv(int cfg_id, const ConvArgs &a_in, hipStream_t s) {
     const ConvConfig *c = nullptr;
     for (const auto &e : g_cfgs) if (e.id == cfg_id) c = &e;
     if (!c) return hipErrorInvalidValue;
-    const int group = c->mb * c->cb * c->wm;
-    if (c->pc == 4) return is_wino24(*c) ? launch_wino24(a, c->tw, c->id == 306, c->wm, s) : launch_wino(a, c->wm, c->th / 2, s);
+    const int group = cout_per_item(*c);
+    if (is_wino(*c)) return is_wino24(*c) ? launch_wino24(a, c->tw, c->id == 306, c->wm, s) : launch_wino(a, c->wm, c->th / 2, s);
     if (a.in0_map) return hipErrorInvalidValue;       // image remapping exists in the Winograd kernel only
-    if (c->pc == 2 || c->pc == 7) {
+    if (fuses_first(*c)) {
         if (!a.first_w || !a.first_b || a.Cout != group) return hipErrorInvalidValue;
     } else if (a.Cout % group || (a.C0 + a.C1) % c->kc || a.C0 % c->kc) {
         return hipErrorInvalidValue;

@@ -906,7 +906,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void lstm_ws_kernel(const ConvArgs
 
 }  // namespace
 
-// W(id, R, CB, NW): ConvConfig::pc == 6, 3x3 stride 1, mb 32, th = R, tw = 32, kc 16, wm 1, wn = NW, cb = CB
+// W(id, R, CB, NW): ConvFamily::Bf16StoreWs, 3x3 stride 1, mb 32, th = R, tw = 32, kc 16, wm 1, wn = NW, cb = CB
 #define UKBB_WS_CONFIGS(W)          \
     W(400, 2, 1, 8)                 \
     W(401, 4, 1, 4)                 \
@@ -930,13 +930,13 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void lstm_ws_kernel(const ConvArgs
     T(412, 2, 4)
 
 #define UKBB_WS_ENTRY(ID, R, CB, NW) \
-    {ID, 3, 1, 32, R, WS_TW, 16, 1, NW, CB, 0, 6, "convBF16ws_3x3s1_r" #R "x32_cb" #CB "_w" #NW, 0},
+    {ID, 3, 1, 32, R, WS_TW, 16, 1, NW, CB, 0, ConvFamily::Bf16StoreWs, "convBF16ws_3x3s1_r" #R "x32_cb" #CB "_w" #NW, 0},
 #define UKBB_WST_ENTRY(ID, R, NW) \
-    {ID, 2, 1, 32, R, WS_TW, 16, 1, NW, 2, 0, 6, "tconvBF16ws_2x2_r" #R "x32_cb2_w" #NW, 0},
+    {ID, 2, 1, 32, R, WS_TW, 16, 1, NW, 2, 0, ConvFamily::Bf16StoreWs, "tconvBF16ws_2x2_r" #R "x32_cb2_w" #NW, 0},
 #define UKBB_WSL_ENTRY(ID, R, NW) \
-    {ID, 3, 1, 32, R, WS_TW, 16, 1, NW, 1, 0, 6, "convBF16ws_3x3s1+logits_r" #R "x32_cb1_w" #NW, 2},
+    {ID, 3, 1, 32, R, WS_TW, 16, 1, NW, 1, 0, ConvFamily::Bf16StoreWs, "convBF16ws_3x3s1+logits_r" #R "x32_cb1_w" #NW, 2},
 #define UKBB_WR_ENTRY(ID, R, CB, NW) \
-    {ID, 3, 1, 32, R, WS_TW, 32, 1, NW, CB, 0, 6, "convBF16wr_3x3s1_r" #R "x32_cb" #CB "_w" #NW, 0},
+    {ID, 3, 1, 32, R, WS_TW, 32, 1, NW, CB, 0, ConvFamily::Bf16StoreWs, "convBF16wr_3x3s1_r" #R "x32_cb" #CB "_w" #NW, 0},
 static const ConvConfig g_ws_cfgs[] = {UKBB_WS_CONFIGS(UKBB_WS_ENTRY) UKBB_WSL_CONFIGS(UKBB_WSL_ENTRY) UKBB_WST_CONFIGS(UKBB_WST_ENTRY) UKBB_WR_CONFIGS(UKBB_WR_ENTRY)};
 
 // Order of the 4 x cout phase-major virtual channels (phase = 2 py + px, then channel) in the packed filter / bias of the transposed

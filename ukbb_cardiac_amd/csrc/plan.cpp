@@ -152,28 +152,27 @@ bool small_batch_tilings() { static const bool on = getenv("UKBB_SMALL_BATCH_TIL
 
 // A tuned tiling is reused for another image size only if its tiles still fit that size well.
 bool tile_fit_ok(const ConvConfig &c, int Ho, int Wo) {
-    const int th = c.th, tw = c.tw;
-    const double covered = (double)((Ho + th - 1) / th * th) * ((Wo + tw - 1) / tw * tw);
+    const double covered = (double)round_up(Ho, c.th) * round_up(Wo, c.tw);
     // Winograd kept its lead over the direct tilings down to 61 % region fill (12x13 maps, r01 sweep)
     // F(2x4) regions: at 61 % fill (12 x 13 maps) the F(2x2) kernel with its half regions (81 %) is as fast, at 74 % (44 x 52, 22 x 26) F(2x4) still wins by 2 %
-    return (double)Ho * Wo >= (is_wino24(c) ? 0.7 : c.pc == 4 ? 0.5 : 0.8) * covered;
+    return (double)Ho * Wo >= (is_wino24(c) ? 0.7 : is_wino(c) ? 0.5 : 0.8) * covered;
 }
 // Fallback preference (small tiles / high occupancy won everywhere in the sweep).
 const int g_pref[] = {4, 5, 18, 3, 11, 7, 31, 23, 22, 29, 27, 26};
 
-// bf16: 0 = fp32 tilings, 1 = bf16 operands / fp32 storage (pc 3), 2 = bf16 operands and storage (pc 5)
+// a bf16-operand tiling only in a bf16-operand plan, a bf16-storage tiling only in a bf16-storage plan, an fp32 tiling in either of the others
 bool cfg_valid(const ConvConfig &c, int ks, int stride, int c0, int c1, int cout, bool fused_first = false,
-               int bf16 = 0, int fuse = 0) {
+               Bf16Mode bf16 = Bf16Mode::None, int fuse = 0) {
     if (c.ks != ks || c.stride != stride) return false;
     if (c.fuse != fuse) return false;
-    if ((c.pc == 2 || c.pc == 7) != fused_first) return false;
-    if (c.pc == 7) {                                  // fused first layer + Winograd conv0_1: the 16 -> 16 stem of the fp32 FCN plans only
+    if (fuses_first(c) != fused_first) return false;
+    if (c.family == ConvFamily::FirstWino22) {        // fused first layer + Winograd conv0_1: the 16 -> 16 stem of the fp32 FCN plans only
         static const bool off = getenv("UKBB_NO_WINOGRAD_FIRST") != nullptr;    // A/B knob: the direct fused kernel (130-133)
         if (off || ks != 3 || stride != 1 || c0 != 16 || c1 != 0 || cout != 16) return false;
     }
-    if ((c.pc == 3) != (bf16 == 1) || (c.pc == 5 || c.pc == 6) != (bf16 == 2)) return false;
-    if (c.pc == 5 || c.pc == 6) cout = round_up(cout, 32);         // 16-channel layers run zero-padded on the 32-row MFMA
-    if (c.pc == 6) {                                  // weight-stationary: the Cout group's whole packed filter + the waves' rings in LDS
+    if ((c.family == ConvFamily::Bf16Operands) != (bf16 == Bf16Mode::Operands) || stores_bf16(c) != (bf16 == Bf16Mode::Storage)) return false;
+    cout = packed_cout(c, cout);
+    if (c.family == ConvFamily::Bf16StoreWs) {        // weight-stationary: the Cout group's whole packed filter + the waves' rings in LDS
         const int nch = (c0 + c1) / 16;
         if (stride != 1 || (c0 + c1) % 16) return false;
         if (ks == 2) {                                // transposed conv as 2x2 sub-pixel conv: cout = 4 x real channels (16, or multiples of 32)
@@ -185,7 +184,7 @@ bool cfg_valid(const ConvConfig &c, int ks, int stride, int c0, int c1, int cout
         if (cout % (32 * c.cb)) return false;
         return ws_lds_bytes_for(c, c0 + c1) <= 160 * 1024;
     }
-    if (c.pc == 4) {                                  // Winograd: 3x3 s1, 64-channel output groups, single source ok
+    if (is_wino(c)) {                                 // Winograd: 3x3 s1, 64-channel output groups, single source ok
         static const bool off = getenv("UKBB_NO_WINOGRAD") != nullptr;
         if (c.id == 306) {                            // image pairs with seam regions (maps with Ho % 8 == 4): only where UKBB_CONV_CFG names it -- at N = 64 its 384
             const char *e = getenv("UKBB_CONV_CFG");   // items leave half the CUs idle in the second round, and the plan must not depend on the batch (r04_notes.md)
@@ -197,12 +196,11 @@ bool cfg_valid(const ConvConfig &c, int ks, int stride, int c0, int c1, int cout
             if (c.wm == 2) { if (cout != 32) return false; }   // 32-channel items (307): the layers with exactly 32 output channels
             else if (cout % 64 || c0 + c1 < 32) return false;   // K = 32: the ConvLSTM gate convs (16 + 16 -> 64)
         }
-        return !off && !fused_first && ks == 3 && stride == 1 && cout % (16 * c.wm) == 0 && c0 % 16 == 0 && c1 % 16 == 0;
+        return !off && !fused_first && ks == 3 && stride == 1 && cout % cout_per_item(c) == 0 && c0 % 16 == 0 && c1 % 16 == 0;
     }
-    if ((c.pc == 2 || c.pc == 7) && cout != c.mb * c.cb * c.wm) return false;   // fused kernel stages its weights once: one Cout group
+    if (fuses_first(c) && cout != cout_per_item(c)) return false;  // fused kernel stages its weights once: one Cout group
     if (c.lds_bytes > 160 * 1024) return false;      // LDS per CU on gfx950
-    const int group = c.mb * c.cb * c.wm;
-    return !(cout % group || c0 % c.kc || c1 % c.kc);
+    return !(cout % cout_per_item(c) || c0 % c.kc || c1 % c.kc);
 }
 
 // Winograd regions are 8x16 (ids 300/301) or 16x8 pixels (302/303): take the orientation with fewer regions.
@@ -214,7 +212,7 @@ int wino_orient(int id, int Ho, int Wo) {
 }
 
 int choose_cfg_raw(const std::string &layer, int ks, int stride, int c0, int c1, int cout, int Ho, int Wo, int N,
-                   bool fused_first, int want_bf16, bool wino_first);
+                   bool fused_first, Bf16Mode want_bf16, bool wino_first);
 
 // Small batches (N <= SMALL_BATCH, e.g. the reference's own sess.run of one frame's 10 slices, deploy_network.py:103-111): the
 // deep levels have fewer work items than the chip has CUs, and a CU streaming an item's weights alone pulls only ~25-50 GB/s
@@ -231,8 +229,7 @@ int finer_sibling(int id, int ks, int stride, int c0, int c1, int cout, int Ho, 
     if (find_cfg(id, c)) return id;
     for (const auto &p : sib) {
         if (p[0] != id || find_cfg(p[1], f) || !cfg_valid(f, ks, stride, c0, c1, cout)) continue;
-        const long long tiles = (long long)((Ho + c.th - 1) / c.th) * ((Wo + c.tw - 1) / c.tw) * N;
-        const long long items = tiles * (cout / (c.pc == 4 ? 16 * c.wm : c.mb * c.cb * c.wm));
+        const long long items = (long long)map_tiles(c, Ho, Wo) * N * (cout / cout_per_item(c));
         if (items <= cus / 2) return p[1];      // at most half the CUs (of the planned device) at work: halve the item (r03 on 256 CUs: 160-210 items were faster left alone)
     }
     return id;
@@ -247,7 +244,7 @@ int pick_wino24(int id, int ks, int stride, int c0, int c1, int cout, int Ho, in
     for (int cand : {304, 305}) {
         ConvConfig c;
         if (find_cfg(cand, c) || !cfg_valid(c, ks, stride, c0, c1, cout) || !tile_fit_ok(c, Ho, Wo)) continue;
-        const long long items = (long long)N * ((Ho + c.th - 1) / c.th) * ((Wo + c.tw - 1) / c.tw) * (cout / 64);
+        const long long items = (long long)N * map_tiles(c, Ho, Wo) * (cout / 64);
         const long long rounds = (items + cus - 1) / cus;
         // makespan in units of an 8 x 16 region's work (an 8 x 32 item is two): the shorter wins -- that counts the padding columns of the
         // wider regions as well as the idle CUs of the last round
@@ -260,7 +257,7 @@ int pick_wino24(int id, int ks, int stride, int c0, int c1, int cout, int Ho, in
 
 // wino_first: the plan may run a fused first layer's conv0_1 as Winograd (tiling 134; plan_conv: fp32 FCN plans only)
 int choose_cfg(const std::string &layer, int ks, int stride, int c0, int c1, int cout, int Ho, int Wo, int N, int cus,
-               bool fused_first = false, int want_bf16 = 0, bool wino_first = false) {
+               bool fused_first = false, Bf16Mode want_bf16 = Bf16Mode::None, bool wino_first = false) {
     const int id = choose_cfg_raw(layer, ks, stride, c0, c1, cout, Ho, Wo, N, fused_first, want_bf16, wino_first);
     if (override_cfg(layer) >= 0) return id;
     return finer_sibling(wino_orient(pick_wino24(id, ks, stride, c0, c1, cout, Ho, Wo, N, cus), Ho, Wo), ks, stride, c0, c1, cout, Ho, Wo, N, cus);
@@ -281,39 +278,36 @@ const Tuned g_tuned_bfio[] = {
 };
 
 int choose_cfg_raw(const std::string &layer, int ks, int stride, int c0, int c1, int cout, int Ho, int Wo, int N,
-                   bool fused_first, int want_bf16, bool wino_first) {
-    if (want_bf16 == 2 && !fused_first && override_cfg(layer) < 0) {
+                   bool fused_first, Bf16Mode want_bf16, bool wino_first) {
+    if (want_bf16 == Bf16Mode::Storage && !fused_first && override_cfg(layer) < 0) {
         for (const Tuned &t : g_tuned_bfio) {
             if (t.ks != ks || t.stride != stride || t.cin != c0 + c1 || t.cout != cout) continue;
             for (int cand : {t.cfg, t.alt, t.alt2}) {
                 ConvConfig cc;
-                if (cand >= 0 && find_cfg(cand, cc) == 0 && cfg_valid(cc, ks, stride, c0, c1, cout, false, 2) && tile_fit_ok(cc, Ho, Wo)) return cand;
+                if (cand >= 0 && find_cfg(cand, cc) == 0 && cfg_valid(cc, ks, stride, c0, c1, cout, false, want_bf16) && tile_fit_ok(cc, Ho, Wo)) return cand;
             }
         }
     }
-    if (want_bf16 && !fused_first) {          // bf16 tilings first; fall back to fp32 where none fits (e.g. Cout = 16 with fp32 storage)
+    if (want_bf16 != Bf16Mode::None && !fused_first) {   // bf16 tilings first; fall back to fp32 where none fits (e.g. Cout = 16 with fp32 storage)
         const int forced_bf = override_cfg(layer);
         double best = 1e300; int best_id = -1;
         for (int i = 0; i < num_conv_configs(); ++i) {
             const ConvConfig &c = conv_config(i);
             if (!cfg_valid(c, ks, stride, c0, c1, cout, false, want_bf16)) continue;
             if (c.id == forced_bf) return c.id;
-            const int group = c.mb * c.cb * c.wm;
-            const int coutp = want_bf16 == 2 ? round_up(cout, 32) : cout;
-            const int tiles = ((Ho + c.th - 1) / c.th) * ((Wo + c.tw - 1) / c.tw);
             const int npb = (c.th * c.tw + c.mb - 1) / c.mb, pbw = (npb + c.wn - 1) / c.wn;
-            const double cost = (double)tiles * (coutp / group) * pbw * c.cb;
+            const double cost = (double)map_tiles(c, Ho, Wo) * (packed_cout(c, cout) / cout_per_item(c)) * pbw * c.cb;
             if (cost < best) { best = cost; best_id = c.id; }
         }
         if (best_id >= 0) return best_id;
-        if (want_bf16 == 2) return -1;        // bf16 storage has no fp32 fallback
+        if (want_bf16 == Bf16Mode::Storage) return -1;   // bf16 storage has no fp32 fallback
     }
     const int forced = override_cfg(layer);
     if (forced >= 0) {
         for (int i = 0; i < num_conv_configs(); ++i)
             if (conv_config(i).id == forced && cfg_valid(conv_config(i), ks, stride, c0, c1, cout, fused_first)) return forced;
     }
-    if (fused_first && wino_first && want_bf16 == 0) {
+    if (fused_first && wino_first && want_bf16 == Bf16Mode::None) {
         // conv0_1 as Winograd F(2x2) behind the fused first layer (kernels_conv.hip, conv_pc_kernel WINO): 64 MFMAs per consumer wave and
         // 16 x 16 tile instead of the direct form's 144, so even at 60-70 % tile fill it issues less than any direct tiling at 100 %
         ConvConfig cw;
@@ -352,18 +346,16 @@ int choose_cfg_raw(const std::string &layer, int ks, int stride, int c0, int c1,
     int best_id = -1;
     for (int i = 0; i < num_conv_configs(); ++i) {
         const ConvConfig &c = conv_config(i);
-        if (c.id == 306 || c.pc == 7 || !cfg_valid(c, ks, stride, c0, c1, cout, fused_first)) continue;
-        const int group = c.mb * c.cb * c.wm;
-        const int tiles = ((Ho + c.th - 1) / c.th) * ((Wo + c.tw - 1) / c.tw);
+        if (c.id == 306 || c.family == ConvFamily::FirstWino22 || !cfg_valid(c, ks, stride, c0, c1, cout, fused_first)) continue;
         const int npb = (c.th * c.tw + c.mb - 1) / c.mb;
         const int pbw = (npb + c.wn - 1) / c.wn;
         // matrix-pipe cycles per wave x workgroups = padded work (tile overhang + block rounding)
-        const double cyc = (double)pbw * c.cb * (ks * ks * (c0 + c1) / (c.mb == 32 ? 2 : 4)) * (c.mb == 32 ? 64 : 32);
-        double cost = (double)tiles * (cout / group) * cyc;
+        double cyc = (double)pbw * c.cb * (ks * ks * (c0 + c1) / (c.mb == 32 ? 2 : 4)) * (c.mb == 32 ? 64 : 32);
         // Winograd: one stage (16 input channels of one 8x16 region, 64 output channels) costs ~5.2k cycles
         // per CU measured; 5800 puts it on the scale of the direct estimate above (which ignores the direct
         // kernels' ~70 % matrix-pipe efficiency), calibrated on the three tuned shapes.
-        if (c.pc == 4) cost = (double)tiles * (cout / (16 * c.wm)) * ((c0 + c1) / 16) * (is_wino24(c) ? (c.tw == 32 ? 9300.0 : 4700.0) : c.wm == 4 ? 5800.0 : 3500.0);   // F(2x4): 256 / 128 pixels per stage
+        if (is_wino(c)) cyc = ((c0 + c1) / 16) * (is_wino24(c) ? (c.tw == 32 ? 9300.0 : 4700.0) : c.wm == 4 ? 5800.0 : 3500.0);   // F(2x4): 256 / 128 pixels per stage
+        double cost = (double)map_tiles(c, Ho, Wo) * (cout / cout_per_item(c)) * cyc;
         int rank = 12;
         for (int r = 0; r < (int)(sizeof(g_pref) / sizeof(g_pref[0])); ++r)
             if (g_pref[r] == c.id) { rank = r % 6; break; }
@@ -373,16 +365,6 @@ int choose_cfg_raw(const std::string &layer, int ks, int stride, int c0, int c1,
     return best_id;
 }
 
-// UKBB_PREC_BF16 on the aortic U-Net: bf16 operands AND bf16 activations in HBM between all layers (r03);
-// on the other graphs: bf16 operands, fp32 storage (r01).
-// r05: the U-Net of a UNet-LSTM handle takes the same bf16-storage plan (its last map, net['conv0_up'], feeds the ConvLSTM as bf16; the
-// LSTM then keeps gx and the hidden maps in bf16 as well, cell state and arithmetic fp32: run_bilstm)
-int bf16_mode(int kind, int precision) { return precision != 1 ? 0 : kind != UKBB_KIND_FCN ? 2 : 1; }
-// ... and with UKBB_PREC_BF16_STORE (FCN handles only; the engine refuses the code elsewhere) the FCN encoder takes the same bf16-storage
-// kernels: mode 2.  Its squeeze launches and head read the bf16 maps (kernels_head.hip) and keep G_l, logits, prob and pred in fp32.  What
-// UKBB_PREC_BF16 means on an FCN handle (mode 1, above) is pinned by recorded plans and graders and does not move.
-int plan_bf16_mode(int kind, int precision) { return kind == UKBB_KIND_FCN && precision == UKBB_PREC_BF16_STORE ? 2 : bf16_mode(kind, precision); }
-
 // bf16 storage: the fused variants of the level-0 tilings (ConvConfig::fuse: 1 = first layer in the staging, 2 = logits in the
 // epilogue), first fit in measured order; -1 if none fits (the plan then keeps that layer as a launch of its own).
 int pick_fused_bf_cfg(const std::string &lname, int ks, int stride, int c0, int c1, int cout, int Ho, int Wo, int fuse_bf) {
@@ -391,7 +373,7 @@ int pick_fused_bf_cfg(const std::string &lname, int ks, int stride, int c0, int 
     // measured order; fused first layer: tile-per-workgroup only (its persistent form was no faster, r03_notes.md)
     for (int cand : {forced, fuse_bf == 1 ? 296 : 404, fuse_bf == 1 ? 294 : 325, fuse_bf == 1 ? 295 : 324, fuse_bf == 1 ? -1 : 298, fuse_bf == 1 ? -1 : 297, fuse_bf == 1 ? -1 : 299}) {
         ConvConfig cc;
-        if (cand >= 0 && find_cfg(cand, cc) == 0 && cfg_valid(cc, ks, stride, c0, c1, cout, false, 2, fuse_bf) &&
+        if (cand >= 0 && find_cfg(cand, cc) == 0 && cfg_valid(cc, ks, stride, c0, c1, cout, false, Bf16Mode::Storage, fuse_bf) &&
             (cand == forced || tile_fit_ok(cc, Ho, Wo))) return cand;
     }
     return -1;
@@ -401,7 +383,7 @@ int pick_fused_bf_cfg(const std::string &lname, int ks, int stride, int c0, int 
 // on a device of `cus` compute units; 0 when the F(2x4) kernel does not apply.  Both shapes give identical bits; the choice sizes the
 // tile-padded gx / cell-state buffers, so it is part of the plan (PlanLayout::lstm_tile_cols).
 int lstm_region_cols(const ukbb_fcn_arch &a, int H, int W, int N, int cus) {
-    int cfg = choose_cfg_raw("lstm_fw", 3, 1, a.n_filter[0], a.same_dim, 4 * a.same_dim, H, W, N, false, 0, false);
+    int cfg = choose_cfg_raw("lstm_fw", 3, 1, a.n_filter[0], a.same_dim, 4 * a.same_dim, H, W, N, false, Bf16Mode::None, false);
     if (override_cfg("lstm_fw") < 0) cfg = pick_wino24(cfg, 3, 1, a.n_filter[0], a.same_dim, 4 * a.same_dim, H, W, N, cus);
     ConvConfig c;
     const bool have24 = cfg >= 0 && !find_cfg(cfg, c) && is_wino24(c) && c.wm == 4 && (c.tw == 32 || c.tw == 16);
@@ -443,8 +425,8 @@ Knobs read_knobs() {
 
 struct Planner {               // what the plan_* helpers below share
     const ukbb_fcn_arch &a;
-    const int bfm, n_hint, cus;      // bfm: bf16_mode of the plan
-    PlanLayout &L;
+    const int n_hint, cus;
+    PlanLayout &L;                   // L.mode is set before any helper runs
     std::vector<Spec> specs;
 
     int layer(const std::string &name) const {
@@ -453,7 +435,7 @@ struct Planner {               // what the plan_* helpers below share
         return -1;
     }
     int new_act(const std::string &name, size_t per_image, int channels = 0) {
-        L.acts.push_back({name, per_image, channels, bfm == 2 && channels > 0 ? 2 : 4});      // bf16 storage: the channel maps
+        L.acts.push_back({name, per_image, channels, L.mode.bfio() && channels > 0 ? 2 : 4});      // bf16 storage: the channel maps
         return (int)L.acts.size() - 1;
     }
 };
@@ -471,23 +453,23 @@ int plan_conv(Planner &p, const std::string &lname, int in0, int in1, int c1, in
     op.pad_x = std::max((op.Wo - 1) * stride + L.ks - W, 0) / 2;
     const int c0 = L.cin - c1;
     op.fused_first = fused_first;
-    const int fuse_bf = p.bfm != 2 ? 0 : fused_first ? 1 : fused_logits ? 2 : 0;
+    const int fuse_bf = !p.L.mode.bfio() ? 0 : fused_first ? 1 : fused_logits ? 2 : 0;
     // the Winograd form of the fused first layer (134) was measured on, and is taken by, the fp32 FCN plans only (UKBB_PREC_F32X3 included:
     // its convs are fp32); the U-Net / UNet-LSTM plans and the bf16-operand FCN plans keep the direct fused kernel (130-133)
-    const bool wino_first = fused_first && p.a.kind == UKBB_KIND_FCN && p.bfm == 0;
+    const bool wino_first = fused_first && p.a.kind == UKBB_KIND_FCN && p.L.mode.bf16 == Bf16Mode::None;
     if (fuse_bf) op.cfg = pick_fused_bf_cfg(lname, L.ks, stride, c0, c1, L.cout, op.Ho, op.Wo, fuse_bf);
-    else op.cfg = choose_cfg(lname, L.ks, stride, c0, c1, L.cout, op.Ho, op.Wo, p.n_hint, p.cus, fused_first, p.bfm, wino_first);
+    else op.cfg = choose_cfg(lname, L.ks, stride, c0, c1, L.cout, op.Ho, op.Wo, p.n_hint, p.cus, fused_first, p.L.mode.bf16, wino_first);
     op.fused_logits = fuse_bf == 2;
     if (op.cfg < 0) { set_error("no conv tiling for layer %s (ks %d stride %d cin %d+%d cout %d)", lname.c_str(), L.ks, stride, c0, c1, L.cout); return UKBB_EARCH; }
     ConvConfig c;
     find_cfg(op.cfg, c);
     op.out = p.new_act(lname, (size_t)op.Ho * op.Wo * L.cout, L.cout);
     op.macs_per_image = (double)op.Ho * op.Wo * L.ks * L.ks * L.cin * L.cout;
+    const double tiles = map_tiles(c, op.Ho, op.Wo);
     if (is_wino24(c)) {
         op.mfma_macs_per_image = op.macs_per_image * (24.0 / 72.0);   // F(2x4,3x3): 24 products per 8 outputs
-        const double regs = (double)((op.Ho + 7) / 8) * ((op.Wo + c.tw - 1) / c.tw);      // every region issues all its tile slots (c.tw / 4 x 4)
-        op.padded_macs_per_image = regs * c.tw * 24.0 * L.cin * L.cout;
-    } else if (c.pc == 4) {
+        op.padded_macs_per_image = tiles * c.tw * 24.0 * L.cin * L.cout;      // every 8-row region issues all its tile slots (c.tw / 4 x 4)
+    } else if (is_wino(c)) {
         op.mfma_macs_per_image = op.macs_per_image * (16.0 / 36.0);   // F(2x2,3x3): 16 products per 4 outputs
         // what the kernel ISSUES: every region runs two MFMA column blocks of 16 tile slots (one for a region whose lower half lies below
         // the map in the 64-channel form, kernels_wino.hip `half`), whatever part of its 4 x 8 (8 x 4) tiles the map fills
@@ -496,17 +478,15 @@ int plan_conv(Planner &p, const std::string &lname, int in0, int in1, int c1, in
         double slots = 0;
         for (int ry = 0; ry < regs_y; ++ry) slots += (double)regs_x * ((c.wm == 4 && ry * 2 * trY + trY >= op.Ho) ? 16 : 32);
         op.padded_macs_per_image = slots * 16.0 * L.cin * L.cout;
-    } else if (c.pc == 7) {
+    } else if (c.family == ConvFamily::FirstWino22) {
         // what the kernel issues: conv0_1 as F(2x2) (16 products per 4 outputs) + conv0_0 on the producers' MFMAs (K = 9 taps of 12
         // issued: three 16x16x4 per 16 halo pixels of every 18 x 18 halo tile)
-        const double tiles = (double)((op.Ho + c.th - 1) / c.th) * ((op.Wo + c.tw - 1) / c.tw);
         const double halo_blocks = (double)(((c.th + 2) * (c.tw + 2) + 15) / 16);
         const double first_macs = (double)op.Ho * op.Wo * 9 * L.cin;   // conv0_0: 1 -> L.cin channels
         op.mfma_macs_per_image = op.macs_per_image * (16.0 / 36.0) + first_macs;
         op.padded_macs_per_image = tiles * ((c.th / 2) * (c.tw / 2) * 16.0 * L.cin * L.cout + halo_blocks * 16 * 12 * L.cin);
-    } else if (c.pc <= 2) {                            // direct tilings: tiles x pixel blocks of the MFMA's N width
+    } else if (!packs_bf16(c)) {                       // direct fp32 tilings: tiles x pixel blocks of the MFMA's N width
         const int npb = (c.th * c.tw + c.mb - 1) / c.mb;
-        const double tiles = (double)((op.Ho + c.th - 1) / c.th) * ((op.Wo + c.tw - 1) / c.tw);
         op.padded_macs_per_image = tiles * npb * c.mb * L.ks * L.ks * (double)L.cin * L.cout;
     } else if (fused_first) {
         op.mfma_macs_per_image = op.macs_per_image;              // conv0_0 itself runs on the vector ALU
@@ -523,7 +503,7 @@ int plan_tconv(Planner &p, const std::string &lname, int in0, int H, int W, int 
     Op op;
     op.kind = OP_TCONV; op.name = lname; op.layer = li; op.in0 = in0;
     op.H = H; op.W = W; op.Ho = H; op.Wo = W; op.stride = 1; op.pad_y = 1; op.pad_x = 1;
-    op.cfg = choose_cfg(lname, 2, 1, L.cin, 0, 4 * L.cout, H, W, p.n_hint, p.cus, false, p.bfm);
+    op.cfg = choose_cfg(lname, 2, 1, L.cin, 0, 4 * L.cout, H, W, p.n_hint, p.cus, false, p.L.mode.bf16);
     if (op.cfg < 0) { set_error("no tiling for transposed conv %s", lname.c_str()); return UKBB_EARCH; }
     op.out = p.new_act(lname, (size_t)4 * H * W * L.cout, L.cout);
     op.macs_per_image = (double)H * W * 9 * L.cin * L.cout;
@@ -617,9 +597,9 @@ int layout_encoder(Planner &p, const Knobs &k, int H, int W, std::vector<int> &l
     const bool std0 = a.n_block[0] >= 2 && a.n_filter[0] == 16;
     // conv0_0 evaluated inside conv0_1's producers; bf16 storage: only if a fused tiling fits conv0_1 at this size (otherwise conv0_0
     // runs as its own launch, bf16 out)
-    const bool can_fuse = !k.no_fuse_first && std0 && (p.bfm != 2 || pick_fused_bf_cfg("conv0_1", 3, 1, 16, 0, 16, H, W, 1) >= 0);
+    const bool can_fuse = !k.no_fuse_first && std0 && (!p.L.mode.bfio() || pick_fused_bf_cfg("conv0_1", 3, 1, 16, 0, 16, H, W, 1) >= 0);
     // bf16 storage with the standard 1 -> 16 -> 16 stem: conv0_0 and conv0_1 as ONE launch of kernels_stem.hip
-    const bool stem = p.bfm == 2 && !k.no_fuse_stem && std0 && override_cfg("conv0_1") < 0;
+    const bool stem = p.L.mode.bfio() && !k.no_fuse_stem && std0 && override_cfg("conv0_1") < 0;
     // levels 1-4 of the standard filter pyramid go out as ONE launch after level 4 (sqg_multi_kernel)
     const bool merge = !k.side_stream && a.n_level == 5 && a.n_filter[1] == 32 && a.n_filter[2] == 64 && a.n_filter[3] == 128 && a.n_filter[4] == 256;
     int cur = -1, hh = H, ww = W;
@@ -695,7 +675,7 @@ int layout_decoder(Planner &p, const Knobs &k, int H, int W, const std::vector<i
     PlanLayout &L = p.L;
     char nm[64];
     // bf16 storage, level 0 with the standard two 16-channel convs: up0_0, up0_1, logits and softmax / argmax as ONE launch (kernels_tail.hip)
-    const bool tail = a.kind == UKBB_KIND_UNET && p.bfm == 2 && !k.no_fuse_tail && a.n_block[0] == 2 && a.n_filter[0] == 16 &&
+    const bool tail = a.kind == UKBB_KIND_UNET && p.L.mode.bfio() && !k.no_fuse_tail && a.n_block[0] == 2 && a.n_filter[0] == 16 &&
                       a.n_class >= 2 && a.n_class <= 4 && override_cfg("up0_0") < 0 && override_cfg("up0_1") < 0;
     int up = level_out[a.n_level - 1];
     for (int l = a.n_level - 2; l >= 0; --l) {
@@ -716,7 +696,7 @@ int layout_decoder(Planner &p, const Knobs &k, int H, int W, const std::vector<i
         for (int i = 0; i < a.n_block[l]; ++i) {
             snprintf(nm, sizeof nm, "up%d_%d", l, i);
             // bf16 storage: logits + softmax / argmax ride in the epilogue of the very last conv (its output is never stored)
-            const bool flg = a.kind == UKBB_KIND_UNET && p.bfm == 2 && !k.no_fuse_logits && l == 0 && i == a.n_block[0] - 1 &&
+            const bool flg = a.kind == UKBB_KIND_UNET && p.L.mode.bfio() && !k.no_fuse_logits && l == 0 && i == a.n_block[0] - 1 &&
                              i > 0 && a.n_filter[0] == 16 && pick_fused_bf_cfg(nm, 3, 1, 16, 0, 16, lh[0], lw[0], 2) >= 0;
             rc = (i == 0) ? plan_conv(p, nm, level_out[l], t, a.n_filter[l], lh[l], lw[l], 1, &x)
                           : plan_conv(p, nm, x, -1, 0, lh[l], lw[l], 1, &x, false, flg);
@@ -744,7 +724,7 @@ int layout_decoder(Planner &p, const Knobs &k, int H, int W, const std::vector<i
         const int cols24 = lstm_region_cols(a, H, W, p.n_hint, p.cus);
         // the bf16 plan's time steps run on launch_lstm_ws (kernels_ws.hip) and never touch the F(2x4) kernel: only the fp32 plan and the
         // bf16-storage Winograd A/B form need that tiling
-        if (!cols24 && (p.bfm != 2 || L.lstm_bf_wino)) {
+        if (!cols24 && (!L.mode.bfio() || L.lstm_bf_wino)) {
             set_error("the ConvLSTM needs the Winograd F(2x4) kernel (unset UKBB_NO_WINOGRAD / UKBB_NO_WINOGRAD24 / UKBB_CONV_CFG overrides)");
             return UKBB_EARCH;
         }
@@ -764,7 +744,7 @@ int layout_decoder(Planner &p, const Knobs &k, int H, int W, const std::vector<i
 void layout_split_range(const Planner &p, const Knobs &kn) {
     const ukbb_fcn_arch &a = p.a;
     PlanLayout &L = p.L;
-    const int k = kn.split_from ? atoi(kn.split_from) : (a.kind == UKBB_KIND_UNET && p.bfm == 0) ? 1 : 0;
+    const int k = kn.split_from ? atoi(kn.split_from) : (a.kind == UKBB_KIND_UNET && p.L.mode.bf16 == Bf16Mode::None) ? 1 : 0;
     if (k >= 1 && k < a.n_level) {
         // U-Net: conv{k}_0 .. up{k}_1; FCN (no decoder): conv{k}_0 .. the last encoder conv (the squeeze launches and the head follow unsplit)
         const std::string c0 = "conv" + std::to_string(k) + "_0";
@@ -784,9 +764,25 @@ void layout_split_range(const Planner &p, const Knobs &kn) {
 
 }  // namespace
 
+int plan_mode(const ukbb_fcn_arch &a, int precision, PlanMode &m, const char **why) {
+    m = PlanMode();
+    *why = "";
+    if (precision != UKBB_PREC_FP32 && precision != UKBB_PREC_BF16 && precision != UKBB_PREC_F32X3 && precision != UKBB_PREC_BF16_STORE) { *why = "bad precision"; return UKBB_EINVAL; }
+    if (a.kind == UKBB_KIND_TEMPORAL_UNET && precision == UKBB_PREC_BF16) { *why = "the Temporal-UNet's 3-D convolutions are built for fp32 only (no bf16 plan)"; return UKBB_EARCH; }
+    if (a.kind != UKBB_KIND_FCN && precision == UKBB_PREC_BF16_STORE) { *why = "UKBB_PREC_BF16_STORE is the FCN's bf16-storage mode; the U-Net kinds already store bf16 under UKBB_PREC_BF16"; return UKBB_EARCH; }
+    // UKBB_PREC_BF16 means operands only on an FCN handle (pinned by recorded plans and graders) and storage on the U-Net kinds; with
+    // UKBB_PREC_BF16_STORE the FCN encoder takes the same bf16-storage kernels (squeeze and head read the bf16 maps and stay fp32)
+    if (precision == UKBB_PREC_BF16) m.bf16 = a.kind == UKBB_KIND_FCN ? Bf16Mode::Operands : Bf16Mode::Storage;
+    if (precision == UKBB_PREC_BF16_STORE) m.bf16 = Bf16Mode::Storage;
+    m.head_x3 = precision == UKBB_PREC_F32X3;
+    return UKBB_OK;
+}
+
 int layout_plan(const ukbb_fcn_arch &a, int precision, int H, int W, int n_hint, int cus, PlanLayout &L) {
     L = PlanLayout();
-    Planner p{a, plan_bf16_mode(a.kind, precision), n_hint, cus, L, {}};
+    const char *refused;
+    if (const int rc = plan_mode(a, precision, L.mode, &refused)) { set_error("%s", refused); return rc; }
+    Planner p{a, n_hint, cus, L, {}};
     std::string why;
     if (!arch_specs(a, p.specs)) { set_error("malformed architecture descriptor"); return UKBB_EARCH; }
     if (!supported(a, why)) { set_error("unsupported architecture: %s", why.c_str()); return UKBB_EARCH; }
@@ -808,7 +804,6 @@ int layout_plan(const ukbb_fcn_arch &a, int precision, int H, int W, int n_hint,
         rc = layout_decoder(p, k, H, W, level_out, lh, lw);
         if (rc) return rc;
     }
-    L.bfio = p.bfm == 2;
     layout_split_range(p, k);
     return UKBB_OK;
 }
@@ -876,8 +871,8 @@ CineUnits cine_units_from(const PlanLayout &L, const ukbb_fcn_arch &a, int H, in
     u.kind = a.kind; u.T = a.fc; u.n_class = a.n_class; u.HW = (size_t)H * W;
     for (const ActSpec &s : L.acts) u.act_frame += s.per_image;
     if (a.kind != UKBB_KIND_UNET_LSTM) return u;
-    const bool wsf = L.bfio && !L.lstm_bf_wino;       // the direct-conv bf16 ConvLSTM (kernels_ws.hip); else the F(2x4) kernel's regions
-    u.esz = L.bfio ? 2 : 4;
+    const bool wsf = L.mode.bfio() && !L.lstm_bf_wino;       // the direct-conv bf16 ConvLSTM (kernels_ws.hip); else the F(2x4) kernel's regions
+    u.esz = L.mode.bfio() ? 2 : 4;
     u.h_item = u.HW * a.same_dim;
     u.gx_frame = wsf ? lstm_ws_gx_elems(H, W) : wino24_lstm_gx_floats(H, W, L.lstm_tile_cols);
     u.c_item = wsf ? lstm_ws_c_floats(H, W) : wino24_lstm_c_floats(H, W, L.lstm_tile_cols);

@@ -48,11 +48,23 @@ struct ActSpec { std::string name; size_t per_image; int channels; int esz = 4; 
 // and the recorded footprints count that); an FCN plan allocates what it stores.
 inline size_t act_alloc_esz(const ukbb_fcn_arch &a, const ActSpec &s) { return a.kind == UKBB_KIND_FCN ? (size_t)s.esz : 4; }
 
+// What a precision code means for a plan of one architecture.  Storage: bf16 operands AND every activation between layers bf16 in HBM
+// (stores_bf16 tilings; an FCN plan: the encoder maps, G_l stays fp32; a UNet-LSTM keeps gx and the hidden maps in bf16 as well)
+enum class Bf16Mode { None, Operands /* fp32 maps in HBM, ConvFamily::Bf16Operands */, Storage };
+struct PlanMode {
+    Bf16Mode bf16 = Bf16Mode::None;
+    bool head_x3 = false;                     // UKBB_PREC_F32X3: the FCN head's out0 / out1 from three bf16 pieces per operand (its convs are fp32)
+    bool bfio() const { return bf16 == Bf16Mode::Storage; }
+};
+// THE list of precision codes and of the (kind, code) pairs the engine refuses.  UKBB_OK; UKBB_EINVAL for an unknown code; UKBB_EARCH
+// for a refused pair, *why then the reason (callers put their own prefix in front of it).
+int plan_mode(const ukbb_fcn_arch &a, int precision, PlanMode &m, const char **why);
+
 struct PlanLayout {
     std::vector<Op> ops;
     std::vector<ActSpec> acts;
     int feat_buf = -1;                        // UNet-LSTM: activation index of net['conv0_up']
-    bool bfio = false;                        // every activation between layers is stored as bf16 (an FCN plan: the encoder maps; G_l stays fp32)
+    PlanMode mode;
     int lstm_tile_cols = 0;                   // region shape of the fused gate-conv / cell kernel (kernels_wino24.hip): 32 | 16
     bool lstm_bf_wino = false;                // UKBB_LSTM_BF16_WINOGRAD: fp32 Winograd arithmetic on bf16 storage (A/B form)
     bool lstm_bf_hoist = true;                // false (UKBB_LSTM_BF16_UNHOIST): the bf16 time steps re-multiply x (r06 experiment)
@@ -62,10 +74,9 @@ struct PlanLayout {
 };
 
 constexpr int SMALL_BATCH = 16;
-inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 int find_cfg(int id, ConvConfig &out);        // 0: found
 
-// The plan for batches of up to n_hint images of H x W on a device of `cus` compute units.  UKBB_OK, or UKBB_EARCH with the error text set.
+// The plan for batches of up to n_hint images of H x W on a device of `cus` compute units.  UKBB_OK, or plan_mode's code / UKBB_EARCH with the error text set.
 int layout_plan(const ukbb_fcn_arch &a, int precision, int H, int W, int n_hint, int cus, PlanLayout &L);
 
 // ---- forward_cine scratch planner ---------------------------------------------------

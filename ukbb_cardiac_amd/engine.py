@@ -154,8 +154,7 @@ class Engine:
         """'fp32' (default), 'bf16' (bf16 MFMA inputs, fp32 accumulate; BASELINE config 5), 'f32x3' (fp32 results from three
         bf16 pieces per operand on the dense matrix cores; FCN head so far; include/ukbb_fcn.h UKBB_PREC_F32X3) or 'bf16_store'
         (FCN models only: bf16 operands and bf16 encoder maps in HBM, squeeze and head in fp32; UKBB_PREC_BF16_STORE)."""
-        code = {'fp32': 0, 'bf16': 1, 'f32x3': 2, 'bf16_store': 3}[precision]
-        _lib.check(_lib.lib.ukbb_fcn_set_precision(self._h, code), 'ukbb_fcn_set_precision')
+        _lib.check(_lib.lib.ukbb_fcn_set_precision(self._h, _PLAN_PREC[precision]), 'ukbb_fcn_set_precision')
 
     def set_scratch_budget(self, nbytes: int):
         """Bound the device memory ``run_cine`` / ``run_cine_device`` may hold for their per-cine scratch (0 = no budget, the default):
@@ -240,7 +239,7 @@ class Engine:
         return buf
 
 
-_PREC = {'fp32': 0, 'bf16': 1}
+_PREC = {'fp32': 0, 'bf16': 1}              # what the cine queries take: any other name is a KeyError
 
 
 def cine_scratch_bytes(arch: ModelArch, precision: str, n_frames: int, height: int, width: int, time_step: int = 1, budget: int = 0) -> int:
@@ -262,7 +261,7 @@ def cine_chunk_windows(arch: ModelArch, precision: str, n_frames: int, height: i
     return int(_lib.lib.ukbb_fcn_cine_chunk_windows(C.byref(a), _PREC[precision], int(n_frames), int(height), int(width), int(time_step), int(budget)))
 
 
-_PLAN_PREC = {'fp32': 0, 'bf16': 1, 'f32x3': 2, 'bf16_store': 3}
+_PLAN_PREC = {'fp32': 0, 'bf16': 1, 'f32x3': 2, 'bf16_store': 3}       # the UKBB_PREC_* codes of include/ukbb_fcn.h (set_precision, plan_layout)
 _OP_FIELDS = ('cfg', 'H', 'W', 'Ho', 'Wo', 'stride', 'in0', 'in1', 'out')
 
 
