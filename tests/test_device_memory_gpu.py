@@ -19,6 +19,7 @@ No tolerance anywhere: bits, and guard bytes."""
 import ctypes as C
 import functools
 import os
+import re
 
 import numpy as np
 import pytest
@@ -273,6 +274,79 @@ def test_poison_is_read_back_and_a_damaged_guard_is_reported():
                                                       'io_prob front -1 -1']), report
         out = eng.run(_image((2, 32, 48)))                              # a damaged guard harms nothing: the handle still runs
         assert np.isfinite(out['prob']).all() and out['prob'].std() > 0
+
+
+# ---- e2. the handle's own buffers, every name -------------------------------------------------------------------------------------
+
+HANDLE_BUFS = ('io_image', 'io_logits', 'io_prob', 'io_pred', 'lstm_gx', 'lstm_c1', 'lstm_h1', 'lstm_c', 'lstm_hall', 'lstm_probw', 'lstm_aux',
+               'lstm_img', 't3d_aux', 't3d_probw')
+KEPT = ('io_image', 'lstm_aux', 't3d_aux')                          # what a call does not rewrite before it reads it: poison() leaves them
+RAW = {'lstm:h1': 'lstm_h1', 'lstm:hall': 'lstm_hall', 'lstm:gx': 'lstm_gx', 'lstm:c1': 'lstm_c1', 'lstm:c': 'lstm_c'}
+
+
+def _payload_bytes(eng, name):
+    """The payload bytes of the buffer ``name``, None if the handle knows the name and has not allocated it: from the refusal to
+    damage offset 0, which lies in no guard.  An unknown name fails here."""
+    with pytest.raises(Exception) as ei:
+        eng.damage_guard(name, 0)
+    msg = str(ei.value)
+    assert 'no buffer named' not in msg, msg
+    if "buffer '%s' is not allocated" % name in msg:
+        return None
+    m = re.search(r"is in no guard of '%s' \(payload (\d+) bytes" % re.escape(name), msg)
+    assert m, msg
+    return int(m.group(1))
+
+
+def _fcn_calls(eng):
+    eng.run(_image((1, 48, 16)), want_logits=True)                   # the host-array forward stages its image and all three outputs
+    return 1, 48, 16
+
+
+def _lstm_calls(eng):
+    from ukbb_cardiac_amd import engine
+    eng.run_seq(_image((1, 9, 16, 48)))
+    sizes = {raw: eng.activation(raw).size * 4 for raw in RAW}      # the raw working buffers answer after a sequence call
+    assert all(sizes.values()), sizes
+    assert sizes == {raw: _payload_bytes(eng, buf) for raw, buf in RAW.items()}
+    low = engine.cine_min_scratch_bytes(eng.arch, 'fp32', 13, 16, 48, 1)
+    assert 0 < engine.cine_chunk_windows(eng.arch, 'fp32', 13, 16, 48, 1, low) < 13      # chunks: the frame run goes through lstm_img
+    eng.set_scratch_budget(low)
+    eng.run_cine(_image((13, 16, 48)))
+    return 13, 16, 48
+
+
+def _t3d_calls(eng):
+    eng.run_cine(_image((13, 16, 48)))
+    return 13 * 9, 16, 48                                            # every window in one chunk
+
+
+@pytest.mark.parametrize('model,calls,allocated', [
+    ('FCN_sa', _fcn_calls, ('io_image', 'io_logits', 'io_prob', 'io_pred')),
+    # lstm_probw stands in for a NULL prob of ukbb_fcn_forward_seq, and Engine.run_seq always passes prob: none of engine.py's calls
+    # allocates it, so on every handle here the name is known and "is not allocated"
+    ('UNet-LSTM_ao', _lstm_calls, ('lstm_gx', 'lstm_c1', 'lstm_h1', 'lstm_c', 'lstm_hall', 'lstm_aux', 'lstm_img')),
+    ('Temporal-UNet_ao', _t3d_calls, ('t3d_aux', 't3d_probw'))])
+def test_every_handle_buffer_is_named_guarded_and_poisoned(model, calls, allocated):
+    """The 14 buffers a handle owns besides its weights and activation maps, under the names check_guards reports them: every handle
+    knows all 14 names, the calls above allocate the listed ones (each of the 14 but lstm_probw on some handle) and a damaged back
+    guard of each is reported under its name; poison() refills the allocated ones a call rewrites and the activation maps."""
+    import torch
+    from ukbb_cardiac_amd import engine
+    with _engine(model, PATTERNS[0]) as eng:                          # a throw-away handle: its guards end up damaged
+        shape = calls(eng)                                            # the largest batch the handle planned for
+        _guards_intact(eng, model)
+        size = {name: _payload_bytes(eng, name) for name in HANDLE_BUFS}
+        assert tuple(name for name in HANDLE_BUFS if size[name] is not None) == allocated, size
+        cus = torch.cuda.get_device_properties(0).multi_processor_count
+        maps = ['act%d%s' % (i, ':' + a['name'] if a['name'] else '') for i, a in enumerate(engine.plan_layout(eng.arch, 'fp32', *shape, cus)['acts'])]
+        n_maps = sum(_payload_bytes(eng, name) is not None for name in maps)
+        assert n_maps == len(maps) > 0
+        assert eng.poison(PATTERNS[1]) == len([name for name in allocated if name not in KEPT]) + n_maps
+        for name in allocated:
+            eng.damage_guard(name, size[name])
+        bad, report = eng.check_guards()
+        assert bad == len(allocated) and sorted(report.splitlines()) == sorted('%s back %d %d' % (name, size[name], size[name]) for name in allocated), report
 
 
 # ---- f. caller-owned outputs ----------------------------------------------------------------------------------------------------------

@@ -77,7 +77,11 @@ struct DevBuf {
     float *p = nullptr;
     size_t n = 0;
     const GuardMode *guard = nullptr;       // the owning handle's mode (NULL / off: plain allocations)
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete; DevBuf &operator=(const DevBuf &) = delete;   // owns p
     ~DevBuf() { release(); }
+    static size_t units(size_t bytes) { return (bytes + 3) / 4; }   // n counts floats: the 4-byte units that hold `bytes` (bf16 maps, int / double tables)
+    hipError_t ensure_bytes(size_t bytes) { return ensure(units(bytes)); }
     bool guarded() const { return guard && guard->on; }
     void release() {
         if (p) (void)hipFree(guarded() ? reinterpret_cast<char *>(p) - GUARD_BYTES : reinterpret_cast<char *>(p));
@@ -114,6 +118,40 @@ struct DevBuf {
     }
 };
 
+// element k of a buffer whose stored elements take esz bytes (2: bf16; the pointers travel as float * either way)
+float *at(float *p, size_t k, size_t esz) { return reinterpret_cast<float *>(reinterpret_cast<char *>(p) + k * esz); }
+
+struct ActMap {               // one activation map of the plan's workspace
+    DevBuf buf;
+    size_t per_image = 0;     // elements per image at the planned H,W
+    int esz = 4, alloc_esz = 4;   // bytes of a stored element (2: bf16) / bytes the workspace holds per element (plan.h act_alloc_esz)
+    int ch = 0;               // channels of the map (0: not a channel map); bf16 plans store maps with C > 16 channel-blocked
+    std::string name;
+    float *image(int n0) const { return at(buf.p, (size_t)n0 * per_image, esz); }
+    size_t units(int n) const { return DevBuf::units(per_image * (size_t)n * alloc_esz); }   // what buf.ensure takes for n images
+};
+
+struct BoundOp : Op {         // the planner's op and the device pointers its launch takes, resolved by materialize_plan
+    explicit BoundOp(Op op) : Op(std::move(op)) {}
+    const float *wpk = nullptr, *bias = nullptr;                  // packed weights / bias of the op's own layer
+    const float *wph[4] = {nullptr, nullptr, nullptr, nullptr};   // OP_TCONV3D: packed weights of the 4 sub-pixel phases
+    const float *sq_w_s[4] = {}, *sq_b_s[4] = {}, *sq_w_g[4] = {};   // OP_SQG ([0]) / OP_SQG_MULTI (levels 1..4): squeeze matrix, its bias, out0's slice
+};
+
+// The parameters ops share or the ConvLSTM stages read: bound by bind_op / bind_lstm for what the current plan launches, null otherwise.
+struct Params {
+    const float *conv0_w, *conv0_b, *conv0_1_b, *up0_0_b, *up0_1_b, *logits_w, *logits_b;
+    const float *stem_wA0, *stem_wA1, *tail_wA0, *tail_wA1;
+    const float *head_w_s0, *head_b_s0, *head_w_o0, *head_b_o0, *head_w_o1, *head_b_o1, *head_w_o1x3, *head_w_o0x3, *head_w_lg;
+    struct { const float *wx, *bx, *wh[2]; } lstm[2];             // ConvLSTM filters per form ([0] fp32 Winograd, [1] bf16 direct) and direction
+    const float *lstm_wxh[2];                                     // ... un-hoisted bf16 time steps, per direction
+    const float *lstm_out_w, *lstm_out_b;
+};
+
+// A row of HANDLE_BUFS (behind the handle).  name: in the guard reports; rewritten: a call rewrites it before it reads it, so ukbb_fcn_debug_poison may refill
+// it (not: the staged input, tables uploaded once per shape); raw: the name under which ukbb_fcn_get_activation hands it out raw (NULL: it does not)
+struct HandleBuf { const char *name; DevBuf ukbb_fcn_handle::*buf; bool rewritten; const char *raw; };
+
 }  // namespace
 
 struct ukbb_fcn_handle {
@@ -124,36 +162,29 @@ struct ukbb_fcn_handle {
     std::map<std::string, int> layer_index;
 
     // device-side parameters
-    std::map<std::string, std::unique_ptr<DevBuf>> dev;   // keyed by "<layer>/<what>"
+    std::map<std::string, std::unique_ptr<DevBuf>> dev;   // keyed by "<layer>/<what>": the owner; launches read the pointers below
+    Params par{};                             // bound when a plan is materialised
 
     // activation workspace
-    std::vector<std::unique_ptr<DevBuf>> act;
-    std::vector<size_t> act_per_image;        // elements per image at the planned H,W
-    std::vector<int> act_esz, act_alloc_esz;  // bytes of a stored element (2: bf16) / bytes the workspace holds per element (plan.h act_alloc_esz)
-    std::vector<int> act_ch;                  // channels of the map (0: not a channel map); bf16 plans store maps with C > 16 channel-blocked
-    std::vector<std::string> act_name;
+    std::vector<ActMap> acts;
     DevBuf io_image, io_logits, io_prob, io_pred;   // staging for forward_host
 
     // plan
     int precision = UKBB_PREC_FP32;           // the code the next plan is built for (ukbb_fcn_set_precision)
-    PlanMode mode;                            // what the CURRENT plan's code means for this architecture (plan.h plan_mode)
+    PlanLayout plan;                          // the CURRENT plan as layout_plan decided it (plan.h); its ops are bound in `ops`, its acts materialised in `acts`
     int plan_h = 0, plan_w = 0, cap_n = 0;
     bool plan_small = false;                  // plan built with the small-batch tilings
     int plan_n = 0;                           // ... for this largest batch
     int max_n = 0;                            // largest batch this handle was asked for (reserve / forward): the small-batch plan is
                                               // used only while that stays <= SMALL_BATCH, so a large-batch caller's tail batches do
                                               // not flip the plan (a rebuild re-allocates the workspace) back and forth
-    std::vector<Op> ops;
+    std::vector<BoundOp> ops;
     CineUnits cine;                           // what forward_cine holds per frame / window of this plan (plan.h)
     int last_n = 0;
 
     // UNet-LSTM (kind 2)
-    int feat_buf = -1;                        // activation index of net['conv0_up']
-    bool lstm_bf_hoist = true;                // bf16 time steps read the hoisted gx (r05; default) -- false (UKBB_LSTM_BF16_UNHOIST at plan build): they re-multiply x (r06 experiment)
-    bool lstm_bf_wino = false;                // UKBB_LSTM_BF16_WINOGRAD at plan build: fp32 Winograd arithmetic on bf16 storage (A/B form)
     bool lstm_bw_zero = false;                // the backward cell's kernel and bias are all zero (the single-direction head Conv_LSTM of network_ao.py:214-252 embedded by
                                               // weights.embed_unidirectional_lstm): its hidden maps are exactly zero, run_bilstm clears them instead of running its time steps
-    int lstm_tile_cols = 0;                   // region shape of the fused gate-conv / cell kernel (kernels_wino24.hip): 32 | 16
     // lstm_gx / lstm_c1 / lstm_h1: per direction and FRAME (the x pass); lstm_c: per window; lstm_hall: per direction, step and window
     DevBuf lstm_gx, lstm_c1, lstm_h1, lstm_c, lstm_hall, lstm_probw, lstm_aux;   // lstm_aux: int maps / orders / double weights (raw bytes)
     long long lstm_aux_key = -1;              // which tables lstm_aux holds (shape-keyed, uploaded once per shape)
@@ -172,8 +203,6 @@ struct ukbb_fcn_handle {
     // side stream for kernels that only feed the head (sqg_l): fork after level l, join before the head
     hipStream_t side = nullptr, side2 = nullptr;
     hipEvent_t ev_split_fork = nullptr, ev_split_join = nullptr;
-    int debug_first_op = 0, debug_last_op = 1 << 30;   // UKBB_DEBUG_OPS="first,last" at plan build: run_plan launches only these ops
-    int split_first = -1, split_last = -2;      // op range run as two half-batch chains (UKBB_SPLIT_FROM at plan build)
     std::vector<hipEvent_t> ev_fork, ev_join;
 
     // timing
@@ -184,13 +213,7 @@ struct ukbb_fcn_handle {
     std::vector<int64_t> t_cnt;
     bool ev_pending = false;
 
-    // the handle's own buffers by name (weights and activation maps are listed by guard_bufs)
-    std::vector<std::pair<const char *, DevBuf *>> named_bufs() {
-        return {{"io_image", &io_image}, {"io_logits", &io_logits}, {"io_prob", &io_prob}, {"io_pred", &io_pred}, {"lstm_gx", &lstm_gx}, {"lstm_c1", &lstm_c1},
-                {"lstm_h1", &lstm_h1}, {"lstm_c", &lstm_c}, {"lstm_hall", &lstm_hall}, {"lstm_probw", &lstm_probw}, {"lstm_aux", &lstm_aux}, {"lstm_img", &lstm_img},
-                {"t3d_aux", &t3d_aux}, {"t3d_probw", &t3d_probw}};
-    }
-    ukbb_fcn_handle() { for (auto &kv : named_bufs()) kv.second->guard = &guard; }
+    ukbb_fcn_handle();                        // wires the guard mode into the buffers of HANDLE_BUFS
     ~ukbb_fcn_handle() {
         for (auto e : ev) (void)hipEventDestroy(e);
         if (ev_split_fork) (void)hipEventDestroy(ev_split_fork);
@@ -202,11 +225,32 @@ struct ukbb_fcn_handle {
     }
 };
 
+// THE list of the DevBufs a handle owns besides its parameters (dev) and its activation maps (acts): each is guarded, named and counted as scratch.
+static const HandleBuf HANDLE_BUFS[] = {
+    {"io_image", &ukbb_fcn_handle::io_image, false, nullptr},  {"io_logits", &ukbb_fcn_handle::io_logits, true, nullptr},
+    {"io_prob", &ukbb_fcn_handle::io_prob, true, nullptr},     {"io_pred", &ukbb_fcn_handle::io_pred, true, nullptr},
+    {"lstm_gx", &ukbb_fcn_handle::lstm_gx, true, "lstm:gx"},   {"lstm_c1", &ukbb_fcn_handle::lstm_c1, true, "lstm:c1"},
+    {"lstm_h1", &ukbb_fcn_handle::lstm_h1, true, "lstm:h1"},   {"lstm_c", &ukbb_fcn_handle::lstm_c, true, "lstm:c"},
+    {"lstm_hall", &ukbb_fcn_handle::lstm_hall, true, "lstm:hall"}, {"lstm_probw", &ukbb_fcn_handle::lstm_probw, true, nullptr},
+    {"lstm_aux", &ukbb_fcn_handle::lstm_aux, false, nullptr},  {"lstm_img", &ukbb_fcn_handle::lstm_img, true, nullptr},
+    {"t3d_aux", &ukbb_fcn_handle::t3d_aux, false, nullptr},    {"t3d_probw", &ukbb_fcn_handle::t3d_probw, true, nullptr},
+};
+ukbb_fcn_handle::ukbb_fcn_handle() { for (const HandleBuf &b : HANDLE_BUFS) (this->*b.buf).guard = &guard; }
+
 namespace {
 
+// THE search of h->dev, for the packers ("is it on the device yet": NULL) and find_param.  Nothing a forward runs through calls it.
 const float *dev_ptr(ukbb_fcn_handle *h, const std::string &key) {
     auto it = h->dev.find(key);
     return it == h->dev.end() ? nullptr : it->second->p;
+}
+
+// The device parameter `key` for `who` (an op, a layer or a stage of the plan being materialised): a missing one is an error here, never a null kernel argument.
+int find_param(ukbb_fcn_handle *h, const std::string &key, const std::string &who, const float **out) {
+    *out = dev_ptr(h, key);
+    if (*out) return UKBB_OK;
+    set_error("plan: %s needs the device parameter '%s', which the handle does not hold", who.c_str(), key.c_str());
+    return UKBB_EARCH;
 }
 
 int upload(ukbb_fcn_handle *h, const std::string &key, const std::vector<float> &v) {
@@ -217,7 +261,7 @@ int upload(ukbb_fcn_handle *h, const std::string &key, const std::vector<float> 
 }
 
 // ---- plan: materialise a PlanLayout (plan.h) on the device -------------------------------------------------------------
-int ensure_packed(ukbb_fcn_handle *h, int layer, const ConvConfig &c, const float **wpk) {
+int ensure_packed(ukbb_fcn_handle *h, int layer, const ConvConfig &c, const float **wpk, const float **bias) {
     const HostLayer &L = h->layers[layer];
     char key[128];
     const int coutp = packed_cout(c, L.cout);
@@ -256,8 +300,8 @@ int ensure_packed(ukbb_fcn_handle *h, int layer, const ConvConfig &c, const floa
         int rc = upload(h, L.name + "/bias_pad", bp);
         if (rc) return rc;
     }
-    *wpk = dev_ptr(h, key);
-    return UKBB_OK;
+    const int rc = find_param(h, key, L.name, wpk);
+    return rc ? rc : find_param(h, L.name + (coutp != L.cout ? "/bias_pad" : "/bias"), L.name, bias);
 }
 
 // conv2d_transpose 3x3 s2 + BN + ReLU as a 2x2 sub-pixel conv (kernels.h, tconv_as_conv2x2): packed weights and the bias of the 4 phases
@@ -290,9 +334,8 @@ int ensure_packed_tconv(ukbb_fcn_handle *h, int layer, const ConvConfig &c, cons
         rc = upload(h, bkey, b4);
         if (rc) return rc;
     }
-    *wpk = dev_ptr(h, key);
-    *bias = dev_ptr(h, bkey);
-    return UKBB_OK;
+    const int rc = find_param(h, key, L.name, wpk);
+    return rc ? rc : find_param(h, bkey, L.name, bias);
 }
 
 // Temporal-UNet (kind 3), kernels_conv3d.hip:
@@ -324,9 +367,8 @@ int ensure_packed_stem(ukbb_fcn_handle *h) {
     std::vector<float> p0((size_t)64 * 4), dummy((size_t)9 * 64 * 4), p1((size_t)5 * 64 * 4), w0z((size_t)9 * 32 * 16, 0.f);
     pack_stem_weights(L0.w.data(), p0.data());
     pack_tail_weights(w0z.data(), L1.w.data(), dummy.data(), p1.data());
-    int rc = upload(h, "stem/wA0", p0);
-    if (rc) return rc;
-    return upload(h, "stem/wA1", p1);
+    const int rc = upload(h, "stem/wA1", p1);
+    return rc ? rc : upload(h, "stem/wA0", p0);            // last: its key stands for the pair (above)
 }
 
 // bf16 storage: up0_0, up0_1 and the logits as one launch (kernels_tail.hip)
@@ -335,114 +377,140 @@ int ensure_packed_tail(ukbb_fcn_handle *h) {
     const HostLayer &L0 = h->layers[h->layer_index.at("up0_0")], &L1 = h->layers[h->layer_index.at("up0_1")];
     std::vector<float> p0((size_t)9 * 64 * 4), p1((size_t)5 * 64 * 4);
     pack_tail_weights(L0.w.data(), L1.w.data(), p0.data(), p1.data());
-    int rc = upload(h, "tail/wA0", p0);
-    if (rc) return rc;
-    return upload(h, "tail/wA1", p1);
+    const int rc = upload(h, "tail/wA1", p1);
+    return rc ? rc : upload(h, "tail/wA0", p0);            // last: its key stands for the pair (above)
 }
 
-// ConvLSTM packed filters: the x rows of both directions as ONE 128-channel conv (groups = directions), the h rows per direction
+// ConvLSTM packed filters: the x rows of both directions as ONE 128-channel conv (groups = directions), the h rows per direction; in the
+// fp32 Winograd form and the bf16 form (kernels_ws.hip, ws_main LS: direct 3x3 conv on the bf16 matrix instruction, its own channel order)
 int ensure_packed_lstm(ukbb_fcn_handle *h) {
     if (dev_ptr(h, "lstm/wx")) return UKBB_OK;
-    const ukbb_fcn_arch &a = h->arch;
-    const size_t per = (size_t)24 * 16 * 64;
-    std::vector<float> wx(2 * per), bx(2 * 64), wh(per);
-    int d = 0;
-    for (const char *nm2 : {"lstm_fw", "lstm_bw"}) {
+    const int nf0 = h->arch.n_filter[0];
+    const size_t per = (size_t)24 * 16 * 64, perb = (size_t)9 * 16 * 64 / 2;          // perb: dwords
+    std::vector<float> wx(2 * per), bx(2 * 64), wh(per), wxb(2 * perb), bxb(2 * 64), whb(perb);
+    int rc = UKBB_OK, d = 0;
+    for (const std::string nm2 : {"lstm_fw", "lstm_bw"}) {
         const HostLayer &L = h->layers[h->layer_index.at(nm2)];
         if (L.cin != 32 || L.cout != 64 || L.ks != 3) { set_error("ConvLSTM gate kernel must be 3x3x(16+16)x64"); return UKBB_EARCH; }
         pack_lstm_gate_weights(L.w.data(), L.cin, 0, L.b.data(), wx.data() + d * per, bx.data() + d * 64);
-        pack_lstm_gate_weights(L.w.data(), L.cin, a.n_filter[0], nullptr, wh.data(), nullptr);
-        int rc = upload(h, std::string(nm2) + "/wh", wh);
-        if (rc) return rc;
-        ++d;
-    }
-    int rc = upload(h, "lstm/wx", wx);
-    if (rc) return rc;
-    rc = upload(h, "lstm/bx", bx);
-    if (rc) return rc;
-    // bf16 form (kernels_ws.hip, ws_main LS): direct 3x3 conv on the bf16 matrix instruction, its own channel order
-    const size_t perb = (size_t)9 * 16 * 64 / 2;          // dwords
-    std::vector<float> wxb(2 * perb), bxb(2 * 64), whb(perb);
-    d = 0;
-    for (const char *nm2 : {"lstm_fw", "lstm_bw"}) {
-        const HostLayer &L = h->layers[h->layer_index.at(nm2)];
+        pack_lstm_gate_weights(L.w.data(), L.cin, nf0, nullptr, wh.data(), nullptr);
         pack_lstm_gate_weights_bf16(L.w.data(), L.cin, 0, L.b.data(), wxb.data() + d * perb, bxb.data() + d * 64);
-        pack_lstm_gate_weights_bf16(L.w.data(), L.cin, a.n_filter[0], nullptr, whb.data(), nullptr);
-        rc = upload(h, std::string(nm2) + "/wh_bf16", whb);
-        if (rc) return rc;
+        pack_lstm_gate_weights_bf16(L.w.data(), L.cin, nf0, nullptr, whb.data(), nullptr);
         std::vector<float> wxhb(2 * perb);               // r06: both halves as one two-chunk filter (un-hoisted time steps, ls_mode 3)
         pack_lstm_gate_weights_bf16_xh(L.w.data(), nullptr, wxhb.data(), nullptr);
-        rc = upload(h, std::string(nm2) + "/wxh_bf16", wxhb);
-        if (rc) return rc;
+        if (!rc) rc = upload(h, nm2 + "/wh", wh);
+        if (!rc) rc = upload(h, nm2 + "/wh_bf16", whb);
+        if (!rc) rc = upload(h, nm2 + "/wxh_bf16", wxhb);
         ++d;
     }
-    rc = upload(h, "lstm/wx_bf16", wxb);
-    if (rc) return rc;
-    return upload(h, "lstm/bx_bf16", bxb);
+    if (!rc) rc = upload(h, "lstm/bx", bx);
+    if (!rc) rc = upload(h, "lstm/wx_bf16", wxb);
+    if (!rc) rc = upload(h, "lstm/bx_bf16", bxb);
+    return rc ? rc : upload(h, "lstm/wx", wx);            // last: its key stands for the whole set (above)
 }
 
-// Takes the layout's ops and activation maps into the handle: packs and uploads what each op's kind and tiling need, resolves the
-// ops' device pointers, and resets the run-time state (events, timing sums) of the previous plan.
+// Packs and uploads what `op`'s kind and tiling need and fills every device pointer its launch takes: the op's own and the shared ones
+// of h->par.  The launches search nothing afterwards; a key the handle lacks ends the plan here, with UKBB_EARCH.
+int bind_op(ukbb_fcn_handle *h, BoundOp &op) {
+    Params &P = h->par;
+    const std::string who = "op " + op.name, lname = op.layer >= 0 ? h->layers[op.layer].name : std::string();
+    int rc = UKBB_OK;
+    auto need = [&](const float *&dst, const std::string &key) { if (!rc) rc = find_param(h, key, who, &dst); };
+    auto sqg = [&](int j, int level, int layer) {
+        const std::string ls = std::to_string(level);
+        need(op.sq_w_s[j], "sqg" + ls + "/w_s"); need(op.sq_b_s[j], h->layers[layer].name + "/bias"); need(op.sq_w_g[j], "sqg" + ls + "/w_g");
+    };
+    auto conv0 = [&] { need(P.conv0_w, "conv0_0/w"); need(P.conv0_b, "conv0_0/bias"); };
+    auto logits = [&] { need(P.logits_w, "logits/w"); need(P.logits_b, "logits/bias"); };
+    ConvConfig c;
+    switch (op.kind) {
+        case OP_FIRST: need(op.wpk, lname + "/w"); need(op.bias, lname + "/bias"); break;
+        case OP_CONV:
+        case OP_TCONV:
+            find_cfg(op.cfg, c);
+            rc = (op.kind == OP_CONV ? ensure_packed : ensure_packed_tconv)(h, op.layer, c, &op.wpk, &op.bias);
+            if (op.fused_first) conv0();
+            if (op.fused_logits) logits();
+            break;
+        case OP_SQG: sqg(0, op.stride, op.layer); break;
+        case OP_SQG_MULTI:
+            for (int j = 0; j < 4; ++j) if (op.mlayer[j] >= 0) sqg(j, j + 1, op.mlayer[j]);
+            break;
+        case OP_HEAD:
+            need(P.head_w_s0, "head/w_s0"); need(P.head_b_s0, "same_dim0/bias"); need(P.head_w_o0, "head/w_o0"); need(P.head_b_o0, "out0/bias");
+            need(P.head_w_o1, "head/w_o1"); need(P.head_b_o1, "out1/bias"); need(P.head_w_o1x3, "head/w_o1x3"); need(P.head_w_o0x3, "head/w_o0x3");
+            need(P.head_w_lg, "head/w_lg"); need(P.logits_b, "logits/bias");
+            break;
+        case OP_STEM:
+            rc = ensure_packed_stem(h);
+            need(P.stem_wA0, "stem/wA0"); need(P.stem_wA1, "stem/wA1"); need(P.conv0_1_b, "conv0_1/bias"); conv0();
+            break;
+        case OP_TAIL:
+            rc = ensure_packed_tail(h);
+            need(P.tail_wA0, "tail/wA0"); need(P.tail_wA1, "tail/wA1"); need(P.up0_0_b, "up0_0/bias"); need(P.up0_1_b, "up0_1/bias"); logits();
+            break;
+        case OP_LOGITS: logits(); break;
+        case OP_FIRST3D: conv0(); need(op.bias, lname + "/bias"); break;
+        case OP_CONV3D:
+            if (!(op.wpk = ensure_packed3d(h, h->layers[op.layer], 0, 0, 3, 3))) rc = UKBB_EDEVICE;
+            need(op.bias, lname + "/bias");
+            break;
+        case OP_TCONV3D:
+            for (int ph = 0; ph < 4 && !rc; ++ph) {
+                const int py = ph >> 1, px = ph & 1;
+                if (!(op.wph[ph] = ensure_packed3d(h, h->layers[op.layer], py, px, py ? 1 : 2, px ? 1 : 2))) rc = UKBB_EDEVICE;
+            }
+            need(op.bias, lname + "/bias");
+            break;
+    }
+    return rc;
+}
+
+// ... and what the ConvLSTM stages behind the plan take: run_bilstm and the two output kernels
+int bind_lstm(ukbb_fcn_handle *h) {
+    const HostLayer &B = h->layers[h->layer_index.at("lstm_bw")];
+    bool z = getenv("UKBB_LSTM_RUN_ZERO_CELL") == nullptr;      // knob: run the zero cell anyway (tests compare both ways)
+    for (size_t i = 0; z && i < B.w.size(); ++i) z = B.w[i] == 0.f;
+    for (size_t i = 0; z && i < B.b.size(); ++i) z = B.b[i] == 0.f;
+    h->lstm_bw_zero = z;
+    int rc = ensure_packed_lstm(h);
+    Params &P = h->par;
+    auto need = [&](const float *&dst, const std::string &key) { if (!rc) rc = find_param(h, key, "the ConvLSTM", &dst); };
+    const std::string dirs[2] = {"lstm_fw", "lstm_bw"};
+    for (int f = 0; f < 2; ++f) {
+        const char *form = f ? "_bf16" : "";
+        need(P.lstm[f].wx, std::string("lstm/wx") + form); need(P.lstm[f].bx, std::string("lstm/bx") + form);
+        for (int d = 0; d < 2; ++d) need(P.lstm[f].wh[d], dirs[d] + "/wh" + form);
+    }
+    for (int d = 0; d < 2; ++d) need(P.lstm_wxh[d], dirs[d] + "/wxh_bf16");
+    need(P.lstm_out_w, "lstm_out/w"); need(P.lstm_out_b, "lstm_out/bias");
+    return rc;
+}
+
+// Takes the layout into the handle: its maps, its ops bound to the device parameters (bind_op, bind_lstm); resets the previous plan's events and timing sums.
 int materialize_plan(ukbb_fcn_handle *h, PlanLayout &L) {
     h->ops.clear();
-    h->act.clear(); h->act_per_image.clear(); h->act_name.clear(); h->act_ch.clear(); h->act_esz.clear(); h->act_alloc_esz.clear();
+    h->acts = std::vector<ActMap>(L.acts.size());
     h->cap_n = 0;
-    for (const ActSpec &s : L.acts) {
-        h->act.emplace_back(new DevBuf);
-        h->act.back()->guard = &h->guard;
-        h->act_per_image.push_back(s.per_image);
-        h->act_name.push_back(s.name);
-        h->act_ch.push_back(s.channels);
-        h->act_esz.push_back(s.esz);
-        h->act_alloc_esz.push_back((int)act_alloc_esz(h->arch, s));
+    h->par = Params{};
+    for (size_t i = 0; i < L.acts.size(); ++i) {
+        const ActSpec &s = L.acts[i];
+        ActMap &m = h->acts[i];
+        m.buf.guard = &h->guard; m.name = s.name;
+        m.per_image = s.per_image; m.esz = s.esz; m.alloc_esz = (int)act_alloc_esz(h->arch, s); m.ch = s.channels;
     }
-    for (Op &op : L.ops) {
-        int rc = UKBB_OK;
-        ConvConfig c;
-        const std::string lname = op.layer >= 0 ? h->layers[op.layer].name : std::string();
-        switch (op.kind) {
-            case OP_CONV:
-                find_cfg(op.cfg, c);
-                rc = ensure_packed(h, op.layer, c, &op.wpk);
-                op.bias = dev_ptr(h, lname + (packed_cout(c, h->layers[op.layer].cout) != h->layers[op.layer].cout ? "/bias_pad" : "/bias"));
-                break;
-            case OP_TCONV:
-                find_cfg(op.cfg, c);
-                rc = ensure_packed_tconv(h, op.layer, c, &op.wpk, &op.bias);
-                break;
-            case OP_STEM: rc = ensure_packed_stem(h); break;
-            case OP_TAIL: rc = ensure_packed_tail(h); break;
-            case OP_CONV3D:
-                if (!(op.wpk = ensure_packed3d(h, h->layers[op.layer], 0, 0, 3, 3))) rc = UKBB_EDEVICE;
-                op.bias = dev_ptr(h, lname + "/bias");
-                break;
-            case OP_TCONV3D:
-                for (int ph = 0; ph < 4 && !rc; ++ph) {
-                    const int py = ph >> 1, px = ph & 1;
-                    if (!(op.wph[ph] = ensure_packed3d(h, h->layers[op.layer], py, px, py ? 1 : 2, px ? 1 : 2))) rc = UKBB_EDEVICE;
-                }
-                op.bias = dev_ptr(h, lname + "/bias");
-                break;
-            case OP_FIRST3D: op.bias = dev_ptr(h, lname + "/bias"); break;
-            default: break;                            // OP_FIRST / OP_SQG* / OP_HEAD / OP_LOGITS: what ukbb_fcn_create uploaded
-        }
+    std::vector<BoundOp> ops;
+    for (const Op &op : L.ops) {
+        ops.emplace_back(op);
+        const int rc = bind_op(h, ops.back());
         if (rc) return rc;
     }
     if (L.needs_lstm) {
-        const HostLayer &B = h->layers[h->layer_index.at("lstm_bw")];
-        bool z = getenv("UKBB_LSTM_RUN_ZERO_CELL") == nullptr;      // knob: run the zero cell anyway (tests compare both ways)
-        for (size_t i = 0; z && i < B.w.size(); ++i) z = B.w[i] == 0.f;
-        for (size_t i = 0; z && i < B.b.size(); ++i) z = B.b[i] == 0.f;
-        h->lstm_bw_zero = z;
-        int rc = ensure_packed_lstm(h);
+        const int rc = bind_lstm(h);
         if (rc) return rc;
-        h->lstm_bf_wino = L.lstm_bf_wino; h->lstm_bf_hoist = L.lstm_bf_hoist; h->lstm_tile_cols = L.lstm_tile_cols;
     }
-    h->ops = std::move(L.ops);
-    h->feat_buf = L.feat_buf;
-    h->mode = L.mode;
-    h->split_first = L.split_first; h->split_last = L.split_last;
-    h->debug_first_op = L.debug_first_op; h->debug_last_op = L.debug_last_op;
+    h->ops = std::move(ops);
+    h->plan = std::move(L);
     for (auto e : h->ev) (void)hipEventDestroy(e);
     h->ev.clear();
     h->t_sum.assign(h->ops.size(), 0.0);
@@ -464,8 +532,7 @@ int build_plan(ukbb_fcn_handle *h, int H, int W, int n_hint) {
 
 int ensure_capacity(ukbb_fcn_handle *h, int n) {
     if (n <= h->cap_n) return UKBB_OK;
-    for (size_t i = 0; i < h->act.size(); ++i)
-        HIP_TRY(h->act[i]->ensure((h->act_per_image[i] * (size_t)n * h->act_alloc_esz[i] + 3) / 4), UKBB_ENOMEM);      // DevBufs count floats
+    for (ActMap &m : h->acts) HIP_TRY(m.buf.ensure(m.units(n)), UKBB_ENOMEM);
     h->cap_n = n;
     return UKBB_OK;
 }
@@ -502,6 +569,13 @@ int prepare(ukbb_fcn_handle *h, int n, int H, int W, int cap = -1) {
     return UKBB_OK;
 }
 
+// ukbb_fcn_forward / ukbb_fcn_forward_host (`what`) take batches of single images
+int refuse_sequence_kinds(const ukbb_fcn_handle *h, const char *what) {
+    if (h->arch.kind != UKBB_KIND_UNET_LSTM && h->arch.kind != UKBB_KIND_TEMPORAL_UNET) return UKBB_OK;
+    set_error("%s: %s models take sequences: use ukbb_fcn_forward_seq / ukbb_fcn_forward_cine", what, h->arch.kind == UKBB_KIND_UNET_LSTM ? "UNet-LSTM" : "Temporal-UNet");
+    return UKBB_EINVAL;
+}
+
 int collect_events(ukbb_fcn_handle *h) {
     if (!h->ev_pending) return UKBB_OK;
     HIP_TRY(hipEventSynchronize(h->ev[h->timing_only >= 0 ? 2 * h->timing_only + 1 : h->ev.size() - 1]), UKBB_EDEVICE);
@@ -516,9 +590,132 @@ int collect_events(ukbb_fcn_handle *h) {
     return UKBB_OK;
 }
 
+// what a forward reads and writes besides the workspace: the caller's device pointers (an output may be NULL)
+struct PlanIo { const float *image; float *logits, *prob; int32_t *pred; };
+
+// One launch of `op` over images [n0, n0 + n) of the batch on stream s (the whole batch everywhere except inside a split range of run_plan).
+int launch_op(ukbb_fcn_handle *h, const BoundOp &op, const PlanIo &io, int n0, int n, hipStream_t s, hipError_t &e) {
+    const ukbb_fcn_arch &a = h->arch;
+    const Params &P = h->par;
+    static const HostLayer no_layer;
+    const HostLayer &L = op.layer >= 0 ? h->layers[op.layer] : no_layer;
+    const int bfio = h->plan.mode.bfio() ? 1 : 0;
+    ConvConfig c;
+    if (op.kind == OP_CONV || op.kind == OP_TCONV) find_cfg(op.cfg, c);
+    auto actp = [&](int id) { return h->acts[id].image(n0); };
+    auto sqg_args = [&](int j, int layer, int in, int out, int H, int W) {      // level j + 1 of the squeeze kernels; OP_SQG binds its one level at [0]
+        SqgArgs sa{};
+        sa.x = actp(in); sa.out = actp(out); sa.w_s = op.sq_w_s[j]; sa.b_s = op.sq_b_s[j]; sa.w_g = op.sq_w_g[j];
+        sa.npix = (long long)n * H * W; sa.cin = h->layers[layer].cin; sa.x_bf16 = bfio; sa.hw = H * W;
+        return sa;
+    };
+    e = hipSuccess;
+    switch (op.kind) {
+        case OP_FIRST: e = launch_first(FirstArgs{io.image, op.wpk, op.bias, actp(op.out), n, op.H, op.W, L.cout, bfio}, s); break;
+        case OP_CONV:
+        case OP_TCONV: {                                     // conv2d_transpose: a 2x2 conv onto the 4 * cout virtual channels of its sub-pixel phases, ReLU always
+            const bool up = op.kind == OP_TCONV;
+            ConvArgs ca{};
+            ca.in0 = op.fused_first ? io.image : actp(op.in0);
+            if (op.fused_first) { ca.first_w = P.conv0_w; ca.first_b = P.conv0_b; }
+            ca.in1 = op.in1 >= 0 ? actp(op.in1) : nullptr;
+            ca.C1 = op.in1 >= 0 ? (int)(h->acts[op.in1].per_image / ((size_t)op.H * op.W)) : 0;
+            ca.C0 = L.cin - ca.C1;
+            ca.wpk = op.wpk; ca.bias = op.bias; ca.out = actp(op.out);
+            ca.N = n; ca.H = op.H; ca.W = op.W; ca.Ho = op.Ho; ca.Wo = op.Wo; ca.Cout = up ? 4 * L.cout : L.cout;
+            if (!up && stores_bf16(c)) { ca.Cout = packed_cout(c, L.cout); ca.cout_store = L.cout; }
+            if (op.fused_logits) {
+                ca.lg_w = P.logits_w; ca.lg_b = P.logits_b;
+                ca.lg_logits = io.logits; ca.lg_prob = io.prob; ca.lg_pred = io.pred; ca.lg_ncls = a.n_class;
+            }
+            ca.pad_y = op.pad_y; ca.pad_x = op.pad_x;
+            ca.tiles_y = (op.Ho + c.th - 1) / c.th; ca.tiles_x = (op.Wo + c.tw - 1) / c.tw;
+            ca.relu = up || L.relu ? 1 : 0; ca.up2 = up ? L.cout : 0;
+            e = launch_conv(op.cfg, ca, s);
+            break;
+        }
+        case OP_SQG: e = launch_sqg(sqg_args(0, op.layer, op.in0, op.out, op.H, op.W), s); break;
+        case OP_SQG_MULTI: {
+            SqgArgs sa[4];
+            for (int j = 0; j < 4; ++j) {
+                sa[j] = SqgArgs{};
+                sa[j].cin = 32 << j;
+                sa[j].x_bf16 = bfio;                         // one input format per launch
+                if (op.mlayer[j] >= 0) sa[j] = sqg_args(j, op.mlayer[j], op.min_[j], op.mout[j], op.mh[j], op.mw[j]);   // else a launch of its own: npix = 0 -> no blocks
+            }
+            e = launch_sqg_multi(sa, s);
+            break;
+        }
+        case OP_HEAD: {
+            HeadArgs ha{};
+            ha.conv0 = actp(op.in0);
+            for (int l = 0; l < 4; ++l) ha.G[l] = actp(op.sq[l]);
+            ha.w_s0 = P.head_w_s0; ha.b_s0 = P.head_b_s0; ha.w_o0 = P.head_w_o0; ha.b_o0 = P.head_b_o0; ha.w_o1 = P.head_w_o1; ha.b_o1 = P.head_b_o1;
+            ha.w_o1x3 = P.head_w_o1x3; ha.w_o0x3 = P.head_w_o0x3; ha.w_lg = P.head_w_lg; ha.b_lg = P.logits_b;
+            ha.logits = io.logits; ha.prob = io.prob; ha.pred = io.pred;
+            ha.N = n; ha.H = op.H; ha.W = op.W; ha.n_class = a.n_class;
+            ha.x3 = h->plan.mode.head_x3; ha.conv0_bf16 = bfio;
+            e = launch_head(ha, s);
+            break;
+        }
+        case OP_STEM: {
+            StemArgs sa{};
+            sa.image = io.image; sa.wA0 = P.stem_wA0; sa.wA1 = P.stem_wA1; sa.b0 = P.conv0_b; sa.b1 = P.conv0_1_b;
+            sa.out = actp(op.out); sa.N = n; sa.H = op.H; sa.W = op.W;
+            e = launch_unet_stem(sa, s);
+            break;
+        }
+        case OP_TAIL: {
+            TailArgs ta{};
+            ta.in0 = actp(op.in0); ta.in1 = actp(op.in1);
+            ta.wA0 = P.tail_wA0; ta.wA1 = P.tail_wA1; ta.b0 = P.up0_0_b; ta.b1 = P.up0_1_b; ta.lg_w = P.logits_w; ta.lg_b = P.logits_b;
+            ta.logits = io.logits; ta.prob = io.prob; ta.pred = io.pred;
+            ta.N = n; ta.H = op.H; ta.W = op.W; ta.ncls = a.n_class;
+            e = launch_unet_tail(ta, s);
+            break;
+        }
+        case OP_LOGITS: {
+            LogitsArgs la{};
+            la.in = actp(op.in0); la.w = P.logits_w; la.bias = P.logits_b;
+            la.logits = io.logits; la.prob = io.prob; la.pred = io.pred;
+            la.npix = (int64_t)n * op.H * op.W; la.C = L.cin; la.n_class = a.n_class; la.in_bf16 = bfio;
+            e = launch_logits(la, s);
+            break;
+        }
+        case OP_FIRST3D: e = launch_conv3d_first(Conv3dFirstArgs{io.image, h->t3d_map, P.conv0_w, op.bias, actp(op.out), n, a.fc, op.H, op.W}, s); break;
+        case OP_CONV3D:
+        case OP_TCONV3D: {
+            Conv3dArgs ca{};
+            ca.in0 = actp(op.in0);
+            ca.in1 = op.in1 >= 0 ? actp(op.in1) : nullptr;
+            ca.C1 = op.in1 >= 0 ? h->acts[op.in1].ch : 0;
+            ca.C0 = L.cin - ca.C1;
+            ca.bias = op.bias; ca.out = actp(op.out);
+            ca.N = n; ca.T = a.fc; ca.Hi = op.H; ca.Wi = op.W;
+            ca.Ho = op.Ho; ca.Wo = op.Wo; ca.Cout = L.cout; ca.Cout_pad = round_up(L.cout, 32);
+            ca.relu = L.relu ? 1 : 0;
+            if (op.kind == OP_CONV3D) {
+                ca.Hg = op.Ho; ca.Wg = op.Wo; ca.stride = op.stride; ca.up = 1;
+                ca.oy = -op.pad_y; ca.ox = -op.pad_x; ca.jstep = 1;
+                ca.nph = 1; ca.ph[0] = Conv3dPhase{op.wpk, 0, 0, 3, 3};
+            } else {
+                ca.Hg = op.H; ca.Wg = op.W; ca.stride = 1; ca.up = 2;
+                ca.oy = 0; ca.ox = 0; ca.jstep = -1;
+                ca.nph = 4;
+                for (int ph = 0; ph < 4; ++ph) ca.ph[ph] = Conv3dPhase{op.wph[ph], ph >> 1, ph & 1, (ph >> 1) ? 1 : 2, (ph & 1) ? 1 : 2};
+            }
+            e = launch_conv3d(ca, s);
+            break;
+        }
+        default:
+            set_error("op kind %d not implemented", (int)op.kind);
+            return UKBB_EARCH;
+    }
+    return UKBB_OK;
+}
+
 int run_plan(ukbb_fcn_handle *h, const float *image, int n, float *logits, float *prob, int32_t *pred,
              hipStream_t s) {
-    const ukbb_fcn_arch &a = h->arch;
     if (h->timing) {
         int rc = collect_events(h);
         if (rc) return rc;
@@ -530,183 +727,19 @@ int run_plan(ukbb_fcn_handle *h, const float *image, int n, float *logits, float
     }
     hipStream_t s_main = s;
     bool forked = false;
-    // One launch of op i over images [n0, n0 + n) of the batch on stream s (the whole batch everywhere except inside a split range, below).
-    auto launch_one = [&](size_t i, int n0, int n, hipStream_t s, hipError_t &e) -> int {
-        const Op &op = h->ops[i];
-        auto actp = [&](int id) -> float * {
-            return reinterpret_cast<float *>(reinterpret_cast<char *>(h->act[id]->p) + (size_t)n0 * h->act_per_image[id] * h->act_esz[id]);
-        };
-        e = hipSuccess;
-        switch (op.kind) {
-            case OP_FIRST: {
-                const HostLayer &L = h->layers[op.layer];
-                FirstArgs fa{image, dev_ptr(h, L.name + "/w"), dev_ptr(h, L.name + "/bias"), actp(op.out),
-                             n, op.H, op.W, L.cout, h->mode.bfio() ? 1 : 0};
-                e = launch_first(fa, s);
-                break;
-            }
-            case OP_CONV: {
-                const HostLayer &L = h->layers[op.layer];
-                ConvConfig c;
-                find_cfg(op.cfg, c);
-                ConvArgs ca{};
-                ca.in0 = op.fused_first ? image : actp(op.in0);
-                if (op.fused_first) { ca.first_w = dev_ptr(h, "conv0_0/w"); ca.first_b = dev_ptr(h, "conv0_0/bias"); }
-                ca.in1 = op.in1 >= 0 ? actp(op.in1) : nullptr;
-                ca.C1 = op.in1 >= 0 ? (int)(h->act_per_image[op.in1] / ((size_t)op.H * op.W)) : 0;
-                ca.C0 = L.cin - ca.C1;
-                ca.wpk = op.wpk; ca.bias = op.bias; ca.out = actp(op.out);
-                ca.N = n; ca.H = op.H; ca.W = op.W; ca.Ho = op.Ho; ca.Wo = op.Wo; ca.Cout = L.cout;
-                if (stores_bf16(c)) { ca.Cout = packed_cout(c, L.cout); ca.cout_store = L.cout; }
-                if (op.fused_logits) {
-                    ca.lg_w = dev_ptr(h, "logits/w"); ca.lg_b = dev_ptr(h, "logits/bias");
-                    ca.lg_logits = logits; ca.lg_prob = prob; ca.lg_pred = pred; ca.lg_ncls = a.n_class;
-                }
-                ca.pad_y = op.pad_y; ca.pad_x = op.pad_x;
-                ca.tiles_y = (op.Ho + c.th - 1) / c.th; ca.tiles_x = (op.Wo + c.tw - 1) / c.tw;
-                ca.relu = L.relu ? 1 : 0;
-                e = launch_conv(op.cfg, ca, s);
-                break;
-            }
-            case OP_SQG: {
-                const HostLayer &L = h->layers[op.layer];
-                const std::string ls = std::to_string(op.stride);
-                SqgArgs sa{};
-                sa.x = actp(op.in0);
-                sa.w_s = dev_ptr(h, "sqg" + ls + "/w_s"); sa.b_s = dev_ptr(h, L.name + "/bias");
-                sa.w_g = dev_ptr(h, "sqg" + ls + "/w_g");
-                sa.out = actp(op.out);
-                sa.npix = (long long)n * op.H * op.W; sa.cin = L.cin;
-                sa.x_bf16 = h->mode.bfio() ? 1 : 0; sa.hw = op.H * op.W;
-                e = launch_sqg(sa, s);
-                break;
-            }
-            case OP_SQG_MULTI: {
-                SqgArgs sa[4];
-                for (int j = 0; j < 4; ++j) {
-                    sa[j] = SqgArgs{};
-                    sa[j].cin = 32 << j;
-                    sa[j].x_bf16 = h->mode.bfio() ? 1 : 0;         // one input format per launch
-                    if (op.mlayer[j] < 0) continue;              // level handled by a launch of its own: npix = 0 -> no blocks
-                    const HostLayer &L = h->layers[op.mlayer[j]];
-                    const std::string ls = std::to_string(j + 1);
-                    sa[j].x = actp(op.min_[j]);
-                    sa[j].w_s = dev_ptr(h, "sqg" + ls + "/w_s"); sa[j].b_s = dev_ptr(h, L.name + "/bias");
-                    sa[j].w_g = dev_ptr(h, "sqg" + ls + "/w_g");
-                    sa[j].out = actp(op.mout[j]);
-                    sa[j].npix = (long long)n * op.mh[j] * op.mw[j]; sa[j].cin = L.cin;
-                    sa[j].hw = op.mh[j] * op.mw[j];
-                }
-                e = launch_sqg_multi(sa, s);
-                break;
-            }
-            case OP_HEAD: {
-                HeadArgs ha{};
-                ha.conv0 = actp(op.in0);
-                for (int l = 0; l < 4; ++l) ha.G[l] = actp(op.sq[l]);
-                ha.w_s0 = dev_ptr(h, "head/w_s0"); ha.b_s0 = dev_ptr(h, "same_dim0/bias");
-                ha.w_o0 = dev_ptr(h, "head/w_o0"); ha.b_o0 = dev_ptr(h, "out0/bias");
-                ha.w_o1 = dev_ptr(h, "head/w_o1"); ha.b_o1 = dev_ptr(h, "out1/bias");
-                ha.w_o1x3 = dev_ptr(h, "head/w_o1x3"); ha.w_o0x3 = dev_ptr(h, "head/w_o0x3");
-                ha.w_lg = dev_ptr(h, "head/w_lg"); ha.b_lg = dev_ptr(h, "logits/bias");
-                ha.logits = logits; ha.prob = prob; ha.pred = pred;
-                ha.N = n; ha.H = op.H; ha.W = op.W; ha.n_class = a.n_class;
-                ha.x3 = h->mode.head_x3;
-                ha.conv0_bf16 = h->mode.bfio() ? 1 : 0;
-                e = launch_head(ha, s);
-                break;
-            }
-            case OP_TCONV: {
-                const HostLayer &L = h->layers[op.layer];
-                ConvConfig c;
-                find_cfg(op.cfg, c);
-                ConvArgs ca{};
-                ca.in0 = actp(op.in0); ca.in1 = nullptr; ca.C0 = L.cin; ca.C1 = 0;
-                ca.wpk = op.wpk; ca.bias = op.bias; ca.out = actp(op.out);
-                ca.N = n; ca.H = op.H; ca.W = op.W; ca.Ho = op.Ho; ca.Wo = op.Wo; ca.Cout = 4 * L.cout;
-                ca.pad_y = 1; ca.pad_x = 1;
-                ca.tiles_y = (op.Ho + c.th - 1) / c.th; ca.tiles_x = (op.Wo + c.tw - 1) / c.tw;
-                ca.relu = 1; ca.up2 = L.cout;
-                e = launch_conv(op.cfg, ca, s);
-                break;
-            }
-            case OP_STEM: {
-                StemArgs sa{};
-                sa.image = image; sa.wA0 = dev_ptr(h, "stem/wA0"); sa.wA1 = dev_ptr(h, "stem/wA1");
-                sa.b0 = dev_ptr(h, "conv0_0/bias"); sa.b1 = dev_ptr(h, "conv0_1/bias");
-                sa.out = actp(op.out); sa.N = n; sa.H = op.H; sa.W = op.W;
-                e = launch_unet_stem(sa, s);
-                break;
-            }
-            case OP_TAIL: {
-                TailArgs ta{};
-                ta.in0 = actp(op.in0); ta.in1 = actp(op.in1);
-                ta.wA0 = dev_ptr(h, "tail/wA0"); ta.wA1 = dev_ptr(h, "tail/wA1");
-                ta.b0 = dev_ptr(h, "up0_0/bias"); ta.b1 = dev_ptr(h, "up0_1/bias");
-                ta.lg_w = dev_ptr(h, "logits/w"); ta.lg_b = dev_ptr(h, "logits/bias");
-                ta.logits = logits; ta.prob = prob; ta.pred = pred;
-                ta.N = n; ta.H = op.H; ta.W = op.W; ta.ncls = a.n_class;
-                e = launch_unet_tail(ta, s);
-                break;
-            }
-            case OP_LOGITS: {
-                const HostLayer &L = h->layers[op.layer];
-                LogitsArgs la{};
-                la.in = actp(op.in0); la.w = dev_ptr(h, "logits/w"); la.bias = dev_ptr(h, "logits/bias");
-                la.logits = logits; la.prob = prob; la.pred = pred;
-                la.npix = (int64_t)n * op.H * op.W; la.C = L.cin; la.n_class = a.n_class;
-                la.in_bf16 = h->mode.bfio() ? 1 : 0;
-                e = launch_logits(la, s);
-                break;
-            }
-            case OP_FIRST3D: {
-                Conv3dFirstArgs fa{image, h->t3d_map, dev_ptr(h, "conv0_0/w"), op.bias, actp(op.out), n, a.fc, op.H, op.W};
-                e = launch_conv3d_first(fa, s);
-                break;
-            }
-            case OP_CONV3D:
-            case OP_TCONV3D: {
-                const HostLayer &L = h->layers[op.layer];
-                Conv3dArgs ca{};
-                ca.in0 = actp(op.in0);
-                ca.in1 = op.in1 >= 0 ? actp(op.in1) : nullptr;
-                ca.C1 = op.in1 >= 0 ? h->act_ch[op.in1] : 0;
-                ca.C0 = L.cin - ca.C1;
-                ca.bias = op.bias; ca.out = actp(op.out);
-                ca.N = n; ca.T = a.fc; ca.Hi = op.H; ca.Wi = op.W;
-                ca.Ho = op.Ho; ca.Wo = op.Wo; ca.Cout = L.cout; ca.Cout_pad = round_up(L.cout, 32);
-                ca.relu = L.relu ? 1 : 0;
-                if (op.kind == OP_CONV3D) {
-                    ca.Hg = op.Ho; ca.Wg = op.Wo; ca.stride = op.stride; ca.up = 1;
-                    ca.oy = -op.pad_y; ca.ox = -op.pad_x; ca.jstep = 1;
-                    ca.nph = 1; ca.ph[0] = Conv3dPhase{op.wpk, 0, 0, 3, 3};
-                } else {
-                    ca.Hg = op.H; ca.Wg = op.W; ca.stride = 1; ca.up = 2;
-                    ca.oy = 0; ca.ox = 0; ca.jstep = -1;
-                    ca.nph = 4;
-                    for (int ph = 0; ph < 4; ++ph) ca.ph[ph] = Conv3dPhase{op.wph[ph], ph >> 1, ph & 1, (ph >> 1) ? 1 : 2, (ph & 1) ? 1 : 2};
-                }
-                e = launch_conv3d(ca, s);
-                break;
-            }
-            default:
-                set_error("op kind %d not implemented", (int)op.kind);
-                return UKBB_EARCH;
-        }
-        return UKBB_OK;
-    };
+    const PlanIo io{image, logits, prob, pred};
     // UKBB_SPLIT_FROM (plan build): the ops of levels >= k -- conv{k}_0 .. up{k}_1, the launches whose fill / drain and serial chains
     // are the largest part of their time -- run as TWO half-batch chains on two streams, enqueued interleaved, joined before the next op
-    const int sp0 = h->split_first, sp1 = h->split_last;
+    const int sp0 = h->plan.split_first, sp1 = h->plan.split_last;
     // debugging aids (r06, tools/two_stream_bisect.py): run only the ops [first, last] of the plan (whatever they read was left by an earlier full forward)
-    const int dbg_first = h->debug_first_op, dbg_last = h->debug_last_op;
+    const int dbg_first = h->plan.debug_first_op, dbg_last = h->plan.debug_last_op;
     const char *poison_env = getenv("UKBB_DEBUG_POISON_LDS");            // hex pattern written to every CU's LDS in front of every launch
     const bool poison_on = poison_env != nullptr;
     const bool fence_on = getenv("UKBB_DEBUG_FENCE_KERNEL") != nullptr;
     const bool sync_on = getenv("UKBB_DEBUG_SYNC_EVERY_OP") != nullptr;
     const uint32_t poison_pat = poison_on ? (uint32_t)strtoul(poison_env, nullptr, 16) : 0u;
     for (size_t i = 0; i < h->ops.size(); ++i) {
-        const Op &op = h->ops[i];
+        const BoundOp &op = h->ops[i];
         s = s_main;
         if ((int)i < dbg_first || (int)i > dbg_last) continue;
         if ((int)i == sp0 && sp1 >= sp0 && n >= 8 && !h->timing) {      // per-kernel timing (set_timing) measures whole-batch launches
@@ -720,9 +753,9 @@ int run_plan(ukbb_fcn_handle *h, const float *image, int n, float *logits, float
             const int nA = (n + 1) / 2;
             for (int j = sp0; j <= sp1; ++j) {
                 hipError_t e;
-                int rc = launch_one(j, 0, nA, s_main, e);
+                int rc = launch_op(h, h->ops[j], io, 0, nA, s_main, e);
                 if (rc) return rc;
-                if (e == hipSuccess) rc = launch_one(j, nA, n - nA, h->side2, e);
+                if (e == hipSuccess) rc = launch_op(h, h->ops[j], io, nA, n - nA, h->side2, e);
                 if (rc) return rc;
                 if (e != hipSuccess) { set_error("launch of %s (split) failed: %s", h->ops[j].name.c_str(), hipGetErrorString(e)); return UKBB_EDEVICE; }
             }
@@ -753,7 +786,7 @@ int run_plan(ukbb_fcn_handle *h, const float *image, int n, float *logits, float
         hipError_t e = hipSuccess;
         if (poison_on) (void)ukbb_fcn_debug_poison_lds(poison_pat, s);      // debugging aid: a kernel that reads LDS it never wrote now reads this pattern
         {
-            const int rc = launch_one(i, 0, n, s, e);
+            const int rc = launch_op(h, op, io, 0, n, s, e);
             if (rc) return rc;
         }
         if (e != hipSuccess) { set_error("launch of %s failed: %s", op.name.c_str(), hipGetErrorString(e)); return UKBB_EDEVICE; }
@@ -769,12 +802,21 @@ int run_plan(ukbb_fcn_handle *h, const float *image, int n, float *logits, float
 
 // every DevBuf of the handle by name: the handle's own ("io_prob", "lstm_hall", ...), the activation maps ("act<index>:<name>") and the
 // device-side parameters ("dev:<layer>/<what>")
-void guard_bufs(ukbb_fcn_handle *h, std::vector<std::pair<std::string, DevBuf *>> &v) {
-    v.clear();
-    for (auto &kv : h->named_bufs()) v.emplace_back(kv.first, kv.second);
-    for (size_t i = 0; i < h->act.size(); ++i)
-        v.emplace_back("act" + std::to_string(i) + (h->act_name[i].empty() ? std::string() : ":" + h->act_name[i]), h->act[i].get());
+std::vector<std::pair<std::string, DevBuf *>> guard_bufs(ukbb_fcn_handle *h) {
+    std::vector<std::pair<std::string, DevBuf *>> v;
+    for (const HandleBuf &b : HANDLE_BUFS) v.emplace_back(b.name, &(h->*b.buf));
+    for (size_t i = 0; i < h->acts.size(); ++i)
+        v.emplace_back("act" + std::to_string(i) + (h->acts[i].name.empty() ? std::string() : ":" + h->acts[i].name), &h->acts[i].buf);
     for (auto &kv : h->dev) v.emplace_back("dev:" + kv.first, kv.second.get());
+    return v;
+}
+
+// The scratch of the handle: its own buffers (rewritten_only: those of them a call rewrites before it reads them) and the activation maps.
+std::vector<DevBuf *> scratch_bufs(ukbb_fcn_handle *h, bool rewritten_only = false) {
+    std::vector<DevBuf *> v;
+    for (const HandleBuf &b : HANDLE_BUFS) if (b.rewritten || !rewritten_only) v.push_back(&(h->*b.buf));
+    for (ActMap &m : h->acts) v.push_back(&m.buf);
+    return v;
 }
 
 int guard_checks(ukbb_fcn_handle *h, const char *what) {
@@ -795,7 +837,7 @@ int ukbb_fcn_abi_version(void) { return UKBB_FCN_ABI_VERSION; }
 // debugging aid, not in the public header (tools/two_stream_bisect.py): forwards launch only the ops [first, last] of the plan from now on
 int ukbb_fcn_debug_set_ops(ukbb_fcn_handle *h, int first, int last) {
     if (!h) return UKBB_EINVAL;
-    h->debug_first_op = first; h->debug_last_op = last;
+    h->plan.debug_first_op = first; h->plan.debug_last_op = last;
     return UKBB_OK;
 }
 
@@ -806,8 +848,7 @@ int ukbb_fcn_debug_set_ops(ukbb_fcn_handle *h, int first, int last) {
 int ukbb_fcn_debug_check_guards(ukbb_fcn_handle *h, char *report, size_t cap) {
     int rc = guard_checks(h, "debug_check_guards");
     if (rc) return rc;
-    std::vector<std::pair<std::string, DevBuf *>> bufs;
-    guard_bufs(h, bufs);
+    const auto bufs = guard_bufs(h);
     std::vector<unsigned char> host(GUARD_BYTES);
     std::string out;
     int bad = 0;
@@ -838,8 +879,7 @@ int ukbb_fcn_debug_check_guards(ukbb_fcn_handle *h, char *report, size_t cap) {
 // The number of guarded buffers the handle holds right now; their payload bytes and the bytes of their guards.
 int ukbb_fcn_debug_guard_info(ukbb_fcn_handle *h, uint64_t *payload_bytes, uint64_t *guard_bytes) {
     if (!h) { set_error("debug_guard_info: NULL handle"); return UKBB_EINVAL; }
-    std::vector<std::pair<std::string, DevBuf *>> bufs;
-    guard_bufs(h, bufs);
+    const auto bufs = guard_bufs(h);
     int nb = 0;
     uint64_t pay = 0;
     for (auto &kv : bufs)
@@ -855,11 +895,8 @@ int ukbb_fcn_debug_guard_info(ukbb_fcn_handle *h, uint64_t *payload_bytes, uint6
 int ukbb_fcn_debug_poison(ukbb_fcn_handle *h, uint32_t pattern) {
     int rc = guard_checks(h, "debug_poison");
     if (rc) return rc;
-    std::vector<DevBuf *> bufs = {&h->io_logits, &h->io_prob, &h->io_pred, &h->lstm_gx, &h->lstm_c1, &h->lstm_h1, &h->lstm_c, &h->lstm_hall,
-                                  &h->lstm_probw, &h->lstm_img, &h->t3d_probw};
-    for (auto &b : h->act) bufs.push_back(b.get());
     int nb = 0;
-    for (DevBuf *b : bufs) {
+    for (DevBuf *b : scratch_bufs(h, true)) {
         if (!b->p) continue;
         HIP_TRY(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(b->p), (int)pattern, b->n), UKBB_EDEVICE);
         ++nb;
@@ -875,8 +912,7 @@ int ukbb_fcn_debug_damage_guard(ukbb_fcn_handle *h, const char *buffer, long lon
     int rc = guard_checks(h, "debug_damage_guard");
     if (rc) return rc;
     if (!buffer) { set_error("debug_damage_guard: NULL buffer name"); return UKBB_EINVAL; }
-    std::vector<std::pair<std::string, DevBuf *>> bufs;
-    guard_bufs(h, bufs);
+    const auto bufs = guard_bufs(h);
     for (auto &kv : bufs) {
         if (kv.first != buffer) continue;
         const DevBuf *b = kv.second;
@@ -1064,9 +1100,8 @@ int ukbb_fcn_reserve(ukbb_fcn_handle *h, int n, int height, int width) {
 int ukbb_fcn_forward(ukbb_fcn_handle *h, const float *image, int n, int height, int width,
                      float *logits, float *prob, int32_t *pred, void *stream) {
     if (!h || !image) { set_error("forward: NULL argument"); return UKBB_EINVAL; }
-    if (h->arch.kind == UKBB_KIND_UNET_LSTM) { set_error("forward: UNet-LSTM models take sequences: use ukbb_fcn_forward_seq / ukbb_fcn_forward_cine"); return UKBB_EINVAL; }
-    if (h->arch.kind == UKBB_KIND_TEMPORAL_UNET) { set_error("forward: Temporal-UNet models take sequences: use ukbb_fcn_forward_seq / ukbb_fcn_forward_cine"); return UKBB_EINVAL; }
-    int rc = prepare(h, n, height, width);
+    int rc = refuse_sequence_kinds(h, "forward");
+    if (!rc) rc = prepare(h, n, height, width);
     if (rc) return rc;
     return run_plan(h, image, n, logits, prob, pred, static_cast<hipStream_t>(stream));
 }
@@ -1074,22 +1109,18 @@ int ukbb_fcn_forward(ukbb_fcn_handle *h, const float *image, int n, int height, 
 int ukbb_fcn_forward_host(ukbb_fcn_handle *h, const float *image, int n, int height, int width,
                           float *logits, float *prob, int32_t *pred) {
     if (!h || !image) { set_error("forward_host: NULL argument"); return UKBB_EINVAL; }
-    if (h->arch.kind == UKBB_KIND_UNET_LSTM) { set_error("forward_host: UNet-LSTM models take sequences: use ukbb_fcn_forward_seq / ukbb_fcn_forward_cine"); return UKBB_EINVAL; }
-    if (h->arch.kind == UKBB_KIND_TEMPORAL_UNET) { set_error("forward_host: Temporal-UNet models take sequences: use ukbb_fcn_forward_seq / ukbb_fcn_forward_cine"); return UKBB_EINVAL; }
-    int rc = prepare(h, n, height, width);
+    int rc = refuse_sequence_kinds(h, "forward_host");
+    if (!rc) rc = prepare(h, n, height, width);
     if (rc) return rc;
     const size_t npix = (size_t)n * height * width, ncls = h->arch.n_class;
+    const struct { void *host; DevBuf &dev; size_t n; } outs[3] = {{logits, h->io_logits, npix * ncls}, {prob, h->io_prob, npix * ncls}, {pred, h->io_pred, npix}};
     HIP_TRY(h->io_image.ensure(npix), UKBB_ENOMEM);
-    if (logits) HIP_TRY(h->io_logits.ensure(npix * ncls), UKBB_ENOMEM);
-    if (prob) HIP_TRY(h->io_prob.ensure(npix * ncls), UKBB_ENOMEM);
-    if (pred) HIP_TRY(h->io_pred.ensure(npix), UKBB_ENOMEM);
+    for (auto &o : outs) if (o.host) HIP_TRY(o.dev.ensure(o.n), UKBB_ENOMEM);
     HIP_TRY(hipMemcpyAsync(h->io_image.p, image, npix * sizeof(float), hipMemcpyHostToDevice, nullptr), UKBB_EDEVICE);
     rc = run_plan(h, h->io_image.p, n, logits ? h->io_logits.p : nullptr, prob ? h->io_prob.p : nullptr,
                   pred ? reinterpret_cast<int32_t *>(h->io_pred.p) : nullptr, nullptr);
     if (rc) return rc;
-    if (logits) HIP_TRY(hipMemcpyAsync(logits, h->io_logits.p, npix * ncls * sizeof(float), hipMemcpyDeviceToHost, nullptr), UKBB_EDEVICE);
-    if (prob) HIP_TRY(hipMemcpyAsync(prob, h->io_prob.p, npix * ncls * sizeof(float), hipMemcpyDeviceToHost, nullptr), UKBB_EDEVICE);
-    if (pred) HIP_TRY(hipMemcpyAsync(pred, h->io_pred.p, npix * sizeof(int32_t), hipMemcpyDeviceToHost, nullptr), UKBB_EDEVICE);
+    for (auto &o : outs) if (o.host) HIP_TRY(hipMemcpyAsync(o.host, o.dev.p, o.n * sizeof(float), hipMemcpyDeviceToHost, nullptr), UKBB_EDEVICE);
     HIP_TRY(hipStreamSynchronize(nullptr), UKBB_EDEVICE);
     return UKBB_OK;
 }
@@ -1111,19 +1142,11 @@ bool cine_query_units(const ukbb_fcn_arch *arch, int precision, int F, int H, in
     return true;
 }
 
-void scratch_bufs(ukbb_fcn_handle *h, std::vector<DevBuf *> &v) {
-    v = {&h->io_image, &h->io_logits, &h->io_prob, &h->io_pred, &h->lstm_gx, &h->lstm_c1, &h->lstm_h1, &h->lstm_c, &h->lstm_hall,
-         &h->lstm_probw, &h->lstm_aux, &h->lstm_img, &h->t3d_aux, &h->t3d_probw};
-    for (auto &b : h->act) v.push_back(b.get());
-}
-
 // frees every activation and cine buffer (the plan stays); nothing of the handle may be in flight afterwards
 int release_scratch(ukbb_fcn_handle *h) {
     HIP_TRY(hipSetDevice(h->device), UKBB_EDEVICE);
     HIP_TRY(hipDeviceSynchronize(), UKBB_EDEVICE);
-    std::vector<DevBuf *> bufs;
-    scratch_bufs(h, bufs);
-    for (DevBuf *b : bufs) b->release();
+    for (DevBuf *b : scratch_bufs(h)) b->release();
     h->cap_n = 0;
     h->lstm_aux_key = h->t3d_aux_key = h->budget_key = -1;
     return UKBB_OK;
@@ -1176,9 +1199,7 @@ int ukbb_fcn_set_scratch_budget(ukbb_fcn_handle *h, uint64_t bytes) {
 uint64_t ukbb_fcn_scratch_bytes(const ukbb_fcn_handle *h) {
     if (!h) return 0;
     uint64_t n = 0;
-    std::vector<DevBuf *> bufs;
-    scratch_bufs(const_cast<ukbb_fcn_handle *>(h), bufs);
-    for (DevBuf *b : bufs) n += b->n;
+    for (DevBuf *b : scratch_bufs(const_cast<ukbb_fcn_handle *>(h))) n += b->n;
     return n * sizeof(float);
 }
 
@@ -1191,25 +1212,24 @@ namespace {
 //   ([dir][k][Wn][HW][16]) for the output conv over concat([h_fw, h_bw]) (:305-312), which the caller runs (lstm_out / lstm_tile).
 int run_bilstm(ukbb_fcn_handle *h, const float *feat, int NF, const int *d_map, int Wn, int H, int W, hipStream_t s) {
     const ukbb_fcn_arch &a = h->arch;
-    const int T = a.fc, NHID = a.same_dim, tc = h->lstm_tile_cols;
+    const int T = a.fc, NHID = a.same_dim, tc = h->plan.lstm_tile_cols;
     const size_t HW = (size_t)H * W;
     // bf16 plan: the direct-conv bf16 form (kernels_ws.hip) unless UKBB_LSTM_BF16_WINOGRAD=1 asks for the fp32 Winograd arithmetic on bf16 storage (A/B)
-    const bool wsf = h->mode.bfio() && !h->lstm_bf_wino;
+    const bool wsf = h->plan.mode.bfio() && !h->plan.lstm_bf_wino;
     // r06 experiment (UKBB_LSTM_BF16_UNHOIST=1): the direct-conv bf16 steps read the feature frame (32 bytes per pixel) and multiply it again
     // instead of reading gx (128 bytes per pixel); no gx buffer exists in that form.  Slower by 5 % per step (plan.cpp, read_knobs), so not the default.
-    const bool unhoist = wsf && !h->lstm_bf_hoist;
+    const bool unhoist = wsf && !h->plan.lstm_bf_hoist;
     const size_t gxf = wsf ? lstm_ws_gx_elems(H, W) : wino24_lstm_gx_floats(H, W, tc), cf = wsf ? lstm_ws_c_floats(H, W) : wino24_lstm_c_floats(H, W, tc);
-    const bool bf = h->mode.bfio();                        // bf16 plan: features, gx and hidden maps are bf16 in HBM
+    const bool bf = h->plan.mode.bfio();                        // bf16 plan: features, gx and hidden maps are bf16 in HBM
     const size_t esz = bf ? 2 : 4;
     // Scratch of one cine (include/ukbb_fcn.h, forward_cine): gx 2 NF gxf + h1 2 NF HW NHID + hall 2 T Wn HW NHID elements of esz bytes,
     // cell state (2 NF + Wn) cf floats.  DevBuf counts 4-byte units: the bf16 maps take half as many.
-    auto units = [esz](size_t elems) { return (elems * esz + 3) / 4; };
-    if (!unhoist) HIP_TRY(h->lstm_gx.ensure(units(2 * (size_t)NF * gxf)), UKBB_ENOMEM);
+    if (!unhoist) HIP_TRY(h->lstm_gx.ensure_bytes(2 * (size_t)NF * gxf * esz), UKBB_ENOMEM);
     HIP_TRY(h->lstm_c1.ensure(2 * (size_t)NF * cf), UKBB_ENOMEM);
-    HIP_TRY(h->lstm_h1.ensure(units(2 * (size_t)NF * HW * NHID)), UKBB_ENOMEM);
+    HIP_TRY(h->lstm_h1.ensure_bytes(2 * (size_t)NF * HW * NHID * esz), UKBB_ENOMEM);
     HIP_TRY(h->lstm_c.ensure((size_t)Wn * cf), UKBB_ENOMEM);
-    HIP_TRY(h->lstm_hall.ensure(units(2 * (size_t)T * Wn * HW * NHID)), UKBB_ENOMEM);
-    auto at = [esz](float *p, size_t elems) { return reinterpret_cast<float *>(reinterpret_cast<char *>(p) + elems * esz); };
+    HIP_TRY(h->lstm_hall.ensure_bytes(2 * (size_t)T * Wn * HW * NHID * esz), UKBB_ENOMEM);
+    const Params &P = h->par;
     ConvArgs base{};
     base.ls_bf16 = bf ? 1 : 0;
     base.C0 = a.n_filter[0]; base.C1 = 0;
@@ -1221,7 +1241,7 @@ int run_bilstm(ukbb_fcn_handle *h, const float *feat, int NF, const int *d_map, 
     {   // x pass
         ConvArgs ca = base;
         ca.in0 = feat; ca.N = NF; ca.Cout = 2 * 4 * NHID;
-        ca.wpk = dev_ptr(h, wsf ? "lstm/wx_bf16" : "lstm/wx"); ca.bias = dev_ptr(h, wsf ? "lstm/bx_bf16" : "lstm/bx");
+        ca.wpk = P.lstm[wsf].wx; ca.bias = P.lstm[wsf].bx;
         ca.ls_mode = 1; ca.ls_gx = unhoist ? nullptr : h->lstm_gx.p; ca.ls_c_out = h->lstm_c1.p; ca.out = h->lstm_h1.p;
         ca.ls_gx_dir = (long long)NF * gxf; ca.ls_c_dir = (long long)NF * cf; ca.ls_h_dir = (long long)NF * HW * NHID;
         hipError_t e = wsf ? launch_lstm_ws(ca, s) : launch_wino24_lstm(ca, tc, s);
@@ -1231,33 +1251,33 @@ int run_bilstm(ukbb_fcn_handle *h, const float *feat, int NF, const int *d_map, 
     // A zero backward cell (the single-direction head served through the bidirectional layer set): from the zero state i = o = 1/2, j = tanh(0) = 0,
     // so c and h stay exactly 0 at every step -- the x pass above already produced zeros for its first step; the other T - 1 maps are cleared, not computed.
     const int ndir = h->lstm_bw_zero ? 1 : 2;
-    if (h->lstm_bw_zero) HIP_TRY(hipMemsetAsync(at(h->lstm_hall.p, (size_t)T * kst), 0, (size_t)T * kst * esz, s), UKBB_EDEVICE);
+    if (h->lstm_bw_zero) HIP_TRY(hipMemsetAsync(at(h->lstm_hall.p, (size_t)T * kst, esz), 0, (size_t)T * kst * esz, s), UKBB_EDEVICE);
     for (int dir = 0; dir < ndir; ++dir) {
-        float *const hall = at(h->lstm_hall.p, (size_t)dir * T * kst);
+        float *const hall = at(h->lstm_hall.p, (size_t)dir * T * kst, esz);
         for (int step = 1; step < T; ++step) {
             const int k = dir ? T - 1 - step : step, kprev = dir ? k + 1 : k - 1;
             ConvArgs ca = base;
             ca.N = Wn; ca.Cout = 4 * NHID;
-            ca.wpk = dev_ptr(h, wsf ? (dir ? "lstm_bw/wh_bf16" : "lstm_fw/wh_bf16") : (dir ? "lstm_bw/wh" : "lstm_fw/wh")); ca.bias = nullptr;
+            ca.wpk = P.lstm[wsf].wh[dir]; ca.bias = nullptr;
             ca.ls_mode = 2;
-            ca.ls_gx = unhoist ? nullptr : at(h->lstm_gx.p, (size_t)dir * NF * gxf); ca.ls_gx_map = d_map + (size_t)k * Wn;
+            ca.ls_gx = unhoist ? nullptr : at(h->lstm_gx.p, (size_t)dir * NF * gxf, esz); ca.ls_gx_map = d_map + (size_t)k * Wn;
             const float *hprev; const int *hmap;
             if (step == 1) {                                // previous state = the x pass's per-frame first step
-                hprev = at(h->lstm_h1.p, (size_t)dir * NF * HW * NHID); hmap = d_map + (size_t)kprev * Wn;
+                hprev = at(h->lstm_h1.p, (size_t)dir * NF * HW * NHID, esz); hmap = d_map + (size_t)kprev * Wn;
                 ca.ls_c_in = h->lstm_c1.p + (size_t)dir * NF * cf;
             } else {
-                hprev = at(hall, (size_t)kprev * kst); hmap = nullptr;
+                hprev = at(hall, (size_t)kprev * kst, esz); hmap = nullptr;
                 ca.ls_c_in = h->lstm_c.p;
             }
             ca.in0 = hprev; ca.in0_map = hmap;
             if (unhoist) {                                  // ls_mode 3: source 0 = the step's feature frames (through ls_gx_map), source 1 = the previous hidden maps (through in0_map)
                 ca.ls_mode = 3;
                 ca.in0 = feat; ca.in1 = hprev; ca.C1 = NHID;
-                ca.wpk = dev_ptr(h, dir ? "lstm_bw/wxh_bf16" : "lstm_fw/wxh_bf16");
-                ca.bias = dev_ptr(h, "lstm/bx_bf16") + dir * 64;
+                ca.wpk = P.lstm_wxh[dir];
+                ca.bias = P.lstm[1].bx + dir * 64;
             }
             ca.ls_c_out = h->lstm_c.p;
-            ca.out = at(hall, (size_t)k * kst);
+            ca.out = at(hall, (size_t)k * kst, esz);
             hipError_t e = wsf ? launch_lstm_ws(ca, s) : launch_wino24_lstm(ca, tc, s);
             if (e != hipSuccess) { set_error("ConvLSTM step launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
         }
@@ -1310,7 +1330,7 @@ int cine_aux(DevBuf &buf, long long &have, long long key, const std::vector<int>
     if (have != key) {
         HIP_TRY(hipStreamSynchronize(s), UKBB_EDEVICE);                      // nothing in flight may still read the old tables
         have = -1;                                                           // until every table is up
-        HIP_TRY(buf.ensure((total + 3) / 4), UKBB_ENOMEM);
+        HIP_TRY(buf.ensure_bytes(total), UKBB_ENOMEM);
         char *aux0 = reinterpret_cast<char *>(buf.p);
         HIP_TRY(hipMemcpy(aux0, map.data(), b_map, hipMemcpyHostToDevice), UKBB_EDEVICE);
         HIP_TRY(hipMemcpy(aux0 + off_ord, order.data(), b_ord, hipMemcpyHostToDevice), UKBB_EDEVICE);
@@ -1335,7 +1355,6 @@ int t3d_forward_seq(ukbb_fcn_handle *h, const float *image, int n_seq, int heigh
     h->t3d_map = nullptr;
     return run_plan(h, image, n_seq * h->arch.fc, logits, prob, pred, s);
 }
-
 
 // The windowed deploy loop (deploy_network_ao.py:129-183) for one slice position: every window runs the whole 3-D network
 // on its T frames (gathered from the cine by the first layer through the window -> frame table); windows go in chunks, in
@@ -1430,7 +1449,7 @@ int ukbb_fcn_forward_seq(ukbb_fcn_handle *h, const float *image, int n_seq, int 
     const long long key = ((long long)n_seq << 8) | T;                       // tables depend on (n_seq, T) only
     if (h->lstm_aux_key != key) {                                            // first call for this shape: upload (blocking)
         HIP_TRY(hipStreamSynchronize(s), UKBB_EDEVICE);                      // nothing in flight may still read the old tables
-        HIP_TRY(h->lstm_aux.ensure((map.size() * sizeof(int) + 3) / 4), UKBB_ENOMEM);
+        HIP_TRY(h->lstm_aux.ensure_bytes(map.size() * sizeof(int)), UKBB_ENOMEM);
         HIP_TRY(hipMemcpy(h->lstm_aux.p, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice), UKBB_EDEVICE);
         h->lstm_aux_key = key;
     }
@@ -1441,19 +1460,17 @@ int ukbb_fcn_forward_seq(ukbb_fcn_handle *h, const float *image, int n_seq, int 
     }
     const int NF = n_seq * T, NHID = h->arch.same_dim;
     const int *d_map = reinterpret_cast<const int *>(h->lstm_aux.p);
-    rc = run_bilstm(h, h->act[h->feat_buf]->p, NF, d_map, n_seq, height, width, s);
+    rc = run_bilstm(h, h->acts[h->plan.feat_buf].buf.p, NF, d_map, n_seq, height, width, s);
     if (rc) return rc;
-    const size_t kst = (size_t)n_seq * HW * NHID;
+    const size_t kst = (size_t)n_seq * HW * NHID, esz = h->plan.mode.bfio() ? 2 : 4;
     for (int k = 0; k < T; ++k) {                                            // outputs straight into [N][T] order
         LstmOutArgs oa{};
-        const size_t esz = h->mode.bfio() ? 2 : 4;
-        auto at = [esz](const float *p, size_t elems) { return reinterpret_cast<const float *>(reinterpret_cast<const char *>(p) + elems * esz); };
-        oa.h_bf16 = h->mode.bfio() ? 1 : 0;
-        oa.hf = k == 0 ? h->lstm_h1.p : at(h->lstm_hall.p, (size_t)k * kst);
+        oa.h_bf16 = h->plan.mode.bfio() ? 1 : 0;
+        oa.hf = k == 0 ? h->lstm_h1.p : at(h->lstm_hall.p, (size_t)k * kst, esz);
         oa.mapf = k == 0 ? d_map : nullptr;
-        oa.hb = k == T - 1 ? at(h->lstm_h1.p, (size_t)NF * HW * NHID) : at(h->lstm_hall.p, (size_t)T * kst + (size_t)k * kst);
+        oa.hb = k == T - 1 ? at(h->lstm_h1.p, (size_t)NF * HW * NHID, esz) : at(h->lstm_hall.p, (size_t)T * kst + (size_t)k * kst, esz);
         oa.mapb = k == T - 1 ? d_map + (size_t)(T - 1) * n_seq : nullptr;
-        oa.w_out = dev_ptr(h, "lstm_out/w"); oa.b_out = dev_ptr(h, "lstm_out/bias");
+        oa.w_out = h->par.lstm_out_w; oa.b_out = h->par.lstm_out_b;
         oa.prob = out + (size_t)k * HW * C;
         oa.logits = logits ? logits + (size_t)k * HW * C : nullptr;
         oa.pred = pred ? pred + (size_t)k * HW : nullptr;
@@ -1493,7 +1510,7 @@ int ukbb_fcn_forward_cine(ukbb_fcn_handle *h, const float *image, int n_frames, 
         return UKBB_EINVAL;
     }
     const int Wc = pl.Wc;
-    if (pl.chunks > 1 && h->mode.bfio() && (h->lstm_bf_wino || !h->lstm_bf_hoist)) {
+    if (pl.chunks > 1 && h->plan.mode.bfio() && (h->plan.lstm_bf_wino || !h->plan.lstm_bf_hoist)) {
         set_error("forward_cine: the A/B forms UKBB_LSTM_BF16_WINOGRAD / UKBB_LSTM_BF16_UNHOIST run unchunked only (unset them or the scratch budget)");
         return UKBB_EINVAL;
     }
@@ -1527,8 +1544,7 @@ int ukbb_fcn_forward_cine(ukbb_fcn_handle *h, const float *image, int n_frames, 
     rc = cine_aux(h->lstm_aux, h->lstm_aux_key, key, map, order, wk, wsum, s, aux);
     if (rc) return rc;
     const int NHID = h->arch.same_dim;
-    const size_t esz = h->mode.bfio() ? 2 : 4;
-    auto at = [esz](const float *p, size_t elems) { return reinterpret_cast<const float *>(reinterpret_cast<const char *>(p) + elems * esz); };
+    const size_t esz = h->plan.mode.bfio() ? 2 : 4;
     if (pl.chunks > 1) HIP_TRY(h->lstm_img.ensure((size_t)pl.run * HW), UKBB_ENOMEM);
     for (int w0 = 0; w0 < Wn; w0 += Wc) {
         const int nw = std::min(Wc, Wn - w0);
@@ -1543,15 +1559,15 @@ int ukbb_fcn_forward_cine(ukbb_fcn_handle *h, const float *image, int n_frames, 
         rc = run_plan(h, frames, R, nullptr, nullptr, nullptr, s);          // each frame's U-Net features, once per chunk that reads it
         if (rc) return rc;
         const int *d_map = aux.map + (size_t)T * w0;
-        rc = run_bilstm(h, h->act[h->feat_buf]->p, R, d_map, nw, height, width, s);
+        rc = run_bilstm(h, h->acts[h->plan.feat_buf].buf.p, R, d_map, nw, height, width, s);
         if (rc) return rc;
         LstmTileArgs ta{};
         ta.k_stride = (long long)nw * HW * NHID;
-        ta.h_bf16 = h->mode.bfio() ? 1 : 0;
-        ta.hf = h->lstm_hall.p; ta.hb = at(h->lstm_hall.p, (size_t)T * ta.k_stride);
-        ta.h1f = h->lstm_h1.p; ta.h1b = at(h->lstm_h1.p, (size_t)R * HW * NHID);
+        ta.h_bf16 = h->plan.mode.bfio() ? 1 : 0;
+        ta.hf = h->lstm_hall.p; ta.hb = at(h->lstm_hall.p, (size_t)T * ta.k_stride, esz);
+        ta.h1f = h->lstm_h1.p; ta.h1b = at(h->lstm_h1.p, (size_t)R * HW * NHID, esz);
         ta.map_first = d_map; ta.map_last = d_map + (size_t)(T - 1) * nw;
-        ta.w_out = dev_ptr(h, "lstm_out/w"); ta.b_out = dev_ptr(h, "lstm_out/bias");
+        ta.w_out = h->par.lstm_out_w; ta.b_out = h->par.lstm_out_b;
         ta.tb = aux.tb;
         ta.prob = prob; ta.pred = pred; ta.Wn = nw; ta.HW = (int)HW; ta.C = C;
         ta.w0 = w0; ta.w1 = w0 + nw; ta.first = w0 == 0; ta.last = w0 + nw == Wn;
@@ -1563,27 +1579,20 @@ int ukbb_fcn_forward_cine(ukbb_fcn_handle *h, const float *image, int n_frames, 
 
 int ukbb_fcn_num_kernels(const ukbb_fcn_handle *h) { return h ? (int)h->ops.size() : 0; }
 
-const char *ukbb_fcn_kernel_name(const ukbb_fcn_handle *h, int i) {
-    if (!h || i < 0 || i >= (int)h->ops.size()) return "";
-    return h->ops[i].name.c_str();
-}
+static const BoundOp *op_at(const ukbb_fcn_handle *h, int i) { return h && i >= 0 && i < (int)h->ops.size() ? &h->ops[i] : nullptr; }
 
-double ukbb_fcn_kernel_macs(const ukbb_fcn_handle *h, int i) {
-    if (!h || i < 0 || i >= (int)h->ops.size()) return 0.0;
-    return h->ops[i].macs_per_image * h->last_n;
-}
+const char *ukbb_fcn_kernel_name(const ukbb_fcn_handle *h, int i) { return op_at(h, i) ? op_at(h, i)->name.c_str() : ""; }
+
+double ukbb_fcn_kernel_macs(const ukbb_fcn_handle *h, int i) { return op_at(h, i) ? op_at(h, i)->macs_per_image * h->last_n : 0.0; }
 
 double ukbb_fcn_kernel_mfma_macs(const ukbb_fcn_handle *h, int i) {
-    if (!h || i < 0 || i >= (int)h->ops.size()) return 0.0;
-    const Op &op = h->ops[i];
-    return (op.mfma_macs_per_image >= 0 ? op.mfma_macs_per_image : op.macs_per_image) * h->last_n;
+    const BoundOp *op = op_at(h, i);
+    return op ? (op->mfma_macs_per_image >= 0 ? op->mfma_macs_per_image : op->macs_per_image) * h->last_n : 0.0;
 }
 
 double ukbb_fcn_kernel_mfma_macs_issued(const ukbb_fcn_handle *h, int i) {
-    if (!h || i < 0 || i >= (int)h->ops.size()) return 0.0;
-    const Op &op = h->ops[i];
-    if (op.padded_macs_per_image >= 0) return op.padded_macs_per_image * h->last_n;
-    return ukbb_fcn_kernel_mfma_macs(h, i);
+    const BoundOp *op = op_at(h, i);
+    return op && op->padded_macs_per_image >= 0 ? op->padded_macs_per_image * h->last_n : ukbb_fcn_kernel_mfma_macs(h, i);
 }
 
 int ukbb_fcn_set_precision(ukbb_fcn_handle *h, int precision) {
@@ -1601,8 +1610,8 @@ int ukbb_fcn_set_precision(ukbb_fcn_handle *h, int precision) {
 }
 
 int ukbb_fcn_kernel_config(const ukbb_fcn_handle *h, int i) {
-    if (!h || i < 0 || i >= (int)h->ops.size() || (h->ops[i].kind != OP_CONV && h->ops[i].kind != OP_TCONV)) return -1;
-    return h->ops[i].cfg;
+    const BoundOp *op = op_at(h, i);
+    return op && (op->kind == OP_CONV || op->kind == OP_TCONV) ? op->cfg : -1;
 }
 
 int ukbb_fcn_head_tail_form(void) { return head_tail_form(); }
@@ -1647,53 +1656,38 @@ int ukbb_fcn_kernel_times(ukbb_fcn_handle *h, double *sum_ms, int64_t *count, in
 
 int64_t ukbb_fcn_get_activation(ukbb_fcn_handle *h, const char *name, float *dst, int64_t cap) {
     if (!h || !name) { set_error("get_activation: NULL argument"); return UKBB_EINVAL; }
-    for (size_t i = 0; i < h->act.size(); ++i) {
-        if (h->act_name[i] != name) continue;
-        const int64_t n = (int64_t)h->act_per_image[i] * h->last_n;
-        if (!dst) return n;
-        if (cap < n) { set_error("get_activation: buffer too small (%lld < %lld)", (long long)cap, (long long)n); return UKBB_EINVAL; }
-        if (h->act_esz[i] == 2) {                      // stored as bf16: widen on the host
-            std::vector<uint16_t> tmp((size_t)n);
-            if (hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-                hipMemcpy(tmp.data(), h->act[i]->p, (size_t)n * 2, hipMemcpyDeviceToHost) != hipSuccess) {
-                set_error("get_activation: device copy failed");
-                return UKBB_EDEVICE;
-            }
-            // channel-blocked on the device ([N][C/16][H][W][16], kernels.h); handed out as NHWC like the fp32 plans' maps
-            const int64_t C = h->act_ch[i], per = (int64_t)h->act_per_image[i], hw = C > 0 ? per / C : 0;
-            for (int64_t k = 0; k < n; ++k) {
-                int64_t src = k;
-                if (C > 16 && C % 16 == 0) {
-                    const int64_t img = k / per, r = k - img * per, px = r / C, c = r - px * C;
-                    src = img * per + ((c >> 4) * hw + px) * 16 + (c & 15);
-                }
-                const uint32_t u = (uint32_t)tmp[(size_t)src] << 16; memcpy(dst + k, &u, 4);
-            }
-            return n;
-        }
-        if (hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-            hipMemcpy(dst, h->act[i]->p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
-            set_error("get_activation: device copy failed");
-            return UKBB_EDEVICE;
-        }
-        return n;
+    // an activation map of the plan by its name, or a ConvLSTM working buffer raw (tools/debug_lstm.py decodes the lane-native ones):
+    // whatever the last sequence call left in it
+    const ActMap *map = nullptr;
+    const DevBuf *src = nullptr;
+    int64_t n = 0;
+    for (const ActMap &m : h->acts)
+        if (!src && m.name == name) { map = &m; src = &m.buf; n = (int64_t)m.per_image * h->last_n; }
+    for (const HandleBuf &b : HANDLE_BUFS)
+        if (!src && b.raw && !strcmp(b.raw, name)) { src = &(h->*b.buf); n = (int64_t)src->n; }
+    if (!src) { set_error("get_activation: no activation named '%s'", name); return UKBB_EINVAL; }
+    if (!dst) return n;
+    if (cap < n) { set_error("get_activation: buffer too small (%lld < %lld)", (long long)cap, (long long)n); return UKBB_EINVAL; }
+    const bool bf = map && map->esz == 2;              // stored as bf16: widen on the host
+    std::vector<uint16_t> tmp(bf ? (size_t)n : 0);
+    if (hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(bf ? (void *)tmp.data() : (void *)dst, src->p, (size_t)n * (bf ? 2 : 4), hipMemcpyDeviceToHost) != hipSuccess) {
+        set_error("get_activation: device copy failed");
+        return UKBB_EDEVICE;
     }
-    // ConvLSTM working buffers, raw (tools/debug_lstm.py decodes the lane-native ones): whatever the last sequence call left in them
-    for (const auto &kv : {std::pair<const char *, const DevBuf *>{"lstm:h1", &h->lstm_h1}, {"lstm:hall", &h->lstm_hall}, {"lstm:gx", &h->lstm_gx},
-                           {"lstm:c1", &h->lstm_c1}, {"lstm:c", &h->lstm_c}}) {
-        if (strcmp(kv.first, name)) continue;
-        const int64_t n = (int64_t)kv.second->n;
-        if (!dst) return n;
-        if (cap < n) { set_error("get_activation: buffer too small (%lld < %lld)", (long long)cap, (long long)n); return UKBB_EINVAL; }
-        if (hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-            hipMemcpy(dst, kv.second->p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
-            set_error("get_activation: device copy failed");
-            return UKBB_EDEVICE;
+    if (bf) {
+        // channel-blocked on the device ([N][C/16][H][W][16], kernels.h); handed out as NHWC like the fp32 plans' maps
+        const int64_t C = map->ch, per = (int64_t)map->per_image, hw = C > 0 ? per / C : 0;
+        for (int64_t k = 0; k < n; ++k) {
+            int64_t at_k = k;
+            if (C > 16 && C % 16 == 0) {
+                const int64_t img = k / per, r = k - img * per, px = r / C, c = r - px * C;
+                at_k = img * per + ((c >> 4) * hw + px) * 16 + (c & 15);
+            }
+            const uint32_t u = (uint32_t)tmp[(size_t)at_k] << 16; memcpy(dst + k, &u, 4);
         }
-        return n;
     }
-    set_error("get_activation: no activation named '%s'", name);
-    return UKBB_EINVAL;
+    return n;
 }
 
 }  // extern "C"

@@ -37,10 +37,7 @@ struct Op {                    // one kernel launch of the plan
     double macs_per_image = 0; // algorithmic
     double mfma_macs_per_image = -1; // issued to the matrix pipe; -1 = same as algorithmic
     double padded_macs_per_image = -1;   // ... including the slots of partly filled tiles / Winograd regions; -1 = same as mfma_macs_per_image
-    // resolved by engine.cpp's materialize_plan (null in a PlanLayout)
-    const float *wpk = nullptr, *bias = nullptr;
-    const float *wph[4] = {nullptr, nullptr, nullptr, nullptr};   // OP_TCONV3D: packed weights of the 4 sub-pixel phases
-};
+};                             // plan data only: engine.cpp's BoundOp adds the device pointers a launch of it takes
 
 struct ActSpec { std::string name; size_t per_image; int channels; int esz = 4; };   // per_image: elements per image; channels 0: not a channel map;
                                                                                        // esz: bytes of a stored element (2: bf16)
