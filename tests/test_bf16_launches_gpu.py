@@ -9,18 +9,16 @@ placements; the fused stem and tail below, between and above one and two rounds,
 tests/test_bf16_launch_coverage.py computes all of that on the CPU from the host planner and the launchers' constants, shows that CASES reaches it
 with no case idle, and that the grade and the copy identity used here tell a planted defect.
 
-One forward per case on a fresh engine created under UKBB_DEBUG_GUARD (every buffer filled with a bf16 NaN pattern when it is allocated, and again by
-Engine.poison() in front of the forward): a tile no walker wrote holds NaN, not a leftover.  The plan that ran (kernel_names() / kernel_configs()) must
-be the plan the CPU test counted (engine.plan_layout on 256 compute units).
-
-Inputs: batch_of_copies of tests/test_fp32_launches_gpu.py, img[i] = distinct[i % 3] (phantom, uniform noise, scaled normal noise), normalised as
-tests/test_bf16_layers_gpu.py does.  The worker of tile t differs between the copies of an image, so a dropped, duplicated or misdirected tile breaks
-either the grade of slices 0..2 or the identity of a later slice with them.
+The method is the graders' common one (tests/launch_grading.py), on a guarded, poisoned engine: one forward per case on a fresh engine created
+under UKBB_DEBUG_GUARD and poisoned again by Engine.poison() in front of the forward, so a tile no walker wrote holds NaN, not a leftover; the plan
+that ran must be the plan the CPU test counted (engine.plan_layout on 256 compute units); inputs are normalised_copies.  The worker of tile t differs
+between the copies of an image, so a dropped, duplicated or misdirected tile breaks either the grade of slices 0..2 or the identity of a later slice
+with them.
   * slices 0..2 of every stored map are graded in float64 from the engine's stored input map(s) of that launch with the bf16-rounded folded kernel
-    (bf16_round, fold, layer, half_ulp, grade of tests/test_bf16_layers_gpu.py): grade(ulps = 0.5, fraction = 1.0) -- half a bf16 ulp + 2^-18 |exact| +
+    (layer(round_w=True) and grade of tests/launch_grading.py): grade(ulps = 0.5, fraction = 1.0) -- half a bf16 ulp + 2^-18 |exact| +
     2^-20 scale, for EVERY element;
   * the fused stem (image -> conv0_0 -> conv0_1) and the fused tail (up0_0 -> up0_1 -> logits, argmax) are graded as units with their intermediate
-    rounding and that test's figures: 4 ulps for every element and half an ulp for 99.5 % (stem); logits within 2e-2 of their scale, 99 % within 2e-4,
+    rounding and the figures of tests/test_bf16_layers_gpu.py: 4 ulps for every element and half an ulp for 99.5 % (stem); logits within 2e-2 of their scale, 99 % within 2e-4,
     label flips only next to a tie (tail).  The stem's un-stored conv0_0 value may legitimately round either way where it lies within fp32 error of
     a rounding boundary; on these rough inputs that moves an output the other taps cancel by more than 4 of ITS ulps (measured: 2 elements of 3.1 M
     at 17 x 256 x 256 on the MI355X at 5.4 ulps, and a float32 numpy evaluation of the same arithmetic shows the same), so exactly those outputs get
@@ -50,154 +48,21 @@ the 32-row MFMA and up0_1 on the tile-per-workgroup 236, on whole and on ragged 
 
 Measured on an MI355X: profiles/bf16_launches.txt (one row per launch: case, layer, tiling, round class, share of elements within the half-ulp
 grade, worst deviation over the bound; per case the seconds of forward + read-back + identity and of float64)."""
-import re
 import time
 
 import numpy as np
 import pytest
 
+from launch_grading import (CUS, POISON, SEEDS, Report, assert_plan_ran, bf16_round, check_copies, fetcher, fold, grade, guarded_engine, half_ulp, launch_class,
+                            launches, layer, normalised_copies, tolerance)
 from oracle import fcn_oracle as O
-import test_fp32_launches_gpu as L32
-from test_bf16_layers_gpu import bf16_round, fold, grade, half_ulp, layer
 
 pytestmark = pytest.mark.gpu
-SEEDS = (1234, 7)
-POISON = '7FC07FC0'                                                # bf16 NaN pairs (one fp32 NaN): no layer produces it from finite inputs
-CUS = 256                                                          # the plans are counted for an MI355X (tests/test_bf16_launch_coverage.py)
 
 CASES = [(1, 32, 48), (1, 48, 32), (1, 16, 112), (1, 112, 16), (1, 48, 80), (129, 16, 208), (9, 256, 256), (17, 256, 256), (103, 80, 208),
          (128, 128, 208), (114, 144, 208)]
 # (sequences, H, W, tiling of up0_0, tiling of up0_1): T = 9 frames each
 SEQ_CASES = [(1, 16, 48, 232, 232), (2, 32, 64, 401, 236), (1, 48, 80, 401, 236)]
-
-# ---- the launchers' grid arithmetic (constants asserted against the sources in tests/test_bf16_launch_coverage.py) ----
-WS_TW = 32
-STEM_R, STEM_NW, STEM_TW, STEM_WG_PER_CU = 8, 4, 30, 2
-TAIL_R, TAIL_NW, TAIL_TW = 8, 8, 14
-LAUNCHER_KNOBS = ('UKBB_WS_XCD_LOCAL', 'UKBB_TAIL_STRIPS', 'UKBB_TAIL_SEG')      # A/B switches of launch_conv_ws / launch_unet_tail: unset here
-
-
-def config_name(cfg):
-    from ukbb_cardiac_amd import _lib
-    return _lib.lib.ukbb_fcn_conv_config_name(cfg).decode()
-
-
-def ws_shape(cfg):
-    """(rows, cb, waves, transposed) of a weight-stationary tiling, from its name: "..._r<rows>x32_cb<cb>_w<waves>"."""
-    name = config_name(cfg)
-    m = re.search(r'^(t?)convBF16w[sr]_\dx\d(?:s1)?_r(\d+)x%d_cb(\d+)_w(\d+)$' % WS_TW, name)
-    assert m, name
-    return int(m.group(2)), int(m.group(3)), int(m.group(4)), m.group(1) == 't'
-
-
-def round_class(ntiles, nworkers):
-    if ntiles <= nworkers:
-        return 'below'
-    if ntiles < 2 * nworkers:
-        return 'between'
-    return 'two+ exact' if ntiles % nworkers == 0 else 'two+ ragged'
-
-
-def ws_launch(op, acts, n, cus=CUS):
-    """launch_conv_ws's arithmetic for one plan op: tiles, grid, workers, round class, tile order, columns, placement."""
-    R, cb, wn, transposed = ws_shape(op['cfg'])
-    ch = acts[op['out']]['channels']
-    cout = 4 * ch if transposed else -(-ch // 32) * 32             # transposed: 4 phases x up2 virtual channels; up0_0 of UNet-LSTM: 16 padded to 32
-    per_group = 64 if transposed else 32 * cb
-    assert cout % per_group == 0, (op, ch)
-    nG = cout // per_group
-    H, W = op['H'], op['W']                                         # a transposed conv walks its INPUT map
-    ntiles = n * -(-H // R) * -(-W // WS_TW)
-    want = -(-ntiles // wn) * nG
-    grid = cus // (8 * nG) * (8 * nG) if cus >= 8 * nG else cus // nG * nG
-    grid = max(grid, nG)
-    if want < grid:
-        grid = -(-want // nG) * nG
-    nworkers = grid // nG * wn
-    return dict(ntiles=ntiles, nworkers=nworkers, grid=grid, nG=nG, cls=round_class(ntiles, nworkers), order='xcd' if H * W >= 128 * 128 else 'wave',
-                cols='ragged columns' if W % WS_TW else 'whole columns', place='grid 8 nG' if grid % (8 * nG) == 0 else 'grid not 8 nG')
-
-
-def stem_launch(n, H, W, cus=CUS):
-    ntiles = n * -(-H // STEM_R) * -(-W // STEM_TW)
-    grid = min(-(-ntiles // STEM_NW), STEM_WG_PER_CU * cus)
-    return dict(ntiles=ntiles, nworkers=grid * STEM_NW, cls=round_class(ntiles, grid * STEM_NW))
-
-
-def tail_launch(n, H, W, cus=CUS):
-    """launch_unet_tail: grid, and the segment length of the strip walk (the split whose busiest worker has the fewest tiles; the longest among equals)."""
-    tiles_y, tiles_x = -(-H // TAIL_R), -(-W // TAIL_TW)
-    ntiles = n * tiles_y * tiles_x
-    grid = min(-(-ntiles // TAIL_NW), cus)
-    workers = grid * TAIL_NW
-    best, best_seg = -1, tiles_y
-    for segs in range(1, tiles_y + 1):
-        seg = -(-tiles_y // segs)
-        if -(-tiles_y // seg) != segs:
-            continue
-        cost = -(-(n * tiles_x * segs) // workers) * seg
-        if best < 0 or cost < best:
-            best, best_seg = cost, seg
-    return dict(ntiles=ntiles, nworkers=workers, cls=round_class(ntiles, workers), seg=best_seg, segs=-(-tiles_y // best_seg), ragged=tiles_y % best_seg != 0)
-
-
-def launch_class(op, acts, n):
-    """The round class of a plan op as the record's rows name it ('-' for a tile-per-workgroup launch)."""
-    if op['kind'] == 'stem':
-        return stem_launch(n, op['H'], op['W'])['cls']
-    if op['kind'] == 'tail':
-        return tail_launch(n, op['H'], op['W'])['cls']
-    if op['kind'] in ('conv', 'tconv') and op['cfg'] >= 400:
-        w = ws_launch(op, acts, n)
-        return '%s %s' % (w['cls'], w['order'])
-    return '-'
-
-
-# ---- inputs, identity, grade ----
-def normalised_copies(index, n, H, W):
-    """batch_of_copies, normalised as tests/test_bf16_layers_gpu.py normalises its phantom."""
-    img, nd = L32.batch_of_copies(index, n, H, W)
-    return ((img - np.float32(0.3)) / np.float32(0.25)).astype(np.float32), nd
-
-
-def check_copies(name, a, nd, what=''):
-    """a[i] for i >= nd must be bit-identical to a[i % nd]; no NaN (the poison pattern) anywhere."""
-    bits = a.view(np.uint32 if a.dtype.itemsize == 4 else a.dtype)
-    if a.dtype.kind == 'f':
-        assert not np.isnan(a).any(), '%s: holds the poison pattern (NaN) at slice, y, x, channel %s %s' % (name, tuple(int(v[0]) for v in np.nonzero(np.isnan(a))), what)
-    for i in range(nd):
-        same = bits[i + nd::nd] == bits[i]
-        if not same.all():
-            k = tuple(int(v[0]) for v in np.nonzero(~same))
-            raise AssertionError('%s: slice %d differs from slice %d of the same image at y, x, channel %s %s' % (name, i + nd * (k[0] + 1), i, k[1:], what))
-
-
-def check_bf16(name, a):
-    assert not (a.view(np.uint32) & np.uint32(0xffff)).any(), '%s: stored values are not bf16' % name
-
-
-def measure(got, exact, scale, ulps=0.5):
-    """(share of the elements inside grade()'s tolerance at `ulps`, worst |got - exact| over that tolerance)."""
-    got = np.asarray(got, np.float64).reshape(exact.shape)
-    tol = 2 * ulps * half_ulp(exact) + np.abs(exact) * 2.0 ** -18 + scale * 2.0 ** -20
-    r = np.abs(got - exact) / tol
-    return float(np.mean(r <= 1.0)), float(r.max())
-
-
-class Report:
-    """Rows of one case, printed as they are measured (before the assertion that may end the test)."""
-
-    def __init__(self, tag, ops, acts, n):
-        self.tag, self.n, self.acts, self.rows = tag, n, acts, []
-        self.op_of = {part: o for o in ops for part in o['name'].split('+')}
-
-    def row(self, lname, got, exact, scale):
-        o = self.op_of[lname]
-        share, worst = measure(got, exact, scale)
-        cfg = o['cfg'] if o['kind'] in ('conv', 'tconv') else -1
-        r = (self.tag, o['name'], cfg, launch_class(o, self.acts, self.n), share, worst)
-        self.rows.append(r)
-        print('bf16-launch %-22s %-18s tiling %3d  %-18s within half an ulp %.6f  worst / bound %.3f' % r)
 
 
 def stem_reference(img, params, kind):
@@ -223,7 +88,7 @@ def stem_reference(img, params, kind):
     amb = (np.abs(q - np.floor(q) - 0.5) * ulp <= 10 * 2.0 ** -24 * mag) & (pre > 0)
     w1 = bf16_round(fold(params['conv0_1'])[0]).astype(np.float64)
     slack = O.conv2d_same(np.where(amb, ulp, 0.0), np.abs(w1), 1)
-    ex = layer(bf16_round(pre.astype(np.float32)), params['conv0_1'])
+    ex = layer(bf16_round(pre.astype(np.float32)), params['conv0_1'], round_w=True)
     return ex, slack, int(amb.sum())
 
 
@@ -231,7 +96,7 @@ def grade_stem(got, ex, sc, slack):
     """The figures of tests/test_bf16_layers_gpu.py for the stem: every element within 4 bf16 ulps (+ slack where an ambiguous conv0_0 value feeds it),
     99.5 % within half an ulp."""
     got = np.asarray(got, np.float64).reshape(ex.shape)
-    tol = 2 * 4.0 * half_ulp(ex) + np.abs(ex) * 2.0 ** -18 + sc * 2.0 ** -20 + slack
+    tol = tolerance(ex, sc, 4.0) + slack
     bad = np.abs(got - ex) > tol
     assert not bad.any(), 'conv0_0+conv0_1: %d elements further than 4 bf16 ulps from the specified result, worst %.3g x the bound at slice, y, x, channel %s' % (
         int(bad.sum()), float((np.abs(got - ex) / tol).max()), np.unravel_index(int((np.abs(got - ex) / tol).argmax()), ex.shape))
@@ -245,7 +110,7 @@ def grade_unet(arch, params, ops, img, fetch, logits, pred, report):
     assert len(first) == 1 and first[0]['name'] == 'conv0_0+conv0_1' and first[0]['kind'] in ('stem', 'conv'), first
     tails = [o for o in ops if o['kind'] == 'tail']
     assert len(tails) == 1 and tails[0]['name'] == 'up0_0+up0_1+logits', [o['name'] for o in ops]
-    for lname, sname, l, srcs, stride, transposed, relu in L32.launches(arch):
+    for lname, sname, l, srcs, stride, transposed, relu in launches(arch):
         if lname in ('conv0_0', 'up0_0', 'up0_1', 'logits'):
             continue
         if lname == 'conv0_1':
@@ -258,7 +123,7 @@ def grade_unet(arch, params, ops, img, fetch, logits, pred, report):
             grade_stem(got, ex, sc, slack)
             continue
         x = np.concatenate([fetch(s) for s in srcs], axis=-1)
-        ex = layer(x, params[lname], stride, transposed, relu)
+        ex = layer(x, params[lname], stride, transposed, relu, round_w=True)
         sc = float(np.abs(ex).max())
         got = fetch(sname)
         report.row(lname, got, ex, sc)
@@ -275,7 +140,7 @@ def grade_unet(arch, params, ops, img, fetch, logits, pred, report):
 def tail_reference(a, params):
     """The fused tail as a unit, float64 logits: up0_0 -> bf16 -> up0_1 -> bf16 -> logits (fp32 kernel; the engine enters it as bf16 hi + lo)."""
     for nm in ('up0_0', 'up0_1'):
-        a = bf16_round(layer(a, params[nm]).astype(np.float32))
+        a = bf16_round(layer(a, params[nm], round_w=True).astype(np.float32))
     pl = params['logits']
     return O.conv2d_same(a.astype(np.float64), pl['kernel'].astype(np.float64), 1) + pl['bias'].astype(np.float64)
 
@@ -294,34 +159,12 @@ def grade_up0(params, fetch, report):
     """up0_0 and up0_1 of the UNet-LSTM's U-Net, each from the stored map(s) in front of it."""
     x = np.concatenate([fetch('conv0'), fetch('up0_t')], axis=-1)          # skip first (network_ao.py:51)
     for lname, sname in (('up0_0', 'up0_0'), ('up0_1', 'up0')):
-        ex = layer(x, params[lname])
+        ex = layer(x, params[lname], round_w=True)
         sc = float(np.abs(ex).max())
         got = fetch(sname)
         report.row(lname, got, ex, sc)
         grade('%s (tiling %d)' % (lname, report.op_of[lname]['cfg']), got, ex, sc, ulps=0.5, fraction=1.0)
         x = got
-
-
-def guarded_engine(monkeypatch, arch, params):
-    from ukbb_cardiac_amd.engine import Engine
-    for k in LAUNCHER_KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    monkeypatch.setenv('UKBB_DEBUG_GUARD', POISON)                   # read in ukbb_fcn_create only
-    eng = Engine(arch, params)
-    eng.set_precision('bf16')
-    return eng
-
-
-def fetcher(eng, shape_of, nd, cache, what):
-    """fetch(stored name): one activation read back, checked (bf16 values, no poison, copies identical), slices 0..nd-1 kept."""
-    def fetch(sname):
-        if sname not in cache:
-            a = eng.activation(sname).reshape(shape_of(sname))
-            check_bf16(sname, a)
-            check_copies(sname, a, nd, what)
-            cache[sname] = a[:nd].copy()
-        return cache[sname]
-    return fetch
 
 
 @pytest.mark.parametrize('index', range(len(CASES)), ids=['%dx%dx%d' % c for c in CASES])
@@ -338,18 +181,15 @@ def test_each_bf16_launch_against_its_specified_arithmetic(index, monkeypatch):
     tag = 'UNet_ao %dx%dx%d' % (n, H, W)
     t0 = time.perf_counter()
     cache = {}
-    with guarded_engine(monkeypatch, arch, params) as eng:
+    with guarded_engine(monkeypatch, arch, params, 'bf16') as eng:
         eng.reserve(n, H, W)
         eng.poison(POISON)
         out = eng.run(img, want_logits=True, want_prob=False)
         t_fwd = time.perf_counter() - t0
-        names, cfgs = eng.kernel_names(), eng.kernel_configs()
-        # the plan that ran is the one tests/test_bf16_launch_coverage.py counted for this case
-        assert names == [o['name'] for o in ops], (names, [o['name'] for o in ops])
-        assert cfgs == [o['cfg'] if o['kind'] in ('conv', 'tconv') else -1 for o in ops], (cfgs, ops)
-        level = {g[1]: g[2] for g in L32.launches(arch)}
+        assert_plan_ran(eng, plan)                                    # the plan tests/test_bf16_launch_coverage.py counted for this case
+        level = {g[1]: g[2] for g in launches(arch)}
         fetch = fetcher(eng, lambda s: (n, H >> level[s], W >> level[s], -1), nd, cache, tag)
-        for g in L32.launches(arch):                                  # every stored map read back and checked once, in graph order
+        for g in launches(arch):                                  # every stored map read back and checked once, in graph order
             if g[0] not in ('conv0_0', 'up0_0', 'up0_1', 'logits'):
                 fetch(g[1])
         damaged, where = eng.check_guards()
@@ -382,13 +222,11 @@ def test_up0_launches_of_the_unet_lstm(index, monkeypatch):
     tag = 'UNet-LSTM_ao %dx%dx%dx%d' % (N, T, H, W)
     cache = {}
     t0 = time.perf_counter()
-    with guarded_engine(monkeypatch, arch, params) as eng:
+    with guarded_engine(monkeypatch, arch, params, 'bf16') as eng:
         eng.reserve(N * T, H, W)
         eng.poison(POISON)
         eng.run_seq(img.reshape(N, T, H, W, 1), want_prob=False)   # the U-Net's maps are per frame; the ConvLSTM behind them is graded in tests/test_lstm_launches_gpu.py
-        names, cfgs = eng.kernel_names(), eng.kernel_configs()
-        assert names == [o['name'] for o in ops], (names, [o['name'] for o in ops])
-        assert cfgs == [o['cfg'] if o['kind'] in ('conv', 'tconv') else -1 for o in ops], (cfgs, ops)
+        assert_plan_ran(eng, plan)
         fetch = fetcher(eng, lambda s: (N * T, H, W, -1), nd, cache, tag)
         for s in ('conv0', 'up0_t', 'up0_0', 'up0'):
             fetch(s)

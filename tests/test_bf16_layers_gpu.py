@@ -20,54 +20,10 @@ tests/test_bf16_launches_gpu.py does the same for every (layer, tiling) combinat
 import numpy as np
 import pytest
 
+from launch_grading import bf16_round, grade, layer, tolerance
 from oracle import fcn_oracle as O
 
 pytestmark = pytest.mark.gpu
-BN_EPS = np.float32(1e-3)
-
-
-def bf16_round(x):
-    """float32 -> nearest bf16 (ties to even), returned as float32."""
-    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
-    r = ((u >> np.uint32(16)) & np.uint32(1)) + np.uint32(0x7fff)
-    return ((u + r) & np.uint32(0xffff0000)).view(np.float32)
-
-
-def fold(p, transposed=False):
-    """engine.cpp create(): sc = gamma / sqrtf(var + eps); W' = W * sc; b' = beta - mean * sc, all float32, no contraction."""
-    k = p['kernel'].astype(np.float32)
-    if 'gamma' not in p:
-        return k, p['bias'].astype(np.float32)
-    sc = (p['gamma'].astype(np.float32) / np.sqrt(p['var'].astype(np.float32) + BN_EPS)).astype(np.float32)
-    ms = (p['mean'].astype(np.float32) * sc).astype(np.float32)
-    b = (p['beta'].astype(np.float32) - ms).astype(np.float32)
-    w = (k * (sc[None, None, :, None] if transposed else sc[None, None, None, :])).astype(np.float32)
-    return w, b
-
-
-def layer(x, p, stride=1, transposed=False, relu=True):
-    """One conv2d_bn_relu / conv2d_transpose_bn_relu of the bf16 plan in float64 on the given (bf16-valued) input: the exact pre-rounding result."""
-    w, b = fold(p, transposed)
-    w = bf16_round(w).astype(np.float64)
-    x = np.asarray(x, np.float64)
-    y = (O.conv2d_transpose_same(x, w, stride) if transposed else O.conv2d_same(x, w, stride)) + b.astype(np.float64)
-    return np.maximum(y, 0.0) if relu else y
-
-
-def half_ulp(v):
-    """Half a bf16 ulp at |v| (float64 array): bf16 keeps 8 significant bits."""
-    a = np.maximum(np.abs(v), 1e-30)
-    return np.exp2(np.floor(np.log2(a)) - 8)
-
-
-def grade(name, got, exact, scale, ulps=0.5, fraction=1.0):
-    """got: the engine's stored bf16 values; exact: float64 result of the specified arithmetic before the final rounding."""
-    got = np.asarray(got, np.float64).reshape(exact.shape)
-    tol = 2 * ulps * half_ulp(exact) + np.abs(exact) * 2.0 ** -18 + scale * 2.0 ** -20
-    ok = np.abs(got - exact) <= tol
-    assert ok.mean() >= fraction, '%s: %.5f of the elements within %.1f bf16 ulp of the specified result (asked %.5f); worst %.3g at value %.3g' % (
-        name, ok.mean(), ulps, fraction, float(np.abs(got - exact).max()), float(exact.flat[np.abs(got - exact).argmax()]))
-    return float(ok.mean())
 
 
 @pytest.mark.parametrize('shape,seed', [((1, 256, 256), 1234), ((3, 64, 96), 7), ((2, 48, 16), 11)])
@@ -109,17 +65,16 @@ def test_every_bf16_launch_against_its_specified_arithmetic(shape, seed):
         assert np.array_equal(v, bf16_round(v)), k
     report = {}
     # ---- stem: image -> bf16; conv0_0 -> bf16; conv0_1 -> bf16 (kernels_stem.hip, or the fused-first tile kernel on small maps: fp32 first layer) ----
-    a00 = bf16_round(layer(bf16_round(img), params['conv0_0']).astype(np.float32))
-    ex = layer(a00, params['conv0_1'])
+    a00 = bf16_round(layer(bf16_round(img), params['conv0_0'], round_w=True).astype(np.float32))
+    ex = layer(a00, params['conv0_1'], round_w=True)
     sc = float(np.abs(ex).max())
     try:
         report['stem'] = grade('conv0_0+conv0_1', stored['conv0_1'], ex, sc, ulps=4.0)
         grade('conv0_0+conv0_1 (half ulp)', stored['conv0_1'], ex, sc, ulps=0.5, fraction=0.995)
     except AssertionError:
         # small maps: conv0_0 evaluated in fp32 on the un-rounded image inside conv0_1's staging (conv_mfma_kernel<..., FUSE = 1>)
-        w0, b0 = fold(params['conv0_0'])
-        a00 = bf16_round(np.maximum(O.conv2d_same(img.astype(np.float64), w0.astype(np.float64), 1) + b0, 0.0).astype(np.float32))
-        ex = layer(a00, params['conv0_1'])
+        a00 = bf16_round(layer(img, params['conv0_0']).astype(np.float32))
+        ex = layer(a00, params['conv0_1'], round_w=True)
         report['stem(fp32 first layer)'] = grade('conv0_0+conv0_1', stored['conv0_1'], ex, sc, ulps=4.0)
         grade('conv0_0+conv0_1 (half ulp)', stored['conv0_1'], ex, sc, ulps=0.5, fraction=0.995)
     # ---- every stored layer from the engine's own stored inputs: half an ulp, every element ----
@@ -127,25 +82,24 @@ def test_every_bf16_launch_against_its_specified_arithmetic(shape, seed):
         x = stored['conv%d_%d' % (l - 1, arch.n_block[l - 1] - 1)]
         for i in range(arch.n_block[l]):
             nm = 'conv%d_%d' % (l, i)
-            ex = layer(x, params[nm], stride=2 if i == 0 else 1)
+            ex = layer(x, params[nm], stride=2 if i == 0 else 1, round_w=True)
             report[nm] = grade(nm, stored[nm], ex, float(np.abs(ex).max()))
             x = stored[nm]
     # the grade is not vacuous: the same layer with the folded kernel NOT rounded to bf16 (what an fp32-weight path would compute) misses it
-    w, b = fold(params['conv2_1'])
-    wrong = np.maximum(O.conv2d_same(stored['conv2_0'].astype(np.float64), w.astype(np.float64), 1) + b, 0.0)
-    tol = 2 * 0.5 * half_ulp(wrong) + np.abs(wrong) * 2.0 ** -18 + float(np.abs(wrong).max()) * 2.0 ** -20
+    wrong = layer(stored['conv2_0'], params['conv2_1'])
+    tol = tolerance(wrong, float(np.abs(wrong).max()), 0.5)
     assert np.mean(np.abs(stored['conv2_1'].astype(np.float64) - wrong) <= tol) < 0.9
     up = stored['conv4_%d' % (arch.n_block[4] - 1)]
     for l in (3, 2, 1, 0):
         nm = 'up%d_t' % l
-        ex = layer(up, params[nm], stride=2, transposed=True)
+        ex = layer(up, params[nm], stride=2, transposed=True, round_w=True)
         report[nm] = grade(nm, stored[nm], ex, float(np.abs(ex).max()))
         x = np.concatenate([stored['conv%d_%d' % (l, arch.n_block[l] - 1)], stored[nm]], axis=-1)      # skip first (network_ao.py:51)
         for i in range(arch.n_block[l]):
             nm = 'up%d_%d' % (l, i)
             if nm not in stored:
                 break
-            ex = layer(x, params[nm])
+            ex = layer(x, params[nm], round_w=True)
             report[nm] = grade(nm, stored[nm], ex, float(np.abs(ex).max()))
             x = stored[nm]
         up = x
@@ -153,7 +107,7 @@ def test_every_bf16_launch_against_its_specified_arithmetic(shape, seed):
     a = x
     for i in range(arch.n_block[0]):
         if 'up0_%d' % i not in stored:
-            a = bf16_round(layer(a, params['up0_%d' % i]).astype(np.float32))
+            a = bf16_round(layer(a, params['up0_%d' % i], round_w=True).astype(np.float32))
     pl = params['logits']
     logits = O.conv2d_same(a.astype(np.float64), pl['kernel'].astype(np.float64), 1) + pl['bias'].astype(np.float64)
     lsc = float(np.abs(logits).max())

@@ -5,7 +5,7 @@ Completeness: the recorded knob-less bf16 plans of FCN_sa (tests/golden/plan_lay
 tilings and hold exactly 25 (layer, tiling) combinations on the tilings {130, 200, 201, 202, 210, 211}.  Every one is planned by some entry of CASES,
 and counts only where the case reaches it on a map its tiles divide, or do not divide, as some recorded plan of that combination has it (the rule of
 tests/test_bf16_launch_coverage.py for tile-per-workgroup tilings; tile sizes from the tiling's name, "..._t<rows>x<columns>_...", and the op's
-Ho / Wo).  "Do not divide" is told apart further (fit_of): 'ragged', whole tiles and a partial last one along an axis, and 'partial', one partial tile
+Ho / Wo).  "Do not divide" is told apart further (fit_of of tests/launch_grading.py): 'ragged', whole tiles and a partial last one along an axis, and 'partial', one partial tile
 only -- a ragged edge tile takes its halo from a neighbouring tile's pixels on one side and from the padding on the other.  Per tiling CASES also
 reaches every (fit, batch class) the records hold, the batch classes being up to plan.h SMALL_BATCH and above it: the bf16 plans do not depend on the
 batch, but the grids do, and the copy identity of the GPU file needs several images.  That is 53 requirements.  The recorded bf16 plans of FCN_la_2ch,
@@ -32,24 +32,15 @@ import re
 import numpy as np
 import pytest
 
+import launch_grading as G
 import test_bf16_operand_launches_gpu as L
 from oracle import fcn_oracle as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'plan_layouts.json')
+GOLDEN = G.GOLDEN
 LA_MODELS = ('FCN_la_2ch', 'FCN_la_4ch', 'FCN_la_4ch_seg4')
 TILINGS = {130, 200, 201, 202, 210, 211}
 BENCH = (64, 192, 208)                  # bench.py BATCH, H, W
-
-
-def fit_of(op):
-    """How the tiling's tile (from its name) fits the op's output map: 'div' (it divides both axes), 'ragged' (some axis has whole tiles AND a partial
-    last one: an edge tile whose halo comes from a neighbour on one side and from the zero padding on the other) or 'partial' (it does not divide,
-    and every axis it does not divide holds one partial tile only).  'ragged' and 'partial' together are the 'nodiv' of the sibling files."""
-    th, tw = map(int, re.search(r'_t(\d+)x(\d+)_', L.config_name(op['cfg'])).groups())
-    if op['Ho'] % th == 0 and op['Wo'] % tw == 0:
-        return 'div'
-    return 'ragged' if (op['Ho'] % th and op['Ho'] > th) or (op['Wo'] % tw and op['Wo'] > tw) else 'partial'
 
 
 def small_batch():
@@ -66,32 +57,22 @@ def batch_class(n):
 def conv_ops(n, H, W, model=L.MODEL):
     from ukbb_cardiac_amd import engine
     from ukbb_cardiac_amd.arch import MODELS
-    return [o for o in engine.plan_layout(MODELS[model], 'bf16', n, H, W, L.CUS)['ops']]
+    return [o for o in engine.plan_layout(MODELS[model], 'bf16', n, H, W, G.CUS)['ops']]
 
 
 def reached(n, H, W, model=L.MODEL):
     """{(layer, tiling): fit} of the bf16 plan's conv launches (the fused first layer as 'conv0_0+conv0_1')."""
-    return {(o['name'], o['cfg']): fit_of(o) for o in conv_ops(n, H, W, model) if o['kind'] == 'conv'}
+    return {(o['name'], o['cfg']): G.fit_of(o) for o in conv_ops(n, H, W, model) if o['kind'] == 'conv'}
 
 
 def replay_records(model):
-    """{(layer, tiling): set of (fit, batch class)} over the recorded knob-less bf16 plans of one model, each replayed (the records hold no map sizes
-    per op) and checked against its own names and tilings."""
-    assert 'UKBB_CONV_CFG' not in os.environ
-    with open(GOLDEN) as f:
-        g = json.load(f)
-    rec, n_records = collections.defaultdict(set), 0
-    for r in g['records']:
-        name, prec, H, W, n, knob, rc = r[:7]
-        if knob != '' or prec != 'bf16' or name != model:
-            continue
-        assert rc == 0, r[:7]
-        ops = conv_ops(n, H, W, model)
-        assert [o['name'] for o in ops] == g['names'][r[8]] and [o['cfg'] if o['kind'] in ('conv', 'tconv') else -1 for o in ops] == g['cfgs'][r[9]], r[:6]
-        for k, fit in reached(n, H, W, model).items():
+    """{(layer, tiling): set of (fit, batch class)} over the recorded knob-less bf16 plans of one model (G.replay_records)."""
+    replayed = G.replay_records(model, 'bf16', lambda n, H, W: reached(n, H, W, model))
+    assert len(replayed) == 48, (model, len(replayed))
+    rec = collections.defaultdict(set)
+    for n, _, _, got in replayed:
+        for k, fit in got.items():
             rec[k].add((fit, batch_class(n)))
-        n_records += 1
-    assert n_records == 48, (model, n_records)
     return dict(rec)
 
 
@@ -144,13 +125,9 @@ def test_cases_reach_every_recorded_combination_and_fit(recorded):
 
 
 def test_no_case_is_idle(recorded):
-    want = requirements(recorded)
-    per_case = [covered([c], recorded) & want for c in L.CASES]
-    assert set().union(*per_case) == want, sorted(want - set().union(*per_case), key=str)
-    for i, c in enumerate(L.CASES):
-        rest = set().union(*(per_case[:i] + per_case[i + 1:]))
-        assert want - rest, 'CASES entry %s adds nothing' % (c,)
-        print('%-14s %7d pixels; only it reaches %s' % (c, c[0] * c[1] * c[2], sorted(want - rest, key=str)))
+    only = G.no_case_is_idle(L.CASES, lambda c: covered([c], recorded), requirements(recorded))
+    for c, mine in zip(L.CASES, only):
+        print('%-14s %7d pixels; only it reaches %s' % (c, c[0] * c[1] * c[2], mine))
     assert sum(n * H * W for n, H, W in L.CASES) == 854016 and sum(min(n, 3) * H * W for n, H, W in L.CASES) == 190976        # the docstring's table
 
 
@@ -163,13 +140,13 @@ def test_graph_lists_every_planned_conv_launch():
     from ukbb_cardiac_amd import engine
     from ukbb_cardiac_amd.arch import MODELS
     arch = MODELS[L.MODEL]
-    graph = [g for g in L.launches(arch) if g[0] != 'logits']
+    graph = [g for g in G.launches(arch) if g[0] != 'logits']
     assert all(not g[5] and g[6] and len(g[3]) == 1 for g in graph)          # no transposed conv, ReLU everywhere, one source
     for n, H, W in L.CASES + L.FORCED_CASES:
         ops = conv_ops(n, H, W)
         assert [part for o in ops if o['kind'] == 'conv' for part in o['name'].split('+')] == [g[0] for g in graph]
         assert [o['name'] for o in ops if o['kind'] != 'conv'] == ['sqg1-4', 'head']
-        stored = {a['name'] for a in engine.plan_layout(arch, 'bf16', n, H, W, L.CUS)['acts']}
+        stored = {a['name'] for a in engine.plan_layout(arch, 'bf16', n, H, W, G.CUS)['acts']}
         assert {g[1] for g in graph if g[0] != 'conv0_0'} <= stored
 
 
@@ -179,7 +156,7 @@ def test_forced_tilings_are_planned_where_they_are_valid(monkeypatch):
     with open(GOLDEN) as f:
         g = json.load(f)
     assert not {L.FORCED_S1, L.FORCED_S2} & {c for cfgs in g['cfgs'] for c in cfgs}
-    assert L.config_name(L.FORCED_S1) == 'convBF16_3x3s1_t16x16_w2x2_cb1' and L.config_name(L.FORCED_S2) == 'convBF16_3x3s2_t8x16_w2x2_cb1'
+    assert G.config_name(L.FORCED_S1) == 'convBF16_3x3s1_t16x16_w2x2_cb1' and G.config_name(L.FORCED_S2) == 'convBF16_3x3s2_t8x16_w2x2_cb1'
     monkeypatch.setenv('UKBB_CONV_CFG', L.forced_spec())                  # read at every plan build (plan.cpp override_cfg)
     for index, (n, H, W) in enumerate(L.FORCED_CASES):
         got = reached(n, H, W)
@@ -206,7 +183,7 @@ def test_tilings_220_and_221_are_unreachable(monkeypatch):
             for prec in ('fp32', 'bf16', 'f32x3', 'bf16_store'):
                 for n, H, W in ((1, 64, 96), (17, 48, 16)):
                     try:
-                        ops = engine.plan_layout(arch, prec, n, H, W, L.CUS)['ops']
+                        ops = engine.plan_layout(arch, prec, n, H, W, G.CUS)['ops']
                     except _lib.UkbbFcnError:
                         refused.add((name, prec))
                         continue
@@ -216,11 +193,11 @@ def test_tilings_220_and_221_are_unreachable(monkeypatch):
                        {(k, 'bf16_store') for k, a in MODELS.items() if a.kind != KIND_FCN}), refused
     assert n_plans == 96
     monkeypatch.delenv('UKBB_CONV_CFG')
-    assert L.config_name(220).startswith('convBF16_2x2s1_') and L.config_name(221).startswith('convBF16_2x2s1_')
+    assert G.config_name(220).startswith('convBF16_2x2s1_') and G.config_name(221).startswith('convBF16_2x2s1_')
     # the FCN graph has no 2 x 2 layer: no transposed conv among its launches, nor in any of its plans; the other kinds plan bf16 storage
     for name, arch in MODELS.items():
         if arch.kind == KIND_FCN:
-            assert not [g for g in L.launches(arch) if g[5]], name
+            assert not [g for g in G.launches(arch) if g[5]], name
             assert {o['kind'] for o in conv_ops(1, 64, 96, name)} == {'conv', 'sqg_multi', 'head'}
     with open(GOLDEN) as f:
         g = json.load(f)
@@ -245,12 +222,12 @@ def truncate(x):
 def launch32(x, p, stride, defect=None):
     """One bf16-operand launch as the engine is specified to run it, in float32 numpy (products of bf16 values are exact in float32, the sum is
     float32) -- with one planted defect, if any."""
-    w, b = L.fold(p)
+    w, b = G.fold(p)
     x = np.ascontiguousarray(x, np.float32)
     if defect == DEFECTS[6]:
         x = np.concatenate([np.zeros_like(x[:, :, :1]), x[:, :, :-1]], axis=2)
-    xr = truncate(x) if defect == DEFECTS[4] else x if defect in (DEFECTS[1], DEFECTS[2]) else L.bf16_round(x)
-    wr = truncate(w) if defect == DEFECTS[3] else w if defect in (DEFECTS[0], DEFECTS[2]) else L.bf16_round(w)
+    xr = truncate(x) if defect == DEFECTS[4] else x if defect in (DEFECTS[1], DEFECTS[2]) else G.bf16_round(x)
+    wr = truncate(w) if defect == DEFECTS[3] else w if defect in (DEFECTS[0], DEFECTS[2]) else G.bf16_round(w)
     if defect == DEFECTS[5]:
         wr = wr.copy()
         wr[0, 2] = 0
@@ -267,24 +244,24 @@ def chain():
     from ukbb_cardiac_amd.weights import synthetic_params
     arch = MODELS[L.MODEL]
     rows = []
-    for seed in L.SEEDS:
+    for seed in G.SEEDS:
         params = synthetic_params(arch, seed)
-        img = L.distinct_images(H, W)
-        x = L.layer(L.layer(img, params['conv0_0']), params['conv0_1']).astype(np.float32)       # the fused first layer: fp32
-        for lname, sname, l, srcs, stride, transposed, relu in L.launches(arch):
+        img = G.distinct_images(H, W)
+        x = G.layer(G.layer(img, params['conv0_0']), params['conv0_1']).astype(np.float32)       # the fused first layer: fp32
+        for lname, sname, l, srcs, stride, transposed, relu in G.launches(arch):
             if lname in ('conv0_0', 'conv0_1', 'logits'):
                 continue
-            ex = L.rounding_model(x, params[lname], stride)
+            ex = G.layer(x, params[lname], stride, round_w=True, round_x=True)
             assert ex.shape[1:3] == (H >> l, W >> l) and ex.max() > 0
             got = launch32(x, params[lname], stride)
-            rows.append((seed, lname, L.rel_err(got, ex)[0], {d: L.rel_err(launch32(x, params[lname], stride, d), ex)[0] for d in DEFECTS},
-                         L.rel_err(L.layer(x, params[lname], stride), ex)[0]))
+            rows.append((seed, lname, G.rel_err(got, ex)[0], {d: G.rel_err(launch32(x, params[lname], stride, d), ex)[0] for d in DEFECTS},
+                         G.rel_err(G.layer(x, params[lname], stride), ex)[0]))
             x = got
     return rows
 
 
 def test_float32_stand_in_passes_the_bound_at_every_layer(chain):
-    assert len(chain) == 11 * len(L.SEEDS)
+    assert len(chain) == 11 * len(G.SEEDS)
     for seed, lname, err, _, _ in chain:
         print('stand-in seed %4d %-8s err/scale %.2e' % (seed, lname, err))
         assert err <= L.BOUND, (seed, lname, err)

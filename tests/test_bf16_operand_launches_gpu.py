@@ -8,16 +8,15 @@ stop in front of it (tests/test_fp32_launches_gpu.py: fp32 plans; tests/test_bf1
 that run this mode compare it with itself.  A bf16 x bf16 product is exact in fp32, so one launch differs from float64 on the rounded operands only
 by its fp32 accumulation:
 
-    convBF16_... launch     expected  relu(conv(bf16_round(x stored), bf16_round(fold(w))) + b)   in float64
+    convBF16_... launch     expected  relu(conv(bf16_round(x stored), bf16_round(fold(w))) + b)   in float64 (layer with round_w and round_x)
     any other launch        expected  the fp32 model of tests/test_fp32_launches_gpu.py (130: the fused first layer conv0_0 + conv0_1, from the image)
 
 The model is decided per launch from its tiling's name (ukbb_fcn_conv_config_name), not from the mode.  Per launch max |engine - model| <= BOUND x
 the layer's largest activation (rel_err); per bf16-tiling launch the engine's map must ALSO be >= 10 x BOUND away from the fp32 model of the same
 launch (operands not rounded), which a layer that quietly ran an fp32 tiling would not be; and every conv from conv1_0 on must be on a convBF16_
 tiling, as the recorded plans say.  The plan that ran (kernel_names() / kernel_configs()) must be the one the CPU test counted (plan_layout on 256
-compute units).  Method, inputs and helpers are those of tests/test_fp32_launches_gpu.py: one forward per case with want_logits, every stored encoder
-map read back with Engine.activation, a batch made of copies of at most three rough images, slices 0-2 graded in float64 and every further slice of
-every stored map and of the logits BIT-IDENTICAL to its copy; weights from seeds 1234 and 7 in turn.  The squeeze and head launches behind this
+compute units).  Method, inputs and helpers are the graders' common ones (tests/launch_grading.py), as tests/test_fp32_launches_gpu.py uses them:
+one forward per case with want_logits, every stored encoder map and the logits under the copy identity.  The squeeze and head launches behind this
 encoder are graded in tests/test_head_launches_gpu.py (mode 'bf16').
 
 CASES: FCN_sa (the records of FCN_la_2ch / FCN_la_4ch / FCN_la_4ch_seg4 are identical, tests/test_bf16_operand_launch_coverage.py), N = 1 or 17 =
@@ -60,23 +59,15 @@ tests fail: each of the 143 bf16-tiling launches that ran (the child stops after
 launches still pass."""
 import json
 import os
-import subprocess
-import sys
 import time
 
-import numpy as np
 import pytest
 
-from oracle import fcn_oracle as O
-from test_bf16_launches_gpu import CUS                                 # 256: the plans are counted for an MI355X
-from test_bf16_layers_gpu import bf16_round
-from test_fp32_launches_gpu import batch_of_copies, distinct_images, fold, launches, layer, rel_err      # noqa: F401 (distinct_images: the coverage test)
+from launch_grading import CUS, SEEDS, assert_plan_ran, batch_of_copies, check_copies, config_name, launches, layer, rel_err, run_in_child, tile_of
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BOUND = 1e-5
 APART = 10 * BOUND                      # a bf16-tiling launch is at least this far from the fp32 model of the same launch
-SEEDS = (1234, 7)
 MODEL = 'FCN_sa'
 BF_PREFIX = 'convBF16_'
 
@@ -87,21 +78,9 @@ CASES = [(1, 48, 16), (1, 32, 32), (1, 80, 16), (1, 16, 160), (1, 208, 16), (1, 
 FORCED_CASES = [(1, 256, 256), (1, 80, 112)]
 FORCED_S1, FORCED_S2 = 203, 212
 
-def config_name(cfg):
-    from ukbb_cardiac_amd import _lib
-    return _lib.lib.ukbb_fcn_conv_config_name(cfg).decode()
-
 
 def is_bf16_tiling(cfg):
     return cfg >= 0 and config_name(cfg).startswith(BF_PREFIX)
-
-
-def rounding_model(x, p, stride=1, round_x=True, round_w=True):
-    """relu(conv(bf16_round(x), bf16_round(fold(w))) + b) in float64; with both flags off it is the fp32 model (layer())."""
-    w, b = fold(p)
-    x = np.ascontiguousarray(x, np.float32)
-    x, w = (bf16_round(x) if round_x else x).astype(np.float64), (bf16_round(w) if round_w else w).astype(np.float64)
-    return np.maximum(O.conv2d_same(x, w, stride) + b.astype(np.float64), 0.0)
 
 
 def grade_forward(index, n, H, W):
@@ -120,15 +99,12 @@ def grade_forward(index, n, H, W):
     with engine.Engine(arch, params) as eng:
         eng.set_precision('bf16')
         out = eng.run(img, want_logits=True)
-        names, cfgs = eng.kernel_names(), eng.kernel_configs()
+        assert_plan_ran(eng, plan)                                       # the plan tests/test_bf16_operand_launch_coverage.py counted for this case
         stored = {'logits': out['logits']}
         for lname, sname, l, _, _, _, _ in graph:
             if lname != 'conv0_0':                                       # conv0_0 lives inside conv0_1's launch
                 stored[sname] = eng.activation(sname).reshape(n, H >> l, W >> l, -1)
     t_gpu = time.perf_counter() - t0
-    # the plan that ran is the one tests/test_bf16_operand_launch_coverage.py counted for this case
-    assert names == [o['name'] for o in plan['ops']], (names, [o['name'] for o in plan['ops']])
-    assert cfgs == [o['cfg'] if o['kind'] in ('conv', 'tconv') else -1 for o in plan['ops']], (cfgs, plan['ops'])
     cfg_of = {part: o['cfg'] for o in plan['ops'] if o['kind'] == 'conv' for part in o['name'].split('+')}
     assert set(cfg_of) == {g[0] for g in graph}, (sorted(cfg_of), graph)
     not_bf = [(k, c) for k, c in cfg_of.items() if k not in ('conv0_0', 'conv0_1') and not is_bf16_tiling(c)]
@@ -136,8 +112,7 @@ def grade_forward(index, n, H, W):
     assert stored['logits'].shape == (n, H, W, arch.n_class)
     # every slice is a bit-identical copy of the graded slice of its image, in every stored map and in the logits
     for sname, a in stored.items():
-        for i in range(nd, n):
-            assert np.array_equal(a[i], a[i % nd]), '%s: slice %d differs from slice %d of the same image (tiling %s)' % (sname, i, i % nd, cfg_of.get(sname))
+        check_copies(sname, a, nd, '(tiling %s)' % cfg_of.get(sname))
     t0 = time.perf_counter()
     tag = '%-8s %2dx%3dx%3d' % (MODEL, n, H, W)
     rows = []
@@ -151,7 +126,7 @@ def grade_forward(index, n, H, W):
         x = fused_first if lname == 'conv0_1' else stored[srcs[0]][:nd]
         fp32_model = layer(x, params[lname], stride)
         if is_bf16_tiling(cfg):
-            err, where = rel_err(stored[sname][:nd], rounding_model(x, params[lname], stride))
+            err, where = rel_err(stored[sname][:nd], layer(x, params[lname], stride, round_w=True, round_x=True))
             apart = rel_err(stored[sname][:nd], fp32_model)[0]
         else:
             (err, where), apart = rel_err(stored[sname][:nd], fp32_model), None
@@ -209,7 +184,7 @@ def run_child(path):
         for o in engine.plan_layout(MODELS[MODEL], 'bf16', n, H, W, CUS)['ops']:
             if o['cfg'] in (FORCED_S1, FORCED_S2):
                 th, tw = (16, 16) if o['cfg'] == FORCED_S1 else (8, 16)
-                assert '_t%dx%d_' % (th, tw) in config_name(o['cfg'])
+                assert tile_of(o['cfg']) == (th, tw)
                 fits.add(o['Ho'] % th == 0 and o['Wo'] % tw == 0)
         assert fits == {index == 0}, (n, H, W, fits)                       # case 0: the tiles divide every map; case 1: none
         check_rows(rows)
@@ -218,21 +193,9 @@ def run_child(path):
         json.dump(out, f)
 
 
-_CHILD = r'''
-import sys
-sys.path.insert(0, sys.argv[1])
-sys.path.insert(0, sys.argv[1] + '/tests')
-from test_bf16_operand_launches_gpu import run_child
-run_child(sys.argv[2])
-'''
-
-
 def test_forced_tilings_203_and_212_against_float64(tmp_path):
-    env = {k: v for k, v in os.environ.items() if not k.startswith('UKBB_')}
-    env['PYTHONPATH'] = ROOT + os.pathsep + env.get('PYTHONPATH', '')
-    env['UKBB_CONV_CFG'] = forced_spec()
     path = str(tmp_path / 'rows.json')
-    r = subprocess.run([sys.executable, '-c', _CHILD, ROOT, path], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+    r = run_in_child('test_bf16_operand_launches_gpu', 'run_child', [path], {'UKBB_CONV_CFG': forced_spec()})
     print(''.join('UKBB_CONV_CFG=203/212 ' + ln + '\n' for ln in r.stdout.splitlines() if ln.startswith('bf16op-launch')), end='')
     assert r.returncode == 0, r.stdout[-3000:]
     with open(path) as f:

@@ -9,7 +9,7 @@ by tests/test_plan_layout.py and do not move.
 
 Coverage: every (layer, tiling, fit, walker round class) those 192 plans hold -- fit: the tiles divide the map / whole tiles and a ragged last one /
 a single partial tile; round class of the weight-stationary walkers and of the stem: below one round, between one and two, two or more exact / ragged,
-in wave-major or XCD-local tile order (tests/test_bf16_launches_gpu.py ws_launch, stem_launch) -- is reached by some case of the GPU file, no case is
+in wave-major or XCD-local tile order (tests/launch_grading.py ws_launch, stem_launch) -- is reached by some case of the GPU file, no case is
 idle, and the four models hold the same set (one encoder graph), which is why the cases take the models in turn.
 
 The grades tell a defect: on the three rough images at 64 x 96 a float32 numpy evaluation of the rounding model (kernels rounded to bf16, every
@@ -22,12 +22,11 @@ import re
 import numpy as np
 import pytest
 
-import test_bf16_launch_coverage as C
-import test_bf16_launches_gpu as B
+import test_bf16_launch_coverage as C                              # its float32 stand-in launch32 and DEFECTS
+import test_bf16_launches_gpu as B                                 # the stem as a unit: stem_reference, grade_stem
 import test_fcn_bf16_store_launches_gpu as L
-import test_head_launches_gpu as HL
-from test_bf16_layers_gpu import grade, layer
-from test_fp32_launches_gpu import distinct_images, launches, rel_err
+import test_head_launches_gpu as HL                                # the squeeze and head models
+from launch_grading import SEEDS, bf16_round, check_bf16, config_name, distinct_images, grade, launches, layer, no_case_is_idle, rel_err
 from test_plan_layout import BATCHES, SHAPES
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -73,7 +72,7 @@ def test_bf16_store_plans_of_the_fcn_models(model):
             assert [o['kind'] for o in ops] == ['stem'] + ['conv'] * 11 + ['sqg_multi', 'head']
             assert p['bfio'] and p['split'] == (-1, -2)                      # UKBB_SPLIT_FROM keeps its FCN default of 0
             for o, gr in zip(ops[1:12], convs):
-                name = B.config_name(o['cfg'])
+                name = config_name(o['cfg'])
                 assert name.startswith(STORAGE_PREFIXES), (o['name'], o['cfg'], name)      # no fp32 tiling, no 200-series (convBF16_) tiling
                 assert not 200 <= o['cfg'] < 230 and o['cfg'] >= 230
                 assert '_3x3s%d_' % gr[4] in name and o['stride'] == gr[4]
@@ -148,17 +147,13 @@ def test_cases_reach_every_situation_and_none_is_idle(wanted):
     cases = L.CASES
     assert len(set(cases)) == len(cases) and all(H % 16 == 0 and W % 16 == 0 and n <= 129 and n * H * W <= 100 * 256 * 256 for n, H, W in cases)
     assert BENCH not in cases, 'the smallest case that reaches a situation, not the workload\'s own batch'
-    per_case = [L.situations(n, H, W, L.model_of(i)) & wanted for i, (n, H, W) in enumerate(cases)]
-    got = set().union(*per_case)
-    assert got == wanted, sorted(wanted - got, key=str)
-    for i, c in enumerate(cases):
-        rest = set().union(*(per_case[:i] + per_case[i + 1:]))
-        assert wanted - rest, 'CASES entry %s adds nothing' % (c,)
-        print('%-16s %-16s %8d pixels; only it reaches %s' % (c, L.model_of(i), c[0] * c[1] * c[2], sorted(wanted - rest, key=str)))
+    only = no_case_is_idle(list(enumerate(cases)), lambda ic: L.situations(*ic[1], L.model_of(ic[0])), wanted)
+    for (i, c), mine in zip(enumerate(cases), only):
+        print('%-16s %-16s %8d pixels; only it reaches %s' % (c, L.model_of(i), c[0] * c[1] * c[2], mine))
     # all four class counts appear, with both seeds
     from ukbb_cardiac_amd.arch import MODELS
     assert {MODELS[L.model_of(i)].n_class for i in range(len(cases))} == {MODELS[m].n_class for m in FCN_MODELS} and len({MODELS[m].n_class for m in FCN_MODELS}) == 4
-    assert {L.SEEDS[i % 2] for i in range(len(cases))} == {1234, 7}
+    assert {SEEDS[i % 2] for i in range(len(cases))} == {1234, 7}
 
 
 # ---- the grades tell a defect ---------------------------------------------------------------------------------------------------------------------------
@@ -188,7 +183,7 @@ def read_undecoded(a):
     return np.resize(raw, a.size).reshape(a.shape)
 
 
-@pytest.fixture(scope='module', params=L.SEEDS)
+@pytest.fixture(scope='module', params=SEEDS)
 def stand_in(request):
     """The float32 stand-in's maps of the three rough images, graded launch by launch as the GPU file grades the engine; per encoder launch, whether
     each planted defect fails the grade.  -> (stored maps, g, rows [(layer, {defect: failed})])."""
@@ -202,7 +197,7 @@ def stand_in(request):
         if lname in ('conv0_0', 'logits'):
             continue
         if lname == 'conv0_1':                                            # the stem as a unit; the defect sits in its second layer
-            a00 = C.launch32(B.bf16_round(img), params['conv0_0'])
+            a00 = C.launch32(bf16_round(img), params['conv0_0'])
             ex, slack, n_amb = B.stem_reference(img, params, 'stem')
             sc = float(np.abs(ex).max())
             stored[sname] = C.launch32(a00, params[lname])
@@ -210,7 +205,7 @@ def stand_in(request):
             rows.append((lname, {d: fails(B.grade_stem, C.launch32(a00, params[lname], defect=d), ex, sc, slack) for d in DEFECTS}))
             continue
         x = stored[srcs[0]]
-        ex = layer(x, params[lname], stride)
+        ex = layer(x, params[lname], stride, round_w=True)
         sc = float(np.abs(ex).max())
         stored[sname] = C.launch32(x, params[lname], stride)
         assert grade(lname, stored[sname], ex, sc, ulps=0.5, fraction=1.0) == 1.0
@@ -224,7 +219,7 @@ def test_stand_in_passes_every_launch(stand_in):
     from ukbb_cardiac_amd.arch import MODELS
     assert [r[0] for r in rows] == [gr[0] for gr in launches(MODELS['FCN_sa']) if gr[0] not in ('conv0_0', 'logits')]
     for a in stored.values():
-        B.check_bf16('stand-in', a)
+        check_bf16('stand-in', a)
     for l in range(1, 5):
         assert g[l].dtype == np.float32
         assert rel_err(g[l], HL.squeeze_map(stored['conv%d' % l], params, l))[0] <= L.BOUND

@@ -6,18 +6,17 @@ The mode runs the FCN encoder on the bf16-storage kernels of the aortic U-Net (t
 launches and the head through their bf16 loaders (kernels_head.hip bf16_block_to_k), behind which they are the fp32 launches.  So:
 
     conv0_0+conv0_1   the stem as a unit, with its intermediate rounding: stem_reference / grade_stem of tests/test_bf16_launches_gpu.py
-    conv1_0 .. conv4_2  float64 on the stored bf16 input with the bf16-rounded folded kernel (layer of tests/test_bf16_layers_gpu.py), the result rounded once:
-                      grade(ulps = 0.5, fraction = 1.0) of that file, imported -- half a bf16 ulp + 2^-18 |exact| + 2^-20 scale, for EVERY element
+    conv1_0 .. conv4_2  float64 on the stored bf16 input with the bf16-rounded folded kernel (layer(round_w=True) of tests/launch_grading.py), the result rounded once:
+                      grade(ulps = 0.5, fraction = 1.0) of that file -- half a bf16 ulp + 2^-18 |exact| + 2^-20 scale, for EVERY element
     g1 .. g4          the fp32 squeeze model of tests/test_head_launches_gpu.py (squeeze_map) on the stored conv_l, max |engine - f64| <= 1e-5 max |f64|
     logits            the head as a unit (head_logits of that file) from the stored conv0 and the stored g1..g4, <= 1e-5 of the logits' scale
     prob              within 1e-6 of a float64 softmax of the engine's own logits;  pred == argmax(prob) exactly, over all slices
 
-One forward per case on a fresh engine created under UKBB_DEBUG_GUARD (every buffer filled with a bf16 NaN pattern when it is allocated and again by
-Engine.poison() in front of the forward): a tile nobody wrote holds NaN.  The plan that ran (kernel_names() / kernel_configs()) must be the planner's
-(engine.plan_layout on 256 compute units), which is what tests/test_fcn_bf16_store.py counts.  Inputs: batch_of_copies of tests/test_fp32_launches_gpu.py,
-normalised as the bf16 U-Net file does; slices 0..2 are graded and every further slice of every stored map, of g1..g4, logits, prob and pred must be
-bit-identical to the graded copy of its image.  Every encoder map holds bf16 values only, no map holds NaN, no guard is damaged.  Weights from seeds
-1234 and 7 in turn; the four models (4, 2, 3 and 6 classes) in turn.
+The method is the graders' common one (tests/launch_grading.py) on a guarded, poisoned engine, as in tests/test_bf16_launches_gpu.py: a tile nobody
+wrote holds NaN.  The plan that ran (kernel_names() / kernel_configs()) must be the planner's (engine.plan_layout on 256 compute units), which is what
+tests/test_fcn_bf16_store.py counts.  Inputs: normalised_copies; slices 0..2 are graded and every further slice of every stored map, of g1..g4, logits,
+prob and pred must be bit-identical to the graded copy of its image.  Every encoder map holds bf16 values only, no map holds NaN, no guard is
+damaged.  Weights from seeds 1234 and 7 in turn; the four models (4, 2, 3 and 6 classes) in turn.
 
 CASES: a greedy cover, cheapest first (pixels + 25 x float64 pixels) and then reduced until no case is idle, of the 88 (layer, tiling, fit, walker
 round class) situations the bf16_store plans of the four models hold over the SHAPES x BATCHES of tests/test_plan_layout.py; tests/test_fcn_bf16_store.py
@@ -30,29 +29,22 @@ CHILD_CASES in the same way, after asserting that the form meant ran.
 Measured on an MI355X: profiles/fcn_bf16_store.txt (worst figure per tiling and per squeeze / head launch): every encoder element of every case within the
 half-ulp grade; g1..g4 <= 4.3e-7, logits <= 5.5e-7 of their scale, prob <= 2.1e-7.  The 22 cases take 14 s together, the largest 1.5 s; each child 3 s."""
 import os
-import re
-import subprocess
-import sys
 import time
 
 import numpy as np
 import pytest
 
-import test_bf16_launches_gpu as B
-import test_head_launches_gpu as HL
-from test_bf16_layers_gpu import grade, layer
-from test_fp32_launches_gpu import launches, rel_err
+import test_bf16_launches_gpu as B                                 # the stem as a unit: stem_reference, grade_stem
+import test_head_launches_gpu as HL                                # the squeeze and head models, their bounds and knobs
+from launch_grading import (CUS, POISON, SEEDS, Report, assert_plan_ran, check_copies, fetcher, fit_of, grade, guarded_engine, launch_class, launches, layer,
+                            normalised_copies, rel_err, run_in_child, stem_launch)
 
 pytestmark = pytest.mark.gpu
-SEEDS = B.SEEDS                                                    # (1234, 7)
-POISON = B.POISON
-CUS = B.CUS
 PREC = 'bf16_store'
 MODELS_IN_TURN = ('FCN_sa', 'FCN_la_2ch', 'FCN_la_4ch', 'FCN_la_4ch_seg4')
 BOUND = HL.BOUND                                                   # 1e-5: squeeze and head, of the launch's scale
 PROB_ATOL = HL.PROB_ATOL                                           # 1e-6
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KNOBS = HL.KNOBS                                                   # UKBB_SIDE_STREAM, UKBB_HEAD_DIRECT_GATHER, UKBB_HEAD_INLINE_TAIL
 CHILD_CASES = (0, 1, 3, 6)                                         # one small case per model (4, 2, 6 and 3 classes)
 DEFAULT_TAIL = ('sqg1-4', 'head')
@@ -67,21 +59,6 @@ def model_of(index):
 
 
 # ---- the situation of a launch (host arithmetic; tests/test_fcn_bf16_store.py counts them) ----
-def tile_of(cfg):
-    """(rows, columns) of a tiling's tile: from its name, "..._t<rows>x<columns>..." (tile per workgroup) or "..._r<rows>x32_..." (walkers)."""
-    if cfg >= 400:
-        return B.ws_shape(cfg)[0], B.WS_TW
-    return tuple(map(int, re.search(r'_t(\d+)x(\d+)', B.config_name(cfg)).groups()))
-
-
-def fit_of(op):
-    """'div': the tiles divide the output map; 'ragged': whole tiles and a partial last one along some axis; 'partial': a single partial tile there."""
-    th, tw = tile_of(op['cfg'])
-    if op['Ho'] % th == 0 and op['Wo'] % tw == 0:
-        return 'div'
-    return 'ragged' if (op['Ho'] % th and op['Ho'] > th) or (op['Wo'] % tw and op['Wo'] > tw) else 'partial'
-
-
 def situations(n, H, W, model='FCN_sa'):
     """{(layer, tiling, fit, walker round class)} of the bf16_store plan's encoder launches ('-' where there is no tile fit / no walker)."""
     from ukbb_cardiac_amd import engine
@@ -90,9 +67,9 @@ def situations(n, H, W, model='FCN_sa'):
     out = set()
     for o in p['ops']:
         if o['kind'] == 'stem':
-            out.add((o['name'], -1, '-', B.stem_launch(n, H, W)['cls']))
+            out.add((o['name'], -1, '-', stem_launch(n, H, W)['cls']))
         elif o['kind'] == 'conv':
-            out.add((o['name'], o['cfg'], fit_of(o), B.launch_class(o, p['acts'], n)))
+            out.add((o['name'], o['cfg'], fit_of(o), launch_class(o, p['acts'], n)))
     return out
 
 
@@ -112,7 +89,7 @@ def grade_fcn(arch, params, ops, img, conv, g, out, report):
             report.row(lname, conv[sname], ex, sc)
             B.grade_stem(conv[sname], ex, sc, slack)
             continue
-        ex = layer(conv[srcs[0]], params[lname], stride)
+        ex = layer(conv[srcs[0]], params[lname], stride, round_w=True)
         sc = float(np.abs(ex).max())
         report.row(lname, conv[sname], ex, sc)
         grade('%s (tiling %d)' % (lname, report.op_of[lname]['cfg']), conv[sname], ex, sc, ulps=0.5, fraction=1.0)
@@ -130,16 +107,6 @@ def grade_fcn(arch, params, ops, img, conv, g, out, report):
     return rows
 
 
-def guarded_engine(monkeypatch, arch, params):
-    from ukbb_cardiac_amd.engine import Engine
-    for k in B.LAUNCHER_KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    monkeypatch.setenv('UKBB_DEBUG_GUARD', POISON)                 # read in ukbb_fcn_create only
-    eng = Engine(arch, params)
-    eng.set_precision(PREC)
-    return eng
-
-
 def run_case(index, monkeypatch, want_tail=DEFAULT_TAIL):
     """One guarded, poisoned forward of case ``index``, every launch graded; returns (report rows of the encoder, squeeze / head rows).
     want_tail: the plan's squeeze and head ops."""
@@ -150,38 +117,36 @@ def run_case(index, monkeypatch, want_tail=DEFAULT_TAIL):
     model = model_of(index)
     arch = MODELS[model]
     params = synthetic_params(arch, SEEDS[index % 2])
-    img, nd = B.normalised_copies(index, n, H, W)
+    img, nd = normalised_copies(index, n, H, W)
     plan = engine.plan_layout(arch, PREC, n, H, W, CUS)
     ops = plan['ops']
     tag = '%s %dx%dx%d' % (model, n, H, W)
     t0 = time.perf_counter()
     conv, g = {}, {}
-    with guarded_engine(monkeypatch, arch, params) as eng:
+    with guarded_engine(monkeypatch, arch, params, PREC) as eng:
         eng.reserve(n, H, W)
         eng.poison(POISON)
         out = eng.run(img, want_logits=True, want_prob=True, want_pred=True)
         t_fwd = time.perf_counter() - t0
-        names, cfgs = eng.kernel_names(), eng.kernel_configs()
-        assert names == [o['name'] for o in ops], (names, [o['name'] for o in ops])
-        assert cfgs == [o['cfg'] if o['kind'] in ('conv', 'tconv') else -1 for o in ops], (cfgs, ops)
+        assert_plan_ran(eng, plan)
         assert [o['name'] for o in ops if o['kind'] in ('sqg', 'sqg_multi', 'head')] == list(want_tail) and plan['bfio']
         level = {gr[1]: gr[2] for gr in launches(arch)}
-        fetch = B.fetcher(eng, lambda s: (n, H >> level[s], W >> level[s], -1), nd, conv, tag)     # bf16 values, no poison, copies identical
+        fetch = fetcher(eng, lambda s: (n, H >> level[s], W >> level[s], -1), nd, conv, tag)     # bf16 values, no poison, copies identical
         for gr in launches(arch):
             if gr[0] not in ('conv0_0', 'logits'):
                 fetch(gr[1])
         for l in range(1, 5):
             a = eng.activation('g%d' % l).reshape(n, H >> l, W >> l, 64)
-            B.check_copies('g%d' % l, a, nd, tag)
+            check_copies('g%d' % l, a, nd, tag)
             g[l] = a[:nd].copy()
         damaged, where = eng.check_guards()
         assert damaged == 0, where
     assert out['logits'].shape == (n, H, W, arch.n_class) and out['prob'].shape == out['logits'].shape and out['pred'].shape == (n, H, W)
     for k in ('logits', 'prob', 'pred'):
-        B.check_copies(k, out[k], nd, tag)
+        check_copies(k, out[k], nd, tag)
     t_gpu = time.perf_counter() - t0
     t0 = time.perf_counter()
-    report = B.Report(tag, ops, plan['acts'], n)
+    report = Report(tag, ops, plan['acts'], n)
     try:
         tail_rows = grade_fcn(arch, params, ops, img[:nd], conv, g, out, report)
     finally:
@@ -210,24 +175,12 @@ def run_child(knob):
             assert int(_lib.lib.ukbb_fcn_head_tail_form()) == (0 if side else 1)
     finally:
         mp.undo()
-
-
-_CHILD = r'''
-import sys
-sys.path.insert(0, sys.argv[1])
-sys.path.insert(0, sys.argv[1] + '/tests')
-from test_fcn_bf16_store_launches_gpu import run_child
-run_child(sys.argv[2])
-print('child done')
-'''
+    print('child done')
 
 
 @pytest.mark.parametrize('knob', KNOBS)
 def test_non_default_squeeze_and_head_forms_against_float64(knob):
-    env = {k: v for k, v in os.environ.items() if not k.startswith('UKBB_')}
-    env['PYTHONPATH'] = ROOT + os.pathsep + env.get('PYTHONPATH', '')
-    env[knob] = '1'
-    r = subprocess.run([sys.executable, '-c', _CHILD, ROOT, knob], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+    r = run_in_child('test_fcn_bf16_store_launches_gpu', 'run_child', [knob], {knob: '1'})
     print(''.join(knob + '=1 ' + ln + '\n' for ln in r.stdout.splitlines() if ln.startswith(('fcn-bf16-store', 'bf16-launch'))), end='')
     assert r.returncode == 0 and r.stdout.strip().endswith('child done'), r.stdout[-3000:]
     assert r.stdout.count('forward ') == len(CHILD_CASES)

@@ -9,26 +9,18 @@ Per tiling, CASES also reaches it on a map its tiles divide, and on one they do 
 from the tiling's name (ukbb_fcn_conv_config_name of the plan op's `cfg`: "..._t<rows>x<columns>...") and the op's Ho / Wo.
 No case is idle: dropping any one entry of CASES leaves one of these requirements unmet."""
 import collections
-import json
 import os
 import re
 
 import numpy as np
 import pytest
 
+import launch_grading as G
 import test_fp32_launches_gpu as L
 from oracle import fcn_oracle as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'plan_layouts.json')
 MODELS_GRADED = ('FCN_sa', 'UNet_ao')
-
-
-def _tile(cfg):
-    from ukbb_cardiac_amd import _lib
-    name = _lib.lib.ukbb_fcn_conv_config_name(cfg).decode()
-    th, tw = map(int, re.search(r'_t(\d+)x(\d+)', name).groups())
-    return name, th, tw
 
 
 def reached(model, n, H, W):
@@ -40,29 +32,20 @@ def reached(model, n, H, W):
         if o['kind'] not in ('conv', 'tconv') or o['cfg'] < 0:
             continue
         fit = None
-        name, th, tw = _tile(o['cfg'])
-        if o['kind'] == 'conv' and (o['stride'] == 2 or 'winograd' in name):
-            fit = 'div' if o['Ho'] % th == 0 and o['Wo'] % tw == 0 else 'nodiv'
+        if o['kind'] == 'conv' and (o['stride'] == 2 or 'winograd' in G.config_name(o['cfg'])):
+            fit = 'div' if G.fit_of(o) == 'div' else 'nodiv'
         out[(model, o['name'], o['cfg'])] = fit
     return out
 
 
 @pytest.fixture(scope='module')
 def recorded():
-    """{combination: set of situations} over the recorded default fp32 plans of the two models (replayed: the records hold no map sizes per op, and
-    tests/test_plan_layout.py asserts the replay equals them), after checking the replay against the records' own names and tilings."""
-    with open(GOLDEN) as f:
-        g = json.load(f)
+    """{combination: set of situations} over the recorded default fp32 plans of the two models (G.replay_records)."""
     rec = collections.defaultdict(set)
-    for r in g['records']:
-        model, prec, H, W, n, knob, rc = r[:7]
-        if knob != '' or prec != 'fp32' or rc != 0 or model not in MODELS_GRADED:
-            continue
-        got = reached(model, n, H, W)
-        want = {(model, nm, c) for nm, c in zip(g['names'][r[8]], g['cfgs'][r[9]]) if c >= 0}
-        assert set(got) == want, (r[:6], sorted(set(got) ^ want))
-        for k, fit in got.items():
-            rec[k].add(fit)
+    for model in MODELS_GRADED:
+        for _, _, _, got in G.replay_records(model, 'fp32', lambda n, H, W: reached(model, n, H, W)):
+            for k, fit in got.items():
+                rec[k].add(fit)
     return dict(rec)
 
 
@@ -101,12 +84,7 @@ def test_cases_reach_every_tiling_on_maps_its_tiles_divide_and_do_not(recorded):
 
 
 def test_no_case_is_idle(recorded):
-    want = requirements(recorded)
-    per_case = [covered([c], recorded) & want for c in L.CASES]
-    assert set().union(*per_case) == want
-    for i, c in enumerate(L.CASES):
-        rest = set().union(*(per_case[:i] + per_case[i + 1:]))
-        assert want - rest, 'CASES entry %s adds nothing' % (c,)
+    G.no_case_is_idle(L.CASES, lambda c: covered([c], recorded), requirements(recorded))
 
 
 def test_large_batch_cases_are_above_the_small_batch_threshold():
@@ -122,19 +100,19 @@ def test_graph_lists_every_planned_conv_launch():
     for model, n, H, W in L.CASES:
         ops = engine.plan_layout(MODELS[model], 'fp32', n, H, W)['ops']
         planned = [part for o in ops if o['kind'] in ('conv', 'tconv', 'logits') for part in o['name'].split('+')]
-        graph = [g[0] for g in L.launches(MODELS[model]) if not (g[0] == 'logits' and model.startswith('FCN'))]
+        graph = [g[0] for g in G.launches(MODELS[model]) if not (g[0] == 'logits' and model.startswith('FCN'))]
         assert planned == graph, (model, planned, graph)
         stored = {a['name'] for a in engine.plan_layout(MODELS[model], 'fp32', n, H, W)['acts']}
-        assert {g[1] for g in L.launches(MODELS[model]) if g[0] not in ('conv0_0', 'logits')} <= stored
+        assert {g[1] for g in G.launches(MODELS[model]) if g[0] not in ('conv0_0', 'logits')} <= stored
 
 
 def test_batch_of_copies():
-    img, nd = L.batch_of_copies(0, 17, 32, 48)
+    img, nd = G.batch_of_copies(0, 17, 32, 48)
     assert img.shape == (17, 32, 48, 1) and nd == 3 and img.dtype == np.float32
     assert all(np.array_equal(img[i], img[i % 3]) for i in range(17)) and not np.array_equal(img[0], img[1]) and not np.array_equal(img[1], img[2])
-    d = L.distinct_images(32, 48)
+    d = G.distinct_images(32, 48)
     assert d[2].min() == d[0].min() and d[2].max() == d[0].max()
-    assert [float(L.batch_of_copies(i, 1, 32, 48)[0].sum()) for i in range(3)] == [float(d[i].sum()) for i in range(3)]
+    assert [float(G.batch_of_copies(i, 1, 32, 48)[0].sum()) for i in range(3)] == [float(d[i].sum()) for i in range(3)]
 
 
 def test_bound_tells_a_wrong_tap_and_a_shifted_input():
@@ -143,20 +121,20 @@ def test_bound_tells_a_wrong_tap_and_a_shifted_input():
     full reference -- by orders of magnitude, so a kernel with that defect cannot pass -- while the full reference evaluated in float32 passes."""
     from ukbb_cardiac_amd.arch import MODELS
     from ukbb_cardiac_amd.weights import synthetic_params
-    params = synthetic_params(MODELS['FCN_sa'], L.SEEDS[0])
-    w, b = L.fold(params['conv1_1'])
+    params = synthetic_params(MODELS['FCN_sa'], G.SEEDS[0])
+    w, b = G.fold(params['conv1_1'])
     w64, b64 = w.astype(np.float64), b.astype(np.float64)
-    for kind, img in enumerate(L.distinct_images(48, 32)):
-        x = L.layer(L.layer(img[None], params['conv0_0']), params['conv1_0'], stride=2).astype(np.float32).astype(np.float64)
-        full = L.layer(x, params['conv1_1'])
+    for kind, img in enumerate(G.distinct_images(48, 32)):
+        x = G.layer(G.layer(img[None], params['conv0_0']), params['conv1_0'], stride=2).astype(np.float32).astype(np.float64)
+        full = G.layer(x, params['conv1_1'])
         assert full.shape == (1, 24, 16, 32) and full.max() > 0
         f32 = np.maximum(O.conv2d_same(x.astype(np.float32), w, 1) + b, np.float32(0))
-        assert L.rel_err(f32, full)[0] <= L.BOUND
+        assert G.rel_err(f32, full)[0] <= L.BOUND
         for ky in range(3):
             for kx in range(3):
                 wz = w64.copy()
                 wz[ky, kx] = 0.0
-                err, _ = L.rel_err(np.maximum(O.conv2d_same(x, wz, 1) + b64, 0.0), full)
+                err, _ = G.rel_err(np.maximum(O.conv2d_same(x, wz, 1) + b64, 0.0), full)
                 assert err > 100 * L.BOUND, (kind, ky, kx, err)
         for axis in (1, 2):
             shifted = np.zeros_like(x)
@@ -164,5 +142,5 @@ def test_bound_tells_a_wrong_tap_and_a_shifted_input():
             src = list(sl)
             sl[axis], src[axis] = slice(1, None), slice(0, -1)
             shifted[tuple(sl)] = x[tuple(src)]
-            err, _ = L.rel_err(L.layer(shifted, params['conv1_1']), full)
+            err, _ = G.rel_err(G.layer(shifted, params['conv1_1']), full)
             assert err > 100 * L.BOUND, (kind, axis, err)

@@ -8,21 +8,9 @@ Bound asserted per layer: max |engine - float64| <= 1e-5 x the layer's largest a
 import numpy as np
 import pytest
 
-from oracle import fcn_oracle as O
+from launch_grading import layer
 
 pytestmark = pytest.mark.gpu
-BN_EPS = np.float32(1e-3)
-
-
-def fold(p):
-    sc = (p['gamma'].astype(np.float32) / np.sqrt(p['var'].astype(np.float32) + BN_EPS)).astype(np.float32)
-    b = (p['beta'].astype(np.float32) - (p['mean'].astype(np.float32) * sc).astype(np.float32)).astype(np.float32)
-    return (p['kernel'].astype(np.float32) * sc[None, None, None, :]).astype(np.float32), b
-
-
-def layer(x, p, stride):
-    w, b = fold(p)
-    return np.maximum(O.conv2d_same(np.asarray(x, np.float64), w.astype(np.float64), stride) + b.astype(np.float64), 0.0)
 
 
 @pytest.mark.parametrize('model,shape', [('FCN_sa', (2, 192, 208)), ('FCN_sa', (3, 80, 112)), ('FCN_la_2ch', (1, 176, 208))])
@@ -42,10 +30,8 @@ def test_each_encoder_launch_against_float64_on_its_own_input(model, shape):
         for l in range(arch.n_level):
             for i in range(arch.n_block[l]):
                 name = 'conv%d' % l if i == arch.n_block[l] - 1 else 'conv%d_%d' % (l, i)
-                try:
+                if (l, i) != (0, 0):                                     # conv0_0 lives inside conv0_1's launch: it is not stored
                     stored['conv%d_%d' % (l, i)] = eng.activation(name).reshape(n, -(-H >> l), -(-W >> l), -1).astype(np.float64)
-                except Exception:
-                    assert (l, i) == (0, 0)                              # conv0_0 lives inside conv0_1's launch
     report = {}
     x = None
     for l in range(arch.n_level):

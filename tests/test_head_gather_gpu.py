@@ -6,15 +6,12 @@ batches: four image sizes (the headline 192 x 208, the long-axis 176 x 208, 208 
 is 17 x 19, so tiles on the right and bottom border read window rows and columns outside the map at every level), N = 1, 10 and 64
 (the first slices of one batch of 64), fp32 and f32x3.  The separable form rounds its sums in another order, so the two gathers agree
 to ordinary fp32 rounding, not bit for bit.  Within one gather the logits of a slice do not depend on the batch it is in."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
+from launch_grading import run_in_child
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LOGIT_RTOL = 1e-3                       # north-star tolerance (tests/test_gpu_parity.py)
 AB_RTOL = 1e-6                          # separable vs direct gather: a few fp32 roundings of out0's pre-activation
 CASES = [('FCN_sa', 192, 208), ('FCN_la_2ch', 176, 208), ('FCN_sa', 208, 256), ('FCN_sa', 272, 304)]
@@ -47,26 +44,12 @@ def run_cases(path):
     np.savez(path, **out)
 
 
-_CHILD = r'''
-import sys
-sys.path.insert(0, sys.argv[1])
-from tests.test_head_gather_gpu import run_cases
-run_cases(sys.argv[2])
-'''
-
-
 @pytest.fixture(scope='module')
 def logits(tmp_path_factory):
-    env = {k: v for k, v in os.environ.items() if not k.startswith('UKBB_')}
-    env['PYTHONPATH'] = ROOT + os.pathsep + env.get('PYTHONPATH', '')
     res = {}
     for tag, knob in (('separable', None), ('direct', '1')):
-        e = dict(env)
-        if knob:
-            e['UKBB_HEAD_DIRECT_GATHER'] = knob
         path = str(tmp_path_factory.mktemp('head_gather') / (tag + '.npz'))
-        r = subprocess.run([sys.executable, '-c', _CHILD, ROOT, path], env=e, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                           text=True, timeout=900)
+        r = run_in_child('test_head_gather_gpu', 'run_cases', [path], {'UKBB_HEAD_DIRECT_GATHER': knob} if knob else {}, timeout=900)
         assert r.returncode == 0, r.stdout[-3000:]
         with np.load(path) as z:
             res[tag] = {k: z[k] for k in z.files}

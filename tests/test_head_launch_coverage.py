@@ -15,12 +15,12 @@ import re
 import numpy as np
 import pytest
 
-import test_fp32_launches_gpu as L
+import launch_grading as G
 import test_head_launches_gpu as HL
 from oracle import fcn_oracle as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CUS = 256                               # engine.plan_layout's default; launch_head_pc: one workgroup per CU
+CUS = G.CUS                             # 256, engine.plan_layout's default; launch_head_pc: one workgroup per CU
 HT = 16
 WIN = {1: 9, 2: 6, 3: 4, 4: 3}          # kernels_head.hip win_n
 
@@ -122,15 +122,11 @@ def test_cases_reach_every_situation_and_none_is_idle():
     assert len(set(HL.CASES)) == len(HL.CASES)
     assert {m for m, _, _, _ in HL.CASES} == {k for k, a in MODELS.items() if a.kind == KIND_FCN}        # all four class-count instantiations
     assert all(H % 16 == 0 and W % 16 == 0 and H >= 16 and W >= 16 and n >= 1 for _, n, H, W in HL.CASES)  # 16 x 16 tiling, integral level sizes
-    per_case = [situations(*c) for c in HL.CASES]
-    for c, s in zip(HL.CASES, per_case):
+    at = {c: situations(*c) for c in HL.CASES}
+    for c, s in at.items():
         print(c, sorted(s))
-    assert set().union(*per_case) >= REQUIRED, REQUIRED - set().union(*per_case)
-    for i, c in enumerate(HL.CASES):
-        rest = set().union(*(per_case[:i] + per_case[i + 1:]))
-        assert REQUIRED - rest, 'CASES entry %s adds nothing' % (c,)
+    G.no_case_is_idle(HL.CASES, at.__getitem__, REQUIRED)
     # the cases the docstring names, where it names them
-    at = {c: s for c, s in zip(HL.CASES, per_case)}
     assert 'single tile' in at[('FCN_sa', 1, 16, 16)] and 'squeeze loop past the cap' in at[('FCN_sa', 17, 256, 256)]
     assert 'squeeze loop past the cap' not in at[('FCN_sa', 17, 240, 256)]
     assert [n * (H // 16) * (W // 16) for _, n, H, W in HL.CASES] == [1, 3, 9, 105, 105, 105, 256, 323, 4352, 4080, 68]
@@ -141,7 +137,7 @@ def test_modes_and_the_plans_behind_them():
     """Every case runs in the three precisions; in each the plan ends in the same sqg1-4 and head launches on the same maps (engine.cpp switches the
     head's arithmetic for f32x3 only), and in bf16 every conv in front of them from conv1_0 on is a bf16-operand tiling storing fp32 maps, so the
     squeeze and head of that mode are fp32 launches on maps another kernel family stored.  The knob children keep fp32 and f32x3."""
-    from ukbb_cardiac_amd import _lib, engine
+    from ukbb_cardiac_amd import engine
     from ukbb_cardiac_amd.arch import MODELS
     assert HL.MODES == ('fp32', 'f32x3', 'bf16') and set(HL.CHILD_MODES) == {'fp32', 'f32x3'}
     for model, n, H, W in HL.CASES:
@@ -152,7 +148,7 @@ def test_modes_and_the_plans_behind_them():
             tails[mode] = [(o['name'], o['kind'], o['H'], o['W']) for o in p['ops'] if o['kind'] != 'conv']
             acts = [(a['name'], a['per_image'], a['channels']) for a in p['acts']]
             assert [t[0] for t in tails[mode]] == ['sqg1-4', 'head'] and {'conv%d' % l for l in range(5)} | {'g%d' % l for l in range(1, 5)} <= {a[0] for a in acts}
-            on_bf16 = [_lib.lib.ukbb_fcn_conv_config_name(o['cfg']).decode().startswith('convBF16_') for o in p['ops'] if o['kind'] == 'conv' and '+' not in o['name']]
+            on_bf16 = [G.config_name(o['cfg']).startswith('convBF16_') for o in p['ops'] if o['kind'] == 'conv' and '+' not in o['name']]
             assert len(on_bf16) == 11 and all(v == (mode == 'bf16') for v in on_bf16), (model, mode)
         assert tails['fp32'] == tails['f32x3'] == tails['bf16']
 
@@ -211,9 +207,9 @@ def small():
     from ukbb_cardiac_amd.arch import MODELS
     from ukbb_cardiac_amd.weights import synthetic_params
     out = []
-    for seed in HL.SEEDS:
+    for seed in G.SEEDS:
         params = synthetic_params(MODELS['FCN_sa'], seed)
-        _, net = O.build_FCN(L.distinct_images(48, 32), params, 4, dtype=np.float64, return_net=True)
+        _, net = O.build_FCN(G.distinct_images(48, 32), params, 4, dtype=np.float64, return_net=True)
         conv = {l: net['conv%d' % l].astype(np.float32) for l in range(5)}
         g = {l: HL.squeeze_map(conv[l], params, l) for l in range(1, 5)}
         out.append((params, conv, g, HL.head_logits(conv[0], g, params)))
@@ -232,9 +228,9 @@ def test_float32_reference_passes_the_bounds(small):
     for params, conv, g, full in small:
         for l in range(1, 5):
             g32 = HL.squeeze_map(conv[l], params, l, np.float32)
-            assert g32.dtype == np.float32 and HL.rel_err(g32, g[l])[0] <= HL.BOUND
+            assert g32.dtype == np.float32 and G.rel_err(g32, g[l])[0] <= HL.BOUND
         lg32 = HL.head_logits(conv[0], {l: g[l].astype(np.float32) for l in g}, params, np.float32)
-        assert lg32.dtype == np.float32 and HL.rel_err(lg32, full)[0] <= HL.BOUND
+        assert lg32.dtype == np.float32 and G.rel_err(lg32, full)[0] <= HL.BOUND
 
 
 def _defects(params, conv, g):
@@ -269,9 +265,9 @@ def _defects(params, conv, g):
 
 def test_bound_tells_each_planted_defect(small):
     """Every defect, at every level it can be planted at, misses the logits bound by more than 100x: a head with it cannot pass."""
-    for seed, (params, conv, g, full) in zip(HL.SEEDS, small):
+    for seed, (params, conv, g, full) in zip(G.SEEDS, small):
         for name, l, bad in _defects(params, conv, g):
-            err, _ = HL.rel_err(bad, full)
+            err, _ = G.rel_err(bad, full)
             print('seed %4d level %d %-36s logits error / scale %.2e' % (seed, l, name, err))
             assert err > 100 * HL.BOUND, (seed, name, l, err)
 
@@ -283,13 +279,13 @@ def test_squeeze_bound_tells_a_defect(small):
             sd = HL.same_dim(conv[l], params, l)
             for m in range(5):
                 if m != l:
-                    assert HL.rel_err(sd @ HL.out0_slice(params, m), g[l])[0] > 100 * HL.BOUND, (l, m)
+                    assert G.rel_err(sd @ HL.out0_slice(params, m), g[l])[0] > 100 * HL.BOUND, (l, m)
             z = sd.copy()
             z[..., int(np.argmax(sd.reshape(-1, 32).max(axis=0)))] = 0.0
-            assert HL.rel_err(z @ HL.out0_slice(params, l), g[l])[0] > 100 * HL.BOUND, l
+            assert G.rel_err(z @ HL.out0_slice(params, l), g[l])[0] > 100 * HL.BOUND, l
             flat = conv[l].reshape(-1, conv[l].shape[-1])
             off = HL.squeeze_map(np.roll(flat, 1, axis=0), params, l).reshape(g[l].shape)
-            assert HL.rel_err(off, g[l])[0] > 100 * HL.BOUND, l
+            assert G.rel_err(off, g[l])[0] > 100 * HL.BOUND, l
 
 
 # ---- softmax ------------------------------------------------------------------------------------------------------------------------------------------------

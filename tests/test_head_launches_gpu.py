@@ -1,5 +1,6 @@
 """The FCN squeeze launches (sqg1-4: sqg_multi_kernel, sqg_body / sqg_stream_body) and the head launch (fcn_head_pc_kernel, kernels_head.hip), one launch
-at a time, against float64 on the engine's OWN stored inputs -- the method and the bound of tests/test_fp32_launches_gpu.py, which stops in front of them.
+at a time, against float64 on the engine's OWN stored inputs -- the graders' common method (tests/launch_grading.py) and the bound of
+tests/test_fp32_launches_gpu.py, which stops in front of them.
 
 One forward per case and mode.  From what the engine stored (Engine.activation), in numpy float64 with the float32 BN fold of engine.cpp create():
 
@@ -18,8 +19,8 @@ Every case runs in fp32, in f32x3 and in bf16 on the same handle, with the same 
 bf16 (UKBB_PREC_BF16 on an FCN handle: bf16-operand convs, fp32 maps in HBM; engine.cpp switches the head for f32x3 only) the squeeze and the head are
 the fp32 launches, fed by maps the bf16-operand convs stored (those are graded in tests/test_bf16_operand_launches_gpu.py); everything here is graded
 from the engine's own stored conv0..4 and g1..4, so the same bounds hold.  Inputs as in
-the fp32 launch test: a batch is made of copies of three rough images (phantom, uniform noise, scaled normal noise), slices 0-2 are graded in float64
-and every other slice of g1..g4, logits, prob and pred must be BIT-IDENTICAL to the graded copy of its image; weights from seeds 1234 and 7 in turn.
+the fp32 launch test (batch_of_copies): slices 0-2 are graded in float64 and every other slice of g1..g4, logits, prob and pred must be BIT-IDENTICAL
+to the graded copy of its image; weights from seeds 1234 and 7 in turn.
 Each case asserts that the plan it ran holds sqg1-4 and head.
 
 CASES: the smallest maps that reach each situation of the squeeze launcher (launch_sqg_multi: one wave per 32-pixel block, four per workgroup, at most
@@ -60,22 +61,19 @@ three children measure the same or less on their cases.  In bf16 (behind the bf1
 largest 0.8 s) and 4.5 s with bf16 (the largest 1.3 s), each child 3 s, most of it starting Python."""
 import json
 import os
-import subprocess
-import sys
 import time
 
 import numpy as np
 import pytest
 
+from launch_grading import SEEDS, batch_of_copies, check_copies, config_name, fold, rel_err, run_in_child
 from oracle import fcn_oracle as O
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BOUND = 1e-5                            # g_l and logits: the project's fp32 launch bound, of the launch's scale
 PROB_ATOL = 1e-6                        # 16 x 2^-24 = 9.5e-7, see above
 NEAR_TIE_GAP = 4e-7                     # kernels.h softmax_argmax
 LABEL_MARGIN = 2e-5                     # of the float64 logits' scale: two fp32-grade evaluations, 1e-5 each
-SEEDS = (1234, 7)
 MODES = ('fp32', 'f32x3', 'bf16')
 CHILD_MODES = ('fp32', 'f32x3')         # the knob children stay on the two modes whose head launches differ
 
@@ -90,8 +88,7 @@ KNOBS = ('UKBB_SIDE_STREAM', 'UKBB_HEAD_DIRECT_GATHER', 'UKBB_HEAD_INLINE_TAIL')
 
 # ---- the float64 reference of the squeeze and of the head, from stored maps -------------------------------------------------------------------------
 def folded(params, name, dtype=np.float64):
-    """The 1 x 1 layer's [Cin, Cout] matrix and bias after the float32 BN fold of engine.cpp create() (tests/test_fp32_launches_gpu.py fold)."""
-    from test_fp32_launches_gpu import fold
+    """The 1 x 1 layer's [Cin, Cout] matrix and bias after the float32 BN fold of engine.cpp create() (tests/launch_grading.py fold)."""
     w, b = fold(params[name])
     assert w.shape[:2] == (1, 1)
     return w[0, 0].astype(dtype), b.astype(dtype)
@@ -141,16 +138,10 @@ def top2_gap(logits):
     return srt[..., -1] - srt[..., -2]
 
 
-def rel_err(got, ex):
-    from test_fp32_launches_gpu import rel_err as r
-    return r(got, ex)
-
-
 # ---- one case, every mode, on one handle ---------------------------------------------------------------------------------------------------------------
 def grade_case(index, want_names=('sqg1-4', 'head'), tail_form=None, modes=MODES):
     """Runs case ``index`` in every mode of ``modes``, prints one line per graded launch and mode, asserts everything the module docstring lists.
     Returns the rows [(mode, launch, figure, where)]."""
-    from test_fp32_launches_gpu import batch_of_copies
     from ukbb_cardiac_amd import _lib, engine
     from ukbb_cardiac_amd.arch import MODELS
     from ukbb_cardiac_amd.weights import synthetic_params
@@ -177,7 +168,7 @@ def grade_case(index, want_names=('sqg1-4', 'head'), tail_form=None, modes=MODES
             for nm in want_names:
                 assert nm in names, (mode, nm, names)
             # bf16: the maps the squeeze and the head read were stored by bf16-operand convs, every one from conv1_0 on
-            on_bf16 = [_lib.lib.ukbb_fcn_conv_config_name(c).decode().startswith('convBF16_') for nm, c in zip(names, cfgs) if nm.startswith('conv') and '+' not in nm]
+            on_bf16 = [config_name(c).startswith('convBF16_') for nm, c in zip(names, cfgs) if nm.startswith('conv') and '+' not in nm]
             assert len(on_bf16) == 11 and all(v == (mode == 'bf16') for v in on_bf16), (mode, list(zip(names, cfgs)))
             if tail_form is not None and mode == 'fp32':                 # f32x3 keeps the in-stage tail in every form
                 assert form == tail_form, (form, tail_form)
@@ -186,8 +177,7 @@ def grade_case(index, want_names=('sqg1-4', 'head'), tail_form=None, modes=MODES
             assert [conv[l].shape[-1] for l in range(5)] == list(arch.n_filter)
             # every slice is a bit-identical copy of the graded slice of its image
             for sname, a in [('g%d' % l, g[l]) for l in range(1, 5)] + [('logits', logits), ('prob', prob), ('pred', pred)]:
-                for i in range(nd, n):
-                    assert np.array_equal(a[i], a[i % nd]), '%s %s: slice %d differs from slice %d of the same image' % (mode, sname, i, i % nd)
+                check_copies('%s %s' % (mode, sname), a, nd)
             # pred: exact statements on the engine's own outputs, all N slices
             assert np.array_equal(pred, np.argmax(prob, axis=-1).astype(np.int32)), mode + ': pred != argmax(prob)'
             clear = top2_gap(logits) >= np.float32(NEAR_TIE_GAP)
@@ -247,22 +237,10 @@ def run_child(knob, path):
         json.dump(rows, f)
 
 
-_CHILD = r'''
-import sys
-sys.path.insert(0, sys.argv[1])
-sys.path.insert(0, sys.argv[1] + '/tests')
-from test_head_launches_gpu import run_child
-run_child(sys.argv[2], sys.argv[3])
-'''
-
-
 @pytest.mark.parametrize('knob', KNOBS)
 def test_non_default_launches_against_float64(knob, tmp_path):
-    env = {k: v for k, v in os.environ.items() if not k.startswith('UKBB_')}
-    env['PYTHONPATH'] = ROOT + os.pathsep + env.get('PYTHONPATH', '')
-    env[knob] = '1'
     path = str(tmp_path / 'rows.json')
-    r = subprocess.run([sys.executable, '-c', _CHILD, ROOT, knob, path], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+    r = run_in_child('test_head_launches_gpu', 'run_child', [knob, path], {knob: '1'})
     print(''.join(knob + '=1 ' + ln + '\n' for ln in r.stdout.splitlines() if ln.startswith('head-launch')), end='')
     assert r.returncode == 0, r.stdout[-3000:]
     with open(path) as f:

@@ -11,15 +11,13 @@ last layer scaled to 1e-7, which puts part of the pixels on the near-tie path of
 some but not all pixels have a top-two logit gap below 4e-7, so both paths ran.  The f32x3 instance keeps the in-stage tail and is
 not a case."""
 import copy
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+from launch_grading import run_in_child
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = [('FCN_sa', 192, 208, 1), ('FCN_sa', 192, 208, 10), ('FCN_sa', 192, 208, 64), ('FCN_la_2ch', 176, 208, 10),
          ('FCN_sa', 208, 256, 10), ('FCN_la_4ch', 80, 112, 3), ('FCN_la_4ch_seg4', 80, 112, 3)]
 SCALES = (1.0, 1e-7)
@@ -60,26 +58,12 @@ def run_cases(path):
     np.savez(path, **out)
 
 
-_CHILD = r'''
-import sys
-sys.path.insert(0, sys.argv[1])
-from tests.test_head_tail_gpu import run_cases
-run_cases(sys.argv[2])
-'''
-
-
 @pytest.fixture(scope='module')
 def outputs(tmp_path_factory):
-    env = {k: v for k, v in os.environ.items() if not k.startswith('UKBB_')}
-    env['PYTHONPATH'] = ROOT + os.pathsep + env.get('PYTHONPATH', '')
     res = {}
     for tag, knob in (('deferred', None), ('inline', '1')):
-        e = dict(env)
-        if knob:
-            e['UKBB_HEAD_INLINE_TAIL'] = knob
         path = str(tmp_path_factory.mktemp('head_tail') / (tag + '.npz'))
-        r = subprocess.run([sys.executable, '-c', _CHILD, ROOT, path], env=e, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                           text=True, timeout=900)
+        r = run_in_child('test_head_tail_gpu', 'run_cases', [path], {'UKBB_HEAD_INLINE_TAIL': knob} if knob else {}, timeout=900)
         assert r.returncode == 0, r.stdout[-3000:]
         with np.load(path) as z:
             res[tag] = {k: z[k] for k in z.files}

@@ -17,12 +17,11 @@ import numpy as np
 import pytest
 
 import test_lstm_launches_gpu as G
+from launch_grading import CUS, bf16_round, fold, no_case_is_idle
 from oracle import fcn_oracle as O
-from test_bf16_layers_gpu import bf16_round
-from test_fp32_launches_gpu import BOUND, fold
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CUS = 256
+BOUND = G.BOUND
 
 REQUIRED = {
     'fp32: regions of 16 columns', 'fp32: regions of 32 columns', 'fp32: regions of 32 columns, ragged', 'fp32: planned 32-column regions',
@@ -74,14 +73,11 @@ def plan_of(case, precision, knob):
 
 def test_runs_reach_every_regime_and_none_is_idle():
     assert len(set(G.RUNS)) == len(G.RUNS) and set(G.EXPECT) <= set(G.RUNS)
-    per_run = [G.regimes(c, p, *plan_of(c, p, k), cus=CUS) for c, p, k in G.RUNS]
-    for run, s in zip(G.RUNS, per_run):
+    per_run = {(c, p, k): G.regimes(c, p, *plan_of(c, p, k), cus=CUS) for c, p, k in G.RUNS}
+    for run, s in per_run.items():
         print(run, sorted(s))
         assert s >= G.EXPECT.get(run, set()), (run, G.EXPECT[run] - s)
-    assert set().union(*per_run) >= REQUIRED, REQUIRED - set().union(*per_run)
-    for i, run in enumerate(G.RUNS):
-        rest = set().union(*(per_run[:i] + per_run[i + 1:]))
-        assert REQUIRED - rest, 'run %s adds nothing' % (run,)
+    no_case_is_idle(G.RUNS, per_run.__getitem__, REQUIRED)
     # every case in both precisions; the figures the case table of the GPU test's docstring rests on
     assert {(c, p) for c, p, k in G.RUNS if k is None} == {(c, p) for c in G.CASES for p in ('fp32', 'bf16')}
     cols = {c: plan_of(c, 'fp32', None)[0]['tile_cols'] for c in G.CASES}

@@ -53,19 +53,16 @@ tests take 17 s together: the largest case 1.5 s (0.02 s of it the run and read-
 import dataclasses
 import json
 import os
-import subprocess
-import sys
 import time
 
 import numpy as np
 import pytest
 
+from launch_grading import bf16_round, fold, grade, half_ulp, run_in_child, tolerance
 from oracle import fcn_oracle as O
-from test_bf16_layers_gpu import bf16_round, grade, half_ulp
-from test_fp32_launches_gpu import BOUND, fold
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BOUND = 1e-5                             # the project's per-launch fp32 bound (tests/test_fp32_launches_gpu.py BOUND)
 MODEL = 'UNet-LSTM_ao'
 NH = 16                                  # hidden channels
 PROB_ATOL = 1e-5
@@ -344,8 +341,7 @@ def run_engine(case, precision, seed):
 
 def share_half_ulp(got, exact, scale=1.0):
     """Share of the elements inside grade()'s half-ulp tolerance (a hidden map: |h| < 1, scale 1)."""
-    tol = half_ulp(exact) + np.abs(exact) * 2.0 ** -18 + scale * 2.0 ** -20
-    return float(np.mean(np.abs(np.asarray(got, np.float64) - exact) <= tol))
+    return float(np.mean(np.abs(np.asarray(got, np.float64) - exact) <= tolerance(exact, scale, 0.5)))
 
 
 def share_one_ulp(got, exact):
@@ -479,25 +475,17 @@ def test_each_lstm_launch_against_float64_on_its_own_input(case, precision):
     grade_run(case, precision)
 
 
-_CHILD = r'''
-import json, sys
-sys.path.insert(0, sys.argv[1])
-sys.path.insert(0, sys.argv[1] + '/tests')
-from test_lstm_launches_gpu import grade_run
-rows = grade_run(sys.argv[2], sys.argv[3], sys.argv[4])
-with open(sys.argv[5], 'w') as f:
-    json.dump(rows, f)
-'''
+def run_child(case, precision, knob, path):
+    """In a process started with ``knob``: grade the run, leave the rows at ``path``."""
+    rows = grade_run(case, precision, knob)
+    with open(path, 'w') as f:
+        json.dump(rows, f)
 
 
 @pytest.mark.parametrize('case,precision,knob', CHILDREN, ids=['%s-%s-%s' % c for c in CHILDREN])
 def test_lstm_launches_behind_a_knob_against_float64(case, precision, knob, tmp_path):
-    env = {k: v for k, v in os.environ.items() if not k.startswith('UKBB_')}
-    env['PYTHONPATH'] = ROOT + os.pathsep + env.get('PYTHONPATH', '')
-    env[knob.split('=')[0]] = knob.split('=')[1]
     path = str(tmp_path / 'rows.json')
-    r = subprocess.run([sys.executable, '-c', _CHILD, ROOT, case, precision, knob, path], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                       text=True, timeout=120)
+    r = run_in_child('test_lstm_launches_gpu', 'run_child', [case, precision, knob, path], dict([knob.split('=')]), timeout=120)
     print(''.join(ln + '\n' for ln in r.stdout.splitlines() if ln.startswith('lstm-launch')), end='')
     assert r.returncode == 0, r.stdout[-3000:]
     with open(path) as f:

@@ -5,30 +5,13 @@ conv0_0 + conv0_1 is one launch, so the stored conv0_1 map is checked against fl
 model sizes, N = 1, a map of odd tile counts and a map of a single 16 x 16 tile (every halo pixel on the border is zero padding).  Then the
 A/B knob UKBB_NO_WINOGRAD_FIRST=1 (the direct fused kernel) against the default: same outputs to ordinary fp32 rounding (the transforms
 reorder the sums), not bit for bit."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
-from oracle import fcn_oracle as O
+from launch_grading import layer, run_in_child
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BN_EPS = np.float32(1e-3)
 WINO_FIRST = 134
-
-
-def fold(p):
-    sc = (p['gamma'].astype(np.float32) / np.sqrt(p['var'].astype(np.float32) + BN_EPS)).astype(np.float32)
-    b = (p['beta'].astype(np.float32) - (p['mean'].astype(np.float32) * sc).astype(np.float32)).astype(np.float32)
-    return (p['kernel'].astype(np.float32) * sc[None, None, None, :]).astype(np.float64), b.astype(np.float64)
-
-
-def layer(x, p):
-    w, b = fold(p)
-    return np.maximum(O.conv2d_same(x, w, 1) + b, 0.0)
 
 
 def conv0_1_map(model, n, H, W):
@@ -62,28 +45,18 @@ def test_winograd_first_layer_against_float64(model, shape):
     assert err <= 1e-5, err
 
 
-_CHILD = r'''
-import sys
-import numpy as np
-sys.path.insert(0, sys.argv[1])
-from tests.test_wino_first_gpu import conv0_1_map
-got, cfg, _, _ = conv0_1_map('FCN_sa', 2, 192, 208)
-np.save(sys.argv[2], got)
-print('cfg', cfg)
-'''
+def save_headline_map(path):
+    """The stored conv0_1 map of FCN_sa 2 x 192 x 208 with the first layer this process's environment selects, saved; the launch's tiling printed."""
+    got, cfg, _, _ = conv0_1_map('FCN_sa', 2, 192, 208)
+    np.save(path, got)
+    print('cfg', cfg)
 
 
 def test_direct_knob_against_winograd(tmp_path):
-    env = {k: v for k, v in os.environ.items() if k not in ('UKBB_CONV_CFG', 'UKBB_NO_WINOGRAD_FIRST', 'UKBB_NO_FUSE_FIRST')}
-    env['PYTHONPATH'] = ROOT + os.pathsep + env.get('PYTHONPATH', '')
     out = {}
     for tag, knob in (('wino', None), ('direct', '1')):
-        e = dict(env)
-        if knob:
-            e['UKBB_NO_WINOGRAD_FIRST'] = knob
         path = str(tmp_path / (tag + '.npy'))
-        r = subprocess.run([sys.executable, '-c', _CHILD, ROOT, path], env=e, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                           text=True, timeout=600)
+        r = run_in_child('test_wino_first_gpu', 'save_headline_map', [path], {'UKBB_NO_WINOGRAD_FIRST': knob} if knob else {}, timeout=600)
         assert r.returncode == 0, r.stdout[-3000:]
         cfg = int(r.stdout.split('cfg')[-1].split()[0])
         assert (cfg == WINO_FIRST) == (knob is None), cfg

@@ -21,56 +21,49 @@ there because without it no case reaches 302.  The ConvLSTM gate convolutions of
 not this instance, so there is no cine case.  Together the ids 300, 301 and 302 are all reached.
 
 The two children take about 7 s together on an MI355X (profiles/r13_notes.md)."""
+import hashlib
 import json
-import os
-import subprocess
-import sys
 
+import numpy as np
 import pytest
 
+from launch_grading import run_in_child
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KNOB = 'UKBB_WINO_STAGE_PARENT'
 
 CASES = [('FCN_sa', 1, 192, 208), ('FCN_sa', 17, 192, 208), ('FCN_sa', 33, 192, 208), ('FCN_sa', 2, 32, 48), ('FCN_sa', 1, 208, 256),
          ('UNet_ao', 1, 256, 256), ('FCN_sa', 17, 144, 16)]
 LEVEL4_TILING = [301, 300, 300, 305, 305, 305, 302]
 
-_CHILD = r'''
-import hashlib, json, sys
-sys.path.insert(0, sys.argv[1])
-import numpy as np
-from ukbb_cardiac_amd import engine
-from ukbb_cardiac_amd.arch import MODELS
-from ukbb_cardiac_amd.weights import synthetic_params
-out = []
-for i, (model, n, H, W) in enumerate(json.loads(sys.argv[2])):
-    arch = MODELS[model]
-    img = np.random.default_rng(100 + i).standard_normal((n, H, W, 1)).astype(np.float32)
-    with engine.Engine(arch, synthetic_params(arch, 1234)) as eng:
-        res = eng.run(img, want_logits=True)
-        cfg = dict(zip(eng.kernel_names(), eng.kernel_configs()))
-        maps = {'logits': res['logits'], 'pred': res['pred']}
-        last = arch.n_block[4] - 1
-        for b in range(1, last + 1):
-            name = 'conv4' if b == last else 'conv4_%d' % b
-            maps['conv4_%d' % b] = eng.activation(name)
-    out.append({'cfg': {k: v for k, v in cfg.items() if k.startswith('conv4_')},
-                'all_cfg': sorted(set(cfg.values())),
-                'sha': {k: hashlib.sha256(np.ascontiguousarray(v).tobytes()).hexdigest() for k, v in maps.items()},
-                'nonzero': {k: int(np.count_nonzero(v)) for k, v in maps.items()}})
-with open(sys.argv[3], 'w') as f:
-    json.dump(out, f)
-'''
+
+def run_cases(path):
+    """Per case, with the stage loop this process's environment selects: the tilings that ran and SHA-256 digests of the level-4 maps, the logits and the labels."""
+    from ukbb_cardiac_amd import engine
+    from ukbb_cardiac_amd.arch import MODELS
+    from ukbb_cardiac_amd.weights import synthetic_params
+    out = []
+    for i, (model, n, H, W) in enumerate(CASES):
+        arch = MODELS[model]
+        img = np.random.default_rng(100 + i).standard_normal((n, H, W, 1)).astype(np.float32)
+        with engine.Engine(arch, synthetic_params(arch, 1234)) as eng:
+            res = eng.run(img, want_logits=True)
+            cfg = dict(zip(eng.kernel_names(), eng.kernel_configs()))
+            maps = {'logits': res['logits'], 'pred': res['pred']}
+            last = arch.n_block[4] - 1
+            for b in range(1, last + 1):
+                name = 'conv4' if b == last else 'conv4_%d' % b
+                maps['conv4_%d' % b] = eng.activation(name)
+        out.append({'cfg': {k: v for k, v in cfg.items() if k.startswith('conv4_')},
+                    'all_cfg': sorted(set(cfg.values())),
+                    'sha': {k: hashlib.sha256(np.ascontiguousarray(v).tobytes()).hexdigest() for k, v in maps.items()},
+                    'nonzero': {k: int(np.count_nonzero(v)) for k, v in maps.items()}})
+    with open(path, 'w') as f:
+        json.dump(out, f)
 
 
 def run_child(knob_value, path):
-    env = {k: v for k, v in os.environ.items() if not k.startswith('UKBB_')}
-    env['PYTHONPATH'] = ROOT + os.pathsep + env.get('PYTHONPATH', '')
-    if knob_value is not None:
-        env[KNOB] = knob_value
-    r = subprocess.run([sys.executable, '-c', _CHILD, ROOT, json.dumps(CASES), path], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                       text=True, timeout=120)
+    r = run_in_child('test_wino_level4_gpu', 'run_cases', [path], {} if knob_value is None else {KNOB: knob_value}, timeout=120)
     assert r.returncode == 0, r.stdout[-3000:]
     with open(path) as f:
         return json.load(f)
