@@ -20,7 +20,11 @@ with a scrubbed environment (run_in_child).
 
 The planner side (config_name, tile_of, fit_of, replay_records, no_case_is_idle) and the mirror of the walker launchers' grid arithmetic (ws_launch,
 stem_launch, tail_launch, launch_class; its constants are asserted against the sources in tests/test_bf16_launch_coverage.py) are what the coverage
-files count situations with, and what the graders name a launch's situation with in the rows they print."""
+files count situations with, and what the graders name a launch's situation with in the rows they print.
+
+The Temporal-UNet (tests/test_temporal_launches_gpu.py, tests/test_temporal_launch_coverage.py) takes the same graph (launches) on 3-D units: layer3d
+on tests/temporal_unet_ref.py, batches of windows (distinct_windows, window_batch), the mirror of launch_conv3d's arithmetic (conv3d_launch) and the
+grid caps of the kind's two grid-stride kernels read from the source (grid_caps_3d)."""
 import json
 import os
 import re
@@ -33,6 +37,8 @@ TESTS = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(TESTS)
 if ROOT not in sys.path:                                            # the oracle, when imported outside pytest (tests/conftest.py does the same)
     sys.path.insert(0, ROOT)
+if TESTS not in sys.path:                                           # tests/temporal_unet_ref.py, likewise
+    sys.path.insert(0, TESTS)
 
 from oracle import fcn_oracle as O                                  # noqa: E402
 
@@ -53,14 +59,14 @@ def bf16_round(x):
 
 def fold(p, transposed=False):
     """engine.cpp create(): sc = gamma / sqrtf(var + eps); W' = W * sc; b' = beta - mean * sc, all float32, no contraction.  A layer without BN
-    keeps its kernel and bias."""
+    keeps its kernel and bias.  2-D ([kh,kw,Cin,Cout], transposed [kh,kw,Cout,Cin]) and 3-D kernels ([kd,kh,kw,Cin,Cout], [kd,kh,kw,Cout,Cin]) alike."""
     k = p['kernel'].astype(np.float32)
     if 'gamma' not in p:
         return k, p['bias'].astype(np.float32)
     sc = (p['gamma'].astype(np.float32) / np.sqrt(p['var'].astype(np.float32) + BN_EPS)).astype(np.float32)
     ms = (p['mean'].astype(np.float32) * sc).astype(np.float32)
     b = (p['beta'].astype(np.float32) - ms).astype(np.float32)
-    return (k * (sc[None, None, :, None] if transposed else sc[None, None, None, :])).astype(np.float32), b
+    return (k * (sc[:, None] if transposed else sc)).astype(np.float32), b          # the scale runs over Cout: the last axis, or the one before it
 
 
 def layer(x, p, stride=1, transposed=False, relu=True, round_w=False, round_x=False):
@@ -74,6 +80,16 @@ def layer(x, p, stride=1, transposed=False, relu=True, round_w=False, round_x=Fa
         x = bf16_round(x)
     x, w = np.asarray(x, np.float64), w.astype(np.float64)
     y = (O.conv2d_transpose_same(x, w, stride) if transposed else O.conv2d_same(x, w, stride)) + b.astype(np.float64)
+    return np.maximum(y, 0.0) if relu else y
+
+
+def layer3d(x, p, stride=1, transposed=False, relu=True):
+    """One conv3d_bn_relu / conv3d_transpose_bn_relu / biased 1x1x1 conv of the Temporal-UNet in float64 on x [N,T,H,W,C] (tests/temporal_unet_ref.py
+    conv3d_same / conv3d_transpose_same; time stride 1, `stride` in space), with the engine's float32 fold applied to float64 copies."""
+    import temporal_unet_ref as R3
+    w, b = fold(p, transposed)
+    x, w = np.asarray(x, np.float64), w.astype(np.float64)
+    y = (R3.conv3d_transpose_same(x, w, stride) if transposed else R3.conv3d_same(x, w, stride)) + b.astype(np.float64)
     return np.maximum(y, 0.0) if relu else y
 
 
@@ -136,20 +152,43 @@ def normalised_copies(index, n, H, W):
     return ((img - np.float32(0.3)) / np.float32(0.25)).astype(np.float32), nd
 
 
+def distinct_windows(T, H, W):
+    """The three input kinds as windows of T frames, [3, T, H, W, 1] float32, normalised as normalised_copies does: a cine_phantom window, a
+    uniform-noise window, standard-normal noise scaled to the phantom's range.  The two noise windows are independent from frame to frame, so a wrong
+    or reversed time tap is not hidden by a cine that is smooth in time."""
+    from ukbb_cardiac_amd.phantom import cine_phantom, uniform_slices
+    ph = cine_phantom(T, H, W, seed=17)
+    un = uniform_slices(T, H, W, seed=5)
+    z = np.random.default_rng(29).standard_normal((T, H, W, 1))
+    lo, hi = float(ph.min()), float(ph.max())
+    nz = (lo + (z - z.min()) / (z.max() - z.min()) * (hi - lo)).astype(np.float32)
+    return ((np.stack([ph, un, nz]).astype(np.float32) - np.float32(0.3)) / np.float32(0.25)).astype(np.float32)
+
+
+def window_batch(index, n, T, H, W):
+    """batch_of_copies for windows: window i = distinct[i % 3]; a batch of one takes the three kinds in turn over the case list.  Returns
+    (batch [n, T, H, W, 1], number of distinct windows)."""
+    d = distinct_windows(T, H, W)
+    if n == 1:
+        return d[index % 3:index % 3 + 1].copy(), 1
+    return np.stack([d[i % 3] for i in range(n)]), min(n, 3)
+
+
 # ---- the graph --------------------------------------------------------------------------------------------------------------------------------------
 def launches(arch):
-    """The graph, launch by launch, as the reference defines it (common/network.py build_FCN's encoder, network_ao.py build_UNet):
-    (layer name, stored name, level, input stored names, stride, transposed, relu).  '' as the input is the image."""
+    """The graph, launch by launch, as the reference defines it (common/network.py build_FCN's encoder, network_ao.py build_UNet; the Temporal-UNet
+    is the same graph on 3-D units): (layer name, stored name, level, input stored names, stride, transposed, relu).  '' as the input is the image."""
+    from ukbb_cardiac_amd.arch import KIND_FCN, KIND_TEMPORAL_UNET
     nb = arch.n_block
 
-    def stored(kind, l, i):
-        return '%s%d' % (kind, l) if i == nb[l] - 1 else '%s%d_%d' % (kind, l, i)
+    def stored(kind, l, i):                                         # the 2-D plans name a level's last map after the level, the 3-D plan after its layer
+        return '%s%d' % (kind, l) if i == nb[l] - 1 and arch.kind != KIND_TEMPORAL_UNET else '%s%d_%d' % (kind, l, i)
     out = []
     for l in range(arch.n_level):
         for i in range(nb[l]):
             src = '' if (l, i) == (0, 0) else stored('conv', l - 1, nb[l - 1] - 1) if i == 0 else stored('conv', l, i - 1)
             out.append(('conv%d_%d' % (l, i), stored('conv', l, i), l, [src], 2 if (l > 0 and i == 0) else 1, False, True))
-    if arch.name.startswith('UNet'):
+    if arch.kind != KIND_FCN:                                       # UNet, UNet-LSTM, Temporal-UNet: the decoder and conv_out
         below = stored('conv', arch.n_level - 1, nb[-1] - 1)
         for l in range(arch.n_level - 2, -1, -1):
             out.append(('up%d_t' % l, 'up%d_t' % l, l, [below], 2, True, True))
@@ -322,6 +361,45 @@ def launch_class(op, acts, n):
         w = ws_launch(op, acts, n)
         return '%s %s' % (w['cls'], w['order'])
     return '-'
+
+
+# ---- the Temporal-UNet's launchers (kernels_conv3d.hip; constants asserted against the source in tests/test_temporal_launch_coverage.py) -------------
+C3D_PIX, C3D_COB, C3D_WAVES = 32, 32, 4                            # pixels and output channels of one MFMA tile; items (waves) per workgroup
+C3D_FIRST_CAP = 256 * 64 * 256                                     # threads launch_conv3d_first starts at most: beyond, conv3d_first_kernel's loop wraps
+T3D_TILE_CAP = 256 * 16 * 256                                      # the same for launch_t3d_tile / t3d_tile_kernel
+
+
+def grid_caps_3d():
+    """(C3D_FIRST_CAP, T3D_TILE_CAP) as kernels_conv3d.hip holds them: the workgroup cap of launch_conv3d_first / launch_t3d_tile x 256 threads, each
+    kernel's loop advancing by gridDim.x * 256.  A graded case that relies on a loop wrapping asserts these, so that a later change of a cap fails the
+    test and does not silently void it."""
+    with open(os.path.join(ROOT, 'ukbb_cardiac_amd', 'csrc', 'kernels_conv3d.hip')) as f:
+        src = f.read()
+    caps = []
+    for launcher, kernel in (('launch_conv3d_first', 'conv3d_first_kernel'), ('launch_t3d_tile', 't3d_tile_kernel')):
+        body = re.search(r'hipError_t %s\(.*?\n}\n' % launcher, src, re.S).group(0)
+        m = re.search(r'long long blocks = \(total \+ 255\) / 256;\n    if \(blocks > (\d+) \* (\d+)\) blocks = \1 \* \2;', body)
+        assert m and re.search(r'dim3\(\(unsigned\)blocks\), dim3\(256\)|dim3 g\(\(unsigned\)blocks\), t\(256\)', body), body     # a 1-D grid of 256 threads
+        loop = re.search(r'void %s\(.*?\n}\n' % kernel, src, re.S).group(0)
+        assert 'for (long long id = (long long)blockIdx.x * 256 + threadIdx.x; id < total; id += (long long)gridDim.x * 256)' in loop, loop
+        caps.append(int(m.group(1)) * int(m.group(2)) * 256)
+    assert tuple(caps) == (C3D_FIRST_CAP, T3D_TILE_CAP), caps
+    return tuple(caps)
+
+
+def conv3d_launch(op, acts, n_images, T):
+    """launch_conv3d's arithmetic for one 'conv3d' / 'tconv3d' plan op on n_images = windows x T frames: the kernel's item count and the facets of the
+    launch's situation.  A transposed conv walks its INPUT map, once per sub-pixel phase."""
+    cout = acts[op['out']]['channels']
+    cout_pad = -(-cout // C3D_COB) * C3D_COB
+    cb = 2 if cout_pad % (2 * C3D_COB) == 0 else 1
+    npix = op['H'] * op['W'] if op['kind'] == 'tconv3d' else op['Ho'] * op['Wo']
+    ptiles, cgroups = -(-npix // C3D_PIX), cout_pad // C3D_COB // cb
+    items = n_images * ptiles * cgroups
+    kind = 'transposed' if op['kind'] == 'tconv3d' else 'two-source' if op['in1'] >= 0 else 'stride-%d' % op['stride']
+    fit = 'divides' if npix % C3D_PIX == 0 else 'single pixel' if npix == 1 else 'one partial tile' if npix < C3D_PIX else 'whole tiles and a partial one'
+    return dict(kind=kind, cb=cb, cgroups=cgroups, padded=cout < cout_pad, fit=fit, items=items, idle=items % C3D_WAVES,
+                T='T=1' if T == 1 else 'T=3' if T == 3 else 'T>=5', windows='one window' if n_images == T else 'several windows')
 
 
 class Report:
