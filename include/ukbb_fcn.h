@@ -64,7 +64,7 @@ extern "C" {
                                weights [TF-recall]: per layer of the UNet order (encoder convs; per decoder level the transposed
                                conv then its convs; conv_out) the kernel -- conv3d DHWIO [3,3,3,Cin,Cout], conv3d_transpose
                                [3,3,3,Cout,Cin], conv_out [1,1,1,16,n_class] -- then gamma, beta, moving_mean, moving_variance
-                               (BN epsilon 1e-3), or the bias for conv_out.  fp32 only (set_precision(BF16) -> UKBB_EARCH).
+                               (BN epsilon 1e-3), or the bias for conv_out.  fp32, or UKBB_PREC_BF16_3D (set_precision(BF16) -> UKBB_EARCH).
                                Use forward_seq / forward_cine. */
 
 /* Hyper-parameters of build_FCN / UNet as bound in common/train_network.py:174-195
@@ -137,6 +137,15 @@ void ukbb_fcn_destroy(ukbb_fcn_handle *h);
  * other kind set_precision returns UKBB_EARCH for this code: those kinds already store bf16 under UKBB_PREC_BF16.  Opt-in; each launch is graded
  * in tests/test_fcn_bf16_store_launches_gpu.py. */
 #define UKBB_PREC_BF16_STORE 3
+/* UKBB_PREC_BF16_3D (UKBB_KIND_TEMPORAL_UNET only; additive to ABI 11, as UKBB_PREC_BF16_STORE is): the 3-D convolutions on v_mfma_f32_32x32x16_bf16 with fp32 accumulation
+ * (kernels_conv3d_bf16.hip).  Where it rounds: the folded 3x3x3 kernels are rounded to bf16 (RNE) once, when they are packed; every map a 3-D
+ * launch stores (conv*, up*_t, up*) is rounded once, after bias + ReLU, as it is stored -- bf16, channel-blocked [N][C/16][H*W][16]; a stored
+ * map is read back without any further rounding.  The first layer (C_in = 1) runs in fp32 on the fp32 frames with the unrounded folded
+ * weights and rounds only what it stores.  conv_out widens the stored up0_1 exactly and runs the fp32 logits launch: logits, prob, the window
+ * probabilities of forward_cine and pred stay fp32 / int32, and the window tiling is the fp32 one.  The activation workspace and the cine
+ * scratch take 2 bytes per activation element.  UKBB_PREC_BF16 and UKBB_PREC_BF16_STORE stay refused on this kind, and every other kind
+ * returns UKBB_EARCH for this code.  Opt-in; each launch is graded in tests/test_temporal_bf16_launches_gpu.py. */
+#define UKBB_PREC_BF16_3D 4
 int ukbb_fcn_set_precision(ukbb_fcn_handle *h, int precision);
 
 /* Pre-size the activation workspace for batches up to n x h x w (optional;
@@ -199,11 +208,11 @@ int ukbb_fcn_forward_seq(ukbb_fcn_handle *h, const float *image, int n_seq, int 
  * Temporal-UNet (kind 3): the same call, bit for bit the same tiling arithmetic and corner cases, but each window runs the whole 3-D
  * network on its T frames (its first layer reads them from `image` through a window -> frame table).  Windows run in chunks of Wc,
  * in ascending order (results do not depend on Wc); device scratch the handle keeps, with HW = H*W, C = n_class and the standard
- * filters 16..256 (the activations of every layer, 152*HW floats per frame):
- *   Wc*T*(152 + C)*HW*4 bytes  +  tables (Wn*T + F*T)*4 + (T + F)*8 bytes,
+ * filters 16..256 (the activations of every layer, 152*HW elements per frame of e = 4 bytes, or 2 under UKBB_PREC_BF16_3D):
+ *   Wc*T*(152*e + C*4)*HW bytes  +  tables (Wn*T + F*T)*4 + (T + F)*8 bytes,
  * Wc = the largest number of windows that keeps the first term within 4e9 bytes (at least 1), or, with a scratch budget, the whole sum
  * within the budget; UKBB_TEMPORAL_CHUNK_WINDOWS=n overrides both (a test knob):
- * 256x256, T = 9, C = 3: Wc = 10, 3.66 GB, whatever the number of frames. */
+ * 256x256, T = 9, C = 3: Wc = 10, 3.66 GB in fp32 (Wc = 21 under UKBB_PREC_BF16_3D), whatever the number of frames. */
 int ukbb_fcn_forward_cine(ukbb_fcn_handle *h, const float *image, int n_frames, int height, int width,
                           int weight_R, double weight_r, int time_step, float *prob, int32_t *pred, void *stream);
 
@@ -220,8 +229,9 @@ int ukbb_fcn_set_scratch_budget(ukbb_fcn_handle *h, uint64_t bytes);
 /* Bytes of device memory the handle holds right now in its activation, staging and cine buffers (weights and packed filters excluded). */
 uint64_t ukbb_fcn_scratch_bytes(const ukbb_fcn_handle *h);
 /* What forward_cine allocates for this call under `budget` (0 = none) on a fresh handle: host arithmetic only, no device needed (like
- * ukbb_fcn_weight_count).  precision: UKBB_PREC_FP32 | UKBB_PREC_BF16.  0 for a malformed request (kinds 0 / 1, shape not a multiple of 16,
- * fewer frames than the window radius, time_step < 1, bf16 Temporal-UNet) and for a budget below the minimum.  The engine plans its chunks
+ * ukbb_fcn_weight_count).  precision: UKBB_PREC_FP32 | UKBB_PREC_BF16 | UKBB_PREC_BF16_3D.  0 for a malformed request (kinds 0 / 1, shape not a
+ * multiple of 16, fewer frames than the window radius, time_step < 1, a precision the kind refuses: UKBB_PREC_BF16 on a Temporal-UNet,
+ * UKBB_PREC_BF16_3D on a UNet-LSTM) and for a budget below the minimum.  The engine plans its chunks
  * with the same function.  The fp32 region shape is chosen for the MI355X's 256 compute units and cines of n_frames frames. */
 uint64_t ukbb_fcn_cine_scratch_bytes(const ukbb_fcn_arch *arch, int precision, int n_frames, int height, int width, int time_step,
                                      uint64_t budget);

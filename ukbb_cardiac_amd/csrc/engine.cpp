@@ -340,13 +340,15 @@ int ensure_packed_tconv(ukbb_fcn_handle *h, int layer, const ConvConfig &c, cons
 
 // Temporal-UNet (kind 3), kernels_conv3d.hip:
 // Weights of conv3d (kernel order (kt, ky, kx)) or of one sub-pixel phase (py, px) of conv3d_transpose (kt reversed: the
-// transposed conv reads in[t + 1 - kt], kernels_conv3d.hip), packed for conv3d_kernel; key "<layer>/pk3d<phase>".
-const float *ensure_packed3d(ukbb_fcn_handle *h, const HostLayer &L, int py, int px, int ny, int nx) {
+// transposed conv reads in[t + 1 - kt], kernels_conv3d.hip), packed for conv3d_kernel; key "<layer>/pk3d<phase>".  bf16 (UKBB_PREC_BF16_3D): the
+// same fold rounded once to bf16, packed for conv3d_bf16_kernel (kernels_conv3d_bf16.hip); key "<layer>/pk3d<phase>bf16".  A handle that
+// switches precision holds both.
+const float *ensure_packed3d(ukbb_fcn_handle *h, const HostLayer &L, int py, int px, int ny, int nx, bool bf16) {
     char key[128];
-    snprintf(key, sizeof key, "%s/pk3d%d%d", L.name.c_str(), py, px);
+    snprintf(key, sizeof key, "%s/pk3d%d%d%s", L.name.c_str(), py, px, bf16 ? "bf16" : "");
     if (const float *p = dev_ptr(h, key)) return p;
     const int ntap = 3 * ny * nx, cpad = round_up(L.cout, 32);
-    std::vector<float> w((size_t)ntap * L.cin * L.cout), pk((size_t)ntap * L.cin * cpad);
+    std::vector<float> w((size_t)ntap * L.cin * L.cout), pk((size_t)ntap * L.cin * cpad / (bf16 ? 2 : 1));
     for (int dti = 0; dti < 3; ++dti)
         for (int jy = 0; jy < ny; ++jy)
             for (int jx = 0; jx < nx; ++jx) {
@@ -355,7 +357,8 @@ const float *ensure_packed3d(ukbb_fcn_handle *h, const HostLayer &L, int py, int
                 const size_t src = (((size_t)kt * 3 + ky) * 3 + kx) * L.cin * L.cout, dst = (((size_t)dti * ny + jy) * nx + jx) * L.cin * L.cout;
                 std::copy(L.w.begin() + src, L.w.begin() + src + (size_t)L.cin * L.cout, w.begin() + dst);
             }
-    pack_conv3d_weights(w.data(), ntap, L.cin, L.cout, cpad, pk.data());
+    if (bf16) pack_conv3d_weights_bf16(w.data(), ntap, L.cin, L.cout, cpad, pk.data());
+    else pack_conv3d_weights(w.data(), ntap, L.cin, L.cout, cpad, pk.data());
     if (upload(h, key, pk)) return nullptr;
     return dev_ptr(h, key);
 }
@@ -410,8 +413,8 @@ int ensure_packed_lstm(ukbb_fcn_handle *h) {
 }
 
 // Packs and uploads what `op`'s kind and tiling need and fills every device pointer its launch takes: the op's own and the shared ones
-// of h->par.  The launches search nothing afterwards; a key the handle lacks ends the plan here, with UKBB_EARCH.
-int bind_op(ukbb_fcn_handle *h, BoundOp &op) {
+// of h->par.  The launches search nothing afterwards; a key the handle lacks ends the plan here, with UKBB_EARCH.  mode: of the plan being bound.
+int bind_op(ukbb_fcn_handle *h, BoundOp &op, const PlanMode &mode) {
     Params &P = h->par;
     const std::string who = "op " + op.name, lname = op.layer >= 0 ? h->layers[op.layer].name : std::string();
     int rc = UKBB_OK;
@@ -452,13 +455,13 @@ int bind_op(ukbb_fcn_handle *h, BoundOp &op) {
         case OP_LOGITS: logits(); break;
         case OP_FIRST3D: conv0(); need(op.bias, lname + "/bias"); break;
         case OP_CONV3D:
-            if (!(op.wpk = ensure_packed3d(h, h->layers[op.layer], 0, 0, 3, 3))) rc = UKBB_EDEVICE;
+            if (!(op.wpk = ensure_packed3d(h, h->layers[op.layer], 0, 0, 3, 3, mode.bfio()))) rc = UKBB_EDEVICE;
             need(op.bias, lname + "/bias");
             break;
         case OP_TCONV3D:
             for (int ph = 0; ph < 4 && !rc; ++ph) {
                 const int py = ph >> 1, px = ph & 1;
-                if (!(op.wph[ph] = ensure_packed3d(h, h->layers[op.layer], py, px, py ? 1 : 2, px ? 1 : 2))) rc = UKBB_EDEVICE;
+                if (!(op.wph[ph] = ensure_packed3d(h, h->layers[op.layer], py, px, py ? 1 : 2, px ? 1 : 2, mode.bfio()))) rc = UKBB_EDEVICE;
             }
             need(op.bias, lname + "/bias");
             break;
@@ -502,7 +505,7 @@ int materialize_plan(ukbb_fcn_handle *h, PlanLayout &L) {
     std::vector<BoundOp> ops;
     for (const Op &op : L.ops) {
         ops.emplace_back(op);
-        const int rc = bind_op(h, ops.back());
+        const int rc = bind_op(h, ops.back(), L.mode);
         if (rc) return rc;
     }
     if (L.needs_lstm) {
@@ -682,7 +685,11 @@ int launch_op(ukbb_fcn_handle *h, const BoundOp &op, const PlanIo &io, int n0, i
             e = launch_logits(la, s);
             break;
         }
-        case OP_FIRST3D: e = launch_conv3d_first(Conv3dFirstArgs{io.image, h->t3d_map, P.conv0_w, op.bias, actp(op.out), n, a.fc, op.H, op.W}, s); break;
+        case OP_FIRST3D: {
+            const Conv3dFirstArgs fa{io.image, h->t3d_map, P.conv0_w, op.bias, actp(op.out), n, a.fc, op.H, op.W};
+            e = bfio ? launch_conv3d_first_bf16(fa, s) : launch_conv3d_first(fa, s);         // UKBB_PREC_BF16_3D: the same arithmetic, 16 bf16 channels stored
+            break;
+        }
         case OP_CONV3D:
         case OP_TCONV3D: {
             Conv3dArgs ca{};
@@ -704,7 +711,7 @@ int launch_op(ukbb_fcn_handle *h, const BoundOp &op, const PlanIo &io, int n0, i
                 ca.nph = 4;
                 for (int ph = 0; ph < 4; ++ph) ca.ph[ph] = Conv3dPhase{op.wph[ph], ph >> 1, ph & 1, (ph >> 1) ? 1 : 2, (ph & 1) ? 1 : 2};
             }
-            e = launch_conv3d(ca, s);
+            e = bfio ? launch_conv3d_bf16(ca, s) : launch_conv3d(ca, s);                     // UKBB_PREC_BF16_3D: bf16 maps and A fragments, same tiling
             break;
         }
         default:
@@ -1133,7 +1140,7 @@ namespace {
 bool cine_query_units(const ukbb_fcn_arch *arch, int precision, int F, int H, int W, int time_step, CineUnits &u) {
     if (!arch || !ukbb_fcn_weight_count(arch)) return false;
     if (arch->kind != UKBB_KIND_UNET_LSTM && arch->kind != UKBB_KIND_TEMPORAL_UNET) return false;
-    if (precision != UKBB_PREC_FP32 && precision != UKBB_PREC_BF16) return false;
+    if (precision != UKBB_PREC_FP32 && precision != UKBB_PREC_BF16 && precision != UKBB_PREC_BF16_3D) return false;
     PlanLayout L;
     const char *why;
     if (plan_mode(*arch, precision, L.mode, &why) || !cine_request_ok(arch->fc, F, H, W, time_step)) return false;
@@ -1156,7 +1163,7 @@ int release_scratch(ukbb_fcn_handle *h) {
 // first (buffers only grow otherwise, and two shapes' maxima together could exceed the budget).
 int budget_enter(ukbb_fcn_handle *h, int F, int H, int W, int time_step, const CinePlan &pl) {
     if (!h->scratch_budget) return UKBB_OK;
-    const long long key = ((((((long long)F * 4099 + H) * 4099 + W) * 4099 + time_step) * 4099 + pl.Wc) * 4 + h->precision) ^ (long long)(h->scratch_budget * 0x9E3779B97F4A7C15ull >> 1);
+    const long long key = ((((((long long)F * 4099 + H) * 4099 + W) * 4099 + time_step) * 4099 + pl.Wc) * 8 + h->precision) ^ (long long)(h->scratch_budget * 0x9E3779B97F4A7C15ull >> 1);
     if (h->budget_key == key) return UKBB_OK;
     int rc = release_scratch(h);
     if (rc) return rc;

@@ -469,6 +469,14 @@ struct Conv3dFirstArgs {    // first layer, C_in = 1 -> 16, 3x3x3, stride 1 (+ f
 };
 hipError_t launch_conv3d_first(const Conv3dFirstArgs &a, hipStream_t s);
 
+// UKBB_PREC_BF16_3D (kernels_conv3d_bf16.hip): the same launches on v_mfma_f32_32x32x16_bf16.  The argument structs are the fp32 ones with
+// every map bf16, channel-blocked [N][C/16][H*W][16] (in0 / in1 / out point at bf16; C0, C1 multiples of 16), wpk the A fragments of
+// pack_conv3d_weights_bf16 (the folded kernel rounded once to bf16); bias stays fp32.  The first layer reads the fp32 cine and the
+// unrounded fp32 folded weights and stores its 16 channels as bf16.
+hipError_t launch_conv3d_bf16(const Conv3dArgs &a, hipStream_t s);
+hipError_t launch_conv3d_first_bf16(const Conv3dFirstArgs &a, hipStream_t s);
+void pack_conv3d_weights_bf16(const float *w /*[ntap][cin][cout]*/, int ntap, int cin, int cout, int cout_pad, float *dst /*ntap * cin * cout_pad / 2 dwords*/);
+
 struct T3dTileArgs {        // weighted circular tiling (deploy_network_ao.py:176-183) of the windows [w0, w1) of a cine
     const float *probw;     // [(w1 - w0) * K][HW][C]: softmax of each window frame
     CineTable tb;           // of the whole cine

@@ -512,7 +512,7 @@ int plan_tconv(Planner &p, const std::string &lname, int in0, int H, int W, int 
     return UKBB_OK;
 }
 
-// ---- Temporal-UNet (kind 3): network_ao.py:67-114 on kernels_conv3d.hip -------------------------------------------
+// ---- Temporal-UNet (kind 3): network_ao.py:67-114 on kernels_conv3d.hip (fp32) / kernels_conv3d_bf16.hip (UKBB_PREC_BF16_3D: the same ops and tiling) -------------------------------------------
 int plan_conv3d(Planner &p, const std::string &lname, int in0, int in1, int H, int W, int stride, int *out_buf) {
     const int li = p.layer(lname);
     const Spec &L = p.specs[li];
@@ -767,13 +767,16 @@ void layout_split_range(const Planner &p, const Knobs &kn) {
 int plan_mode(const ukbb_fcn_arch &a, int precision, PlanMode &m, const char **why) {
     m = PlanMode();
     *why = "";
-    if (precision != UKBB_PREC_FP32 && precision != UKBB_PREC_BF16 && precision != UKBB_PREC_F32X3 && precision != UKBB_PREC_BF16_STORE) { *why = "bad precision"; return UKBB_EINVAL; }
-    if (a.kind == UKBB_KIND_TEMPORAL_UNET && precision == UKBB_PREC_BF16) { *why = "the Temporal-UNet's 3-D convolutions are built for fp32 only (no bf16 plan)"; return UKBB_EARCH; }
+    if (precision != UKBB_PREC_FP32 && precision != UKBB_PREC_BF16 && precision != UKBB_PREC_F32X3 && precision != UKBB_PREC_BF16_STORE && precision != UKBB_PREC_BF16_3D) { *why = "bad precision"; return UKBB_EINVAL; }
+    if (a.kind == UKBB_KIND_TEMPORAL_UNET && precision == UKBB_PREC_BF16) { *why = "the Temporal-UNet's 3-D convolutions are built for fp32 only (no bf16 plan) under this code; their bf16 mode is UKBB_PREC_BF16_3D ('bf16_3d')"; return UKBB_EARCH; }
+    if (a.kind == UKBB_KIND_TEMPORAL_UNET && precision == UKBB_PREC_BF16_STORE) { *why = "UKBB_PREC_BF16_STORE is the FCN's bf16-storage mode; the U-Net kinds already store bf16 under UKBB_PREC_BF16 (the Temporal-UNet: fp32 only under that code, bf16 under UKBB_PREC_BF16_3D, 'bf16_3d')"; return UKBB_EARCH; }
     if (a.kind != UKBB_KIND_FCN && precision == UKBB_PREC_BF16_STORE) { *why = "UKBB_PREC_BF16_STORE is the FCN's bf16-storage mode; the U-Net kinds already store bf16 under UKBB_PREC_BF16"; return UKBB_EARCH; }
+    if (a.kind != UKBB_KIND_TEMPORAL_UNET && precision == UKBB_PREC_BF16_3D) { *why = "UKBB_PREC_BF16_3D is the bf16 mode of the Temporal-UNet's 3-D convolutions; the 2-D kinds take UKBB_PREC_BF16 (the FCN also UKBB_PREC_BF16_STORE)"; return UKBB_EARCH; }
     // UKBB_PREC_BF16 means operands only on an FCN handle (pinned by recorded plans and graders) and storage on the U-Net kinds; with
     // UKBB_PREC_BF16_STORE the FCN encoder takes the same bf16-storage kernels (squeeze and head read the bf16 maps and stay fp32)
     if (precision == UKBB_PREC_BF16) m.bf16 = a.kind == UKBB_KIND_FCN ? Bf16Mode::Operands : Bf16Mode::Storage;
     if (precision == UKBB_PREC_BF16_STORE) m.bf16 = Bf16Mode::Storage;
+    if (precision == UKBB_PREC_BF16_3D) m.bf16 = Bf16Mode::Storage;       // every 3-D map bf16, channel-blocked (kernels_conv3d_bf16.hip)
     m.head_x3 = precision == UKBB_PREC_F32X3;
     return UKBB_OK;
 }
@@ -786,7 +789,7 @@ int layout_plan(const ukbb_fcn_arch &a, int precision, int H, int W, int n_hint,
     std::string why;
     if (!arch_specs(a, p.specs)) { set_error("malformed architecture descriptor"); return UKBB_EARCH; }
     if (!supported(a, why)) { set_error("unsupported architecture: %s", why.c_str()); return UKBB_EARCH; }
-    if (a.kind == UKBB_KIND_TEMPORAL_UNET) return layout_t3d(p, H, W);      // fp32 only, no split range, no knobs
+    if (a.kind == UKBB_KIND_TEMPORAL_UNET) return layout_t3d(p, H, W);      // fp32 or UKBB_PREC_BF16_3D (the same ops on 2-byte maps), no split range, no knobs
     const Knobs k = read_knobs();
     std::vector<int> level_out(a.n_level), lh(a.n_level), lw(a.n_level), sqg_out(a.n_level, -1);
     int rc = layout_encoder(p, k, H, W, level_out, lh, lw, sqg_out);
@@ -840,7 +843,7 @@ bool plan_cine(const CineUnits &u, int F, int time_step, uint64_t budget, CinePl
     pl = CinePlan();
     pl.Wn = Wn;
     if (u.kind == UKBB_KIND_TEMPORAL_UNET) {
-        const uint64_t per_window = (uint64_t)(u.act_frame + u.HW * u.n_class) * 4 * T, tables = cine_table_bytes(F, T, Wn);
+        const uint64_t per_window = (uint64_t)(u.act_frame * u.esz + u.HW * u.n_class * 4) * T, tables = cine_table_bytes(F, T, Wn);
         pl.min_bytes = per_window + tables;
         int Wc;
         if (!budget) Wc = std::max(1, (int)std::min<double>(Wn, T3D_CHUNK_BYTES / (double)per_window));
@@ -870,6 +873,7 @@ CineUnits cine_units_from(const PlanLayout &L, const ukbb_fcn_arch &a, int H, in
     CineUnits u;
     u.kind = a.kind; u.T = a.fc; u.n_class = a.n_class; u.HW = (size_t)H * W;
     for (const ActSpec &s : L.acts) u.act_frame += s.per_image;
+    if (a.kind == UKBB_KIND_TEMPORAL_UNET) u.esz = L.mode.bfio() ? 2 : 4;       // UKBB_PREC_BF16_3D: the workspace holds what it stores (plan.h act_alloc_esz)
     if (a.kind != UKBB_KIND_UNET_LSTM) return u;
     const bool wsf = L.mode.bfio() && !L.lstm_bf_wino;       // the direct-conv bf16 ConvLSTM (kernels_ws.hip); else the F(2x4) kernel's regions
     u.esz = L.mode.bfio() ? 2 : 4;

@@ -42,8 +42,8 @@ struct Op {                    // one kernel launch of the plan
 struct ActSpec { std::string name; size_t per_image; int channels; int esz = 4; };   // per_image: elements per image; channels 0: not a channel map;
                                                                                        // esz: bytes of a stored element (2: bf16)
 // Bytes the workspace holds per element of a map.  The U-Net kinds allocate every map as floats in either precision (CineUnits::act_frame
-// and the recorded footprints count that); an FCN plan allocates what it stores.
-inline size_t act_alloc_esz(const ukbb_fcn_arch &a, const ActSpec &s) { return a.kind == UKBB_KIND_FCN ? (size_t)s.esz : 4; }
+// and the recorded footprints count that); an FCN plan and a Temporal-UNet plan (fp32: 4, UKBB_PREC_BF16_3D: 2) allocate what they store.
+inline size_t act_alloc_esz(const ukbb_fcn_arch &a, const ActSpec &s) { return a.kind == UKBB_KIND_FCN || a.kind == UKBB_KIND_TEMPORAL_UNET ? (size_t)s.esz : 4; }
 
 // What a precision code means for a plan of one architecture.  Storage: bf16 operands AND every activation between layers bf16 in HBM
 // (stores_bf16 tilings; an FCN plan: the encoder maps, G_l stays fp32; a UNet-LSTM keeps gx and the hidden maps in bf16 as well)
@@ -81,8 +81,8 @@ int layout_plan(const ukbb_fcn_arch &a, int precision, int H, int W, int n_hint,
 struct CineUnits {
     int kind = 0, T = 0, n_class = 0;
     size_t HW = 0;
-    size_t act_frame = 0;        // the plan's activation workspace, floats per frame (U-Net: allocated as floats in either precision)
-    size_t esz = 4;              // UNet-LSTM: bytes per stored gx / hidden element
+    size_t act_frame = 0;        // the plan's activation workspace, elements per frame (U-Net: allocated as floats in either precision)
+    size_t esz = 4;              // UNet-LSTM: bytes per stored gx / hidden element; Temporal-UNet: bytes per activation element (2: UKBB_PREC_BF16_3D)
     size_t gx_frame = 0;         // UNet-LSTM: gx elements per frame and direction (tile-padded: wino24_lstm_gx_floats / lstm_ws_gx_elems)
     size_t c_item = 0;           // UNet-LSTM: cell-state floats per frame (c1, per direction) or window (c) (tile-padded likewise)
     size_t h_item = 0;           // UNet-LSTM: hidden elements per frame or window, direction and step (HW * 16)

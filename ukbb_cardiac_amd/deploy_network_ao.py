@@ -7,7 +7,7 @@ Command line as in ``demo_pipeline.py:116-117``.  Implemented: ``--model UNet``
 mode, the reference's default ``--model UNet-LSTM`` (U-Net features +
 bidirectional ConvLSTM over circular 9-frame windows with weighted tiling,
 ``:129-183``) and ``--model Temporal-UNet`` (3-D convolutions over the same
-windows, ``network_ao.py:67-114``; fp32 only) in sequence mode, any ``--time_step``.
+windows, ``network_ao.py:67-114``; fp32, or ``--precision bf16_3d``) in sequence mode, any ``--time_step``.
 
 Output: ``seg_ao.nii.gz`` int32 with the input's affine and pixdim (``:189-196``).
 """
@@ -49,10 +49,12 @@ def define_flags():
                       'write finished segmentations behind it; 0 = strictly sequential subjects as in the reference.')
     fs.DEFINE_boolean('device_preproc', True, 'Sequences: z-score, padding, transposes and the argmax on the GPU '
                       '(float32, uint8, int16 and uint16 cines; bit-identical to the host path; --nodevice_preproc restores it).')
-    fs.DEFINE_enum('precision', 'fp32', ['fp32', 'bf16'], 'Arithmetic of the U-Net convolutions: fp32 MFMA (default) or bf16 MFMA operands with fp32 '
+    fs.DEFINE_enum('precision', 'fp32', ['fp32', 'bf16', 'bf16_3d'], 'Arithmetic of the U-Net convolutions: fp32 MFMA (default) or bf16 MFMA operands with fp32 '
                    'accumulation (UKBB_PREC_BF16, include/ukbb_fcn.h; --model UNet: bf16 activations in HBM too, 2.8x the fp32 rate, '
                    'Dice 0.99 against fp32; BASELINE config 5.  Default UNet-LSTM model: the same U-Net plan, ConvLSTM on the bf16 matrix '
-                   'instruction with bf16 hidden maps and fp32 cell state, 2.3x the fp32 rate, Dice >= 0.98 against fp32).')
+                   'instruction with bf16 hidden maps and fp32 cell state, 2.3x the fp32 rate, Dice >= 0.98 against fp32), or bf16_3d '
+                   '(--model Temporal-UNet only, UKBB_PREC_BF16_3D: its 3-D convolutions on the bf16 matrix instruction, every 3-D map '
+                   'bf16 in HBM, logits and softmax fp32; bf16 itself stays refused on that model).')
     fs.DEFINE_float('cine_scratch_gb', 0.0, 'UNet-LSTM and Temporal-UNet: device memory (GB, 1e9 bytes) the engine may hold for the per-cine scratch of the '
                     'windowed forward (hidden maps, gate pre-activations, cell state, network activations).  The windows of a cine then run in '
                     'chunks that fit, with the same bits as the unchunked run; a cine of any length fits a few GB, at the price of recomputing '
@@ -246,8 +248,11 @@ def main(argv=None):
         sys.exit('FATAL Flags parsing error: %s\n%s' % (e, fs.usage()))
     if 'CUDA_VISIBLE_DEVICES' in os.environ and 'HIP_VISIBLE_DEVICES' not in os.environ:
         os.environ['HIP_VISIBLE_DEVICES'] = os.environ['CUDA_VISIBLE_DEVICES']
-    if FLAGS.model == 'Temporal-UNet' and FLAGS.precision != 'fp32':
-        sys.exit('Error: --model Temporal-UNet runs in fp32 only (no bf16 plan for its 3-D convolutions).')
+    if FLAGS.model == 'Temporal-UNet' and FLAGS.precision not in ('fp32', 'bf16_3d'):
+        sys.exit('Error: --model Temporal-UNet runs in fp32 only (no bf16 plan for its 3-D convolutions) under --precision %s; '
+                 'its bf16 mode is --precision bf16_3d.' % FLAGS.precision)
+    if FLAGS.model != 'Temporal-UNet' and FLAGS.precision == 'bf16_3d':
+        sys.exit('Error: --precision bf16_3d is the bf16 mode of --model Temporal-UNet (3-D convolutions); --model %s takes --precision bf16.' % FLAGS.model)
     from ukbb_cardiac_amd.shard import apply_cpu_set_from_env
     apply_cpu_set_from_env()                             # shard.launch's per-worker CPU set, before the first GPU call starts threads
     from ukbb_cardiac_amd.arch import KIND_TEMPORAL_UNET, KIND_UNET_LSTM

@@ -152,8 +152,10 @@ class Engine:
 
     def set_precision(self, precision: str):
         """'fp32' (default), 'bf16' (bf16 MFMA inputs, fp32 accumulate; BASELINE config 5), 'f32x3' (fp32 results from three
-        bf16 pieces per operand on the dense matrix cores; FCN head so far; include/ukbb_fcn.h UKBB_PREC_F32X3) or 'bf16_store'
-        (FCN models only: bf16 operands and bf16 encoder maps in HBM, squeeze and head in fp32; UKBB_PREC_BF16_STORE)."""
+        bf16 pieces per operand on the dense matrix cores; FCN head so far; include/ukbb_fcn.h UKBB_PREC_F32X3), 'bf16_store'
+        (FCN models only: bf16 operands and bf16 encoder maps in HBM, squeeze and head in fp32; UKBB_PREC_BF16_STORE) or 'bf16_3d'
+        (Temporal-UNet only: its 3-D convolutions on the bf16 matrix instruction, every 3-D map bf16 in HBM, the first layer's
+        arithmetic, logits, prob and pred fp32; UKBB_PREC_BF16_3D.  'bf16' and 'bf16_store' stay refused on that model)."""
         _lib.check(_lib.lib.ukbb_fcn_set_precision(self._h, _PLAN_PREC[precision]), 'ukbb_fcn_set_precision')
 
     def set_scratch_budget(self, nbytes: int):
@@ -239,7 +241,7 @@ class Engine:
         return buf
 
 
-_PREC = {'fp32': 0, 'bf16': 1}              # what the cine queries take: any other name is a KeyError
+_PREC = {'fp32': 0, 'bf16': 1, 'bf16_3d': 4}   # what the cine queries take: any other name is a KeyError
 
 
 def cine_scratch_bytes(arch: ModelArch, precision: str, n_frames: int, height: int, width: int, time_step: int = 1, budget: int = 0) -> int:
@@ -261,7 +263,7 @@ def cine_chunk_windows(arch: ModelArch, precision: str, n_frames: int, height: i
     return int(_lib.lib.ukbb_fcn_cine_chunk_windows(C.byref(a), _PREC[precision], int(n_frames), int(height), int(width), int(time_step), int(budget)))
 
 
-_PLAN_PREC = {'fp32': 0, 'bf16': 1, 'f32x3': 2, 'bf16_store': 3}       # the UKBB_PREC_* codes of include/ukbb_fcn.h (set_precision, plan_layout)
+_PLAN_PREC = {'fp32': 0, 'bf16': 1, 'f32x3': 2, 'bf16_store': 3, 'bf16_3d': 4}       # the UKBB_PREC_* codes of include/ukbb_fcn.h (set_precision, plan_layout)
 _OP_FIELDS = ('cfg', 'H', 'W', 'Ho', 'Wo', 'stride', 'in0', 'in1', 'out')
 
 
