@@ -146,6 +146,22 @@ void ukbb_fcn_destroy(ukbb_fcn_handle *h);
  * scratch take 2 bytes per activation element.  UKBB_PREC_BF16 and UKBB_PREC_BF16_STORE stay refused on this kind, and every other kind
  * returns UKBB_EARCH for this code.  Opt-in; each launch is graded in tests/test_temporal_bf16_launches_gpu.py. */
 #define UKBB_PREC_BF16_3D 4
+/* UKBB_PREC_BF16_FULL (UKBB_KIND_FCN only; additive to ABI 11, as codes 3 and 4 are): UKBB_PREC_BF16_STORE with the head's three matrix products
+ * on v_mfma_f32_32x32x16_bf16 as well (kernels_head.hip, the BM instance of fcn_head_pc_kernel: 1 + 4 + 8 matrix instructions per 32-pixel
+ * block instead of 8 + 32 + 64 fp32 ones).  The encoder and the squeeze launches are those of UKBB_PREC_BF16_STORE, launch for launch and bit
+ * for bit.  The head, per pixel, from the stored bf16 conv0 (16 channels, used as stored) and the handed tile T = b_o0 + sum_l up_l(G_l), which
+ * the producer waves compute in fp32 from the fp32 G_1..G_4 exactly as in every other mode:
+ *     S = relu(b_s0 + bf16(W_s0) . conv0)              K = 16, fp32 accumulation
+ *     P = relu(T + bf16(W_o0[:, 0:32]) . bf16(S))      T enters as the fp32 accumulator
+ *     Q = relu(b_o1 + bf16(W_o1) . bf16(P))
+ *     logits = W_lg . Q + b_lg, softmax, argmax        the fp32 vector code of every other mode
+ * Where it rounds: the three folded weight matrices to bf16 (RNE) once, on the host, when they are packed (pack_head_bf16); S and P once (RNE)
+ * in registers, after bias + ReLU.  What stays fp32 / int32: the biases, T, every accumulator, the G_l maps, W_lg, logits, prob and pred -- so
+ * every table and file path works unchanged.  UKBB_HEAD_DIRECT_GATHER and UKBB_HEAD_INLINE_TAIL do not apply to this mode (one form: separable
+ * gather, in-stage tail).  On every other kind set_precision returns UKBB_EARCH for this code.  Not bit-compatible with the other modes; judged by
+ * Dice against the fp32 labels (>= 0.98 per class, tests/test_fcn_bf16_full_gpu.py) and graded as a unit against a float64 model of the lines
+ * above in tests/test_fcn_bf16_full_launches_gpu.py.  Opt-in; the default and the benchmark's headline stay UKBB_PREC_FP32. */
+#define UKBB_PREC_BF16_FULL 5
 int ukbb_fcn_set_precision(ukbb_fcn_handle *h, int precision);
 
 /* Pre-size the activation workspace for batches up to n x h x w (optional;

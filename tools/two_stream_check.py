@@ -3,7 +3,7 @@ Two engines of one model on two streams, four batches in flight on each, every l
 r06: this is the check that exposed (and now guards) the wide-store hazard of kernels_ws.hip -- the bf16-storage U-Net failed 85-98 % of
 its forwards here until its 16-byte buffer stores were padded (profiles/r06_notes.md section 10).  A 'UNet-LSTM...' model runs whole cines
 (N = frames) through ukbb_fcn_forward_cine.
-    PREC=fp32|bf16|f32x3|bf16_store python tools/two_stream_check.py [model] [N H W] [iterations]        GPU box; prints OK / FAILED."""
+    PREC=fp32|bf16|f32x3|bf16_store|bf16_full python tools/two_stream_check.py [model] [N H W] [iterations]        GPU box; prints OK / FAILED."""
 import os
 import sys
 

@@ -143,6 +143,7 @@ struct Params {
     const float *conv0_w, *conv0_b, *conv0_1_b, *up0_0_b, *up0_1_b, *logits_w, *logits_b;
     const float *stem_wA0, *stem_wA1, *tail_wA0, *tail_wA1;
     const float *head_w_s0, *head_b_s0, *head_w_o0, *head_b_o0, *head_w_o1, *head_b_o1, *head_w_o1x3, *head_w_o0x3, *head_w_lg;
+    const float *head_w_s0bf, *head_w_o0bf, *head_w_o1bf;         // UKBB_PREC_BF16_FULL: pack_head_bf16 of same_dim0, out0's level-0 slice, out1
     struct { const float *wx, *bx, *wh[2]; } lstm[2];             // ConvLSTM filters per form ([0] fp32 Winograd, [1] bf16 direct) and direction
     const float *lstm_wxh[2];                                     // ... un-hoisted bf16 time steps, per direction
     const float *lstm_out_w, *lstm_out_b;
@@ -443,6 +444,7 @@ int bind_op(ukbb_fcn_handle *h, BoundOp &op, const PlanMode &mode) {
             need(P.head_w_s0, "head/w_s0"); need(P.head_b_s0, "same_dim0/bias"); need(P.head_w_o0, "head/w_o0"); need(P.head_b_o0, "out0/bias");
             need(P.head_w_o1, "head/w_o1"); need(P.head_b_o1, "out1/bias"); need(P.head_w_o1x3, "head/w_o1x3"); need(P.head_w_o0x3, "head/w_o0x3");
             need(P.head_w_lg, "head/w_lg"); need(P.logits_b, "logits/bias");
+            if (mode.head_bf16) { need(P.head_w_s0bf, "head/w_s0bf"); need(P.head_w_o0bf, "head/w_o0bf"); need(P.head_w_o1bf, "head/w_o1bf"); }
             break;
         case OP_STEM:
             rc = ensure_packed_stem(h);
@@ -658,6 +660,7 @@ int launch_op(ukbb_fcn_handle *h, const BoundOp &op, const PlanIo &io, int n0, i
             ha.logits = io.logits; ha.prob = io.prob; ha.pred = io.pred;
             ha.N = n; ha.H = op.H; ha.W = op.W; ha.n_class = a.n_class;
             ha.x3 = h->plan.mode.head_x3; ha.conv0_bf16 = bfio;
+            ha.mm_bf16 = h->plan.mode.head_bf16; ha.w_s0bf = P.head_w_s0bf; ha.w_o0bf = P.head_w_o0bf; ha.w_o1bf = P.head_w_o1bf;
             e = launch_head(ha, s);
             break;
         }
@@ -962,11 +965,19 @@ int ukbb_fcn_debug_plan_layout(const ukbb_fcn_arch *arch, int precision, int n, 
         snprintf(line, sizeof line, "act %s %zu %d %zu\n", s.name.empty() ? "-" : s.name.c_str(), s.per_image, s.channels, act_alloc_esz(*arch, s));
         out += line;
     }
-    snprintf(line, sizeof line, "plan split %d %d bfio %d feat_buf %d lstm %d %d %d %d\n", L.split_first, L.split_last, (int)L.mode.bfio(), L.feat_buf,
-             (int)L.needs_lstm, L.lstm_tile_cols, (int)L.lstm_bf_wino, (int)L.lstm_bf_hoist);
+    snprintf(line, sizeof line, "plan split %d %d bfio %d feat_buf %d lstm %d %d %d %d head_bf16 %d\n", L.split_first, L.split_last, (int)L.mode.bfio(), L.feat_buf,
+             (int)L.needs_lstm, L.lstm_tile_cols, (int)L.lstm_bf_wino, (int)L.lstm_bf_hoist, (int)L.mode.head_bf16);
     out += line;
     if (cap) { const size_t m = std::min(out.size(), cap - 1); memcpy(buf, out.data(), m); buf[m] = 0; }
     return (int)out.size();
+}
+
+// debugging / testing aid, not in the public header: pack_head_bf16 (kernels_head.hip) on a host matrix, host arithmetic only.  dst takes
+// (n_out / 32) * (k_in / 16) * 256 dwords.
+int ukbb_fcn_debug_pack_head_bf16(const float *w, int k_in, int n_out, int acc_k, uint32_t *dst) {
+    if (!w || !dst || (k_in != 16 && k_in != 32 && k_in != 64) || (n_out != 32 && n_out != 64) || (acc_k && k_in < 32)) { set_error("debug_pack_head_bf16: bad argument"); return UKBB_EINVAL; }
+    pack_head_bf16(w, k_in, n_out, acc_k, reinterpret_cast<float *>(dst));
+    return UKBB_OK;
 }
 
 const char *ukbb_fcn_last_error(void) { return g_err.c_str(); }
@@ -1085,6 +1096,13 @@ ukbb_fcn_handle *ukbb_fcn_create(const ukbb_fcn_arch *arch, const float *weights
             v.assign(2 * 4 * 64 * 4, 0.f);       pack_rowmap_32x64(o0.w.data() + (size_t)32 * l * 64, 64, v.data());
             if (upload(h.get(), "sqg" + std::to_string(l) + "/w_g", v)) return nullptr;
         }
+        // UKBB_PREC_BF16_FULL: the head's three matrices as one bf16 piece each (behind every record that existed before the mode)
+        v.assign(1 * 1 * 64 * 4, 0.f);          pack_head_bf16(s0.w.data(), 16, 32, 0, v.data());
+        if (upload(h.get(), "head/w_s0bf", v)) return nullptr;
+        v.assign(2 * 2 * 64 * 4, 0.f);          pack_head_bf16(o0.w.data(), 32, 64, 1, v.data());
+        if (upload(h.get(), "head/w_o0bf", v)) return nullptr;
+        v.assign(2 * 4 * 64 * 4, 0.f);          pack_head_bf16(o1.w.data(), 64, 64, 1, v.data());
+        if (upload(h.get(), "head/w_o1bf", v)) return nullptr;
     } else if (arch->kind == UKBB_KIND_UNET || arch->kind == UKBB_KIND_TEMPORAL_UNET) {
         const HostLayer &lg = h->layers[h->layer_index.at("logits")];
         if (upload(h.get(), "logits/w", lg.w)) return nullptr;

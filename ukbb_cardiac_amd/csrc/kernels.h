@@ -347,6 +347,11 @@ struct HeadArgs {
     int diag;                // diagnostic builds only (-DUKBB_DIAG, env UKBB_HEAD_DIAG): ablation bits of fcn_head_pc_kernel
     int conv0_bf16;          // input format of conv0.  0: fp32 [N,H,W,16].  1 (UKBB_PREC_BF16_STORE): bf16 [N][1][H][W][16], decoded to fp32 on the
                              // way in (exact); not combined with x3
+    int mm_bf16;             // UKBB_PREC_BF16_FULL: same_dim0, out0's level-0 slice and out1 on v_mfma_f32_32x32x16_bf16, one bf16 piece per operand
+                             // (needs conv0_bf16 and the three blocks below; not combined with x3)
+    const float *w_s0bf;     // pack_head_bf16(same_dim0, 16, 32, natural k): 256 dwords
+    const float *w_o0bf;     // pack_head_bf16(out0 rows 0..31, 32, 64, accumulator k): 1024 dwords
+    const float *w_o1bf;     // pack_head_bf16(out1, 64, 64, accumulator k): 2048 dwords
 };
 hipError_t launch_head(const HeadArgs &a, hipStream_t s);
 int head_tail_form();      // ukbb_fcn_head_tail_form()
@@ -354,6 +359,9 @@ void pack_sq(const float *w /*[cin][32] folded*/, int cin, float *dst /*cin*32*/
 void pack_rowmap_32x64(const float *w /*32 rows x 64 cols*/, int ld, float *dst /*2*4*64*4*/);
 void pack_head_lg(const float *w /*[64][n_class]*/, int n_class, float *dst /*2*n_class*32*/);
 void pack_head_x3(const float *w /*[k_in][64 out]*/, int k_in /*32 | 64*/, float *dst /*3*2*(k_in/16)*64*4 dwords*/);
+// UKBB_PREC_BF16_FULL: W rounded to bf16 (RNE) once, as A fragments of mfma_bf16.  acc_k 0: k in the order of the stored conv0 block (same_dim0);
+// 1: k in the order an accumulator tile's registers supply it (out0, out1)
+void pack_head_bf16(const float *w /*[k_in][n_out]*/, int k_in /*16 | 32 | 64*/, int n_out /*32 | 64*/, int acc_k, float *dst /*(n_out/32)*(k_in/16)*64*4 dwords*/);
 
 // ---------------------------------------------------------------------------
 // U-Net pieces (network_ao.py:48-63)

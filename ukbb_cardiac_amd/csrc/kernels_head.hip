@@ -426,12 +426,13 @@ constexpr int PX_WAVE = 8 * 64 * 4;                    // floats of one handed-o
 // LDS map of fcn_head_pc_kernel (floats)
 constexpr int L_GW = 0;                                // [2][GPIX][GSTRIDE]  G windows, double buffered per tile
 constexpr int L_PX = L_GW + 2 * GPIX * GSTRIDE;        // [4][PX_WAVE]        hand-over tiles (single buffered)
-// Weight part of the map: fp32 fragments, or (X3) out0's level-0 slice and out1 as three bf16 pieces per weight
-template <bool X3> struct HeadLds {
-    static constexpr int WS0 = L_PX + 4 * PX_WAVE;             // pack_sq(same_dim0)                                   512
-    static constexpr int WO0 = WS0 + 512;                      // pack_rowmap(out0 rows 0..31) 2048 | pack_head_x3(.., 32) 3072 dwords
-    static constexpr int WO1 = WO0 + (X3 ? 3072 : 2048);       // pack_rowmap(out1) x2         4096 | pack_head_x3(.., 64) 6144 dwords
-    static constexpr int BS0 = WO1 + (X3 ? 6144 : 4096);       // 32
+// Weight part of the map: fp32 fragments, or (X3) out0's level-0 slice and out1 as three bf16 pieces per weight, or (BM, UKBB_PREC_BF16_FULL)
+// the three matrices as one bf16 piece each (pack_head_bf16)
+template <bool X3, bool BM = false> struct HeadLds {
+    static constexpr int WS0 = L_PX + 4 * PX_WAVE;             // pack_sq(same_dim0)                                   512 | BM 256 dwords
+    static constexpr int WO0 = WS0 + (BM ? 256 : 512);         // pack_rowmap(out0 rows 0..31) 2048 | pack_head_x3(.., 32) 3072 dwords | BM 1024
+    static constexpr int WO1 = WO0 + (BM ? 1024 : X3 ? 3072 : 2048);   // pack_rowmap(out1) x2  4096 | pack_head_x3(.., 64) 6144 dwords | BM 2048
+    static constexpr int BS0 = WO1 + (BM ? 2048 : X3 ? 6144 : 4096);   // 32
     static constexpr int BO0 = BS0 + 32;                       // 64
     static constexpr int BO1 = BO0 + 64;                       // 64
     static constexpr int WLG = BO1 + 64;                       // [2][NCLS][32] <= 384
@@ -440,6 +441,8 @@ template <bool X3> struct HeadLds {
 };
 constexpr int HEADPC_LDS_FLOATS = HeadLds<false>::FLOATS;
 constexpr int HEADPC_X3_LDS_FLOATS = HeadLds<true>::FLOATS;
+constexpr int HEADPC_BM_LDS_FLOATS = HeadLds<false, true>::FLOATS;
+static_assert(HEADPC_BM_LDS_FLOATS < HEADPC_LDS_FLOATS, "the bf16 head's weights take less LDS than the fp32 fragments");
 static_assert(HEADPC_X3_LDS_FLOATS * 4 <= 160 * 1024, "head kernel LDS");
 
 // An LDS pointer the optimiser cannot see through: reads at compile-time distances from it become one base register plus the
@@ -751,12 +754,19 @@ __device__ __forceinline__ void head_consumer_deferred(const HeadArgs &a, float 
 // DG: the r02-r07 direct 2-D gather (UKBB_HEAD_DIRECT_GATHER=1, A/B); otherwise the separable one
 // IT: the consumers finish a block's logits inside its own stage (r01-r08; UKBB_HEAD_INLINE_TAIL=1, A/B).  The fp32 separable instance
 // defers them instead (r11, DESIGN.md section 4 "Deferred tail"); the X3 and DG instances exist with IT = true only.
-// BF: conv0 is bf16 [N][1][H][W][16] (HeadArgs::conv0_bf16, UKBB_PREC_BF16_STORE), widened to fp32 on the way in; the fp32 instances only.
-template <int NCLS, bool X3 = false, bool DG = false, bool IT = true, bool BF = false>
+// BF: conv0 is bf16 [N][1][H][W][16] (HeadArgs::conv0_bf16, UKBB_PREC_BF16_STORE), widened to fp32 on the way in; the fp32 instances, and BM (below), which takes it as stored.
+// BM: UKBB_PREC_BF16_FULL (HeadArgs::mm_bf16, include/ukbb_fcn.h).  The BF instance with same_dim0, out0's level-0 slice and out1 on
+// v_mfma_f32_32x32x16_bf16, one bf16 piece per operand: 1 + 4 + 8 MFMAs per block instead of 8 + 32 + 64.  The stored conv0 half-block a lane
+// loads (channels 8 g .. 8 g + 7 of pixel p) IS the B fragment of same_dim0, so nothing is widened or exchanged; S and P are rounded once (RNE)
+// in registers as X3 rounds its high piece, and their registers are the next product's B fragments in the k order pack_head_bf16 gives the
+// weights.  The handed tile enters out0 as the fp32 accumulator; biases, accumulators and everything behind out1's ReLU are the fp32 code of the
+// in-stage form.  Separable gather and in-stage tail only: 13 MFMAs leave nothing to defer a tail under, and the two A/B knobs do not apply.
+template <int NCLS, bool X3 = false, bool DG = false, bool IT = true, bool BF = false, bool BM = false>
 __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
     static_assert(!(X3 && BF), "bf16 conv0 is not combined with the f32x3 head");
+    static_assert(!BM || (BF && !DG && IT), "the bf16 head reads the bf16 conv0 and exists in the separable, in-stage form only");
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    using LM = HeadLds<X3>;
+    using LM = HeadLds<X3, BM>;
     constexpr int L_WS0 = LM::WS0, L_WO0 = LM::WO0, L_WO1 = LM::WO1, L_BS0 = LM::BS0, L_BO0 = LM::BO0, L_BO1 = LM::BO1, L_WLG = LM::WLG, L_BLG = LM::BLG;
     float *gw = lds + L_GW;
     float *px = lds + L_PX;
@@ -773,9 +783,12 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
         auto copy = [&](int dst, const float *src, int nfloat) {
             for (int i = t; i < nfloat; i += 768) lds[dst + i] = src[i];
         };
+        if constexpr (BM) { copy(L_WS0, a.w_s0bf, 256); copy(L_WO0, a.w_o0bf, 1024); copy(L_WO1, a.w_o1bf, 2048); }
+        else {
         copy(L_WS0, a.w_s0, 512);
         if constexpr (X3) { copy(L_WO0, a.w_o0x3, 3072); copy(L_WO1, a.w_o1x3, 6144); }
         else              { copy(L_WO0, a.w_o0, 2048);   copy(L_WO1, a.w_o1, 4096); }
+        }
         copy(L_BS0, a.b_s0, 32);  copy(L_BO0, a.b_o0, 64);   copy(L_BO1, a.b_o1, 64);
         copy(L_WLG, a.w_lg, 2 * NCLS * 32); copy(L_BLG, a.b_lg, NCLS);
     }
@@ -1059,11 +1072,22 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
             UKBB_HS(hs_r, hs_p)
             __syncthreads();                            // barrier B_s: px may be overwritten
             UKBB_HS(hs_b, hs_p)
-            if constexpr (BF) bf16_block_to_k(__builtin_bit_cast(u32x4, xv0), x0, x1);
+            if constexpr (BF && !BM) bf16_block_to_k(__builtin_bit_cast(u32x4, xv0), x0, x1);
             if (s + 1 < nstages) fetch_conv0(pixel_of(s + 1));   // features of the next block: a whole stage to arrive
             // ---- same_dim0 ----
             f32x16 S = bias_tile_lds(lds + L_BS0, g);
-            {
+            // BM: A fragment f of a block lies at [f][lane] float4; element e of the B fragment built from registers 8 c .. 8 c + 7 of a tile is
+            // its row rowmap(8 c + e, g), the k order of pack_head_bf16(.., acc_k = 1)
+            [[maybe_unused]] auto frag = [&](const float *w, int f) { return __builtin_bit_cast(u32x4, ld4(w + f * 256 + lane * 4)); };
+            [[maybe_unused]] auto tile_b = [&](const f32x16 &X, int c) {
+                u32x4 b;
+#pragma unroll
+                for (int d = 0; d < 4; ++d) b[d] = pack_bf16x2(X[8 * c + 2 * d], X[8 * c + 2 * d + 1]);
+                return b;
+            };
+            if constexpr (BM) {                         // K = 16: the stored half-block as it was loaded is the B fragment
+                S = mfma_bf16(frag(w_s0, 0), __builtin_bit_cast(u32x4, x0), S);
+            } else {
                 const f32x4 wv0 = ld4(w_s0 + lane * 4), wv1 = ld4(w_s0 + (64 + lane) * 4);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) S = MFMA32(wv0[i], x0[i], S);
@@ -1076,7 +1100,11 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
             if (a.diag & 2) { relu16(P0); relu16(P1); if (a.pred) a.pred[q] = (int)P0[0]; continue; }   // ablation: no out0/out1/logits
 #endif
             // ---- out0: handed tile (bias + upsampled levels 1..4) + W0_0 * S ----
-            if constexpr (X3) {                         // out0's level-0 slice from bf16 pieces: K = 32 -> two chunks of 16
+            if constexpr (BM) {                         // bf16(W) . bf16(S) onto the handed fp32 tile: fragment 2 cb + kc
+                const u32x4 s0 = tile_b(S, 0), s1 = tile_b(S, 1);
+                P0 = mfma_bf16(frag(w_o0, 0), s0, P0); P1 = mfma_bf16(frag(w_o0, 2), s0, P1);
+                P0 = mfma_bf16(frag(w_o0, 1), s1, P0); P1 = mfma_bf16(frag(w_o0, 3), s1, P1);
+            } else if constexpr (X3) {                  // out0's level-0 slice from bf16 pieces: K = 32 -> two chunks of 16
                 u32x4 sh[2], sm[2], sl[2];
 #pragma unroll
                 for (int kc = 0; kc < 2; ++kc)
@@ -1106,7 +1134,13 @@ __global__ __launch_bounds__(768) void fcn_head_pc_kernel(const HeadArgs a) {
             UKBB_HS(hs_j[1], hs_p)
             // ---- out1 ----
             f32x16 Q0 = bias_tile_lds(lds + L_BO1, g), Q1 = bias_tile_lds(lds + L_BO1 + 32, g);
-            if constexpr (X3) {
+            if constexpr (BM) {                         // K = 64: chunks 0, 1 are P0's registers, 2, 3 are P1's; fragment 4 cb + kc
+                const u32x4 b0 = tile_b(P0, 0), b1 = tile_b(P0, 1), b2 = tile_b(P1, 0), b3 = tile_b(P1, 1);
+                Q0 = mfma_bf16(frag(w_o1, 0), b0, Q0); Q1 = mfma_bf16(frag(w_o1, 4), b0, Q1);
+                Q0 = mfma_bf16(frag(w_o1, 1), b1, Q0); Q1 = mfma_bf16(frag(w_o1, 5), b1, Q1);
+                Q0 = mfma_bf16(frag(w_o1, 2), b2, Q0); Q1 = mfma_bf16(frag(w_o1, 6), b2, Q1);
+                Q0 = mfma_bf16(frag(w_o1, 3), b3, Q0); Q1 = mfma_bf16(frag(w_o1, 7), b3, Q1);
+            } else if constexpr (X3) {
                 // B operands: lane (pixel p, half g) supplies k slots e = 0..7 of chunk kc = registers 8 (kc & 1) + e of P0 (kc < 2) / P1.
                 // The split of chunk kc+1 (~60 vector instructions) is interleaved with the 12 MFMAs of chunk kc: a bf16 MFMA leaves
                 // about six vector-issue slots free inside the issuing wave (tools/mfma_bf16_coissue.hip).
@@ -1213,6 +1247,11 @@ static hipError_t launch_head_pc_nc(const HeadArgs &a, dim3 grid, hipStream_t s)
 #define UKBB_HEAD_GO(X3, DG, IT, BYTES) launch_lds<fcn_head_pc_kernel<NC, X3, DG, IT>>(grid, dim3(768), BYTES, s, a)
 #define UKBB_HEAD_GO_BF(DG, IT, BYTES) launch_lds<fcn_head_pc_kernel<NC, false, DG, IT, true>>(grid, dim3(768), BYTES, s, a)
     if (a.x3 && a.conv0_bf16) return hipErrorInvalidValue;      // no such instance (include/ukbb_fcn.h: the modes are not combined)
+    if (a.mm_bf16) {                                    // UKBB_PREC_BF16_FULL: one form (separable gather, in-stage tail); the two knobs do not apply
+        if (a.x3 || !a.conv0_bf16 || !a.w_s0bf || !a.w_o0bf || !a.w_o1bf) return hipErrorInvalidValue;
+        g_head_tail_form.store(1, std::memory_order_relaxed);
+        return launch_lds<fcn_head_pc_kernel<NC, false, false, true, true, true>>(grid, dim3(768), HEADPC_BM_LDS_FLOATS * 4, s, a);
+    }
     if (a.x3 && a.w_o1x3 && a.w_o0x3) {                 // UKBB_PREC_F32X3; its tail stays in the stage (profiles/r11_notes.md)
         constexpr int ldsx = HEADPC_X3_LDS_FLOATS * 4;
         g_head_tail_form.store(1, std::memory_order_relaxed);
@@ -1330,6 +1369,27 @@ void pack_head_x3(const float *w, int k_in, float *dst) {
                         }
                         o[((((t * 2 + cb) * nkc + kc) * 64 + lane) * 4) + d] = (unsigned)piece[0] | ((unsigned)piece[1] << 16);
                     }
+}
+
+void pack_head_bf16(const float *w, int k_in, int n_out, int acc_k, float *dst) {
+    // W is [k_in rows][n_out], row stride n_out.  dst[cb][kc][lane][d] (dwords), cb < n_out / 32, kc < k_in / 16: the A fragments of mfma_bf16,
+    // lane = (g << 5) | m, cout = 32 cb + m, k slot e = 2 d (+1 in the high half) of chunk kc <-> input row 16 kc + 8 g + e (acc_k 0: the
+    // stored conv0 half-block) or 32 (kc / 2) + rowmap(8 (kc & 1) + e, g) (acc_k 1: the registers of the accumulator tile(s), as pack_head_x3).
+    // Each weight is rounded to bf16 (RNE) once, here.
+    unsigned *o = reinterpret_cast<unsigned *>(dst);
+    const int nkc = k_in / 16;
+    for (int cb = 0; cb < n_out / 32; ++cb)
+        for (int kc = 0; kc < nkc; ++kc)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int d = 0; d < 4; ++d) {
+                    const int g = lane >> 5, m = lane & 31;
+                    unsigned short piece[2];
+                    for (int hh = 0; hh < 2; ++hh) {
+                        const int e = 2 * d + hh, row = acc_k ? 32 * (kc / 2) + rowmap(8 * (kc & 1) + e, g) : 16 * kc + 8 * g + e;
+                        piece[hh] = host_bf16_rne(w[row * n_out + 32 * cb + m]);
+                    }
+                    o[(((cb * nkc + kc) * 64 + lane) * 4) + d] = (unsigned)piece[0] | ((unsigned)piece[1] << 16);
+                }
 }
 
 void pack_head_lg(const float *w, int n_class, float *dst) {

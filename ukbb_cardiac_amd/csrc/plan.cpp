@@ -767,15 +767,18 @@ void layout_split_range(const Planner &p, const Knobs &kn) {
 int plan_mode(const ukbb_fcn_arch &a, int precision, PlanMode &m, const char **why) {
     m = PlanMode();
     *why = "";
-    if (precision != UKBB_PREC_FP32 && precision != UKBB_PREC_BF16 && precision != UKBB_PREC_F32X3 && precision != UKBB_PREC_BF16_STORE && precision != UKBB_PREC_BF16_3D) { *why = "bad precision"; return UKBB_EINVAL; }
+    if (precision != UKBB_PREC_FP32 && precision != UKBB_PREC_BF16 && precision != UKBB_PREC_F32X3 && precision != UKBB_PREC_BF16_STORE && precision != UKBB_PREC_BF16_3D && precision != UKBB_PREC_BF16_FULL) { *why = "bad precision"; return UKBB_EINVAL; }
     if (a.kind == UKBB_KIND_TEMPORAL_UNET && precision == UKBB_PREC_BF16) { *why = "the Temporal-UNet's 3-D convolutions are built for fp32 only (no bf16 plan) under this code; their bf16 mode is UKBB_PREC_BF16_3D ('bf16_3d')"; return UKBB_EARCH; }
     if (a.kind == UKBB_KIND_TEMPORAL_UNET && precision == UKBB_PREC_BF16_STORE) { *why = "UKBB_PREC_BF16_STORE is the FCN's bf16-storage mode; the U-Net kinds already store bf16 under UKBB_PREC_BF16 (the Temporal-UNet: fp32 only under that code, bf16 under UKBB_PREC_BF16_3D, 'bf16_3d')"; return UKBB_EARCH; }
     if (a.kind != UKBB_KIND_FCN && precision == UKBB_PREC_BF16_STORE) { *why = "UKBB_PREC_BF16_STORE is the FCN's bf16-storage mode; the U-Net kinds already store bf16 under UKBB_PREC_BF16"; return UKBB_EARCH; }
+    if (a.kind == UKBB_KIND_TEMPORAL_UNET && precision == UKBB_PREC_BF16_FULL) { *why = "UKBB_PREC_BF16_FULL is the FCN's bf16-storage mode with its head on the bf16 matrix instruction; the Temporal-UNet's bf16 mode is UKBB_PREC_BF16_3D ('bf16_3d')"; return UKBB_EARCH; }
+    if (a.kind != UKBB_KIND_FCN && precision == UKBB_PREC_BF16_FULL) { *why = "UKBB_PREC_BF16_FULL is the FCN's bf16-storage mode with its head on the bf16 matrix instruction; the U-Net kinds have no such head and already store bf16 under UKBB_PREC_BF16"; return UKBB_EARCH; }
     if (a.kind != UKBB_KIND_TEMPORAL_UNET && precision == UKBB_PREC_BF16_3D) { *why = "UKBB_PREC_BF16_3D is the bf16 mode of the Temporal-UNet's 3-D convolutions; the 2-D kinds take UKBB_PREC_BF16 (the FCN also UKBB_PREC_BF16_STORE)"; return UKBB_EARCH; }
     // UKBB_PREC_BF16 means operands only on an FCN handle (pinned by recorded plans and graders) and storage on the U-Net kinds; with
     // UKBB_PREC_BF16_STORE the FCN encoder takes the same bf16-storage kernels (squeeze and head read the bf16 maps and stay fp32)
     if (precision == UKBB_PREC_BF16) m.bf16 = a.kind == UKBB_KIND_FCN ? Bf16Mode::Operands : Bf16Mode::Storage;
     if (precision == UKBB_PREC_BF16_STORE) m.bf16 = Bf16Mode::Storage;
+    if (precision == UKBB_PREC_BF16_FULL) { m.bf16 = Bf16Mode::Storage; m.head_bf16 = true; }      // bf16_store's plan, the head launch on bf16 MFMA
     if (precision == UKBB_PREC_BF16_3D) m.bf16 = Bf16Mode::Storage;       // every 3-D map bf16, channel-blocked (kernels_conv3d_bf16.hip)
     m.head_x3 = precision == UKBB_PREC_F32X3;
     return UKBB_OK;

@@ -51,6 +51,8 @@ enum class Bf16Mode { None, Operands /* fp32 maps in HBM, ConvFamily::Bf16Operan
 struct PlanMode {
     Bf16Mode bf16 = Bf16Mode::None;
     bool head_x3 = false;                     // UKBB_PREC_F32X3: the FCN head's out0 / out1 from three bf16 pieces per operand (its convs are fp32)
+    bool head_bf16 = false;                   // UKBB_PREC_BF16_FULL: the FCN head's same_dim0 / out0 / out1 on the bf16 matrix instruction, one piece per operand
+                                              // (the encoder and the squeeze launches are those of UKBB_PREC_BF16_STORE: bf16 == Storage)
     bool bfio() const { return bf16 == Bf16Mode::Storage; }
 };
 // THE list of precision codes and of the (kind, code) pairs the engine refuses.  UKBB_OK; UKBB_EINVAL for an unknown code; UKBB_EARCH

@@ -62,10 +62,13 @@ def define_flags():
                       'launch (one wave per file; the readers only read).  0 = off: the reader threads inflate.  A file the device path declines '
                       '(scaled / big-endian / float64 voxels, several gzip members, anything its strict decoder or the CRC-32 check refuses) '
                       'takes the host reader as before.  Same output files.')
-    fs.DEFINE_enum('precision', 'fp32', ['fp32', 'f32x3', 'bf16_store'], 'Arithmetic of the matrix products: fp32 MFMA (default), fp32 results from three '
+    fs.DEFINE_enum('precision', 'fp32', ['fp32', 'f32x3', 'bf16_store', 'bf16_full'], 'Arithmetic of the matrix products: fp32 MFMA (default), fp32 results from three '
                    'bf16 pieces per operand (UKBB_PREC_F32X3, include/ukbb_fcn.h; same labels, faster head), or bf16_store: the encoder on bf16 '
                    'matrix instructions with its maps stored as bf16, squeeze and head in fp32 on the stored values (UKBB_PREC_BF16_STORE; labels '
-                   'differ from fp32 next to class borders, Dice >= 0.98 per class on the test phantoms).')
+                   'differ from fp32 next to class borders, Dice >= 0.98 per class on the test phantoms), or bf16_full: bf16_store with the '
+                   'head\'s three matrix products on bf16 matrix instructions too -- their weights rounded to bf16 once when packed, the two '
+                   'hidden activations once in registers; biases, the upsampled G_l sum, accumulators, logits, softmax and labels stay fp32 '
+                   '(UKBB_PREC_BF16_FULL; same Dice bound).')
     fs.DEFINE_enum('label_gzip', 'small', list(nifti.LABEL_GZIP_MODES), 'Deflate of the label volumes: small = run-length tokens + dynamic Huffman '
                    '(typically below the size of zlib level 1, ~20x less CPU), fast = fixed Huffman (2-4x larger files), zlib = as nibabel. Same inflated bytes.')
     fs.DEFINE_boolean('device_label_gzip', False, 'Sequence mode, pipelined loop (--device_preproc with --io_threads > 0, without --device_inflate): '

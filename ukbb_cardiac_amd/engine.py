@@ -153,7 +153,10 @@ class Engine:
     def set_precision(self, precision: str):
         """'fp32' (default), 'bf16' (bf16 MFMA inputs, fp32 accumulate; BASELINE config 5), 'f32x3' (fp32 results from three
         bf16 pieces per operand on the dense matrix cores; FCN head so far; include/ukbb_fcn.h UKBB_PREC_F32X3), 'bf16_store'
-        (FCN models only: bf16 operands and bf16 encoder maps in HBM, squeeze and head in fp32; UKBB_PREC_BF16_STORE) or 'bf16_3d'
+        (FCN models only: bf16 operands and bf16 encoder maps in HBM, squeeze and head in fp32; UKBB_PREC_BF16_STORE), 'bf16_full'
+        (FCN models only: 'bf16_store' with the head's three matrix products on the bf16 matrix instruction as well -- weights rounded
+        once when packed, the two hidden activations once in registers; biases, the G_l maps, accumulators, logits, prob and pred
+        fp32; UKBB_PREC_BF16_FULL) or 'bf16_3d'
         (Temporal-UNet only: its 3-D convolutions on the bf16 matrix instruction, every 3-D map bf16 in HBM, the first layer's
         arithmetic, logits, prob and pred fp32; UKBB_PREC_BF16_3D.  'bf16' and 'bf16_store' stay refused on that model)."""
         _lib.check(_lib.lib.ukbb_fcn_set_precision(self._h, _PLAN_PREC[precision]), 'ukbb_fcn_set_precision')
@@ -263,13 +266,13 @@ def cine_chunk_windows(arch: ModelArch, precision: str, n_frames: int, height: i
     return int(_lib.lib.ukbb_fcn_cine_chunk_windows(C.byref(a), _PREC[precision], int(n_frames), int(height), int(width), int(time_step), int(budget)))
 
 
-_PLAN_PREC = {'fp32': 0, 'bf16': 1, 'f32x3': 2, 'bf16_store': 3, 'bf16_3d': 4}       # the UKBB_PREC_* codes of include/ukbb_fcn.h (set_precision, plan_layout)
+_PLAN_PREC = {'fp32': 0, 'bf16': 1, 'f32x3': 2, 'bf16_store': 3, 'bf16_3d': 4, 'bf16_full': 5}       # the UKBB_PREC_* codes of include/ukbb_fcn.h (set_precision, plan_layout)
 _OP_FIELDS = ('cfg', 'H', 'W', 'Ho', 'Wo', 'stride', 'in0', 'in1', 'out')
 
 
 def plan_layout(arch: ModelArch, precision: str, n: int, h: int, w: int, cus: int = 256) -> dict:
     """The launch plan the engine builds for batches of ``n`` images of ``h`` x ``w`` on a device of ``cus`` compute units, from
-    the host-only planner (no GPU needed): ``{'ops': [dict], 'acts': [dict], 'split': (first, last), 'bfio', 'feat_buf', 'lstm'}``.
+    the host-only planner (no GPU needed): ``{'ops': [dict], 'acts': [dict], 'split': (first, last), 'bfio', 'feat_buf', 'lstm', 'head_bf16'}``.
     An op's ``macs`` / ``mfma_macs`` / ``issued_macs`` are per image, as ``Engine.kernel_macs()`` etc. report them per batch.
     A map of the workspace takes ``per_image * bytes_per_element`` bytes per image.
     Raises UkbbFcnError where ``Engine`` would refuse the combination."""
@@ -298,6 +301,7 @@ def plan_layout(arch: ModelArch, precision: str, n: int, h: int, w: int, cus: in
             v = list(map(int, f[2:4] + f[5:6] + f[7:8] + f[9:13]))
             out.update(split=(v[0], v[1]), bfio=bool(v[2]), feat_buf=v[3],
                        lstm={'needed': bool(v[4]), 'tile_cols': v[5], 'bf_wino': bool(v[6]), 'bf_hoist': bool(v[7])})
+            out['head_bf16'] = len(f) > 14 and f[13] == 'head_bf16' and bool(int(f[14]))      # UKBB_PREC_BF16_FULL: the head on bf16 MFMA
     return out
 
 
