@@ -120,13 +120,15 @@ void ukbb_fcn_destroy(ukbb_fcn_handle *h);
  * store_b128_sofs, profiles/r06_notes.md section 10; tests/test_store_hazard.py guards the ISA of the whole library). */
 #define UKBB_PREC_FP32 0
 #define UKBB_PREC_BF16 1
-/* UKBB_PREC_F32X3 (round 2, FCN head only so far): fp32 results from bf16 matrix instructions.  Every fp32 operand x is
+/* UKBB_PREC_F32X3 (round 2: the FCN head; the FCN's 3x3 conv stack behind ukbb_fcn_set_f32x3_convs
+ * below): fp32 results from bf16 matrix instructions.  Every fp32 operand x is
  * split exactly into three bf16 pieces (h = bf16(x), m = bf16(x - h), l = x - h - m); the six partial products whose
  * magnitude can reach 2^-24 of |x||w| (hh, hm, mh, mm, hl, lh) run on the dense matrix cores with fp32 accumulation,
  * the other three (< 2^-24 |x||w|) are dropped -- less than what fp32 accumulation itself rounds away.  Measured
  * against the fp64 oracle the logits error is the same as UKBB_PREC_FP32's (4e-6 relative) and the label maps are
  * identical; it is a different instruction sequence from an fp32 MFMA, so it is offered as its own mode and reported
- * under its own name, never as the default.  Layers not converted yet run exactly as in UKBB_PREC_FP32. */
+ * under its own name, never as the default.  Without ukbb_fcn_set_f32x3_convs only the head is converted: every other launch runs exactly
+ * as in UKBB_PREC_FP32. */
 #define UKBB_PREC_F32X3 2
 /* UKBB_PREC_BF16_STORE (UKBB_KIND_FCN only; additive to ABI 11): the FCN encoder on the bf16-storage kernels of the aortic U-Net.  Where it
  * rounds: the folded 3x3 kernels are rounded to bf16 (RNE) once, when they are packed; the image is rounded to bf16 as the fused 1 -> 16 -> 16
@@ -163,6 +165,23 @@ void ukbb_fcn_destroy(ukbb_fcn_handle *h);
  * above in tests/test_fcn_bf16_full_launches_gpu.py.  Opt-in; the default and the benchmark's headline stay UKBB_PREC_FP32. */
 #define UKBB_PREC_BF16_FULL 5
 int ukbb_fcn_set_precision(ukbb_fcn_handle *h, int precision);
+
+/* The FCN's 3x3 conv stack on three bf16 pieces per operand as well (UKBB_KIND_FCN only; additive to ABI 11; off by default).  The setting
+ * is stored on the handle and takes effect on plans made while the precision is UKBB_PREC_F32X3; under any other precision it is kept and
+ * ignored.  Toggling it re-plans, as ukbb_fcn_set_precision does.  With it on the plan is the UKBB_PREC_F32X3 plan -- the fp32 fused stem
+ * conv0_0 + conv0_1, the fp32 squeeze launches, the three-piece head, the same fp32 maps and workspace -- with the eleven layers
+ * conv1_0 .. conv4_2 on the kernel of kernels_conv_x3.hip (tilings 330-345).
+ * Where the arithmetic splits: every fp32 activation is split once as its 16-channel chunk of a halo tile is staged into LDS
+ * (h = bf16(x), m = bf16(x - h), l = bf16(x - h - m), round to nearest even, residuals exact in fp32); the folded weights likewise on the
+ * host when they are packed.  Per filter tap and 16-channel chunk six v_mfma_f32_32x32x16_bf16 add into the one fp32 accumulator, weight
+ * piece x activation piece, small terms first: l.h, h.l, m.m, m.h, h.m, h.h.
+ * What is dropped: the products m.l, l.m and l.l (each below 2^-24 |w||x|) and what the third piece does not hold (below 2^-24 of the
+ * operand) -- less than what the fp32 accumulation rounds away.
+ * What stays fp32: every map in HBM (the layers read and store fp32 NHWC), the accumulators, bias, ReLU, the stem, the squeeze launches,
+ * logits, prob and pred -- so every table and file path works unchanged.  Not bit-compatible with UKBB_PREC_FP32 or with the plain
+ * UKBB_PREC_F32X3; each launch is graded against float64 in tests/test_f32x3_convs_launches_gpu.py.
+ * Returns UKBB_EARCH (with a message) on any other kind. */
+int ukbb_fcn_set_f32x3_convs(ukbb_fcn_handle *h, int on);
 
 /* Pre-size the activation workspace for batches up to n x h x w (optional;
  * forward() grows it on demand, which synchronises the device). */

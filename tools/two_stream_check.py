@@ -3,7 +3,7 @@ Two engines of one model on two streams, four batches in flight on each, every l
 r06: this is the check that exposed (and now guards) the wide-store hazard of kernels_ws.hip -- the bf16-storage U-Net failed 85-98 % of
 its forwards here until its 16-byte buffer stores were padded (profiles/r06_notes.md section 10).  A 'UNet-LSTM...' model runs whole cines
 (N = frames) through ukbb_fcn_forward_cine.
-    PREC=fp32|bf16|f32x3|bf16_store|bf16_full python tools/two_stream_check.py [model] [N H W] [iterations]        GPU box; prints OK / FAILED."""
+    PREC=fp32|bf16|f32x3|bf16_store|bf16_full [F32X3_CONVS=1] python tools/two_stream_check.py [model] [N H W] [iterations]        GPU box; prints OK / FAILED."""
 import os
 import sys
 
@@ -21,6 +21,7 @@ if __name__ == '__main__':
     n, h, w = (int(v) for v in sys.argv[2:5]) if len(sys.argv) > 4 else (64, 192, 208)
     iters = int(sys.argv[5]) if len(sys.argv) > 5 else 300
     prec = os.environ.get('PREC', 'fp32')
+    convs = os.environ.get('F32X3_CONVS') == '1'                 # with PREC=f32x3: the conv stack on three bf16 pieces as well (Engine.set_f32x3_convs)
     arch = MODELS[model]
     params = synthetic_params(arch, 1234)
     dev = torch.device('cuda', 0)
@@ -30,6 +31,8 @@ if __name__ == '__main__':
     for e in engs:
         if prec != 'fp32':
             e.set_precision(prec)
+        if convs:
+            e.set_f32x3_convs(True)
     streams = [torch.cuda.Stream(dev) for _ in range(2)]
 
     def forward(i, pred, stream=0):
@@ -58,6 +61,6 @@ if __name__ == '__main__':
                     bad += 1
                     if bad <= 5:
                         print('iteration %d stream %d: %d label pixels differ from the single-stream result' % (it + k, i, d), flush=True)
-    print('%s %s %dx%dx%d: %d forwards per stream on two streams, %d with differing labels' % (model, prec, n, h, w, iters, bad))
+    print('%s %s %dx%dx%d: %d forwards per stream on two streams, %d with differing labels' % (model, prec + ('+convs' if convs else ''), n, h, w, iters, bad))
     print('OK' if bad == 0 else 'FAILED')
     sys.exit(1 if bad else 0)

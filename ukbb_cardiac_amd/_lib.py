@@ -38,6 +38,9 @@ EXPORTS = [
     'ukbb_fcn_gzip_labels_device_scratch', 'ukbb_fcn_gzip_labels_device_geometry', 'ukbb_fcn_gzip_labels_device',
     'ukbb_fcn_gzip_labels_parallel_host',
 ]
+# ... and those whose names hold digits, listed apart: the header scan of tests/test_abi.py reads names of letters and underscores only and
+# holds EXPORTS to exactly what it finds.  build() and tests/test_f32x3_convs.py check this list the same way
+EXPORTS_NUMBERED = ['ukbb_fcn_set_f32x3_convs']
 
 
 class ArchStruct(C.Structure):
@@ -101,6 +104,7 @@ def _load():
     lib.ukbb_fcn_set_timing.argtypes = [vp, C.c_int]
     lib.ukbb_fcn_set_timing_kernel.argtypes = [vp, C.c_int]
     lib.ukbb_fcn_set_precision.argtypes = [vp, C.c_int]
+    lib.ukbb_fcn_set_f32x3_convs.argtypes = [vp, C.c_int]
     lib.ukbb_fcn_forward_seq.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.ukbb_fcn_forward_cine.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, vp, vp, vp]
     lib.ukbb_fcn_select_kth.argtypes = [vp, C.c_size_t, C.POINTER(C.c_uint64), C.c_int, f32p, vp]

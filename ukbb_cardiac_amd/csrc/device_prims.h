@@ -41,6 +41,17 @@ __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
     return (unsigned)__builtin_bit_cast(unsigned short, l) | ((unsigned)__builtin_bit_cast(unsigned short, h) << 16);
 }
 
+// UKBB_PREC_F32X3: the three bf16 pieces of two fp32 values, packed pairwise (low half = x0): x = h + m + l with h = bf16(x), m = bf16(x - h),
+// l = bf16(x - h - m), every rounding to nearest even and both residuals exact in fp32 (the library is built with -ffp-contract=off).  What the
+// third piece leaves is below 2^-24 |x|.  The FCN head (kernels_head.hip) and the X3 convs (kernels_conv_x3.hip) split their B operands with it.
+__device__ __forceinline__ void split_pair(float x0, float x1, unsigned &h, unsigned &m, unsigned &l) {
+    h = pack_bf16x2(x0, x1);
+    const float r0 = x0 - __builtin_bit_cast(float, h << 16), r1 = x1 - __builtin_bit_cast(float, h & 0xffff0000u);
+    m = pack_bf16x2(r0, r1);
+    const float q0 = r0 - __builtin_bit_cast(float, m << 16), q1 = r1 - __builtin_bit_cast(float, m & 0xffff0000u);
+    l = pack_bf16x2(q0, q1);
+}
+
 // ReLU as one integer max: for IEEE floats max_i32(bits(x), 0) is x for x >= +0 and +0 for anything
 // with the sign bit set.  fmaxf() on an MFMA result compiles to two instructions (a canonicalising
 // max and the max), and on gfx950 every VALU instruction takes issue time away from the fp32 MFMA

@@ -172,6 +172,7 @@ struct ukbb_fcn_handle {
 
     // plan
     int precision = UKBB_PREC_FP32;           // the code the next plan is built for (ukbb_fcn_set_precision)
+    bool f32x3_convs = false;                 // ukbb_fcn_set_f32x3_convs: plans made under UKBB_PREC_F32X3 run the 3x3 layers on three bf16 pieces too
     PlanLayout plan;                          // the CURRENT plan as layout_plan decided it (plan.h); its ops are bound in `ops`, its acts materialised in `acts`
     int plan_h = 0, plan_w = 0, cap_n = 0;
     bool plan_small = false;                  // plan built with the small-batch tilings
@@ -283,6 +284,9 @@ int ensure_packed(ukbb_fcn_handle *h, int layer, const ConvConfig &c, const floa
                 for (size_t r = 0; r < rows; ++r) std::copy(L.w.begin() + r * L.cout, L.w.begin() + (r + 1) * L.cout, wp.begin() + r * coutp);
                 pack_conv_weights_bf16(wp.data(), L.ks, L.cin, coutp, c.wm * c.cb, pk.data());
             }
+            break;
+        case ConvFamily::F32x3Operands:
+            if (fresh("x3", 3 * rows * coutp / 2)) pack_conv_x3(L.w.data(), L.cin, L.cout, c.wm * c.cb, pk.data());
             break;
         case ConvFamily::Wino22: if (fresh("wino", (size_t)16 * L.cin * L.cout)) pack_wino_weights(L.w.data(), L.cin, L.cout, c.wm, pk.data()); break;
         case ConvFamily::Wino24: if (fresh("wino24", (size_t)24 * L.cin * L.cout)) pack_wino24_weights(L.w.data(), L.cin, L.cout, c.wm, pk.data()); break;
@@ -526,7 +530,7 @@ int materialize_plan(ukbb_fcn_handle *h, PlanLayout &L) {
 
 int build_plan(ukbb_fcn_handle *h, int H, int W, int n_hint) {
     PlanLayout L;
-    int rc = layout_plan(h->arch, h->precision, H, W, n_hint, device_cu_count(), L);
+    int rc = layout_plan(h->arch, h->precision, H, W, n_hint, device_cu_count(), L, h->f32x3_convs);
     if (rc) return rc;
     h->cine = cine_units_from(L, h->arch, H, W);
     rc = materialize_plan(h, L);
@@ -940,10 +944,17 @@ int ukbb_fcn_debug_damage_guard(ukbb_fcn_handle *h, const char *buffer, long lon
     return UKBB_EINVAL;
 }
 
+// ukbb_fcn_set_f32x3_convs on any kind but the FCN: the error text set, true
+static bool refuse_f32x3_convs(int kind) {
+    if (kind == UKBB_KIND_FCN) return false;
+    set_error("set_f32x3_convs: the three-piece convolutions are built for the FCN models only (the U-Net kinds have no f32x3 conv kernels)");
+    return true;
+}
+
 // debugging / testing aid, not in the public header: the plan layout_plan makes for batches of n images of H x W on a device of `cus`
 // compute units, as text -- host arithmetic only, no device needed.  One line per op, one per activation map, then the plan's fields.
 // Returns the text's length (it is truncated when cap is smaller), or the negative code create / set_precision / reserve would give.
-int ukbb_fcn_debug_plan_layout(const ukbb_fcn_arch *arch, int precision, int n, int H, int W, int cus, char *buf, size_t cap) {
+static int debug_plan_text(const ukbb_fcn_arch *arch, int precision, bool f32x3_convs, int n, int H, int W, int cus, char *buf, size_t cap) {
     static const char *const kinds[] = {"first", "conv", "head", "tconv", "logits", "sqg", "sqg_multi", "tail", "stem", "first3d", "conv3d", "tconv3d"};
     if (!arch || (!buf && cap) || cus < 1) { set_error("debug_plan_layout: bad argument"); return UKBB_EINVAL; }
     PlanLayout L;
@@ -951,7 +962,7 @@ int ukbb_fcn_debug_plan_layout(const ukbb_fcn_arch *arch, int precision, int n, 
     if (plan_mode(*arch, precision, L.mode, &why) == UKBB_EINVAL) { set_error("debug_plan_layout: bad precision"); return UKBB_EINVAL; }
     int rc = check_shape(n, H, W);
     if (rc) return rc;
-    rc = layout_plan(*arch, precision, H, W, n, cus, L);      // refuses the (kind, precision) pairs plan_mode refuses
+    rc = layout_plan(*arch, precision, H, W, n, cus, L, f32x3_convs);      // refuses the (kind, precision) pairs plan_mode refuses
     if (rc) return rc;
     std::string out;
     char line[512];
@@ -968,8 +979,17 @@ int ukbb_fcn_debug_plan_layout(const ukbb_fcn_arch *arch, int precision, int n, 
     snprintf(line, sizeof line, "plan split %d %d bfio %d feat_buf %d lstm %d %d %d %d head_bf16 %d\n", L.split_first, L.split_last, (int)L.mode.bfio(), L.feat_buf,
              (int)L.needs_lstm, L.lstm_tile_cols, (int)L.lstm_bf_wino, (int)L.lstm_bf_hoist, (int)L.mode.head_bf16);
     out += line;
+    if (L.mode.conv_x3) out.replace(out.size() - 1, 1, " conv_x3 1\n");      // only a plan that has it says so: every other text is unchanged
     if (cap) { const size_t m = std::min(out.size(), cap - 1); memcpy(buf, out.data(), m); buf[m] = 0; }
     return (int)out.size();
+}
+int ukbb_fcn_debug_plan_layout(const ukbb_fcn_arch *arch, int precision, int n, int H, int W, int cus, char *buf, size_t cap) {
+    return debug_plan_text(arch, precision, false, n, H, W, cus, buf, cap);
+}
+// ... with the handle's ukbb_fcn_set_f32x3_convs setting as an argument (it takes effect under UKBB_PREC_F32X3 on an FCN architecture only)
+int ukbb_fcn_debug_plan_layout_x3(const ukbb_fcn_arch *arch, int precision, int f32x3_convs, int n, int H, int W, int cus, char *buf, size_t cap) {
+    if (arch && f32x3_convs && refuse_f32x3_convs(arch->kind)) return UKBB_EARCH;      // as ukbb_fcn_set_f32x3_convs on a handle of that kind
+    return debug_plan_text(arch, precision, f32x3_convs != 0, n, H, W, cus, buf, cap);
 }
 
 // debugging / testing aid, not in the public header: pack_head_bf16 (kernels_head.hip) on a host matrix, host arithmetic only.  dst takes
@@ -1630,6 +1650,18 @@ int ukbb_fcn_set_precision(ukbb_fcn_handle *h, int precision) {
         if (hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { set_error("set_precision: device sync failed"); return UKBB_EDEVICE; }
         h->precision = precision;
         h->plan_h = h->plan_w = 0;               // re-plan (tilings and packed weights differ)
+    }
+    return UKBB_OK;
+}
+
+int ukbb_fcn_set_f32x3_convs(ukbb_fcn_handle *h, int on) {
+    if (!h) { set_error("set_f32x3_convs: NULL handle"); return UKBB_EINVAL; }
+    if (refuse_f32x3_convs(h->arch.kind)) return UKBB_EARCH;
+    const bool want = on != 0;
+    if (want != h->f32x3_convs) {
+        if (hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { set_error("set_f32x3_convs: device sync failed"); return UKBB_EDEVICE; }
+        h->f32x3_convs = want;
+        h->plan_h = h->plan_w = 0;               // re-plan, as set_precision does (under any precision but UKBB_PREC_F32X3 the same plan comes back)
     }
     return UKBB_OK;
 }

@@ -206,6 +206,9 @@ enum class ConvFamily {
     Bf16StoreWs,    // bf16 storage as Bf16Store, weight-stationary persistent kernel of independent waves (kernels_ws.hip)
     FirstWino22,    // as ProdConsFirst (fused first layer, fp32), the 16 -> 16 conv as Winograd F(2x2,3x3) in the consumers (id 134;
                     // weights from pack_wino_first_weights)
+    F32x3Operands,  // single-role kernel of kernels_conv_x3.hip (ids 330-345): fp32 maps in HBM on both sides, each operand as three bf16 pieces
+                    // (activations split while staging, weights when packed: pack_conv_x3), six bf16 MFMAs per (tap, chunk) into the one
+                    // fp32 accumulator, fp32 epilogue.  Planned only with PlanMode::conv_x3 (UKBB_PREC_F32X3 + ukbb_fcn_set_f32x3_convs)
 };
 
 // One compiled tiling of the conv kernel.
@@ -248,6 +251,11 @@ const ConvConfig &ws_config(int i);
 int ws_lds_bytes_for(const ConvConfig &c, int cin);
 int wst_pack_order(int cout, int v);    // transposed-conv tilings (ids 410-, ks 2): source column of packed virtual channel v
 hipError_t launch_conv_ws(int cfg_id, const ConvArgs &a, hipStream_t s);
+// the three-piece (UKBB_PREC_F32X3) 3x3 tilings of ConvFamily::F32x3Operands (ids 330-345) live in kernels_conv_x3.hip; the three functions above
+// cover them.  LDS = three times the bf16-operand tiling's
+int num_x3_configs();
+const ConvConfig &x3_config(int i);
+hipError_t launch_conv_x3(int cfg_id, const ConvArgs &a, hipStream_t s);
 // cout handled by one workgroup = mb*cb*wm
 hipError_t launch_conv(int cfg_id, const ConvArgs &a, hipStream_t s);
 
@@ -256,6 +264,9 @@ hipError_t launch_conv(int cfg_id, const ConvArgs &a, hipStream_t s);
 size_t pack_conv_weights(const float *w, int ks, int cin, int cout, int mb, int kc, int ncbl, float *dst);
 // bf16 operand variant (packs_bf16): 8 bf16 per lane per tap, returns dwords written.
 size_t pack_conv_weights_bf16(const float *w, int ks, int cin, int cout, int ncbl, float *dst);
+// three-piece variant (ConvFamily::F32x3Operands, 3x3 only): per chunk the bf16 pieces h, m, l of the bf16 layout above, residuals formed in
+// fp32 (as pack_head_x3); returns dwords written (3 x the bf16 packing)
+size_t pack_conv_x3(const float *w, int cin, int cout, int ncbl, float *dst);
 
 // Winograd F(2x2,3x3) producer/consumer kernel (kernels_wino.hip): 3x3, stride 1, C_out % 64 == 0,
 // C_in % 16 == 0.  ConvFamily::Wino22, ids 300-303.  Same ConvArgs; wpk from pack_wino_weights().

@@ -1452,8 +1452,9 @@ static const ConvConfig g_cfgs[] = {UKBB_CONV_CONFIGS(UKBB_CFG_ENTRY) UKBB_PC_CO
                                     {134, 3, 1, 16, 16, 16, 16, 1, 4, 1, (2 * 324 * 20 + 2 * 16 * 64 * 2 + 2 * 400) * 4, ConvFamily::FirstWino22, "winogradF2x2_first+3x3s1_t16x16_kc16_cout16"}};
 
 static constexpr int N_BASE_CFGS = (int)(sizeof(g_cfgs) / sizeof(g_cfgs[0]));
-int num_conv_configs() { return N_BASE_CFGS + num_pk16_configs() + num_ws_configs(); }
+int num_conv_configs() { return N_BASE_CFGS + num_pk16_configs() + num_ws_configs() + num_x3_configs(); }
 const ConvConfig &conv_config(int i) {
+    if (i >= N_BASE_CFGS + num_pk16_configs() + num_ws_configs()) return x3_config(i - N_BASE_CFGS - num_pk16_configs() - num_ws_configs());
     return i < N_BASE_CFGS ? g_cfgs[i] : i < N_BASE_CFGS + num_pk16_configs() ? pk16_config(i - N_BASE_CFGS) : ws_config(i - N_BASE_CFGS - num_pk16_configs());
 }
 
@@ -1462,6 +1463,8 @@ hipError_t launch_conv(int cfg_id, const ConvArgs &a_in, hipStream_t s) {
         if (pk16_config(i).id == cfg_id) return launch_conv16_pk(cfg_id, a_in, s);
     for (int i = 0; i < num_ws_configs(); ++i)
         if (ws_config(i).id == cfg_id) return launch_conv_ws(cfg_id, a_in, s);
+    for (int i = 0; i < num_x3_configs(); ++i)
+        if (x3_config(i).id == cfg_id) return launch_conv_x3(cfg_id, a_in, s);
     ConvArgs a = a_in;
 #ifdef UKBB_DIAG
     { const char *e = getenv("UKBB_CONV_DIAG"); a.diag = e ? atoi(e) : 0; }

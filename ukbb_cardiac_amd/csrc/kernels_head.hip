@@ -480,13 +480,7 @@ __device__ __forceinline__ void chain_32to64_lds(const float *wp, int lane, cons
 // x = h + m + l with h = bf16(x), m = bf16(x - h), l = x - h - m (all exact in fp32); W likewise on the host.  The six partial
 // products that matter (hh, hm, mh, mm, hl, lh) run as v_mfma_f32_32x32x16_bf16 with fp32 accumulation; what is dropped is
 // below 2^-24 of |x||w| per product (profiles/r02_notes.md section 11).
-__device__ __forceinline__ void split_pair(float x0, float x1, unsigned &h, unsigned &m, unsigned &l) {
-    h = pack_bf16x2(x0, x1);
-    const float r0 = x0 - __builtin_bit_cast(float, h << 16), r1 = x1 - __builtin_bit_cast(float, h & 0xffff0000u);
-    m = pack_bf16x2(r0, r1);
-    const float q0 = r0 - __builtin_bit_cast(float, m << 16), q1 = r1 - __builtin_bit_cast(float, m & 0xffff0000u);
-    l = pack_bf16x2(q0, q1);
-}
+// split_pair (device_prims.h) forms the pieces of two values at once.
 
 // ---- separable gather (r08): which x-interpolated window rows a run of four output rows reads ---------------------------------
 // Tile origins are multiples of 16 >= f, so for tile row r the level-l taps sit in window rows (r + pb) >> l (weight

@@ -160,10 +160,15 @@ bool tile_fit_ok(const ConvConfig &c, int Ho, int Wo) {
 // Fallback preference (small tiles / high occupancy won everywhere in the sweep).
 const int g_pref[] = {4, 5, 18, 3, 11, 7, 31, 23, 22, 29, 27, 26};
 
-// a bf16-operand tiling only in a bf16-operand plan, a bf16-storage tiling only in a bf16-storage plan, an fp32 tiling in either of the others
+// a bf16-operand tiling only in a bf16-operand plan, a bf16-storage tiling only in a bf16-storage plan, an fp32 tiling in either of the others;
+// x3: the layer is one a conv_x3 plan runs on three bf16 pieces (x3_layer) -- it then takes a ConvFamily::F32x3Operands tiling and no other,
+// and no other layer of any plan takes one
 bool cfg_valid(const ConvConfig &c, int ks, int stride, int c0, int c1, int cout, bool fused_first = false,
-               Bf16Mode bf16 = Bf16Mode::None, int fuse = 0) {
+               Bf16Mode bf16 = Bf16Mode::None, int fuse = 0, bool x3 = false) {
     if (c.ks != ks || c.stride != stride) return false;
+    if ((c.family == ConvFamily::F32x3Operands) != x3) return false;
+    if (x3) return !fused_first && !fuse && bf16 == Bf16Mode::None && ks == 3 && c1 == 0 && c0 >= c.kc && c0 % c.kc == 0 &&
+                   cout % cout_per_item(c) == 0 && c.lds_bytes <= 160 * 1024;
     if (c.fuse != fuse) return false;
     if (fuses_first(c) != fused_first) return false;
     if (c.family == ConvFamily::FirstWino22) {        // fused first layer + Winograd conv0_1: the 16 -> 16 stem of the fp32 FCN plans only
@@ -365,6 +370,53 @@ int choose_cfg_raw(const std::string &layer, int ks, int stride, int c0, int c1,
     return best_id;
 }
 
+// ---- conv_x3 plans (UKBB_PREC_F32X3 + ukbb_fcn_set_f32x3_convs) ----
+// The layers such a plan runs on ConvFamily::F32x3Operands: every single-source 3x3 conv behind the stem with whole 16-channel chunks in
+// and whole 32-row blocks out -- conv1_0 .. conv4_2 of the FCN graph.
+bool x3_layer(const PlanMode &m, int ks, int c0, int c1, int cout, bool fused_first) {
+    return m.conv_x3 && ks == 3 && !fused_first && c1 == 0 && c0 >= 16 && c0 % 16 == 0 && cout % 32 == 0;
+}
+// ONE table for every batch size (the plan must not depend on the batch): per layer type the tilings in order of preference among equals.
+// 12 x 13 tiles divide the 192 x 208 pyramid, 11 x 13 the long-axis models' 176 x 208, 8 x 16 power-of-two maps.  Measured per kernel at
+// N = 64 x 192 x 208 (profiles/f32x3_convs.txt): what a launch costs follows the 32-pixel MFMA blocks it issues, idle wave slots included -- a
+// 12 x 13 tile is 5 blocks in 6 slots (8 with four pixel waves), an 8 x 16 tile 4 in 4 -- so 8 x 16 wins level 1 outright (conv1_1 73 against
+// 92 us, conv1_0 97 against 104) and 12 x 13 level 4 (75 against 89); where the counts tie (levels 2 and 3) the stride-1 layers were faster on
+// 8 x 16 (75 / 72 against 85 / 80 us) and the stride-2 layers, whose halo is four times the tile, on 12 x 13 (68 / 61 against 72 / 62).
+// 64 output channels per workgroup wherever the layer has them: with 32 a second workgroup fits the CU, and every layer was slower
+// (conv2_1 87 against 85 us, conv2_0 93 against 68).
+// Only those two pyramids were timed.  choose_x3_cfg decides by the block count alone, so on other shapes 12 x 13 and 11 x 13 are also taken
+// on maps of several tiles with ragged edges (a 12 x 20 map: 12 slots against 16 for 8 x 16) and as single partial tiles: there the order
+// among equals is an extrapolation of the measurement, not a measurement.
+const Tuned g_tuned_x3[] = {
+    {3, 2, 16, 32, 345, -1, -1},    {3, 1, 32, 32, 335, -1, -1},
+    {3, 2, 32, 64, 342, 340, 344},  {3, 1, 64, 64, 334, 332, 330},
+    {3, 2, 64, 128, 342, 340, 344}, {3, 1, 128, 128, 334, 332, 330},
+    {3, 2, 128, 256, 342, 340, 344}, {3, 1, 256, 256, 334, 332, 330},
+};
+// Of the layer type's tilings the one that issues the fewest 32-pixel MFMA blocks over the map (tiles x block slots of a tile, the slots of
+// waves a tile leaves idle included); the table's order among equals.  A layer type the table lacks: the same rule over every valid tiling
+// of the family.
+int choose_x3_cfg(const std::string &layer, int stride, int c0, int cout, int Ho, int Wo) {
+    auto pick = [&](const std::vector<int> &cand) {
+        int best = -1; long long best_slots = 0;
+        for (int id : cand) {
+            ConvConfig c;
+            if (id < 0 || find_cfg(id, c) || !cfg_valid(c, 3, stride, c0, 0, cout, false, Bf16Mode::None, 0, true)) continue;
+            const int npb = (c.th * c.tw + c.mb - 1) / c.mb, pbw = (npb + c.wn - 1) / c.wn;
+            const long long slots = (long long)map_tiles(c, Ho, Wo) * pbw * c.wn;
+            if (best < 0 || slots < best_slots) { best = id; best_slots = slots; }
+        }
+        return best;
+    };
+    const int forced = pick({override_cfg(layer)});     // UKBB_CONV_CFG, where it names a tiling of the family that is valid for the layer
+    if (forced >= 0) return forced;
+    for (const Tuned &t : g_tuned_x3)
+        if (t.stride == stride && t.cin == c0 && t.cout == cout) return pick({t.cfg, t.alt, t.alt2});
+    std::vector<int> all;
+    for (int i = 0; i < num_conv_configs(); ++i) all.push_back(conv_config(i).id);
+    return pick(all);
+}
+
 // bf16 storage: the fused variants of the level-0 tilings (ConvConfig::fuse: 1 = first layer in the staging, 2 = logits in the
 // epilogue), first fit in measured order; -1 if none fits (the plan then keeps that layer as a launch of its own).
 int pick_fused_bf_cfg(const std::string &lname, int ks, int stride, int c0, int c1, int cout, int Ho, int Wo, int fuse_bf) {
@@ -457,7 +509,9 @@ int plan_conv(Planner &p, const std::string &lname, int in0, int in1, int c1, in
     // the Winograd form of the fused first layer (134) was measured on, and is taken by, the fp32 FCN plans only (UKBB_PREC_F32X3 included:
     // its convs are fp32); the U-Net / UNet-LSTM plans and the bf16-operand FCN plans keep the direct fused kernel (130-133)
     const bool wino_first = fused_first && p.a.kind == UKBB_KIND_FCN && p.L.mode.bf16 == Bf16Mode::None;
+    const bool x3 = x3_layer(p.L.mode, L.ks, c0, c1, L.cout, fused_first);
     if (fuse_bf) op.cfg = pick_fused_bf_cfg(lname, L.ks, stride, c0, c1, L.cout, op.Ho, op.Wo, fuse_bf);
+    else if (x3) op.cfg = choose_x3_cfg(lname, stride, c0, L.cout, op.Ho, op.Wo);
     else op.cfg = choose_cfg(lname, L.ks, stride, c0, c1, L.cout, op.Ho, op.Wo, p.n_hint, p.cus, fused_first, p.L.mode.bf16, wino_first);
     op.fused_logits = fuse_bf == 2;
     if (op.cfg < 0) { set_error("no conv tiling for layer %s (ks %d stride %d cin %d+%d cout %d)", lname.c_str(), L.ks, stride, c0, c1, L.cout); return UKBB_EARCH; }
@@ -485,6 +539,10 @@ int plan_conv(Planner &p, const std::string &lname, int in0, int in1, int c1, in
         const double first_macs = (double)op.Ho * op.Wo * 9 * L.cin;   // conv0_0: 1 -> L.cin channels
         op.mfma_macs_per_image = op.macs_per_image * (16.0 / 36.0) + first_macs;
         op.padded_macs_per_image = tiles * ((c.th / 2) * (c.tw / 2) * 16.0 * L.cin * L.cout + halo_blocks * 16 * 12 * L.cin);
+    } else if (c.family == ConvFamily::F32x3Operands) {  // six bf16 products per fp32 one, over tiles x 32-pixel blocks
+        const int npb = (c.th * c.tw + c.mb - 1) / c.mb;
+        op.mfma_macs_per_image = 6.0 * op.macs_per_image;
+        op.padded_macs_per_image = 6.0 * tiles * npb * c.mb * L.ks * L.ks * (double)L.cin * L.cout;
     } else if (!packs_bf16(c)) {                       // direct fp32 tilings: tiles x pixel blocks of the MFMA's N width
         const int npb = (c.th * c.tw + c.mb - 1) / c.mb;
         op.padded_macs_per_image = tiles * npb * c.mb * L.ks * L.ks * (double)L.cin * L.cout;
@@ -784,10 +842,11 @@ int plan_mode(const ukbb_fcn_arch &a, int precision, PlanMode &m, const char **w
     return UKBB_OK;
 }
 
-int layout_plan(const ukbb_fcn_arch &a, int precision, int H, int W, int n_hint, int cus, PlanLayout &L) {
+int layout_plan(const ukbb_fcn_arch &a, int precision, int H, int W, int n_hint, int cus, PlanLayout &L, bool f32x3_convs) {
     L = PlanLayout();
     const char *refused;
     if (const int rc = plan_mode(a, precision, L.mode, &refused)) { set_error("%s", refused); return rc; }
+    L.mode.conv_x3 = f32x3_convs && L.mode.head_x3 && a.kind == UKBB_KIND_FCN;      // kept and ignored under any other precision
     Planner p{a, n_hint, cus, L, {}};
     std::string why;
     if (!arch_specs(a, p.specs)) { set_error("malformed architecture descriptor"); return UKBB_EARCH; }

@@ -53,6 +53,8 @@ struct PlanMode {
     bool head_x3 = false;                     // UKBB_PREC_F32X3: the FCN head's out0 / out1 from three bf16 pieces per operand (its convs are fp32)
     bool head_bf16 = false;                   // UKBB_PREC_BF16_FULL: the FCN head's same_dim0 / out0 / out1 on the bf16 matrix instruction, one piece per operand
                                               // (the encoder and the squeeze launches are those of UKBB_PREC_BF16_STORE: bf16 == Storage)
+    bool conv_x3 = false;                     // UKBB_PREC_F32X3 with ukbb_fcn_set_f32x3_convs on (FCN only): the 3x3 layers behind the stem on
+                                              // ConvFamily::F32x3Operands as well; maps, squeeze launches, stem and head as in the f32x3 plan
     bool bfio() const { return bf16 == Bf16Mode::Storage; }
 };
 // THE list of precision codes and of the (kind, code) pairs the engine refuses.  UKBB_OK; UKBB_EINVAL for an unknown code; UKBB_EARCH
@@ -76,7 +78,8 @@ constexpr int SMALL_BATCH = 16;
 int find_cfg(int id, ConvConfig &out);        // 0: found
 
 // The plan for batches of up to n_hint images of H x W on a device of `cus` compute units.  UKBB_OK, or plan_mode's code / UKBB_EARCH with the error text set.
-int layout_plan(const ukbb_fcn_arch &a, int precision, int H, int W, int n_hint, int cus, PlanLayout &L);
+// f32x3_convs: the handle's ukbb_fcn_set_f32x3_convs setting; it becomes PlanMode::conv_x3 on an FCN plan under UKBB_PREC_F32X3 and is ignored otherwise.
+int layout_plan(const ukbb_fcn_arch &a, int precision, int H, int W, int n_hint, int cus, PlanLayout &L, bool f32x3_convs = false);
 
 // ---- forward_cine scratch planner ---------------------------------------------------
 // Device bytes forward_cine holds per frame / per window of a cine at one (arch, precision, H, W).  DevBufs count floats; bf16 maps take half.

@@ -69,6 +69,9 @@ def define_flags():
                    'head\'s three matrix products on bf16 matrix instructions too -- their weights rounded to bf16 once when packed, the two '
                    'hidden activations once in registers; biases, the upsampled G_l sum, accumulators, logits, softmax and labels stay fp32 '
                    '(UKBB_PREC_BF16_FULL; same Dice bound).')
+    fs.DEFINE_boolean('f32x3_convs', False, 'With --precision f32x3: the eleven 3x3 layers conv1_0 .. conv4_2 from three bf16 pieces per operand as '
+                      'well (ukbb_fcn_set_f32x3_convs, include/ukbb_fcn.h): fp32 maps, fp32 accumulation, bias, ReLU and stores; same output files '
+                      'up to voxels next to a tie of the two largest logits.  A flag error under any other --precision.')
     fs.DEFINE_enum('label_gzip', 'small', list(nifti.LABEL_GZIP_MODES), 'Deflate of the label volumes: small = run-length tokens + dynamic Huffman '
                    '(typically below the size of zlib level 1, ~20x less CPU), fast = fixed Huffman (2-4x larger files), zlib = as nibabel. Same inflated bytes.')
     fs.DEFINE_boolean('device_label_gzip', False, 'Sequence mode, pipelined loop (--device_preproc with --io_threads > 0, without --device_inflate): '
@@ -202,6 +205,8 @@ def main(argv=None):
         FLAGS, rest = fs.parse(sys.argv[1:] if argv is None else argv)
     except FlagError as e:
         sys.exit('FATAL Flags parsing error: %s\n%s' % (e, fs.usage()))
+    if FLAGS.f32x3_convs and FLAGS.precision != 'f32x3':
+        sys.exit('FATAL Flags parsing error: --f32x3_convs needs --precision f32x3 (got --precision %s)\n%s' % (FLAGS.precision, fs.usage()))
     if 'CUDA_VISIBLE_DEVICES' in os.environ and 'HIP_VISIBLE_DEVICES' not in os.environ:
         os.environ['HIP_VISIBLE_DEVICES'] = os.environ['CUDA_VISIBLE_DEVICES']   # demo_pipeline.py:25,63
     apply_cpu_set_from_env()                             # shard.launch's per-worker CPU set, before the first GPU call starts threads
@@ -209,6 +214,8 @@ def main(argv=None):
     with Session(FLAGS.model_path, device=FLAGS.device) as sess:
         if FLAGS.precision != 'fp32':
             sess.engine.set_precision(FLAGS.precision)
+        if FLAGS.f32x3_convs:
+            sess.engine.set_f32x3_convs(True)
         nifti.set_label_gzip(FLAGS.label_gzip)
         print('Start deployment on the data set ...')
 

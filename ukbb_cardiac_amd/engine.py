@@ -152,7 +152,7 @@ class Engine:
 
     def set_precision(self, precision: str):
         """'fp32' (default), 'bf16' (bf16 MFMA inputs, fp32 accumulate; BASELINE config 5), 'f32x3' (fp32 results from three
-        bf16 pieces per operand on the dense matrix cores; FCN head so far; include/ukbb_fcn.h UKBB_PREC_F32X3), 'bf16_store'
+        bf16 pieces per operand on the dense matrix cores: the FCN head, and with ``set_f32x3_convs(True)`` the FCN's 3x3 conv stack; include/ukbb_fcn.h UKBB_PREC_F32X3), 'bf16_store'
         (FCN models only: bf16 operands and bf16 encoder maps in HBM, squeeze and head in fp32; UKBB_PREC_BF16_STORE), 'bf16_full'
         (FCN models only: 'bf16_store' with the head's three matrix products on the bf16 matrix instruction as well -- weights rounded
         once when packed, the two hidden activations once in registers; biases, the G_l maps, accumulators, logits, prob and pred
@@ -160,6 +160,12 @@ class Engine:
         (Temporal-UNet only: its 3-D convolutions on the bf16 matrix instruction, every 3-D map bf16 in HBM, the first layer's
         arithmetic, logits, prob and pred fp32; UKBB_PREC_BF16_3D.  'bf16' and 'bf16_store' stay refused on that model)."""
         _lib.check(_lib.lib.ukbb_fcn_set_precision(self._h, _PLAN_PREC[precision]), 'ukbb_fcn_set_precision')
+
+    def set_f32x3_convs(self, on: bool):
+        """FCN models only, off by default: under 'f32x3' run the eleven 3x3 layers conv1_0 .. conv4_2 on three bf16 pieces per operand as
+        well (include/ukbb_fcn.h ukbb_fcn_set_f32x3_convs): fp32 maps in HBM, six bf16 matrix instructions per tap and 16-channel chunk into
+        one fp32 accumulator, fp32 bias / ReLU / store.  Stored on the handle; kept and ignored under any other precision."""
+        _lib.check(_lib.lib.ukbb_fcn_set_f32x3_convs(self._h, int(bool(on))), 'ukbb_fcn_set_f32x3_convs')
 
     def set_scratch_budget(self, nbytes: int):
         """Bound the device memory ``run_cine`` / ``run_cine_device`` may hold for their per-cine scratch (0 = no budget, the default):
@@ -270,20 +276,28 @@ _PLAN_PREC = {'fp32': 0, 'bf16': 1, 'f32x3': 2, 'bf16_store': 3, 'bf16_3d': 4, '
 _OP_FIELDS = ('cfg', 'H', 'W', 'Ho', 'Wo', 'stride', 'in0', 'in1', 'out')
 
 
-def plan_layout(arch: ModelArch, precision: str, n: int, h: int, w: int, cus: int = 256) -> dict:
+def plan_layout(arch: ModelArch, precision: str, n: int, h: int, w: int, cus: int = 256, f32x3_convs: bool = False) -> dict:
     """The launch plan the engine builds for batches of ``n`` images of ``h`` x ``w`` on a device of ``cus`` compute units, from
     the host-only planner (no GPU needed): ``{'ops': [dict], 'acts': [dict], 'split': (first, last), 'bfio', 'feat_buf', 'lstm', 'head_bf16'}``.
     An op's ``macs`` / ``mfma_macs`` / ``issued_macs`` are per image, as ``Engine.kernel_macs()`` etc. report them per batch.
     A map of the workspace takes ``per_image * bytes_per_element`` bytes per image.
+    ``f32x3_convs``: the plan of an engine with ``set_f32x3_convs(True)``; where it takes effect (an FCN model under 'f32x3') the dict
+    also holds ``'conv_x3': True``.
     Raises UkbbFcnError where ``Engine`` would refuse the combination."""
-    fn = _lib.lib.ukbb_fcn_debug_plan_layout                     # debugging aid: not part of the public header
-    fn.argtypes = [C.POINTER(_lib.ArchStruct)] + [C.c_int] * 5 + [C.c_char_p, C.c_size_t]
     a = _lib.arch_struct(arch)
+    if f32x3_convs:
+        fn = _lib.lib.ukbb_fcn_debug_plan_layout_x3              # the same text for a handle with the switch on
+        fn.argtypes = [C.POINTER(_lib.ArchStruct)] + [C.c_int] * 6 + [C.c_char_p, C.c_size_t]
+        args = (C.byref(a), _PLAN_PREC[precision], 1, int(n), int(h), int(w), int(cus))
+    else:
+        fn = _lib.lib.ukbb_fcn_debug_plan_layout                 # debugging aid: not part of the public header
+        fn.argtypes = [C.POINTER(_lib.ArchStruct)] + [C.c_int] * 5 + [C.c_char_p, C.c_size_t]
+        args = (C.byref(a), _PLAN_PREC[precision], int(n), int(h), int(w), int(cus))
     buf = C.create_string_buffer(1 << 16)
-    got = _lib.check(fn(C.byref(a), _PLAN_PREC[precision], int(n), int(h), int(w), int(cus), buf, len(buf)), 'ukbb_fcn_debug_plan_layout')
+    got = _lib.check(fn(*args, buf, len(buf)), 'ukbb_fcn_debug_plan_layout')
     if got >= len(buf):
         buf = C.create_string_buffer(got + 1)
-        _lib.check(fn(C.byref(a), _PLAN_PREC[precision], int(n), int(h), int(w), int(cus), buf, len(buf)), 'ukbb_fcn_debug_plan_layout')
+        _lib.check(fn(*args, buf, len(buf)), 'ukbb_fcn_debug_plan_layout')
     out = {'ops': [], 'acts': []}
     for line in buf.value.decode().splitlines():
         f = line.split(' ')
@@ -302,6 +316,8 @@ def plan_layout(arch: ModelArch, precision: str, n: int, h: int, w: int, cus: in
             out.update(split=(v[0], v[1]), bfio=bool(v[2]), feat_buf=v[3],
                        lstm={'needed': bool(v[4]), 'tile_cols': v[5], 'bf_wino': bool(v[6]), 'bf_hoist': bool(v[7])})
             out['head_bf16'] = len(f) > 14 and f[13] == 'head_bf16' and bool(int(f[14]))      # UKBB_PREC_BF16_FULL: the head on bf16 MFMA
+            if len(f) > 16 and f[15] == 'conv_x3' and int(f[16]):                             # only a plan that has it
+                out['conv_x3'] = True
     return out
 
 
