@@ -94,7 +94,13 @@ size_t ukbb_fcn_weight_count(const ukbb_fcn_arch *arch);
 
 /* Bind a model to `device` (HIP ordinal).  Folds BN into the kernels, packs
  * MFMA operand fragments and uploads them.  `weights` is host memory and is
- * not referenced after return.  NULL on failure. */
+ * not referenced after return.  NULL on failure.
+ * Accepted architectures (anything else: NULL, ukbb_fcn_last_error() gives the reason): n_level 5, n_filter[0] 16, n_filter[l>0]
+ * positive multiples of 32, n_block[l] >= 1.  FCN: same_dim 32,
+ * fc 64, n_class 2..6, and n_filter[l>0] one of 32, 64, 128, 256 (the widths the squeeze kernels are built for).  UNet kinds:
+ * n_class 2..4; UNet-LSTM: 16 hidden channels; UNet-LSTM and Temporal-UNet: an odd window below 32 frames.  Every launch of the
+ * named models and of the descriptors of tests/custom_archs.py (widths 32..256, blocks 1..4 per level) is graded against float64;
+ * wider U-Net pyramids are accepted as before and have not been run. */
 ukbb_fcn_handle *ukbb_fcn_create(const ukbb_fcn_arch *arch, const float *weights,
                                  size_t n_floats, int device);
 void ukbb_fcn_destroy(ukbb_fcn_handle *h);

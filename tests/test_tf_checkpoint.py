@@ -188,3 +188,22 @@ def test_unidirectional_conv_lstm_checkpoint_loads_as_a_zero_backward_cell(tmp_p
     write_checkpoint(prefix, both, tensor_crc=False)
     _, params3 = tfc.checkpoint_to_params(prefix)
     np.testing.assert_array_equal(pack_flat(arch, params3), pack_flat(arch, params))
+
+
+def test_custom_checkpoint_the_engine_refuses_gets_the_reason_at_load_time(tmp_path):
+    """infer_arch builds FCN_custom / UNet_custom from the kernel shapes; a pyramid plan.cpp supported() refuses (the FCN squeeze kernels exist for 32, 64,
+    128 and 256 channels) is refused when the checkpoint is loaded, with supported()'s reason, not at the first forward; an accepted one loads."""
+    import dataclasses
+    wide = dataclasses.replace(MODELS['FCN_sa'], name='FCN_custom', n_filter=(16, 32, 96, 160, 96), n_block=(2, 2, 3, 2, 2))
+    prefix = str(tmp_path / 'wide')
+    write_checkpoint(prefix, _tf_tensors(wide, synthetic_params(wide, 3), with_slots=False), tensor_crc=False)
+    assert tfc.infer_arch(tfc.CheckpointReader(prefix)) == wide
+    with pytest.raises(tfc.CheckpointError, match=r'FCN squeeze kernels are built for n_filter\[l>0\] in \{32, 64, 128, 256\}'):
+        tfc.checkpoint_to_params(prefix)
+    ok = dataclasses.replace(MODELS['UNet_ao'], name='UNet_custom', n_filter=(16, 32, 96, 160, 96), n_block=(3, 1, 2, 3, 1), n_class=4)
+    prefix = str(tmp_path / 'ok')
+    params = synthetic_params(ok, 3)
+    write_checkpoint(prefix, _tf_tensors(ok, params, with_slots=False), tensor_crc=False)
+    arch2, params2 = tfc.checkpoint_to_params(prefix)
+    assert arch2 == ok
+    np.testing.assert_array_equal(pack_flat(arch2, params2), pack_flat(ok, params))

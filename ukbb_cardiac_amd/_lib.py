@@ -187,7 +187,10 @@ lib = _load()
 
 
 class UkbbFcnError(RuntimeError):
-    pass
+    code = None                           # the UKBB_E* return code of include/ukbb_fcn.h, where check() raised it
+
+
+UKBB_EARCH = -2                           # architecture not supported by the kernels
 
 
 def last_error() -> str:
@@ -196,7 +199,9 @@ def last_error() -> str:
 
 def check(rc: int, what: str):
     if rc < 0:
-        raise UkbbFcnError('%s failed (%d): %s' % (what, rc, last_error()))
+        e = UkbbFcnError('%s failed (%d): %s' % (what, rc, last_error()))
+        e.code = int(rc)
+        raise e
     return rc
 
 

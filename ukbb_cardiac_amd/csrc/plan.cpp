@@ -83,10 +83,14 @@ bool supported(const ukbb_fcn_arch &a, std::string &why) {
     if (a.n_level != 5) { why = "n_level must be 5"; return false; }
     if (a.n_filter[0] != 16) { why = "n_filter[0] must be 16"; return false; }
     for (int l = 1; l < a.n_level; ++l)
-        if (a.n_filter[l] % 32) { why = "n_filter[l>0] must be multiples of 32"; return false; }
+        if (a.n_filter[l] < 32 || a.n_filter[l] % 32) { why = "n_filter[l>0] must be multiples of 32"; return false; }
     if (a.kind == UKBB_KIND_FCN) {
         if (a.same_dim != 32 || a.fc != 64) { why = "FCN head kernel is built for same_dim=32, fc=64"; return false; }
         if (a.n_class < 2 || a.n_class > 6) { why = "n_class must be in 2..6"; return false; }
+        for (int l = 1; l < a.n_level; ++l)                  // launch_sqg's instances (kernels_head.hip); sqg_body's load loop covers no other width
+            if (a.n_filter[l] != 32 && a.n_filter[l] != 64 && a.n_filter[l] != 128 && a.n_filter[l] != 256) {
+                why = "FCN squeeze kernels are built for n_filter[l>0] in {32, 64, 128, 256}"; return false;
+            }
     } else {
         if (a.n_class < 2 || a.n_class > 4) { why = "UNet n_class must be in 2..4"; return false; }
         if (a.kind == UKBB_KIND_TEMPORAL_UNET) {

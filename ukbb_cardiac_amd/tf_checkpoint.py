@@ -493,11 +493,31 @@ def infer_arch(reader: CheckpointReader) -> ModelArch:
     return cand
 
 
+def engine_refusal(arch: ModelArch) -> Optional[str]:
+    """The reason ukbb_fcn_create would refuse ``arch`` (plan.cpp supported(), asked through the host-only planner: UKBB_EARCH), or None.  Reading a
+    checkpoint stays pure Python: where the native library is not built this returns None, and Engine refuses the descriptor when it is created."""
+    try:
+        from . import _lib
+        from .engine import plan_layout
+    except (ImportError, OSError):
+        return None
+    try:
+        plan_layout(arch, 'fp32', arch.fc if arch.kind in (KIND_UNET_LSTM, KIND_TEMPORAL_UNET) else 1, 16, 16)
+    except _lib.UkbbFcnError as e:
+        if e.code == _lib.UKBB_EARCH:                        # any other refusal is about the call, not the architecture
+            return _lib.last_error()
+    return None
+
+
 def checkpoint_to_params(prefix: str, arch: Optional[ModelArch] = None, verify_crc: bool = False):
     """-> (arch, params) with params[layer] = {'kernel', 'gamma', 'beta', 'mean', 'var'} / {'kernel', 'bias'}."""
     reader = CheckpointReader(prefix)
     if arch is None:
         arch = infer_arch(reader)
+        if arch.name.endswith('_custom'):                    # not one of MODELS: ask the engine's planner now, not at the first forward
+            why = engine_refusal(arch)
+            if why:
+                raise CheckpointError('%s: the engine does not serve this architecture (%s)' % (prefix, why))
     params = {}
     specs = {s.name: s for s in arch.layer_specs()}
     uni = unidirectional_lstm_variables(reader.names()) if arch.kind == KIND_UNET_LSTM else None
