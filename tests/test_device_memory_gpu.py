@@ -8,12 +8,18 @@ any of that.  Here handles created under UKBB_DEBUG_GUARD=<hex pattern> allocate
 fill a payload with the pattern when it is allocated, and ``Engine.poison(p)`` refills everything the engine rewrites per call:
 
   a. first use of fresh memory: a guarded and a plain handle in one process, every model and precision, ragged shapes -> identical bits;
-  b. small after large on one handle, a tail batch in a kept plan, each pattern -> the bits of a fresh plain handle that ran only that case;
-  c. precision switches on one handle;
-  d. cines (UNet-LSTM whole and in chunks under the minimum scratch budget, Temporal-UNet in chunks of one window and unchunked);
+  b. small after large on one handle, a tail batch in a kept plan, each pattern -> the bits of a fresh plain handle that ran only that case
+     (frame batches, and sequences through run_seq);
+  c. precision switches on one handle, at one shape and with a shape change (bf16 maps take 2 bytes per channel, fp32 maps 4: the stale
+     bytes are of the other element size);
+  d. cines (UNet-LSTM whole and in chunks under the minimum scratch budget, Temporal-UNet fp32 and bf16_3d in chunks of one window,
+     unchunked and under a scratch budget);
   e. the instrument itself: the poison is read back, a damaged guard is reported with buffer and offset;
-  f. caller-owned outputs of the device-pointer forward and of the pre- / post-processing entries, carved from the middle of larger
-     tensors filled with a sentinel: nothing beside an output changes, everything the entry's contract covers is written.
+  f. caller-owned outputs of the device-pointer forwards (frame, sequence, cine) and of the pre- / post-processing entries, carved from
+     the middle of larger tensors filled with a sentinel: nothing beside an output changes, everything the entry's contract covers is written.
+
+A precision is a tag: the names Engine.set_precision takes, and 'f32x3+convs' for 'f32x3' with set_f32x3_convs(True).  The switch is stored
+on the handle and the module's guarded engines are shared, so every tag sets it (_set_precision).
 
 No tolerance anywhere: bits, and guard bytes."""
 import ctypes as C
@@ -28,8 +34,8 @@ pytestmark = pytest.mark.gpu
 
 PATTERNS = ('7FC07FC0', 'FFFFFFFF', '7F800000')                   # bf16 NaN pairs, all ones, fp32 +inf (as tests/test_concurrency_gpu.py)
 FRAME_MODELS = ['FCN_sa', 'FCN_la_2ch', 'FCN_la_4ch', 'FCN_la_4ch_seg4', 'UNet_ao']
-PRECISIONS = {m: ('fp32', 'bf16', 'f32x3') for m in FRAME_MODELS + ['UNet-LSTM_ao']}
-PRECISIONS['Temporal-UNet_ao'] = ('fp32', 'f32x3')                # its 3-D convolutions have no bf16 plan
+PRECISIONS = {m: ('fp32', 'bf16', 'f32x3') + (('f32x3+convs', 'bf16_store', 'bf16_full') if m.startswith('FCN') else ()) for m in FRAME_MODELS + ['UNet-LSTM_ao']}
+PRECISIONS['Temporal-UNet_ao'] = ('fp32', 'f32x3', 'bf16_3d')
 # ascending in pixels, so that the staging buffers of a handle are re-allocated (fresh, poisoned) by every case; 16 and 17 images of
 # 64 x 96 lie on either side of the planner's small-batch threshold (plan.h, SMALL_BATCH = 16), and 16 comes first: a handle leaves the
 # small-batch plans for good with the first larger batch it sees
@@ -80,6 +86,13 @@ def _image(shape):
     return rng.standard_normal(shape).astype(np.float32)
 
 
+def _set_precision(eng, tag):
+    from ukbb_cardiac_amd.arch import KIND_FCN
+    eng.set_precision(tag.split('+')[0])
+    if eng.arch.kind == KIND_FCN:                                  # (the other kinds refuse the switch)
+        eng.set_f32x3_convs(tag.endswith('+convs'))
+
+
 def _run(eng, shape):
     img = _image(shape)
     return eng.run_seq(img, want_logits=True) if len(shape) == 4 else eng.run(img, want_logits=True)
@@ -103,7 +116,7 @@ def _fresh_plain(model, prec, shape):
     key = (model, prec, shape)
     if key not in _REF:
         with _engine(model) as eng:
-            eng.set_precision(prec)
+            _set_precision(eng, prec)
             out = _run(eng, shape)
         for v in out.values():
             v.setflags(write=False)
@@ -122,7 +135,7 @@ def test_first_use_of_fresh_memory(model, prec):
         with pytest.raises(Exception, match='UKBB_DEBUG_GUARD'):
             p.check_guards()                                       # the plain handle really is plain
         for eng in (g, p):
-            eng.set_precision(prec)
+            _set_precision(eng, prec)
         for shape in shapes:
             got, want = _run(g, shape), _run(p, shape)
             _same_bits(got, want, (model, prec, shape))
@@ -144,14 +157,33 @@ def test_first_use_of_fresh_memory(model, prec):
 def test_small_after_large_on_one_handle(guarded, model, prec, pattern):
     """17 images of 272 x 304, then -- a poison in front of each -- a tail batch in the kept plan, a small ragged shape, a smaller batch of
     it (plan kept: the tail of every map is stale), the smallest shape.  Each equals a fresh plain handle that ran only that case."""
-    eng = guarded(model)
-    eng.set_precision(prec)
-    for i, shape in enumerate([LARGE, (5,) + LARGE[1:], (3, 80, 112), (2, 80, 112), (1, 16, 16)]):
+    _small_after_large(guarded(model), model, prec, pattern, [LARGE, (5,) + LARGE[1:], (3, 80, 112), (2, 80, 112), (1, 16, 16)])
+
+
+def _small_after_large(eng, model, prec, pattern, shapes):
+    _set_precision(eng, prec)
+    for i, shape in enumerate(shapes):
         if i:
             assert eng.poison(pattern) > 10
         got = _run(eng, shape)
         _same_bits(got, _fresh_plain(model, prec, shape), (model, prec, pattern, shape))
         _guards_intact(eng, (model, prec, pattern, shape))
+
+
+@pytest.mark.parametrize('pattern', PATTERNS)
+@pytest.mark.parametrize('prec', ['f32x3+convs', 'bf16_store', 'bf16_full'])
+@pytest.mark.parametrize('model', ['FCN_sa', 'FCN_la_4ch_seg4'])
+def test_small_after_large_on_one_handle_newer_precisions(guarded, model, prec, pattern):
+    """The same sequence under the conv stack on three bf16 pieces and under bf16 maps in HBM (half the bytes per channel)."""
+    _small_after_large(guarded(model), model, prec, pattern, [LARGE, (5,) + LARGE[1:], (3, 80, 112), (2, 80, 112), (1, 16, 16)])
+
+
+@pytest.mark.parametrize('pattern', PATTERNS)
+@pytest.mark.parametrize('model,prec', [('UNet-LSTM_ao', 'fp32'), ('UNet-LSTM_ao', 'bf16'), ('Temporal-UNet_ao', 'fp32'), ('Temporal-UNet_ao', 'bf16_3d')])
+def test_small_after_large_sequences_on_one_handle(guarded, model, prec, pattern):
+    """run_seq: two windows of 48 x 80, one window in the kept plan (the second window's half of every map, of the ConvLSTM working
+    buffers too, is stale), one window of a smaller shape."""
+    _small_after_large(guarded(model), model, prec, pattern, [(2, 9, 48, 80), (1, 9, 48, 80), (1, 9, 32, 48)])
 
 
 # ---- c. precision switches --------------------------------------------------------------------------------------------------------
@@ -163,17 +195,33 @@ def test_precision_switches_on_one_handle(guarded, model, other, shape):
     for i, prec in enumerate(('fp32', other, 'fp32')):
         if i:
             eng.poison(PATTERNS[i])
-        eng.set_precision(prec)
+        _set_precision(eng, prec)
         outs.append(_run(eng, shape))
         _guards_intact(eng, (model, prec, i))
     _same_bits(outs[2], outs[0], (model, 'fp32 again'))
     with _engine(model, PATTERNS[0]) as fresh:
-        fresh.set_precision(other)
+        _set_precision(fresh, other)
         want = _run(fresh, shape)
         _guards_intact(fresh, (model, other, 'fresh'))
     _same_bits(outs[1], want, (model, other))
     if other == 'bf16':
         assert outs[1]['logits'].tobytes() != outs[0]['logits'].tobytes()  # the other precision really ran
+
+
+@pytest.mark.parametrize('model,steps', [
+    ('FCN_sa', [('fp32', (6, 128, 144)), ('bf16_store', (3, 80, 112)), ('f32x3+convs', (2, 80, 112)), ('bf16_full', (1, 16, 16)), ('fp32', (3, 80, 112))]),
+    ('Temporal-UNet_ao', [('fp32', (2, 9, 48, 80)), ('bf16_3d', (1, 9, 32, 48)), ('fp32', (1, 9, 32, 48))])])
+def test_precision_switches_with_a_shape_change(guarded, model, steps):
+    """Each step under another precision AND another shape than the one before it, a poison in front of each: what the maps hold from
+    the previous step is of the other element size and of another geometry.  Each equals a fresh plain handle that ran only that case."""
+    eng = guarded(model)
+    for i, (prec, shape) in enumerate(steps):
+        eng.poison(PATTERNS[i % len(PATTERNS)])
+        _set_precision(eng, prec)
+        got = _run(eng, shape)
+        _same_bits(got, _fresh_plain(model, prec, shape), (model, i, prec, shape))
+        _guards_intact(eng, (model, i, prec, shape))
+        assert np.isfinite(got['logits']).all() and got['logits'].std() > 0
 
 
 # ---- d. cines ------------------------------------------------------------------------------------------------------------------------
@@ -189,7 +237,7 @@ def _lstm_cines(eng, prec, pattern=None):
     them poisoned with ``pattern``."""
     from ukbb_cardiac_amd import engine
     out = []
-    eng.set_precision(prec)
+    _set_precision(eng, prec)
     for F, ts in ((13, 1), (13, 2), (5, 1)):
         frames = _image((F, 48, 64))
         low = engine.cine_min_scratch_bytes(eng.arch, prec, F, 48, 64, ts)
@@ -228,19 +276,58 @@ def test_unet_lstm_cines(guarded, prec, pattern):
 def test_temporal_unet_cines(guarded, pattern, monkeypatch):
     frames = _image((13, 32, 48))
     eng = guarded('Temporal-UNet_ao')
-    eng.set_precision('fp32')
     with _engine('Temporal-UNet_ao') as plain:
-        for chunk in ('1', None):
-            if chunk is None:
-                monkeypatch.delenv('UKBB_TEMPORAL_CHUNK_WINDOWS', raising=False)
-            else:
-                monkeypatch.setenv('UKBB_TEMPORAL_CHUNK_WINDOWS', chunk)
-            want = plain.run_cine(frames)
+        for prec in ('fp32', 'bf16_3d'):
+            for e in (eng, plain):
+                _set_precision(e, prec)
+            for chunk in ('1', None):
+                if chunk is None:
+                    monkeypatch.delenv('UKBB_TEMPORAL_CHUNK_WINDOWS', raising=False)
+                else:
+                    monkeypatch.setenv('UKBB_TEMPORAL_CHUNK_WINDOWS', chunk)
+                want = plain.run_cine(frames)
+                eng.poison(pattern)
+                got = eng.run_cine(frames)
+                _same_cine(got, want, (prec, pattern, chunk))
+                _guards_intact(eng, (prec, pattern, chunk))
+                assert np.isfinite(got[0]).all() and got[0].std() > 0
+
+
+def _plain_cine(model, prec, F, H, W, ts):
+    """What a fresh plain handle returns for the cine, whole (computed once, shared, never modified)."""
+    key = (model, prec, F, H, W, ts)
+    if key not in _CINE_REF:
+        with _engine(model) as plain:
+            _set_precision(plain, prec)
+            _CINE_REF[key] = plain.run_cine(_image((F, H, W)), time_step=ts)
+        for v in _CINE_REF[key]:
+            v.setflags(write=False)
+    return _CINE_REF[key]
+
+
+@pytest.mark.parametrize('pattern', PATTERNS)
+@pytest.mark.parametrize('prec', ['fp32', 'bf16_3d'])
+def test_temporal_unet_cines_under_a_scratch_budget(guarded, prec, pattern, monkeypatch):
+    """A third of what the unchunked cine takes: chunks of several windows sized by the budget.  Twice -- the first call allocates the
+    released buffers, the second finds them poisoned."""
+    from ukbb_cardiac_amd import engine
+    monkeypatch.delenv('UKBB_TEMPORAL_CHUNK_WINDOWS', raising=False)
+    F, H, W = 13, 32, 48
+    eng = guarded('Temporal-UNet_ao')
+    _set_precision(eng, prec)
+    budget = engine.cine_scratch_bytes(eng.arch, prec, F, H, W, 1) // 3
+    assert 1 <= engine.cine_chunk_windows(eng.arch, prec, F, H, W, 1, budget) < F        # accepted, and really chunked
+    want = _plain_cine('Temporal-UNet_ao', prec, F, H, W, 1)
+    eng.set_scratch_budget(budget)
+    try:
+        for call in range(2):
             eng.poison(pattern)
-            got = eng.run_cine(frames)
-            _same_cine(got, want, (pattern, chunk))
-            _guards_intact(eng, (pattern, chunk))
-            assert np.isfinite(got[0]).all() and got[0].std() > 0
+            got = eng.run_cine(_image((F, H, W)))
+            _same_cine(got, want, (prec, pattern, call))
+            _guards_intact(eng, (prec, pattern, call))
+            assert 0 < eng.scratch_bytes() <= budget
+    finally:
+        eng.set_scratch_budget(0)
 
 
 # ---- e. the instrument works ----------------------------------------------------------------------------------------------------------
@@ -489,11 +576,12 @@ def test_prep_entries_write_their_outputs_and_nothing_else(shape, order, dtype):
         labels.untouched('the labels')
 
 
-@pytest.mark.parametrize('model,prec', [('FCN_sa', 'fp32'), ('FCN_sa', 'bf16'), ('FCN_sa', 'f32x3'), ('FCN_la_4ch_seg4', 'fp32'), ('UNet_ao', 'fp32'), ('UNet_ao', 'bf16')])
+@pytest.mark.parametrize('model,prec', [('FCN_sa', 'fp32'), ('FCN_sa', 'bf16'), ('FCN_sa', 'f32x3'), ('FCN_la_4ch_seg4', 'fp32'), ('UNet_ao', 'fp32'), ('UNet_ao', 'bf16'),
+                                        ('FCN_sa', 'bf16_store'), ('FCN_sa', 'bf16_full'), ('FCN_la_4ch_seg4', 'bf16_full'), ('FCN_sa', 'f32x3+convs')])
 def test_device_pointer_forward_writes_only_the_callers_outputs(guarded, model, prec):
     """ukbb_fcn_forward with the image between NaNs and logits / prob / pred each between sentinels: the bits of the host-array call."""
     eng = guarded(model)
-    eng.set_precision(prec)
+    _set_precision(eng, prec)
     ncls = eng.arch.n_class
     for shape in [(3, 80, 112), (1, 16, 16), (2, 48, 400)]:
         n, h, w = shape
@@ -510,3 +598,123 @@ def test_device_pointer_forward_writes_only_the_callers_outputs(guarded, model, 
             assert np.array_equal(pd.read(what + ('pred',)), _bytes(want['pred'])), what
             x.untouched(what + ('image',))
             _guards_intact(eng, what)
+
+
+SEQ_MODELS = [('UNet-LSTM_ao', 'fp32'), ('UNet-LSTM_ao', 'bf16'), ('Temporal-UNet_ao', 'fp32'), ('Temporal-UNet_ao', 'bf16_3d')]
+
+
+@pytest.mark.parametrize('model,prec', SEQ_MODELS)
+def test_forward_seq_writes_only_the_callers_outputs(guarded, model, prec):
+    """ukbb_fcn_forward_seq on carved pointers: all three outputs, then logits = NULL, then prob alone.  A NULL output has no region;
+    every region passed holds the bits a fresh plain handle returns, under both sentinels; the frames stay untouched."""
+    eng = guarded(model)
+    _set_precision(eng, prec)
+    shape = (2, 9, 32, 48)
+    n, t, h, w = shape
+    assert t == eng.arch.n_step
+    ncls = eng.arch.n_class
+    img = _image(shape)
+    want = _fresh_plain(model, prec, shape)
+    size = {'logits': img.nbytes * ncls, 'prob': img.nbytes * ncls, 'pred': img.nbytes}
+    for s in SENTINELS:
+        for outputs in (('logits', 'prob', 'pred'), ('prob', 'pred'), ('prob',)):
+            eng.poison(PATTERNS[0])
+            x = Carved(img.nbytes, 'nan', img)
+            out = {k: Carved(size[k], s) for k in outputs}
+            eng.run_seq_device(x.ptr, n, h, w, stream=0, **{k + '_ptr': r.ptr for k, r in out.items()})
+            what = (model, prec, s, outputs)
+            for k, r in out.items():
+                assert np.array_equal(r.read(what + (k,)), _bytes(want[k])), what + (k,)
+            x.untouched(what + ('frames',))
+            _guards_intact(eng, what)
+
+
+@pytest.mark.parametrize('model,prec', SEQ_MODELS)
+def test_forward_cine_writes_only_the_callers_outputs(guarded, model, prec, monkeypatch):
+    """ukbb_fcn_forward_cine on carved pointers, the bits of Engine.run_cine on a fresh plain handle: 13 frames whole, in chunks (the
+    UNet-LSTM under its minimum scratch budget, the Temporal-UNet one window at a time), with pred = NULL, and 12 frames at time_step 10,
+    where frame 5 lies in neither window: its prob must be WRITTEN as NaN and its pred as 0, whatever the regions held."""
+    from ukbb_cardiac_amd import engine
+    monkeypatch.delenv('UKBB_TEMPORAL_CHUNK_WINDOWS', raising=False)
+    eng = guarded(model)
+    _set_precision(eng, prec)
+    lstm = model.startswith('UNet-LSTM')
+    H, W, ncls, T = 32, 48, eng.arch.n_class, eng.arch.n_step
+    low = engine.cine_min_scratch_bytes(eng.arch, prec, 13, H, W, 1) if lstm else 0
+    if lstm:
+        assert low > 0 and 0 < engine.cine_chunk_windows(eng.arch, prec, 13, H, W, 1, low) < 13         # really chunked
+    unreached = sorted(set(range(12)) - {(c - (T - 1) // 2 + k) % 12 for c in range(0, 12, 10) for k in range(T)})
+    assert unreached == [5]
+    try:
+        for F, ts, chunked, with_pred in ((13, 1, False, True), (13, 1, True, True), (12, 10, False, True), (13, 1, False, False)):
+            frames = _image((F, H, W))
+            want = _plain_cine(model, prec, F, H, W, ts)
+            eng.set_scratch_budget(low if chunked and lstm else 0)
+            if chunked and not lstm:
+                monkeypatch.setenv('UKBB_TEMPORAL_CHUNK_WINDOWS', '1')
+            else:
+                monkeypatch.delenv('UKBB_TEMPORAL_CHUNK_WINDOWS', raising=False)
+            for s in SENTINELS:
+                eng.poison(PATTERNS[0])
+                x = Carved(frames.nbytes, 'nan', frames)
+                pr, pd = Carved(frames.nbytes * ncls, s), Carved(frames.nbytes, s) if with_pred else None
+                eng.run_cine_device(x.ptr, F, H, W, pr.ptr, pd.ptr if pd else 0, time_step=ts, stream=0)
+                what = (model, prec, F, ts, chunked, with_pred, s)
+                got_prob = pr.read(what + ('prob',))
+                assert np.array_equal(got_prob, _bytes(want[0])), what
+                if pd:
+                    got_pred = pd.read(what + ('pred',))
+                    assert np.array_equal(got_pred, _bytes(want[1])), what
+                if ts == 10:
+                    assert np.isnan(got_prob.view(np.float32).reshape(F, H, W, ncls)[unreached]).all(), what
+                    assert not got_pred.view(np.int32).reshape(F, H, W)[unreached].any(), what
+                    assert np.isfinite(np.delete(want[0], unreached, axis=0)).all()
+                else:
+                    assert np.isfinite(want[0]).all() and want[0].std() > 0
+                x.untouched(what + ('frames',))
+                _guards_intact(eng, what)
+    finally:
+        eng.set_scratch_budget(0)
+
+
+def _blobs(shape, n_class, seed):
+    """A label volume (uint8, NIfTI order) of blocks of 1 .. 6 voxels a side with single voxels flipped: components of every size,
+    many around the default threshold, some that join only through a diagonal neighbour or across z."""
+    X, Y, Z, T = shape
+    rng = np.random.default_rng(seed)
+    lab = np.zeros(shape, np.uint8)
+    for t in range(T):
+        for z in range(Z):
+            b = int(rng.integers(1, 7))
+            coarse = rng.integers(0, n_class, size=(-(-X // b), -(-Y // b))).astype(np.uint8)
+            lab[:, :, z, t] = np.kron(coarse, np.ones((b, b), np.uint8))[:X, :Y]
+    flip = rng.random(shape) < 0.05
+    lab[flip] = rng.integers(0, n_class, size=int(flip.sum())).astype(np.uint8)
+    return np.asfortranarray(lab)
+
+
+@pytest.mark.parametrize('shape', [(37, 29, 1, 7), (65, 33, 2, 3)])
+def test_label_components_writes_its_outputs_and_nothing_else(shape):
+    """ukbb_fcn_label_components on carved pointers: the labels lie between bytes of label value 1 (a read beside the volume would
+    join a component), d_work is exactly the 2*X*Y*Z*T int32 the contract asks for, d_n_large exactly T x n_class int32.  Against
+    aorta_qc.count_large_components for min_size 0 and the default; a second call on the same, now dirty, d_work gives the same."""
+    from ukbb_cardiac_amd import _lib, aorta_qc
+    X, Y, Z, T = shape
+    n_class = 3
+    seg = _blobs(shape, n_class, X + Y)
+    for min_size in (0, aorta_qc.PIXEL_THRES):
+        want = aorta_qc.count_large_components(seg, n_class, min_size)
+        assert want.dtype == np.int32 and want.shape == (T, n_class) and not want[:, 0].any()
+        assert (want[:, 1:] > 0).any() and len(np.unique(want[:, 1:])) > 2                       # a grading signal
+        for s in SENTINELS:
+            labels = Carved(seg.nbytes, 0x01, seg)
+            work = Carved(4 * 2 * X * Y * Z * T, s)
+            for call in range(2):
+                out = Carved(want.nbytes, s)
+                _lib.check(_lib.lib.ukbb_fcn_label_components(labels.ptr, X, Y, Z, T, n_class, min_size, work.ptr, out.ptr, 0), 'label_components')
+                what = (shape, min_size, s, call)
+                got = out.read(what + ('n_large',)).view(np.int32).reshape(T, n_class)
+                assert np.array_equal(got, want), what
+                work.read(what + ('work',))                                                      # nothing beside d_work changed
+                labels.untouched(what + ('labels',))
+    assert not np.array_equal(aorta_qc.count_large_components(seg, n_class, 0), aorta_qc.count_large_components(seg, n_class))

@@ -178,6 +178,7 @@ def _load():
     lib.ukbb_fcn_debug_guard_info.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.ukbb_fcn_debug_poison.argtypes = [vp, C.c_uint32]
     lib.ukbb_fcn_debug_damage_guard.argtypes = [vp, C.c_char_p, C.c_longlong]
+    lib.ukbb_fcn_debug_launch_counts.argtypes = [vp, C.POINTER(C.c_uint64 * 2)]     # launches, LDS poisons (UKBB_DEBUG_POISON_LDS)
     if lib.ukbb_fcn_abi_version() != ABI_VERSION:
         raise ImportError('libukbb_fcn.so ABI %d != binding ABI %d: rebuild' % (lib.ukbb_fcn_abi_version(), ABI_VERSION))
     return lib

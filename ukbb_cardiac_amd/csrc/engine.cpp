@@ -207,6 +207,11 @@ struct ukbb_fcn_handle {
     hipEvent_t ev_split_fork = nullptr, ev_split_join = nullptr;
     std::vector<hipEvent_t> ev_fork, ev_join;
 
+    // UKBB_DEBUG_POISON_LDS (debugging aid): read once per API call (lds_poison_begin), consulted in front of every launch (announce_launch)
+    bool lds_poison_on = false;
+    uint32_t lds_poison_pat = 0;
+    uint64_t n_launches = 0, n_lds_poisons = 0;   // since the handle was created (ukbb_fcn_debug_launch_counts)
+
     // timing
     bool timing = false;
     int timing_only = -1;                     // -1: every kernel; else only this op index
@@ -602,6 +607,20 @@ int collect_events(ukbb_fcn_handle *h) {
 // what a forward reads and writes besides the workspace: the caller's device pointers (an output may be NULL)
 struct PlanIo { const float *image; float *logits, *prob; int32_t *pred; };
 
+// UKBB_DEBUG_POISON_LDS=<hex pattern>: every CU's LDS is filled with the pattern in front of EVERY launch the handle makes -- a kernel that
+// reads LDS it never wrote now reads this pattern.  The API entries read the variable (once per call); every launch site of the handle
+// (launch_op, the ConvLSTM x pass and time steps, lstm_out, lstm_tile, t3d_tile) announces its launch and the stream it goes to here.
+void lds_poison_begin(ukbb_fcn_handle *h) {
+    const char *env = getenv("UKBB_DEBUG_POISON_LDS");
+    h->lds_poison_on = env != nullptr;
+    h->lds_poison_pat = env ? (uint32_t)strtoul(env, nullptr, 16) : 0u;
+}
+
+void announce_launch(ukbb_fcn_handle *h, hipStream_t s) {
+    ++h->n_launches;
+    if (h->lds_poison_on && ukbb_fcn_debug_poison_lds(h->lds_poison_pat, s) == UKBB_OK) ++h->n_lds_poisons;
+}
+
 // One launch of `op` over images [n0, n0 + n) of the batch on stream s (the whole batch everywhere except inside a split range of run_plan).
 int launch_op(ukbb_fcn_handle *h, const BoundOp &op, const PlanIo &io, int n0, int n, hipStream_t s, hipError_t &e) {
     const ukbb_fcn_arch &a = h->arch;
@@ -619,6 +638,7 @@ int launch_op(ukbb_fcn_handle *h, const BoundOp &op, const PlanIo &io, int n0, i
         return sa;
     };
     e = hipSuccess;
+    announce_launch(h, s);
     switch (op.kind) {
         case OP_FIRST: e = launch_first(FirstArgs{io.image, op.wpk, op.bias, actp(op.out), n, op.H, op.W, L.cout, bfio}, s); break;
         case OP_CONV:
@@ -747,11 +767,8 @@ int run_plan(ukbb_fcn_handle *h, const float *image, int n, float *logits, float
     const int sp0 = h->plan.split_first, sp1 = h->plan.split_last;
     // debugging aids (r06, tools/two_stream_bisect.py): run only the ops [first, last] of the plan (whatever they read was left by an earlier full forward)
     const int dbg_first = h->plan.debug_first_op, dbg_last = h->plan.debug_last_op;
-    const char *poison_env = getenv("UKBB_DEBUG_POISON_LDS");            // hex pattern written to every CU's LDS in front of every launch
-    const bool poison_on = poison_env != nullptr;
     const bool fence_on = getenv("UKBB_DEBUG_FENCE_KERNEL") != nullptr;
     const bool sync_on = getenv("UKBB_DEBUG_SYNC_EVERY_OP") != nullptr;
-    const uint32_t poison_pat = poison_on ? (uint32_t)strtoul(poison_env, nullptr, 16) : 0u;
     for (size_t i = 0; i < h->ops.size(); ++i) {
         const BoundOp &op = h->ops[i];
         s = s_main;
@@ -798,7 +815,6 @@ int run_plan(ukbb_fcn_handle *h, const float *image, int n, float *logits, float
         const bool timed = h->timing && (h->timing_only < 0 || h->timing_only == (int)i);
         if (timed) HIP_TRY(hipEventRecord(h->ev[2 * i], s), UKBB_EDEVICE);
         hipError_t e = hipSuccess;
-        if (poison_on) (void)ukbb_fcn_debug_poison_lds(poison_pat, s);      // debugging aid: a kernel that reads LDS it never wrote now reads this pattern
         {
             const int rc = launch_op(h, op, io, 0, n, s, e);
             if (rc) return rc;
@@ -917,6 +933,15 @@ int ukbb_fcn_debug_poison(ukbb_fcn_handle *h, uint32_t pattern) {
     }
     HIP_TRY(hipDeviceSynchronize(), UKBB_EDEVICE);
     return nb;
+}
+
+// Launches the handle has made since it was created (out[0]: the plan's ops, a split op counting twice; the ConvLSTM x pass and time steps;
+// lstm_out, lstm_tile, t3d_tile) and the LDS poison launches issued in front of them under UKBB_DEBUG_POISON_LDS (out[1]): a call that
+// ran with the variable set advances both by the same number.
+int ukbb_fcn_debug_launch_counts(ukbb_fcn_handle *h, uint64_t out[2]) {
+    if (!h || !out) { set_error("debug_launch_counts: NULL argument"); return UKBB_EINVAL; }
+    out[0] = h->n_launches; out[1] = h->n_lds_poisons;
+    return UKBB_OK;
 }
 
 // Writes one byte that differs from the guard's into a guard of `buffer` (a name as debug_check_guards reports it), `offset` bytes from the
@@ -1145,6 +1170,7 @@ int ukbb_fcn_reserve(ukbb_fcn_handle *h, int n, int height, int width) {
 int ukbb_fcn_forward(ukbb_fcn_handle *h, const float *image, int n, int height, int width,
                      float *logits, float *prob, int32_t *pred, void *stream) {
     if (!h || !image) { set_error("forward: NULL argument"); return UKBB_EINVAL; }
+    lds_poison_begin(h);
     int rc = refuse_sequence_kinds(h, "forward");
     if (!rc) rc = prepare(h, n, height, width);
     if (rc) return rc;
@@ -1154,6 +1180,7 @@ int ukbb_fcn_forward(ukbb_fcn_handle *h, const float *image, int n, int height, 
 int ukbb_fcn_forward_host(ukbb_fcn_handle *h, const float *image, int n, int height, int width,
                           float *logits, float *prob, int32_t *pred) {
     if (!h || !image) { set_error("forward_host: NULL argument"); return UKBB_EINVAL; }
+    lds_poison_begin(h);
     int rc = refuse_sequence_kinds(h, "forward_host");
     if (!rc) rc = prepare(h, n, height, width);
     if (rc) return rc;
@@ -1289,6 +1316,7 @@ int run_bilstm(ukbb_fcn_handle *h, const float *feat, int NF, const int *d_map, 
         ca.wpk = P.lstm[wsf].wx; ca.bias = P.lstm[wsf].bx;
         ca.ls_mode = 1; ca.ls_gx = unhoist ? nullptr : h->lstm_gx.p; ca.ls_c_out = h->lstm_c1.p; ca.out = h->lstm_h1.p;
         ca.ls_gx_dir = (long long)NF * gxf; ca.ls_c_dir = (long long)NF * cf; ca.ls_h_dir = (long long)NF * HW * NHID;
+        announce_launch(h, s);
         hipError_t e = wsf ? launch_lstm_ws(ca, s) : launch_wino24_lstm(ca, tc, s);
         if (e != hipSuccess) { set_error("ConvLSTM x-pass launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
     }
@@ -1323,6 +1351,7 @@ int run_bilstm(ukbb_fcn_handle *h, const float *feat, int NF, const int *d_map, 
             }
             ca.ls_c_out = h->lstm_c.p;
             ca.out = at(hall, (size_t)k * kst, esz);
+            announce_launch(h, s);
             hipError_t e = wsf ? launch_lstm_ws(ca, s) : launch_wino24_lstm(ca, tc, s);
             if (e != hipSuccess) { set_error("ConvLSTM step launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
         }
@@ -1458,6 +1487,7 @@ int t3d_forward_cine(ukbb_fcn_handle *h, const float *image, int F, int height, 
         ta.prob = prob; ta.pred = pred;
         ta.HW = (int)HW; ta.C = C; ta.w0 = w0; ta.w1 = w0 + nw;
         ta.first = w0 == 0; ta.last = w0 + nw == Wn;
+        announce_launch(h, s);
         hipError_t e = launch_t3d_tile(ta, s);
         if (e != hipSuccess) { set_error("tiling kernel launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
     }
@@ -1474,6 +1504,7 @@ int lstm_common_checks(ukbb_fcn_handle *h, const float *image, const char *what)
 
 int ukbb_fcn_forward_seq(ukbb_fcn_handle *h, const float *image, int n_seq, int height, int width,
                          float *logits, float *prob, int32_t *pred, void *stream) {
+    if (h) lds_poison_begin(h);
     if (h && image && h->arch.kind == UKBB_KIND_TEMPORAL_UNET)
         return t3d_forward_seq(h, image, n_seq, height, width, logits, prob, pred, static_cast<hipStream_t>(stream));
     int rc = lstm_common_checks(h, image, "forward_seq");
@@ -1520,6 +1551,7 @@ int ukbb_fcn_forward_seq(ukbb_fcn_handle *h, const float *image, int n_seq, int 
         oa.logits = logits ? logits + (size_t)k * HW * C : nullptr;
         oa.pred = pred ? pred + (size_t)k * HW : nullptr;
         oa.m_stride = (long long)T * HW * C; oa.M = n_seq; oa.HW = (int)HW; oa.n_class = C;
+        announce_launch(h, s);
         hipError_t e = launch_lstm_out(oa, s);
         if (e != hipSuccess) { set_error("ConvLSTM output kernel launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
     }
@@ -1528,6 +1560,7 @@ int ukbb_fcn_forward_seq(ukbb_fcn_handle *h, const float *image, int n_seq, int 
 
 int ukbb_fcn_forward_cine(ukbb_fcn_handle *h, const float *image, int n_frames, int height, int width,
                           int weight_R, double weight_r, int time_step, float *prob, int32_t *pred, void *stream) {
+    if (h) lds_poison_begin(h);
     if (h && image && h->arch.kind == UKBB_KIND_TEMPORAL_UNET)
         return t3d_forward_cine(h, image, n_frames, height, width, weight_R, weight_r, time_step, prob, pred, static_cast<hipStream_t>(stream));
     int rc = lstm_common_checks(h, image, "forward_cine");
@@ -1616,6 +1649,7 @@ int ukbb_fcn_forward_cine(ukbb_fcn_handle *h, const float *image, int n_frames, 
         ta.tb = aux.tb;
         ta.prob = prob; ta.pred = pred; ta.Wn = nw; ta.HW = (int)HW; ta.C = C;
         ta.w0 = w0; ta.w1 = w0 + nw; ta.first = w0 == 0; ta.last = w0 + nw == Wn;
+        announce_launch(h, s);
         hipError_t e = launch_lstm_tile(ta, s);
         if (e != hipSuccess) { set_error("tiling kernel launch failed: %s", hipGetErrorString(e)); return UKBB_EDEVICE; }
     }

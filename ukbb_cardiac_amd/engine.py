@@ -123,6 +123,13 @@ class Engine:
             out['pred'] = pd.cpu().numpy()
         return out
 
+    def run_seq_device(self, image_ptr: int, n: int, h: int, w: int, logits_ptr: int = 0, prob_ptr: int = 0, pred_ptr: int = 0, stream: int = 0):
+        """``run_seq`` on device pointers (image [N,T,H,W] float32; logits / prob [N,T,H,W,C] float32, pred [N,T,H,W] int32, each
+        optional), asynchronous on ``stream``."""
+        rc = _lib.lib.ukbb_fcn_forward_seq(self._h, C.c_void_p(image_ptr), int(n), int(h), int(w), C.c_void_p(logits_ptr or None),
+                                           C.c_void_p(prob_ptr or None), C.c_void_p(pred_ptr or None), C.c_void_p(stream or None))
+        _lib.check(rc, 'ukbb_fcn_forward_seq')
+
     def run_cine(self, frames: np.ndarray, weight_R: int = 5, weight_r: float = 0.1, time_step: int = 1):
         """One slice position of the 'UNet-LSTM' / 'Temporal-UNet' branch of common/deploy_network_ao.py:129-183,189: frames
         float32 [F,H,W] (normalised, padded) -> (prob [F,H,W,C] float32, pred [F,H,W] int32), circular windows centred
@@ -203,6 +210,14 @@ class Engine:
         """Write one byte into a guard of ``buffer`` (a name as ``check_guards`` reports it) at ``offset`` bytes from its payload's
         start -- inside the buffer's own allocation; shows that ``check_guards`` sees damage."""
         _lib.check(_lib.lib.ukbb_fcn_debug_damage_guard(self._h, buffer.encode(), int(offset)), 'ukbb_fcn_debug_damage_guard')
+
+    def launch_counts(self):
+        """``(launches, lds_poisons)`` since the handle was created: every kernel launch a forward of this handle made (a plan op
+        that ran as two half-batch launches counts twice; the ConvLSTM, output and tiling launches count too) and the LDS poison
+        launches issued in front of them under ``UKBB_DEBUG_POISON_LDS`` -- a call with the variable set advances both alike."""
+        out = (C.c_uint64 * 2)()
+        _lib.check(_lib.lib.ukbb_fcn_debug_launch_counts(self._h, C.byref(out)), 'ukbb_fcn_debug_launch_counts')
+        return int(out[0]), int(out[1])
 
     # -- measurement -----------------------------------------------------------
     def kernel_names(self):
