@@ -4,7 +4,7 @@ the head's bf16 weight blocks, and that the head's grade (tests/fcn_bf16_full_gr
 Plan: bf16_store's, op for op, tiling for tiling and map for map, plus the head flag (plan_layout's 'head_bf16'); every other precision keeps the flag
 off.  The U-Net, UNet-LSTM and Temporal-UNet kinds refuse the code with UKBB_EARCH.
 
-Packer: ukbb_fcn_debug_pack_head_bf16 (pack_head_bf16 of kernels_head.hip, host arithmetic only) against a numpy restatement of the A-fragment order of
+Packer: ukbb_fcn_debug_pack_head_bf16 (pack_head_bf16 of pack.cpp, host arithmetic only) against a numpy restatement of the A-fragment order of
 v_mfma_f32_32x32x16_bf16 -- lane (m = lane & 31, g = lane >> 5) holds A[row m][k = 8 g + e], e = 0..7, two bf16 per dword, low half first -- with
 same_dim0's k in the order of the stored conv0 half-block and out0's / out1's k in the order the registers of a 32 x 32 accumulator tile supply it
 (register r of lane half g = row (r & 3) + 8 (r >> 2) + 4 g), every weight rounded to bf16 once, ties to even.

@@ -50,7 +50,7 @@ def test_launcher_constants_are_the_ones_assumed():
     assert 'tile_cols == 32 ? launch_wino24_lstm_t<2, 2, false>(a, s) : launch_wino24_lstm_t<1, 2, false>(a, s)' in w24
     assert int(re.search(r'constexpr int WS_TW = (\d+);', ws).group(1)) == G.WS_TW
     assert tuple(map(int, re.search(r'constexpr int LSW_R = (\d+), LSW_NW = (\d+);', ws).groups())) == (G.WS_R, G.WS_NW)
-    lw = ws[ws.index('hipError_t launch_lstm_ws('):ws.index('size_t pack_lstm_gate_weights_bf16_xh(')]
+    lw = ws[ws.index('hipError_t launch_lstm_ws('):ws.index('hipError_t launch_conv_ws(')]
     assert 'a.xcd_local = force ? atoi(force) : ((long long)a.H * a.W >= 128ll * 128);' in lw
     assert 'long long want = ((ntiles + LSW_NW - 1) / LSW_NW) * nG;' in lw and 'const int nG = a.Cout / 64;' in lw
     assert 'int grid = cus >= 8 * nG ? cus / (8 * nG) * (8 * nG) : cus / nG * nG;' in lw and 'if (want < grid) grid = (int)((want + nG - 1) / nG * nG);' in lw

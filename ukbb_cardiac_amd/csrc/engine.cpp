@@ -6,6 +6,7 @@
 // common/deploy_network.py:44-49 and the sess.run call at :110-111.
 #include "../../include/ukbb_fcn.h"
 #include "kernels.h"
+#include "pack.h"
 #include "plan.h"
 
 #include <algorithm>
@@ -314,7 +315,7 @@ int ensure_packed(ukbb_fcn_handle *h, int layer, const ConvConfig &c, const floa
     return rc ? rc : find_param(h, L.name + (coutp != L.cout ? "/bias_pad" : "/bias"), L.name, bias);
 }
 
-// conv2d_transpose 3x3 s2 + BN + ReLU as a 2x2 sub-pixel conv (kernels.h, tconv_as_conv2x2): packed weights and the bias of the 4 phases
+// conv2d_transpose 3x3 s2 + BN + ReLU as a 2x2 sub-pixel conv (pack.h, tconv_as_conv2x2): packed weights and the bias of the 4 phases
 int ensure_packed_tconv(ukbb_fcn_handle *h, int layer, const ConvConfig &c, const float **wpk, const float **bias) {
     const HostLayer &L = h->layers[layer];
     char key[128];
@@ -1017,7 +1018,7 @@ int ukbb_fcn_debug_plan_layout_x3(const ukbb_fcn_arch *arch, int precision, int 
     return debug_plan_text(arch, precision, f32x3_convs != 0, n, H, W, cus, buf, cap);
 }
 
-// debugging / testing aid, not in the public header: pack_head_bf16 (kernels_head.hip) on a host matrix, host arithmetic only.  dst takes
+// debugging / testing aid, not in the public header: pack_head_bf16 (pack.cpp) on a host matrix, host arithmetic only.  dst takes
 // (n_out / 32) * (k_in / 16) * 256 dwords.
 int ukbb_fcn_debug_pack_head_bf16(const float *w, int k_in, int n_out, int acc_k, uint32_t *dst) {
     if (!w || !dst || (k_in != 16 && k_in != 32 && k_in != 64) || (n_out != 32 && n_out != 64) || (acc_k && k_in < 32)) { set_error("debug_pack_head_bf16: bad argument"); return UKBB_EINVAL; }

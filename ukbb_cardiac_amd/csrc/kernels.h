@@ -249,7 +249,6 @@ hipError_t launch_conv16_pk(int cfg_id, const ConvArgs &a, hipStream_t s);
 int num_ws_configs();
 const ConvConfig &ws_config(int i);
 int ws_lds_bytes_for(const ConvConfig &c, int cin);
-int wst_pack_order(int cout, int v);    // transposed-conv tilings (ids 410-, ks 2): source column of packed virtual channel v
 hipError_t launch_conv_ws(int cfg_id, const ConvArgs &a, hipStream_t s);
 // the three-piece (UKBB_PREC_F32X3) 3x3 tilings of ConvFamily::F32x3Operands (ids 330-345) live in kernels_conv_x3.hip; the three functions above
 // cover them.  LDS = three times the bf16-operand tiling's
@@ -259,14 +258,7 @@ hipError_t launch_conv_x3(int cfg_id, const ConvArgs &a, hipStream_t s);
 // cout handled by one workgroup = mb*cb*wm
 hipError_t launch_conv(int cfg_id, const ConvArgs &a, hipStream_t s);
 
-// Host-side: pack folded weights W[ks][ks][Cin][Cout] into A-fragment order
-// for tiling (mb, kc) and workgroups of ncbl = wm*cb Cout blocks.  Returns floats written.
-size_t pack_conv_weights(const float *w, int ks, int cin, int cout, int mb, int kc, int ncbl, float *dst);
-// bf16 operand variant (packs_bf16): 8 bf16 per lane per tap, returns dwords written.
-size_t pack_conv_weights_bf16(const float *w, int ks, int cin, int cout, int ncbl, float *dst);
-// three-piece variant (ConvFamily::F32x3Operands, 3x3 only): per chunk the bf16 pieces h, m, l of the bf16 layout above, residuals formed in
-// fp32 (as pack_head_x3); returns dwords written (3 x the bf16 packing)
-size_t pack_conv_x3(const float *w, int cin, int cout, int ncbl, float *dst);
+// The host-side weight packers (pack_*, tconv_as_conv2x2, wst_pack_order) live in pack.h / pack.cpp, a host-only unit without HIP.
 
 // Winograd F(2x2,3x3) producer/consumer kernel (kernels_wino.hip): 3x3, stride 1, C_out % 64 == 0,
 // C_in % 16 == 0.  ConvFamily::Wino22, ids 300-303.  Same ConvArgs; wpk from pack_wino_weights().
@@ -275,32 +267,22 @@ void set_error(const char *fmt, ...);
 
 hipError_t launch_wino(const ConvArgs &a, int ncb /*16-channel blocks per item: 4 or 2*/, int tile_rows /*4: 8x16-pixel regions, 8: 16x8*/,
                        hipStream_t s);
-size_t pack_wino_weights(const float *w /*[3][3][cin][cout] folded*/, int cin, int cout, int ncb, float *dst /*16*cin*cout*/);
-size_t pack_wino_first_weights(const float *w /*[3][3][16][16] folded*/, float *dst /*16*16*16*/);
 int wino_lds_bytes();
 // Winograd F(2x4,3x3) (kernels_wino24.hip): 64-channel output groups, 8 x 32- or 8 x 16-pixel regions, ConvFamily::Wino24, ids 304 / 305 / 306 / 307 (306: 8 x 16 over image pairs; 307: 32-channel items)
 hipError_t launch_wino24(const ConvArgs &a, int tile_cols /*32 | 16*/, int pair /*id 306: image pairs with seam regions, Ho % 8 == 4*/, int ncb /*4 | 2 (id 307)*/,
                          hipStream_t s);
-size_t pack_wino24_weights(const float *w /*[3][3][cin][cout] folded*/, int cin, int cout, int ncb, float *dst /*24*cin*cout*/);
 int wino24_lds_bytes(int tbw, int pair);
 // ConvLSTM forms of the same kernel (ConvArgs::ls_mode 1 | 2): tile_cols 32 | 16.  Both region shapes give identical bits.
 hipError_t launch_wino24_lstm(const ConvArgs &a, int tile_cols, hipStream_t s);
 // floats of the lane-native gx / c buffers per image (frame or window) for maps of Ho x Wo
 size_t wino24_lstm_gx_floats(int Ho, int Wo, int tile_cols);
 size_t wino24_lstm_c_floats(int Ho, int Wo, int tile_cols);
-// gate filter rows [3][3][cin_total][64] (HWIO, channels i | j | f | o x 16 hidden) -> packed F(2x4) A fragments of the input-channel slice
-// [c_first, c_first + 16) with the output channels permuted so that MFMA row 4 g + e of 16-channel block w is gate e of hidden channel
-// 4 w + g; `bias_perm` (optional, 64) receives the bias in the same order.  Returns floats written to dst (24 * 16 * 64).
-size_t pack_lstm_gate_weights(const float *w, int cin_total, int c_first, const float *bias, float *dst, float *bias_perm);
 // bf16 form of the same pair of kernels (kernels_ws.hip, ws_main LS): direct 3x3 conv on v_mfma_f32_32x32x16_bf16 (bf16 hidden maps / features / gx, fp32
-// accumulation and cell state), weight-stationary independent waves.  ConvArgs as above with ls_bf16 = 1; its own lane-native layouts and packing:
+// accumulation and cell state), weight-stationary independent waves.  ConvArgs as above with ls_bf16 = 1; its own lane-native layouts and packing
+// (pack_lstm_gate_weights_bf16; ls_mode 3, a time step with the x half not hoisted: pack_lstm_gate_weights_bf16_xh)
 hipError_t launch_lstm_ws(const ConvArgs &a, hipStream_t s);
 size_t lstm_ws_gx_elems(int H, int W);      // bf16 values of gx per image (frame)
 size_t lstm_ws_c_floats(int H, int W);      // fp32 values of the cell state per image
-size_t pack_lstm_gate_weights_bf16(const float *w, int cin_total, int c_first, const float *bias, float *dst /*9 * 16 * 64 / 2 dwords*/, float *bias_perm);
-// r06, ls_mode 3 (a time step with the x half NOT hoisted: in0 = feature frames through ls_gx_map, in1 = previous hidden maps through in0_map, bias = the
-// permuted gate bias, no gx): the whole [3][3][32][64] gate kernel as one two-chunk filter
-size_t pack_lstm_gate_weights_bf16_xh(const float *w /*[3][3][32][64]*/, const float *bias, float *dst /*9 * 32 * 64 / 2 dwords*/, float *bias_perm);
 
 // ---------------------------------------------------------------------------
 // First layer: conv3x3, C_in = 1 (network.py:186 with l = 0), direct stencil.
@@ -366,24 +348,13 @@ struct HeadArgs {
 };
 hipError_t launch_head(const HeadArgs &a, hipStream_t s);
 int head_tail_form();      // ukbb_fcn_head_tail_form()
-void pack_sq(const float *w /*[cin][32] folded*/, int cin, float *dst /*cin*32*/);
-void pack_rowmap_32x64(const float *w /*32 rows x 64 cols*/, int ld, float *dst /*2*4*64*4*/);
-void pack_head_lg(const float *w /*[64][n_class]*/, int n_class, float *dst /*2*n_class*32*/);
-void pack_head_x3(const float *w /*[k_in][64 out]*/, int k_in /*32 | 64*/, float *dst /*3*2*(k_in/16)*64*4 dwords*/);
-// UKBB_PREC_BF16_FULL: W rounded to bf16 (RNE) once, as A fragments of mfma_bf16.  acc_k 0: k in the order of the stored conv0 block (same_dim0);
-// 1: k in the order an accumulator tile's registers supply it (out0, out1)
-void pack_head_bf16(const float *w /*[k_in][n_out]*/, int k_in /*16 | 32 | 64*/, int n_out /*32 | 64*/, int acc_k, float *dst /*(n_out/32)*(k_in/16)*64*4 dwords*/);
 
 // ---------------------------------------------------------------------------
 // U-Net pieces (network_ao.py:48-63)
 // ---------------------------------------------------------------------------
 // conv2d_transpose 3x3 stride 2 'SAME' (network.py:28-34 via network_ao.py:49) is run by
 // conv_mfma_kernel as a 2x2-tap stride-1 conv over the INPUT grid with 4*Cout output channels
-// (phase-major: (py,px,co)) and ConvArgs::up2 = Cout.  This builds that dense filter
-// [2][2][Cin][4*Cout] from the folded transposed filter w[3][3][Cin][Cout] (already re-laid
-// out as HWIO by the engine):  out[2m+py] = sum_a x[m+a-1] * w[kh(py,a)],
-//   py = 0: a=0 -> kh=2, a=1 -> kh=0 ;  py = 1: a=1 -> kh=1 (a=0: no tap).
-void tconv_as_conv2x2(const float *w, int cin, int cout, float *dst);
+// (phase-major: (py,px,co)) and ConvArgs::up2 = Cout; tconv_as_conv2x2 (pack.h) builds that dense filter.
 
 // Fused tail of the bf16 U-Net (kernels_tail.hip): up0_0 -> up0_1 -> logits -> softmax / argmax in one launch (network_ao.py:51-63,159-160)
 struct TailArgs {
@@ -398,7 +369,6 @@ struct TailArgs {
     int seg_tiles;               // strip mode (set by the launcher): tile rows per segment of a column strip; 0 = whole strips
 };
 hipError_t launch_unet_tail(const TailArgs &a, hipStream_t s);
-void pack_tail_weights(const float *w0 /*[3][3][32][16] folded*/, const float *w1 /*[3][3][16][16] folded*/, float *dst0 /*9*64*4*/, float *dst1 /*5*64*4*/);
 
 // Fused stem of the bf16 U-Net (kernels_stem.hip): conv0_0 -> conv0_1 in one launch (network_ao.py:31-35 with l = 0)
 struct StemArgs {
@@ -409,7 +379,6 @@ struct StemArgs {
     int N, H, W;
 };
 hipError_t launch_unet_stem(const StemArgs &a, hipStream_t s);
-void pack_stem_weights(const float *w0 /*[3][3][1][16] folded*/, float *dst0 /*64*4*/);
 
 struct LogitsArgs {         // 1x1 conv C -> n_class + bias, softmax / argmax (network_ao.py:63,159-160)
     const float *in;        // [N,H,W,C]
@@ -476,7 +445,6 @@ struct Conv3dArgs {         // 3x3x3 conv (+ folded BN + ReLU) over windows of T
     Conv3dPhase ph[4];
 };
 hipError_t launch_conv3d(const Conv3dArgs &a, hipStream_t s);
-void pack_conv3d_weights(const float *w /*[ntap][cin][cout]*/, int ntap, int cin, int cout, int cout_pad, float *dst);
 
 struct Conv3dFirstArgs {    // first layer, C_in = 1 -> 16, 3x3x3, stride 1 (+ folded BN + ReLU)
     const float *image;     // frames [.][H][W]
@@ -494,7 +462,6 @@ hipError_t launch_conv3d_first(const Conv3dFirstArgs &a, hipStream_t s);
 // unrounded fp32 folded weights and stores its 16 channels as bf16.
 hipError_t launch_conv3d_bf16(const Conv3dArgs &a, hipStream_t s);
 hipError_t launch_conv3d_first_bf16(const Conv3dFirstArgs &a, hipStream_t s);
-void pack_conv3d_weights_bf16(const float *w /*[ntap][cin][cout]*/, int ntap, int cin, int cout, int cout_pad, float *dst /*ntap * cin * cout_pad / 2 dwords*/);
 
 struct T3dTileArgs {        // weighted circular tiling (deploy_network_ao.py:176-183) of the windows [w0, w1) of a cine
     const float *probw;     // [(w1 - w0) * K][HW][C]: softmax of each window frame

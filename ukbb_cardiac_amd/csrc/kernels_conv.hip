@@ -25,7 +25,6 @@
 
 #include <cstdlib>
 #include <algorithm>
-#include <cstring>
 #include <cstdio>
 #include <vector>
 #include <type_traits>
@@ -150,7 +149,7 @@ __global__ __launch_bounds__(256, conv_min_waves(KS, STRIDE, MB, TH, TW, KC, WM,
 
     // Sub-pixel form of the 3x3 stride-2 transposed conv (up2 > 0, KS = 2): output phase (py, px) of a Cout block uses
     // tap (a, b) of the 2x2 window only if (py == 0 || a == 1) && (px == 0 || b == 1) -- 9 of the 16 (tap, phase) pairs;
-    // the other 7 hold zero weights (kernels.h, tconv_as_conv2x2) and their MFMAs are skipped (wave-uniform test).
+    // the other 7 hold zero weights (pack.h, tconv_as_conv2x2) and their MFMAs are skipped (wave-uniform test).
     unsigned tapmask[CB];
 #pragma unroll
     for (int cb = 0; cb < CB; ++cb) {
@@ -1561,78 +1560,6 @@ hipError_t launch_conv(int cfg_id, const ConvArgs &a_in, hipStream_t s) {
         UKBB_BFIOF_CONFIGS(UKBB_BFIOF_CASE)
         default: return hipErrorInvalidValue;
     }
-}
-
-size_t pack_conv_weights(const float *w, int ks, int cin, int cout, int mb, int kc, int ncbl, float *dst) {
-    // dst[group][chunk][cbl][tap][lane][s] = W[tap][ci][co],  cb = group*ncbl + cbl
-    //   k-step s of lane group g uses channel ci = chunk*kc + g*ksteps + s  (so the B operands
-    //   of a lane for all k-steps of a tap are ksteps CONSECUTIVE channels = one LDS vector read)
-    //   mb = 32: lane = (g<<5)|m (g < 2), co = cb*32 + m ;  mb = 16: lane = (g<<4)|m (g < 4), co = cb*16 + m
-    // One workgroup (= one group of ncbl Cout blocks) reads, per chunk, one contiguous slab.
-    const int kk = (mb == 32) ? 2 : 4, ksteps = kc / kk, ks2 = ks * ks, nchunk = cin / kc;
-    size_t o = 0;
-    for (int grp = 0; grp < cout / (mb * ncbl); ++grp)
-        for (int ch = 0; ch < nchunk; ++ch)
-            for (int cbl = 0; cbl < ncbl; ++cbl)
-                for (int tap = 0; tap < ks2; ++tap)
-                    for (int lane = 0; lane < 64; ++lane) {
-                        const int m = lane % mb, g = lane / mb;
-                        for (int s = 0; s < ksteps; ++s) {
-                            const int ci = ch * kc + g * ksteps + s, co = (grp * ncbl + cbl) * mb + m;
-                            dst[o++] = w[((size_t)tap * cin + ci) * cout + co];
-                        }
-                    }
-    return o;
-}
-
-size_t pack_wino_first_weights(const float *w, float *dst) {
-    // w: folded [3][3][16][16] of a 16 -> 16 3x3 conv.  U = G g G^T per (ci, co), G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]] (the +-1/2
-    // factors stay in the weights, as in pack_wino_weights).  dst[h][k = 4*xi + nu][lane][s]: the A fragment of k-step s of half h of the
-    // Winograd consumers of conv_pc_kernel<..., WINO>: lane = (g << 4) | m, co = m, ci = 4*g + 2*h + s.
-    static const float G[4][3] = {{1.f, 0.f, 0.f}, {.5f, .5f, .5f}, {.5f, -.5f, .5f}, {0.f, 0.f, 1.f}};
-    size_t o = 0;
-    for (int h = 0; h < 2; ++h)
-        for (int k = 0; k < 16; ++k)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int s = 0; s < 2; ++s) {
-                    const int m = lane & 15, g = lane >> 4, ci = 4 * g + 2 * h + s, co = m;
-                    const int xi = k >> 2, nu = k & 3;
-                    double u = 0.0;                         // exact products of small dyadic factors; one rounding
-                    for (int i = 0; i < 3; ++i)
-                        for (int j = 0; j < 3; ++j)
-                            u += (double)G[xi][i] * (double)w[((size_t)(i * 3 + j) * 16 + ci) * 16 + co] * (double)G[nu][j];
-                    dst[o++] = (float)u;
-                }
-    return o;
-}
-
-static inline unsigned short f32_to_bf16_rne(float f) {
-    unsigned u; memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);   // NaN stays NaN
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
-
-size_t pack_conv_weights_bf16(const float *w, int ks, int cin, int cout, int ncbl, float *dst) {
-    // dst[group][chunk][cbl][tap][lane][4 dwords]; dword d of lane (g<<5)|m holds bf16 pair
-    //   W[tap][ci = chunk*16 + 8g + 2d (+1)][co = cb*32 + m]   (low half = even channel)
-    const int ks2 = ks * ks, nchunk = cin / 16;
-    unsigned *out = reinterpret_cast<unsigned *>(dst);
-    size_t o = 0;
-    for (int grp = 0; grp < cout / (32 * ncbl); ++grp)
-        for (int ch = 0; ch < nchunk; ++ch)
-            for (int cbl = 0; cbl < ncbl; ++cbl)
-                for (int tap = 0; tap < ks2; ++tap)
-                    for (int lane = 0; lane < 64; ++lane) {
-                        const int m = lane & 31, g = lane >> 5, co = (grp * ncbl + cbl) * 32 + m;
-                        for (int d = 0; d < 4; ++d) {
-                            const int ci = ch * 16 + 8 * g + 2 * d;
-                            const unsigned lo = f32_to_bf16_rne(w[((size_t)tap * cin + ci) * cout + co]);
-                            const unsigned hi = f32_to_bf16_rne(w[((size_t)tap * cin + ci + 1) * cout + co]);
-                            out[o++] = lo | (hi << 16);
-                        }
-                    }
-    return o;
 }
 
 // ---------------------------------------------------------------------------

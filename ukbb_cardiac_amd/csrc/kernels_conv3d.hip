@@ -200,19 +200,4 @@ hipError_t launch_t3d_tile(const T3dTileArgs &a, hipStream_t s) {
     return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
-// w: folded weights [3 dt][ny][nx][cin][cout] of ONE phase (dt = time tap - 1, taps already in kernel order);
-// dst: [tap][chunk of 8 channels][32-channel block][lane][4]: lane (m, h) k-step s -> W[c*8 + 4h + s][blk*32 + m] (0 beyond cout)
-void pack_conv3d_weights(const float *w, int ntap, int cin, int cout, int cout_pad, float *dst) {
-    const int nch = cin / 8, ncob = cout_pad / 32;
-    for (int tap = 0; tap < ntap; ++tap)
-        for (int c = 0; c < nch; ++c)
-            for (int blk = 0; blk < ncob; ++blk)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int s = 0; s < 4; ++s) {
-                        const int m = lane & 31, hh = lane >> 5, ci = c * 8 + 4 * hh + s, co = blk * 32 + m;
-                        dst[((((size_t)tap * nch + c) * ncob + blk) * 64 + lane) * 4 + s] =
-                            co < cout ? w[((size_t)tap * cin + ci) * cout + co] : 0.f;
-                    }
-}
-
 }  // namespace ukbb

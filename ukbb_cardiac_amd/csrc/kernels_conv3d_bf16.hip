@@ -25,8 +25,6 @@
 #include "kernels.h"
 #include "device_prims.h"
 
-#include <cstring>
-
 namespace ukbb {
 
 namespace {
@@ -159,13 +157,6 @@ __global__ __launch_bounds__(256) void conv3d_first_bf16_kernel(const Conv3dFirs
     }
 }
 
-inline bf16_t host_bf16(float f) {          // round to nearest, ties to even
-    unsigned u; memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (bf16_t)((u >> 16) | 0x40);   // NaN stays NaN
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (bf16_t)(u >> 16);
-}
-
 }  // namespace
 
 hipError_t launch_conv3d_bf16(const Conv3dArgs &a, hipStream_t s) {
@@ -187,23 +178,6 @@ hipError_t launch_conv3d_first_bf16(const Conv3dFirstArgs &a, hipStream_t s) {
     if (blocks < 1 || blocks > 0x7fffffffll) return hipErrorInvalidValue;
     hipLaunchKernelGGL(conv3d_first_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a);
     return hipGetLastError();
-}
-
-// w: folded fp32 weights [ntap][cin][cout] of ONE phase (taps already in kernel order), rounded here, once, to bf16;
-// dst: [tap][K step of 16 channels][32-channel block][lane][8] bf16: lane (m, h) element j -> W[16 c + 8 h + j][32 blk + m] (0 beyond cout);
-// ntap * cin * cout_pad / 2 dwords
-void pack_conv3d_weights_bf16(const float *w, int ntap, int cin, int cout, int cout_pad, float *dst) {
-    const int nk = cin / 16, ncob = cout_pad / 32;
-    bf16_t *d = reinterpret_cast<bf16_t *>(dst);
-    for (int tap = 0; tap < ntap; ++tap)
-        for (int c = 0; c < nk; ++c)
-            for (int blk = 0; blk < ncob; ++blk)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const int m = lane & 31, hh = lane >> 5, ci = c * 16 + 8 * hh + j, co = blk * 32 + m;
-                        d[((((size_t)tap * nk + c) * ncob + blk) * 64 + lane) * 8 + j] =
-                            co < cout ? host_bf16(w[((size_t)tap * cin + ci) * cout + co]) : (bf16_t)0;
-                    }
 }
 
 }  // namespace ukbb

@@ -16,8 +16,6 @@
 #include "kernels.h"
 #include "device_prims.h"
 
-#include <cstring>
-
 namespace ukbb {
 
 namespace {
@@ -210,13 +208,6 @@ __global__ __launch_bounds__(256) void conv_x3_kernel(const ConvArgs a) {
      "convF32x3_3x3s" #S "_t" #TH "x" #TW "_w" #WM "x" #WN "_cb" #CB},
 const ConvConfig g_x3_cfgs[] = {UKBB_X3_CONFIGS(UKBB_X3_ENTRY)};
 
-static inline unsigned short host_bf16_rne(float f) {
-    unsigned u; memcpy(&u, &f, 4);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
-static inline float host_bf16_to_f32(unsigned short b) { const unsigned u = (unsigned)b << 16; float f; memcpy(&f, &u, 4); return f; }
-
 }  // namespace
 
 int num_x3_configs() { return (int)(sizeof(g_x3_cfgs) / sizeof(g_x3_cfgs[0])); }
@@ -238,34 +229,6 @@ hipError_t launch_conv_x3(int cfg_id, const ConvArgs &a, hipStream_t s) {
         UKBB_X3_CONFIGS(UKBB_X3_CASE)
         default: return hipErrorInvalidValue;
     }
-}
-
-size_t pack_conv_x3(const float *w, int cin, int cout, int ncbl, float *dst) {
-    // dst[group][chunk][piece][cbl][tap][lane][4 dwords]: piece t of pack_conv_weights_bf16's layout -- dword d of lane (g << 5) | m holds the
-    // bf16 pair of W[tap][ci = chunk * 16 + 8 g + 2 d (+ 1)][co = cb * 32 + m] (low half = even channel).  Piece 0 = bf16(w), piece 1 =
-    // bf16(w - piece 0), piece 2 = bf16(w - piece 0 - piece 1), the residuals formed in fp32 (exact), as pack_head_x3 does.
-    const int nchunk = cin / 16;
-    unsigned *out = reinterpret_cast<unsigned *>(dst);
-    size_t o = 0;
-    for (int grp = 0; grp < cout / (32 * ncbl); ++grp)
-        for (int ch = 0; ch < nchunk; ++ch)
-            for (int t = 0; t < 3; ++t)
-                for (int cbl = 0; cbl < ncbl; ++cbl)
-                    for (int tap = 0; tap < 9; ++tap)
-                        for (int lane = 0; lane < 64; ++lane) {
-                            const int m = lane & 31, g = lane >> 5, co = (grp * ncbl + cbl) * 32 + m;
-                            for (int d = 0; d < 4; ++d) {
-                                unsigned short piece[2];
-                                for (int hh = 0; hh < 2; ++hh) {
-                                    float x = w[((size_t)tap * cin + ch * 16 + 8 * g + 2 * d + hh) * cout + co];
-                                    unsigned short b = 0;
-                                    for (int k = 0; k <= t; ++k) { b = host_bf16_rne(x); x -= host_bf16_to_f32(b); }
-                                    piece[hh] = b;
-                                }
-                                out[o++] = (unsigned)piece[0] | ((unsigned)piece[1] << 16);
-                            }
-                        }
-    return o;
 }
 
 }  // namespace ukbb

@@ -25,20 +25,15 @@
 // lanes 32-63, and the weights are packed on the host in that k order.
 #include "kernels.h"
 #include "device_prims.h"
+#include "pack.h"       // rowmap
 
 #include <atomic>
 #include <cstdio>
 
 #include <cstdlib>
-#include <cstring>
 #include <type_traits>
 
 namespace ukbb {
-
-__host__ __device__ __forceinline__ constexpr int rowmap(int r, int g) {
-    // row of a 32x32 f32 MFMA result held in register r by lane half g
-    return (r & 3) + 8 * (r >> 2) + 4 * g;
-}
 
 #define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 
@@ -1311,88 +1306,6 @@ hipError_t launch_head(const HeadArgs &a_in, hipStream_t s) {
     }
 #endif
     return launch_head_pc(a, s);
-}
-
-// ---- host-side weight packers (k order documented at the top) ---------------
-void pack_sq(const float *w, int cin, float *dst) {
-    // W is [cin][32].  dst[j][lane][i] = W[ci = 8j + 4g + i][co = m],  lane = (g<<5)|m
-    for (int j = 0; j < cin / 8; ++j)
-        for (int lane = 0; lane < 64; ++lane)
-            for (int i = 0; i < 4; ++i)
-                dst[(j * 64 + lane) * 4 + i] = w[(8 * j + 4 * (lane >> 5) + i) * 32 + (lane & 31)];
-}
-
-void pack_rowmap_32x64(const float *w, int ld, float *dst) {
-    // W is 32 rows (k) x 64 cols (cout), row stride ld.  dst[cb][q4][lane][i]:
-    //   k = rowmap(4*q4 + i, g), co = 32*cb + m   (B operand = a 32-row accumulator tile)
-    for (int cb = 0; cb < 2; ++cb)
-        for (int q4 = 0; q4 < 4; ++q4)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int i = 0; i < 4; ++i) {
-                    const int g = lane >> 5, m = lane & 31;
-                    dst[(((cb * 4 + q4) * 64 + lane) * 4) + i] = w[rowmap(4 * q4 + i, g) * ld + cb * 32 + m];
-                }
-}
-
-static inline unsigned short host_bf16_rne(float f) {
-    unsigned u; memcpy(&u, &f, 4);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
-static inline float host_bf16_to_f32(unsigned short b) { const unsigned u = (unsigned)b << 16; float f; memcpy(&f, &u, 4); return f; }
-
-void pack_head_x3(const float *w, int k_in, float *dst) {
-    // W is [k_in rows (32 or 64)][64 out], row stride 64.  dst[t][cb][kc][lane][d] (dwords), kc < k_in / 16: t = piece (bf16 of w, of
-    // the remainder, of the rest), lane = (g << 5) | m, cout = 32 cb + m, k slot e = 2 d (+1 in the high half) <-> input row
-    // 32 (kc / 2) + rowmap(8 (kc & 1) + e, g): the registers of the 32-row accumulator tile(s) the MFMA wave holds
-    unsigned *o = reinterpret_cast<unsigned *>(dst);
-    const int nkc = k_in / 16;
-    for (int t = 0; t < 3; ++t)
-        for (int cb = 0; cb < 2; ++cb)
-            for (int kc = 0; kc < nkc; ++kc)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int d = 0; d < 4; ++d) {
-                        const int g = lane >> 5, m = lane & 31;
-                        unsigned short piece[2];
-                        for (int hh = 0; hh < 2; ++hh) {
-                            const int e = 2 * d + hh, ch = 32 * (kc / 2) + rowmap(8 * (kc & 1) + e, g);
-                            float x = w[ch * 64 + 32 * cb + m];
-                            unsigned short b = 0;
-                            for (int k = 0; k <= t; ++k) { b = host_bf16_rne(x); x -= host_bf16_to_f32(b); }
-                            piece[hh] = b;
-                        }
-                        o[((((t * 2 + cb) * nkc + kc) * 64 + lane) * 4) + d] = (unsigned)piece[0] | ((unsigned)piece[1] << 16);
-                    }
-}
-
-void pack_head_bf16(const float *w, int k_in, int n_out, int acc_k, float *dst) {
-    // W is [k_in rows][n_out], row stride n_out.  dst[cb][kc][lane][d] (dwords), cb < n_out / 32, kc < k_in / 16: the A fragments of mfma_bf16,
-    // lane = (g << 5) | m, cout = 32 cb + m, k slot e = 2 d (+1 in the high half) of chunk kc <-> input row 16 kc + 8 g + e (acc_k 0: the
-    // stored conv0 half-block) or 32 (kc / 2) + rowmap(8 (kc & 1) + e, g) (acc_k 1: the registers of the accumulator tile(s), as pack_head_x3).
-    // Each weight is rounded to bf16 (RNE) once, here.
-    unsigned *o = reinterpret_cast<unsigned *>(dst);
-    const int nkc = k_in / 16;
-    for (int cb = 0; cb < n_out / 32; ++cb)
-        for (int kc = 0; kc < nkc; ++kc)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int d = 0; d < 4; ++d) {
-                    const int g = lane >> 5, m = lane & 31;
-                    unsigned short piece[2];
-                    for (int hh = 0; hh < 2; ++hh) {
-                        const int e = 2 * d + hh, row = acc_k ? 32 * (kc / 2) + rowmap(8 * (kc & 1) + e, g) : 16 * kc + 8 * g + e;
-                        piece[hh] = host_bf16_rne(w[row * n_out + 32 * cb + m]);
-                    }
-                    o[(((cb * nkc + kc) * 64 + lane) * 4) + d] = (unsigned)piece[0] | ((unsigned)piece[1] << 16);
-                }
-}
-
-void pack_head_lg(const float *w, int n_class, float *dst) {
-    // W is [64][n_class].  dst[g][c][cb*16 + r] = W[cb*32 + rowmap(r, g)][c]
-    for (int g = 0; g < 2; ++g)
-        for (int c = 0; c < n_class; ++c)
-            for (int cb = 0; cb < 2; ++cb)
-                for (int r = 0; r < 16; ++r)
-                    dst[(g * n_class + c) * 32 + cb * 16 + r] = w[(cb * 32 + rowmap(r, g)) * n_class + c];
 }
 
 // ---------------------------------------------------------------------------

@@ -17,7 +17,6 @@
 #include "kernels.h"
 #include "device_prims.h"
 
-#include <cstring>
 #include <type_traits>
 
 namespace ukbb {
@@ -240,27 +239,6 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void unet_stem_kernel(const StemAr
 }
 
 }  // namespace
-
-// A fragments (lane l: row l & 15, k = 8 (l >> 4) + j):
-//   wA0 [64 lanes][4 dwords]: conv0_0 [3][3][1][16] folded: k = 4 kh + kw for kw < 3, kh < 3; zero elsewhere
-static inline unsigned short st_bf16(float f) {
-    unsigned u; memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
-void pack_stem_weights(const float *w0 /*[3][3][1][16] folded*/, float *dst0 /*64*4*/) {
-    unsigned *o0 = reinterpret_cast<unsigned *>(dst0);
-    for (int l = 0; l < 64; ++l)
-        for (int d = 0; d < 4; ++d) {
-            unsigned short h[2];
-            for (int e = 0; e < 2; ++e) {
-                const int m = l & 15, k = 8 * (l >> 4) + 2 * d + e, kh = k >> 2, kw = k & 3;
-                h[e] = (kh < 3 && kw < 3) ? st_bf16(w0[(kh * 3 + kw) * 16 + m]) : (unsigned short)0;
-            }
-            o0[l * 4 + d] = (unsigned)h[0] | ((unsigned)h[1] << 16);
-        }
-}
 
 hipError_t launch_unet_stem(const StemArgs &a, hipStream_t s) {
     if (!a.image || !a.wA0 || !a.wA1 || !a.b0 || !a.b1 || !a.out || a.N < 1) return hipErrorInvalidValue;

@@ -26,7 +26,6 @@
 
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <type_traits>
 #include <vector>
 
@@ -405,32 +404,6 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void unet_tail_kernel(const TailAr
 }
 
 }  // namespace
-
-// Host side: A fragments of v_mfma_f32_16x16x32_bf16 (lane l: row l & 15, k = 8 (l >> 4) + j, j = 0..7; two bf16 per dword).
-//   wA0 [9 taps][64 lanes][4 dwords]: up0_0, k = input channel of concat[skip 0..15, up 16..31], row = output channel
-//   wA1 [5 pairs][64][4]: up0_1, k < 16: tap 2 p, channel k; k >= 16: tap 2 p + 1, channel k - 16 (zero for the missing tap 9)
-static inline unsigned short tl_bf16(float f) {
-    unsigned u; memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
-void pack_tail_weights(const float *w0 /*[3][3][32][16] folded*/, const float *w1 /*[3][3][16][16] folded*/, float *dst0 /*9*64*4*/, float *dst1 /*5*64*4*/) {
-    unsigned *o0 = reinterpret_cast<unsigned *>(dst0), *o1 = reinterpret_cast<unsigned *>(dst1);
-    for (int t = 0; t < 9; ++t)
-        for (int l = 0; l < 64; ++l)
-            for (int d = 0; d < 4; ++d) {
-                const int m = l & 15, k = 8 * (l >> 4) + 2 * d;
-                o0[(t * 64 + l) * 4 + d] = (unsigned)tl_bf16(w0[((size_t)t * 32 + k) * 16 + m]) | ((unsigned)tl_bf16(w0[((size_t)t * 32 + k + 1) * 16 + m]) << 16);
-            }
-    for (int p = 0; p < 5; ++p)
-        for (int l = 0; l < 64; ++l)
-            for (int d = 0; d < 4; ++d) {
-                const int m = l & 15, k = 8 * (l >> 4) + 2 * d, t = 2 * p + (k >> 4), c = k & 15;
-                const float v0 = t < 9 ? w1[((size_t)t * 16 + c) * 16 + m] : 0.f, v1 = t < 9 ? w1[((size_t)t * 16 + c + 1) * 16 + m] : 0.f;
-                o1[(p * 64 + l) * 4 + d] = (unsigned)tl_bf16(v0) | ((unsigned)tl_bf16(v1) << 16);
-            }
-}
 
 hipError_t launch_unet_tail(const TailArgs &a_in, hipStream_t s) {
     TailArgs a = a_in;

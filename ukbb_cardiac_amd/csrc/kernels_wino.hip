@@ -22,6 +22,7 @@
 // One barrier per stage.
 #include "kernels.h"
 #include "device_prims.h"
+#include "pack.h"       // WKC
 
 #include <cstdio>
 #include <cstdlib>
@@ -32,7 +33,7 @@ namespace ukbb {
 namespace {
 
 constexpr int NT = 32;                                // Winograd tiles per region (two MFMA N blocks): 4 x 8 or 8 x 4 tiles
-constexpr int WKC = 16, WXS = WKC + 4;                // channels per stage, LDS pixel stride (floats)
+constexpr int WXS = WKC + 4;                          // LDS pixel stride (floats); WKC = channels per stage (pack.h)
 constexpr int WHP = 180;                              // raw halo tile: 10 x 18 or 18 x 10 pixels
 constexpr int NITX = (WHP * (WKC / 4) + 255) / 256;   // staging passes of the 256 producer threads (3)
 // Raw halo tile XS: pixel stride WXSX = 24 floats and row pitch RS pixels (18 for the 18-wide halo of 4 x 8-tile regions, 12 for the
@@ -531,32 +532,6 @@ hipError_t launch_wino(const ConvArgs &a_in, int ncb, int tile_rows, hipStream_t
     if (ncb == 4) return tile_rows == 8 ? launch_wino_t<4, 8>(a, s) : launch_wino_t<4, 4>(a, s);
     if (ncb == 2) return tile_rows == 8 ? launch_wino_t<2, 8>(a, s) : launch_wino_t<2, 4>(a, s);
     return hipErrorInvalidValue;
-}
-
-size_t pack_wino_weights(const float *w, int cin, int cout, int ncb, float *dst) {
-    const int WNCBL = ncb;
-    // w: folded [3][3][cin][cout].  U = G g G^T per (ci, co), G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]].
-    // dst[group][chunk][cbl][k = 4*xi + nu][lane][s]:  lane = (g << 4) | m,
-    //   ci = chunk*16 + 4*g + s, co = (group*4 + cbl)*16 + m          (A fragment of v_mfma_f32_16x16x4_f32)
-    static const float G[4][3] = {{1.f, 0.f, 0.f}, {.5f, .5f, .5f}, {.5f, -.5f, .5f}, {0.f, 0.f, 1.f}};
-    const int nchunk = cin / WKC;
-    size_t o = 0;
-    for (int grp = 0; grp < cout / (16 * WNCBL); ++grp)
-        for (int ch = 0; ch < nchunk; ++ch)
-            for (int cbl = 0; cbl < WNCBL; ++cbl)
-                for (int k = 0; k < 16; ++k)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int s = 0; s < 4; ++s) {
-                            const int m = lane & 15, g = lane >> 4;
-                            const int ci = ch * WKC + 4 * g + s, co = (grp * WNCBL + cbl) * 16 + m;
-                            const int xi = k >> 2, nu = k & 3;
-                            double u = 0.0;                 // exact products of small dyadic factors; one rounding
-                            for (int i = 0; i < 3; ++i)
-                                for (int j = 0; j < 3; ++j)
-                                    u += (double)G[xi][i] * (double)w[((size_t)(i * 3 + j) * cin + ci) * cout + co] * (double)G[nu][j];
-                            dst[o++] = (float)u;
-                        }
-    return o;
 }
 
 }  // namespace ukbb

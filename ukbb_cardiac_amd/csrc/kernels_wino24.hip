@@ -21,6 +21,7 @@
 // conflict-free at a pixel stride of 16 floats (slot = q ^ 3 for tiles 8-15 of each 16-tile block): 153 KB of the 160.
 #include "kernels.h"
 #include "device_prims.h"
+#include "pack.h"       // WKC, NK
 
 #include <cstdio>
 #include <cstdlib>
@@ -31,8 +32,7 @@ namespace ukbb {
 namespace {
 
 constexpr int TRY = 4;                                // tile rows per region (8 pixel rows)
-constexpr int NK = 24;                                // GEMM positions: k = 6 i + j, i = row position 0..3, j = column position 0..5
-constexpr int WKC = 16;                               // input channels per stage
+// NK = 24 GEMM positions and WKC = 16 input channels per stage: pack.h, shared with pack_wino24_weights
 constexpr int XS_S = 20;                              // raw tile: floats per pixel
 // TBW = 16-tile MFMA column blocks per region: 2 -> 4 x 8 tiles = 8 x 32 pixels, 1 -> 4 x 4 tiles = 8 x 16 pixels (twice the items:
 // maps whose 8 x 32 regions do not fill the CUs evenly, e.g. 24 x 26 at N = 64: 384 items on 256 CUs)
@@ -731,44 +731,5 @@ static size_t lstm_regions(int Ho, int Wo, int tile_cols) { return (size_t)((Ho 
 // per region: 4 consumer waves x (tile_cols / 16 tile blocks x 8 pixels of a tile) x 64 lanes, one float (c) or four (gx) each
 size_t wino24_lstm_c_floats(int Ho, int Wo, int tile_cols) { return lstm_regions(Ho, Wo, tile_cols) * 4 * (size_t)(tile_cols / 16) * 8 * 64; }
 size_t wino24_lstm_gx_floats(int Ho, int Wo, int tile_cols) { return 4 * wino24_lstm_c_floats(Ho, Wo, tile_cols); }
-
-size_t pack_wino24_weights(const float *w, int cin, int cout, int ncb, float *dst);
-size_t pack_lstm_gate_weights(const float *w, int cin_total, int c_first, const float *bias, float *dst, float *bias_perm) {
-    // packed channel P = 16 w + m (MFMA row m = 4 g + e of block w)  <-  original channel 16 e + (4 w + g): gate e of hidden channel 4 w + g
-    float tmp[9 * WKC * 64];
-    for (int P = 0; P < 64; ++P) {
-        const int wv = P / 16, m = P % 16, orig = (m % 4) * 16 + 4 * wv + m / 4;
-        if (bias_perm) bias_perm[P] = bias ? bias[orig] : 0.f;
-        for (int t = 0; t < 9; ++t)
-            for (int ci = 0; ci < WKC; ++ci) tmp[(t * WKC + ci) * 64 + P] = w[((size_t)t * cin_total + c_first + ci) * 64 + orig];
-    }
-    return pack_wino24_weights(tmp, WKC, 64, 4, dst);
-}
-
-size_t pack_wino24_weights(const float *w, int cin, int cout, int ncb, float *dst) {
-    // w: folded [3][3][cin][cout].  U = G_y g G_x^T per (ci, co); G_y = F(2,3) rows, G_x = F(4,3) columns.
-    // dst[group of 16 ncb][chunk][cbl 0..ncb-1][k = 6 i + j][lane][s]:  lane = (g << 4) | m, ci = chunk*16 + 4*g + s, co = (group*ncb + cbl)*16 + m
-    static const double GY[4][3] = {{1, 0, 0}, {.5, .5, .5}, {.5, -.5, .5}, {0, 0, 1}};
-    static const double GX[6][3] = {{1.0 / 4, 0, 0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
-                                    {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
-    const int nchunk = cin / WKC;
-    size_t o = 0;
-    for (int grp = 0; grp < cout / (16 * ncb); ++grp)
-        for (int ch = 0; ch < nchunk; ++ch)
-            for (int cbl = 0; cbl < ncb; ++cbl)
-                for (int k = 0; k < NK; ++k)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int s = 0; s < 4; ++s) {
-                            const int m = lane & 15, g = lane >> 4;
-                            const int ci = ch * WKC + 4 * g + s, co = (grp * ncb + cbl) * 16 + m;
-                            const int i = k / 6, j = k % 6;
-                            double u = 0.0;
-                            for (int p = 0; p < 3; ++p)
-                                for (int q = 0; q < 3; ++q)
-                                    u += GY[i][p] * (double)w[((size_t)(p * 3 + q) * cin + ci) * cout + co] * GX[j][q];
-                            dst[o++] = (float)u;
-                        }
-    return o;
-}
 
 }  // namespace ukbb

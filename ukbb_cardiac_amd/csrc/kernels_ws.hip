@@ -27,7 +27,7 @@
 // rounding of the accumulator, not bit for bit.
 //
 // KIND = 1 is the same machine for conv2d_transpose 3x3 stride 2 'SAME' + BN + ReLU (reference common/network.py:28-34 as used
-// by network_ao.py:48-49) in its 4-phase sub-pixel form (kernels.h, tconv_as_conv2x2): a tile is R INPUT rows x 32 input pixels
+// by network_ao.py:48-49) in its 4-phase sub-pixel form (pack.h, tconv_as_conv2x2): a tile is R INPUT rows x 32 input pixels
 // (2R x 64 outputs), the halo is one row above and one column left, the four 2x2 taps (a, b) read input (m + a - 1, x + b - 1),
 // and output phase (py, px) uses tap (a, b) only if (py == 0 || a == 1) && (px == 0 || b == 1): 9 of the 16 (tap, phase) pairs.
 // A workgroup owns TWO 32-row blocks of the 4 x Cout phase-major "virtual" channels, paired so that every workgroup has about the
@@ -939,16 +939,6 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void lstm_ws_kernel(const ConvArgs
     {ID, 3, 1, 32, R, WS_TW, 32, 1, NW, CB, 0, ConvFamily::Bf16StoreWs, "convBF16wr_3x3s1_r" #R "x32_cb" #CB "_w" #NW, 0},
 static const ConvConfig g_ws_cfgs[] = {UKBB_WS_CONFIGS(UKBB_WS_ENTRY) UKBB_WSL_CONFIGS(UKBB_WSL_ENTRY) UKBB_WST_CONFIGS(UKBB_WST_ENTRY) UKBB_WR_CONFIGS(UKBB_WR_ENTRY)};
 
-// Order of the 4 x cout phase-major virtual channels (phase = 2 py + px, then channel) in the packed filter / bias of the transposed
-// conv tilings: dst column v takes source column wst_pack_order(cout, v).  cout = 16: unchanged (blocks {00 + 01}, {10 + 11}).
-// cout % 32 == 0: workgroup (group) 2 i holds {phase 00, phase 11} of channels 32 i .., group 2 i + 1 holds {01, 10} (tconv_ws_kernel).
-int wst_pack_order(int cout, int v) {
-    if (cout == 16) return v;
-    const int nb = v / 32, r = v % 32, grp = nb / 2, k = nb % 2, i = grp / 2;
-    const int ph = (grp & 1) ? (k == 0 ? 1 : 2) : (k == 0 ? 0 : 3);
-    return ph * cout + i * 32 + r;
-}
-
 int num_ws_configs() { return (int)(sizeof(g_ws_cfgs) / sizeof(g_ws_cfgs[0])); }
 const ConvConfig &ws_config(int i) { return g_ws_cfgs[i]; }
 int ws_lds_bytes_for(const ConvConfig &c, int cin) {
@@ -1041,34 +1031,6 @@ hipError_t launch_lstm_ws(const ConvArgs &a_in, hipStream_t s) {
     if (a.ls_mode == 1) return launch_lds<lstm_ws_kernel<LSW_R, LSW_NW, 1>>(g, b, bytes, s, a);
     if (a.ls_mode == 3) return launch_lds<lstm_ws_kernel<LSW_R, LSW_NW, 3>>(g, b, bytes3, s, a);
     return launch_lds<lstm_ws_kernel<LSW_R, LSW_NW, 2>>(g, b, bytes, s, a);
-}
-
-size_t pack_lstm_gate_weights_bf16_xh(const float *w, const float *bias, float *dst, float *bias_perm) {
-    // both 16-channel halves of the gate kernel [3][3][16 + 16][64] as the two chunks of ONE filter (chunk 0 = x rows, chunk 1 = h rows),
-    // output channels permuted as in pack_lstm_gate_weights_bf16: the resident filter of ws_main LS 3
-    std::vector<float> tmp((size_t)9 * 32 * 64);
-    for (int P = 0; P < 64; ++P) {
-        const int cb = P / 32, row = P % 32, j = row / 8, g = (row / 4) & 1, i = row % 4;
-        const int orig = (2 * cb + (j >> 1)) * 16 + 8 * g + 4 * (j & 1) + i;
-        if (bias_perm) bias_perm[P] = bias ? bias[orig] : 0.f;
-        for (int t = 0; t < 9; ++t)
-            for (int ci = 0; ci < 32; ++ci) tmp[((size_t)t * 32 + ci) * 64 + P] = w[((size_t)t * 32 + ci) * 64 + orig];
-    }
-    return pack_conv_weights_bf16(tmp.data(), 3, 32, 64, 2, dst);
-}
-
-size_t pack_lstm_gate_weights_bf16(const float *w, int cin_total, int c_first, const float *bias, float *dst, float *bias_perm) {
-    // packed channel P = 32 cb + 8 j + 4 g + i (MFMA row 8 j + 4 g + i of block cb)  <-  gate e = 2 cb + (j >> 1) of hidden channel 8 g + 4 (j & 1) + i:
-    // the accumulator registers of lane half g are then (i | j) in block 0 and (f | o) in block 1, eight hidden channels each (ws_main, LS)
-    std::vector<float> tmp((size_t)9 * 16 * 64);
-    for (int P = 0; P < 64; ++P) {
-        const int cb = P / 32, row = P % 32, j = row / 8, g = (row / 4) & 1, i = row % 4;
-        const int orig = (2 * cb + (j >> 1)) * 16 + 8 * g + 4 * (j & 1) + i;
-        if (bias_perm) bias_perm[P] = bias ? bias[orig] : 0.f;
-        for (int t = 0; t < 9; ++t)
-            for (int ci = 0; ci < 16; ++ci) tmp[((size_t)t * 16 + ci) * 64 + P] = w[((size_t)t * cin_total + c_first + ci) * 64 + orig];
-    }
-    return pack_conv_weights_bf16(tmp.data(), 3, 16, 64, 2, dst);
 }
 
 hipError_t launch_conv_ws(int cfg_id, const ConvArgs &a_in, hipStream_t s) {

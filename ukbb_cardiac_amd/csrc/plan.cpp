@@ -558,7 +558,7 @@ int plan_conv(Planner &p, const std::string &lname, int in0, int in1, int c1, in
     return UKBB_OK;
 }
 
-// conv2d_transpose 3x3 s2 + BN + ReLU as a 2x2 sub-pixel conv (kernels.h, tconv_as_conv2x2)
+// conv2d_transpose 3x3 s2 + BN + ReLU as a 2x2 sub-pixel conv (pack.h, tconv_as_conv2x2)
 int plan_tconv(Planner &p, const std::string &lname, int in0, int H, int W, int *out_buf) {
     const int li = p.layer(lname);
     const Spec &L = p.specs[li];
