@@ -126,7 +126,8 @@ def test_claim_files_are_exclusive_and_stale_ones_are_swept(tmp_path, monkeypatc
     d = str(tmp_path)
     assert shard.try_claim(d, 'seg_sa') and not shard.try_claim(d, 'seg_sa')          # O_EXCL: one winner (our own live claim is not stale)
     assert shard.try_claim(d, 'seg_la_2ch')                                            # another sequence of the same subject is another claim
-    assert open(shard.claim_path(d, 'seg_sa')).read().split() == [nifti._host_tag(), str(os.getpid())]
+    stat = open('/proc/self/stat').read()                                              # host tag, pid, start time of the pid (field 22)
+    assert open(shard.claim_path(d, 'seg_sa')).read().split() == [nifti._host_tag(), str(os.getpid()), stat[stat.rindex(')') + 2:].split()[19]]
     shard.release_claim(d, 'seg_sa')
     shard.release_claim(d, 'seg_sa')                                                   # idempotent
     assert shard.try_claim(d, 'seg_sa')

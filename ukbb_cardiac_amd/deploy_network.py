@@ -35,7 +35,8 @@ from ukbb_cardiac_amd.label_tables import LabelTables              # noqa: E402
 # how it routes a subject
 from ukbb_cardiac_amd.sequence_run import (SequenceRun, device_label_gzip_mode, device_path, pipelined_on_device, seg_prefix,   # noqa: E402,F401
                                             sequence_on_device)
-from ukbb_cardiac_amd.shard import ClaimQueue, apply_cpu_set_from_env, default_device, shard_from_env   # noqa: E402
+from ukbb_cardiac_amd.shard import (ClaimQueue, apply_cpu_set_from_env, claim_path, default_device, io_threads_from_env,   # noqa: E402
+                                    shard_from_env)
 
 
 def define_flags():
@@ -56,7 +57,7 @@ def define_flags():
                       '(float32, uint8, int16 and uint16 sequences; results identical to the host path).')
     fs.DEFINE_boolean('numpy1_casting', False, 'Rescale intensities with the float32 arithmetic numpy 1.x used when the reference '
                       'was written (1 ulp from numpy 2; host pre-processing only; INTEGRATION.md section 5).')
-    fs.DEFINE_integer('io_threads', int(os.environ.get('UKBB_IO_THREADS', 8)), 'Reader threads (gzip NIfTI -> pinned staging) and writer threads (float64 label volume, gzip) '
+    fs.DEFINE_integer('io_threads', io_threads_from_env(8), 'Reader threads (gzip NIfTI -> pinned staging) and writer threads (float64 label volume, gzip) '
                       'around the GPU in sequence mode; 0 = strictly sequential subjects as in the reference.')
     fs.DEFINE_integer('device_inflate', 0, 'Sequence mode with --device_preproc: inflate the gzip NIfTI inputs on the GPU, up to this many subjects per '
                       'launch (one wave per file; the readers only read).  0 = off: the reader threads inflate.  A file the device path declines '
@@ -111,7 +112,8 @@ def define_flags():
     fs.DEFINE_integer('shard_index', env_idx, 'This worker: subjects i with i % num_shards == shard_index.')
     fs.DEFINE_boolean('work_stealing', True, 'With num_shards > 1: after its own share a worker takes subjects of the other shards that '
                       'nobody has claimed yet (claim file <subject>/.claim.<seg>_<seq>, created with O_EXCL; claims of dead workers are swept). '
-                      '--nowork_stealing = the strict i % num_shards split.')
+                      'Sequence mode with --save_seg only: the saved label file is what marks a subject done, so a run that saves none '
+                      '(--nosave_seg, tables only) keeps the strict split and says so.  --nowork_stealing = the strict i % num_shards split.')
     return fs
 
 
@@ -131,9 +133,13 @@ def run(FLAGS, forward, log=print, engine=None):
     (sequence_run.py): with ``engine`` and --device_preproc, float32 and integer sequences take one of its device loops."""
     start_time = time.time()
     seq, pre = FLAGS.seq_name, seg_prefix(FLAGS)
-    # the static split (subject i -> shard i mod num_shards) and, on top of it, claim-file work stealing in sequence mode
-    queue = ClaimQueue(FLAGS.data_dir, sorted(os.listdir(FLAGS.data_dir)), FLAGS.shard_index, FLAGS.num_shards, '%s_%s' % (pre, seq),
-                       stealing=bool(getattr(FLAGS, 'work_stealing', False)) and FLAGS.process_seq)
+    # the static split (subject i -> shard i mod num_shards) and, on top of it, claim-file work stealing in sequence mode -- with
+    # --save_seg only: a claim says "someone is on it" and is gone when the subject is finished; what then says "done" is the label
+    # file.  Without one a finished subject would look open again to every other worker
+    stealing = bool(getattr(FLAGS, 'work_stealing', False)) and FLAGS.process_seq and FLAGS.save_seg
+    if FLAGS.num_shards > 1 and getattr(FLAGS, 'work_stealing', False) and FLAGS.process_seq and not stealing:
+        log('--work_stealing off, the static split i % num_shards instead: no label file is saved (--save_seg off) to mark a subject done')
+    queue = ClaimQueue(FLAGS.data_dir, sorted(os.listdir(FLAGS.data_dir)), FLAGS.shard_index, FLAGS.num_shards, '%s_%s' % (pre, seq), stealing=stealing)
     data_list = list(queue)
     processed, table_time = [], []
     tables = LabelTables(FLAGS, engine)                 # --output_csv, --qc_csv, --atrial_csv, --score_csv, --confidence_csv: flag checks first
@@ -185,6 +191,9 @@ def run(FLAGS, forward, log=print, engine=None):
             processed, table_time = seq_run.run(seq_run.pipelined)
         else:
             processed, table_time = seq_run.run(seq_run.sequential, forward)
+        busy = [data for data in queue.still_busy() if not os.path.exists('{0}/{1}/{2}_{3}.nii.gz'.format(FLAGS.data_dir, data, pre, seq))]
+        if busy:                                        # never silently: a claim that no rule sweeps would hide its subject on every rerun
+            log('Left to the worker whose claim ({0}) they carry, not segmented here: {1}'.format(os.path.basename(claim_path('', queue.what)), ' '.join(busy)))
     else:
         for data in data_list:
             one_subject(data)

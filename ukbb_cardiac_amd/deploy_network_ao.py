@@ -24,7 +24,7 @@ if __package__ in (None, ''):
 from ukbb_cardiac_amd import nifti, pipeline                      # noqa: E402
 from ukbb_cardiac_amd.flags import FlagError, FlagSet              # noqa: E402
 from ukbb_cardiac_amd.label_tables import AorticTable             # noqa: E402
-from ukbb_cardiac_amd.shard import default_device, shard_from_env, subjects_for_shard   # noqa: E402
+from ukbb_cardiac_amd.shard import default_device, io_threads_from_env, shard_from_env, subjects_for_shard  # noqa: E402
 
 
 def define_flags():
@@ -45,7 +45,7 @@ def define_flags():
     fs.DEFINE_integer('device', default_device(), 'HIP device ordinal (after HIP_VISIBLE_DEVICES); defaults to '
                       'LOCAL_RANK under torch.distributed.run.')
     fs.DEFINE_integer('batch_slices', 64, 'Slices per forward call.')
-    fs.DEFINE_integer('io_threads', min(2, int(os.environ.get('UKBB_IO_THREADS', 2))), 'Sequence mode: threads that read (inflate) the next cines ahead of the GPU and threads that '
+    fs.DEFINE_integer('io_threads', min(2, io_threads_from_env(2)), 'Sequence mode: threads that read (inflate) the next cines ahead of the GPU and threads that '
                       'write finished segmentations behind it; 0 = strictly sequential subjects as in the reference.')
     fs.DEFINE_boolean('device_preproc', True, 'Sequences: z-score, padding, transposes and the argmax on the GPU '
                       '(float32, uint8, int16 and uint16 cines; bit-identical to the host path; --nodevice_preproc restores it).')

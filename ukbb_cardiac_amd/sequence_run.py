@@ -133,6 +133,13 @@ class SequenceRun:
                         self.log('  Directory {0} does not contain an image with file name {1}. Skip.'.format(data_dir, os.path.basename(image_name)))
                     continue
                 if self.queue.take(data):               # else another worker is on it: its name appears where it is segmented
+                    # its owner may have written the label file and released the claim between the look above and the take:
+                    # what is done is decided while the claim is held
+                    if os.path.exists('{0}/{1}_{2}.nii.gz'.format(data_dir, self.pre, self.seq)):
+                        self.queue.done(data)
+                        if first:
+                            self.log(data)
+                        continue
                     yield (data, data_dir, image_name)
         yield from candidates(self.data_list, True)
         yield from candidates(self.queue.second_chance(), False)

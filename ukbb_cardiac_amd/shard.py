@@ -35,73 +35,172 @@ def shard_from_env(default_index=0, default_count=1):
     return (int(idx) if idx is not None else default_index, int(cnt) if cnt is not None else default_count)
 
 
+def io_threads_from_env(default: int) -> int:
+    """UKBB_IO_THREADS (``launch`` sets it for every worker) as the default of --io_threads of both deploy scripts: a positive
+    integer, else ``default`` -- an empty or malformed value must not stop a script while it defines its flags."""
+    try:
+        n = int(os.environ.get('UKBB_IO_THREADS', default))
+    except ValueError:
+        return default
+    return n if n > 0 else default
+
+
 # ---- work stealing on top of the static split: claim files ---------------------------------------------------------
 # Static i mod G leaves the worker that drew the large subjects (or the slow disk, or a GPU shared with someone else) finishing
 # last while the others idle.  With --work_stealing every worker walks the WHOLE sorted list -- its own share first, in order,
 # then the other shares from their tails -- and takes a subject only after creating ``<subject>/.claim.<pre>_<seq>`` with
 # O_CREAT | O_EXCL (atomic on local and NFSv3+ file systems): exactly one worker wins.  The reference's skip-if-output-exists
-# (common/deploy_network.py:62-67) still decides what is done; the claim only says "someone is on it".  A claim whose writer is
-# gone (worker killed mid-subject) is swept like nifti.py's tmp files: same host + pid namespace and the pid is dead -> removed at
-# once; another host -> removed after CLAIM_MAX_AGE_S.  No claim is ever waited for.
+# (common/deploy_network.py:62-67) still decides what is done; the claim only says "someone is on it", which is why stealing
+# needs --save_seg (deploy_network.run).  A claim names its writer: host tag, pid and the start time of that pid.  A claim whose
+# writer is gone (worker killed mid-subject) is swept like nifti.py's tmp files: same host + pid namespace and the pid is dead,
+# or alive with another start time (the pid was reused) -> at once; another host -> after CLAIM_MAX_AGE_S.
+# Remove-then-create is NOT a safe take-over: of two sweepers that both judged the old claim, the slower one removes the faster
+# one's fresh claim and both own the subject.  Moving the claim aside with os.rename, looking at what was moved and putting it
+# back if it is not the claim that was judged fails the same way once a third worker comes by: while the fresh claim is aside, its
+# plain O_EXCL create succeeds.  So a sweep happens behind a second O_EXCL file, ``<claim>.sweep``: only its
+# holder removes a claim, and only after judging it again while it holds the file (the claim it judged before may have been
+# replaced since).  Whoever finds the sweep file taken leaves the subject alone.  A sweep file whose writer is gone is judged like
+# a claim and removed, and the subject is left for the next visit (ClaimQueue.second_chance, or another worker): taking it over
+# in the same call would be remove-then-create once more.  That leaves one collision, which needs two crashes on one subject
+# (a claim and a sweep file, both abandoned) and four workers at it within the same few system calls.  No claim is ever waited for.
+# tests/test_shard_claims.py runs every interleaving of two sweepers, and seeded ones of three workers, against this protocol and
+# against the remove-then-create it replaces.
 
 CLAIM_MAX_AGE_S = 6 * 3600.0
+EMPTY_CLAIM_MAX_AGE_S = 60.0
 
 
 def claim_path(subject_dir: str, what: str) -> str:
     return os.path.join(subject_dir, '.claim.' + what)
 
 
-def _claim_is_stale(path: str) -> bool:
+# Every file-system and process call of the protocol goes through one of these, so that a test can hold each of them back and
+# let the calls of several workers through in an order of its choosing.
+def _create_excl(path: str, text: str) -> None:
+    """Create ``path`` holding ``text``; FileExistsError if it is there already."""
+    fd = os.open(path, os.O_CREAT | os.O_EXCL | os.O_WRONLY, 0o644)
+    with os.fdopen(fd, 'w') as f:
+        f.write(text)
+
+
+def _read_text(path: str) -> str:
+    with open(path) as f:
+        return f.read()
+
+
+def _mtime(path: str) -> float:
+    return os.path.getmtime(path)
+
+
+def _remove(path: str) -> None:
+    os.remove(path)
+
+
+def _now() -> float:
     import time
+    return time.time()
+
+
+def _own_pid() -> int:
+    return os.getpid()
+
+
+def _pid_alive(pid: int) -> bool:
+    try:
+        os.kill(pid, 0)
+        return True
+    except ProcessLookupError:
+        return False
+    except OSError:
+        return True                                         # exists but is not ours to signal
+
+
+def _pid_start(pid: int):
+    """Start time of ``pid`` (field 22 of /proc/<pid>/stat, clock ticks since boot) as text, or None where it cannot be read."""
+    try:
+        stat = _read_text('/proc/%d/stat' % pid)
+        return stat[stat.rindex(')') + 2:].split()[19]      # the fields behind "(comm)" start at field 3
+    except (OSError, ValueError, IndexError):
+        return None
+
+
+def _claim_text() -> str:
+    """What this process writes into a claim: host tag, pid, start time of the pid ('-' where /proc does not tell)."""
+    from .nifti import _host_tag
+    pid = _own_pid()
+    return '%s %d %s\n' % (_host_tag(), pid, _pid_start(pid) or '-')
+
+
+def _claim_is_stale(path: str) -> bool:
     from .nifti import _host_tag
     try:
-        with open(path) as f:
-            parts = f.read().split()
-        age = time.time() - os.path.getmtime(path)
+        parts = _read_text(path).split()
+        age = _now() - _mtime(path)
     except OSError:
         return False                                        # vanished (its owner finished) or unreadable: not ours to judge
     if len(parts) < 2 or not parts[1].isdigit():
-        return age > 60.0                                   # a claim is written in one go; an empty one this old lost its writer
+        return age > EMPTY_CLAIM_MAX_AGE_S                  # a claim is written in one go; an empty one this old lost its writer
     tag, pid = parts[0], int(parts[1])
     if tag != _host_tag():
         return age > CLAIM_MAX_AGE_S
-    if pid == os.getpid():
-        return False
-    try:
-        os.kill(pid, 0)
-        return False
-    except ProcessLookupError:
+    # the claim of another process that had this pid: the start time tells them apart.  A claim without one (two fields, written
+    # by an earlier version, or '-') is judged by the pid alone
+    started = parts[2] if len(parts) > 2 and parts[2] != '-' else None
+    if not _pid_alive(pid):
         return True
-    except OSError:
-        return False                                        # exists but is not ours to signal
+    if started is not None:
+        now = _pid_start(pid)
+        if now is not None and now != started:
+            return True
+    return False
 
 
 def try_claim(subject_dir: str, what: str) -> bool:
     """Atomically take ``what`` (e.g. 'seg_sa') of a subject.  True: this process owns it until ``release_claim``."""
-    from .nifti import _host_tag
-    path = claim_path(subject_dir, what)
-    for attempt in range(2):
-        try:
-            fd = os.open(path, os.O_CREAT | os.O_EXCL | os.O_WRONLY, 0o644)
-        except FileExistsError:
-            if attempt == 0 and _claim_is_stale(path):
-                try:
-                    os.remove(path)                         # several sweepers may race here: one remove wins, O_EXCL arbitrates the re-claim
-                except OSError:
-                    pass
-                continue
-            return False
-        except OSError:
-            return False                                    # read-only / vanished directory: leave the subject to whoever can write there
-        with os.fdopen(fd, 'w') as f:
-            f.write('%s %d\n' % (_host_tag(), os.getpid()))
+    path, text = claim_path(subject_dir, what), _claim_text()
+    try:
+        _create_excl(path, text)
         return True
-    return False
+    except FileExistsError:
+        pass
+    except OSError:
+        return False                                        # read-only / vanished directory: leave the subject to whoever can write there
+    if not _claim_is_stale(path):
+        return False
+    sweep = path + '.sweep'
+    try:
+        _create_excl(sweep, text)
+    except FileExistsError:
+        if _claim_is_stale(sweep):                          # its writer died inside the few calls below
+            try:
+                _remove(sweep)
+            except OSError:
+                pass
+        return False
+    except OSError:
+        return False
+    try:
+        if not _claim_is_stale(path):                       # swept and taken by someone else since the first look
+            return False
+        try:
+            _remove(path)
+        except OSError:
+            pass
+        try:
+            _create_excl(path, text)                        # a worker that came by between the two calls may have won: it owns the subject
+            return True
+        except OSError:
+            return False
+    finally:
+        try:
+            _remove(sweep)
+        except OSError:
+            pass
 
 
 def release_claim(subject_dir: str, what: str) -> None:
     try:
-        os.remove(claim_path(subject_dir, what))
+        _remove(claim_path(subject_dir, what))
     except OSError:
         pass
 
@@ -129,6 +228,7 @@ class ClaimQueue:
         self.order = stealing_order(subjects, shard_index, num_shards) if self.stealing else list(self.static)
         self.held, self.busy_elsewhere, self.stolen = set(), [], []
         self._static_set = set(self.static)
+        self._second_pass = False
 
     def __iter__(self):
         return iter(self.order)
@@ -151,7 +251,13 @@ class ClaimQueue:
 
     def second_chance(self):
         again, self.busy_elsewhere = self.busy_elsewhere, []
+        self._second_pass = True
         return again
+
+    def still_busy(self):
+        """Subjects that another worker's claim kept from this one on the second visit too: neither done nor taken here.  Their
+        owner is at work on them, or the claim is one that no rule sweeps yet (another host's, younger than CLAIM_MAX_AGE_S)."""
+        return list(self.busy_elsewhere) if self._second_pass else []
 
     def release_all(self):
         for name in list(self.held):
